@@ -24,13 +24,24 @@ processes under `python -m torch.distributed.run` (127.0.0.1 rendezvous, a free 
 imported torch or touched the GPU; rank 0's JSON line is relayed and the exit status is the children's.  The N > 1
 line carries `rccl`: the world RCCL saw, every rank's device, the bytes and the time of the one all-gather.
 
-At N = 1 the line also carries `other_configs` -- ONE event-timed pass each of BASELINE configs[2] (Twothick x 65 536
+A plain run does only what the headline needs: it sets the inputs up, runs --warmup untimed and --steps timed steps,
+writes the last timed step's outputs if --dump-outputs DIR is given, and prints the line.  `--dump-outputs DIR` writes
+what a caller of the timed path receives from its last step as DIR/<name>.npy (float64, status as float32): P, the
+per-sample log-likelihoods (the gathered vector for N > 1), and at N = 1 also sse, status and iters_total per curve x
+sample; the inputs are seeded, so two runs with the same arguments are compared output for output.  Above 64 MB the
+files hold the same fixed, seeded subset of samples, whose indices are in sample_index.npy.
+
+`--full` adds every further measurement and check described below (CPU baselines, other configurations and precisions,
+rooflines with runs of their own, the full-length pass, the reference-API block, the production-shape entry, the
+library record and the quoted profile traffic); the --no-* switches leave out single legs of it.
+
+With --full, at N = 1 the line also carries `other_configs` -- ONE event-timed pass each of BASELINE configs[2] (Twothick x 65 536
 samples x 6 curves) and of one GPU's share of configs[4] (L = 512 x 32 768 of 262 144 samples: fp64 at tol 1e-7 and 1e-6, and the config
 as worded -- fp32 state, labelled "screening", with its PL error against fp64) -- `roofline_hbm_pcr_L512` -- U1 on configs[4]'s 512-node
 rows, fp32 and fp64 -- `library` -- which libtrpl_hip.so was measured (source hash; `roofline.traffic_source_stale` says whether the quoted
 PMC profile is of that library) -- `host_api_block` -- the reference's own call sequence (pvSim -> fastlog -> prob per
 curve, host buffers) on one reference-shaped 1024-sample block, PCIe included -- and `full_length`: ONE extra pass at the production length T = 80 000 over the
-same resident batch (event-timed, ~26 s), so that the full-length rate is measured by every driver run.
+same resident batch (event-timed, ~26 s), so that every --full run measures the full-length rate.
 
 `--single-process --gpus N` runs the same step with ONE process driving all N devices through
 trpl_loglik_multi_dev (RCCL ncclCommInitAll + one ncclAllGather; P left resident on every device).
@@ -40,16 +51,18 @@ that --gpus need not divide), `--backend gloo` (ranks share the GPU, host-staged
 code path over real RCCL on a one-rank communicator), `--single-process --rehearse-on-device0` (N ranks of one process on device 0
 against a stand-in collective library).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step = wall milliseconds of one timed
+step, ...) with one extra object, and with --full two more:
   roofline      the dominant kernel (the fused time-stepper): achieved fp64 FLOP/s from the
                 device's own iteration counters (268*L flop per inner iteration)
-                over the kernel's average duration measured with events on its stream, against
-                the fp64 vector peak.  It is VALU-bound by construction (state lives in
-                registers), so `bound` is "valu-fp64"; `roofline_hbm_pcr` is the HBM roofline of
+                over the kernel's average duration measured with events on its stream (the timed
+                steps themselves), against the fp64 vector peak.  It is VALU-bound by construction
+                (state lives in registers), so `bound` is "valu-fp64".
+  roofline_hbm_pcr  (--full) the HBM roofline of
                 the stand-alone batched PCR solve (U1, 5*L*8 B per system), the kernel the
                 north-star's ">= 40 % of HBM roofline" target names; its launches rotate over four
                 distinct operand sets (1.34 GB, 5x the Infinity Cache) so the rate is an HBM rate.
-  cpu_baseline  the CPU oracle (the reference's algorithm restated in C, bit-identical to it)
+  cpu_baseline  (--full) the CPU oracle (the reference's algorithm restated in C, bit-identical to it)
                 timed on this host's cores on a bounded sample of the same workload.
 """
 import argparse
@@ -136,7 +149,15 @@ def main():
                          "with host-staged collectives (ranks may share a GPU)")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the one pass each of configs[2] (Twothick) and configs[4]'s share (L = 512) (N = 1 only, ~22 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline (CPU baselines, other configs, PCR "
+                         "rooflines, full-length pass, host-API block, production-shape entry, library record, profile "
+                         "traffic); the --no-* switches leave out single legs of it.  Off: the plain run times --steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's outputs as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.single_process:
         return main_single_process(args)
@@ -150,10 +171,10 @@ def main():
     import trpl_amd
     from trpl_amd import workloads as wl
 
-    # CPU baselines first: they fork worker processes, which must happen before this process
+    # CPU baselines first (--full): they fork worker processes, which must happen before this process
     # initialises the GPU.  Rank 0 at N = 1 only; bounded samples of the same workload.
     cpu_legs = {}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         ini_c, lens_c = wl.power_scan(args.L) if args.workload == "power_scan" else wl.twothick(args.L)
         cpu_legs["cpu_baseline"] = cpu_baseline(wl, trpl_amd, ini_c, lens_c, args.T * 0.025, args.L, args.T, args.cpu_seconds)
         cpu_legs["cpu_baseline_scipy"] = cpu_baseline_scipy(wl, ini_c, lens_c, args.T * 0.025, args.L, args.T)
@@ -255,6 +276,11 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if rank == 0 and args.dump_outputs:                       # what the last timed step handed its caller
+        outputs = {"P": full[0]}
+        if not multi:
+            outputs.update(sse=sse, status=status, iters_total=iters)
+        dump_outputs(args.dump_outputs, outputs)
 
     # ---- bookkeeping from the device's own counters ----
     n_fail = int((status != 0).sum().item())
@@ -343,28 +369,30 @@ def main():
                                                for k in range(n_tab)])
     if multi:
         out["rccl"] = rccl_record(torch, dist, trpl_amd, args, rank, world, local_rank, dev, cdev, S_total, ev_ag)
-    if rank == 0 and world == 1 and not args.no_other_configs and args.workload == "power_scan" and L == 128 \
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs and args.workload == "power_scan" and L == 128 \
             and not (args.fp32 or args.mixed or args.strict):
         out["other_configs"] = other_configs(torch, tdev, trpl_amd, wl, dev, args.samples_per_gpu, T, dt_ns)
-    if rank == 0 and not args.no_pcr:
+    if args.full and rank == 0 and not args.no_pcr:
         out["roofline_hbm_pcr"] = bench_pcr(torch, tdev, dev, flags & trpl_amd.FLAG_STRICT, L=L,
                                             dtype=torch.float32 if args.fp32 else torch.float64)
-    if rank == 0 and world == 1 and not args.no_pcr and not args.no_other_configs and L == 128 and not (args.fp32 or args.strict):
+    if args.full and rank == 0 and world == 1 and not args.no_pcr and not args.no_other_configs and L == 128 \
+            and not (args.fp32 or args.strict):
         # U1 at configs[4]'s grid ("LDS-pressure / bandwidth stress"): rows of 2 KB (fp32, the config's dtype) and 4 KB (fp64) -- a
         # lane holds 8 adjacent rows, loaded in node order and transposed through LDS (pcr_batched_impl.hpp)
         torch.cuda.empty_cache()
         out["roofline_hbm_pcr_L512"] = [dict(config="configs[4] grid, %s" % name, **bench_pcr(torch, tdev, dev, 0, L=512, dtype=dt))
                                         for name, dt in (("fp32", torch.float32), ("fp64", torch.float64))]
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_full_length and args.full_length_T != T:
+    if args.full and rank == 0 and world == 1 and not args.no_full_length and args.full_length_T != T:
         out["full_length"] = full_length_pass(torch, tdev, trpl_amd, dev, X, ini_d, mark, lens, L, args.full_length_T, dt_ns,
                                               flags, tol, C, args.fp32)
-    if rank == 0 and world == 1 and not args.no_host_api and L == 128 and not (args.fp32 or args.mixed or args.strict):
+    if args.full and rank == 0 and world == 1 and not args.no_host_api and L == 128 \
+            and not (args.fp32 or args.mixed or args.strict):
         out["host_api_block"] = host_api_block(trpl_amd, wl, ini, lens, L, T, dt_ns)
-    if rank == 0 and world == 1 and not args.no_e2e and args.workload == "power_scan" and L == 128 \
+    if args.full and rank == 0 and world == 1 and not args.no_e2e and args.workload == "power_scan" and L == 128 \
             and not (args.fp32 or args.mixed or args.strict):
         out["e2e_production"] = e2e_production(trpl_amd)
-    if rank == 0:
+    if args.full and rank == 0:
         out["library"] = library_record(trpl_amd)
         attach_traffic(out, args.traffic_profile)
     out.update(cpu_legs)
@@ -439,6 +467,10 @@ def main_single_process(args):
     assert np.isfinite(full).sum() >= S_total - fail_all
     if args.dump_p:
         np.save(args.dump_p, full[None, :])
+    if args.dump_outputs:                                      # the shards are contiguous: concatenated, they are the batch's
+        dump_outputs(args.dump_outputs, {"P": full, "sse": torch.cat([t.cpu() for t in sses], dim=1),
+                                         "status": torch.cat([t.cpu() for t in sts], dim=1),
+                                         "iters_total": torch.cat([t.cpu() for t in its], dim=1)})
     sys_steps = S_total * C * (T + 1)
     value = sys_steps * args.steps / elapsed
     tf = it_all * FLOP_PER_ITER_PER_NODE * L / (elapsed / args.steps) / 1e12
@@ -475,6 +507,30 @@ def main_single_process(args):
                         "note": "wall-clock over the whole step (solve + all-gather + unpadding) on all devices"}}
     md.close()
     print(json.dumps(out), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+NPY_HEADER_BYTES = 128
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: each array as <path>/<name>.npy -- float64, or float32 where that is exact (int32 status).  The last
+    axis of every array is the sample axis; if the files would exceed DUMP_LIMIT_BYTES they hold the same fixed, seeded
+    subset of samples (sorted), and sample_index.npy says which."""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        host[name] = a.astype(np.float32 if a.dtype in (np.int32, np.float32) else np.float64)
+    S = next(iter(host.values())).shape[-1]
+    per_sample = sum(a.nbytes // S for a in host.values())
+    if per_sample * S + NPY_HEADER_BYTES * len(host) > DUMP_LIMIT_BYTES:
+        room = DUMP_LIMIT_BYTES - NPY_HEADER_BYTES * (len(host) + 1)
+        keep = np.sort(np.random.default_rng(seed).choice(S, room // (per_sample + 8), replace=False))
+        host = {name: np.ascontiguousarray(a[..., keep]) for name, a in host.items()}
+        host["sample_index"] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def rccl_record(torch, dist, trpl_amd, args, rank, world, local_rank, dev, cdev, S_total, ev_ag):
@@ -910,14 +966,17 @@ def cpu_baseline_scipy(wl, ini, lens, Time, L, T):
 def cpu_reference_recorded():
     """What the REFERENCE'S OWN CPU path measured for BASELINE.json configs[0] (Power_scan x 64 samples through
     bayeslib.bayes(pvSim_fallback.pvSim_cpu_fallback), has_GPU False, 8 SLURM-style array tasks) where the reference can run --
-    the development container -- as recorded in tests/golden/fallback64.npz by oracle/gen_golden.py case_fallback64.  A recorded
+    the machine that generated the fixtures -- as recorded in tests/golden/fallback64{,_full}.npz by oracle/gen_golden.py
+    case_fallback64.  A recorded
     figure of another machine, NOT timed in this run (the reference never travels to the GPU box); `cpu_baseline_scipy` is its
     pinned port timed here."""
     path = os.path.join(ROOT, "tests", "golden", "fallback64.npz")
-    if not os.path.isfile(path):
+    path_full = os.path.join(ROOT, "tests", "golden", "fallback64_full.npz")     # the full window's arrays
+    if not (os.path.isfile(path) and os.path.isfile(path_full)):
         return None
-    g = np.load(path)
-    out = {"kind": "reference", "measured": "development container, recorded in tests/golden/fallback64.npz", "cores": int(g["ntasks"]),
+    g = dict(np.load(path))
+    g.update(np.load(path_full))
+    out = {"kind": "reference", "measured": "where the fixtures were generated, recorded in tests/golden/fallback64{,_full}.npz", "cores": int(g["ntasks"]),
            "cpu_model": str(g["cpu_model"]), "samples": 64, "curves": 3, "unit": "system-timesteps/s"}
     for tag, name in (("w8k", "bench_window"), ("full", "full_window")):
         T, wall = int(g[tag + "_T"]), float(g[tag + "_wall"])

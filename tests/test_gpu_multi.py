@@ -240,6 +240,31 @@ REHEARSAL = ["--steps", "1", "--warmup", "1", "--T", "200", "--no-cpu-baseline",
              "--no-other-configs", "--no-e2e"]
 
 
+def test_plain_bench_line_and_reproducible_dumped_outputs(gpu, tmp_path):
+    """A plain run (no --full) is the headline alone: --steps timed steps, ms_per_step, none of --full's legs.  Its
+    --dump-outputs files are what the last timed step handed its caller -- P (the vector --dump-p saves), sse / status /
+    iters_total per curve x sample -- and two runs with the same arguments write identical files (seeded inputs)."""
+    env = {k: v for k, v in dict(os.environ, TRPL_AUTOBUILD="0").items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    args = ["--gpus", "1", "--samples-total", "4099", "--steps", "2", "--warmup", "1", "--T", "200"]
+    d1, d2, p1 = tmp_path / "d1", tmp_path / "d2", str(tmp_path / "p1.npy")
+    lines = [_bench(args + ["--dump-outputs", str(d1), "--dump-p", p1], env), _bench(args + ["--dump-outputs", str(d2)], env)]
+    for line in lines:
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "system-timesteps/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert not {"cpu_baseline", "cpu_baseline_scipy", "other_configs", "roofline_hbm_pcr", "roofline_hbm_pcr_L512",
+                    "full_length", "host_api_block", "e2e_production", "library"} & set(line)
+    names = sorted(os.listdir(d1))
+    assert names == sorted(os.listdir(d2)) == ["P.npy", "iters_total.npy", "sse.npy", "status.npy"]
+    for name in names:
+        a, b = np.load(d1 / name), np.load(d2 / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    P = np.load(d1 / "P.npy")
+    assert P.shape == (4099,) and np.array_equal(P, np.load(p1)[0]) and np.isfinite(P).all()
+    assert np.load(d1 / "sse.npy").shape == np.load(d1 / "status.npy").shape == (3, 4099)
+    assert not np.load(d1 / "status.npy").any() and (np.load(d1 / "iters_total.npy") > 0).all()
+
+
 @pytest.mark.parametrize("S_total", [4098, 4099])
 def test_bench_three_rank_rehearsal_with_even_and_uneven_shards(gpu, tmp_path, S_total):
     """The driver's N > 1 form of bench.py with more than two ranks on this box's one GPU: `bench.py --gpus 3 --backend gloo`
@@ -253,8 +278,9 @@ def test_bench_three_rank_rehearsal_with_even_and_uneven_shards(gpu, tmp_path, S
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     W = 3
     p1, pw = str(tmp_path / "p1.npy"), str(tmp_path / "pw.npy")
-    one = _bench(["--gpus", "1", "--samples-total", str(S_total), "--dump-p", p1] + REHEARSAL, env)
-    many = _bench(["--gpus", str(W), "--backend", "gloo", "--samples-total", str(S_total), "--dump-p", pw] + REHEARSAL, env)
+    # --full: the `library` record compared below is not part of a plain run (with REHEARSAL's --no-* switches it adds nothing else)
+    one = _bench(["--gpus", "1", "--samples-total", str(S_total), "--dump-p", p1, "--full"] + REHEARSAL, env)
+    many = _bench(["--gpus", str(W), "--backend", "gloo", "--samples-total", str(S_total), "--dump-p", pw, "--full"] + REHEARSAL, env)
     assert many["n_gpus"] == W and many["scaling"] == "weak" and many["config"]["samples_total"] == S_total
     assert many["config"]["collective"].startswith("gloo") and many["nonconverged_systems"] == one["nonconverged_systems"] == 0
     rc = many["rccl"]

@@ -335,3 +335,37 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did():
     assert r.stderr.count("bench.py needs a GPU") >= 2, r.stderr[-3000:]          # both ranks got as far as the device check
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]            # and no line was invented
     assert time.time() - t0 < 120
+
+
+def test_bench_dump_outputs_is_bounded_and_seeded(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 files, at most 64 MB in all; above that, every file holds the same fixed,
+    seeded subset of samples (sample_index.npy), the same in every run.  --steps below 1 is refused before any work."""
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    import bench
+    S = 2_000_000
+    rng = np.random.default_rng(1)
+    arrays = {"P": rng.standard_normal(S), "sse": rng.random((3, S)), "status": rng.integers(0, 9, (3, S), dtype=np.int32),
+              "iters_total": rng.integers(1, 10 ** 6, (3, S), dtype=np.int64)}
+    small = {k: v[..., :1000] for k, v in arrays.items()}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert sorted(os.listdir(tmp_path / "small")) == ["P.npy", "iters_total.npy", "sse.npy", "status.npy"]
+    for k, v in small.items():
+        got = np.load(tmp_path / "small" / (k + ".npy"))
+        assert got.dtype == (np.float32 if v.dtype == np.int32 else np.float64) and np.array_equal(got, v)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["P.npy", "iters_total.npy", "sample_index.npy", "sse.npy", "status.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10 ** 6
+    idx = np.load(tmp_path / "a" / "sample_index.npy").astype(np.int64)
+    assert len(idx) > S // 4 and (np.diff(idx) > 0).all()
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    for k, v in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "a" / (k + ".npy")), v[..., idx]), k
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -301,16 +301,17 @@ def test_scipy_port_matches_the_reference_cpu_path_on_configs0(golden):
     assert np.max(np.abs(pl[:, :2, :401] / g["w8k_pl_head"] - 1)) < 1e-12
     P = sum(scipy_mol.cpu_branch_loglik(pl[c], g["w8k_obs_%d" % c], Time, T) for c in range(3))
     assert np.max(np.abs(P / g["w8k_P"][0] - 1)) < 1e-12
-    # the reference's full window (T = 80 000, 2000 ns): four of the 192 curves
-    T, Time, dec = int(g["full_T"]), float(g["full_time"]), int(g["full_dec"])
+    # the reference's full window (T = 80 000, 2000 ns; its full_* arrays are stored in fallback64_full.npz): four of the 192 curves
+    gf = golden("fallback64_full")
+    T, Time, dec = int(gf["full_T"]), float(gf["full_time"]), int(gf["full_dec"])
     plf = scipy_mol.pl_batch(X[:2], ini[[0, 2]], [length] * 2, Time, L, T, min(procs, 4))
-    reff = g["full_pl32"][[0, 2]][:, :2].astype(np.float64)
+    reff = gf["full_pl32"][[0, 2]][:, :2].astype(np.float64)
     live = np.abs(reff) > 1e-30                                    # (a fully decayed tail is stored as float32 zeros / denormals)
     assert live.mean() > 0.5 and np.max(np.abs(plf[:, :, ::dec] / reff - 1)[live]) < 2e-7
-    assert np.max(np.abs(plf[:, :, :401] / g["full_pl_head"][[0, 2]] - 1)) < 1e-12
+    assert np.max(np.abs(plf[:, :, :401] / gf["full_pl_head"][[0, 2]] - 1)) < 1e-12
     # what the fixture says about the reference's own speed (the figures DESIGN.md quotes)
     assert int(g["ntasks"]) == 8 and g["w8k_model_seconds"].shape == (3, 8)
-    assert 5 < float(g["w8k_wall"]) < 600 and 20 < float(g["full_wall"]) < 3600
+    assert 5 < float(g["w8k_wall"]) < 600 and 20 < float(gf["full_wall"]) < 3600
 
 
 def test_posterior_core_restatement_matches_the_reference(golden):

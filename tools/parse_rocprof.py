@@ -69,7 +69,7 @@ for k, d in traffic.items():
 # ... and WHICH library: bench.py's attach_traffic flags the quotation as stale when the loaded library's hash differs
 out["_meta"] = {"tag": tag, "T": bench["config"].get("T"), "workload": bench["config"].get("workload"),
                 "srchash": (bench.get("library") or {}).get("srchash"),
-                "command": "bench.py --no-cpu-baseline --no-full-length (tools/profile_round.sh)"}
+                "command": "bench.py --full --no-cpu-baseline --no-full-length --no-host-api --no-other-configs --no-e2e (tools/profile_round.sh)"}
 json.dump(out, open(os.path.join(dst, tag + "_hbm_traffic.json"), "w"), indent=1)
 print(json.dumps({k: v["hbm_bytes_per_launch"] for k, v in out.items() if k != "_meta"}, indent=1))
 print("value", bench["value"], "pcr frac", bench.get("roofline_hbm_pcr", {}).get("frac"))
