@@ -19,6 +19,7 @@ FLAG_KERNEL_PAIR, FLAG_KERNEL_SINGLE, FLAG_MIXED, FLAG_SNAP_RAW = 0x10, 0x20, 0x
 FLAG_FP32_LONG, FP32_MAX_STEPS = 0x1000, 256
 FLAG_HIST32 = 0x2000
 FLAG_PAIR_ALWAYS_SEAM, FLAG_PAIR_ADJACENT, FLAG_MULTI_FORCE_PAD = 0x20000, 0x40000, 0x80000   # tests / measurements
+FLAG_PREDICT = 0x100000    # opt-in: extrapolated start of every time step's iteration (include/trpl.h)
 MULTI_ALLOW_DUPLICATE_DEVICES = 0x1     # trpl_multi_create_ex
 
 

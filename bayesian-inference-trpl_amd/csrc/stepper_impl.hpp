@@ -23,6 +23,22 @@
 #pragma once
 #include "pcr.hpp"
 
+// TRPL_FLAG_PREDICT (include/trpl.h): a translation unit that defines TRPL_STEPPER_PREDICT=1 before including this header
+// (stepper_predict_*.hip) gets the steppers with the extrapolated start of every time step, as namespace trpl::predict
+// (its kernels are trpl::predict::stepper_kernel<...> and trpl::predict::pair::stepper_pair_kernel<...>); the helpers
+// stay in trpl.  Everywhere else the mode does not exist: PREDICT is false and its code is discarded at compile time,
+// so the default kernels are the same machine code as without it.
+#ifndef TRPL_STEPPER_PREDICT
+#define TRPL_STEPPER_PREDICT 0
+#endif
+#if TRPL_STEPPER_PREDICT
+#define TRPL_PREDICT_NS_BEGIN namespace predict {
+#define TRPL_PREDICT_NS_END }
+#else
+#define TRPL_PREDICT_NS_BEGIN
+#define TRPL_PREDICT_NS_END
+#endif
+
 namespace trpl {
 
 constexpr uint32_t kFlagPlF32 = 0x2;       // TRPL_FLAG_PL_F32
@@ -428,6 +444,16 @@ struct SnapSink {
     }
 };
 
+// TRPL_FLAG_PREDICT: the starting iterate of step t, from U^t (u0) and the older levels U^{t-1} (u1), U^{t-2} (u2) --
+// quadratic 3 u0 - 3 u1 + u2 from global step 2 on, linear 2 u0 - u1 at step 1, u0 at step 0 -- in difference form,
+// u0 + (2 (u0 - u1) - (u1 - u2)), so that the state's magnitude cancels before the change is scaled.  t is the global
+// step (a resumed launch continues the sequence) and wave-uniform; the coefficients are exact.
+__device__ __forceinline__ double predict_start(double u0, double u1, double u2, int32_t t)
+{
+    const double c1 = t >= 2 ? 2.0 : (t == 1 ? 1.0 : 0.0), c2 = t >= 2 ? 1.0 : 0.0;
+    return u0 + (c1 * (u0 - u1) - c2 * (u1 - u2));
+}
+
 // the 12 non-dimensional material parameters of one system (wave-uniform) + N0*P0
 struct MatPar {
     double N0, P0, DN, DP, rate, sr0, srL, CN, CP, tauN, tauP, Lambda, n0p0;
@@ -626,6 +652,7 @@ __device__ __forceinline__ void update_field(const MatPar &m, double a0, const d
 // differences are read from a 3-slot fp32 ring (d_m in slot m mod 3, each rounded ONCE, when it is stored).  All three
 // fields live in LDS: 20 B per node and field instead of 32 B (N, P) / 16 registers (E).  State, assembly, solves,
 // residuals and PL stay fp64.  What it buys and what it costs: DESIGN.md section 8 (round 4).
+TRPL_PREDICT_NS_BEGIN
 template <int L, bool STRICT, bool SNAP = false, bool MIXED = false, bool BUNDLE = false, bool HIST32 = false>
 __global__ void __launch_bounds__(BUNDLE ? 64 * bundle_cap(L) : 64, BUNDLE ? 1 : ((STRICT || L > 128) ? (L > 256 ? 1 : 2) : 3))
 stepper_kernel(const StepArgs a)
@@ -636,6 +663,9 @@ stepper_kernel(const StepArgs a)
     static_assert(!MIXED || LAY == 2, "the mixed-precision correction exists for the interleaved layout (L >= 128)");
     static_assert(!HIST32 || (LAY == 2 && !BUNDLE && !SNAP && !MIXED), "the fp32-difference history exists for the plain FAST one-system stepper (L >= 128), without snapshots / resume");
     static_assert(!BUNDLE || (!MIXED && (STRICT || L <= 128)), "bundles: STRICT at any L, FAST up to L = 128 (LDS: one history ring per system)");
+    // TRPL_FLAG_PREDICT: each step's iteration starts from predict_start() of the history instead of U^t
+    constexpr bool PREDICT = TRPL_STEPPER_PREDICT != 0;
+    static_assert(!PREDICT || (!MIXED && !BUNDLE && !HIST32), "the extrapolated start exists for the plain fp64 one-system stepper");
     const int wv = BUNDLE ? (int)(threadIdx.x >> 6) : 0;                 // which system of the bundle
     const int lane64 = BUNDLE ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
     const int ln = lane64 & (W - 1);               // lanes >= W replicate lane (lane mod W)
@@ -818,6 +848,11 @@ stepper_kernel(const StepArgs a)
 #pragma unroll
                 for (int m = 3; m >= 1; m--) { hN[m][j] = hN[m - 1][j]; hP[m][j] = hP[m - 1][j]; hE[m][j] = hE[m - 1][j]; }
                 hN[0][j] = Nk[j]; hP[0][j] = Pk[j]; hE[0][j] = Ek[j];
+                if constexpr (PREDICT) {           // the iteration starts from the extrapolated state (U^t is in the history)
+                    Nk[j] = predict_start(Nk[j], hN[1][j], hN[2][j], t);
+                    Pk[j] = predict_start(Pk[j], hP[1][j], hP[2][j], t);
+                    Ek[j] = predict_start(Ek[j], hE[1][j], hE[2][j], t);
+                }
             }
         } else if constexpr (HIST32) {
             const double w4 = a5, w3 = a4 + w4, w2 = a3 + w3, w1 = a2 + w2;
@@ -855,6 +890,11 @@ stepper_kernel(const StepArgs a)
 #pragma unroll
                 for (int m = 3; m >= 1; m--) hE[m][j] = hE[m - 1][j];
                 hE[0][j] = Ek[j];
+                if constexpr (PREDICT) {           // the iteration starts from the extrapolated state (U^t is in the ring)
+                    Nk[j] = predict_start(Nk[j], h1.x, h2.x, t);
+                    Pk[j] = predict_start(Pk[j], h1.y, h2.y, t);
+                    Ek[j] = predict_start(Ek[j], hE[1][j], hE[2][j], t);
+                }
             }
         }
         int it = MAX;                              // value if the loop runs to exhaustion (:225)
@@ -934,7 +974,9 @@ hipError_t launch_stepper(const StepArgs &a, hipStream_t stream)
     if (nsys <= 0) return hipSuccess;
     dim3 grid((unsigned)nsys), block(64);
     const bool snap = a.n_snap > 0 || a.resN != nullptr;   // snapshot / resume code only exists in its own instantiation
-    if (a.bundle > 1) {                            // one workgroup per bundle of a.bundle consecutive samples of a curve
+    if constexpr (TRPL_STEPPER_PREDICT != 0) {
+        if (a.bundle > 1) return hipErrorInvalidValue;      // no bundled predict kernels (refused by check_launch)
+    } else if (a.bundle > 1) {                            // one workgroup per bundle of a.bundle consecutive samples of a curve
         if (a.bundle > bundle_cap(a.L) || (!STRICT && a.L > 128)) return hipErrorInvalidValue;
         grid = dim3((unsigned)(((a.S + a.bundle - 1) / a.bundle) * a.C));
         block = dim3(64 * a.bundle);
@@ -972,5 +1014,6 @@ hipError_t launch_stepper(const StepArgs &a, hipStream_t stream)
     }
     return hipGetLastError();
 }
+TRPL_PREDICT_NS_END
 
 }  // namespace trpl

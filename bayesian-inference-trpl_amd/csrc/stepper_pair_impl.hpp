@@ -31,6 +31,7 @@
 #include "stepper_impl.hpp"
 
 namespace trpl {
+TRPL_PREDICT_NS_BEGIN                                // trpl::predict::pair in a TRPL_STEPPER_PREDICT unit (stepper_impl.hpp)
 namespace pair {
 
 constexpr int L = 128;      // nodes per system
@@ -188,6 +189,7 @@ __global__ void __launch_bounds__(64, 2) stepper_pair_kernel(const StepArgs a)
     const double mag = a.xld > 12 ? xs[12] : 0.0;
     const double TOL = a.TOL;
     const int MAX = a.MAX;
+    constexpr bool PREDICT = TRPL_STEPPER_PREDICT != 0;    // TRPL_FLAG_PREDICT: the extrapolated start (predict_start)
 
     // ---- state U^t in registers; U^{t-1..t-4} of N and P in a 4-slot LDS ring (slot = t mod 4), E's in registers ----
     // ring layout [slot][row][lane]{N, P}: a lane's N and P of one row and level are one ds_read_b128 / ds_write_b128
@@ -320,6 +322,10 @@ __global__ void __launch_bounds__(64, 2) stepper_pair_kernel(const StepArgs a)
                 bN[j] = a1 * Nk[j] + a2 * h1.x + a3 * h2.x + a4 * h3.x + a5 * h4.x;
                 bP[j] = a1 * Pk[j] + a2 * h1.y + a3 * h2.y + a4 * h3.y + a5 * h4.y;
                 hist2[(s4 + j) * 64 + lane] = make_double2(Nk[j], Pk[j]);
+                if constexpr (PREDICT) {
+                    Nk[j] = predict_start(Nk[j], h1.x, h2.x, t);
+                    Pk[j] = predict_start(Pk[j], h1.y, h2.y, t);
+                }
             }
             // the field's history stays in registers and is shifted here, before the iterations (12 v_mov_b64; no copy of
             // E^t is carried through them).  A register ring without the shift was measured and spills: DESIGN.md section 8
@@ -329,6 +335,7 @@ __global__ void __launch_bounds__(64, 2) stepper_pair_kernel(const StepArgs a)
 #pragma unroll
                 for (int m = 3; m >= 1; m--) hE[m][j] = hE[m - 1][j];
                 hE[0][j] = Ek[j];
+                if constexpr (PREDICT) Ek[j] = predict_start(Ek[j], hE[1][j], hE[2][j], t);
             }
         }
 
@@ -414,7 +421,16 @@ __global__ void __launch_bounds__(64, 2) stepper_pair_kernel(const StepArgs a)
 #pragma unroll
                 for (int j = 0; j < NR; j++) {
                     const double2 h = hist2[(s4 + j) * 64 + lane];
-                    Nk[j] = h.x; Pk[j] = h.y; Ek[j] = hE[0][j];
+                    if constexpr (PREDICT) {
+                        // back to the step's extrapolated start, formed from the same operands as above: the same bits
+                        const double2 h1 = hist2[((int)((t + 3) & 3) * NR + j) * 64 + lane],
+                                      h2 = hist2[((int)((t + 2) & 3) * NR + j) * 64 + lane];
+                        Nk[j] = predict_start(h.x, h1.x, h2.x, t);
+                        Pk[j] = predict_start(h.y, h1.y, h2.y, t);
+                        Ek[j] = predict_start(hE[0][j], hE[1][j], hE[2][j], t);
+                    } else {
+                        Nk[j] = h.x; Pk[j] = h.y; Ek[j] = hE[0][j];
+                    }
                 }
                 doneA = deadA; doneB = deadB; itA = itB = MAX;
                 iterate_step(std::true_type{});
@@ -482,5 +498,6 @@ hipError_t launch_stepper_pair_t(const StepArgs &a, hipStream_t stream)
     }
     return hipGetLastError();
 }
+TRPL_PREDICT_NS_END
 
 }  // namespace trpl

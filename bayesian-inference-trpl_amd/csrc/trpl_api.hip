@@ -205,6 +205,11 @@ int check_launch(uint32_t flags, int32_t L, int64_t steps, bool snap, bool resum
     if (int rc = check_variant_flags(flags, L)) return rc;
     if (((flags >> 14) & 7u) > 5u) return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_BDF_ORDER(%u): the order cap must be 1 .. 5 (0: the reference's ramp)", (flags >> 14) & 7u);
     const int32_t bundle = (int32_t)((flags >> 8) & 0xF) + 1;             // TRPL_FLAG_BUNDLE(m)
+    if (flags & TRPL_FLAG_PREDICT) {                                        // the extrapolated start: plain fp64 steppers only
+        if (flags & (TRPL_FLAG_FP32 | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
+            return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_PREDICT excludes TRPL_FLAG_FP32, TRPL_FLAG_MIXED and TRPL_FLAG_HIST32");
+        if (bundle > 1) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_PREDICT is not built for TRPL_FLAG_BUNDLE(m > 1)");
+    }
 #ifndef TRPL_EXPERIMENTAL
     if (flags & (TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
         return api_fail(TRPL_ERR_UNSUPPORTED, "%s: this library was built without the experimental steppers (measured and rejected, "
@@ -280,11 +285,15 @@ int launch(const trpl::StepArgs &a_in, uint32_t flags, hipStream_t st, int64_t s
 #endif
     if (pick_pair_kernel(a.S * a.C, a.L, steps, flags)) {
         build_pair_table(a);
-        hipError_t ep = trpl::launch_stepper_pair(a, st);
+        hipError_t ep = (flags & TRPL_FLAG_PREDICT) ? trpl::launch_stepper_pair_predict(a, st) : trpl::launch_stepper_pair(a, st);
         if (ep != hipSuccess) return api_fail(TRPL_ERR_HIP, "pair stepper launch: %s", hipGetErrorString(ep));
         return TRPL_OK;
     }
-    hipError_t e = (flags & TRPL_FLAG_STRICT) ? trpl::launch_stepper_strict(a, st) : trpl::launch_stepper_fast(a, st);
+    hipError_t e;
+    if (flags & TRPL_FLAG_PREDICT)
+        e = (flags & TRPL_FLAG_STRICT) ? trpl::launch_stepper_predict_strict(a, st) : trpl::launch_stepper_predict_fast(a, st);
+    else
+        e = (flags & TRPL_FLAG_STRICT) ? trpl::launch_stepper_strict(a, st) : trpl::launch_stepper_fast(a, st);
     if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "stepper launch: %s", hipGetErrorString(e));
     return TRPL_OK;
 }
@@ -322,12 +331,18 @@ int trpl_kernel_name(int64_t nsys, int32_t L, int64_t steps, uint32_t flags, int
     if (int rc = check_launch(flags, L, steps, snapshots != 0 && !(flags & TRPL_FLAG_FP32), false)) return rc;
     const char *tf[2] = {"false", "true"};
     const int snap = snapshots != 0, bundle = ((flags >> 8) & 0xF) != 0;
+    const bool optimistic = TRPL_PAIR_OPTIMISTIC != 0 && !(flags & TRPL_FLAG_PAIR_ALWAYS_SEAM);
     int n;
-    if (flags & TRPL_FLAG_FP32)
+    if (flags & TRPL_FLAG_PREDICT) {                // stepper_predict_*.hip (FP32 / MIXED / HIST32 / bundles refused above)
+        if (!(flags & TRPL_FLAG_STRICT) && pick_pair_kernel(nsys, L, steps, flags))
+            n = snprintf(buf, (size_t)buflen, "trpl::predict::pair::stepper_pair_kernel<true, %s, %s>", tf[snap], tf[optimistic]);
+        else
+            n = snprintf(buf, (size_t)buflen, "trpl::predict::stepper_kernel<%d, %s, %s, false, false, false>", L,
+                         tf[(flags & TRPL_FLAG_STRICT) != 0], tf[snap]);
+    } else if (flags & TRPL_FLAG_FP32)
         n = snprintf(buf, (size_t)buflen, "trpl::f32::stepper_kernel<%d>", L);
     else if (!(flags & (TRPL_FLAG_STRICT | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32)) && pick_pair_kernel(nsys, L, steps, flags))
-        n = snprintf(buf, (size_t)buflen, "trpl::pair::stepper_pair_kernel<true, %s, %s>", tf[snap],
-                     tf[TRPL_PAIR_OPTIMISTIC != 0 && !(flags & TRPL_FLAG_PAIR_ALWAYS_SEAM)]);
+        n = snprintf(buf, (size_t)buflen, "trpl::pair::stepper_pair_kernel<true, %s, %s>", tf[snap], tf[optimistic]);
     else
         n = snprintf(buf, (size_t)buflen, "trpl::stepper_kernel<%d, %s, %s, %s, %s, %s>", L, tf[(flags & TRPL_FLAG_STRICT) != 0],
                      tf[snap], tf[(flags & TRPL_FLAG_MIXED) != 0], tf[bundle], tf[(flags & TRPL_FLAG_HIST32) != 0]);

@@ -98,6 +98,10 @@ hipError_t launch_stepper_mixed(const StepArgs &a, hipStream_t stream);  // step
 hipError_t launch_stepper_hist32(const StepArgs &a, hipStream_t stream); // stepper_hist32.hip, L = 256 / 512
 // stepper_pair.hip: FAST, L = 128, two systems per wavefront
 hipError_t launch_stepper_pair(const StepArgs &a, hipStream_t stream);
+// TRPL_FLAG_PREDICT (stepper_predict_{fast,strict,pair}.hip): the same steppers with the extrapolated start of each step
+hipError_t launch_stepper_predict_fast(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_predict_strict(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_pair_predict(const StepArgs &a, hipStream_t stream);
 
 // likelihood.hip
 hipError_t launch_log10_clamp(void *x, int elem_bytes, int64_t rows, int64_t cols, int64_t ld, double mn,

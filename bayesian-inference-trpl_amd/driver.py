@@ -137,7 +137,7 @@ def overlap_window(full, done, budget, num_curves):
 
 def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=None, pl_f32=False,
            normalize=False, strict=False, device=0, info=None, times=None, fp32=False, devices=None, kernel=None,
-           mixed=False, bundle=1, hist32=False, bdf_order=None, extra_flags=0):
+           mixed=False, bundle=1, hist32=False, bdf_order=None, extra_flags=0, predict=False):
     """Fused likelihood of one experiment (trpl_loglik / trpl_loglik_obs / trpl_loglik_multi).
 
     X (S,13) solver units; init_params (C,L) nm^-3; lengths scalar or (C,); obs = list of C
@@ -151,6 +151,8 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
     bundle: the reference's max_sims_per_block (TRPL_FLAG_BUNDLE; single-device calls only).
     bdf_order: cap the BDF order ramp at 1 .. 5 (TRPL_FLAG_BDF_ORDER); extra_flags: further TRPL_FLAG_* bits, ORed in
     (tests / measurements: _abi.FLAG_PAIR_ALWAYS_SEAM, _abi.FLAG_PAIR_ADJACENT, ...).
+    predict: start each time step's iteration from the extrapolated history (TRPL_FLAG_PREDICT; opt-in, off by default:
+    about half the solves; PL agrees with the default path to ~1e-9 median, within the tolerance include/trpl.h states).
     """
     X = np.ascontiguousarray(X, dtype=np.float64)
     if X.ndim != 2 or X.shape[1] != 13:
@@ -197,7 +199,7 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
     flags = (_abi.FLAG_STRICT if strict else 0) | (_abi.FLAG_PL_F32 if pl_f32 else 0) \
         | (_abi.FLAG_NORMALIZE if normalize else 0) | _abi.fp32_flags(fp32) | _abi.kernel_flag(kernel) \
         | (_abi.FLAG_MIXED if mixed else 0) | _abi.flag_bundle(bundle, L) | (_abi.FLAG_HIST32 if hist32 else 0) \
-        | _abi.flag_bdf_order(bdf_order) | int(extra_flags)
+        | _abi.flag_bdf_order(bdf_order) | int(extra_flags) | (_abi.FLAG_PREDICT if predict else 0)
     sec = _abi.C.c_double(0.0)
     lib = _abi.lib()
     if devices is not None:
@@ -239,7 +241,7 @@ def _bundle_of(gpu_info, L):
 
 
 def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_params, normalize, pl_dtype, group,
-                       num_gpus, gpu_id, device, solver_time, err_sq_time, sim_t, bundle=1, literal=False):
+                       num_gpus, gpu_id, device, solver_time, err_sq_time, sim_t, bundle=1, literal=False, predict=False):
     """Several experiments, fused option on: the reference's own loop order -- curves -> sample blocks ->
     experiments (bayeslib.py:117-171) -- with the block's PL matrix kept in HBM: one solve per (curve, block)
     (trpl_solve_pl_dev), then one pass over it per experiment (trpl_loglik_from_pl_dev: normalise, clamp,
@@ -283,7 +285,7 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
                 t0 = time.perf_counter()
                 tdev.solve_pl_device(mat_d, thicknesses[c], Time, L, T, ini_d[c].contiguous(), pl_d, status=st_d,
                                      tol=sim_params[6], MAX=sim_params[7], plT=sim_params[4],
-                                     flags=_abi.flag_bundle(bundle, L))
+                                     flags=_abi.flag_bundle(bundle, L) | (_abi.FLAG_PREDICT if predict else 0))
                 torch.cuda.synchronize(dev)
                 t1 = time.perf_counter()
                 for e, per_curve in enumerate(staged):                        # :171
@@ -306,7 +308,8 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
     num_gpus, ...) -> experiments; float32 PL buffer (:137); X[:, :-1] to the model and
     X[:, -1] as the log offset (:144,:195).  With gpu_info['fused'] true and every observation
     grid a prefix of the simulation grid, each (curve-set, block, experiment) is one fused launch
-    (spread over gpu_info['devices'] when that is given, see loglik).
+    (spread over gpu_info['devices'] when that is given, see loglik).  gpu_info['predict'] = True (default False) runs
+    every solve with the extrapolated start of TRPL_FLAG_PREDICT, on the fused and the unfused (pvSim) paths alike.
     """
     group = int(gpu_info["sims_per_gpu"])
     num_gpus = int(gpu_info["num_gpus"])
@@ -322,6 +325,10 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
     Time, L, T = sim_params[1], sim_params[2], sim_params[3]
     sim_t = np.linspace(0, Time, T + 1)                                   # :115
     pl_dtype = np.dtype(gpu_info.get("pl_dtype", np.float32))
+    predict = bool(gpu_info.get("predict", False))
+    if predict and int(gpu_info.get("max_sims_per_block", 1)) > 1:
+        raise ValueError("gpu_info['predict'] does not combine with gpu_info['max_sims_per_block'] > 1: there is no bundled "
+                         "stepper with the extrapolated start (TRPL_FLAG_PREDICT)")
 
     def in_range(t):
         t = np.asarray(t, dtype=float)
@@ -332,7 +339,8 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
     if fused and len(e_data) > 1 and gpu_info.get("devices") is None:
         _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_params, NORMALIZE, pl_dtype,
                            group, num_gpus, gpu_id, device, solver_time, err_sq_time, sim_t,
-                           bundle=_bundle_of(gpu_info, L), literal=bool(gpu_info.get("interpolate_prefix", False)))
+                           bundle=_bundle_of(gpu_info, L), literal=bool(gpu_info.get("interpolate_prefix", False)),
+                           predict=predict)
         return
     if fused:
         # An experiment sampled exactly on the full simulation grid is compared point by point (the reference's bypass,
@@ -352,7 +360,7 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
                        [exp[1][c] for c in range(num_curves)], tol=sim_params[6], MAX=sim_params[7],
                        P=P[e, blk:blk + size], pl_f32=(pl_dtype == np.float32), normalize=NORMALIZE,
                        device=device, info=info, devices=gpu_info.get("devices"), bundle=_bundle_of(gpu_info, L),
-                       times=None if on_grid else [exp[0][c] for c in range(num_curves)])
+                       times=None if on_grid else [exp[0][c] for c in range(num_curves)], predict=predict)
                 solver_time[gpu_id] += info["seconds"]
         return
 
@@ -378,6 +386,10 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
     model_kw = {}
     if model is pvSim and gpu_info.get("kernel") is not None and int(gpu_info.get("max_sims_per_block", 1)) == 1:
         model_kw["kernel"] = gpu_info["kernel"]
+    if predict:                                  # never dropped silently: only this package's pvSim has the mode
+        if model is not pvSim:
+            raise ValueError("gpu_info['predict'] needs this package's model (pvSim) on the unfused path, got %r" % (model,))
+        model_kw["predict"] = True
     reads_pl = [any(on_grid[e][c] for e in range(len(e_data))) for c in range(num_curves)]
 
     def process_curve(ic_num, blk, size, last=True):

@@ -12,7 +12,8 @@ def _as_f64(a):
 
 def solve_pl(matPar, Length, Time, L, T, dN, plT=1, tol=7, MAX=10000, out=None, dtype=np.float64,
              strict=False, device=0, fp32=False, kernel=None, mixed=False, snap_steps=None, plN=None, plP=None, plE=None,
-             snapshots=None, resume=None, snap_raw=False, bundle=1, hist32=False, bdf_order=None, extra_flags=0):
+             snapshots=None, resume=None, snap_raw=False, bundle=1, hist32=False, bdf_order=None, extra_flags=0,
+             predict=False):
     """PL(t) for S systems of one curve.  matPar (S,12) and dN (L,) in nm/ns units.
     Returns (plI, status, iters_total, seconds).
 
@@ -31,6 +32,8 @@ def solve_pl(matPar, Length, Time, L, T, dN, plT=1, tol=7, MAX=10000, out=None, 
     convergence test per inner iteration (pvSimPCR.py:211-216) -- strict=True bit-identical to the reference run that
     way, otherwise to rounding (L <= 128, one-system kernel).
     bdf_order: cap the BDF order ramp (pvSimPCR.py:241-250) at 1 .. 5 (TRPL_FLAG_BDF_ORDER; 2 = Legacy/pvSim.py's scheme).
+    predict: start each time step's iteration from the extrapolated history instead of U^t (TRPL_FLAG_PREDICT; opt-in,
+    about half the solves; PL agrees with the default path to ~1e-9 median, within the tolerance include/trpl.h states).
     extra_flags: further TRPL_FLAG_* bits, ORed in (tests / measurements: _abi.FLAG_PAIR_ALWAYS_SEAM, ...)."""
     matPar = _as_f64(matPar)
     if matPar.ndim != 2 or matPar.shape[1] != 12:
@@ -56,7 +59,8 @@ def solve_pl(matPar, Length, Time, L, T, dN, plT=1, tol=7, MAX=10000, out=None, 
     sec = _abi.C.c_double(0.0)
     flags = (_abi.FLAG_STRICT if strict else 0) | _abi.fp32_flags(fp32) | _abi.kernel_flag(kernel) \
         | (_abi.FLAG_MIXED if mixed else 0) | (_abi.FLAG_SNAP_RAW if snap_raw else 0) | _abi.flag_bundle(bundle, L) \
-        | (_abi.FLAG_HIST32 if hist32 else 0) | _abi.flag_bdf_order(bdf_order) | int(extra_flags)
+        | (_abi.FLAG_HIST32 if hist32 else 0) | _abi.flag_bdf_order(bdf_order) | int(extra_flags) \
+        | (_abi.FLAG_PREDICT if predict else 0)
     steps = None
     n_snap = 0
     if snap_steps is not None and len(snap_steps):
@@ -100,7 +104,7 @@ def _snapshot_target(arr, S, n, width):
 
 
 def pvSim(plI_main, plN_main, plP_main, plE_main, matPar, simPar, iniPar, TPB=None, BPG=None,
-          max_sims_per_block=1, init_mode="exp", strict=False, device=0, info=None, kernel=None):
+          max_sims_per_block=1, init_mode="exp", strict=False, device=0, info=None, kernel=None, predict=False):
     """pvSimPCR.pvSim (pvSimPCR.py:309).  TPB and BPG (CUDA launch shape) are accepted and ignored: one wavefront owns
     one system (or two).  max_sims_per_block = 2 .. 4 (2 .. 16 on grids of up to 64 nodes) -- neighbouring samples
     sharing one convergence test -- is honoured (bit for bit with strict=True).  init_mode "continue" (a stub in the reference,
@@ -110,13 +114,17 @@ def pvSim(plI_main, plN_main, plP_main, plE_main, matPar, simPar, iniPar, TPB=No
     densities (nm^-3) and the field (nm^-1) of the state at the time steps pT = simPar[5]; anything else
     (None, the dummies bayeslib passes) is ignored as before.  `info`, if a dict, receives 'status' and
     'iters_total'.  kernel: None (the library picks the FAST stepper by launch size) | "pair" | "single" (TRPL_FLAG_KERNEL_*;
-    driver.simulate pins it for the launches it overlaps)."""
+    driver.simulate pins it for the launches it overlaps).  predict=True: TRPL_FLAG_PREDICT (solve_pl); not with
+    max_sims_per_block > 1 (ValueError: there is no bundled predict stepper)."""
     Length, Time, L, T, plT, pT, tol, MAX = simPar
     # max_sims_per_block > 1 couples the convergence of neighbouring samples in the reference (pvSimPCR.py:213-216):
     # honoured up to 4 per bundle from L = 128 on and 16 up to L = 64 (strict: any L, bit for bit; otherwise L <= 128, to
     # rounding) -- the reference's 48 KB of shared memory hold 3 / 6 / 13 at L = 128 / 64 / 32; beyond that every sample
     # converges on its own
     bundle = int(max_sims_per_block)
+    if predict and bundle > 1:
+        raise ValueError("predict=True does not combine with max_sims_per_block=%d > 1: there is no bundled stepper with the "
+                         "extrapolated start (TRPL_FLAG_PREDICT)" % bundle)
     if not (1 <= bundle <= _abi.bundle_cap(L) and (strict or int(L) <= 128)):
         bundle = 1
     dx = Length / L
@@ -146,7 +154,7 @@ def pvSim(plI_main, plN_main, plP_main, plE_main, matPar, simPar, iniPar, TPB=No
                                      MAX=int(MAX), out=plI_main, strict=strict, device=device,
                                      resume=tuple(iniPar) if init_mode == "continue" else None, bundle=bundle,
                                      kernel=kernel if (bundle == 1 and not strict and int(L) == 128) else None,
-                                     snap_steps=steps if want else None, **(snaps if want else {}))
+                                     snap_steps=steps if want else None, predict=predict, **(snaps if want else {}))
     if info is not None:
         info["status"] = status
         info["iters_total"] = iters

@@ -36,7 +36,8 @@ extern "C" {
 
 #define TRPL_ABI_VERSION 5   /* 5 (round 6): trpl_has_experimental(); TRPL_FLAG_MIXED / TRPL_FLAG_HIST32 exist only in a library built with
                                 `make EXPERIMENTAL=1` (the default library answers TRPL_ERR_UNSUPPORTED); trpl_kernel_name validates like a
-                                launch; roctx ranges around the host-buffer calls when libroctx64.so is loadable; trpl_interp_rows (host).
+                                launch; roctx ranges around the host-buffer calls when libroctx64.so is loadable; trpl_interp_rows (host);
+                                TRPL_FLAG_PREDICT (an additive, opt-in flag: no existing call changes).
                                 4 (round 5): TRPL_FLAG_BDF_ORDER, TRPL_FLAG_PAIR_ALWAYS_SEAM / _PAIR_ADJACENT / _MULTI_FORCE_PAD (were
                                 process-wide environment switches), trpl_multi_create_ex, TRPL_PL_ENVELOPE_K_L512; floor_col = -2 for
                                 flagged systems, T <= 2^30 - 16, up to TRPL_MAX_CURVES curves and TRPL_FLAG_HIST32 (round 4, then
@@ -135,6 +136,32 @@ extern "C" {
                                      matter only, results are bit-identical either way */
 #define TRPL_FLAG_MULTI_FORCE_PAD 0x80000   /* trpl_loglik_multi_dev, tests: take the padded all-gather + unpadding pass even when
                                      the shards are equal */
+#define TRPL_FLAG_PREDICT 0x100000  /* opt-in, OFF by default: each time step's Newton/Picard iteration starts from an
+                                     extrapolation of the history instead of U^t (pvSimPCR.py:130-132) -- 3 U^t - 3 U^{t-1} + U^{t-2}
+                                     from global step 2 on, 2 U^t - U^{t-1} at step 1, U^t at step 0, for N, P and E.  Nothing else
+                                     changes: the BDF right-hand sides are formed from U^t, U^t enters the history, assembly, both
+                                     residual tests, both solves, the field update, the break rule and the iters >= MAX flagging are
+                                     the default path's.  The first test of a step then usually passes: 1.01 - 1.13 inner
+                                     iterations per step instead of 2.01 - 2.25, 1.63 - 1.71 x the system-timesteps/s on
+                                     every measured configuration, L = 512 included.  A resumed launch
+                                     continues the same sequence (t is the global step), snapshots / resume, FAST and STRICT, every
+                                     L and both FAST kernels accept it (their own instantiations, trpl::predict::...).
+                                     Tolerance: each step is still solved to the caller's tol, by a different route, so results are
+                                     NOT the default path's bits.  Above TRPL_PL_FLOOR_EXCESS, PL is within 5e-5 relative of
+                                     the default path for windows of up to 8000 steps and within 3e-4 up to 80 000 steps, with
+                                     the same flagged systems (medians ~1e-9; maxima measured on 256-sample subsets of the four
+                                     configurations of tools/bench_predict.py: 2.8e-6 .. 2.1e-5 at T = 8000, 1.7e-4 at
+                                     T = 80 000).  The gap is NOT a floor effect: near the floor (r = PL / (B L n0p0) < 1) the
+                                     paths agree within 2e-8 at T = 8000.  It is the default path's own tol-sized drift in
+                                     strongly excited, slowly decaying systems (r ~ 1e5 .. 1e6), growing ~2.5e-9 per step at the
+                                     worst point: there the default path is 2.4e-6 (T = 8000) / 1.7e-4 (T = 80 000) away from a
+                                     tol-11 solution and predict 4.6e-7 / 6.8e-6.  Predict is never farther from the tol-11
+                                     solution than the default path (max over a batch; measured 0.16 - 0.21 of its distance).
+                                     The extra 60 B of scratch per lane of trpl::predict::pair::stepper_pair_kernel<true, true,
+                                     true> (snapshots + optimistic seam; the default counterpart uses 36 B) is the only resource
+                                     difference from the default kernels; the timed, snapshot-free kernels use none.
+                                     Refused: with TRPL_FLAG_FP32, _MIXED or _HIST32 TRPL_ERR_ARG; with TRPL_FLAG_BUNDLE(m > 1)
+                                     TRPL_ERR_UNSUPPORTED.  Python: predict=True, gpu_info["predict"] */
 #define TRPL_FLAG_KERNEL_PAIR 0x10    /* run the two-systems-per-wavefront stepper whatever the launch size (L = 128,
                                         fp64, not STRICT -- anything else is TRPL_ERR_ARG) */
 #define TRPL_FLAG_KERNEL_SINGLE 0x20  /* run the one-system-per-wavefront stepper whatever the launch size */

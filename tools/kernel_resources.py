@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Register / LDS / occupancy table of the stepper kernels from hipcc's kernel-resource-usage remarks.
-    python tools/kernel_resources.py [pair fast strict mixed f32]   (cross-compiles, no GPU needed)"""
+    python tools/kernel_resources.py [pair fast strict mixed f32 predict_fast predict_strict predict_pair]
+(cross-compiles, no GPU needed; a name is the translation unit csrc/stepper_<name>.hip)"""
 import os
 import re
 import subprocess
@@ -8,7 +9,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bayesian-inference-trpl_amd", "csrc")
-CONTRACT = {"strict": "off"}
+CONTRACT = {"strict": "off", "predict_strict": "off"}      # the Makefile's -ffp-contract of each unit; default on
 
 
 def main():
@@ -20,7 +21,7 @@ def main():
             name = b.split("\n")[0].split(" ")[0]
             g = lambda k: (re.search(k + r": (\d+)", b) or [None, "?"])[1]
             dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-            print("%-7s %-78s VGPR %3s AGPR %3s spill %3s scratch %4s occ %s LDS %6s" % (
+            print("%-14s %-78s VGPR %3s AGPR %3s spill %3s scratch %4s occ %s LDS %6s" % (
                 n, dem[:78], g("VGPRs"), g("AGPRs"), g("VGPR Spill"), g(r"ScratchSize \[bytes/lane\]"),
                 g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")))
 
