@@ -136,14 +136,11 @@ int check_grid(int32_t L, int64_t T, int32_t plT, int32_t max_iter, double time_
 // the observation brackets of trpl_loglik_obs are host data in the host-buffer calls: sorted, in [1, T]
 int check_brackets(const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int32_t C, int64_t obs_ld,
                    const int64_t *n_obs, int64_t T);
-// which FAST kernel a logical batch of nsys systems runs (flags may force it); see trpl_kernel_variant
-bool pick_pair_kernel(int64_t nsys, int32_t L, int64_t steps, uint32_t flags);
-int check_variant_flags(uint32_t flags, int32_t L);
-// every flag / shape combination a stepper launch refuses (trpl_api.hip); launch() and trpl_kernel_name share it
-int check_launch(uint32_t flags, int32_t L, int64_t steps, bool snap, bool resume);
-// flags with the kernel variant of the logical batch pinned (TRPL_FLAG_KERNEL_PAIR / _SINGLE set)
-uint32_t pin_variant(uint32_t flags, int64_t nsys, int32_t L, int64_t steps);
 // time steps a likelihood launch takes: up to the last observation (on-grid), T off-grid
 int64_t loglik_steps(bool interp, int32_t C, const int64_t *n_obs, int32_t plT, int64_t T);
+// trpl_loglik_multi[_dev], S samples cut into shards: refuses contradictory TRPL_FLAG_KERNEL_* bits, bundles and an n_obs out
+// of range, then sets in `flags` the kernel variant a launch of the WHOLE batch runs (TRPL_FLAG_KERNEL_PAIR / _SINGLE), whatever
+// the shard sizes: a sample's bits then do not depend on how the batch is cut (the two FAST kernels agree to rounding only)
+int pin_sharded_batch(uint32_t &flags, int64_t S, int32_t C, int32_t L, int64_t T, int32_t plT, bool interp, const int64_t *n_obs, int64_t obs_ld);
 
 }  // namespace trpl

@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "api_util.hpp"
-#include "crosslane.hpp"      // TRPL_PAIR_OPTIMISTIC (trpl_kernel_name)
+#include "crosslane.hpp"      // TRPL_PAIR_OPTIMISTIC (classify_stepper)
 
 namespace trpl {
 
@@ -170,7 +170,37 @@ void build_pair_table(trpl::StepArgs &a)
     a.pair_n = k;                                   // == a.C
 }
 
-}  // namespace
+// Which stepper instantiation a launch runs: the kernel family and the template arguments of its kernel.
+struct StepperChoice {
+    enum Family { Single, Pair, F32 } family;        // trpl::stepper_kernel / pair::stepper_pair_kernel / f32::stepper_kernel
+    int32_t L, bundle;                               // bundle: m of TRPL_FLAG_BUNDLE(m)
+    bool strict, snap, mixed, hist32;                // template arguments of the one-system kernel, with bundle > 1
+    bool predict;                                    // the instantiation in namespace trpl::predict
+    bool optimistic;                                 // paired kernel: the optimistic seam (not TRPL_FLAG_PAIR_ALWAYS_SEAM)
+};
+
+// THE function that maps a call to a kernel: launch(), trpl_kernel_name, trpl_kernel_variant and pin_variant read its answer.
+// It does not validate (check_launch does); on what check_launch accepts at most one of FP32 / STRICT / MIXED / HIST32 is
+// set, and the precedence below is what trpl_kernel_variant answers for the rest (STRICT | FP32 -> FP32, KERNEL_PAIR | STRICT
+// -> STRICT).  HIST32 leaves the paired-or-single rung alone: launches accept it at L = 256 / 512 only, and pin_variant
+// pins by launch size whatever it is.  snap: state snapshots or a resume (their own instantiation).
+StepperChoice classify_stepper(uint32_t flags, int32_t L, int64_t nsys, int64_t steps, bool snap)
+{
+    StepperChoice c = {StepperChoice::Single, L, flags_bundle(flags)};
+    c.snap = snap;
+    c.predict = (flags & TRPL_FLAG_PREDICT) != 0;
+    c.optimistic = TRPL_PAIR_OPTIMISTIC != 0 && !(flags & TRPL_FLAG_PAIR_ALWAYS_SEAM);
+    if (flags & TRPL_FLAG_FP32) c.family = StepperChoice::F32;
+    else if (flags & TRPL_FLAG_STRICT) c.strict = true;
+    else if (flags & TRPL_FLAG_MIXED) c.mixed = true;
+    else {
+        c.hist32 = (flags & TRPL_FLAG_HIST32) != 0;
+        if (L == 128 && c.bundle == 1 &&                                             // a bundle is one system per wavefront
+            ((flags & TRPL_FLAG_KERNEL_PAIR) || (!(flags & TRPL_FLAG_KERNEL_SINGLE) && use_pair_kernel(nsys, steps))))
+            c.family = StepperChoice::Pair;
+    }
+    return c;
+}
 
 int check_variant_flags(uint32_t flags, int32_t L)
 {
@@ -181,30 +211,21 @@ int check_variant_flags(uint32_t flags, int32_t L)
     return TRPL_OK;
 }
 
-bool pick_pair_kernel(int64_t nsys, int32_t L, int64_t steps, uint32_t flags)
-{
-    if (L != 128 || (flags & (TRPL_FLAG_STRICT | TRPL_FLAG_FP32 | TRPL_FLAG_MIXED))) return false;
-    if (flags & 0xF00u) return false;                          // TRPL_FLAG_BUNDLE(m > 1): one system per wavefront, one bundle per workgroup
-    if (flags & TRPL_FLAG_KERNEL_PAIR) return true;
-    if (flags & TRPL_FLAG_KERNEL_SINGLE) return false;
-    return use_pair_kernel(nsys, steps);
-}
-
 uint32_t pin_variant(uint32_t flags, int64_t nsys, int32_t L, int64_t steps)
 {
     if (flags & kVariantBits) return flags;
-    return flags | (pick_pair_kernel(nsys, L, steps, flags) ? TRPL_FLAG_KERNEL_PAIR : TRPL_FLAG_KERNEL_SINGLE);
+    return flags | (classify_stepper(flags, L, nsys, steps, false).family == StepperChoice::Pair ? TRPL_FLAG_KERNEL_PAIR : TRPL_FLAG_KERNEL_SINGLE);
 }
 
-// Everything a stepper launch refuses because of its flags and shape, in ONE place: launch() and trpl_kernel_name run the
-// same checks, so a kernel name is only ever returned for an instantiation that exists and that the launch would run.
+// Everything a stepper launch refuses because of its flags and shape: launch() and trpl_kernel_name run the same checks
+// before they classify, so a kernel name is only ever returned for an instantiation that exists and that the launch would run.
 // snap: state snapshots requested; resume: the launch continues from a checkpoint.
 int check_launch(uint32_t flags, int32_t L, int64_t steps, bool snap, bool resume)
 {
     if (!pow2(L) || L < 4 || L > 512) return api_fail(TRPL_ERR_ARG, "L=%d must be a power of two in [4, 512]", L);
     if (int rc = check_variant_flags(flags, L)) return rc;
-    if (((flags >> 14) & 7u) > 5u) return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_BDF_ORDER(%u): the order cap must be 1 .. 5 (0: the reference's ramp)", (flags >> 14) & 7u);
-    const int32_t bundle = (int32_t)((flags >> 8) & 0xF) + 1;             // TRPL_FLAG_BUNDLE(m)
+    if (flags_bdf_order(flags) > 5u) return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_BDF_ORDER(%u): the order cap must be 1 .. 5 (0: the reference's ramp)", flags_bdf_order(flags));
+    const int32_t bundle = flags_bundle(flags);
     if (flags & TRPL_FLAG_PREDICT) {                                        // the extrapolated start: plain fp64 steppers only
         if (flags & (TRPL_FLAG_FP32 | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
             return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_PREDICT excludes TRPL_FLAG_FP32, TRPL_FLAG_MIXED and TRPL_FLAG_HIST32");
@@ -245,6 +266,19 @@ int check_launch(uint32_t flags, int32_t L, int64_t steps, bool snap, bool resum
     return TRPL_OK;
 }
 
+}  // namespace
+
+int pin_sharded_batch(uint32_t &flags, int64_t S, int32_t C, int32_t L, int64_t T, int32_t plT, bool interp, const int64_t *n_obs, int64_t obs_ld)
+{
+    if (int rc = check_variant_flags(flags, L)) return rc;
+    if (flags_bundle(flags) > 1) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_BUNDLE couples neighbouring samples: a sharded batch would depend on where it is cut");
+    for (int c = 0; c < C; c++)
+        if (n_obs[c] < 1 || n_obs[c] > obs_ld)
+            return api_fail(TRPL_ERR_ARG, "n_obs[%d]=%lld out of range (obs_ld %lld)", c, (long long)n_obs[c], (long long)obs_ld);
+    flags = pin_variant(flags, S * (int64_t)C, L, loglik_steps(interp, C, n_obs, plT, T));
+    return TRPL_OK;
+}
+
 int select_device(int32_t device)
 {
     int n = 0;
@@ -264,37 +298,21 @@ namespace {
 int launch(const trpl::StepArgs &a_in, uint32_t flags, hipStream_t st, int64_t steps)
 {
     if (int rc = check_launch(flags, a_in.L, steps, a_in.n_snap > 0, a_in.resN != nullptr)) return rc;
+    const StepperChoice c = classify_stepper(flags, a_in.L, a_in.S * a_in.C, steps, a_in.n_snap > 0 || a_in.resN != nullptr);
     trpl::StepArgs a = a_in;
-    a.bundle = (int32_t)((flags >> 8) & 0xF) + 1;             // TRPL_FLAG_BUNDLE(m)
-    if (flags & TRPL_FLAG_FP32) {
-        hipError_t e32 = trpl::launch_stepper_f32(a, st);
-        if (e32 != hipSuccess) return api_fail(TRPL_ERR_HIP, "fp32 stepper launch: %s", hipGetErrorString(e32));
-        return TRPL_OK;
-    }
+    a.bundle = c.bundle;
+    if (c.family == StepperChoice::Pair) build_pair_table(a);
+    hipError_t (*fn)(const trpl::StepArgs &, hipStream_t) = c.predict ? trpl::launch_stepper_predict_fast : trpl::launch_stepper_fast;
+    const char *what = "";                          // the word the error message starts with
+    if (c.family == StepperChoice::F32) { fn = trpl::launch_stepper_f32; what = "fp32 "; }
 #ifdef TRPL_EXPERIMENTAL
-    if (flags & TRPL_FLAG_MIXED) {
-        hipError_t em = trpl::launch_stepper_mixed(a, st);
-        if (em != hipSuccess) return api_fail(TRPL_ERR_HIP, "mixed stepper launch: %s", hipGetErrorString(em));
-        return TRPL_OK;
-    }
-    if (flags & TRPL_FLAG_HIST32) {
-        hipError_t eh = trpl::launch_stepper_hist32(a, st);
-        if (eh != hipSuccess) return api_fail(TRPL_ERR_HIP, "hist32 stepper launch: %s", hipGetErrorString(eh));
-        return TRPL_OK;
-    }
+    else if (c.mixed) { fn = trpl::launch_stepper_mixed; what = "mixed "; }
+    else if (c.hist32) { fn = trpl::launch_stepper_hist32; what = "hist32 "; }
 #endif
-    if (pick_pair_kernel(a.S * a.C, a.L, steps, flags)) {
-        build_pair_table(a);
-        hipError_t ep = (flags & TRPL_FLAG_PREDICT) ? trpl::launch_stepper_pair_predict(a, st) : trpl::launch_stepper_pair(a, st);
-        if (ep != hipSuccess) return api_fail(TRPL_ERR_HIP, "pair stepper launch: %s", hipGetErrorString(ep));
-        return TRPL_OK;
-    }
-    hipError_t e;
-    if (flags & TRPL_FLAG_PREDICT)
-        e = (flags & TRPL_FLAG_STRICT) ? trpl::launch_stepper_predict_strict(a, st) : trpl::launch_stepper_predict_fast(a, st);
-    else
-        e = (flags & TRPL_FLAG_STRICT) ? trpl::launch_stepper_strict(a, st) : trpl::launch_stepper_fast(a, st);
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "stepper launch: %s", hipGetErrorString(e));
+    else if (c.family == StepperChoice::Pair) { fn = c.predict ? trpl::launch_stepper_pair_predict : trpl::launch_stepper_pair; what = "pair "; }
+    else if (c.strict) fn = c.predict ? trpl::launch_stepper_predict_strict : trpl::launch_stepper_strict;
+    const hipError_t e = fn(a, st);
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "%sstepper launch: %s", what, hipGetErrorString(e));
     return TRPL_OK;
 }
 
@@ -315,11 +333,12 @@ const char *trpl_last_error(void) { return g_err; }
 
 int trpl_kernel_variant(int64_t nsys, int32_t L, int64_t steps, uint32_t flags)
 {
-    if (flags & TRPL_FLAG_FP32) return TRPL_KERNEL_FP32;
-    if (flags & TRPL_FLAG_STRICT) return TRPL_KERNEL_STRICT;
-    if (flags & TRPL_FLAG_MIXED) return TRPL_KERNEL_MIXED;
-    if (flags & TRPL_FLAG_HIST32) return TRPL_KERNEL_HIST32;
-    return pick_pair_kernel(nsys, L, steps, flags) ? TRPL_KERNEL_FAST_PAIR : TRPL_KERNEL_FAST;
+    const StepperChoice c = classify_stepper(flags, L, nsys, steps, false);
+    if (c.family == StepperChoice::F32) return TRPL_KERNEL_FP32;
+    if (c.strict) return TRPL_KERNEL_STRICT;
+    if (c.mixed) return TRPL_KERNEL_MIXED;
+    if (c.hist32) return TRPL_KERNEL_HIST32;
+    return c.family == StepperChoice::Pair ? TRPL_KERNEL_FAST_PAIR : TRPL_KERNEL_FAST;
 }
 
 int trpl_kernel_name(int64_t nsys, int32_t L, int64_t steps, uint32_t flags, int32_t snapshots, char *buf, int64_t buflen)
@@ -329,23 +348,16 @@ int trpl_kernel_name(int64_t nsys, int32_t L, int64_t steps, uint32_t flags, int
     // the checks of a launch: no name for a combination launch() refuses or for an instantiation that does not exist
     // (`snapshots` covers snapshots AND resume; the fp32 stepper has one instantiation and accepts a resume)
     if (int rc = check_launch(flags, L, steps, snapshots != 0 && !(flags & TRPL_FLAG_FP32), false)) return rc;
-    const char *tf[2] = {"false", "true"};
-    const int snap = snapshots != 0, bundle = ((flags >> 8) & 0xF) != 0;
-    const bool optimistic = TRPL_PAIR_OPTIMISTIC != 0 && !(flags & TRPL_FLAG_PAIR_ALWAYS_SEAM);
+    const StepperChoice c = classify_stepper(flags, L, nsys, steps, snapshots != 0);
+    const char *tf[2] = {"false", "true"}, *ns = c.predict ? "trpl::predict::" : "trpl::";      // stepper_predict_*.hip
     int n;
-    if (flags & TRPL_FLAG_PREDICT) {                // stepper_predict_*.hip (FP32 / MIXED / HIST32 / bundles refused above)
-        if (!(flags & TRPL_FLAG_STRICT) && pick_pair_kernel(nsys, L, steps, flags))
-            n = snprintf(buf, (size_t)buflen, "trpl::predict::pair::stepper_pair_kernel<true, %s, %s>", tf[snap], tf[optimistic]);
-        else
-            n = snprintf(buf, (size_t)buflen, "trpl::predict::stepper_kernel<%d, %s, %s, false, false, false>", L,
-                         tf[(flags & TRPL_FLAG_STRICT) != 0], tf[snap]);
-    } else if (flags & TRPL_FLAG_FP32)
-        n = snprintf(buf, (size_t)buflen, "trpl::f32::stepper_kernel<%d>", L);
-    else if (!(flags & (TRPL_FLAG_STRICT | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32)) && pick_pair_kernel(nsys, L, steps, flags))
-        n = snprintf(buf, (size_t)buflen, "trpl::pair::stepper_pair_kernel<true, %s, %s>", tf[snap], tf[optimistic]);
+    if (c.family == StepperChoice::F32)
+        n = snprintf(buf, (size_t)buflen, "%sf32::stepper_kernel<%d>", ns, c.L);
+    else if (c.family == StepperChoice::Pair)
+        n = snprintf(buf, (size_t)buflen, "%spair::stepper_pair_kernel<true, %s, %s>", ns, tf[c.snap], tf[c.optimistic]);
     else
-        n = snprintf(buf, (size_t)buflen, "trpl::stepper_kernel<%d, %s, %s, %s, %s, %s>", L, tf[(flags & TRPL_FLAG_STRICT) != 0],
-                     tf[snap], tf[(flags & TRPL_FLAG_MIXED) != 0], tf[bundle], tf[(flags & TRPL_FLAG_HIST32) != 0]);
+        n = snprintf(buf, (size_t)buflen, "%sstepper_kernel<%d, %s, %s, %s, %s, %s>", ns, c.L, tf[c.strict], tf[c.snap],
+                     tf[c.mixed], tf[c.bundle > 1], tf[c.hist32]);
     if (n < 0 || n >= buflen) return api_fail(TRPL_ERR_ARG, "buflen=%lld is too small for the kernel name", (long long)buflen);
     return TRPL_OK;
 }

@@ -76,7 +76,9 @@ struct StepArgs {
 // caps the order at k: the row is min(t, k - 1).  k = 2 is the scheme of the reference's older solver Legacy/pvSim.py:94-97
 // (Euler, then BDF2), which makes that file a whole-curve parity reference.  The cap is wave-uniform
 // scalar code outside the iterations: no cost when it is off.
-__host__ __device__ constexpr int32_t bdf_row_cap(uint32_t flags) { return ((flags >> 14) & 7u) ? (int32_t)((flags >> 14) & 7u) - 1 : 4; }
+__host__ __device__ constexpr uint32_t flags_bdf_order(uint32_t flags) { return (flags >> 14) & 7u; }    // k of TRPL_FLAG_BDF_ORDER(k)
+__host__ __device__ constexpr int32_t bdf_row_cap(uint32_t flags) { return flags_bdf_order(flags) ? (int32_t)flags_bdf_order(flags) - 1 : 4; }
+constexpr int32_t flags_bundle(uint32_t flags) { return (int32_t)((flags >> 8) & 0xFu) + 1; }                // m of TRPL_FLAG_BUNDLE(m), 1 .. 16
 template <typename T>
 __device__ __forceinline__ void bdf_row(int32_t row, T &a0, T &a1, T &a2, T &a3, T &a4, T &a5)
 {
@@ -87,21 +89,21 @@ __device__ __forceinline__ void bdf_row(int32_t row, T &a0, T &a1, T &a2, T &a3,
     else               { a0 = (T)(137.0 / 60); a1 = (T)-5.0; a2 = (T)5.0; a3 = (T)(-10.0 / 3); a4 = (T)1.25; a5 = (T)-0.2; }
 }
 
-// Launchers (one translation unit per arithmetic mode, see stepper_strict.hip / stepper_fast.hip).
 // host-side row interpolation of the unfused call sequence (likelihood.hip; -ffp-contract=off)
 void interp_rows_any(const void *pl, int elem_bytes, int64_t rows, int64_t ld, const int32_t *hi, const double *dx,
                      const double *h, int64_t n_obs, double *out, int64_t out_ld);
+// The stepper launchers, one per translation unit because each unit has its own -ffp-contract flag (Makefile): what a
+// StepperChoice selects among (launch(), trpl_api.hip).  Inside a unit L, snapshots and bundles pick the instantiation.
+hipError_t launch_stepper_fast(const StepArgs &a, hipStream_t stream);            // one system per wavefront, fp64
 hipError_t launch_stepper_strict(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_fast(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_f32(const StepArgs &a, hipStream_t stream);   // stepper_f32.hip, L >= 128
-hipError_t launch_stepper_mixed(const StepArgs &a, hipStream_t stream);  // stepper_mixed.hip, L >= 128
-hipError_t launch_stepper_hist32(const StepArgs &a, hipStream_t stream); // stepper_hist32.hip, L = 256 / 512
-// stepper_pair.hip: FAST, L = 128, two systems per wavefront
-hipError_t launch_stepper_pair(const StepArgs &a, hipStream_t stream);
-// TRPL_FLAG_PREDICT (stepper_predict_{fast,strict,pair}.hip): the same steppers with the extrapolated start of each step
+hipError_t launch_stepper_pair(const StepArgs &a, hipStream_t stream);            // two systems per wavefront: FAST, L = 128
+hipError_t launch_stepper_f32(const StepArgs &a, hipStream_t stream);             // fp32 state, L >= 128
+// TRPL_FLAG_PREDICT (stepper_predict_{fast,strict,pair}.hip): the fp64 steppers with the extrapolated start of each step
 hipError_t launch_stepper_predict_fast(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_predict_strict(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_pair_predict(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_mixed(const StepArgs &a, hipStream_t stream);           // L >= 128; `make EXPERIMENTAL=1` only: the default
+hipError_t launch_stepper_hist32(const StepArgs &a, hipStream_t stream);          // L = 256 / 512;   library must not reference them
 
 // likelihood.hip
 hipError_t launch_log10_clamp(void *x, int elem_bytes, int64_t rows, int64_t cols, int64_t ld, double mn,

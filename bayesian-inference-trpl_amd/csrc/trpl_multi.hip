@@ -100,11 +100,7 @@ int trpl_loglik_multi(const double *X, int64_t S, int32_t C, const double *lengt
     for (int r = 0; devices && r < n_devices; r++)
         if (devices[r] < 0 || devices[r] >= visible)
             return api_fail(TRPL_ERR_ARG, "devices[%d]=%d out of range (%d visible)", r, devices[r], visible);
-    if (int rc = check_variant_flags(flags, L)) return rc;
-    if (flags & 0xF00u) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_BUNDLE couples neighbouring samples: a sharded batch would depend on where it is cut");
-    for (int c = 0; c < C; c++)
-        if (n_obs[c] < 1 || n_obs[c] > obs_ld)
-            return api_fail(TRPL_ERR_ARG, "n_obs[%d]=%lld out of range (obs_ld %lld)", c, (long long)n_obs[c], (long long)obs_ld);
+    if (int rc = pin_sharded_batch(flags, S, C, L, T, plT, interp, n_obs, obs_ld)) return rc;
     if (interp) {                                    // host data: the same checks as trpl_loglik_obs
         if (plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
         if (int rc = check_brackets(obs_hi, obs_dx, obs_h, C, obs_ld, n_obs, T)) return rc;
@@ -112,9 +108,6 @@ int trpl_loglik_multi(const double *X, int64_t S, int32_t C, const double *lengt
     if (S == 0) return TRPL_OK;
     int prev = 0;
     (void)hipGetDevice(&prev);
-    // ONE kernel variant for the whole logical batch, whatever the shard sizes: a sample's bits then do not
-    // depend on how the batch is cut (the two FAST kernels agree to rounding only)
-    flags = pin_variant(flags, S * (int64_t)C, L, loglik_steps(interp, C, n_obs, plT, T));
 
     std::vector<Shard> sh(n_devices);
     const size_t nobs = (size_t)C * obs_ld;
@@ -413,11 +406,7 @@ int trpl_loglik_multi_dev(trpl_multi_t *h, const double *const *X, int64_t S, in
     const bool interp = obs_hi || obs_dx || obs_h;
     if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
     if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
-    if (int rc = check_variant_flags(flags, L)) return rc;
-    if (flags & 0xF00u) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_BUNDLE couples neighbouring samples: a sharded batch would depend on where it is cut");
-    for (int c = 0; c < C; c++)
-        if (n_obs[c] < 1 || n_obs[c] > obs_ld)
-            return api_fail(TRPL_ERR_ARG, "n_obs[%d]=%lld out of range (obs_ld %lld)", c, (long long)n_obs[c], (long long)obs_ld);
+    if (int rc = pin_sharded_batch(flags, S, C, L, T, plT, interp, n_obs, obs_ld)) return rc;
     if (S == 0) return TRPL_OK;
     const int n = h->n;
     for (int r = 0; r < n; r++)                          // every rank receives the gathered vector, also one whose shard is empty
@@ -426,7 +415,6 @@ int trpl_loglik_multi_dev(trpl_multi_t *h, const double *const *X, int64_t S, in
     const RcclApi *api = rccl_api();
     int prev = 0;
     (void)hipGetDevice(&prev);
-    flags = pin_variant(flags, S * (int64_t)C, L, loglik_steps(interp, C, n_obs, plT, T));     // see trpl_loglik_multi
 
     int rc = [&]() -> int {
         if (widest > h->cap) {                       // scratch for the padded exchange, grown on demand

@@ -363,22 +363,23 @@ def test_kernel_name_refuses_what_a_launch_refuses(trpl):
     """trpl_kernel_name runs the flag / shape checks of a launch (csrc/trpl_api.hip check_launch): it returns a name exactly
     for the combinations a launch accepts, and every name it returns is an instantiation the library contains (the mangled
     kernel symbols of the shared object are the instantiation list).  bench.py attaches rocprof statistics by that name, so a
-    name without a kernel would silently attach nothing."""
+    name without a kernel would silently attach nothing.  On every accepted combination the name and trpl_kernel_variant's
+    code describe the same kernel (both are read off one classification, csrc/trpl_api.hip classify_stepper)."""
     import itertools
     import subprocess
     A = trpl._abi
     nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
     filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
-    have = set(re.findall(r"(trpl::(?:pair::|f32::)?stepper(?:_pair)?_kernel<[^>]*>)", filt))
+    have = set(re.findall(r"(trpl::(?:predict::)?(?:pair::|f32::)?stepper(?:_pair)?_kernel<[^>]*>)", filt))
     assert len(have) >= 40, len(have)
     exp = A.has_experimental()
     named = refused = 0
     arith = [0, A.FLAG_STRICT, A.FLAG_FP32, A.FLAG_FP32 | A.FLAG_FP32_LONG, A.FLAG_MIXED, A.FLAG_HIST32, A.FLAG_STRICT | A.FLAG_FP32,
              A.FLAG_MIXED | A.FLAG_HIST32]
-    for L, ar, kern, bundle, snap, steps in itertools.product(
+    for L, ar, kern, bundle, snap, steps, predict, seam in itertools.product(
             (2, 4, 64, 128, 256, 512, 1024, 96), arith, (0, A.FLAG_KERNEL_PAIR, A.FLAG_KERNEL_SINGLE, A.FLAG_KERNEL_PAIR | A.FLAG_KERNEL_SINGLE),
-            (1, 2, 4, 5, 16), (False, True), (100, 8000)):
-        flags = ar | kern | (((bundle - 1) & 0xF) << 8)
+            (1, 2, 4, 5, 16), (False, True), (100, 8000), (0, A.FLAG_PREDICT), (0, A.FLAG_PAIR_ALWAYS_SEAM)):
+        flags = ar | kern | (((bundle - 1) & 0xF) << 8) | predict | seam
         # what a launch accepts, restated from include/trpl.h's flag paragraphs
         ok = L in (4, 8, 16, 32, 64, 128, 256, 512) and kern != (A.FLAG_KERNEL_PAIR | A.FLAG_KERNEL_SINGLE)
         fp32, strict, mixed, hist = bool(ar & A.FLAG_FP32), bool(ar & A.FLAG_STRICT), bool(ar & A.FLAG_MIXED), bool(ar & A.FLAG_HIST32)
@@ -389,6 +390,7 @@ def test_kernel_name_refuses_what_a_launch_refuses(trpl):
         ok &= not (mixed and (strict or fp32 or L < 128))
         ok &= not (fp32 and (strict or L < 128 or (steps > A.FP32_MAX_STEPS and not ar & A.FLAG_FP32_LONG)))
         ok &= not (bundle > 1 and (fp32 or mixed or kern == A.FLAG_KERNEL_PAIR or bundle > A.bundle_cap(L) or (not strict and L > 128)))
+        ok &= not (predict and (fp32 or mixed or hist or bundle > 1))
         try:
             name = A.kernel_name(10 ** 6, L, steps, flags, snapshots=snap)
         except A.TrplError as e:
@@ -398,6 +400,22 @@ def test_kernel_name_refuses_what_a_launch_refuses(trpl):
             continue
         assert ok, (L, hex(flags), snap, steps, name)
         assert name in have, (name, L, hex(flags), snap, steps)
+        # the variant code and the name say the same: family, arithmetic mode (the one-system kernel's template arguments
+        # are <L, strict, snap, mixed, bundled, hist32>), and the predict namespace exactly with TRPL_FLAG_PREDICT
+        variant = A.lib().trpl_kernel_variant(10 ** 6, L, steps, flags)
+        targs = name[name.index("<") + 1:-1].split(", ")
+        one = "stepper_kernel<" in name and "f32::" not in name
+        assert (variant == A.KERNEL_FAST_PAIR) == ("stepper_pair_kernel" in name), (name, variant, hex(flags))
+        assert (variant == A.KERNEL_FP32) == ("f32::" in name) == fp32, (name, variant, hex(flags))
+        assert (variant == A.KERNEL_STRICT) == (one and targs[1] == "true") == strict, (name, variant, hex(flags))
+        assert (variant == A.KERNEL_MIXED) == (one and targs[3] == "true") == mixed, (name, variant, hex(flags))
+        assert (variant == A.KERNEL_HIST32) == (one and targs[5] == "true") == hist, (name, variant, hex(flags))
+        assert (variant == A.KERNEL_FAST) == (one and [targs[1], targs[3], targs[5]] == ["false"] * 3), (name, variant, hex(flags))
+        assert ("predict::" in name) == bool(predict), (name, hex(flags))
+        if one:
+            assert targs[0] == str(L) and targs[2] == str(snap).lower() and targs[4] == str(bundle > 1).lower(), (name, hex(flags))
+        elif variant == A.KERNEL_FAST_PAIR:
+            assert L == 128 and targs[1] == str(snap).lower() and not (seam and targs[2] == "true"), (name, hex(flags))
         named += 1
     assert named > 100 and refused > 1000, (named, refused)
 
