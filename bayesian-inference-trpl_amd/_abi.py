@@ -20,6 +20,9 @@ FLAG_FP32_LONG, FP32_MAX_STEPS = 0x1000, 256
 FLAG_HIST32 = 0x2000
 FLAG_PAIR_ALWAYS_SEAM, FLAG_PAIR_ADJACENT, FLAG_MULTI_FORCE_PAD = 0x20000, 0x40000, 0x80000   # tests / measurements
 FLAG_PREDICT = 0x100000    # opt-in: extrapolated start of every time step's iteration (include/trpl.h)
+FLAG_MOMENTS = 0x200000    # set by trpl_loglik_moments[_dev] themselves (esum beside sse); trpl_kernel_name accepts it
+MAG_PER_CURVE = 0x1        # trpl_mag_profile: one best offset per curve instead of one per sample
+MAG_MAX_CURVES = 64        # TRPL_MAG_MAX_CURVES
 MULTI_ALLOW_DUPLICATE_DEVICES = 0x1     # trpl_multi_create_ex
 
 
@@ -105,6 +108,16 @@ SIGNATURES = {
                             _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "trpl_interp_rows": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64],
     "trpl_loglik_from_pl_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _u32, _vp],
+    "trpl_loglik_moments": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
+                            _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _pd],
+    "trpl_loglik_moments_dev": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
+    "trpl_loglik_moments_from_pl_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                        _u32, _vp],
+    "trpl_mag_grid": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp],
+    "trpl_mag_grid_dev": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp],
+    "trpl_mag_profile": [_vp, _vp, _vp, _i64, _i32, _u32, _vp, _vp],
+    "trpl_mag_profile_dev": [_vp, _vp, _vp, _i64, _i32, _u32, _vp, _vp, _vp],
     "trpl_loglik_multi": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64,
                           _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _i32, _pd],
     "trpl_multi_create": [_vp, _i32, _vp],

@@ -210,20 +210,22 @@ __device__ __forceinline__ double log_pl(T v, T v0, bool normalize, bool f32_sta
     return log10(d);
 }
 
-template <typename T>
+// MOM (trpl_loglik_moments_from_pl_dev): the sum of the errors beside the sum of their squares, in its own instantiation --
+// the MOM = false kernels are the code they were before the moments existed
+template <typename T, bool MOM>
 __global__ void __launch_bounds__(256) pl_loglik_kernel(const T *pl, int64_t rows, int64_t ld, const double *obs,
                                                         const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
                                                         int64_t n_obs, const double *mag, const int32_t *status,
-                                                        double *P, double *sse_out, uint32_t flags)
+                                                        double *P, double *sse_out, uint32_t flags, double *esum_out)
 {
-    __shared__ double part[4];
+    __shared__ double part[4], part1[MOM ? 4 : 1];
     const int lane = threadIdx.x & 63;
     const int64_t row = blockIdx.x;
     const T *r = pl + row * ld;
     const bool normalize = (flags & 0x4u) != 0, f32 = (flags & 0x2u) != 0 || sizeof(T) == 4;
     const T v0 = r[0];
     const double m = mag[row];
-    double acc = 0.0;
+    double acc = 0.0, acc1 = 0.0;                // acc1: sum of the errors (esum_out, trpl_loglik_moments_from_pl_dev)
     for (int64_t i = threadIdx.x; i < n_obs; i += 256) {
         double y;
         if (obs_hi) {
@@ -237,15 +239,22 @@ __global__ void __launch_bounds__(256) pl_loglik_kernel(const T *pl, int64_t row
         double err = y + m;
         err -= obs[i];
         acc += err * err;
+        if constexpr (MOM) acc1 += err;
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (lane == 0) part[threadIdx.x >> 6] = acc;
+    if constexpr (MOM) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc1 += __shfl_xor(acc1, off, 64);
+    }
+    if (lane == 0) { part[threadIdx.x >> 6] = acc; if constexpr (MOM) part1[threadIdx.x >> 6] = acc1; }
     __syncthreads();
     if (threadIdx.x == 0) {
         acc = ((part[0] + part[1]) + part[2]) + part[3];
+        if constexpr (MOM) acc1 = ((part1[0] + part1[1]) + part1[2]) + part1[3];
         // a system flagged non-converged (its PL is NaN from that step on) scores +inf, like the fused path
-        if ((status && status[row] != 0) || !(acc == acc)) acc = INFINITY;
+        if ((status && status[row] != 0) || !(acc == acc)) { acc = INFINITY; acc1 = NAN; }
+        if constexpr (MOM) { if (esum_out) esum_out[row] = acc1; }
         if (sse_out) sse_out[row] = acc;
         if (P) P[row] -= acc;                                   // probs.py:44,:60
     }
@@ -254,16 +263,143 @@ __global__ void __launch_bounds__(256) pl_loglik_kernel(const T *pl, int64_t row
 hipError_t launch_pl_loglik(const void *pl, int elem_bytes, int64_t rows, int64_t ld, const double *obs,
                             const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t n_obs,
                             const double *mag, const int32_t *status, double *P, double *sse_out, uint32_t flags,
-                            hipStream_t stream)
+                            hipStream_t stream, double *esum_out)
 {
     if (rows <= 0) return hipSuccess;
     const dim3 grid((unsigned)rows), block(256);
-    if (elem_bytes == 4)
-        hipLaunchKernelGGL(pl_loglik_kernel<float>, grid, block, 0, stream, (const float *)pl, rows, ld, obs, obs_hi, obs_dx,
-                           obs_h, n_obs, mag, status, P, sse_out, flags);
-    else
-        hipLaunchKernelGGL(pl_loglik_kernel<double>, grid, block, 0, stream, (const double *)pl, rows, ld, obs, obs_hi, obs_dx,
-                           obs_h, n_obs, mag, status, P, sse_out, flags);
+#define TRPL_PLL(TT, MM)                                                                                                  \
+    hipLaunchKernelGGL((pl_loglik_kernel<TT, MM>), grid, block, 0, stream, (const TT *)pl, rows, ld, obs, obs_hi, obs_dx, obs_h, \
+                       n_obs, mag, status, P, sse_out, flags, esum_out)
+    if (elem_bytes == 4) { if (esum_out) TRPL_PLL(float, true); else TRPL_PLL(float, false); }
+    else                 { if (esum_out) TRPL_PLL(double, true); else TRPL_PLL(double, false); }
+#undef TRPL_PLL
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The mag_grid loop of the reference's older likelihood (probs.lnP, probs.py:5-18) from the two moments the
+// TRPL_FLAG_MOMENTS steppers emit: sum_i (e_i + d)^2 = sse + 2 d esum + n d^2.  ONE expression, compiled for the host and
+// for the device in this translation unit (-ffp-contract=off: no fused multiply-add on either side, IEEE divide), so
+// that the plain host forms and the kernels agree bit for bit.
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ inline double mag_term(double sse, double esum, double n, double d)
+{
+    const double t1 = (2.0 * d) * esum;
+    const double t2 = n * (d * d);
+    const double v = (sse + t1) + t2;
+    if (!(sse < INFINITY) || !(esum - esum == 0.0) || !(v == v)) return INFINITY;       // a flagged system, or NaN / inf moments
+    return v < 0.0 ? 0.0 : v;
+}
+
+// P[m][s] -= sum_c mag_term(.., offsets[m]), curves in order
+__host__ __device__ inline void mag_grid_one(const double *sse, const double *esum, const double *n, int64_t S, int C, int64_t s,
+                                             double d, double *P)
+{
+    double acc = 0.0;
+    for (int c = 0; c < C; c++) acc += mag_term(sse[(int64_t)c * S + s], esum[(int64_t)c * S + s], n[c], d);
+    *P = *P - acc;
+}
+
+__host__ __device__ inline void mag_profile_one(const double *sse, const double *esum, const double *n, int64_t S, int C, int64_t s,
+                                                bool per_curve, double *best, double *P)
+{
+    double acc = 0.0;
+    if (per_curve) {
+        for (int c = 0; c < C; c++) {
+            const double e = esum[(int64_t)c * S + s];
+            const double d = (0.0 - e) / n[c];
+            best[(int64_t)c * S + s] = (e - e == 0.0 && sse[(int64_t)c * S + s] < INFINITY) ? d : NAN;
+            acc += mag_term(sse[(int64_t)c * S + s], e, n[c], d);
+        }
+    } else {
+        double E = 0.0, N = 0.0;
+        bool ok = true;
+        for (int c = 0; c < C; c++) { E += esum[(int64_t)c * S + s]; N += n[c]; ok = ok && sse[(int64_t)c * S + s] < INFINITY; }
+        const double d = (0.0 - E) / N;
+        best[s] = (ok && E - E == 0.0) ? d : NAN;
+        for (int c = 0; c < C; c++) acc += mag_term(sse[(int64_t)c * S + s], esum[(int64_t)c * S + s], n[c], d);
+    }
+    *P = *P - acc;
+}
+
+void mag_grid_host(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, const double *offsets,
+                   int64_t M, double *P)
+{
+    double n[kMagMaxCurves];
+    for (int c = 0; c < C; c++) n[c] = (double)n_obs[c];
+    for (int64_t m = 0; m < M; m++)
+        for (int64_t s = 0; s < S; s++) mag_grid_one(sse, esum, n, S, C, s, offsets[m], P + m * S + s);
+}
+
+void mag_profile_host(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, bool per_curve,
+                      double *best, double *P)
+{
+    double n[kMagMaxCurves];
+    for (int c = 0; c < C; c++) n[c] = (double)n_obs[c];
+    for (int64_t s = 0; s < S; s++) mag_profile_one(sse, esum, n, S, C, s, per_curve, best, P + s);
+}
+
+struct MagArgs {
+    double n[kMagMaxCurves];
+    double d[kMagChunk];
+};
+
+// One thread per sample; a wavefront's accesses to every array are contiguous.  The curves are the OUTER loop over kMagAcc
+// offsets at a time, their sums in registers: a sample's 2 C moments are loaded once per kMagAcc offsets (2 C S 8 B per
+// 32 offsets against 32 S 16 B of P traffic) and every P[m][s] sees its curves in order, as mag_grid_one adds them.
+constexpr int kMagAcc = 32;
+__global__ void __launch_bounds__(256) mag_grid_kernel(const double *sse, const double *esum, int64_t S, int C, int M,
+                                                       double *P, const MagArgs g)
+{
+    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < S; s += (int64_t)gridDim.x * blockDim.x)
+        for (int m0 = 0; m0 < M; m0 += kMagAcc) {
+            double acc[kMagAcc];
+#pragma unroll
+            for (int k = 0; k < kMagAcc; k++) acc[k] = 0.0;
+            for (int c = 0; c < C; c++) {
+                const double q2 = sse[(int64_t)c * S + s], q1 = esum[(int64_t)c * S + s], n = g.n[c];
+#pragma unroll
+                for (int k = 0; k < kMagAcc; k++) acc[k] += mag_term(q2, q1, n, g.d[m0 + k < M ? m0 + k : M - 1]);
+            }
+#pragma unroll
+            for (int k = 0; k < kMagAcc; k++)
+                if (m0 + k < M) { double *p = P + (int64_t)(m0 + k) * S + s; *p = *p - acc[k]; }
+        }
+}
+
+__global__ void __launch_bounds__(256) mag_profile_kernel(const double *sse, const double *esum, int64_t S, int C, int per_curve,
+                                                          double *best, double *P, const MagArgs g)
+{
+    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < S; s += (int64_t)gridDim.x * blockDim.x)
+        mag_profile_one(sse, esum, g.n, S, C, s, per_curve != 0, best, P + s);
+}
+
+hipError_t launch_mag_grid(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C,
+                           const double *offsets, int64_t M, double *P, hipStream_t stream)
+{
+    if (S <= 0 || M <= 0) return hipSuccess;
+    MagArgs g = {};
+    for (int c = 0; c < C; c++) g.n[c] = (double)n_obs[c];
+    int64_t blocks = (S + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    for (int64_t m0 = 0; m0 < M; m0 += kMagChunk) {          // offsets travel as kernel arguments, kMagChunk per launch
+        const int mc = (int)(M - m0 < kMagChunk ? M - m0 : kMagChunk);
+        for (int m = 0; m < mc; m++) g.d[m] = offsets[m0 + m];
+        hipLaunchKernelGGL(mag_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, sse, esum, S, C, mc, P + m0 * S, g);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_mag_profile(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, bool per_curve,
+                              double *best, double *P, hipStream_t stream)
+{
+    if (S <= 0) return hipSuccess;
+    MagArgs g = {};
+    for (int c = 0; c < C; c++) g.n[c] = (double)n_obs[c];
+    int64_t blocks = (S + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(mag_profile_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, sse, esum, S, C, per_curve ? 1 : 0,
+                       best, P, g);
     return hipGetLastError();
 }
 

@@ -31,12 +31,25 @@
 #ifndef TRPL_STEPPER_PREDICT
 #define TRPL_STEPPER_PREDICT 0
 #endif
-#if TRPL_STEPPER_PREDICT
-#define TRPL_PREDICT_NS_BEGIN namespace predict {
-#define TRPL_PREDICT_NS_END }
+// TRPL_FLAG_MOMENTS (include/trpl.h) is built the same way: a unit that defines TRPL_STEPPER_MOMENTS=1 (stepper_moments_*.hip)
+// gets the steppers whose likelihood sink also emits esum = sum e_i beside sse = sum e_i^2 (PlSinkT<true>), as namespace
+// trpl::moments -- outside predict, so the kernels are trpl::moments::[predict::][pair::]stepper...  Everywhere else the sink is
+// PlSinkT<false>, whose moments code is discarded at compile time.
+#ifndef TRPL_STEPPER_MOMENTS
+#define TRPL_STEPPER_MOMENTS 0
+#endif
+#if TRPL_STEPPER_MOMENTS && TRPL_STEPPER_PREDICT
+#define TRPL_VARIANT_NS_BEGIN namespace moments { namespace predict {
+#define TRPL_VARIANT_NS_END } }
+#elif TRPL_STEPPER_MOMENTS
+#define TRPL_VARIANT_NS_BEGIN namespace moments {
+#define TRPL_VARIANT_NS_END }
+#elif TRPL_STEPPER_PREDICT
+#define TRPL_VARIANT_NS_BEGIN namespace predict {
+#define TRPL_VARIANT_NS_END }
 #else
-#define TRPL_PREDICT_NS_BEGIN
-#define TRPL_PREDICT_NS_END
+#define TRPL_VARIANT_NS_BEGIN
+#define TRPL_VARIANT_NS_END
 #endif
 
 namespace trpl {
@@ -200,7 +213,14 @@ __device__ __forceinline__ bool correct_mixed(const double (&lo)[NR], const doub
 // What a system emits: PL(t) to memory (pvSim mode, pvSimPCR.py:281,:393) and/or the running squared
 // log-error against the observations (fused likelihood: bayeslib.py:150-157,:184-191, probs.py:29-44).
 // Shared by the fp64 and fp32 steppers; every member is wave-uniform.
-struct PlSink {
+// MOMENTS (TRPL_FLAG_MOMENTS): esum = sum err runs beside sse = sum err^2, over the same err values, in the same order and
+// association (serial in emit(), one more wave reduction per batch in flush_batch()).  The sums are wave-uniform and touched
+// once per 64 columns: between batches the batched path parks them in scalar registers (uniform_d after each add) or, PARK,
+// in two LDS words the kernel provides -- the paired kernel has neither a vector nor a scalar register to spare (253 of 256
+// VGPRs, 75 spilled SGPRs), and with both of its running sums in LDS it needs fewer registers than its counterpart.
+template <bool MOMENTS, bool PARK = false>
+struct PlSinkT {
+    static_assert(MOMENTS || !PARK, "only the moments sink parks its sums in LDS");
     const StepArgs &a;
     const CurveConst &cc;
     int64_t orow;            // output row (curve-major: c*S + s)
@@ -213,6 +233,27 @@ struct PlSink {
     int32_t t_last;          // last step that can influence an output
     int32_t next_obs = 0;
     double mag, lg_prev = 0.0, sse = 0.0, pl0_d = 1.0;
+    double esum = 0.0;       // MOMENTS only
+    // PARK only: {sse, esum, pl_floor} of this system in LDS (set_park).  An LDS-qualified pointer: the accesses are DS
+    // instructions on a 32-bit constant address (as a generic pointer it was a 64-bit value the allocator spilled)
+    typedef volatile __attribute__((address_space(3))) double lds_double;
+    lds_double *park = nullptr;
+    __device__ __forceinline__ void set_park(double *three)
+    {
+        park = (lds_double *)three;
+        if (lane_ == 0) { park[0] = 0.0; park[1] = 0.0; }
+    }
+    // the sums of one batch's err^2 and err (wave-uniform) join the running sums
+    __device__ __forceinline__ void add_batch(double q2, double q1)
+    {
+        if constexpr (PARK) {
+            const double s2 = park[0] + q2, s1 = park[1] + q1;         // one wavefront: its LDS accesses are in program order
+            if (lane_ == 0) { park[0] = s2; park[1] = s1; }
+        } else {
+            sse = uniform_d(sse + q2);                                  // the same bits, held in scalar registers
+            esum = uniform_d(esum + q1);
+        }
+    }
     float pl0_f = 1.0f;
     bool want_pl, want_ll, interp;
     // batched emission (FAST): lane k parks column base+k; a batch of up to 64 columns is processed at once
@@ -223,11 +264,17 @@ struct PlSink {
     // ~1e-12 by which two correct fp64 evaluations of the state differ is then amplified to >= 1e-8 of PL
     double pl_floor = 0.0;                   // set_floor(); 0: only a non-positive PL counts
     int32_t first_floor = -1;
-    __device__ __forceinline__ void set_floor(double rate, double n0p0, int L) { pl_floor = kPlFloorExcess * (rate * ((double)L * n0p0)); }
+    __device__ __forceinline__ void set_floor(double rate, double n0p0, int L)
+    {
+        const double f = kPlFloorExcess * (rate * ((double)L * n0p0));
+        if constexpr (PARK) { if (lane_ == 0) park[2] = f; }      // read once per batch: parked with the sums (after set_park)
+        else pl_floor = f;
+    }
+    __device__ __forceinline__ double floor_level() const { if constexpr (PARK) return park[2]; else return pl_floor; }
 
     int lane_;               // lane within the wavefront (== threadIdx.x except in the multi-wave bundled kernel)
 
-    __device__ PlSink(const StepArgs &a_, const CurveConst &cc_, int c, int64_t s, double mag_, int lane = (int)threadIdx.x)
+    __device__ PlSinkT(const StepArgs &a_, const CurveConst &cc_, int c, int64_t s, double mag_, int lane = (int)threadIdx.x)
         : a(a_), cc(cc_), orow((int64_t)c * a_.S + s), mag(mag_), lane_(lane)
     {
         want_pl = a.pl != nullptr;
@@ -250,7 +297,8 @@ struct PlSink {
     // PL columns instead of dividing t by plT every step (a 64-bit scalar division is ~130 instructions).
     __device__ __forceinline__ void emit(int32_t col, double plv)
     {
-        if (a.floor_col && (interp || col < ncol_ll) && first_floor < 0 && !(plv >= pl_floor)) first_floor = (int32_t)col;
+        static_assert(!PARK, "emit() accumulates in the members: a parked sink (sums in LDS) emits through push() / flush_batch() only");
+        if (a.floor_col && (interp || col < ncol_ll) && first_floor < 0 && !(plv >= floor_level())) first_floor = (int32_t)col;
         if (want_pl && lane_ == 0) {                                                   // :281,:393
             if (a.pl_bytes == 4) ((float *)a.pl)[orow * a.pl_ld + col] = (float)plv / (float)cc.plnorm;
             else                 ((double *)a.pl)[orow * a.pl_ld + col] = plv / cc.plnorm;
@@ -272,6 +320,7 @@ struct PlSink {
             double err = lg + mag;
             err -= obs[col];
             sse += err * err;
+            if constexpr (MOMENTS) esum += err;
         } else {
             // every observation bracketed by grid points (col-1, col): scipy interp1d's
             // slope * (x - x_lo) + y_lo (bayeslib.py:189)
@@ -281,6 +330,7 @@ struct PlSink {
                 double err = y + mag;
                 err -= obs[next_obs];
                 sse += err * err;
+                if constexpr (MOMENTS) esum += err;
                 next_obs++;
             }
             lg_prev = lg;
@@ -317,7 +367,7 @@ struct PlSink {
                 else                 ((double *)a.pl)[orow * a.pl_ld + col] = pend / cc.plnorm;
             }
             if (a.floor_col && (interp || base < ncol_ll) && first_floor < 0) {
-                const uint64_t below = __builtin_amdgcn_ballot_w64(live && (interp || col < ncol_ll) && !(pend >= pl_floor));
+                const uint64_t below = __builtin_amdgcn_ballot_w64(live && (interp || col < ncol_ll) && !(pend >= floor_level()));
                 if (below) first_floor = (int32_t)(base + __builtin_ctzll(below));
             }
             if (interp || base < ncol_ll) {                 // bayeslib.py:150-157, probs.py:29-44
@@ -337,7 +387,11 @@ struct PlSink {
                     const bool use = live && col < ncol_ll;
                     double err = lg + mag;
                     err -= obs[use ? col : 0];
-                    sse += wave_sum(use ? err * err : 0.0);
+                    if constexpr (MOMENTS) {
+                        add_batch(wave_sum(use ? err * err : 0.0), wave_sum(use ? err : 0.0));
+                    } else {
+                        sse += wave_sum(use ? err * err : 0.0);
+                    }
                 } else {
                     // Off-grid observation times (trpl_loglik_obs; bayeslib.py:184-191): observation i is bracketed by the grid
                     // columns (hi_i - 1, hi_i).  The observations whose upper column lies in this batch are taken 64 at a
@@ -361,7 +415,11 @@ struct PlSink {
                         const double h = mine ? obs_h[idx] : 1.0, dx = mine ? obs_dx[idx] : 0.0;
                         double err = ((dy / h) * dx + y_lo) + mag;
                         err -= obs[mine ? idx : 0];
-                        sse += wave_sum(mine ? err * err : 0.0);
+                        if constexpr (MOMENTS) {
+                            add_batch(wave_sum(mine ? err * err : 0.0), wave_sum(mine ? err : 0.0));
+                        } else {
+                            sse += wave_sum(mine ? err * err : 0.0);
+                        }
                         const int cnt = __builtin_popcountll(m);
                         next_obs += cnt;
                         if (cnt < 64) break;                                    // the next observation's bracket ends beyond this batch
@@ -386,7 +444,12 @@ struct PlSink {
                     else                 ((double *)a.pl)[orow * a.pl_ld + col] = __builtin_nan("");
                 }
         }
-        if (want_ll) a.sse[orow] = status ? __builtin_inf() : sse;
+        if constexpr (PARK) {
+            if (want_ll) { a.sse[orow] = status ? __builtin_inf() : park[0]; a.esum[orow] = status ? __builtin_nan("") : park[1]; }
+        } else {
+            if (want_ll) a.sse[orow] = status ? __builtin_inf() : sse;
+            if constexpr (MOMENTS) { if (want_ll) a.esum[orow] = status ? __builtin_nan("") : esum; }
+        }
         if (a.status) a.status[orow] = status;
         if (a.iters_total) a.iters_total[orow] = itot;
         if (a.floor_col) a.floor_col[orow] = status ? -2 : first_floor;      // a flagged system: sse = +inf, no column to report
@@ -652,7 +715,7 @@ __device__ __forceinline__ void update_field(const MatPar &m, double a0, const d
 // differences are read from a 3-slot fp32 ring (d_m in slot m mod 3, each rounded ONCE, when it is stored).  All three
 // fields live in LDS: 20 B per node and field instead of 32 B (N, P) / 16 registers (E).  State, assembly, solves,
 // residuals and PL stay fp64.  What it buys and what it costs: DESIGN.md section 8 (round 4).
-TRPL_PREDICT_NS_BEGIN
+TRPL_VARIANT_NS_BEGIN
 template <int L, bool STRICT, bool SNAP = false, bool MIXED = false, bool BUNDLE = false, bool HIST32 = false>
 __global__ void __launch_bounds__(BUNDLE ? 64 * bundle_cap(L) : 64, BUNDLE ? 1 : ((STRICT || L > 128) ? (L > 256 ? 1 : 2) : 3))
 stepper_kernel(const StepArgs a)
@@ -665,6 +728,8 @@ stepper_kernel(const StepArgs a)
     static_assert(!BUNDLE || (!MIXED && (STRICT || L <= 128)), "bundles: STRICT at any L, FAST up to L = 128 (LDS: one history ring per system)");
     // TRPL_FLAG_PREDICT: each step's iteration starts from predict_start() of the history instead of U^t
     constexpr bool PREDICT = TRPL_STEPPER_PREDICT != 0;
+    constexpr bool MOMENTS = TRPL_STEPPER_MOMENTS != 0;       // TRPL_FLAG_MOMENTS: the sink emits esum beside sse
+    static_assert(!MOMENTS || (!SNAP && !MIXED && !BUNDLE && !HIST32), "the moments sink exists for the plain fp64 one-system stepper, likelihood mode");
     static_assert(!PREDICT || (!MIXED && !BUNDLE && !HIST32), "the extrapolated start exists for the plain fp64 one-system stepper");
     const int wv = BUNDLE ? (int)(threadIdx.x >> 6) : 0;                 // which system of the bundle
     const int lane64 = BUNDLE ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
@@ -745,7 +810,7 @@ stepper_kernel(const StepArgs a)
         }
     }
 
-    PlSink sink(a, cc, c, s, mag, lane64);
+    PlSinkT<MOMENTS> sink(a, cc, c, s, mag, lane64);
     sink.set_floor(rate, n0p0, L);
     if constexpr (BUNDLE) { if (!valid) sink.mute(); }
     SnapSink snap(a, cc);
@@ -967,6 +1032,26 @@ stepper_kernel(const StepArgs a)
     if (valid) sink.finish(status, itot);
 }
 
+#if TRPL_STEPPER_MOMENTS
+// TRPL_FLAG_MOMENTS: likelihood mode only -- one instantiation per L, no bundles, no snapshot / resume forms (check_launch)
+template <bool STRICT>
+hipError_t launch_stepper(const StepArgs &a, hipStream_t stream)
+{
+    const int64_t nsys = a.S * a.C;
+    if (nsys <= 0) return hipSuccess;
+    if (a.bundle > 1 || a.n_snap > 0 || a.resN != nullptr || !a.sse || !a.esum) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)nsys), block(64);
+    switch (a.L) {
+#define TRPL_CASE(LL) \
+    case LL: hipLaunchKernelGGL((stepper_kernel<LL, STRICT, false>), grid, block, 0, stream, a); break;
+        TRPL_CASE(4) TRPL_CASE(8) TRPL_CASE(16) TRPL_CASE(32) TRPL_CASE(64) TRPL_CASE(128)
+        TRPL_CASE(256) TRPL_CASE(512)
+#undef TRPL_CASE
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+#else
 template <bool STRICT>
 hipError_t launch_stepper(const StepArgs &a, hipStream_t stream)
 {
@@ -1014,6 +1099,7 @@ hipError_t launch_stepper(const StepArgs &a, hipStream_t stream)
     }
     return hipGetLastError();
 }
-TRPL_PREDICT_NS_END
+#endif
+TRPL_VARIANT_NS_END
 
 }  // namespace trpl

@@ -31,7 +31,7 @@
 #include "stepper_impl.hpp"
 
 namespace trpl {
-TRPL_PREDICT_NS_BEGIN                                // trpl::predict::pair in a TRPL_STEPPER_PREDICT unit (stepper_impl.hpp)
+TRPL_VARIANT_NS_BEGIN                                // trpl::[moments::][predict::]pair by the unit's switches (stepper_impl.hpp)
 namespace pair {
 
 constexpr int L = 128;      // nodes per system
@@ -195,7 +195,8 @@ __global__ void __launch_bounds__(64, 2) stepper_pair_kernel(const StepArgs a)
     // ring layout [slot][row][lane]{N, P}: a lane's N and P of one row and level are one ds_read_b128 / ds_write_b128
     // (20 DS instructions per time step instead of 40); the field history hE[m] = E^{t-1-m} stays in registers
     constexpr int HSLOT = 2 * NR * 64;
-    __shared__ __attribute__((aligned(16))) double lds[4 * HSLOT];
+    constexpr bool MOMENTS = TRPL_STEPPER_MOMENTS != 0;    // TRPL_FLAG_MOMENTS: {sse, esum, pl_floor} of both systems in six more LDS words
+    __shared__ __attribute__((aligned(16))) double lds[4 * HSLOT + (MOMENTS ? 6 : 0)];
     double2 *hist2 = reinterpret_cast<double2 *>(lds);            // hist2[(slot * NR + row) * 64 + lane] = {N, P}
     double *xch = nullptr;                          // the solver's exchanges are DPP moves and ds_swizzle rotates: no buffer
     double Nk[NR], Pk[NR], Ek[NR], hE[4][NR];
@@ -214,9 +215,10 @@ __global__ void __launch_bounds__(64, 2) stepper_pair_kernel(const StepArgs a)
         }
     }
 
-    PlSink sinkA(a, cc, cA, sA, lane_value(mag, 0));
-    PlSink sinkB(a, cc, cB, sB, lane_value(mag, WS));      // same n_obs and plnorm as cA's by construction of the table
+    PlSinkT<MOMENTS, MOMENTS> sinkA(a, cc, cA, sA, lane_value(mag, 0));
+    PlSinkT<MOMENTS, MOMENTS> sinkB(a, cc, cB, sB, lane_value(mag, WS));      // same n_obs and plnorm as cA's by construction of the table
     const double rateA = lane_value(rate, 0), rateB = lane_value(rate, WS);
+    if constexpr (MOMENTS) { sinkA.set_park(lds + 4 * HSLOT); sinkB.set_park(lds + 4 * HSLOT + 3); }
     sinkA.set_floor(rateA, lane_value(n0p0, 0), L);
     sinkB.set_floor(rateB, lane_value(n0p0, WS), L);
     int statusA = 0, statusB = 0;
@@ -489,6 +491,11 @@ hipError_t launch_stepper_pair_t(const StepArgs &a, hipStream_t stream)
     const bool always_seam = (a.flags & kFlagPairAlwaysSeam) != 0;
     const bool snap = a.n_snap > 0 || a.resN != nullptr;
     const dim3 grid((unsigned)nblk), block(64);
+#if TRPL_STEPPER_MOMENTS                            // likelihood mode only: no snapshot forms (check_launch)
+    if (snap || !a.sse || !a.esum) return hipErrorInvalidValue;
+    if (always_seam) hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false, false>), grid, block, 0, stream, a);
+    else             hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false>), grid, block, 0, stream, a);
+#else
     if (always_seam) {
         if (snap) hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, true, false>), grid, block, 0, stream, a);
         else      hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false, false>), grid, block, 0, stream, a);
@@ -496,8 +503,9 @@ hipError_t launch_stepper_pair_t(const StepArgs &a, hipStream_t stream)
         if (snap) hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, true>), grid, block, 0, stream, a);
         else      hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false>), grid, block, 0, stream, a);
     }
+#endif
     return hipGetLastError();
 }
-TRPL_PREDICT_NS_END
+TRPL_VARIANT_NS_END
 
 }  // namespace trpl

@@ -176,6 +176,7 @@ struct StepperChoice {
     int32_t L, bundle;                               // bundle: m of TRPL_FLAG_BUNDLE(m)
     bool strict, snap, mixed, hist32;                // template arguments of the one-system kernel, with bundle > 1
     bool predict;                                    // the instantiation in namespace trpl::predict
+    bool moments;                                    // TRPL_FLAG_MOMENTS: the instantiation in namespace trpl::moments[::predict]
     bool optimistic;                                 // paired kernel: the optimistic seam (not TRPL_FLAG_PAIR_ALWAYS_SEAM)
 };
 
@@ -189,6 +190,7 @@ StepperChoice classify_stepper(uint32_t flags, int32_t L, int64_t nsys, int64_t 
     StepperChoice c = {StepperChoice::Single, L, flags_bundle(flags)};
     c.snap = snap;
     c.predict = (flags & TRPL_FLAG_PREDICT) != 0;
+    c.moments = (flags & TRPL_FLAG_MOMENTS) != 0;
     c.optimistic = TRPL_PAIR_OPTIMISTIC != 0 && !(flags & TRPL_FLAG_PAIR_ALWAYS_SEAM);
     if (flags & TRPL_FLAG_FP32) c.family = StepperChoice::F32;
     else if (flags & TRPL_FLAG_STRICT) c.strict = true;
@@ -226,6 +228,12 @@ int check_launch(uint32_t flags, int32_t L, int64_t steps, bool snap, bool resum
     if (int rc = check_variant_flags(flags, L)) return rc;
     if (flags_bdf_order(flags) > 5u) return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_BDF_ORDER(%u): the order cap must be 1 .. 5 (0: the reference's ramp)", flags_bdf_order(flags));
     const int32_t bundle = flags_bundle(flags);
+    if (flags & TRPL_FLAG_MOMENTS) {                                        // the moments sink: plain fp64 steppers, likelihood mode
+        if (flags & (TRPL_FLAG_FP32 | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
+            return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_MOMENTS is not built for TRPL_FLAG_FP32, TRPL_FLAG_MIXED or TRPL_FLAG_HIST32");
+        if (bundle > 1) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_MOMENTS is not built for TRPL_FLAG_BUNDLE(m > 1)");
+        if (snap || resume) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_MOMENTS has no snapshot / resume instantiations (likelihood mode only)");
+    }
     if (flags & TRPL_FLAG_PREDICT) {                                        // the extrapolated start: plain fp64 steppers only
         if (flags & (TRPL_FLAG_FP32 | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
             return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_PREDICT excludes TRPL_FLAG_FP32, TRPL_FLAG_MIXED and TRPL_FLAG_HIST32");
@@ -279,6 +287,14 @@ int pin_sharded_batch(uint32_t &flags, int64_t S, int32_t C, int32_t L, int64_t 
     return TRPL_OK;
 }
 
+// TRPL_FLAG_MOMENTS belongs to trpl_loglik_moments[_dev], which set it themselves: the other entry points have no esum output
+int no_moments_flag(uint32_t flags)
+{
+    if (flags & TRPL_FLAG_MOMENTS)
+        return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_MOMENTS is set by trpl_loglik_moments[_dev] only: this entry point has no esum output");
+    return TRPL_OK;
+}
+
 int select_device(int32_t device)
 {
     int n = 0;
@@ -311,6 +327,11 @@ int launch(const trpl::StepArgs &a_in, uint32_t flags, hipStream_t st, int64_t s
 #endif
     else if (c.family == StepperChoice::Pair) { fn = c.predict ? trpl::launch_stepper_pair_predict : trpl::launch_stepper_pair; what = "pair "; }
     else if (c.strict) fn = c.predict ? trpl::launch_stepper_predict_strict : trpl::launch_stepper_strict;
+    if (c.moments) {                                 // check_launch has left the plain fp64 steppers only
+        if (c.family == StepperChoice::Pair) fn = c.predict ? trpl::launch_stepper_moments_predict_pair : trpl::launch_stepper_moments_pair;
+        else if (c.strict) fn = c.predict ? trpl::launch_stepper_moments_predict_strict : trpl::launch_stepper_moments_strict;
+        else fn = c.predict ? trpl::launch_stepper_moments_predict_fast : trpl::launch_stepper_moments_fast;
+    }
     const hipError_t e = fn(a, st);
     if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "%sstepper launch: %s", what, hipGetErrorString(e));
     return TRPL_OK;
@@ -349,7 +370,8 @@ int trpl_kernel_name(int64_t nsys, int32_t L, int64_t steps, uint32_t flags, int
     // (`snapshots` covers snapshots AND resume; the fp32 stepper has one instantiation and accepts a resume)
     if (int rc = check_launch(flags, L, steps, snapshots != 0 && !(flags & TRPL_FLAG_FP32), false)) return rc;
     const StepperChoice c = classify_stepper(flags, L, nsys, steps, snapshots != 0);
-    const char *tf[2] = {"false", "true"}, *ns = c.predict ? "trpl::predict::" : "trpl::";      // stepper_predict_*.hip
+    const char *tf[2] = {"false", "true"};           // stepper_predict_*.hip, stepper_moments_*.hip
+    const char *ns = c.moments ? (c.predict ? "trpl::moments::predict::" : "trpl::moments::") : (c.predict ? "trpl::predict::" : "trpl::");
     int n;
     if (c.family == StepperChoice::F32)
         n = snprintf(buf, (size_t)buflen, "%sf32::stepper_kernel<%d>", ns, c.L);
@@ -397,6 +419,7 @@ static int solve_pl_dev_impl(const double *matpar, int64_t S, double length_nm, 
                              uint32_t flags, void *stream)
 {
     const bool resume = resN || resP || resE;
+    if (int rc = no_moments_flag(flags)) return rc;
     if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
     if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
     if (n_snap < 0 || n_snap > trpl::kMaxSnaps) return api_fail(TRPL_ERR_ARG, "n_snap=%d must be in [0, %d]", n_snap, trpl::kMaxSnaps);
@@ -477,6 +500,7 @@ static int solve_pl_host_impl(const double *matpar, int64_t S, double length_nm,
                               uint32_t flags, int32_t device, double *seconds)
 {
     const bool resume = resN || resP || resE;
+    if (int rc = no_moments_flag(flags)) return rc;
     if (resume && !(resN && resP && resE)) return api_fail(TRPL_ERR_ARG, "resN, resP and resE go together");
     if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
     if (pl_elem_bytes != 4 && pl_elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "pl_elem_bytes must be 4 or 8");
@@ -668,11 +692,12 @@ int trpl_sse_accumulate(double *P, const void *plI, int32_t elem_bytes, int64_t 
 }
 
 /* ------------------------------------------------------------------ loglik from stored PL */
-int trpl_loglik_from_pl_dev(const void *plI, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld,
-                            const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
-                            int64_t n_obs, const double *mag, const int32_t *status, double *P, double *sse,
-                            uint32_t flags, void *stream)
+static int loglik_from_pl_impl(const void *plI, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld,
+                               const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                               int64_t n_obs, const double *mag, const int32_t *status, double *P, double *sse,
+                               double *esum, uint32_t flags, void *stream)
 {
+    if (int rc = no_moments_flag(flags)) return rc;
     if (elem_bytes != 4 && elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "elem_bytes must be 4 or 8");
     if (rows < 0 || ncol < 1 || ld < ncol || n_obs < 0) return api_fail(TRPL_ERR_ARG, "bad shape");
     const bool interp = obs_hi || obs_dx || obs_h;
@@ -680,11 +705,29 @@ int trpl_loglik_from_pl_dev(const void *plI, int32_t elem_bytes, int64_t rows, i
     if (!interp && n_obs > ncol) return api_fail(TRPL_ERR_ARG, "n_obs=%lld exceeds the %lld PL columns", (long long)n_obs, (long long)ncol);
     if (rows > 0x7fffffffLL) return api_fail(TRPL_ERR_ARG, "too many rows for one launch");
     if (rows == 0) return TRPL_OK;
-    if (!plI || !mag || (n_obs && !obs) || (!P && !sse)) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
+    if (!plI || !mag || (n_obs && !obs) || (!P && !sse && !esum)) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
     hipError_t e = trpl::launch_pl_loglik(plI, elem_bytes, rows, ld, obs, obs_hi, obs_dx, obs_h, n_obs, mag, status, P, sse, flags,
-                                          (hipStream_t)stream);
+                                          (hipStream_t)stream, esum);
     if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "pl_loglik launch: %s", hipGetErrorString(e));
     return TRPL_OK;
+}
+
+int trpl_loglik_from_pl_dev(const void *plI, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld,
+                            const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                            int64_t n_obs, const double *mag, const int32_t *status, double *P, double *sse,
+                            uint32_t flags, void *stream)
+{
+    return loglik_from_pl_impl(plI, elem_bytes, rows, ncol, ld, obs, obs_hi, obs_dx, obs_h, n_obs, mag, status, P, sse, nullptr,
+                               flags, stream);
+}
+
+int trpl_loglik_moments_from_pl_dev(const void *plI, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld,
+                                    const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                                    int64_t n_obs, const double *mag, const int32_t *status, double *P, double *sse,
+                                    double *esum, uint32_t flags, void *stream)
+{
+    return loglik_from_pl_impl(plI, elem_bytes, rows, ncol, ld, obs, obs_hi, obs_dx, obs_h, n_obs, mag, status, P, sse, esum,
+                               flags, stream);
 }
 
 /* ------------------------------------------------------------------ fused loglik -------- */
@@ -692,8 +735,11 @@ static int loglik_dev_impl(const double *X, int64_t S, int32_t C, const double *
                            int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
                            const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
                            int64_t obs_ld, const int64_t *n_obs, double *P, double *sse, int32_t *status,
-                           int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream)
+                           int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream, double *esum = nullptr)
 {
+    // esum: the moments entry points (they set TRPL_FLAG_MOMENTS themselves); every other caller must not carry the flag
+    if (esum) flags |= TRPL_FLAG_MOMENTS;
+    else if (int rc = no_moments_flag(flags)) return rc;
     if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
     if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
     if (C < 1 || C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAX_CURVES);
@@ -725,6 +771,7 @@ static int loglik_dev_impl(const double *X, int64_t S, int32_t C, const double *
         a.obs_dx = obs_dx ? obs_dx + (int64_t)c0 * obs_ld : nullptr;
         a.obs_h = obs_h ? obs_h + (int64_t)c0 * obs_ld : nullptr;
         a.obs_ld = obs_ld; a.sse = sse + (int64_t)c0 * S;
+        a.esum = esum ? esum + (int64_t)c0 * S : nullptr;
         a.status = status ? status + (int64_t)c0 * S : nullptr;
         a.iters_total = iters_total ? iters_total + (int64_t)c0 * S : nullptr;
         a.floor_col = floor_col ? floor_col + (int64_t)c0 * S : nullptr;
@@ -765,8 +812,10 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
                             int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
                             const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
                             int64_t obs_ld, const int64_t *n_obs, double *P, double *sse, int32_t *status,
-                            int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device, double *seconds)
+                            int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device, double *seconds,
+                            double *esum = nullptr)
 {
+    if (!esum) { if (int rc = no_moments_flag(flags)) return rc; }
     if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
     if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
     if (C < 1 || C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAX_CURVES);
@@ -781,7 +830,7 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
     if (interp) {                                    // the brackets are host data here: validate them
         if (int rc = check_brackets(obs_hi, obs_dx, obs_h, C, obs_ld, n_obs, T)) return rc;
     }
-    DevBuf dX, ddN, dobs, dhi, ddx, dh, dP, dsse, dst, dit, dfl;
+    DevBuf dX, ddN, dobs, dhi, ddx, dh, dP, dsse, dst, dit, dfl, des;
     const size_t nsys = (size_t)S * C, nobs = (size_t)C * obs_ld;
     HIP_TRY(dX.alloc((size_t)S * 13 * 8, cs.st));
     HIP_TRY(ddN.alloc((size_t)C * L * 8, cs.st));
@@ -791,6 +840,7 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
     HIP_TRY(dst.alloc(nsys * 4, cs.st));
     HIP_TRY(dit.alloc(nsys * 8, cs.st));
     if (floor_col) HIP_TRY(dfl.alloc(nsys * 4, cs.st));
+    if (esum) HIP_TRY(des.alloc(nsys * 8, cs.st));
     HIP_TRY(hipMemcpyAsync(dX.p, X, (size_t)S * 13 * 8, hipMemcpyHostToDevice, cs.st));
     HIP_TRY(hipMemcpyAsync(ddN.p, dN, (size_t)C * L * 8, hipMemcpyHostToDevice, cs.st));
     HIP_TRY(hipMemcpyAsync(dobs.p, obs, nobs * 8, hipMemcpyHostToDevice, cs.st));
@@ -806,12 +856,13 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
                                  ddN.as<double>(), dobs.as<double>(), interp ? dhi.as<int32_t>() : nullptr,
                                  interp ? ddx.as<double>() : nullptr, interp ? dh.as<double>() : nullptr, obs_ld, n_obs,
                                  dP.as<double>(), dsse.as<double>(), dst.as<int32_t>(), dit.as<int64_t>(),
-                                 dfl.as<int32_t>(), flags, cs.st))
+                                 dfl.as<int32_t>(), flags, cs.st, esum ? des.as<double>() : nullptr))
         return rc;
     HIP_TRY(hipStreamSynchronize(cs.st));
     if (seconds) *seconds = now_s() - t0;
     HIP_TRY(hipMemcpyAsync(P, dP.p, (size_t)S * 8, hipMemcpyDeviceToHost, cs.st));
     if (sse) HIP_TRY(hipMemcpyAsync(sse, dsse.p, nsys * 8, hipMemcpyDeviceToHost, cs.st));
+    if (esum) HIP_TRY(hipMemcpyAsync(esum, des.p, nsys * 8, hipMemcpyDeviceToHost, cs.st));
     if (status) HIP_TRY(hipMemcpyAsync(status, dst.p, nsys * 4, hipMemcpyDeviceToHost, cs.st));
     if (iters_total) HIP_TRY(hipMemcpyAsync(iters_total, dit.p, nsys * 8, hipMemcpyDeviceToHost, cs.st));
     if (floor_col) HIP_TRY(hipMemcpyAsync(floor_col, dfl.p, nsys * 4, hipMemcpyDeviceToHost, cs.st));
@@ -839,6 +890,92 @@ int trpl_loglik_obs(const double *X, int64_t S, int32_t C, const double *lengths
     if (!obs_hi || !obs_dx || !obs_h) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h must not be NULL");
     return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, 1, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
                             obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds);
+}
+
+/* ------------------------------------------------------------------ moments + magnitude grid (probs.py:5-18) */
+int trpl_loglik_moments_dev(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
+                            int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN, const double *obs,
+                            const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t obs_ld,
+                            const int64_t *n_obs, double *P, double *sse, double *esum, int32_t *status,
+                            int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream)
+{
+    if (S > 0 && !esum) return api_fail(TRPL_ERR_ARG, "esum must not be NULL");
+    if (S == 0) flags &= ~(uint32_t)TRPL_FLAG_MOMENTS;            // nothing is launched; the common checks still run
+    return loglik_dev_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
+                           obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, stream, esum);
+}
+
+int trpl_loglik_moments(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
+                        int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN, const double *obs,
+                        const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t obs_ld,
+                        const int64_t *n_obs, double *P, double *sse, double *esum, int32_t *status, int64_t *iters_total,
+                        int32_t *floor_col, uint32_t flags, int32_t device, double *seconds)
+{
+    ProfRange range("trpl_loglik_moments (pvSim + fastlog + lnP's mag_grid moments, fused)");
+    if (S > 0 && !esum) return api_fail(TRPL_ERR_ARG, "esum must not be NULL");
+    const bool interp = obs_hi || obs_dx || obs_h;
+    if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
+    if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
+    if (S == 0) flags &= ~(uint32_t)TRPL_FLAG_MOMENTS;
+    return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
+                            obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds, esum);
+}
+
+static int check_mag(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C, const double *P, bool need_P)
+{
+    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
+    if (C < 1 || C > TRPL_MAG_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAG_MAX_CURVES);
+    if (!n_obs) return api_fail(TRPL_ERR_ARG, "n_obs must not be NULL");
+    for (int c = 0; c < C; c++)
+        if (n_obs[c] < 1) return api_fail(TRPL_ERR_ARG, "n_obs[%d]=%lld must be >= 1", c, (long long)n_obs[c]);
+    if (S > 0 && (!sse || !esum || (need_P && !P))) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
+    return TRPL_OK;
+}
+
+int trpl_mag_grid(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C, const double *offsets,
+                  int64_t M, double *P)
+{
+    if (M < 0) return api_fail(TRPL_ERR_ARG, "M must be >= 0");
+    if (int rc = check_mag(sse, esum, n_obs, S, C, P, M > 0)) return rc;
+    if (S == 0 || M == 0) return TRPL_OK;
+    if (!offsets) return api_fail(TRPL_ERR_ARG, "offsets must not be NULL");
+    trpl::mag_grid_host(sse, esum, n_obs, S, C, offsets, M, P);
+    return TRPL_OK;
+}
+
+int trpl_mag_grid_dev(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C, const double *offsets,
+                      int64_t M, double *P, void *stream)
+{
+    if (M < 0) return api_fail(TRPL_ERR_ARG, "M must be >= 0");
+    if (int rc = check_mag(sse, esum, n_obs, S, C, P, M > 0)) return rc;
+    if (S == 0 || M == 0) return TRPL_OK;
+    if (!offsets) return api_fail(TRPL_ERR_ARG, "offsets must not be NULL");
+    hipError_t e = trpl::launch_mag_grid(sse, esum, n_obs, S, C, offsets, M, P, (hipStream_t)stream);
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mag_grid launch: %s", hipGetErrorString(e));
+    return TRPL_OK;
+}
+
+int trpl_mag_profile(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C, uint32_t flags,
+                     double *best, double *P)
+{
+    if (flags & ~(uint32_t)TRPL_MAG_PER_CURVE) return api_fail(TRPL_ERR_ARG, "trpl_mag_profile: unknown flag bits 0x%x", flags);
+    if (int rc = check_mag(sse, esum, n_obs, S, C, P, true)) return rc;
+    if (S == 0) return TRPL_OK;
+    if (!best) return api_fail(TRPL_ERR_ARG, "best must not be NULL");
+    trpl::mag_profile_host(sse, esum, n_obs, S, C, (flags & TRPL_MAG_PER_CURVE) != 0, best, P);
+    return TRPL_OK;
+}
+
+int trpl_mag_profile_dev(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C, uint32_t flags,
+                         double *best, double *P, void *stream)
+{
+    if (flags & ~(uint32_t)TRPL_MAG_PER_CURVE) return api_fail(TRPL_ERR_ARG, "trpl_mag_profile: unknown flag bits 0x%x", flags);
+    if (int rc = check_mag(sse, esum, n_obs, S, C, P, true)) return rc;
+    if (S == 0) return TRPL_OK;
+    if (!best) return api_fail(TRPL_ERR_ARG, "best must not be NULL");
+    hipError_t e = trpl::launch_mag_profile(sse, esum, n_obs, S, C, (flags & TRPL_MAG_PER_CURVE) != 0, best, P, (hipStream_t)stream);
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mag_profile launch: %s", hipGetErrorString(e));
+    return TRPL_OK;
 }
 
 /* ------------------------------------------------------------------ host interpolation --- */

@@ -69,6 +69,7 @@ struct StepArgs {
     int32_t pair_n;
     uint8_t pair_cA[kMaxCurves], pair_oA[kMaxCurves], pair_cB[kMaxCurves], pair_oB[kMaxCurves];
     CurveConst curve[kMaxCurves];
+    double *esum;           // [C][S] out: sum of the errors whose squares make sse (TRPL_FLAG_MOMENTS kernels only), or nullptr
 };
 
 // BDF coefficient table of tEvol (pvSimPCR.py:241-250): time step t takes the row min(t, 4) -- order 1 (Euler) at t = 0,
@@ -102,6 +103,13 @@ hipError_t launch_stepper_f32(const StepArgs &a, hipStream_t stream);           
 hipError_t launch_stepper_predict_fast(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_predict_strict(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_pair_predict(const StepArgs &a, hipStream_t stream);
+// TRPL_FLAG_MOMENTS (stepper_moments_*.hip): the fp64 steppers whose sink also emits esum, with and without PREDICT
+hipError_t launch_stepper_moments_fast(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_moments_strict(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_moments_pair(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_moments_predict_fast(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_moments_predict_strict(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_moments_predict_pair(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_mixed(const StepArgs &a, hipStream_t stream);           // L >= 128; `make EXPERIMENTAL=1` only: the default
 hipError_t launch_stepper_hist32(const StepArgs &a, hipStream_t stream);          // L = 256 / 512;   library must not reference them
 
@@ -114,7 +122,18 @@ hipError_t launch_reduce_curves(double *P, const double *sse, int64_t S, int C, 
 hipError_t launch_pl_loglik(const void *pl, int elem_bytes, int64_t rows, int64_t ld, const double *obs,
                             const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t n_obs,
                             const double *mag, const int32_t *status, double *P, double *sse_out, uint32_t flags,
-                            hipStream_t stream);
+                            hipStream_t stream, double *esum_out = nullptr);
+// the magnitude-offset grid / profile from the moments (trpl_mag_grid, trpl_mag_profile): host forms and their kernels
+constexpr int kMagMaxCurves = 64;          // TRPL_MAG_MAX_CURVES
+constexpr int kMagChunk = 256;             // offsets per launch (kernel arguments)
+void mag_grid_host(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, const double *offsets,
+                   int64_t M, double *P);
+void mag_profile_host(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, bool per_curve,
+                      double *best, double *P);
+hipError_t launch_mag_grid(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C,
+                           const double *offsets, int64_t M, double *P, hipStream_t stream);
+hipError_t launch_mag_profile(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, bool per_curve,
+                              double *best, double *P, hipStream_t stream);
 
 // posterior.hip: the consumer of P[S] (weights, weighted moments, weighted histograms)
 size_t posterior_workspace_bytes(int D);

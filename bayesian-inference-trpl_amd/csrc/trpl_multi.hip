@@ -82,6 +82,7 @@ int trpl_loglik_multi(const double *X, int64_t S, int32_t C, const double *lengt
                       int32_t *floor_col, uint32_t flags, const int32_t *devices, int32_t n_devices, double *seconds)
 {
     ProfRange range("trpl_loglik_multi (sample shards over the visible devices)");
+    if (int rc = no_moments_flag(flags)) return rc;
     if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
     if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
     if (C < 1 || C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAX_CURVES);
@@ -406,6 +407,7 @@ int trpl_loglik_multi_dev(trpl_multi_t *h, const double *const *X, int64_t S, in
     const bool interp = obs_hi || obs_dx || obs_h;
     if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
     if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
+    if (int rc = no_moments_flag(flags)) return rc;
     if (int rc = pin_sharded_batch(flags, S, C, L, T, plT, interp, n_obs, obs_ld)) return rc;
     if (S == 0) return TRPL_OK;
     const int n = h->n;

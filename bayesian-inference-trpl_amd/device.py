@@ -61,6 +61,58 @@ def loglik_obs_device(X, init_params, lengths, Time, L, T, obs, obs_hi, obs_dx, 
         None if floor_col is None else _chk(floor_col, torch.int32, "floor_col"), int(flags), _stream()))
 
 
+def loglik_moments_device(X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, esum, status=None, iters_total=None,
+                          tol=7, MAX=10000, plT=1, flags=0, floor_col=None, obs_hi=None, obs_dx=None, obs_h=None):
+    """trpl_loglik_moments_dev: loglik_device / loglik_obs_device (with the bracketing arrays obs_hi, obs_dx, obs_h) that
+    also fills esum (C,S) f64, the sum of the log-errors whose squares make sse -- the input of mag_grid_device and
+    mag_profile_device.  P, sse, status, iters_total and floor_col are loglik[_obs]_device's, bit for bit."""
+    import torch
+    S, Cn = X.shape[0], init_params.shape[0]
+    interp = obs_hi is not None
+    if X.shape[1] != 13 or init_params.shape[1] != L or obs.shape[0] != Cn or tuple(sse.shape) != (Cn, S) \
+            or tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (S,) \
+            or (interp and not (obs.shape == obs_hi.shape == obs_dx.shape == obs_h.shape)):
+        raise ValueError("shape mismatch")
+    lengths = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.float64), (Cn,)))
+    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
+    _abi.check(_abi.lib().trpl_loglik_moments_dev(
+        _chk(X, torch.float64, "X"), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol),
+        int(MAX), _chk(init_params, torch.float64, "init_params"), _chk(obs, torch.float64, "obs"),
+        _chk(obs_hi, torch.int32, "obs_hi") if interp else None, _chk(obs_dx, torch.float64, "obs_dx") if interp else None,
+        _chk(obs_h, torch.float64, "obs_h") if interp else None, obs.shape[1], _abi.ptr(n_obs),
+        _chk(P, torch.float64, "P"), _chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
+        None if status is None else _chk(status, torch.int32, "status"),
+        None if iters_total is None else _chk(iters_total, torch.int64, "iters_total"),
+        None if floor_col is None else _chk(floor_col, torch.int32, "floor_col"), int(flags), _stream()))
+
+
+def mag_grid_device(sse, esum, n_obs, offsets, P):
+    """trpl_mag_grid_dev: P (M,S) f64 -= sum_c max(sse + 2 d_m esum + n_c d_m^2, 0) for the offsets d_m (host sequence,
+    added to X[:, 12]); sse, esum (C,S) f64 from loglik_moments_device, n_obs a host sequence (C,)."""
+    import torch
+    Cn, S = sse.shape
+    off = np.ascontiguousarray(offsets, dtype=np.float64).ravel()
+    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
+    if tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (len(off), S):
+        raise ValueError("shape mismatch")
+    _abi.check(_abi.lib().trpl_mag_grid_dev(_chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
+                                            _abi.ptr(n_obs), S, Cn, _abi.ptr(off), len(off),
+                                            _chk(P, torch.float64, "P"), _stream()))
+
+
+def mag_profile_device(sse, esum, n_obs, best, P, per_curve=False):
+    """trpl_mag_profile_dev: the likelihood-maximising offset best (S,) -- (C,S) with per_curve -- and P (S,) -= the
+    squared error there (the profile likelihood over the magnitude offset)."""
+    import torch
+    Cn, S = sse.shape
+    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
+    if tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (S,) or tuple(best.shape) != ((Cn, S) if per_curve else (S,)):
+        raise ValueError("shape mismatch")
+    _abi.check(_abi.lib().trpl_mag_profile_dev(_chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
+                                               _abi.ptr(n_obs), S, Cn, _abi.MAG_PER_CURVE if per_curve else 0,
+                                               _chk(best, torch.float64, "best"), _chk(P, torch.float64, "P"), _stream()))
+
+
 def solve_pl_device(matPar, Length, Time, L, T, dN, plI, status=None, iters_total=None, tol=7, MAX=10000, plT=1,
                     flags=0):
     """trpl_solve_pl_dev: matPar (S,12) f64, dN (L,) f64, plI (S, T//plT+1) f32/f64 out."""
@@ -178,6 +230,24 @@ def loglik_from_pl_device(pl, obs, mag, P=None, sse=None, obs_hi=None, obs_dx=No
         obs.shape[0], _chk(mag, torch.float64, "mag"), None if status is None else _chk(status, torch.int32, "status"),
         None if P is None else _chk(P, torch.float64, "P"),
         None if sse is None else _chk(sse, torch.float64, "sse"), int(flags), _stream()))
+
+
+def loglik_moments_from_pl_device(pl, obs, mag, P=None, sse=None, esum=None, obs_hi=None, obs_dx=None, obs_h=None,
+                                  ncol=None, flags=0, status=None):
+    """trpl_loglik_moments_from_pl_dev: loglik_from_pl_device that also fills esum (rows,) f64, the sum of the row's
+    log-errors (NaN for a flagged row): the resident-PL source of mag_grid_device's moments."""
+    import torch
+    if pl.dim() != 2 or pl.dtype not in (torch.float32, torch.float64):
+        raise ValueError("pl must be a 2-D float32/float64 tensor")
+    rows, ld = pl.shape
+    interp = obs_hi is not None
+    _abi.check(_abi.lib().trpl_loglik_moments_from_pl_dev(
+        _chk(pl, pl.dtype, "pl"), pl.element_size(), rows, int(ld if ncol is None else ncol), ld,
+        _chk(obs, torch.float64, "obs"), _chk(obs_hi, torch.int32, "obs_hi") if interp else None,
+        _chk(obs_dx, torch.float64, "obs_dx") if interp else None, _chk(obs_h, torch.float64, "obs_h") if interp else None,
+        obs.shape[0], _chk(mag, torch.float64, "mag"), None if status is None else _chk(status, torch.int32, "status"),
+        None if P is None else _chk(P, torch.float64, "P"), None if sse is None else _chk(sse, torch.float64, "sse"),
+        None if esum is None else _chk(esum, torch.float64, "esum"), int(flags), _stream()))
 
 
 def solve_pl_snap_device(matPar, Length, Time, L, T, dN, plI, snap_steps, plN=None, plP=None, plE=None, status=None,

@@ -137,7 +137,8 @@ def overlap_window(full, done, budget, num_curves):
 
 def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=None, pl_f32=False,
            normalize=False, strict=False, device=0, info=None, times=None, fp32=False, devices=None, kernel=None,
-           mixed=False, bundle=1, hist32=False, bdf_order=None, extra_flags=0, predict=False):
+           mixed=False, bundle=1, hist32=False, bdf_order=None, extra_flags=0, predict=False, mag_grid=None,
+           mag_profile=False):
     """Fused likelihood of one experiment (trpl_loglik / trpl_loglik_obs / trpl_loglik_multi).
 
     X (S,13) solver units; init_params (C,L) nm^-3; lengths scalar or (C,); obs = list of C
@@ -153,7 +154,19 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
     (tests / measurements: _abi.FLAG_PAIR_ALWAYS_SEAM, _abi.FLAG_PAIR_ADJACENT, ...).
     predict: start each time step's iteration from the extrapolated history (TRPL_FLAG_PREDICT; opt-in, off by default:
     about half the solves; PL agrees with the default path to ~1e-9 median, within the tolerance include/trpl.h states).
+    mag_grid: a sequence of M magnitude offsets ADDED to X[:, 12] -- the mag_grid loop of the reference's older
+    likelihood (probs.lnP, probs.py:5-18) from ONE solve (trpl_loglik_moments + trpl_mag_grid): returns P (M, S), row m
+    the likelihood at X[:, 12] + mag_grid[m] (accumulated into P if P (M, S) is given).  mag_profile=True (or
+    "per_curve"): returns (best, P) -- the likelihood-maximising offset, (S,) or (C, S), and the likelihood there.
+    Single-device calls only; info also receives esum and P, the one-offset likelihood trpl_loglik would return.
     """
+    moments = mag_grid is not None or bool(mag_profile)
+    if moments:
+        if mag_grid is not None and mag_profile:
+            raise ValueError("mag_grid and mag_profile exclude each other")
+        if devices is not None:
+            raise ValueError("mag_grid / mag_profile: not available with devices= (trpl_loglik_multi has no moments form)")
+        P_out, P = P, None
     X = np.ascontiguousarray(X, dtype=np.float64)
     if X.ndim != 2 or X.shape[1] != 13:
         raise ValueError("X must have shape (S, 13)")
@@ -202,6 +215,31 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
         | _abi.flag_bdf_order(bdf_order) | int(extra_flags) | (_abi.FLAG_PREDICT if predict else 0)
     sec = _abi.C.c_double(0.0)
     lib = _abi.lib()
+    if moments:
+        off = times is not None
+        esum = np.zeros((Cn, S))
+        _abi.check(lib.trpl_loglik_moments(
+            _abi.ptr(X), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol), int(MAX), _abi.ptr(ini),
+            _abi.ptr(obs_mat), _abi.ptr(hi_mat) if off else None, _abi.ptr(dx_mat) if off else None,
+            _abi.ptr(h_mat) if off else None, obs_ld, _abi.ptr(n_obs), _abi.ptr(P), _abi.ptr(sse), _abi.ptr(esum),
+            _abi.ptr(status), _abi.ptr(iters), _abi.ptr(floor_col), flags, int(device), _abi.C.byref(sec)))
+        if info is not None:
+            info.update(sse=sse, esum=esum, status=status, iters_total=iters, floor_col=floor_col, seconds=sec.value, P=P)
+        if mag_grid is not None:
+            offs = np.ascontiguousarray(mag_grid, dtype=np.float64).ravel()
+            Pm = np.zeros((len(offs), S)) if P_out is None else P_out
+            if not (Pm.dtype == np.float64 and Pm.flags.c_contiguous and Pm.shape == (len(offs), S)):
+                raise ValueError("P must be a contiguous float64 array of shape (len(mag_grid), S)")
+            _abi.check(lib.trpl_mag_grid(_abi.ptr(sse), _abi.ptr(esum), _abi.ptr(n_obs), S, Cn, _abi.ptr(offs), len(offs), _abi.ptr(Pm)))
+            return Pm
+        per_curve = mag_profile == "per_curve"
+        Pp = np.zeros(S) if P_out is None else P_out
+        if not (Pp.dtype == np.float64 and Pp.flags.c_contiguous and Pp.shape == (S,)):
+            raise ValueError("P must be a contiguous float64 array of shape (S,)")
+        best = np.zeros((Cn, S) if per_curve else S)
+        _abi.check(lib.trpl_mag_profile(_abi.ptr(sse), _abi.ptr(esum), _abi.ptr(n_obs), S, Cn,
+                                        _abi.MAG_PER_CURVE if per_curve else 0, _abi.ptr(best), _abi.ptr(Pp)))
+        return best, Pp
     if devices is not None:
         dev = None if isinstance(devices, str) else np.ascontiguousarray(devices, dtype=np.int32)
         if isinstance(devices, str) and devices != "all":
@@ -241,12 +279,15 @@ def _bundle_of(gpu_info, L):
 
 
 def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_params, normalize, pl_dtype, group,
-                       num_gpus, gpu_id, device, solver_time, err_sq_time, sim_t, bundle=1, literal=False, predict=False):
+                       num_gpus, gpu_id, device, solver_time, err_sq_time, sim_t, bundle=1, literal=False, predict=False,
+                       mag_grid=None):
     """Several experiments, fused option on: the reference's own loop order -- curves -> sample blocks ->
     experiments (bayeslib.py:117-171) -- with the block's PL matrix kept in HBM: one solve per (curve, block)
     (trpl_solve_pl_dev), then one pass over it per experiment (trpl_loglik_from_pl_dev: normalise, clamp,
     log10, time interpolation, squared error).  Only X goes in and P comes out.  literal: observations_on_grid's switch
-    (gpu_info["interpolate_prefix"])."""
+    (gpu_info["interpolate_prefix"]).  mag_grid (gpu_info["mag_grid"]): P is (n_exp, M * S); each pass over the PL block also
+    returns the first moment of the errors (trpl_loglik_moments_from_pl_dev), and after a block's last curve
+    trpl_mag_grid_dev fills the M rows of every experiment."""
     import time
 
     import torch
@@ -280,6 +321,12 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
             P_d = torch.from_numpy(np.ascontiguousarray(P[:, blk:blk + size])).to(dev)
             pl_d = torch.empty((size, T // sim_params[4] + 1), dtype=tdt, device=dev)     # :137
             st_d = torch.empty(size, dtype=torch.int32, device=dev)
+            if mag_grid is not None:
+                S_all, M = len(X), len(mag_grid)
+                P_d = torch.from_numpy(np.ascontiguousarray(
+                    P.reshape(len(e_data), M, S_all)[:, :, blk:blk + size])).to(dev)            # (n_exp, M, size)
+                sse_d = torch.zeros((len(e_data), num_curves, size), dtype=torch.float64, device=dev)
+                esum_d = torch.zeros_like(sse_d)
             for c in range(num_curves):                                       # :117
                 torch.cuda.synchronize(dev)
                 t0 = time.perf_counter()
@@ -290,6 +337,12 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
                 t1 = time.perf_counter()
                 for e, per_curve in enumerate(staged):                        # :171
                     o_d, br = per_curve[c]
+                    if mag_grid is not None:
+                        tdev.loglik_moments_from_pl_device(pl_d, o_d, mag_d, sse=sse_d[e, c], esum=esum_d[e, c], flags=flags,
+                                                           status=st_d, obs_hi=None if br is None else br[0],
+                                                           obs_dx=None if br is None else br[1],
+                                                           obs_h=None if br is None else br[2])
+                        continue
                     tdev.loglik_from_pl_device(pl_d, o_d, mag_d, P=P_d[e], flags=flags, status=st_d,
                                                obs_hi=None if br is None else br[0],
                                                obs_dx=None if br is None else br[1],
@@ -297,6 +350,11 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
                 torch.cuda.synchronize(dev)
                 solver_time[gpu_id] += t1 - t0
                 err_sq_time[gpu_id] += time.perf_counter() - t1
+            if mag_grid is not None:
+                for e, per_curve in enumerate(staged):
+                    tdev.mag_grid_device(sse_d[e], esum_d[e], [len(per_curve[c][0]) for c in range(num_curves)], mag_grid, P_d[e])
+                P.reshape(len(e_data), M, S_all)[:, :, blk:blk + size] = P_d.cpu().numpy()
+                continue
             P[:, blk:blk + size] = P_d.cpu().numpy()
 
 
@@ -310,6 +368,10 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
     grid a prefix of the simulation grid, each (curve-set, block, experiment) is one fused launch
     (spread over gpu_info['devices'] when that is given, see loglik).  gpu_info['predict'] = True (default False) runs
     every solve with the extrapolated start of TRPL_FLAG_PREDICT, on the fused and the unfused (pvSim) paths alike.
+    gpu_info['mag_grid'] = offsets (default None: nothing changes): the likelihood at the M magnitude offsets X[:, 12] +
+    offsets[m] from ONE solve per sample (trpl_loglik_moments + trpl_mag_grid; the mag_grid loop of the reference's probs.lnP,
+    probs.py:5-18).  X stays (S, 13); P must then be (n_exp, M * S), column m * S + s = sample s at offset m (mag_grid_samples
+    builds the matching X).  Fused levels on one device only: anything else is a ValueError naming the option.
     """
     group = int(gpu_info["sims_per_gpu"])
     num_gpus = int(gpu_info["num_gpus"])
@@ -336,11 +398,26 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
 
     fused = bool(gpu_info.get("fused", False)) and LOG_PL and sim_params[4] == 1 and all(
         in_range(exp[0][c]) for exp in e_data for c in range(num_curves))
+    mag_grid = gpu_info.get("mag_grid")
+    if mag_grid is not None:
+        mag_grid = np.ascontiguousarray(mag_grid, dtype=np.float64).ravel()
+        if gpu_info.get("devices") is not None:
+            raise ValueError("gpu_info['mag_grid'] does not combine with gpu_info['devices']: trpl_loglik_multi has no moments form")
+        if num_gpus != 1:
+            raise ValueError("gpu_info['mag_grid'] needs gpu_info['num_gpus'] = 1 (the rank driver keeps the one-offset likelihood)")
+        if not fused:
+            raise ValueError("gpu_info['mag_grid'] needs the fused level: gpu_info['fused'] = True, log_pl, PL stride 1 and "
+                             "observation times inside the simulated window")
+        if int(gpu_info.get("max_sims_per_block", 1)) > 1:
+            raise ValueError("gpu_info['mag_grid'] does not combine with gpu_info['max_sims_per_block'] > 1 (TRPL_FLAG_MOMENTS has no bundles)")
+        if P.shape != (len(e_data), len(mag_grid) * len(X)) or not P.flags.c_contiguous:
+            raise ValueError("gpu_info['mag_grid']: P must be a contiguous (n_exp, M * S) = (%d, %d) array"
+                             % (len(e_data), len(mag_grid) * len(X)))
     if fused and len(e_data) > 1 and gpu_info.get("devices") is None:
         _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_params, NORMALIZE, pl_dtype,
                            group, num_gpus, gpu_id, device, solver_time, err_sq_time, sim_t,
                            bundle=_bundle_of(gpu_info, L), literal=bool(gpu_info.get("interpolate_prefix", False)),
-                           predict=predict)
+                           predict=predict, mag_grid=mag_grid)
         return
     if fused:
         # An experiment sampled exactly on the full simulation grid is compared point by point (the reference's bypass,
@@ -356,6 +433,17 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
             for e, exp in enumerate(e_data):
                 on_grid = fused_entry_point(exp[0], sim_t, num_curves, literal) == "trpl_loglik"
                 info = {}
+                if mag_grid is not None:
+                    Pe = P[e].reshape(len(mag_grid), len(X))
+                    Pm = np.ascontiguousarray(Pe[:, blk:blk + size])
+                    loglik(X[blk:blk + size], init_params, thicknesses, Time, L, T,
+                           [exp[1][c] for c in range(num_curves)], tol=sim_params[6], MAX=sim_params[7], P=Pm,
+                           pl_f32=(pl_dtype == np.float32), normalize=NORMALIZE, device=device, info=info,
+                           times=None if on_grid else [exp[0][c] for c in range(num_curves)], predict=predict,
+                           mag_grid=mag_grid)
+                    Pe[:, blk:blk + size] = Pm
+                    solver_time[gpu_id] += info["seconds"]
+                    continue
                 loglik(X[blk:blk + size], init_params, thicknesses, Time, L, T,
                        [exp[1][c] for c in range(num_curves)], tol=sim_params[6], MAX=sim_params[7],
                        P=P[e, blk:blk + size], pl_f32=(pl_dtype == np.float32), normalize=NORMALIZE,
@@ -475,6 +563,15 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
             pool.shutdown(wait=True)
 
 
+def mag_grid_samples(X, offsets):
+    """The sample matrix that goes with a gpu_info['mag_grid'] result: (M * S, 13), row m * S + s = sample s with
+    offsets[m] added to its magnitude offset (column 12)."""
+    X = np.asarray(X, dtype=np.float64)
+    out = np.tile(X, (len(offsets), 1))
+    out[:, 12] += np.repeat(np.asarray(offsets, dtype=np.float64), len(X))
+    return out
+
+
 def bayes(model, N, P, minX, maxX, do_log, init_params, sim_params, e_data, sim_flags, gpu_info, logger=None,
           rng=None):
     """bayeslib.bayes (bayeslib.py:207-252): sample the box, run simulate() for this process's
@@ -487,6 +584,9 @@ def bayes(model, N, P, minX, maxX, do_log, init_params, sim_params, e_data, sim_
     if not 0 <= gpu_id < num_gpus:
         raise ValueError("process index %d outside num_gpus=%d" % (gpu_id, num_gpus))
     plI, plI_int = [None] * num_gpus, [None] * num_gpus
+    offsets = gpu_info.get("mag_grid")
+    if offsets is not None:                           # M likelihoods per solved sample: P (n_exp, M * S), X (M * S, 13) below
+        P = np.tile(P, (1, len(offsets)))
     simulate(model if model is not None else pvSim, e_data, P, X, plI, plI_int, len(init_params),
              list(sim_params), init_params, sim_flags, gpu_info, gpu_id, solver_time, err_sq_time, misc_time,
              logger=logger)
@@ -494,4 +594,7 @@ def bayes(model, N, P, minX, maxX, do_log, init_params, sim_params, e_data, sim_
         logger.info("Total tEvol time: {}".format(solver_time))
         logger.info("Total err_sq time: {}".format(err_sq_time))
         logger.info("Total misc time: {}".format(misc_time))
+    if offsets is not None:
+        X = mag_grid_samples(X, offsets)
+        N = np.arange(len(X)) if isinstance(N, np.ndarray) and N.ndim == 1 else N
     return N, P, X

@@ -162,6 +162,14 @@ extern "C" {
                                      difference from the default kernels; the timed, snapshot-free kernels use none.
                                      Refused: with TRPL_FLAG_FP32, _MIXED or _HIST32 TRPL_ERR_ARG; with TRPL_FLAG_BUNDLE(m > 1)
                                      TRPL_ERR_UNSUPPORTED.  Python: predict=True, gpu_info["predict"] */
+#define TRPL_FLAG_MOMENTS 0x200000  /* the likelihood-mode steppers whose sink emits esum = sum e_i beside sse = sum e_i^2 (their own
+                                     instantiations, trpl::moments::[predict::][pair::]stepper...; the existing kernels are the same
+                                     machine code as without them).  SET BY trpl_loglik_moments[_dev] THEMSELVES: every other entry
+                                     point has nowhere to put esum and answers TRPL_ERR_ARG before it touches a device.
+                                     trpl_kernel_name / trpl_kernel_variant accept it and name the instantiation after the usual
+                                     launch checks.  FAST and STRICT, every L, both FAST kernels, with and without
+                                     TRPL_FLAG_PREDICT; no snapshot / resume forms.  Refused with TRPL_ERR_UNSUPPORTED:
+                                     TRPL_FLAG_FP32, _MIXED, _HIST32, TRPL_FLAG_BUNDLE(m > 1) */
 #define TRPL_FLAG_KERNEL_PAIR 0x10    /* run the two-systems-per-wavefront stepper whatever the launch size (L = 128,
                                         fp64, not STRICT -- anything else is TRPL_ERR_ARG) */
 #define TRPL_FLAG_KERNEL_SINGLE 0x20  /* run the one-system-per-wavefront stepper whatever the launch size */
@@ -416,6 +424,68 @@ int trpl_loglik_obs_dev(const double *X, int64_t S, int32_t C, const double *len
                         const double *obs_h, int64_t obs_ld, const int64_t *n_obs /*host*/, double *P,
                         double *sse, int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags,
                         void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * trpl_loglik_moments -- trpl_loglik / trpl_loglik_obs that also return the FIRST moment of the log-errors, so that the
+ * likelihood at ANY magnitude offset follows from ONE solve.  Restores what the reference's older likelihood did,
+ * probs.lnP (probs.py:5-18): its loop over a `mag_grid` fills P[:, m] for every offset from one simulated curve (the
+ * argument of probs.prob, probs.py:20, is still called mag_grid), where the live path compares at the one offset of
+ * X[:, 12] (probs.py:33, bayeslib.py:195) and every other trial offset costs a full solve.  With
+ *     e_i = log10 PL_i + X[s][12] - obs_i,      sum_i (e_i + d)^2 = sum e_i^2 + 2 d sum e_i + n d^2,
+ * so beside sse[c][s] = sum e_i^2 the steppers emit
+ *     esum[c][s] = sum_i e_i      -- the very values that are squared: after the optional fp32 rounding, normalisation,
+ *                                    the clamp at DBL_MIN, the interpolation and + X[s][12]; summed in sse's order and
+ *                                    association (serially under TRPL_FLAG_STRICT; FAST: a wave reduction per 64 columns,
+ *                                    the batches added in order).
+ * Arguments: those of trpl_loglik_obs[_dev] plus plT and esum [C][S]; obs_hi / obs_dx / obs_h all NULL: observations on
+ * the grid (as trpl_loglik, n_obs <= T/plT + 1), all non-NULL: off-grid (plT must be 1).  P, sse, status, iters_total
+ * and floor_col are EXACTLY trpl_loglik[_obs]'s on the same inputs and flags, bit for bit (P[s] -= sum_c sse[c][s]); a
+ * flagged system has esum = NaN (its sse stays +inf).  TRPL_FLAG_MOMENTS is set by the call.
+ * trpl_loglik_multi* has no moments form (out of scope: the sharded drivers keep the one-offset likelihood).
+ *
+ * trpl_mag_grid -- the mag_grid loop of probs.lnP (probs.py:5-18) from the moments:
+ *     P[m][s] -= sum_c max(sse[c][s] + 2 d_m esum[c][s] + n_c d_m^2, 0)
+ * evaluated as written -- ((sse + (2 d) esum) + n (d d)), curves in order, no fused multiply-add -- for the offsets
+ * d_m = offsets[m] ADDED to X[s][12].  A +inf / NaN moment gives P = -inf.
+ * trpl_mag_profile -- the offset that maximises the likelihood and the likelihood there (the profile likelihood):
+ *     default (one offset shared by a sample's curves): best[s] = -(sum_c esum[c][s]) / (sum_c n_c)
+ *     TRPL_MAG_PER_CURVE:                               best[c][s] = -esum[c][s] / n_c
+ *     P[s] -= the grid expression at best;  a flagged system: best = NaN, P = -inf.
+ * ERROR BOUND (A(d) = sse + 2 |d esum| + n d^2, eps = 2^-52): against a direct evaluation of sum (e_i + d)^2 on the same PL,
+ *     |P_grid - P_direct| <= k eps (A(d) + |d| sum|e_i|),   k = 6 + ceil(n / 64) + 4
+ * (the depth of a batch's reduction tree, the batches added serially, the polynomial; k = n + 4 under TRPL_FLAG_STRICT).
+ * The clamp at 0 only acts where cancellation has taken the sum below its own rounding error.  lnP's bval_cutoff clamp
+ * depends on the offset and is not reproduced (the live reference has it commented out); no sigma weighting.
+ *   sse, esum [C][S];  n_obs [C] HOST int64;  offsets [M] HOST fp64;  P [M][S];  best [S] or [C][S];  C <= TRPL_MAG_MAX_CURVES
+ * The host forms are PLAIN HOST CODE (no device, like trpl_interp_rows) in the same operation order; the _dev kernels
+ * (device pointers sse / esum / P / best, nothing allocated) equal them bit for bit.
+ * trpl_loglik_moments_from_pl_dev -- trpl_loglik_from_pl_dev with an esum [rows] output (nullable), for a resident PL block
+ * that serves several experiments; sse / P as that call's, a flagged row: esum = NaN.
+ * ------------------------------------------------------------------------------------- */
+#define TRPL_MAG_PER_CURVE 0x1
+#define TRPL_MAG_MAX_CURVES 64
+int trpl_loglik_moments(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns,
+                        int32_t L, int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
+                        const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                        int64_t obs_ld, const int64_t *n_obs, double *P, double *sse, double *esum, int32_t *status,
+                        int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device, double *seconds);
+int trpl_loglik_moments_dev(const double *X, int64_t S, int32_t C, const double *lengths_nm /*host*/, double time_ns,
+                            int32_t L, int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
+                            const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                            int64_t obs_ld, const int64_t *n_obs /*host*/, double *P, double *sse, double *esum,
+                            int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream);
+int trpl_loglik_moments_from_pl_dev(const void *plI, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld,
+                                    const double *obs, const int32_t *obs_hi, const double *obs_dx,
+                                    const double *obs_h, int64_t n_obs, const double *mag, const int32_t *status,
+                                    double *P, double *sse, double *esum, uint32_t flags, void *stream);
+int trpl_mag_grid(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C,
+                  const double *offsets, int64_t M, double *P);
+int trpl_mag_grid_dev(const double *sse, const double *esum, const int64_t *n_obs /*host*/, int64_t S, int32_t C,
+                      const double *offsets /*host*/, int64_t M, double *P, void *stream);
+int trpl_mag_profile(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C,
+                     uint32_t flags, double *best, double *P);
+int trpl_mag_profile_dev(const double *sse, const double *esum, const int64_t *n_obs /*host*/, int64_t S, int32_t C,
+                         uint32_t flags, double *best, double *P, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * trpl_loglik_multi -- trpl_loglik / trpl_loglik_obs over several devices from ONE host thread:
