@@ -131,6 +131,7 @@ struct ProfRange {
     ProfRange &operator=(const ProfRange &) = delete;
 };
 
+int no_weighted_flag(uint32_t flags);      // TRPL_ERR_ARG when TRPL_FLAG_WEIGHTED reaches an entry point that takes no weights
 int no_moments_flag(uint32_t flags);       // TRPL_ERR_ARG when TRPL_FLAG_MOMENTS reaches an entry point without an esum output
 int select_device(int32_t device);          // hipSetDevice with range check (trpl_api.hip)
 int check_grid(int32_t L, int64_t T, int32_t plT, int32_t max_iter, double time_ns);

@@ -80,9 +80,13 @@ hipError_t launch_log10_clamp(void *x, int elem_bytes, int64_t rows, int64_t col
 // lanes along the columns (256/512-byte contiguous segments), squares the residuals in parallel,
 // transposes through LDS, and lanes 0..R-1 add their row's 64 values in order while the loads of
 // the next tile are already in flight.
-template <typename T, int R>
+// W (trpl_sse_accumulate_w): every squared residual times its column's weight, (e * e) * w[i] -- the weighting line of
+// kernel_lnP (probs.py:40) with w = 1 / (2 u^2) formed by the caller -- in its own instantiations, same serial order;
+// the W = false kernels are the code they were before.
+template <typename T, int R, bool W = false>
 __global__ void __launch_bounds__(64) sse_accumulate_kernel(double *P, const T *pl, int64_t rows, int64_t n_obs,
-                                                            int64_t ld, const double *values, const double *mag)
+                                                            int64_t ld, const double *values, const double *mag,
+                                                            const double *wts = nullptr)
 {
     __shared__ double tile[R][65];
     const int lane = threadIdx.x;
@@ -101,18 +105,19 @@ __global__ void __launch_bounds__(64) sse_accumulate_kernel(double *P, const T *
     // load+arithmetic made it wait for every single load: 0.1 % of HBM peak).
     constexpr int D = 32 / R;
     T raw[D][R];
-    double vraw[D];
-    auto issue = [&](int64_t c0, T (&v)[R], double &val) {
+    double vraw[D], wraw[W ? D : 1];
+    auto issue = [&](int64_t c0, T (&v)[R], double &val, double &wt) {
         int64_t col = c0 + lane;
         col = col < n_obs ? col : n_obs - 1;
         val = values[col];
+        if constexpr (W) wt = wts[col];
 #pragma unroll
         for (int r = 0; r < R; r++) v[r] = rowp[r][col];
     };
     double acc = 0.0;
     if (n_obs > 0) {
 #pragma unroll
-        for (int d = 0; d < D; d++) issue((int64_t)d * 64, raw[d], vraw[d]);
+        for (int d = 0; d < D; d++) issue((int64_t)d * 64, raw[d], vraw[d], wraw[W ? d : 0]);
     }
     for (int64_t c0 = 0; c0 < n_obs; c0 += 64 * D) {
 #pragma unroll
@@ -123,9 +128,10 @@ __global__ void __launch_bounds__(64) sse_accumulate_kernel(double *P, const T *
             for (int r = 0; r < R; r++) {
                 double e = (double)raw[d][r] + mg[r];              // probs.py:33
                 e -= vraw[d];                                      // :37
-                tile[r][lane] = e * e;                             // :39
+                if constexpr (W) tile[r][lane] = (e * e) * wraw[d];   // :39, :40
+                else tile[r][lane] = e * e;                        // :39
             }
-            issue(cc + 64 * D, raw[d], vraw[d]);                   // refill this slot D tiles ahead
+            issue(cc + 64 * D, raw[d], vraw[d], wraw[W ? d : 0]);                   // refill this slot D tiles ahead
             const int ncol = (int)((n_obs - cc) < 64 ? (n_obs - cc) : 64);
             if (lane < R) {
                 const double *t = tile[lane];
@@ -141,13 +147,13 @@ __global__ void __launch_bounds__(64) sse_accumulate_kernel(double *P, const T *
     if (lane < R && row0 + lane < rows) P[row0 + lane] += (0.0 - acc);   // :44, :57-60
 }
 
-template <typename T>
+template <typename T, bool W = false>
 static hipError_t launch_sse_t(double *P, const T *pl, int64_t rows, int64_t n_obs, int64_t ld, const double *values,
-                               const double *mag, hipStream_t stream)
+                               const double *mag, hipStream_t stream, const double *wts = nullptr)
 {
 #define TRPL_SSE(RR)                                                                                              \
-    hipLaunchKernelGGL((sse_accumulate_kernel<T, RR>), dim3((unsigned)((rows + RR - 1) / RR)), dim3(64), 0, stream, \
-                       P, pl, rows, n_obs, ld, values, mag)
+    hipLaunchKernelGGL((sse_accumulate_kernel<T, RR, W>), dim3((unsigned)((rows + RR - 1) / RR)), dim3(64), 0, stream, \
+                       P, pl, rows, n_obs, ld, values, mag, wts)
     if (rows <= 4 * 1024) TRPL_SSE(4);               // >= rows/4 workgroups: cover the 256 CUs
     else if (rows <= 16 * 1024) TRPL_SSE(8);
     else TRPL_SSE(16);
@@ -161,6 +167,14 @@ hipError_t launch_sse_accumulate(double *P, const void *pl, int elem_bytes, int6
     if (rows <= 0) return hipSuccess;
     return elem_bytes == 4 ? launch_sse_t<float>(P, (const float *)pl, rows, n_obs, ld, values, mag, stream)
                            : launch_sse_t<double>(P, (const double *)pl, rows, n_obs, ld, values, mag, stream);
+}
+
+hipError_t launch_sse_accumulate_w(double *P, const void *pl, int elem_bytes, int64_t rows, int64_t n_obs, int64_t ld,
+                                   const double *values, const double *wts, const double *mag, hipStream_t stream)
+{
+    if (rows <= 0) return hipSuccess;
+    return elem_bytes == 4 ? launch_sse_t<float, true>(P, (const float *)pl, rows, n_obs, ld, values, mag, stream, wts)
+                           : launch_sse_t<double, true>(P, (const double *)pl, rows, n_obs, ld, values, mag, stream, wts);
 }
 
 // P[s] -= sse[c][s] for c = 0..C-1 in curve order (the order bayeslib.simulate calls prob in,
@@ -212,12 +226,15 @@ __device__ __forceinline__ double log_pl(T v, T v0, bool normalize, bool f32_sta
 
 // MOM (trpl_loglik_moments_from_pl_dev): the sum of the errors beside the sum of their squares, in its own instantiation --
 // the MOM = false kernels are the code they were before the moments existed
-template <typename T, bool MOM>
+// WT (trpl_loglik_weighted_from_pl_dev; implies MOM): every term times its observation's weight, (err * err) * w and err * w
+template <typename T, bool MOM, bool WT = false>
 __global__ void __launch_bounds__(256) pl_loglik_kernel(const T *pl, int64_t rows, int64_t ld, const double *obs,
                                                         const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
                                                         int64_t n_obs, const double *mag, const int32_t *status,
-                                                        double *P, double *sse_out, uint32_t flags, double *esum_out)
+                                                        double *P, double *sse_out, uint32_t flags, double *esum_out,
+                                                        const double *wts = nullptr)
 {
+    static_assert(MOM || !WT, "the weighted form emits both sums");
     __shared__ double part[4], part1[MOM ? 4 : 1];
     const int lane = threadIdx.x & 63;
     const int64_t row = blockIdx.x;
@@ -238,8 +255,11 @@ __global__ void __launch_bounds__(256) pl_loglik_kernel(const T *pl, int64_t row
         }
         double err = y + m;
         err -= obs[i];
-        acc += err * err;
-        if constexpr (MOM) acc1 += err;
+        if constexpr (WT) { const double w = wts[i]; acc += (err * err) * w; acc1 += err * w; }
+        else {
+            acc += err * err;
+            if constexpr (MOM) acc1 += err;
+        }
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
@@ -263,10 +283,19 @@ __global__ void __launch_bounds__(256) pl_loglik_kernel(const T *pl, int64_t row
 hipError_t launch_pl_loglik(const void *pl, int elem_bytes, int64_t rows, int64_t ld, const double *obs,
                             const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t n_obs,
                             const double *mag, const int32_t *status, double *P, double *sse_out, uint32_t flags,
-                            hipStream_t stream, double *esum_out)
+                            hipStream_t stream, double *esum_out, const double *wts)
 {
     if (rows <= 0) return hipSuccess;
     const dim3 grid((unsigned)rows), block(256);
+    if (wts) {                                       // trpl_loglik_weighted_from_pl_dev: both sums, weighted
+        if (elem_bytes == 4)
+            hipLaunchKernelGGL((pl_loglik_kernel<float, true, true>), grid, block, 0, stream, (const float *)pl, rows, ld, obs,
+                               obs_hi, obs_dx, obs_h, n_obs, mag, status, P, sse_out, flags, esum_out, wts);
+        else
+            hipLaunchKernelGGL((pl_loglik_kernel<double, true, true>), grid, block, 0, stream, (const double *)pl, rows, ld, obs,
+                               obs_hi, obs_dx, obs_h, n_obs, mag, status, P, sse_out, flags, esum_out, wts);
+        return hipGetLastError();
+    }
 #define TRPL_PLL(TT, MM)                                                                                                  \
     hipLaunchKernelGGL((pl_loglik_kernel<TT, MM>), grid, block, 0, stream, (const TT *)pl, rows, ld, obs, obs_hi, obs_dx, obs_h, \
                        n_obs, mag, status, P, sse_out, flags, esum_out)
@@ -307,6 +336,9 @@ __host__ __device__ inline void mag_profile_one(const double *sse, const double 
     if (per_curve) {
         for (int c = 0; c < C; c++) {
             const double e = esum[(int64_t)c * S + s];
+            // a curve whose weights are all zero (trpl_mag_profile_w; n_obs >= 1 never gets here) has no observation:
+            // no best offset, and it contributes nothing
+            if (n[c] == 0.0 && sse[(int64_t)c * S + s] < INFINITY) { best[(int64_t)c * S + s] = NAN; continue; }
             const double d = (0.0 - e) / n[c];
             best[(int64_t)c * S + s] = (e - e == 0.0 && sse[(int64_t)c * S + s] < INFINITY) ? d : NAN;
             acc += mag_term(sse[(int64_t)c * S + s], e, n[c], d);
@@ -315,6 +347,7 @@ __host__ __device__ inline void mag_profile_one(const double *sse, const double 
         double E = 0.0, N = 0.0;
         bool ok = true;
         for (int c = 0; c < C; c++) { E += esum[(int64_t)c * S + s]; N += n[c]; ok = ok && sse[(int64_t)c * S + s] < INFINITY; }
+        if (N == 0.0 && ok) { best[s] = NAN; return; }                // every weight zero: nothing to fit, P stays
         const double d = (0.0 - E) / N;
         best[s] = (ok && E - E == 0.0) ? d : NAN;
         for (int c = 0; c < C; c++) acc += mag_term(sse[(int64_t)c * S + s], esum[(int64_t)c * S + s], n[c], d);
@@ -322,13 +355,27 @@ __host__ __device__ inline void mag_profile_one(const double *sse, const double 
     *P = *P - acc;
 }
 
+// The quadratic coefficient of a curve is a double everywhere below: (double)n_obs[c] for the unweighted calls, wsum[c] =
+// sum_i w_ci for the weighted ones (trpl_mag_grid_w, trpl_mag_profile_w) -- one expression for both.
+void mag_grid_host_w(const double *sse, const double *esum, const double *wsum, int64_t S, int C, const double *offsets,
+                     int64_t M, double *P)
+{
+    for (int64_t m = 0; m < M; m++)
+        for (int64_t s = 0; s < S; s++) mag_grid_one(sse, esum, wsum, S, C, s, offsets[m], P + m * S + s);
+}
+
+void mag_profile_host_w(const double *sse, const double *esum, const double *wsum, int64_t S, int C, bool per_curve,
+                        double *best, double *P)
+{
+    for (int64_t s = 0; s < S; s++) mag_profile_one(sse, esum, wsum, S, C, s, per_curve, best, P + s);
+}
+
 void mag_grid_host(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, const double *offsets,
                    int64_t M, double *P)
 {
     double n[kMagMaxCurves];
     for (int c = 0; c < C; c++) n[c] = (double)n_obs[c];
-    for (int64_t m = 0; m < M; m++)
-        for (int64_t s = 0; s < S; s++) mag_grid_one(sse, esum, n, S, C, s, offsets[m], P + m * S + s);
+    mag_grid_host_w(sse, esum, n, S, C, offsets, M, P);
 }
 
 void mag_profile_host(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, bool per_curve,
@@ -336,7 +383,7 @@ void mag_profile_host(const double *sse, const double *esum, const int64_t *n_ob
 {
     double n[kMagMaxCurves];
     for (int c = 0; c < C; c++) n[c] = (double)n_obs[c];
-    for (int64_t s = 0; s < S; s++) mag_profile_one(sse, esum, n, S, C, s, per_curve, best, P + s);
+    mag_profile_host_w(sse, esum, n, S, C, per_curve, best, P);
 }
 
 struct MagArgs {
@@ -374,12 +421,12 @@ __global__ void __launch_bounds__(256) mag_profile_kernel(const double *sse, con
         mag_profile_one(sse, esum, g.n, S, C, s, per_curve != 0, best, P + s);
 }
 
-hipError_t launch_mag_grid(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C,
-                           const double *offsets, int64_t M, double *P, hipStream_t stream)
+hipError_t launch_mag_grid_w(const double *sse, const double *esum, const double *wsum, int64_t S, int C,
+                             const double *offsets, int64_t M, double *P, hipStream_t stream)
 {
     if (S <= 0 || M <= 0) return hipSuccess;
     MagArgs g = {};
-    for (int c = 0; c < C; c++) g.n[c] = (double)n_obs[c];
+    for (int c = 0; c < C; c++) g.n[c] = wsum[c];
     int64_t blocks = (S + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     for (int64_t m0 = 0; m0 < M; m0 += kMagChunk) {          // offsets travel as kernel arguments, kMagChunk per launch
@@ -390,17 +437,33 @@ hipError_t launch_mag_grid(const double *sse, const double *esum, const int64_t 
     return hipGetLastError();
 }
 
-hipError_t launch_mag_profile(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, bool per_curve,
-                              double *best, double *P, hipStream_t stream)
+hipError_t launch_mag_grid(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C,
+                           const double *offsets, int64_t M, double *P, hipStream_t stream)
+{
+    double n[kMagMaxCurves];
+    for (int c = 0; c < C; c++) n[c] = (double)n_obs[c];
+    return launch_mag_grid_w(sse, esum, n, S, C, offsets, M, P, stream);
+}
+
+hipError_t launch_mag_profile_w(const double *sse, const double *esum, const double *wsum, int64_t S, int C, bool per_curve,
+                                double *best, double *P, hipStream_t stream)
 {
     if (S <= 0) return hipSuccess;
     MagArgs g = {};
-    for (int c = 0; c < C; c++) g.n[c] = (double)n_obs[c];
+    for (int c = 0; c < C; c++) g.n[c] = wsum[c];
     int64_t blocks = (S + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(mag_profile_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, sse, esum, S, C, per_curve ? 1 : 0,
                        best, P, g);
     return hipGetLastError();
+}
+
+hipError_t launch_mag_profile(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, bool per_curve,
+                              double *best, double *P, hipStream_t stream)
+{
+    double n[kMagMaxCurves];
+    for (int c = 0; c < C; c++) n[c] = (double)n_obs[c];
+    return launch_mag_profile_w(sse, esum, n, S, C, per_curve, best, P, stream);
 }
 
 // ---- host-side time interpolation of the unfused call sequence (bayeslib.py:184-191) ----

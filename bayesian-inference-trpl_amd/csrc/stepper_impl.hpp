@@ -38,7 +38,25 @@
 #ifndef TRPL_STEPPER_MOMENTS
 #define TRPL_STEPPER_MOMENTS 0
 #endif
-#if TRPL_STEPPER_MOMENTS && TRPL_STEPPER_PREDICT
+// TRPL_FLAG_WEIGHTED (include/trpl.h): a unit that defines TRPL_STEPPER_WEIGHTED=1 (stepper_weighted_*.hip) gets the moments
+// steppers whose sink multiplies every squared error and every error by the observation's weight (PlSinkT<true, PARK, true>:
+// sse = sum w e^2, esum = sum w e), as namespace trpl::weighted -- beside moments, not inside it: the kernels are
+// trpl::weighted::[predict::][pair::]stepper...  The weighted sink IS the moments sink plus one load and two multiplies per
+// batch, so such a unit is a TRPL_STEPPER_MOMENTS unit in everything but its namespace.
+#ifndef TRPL_STEPPER_WEIGHTED
+#define TRPL_STEPPER_WEIGHTED 0
+#endif
+#if TRPL_STEPPER_WEIGHTED
+#undef TRPL_STEPPER_MOMENTS
+#define TRPL_STEPPER_MOMENTS 1
+#endif
+#if TRPL_STEPPER_WEIGHTED && TRPL_STEPPER_PREDICT
+#define TRPL_VARIANT_NS_BEGIN namespace weighted { namespace predict {
+#define TRPL_VARIANT_NS_END } }
+#elif TRPL_STEPPER_WEIGHTED
+#define TRPL_VARIANT_NS_BEGIN namespace weighted {
+#define TRPL_VARIANT_NS_END }
+#elif TRPL_STEPPER_MOMENTS && TRPL_STEPPER_PREDICT
 #define TRPL_VARIANT_NS_BEGIN namespace moments { namespace predict {
 #define TRPL_VARIANT_NS_END } }
 #elif TRPL_STEPPER_MOMENTS
@@ -218,9 +236,16 @@ __device__ __forceinline__ bool correct_mixed(const double (&lo)[NR], const doub
 // once per 64 columns: between batches the batched path parks them in scalar registers (uniform_d after each add) or, PARK,
 // in two LDS words the kernel provides -- the paired kernel has neither a vector nor a scalar register to spare (253 of 256
 // VGPRs, 75 spilled SGPRs), and with both of its running sums in LDS it needs fewer registers than its counterpart.
-template <bool MOMENTS, bool PARK = false>
+// WEIGHTED (TRPL_FLAG_WEIGHTED): the moments sink with every term multiplied by the observation's weight, (err * err) * w and
+// err * w -- the square first, then the weight, so that w = 1 leaves the moments sink's bits and a power of two scales them
+// exactly.  The weight is one more coalesced load beside obs's; its row pointer is not kept (the paired kernel has no
+// register for it) but formed from obs's when a batch is flushed: wts and obs share their indexing.
+template <bool MOMENTS, bool PARK = false, bool WEIGHTED = false>
 struct PlSinkT {
     static_assert(MOMENTS || !PARK, "only the moments sink parks its sums in LDS");
+    static_assert(MOMENTS || !WEIGHTED, "the weighted sink is built on the moments sink");
+    // the weights of this system's curve, [obs_ld] (WEIGHTED only)
+    __device__ __forceinline__ const double *wts_row() const { return a.wts + (obs - a.obs); }
     const StepArgs &a;
     const CurveConst &cc;
     int64_t orow;            // output row (curve-major: c*S + s)
@@ -319,8 +344,11 @@ struct PlSinkT {
         if (!interp) {
             double err = lg + mag;
             err -= obs[col];
-            sse += err * err;
-            if constexpr (MOMENTS) esum += err;
+            if constexpr (WEIGHTED) { const double w = wts_row()[col]; sse += (err * err) * w; esum += err * w; }
+            else {
+                sse += err * err;
+                if constexpr (MOMENTS) esum += err;
+            }
         } else {
             // every observation bracketed by grid points (col-1, col): scipy interp1d's
             // slope * (x - x_lo) + y_lo (bayeslib.py:189)
@@ -329,8 +357,11 @@ struct PlSinkT {
                 const double y = (dy / obs_h[next_obs]) * obs_dx[next_obs] + lg_prev;
                 double err = y + mag;
                 err -= obs[next_obs];
-                sse += err * err;
-                if constexpr (MOMENTS) esum += err;
+                if constexpr (WEIGHTED) { const double w = wts_row()[next_obs]; sse += (err * err) * w; esum += err * w; }
+                else {
+                    sse += err * err;
+                    if constexpr (MOMENTS) esum += err;
+                }
                 next_obs++;
             }
             lg_prev = lg;
@@ -387,7 +418,10 @@ struct PlSinkT {
                     const bool use = live && col < ncol_ll;
                     double err = lg + mag;
                     err -= obs[use ? col : 0];
-                    if constexpr (MOMENTS) {
+                    if constexpr (WEIGHTED) {
+                        const double w = wts_row()[use ? col : 0];
+                        add_batch(wave_sum(use ? (err * err) * w : 0.0), wave_sum(use ? err * w : 0.0));
+                    } else if constexpr (MOMENTS) {
                         add_batch(wave_sum(use ? err * err : 0.0), wave_sum(use ? err : 0.0));
                     } else {
                         sse += wave_sum(use ? err * err : 0.0);
@@ -415,7 +449,10 @@ struct PlSinkT {
                         const double h = mine ? obs_h[idx] : 1.0, dx = mine ? obs_dx[idx] : 0.0;
                         double err = ((dy / h) * dx + y_lo) + mag;
                         err -= obs[mine ? idx : 0];
-                        if constexpr (MOMENTS) {
+                        if constexpr (WEIGHTED) {
+                            const double w = wts_row()[mine ? idx : 0];
+                            add_batch(wave_sum(mine ? (err * err) * w : 0.0), wave_sum(mine ? err * w : 0.0));
+                        } else if constexpr (MOMENTS) {
                             add_batch(wave_sum(mine ? err * err : 0.0), wave_sum(mine ? err : 0.0));
                         } else {
                             sse += wave_sum(mine ? err * err : 0.0);
@@ -729,6 +766,7 @@ stepper_kernel(const StepArgs a)
     // TRPL_FLAG_PREDICT: each step's iteration starts from predict_start() of the history instead of U^t
     constexpr bool PREDICT = TRPL_STEPPER_PREDICT != 0;
     constexpr bool MOMENTS = TRPL_STEPPER_MOMENTS != 0;       // TRPL_FLAG_MOMENTS: the sink emits esum beside sse
+    constexpr bool WEIGHTED = TRPL_STEPPER_WEIGHTED != 0;     // TRPL_FLAG_WEIGHTED: ... each term times its observation's weight
     static_assert(!MOMENTS || (!SNAP && !MIXED && !BUNDLE && !HIST32), "the moments sink exists for the plain fp64 one-system stepper, likelihood mode");
     static_assert(!PREDICT || (!MIXED && !BUNDLE && !HIST32), "the extrapolated start exists for the plain fp64 one-system stepper");
     const int wv = BUNDLE ? (int)(threadIdx.x >> 6) : 0;                 // which system of the bundle
@@ -810,7 +848,7 @@ stepper_kernel(const StepArgs a)
         }
     }
 
-    PlSinkT<MOMENTS> sink(a, cc, c, s, mag, lane64);
+    PlSinkT<MOMENTS, false, WEIGHTED> sink(a, cc, c, s, mag, lane64);
     sink.set_floor(rate, n0p0, L);
     if constexpr (BUNDLE) { if (!valid) sink.mute(); }
     SnapSink snap(a, cc);
@@ -1040,6 +1078,7 @@ hipError_t launch_stepper(const StepArgs &a, hipStream_t stream)
     const int64_t nsys = a.S * a.C;
     if (nsys <= 0) return hipSuccess;
     if (a.bundle > 1 || a.n_snap > 0 || a.resN != nullptr || !a.sse || !a.esum) return hipErrorInvalidValue;
+    if ((TRPL_STEPPER_WEIGHTED != 0) != (a.wts != nullptr)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)nsys), block(64);
     switch (a.L) {
 #define TRPL_CASE(LL) \

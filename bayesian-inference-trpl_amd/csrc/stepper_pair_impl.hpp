@@ -31,7 +31,7 @@
 #include "stepper_impl.hpp"
 
 namespace trpl {
-TRPL_VARIANT_NS_BEGIN                                // trpl::[moments::][predict::]pair by the unit's switches (stepper_impl.hpp)
+TRPL_VARIANT_NS_BEGIN                                // trpl::[moments:: | weighted::][predict::]pair by the unit's switches (stepper_impl.hpp)
 namespace pair {
 
 constexpr int L = 128;      // nodes per system
@@ -196,6 +196,7 @@ __global__ void __launch_bounds__(64, 2) stepper_pair_kernel(const StepArgs a)
     // (20 DS instructions per time step instead of 40); the field history hE[m] = E^{t-1-m} stays in registers
     constexpr int HSLOT = 2 * NR * 64;
     constexpr bool MOMENTS = TRPL_STEPPER_MOMENTS != 0;    // TRPL_FLAG_MOMENTS: {sse, esum, pl_floor} of both systems in six more LDS words
+    constexpr bool WEIGHTED = TRPL_STEPPER_WEIGHTED != 0;  // TRPL_FLAG_WEIGHTED: the same sink, every term times its observation's weight
     __shared__ __attribute__((aligned(16))) double lds[4 * HSLOT + (MOMENTS ? 6 : 0)];
     double2 *hist2 = reinterpret_cast<double2 *>(lds);            // hist2[(slot * NR + row) * 64 + lane] = {N, P}
     double *xch = nullptr;                          // the solver's exchanges are DPP moves and ds_swizzle rotates: no buffer
@@ -215,8 +216,8 @@ __global__ void __launch_bounds__(64, 2) stepper_pair_kernel(const StepArgs a)
         }
     }
 
-    PlSinkT<MOMENTS, MOMENTS> sinkA(a, cc, cA, sA, lane_value(mag, 0));
-    PlSinkT<MOMENTS, MOMENTS> sinkB(a, cc, cB, sB, lane_value(mag, WS));      // same n_obs and plnorm as cA's by construction of the table
+    PlSinkT<MOMENTS, MOMENTS, WEIGHTED> sinkA(a, cc, cA, sA, lane_value(mag, 0));
+    PlSinkT<MOMENTS, MOMENTS, WEIGHTED> sinkB(a, cc, cB, sB, lane_value(mag, WS));      // same n_obs and plnorm as cA's by construction of the table
     const double rateA = lane_value(rate, 0), rateB = lane_value(rate, WS);
     if constexpr (MOMENTS) { sinkA.set_park(lds + 4 * HSLOT); sinkB.set_park(lds + 4 * HSLOT + 3); }
     sinkA.set_floor(rateA, lane_value(n0p0, 0), L);
@@ -492,7 +493,7 @@ hipError_t launch_stepper_pair_t(const StepArgs &a, hipStream_t stream)
     const bool snap = a.n_snap > 0 || a.resN != nullptr;
     const dim3 grid((unsigned)nblk), block(64);
 #if TRPL_STEPPER_MOMENTS                            // likelihood mode only: no snapshot forms (check_launch)
-    if (snap || !a.sse || !a.esum) return hipErrorInvalidValue;
+    if (snap || !a.sse || !a.esum || (TRPL_STEPPER_WEIGHTED != 0) != (a.wts != nullptr)) return hipErrorInvalidValue;
     if (always_seam) hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false, false>), grid, block, 0, stream, a);
     else             hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false>), grid, block, 0, stream, a);
 #else

@@ -1,0 +1,9 @@
+// TRPL_FLAG_WEIGHTED, FAST, two systems per wavefront: the likelihood-mode stepper whose sink emits sse = sum w_i e_i^2 and esum = sum w_i e_i,
+// trpl::weighted::pair::stepper_pair_kernel<true, false, OPT>.  A translation unit of its own, compiled like
+// stepper_pair.hip (-ffp-contract=on): the existing kernels' objects do not change.
+#define TRPL_STEPPER_WEIGHTED 1
+#include "stepper_pair_impl.hpp"
+
+namespace trpl {
+hipError_t launch_stepper_weighted_pair(const StepArgs &a, hipStream_t stream) { return weighted::launch_stepper_pair_t<true>(a, stream); }
+}  // namespace trpl

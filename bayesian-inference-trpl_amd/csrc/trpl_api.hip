@@ -177,6 +177,7 @@ struct StepperChoice {
     bool strict, snap, mixed, hist32;                // template arguments of the one-system kernel, with bundle > 1
     bool predict;                                    // the instantiation in namespace trpl::predict
     bool moments;                                    // TRPL_FLAG_MOMENTS: the instantiation in namespace trpl::moments[::predict]
+    bool weighted;                                   // TRPL_FLAG_WEIGHTED: the instantiation in namespace trpl::weighted[::predict]
     bool optimistic;                                 // paired kernel: the optimistic seam (not TRPL_FLAG_PAIR_ALWAYS_SEAM)
 };
 
@@ -191,6 +192,7 @@ StepperChoice classify_stepper(uint32_t flags, int32_t L, int64_t nsys, int64_t 
     c.snap = snap;
     c.predict = (flags & TRPL_FLAG_PREDICT) != 0;
     c.moments = (flags & TRPL_FLAG_MOMENTS) != 0;
+    c.weighted = (flags & TRPL_FLAG_WEIGHTED) != 0;
     c.optimistic = TRPL_PAIR_OPTIMISTIC != 0 && !(flags & TRPL_FLAG_PAIR_ALWAYS_SEAM);
     if (flags & TRPL_FLAG_FP32) c.family = StepperChoice::F32;
     else if (flags & TRPL_FLAG_STRICT) c.strict = true;
@@ -233,6 +235,14 @@ int check_launch(uint32_t flags, int32_t L, int64_t steps, bool snap, bool resum
             return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_MOMENTS is not built for TRPL_FLAG_FP32, TRPL_FLAG_MIXED or TRPL_FLAG_HIST32");
         if (bundle > 1) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_MOMENTS is not built for TRPL_FLAG_BUNDLE(m > 1)");
         if (snap || resume) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_MOMENTS has no snapshot / resume instantiations (likelihood mode only)");
+    }
+    if (flags & TRPL_FLAG_WEIGHTED) {                                       // the weighted sink: where the moments sink exists
+        if (flags & TRPL_FLAG_MOMENTS)
+            return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_WEIGHTED and TRPL_FLAG_MOMENTS exclude each other (the weighted sink already emits both sums)");
+        if (flags & (TRPL_FLAG_FP32 | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
+            return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_WEIGHTED is not built for TRPL_FLAG_FP32, TRPL_FLAG_MIXED or TRPL_FLAG_HIST32");
+        if (bundle > 1) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_WEIGHTED is not built for TRPL_FLAG_BUNDLE(m > 1)");
+        if (snap || resume) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_WEIGHTED has no snapshot / resume instantiations (likelihood mode only)");
     }
     if (flags & TRPL_FLAG_PREDICT) {                                        // the extrapolated start: plain fp64 steppers only
         if (flags & (TRPL_FLAG_FP32 | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
@@ -288,8 +298,17 @@ int pin_sharded_batch(uint32_t &flags, int64_t S, int32_t C, int32_t L, int64_t 
 }
 
 // TRPL_FLAG_MOMENTS belongs to trpl_loglik_moments[_dev], which set it themselves: the other entry points have no esum output
+// ... and TRPL_FLAG_WEIGHTED to trpl_loglik_weighted[_dev]: the other entry points take no weights
+int no_weighted_flag(uint32_t flags)
+{
+    if (flags & TRPL_FLAG_WEIGHTED)
+        return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_WEIGHTED is set by trpl_loglik_weighted[_dev] only: this entry point takes no weights");
+    return TRPL_OK;
+}
+
 int no_moments_flag(uint32_t flags)
 {
+    if (int rc = no_weighted_flag(flags)) return rc;
     if (flags & TRPL_FLAG_MOMENTS)
         return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_MOMENTS is set by trpl_loglik_moments[_dev] only: this entry point has no esum output");
     return TRPL_OK;
@@ -332,6 +351,11 @@ int launch(const trpl::StepArgs &a_in, uint32_t flags, hipStream_t st, int64_t s
         else if (c.strict) fn = c.predict ? trpl::launch_stepper_moments_predict_strict : trpl::launch_stepper_moments_strict;
         else fn = c.predict ? trpl::launch_stepper_moments_predict_fast : trpl::launch_stepper_moments_fast;
     }
+    if (c.weighted) {                                // likewise
+        if (c.family == StepperChoice::Pair) fn = c.predict ? trpl::launch_stepper_weighted_predict_pair : trpl::launch_stepper_weighted_pair;
+        else if (c.strict) fn = c.predict ? trpl::launch_stepper_weighted_predict_strict : trpl::launch_stepper_weighted_strict;
+        else fn = c.predict ? trpl::launch_stepper_weighted_predict_fast : trpl::launch_stepper_weighted_fast;
+    }
     const hipError_t e = fn(a, st);
     if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "%sstepper launch: %s", what, hipGetErrorString(e));
     return TRPL_OK;
@@ -370,8 +394,8 @@ int trpl_kernel_name(int64_t nsys, int32_t L, int64_t steps, uint32_t flags, int
     // (`snapshots` covers snapshots AND resume; the fp32 stepper has one instantiation and accepts a resume)
     if (int rc = check_launch(flags, L, steps, snapshots != 0 && !(flags & TRPL_FLAG_FP32), false)) return rc;
     const StepperChoice c = classify_stepper(flags, L, nsys, steps, snapshots != 0);
-    const char *tf[2] = {"false", "true"};           // stepper_predict_*.hip, stepper_moments_*.hip
-    const char *ns = c.moments ? (c.predict ? "trpl::moments::predict::" : "trpl::moments::") : (c.predict ? "trpl::predict::" : "trpl::");
+    const char *tf[2] = {"false", "true"};           // stepper_predict_*.hip, stepper_moments_*.hip, stepper_weighted_*.hip
+    const char *ns = c.weighted ? (c.predict ? "trpl::weighted::predict::" : "trpl::weighted::") : c.moments ? (c.predict ? "trpl::moments::predict::" : "trpl::moments::") : (c.predict ? "trpl::predict::" : "trpl::");
     int n;
     if (c.family == StepperChoice::F32)
         n = snprintf(buf, (size_t)buflen, "%sf32::stepper_kernel<%d>", ns, c.L);
@@ -691,11 +715,73 @@ int trpl_sse_accumulate(double *P, const void *plI, int32_t elem_bytes, int64_t 
     return TRPL_OK;
 }
 
+/* ------------------------------------------------------------------ weighted sse accumulate (probs.py:40) */
+int trpl_sse_accumulate_w_dev(double *P, const void *plI, int32_t elem_bytes, int64_t rows, int64_t n_obs, int64_t ld,
+                              const double *values, const double *wts, const double *mag, void *stream)
+{
+    if (elem_bytes != 4 && elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "elem_bytes must be 4 or 8");
+    if (rows < 0 || n_obs < 0 || ld < n_obs) return api_fail(TRPL_ERR_ARG, "bad shape");
+    if (rows == 0) return TRPL_OK;
+    if (!P || !mag || (n_obs && (!plI || !values || !wts))) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
+    hipError_t e = trpl::launch_sse_accumulate_w(P, plI, elem_bytes, rows, n_obs, ld, values, wts, mag, (hipStream_t)stream);
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "sse_accumulate_w launch: %s", hipGetErrorString(e));
+    return TRPL_OK;
+}
+
+// the weights of one curve, host data: finite and >= 0
+static int check_weights(const double *w, int64_t n, int c)
+{
+    for (int64_t i = 0; i < n; i++)
+        if (!(w[i] >= 0.0) || !(w[i] < INFINITY))
+            return api_fail(TRPL_ERR_ARG, "weight of curve %d, index %lld is %g: weights must be finite and >= 0", c, (long long)i, w[i]);
+    return TRPL_OK;
+}
+
+int trpl_sse_accumulate_w(double *P, const void *plI, int32_t elem_bytes, int64_t rows, int64_t n_obs, int64_t ld,
+                          const double *values, const double *wts, const double *mag, int32_t device, double *seconds)
+{
+    ProfRange range("trpl_sse_accumulate_w (prob, uncertainty-weighted)");
+    if (elem_bytes != 4 && elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "elem_bytes must be 4 or 8");
+    if (rows < 0 || n_obs < 0 || ld < n_obs) return api_fail(TRPL_ERR_ARG, "bad shape");
+    if (seconds) *seconds = 0.0;
+    if (rows == 0) return TRPL_OK;
+    if (!P || !mag || (n_obs && (!plI || !values || !wts))) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
+    if (int rc = check_weights(wts, n_obs, 0)) return rc;
+    if (int rc = select_device(device)) return rc;
+    HostPin pin;
+    CallScope cs;
+    HIP_TRY(cs.open());
+    const double t0 = now_s();
+    DevBuf dP, dpl, dv, dw, dm;
+    const size_t rowb = (size_t)n_obs * elem_bytes;
+    if (n_obs) pin.pin(plI, ((size_t)(rows - 1) * ld + n_obs) * elem_bytes);
+    HIP_TRY(dP.alloc((size_t)rows * 8, cs.st));
+    HIP_TRY(dpl.alloc(rowb * rows, cs.st));
+    HIP_TRY(dv.alloc((size_t)n_obs * 8, cs.st));
+    HIP_TRY(dw.alloc((size_t)n_obs * 8, cs.st));
+    HIP_TRY(dm.alloc((size_t)rows * 8, cs.st));
+    HIP_TRY(hipMemcpyAsync(dP.p, P, (size_t)rows * 8, hipMemcpyHostToDevice, cs.st));
+    if (n_obs) {
+        HIP_TRY(hipMemcpy2DAsync(dpl.p, rowb, plI, (size_t)ld * elem_bytes, rowb, (size_t)rows, hipMemcpyHostToDevice, cs.st));
+        HIP_TRY(hipMemcpyAsync(dv.p, values, (size_t)n_obs * 8, hipMemcpyHostToDevice, cs.st));
+        HIP_TRY(hipMemcpyAsync(dw.p, wts, (size_t)n_obs * 8, hipMemcpyHostToDevice, cs.st));
+    }
+    HIP_TRY(hipMemcpyAsync(dm.p, mag, (size_t)rows * 8, hipMemcpyHostToDevice, cs.st));
+    if (int rc = trpl_sse_accumulate_w_dev(dP.as<double>(), dpl.p, elem_bytes, rows, n_obs, n_obs, dv.as<double>(),
+                                           dw.as<double>(), dm.as<double>(), cs.st))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(cs.st));
+    HIP_TRY(hipMemcpyAsync(P, dP.p, (size_t)rows * 8, hipMemcpyDeviceToHost, cs.st));
+    if (seconds) *seconds = now_s() - t0;
+    HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
+    return TRPL_OK;
+}
+
 /* ------------------------------------------------------------------ loglik from stored PL */
 static int loglik_from_pl_impl(const void *plI, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld,
                                const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
                                int64_t n_obs, const double *mag, const int32_t *status, double *P, double *sse,
-                               double *esum, uint32_t flags, void *stream)
+                               double *esum, uint32_t flags, void *stream, const double *wts = nullptr)
 {
     if (int rc = no_moments_flag(flags)) return rc;
     if (elem_bytes != 4 && elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "elem_bytes must be 4 or 8");
@@ -707,7 +793,7 @@ static int loglik_from_pl_impl(const void *plI, int32_t elem_bytes, int64_t rows
     if (rows == 0) return TRPL_OK;
     if (!plI || !mag || (n_obs && !obs) || (!P && !sse && !esum)) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
     hipError_t e = trpl::launch_pl_loglik(plI, elem_bytes, rows, ld, obs, obs_hi, obs_dx, obs_h, n_obs, mag, status, P, sse, flags,
-                                          (hipStream_t)stream, esum);
+                                          (hipStream_t)stream, esum, wts);
     if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "pl_loglik launch: %s", hipGetErrorString(e));
     return TRPL_OK;
 }
@@ -730,16 +816,44 @@ int trpl_loglik_moments_from_pl_dev(const void *plI, int32_t elem_bytes, int64_t
                                flags, stream);
 }
 
+int trpl_loglik_weighted_from_pl_dev(const void *plI, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld,
+                                     const double *obs, const double *wts, const int32_t *obs_hi, const double *obs_dx,
+                                     const double *obs_h, int64_t n_obs, const double *mag, const int32_t *status, double *P,
+                                     double *sse, double *esum, uint32_t flags, void *stream)
+{
+    if (rows > 0 && n_obs > 0 && !wts) return api_fail(TRPL_ERR_ARG, "wts must not be NULL");
+    return loglik_from_pl_impl(plI, elem_bytes, rows, ncol, ld, obs, obs_hi, obs_dx, obs_h, n_obs, mag, status, P, sse, esum,
+                               flags, stream, n_obs > 0 ? wts : nullptr);
+}
+
 /* ------------------------------------------------------------------ fused loglik -------- */
+// Which of the two flags the entry points set themselves a call may carry: wts -- the weighted entry points (they set
+// TRPL_FLAG_WEIGHTED; with TRPL_FLAG_MOMENTS: refused, the weighted sink already emits both sums); esum alone -- the moments entry
+// points (they set TRPL_FLAG_MOMENTS); every other caller must carry neither.
+static int entry_flags(uint32_t &flags, bool esum, bool wts)
+{
+    if (wts) {
+        if (flags & TRPL_FLAG_MOMENTS)
+            return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_MOMENTS does not combine with TRPL_FLAG_WEIGHTED: the weighted sink already emits both sums");
+        flags |= TRPL_FLAG_WEIGHTED;
+        return TRPL_OK;
+    }
+    if (esum) {
+        if (int rc = no_weighted_flag(flags)) return rc;
+        flags |= TRPL_FLAG_MOMENTS;
+        return TRPL_OK;
+    }
+    return no_moments_flag(flags);
+}
+
 static int loglik_dev_impl(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
                            int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
                            const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
                            int64_t obs_ld, const int64_t *n_obs, double *P, double *sse, int32_t *status,
-                           int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream, double *esum = nullptr)
+                           int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream, double *esum = nullptr,
+                           const double *wts = nullptr)
 {
-    // esum: the moments entry points (they set TRPL_FLAG_MOMENTS themselves); every other caller must not carry the flag
-    if (esum) flags |= TRPL_FLAG_MOMENTS;
-    else if (int rc = no_moments_flag(flags)) return rc;
+    if (int rc = entry_flags(flags, esum != nullptr, wts != nullptr)) return rc;
     if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
     if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
     if (C < 1 || C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAX_CURVES);
@@ -772,6 +886,7 @@ static int loglik_dev_impl(const double *X, int64_t S, int32_t C, const double *
         a.obs_h = obs_h ? obs_h + (int64_t)c0 * obs_ld : nullptr;
         a.obs_ld = obs_ld; a.sse = sse + (int64_t)c0 * S;
         a.esum = esum ? esum + (int64_t)c0 * S : nullptr;
+        a.wts = wts ? wts + (int64_t)c0 * obs_ld : nullptr;
         a.status = status ? status + (int64_t)c0 * S : nullptr;
         a.iters_total = iters_total ? iters_total + (int64_t)c0 * S : nullptr;
         a.floor_col = floor_col ? floor_col + (int64_t)c0 * S : nullptr;
@@ -813,9 +928,9 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
                             const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
                             int64_t obs_ld, const int64_t *n_obs, double *P, double *sse, int32_t *status,
                             int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device, double *seconds,
-                            double *esum = nullptr)
+                            double *esum = nullptr, const double *wts = nullptr)
 {
-    if (!esum) { if (int rc = no_moments_flag(flags)) return rc; }
+    { uint32_t f = flags; if (int rc = entry_flags(f, esum != nullptr, wts != nullptr)) return rc; }
     if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
     if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
     if (C < 1 || C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAX_CURVES);
@@ -830,7 +945,7 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
     if (interp) {                                    // the brackets are host data here: validate them
         if (int rc = check_brackets(obs_hi, obs_dx, obs_h, C, obs_ld, n_obs, T)) return rc;
     }
-    DevBuf dX, ddN, dobs, dhi, ddx, dh, dP, dsse, dst, dit, dfl, des;
+    DevBuf dX, ddN, dobs, dhi, ddx, dh, dP, dsse, dst, dit, dfl, des, dwt;
     const size_t nsys = (size_t)S * C, nobs = (size_t)C * obs_ld;
     HIP_TRY(dX.alloc((size_t)S * 13 * 8, cs.st));
     HIP_TRY(ddN.alloc((size_t)C * L * 8, cs.st));
@@ -841,6 +956,7 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
     HIP_TRY(dit.alloc(nsys * 8, cs.st));
     if (floor_col) HIP_TRY(dfl.alloc(nsys * 4, cs.st));
     if (esum) HIP_TRY(des.alloc(nsys * 8, cs.st));
+    if (wts) { HIP_TRY(dwt.alloc(nobs * 8, cs.st)); HIP_TRY(hipMemcpyAsync(dwt.p, wts, nobs * 8, hipMemcpyHostToDevice, cs.st)); }
     HIP_TRY(hipMemcpyAsync(dX.p, X, (size_t)S * 13 * 8, hipMemcpyHostToDevice, cs.st));
     HIP_TRY(hipMemcpyAsync(ddN.p, dN, (size_t)C * L * 8, hipMemcpyHostToDevice, cs.st));
     HIP_TRY(hipMemcpyAsync(dobs.p, obs, nobs * 8, hipMemcpyHostToDevice, cs.st));
@@ -856,7 +972,8 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
                                  ddN.as<double>(), dobs.as<double>(), interp ? dhi.as<int32_t>() : nullptr,
                                  interp ? ddx.as<double>() : nullptr, interp ? dh.as<double>() : nullptr, obs_ld, n_obs,
                                  dP.as<double>(), dsse.as<double>(), dst.as<int32_t>(), dit.as<int64_t>(),
-                                 dfl.as<int32_t>(), flags, cs.st, esum ? des.as<double>() : nullptr))
+                                 dfl.as<int32_t>(), flags, cs.st, esum ? des.as<double>() : nullptr,
+                                 wts ? dwt.as<double>() : nullptr))
         return rc;
     HIP_TRY(hipStreamSynchronize(cs.st));
     if (seconds) *seconds = now_s() - t0;
@@ -919,6 +1036,97 @@ int trpl_loglik_moments(const double *X, int64_t S, int32_t C, const double *len
     if (S == 0) flags &= ~(uint32_t)TRPL_FLAG_MOMENTS;
     return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
                             obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds, esum);
+}
+
+/* ------------------------------------------------------------------ uncertainty-weighted fused loglik (probs.py:40) */
+int trpl_loglik_weighted_dev(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
+                             int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN, const double *obs,
+                             const double *wts, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                             int64_t obs_ld, const int64_t *n_obs, double *P, double *sse, double *esum, int32_t *status,
+                             int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream)
+{
+    if (S > 0 && (!esum || !wts)) return api_fail(TRPL_ERR_ARG, "esum and wts must not be NULL");
+    if (S == 0) flags &= ~(uint32_t)TRPL_FLAG_WEIGHTED;           // nothing is launched; the common checks still run
+    return loglik_dev_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
+                           obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, stream, esum, S > 0 ? wts : nullptr);
+}
+
+int trpl_loglik_weighted(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
+                         int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN, const double *obs,
+                         const double *wts, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                         int64_t obs_ld, const int64_t *n_obs, double *P, double *sse, double *esum, int32_t *status,
+                         int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device, double *seconds)
+{
+    ProfRange range("trpl_loglik_weighted (pvSim + fastlog + uncertainty-weighted prob, fused)");
+    if (S > 0 && (!esum || !wts)) return api_fail(TRPL_ERR_ARG, "esum and wts must not be NULL");
+    const bool interp = obs_hi || obs_dx || obs_h;
+    if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
+    if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
+    if (S == 0) flags &= ~(uint32_t)TRPL_FLAG_WEIGHTED;
+    if (S > 0 && n_obs && C >= 1 && C <= TRPL_MAX_CURVES && obs_ld >= 1)      // the weights are host data here: validate them
+        for (int c = 0; c < C; c++)
+            if (n_obs[c] >= 1 && n_obs[c] <= obs_ld)
+                if (int rc = check_weights(wts + (int64_t)c * obs_ld, n_obs[c], c)) return rc;
+    return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
+                            obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds, esum,
+                            S > 0 ? wts : nullptr);
+}
+
+static int check_mag_w(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C, const double *P, bool need_P)
+{
+    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
+    if (C < 1 || C > TRPL_MAG_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAG_MAX_CURVES);
+    if (!wsum) return api_fail(TRPL_ERR_ARG, "wsum must not be NULL");
+    for (int c = 0; c < C; c++)
+        if (!(wsum[c] >= 0.0) || !(wsum[c] < INFINITY)) return api_fail(TRPL_ERR_ARG, "wsum[%d]=%g must be finite and >= 0", c, wsum[c]);
+    if (S > 0 && (!sse || !esum || (need_P && !P))) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
+    return TRPL_OK;
+}
+
+int trpl_mag_grid_w(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C, const double *offsets,
+                    int64_t M, double *P)
+{
+    if (M < 0) return api_fail(TRPL_ERR_ARG, "M must be >= 0");
+    if (int rc = check_mag_w(sse, esum, wsum, S, C, P, M > 0)) return rc;
+    if (S == 0 || M == 0) return TRPL_OK;
+    if (!offsets) return api_fail(TRPL_ERR_ARG, "offsets must not be NULL");
+    trpl::mag_grid_host_w(sse, esum, wsum, S, C, offsets, M, P);
+    return TRPL_OK;
+}
+
+int trpl_mag_grid_w_dev(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C, const double *offsets,
+                        int64_t M, double *P, void *stream)
+{
+    if (M < 0) return api_fail(TRPL_ERR_ARG, "M must be >= 0");
+    if (int rc = check_mag_w(sse, esum, wsum, S, C, P, M > 0)) return rc;
+    if (S == 0 || M == 0) return TRPL_OK;
+    if (!offsets) return api_fail(TRPL_ERR_ARG, "offsets must not be NULL");
+    hipError_t e = trpl::launch_mag_grid_w(sse, esum, wsum, S, C, offsets, M, P, (hipStream_t)stream);
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mag_grid_w launch: %s", hipGetErrorString(e));
+    return TRPL_OK;
+}
+
+int trpl_mag_profile_w(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C, uint32_t flags,
+                       double *best, double *P)
+{
+    if (flags & ~(uint32_t)TRPL_MAG_PER_CURVE) return api_fail(TRPL_ERR_ARG, "trpl_mag_profile_w: unknown flag bits 0x%x", flags);
+    if (int rc = check_mag_w(sse, esum, wsum, S, C, P, true)) return rc;
+    if (S == 0) return TRPL_OK;
+    if (!best) return api_fail(TRPL_ERR_ARG, "best must not be NULL");
+    trpl::mag_profile_host_w(sse, esum, wsum, S, C, (flags & TRPL_MAG_PER_CURVE) != 0, best, P);
+    return TRPL_OK;
+}
+
+int trpl_mag_profile_w_dev(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C, uint32_t flags,
+                           double *best, double *P, void *stream)
+{
+    if (flags & ~(uint32_t)TRPL_MAG_PER_CURVE) return api_fail(TRPL_ERR_ARG, "trpl_mag_profile_w: unknown flag bits 0x%x", flags);
+    if (int rc = check_mag_w(sse, esum, wsum, S, C, P, true)) return rc;
+    if (S == 0) return TRPL_OK;
+    if (!best) return api_fail(TRPL_ERR_ARG, "best must not be NULL");
+    hipError_t e = trpl::launch_mag_profile_w(sse, esum, wsum, S, C, (flags & TRPL_MAG_PER_CURVE) != 0, best, P, (hipStream_t)stream);
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mag_profile_w launch: %s", hipGetErrorString(e));
+    return TRPL_OK;
 }
 
 static int check_mag(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C, const double *P, bool need_P)

@@ -70,6 +70,7 @@ struct StepArgs {
     uint8_t pair_cA[kMaxCurves], pair_oA[kMaxCurves], pair_cB[kMaxCurves], pair_oB[kMaxCurves];
     CurveConst curve[kMaxCurves];
     double *esum;           // [C][S] out: sum of the errors whose squares make sse (TRPL_FLAG_MOMENTS kernels only), or nullptr
+    const double *wts;      // [C][obs_ld] observation weights, indexed like obs (TRPL_FLAG_WEIGHTED kernels only), or nullptr
 };
 
 // BDF coefficient table of tEvol (pvSimPCR.py:241-250): time step t takes the row min(t, 4) -- order 1 (Euler) at t = 0,
@@ -110,6 +111,13 @@ hipError_t launch_stepper_moments_pair(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_moments_predict_fast(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_moments_predict_strict(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_moments_predict_pair(const StepArgs &a, hipStream_t stream);
+// TRPL_FLAG_WEIGHTED (stepper_weighted_*.hip): the moments steppers whose sink weights every term
+hipError_t launch_stepper_weighted_fast(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_weighted_strict(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_weighted_pair(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_weighted_predict_fast(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_weighted_predict_strict(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_weighted_predict_pair(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_mixed(const StepArgs &a, hipStream_t stream);           // L >= 128; `make EXPERIMENTAL=1` only: the default
 hipError_t launch_stepper_hist32(const StepArgs &a, hipStream_t stream);          // L = 256 / 512;   library must not reference them
 
@@ -122,7 +130,10 @@ hipError_t launch_reduce_curves(double *P, const double *sse, int64_t S, int C, 
 hipError_t launch_pl_loglik(const void *pl, int elem_bytes, int64_t rows, int64_t ld, const double *obs,
                             const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t n_obs,
                             const double *mag, const int32_t *status, double *P, double *sse_out, uint32_t flags,
-                            hipStream_t stream, double *esum_out = nullptr);
+                            hipStream_t stream, double *esum_out = nullptr, const double *wts = nullptr);
+// trpl_sse_accumulate_w: launch_sse_accumulate with every squared residual times wts[i] (probs.py:40)
+hipError_t launch_sse_accumulate_w(double *P, const void *pl, int elem_bytes, int64_t rows, int64_t n_obs, int64_t ld,
+                                   const double *values, const double *wts, const double *mag, hipStream_t stream);
 // the magnitude-offset grid / profile from the moments (trpl_mag_grid, trpl_mag_profile): host forms and their kernels
 constexpr int kMagMaxCurves = 64;          // TRPL_MAG_MAX_CURVES
 constexpr int kMagChunk = 256;             // offsets per launch (kernel arguments)
@@ -134,6 +145,15 @@ hipError_t launch_mag_grid(const double *sse, const double *esum, const int64_t 
                            const double *offsets, int64_t M, double *P, hipStream_t stream);
 hipError_t launch_mag_profile(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, bool per_curve,
                               double *best, double *P, hipStream_t stream);
+// the weighted forms (trpl_mag_grid_w, trpl_mag_profile_w): wsum[c] = sum_i w_ci in place of n_obs[c]
+void mag_grid_host_w(const double *sse, const double *esum, const double *wsum, int64_t S, int C, const double *offsets,
+                     int64_t M, double *P);
+void mag_profile_host_w(const double *sse, const double *esum, const double *wsum, int64_t S, int C, bool per_curve,
+                        double *best, double *P);
+hipError_t launch_mag_grid_w(const double *sse, const double *esum, const double *wsum, int64_t S, int C,
+                             const double *offsets, int64_t M, double *P, hipStream_t stream);
+hipError_t launch_mag_profile_w(const double *sse, const double *esum, const double *wsum, int64_t S, int C, bool per_curve,
+                                double *best, double *P, hipStream_t stream);
 
 // posterior.hip: the consumer of P[S] (weights, weighted moments, weighted histograms)
 size_t posterior_workspace_bytes(int D);

@@ -113,6 +113,59 @@ def mag_profile_device(sse, esum, n_obs, best, P, per_curve=False):
                                                _chk(best, torch.float64, "best"), _chk(P, torch.float64, "P"), _stream()))
 
 
+def loglik_weighted_device(X, init_params, lengths, Time, L, T, obs, wts, n_obs, P, sse, esum, status=None,
+                           iters_total=None, tol=7, MAX=10000, plT=1, flags=0, floor_col=None, obs_hi=None, obs_dx=None,
+                           obs_h=None):
+    """trpl_loglik_weighted_dev: loglik_moments_device with the observation weights wts, a device tensor shaped like obs:
+    sse (C,S) = sum w e^2, esum (C,S) = sum w e, P (S,) -= sum_c sse.  The weights are NOT checked here (no
+    synchronisation): finite and >= 0 is the caller's responsibility."""
+    import torch
+    S, Cn = X.shape[0], init_params.shape[0]
+    interp = obs_hi is not None
+    if X.shape[1] != 13 or init_params.shape[1] != L or obs.shape[0] != Cn or tuple(sse.shape) != (Cn, S) \
+            or tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (S,) or wts.shape != obs.shape \
+            or (interp and not (obs.shape == obs_hi.shape == obs_dx.shape == obs_h.shape)):
+        raise ValueError("shape mismatch")
+    lengths = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.float64), (Cn,)))
+    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
+    _abi.check(_abi.lib().trpl_loglik_weighted_dev(
+        _chk(X, torch.float64, "X"), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol),
+        int(MAX), _chk(init_params, torch.float64, "init_params"), _chk(obs, torch.float64, "obs"),
+        _chk(wts, torch.float64, "wts"),
+        _chk(obs_hi, torch.int32, "obs_hi") if interp else None, _chk(obs_dx, torch.float64, "obs_dx") if interp else None,
+        _chk(obs_h, torch.float64, "obs_h") if interp else None, obs.shape[1], _abi.ptr(n_obs),
+        _chk(P, torch.float64, "P"), _chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
+        None if status is None else _chk(status, torch.int32, "status"),
+        None if iters_total is None else _chk(iters_total, torch.int64, "iters_total"),
+        None if floor_col is None else _chk(floor_col, torch.int32, "floor_col"), int(flags), _stream()))
+
+
+def mag_grid_w_device(sse, esum, wsum, offsets, P):
+    """trpl_mag_grid_w_dev: mag_grid_device from the weighted moments; wsum a host sequence (C,), the sum of each
+    curve's weights, in place of n_obs."""
+    import torch
+    Cn, S = sse.shape
+    off = np.ascontiguousarray(offsets, dtype=np.float64).ravel()
+    wsum = np.ascontiguousarray(np.broadcast_to(np.asarray(wsum, dtype=np.float64), (Cn,)))
+    if tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (len(off), S):
+        raise ValueError("shape mismatch")
+    _abi.check(_abi.lib().trpl_mag_grid_w_dev(_chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
+                                              _abi.ptr(wsum), S, Cn, _abi.ptr(off), len(off),
+                                              _chk(P, torch.float64, "P"), _stream()))
+
+
+def mag_profile_w_device(sse, esum, wsum, best, P, per_curve=False):
+    """trpl_mag_profile_w_dev: mag_profile_device from the weighted moments (wsum as in mag_grid_w_device)."""
+    import torch
+    Cn, S = sse.shape
+    wsum = np.ascontiguousarray(np.broadcast_to(np.asarray(wsum, dtype=np.float64), (Cn,)))
+    if tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (S,) or tuple(best.shape) != ((Cn, S) if per_curve else (S,)):
+        raise ValueError("shape mismatch")
+    _abi.check(_abi.lib().trpl_mag_profile_w_dev(_chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
+                                                 _abi.ptr(wsum), S, Cn, _abi.MAG_PER_CURVE if per_curve else 0,
+                                                 _chk(best, torch.float64, "best"), _chk(P, torch.float64, "P"), _stream()))
+
+
 def solve_pl_device(matPar, Length, Time, L, T, dN, plI, status=None, iters_total=None, tol=7, MAX=10000, plT=1,
                     flags=0):
     """trpl_solve_pl_dev: matPar (S,12) f64, dN (L,) f64, plI (S, T//plT+1) f32/f64 out."""
@@ -248,6 +301,41 @@ def loglik_moments_from_pl_device(pl, obs, mag, P=None, sse=None, esum=None, obs
         obs.shape[0], _chk(mag, torch.float64, "mag"), None if status is None else _chk(status, torch.int32, "status"),
         None if P is None else _chk(P, torch.float64, "P"), None if sse is None else _chk(sse, torch.float64, "sse"),
         None if esum is None else _chk(esum, torch.float64, "esum"), int(flags), _stream()))
+
+
+def loglik_weighted_from_pl_device(pl, obs, wts, mag, P=None, sse=None, esum=None, obs_hi=None, obs_dx=None, obs_h=None,
+                                   ncol=None, flags=0, status=None):
+    """trpl_loglik_weighted_from_pl_dev: loglik_moments_from_pl_device with the weights wts (n_obs,) f64 of the
+    observations: sse = sum w e^2, esum = sum w e per row."""
+    import torch
+    if pl.dim() != 2 or pl.dtype not in (torch.float32, torch.float64):
+        raise ValueError("pl must be a 2-D float32/float64 tensor")
+    if wts.shape != obs.shape:
+        raise ValueError("shape mismatch")
+    rows, ld = pl.shape
+    interp = obs_hi is not None
+    _abi.check(_abi.lib().trpl_loglik_weighted_from_pl_dev(
+        _chk(pl, pl.dtype, "pl"), pl.element_size(), rows, int(ld if ncol is None else ncol), ld,
+        _chk(obs, torch.float64, "obs"), _chk(wts, torch.float64, "wts"),
+        _chk(obs_hi, torch.int32, "obs_hi") if interp else None,
+        _chk(obs_dx, torch.float64, "obs_dx") if interp else None, _chk(obs_h, torch.float64, "obs_h") if interp else None,
+        obs.shape[0], _chk(mag, torch.float64, "mag"), None if status is None else _chk(status, torch.int32, "status"),
+        None if P is None else _chk(P, torch.float64, "P"), None if sse is None else _chk(sse, torch.float64, "sse"),
+        None if esum is None else _chk(esum, torch.float64, "esum"), int(flags), _stream()))
+
+
+def sse_accumulate_w_device(P, pl, values, wts, mag):
+    """trpl_sse_accumulate_w_dev: P (rows,) f64 -= sum_i ((pl[j,i] + mag[j] - values[i])^2 * wts[i]), fp64, index order;
+    pl (rows, n_obs) f32/f64 with contiguous rows, values / wts (n_obs,), mag (rows,) f64."""
+    import torch
+    if pl.dim() != 2 or pl.dtype not in (torch.float32, torch.float64):
+        raise ValueError("pl must be a 2-D float32/float64 tensor")
+    rows, n = pl.shape
+    if tuple(P.shape) != (rows,) or tuple(mag.shape) != (rows,) or tuple(values.shape) != (n,) or tuple(wts.shape) != (n,):
+        raise ValueError("shape mismatch")
+    _abi.check(_abi.lib().trpl_sse_accumulate_w_dev(
+        _chk(P, torch.float64, "P"), _chk(pl, pl.dtype, "pl"), pl.element_size(), rows, n, n,
+        _chk(values, torch.float64, "values"), _chk(wts, torch.float64, "wts"), _chk(mag, torch.float64, "mag"), _stream()))
 
 
 def solve_pl_snap_device(matPar, Length, Time, L, T, dN, plI, snap_steps, plN=None, plP=None, plE=None, status=None,

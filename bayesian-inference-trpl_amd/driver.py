@@ -14,7 +14,7 @@ import time
 import numpy as np
 
 from . import _abi
-from .likelihood import fastlog, prob
+from .likelihood import fastlog, prob, weights_from_uncertainty
 from .model import pvSim
 from .sampler import make_grid
 
@@ -138,7 +138,7 @@ def overlap_window(full, done, budget, num_curves):
 def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=None, pl_f32=False,
            normalize=False, strict=False, device=0, info=None, times=None, fp32=False, devices=None, kernel=None,
            mixed=False, bundle=1, hist32=False, bdf_order=None, extra_flags=0, predict=False, mag_grid=None,
-           mag_profile=False):
+           mag_profile=False, weights=None):
     """Fused likelihood of one experiment (trpl_loglik / trpl_loglik_obs / trpl_loglik_multi).
 
     X (S,13) solver units; init_params (C,L) nm^-3; lengths scalar or (C,); obs = list of C
@@ -159,7 +159,14 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
     the likelihood at X[:, 12] + mag_grid[m] (accumulated into P if P (M, S) is given).  mag_profile=True (or
     "per_curve"): returns (best, P) -- the likelihood-maximising offset, (S,) or (C, S), and the likelihood there.
     Single-device calls only; info also receives esum and P, the one-offset likelihood trpl_loglik would return.
+    weights: a list of C arrays shaped like obs (sorted together with times when off-grid), finite and >= 0 -- the
+    uncertainty-weighted likelihood P[s] -= sum_c sum_i w_ci e_i^2 (trpl_loglik_weighted; likelihood.weights_from_uncertainty
+    gives the chi-square weights 1 / (2 u^2) of probs.py:40).  A zero weight masks an observation.  info receives the weighted
+    sse and esum and wsum (C,), the sum of each curve's weights.  Combines with mag_grid / mag_profile (trpl_mag_grid_w,
+    trpl_mag_profile_w); single-device calls only.
     """
+    if weights is not None and devices is not None:
+        raise ValueError("weights: not available with devices= (trpl_loglik_multi has no weighted form)")
     moments = mag_grid is not None or bool(mag_profile)
     if moments:
         if mag_grid is not None and mag_profile:
@@ -178,12 +185,15 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
     lengths = np.full(Cn, float(lengths)) if np.isscalar(lengths) else np.ascontiguousarray(lengths, dtype=float)
     if lengths.shape != (Cn,) or len(obs) != Cn or (times is not None and len(times) != Cn):
         raise ValueError("need one length and one observation set per curve")
+    if weights is not None and len(weights) != Cn:
+        raise ValueError("weights: need one array of weights per curve")
     n_obs = np.array([len(o) for o in obs], dtype=np.int64)
     obs_ld = int(n_obs.max())
     obs_mat = np.zeros((Cn, obs_ld))
     hi_mat = np.ones((Cn, obs_ld), dtype=np.int32)
     dx_mat = np.zeros((Cn, obs_ld))
     h_mat = np.ones((Cn, obs_ld))
+    w_mat = np.zeros((Cn, obs_ld)) if weights is not None else None
     if times is not None:
         if plT != 1:
             raise ValueError("off-grid observation times need plT = 1")
@@ -201,6 +211,11 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
             tc, o = tc[order], o[order]
             hi_mat[c, :len(o)], dx_mat[c, :len(o)], h_mat[c, :len(o)] = bracket_times(sim_t, tc)
         obs_mat[c, :len(o)] = o
+        if weights is not None:
+            w = np.asarray(weights[c], dtype=float)
+            if w.shape != o.shape:
+                raise ValueError("curve %d: %d weights for %d observations" % (c, len(w), len(o)))
+            w_mat[c, :len(o)] = w[order] if times is not None else w
     if P is None:
         P = np.zeros(S)
     if not (P.dtype == np.float64 and P.flags.c_contiguous and P.shape == (S,)):
@@ -215,6 +230,36 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
         | _abi.flag_bdf_order(bdf_order) | int(extra_flags) | (_abi.FLAG_PREDICT if predict else 0)
     sec = _abi.C.c_double(0.0)
     lib = _abi.lib()
+    if weights is not None:
+        import math
+        off = times is not None
+        esum = np.zeros((Cn, S))
+        wsum = np.array([math.fsum(w_mat[c, :n_obs[c]]) for c in range(Cn)])
+        _abi.check(lib.trpl_loglik_weighted(
+            _abi.ptr(X), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol), int(MAX), _abi.ptr(ini),
+            _abi.ptr(obs_mat), _abi.ptr(w_mat), _abi.ptr(hi_mat) if off else None, _abi.ptr(dx_mat) if off else None,
+            _abi.ptr(h_mat) if off else None, obs_ld, _abi.ptr(n_obs), _abi.ptr(P), _abi.ptr(sse), _abi.ptr(esum),
+            _abi.ptr(status), _abi.ptr(iters), _abi.ptr(floor_col), flags, int(device), _abi.C.byref(sec)))
+        if info is not None:
+            info.update(sse=sse, esum=esum, wsum=wsum, status=status, iters_total=iters, floor_col=floor_col,
+                        seconds=sec.value, P=P)
+        if mag_grid is not None:
+            offs = np.ascontiguousarray(mag_grid, dtype=np.float64).ravel()
+            Pm = np.zeros((len(offs), S)) if P_out is None else P_out
+            if not (Pm.dtype == np.float64 and Pm.flags.c_contiguous and Pm.shape == (len(offs), S)):
+                raise ValueError("P must be a contiguous float64 array of shape (len(mag_grid), S)")
+            _abi.check(lib.trpl_mag_grid_w(_abi.ptr(sse), _abi.ptr(esum), _abi.ptr(wsum), S, Cn, _abi.ptr(offs), len(offs), _abi.ptr(Pm)))
+            return Pm
+        if mag_profile:
+            per_curve = mag_profile == "per_curve"
+            Pp = np.zeros(S) if P_out is None else P_out
+            if not (Pp.dtype == np.float64 and Pp.flags.c_contiguous and Pp.shape == (S,)):
+                raise ValueError("P must be a contiguous float64 array of shape (S,)")
+            best = np.zeros((Cn, S) if per_curve else S)
+            _abi.check(lib.trpl_mag_profile_w(_abi.ptr(sse), _abi.ptr(esum), _abi.ptr(wsum), S, Cn,
+                                              _abi.MAG_PER_CURVE if per_curve else 0, _abi.ptr(best), _abi.ptr(Pp)))
+            return best, Pp
+        return P
     if moments:
         off = times is not None
         esum = np.zeros((Cn, S))
@@ -280,14 +325,16 @@ def _bundle_of(gpu_info, L):
 
 def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_params, normalize, pl_dtype, group,
                        num_gpus, gpu_id, device, solver_time, err_sq_time, sim_t, bundle=1, literal=False, predict=False,
-                       mag_grid=None):
+                       mag_grid=None, weighted=False):
     """Several experiments, fused option on: the reference's own loop order -- curves -> sample blocks ->
     experiments (bayeslib.py:117-171) -- with the block's PL matrix kept in HBM: one solve per (curve, block)
     (trpl_solve_pl_dev), then one pass over it per experiment (trpl_loglik_from_pl_dev: normalise, clamp,
     log10, time interpolation, squared error).  Only X goes in and P comes out.  literal: observations_on_grid's switch
     (gpu_info["interpolate_prefix"]).  mag_grid (gpu_info["mag_grid"]): P is (n_exp, M * S); each pass over the PL block also
     returns the first moment of the errors (trpl_loglik_moments_from_pl_dev), and after a block's last curve
-    trpl_mag_grid_dev fills the M rows of every experiment."""
+    trpl_mag_grid_dev fills the M rows of every experiment.  weighted (gpu_info["weighted"]): every pass is
+    trpl_loglik_weighted_from_pl_dev with the weights of the experiment's uncertainty column (and trpl_mag_grid_w_dev)."""
+    import math
     import time
 
     import torch
@@ -306,6 +353,7 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
             for c in range(num_curves):
                 t = np.asarray(exp[0][c], dtype=float)
                 o = np.asarray(exp[1][c], dtype=float)
+                w = weights_from_uncertainty(exp[2][c]) if weighted else None
                 if observations_on_grid(t, sim_t, literal):                   # bayeslib.py:182-183, and prefixes of the grid (below)
                     per_curve.append((torch.from_numpy(np.ascontiguousarray(o)).to(dev), None))
                 else:
@@ -313,6 +361,9 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
                     hi, dx, h = bracket_times(sim_t, t[order])
                     per_curve.append((torch.from_numpy(np.ascontiguousarray(o[order])).to(dev),
                                       tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (hi, dx, h))))
+                    w = w[order] if weighted else None
+                if weighted:                                                  # (obs, brackets, weights, their sum)
+                    per_curve[-1] += (torch.from_numpy(np.ascontiguousarray(w)).to(dev), math.fsum(w))
             staged.append(per_curve)
         for blk in range(gpu_id * group, len(X), num_gpus * group):           # :131
             size = min(group, len(X) - blk)
@@ -336,7 +387,16 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
                 torch.cuda.synchronize(dev)
                 t1 = time.perf_counter()
                 for e, per_curve in enumerate(staged):                        # :171
-                    o_d, br = per_curve[c]
+                    o_d, br = per_curve[c][:2]
+                    if weighted:
+                        tdev.loglik_weighted_from_pl_device(pl_d, o_d, per_curve[c][2], mag_d,
+                                                            P=None if mag_grid is not None else P_d[e],
+                                                            sse=None if mag_grid is None else sse_d[e, c],
+                                                            esum=None if mag_grid is None else esum_d[e, c], flags=flags,
+                                                            status=st_d, obs_hi=None if br is None else br[0],
+                                                            obs_dx=None if br is None else br[1],
+                                                            obs_h=None if br is None else br[2])
+                        continue
                     if mag_grid is not None:
                         tdev.loglik_moments_from_pl_device(pl_d, o_d, mag_d, sse=sse_d[e, c], esum=esum_d[e, c], flags=flags,
                                                            status=st_d, obs_hi=None if br is None else br[0],
@@ -352,6 +412,9 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
                 err_sq_time[gpu_id] += time.perf_counter() - t1
             if mag_grid is not None:
                 for e, per_curve in enumerate(staged):
+                    if weighted:
+                        tdev.mag_grid_w_device(sse_d[e], esum_d[e], [per_curve[c][3] for c in range(num_curves)], mag_grid, P_d[e])
+                        continue
                     tdev.mag_grid_device(sse_d[e], esum_d[e], [len(per_curve[c][0]) for c in range(num_curves)], mag_grid, P_d[e])
                 P.reshape(len(e_data), M, S_all)[:, :, blk:blk + size] = P_d.cpu().numpy()
                 continue
@@ -372,6 +435,11 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
     offsets[m] from ONE solve per sample (trpl_loglik_moments + trpl_mag_grid; the mag_grid loop of the reference's probs.lnP,
     probs.py:5-18).  X stays (S, 13); P must then be (n_exp, M * S), column m * S + s = sample s at offset m (mag_grid_samples
     builds the matching X).  Fused levels on one device only: anything else is a ValueError naming the option.
+    gpu_info['weighted'] = True (default False: nothing changes): the uncertainty column of the observations, e_data[e][2][c],
+    weights every squared error by 1 / (2 u^2) -- the line the reference has commented out (probs.py:40) -- on all three
+    levels: the fused single-experiment call (trpl_loglik_weighted), the resident-PL level
+    (trpl_loglik_weighted_from_pl_dev) and the unfused sequence (prob(..., weighted=True); interpolated rows take the weights
+    of their observation times).  Combines with 'mag_grid' and 'predict'; not with 'devices' or 'max_sims_per_block' > 1.
     """
     group = int(gpu_info["sims_per_gpu"])
     num_gpus = int(gpu_info["num_gpus"])
@@ -398,6 +466,12 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
 
     fused = bool(gpu_info.get("fused", False)) and LOG_PL and sim_params[4] == 1 and all(
         in_range(exp[0][c]) for exp in e_data for c in range(num_curves))
+    weighted = bool(gpu_info.get("weighted", False))
+    if weighted:
+        if gpu_info.get("devices") is not None:
+            raise ValueError("gpu_info['weighted'] does not combine with gpu_info['devices']: trpl_loglik_multi has no weighted form")
+        if int(gpu_info.get("max_sims_per_block", 1)) > 1:
+            raise ValueError("gpu_info['weighted'] does not combine with gpu_info['max_sims_per_block'] > 1 (TRPL_FLAG_WEIGHTED has no bundles)")
     mag_grid = gpu_info.get("mag_grid")
     if mag_grid is not None:
         mag_grid = np.ascontiguousarray(mag_grid, dtype=np.float64).ravel()
@@ -417,7 +491,7 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
         _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_params, NORMALIZE, pl_dtype,
                            group, num_gpus, gpu_id, device, solver_time, err_sq_time, sim_t,
                            bundle=_bundle_of(gpu_info, L), literal=bool(gpu_info.get("interpolate_prefix", False)),
-                           predict=predict, mag_grid=mag_grid)
+                           predict=predict, mag_grid=mag_grid, weighted=weighted)
         return
     if fused:
         # An experiment sampled exactly on the full simulation grid is compared point by point (the reference's bypass,
@@ -433,6 +507,7 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
             for e, exp in enumerate(e_data):
                 on_grid = fused_entry_point(exp[0], sim_t, num_curves, literal) == "trpl_loglik"
                 info = {}
+                wkw = {"weights": [weights_from_uncertainty(exp[2][c]) for c in range(num_curves)]} if weighted else {}
                 if mag_grid is not None:
                     Pe = P[e].reshape(len(mag_grid), len(X))
                     Pm = np.ascontiguousarray(Pe[:, blk:blk + size])
@@ -440,7 +515,7 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
                            [exp[1][c] for c in range(num_curves)], tol=sim_params[6], MAX=sim_params[7], P=Pm,
                            pl_f32=(pl_dtype == np.float32), normalize=NORMALIZE, device=device, info=info,
                            times=None if on_grid else [exp[0][c] for c in range(num_curves)], predict=predict,
-                           mag_grid=mag_grid)
+                           mag_grid=mag_grid, **wkw)
                     Pe[:, blk:blk + size] = Pm
                     solver_time[gpu_id] += info["seconds"]
                     continue
@@ -448,7 +523,7 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
                        [exp[1][c] for c in range(num_curves)], tol=sim_params[6], MAX=sim_params[7],
                        P=P[e, blk:blk + size], pl_f32=(pl_dtype == np.float32), normalize=NORMALIZE,
                        device=device, info=info, devices=gpu_info.get("devices"), bundle=_bundle_of(gpu_info, L),
-                       times=None if on_grid else [exp[0][c] for c in range(num_curves)], predict=predict)
+                       times=None if on_grid else [exp[0][c] for c in range(num_curves)], predict=predict, **wkw)
                 solver_time[gpu_id] += info["seconds"]
         return
 
@@ -553,6 +628,10 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
             misc_time[gpu_id] += misc
             for e, exp in enumerate(e_data):
                 plI_int[gpu_id] = ints[e]
+                if weighted:
+                    err_sq_time[gpu_id] += prob(P[e, blk:blk + size], ints[e], exp[1][ic_num], exp[2][ic_num], mag,
+                                                device=device, weighted=True)
+                    continue
                 err_sq_time[gpu_id] += prob(P[e, blk:blk + size], ints[e], exp[1][ic_num], None, mag, device=device)
             del ints                                                      # plI_int[gpu_id] keeps the last matrix, as there
             if overlap and nxt < len(tasks):                              # the previous result is gone: the window has room

@@ -170,6 +170,16 @@ extern "C" {
                                      launch checks.  FAST and STRICT, every L, both FAST kernels, with and without
                                      TRPL_FLAG_PREDICT; no snapshot / resume forms.  Refused with TRPL_ERR_UNSUPPORTED:
                                      TRPL_FLAG_FP32, _MIXED, _HIST32, TRPL_FLAG_BUNDLE(m > 1) */
+#define TRPL_FLAG_WEIGHTED 0x400000 /* the moments steppers whose sink multiplies every term by its observation's weight: sse = sum w_i e_i^2,
+                                     esum = sum w_i e_i (their own instantiations, trpl::weighted::[predict::][pair::]stepper...; the
+                                     existing kernels are the same machine code as without them).  SET BY trpl_loglik_weighted[_dev]
+                                     THEMSELVES: every other entry point takes no weights and answers TRPL_ERR_ARG before it touches
+                                     a device.  With TRPL_FLAG_MOMENTS: TRPL_ERR_ARG (the weighted sink already emits both sums).
+                                     trpl_kernel_name / trpl_kernel_variant accept it and name the instantiation after the usual
+                                     launch checks.  FAST and STRICT, every L, both FAST kernels, with and without
+                                     TRPL_FLAG_PREDICT; no snapshot / resume forms.  Refused with TRPL_ERR_UNSUPPORTED:
+                                     TRPL_FLAG_FP32, _MIXED, _HIST32, TRPL_FLAG_BUNDLE(m > 1).  Python: loglik(weights=),
+                                     gpu_info["weighted"] */
 #define TRPL_FLAG_KERNEL_PAIR 0x10    /* run the two-systems-per-wavefront stepper whatever the launch size (L = 128,
                                         fp64, not STRICT -- anything else is TRPL_ERR_ARG) */
 #define TRPL_FLAG_KERNEL_SINGLE 0x20  /* run the one-system-per-wavefront stepper whatever the launch size */
@@ -310,8 +320,14 @@ int trpl_log10_clamp_dev(void *x, int32_t elem_bytes, int64_t rows, int64_t cols
 /* ---------------------------------------------------------------------------------------
  * trpl_sse_accumulate -- replaces probs.prob(P, plI, values, uncertainty, mag_grid, TPB, BPG)
  * (probs.py:20-62):  P[j] -= sum_i (plI[j][i] + mag[j] - values[i])^2, fp64 accumulation in
- * index order.  `uncertainty` is not part of the ABI because the reference never reads it
- * (probs.py:40).
+ * index order.  `uncertainty` is not part of THIS call because the reference never reads it
+ * (probs.py:40, commented out).
+ * trpl_sse_accumulate_w -- the same with that line restored:
+ *     P[j] -= sum_i ((plI[j][i] + mag[j] - values[i])^2 * w[i]),     w [n_obs] fp64, w[i] = 1 / (2 uncertainty[i]^2)
+ * formed ONCE by the caller (Python: likelihood.weights_from_uncertainty; the uncertainty column in log10 units,
+ * bayes_io.py:75-76), fp64, index order, each term ((e * e) * w).  This is a multiplication by the rounded reciprocal,
+ * not the reference's division err / (2 u^2): the two differ by <= 1 ulp per term.  The host form checks the weights
+ * (finite, >= 0; TRPL_ERR_ARG naming the index); the _dev form cannot look.
  * ------------------------------------------------------------------------------------- */
 int trpl_sse_accumulate(double *P, const void *plI, int32_t elem_bytes, int64_t rows,
                         int64_t n_obs, int64_t ld, const double *values, const double *mag,
@@ -319,6 +335,12 @@ int trpl_sse_accumulate(double *P, const void *plI, int32_t elem_bytes, int64_t 
 int trpl_sse_accumulate_dev(double *P, const void *plI, int32_t elem_bytes, int64_t rows,
                             int64_t n_obs, int64_t ld, const double *values, const double *mag,
                             void *stream);
+int trpl_sse_accumulate_w(double *P, const void *plI, int32_t elem_bytes, int64_t rows,
+                          int64_t n_obs, int64_t ld, const double *values, const double *wts,
+                          const double *mag, int32_t device, double *seconds);
+int trpl_sse_accumulate_w_dev(double *P, const void *plI, int32_t elem_bytes, int64_t rows,
+                              int64_t n_obs, int64_t ld, const double *values, const double *wts,
+                              const double *mag, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * trpl_interp_rows -- the time interpolation of the UNFUSED call sequence, bayeslib.py:184-191 (a Python loop of
@@ -455,7 +477,8 @@ int trpl_loglik_obs_dev(const double *X, int64_t S, int32_t C, const double *len
  *     |P_grid - P_direct| <= k eps (A(d) + |d| sum|e_i|),   k = 6 + ceil(n / 64) + 4
  * (the depth of a batch's reduction tree, the batches added serially, the polynomial; k = n + 4 under TRPL_FLAG_STRICT).
  * The clamp at 0 only acts where cancellation has taken the sum below its own rounding error.  lnP's bval_cutoff clamp
- * depends on the offset and is not reproduced (the live reference has it commented out); no sigma weighting.
+ * depends on the offset and is not reproduced (the live reference has it commented out); no sigma weighting in
+ * these calls -- trpl_loglik_weighted, trpl_mag_grid_w and trpl_mag_profile_w below are the weighted forms.
  *   sse, esum [C][S];  n_obs [C] HOST int64;  offsets [M] HOST fp64;  P [M][S];  best [S] or [C][S];  C <= TRPL_MAG_MAX_CURVES
  * The host forms are PLAIN HOST CODE (no device, like trpl_interp_rows) in the same operation order; the _dev kernels
  * (device pointers sse / esum / P / best, nothing allocated) equal them bit for bit.
@@ -486,6 +509,67 @@ int trpl_mag_profile(const double *sse, const double *esum, const int64_t *n_obs
                      uint32_t flags, double *best, double *P);
 int trpl_mag_profile_dev(const double *sse, const double *esum, const int64_t *n_obs /*host*/, int64_t S, int32_t C,
                          uint32_t flags, double *best, double *P, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * trpl_loglik_weighted -- the UNCERTAINTY-WEIGHTED fused likelihood.  Every observation file has a third column; the
+ * reference rescales it to log10 units (bayes_io.py:75-76: sigma / PL / 2.3), ships it to the device and never reads it: the
+ * weighting line of kernel_lnP is commented out (probs.py:20-62, :40: `#err /= (2 * uncertainty[i] ** 2)`).  This call
+ * restores it on the fused path, inside the stepper's sink (PL never leaves the registers):
+ *     e_i = log10 PL_i + X[s][12] - obs_ci  (exactly trpl_loglik[_obs]'s errors),
+ *     sse[c][s]  = sum_i w_ci e_i^2,     esum[c][s] = sum_i w_ci e_i,     P[s] -= sum_c sse[c][s]   (curves in order)
+ * with each term formed as ((e * e) * w) and (e * w), summed in trpl_loglik_moments' order and association.  Hence
+ * weights of 1.0 give trpl_loglik_moments' outputs bit for bit, and a power-of-two weight scales them exactly.
+ * Arguments: those of trpl_loglik_moments[_dev] plus wts [C][obs_ld] fp64 directly after obs, indexed like obs (the first
+ * n_obs[c] entries of row c are read; off-grid: sorted together with the observation times).  w = 1 / (2 sigma^2) is the
+ * chi-square weight of the commented line (Python: likelihood.weights_from_uncertainty).
+ * status, iters_total and floor_col do NOT depend on the weights: a weight never enters the solve, and the simulated
+ * window still ends at the last observation whatever its weight.  A ZERO WEIGHT removes a finite term -- the observation
+ * counts as absent from both sums -- but it does not hide a NaN or infinite observation or error (0 * NaN = NaN).  A
+ * flagged system: sse = +inf, esum = NaN.  On- and off-grid (obs_hi / obs_dx / obs_h all NULL or all non-NULL, then
+ * plT = 1); any number of curves up to TRPL_MAX_CURVES, run as consecutive launches like the other calls.
+ * The host form checks the n_obs[c] weights of every curve BEFORE it touches a device: finite and >= 0, otherwise
+ * TRPL_ERR_ARG naming curve and index.  The _dev form cannot look (a device pointer, no synchronisation): there the
+ * caller owns that -- a negative weight gives a meaningless sum, a NaN weight a NaN likelihood.
+ * TRPL_FLAG_WEIGHTED is set by the call.  Refused: TRPL_FLAG_MOMENTS in flags (TRPL_ERR_ARG); TRPL_FLAG_FP32, _MIXED,
+ * _HIST32, TRPL_FLAG_BUNDLE(m > 1) (TRPL_ERR_UNSUPPORTED); there are no snapshot / resume forms.
+ * trpl_loglik_multi* has no weighted form (out of scope: the sharded drivers keep the unweighted one-offset likelihood).
+ *
+ * trpl_mag_grid_w / trpl_mag_profile_w -- trpl_mag_grid / trpl_mag_profile from the weighted moments, with
+ * wsum [C] HOST fp64, wsum_c = sum_i w_ci (finite, >= 0), in place of n_obs:  sum_i w (e_i + d)^2 = sse + 2 d esum + wsum d^2,
+ *     P[m][s] -= sum_c max(sse[c][s] + (2 d_m) esum[c][s] + wsum_c (d_m d_m), 0)
+ *     best[s] = -(sum_c esum[c][s]) / (sum_c wsum_c);   TRPL_MAG_PER_CURVE: best[c][s] = -esum[c][s] / wsum_c
+ * -- the SAME expression as the unweighted calls (they pass (double)n_obs[c]): with wsum = n_obs the results are equal bit
+ * for bit.  wsum_c = 0 (every weight of the curve zero): best = NaN, and the curve contributes 0 to P.
+ * ERROR BOUND (A_w(d) = sse + 2 |d esum| + wsum d^2, eps = 2^-52): against a direct evaluation of sum w_i (e_i + d)^2 on the
+ * same PL,   |P_grid - P_direct| <= k eps (A_w(d) + |d| sum w_i |e_i|),   k = 6 + ceil(n / 64) + 6
+ * (the moments bound with two more roundings, one for each multiplication by the weight; k = n + 6 for serial sums).
+ * trpl_loglik_weighted_from_pl_dev -- trpl_loglik_moments_from_pl_dev with wts [n_obs] directly after obs: the weighted
+ * sums of a resident PL block (sse [rows], esum [rows], P[j] -= sse_j).
+ * ------------------------------------------------------------------------------------- */
+int trpl_loglik_weighted(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns,
+                         int32_t L, int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
+                         const double *obs, const double *wts, const int32_t *obs_hi, const double *obs_dx,
+                         const double *obs_h, int64_t obs_ld, const int64_t *n_obs, double *P, double *sse, double *esum,
+                         int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device,
+                         double *seconds);
+int trpl_loglik_weighted_dev(const double *X, int64_t S, int32_t C, const double *lengths_nm /*host*/, double time_ns,
+                             int32_t L, int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
+                             const double *obs, const double *wts, const int32_t *obs_hi, const double *obs_dx,
+                             const double *obs_h, int64_t obs_ld, const int64_t *n_obs /*host*/, double *P, double *sse,
+                             double *esum, int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags,
+                             void *stream);
+int trpl_loglik_weighted_from_pl_dev(const void *plI, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld,
+                                     const double *obs, const double *wts, const int32_t *obs_hi, const double *obs_dx,
+                                     const double *obs_h, int64_t n_obs, const double *mag, const int32_t *status,
+                                     double *P, double *sse, double *esum, uint32_t flags, void *stream);
+int trpl_mag_grid_w(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C,
+                    const double *offsets, int64_t M, double *P);
+int trpl_mag_grid_w_dev(const double *sse, const double *esum, const double *wsum /*host*/, int64_t S, int32_t C,
+                        const double *offsets /*host*/, int64_t M, double *P, void *stream);
+int trpl_mag_profile_w(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C,
+                       uint32_t flags, double *best, double *P);
+int trpl_mag_profile_w_dev(const double *sse, const double *esum, const double *wsum /*host*/, int64_t S, int32_t C,
+                           uint32_t flags, double *best, double *P, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * trpl_loglik_multi -- trpl_loglik / trpl_loglik_obs over several devices from ONE host thread:

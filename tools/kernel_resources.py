@@ -2,7 +2,8 @@
 """Register / LDS / occupancy table of the stepper kernels from hipcc's kernel-resource-usage remarks.
     python tools/kernel_resources.py [pair fast strict mixed f32 predict_fast predict_strict predict_pair
                                        moments_fast moments_strict moments_pair moments_predict_fast
-                                       moments_predict_strict moments_predict_pair]
+                                       moments_predict_strict moments_predict_pair weighted_fast weighted_strict
+                                       weighted_pair weighted_predict_fast weighted_predict_strict weighted_predict_pair]
 (cross-compiles, no GPU needed; a name is the translation unit csrc/stepper_<name>.hip)"""
 import os
 import re
@@ -11,7 +12,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bayesian-inference-trpl_amd", "csrc")
-CONTRACT = {"strict": "off", "predict_strict": "off", "moments_strict": "off", "moments_predict_strict": "off"}      # the Makefile's -ffp-contract of each unit; default on
+CONTRACT = {"strict": "off", "predict_strict": "off", "moments_strict": "off", "moments_predict_strict": "off",
+            "weighted_strict": "off", "weighted_predict_strict": "off"}      # the Makefile's -ffp-contract of each unit; default on
 
 
 def main():
