@@ -1,0 +1,9 @@
+// TRPL_FLAG_CUT, FAST, two systems per wavefront: the likelihood-mode stepper whose sink stops a system once its running sse is above
+// StepArgs::sse_cut, trpl::cut::pair::stepper_pair_kernel<true, false, OPT>.  A translation unit of its own, compiled like
+// stepper_pair.hip (-ffp-contract=on): the existing kernels' objects do not change.
+#define TRPL_STEPPER_CUT 1
+#include "stepper_pair_impl.hpp"
+
+namespace trpl {
+hipError_t launch_stepper_cut_pair(const StepArgs &a, hipStream_t stream) { return cut::launch_stepper_pair_t<true>(a, stream); }
+}  // namespace trpl

@@ -50,7 +50,23 @@
 #undef TRPL_STEPPER_MOMENTS
 #define TRPL_STEPPER_MOMENTS 1
 #endif
-#if TRPL_STEPPER_WEIGHTED && TRPL_STEPPER_PREDICT
+// TRPL_FLAG_CUT (include/trpl.h): a unit that defines TRPL_STEPPER_CUT=1 (stepper_cut_*.hip) gets the FAST likelihood steppers whose
+// sink compares the running sse with StepArgs::sse_cut after every batch it adds and stops the system the first time it is above
+// (PlSinkT<false, PARK, false, true>), as namespace trpl::cut -- the kernels are trpl::cut::[predict::][pair::]stepper...  The cut
+// does not compose with the moments / weighted sinks.  Everywhere else CUT is false and its code is discarded at compile time.
+#ifndef TRPL_STEPPER_CUT
+#define TRPL_STEPPER_CUT 0
+#endif
+#if TRPL_STEPPER_CUT && TRPL_STEPPER_MOMENTS
+#error "TRPL_STEPPER_CUT does not combine with TRPL_STEPPER_MOMENTS / TRPL_STEPPER_WEIGHTED"
+#endif
+#if TRPL_STEPPER_CUT && TRPL_STEPPER_PREDICT
+#define TRPL_VARIANT_NS_BEGIN namespace cut { namespace predict {
+#define TRPL_VARIANT_NS_END } }
+#elif TRPL_STEPPER_CUT
+#define TRPL_VARIANT_NS_BEGIN namespace cut {
+#define TRPL_VARIANT_NS_END }
+#elif TRPL_STEPPER_WEIGHTED && TRPL_STEPPER_PREDICT
 #define TRPL_VARIANT_NS_BEGIN namespace weighted { namespace predict {
 #define TRPL_VARIANT_NS_END } }
 #elif TRPL_STEPPER_WEIGHTED
@@ -240,10 +256,16 @@ __device__ __forceinline__ bool correct_mixed(const double (&lo)[NR], const doub
 // err * w -- the square first, then the weight, so that w = 1 leaves the moments sink's bits and a power of two scales them
 // exactly.  The weight is one more coalesced load beside obs's; its row pointer is not kept (the paired kernel has no
 // register for it) but formed from obs's when a batch is flushed: wts and obs share their indexing.
-template <bool MOMENTS, bool PARK = false, bool WEIGHTED = false>
+// CUT (TRPL_FLAG_CUT): after every batch the sink adds, the running sse is compared with a.sse_cut (wave-uniform; a NaN sum never
+// compares true); the first time it is above, the number of leading observations in the sum is recorded and the sink accepts
+// nothing more: the kernel leaves its time loop (one system) or parks the system like a flagged one (paired).  sse is a sum of
+// non-negative terms and never decreases, so the system's final sse would have been above the level too.  The paired kernel's
+// cut sink parks like the moments sink -- {sse, recorded count, pl_floor} in the same three LDS words, the count as a double.
+template <bool MOMENTS, bool PARK = false, bool WEIGHTED = false, bool CUT = false>
 struct PlSinkT {
-    static_assert(MOMENTS || !PARK, "only the moments sink parks its sums in LDS");
+    static_assert(MOMENTS || CUT || !PARK, "only the moments sink and the cut sink park their sums in LDS");
     static_assert(MOMENTS || !WEIGHTED, "the weighted sink is built on the moments sink");
+    static_assert(!CUT || !MOMENTS, "the cut sink is built on the plain sink");
     // the weights of this system's curve, [obs_ld] (WEIGHTED only)
     __device__ __forceinline__ const double *wts_row() const { return a.wts + (obs - a.obs); }
     const StepArgs &a;
@@ -266,7 +288,27 @@ struct PlSinkT {
     __device__ __forceinline__ void set_park(double *three)
     {
         park = (lds_double *)three;
-        if (lane_ == 0) { park[0] = 0.0; park[1] = 0.0; }
+        if (lane_ == 0) { park[0] = 0.0; park[1] = CUT ? -1.0 : 0.0; }
+    }
+    // CUT only: the number of leading observations in the sum when it first passed a.sse_cut, or -1
+    int32_t cut_at = -1;
+    __device__ __forceinline__ int32_t cut_count() const
+    {
+        if constexpr (PARK) return __builtin_amdgcn_readfirstlane((int32_t)park[1]);
+        else return cut_at;
+    }
+    __device__ __forceinline__ bool is_cut() const { return cut_count() >= 0; }
+    // CUT only: one batch's sum of err^2 (wave-uniform) joins the running sse, which is then tested; count: the observations in
+    // the sum after it.  Returns whether the system is cut now.
+    __device__ __forceinline__ bool add_and_test(double q2, int32_t count)
+    {
+        double s2;
+        if constexpr (PARK) s2 = park[0] + q2;                       // one wavefront: its LDS accesses are in program order
+        else s2 = sse + q2;
+        const bool over = uniform_d(s2) > a.sse_cut;
+        if constexpr (PARK) { if (lane_ == 0) { park[0] = s2; if (over) park[1] = (double)count; } }
+        else { sse = s2; if (over) cut_at = count; }
+        return over;
     }
     // the sums of one batch's err^2 and err (wave-uniform) join the running sums
     __device__ __forceinline__ void add_batch(double q2, double q1)
@@ -323,6 +365,7 @@ struct PlSinkT {
     __device__ __forceinline__ void emit(int32_t col, double plv)
     {
         static_assert(!PARK, "emit() accumulates in the members: a parked sink (sums in LDS) emits through push() / flush_batch() only");
+        static_assert(!CUT, "the cut is tested once per batch: the cut sink emits through push() / flush_batch() only");
         if (a.floor_col && (interp || col < ncol_ll) && first_floor < 0 && !(plv >= floor_level())) first_floor = (int32_t)col;
         if (want_pl && lane_ == 0) {                                                   // :281,:393
             if (a.pl_bytes == 4) ((float *)a.pl)[orow * a.pl_ld + col] = (float)plv / (float)cc.plnorm;
@@ -384,6 +427,7 @@ struct PlSinkT {
 
     __device__ __forceinline__ void flush_batch(int n)      // columns base .. base+n-1, wave-uniform n in [0, 64]
     {
+        if constexpr (CUT) { if (is_cut()) return; }        // a cut system takes no further observation
         if (n > 0) {
             const int lane = lane_;
             const int32_t col = base + lane;
@@ -423,6 +467,8 @@ struct PlSinkT {
                         add_batch(wave_sum(use ? (err * err) * w : 0.0), wave_sum(use ? err * w : 0.0));
                     } else if constexpr (MOMENTS) {
                         add_batch(wave_sum(use ? err * err : 0.0), wave_sum(use ? err : 0.0));
+                    } else if constexpr (CUT) {             // on the grid the sum holds the columns up to the end of this batch
+                        add_and_test(wave_sum(use ? err * err : 0.0), base + n < ncol_ll ? base + n : ncol_ll);
                     } else {
                         sse += wave_sum(use ? err * err : 0.0);
                     }
@@ -454,6 +500,14 @@ struct PlSinkT {
                             add_batch(wave_sum(mine ? (err * err) * w : 0.0), wave_sum(mine ? err * w : 0.0));
                         } else if constexpr (MOMENTS) {
                             add_batch(wave_sum(mine ? err * err : 0.0), wave_sum(mine ? err : 0.0));
+                        } else if constexpr (CUT) {
+                            const int32_t upto = next_obs + __builtin_popcountll(m);
+                            if (add_and_test(wave_sum(mine ? err * err : 0.0), upto)) {
+                                // the floor a call truncated here reports: only columns up to this observation's upper one
+                                if (first_floor > obs_hi[upto - 1]) first_floor = -1;
+                                next_obs = upto;
+                                break;
+                            }
                         } else {
                             sse += wave_sum(mine ? err * err : 0.0);
                         }
@@ -481,7 +535,10 @@ struct PlSinkT {
                     else                 ((double *)a.pl)[orow * a.pl_ld + col] = __builtin_nan("");
                 }
         }
-        if constexpr (PARK) {
+        if constexpr (CUT) {
+            if (want_ll) a.sse[orow] = status ? __builtin_inf() : (PARK ? (double)park[0] : sse);
+            if (a.cut_col) a.cut_col[orow] = status ? -2 : cut_count();      // -1: the sum never passed the level
+        } else if constexpr (PARK) {
             if (want_ll) { a.sse[orow] = status ? __builtin_inf() : park[0]; a.esum[orow] = status ? __builtin_nan("") : park[1]; }
         } else {
             if (want_ll) a.sse[orow] = status ? __builtin_inf() : sse;
@@ -767,6 +824,8 @@ stepper_kernel(const StepArgs a)
     constexpr bool PREDICT = TRPL_STEPPER_PREDICT != 0;
     constexpr bool MOMENTS = TRPL_STEPPER_MOMENTS != 0;       // TRPL_FLAG_MOMENTS: the sink emits esum beside sse
     constexpr bool WEIGHTED = TRPL_STEPPER_WEIGHTED != 0;     // TRPL_FLAG_WEIGHTED: ... each term times its observation's weight
+    constexpr bool CUT = TRPL_STEPPER_CUT != 0;               // TRPL_FLAG_CUT: the sink stops the system once its sse is above a.sse_cut
+    static_assert(!CUT || (!STRICT && !SNAP && !MIXED && !BUNDLE && !HIST32), "the cut sink exists for the plain fp64 FAST one-system stepper, likelihood mode");
     static_assert(!MOMENTS || (!SNAP && !MIXED && !BUNDLE && !HIST32), "the moments sink exists for the plain fp64 one-system stepper, likelihood mode");
     static_assert(!PREDICT || (!MIXED && !BUNDLE && !HIST32), "the extrapolated start exists for the plain fp64 one-system stepper");
     const int wv = BUNDLE ? (int)(threadIdx.x >> 6) : 0;                 // which system of the bundle
@@ -848,7 +907,7 @@ stepper_kernel(const StepArgs a)
         }
     }
 
-    PlSinkT<MOMENTS, false, WEIGHTED> sink(a, cc, c, s, mag, lane64);
+    PlSinkT<MOMENTS, false, WEIGHTED, CUT> sink(a, cc, c, s, mag, lane64);
     sink.set_floor(rate, n0p0, L);
     if constexpr (BUNDLE) { if (!valid) sink.mute(); }
     SnapSink snap(a, cc);
@@ -1052,10 +1111,11 @@ stepper_kernel(const StepArgs a)
         if (it >= MAX) { status = 1 + (int)t; break; }                                     // :269-274
 
         if (pl_step) {
-            if (STRICT) sink.emit(pl_col, plv);
+            if constexpr (STRICT) sink.emit(pl_col, plv);
             else sink.push(pl_col, plv);
             pl_next += a.plT;
             pl_col++;
+            if constexpr (CUT) { if (sink.is_cut()) break; }      // after the step has iterated: itot is a truncated call's
         }
 
     }
@@ -1070,7 +1130,27 @@ stepper_kernel(const StepArgs a)
     if (valid) sink.finish(status, itot);
 }
 
-#if TRPL_STEPPER_MOMENTS
+#if TRPL_STEPPER_CUT
+// TRPL_FLAG_CUT: FAST, likelihood mode only -- one instantiation per L, no bundles, no snapshot / resume forms (check_launch)
+template <bool STRICT>
+hipError_t launch_stepper(const StepArgs &a, hipStream_t stream)
+{
+    static_assert(!STRICT, "the cut sink is batched: FAST only");
+    const int64_t nsys = a.S * a.C;
+    if (nsys <= 0) return hipSuccess;
+    if (a.bundle > 1 || a.n_snap > 0 || a.resN != nullptr || !a.sse || a.pl || a.esum || a.wts || !(a.sse_cut >= 0.0)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)nsys), block(64);
+    switch (a.L) {
+#define TRPL_CASE(LL) \
+    case LL: hipLaunchKernelGGL((stepper_kernel<LL, false, false>), grid, block, 0, stream, a); break;
+        TRPL_CASE(4) TRPL_CASE(8) TRPL_CASE(16) TRPL_CASE(32) TRPL_CASE(64) TRPL_CASE(128)
+        TRPL_CASE(256) TRPL_CASE(512)
+#undef TRPL_CASE
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+#elif TRPL_STEPPER_MOMENTS
 // TRPL_FLAG_MOMENTS: likelihood mode only -- one instantiation per L, no bundles, no snapshot / resume forms (check_launch)
 template <bool STRICT>
 hipError_t launch_stepper(const StepArgs &a, hipStream_t stream)

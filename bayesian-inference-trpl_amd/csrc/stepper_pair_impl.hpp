@@ -31,7 +31,7 @@
 #include "stepper_impl.hpp"
 
 namespace trpl {
-TRPL_VARIANT_NS_BEGIN                                // trpl::[moments:: | weighted::][predict::]pair by the unit's switches (stepper_impl.hpp)
+TRPL_VARIANT_NS_BEGIN                                // trpl::[moments:: | weighted:: | cut::][predict::]pair by the unit's switches (stepper_impl.hpp)
 namespace pair {
 
 constexpr int L = 128;      // nodes per system
@@ -197,7 +197,11 @@ __global__ void __launch_bounds__(64, 2) stepper_pair_kernel(const StepArgs a)
     constexpr int HSLOT = 2 * NR * 64;
     constexpr bool MOMENTS = TRPL_STEPPER_MOMENTS != 0;    // TRPL_FLAG_MOMENTS: {sse, esum, pl_floor} of both systems in six more LDS words
     constexpr bool WEIGHTED = TRPL_STEPPER_WEIGHTED != 0;  // TRPL_FLAG_WEIGHTED: the same sink, every term times its observation's weight
-    __shared__ __attribute__((aligned(16))) double lds[4 * HSLOT + (MOMENTS ? 6 : 0)];
+    // TRPL_FLAG_CUT: a system whose running sse passes a.sse_cut is parked like a flagged one; its sink parks {sse, count, pl_floor} like the moments sink
+    constexpr bool CUT = TRPL_STEPPER_CUT != 0;
+    constexpr bool PARKED = MOMENTS || CUT;                // the sinks' sums live in six LDS words behind the ring
+    static_assert(!CUT || !SNAP, "the cut sink exists in likelihood mode only");
+    __shared__ __attribute__((aligned(16))) double lds[4 * HSLOT + (PARKED ? 6 : 0)];
     double2 *hist2 = reinterpret_cast<double2 *>(lds);            // hist2[(slot * NR + row) * 64 + lane] = {N, P}
     double *xch = nullptr;                          // the solver's exchanges are DPP moves and ds_swizzle rotates: no buffer
     double Nk[NR], Pk[NR], Ek[NR], hE[4][NR];
@@ -216,10 +220,10 @@ __global__ void __launch_bounds__(64, 2) stepper_pair_kernel(const StepArgs a)
         }
     }
 
-    PlSinkT<MOMENTS, MOMENTS, WEIGHTED> sinkA(a, cc, cA, sA, lane_value(mag, 0));
-    PlSinkT<MOMENTS, MOMENTS, WEIGHTED> sinkB(a, cc, cB, sB, lane_value(mag, WS));      // same n_obs and plnorm as cA's by construction of the table
+    PlSinkT<MOMENTS, PARKED, WEIGHTED, CUT> sinkA(a, cc, cA, sA, lane_value(mag, 0));
+    PlSinkT<MOMENTS, PARKED, WEIGHTED, CUT> sinkB(a, cc, cB, sB, lane_value(mag, WS));      // same n_obs and plnorm as cA's by construction of the table
     const double rateA = lane_value(rate, 0), rateB = lane_value(rate, WS);
-    if constexpr (MOMENTS) { sinkA.set_park(lds + 4 * HSLOT); sinkB.set_park(lds + 4 * HSLOT + 3); }
+    if constexpr (PARKED) { sinkA.set_park(lds + 4 * HSLOT); sinkB.set_park(lds + 4 * HSLOT + 3); }
     sinkA.set_floor(rateA, lane_value(n0p0, 0), L);
     sinkB.set_floor(rateB, lane_value(n0p0, WS), L);
     int statusA = 0, statusB = 0;
@@ -457,6 +461,18 @@ __global__ void __launch_bounds__(64, 2) stepper_pair_kernel(const StepArgs a)
             if (!deadB) sinkB.push(pl_col, plB);
             pl_next += a.plT;
             pl_col++;
+            if constexpr (CUT) {
+                // a batch ends every 64 columns: a system whose sum has passed the level is treated like a flagged one from
+                // here on -- it pushes nothing more and is parked at equilibrium, so its live partner's bits do not change
+                if ((pl_col & 63) == 0) {
+                    const bool cutA = !deadA && sinkA.is_cut(), cutB = !deadB && sinkB.is_cut();
+                    if (cutA || cutB) {
+                        park(hi ? cutB : cutA);
+                        deadA = deadA || cutA;
+                        deadB = deadB || cutB;
+                    }
+                }
+            }
         }
 
     }
@@ -492,7 +508,11 @@ hipError_t launch_stepper_pair_t(const StepArgs &a, hipStream_t stream)
     const bool always_seam = (a.flags & kFlagPairAlwaysSeam) != 0;
     const bool snap = a.n_snap > 0 || a.resN != nullptr;
     const dim3 grid((unsigned)nblk), block(64);
-#if TRPL_STEPPER_MOMENTS                            // likelihood mode only: no snapshot forms (check_launch)
+#if TRPL_STEPPER_CUT                                // likelihood mode only: no snapshot forms (check_launch)
+    if (snap || !a.sse || a.pl || a.esum || a.wts || !(a.sse_cut >= 0.0)) return hipErrorInvalidValue;
+    if (always_seam) hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false, false>), grid, block, 0, stream, a);
+    else             hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false>), grid, block, 0, stream, a);
+#elif TRPL_STEPPER_MOMENTS                          // likelihood mode only: no snapshot forms (check_launch)
     if (snap || !a.sse || !a.esum || (TRPL_STEPPER_WEIGHTED != 0) != (a.wts != nullptr)) return hipErrorInvalidValue;
     if (always_seam) hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false, false>), grid, block, 0, stream, a);
     else             hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false>), grid, block, 0, stream, a);

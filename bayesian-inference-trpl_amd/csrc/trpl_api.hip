@@ -178,6 +178,7 @@ struct StepperChoice {
     bool predict;                                    // the instantiation in namespace trpl::predict
     bool moments;                                    // TRPL_FLAG_MOMENTS: the instantiation in namespace trpl::moments[::predict]
     bool weighted;                                   // TRPL_FLAG_WEIGHTED: the instantiation in namespace trpl::weighted[::predict]
+    bool cut;                                        // TRPL_FLAG_CUT: the instantiation in namespace trpl::cut[::predict]
     bool optimistic;                                 // paired kernel: the optimistic seam (not TRPL_FLAG_PAIR_ALWAYS_SEAM)
 };
 
@@ -193,6 +194,7 @@ StepperChoice classify_stepper(uint32_t flags, int32_t L, int64_t nsys, int64_t 
     c.predict = (flags & TRPL_FLAG_PREDICT) != 0;
     c.moments = (flags & TRPL_FLAG_MOMENTS) != 0;
     c.weighted = (flags & TRPL_FLAG_WEIGHTED) != 0;
+    c.cut = (flags & TRPL_FLAG_CUT) != 0;
     c.optimistic = TRPL_PAIR_OPTIMISTIC != 0 && !(flags & TRPL_FLAG_PAIR_ALWAYS_SEAM);
     if (flags & TRPL_FLAG_FP32) c.family = StepperChoice::F32;
     else if (flags & TRPL_FLAG_STRICT) c.strict = true;
@@ -221,6 +223,21 @@ uint32_t pin_variant(uint32_t flags, int64_t nsys, int32_t L, int64_t steps)
     return flags | (classify_stepper(flags, L, nsys, steps, false).family == StepperChoice::Pair ? TRPL_FLAG_KERNEL_PAIR : TRPL_FLAG_KERNEL_SINGLE);
 }
 
+// TRPL_FLAG_CUT: what the cut sink does not combine with.  Flags only, so that trpl_loglik_cut[_dev] can answer before they touch a device.
+int check_cut_flags(uint32_t flags)
+{
+    if (!(flags & TRPL_FLAG_CUT)) return TRPL_OK;
+    if (flags & (TRPL_FLAG_MOMENTS | TRPL_FLAG_WEIGHTED))
+        return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_CUT does not combine with %s (out of scope: the cut tests the plain sse)",
+                        (flags & TRPL_FLAG_MOMENTS) ? "TRPL_FLAG_MOMENTS" : "TRPL_FLAG_WEIGHTED");
+    if (flags & TRPL_FLAG_STRICT)
+        return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_CUT is not built for TRPL_FLAG_STRICT (its sink emits column by column: another granularity)");
+    if (flags & (TRPL_FLAG_FP32 | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
+        return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_CUT is not built for TRPL_FLAG_FP32, TRPL_FLAG_MIXED or TRPL_FLAG_HIST32");
+    if (flags_bundle(flags) > 1) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_CUT is not built for TRPL_FLAG_BUNDLE(m > 1)");
+    return TRPL_OK;
+}
+
 // Everything a stepper launch refuses because of its flags and shape: launch() and trpl_kernel_name run the same checks
 // before they classify, so a kernel name is only ever returned for an instantiation that exists and that the launch would run.
 // snap: state snapshots requested; resume: the launch continues from a checkpoint.
@@ -244,6 +261,9 @@ int check_launch(uint32_t flags, int32_t L, int64_t steps, bool snap, bool resum
         if (bundle > 1) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_WEIGHTED is not built for TRPL_FLAG_BUNDLE(m > 1)");
         if (snap || resume) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_WEIGHTED has no snapshot / resume instantiations (likelihood mode only)");
     }
+    if (int rc = check_cut_flags(flags)) return rc;
+    if ((flags & TRPL_FLAG_CUT) && (snap || resume))
+        return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_CUT has no snapshot / resume instantiations (likelihood mode only)");
     if (flags & TRPL_FLAG_PREDICT) {                                        // the extrapolated start: plain fp64 steppers only
         if (flags & (TRPL_FLAG_FP32 | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
             return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_PREDICT excludes TRPL_FLAG_FP32, TRPL_FLAG_MIXED and TRPL_FLAG_HIST32");
@@ -299,8 +319,17 @@ int pin_sharded_batch(uint32_t &flags, int64_t S, int32_t C, int32_t L, int64_t 
 
 // TRPL_FLAG_MOMENTS belongs to trpl_loglik_moments[_dev], which set it themselves: the other entry points have no esum output
 // ... and TRPL_FLAG_WEIGHTED to trpl_loglik_weighted[_dev]: the other entry points take no weights
+// ... and TRPL_FLAG_CUT to trpl_loglik_cut[_dev]: the other entry points have no sse_cut
+static int no_cut_flag(uint32_t flags)
+{
+    if (flags & TRPL_FLAG_CUT)
+        return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_CUT is set by trpl_loglik_cut[_dev] only: this entry point has no sse_cut");
+    return TRPL_OK;
+}
+
 int no_weighted_flag(uint32_t flags)
 {
+    if (int rc = no_cut_flag(flags)) return rc;      // every entry point without an sse_cut passes here
     if (flags & TRPL_FLAG_WEIGHTED)
         return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_WEIGHTED is set by trpl_loglik_weighted[_dev] only: this entry point takes no weights");
     return TRPL_OK;
@@ -356,6 +385,10 @@ int launch(const trpl::StepArgs &a_in, uint32_t flags, hipStream_t st, int64_t s
         else if (c.strict) fn = c.predict ? trpl::launch_stepper_weighted_predict_strict : trpl::launch_stepper_weighted_strict;
         else fn = c.predict ? trpl::launch_stepper_weighted_predict_fast : trpl::launch_stepper_weighted_fast;
     }
+    if (c.cut) {                                     // check_launch has left the two FAST steppers only
+        if (c.family == StepperChoice::Pair) fn = c.predict ? trpl::launch_stepper_cut_predict_pair : trpl::launch_stepper_cut_pair;
+        else fn = c.predict ? trpl::launch_stepper_cut_predict_fast : trpl::launch_stepper_cut_fast;
+    }
     const hipError_t e = fn(a, st);
     if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "%sstepper launch: %s", what, hipGetErrorString(e));
     return TRPL_OK;
@@ -394,8 +427,8 @@ int trpl_kernel_name(int64_t nsys, int32_t L, int64_t steps, uint32_t flags, int
     // (`snapshots` covers snapshots AND resume; the fp32 stepper has one instantiation and accepts a resume)
     if (int rc = check_launch(flags, L, steps, snapshots != 0 && !(flags & TRPL_FLAG_FP32), false)) return rc;
     const StepperChoice c = classify_stepper(flags, L, nsys, steps, snapshots != 0);
-    const char *tf[2] = {"false", "true"};           // stepper_predict_*.hip, stepper_moments_*.hip, stepper_weighted_*.hip
-    const char *ns = c.weighted ? (c.predict ? "trpl::weighted::predict::" : "trpl::weighted::") : c.moments ? (c.predict ? "trpl::moments::predict::" : "trpl::moments::") : (c.predict ? "trpl::predict::" : "trpl::");
+    const char *tf[2] = {"false", "true"};           // stepper_predict_*.hip, stepper_moments_*.hip, stepper_weighted_*.hip, stepper_cut_*.hip
+    const char *ns = c.cut ? (c.predict ? "trpl::cut::predict::" : "trpl::cut::") : c.weighted ? (c.predict ? "trpl::weighted::predict::" : "trpl::weighted::") : c.moments ? (c.predict ? "trpl::moments::predict::" : "trpl::moments::") : (c.predict ? "trpl::predict::" : "trpl::");
     int n;
     if (c.family == StepperChoice::F32)
         n = snprintf(buf, (size_t)buflen, "%sf32::stepper_kernel<%d>", ns, c.L);
@@ -830,9 +863,14 @@ int trpl_loglik_weighted_from_pl_dev(const void *plI, int32_t elem_bytes, int64_
 // Which of the two flags the entry points set themselves a call may carry: wts -- the weighted entry points (they set
 // TRPL_FLAG_WEIGHTED; with TRPL_FLAG_MOMENTS: refused, the weighted sink already emits both sums); esum alone -- the moments entry
 // points (they set TRPL_FLAG_MOMENTS); every other caller must carry neither.
-static int entry_flags(uint32_t &flags, bool esum, bool wts)
+static int entry_flags(uint32_t &flags, bool esum, bool wts, bool cut = false)
 {
+    if (cut) {                                       // trpl_loglik_cut[_dev]: they set TRPL_FLAG_CUT
+        flags |= TRPL_FLAG_CUT;
+        return check_cut_flags(flags);
+    }
     if (wts) {
+        if (int rc = no_cut_flag(flags)) return rc;
         if (flags & TRPL_FLAG_MOMENTS)
             return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_MOMENTS does not combine with TRPL_FLAG_WEIGHTED: the weighted sink already emits both sums");
         flags |= TRPL_FLAG_WEIGHTED;
@@ -851,9 +889,11 @@ static int loglik_dev_impl(const double *X, int64_t S, int32_t C, const double *
                            const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
                            int64_t obs_ld, const int64_t *n_obs, double *P, double *sse, int32_t *status,
                            int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream, double *esum = nullptr,
-                           const double *wts = nullptr)
+                           const double *wts = nullptr, const double *sse_cut = nullptr, int32_t *cut_col = nullptr)
 {
-    if (int rc = entry_flags(flags, esum != nullptr, wts != nullptr)) return rc;
+    // sse_cut: the cut entry points (NULL everywhere else)
+    if (int rc = entry_flags(flags, esum != nullptr, wts != nullptr, sse_cut != nullptr)) return rc;
+    if (sse_cut && !(*sse_cut >= 0.0)) return api_fail(TRPL_ERR_ARG, "sse_cut=%g must be >= 0 or +inf", *sse_cut);
     if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
     if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
     if (C < 1 || C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAX_CURVES);
@@ -887,6 +927,8 @@ static int loglik_dev_impl(const double *X, int64_t S, int32_t C, const double *
         a.obs_ld = obs_ld; a.sse = sse + (int64_t)c0 * S;
         a.esum = esum ? esum + (int64_t)c0 * S : nullptr;
         a.wts = wts ? wts + (int64_t)c0 * obs_ld : nullptr;
+        a.sse_cut = sse_cut ? *sse_cut : 0.0;
+        a.cut_col = cut_col ? cut_col + (int64_t)c0 * S : nullptr;
         a.status = status ? status + (int64_t)c0 * S : nullptr;
         a.iters_total = iters_total ? iters_total + (int64_t)c0 * S : nullptr;
         a.floor_col = floor_col ? floor_col + (int64_t)c0 * S : nullptr;
@@ -928,9 +970,11 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
                             const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
                             int64_t obs_ld, const int64_t *n_obs, double *P, double *sse, int32_t *status,
                             int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device, double *seconds,
-                            double *esum = nullptr, const double *wts = nullptr)
+                            double *esum = nullptr, const double *wts = nullptr, const double *sse_cut = nullptr,
+                            int32_t *cut_col = nullptr)
 {
-    { uint32_t f = flags; if (int rc = entry_flags(f, esum != nullptr, wts != nullptr)) return rc; }
+    { uint32_t f = flags; if (int rc = entry_flags(f, esum != nullptr, wts != nullptr, sse_cut != nullptr)) return rc; }
+    if (sse_cut && !(*sse_cut >= 0.0)) return api_fail(TRPL_ERR_ARG, "sse_cut=%g must be >= 0 or +inf", *sse_cut);
     if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
     if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
     if (C < 1 || C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAX_CURVES);
@@ -945,7 +989,7 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
     if (interp) {                                    // the brackets are host data here: validate them
         if (int rc = check_brackets(obs_hi, obs_dx, obs_h, C, obs_ld, n_obs, T)) return rc;
     }
-    DevBuf dX, ddN, dobs, dhi, ddx, dh, dP, dsse, dst, dit, dfl, des, dwt;
+    DevBuf dX, ddN, dobs, dhi, ddx, dh, dP, dsse, dst, dit, dfl, des, dwt, dcc;
     const size_t nsys = (size_t)S * C, nobs = (size_t)C * obs_ld;
     HIP_TRY(dX.alloc((size_t)S * 13 * 8, cs.st));
     HIP_TRY(ddN.alloc((size_t)C * L * 8, cs.st));
@@ -956,6 +1000,7 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
     HIP_TRY(dit.alloc(nsys * 8, cs.st));
     if (floor_col) HIP_TRY(dfl.alloc(nsys * 4, cs.st));
     if (esum) HIP_TRY(des.alloc(nsys * 8, cs.st));
+    if (cut_col) HIP_TRY(dcc.alloc(nsys * 4, cs.st));
     if (wts) { HIP_TRY(dwt.alloc(nobs * 8, cs.st)); HIP_TRY(hipMemcpyAsync(dwt.p, wts, nobs * 8, hipMemcpyHostToDevice, cs.st)); }
     HIP_TRY(hipMemcpyAsync(dX.p, X, (size_t)S * 13 * 8, hipMemcpyHostToDevice, cs.st));
     HIP_TRY(hipMemcpyAsync(ddN.p, dN, (size_t)C * L * 8, hipMemcpyHostToDevice, cs.st));
@@ -973,13 +1018,14 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
                                  interp ? ddx.as<double>() : nullptr, interp ? dh.as<double>() : nullptr, obs_ld, n_obs,
                                  dP.as<double>(), dsse.as<double>(), dst.as<int32_t>(), dit.as<int64_t>(),
                                  dfl.as<int32_t>(), flags, cs.st, esum ? des.as<double>() : nullptr,
-                                 wts ? dwt.as<double>() : nullptr))
+                                 wts ? dwt.as<double>() : nullptr, sse_cut, cut_col ? dcc.as<int32_t>() : nullptr))
         return rc;
     HIP_TRY(hipStreamSynchronize(cs.st));
     if (seconds) *seconds = now_s() - t0;
     HIP_TRY(hipMemcpyAsync(P, dP.p, (size_t)S * 8, hipMemcpyDeviceToHost, cs.st));
     if (sse) HIP_TRY(hipMemcpyAsync(sse, dsse.p, nsys * 8, hipMemcpyDeviceToHost, cs.st));
     if (esum) HIP_TRY(hipMemcpyAsync(esum, des.p, nsys * 8, hipMemcpyDeviceToHost, cs.st));
+    if (cut_col) HIP_TRY(hipMemcpyAsync(cut_col, dcc.p, nsys * 4, hipMemcpyDeviceToHost, cs.st));
     if (status) HIP_TRY(hipMemcpyAsync(status, dst.p, nsys * 4, hipMemcpyDeviceToHost, cs.st));
     if (iters_total) HIP_TRY(hipMemcpyAsync(iters_total, dit.p, nsys * 8, hipMemcpyDeviceToHost, cs.st));
     if (floor_col) HIP_TRY(hipMemcpyAsync(floor_col, dfl.p, nsys * 4, hipMemcpyDeviceToHost, cs.st));
@@ -1036,6 +1082,33 @@ int trpl_loglik_moments(const double *X, int64_t S, int32_t C, const double *len
     if (S == 0) flags &= ~(uint32_t)TRPL_FLAG_MOMENTS;
     return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
                             obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds, esum);
+}
+
+/* ------------------------------------------------------------------ fused loglik with early stop (probs.py:5-18 bval_cutoff) */
+int trpl_loglik_cut_dev(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
+                        int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN, const double *obs,
+                        const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t obs_ld,
+                        const int64_t *n_obs, double sse_cut, double *P, double *sse, int32_t *cut_col, int32_t *status,
+                        int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream)
+{
+    return loglik_dev_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
+                           obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, stream, nullptr, nullptr, &sse_cut,
+                           cut_col);
+}
+
+int trpl_loglik_cut(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
+                    int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN, const double *obs,
+                    const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t obs_ld,
+                    const int64_t *n_obs, double sse_cut, double *P, double *sse, int32_t *cut_col, int32_t *status,
+                    int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device, double *seconds)
+{
+    ProfRange range("trpl_loglik_cut (pvSim + fastlog + prob with early stop, fused)");
+    const bool interp = obs_hi || obs_dx || obs_h;
+    if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
+    if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
+    return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
+                            obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds, nullptr, nullptr,
+                            &sse_cut, cut_col);
 }
 
 /* ------------------------------------------------------------------ uncertainty-weighted fused loglik (probs.py:40) */

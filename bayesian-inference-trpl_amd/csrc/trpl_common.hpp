@@ -71,6 +71,8 @@ struct StepArgs {
     CurveConst curve[kMaxCurves];
     double *esum;           // [C][S] out: sum of the errors whose squares make sse (TRPL_FLAG_MOMENTS kernels only), or nullptr
     const double *wts;      // [C][obs_ld] observation weights, indexed like obs (TRPL_FLAG_WEIGHTED kernels only), or nullptr
+    double sse_cut;         // TRPL_FLAG_CUT kernels only: a system stops once its running sse is above this (>= 0 or +inf)
+    int32_t *cut_col;       // [C][S] out (TRPL_FLAG_CUT kernels only) or nullptr: leading observations in a cut system's sse; -1 uncut; -2 flagged
 };
 
 // BDF coefficient table of tEvol (pvSimPCR.py:241-250): time step t takes the row min(t, 4) -- order 1 (Euler) at t = 0,
@@ -118,6 +120,11 @@ hipError_t launch_stepper_weighted_pair(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_weighted_predict_fast(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_weighted_predict_strict(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_weighted_predict_pair(const StepArgs &a, hipStream_t stream);
+// TRPL_FLAG_CUT (stepper_cut_*.hip): the FAST likelihood steppers whose sink stops a system once its sse is above StepArgs::sse_cut
+hipError_t launch_stepper_cut_fast(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_cut_pair(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_cut_predict_fast(const StepArgs &a, hipStream_t stream);
+hipError_t launch_stepper_cut_predict_pair(const StepArgs &a, hipStream_t stream);
 hipError_t launch_stepper_mixed(const StepArgs &a, hipStream_t stream);           // L >= 128; `make EXPERIMENTAL=1` only: the default
 hipError_t launch_stepper_hist32(const StepArgs &a, hipStream_t stream);          // L = 256 / 512;   library must not reference them
 

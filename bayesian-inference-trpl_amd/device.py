@@ -86,6 +86,34 @@ def loglik_moments_device(X, init_params, lengths, Time, L, T, obs, n_obs, P, ss
         None if floor_col is None else _chk(floor_col, torch.int32, "floor_col"), int(flags), _stream()))
 
 
+def loglik_cut_device(X, init_params, lengths, Time, L, T, obs, n_obs, sse_cut, P, sse, cut_col=None, status=None,
+                      iters_total=None, tol=7, MAX=10000, plT=1, flags=0, floor_col=None, obs_hi=None, obs_dx=None,
+                      obs_h=None):
+    """trpl_loglik_cut_dev: loglik_device / loglik_obs_device (with the bracketing arrays obs_hi, obs_dx, obs_h) with an
+    early stop -- a system whose running sse is above sse_cut (a float >= 0 or +inf) after one of its 64-column batches
+    takes no further time step.  cut_col (C,S) int32 optional: the leading observations in a cut system's sse, -1 for an
+    uncut system (all its outputs are loglik_device's, bit for bit), -2 for a flagged one (include/trpl.h)."""
+    import torch
+    S, Cn = X.shape[0], init_params.shape[0]
+    interp = obs_hi is not None
+    if X.shape[1] != 13 or init_params.shape[1] != L or obs.shape[0] != Cn or tuple(sse.shape) != (Cn, S) \
+            or tuple(P.shape) != (S,) or (cut_col is not None and tuple(cut_col.shape) != (Cn, S)) \
+            or (interp and not (obs.shape == obs_hi.shape == obs_dx.shape == obs_h.shape)):
+        raise ValueError("shape mismatch")
+    lengths = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.float64), (Cn,)))
+    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
+    _abi.check(_abi.lib().trpl_loglik_cut_dev(
+        _chk(X, torch.float64, "X"), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol),
+        int(MAX), _chk(init_params, torch.float64, "init_params"), _chk(obs, torch.float64, "obs"),
+        _chk(obs_hi, torch.int32, "obs_hi") if interp else None, _chk(obs_dx, torch.float64, "obs_dx") if interp else None,
+        _chk(obs_h, torch.float64, "obs_h") if interp else None, obs.shape[1], _abi.ptr(n_obs), float(sse_cut),
+        _chk(P, torch.float64, "P"), _chk(sse, torch.float64, "sse"),
+        None if cut_col is None else _chk(cut_col, torch.int32, "cut_col"),
+        None if status is None else _chk(status, torch.int32, "status"),
+        None if iters_total is None else _chk(iters_total, torch.int64, "iters_total"),
+        None if floor_col is None else _chk(floor_col, torch.int32, "floor_col"), int(flags), _stream()))
+
+
 def mag_grid_device(sse, esum, n_obs, offsets, P):
     """trpl_mag_grid_dev: P (M,S) f64 -= sum_c max(sse + 2 d_m esum + n_c d_m^2, 0) for the offsets d_m (host sequence,
     added to X[:, 12]); sse, esum (C,S) f64 from loglik_moments_device, n_obs a host sequence (C,)."""

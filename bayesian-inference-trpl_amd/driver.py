@@ -138,7 +138,7 @@ def overlap_window(full, done, budget, num_curves):
 def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=None, pl_f32=False,
            normalize=False, strict=False, device=0, info=None, times=None, fp32=False, devices=None, kernel=None,
            mixed=False, bundle=1, hist32=False, bdf_order=None, extra_flags=0, predict=False, mag_grid=None,
-           mag_profile=False, weights=None):
+           mag_profile=False, weights=None, sse_cut=None):
     """Fused likelihood of one experiment (trpl_loglik / trpl_loglik_obs / trpl_loglik_multi).
 
     X (S,13) solver units; init_params (C,L) nm^-3; lengths scalar or (C,); obs = list of C
@@ -164,7 +164,20 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
     gives the chi-square weights 1 / (2 u^2) of probs.py:40).  A zero weight masks an observation.  info receives the weighted
     sse and esum and wsum (C,), the sum of each curve's weights.  Combines with mag_grid / mag_profile (trpl_mag_grid_w,
     trpl_mag_profile_w); single-device calls only.
+    sse_cut: a float >= 0 (or +inf) routes to trpl_loglik_cut -- a system whose running squared error is above it after one
+    of its 64-column batches stops there (include/trpl.h): its sse is the partial sum (> sse_cut), every other system's
+    outputs are the plain call's bit for bit.  info also receives cut_col (C, S) (leading observations in a cut system's sum,
+    -1 uncut, -2 flagged) and cut_fraction, the share of systems with cut_col >= 0.  Single-device calls on the plain FAST
+    steppers only: not with mag_grid, mag_profile, weights, devices or bundle > 1.
     """
+    if sse_cut is not None:
+        for name, on in (("mag_grid", mag_grid is not None), ("mag_profile", bool(mag_profile)), ("weights", weights is not None),
+                         ("devices", devices is not None), ("bundle", int(bundle) != 1)):
+            if on:
+                raise ValueError("sse_cut: not available with %s (trpl_loglik_cut runs the plain FAST steppers on one device)" % name)
+        sse_cut = float(sse_cut)
+        if not sse_cut >= 0.0:
+            raise ValueError("sse_cut must be >= 0 or +inf, got %r" % (sse_cut,))
     if weights is not None and devices is not None:
         raise ValueError("weights: not available with devices= (trpl_loglik_multi has no weighted form)")
     moments = mag_grid is not None or bool(mag_profile)
@@ -285,6 +298,18 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
         _abi.check(lib.trpl_mag_profile(_abi.ptr(sse), _abi.ptr(esum), _abi.ptr(n_obs), S, Cn,
                                         _abi.MAG_PER_CURVE if per_curve else 0, _abi.ptr(best), _abi.ptr(Pp)))
         return best, Pp
+    if sse_cut is not None:
+        off = times is not None
+        cut_col = np.full((Cn, S), -1, dtype=np.int32)
+        _abi.check(lib.trpl_loglik_cut(
+            _abi.ptr(X), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol), int(MAX), _abi.ptr(ini),
+            _abi.ptr(obs_mat), _abi.ptr(hi_mat) if off else None, _abi.ptr(dx_mat) if off else None,
+            _abi.ptr(h_mat) if off else None, obs_ld, _abi.ptr(n_obs), sse_cut, _abi.ptr(P), _abi.ptr(sse), _abi.ptr(cut_col),
+            _abi.ptr(status), _abi.ptr(iters), _abi.ptr(floor_col), flags, int(device), _abi.C.byref(sec)))
+        if info is not None:
+            info.update(sse=sse, status=status, iters_total=iters, floor_col=floor_col, seconds=sec.value, cut_col=cut_col,
+                        cut_fraction=float(np.mean(cut_col >= 0)) if cut_col.size else 0.0)
+        return P
     if devices is not None:
         dev = None if isinstance(devices, str) else np.ascontiguousarray(devices, dtype=np.int32)
         if isinstance(devices, str) and devices != "all":
@@ -313,6 +338,15 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
     if info is not None:
         info.update(sse=sse, status=status, iters_total=iters, floor_col=floor_col, seconds=sec.value)
     return P
+
+
+def next_cut(margin, best_total):
+    """The sse_cut of the next sample block under gpu_info["cut_margin"]: +inf while no block has finished
+    (best_total None), otherwise margin + best_total, where best_total is the smallest sum_c sse over all finished samples.
+    The running minimum only falls, so every block's level is looser than the final one needs."""
+    if best_total is None:
+        return float("inf")
+    return float(margin) + float(best_total)
 
 
 def _bundle_of(gpu_info, L):
@@ -440,6 +474,13 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
     levels: the fused single-experiment call (trpl_loglik_weighted), the resident-PL level
     (trpl_loglik_weighted_from_pl_dev) and the unfused sequence (prob(..., weighted=True); interpolated rows take the weights
     of their observation times).  Combines with 'mag_grid' and 'predict'; not with 'devices' or 'max_sims_per_block' > 1.
+    gpu_info['cut_margin'] = a float (default None: every call path as before): early stop of hopeless samples on the fused
+    single-experiment level, on one device.  The first sample block runs uncut; each later block runs trpl_loglik_cut with
+    sse_cut = next_cut(margin, smallest sum_c sse over all finished samples).  A cut sample's P is an upper bound of its
+    likelihood, at least `margin` below the best finished sample's; with margin = posterior.exact_cut_margin(tf) (and P
+    starting from equal values, as bayes() does) the posterior weights at that tf equal the uncut run's.
+    gpu_info['cut_log'], if a list, receives one dict per block (sse_cut, cut_fraction, iters_total summed).  Anything but
+    the fused one-experiment level on one device is a ValueError naming the option.
     """
     group = int(gpu_info["sims_per_gpu"])
     num_gpus = int(gpu_info["num_gpus"])
@@ -472,6 +513,20 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
             raise ValueError("gpu_info['weighted'] does not combine with gpu_info['devices']: trpl_loglik_multi has no weighted form")
         if int(gpu_info.get("max_sims_per_block", 1)) > 1:
             raise ValueError("gpu_info['weighted'] does not combine with gpu_info['max_sims_per_block'] > 1 (TRPL_FLAG_WEIGHTED has no bundles)")
+    cut_margin = gpu_info.get("cut_margin")
+    if cut_margin is not None:
+        cut_margin = float(cut_margin)
+        if not cut_margin >= 0.0:
+            raise ValueError("gpu_info['cut_margin'] must be >= 0, got %r" % (cut_margin,))
+        for name, bad in (("len(e_data) > 1", len(e_data) > 1), ("devices", gpu_info.get("devices") is not None),
+                          ("num_gpus", num_gpus != 1), ("max_sims_per_block", int(gpu_info.get("max_sims_per_block", 1)) > 1),
+                          ("mag_grid", gpu_info.get("mag_grid") is not None), ("weighted", weighted)):
+            if bad:
+                raise ValueError("gpu_info['cut_margin'] does not combine with %s: the early stop runs on the fused "
+                                 "single-experiment level, on one device (trpl_loglik_cut)" % name)
+        if not fused:
+            raise ValueError("gpu_info['cut_margin'] needs the fused level: gpu_info['fused'] = True, log_pl, PL stride 1 and "
+                             "observation times inside the simulated window")
     mag_grid = gpu_info.get("mag_grid")
     if mag_grid is not None:
         mag_grid = np.ascontiguousarray(mag_grid, dtype=np.float64).ravel()
@@ -502,11 +557,30 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
         # the production shape, likelihoods equal to 7e-15, tools/bench_prefix_vs_interp.py); gpu_info["interpolate_prefix"]
         # = True keeps the literal interpolation (both fused branches: this one and _simulate_resident).
         literal = bool(gpu_info.get("interpolate_prefix", False))
+        best_total = None                          # cut_margin: smallest sum_c sse over the finished samples
         for blk in range(gpu_id * group, len(X), num_gpus * group):
             size = min(group, len(X) - blk)
             for e, exp in enumerate(e_data):
                 on_grid = fused_entry_point(exp[0], sim_t, num_curves, literal) == "trpl_loglik"
                 info = {}
+                if cut_margin is not None:         # one experiment, one device (checked above)
+                    level = next_cut(cut_margin, best_total)
+                    loglik(X[blk:blk + size], init_params, thicknesses, Time, L, T,
+                           [exp[1][c] for c in range(num_curves)], tol=sim_params[6], MAX=sim_params[7],
+                           P=P[e, blk:blk + size], pl_f32=(pl_dtype == np.float32), normalize=NORMALIZE,
+                           device=device, info=info, times=None if on_grid else [exp[0][c] for c in range(num_curves)],
+                           predict=predict, sse_cut=level)
+                    solver_time[gpu_id] += info["seconds"]
+                    # a cut sample's reported total is above the level it was cut at, hence above the minimum so far:
+                    # it never lowers it; NaN totals are skipped
+                    total = info["sse"].sum(axis=0)
+                    if np.any(total == total):
+                        low = float(np.nanmin(total))
+                        best_total = low if best_total is None else min(best_total, low)
+                    if isinstance(gpu_info.get("cut_log"), list):
+                        gpu_info["cut_log"].append({"block": blk, "sse_cut": level, "cut_fraction": info["cut_fraction"],
+                                                    "iters_total": int(info["iters_total"].sum())})
+                    continue
                 wkw = {"weights": [weights_from_uncertainty(exp[2][c]) for c in range(num_curves)]} if weighted else {}
                 if mag_grid is not None:
                     Pe = P[e].reshape(len(mag_grid), len(X))

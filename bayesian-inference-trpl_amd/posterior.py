@@ -44,6 +44,22 @@ def weights(LL, tf=1.0, device=0, info=None):
     return W
 
 
+def exact_cut_margin(tf=1.0):
+    """The margin below the best sample's likelihood from which a sample's posterior weight at tempering factor tf is
+    EXACTLY 0.0 in fp64: tf * (1000 ln 2 + 746).  For driver.simulate's gpu_info["cut_margin"] / loglik(sse_cut=).
+
+    The weight kernel (csrc/posterior.hip, weights_partial; utils.py:164) forms, in this order,
+        q = LL / tf;   w = exp(((q - max q) + 1000 ln 2) - ln S).
+    A sample cut at sse_cut = margin + best_total has LL <= -(margin + best_total) while max LL >= -best_total' with
+    best_total' <= best_total (the running minimum only falls), so q - max q <= -margin / tf = -(1000 ln 2 + 746): the
+    argument of exp is <= -746 - ln S, and ln S >= 0 is dropped conservatively.  exp underflows to 0.0 below
+    ln(2^-1075) = -745.14 (half the smallest subnormal); the 0.86 in between covers the roundings of the division and the
+    three additions, each below 1e-10 for |LL / tf| < 1e5.  A zero weight contributes nothing to the sum the others are
+    divided by, so the weights of the uncut samples are unchanged too: the posterior equals the uncut run's."""
+    import math
+    return float(tf) * (1000.0 * math.log(2.0) + 746.0)
+
+
 def normalize(lnP, device=0):
     """utils.py:157-166."""
     return weights(lnP, 1.0, device=device)

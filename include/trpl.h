@@ -180,6 +180,15 @@ extern "C" {
                                      TRPL_FLAG_PREDICT; no snapshot / resume forms.  Refused with TRPL_ERR_UNSUPPORTED:
                                      TRPL_FLAG_FP32, _MIXED, _HIST32, TRPL_FLAG_BUNDLE(m > 1).  Python: loglik(weights=),
                                      gpu_info["weighted"] */
+#define TRPL_FLAG_CUT 0x800000      /* the FAST likelihood-mode steppers whose sink stops a system as soon as its running sse is above
+                                     the caller's sse_cut (their own instantiations, trpl::cut::[predict::][pair::]stepper...; the
+                                     existing kernels are the same machine code as without them).  SET BY trpl_loglik_cut[_dev]
+                                     THEMSELVES: every other entry point has no sse_cut and answers TRPL_ERR_ARG before it touches
+                                     a device.  trpl_kernel_name / trpl_kernel_variant accept it and name the instantiation after
+                                     the usual launch checks.  FAST only, every L, both FAST kernels, with and without
+                                     TRPL_FLAG_PREDICT; no snapshot / resume / multi forms.  With TRPL_FLAG_MOMENTS or _WEIGHTED:
+                                     TRPL_ERR_ARG.  Refused with TRPL_ERR_UNSUPPORTED: TRPL_FLAG_STRICT, _FP32, _MIXED, _HIST32,
+                                     TRPL_FLAG_BUNDLE(m > 1).  Python: loglik(sse_cut=), gpu_info["cut_margin"] */
 #define TRPL_FLAG_KERNEL_PAIR 0x10    /* run the two-systems-per-wavefront stepper whatever the launch size (L = 128,
                                         fp64, not STRICT -- anything else is TRPL_ERR_ARG) */
 #define TRPL_FLAG_KERNEL_SINGLE 0x20  /* run the one-system-per-wavefront stepper whatever the launch size */
@@ -570,6 +579,60 @@ int trpl_mag_profile_w(const double *sse, const double *esum, const double *wsum
                        uint32_t flags, double *best, double *P);
 int trpl_mag_profile_w_dev(const double *sse, const double *esum, const double *wsum /*host*/, int64_t S, int32_t C,
                            uint32_t flags, double *best, double *P, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * trpl_loglik_cut -- the fused likelihood with an EARLY STOP of hopeless systems (opt-in; the exact, work-saving form of the
+ * bval_cutoff of the reference's older likelihood, probs.py:5-18, commented out in the live kernel at probs.py:34-35).
+ * sse[c][s] is a running sum of non-negative terms e_i^2, so it never decreases: once it is above a level, the system's
+ * final likelihood is known to be below minus that level whatever the remaining time steps would add, and a caller that
+ * only needs to know THAT (a posterior weight that underflows to 0.0, see Python posterior.exact_cut_margin) need not
+ * pay for them.  On the fused path PL never leaves the registers, so the stop happens inside the stepper's sink.
+ * Arguments: those of trpl_loglik_moments[_dev] without esum, plus
+ *   sse_cut   the level, directly after n_obs: >= 0 or +inf (NaN or negative: TRPL_ERR_ARG);
+ *   cut_col   [C][S] int32 out, directly after sse, nullable.
+ * obs_hi / obs_dx / obs_h all NULL: observations on the grid (as trpl_loglik); all non-NULL: off-grid (as trpl_loglik_obs,
+ * plT must be 1).  TRPL_FLAG_CUT is set by the call.
+ * WHEN THE TEST RUNS.  The FAST sinks add the squared errors one batch of 64 PL columns at a time; each system tests
+ * `running sse > sse_cut` after every batch its sink adds, the final (partial) batch included.  The first time the test is
+ * true the system stops: no further time step, no further observation.
+ * WHAT A CUT SYSTEM REPORTS.  sse[c][s]: the running sum at that moment -- what the plain call (trpl_loglik / trpl_loglik_obs,
+ * same flags) returns for n_obs[c] = cut_col[c][s], bit for bit.  cut_col[c][s]: the number of leading observations in that
+ * sum (on-grid: a multiple of 64, or n_obs[c]).  status: 0.  floor_col: what the plain call truncated there reports.
+ * iters_total, on-grid: the truncated plain call's (both run the steps 0 .. (cut_col - 1) plT).  iters_total, off-grid: a cut
+ * system runs to the end of its 64-column batch, so only iters_total <= the plain full call's is promised.
+ * AN UNCUT SYSTEM: cut_col = -1 and every output is the plain call's, bit for bit.  A NON-CONVERGED SYSTEM: as in the plain
+ * call (sse = +inf, floor_col = -2), and cut_col = -2 -- unless its sum passed the level BEFORE the time step that fails: it
+ * stopped there and never takes that step, so it is a cut system like any other (status 0, the truncated plain call's
+ * outputs).  The plain call's sse of such a system is +inf, above every level: it is never reported uncut.
+ * A NaN running sum never compares true: such a system is never cut.
+ * EXACT EQUIVALENCE.  Adding a non-negative term in floating point never decreases a sum, so cut_col >= 0 holds exactly when
+ * the plain call's final sse > sse_cut.  Hence sse_cut = +inf gives the plain call's outputs with cut_col = -1 everywhere,
+ * and sse_cut = 0 stops every converging system with a non-zero error after its first batch.
+ * P[s] -= sum_c sse[c][s] over the REPORTED values (curves in order): for a sample with a cut curve the reported P is at or
+ * above the true P, and at or below P_in - sse_cut.
+ * The test is per system, against the system's own sum -- never the wavefront partner's or the sample's total: a system's
+ * outputs do not depend on sharding, wavefront partner, pairing rule (TRPL_FLAG_PAIR_ADJACENT) or seam form
+ * (TRPL_FLAG_PAIR_ALWAYS_SEAM).  In the paired kernel a cut system is parked like a non-converged one and its wavefront
+ * ends when both halves are done; workgroups are dispatched in order, so a wave that ends early hands its slot to the next.
+ * Combines with TRPL_FLAG_PREDICT, _PL_F32, _NORMALIZE, _BDF_ORDER, _KERNEL_PAIR / _SINGLE, _PAIR_ALWAYS_SEAM, _PAIR_ADJACENT;
+ * any number of curves up to TRPL_MAX_CURVES, run as consecutive launches like the other calls.
+ * Refused with TRPL_ERR_UNSUPPORTED, before a device is touched: TRPL_FLAG_STRICT (its sink emits column by column: another
+ * granularity), _FP32, _MIXED, _HIST32, TRPL_FLAG_BUNDLE(m > 1).  Refused with TRPL_ERR_ARG: TRPL_FLAG_MOMENTS, _WEIGHTED
+ * (the profile minimum sse - esum^2 / wsum is non-decreasing too: a later change can compose them).  There are no snapshot,
+ * resume or trpl_loglik_multi* forms.
+ * ------------------------------------------------------------------------------------- */
+int trpl_loglik_cut(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns,
+                    int32_t L, int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
+                    const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                    int64_t obs_ld, const int64_t *n_obs, double sse_cut, double *P, double *sse, int32_t *cut_col,
+                    int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device,
+                    double *seconds);
+int trpl_loglik_cut_dev(const double *X, int64_t S, int32_t C, const double *lengths_nm /*host*/, double time_ns,
+                        int32_t L, int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
+                        const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                        int64_t obs_ld, const int64_t *n_obs /*host*/, double sse_cut, double *P, double *sse,
+                        int32_t *cut_col, int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags,
+                        void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * trpl_loglik_multi -- trpl_loglik / trpl_loglik_obs over several devices from ONE host thread:

@@ -3,7 +3,8 @@
     python tools/kernel_resources.py [pair fast strict mixed f32 predict_fast predict_strict predict_pair
                                        moments_fast moments_strict moments_pair moments_predict_fast
                                        moments_predict_strict moments_predict_pair weighted_fast weighted_strict
-                                       weighted_pair weighted_predict_fast weighted_predict_strict weighted_predict_pair]
+                                       weighted_pair weighted_predict_fast weighted_predict_strict weighted_predict_pair
+                                       cut_fast cut_pair cut_predict_fast cut_predict_pair]
 (cross-compiles, no GPU needed; a name is the translation unit csrc/stepper_<name>.hip)"""
 import os
 import re
