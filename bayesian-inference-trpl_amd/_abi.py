@@ -66,6 +66,7 @@ def flag_bundle(m, L=None):
 KERNEL_FAST, KERNEL_FAST_PAIR, KERNEL_STRICT, KERNEL_FP32, KERNEL_MIXED, KERNEL_HIST32 = 0, 1, 2, 3, 4, 5
 ABI_VERSION = 5
 MAX_SNAPS = 16
+TF_SCAN_MAX = 64              # TRPL_TF_SCAN_MAX: temperatures of one trpl_posterior_tf_scan
 
 
 class TrplError(RuntimeError):
@@ -160,6 +161,9 @@ SIGNATURES = {
     "trpl_posterior_moments_dev": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "trpl_posterior_hist": [_vp, _vp, _vp, _i64, _f64, _f64, _i32, _f64, _f64, _i32, _vp, _i32, _pd],
     "trpl_posterior_hist_dev": [_vp, _vp, _vp, _i64, _f64, _f64, _i32, _f64, _f64, _i32, _vp, _vp],
+    "trpl_posterior_tf_scan_workspace": [_i64, _i32, _i32],
+    "trpl_posterior_tf_scan": [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _pd],
+    "trpl_posterior_tf_scan_dev": [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
     "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
 }
@@ -287,7 +291,7 @@ def lib():
             fn = getattr(dll, name)
             fn.argtypes = argtypes
             fn.restype = C.c_char_p if name == "trpl_last_error" else (
-                C.c_int64 if name in ("trpl_posterior_workspace_bytes", "trpl_shard_of") else C.c_int)
+                C.c_int64 if name in ("trpl_posterior_workspace_bytes", "trpl_posterior_tf_scan_workspace", "trpl_shard_of") else C.c_int)
         _lib = dll
     return _lib
 

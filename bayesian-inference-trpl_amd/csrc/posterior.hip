@@ -13,42 +13,13 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "posterior_common.hpp"
 #include "trpl_common.hpp"
 
 namespace trpl {
 namespace post {
 
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 1024;
-constexpr int kMaxDim = 16;
 constexpr int kLdsBins = 4096;
-
-__device__ __forceinline__ double wave_add(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
-// block-wide sum / max of one value per thread (kThreads = 4 waves); result valid in thread 0
-template <bool MAX>
-__device__ __forceinline__ double block_reduce(double v, double *sm)
-{
-    v = MAX ? wave_max(v) : wave_add(v);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm[w] = v;
-    __syncthreads();
-    double r = sm[0];
-#pragma unroll
-    for (int i = 1; i < kThreads / 64; i++) r = MAX ? fmax(r, sm[i]) : r + sm[i];
-    return r;
-}
 
 // ---- weights: q = LL / tf; W = exp(q - nanmax(q) + c_up - c_size); W /= nansum(W) ----
 __global__ void __launch_bounds__(kThreads) nanmax_partial(const double *LL, int64_t S, double tf, double *part)
@@ -62,8 +33,7 @@ __global__ void __launch_bounds__(kThreads) nanmax_partial(const double *LL, int
     m = block_reduce<true>(m, sm);
     if (threadIdx.x == 0) part[blockIdx.x] = m;
 }
-// part is [gridDim.y][nb][ncol]; block (c, y) reduces column c of slab y over the nb block partials:
-// thread t takes b = t, t + 256, ... in order, then the fixed block tree -- deterministic
+// declared and described in posterior_common.hpp (posterior_scan.hip launches it too)
 __global__ void __launch_bounds__(kThreads) final_reduce(const double *part, int nb, int ncol, bool is_max, double *out)
 {
     __shared__ double sm[kThreads / 64];
@@ -81,8 +51,7 @@ __global__ void __launch_bounds__(kThreads) weights_partial(const double *LL, in
     const double m = mx[0];
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < S; i += (int64_t)gridDim.x * kThreads) {
-        const double q = LL[i] / tf;
-        const double w = exp(((q - m) + c_up) - c_size);      // utils.py:164, in its order of operations
+        const double w = tempered_weight(LL[i], tf, m, c_up, c_size);
         W[i] = w;
         if (w == w) acc += w;                                 // np.nansum
     }
@@ -270,12 +239,6 @@ __global__ void __launch_bounds__(kThreads) hist_kernel(const double *x, const d
             if (t != 0.0) atomicAdd(&out[k], t);
         }
     }
-}
-
-inline int grid_for(int64_t S)
-{
-    int64_t nb = (S + kThreads - 1) / kThreads;
-    return (int)(nb < 1 ? 1 : (nb > kMaxBlocks ? kMaxBlocks : nb));
 }
 
 }  // namespace post

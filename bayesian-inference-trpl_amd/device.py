@@ -258,6 +258,35 @@ def posterior_moments_device(V, W, sums, central, workspace, mean_in=None):
         _stream()))
 
 
+def posterior_tf_scan_workspace(S, D, K):
+    """A workspace tensor for posterior_tf_scan_device with S samples, D columns and K temperatures."""
+    import torch
+    n = int(_abi.lib().trpl_posterior_tf_scan_workspace(int(S), int(D), int(K)))
+    if n <= 0:
+        raise ValueError("S, D, K = %r are outside what trpl_posterior_tf_scan accepts" % ((S, D, K),))
+    return torch.empty(n // 8, dtype=torch.float64, device="cuda")
+
+
+def posterior_tf_scan_device(LL, tfs, stats, workspace, V=None, mean=None, var=None, Q=None):
+    """The posterior at the K temperatures tfs (device tensor) in one scan: stats (K, 4); with V (D, S) also mean, var,
+    Q (K, D), row k being the bits of posterior_weights_device(LL, tfs[k]) + posterior_moments_device
+    (trpl_posterior_tf_scan_dev)."""
+    import torch
+    S, K = LL.shape[0], tfs.shape[0]
+    D = 0 if V is None else V.shape[0]
+    if LL.dim() != 1 or tfs.dim() != 1 or tuple(stats.shape) != (K, 4) or (D and tuple(V.shape) != (D, S)):
+        raise ValueError("shape mismatch")
+    outs = []
+    for t, name in ((mean, "mean"), (var, "var"), (Q, "Q")):
+        if D and (t is None or tuple(t.shape) != (K, D)):
+            raise ValueError("%s must be (K, D)" % name)
+        outs.append(_chk(t, torch.float64, name) if D else None)
+    _abi.check(_abi.lib().trpl_posterior_tf_scan_dev(
+        _chk(LL, torch.float64, "LL"), S, _chk(V, torch.float64, "V") if D else None, D, _chk(tfs, torch.float64, "tfs"), K,
+        _chk(stats, torch.float64, "stats"), outs[0], outs[1], outs[2], _chk(workspace, torch.float64, "workspace"),
+        workspace.numel() * 8, _stream()))
+
+
 def posterior_hist_device(x, W, lo, hi, out, y=None, ylo=0.0, yhi=1.0):
     """out (bins,) or (bins, ybins) += weighted counts (W None: counts); the caller zeroes out."""
     import torch

@@ -196,3 +196,135 @@ def summarize(columns, P, device=0):
     return {"names": names, "mean": mean, "variance": var, "sample_std": np.sqrt(s[1] * var),
             "skew": (c[:, D] / s[0]) / var ** 1.5, "kurtosis": (c[:, D + 1] / s[0]) / var ** 2,
             "covariance": cov, "w2": s[1]}
+
+
+# ---- choosing the temperature factor (utils.py:128-133, 168-183) on the device: trpl_posterior_tf_scan ----
+TF_SCAN_POINTS = _abi.TF_SCAN_MAX          # temperatures per scan of the bracketed search
+
+
+def tf_scan(LL, tfs, V=None, device=0):
+    """The posterior at every temperature of `tfs` (at most TF_SCAN_MAX) from one scan of the samples.
+
+    Returns dict(stats (K, 4) = [nanmax(LL / tf), raw normalising sum, sum W^2, count of non-NaN LL], mean (K, D),
+    var (K, D), Q (K, D) = sqrt(sum W^2 * var), the objective of tf_driver), row k being bit for bit what
+    weights(LL, tfs[k]) followed by moments(V, W) gives.  V is (D, S) or (S,); None: stats only (D = 0)."""
+    LL = _f64(LL)
+    tfs = np.atleast_1d(_f64(tfs))
+    if LL.ndim != 1 or tfs.ndim != 1:
+        raise ValueError("LL and tfs must be one-dimensional")
+    if V is None:
+        V = np.empty((0, LL.size))
+    V = _f64(V)
+    if V.ndim == 1:
+        V = V[None, :]
+    D, S = V.shape
+    if S != LL.size:
+        raise ValueError("V must have one column entry per sample")
+    K = tfs.size
+    out = {"stats": np.zeros((K, 4)), "mean": np.zeros((K, D)), "var": np.zeros((K, D)), "Q": np.zeros((K, D))}
+    _abi.check(_abi.lib().trpl_posterior_tf_scan(_abi.ptr(LL), S, _abi.ptr(V) if D else None, D, _abi.ptr(tfs), K,
+                                                 _abi.ptr(out["stats"]), _abi.ptr(out["mean"]), _abi.ptr(out["var"]),
+                                                 _abi.ptr(out["Q"]), int(device), None))
+    return out
+
+
+def _bracket_search(objective, lo, hi, k, rtol):
+    """Deterministic bracketed maximisation over ln tf, for C independent brackets at once.
+
+    objective(tfs) takes a (k, C) array of temperatures (column c is bracket c's grid) and returns the (k, C) values.
+    Every round lays k points, equally spaced in ln tf and including both ends, over each bracket [lo_c, hi_c], takes
+    the FIRST largest value of each column (ties resolve to the lowest index) and shrinks that bracket to the two
+    neighbours of that point (an end point keeps itself as that side).  A column is finished, and from then on frozen,
+    once hi / lo - 1 <= rtol: its result does not depend on the other columns.  k >= 4.
+
+    Rounds: a round multiplies ln(hi / lo) by 2 / (k - 1), so a column takes
+        rounds = max(1, ceil(ln(ln(hi / lo) / ln(1 + rtol)) / ln((k - 1) / 2)))
+    objective calls and rounds * k temperatures -- fewer only where a round's maximum is an end point of its grid (that
+    round shrinks the bracket by 1 / (k - 1)).
+
+    Returns (tf (C,), value (C,), info): info = dict(scans (rounds run), rounds (C,) per column, lo, hi (C,) the final
+    brackets, at_edge (C,) bool: the maximum of the FIRST round was an end point of the outer bracket, so the maximiser
+    may lie outside it)."""
+    lo = np.atleast_1d(np.asarray(lo, dtype=np.float64)).copy()
+    hi = np.atleast_1d(np.asarray(hi, dtype=np.float64)).copy()
+    if lo.shape != hi.shape or lo.ndim != 1 or not (np.all(lo > 0) and np.all(hi > lo) and np.all(np.isfinite(hi))):
+        raise ValueError("brackets need 0 < lo < hi < inf, one pair per column")
+    if k < 4 or not rtol > 0:
+        raise ValueError("k must be >= 4 and rtol > 0")
+    C = lo.size
+    frac = (np.arange(k) / (k - 1))[:, None]
+    at_edge = np.zeros(C, dtype=bool)
+    tf, val = np.full(C, np.nan), np.full(C, np.nan)
+    rounds = np.zeros(C, dtype=np.int64)
+    live = np.ones(C, dtype=bool)
+    scans = 0
+    while live.any():
+        llo, lhi = np.log(lo), np.log(hi)
+        tfs = np.exp(llo + (lhi - llo) * frac)
+        tfs[0], tfs[-1] = lo, hi                                     # the ends exactly: a grid never leaves its bracket
+        q = np.asarray(objective(tfs), dtype=np.float64).reshape(k, C)
+        scans += 1
+        best = np.argmax(np.where(np.isnan(q), -np.inf, q), axis=0)  # the first maximum of each column
+        if scans == 1:
+            at_edge = (best == 0) | (best == k - 1)
+        c = np.flatnonzero(live)
+        tf[c], val[c] = tfs[best[c], c], q[best[c], c]
+        lo[c], hi[c] = tfs[np.maximum(best[c] - 1, 0), c], tfs[np.minimum(best[c] + 1, k - 1), c]
+        rounds[c] += 1
+        live &= ~(hi / lo - 1.0 <= rtol)
+    return tf, val, {"scans": scans, "rounds": rounds, "lo": lo, "hi": hi, "at_edge": at_edge}
+
+
+def _find_best_tf_columns(V, LL, u0, device, span, rtol):
+    """find_best_tf of every row of V (D, S): (tf (D,), Q (D,), info of _bracket_search + device_scans)."""
+    V, LL = _f64(V), _f64(LL)
+    D = V.shape[0]
+    device_scans = [0]
+
+    def objective(tfs):                              # (k, D) -> Q (k, D): column d's temperatures matter for Q[:, d] only
+        uniq, inv = np.unique(tfs, return_inverse=True)
+        inv = inv.reshape(tfs.shape)
+        Q = np.empty((uniq.size, D))
+        for a in range(0, uniq.size, _abi.TF_SCAN_MAX):          # one device scan serves all D columns
+            Q[a:a + _abi.TF_SCAN_MAX] = tf_scan(LL, uniq[a:a + _abi.TF_SCAN_MAX], V, device=device)["Q"]
+            device_scans[0] += 1
+        return Q[inv, np.arange(D)[None, :]]
+
+    u0, span = float(u0), float(span)
+    if not (u0 > 0 and span > 1):
+        raise ValueError("u0 must be > 0 and span > 1")
+    tf, q, info = _bracket_search(objective, np.full(D, u0 / span), np.full(D, u0 * span), TF_SCAN_POINTS, rtol)
+    info["device_scans"] = device_scans[0]
+    return tf, q, info
+
+
+def find_best_tf(xi, P, u0, device=0, span=1e4, rtol=1e-6, info=None):
+    """utils.py:181-183, same positional arguments (xi the parameter's values, P the log-likelihoods, u0 the starting
+    temperature) and return value (tf, Q) with Q = -tf_driver(ln tf, xi, P) = sqrt(sum W^2 * weighted variance),
+    W = normalize(P / tf).  Instead of fmin from ln u0: the deterministic search of _bracket_search over
+    [u0 / span, u0 * span] with TF_SCAN_POINTS temperatures per device scan (tf_scan), until the bracket's relative width
+    is at most rtol.  info receives scans, lo, hi (the final bracket) and at_edge: True when the largest Q of the first
+    scan sat on an end of the outer bracket (the returned tf is then the best of that side, not a located maximum)."""
+    xi = _f64(xi)
+    if xi.ndim != 1:
+        raise ValueError("xi must be one-dimensional")
+    tf, q, inf = _find_best_tf_columns(xi[None, :], P, u0, device, span, rtol)
+    if info is not None:
+        info.update(scans=inf["scans"], device_scans=inf["device_scans"], lo=float(inf["lo"][0]), hi=float(inf["hi"][0]),
+                    at_edge=bool(inf["at_edge"][0]))
+    return float(tf[0]), float(q[0])
+
+
+def calc_max_uncertainty(columns, LL, num_observations, device=0, span=1e4, rtol=1e-6, info=None):
+    """LikelihoodData.calc_max_uncertainty (utils.py:128-133): dict param -> (tf, Q) = find_best_tf(columns[param], LL,
+    num_observations / 2000), bit for bit.  The columns share the rounds and the device scans: the first round is one scan
+    for all of them (the same outer bracket), a later round scans its distinct temperatures once for all D columns
+    (each column keeps its own bracket, so that is up to one scan per distinct bracket).  info receives scans (rounds: those
+    of a single find_best_tf), device_scans, and per-parameter dicts lo, hi, at_edge."""
+    names = list(columns)
+    V = np.stack([_f64(columns[k]) for k in names])
+    tf, q, inf = _find_best_tf_columns(V, LL, float(num_observations) / 2000.0, device, span, rtol)
+    if info is not None:
+        info.update(scans=inf["scans"], device_scans=inf["device_scans"], lo=dict(zip(names, inf["lo"].tolist())),
+                    hi=dict(zip(names, inf["hi"].tolist())), at_edge=dict(zip(names, inf["at_edge"].tolist())))
+    return {n: (float(tf[i]), float(q[i])) for i, n in enumerate(names)}

@@ -775,6 +775,36 @@ int trpl_posterior_hist_dev(const double *x, const double *y, const double *W, i
                             void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_posterior_tf_scan -- the posterior at K temperatures from one scan of the samples: what choosing the temperature
+ * factor needs (LikelihoodData.calc_max_uncertainty -> find_best_tf -> tf_driver, Visualization/utils.py:128-133, 168-183:
+ * the tf that maximises Q(tf) = sqrt(sum W^2 * weighted variance), W = normalize(LL / tf)).  For every k < K, with
+ * W_k = trpl_posterior_weights(LL, S, tfs[k]) and {sums, central} = trpl_posterior_moments(V, S, D, W_k):
+ *     stats[K][4] = { nanmax(LL / tfs[k]), nansum of the unnormalised weights, sum W_k^2 (= sums[1]),
+ *                     count of non-NaN entries of LL (the same for every k) }
+ *     mean[K][D]  = sums[2 + d] / sums[0]                       w_mean      :197-199
+ *     var[K][D]   = central[d][d] / sums[0]                     w_variance  :202-204
+ *     Q[K][D]     = sqrt(sums[1] * var[k][d])                   w_sample_var :168-170
+ * BIT FOR BIT what those two calls give (the same weight expression, the same per-block partials combined in the same
+ * fixed order: csrc/posterior_common.hpp), so a temperature found with the scan is the temperature of the calls that then
+ * use it.  No weight vector is written: each phase recomputes the K exponentials of LL[s] in registers.  No atomics; the
+ * result does not depend on scheduling.  NaN and -inf follow the two calls: a NaN likelihood is skipped by the maximum and
+ * the normalising sum, its weight is NaN and so are the sums over the weights; -inf has weight 0.
+ * V is [D][S] as in trpl_posterior_moments; D == 0 (V, mean, var, Q may then be NULL) returns stats alone.
+ * Refused with TRPL_ERR_ARG before a device is touched, the message naming the argument (and the index in tfs):
+ * S < 1; D outside [0, 16]; K < 1 or K > TRPL_TF_SCAN_MAX; a NULL LL, tfs, stats, or (D > 0) V, mean, var, Q; a tfs[k] that
+ * is not finite and > 0 (host form; in the _dev form tfs is device memory and cannot be looked at).
+ * The _dev form takes device pointers for everything and a workspace of trpl_posterior_tf_scan_workspace(S, D, K) bytes
+ * (0 for arguments the scan refuses); it allocates nothing, never synchronises and can be captured in a HIP graph.
+ * ------------------------------------------------------------------------------------- */
+#define TRPL_TF_SCAN_MAX 64
+int64_t trpl_posterior_tf_scan_workspace(int64_t S, int32_t D, int32_t K);
+int trpl_posterior_tf_scan(const double *LL, int64_t S, const double *V /*nullable: D == 0*/, int32_t D, const double *tfs,
+                           int32_t K, double *stats, double *mean, double *var, double *Q, int32_t device, double *seconds);
+int trpl_posterior_tf_scan_dev(const double *LL, int64_t S, const double *V, int32_t D, const double *tfs, int32_t K,
+                               double *stats, double *mean, double *var, double *Q, void *workspace,
+                               int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the
  * measurement plan): S independent systems  ld[i] x[i-1] + d[i] x[i] + ud[i] x[i+1] = b[i],
  * i < L, the problem pcreduce solves (pvSimPCR.py:42-81), operands and result in HBM, arrays

@@ -1,13 +1,18 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf]
+--find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
+(posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
+without it the output is unchanged.
 """
 import json
 import sys
 import time
 
 sys.path.insert(0, ".")
+FIND_TF = "--find-tf" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--find-tf"]
 import numpy as np
 import torch
 import trpl_amd
@@ -78,4 +83,12 @@ out = {
                    for k, (n, tr, m, sd) in enumerate(zip(names, truth, mean, std))},
     "taun_marginal_32_bins_1_to_1000": [float(v) for v in (h / h.sum()).cpu().numpy()],
 }
+if FIND_TF:
+    from trpl_amd import posterior
+    t6 = sync()
+    info = {}
+    unc = posterior.calc_max_uncertainty(dict(zip(names, V.cpu().numpy())), P.cpu().numpy(), n_obs, info=info)
+    out["seconds"]["find_tf"] = sync() - t6
+    out["max_uncertainty"] = {n: {"tf": tf, "Q": q, "at_edge": bool(info["at_edge"][n])} for n, (tf, q) in unc.items()}
+    out["find_tf_scans"] = {"rounds": info["scans"], "device_scans": info["device_scans"]}
 print(json.dumps(out))

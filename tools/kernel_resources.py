@@ -4,8 +4,8 @@
                                        moments_fast moments_strict moments_pair moments_predict_fast
                                        moments_predict_strict moments_predict_pair weighted_fast weighted_strict
                                        weighted_pair weighted_predict_fast weighted_predict_strict weighted_predict_pair
-                                       cut_fast cut_pair cut_predict_fast cut_predict_pair]
-(cross-compiles, no GPU needed; a name is the translation unit csrc/stepper_<name>.hip)"""
+                                       cut_fast cut_pair cut_predict_fast cut_predict_pair posterior posterior_scan]
+(cross-compiles, no GPU needed; a name is the translation unit csrc/stepper_<name>.hip, or csrc/<name>.hip where that exists)"""
 import os
 import re
 import subprocess
@@ -14,13 +14,17 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bayesian-inference-trpl_amd", "csrc")
 CONTRACT = {"strict": "off", "predict_strict": "off", "moments_strict": "off", "moments_predict_strict": "off",
-            "weighted_strict": "off", "weighted_predict_strict": "off"}      # the Makefile's -ffp-contract of each unit; default on
+            "weighted_strict": "off", "weighted_predict_strict": "off", "posterior": "off",
+            "posterior_scan": "off"}                                         # the Makefile's -ffp-contract of each unit; default on
 
 
 def main():
     for n in sys.argv[1:] or ["pair", "fast", "strict", "hist32"]:
+        src = os.path.join(CSRC, "%s.hip" % n)
+        if not os.path.isfile(src):
+            src = os.path.join(CSRC, "stepper_%s.hip" % n)
         r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950",
-                            "-ffp-contract=" + CONTRACT.get(n, "on"), "-c", os.path.join(CSRC, "stepper_%s.hip" % n),
+                            "-ffp-contract=" + CONTRACT.get(n, "on"), "-c", src,
                             "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
         for b in re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]:
             name = b.split("\n")[0].split(" ")[0]
