@@ -21,7 +21,7 @@ namespace post {
 
 constexpr int kLdsBins = 4096;
 
-// ---- weights: q = LL / tf; W = exp(q - nanmax(q) + c_up - c_size); W /= nansum(W) ----
+// ---- weights: q = LL / tf; W = exp(q - nanmax(q) + c_up - c_size), roundings of the exponent put back; W /= nansum(W) ----
 __global__ void __launch_bounds__(kThreads) nanmax_partial(const double *LL, int64_t S, double tf, double *part)
 {
     __shared__ double sm[kThreads / 64];
@@ -181,11 +181,13 @@ __global__ void __launch_bounds__(kThreads, 1) moments2_partial(const double *V,
 __device__ __forceinline__ double edge(double lo, double hi, int k, int bins) { return lo + ((hi - lo) * k) / bins; }
 // numpy's bin of x against edges e_0..e_bins (e_k as the reference builds them, utils.py:243-244): -1 = dropped.
 // tab (LDS, bins + 1 entries) holds those edges when the axis is small enough, `scale` = bins / (hi - lo):
-// a multiply finds the candidate bin, comparisons against the exact edges settle it.
+// a multiply finds the candidate bin, comparisons against the exact edges settle it.  The range is [e_0, e_bins]: e_0 is lo, but
+// `last` = e_bins = lo + (hi - lo) * bins / bins is not always hi (0.8999999999999999 for (0.2, 0.9), 0.30000000000000004 for
+// (0.1, 0.3) at 100 bins), and numpy keeps or drops a sample by the edge.
 constexpr int kMaxAxisTab = 1024;
-__device__ __forceinline__ int bin_of(double x, double lo, double hi, int bins, double scale, const double *tab)
+__device__ __forceinline__ int bin_of(double x, double lo, double hi, double last, int bins, double scale, const double *tab)
 {
-    if (!(x >= lo && x <= hi)) return -1;                       // also drops NaN
+    if (!(x >= lo && x <= last)) return -1;                     // also drops NaN
     int k = (int)((x - lo) * scale);
     k = k < 0 ? 0 : (k > bins - 1 ? bins - 1 : k);
     if (tab) {
@@ -207,6 +209,7 @@ __global__ void __launch_bounds__(kThreads) hist_kernel(const double *x, const d
     if (xt) for (int k = threadIdx.x; k <= xb; k += kThreads) xtab[k] = edge(xlo, xhi, k, xb);
     if (yt) for (int k = threadIdx.x; k <= yb; k += kThreads) ytab[k] = edge(ylo, yhi, k, yb);
     const double xs = xb / (xhi - xlo), ys = y ? yb / (yhi - ylo) : 0.0;
+    const double xlast = edge(xlo, xhi, xb, xb), ylast = y ? edge(ylo, yhi, yb, yb) : 0.0;
     __syncthreads();
     const int nb = y ? xb * yb : xb;
     const bool use_lds = nb <= kLdsBins;
@@ -222,9 +225,9 @@ __global__ void __launch_bounds__(kThreads) hist_kernel(const double *x, const d
         // all of a sample's loads first, unconditionally: a load behind a data-dependent branch waits for the
         // previous one (the coordinates and the weight are three independent streams)
         const double xi = x[i], yi = y ? y[i] : 0.0, w = W ? W[i] : 1.0;
-        int k = bin_of(xi, xlo, xhi, xb, xs, xt);
+        int k = bin_of(xi, xlo, xhi, xlast, xb, xs, xt);
         if (k >= 0 && y) {
-            const int ky = bin_of(yi, ylo, yhi, yb, ys, yt);
+            const int ky = bin_of(yi, ylo, yhi, ylast, yb, ys, yt);
             k = ky < 0 ? -1 : k * yb + ky;                      // [x bin][y bin], like np.histogram2d
         }
         if (k < 0) continue;

@@ -42,11 +42,26 @@ __device__ __forceinline__ double block_reduce(double v, double *sm)
 }
 
 // the unnormalised weight of a sample with log-likelihood ll at temperature tf, m = nanmax(LL / tf), c_up = 1000 ln 2,
-// c_size = ln S: utils.py:164, in its order of operations
+// c_size = ln S: utils.py:164, in its order of operations, with what that order rounds away put back.  The exponent u is the
+// reference's fp64 one; at |ll / tf| ~ 1000 the quotient and the three sums each round by up to 5.7e-14, which is the weight's
+// relative error.  The remainder of the division (one fma) and the rounding of each sum (two_sum) are exact in fp64, so
+// w (1 + corr) carries the exponent to ~1e-19 and the weight to exp's own error.  The roundings of m, c_up and c_size
+// themselves are common to all samples and leave with the division by the sum.  corr depends on the sample alone, and a
+// weight that is 0, inf or NaN stays what it is (so does the smallest subnormal: exact_cut_margin holds as derived).
+__device__ __forceinline__ double two_sum(double a, double b, double &err)
+{
+    const double s = a + b, bb = s - a;
+    err = (a - (s - bb)) + (b - bb);
+    return s;
+}
 __device__ __forceinline__ double tempered_weight(double ll, double tf, double m, double c_up, double c_size)
 {
     const double q = ll / tf;
-    return exp(((q - m) + c_up) - c_size);
+    double e0, e1, e2;
+    const double u = two_sum(two_sum(two_sum(q, -m, e0), c_up, e1), -c_size, e2);
+    const double corr = fma(-q, tf, ll) * __builtin_amdgcn_rcp(tf) + ((e0 + e1) + e2);      // ~1e-13: v_rcp_f64 is plenty
+    const double w = exp(u);
+    return fabs(corr) < 0x1p-30 ? fma(w, corr, w) : w;        // false for the NaN that an infinite q leaves in corr
 }
 
 // part is [gridDim.y][nb][ncol]; block (c, y) reduces column c of slab y over the nb block partials:

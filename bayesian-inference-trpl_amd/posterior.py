@@ -54,8 +54,10 @@ def exact_cut_margin(tf=1.0):
     best_total' <= best_total (the running minimum only falls), so q - max q <= -margin / tf = -(1000 ln 2 + 746): the
     argument of exp is <= -746 - ln S, and ln S >= 0 is dropped conservatively.  exp underflows to 0.0 below
     ln(2^-1075) = -745.14 (half the smallest subnormal); the 0.86 in between covers the roundings of the division and the
-    three additions, each below 1e-10 for |LL / tf| < 1e5.  A zero weight contributes nothing to the sum the others are
-    divided by, so the weights of the uncut samples are unchanged too: the posterior equals the uncut run's."""
+    three additions, each below 1e-10 for |LL / tf| < 1e5.  The kernel then multiplies w by 1 + corr, |corr| < 2^-30, which
+    puts those roundings back (posterior_common.hpp, tempered_weight): a w of 0.0 stays 0.0, and corr is a function of the
+    sample's own LL alone.  A zero weight contributes nothing to the sum the others are divided by, so the weights of the
+    uncut samples are unchanged too: the posterior equals the uncut run's."""
     import math
     return float(tf) * (1000.0 * math.log(2.0) + 746.0)
 

@@ -3,6 +3,7 @@ driver.loglik / driver.simulate.  No GPU needed.
 
 exact_cut_margin is checked against the expression it is derived for -- the weights of Visualization/utils.py:157-166, which
 csrc/posterior.hip restates operation by operation: w = exp(((LL / tf - max) + 1000 ln 2) - ln S), then w / nansum(w) --
+(the kernel then scales w by 1 + corr, |corr| < 2^-30, a function of the sample alone that leaves a zero a zero) --
 evaluated here in NumPy: samples `margin` below the best one have a weight of exactly 0.0, so the weights of the others do
 not depend on how far below they are.  The bound is the derivation's (exp underflows below ln 2^-1075 = -745.14), not a
 measured figure."""
