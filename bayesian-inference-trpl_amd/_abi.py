@@ -164,6 +164,13 @@ SIGNATURES = {
     "trpl_posterior_tf_scan_workspace": [_i64, _i32, _i32],
     "trpl_posterior_tf_scan": [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _pd],
     "trpl_posterior_tf_scan_dev": [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "trpl_predictive_state_bytes": [_i64],
+    "trpl_predictive_workspace_bytes": [_i64, _i64, _i32],
+    "trpl_predictive_chunks": [_i64, _i64, _i32],
+    "trpl_predictive_init_dev": [_vp, _i64, _vp],
+    "trpl_predictive_accumulate_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _u32, _vp, _vp, _i64, _vp],
+    "trpl_predictive_finish_dev": [_vp, _i64, _vp, _vp],
+    "trpl_predictive": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _u32, _vp, _i32, _pd],
     "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
     "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
 }
@@ -291,7 +298,8 @@ def lib():
             fn = getattr(dll, name)
             fn.argtypes = argtypes
             fn.restype = C.c_char_p if name == "trpl_last_error" else (
-                C.c_int64 if name in ("trpl_posterior_workspace_bytes", "trpl_posterior_tf_scan_workspace", "trpl_shard_of") else C.c_int)
+                C.c_int64 if name in ("trpl_posterior_workspace_bytes", "trpl_posterior_tf_scan_workspace", "trpl_shard_of",
+                                     "trpl_predictive_state_bytes", "trpl_predictive_workspace_bytes") else C.c_int)
         _lib = dll
     return _lib
 

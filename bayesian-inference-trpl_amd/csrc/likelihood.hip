@@ -4,6 +4,7 @@
 #include <float.h>
 #include <math.h>
 
+#include "log_pl.hpp"
 #include "trpl_common.hpp"
 
 namespace trpl {
@@ -207,22 +208,8 @@ hipError_t launch_reduce_curves(double *P, const double *sse, int64_t S, int C, 
 // otherwise leave most of the chip idle behind the fp64 log10), threads stride over the observations,
 // fixed-order block reduction at the end: the sum is associated differently from probs.prob's serial loop (~1e-16);
 // trpl_log10_clamp + trpl_sse_accumulate remain the bit-exact pair.  HBM-bound: n_obs (or 2 n_obs,
-// off-grid) PL elements per row.
+// off-grid) PL elements per row.  log_pl (log_pl.hpp) forms the model value; the predictive band shares it.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ double log_pl(T v, T v0, bool normalize, bool f32_staging)
-{
-    if (f32_staging) {                       // the reference's float32 plI buffer (bayeslib.py:137)
-        float f = (float)v;
-        if (normalize) f = f / (float)v0;
-        if ((double)f < DBL_MIN) f = (float)DBL_MIN;
-        return (double)(float)log10((double)f);
-    }
-    double d = (double)v;
-    if (normalize) d = d / (double)v0;
-    if (d < DBL_MIN) d = DBL_MIN;
-    return log10(d);
-}
 
 // MOM (trpl_loglik_moments_from_pl_dev): the sum of the errors beside the sum of their squares, in its own instantiation --
 // the MOM = false kernels are the code they were before the moments existed

@@ -287,6 +287,60 @@ def posterior_tf_scan_device(LL, tfs, stats, workspace, V=None, mean=None, var=N
         workspace.numel() * 8, _stream()))
 
 
+# ---- posterior-predictive band, device-resident (trpl_predictive_*_dev) ----
+def predictive_state(ncol):
+    """The running state (5, ncol) f64 of a predictive band over ncol time columns: sw, mean, M2, lo, hi per column.
+    Uninitialised: predictive_init_device sets it."""
+    import torch
+    if int(_abi.lib().trpl_predictive_state_bytes(int(ncol))) <= 0:
+        raise ValueError("ncol = %r is outside what trpl_predictive accepts" % (ncol,))
+    return torch.empty((5, int(ncol)), dtype=torch.float64, device="cuda")
+
+
+def predictive_workspace(rows, ncol, elem):
+    """A workspace tensor for predictive_accumulate_device over a (rows, >= ncol) block of `elem`-byte PL elements."""
+    import torch
+    n = int(_abi.lib().trpl_predictive_workspace_bytes(int(rows), int(ncol), int(elem)))
+    if n <= 0:
+        raise ValueError("rows, ncol, elem = %r are outside what trpl_predictive accepts" % ((rows, ncol, elem),))
+    return torch.empty(n // 8, dtype=torch.float64, device="cuda")
+
+
+def predictive_init_device(state):
+    """trpl_predictive_init_dev: no row seen yet (sw = 0, lo = +inf, hi = -inf)."""
+    import torch
+    if state.dim() != 2 or state.shape[0] != 5:
+        raise ValueError("state must be (5, ncol)")
+    _abi.check(_abi.lib().trpl_predictive_init_dev(_chk(state, torch.float64, "state"), state.shape[1], _stream()))
+
+
+def predictive_accumulate_device(pl, W, state, workspace, mag=None, status=None, ncol=None, flags=0):
+    """trpl_predictive_accumulate_dev: add the used rows of pl (rows, ld) f32/f64 -- W (rows,) f64 finite and > 0, status
+    (rows,) int32 zero or absent -- to state (5, ncol): y = log10 PL + mag (rows,) f64, formed as loglik_from_pl_device
+    forms it (flags: FLAG_NORMALIZE, FLAG_PL_F32).  ncol defaults to ld."""
+    import torch
+    if pl.dim() != 2 or pl.dtype not in (torch.float32, torch.float64):
+        raise ValueError("pl must be a 2-D float32/float64 tensor")
+    rows, ld = pl.shape
+    ncol = int(ld if ncol is None else ncol)
+    if tuple(W.shape) != (rows,) or tuple(state.shape) != (5, ncol) or (mag is not None and tuple(mag.shape) != (rows,)) \
+            or (status is not None and tuple(status.shape) != (rows,)):
+        raise ValueError("shape mismatch")
+    _abi.check(_abi.lib().trpl_predictive_accumulate_dev(
+        _chk(pl, pl.dtype, "pl"), pl.element_size(), rows, ncol, ld, None if mag is None else _chk(mag, torch.float64, "mag"),
+        _chk(W, torch.float64, "W"), None if status is None else _chk(status, torch.int32, "status"), int(flags),
+        _chk(state, torch.float64, "state"), _chk(workspace, torch.float64, "workspace"), workspace.numel() * 8, _stream()))
+
+
+def predictive_finish_device(state, out):
+    """trpl_predictive_finish_dev: out (5, ncol) f64 <- mean, var, lo, hi, sw of the rows accumulated so far."""
+    import torch
+    if state.dim() != 2 or state.shape[0] != 5 or out.shape != state.shape:
+        raise ValueError("state and out must be (5, ncol)")
+    _abi.check(_abi.lib().trpl_predictive_finish_dev(_chk(state, torch.float64, "state"), state.shape[1],
+                                                     _chk(out, torch.float64, "out"), _stream()))
+
+
 def posterior_hist_device(x, W, lo, hi, out, y=None, ylo=0.0, yhi=1.0):
     """out (bins,) or (bins, ybins) += weighted counts (W None: counts); the caller zeroes out."""
     import torch

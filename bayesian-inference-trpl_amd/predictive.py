@@ -1,0 +1,132 @@
+"""Posterior-predictive PL band: the posterior taken back to the data.
+
+Per time column, the weighted mean, the weighted variance and the envelope of the model values
+y = log10 PL + mag -- the values the likelihood compared with the observations -- over the samples whose posterior weight
+is finite and > 0 and whose solve converged (trpl_predictive*, include/trpl.h; csrc/predictive.hip).  Every reduction over
+the samples runs on the GPU; there is no CPU fallback.
+
+    band(pl, W, ...)                        one PL matrix on the host -> dict(mean, var, lo, hi, sw)
+    merge(a, b)                             two finished bands (shards of a multi-GPU run, separate runs) -> one; NumPy
+    posterior_predictive(X, W, ...)         re-solve the weighted samples per curve and accumulate on the device
+"""
+import numpy as np
+
+from . import _abi
+
+FIELDS = ("mean", "var", "lo", "hi", "sw")       # the rows of trpl_predictive_finish_dev's out[5][ncol]
+
+
+def _result(out):
+    return {k: out[i].copy() for i, k in enumerate(FIELDS)}
+
+
+def band(pl, W, mag=None, status=None, normalize=False, device=0, ncol=None, info=None):
+    """trpl_predictive on host arrays: pl (rows, ld) float32 / float64 PL as solve_pl returns it, W (rows,) posterior
+    weights (a row counts iff its weight is finite and > 0), mag (rows,) log offsets (X[:, 12]; None: 0), status (rows,)
+    int32 of the solve (a nonzero entry drops the row; None: all converged).  ncol (default ld): the valid columns.
+    Returns dict(mean, var, lo, hi, sw), each (ncol,); a column no used row reached has sw = 0, NaN mean / var, lo = +inf,
+    hi = -inf."""
+    pl = np.asarray(pl)
+    if pl.ndim != 2 or pl.dtype not in (np.float32, np.float64):
+        raise ValueError("pl must be a 2-D float32/float64 array")
+    pl = np.ascontiguousarray(pl)
+    rows, ld = pl.shape
+    ncol = int(ld if ncol is None else ncol)
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    mag = None if mag is None else np.ascontiguousarray(mag, dtype=np.float64)
+    status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+    if W.shape != (rows,) or (mag is not None and mag.shape != (rows,)) or (status is not None and status.shape != (rows,)):
+        raise ValueError("W, mag and status must have one entry per row of pl")
+    out = np.empty((5, max(ncol, 1)))
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_predictive(_abi.ptr(pl), pl.itemsize, rows, ncol, ld, _abi.ptr(mag), _abi.ptr(W), _abi.ptr(status),
+                                          _abi.FLAG_NORMALIZE if normalize else 0, _abi.ptr(out), int(device), _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value, chunks=int(_abi.lib().trpl_predictive_chunks(rows, ncol, pl.itemsize)))
+    return _result(out)
+
+
+def merge(a, b):
+    """Two FINISHED bands over the same columns -> the band of their union (Chan's pairwise formula on sw, mean,
+    M2 = var * sw; lo / hi by min / max).  A side whose sw is 0 passes the other through bit for bit.  Plain NumPy."""
+    a = {k: np.asarray(a[k], dtype=np.float64) for k in FIELDS}
+    b = {k: np.asarray(b[k], dtype=np.float64) for k in FIELDS}
+    if any(a[k].shape != a["sw"].shape or b[k].shape != a["sw"].shape for k in FIELDS):
+        raise ValueError("both bands must cover the same columns")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s = a["sw"] + b["sw"]
+        d = b["mean"] - a["mean"]
+        mean = a["mean"] + d * (b["sw"] / s)
+        var = ((a["var"] * a["sw"] + b["var"] * b["sw"]) + (d * d) * ((a["sw"] * b["sw"]) / s)) / s
+    ea, eb = a["sw"] == 0, b["sw"] == 0
+    out = {"mean": np.where(eb, a["mean"], np.where(ea, b["mean"], mean)),
+           "var": np.where(eb, a["var"], np.where(ea, b["var"], var)),
+           "lo": np.fmin(a["lo"], b["lo"]), "hi": np.fmax(a["hi"], b["hi"]),
+           "sw": np.where(eb, a["sw"], np.where(ea, b["sw"], s))}
+    return out
+
+
+def posterior_predictive(X, W, init_params, sim_params, lengths=None, block=4096, predict=False, normalize=False, tol=7,
+                         MAX=10000, device=0):
+    """The posterior-predictive band of every curve.
+
+    X (S, 13) samples in the solver's units (columns 0..11 matPar, 12 the magnitude offset), W (S,) their posterior weights
+    (posterior.weights), init_params (C, L) the curves' excitations, sim_params = [Length or per-curve lengths, Time, L, T,
+    plT, ...] as driver.simulate takes them (lengths overrides its first entry).  The samples with a finite weight > 0 are
+    selected on the host -- most weights are exactly 0.0 (posterior.exact_cut_margin) and those samples are never solved;
+    per curve they are solved in blocks of `block` (solve_pl_device, fp64 PL) and every block is accumulated on the device
+    (predictive_accumulate_device, mag = X[:, 12]).  Flagged systems are left out and counted.
+    Returns one dict per curve: times (ncol,), mean, var, lo, hi, sw (ncol,), n_used (samples with weight), n_solved
+    (systems solved for this curve, = n_used), n_flagged (of those, the non-converged ones)."""
+    import torch
+
+    from . import device as tdev
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    init_params = np.atleast_2d(np.ascontiguousarray(init_params, dtype=np.float64))
+    if X.ndim != 2 or X.shape[1] != 13 or W.shape != (X.shape[0],):
+        raise ValueError("X must be (S, 13) and W (S,)")
+    Cn = init_params.shape[0]
+    Time, L, T, plT = float(sim_params[1]), int(sim_params[2]), int(sim_params[3]), int(sim_params[4])
+    lens = sim_params[0] if lengths is None else lengths
+    lens = np.broadcast_to(np.asarray(lens, dtype=np.float64), (Cn,))
+    if init_params.shape[1] != L or int(block) < 1:
+        raise ValueError("init_params must be (C, L) and block >= 1")
+    with np.errstate(invalid="ignore"):
+        sel = np.flatnonzero(np.isfinite(W) & (W > 0))
+    ncol = T // plT + 1
+    times = np.linspace(0, Time, T + 1)[::plT]
+    empty = {"mean": np.full(ncol, np.nan), "var": np.full(ncol, np.nan), "lo": np.full(ncol, np.inf),
+             "hi": np.full(ncol, -np.inf), "sw": np.zeros(ncol)}
+    if sel.size == 0:
+        return [dict(times=times, n_used=0, n_solved=0, n_flagged=0, **{k: v.copy() for k, v in empty.items()}) for _ in range(Cn)]
+    block = min(int(block), sel.size)
+    dev = torch.device("cuda", device)
+    flags = _abi.FLAG_PREDICT if predict else 0
+    result = []
+    with torch.cuda.device(dev):
+        ini_d = torch.from_numpy(init_params).to(dev)
+        Xs = torch.from_numpy(np.ascontiguousarray(X[sel])).to(dev)
+        Ws = torch.from_numpy(np.ascontiguousarray(W[sel])).to(dev)
+        pl_d = torch.empty((block, ncol), dtype=torch.float64, device=dev)
+        st_d = torch.empty(block, dtype=torch.int32, device=dev)
+        state, out = tdev.predictive_state(ncol), torch.empty((5, ncol), dtype=torch.float64, device=dev)
+        sizes = {block, sel.size % block or block}               # the row counts that occur: full blocks and the last one
+        ws = max((tdev.predictive_workspace(n, ncol, 8) for n in sizes), key=lambda t: t.numel())
+        for c in range(Cn):
+            tdev.predictive_init_device(state)
+            n_flagged = n_solved = 0
+            for a in range(0, sel.size, block):
+                n = min(block, sel.size - a)
+                mat_d, mag_d = Xs[a:a + n, :12].contiguous(), Xs[a:a + n, 12].contiguous()
+                tdev.solve_pl_device(mat_d, lens[c], Time, L, T, ini_d[c].contiguous(), pl_d[:n], status=st_d[:n], tol=tol,
+                                     MAX=MAX, plT=plT, flags=flags)
+                tdev.predictive_accumulate_device(pl_d[:n], Ws[a:a + n], state, ws, mag=mag_d, status=st_d[:n],
+                                                  flags=_abi.FLAG_NORMALIZE if normalize else 0)
+                n_flagged += int((st_d[:n] != 0).sum().item())
+                n_solved += n
+            tdev.predictive_finish_device(state, out)
+            r = _result(out.cpu().numpy())
+            r.update(times=times, n_used=int(sel.size), n_solved=n_solved, n_flagged=n_flagged)
+            result.append(r)
+    return result

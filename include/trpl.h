@@ -805,6 +805,58 @@ int trpl_posterior_tf_scan_dev(const double *LL, int64_t S, const double *V, int
                                int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_predictive* -- the posterior-predictive PL band: the posterior taken back to the DATA.  Which PL(t) does the posterior
+ * predict, and how wide is that prediction next to the measured curve (the check a user of the reference does by hand in NumPy
+ * on a PL matrix copied to the host).  A streaming reduction over the samples, per time column, of a PL block resident in HBM
+ * (the output of trpl_solve_pl_dev) under the weights of trpl_posterior_weights_dev.
+ *
+ * Definition.  For row j (one sample of one curve) and column i < ncol the model value is
+ *     y[j][i] = log10 PL[j][i] + mag[j]                                     (mag == NULL: 0)
+ * formed EXACTLY as the on-grid path of trpl_loglik_from_pl_dev forms the value it subtracts the observation from: the same
+ * optional fp32 rounding (TRPL_FLAG_PL_F32, implied by a 4-byte buffer), the same optional self-normalisation to column 0
+ * (TRPL_FLAG_NORMALIZE), the same clamp at DBL_MIN, the same device function (csrc/log_pl.hpp).
+ * A row is USED iff W[j] is finite and > 0 and (status == NULL or status[j] == 0).  Over the used rows, per column,
+ *     sw = sum W_j,   mean = sum W_j y_ji / sw,   var = sum W_j (y_ji - mean)^2 / sw,   lo = min y_ji,   hi = max y_ji.
+ * An unused row's PL is never read.  A column no used row reached finishes as sw = 0, mean = var = NaN, lo = +inf, hi = -inf.
+ * NaN rule: a NaN PL element in a used row makes that column's mean and var NaN; lo and hi ignore it (fmin / fmax).  The same
+ * holds for a y that is infinite -- PL <= 0 in a 4-byte buffer, whose clamp (float)DBL_MIN is 0 exactly as in
+ * trpl_log10_clamp, gives y = -inf: mean and var of that column are NaN, and lo is -inf.
+ *
+ * State and passes.  state [5][ncol] fp64 = running (sw, mean, M2 = sum W (y - mean)^2, lo, hi) per column
+ * (trpl_predictive_state_bytes = 40 ncol).  trpl_predictive_init_dev sets sw = 0, lo = +inf, hi = -inf;
+ * trpl_predictive_accumulate_dev adds the used rows of one block -- any number of calls, e.g. one per solved block;
+ * trpl_predictive_finish_dev writes out [5][ncol] = mean, var, lo, hi, sw and leaves the state as it is.  One accumulation:
+ * the rows are cut into trpl_predictive_chunks(rows, ncol, elem_bytes) chunks of ceil(rows / chunks) consecutive rows; every
+ * chunk accumulates its columns in row order with the weighted one-pass update (West 1979) and writes its partials to the
+ * workspace (chunks * ncol * 40 B = trpl_predictive_workspace_bytes; 0 for refused arguments); a second kernel merges the
+ * chunks IN CHUNK ORDER with the pairwise formula of Chan, Golub and LeVeque, then the call's result into the state.
+ * Determinism: no atomics; the chunking is a pure function of (rows, ncol, elem_bytes) and never of the device, so the same
+ * sequence of calls gives the same bits on any device, and the host form equals init + one accumulate + finish bit for bit.
+ * A different cut of the rows into calls is a different (equally accurate) summation order.  Against a two-pass
+ * extended-precision evaluation on the same y: mean within 1e-12 sum W |y| / sw, var within 1e-10 var; one used row, or a
+ * constant column, gives mean = y and var = 0 exactly; lo and hi are the exact minimum and maximum.
+ * Any ld >= ncol: rows need only element alignment (trpl_solve_pl_dev's ld = T/plT + 1 is usually odd).
+ *
+ * Refused with TRPL_ERR_ARG before a device is touched, the message naming the argument: rows < 1; ncol < 1 (or > 2^36);
+ * ld < ncol; elem_bytes other than 4 or 8; a NULL plI, W, state, workspace or out; a workspace smaller than
+ * trpl_predictive_workspace_bytes returns; flags other than TRPL_FLAG_PL_F32 / TRPL_FLAG_NORMALIZE.
+ * The _dev calls take device pointers only (mag and status nullable), allocate nothing and never synchronise.
+ * trpl_predictive is the host-buffer form: init, one accumulate, finish; seconds (nullable) the time of the three on the device.
+ * Python: trpl_amd.predictive.band / merge / posterior_predictive, trpl_amd.device.predictive_*.
+ * ------------------------------------------------------------------------------------- */
+int64_t trpl_predictive_state_bytes(int64_t ncol);
+int64_t trpl_predictive_workspace_bytes(int64_t rows, int64_t ncol, int32_t elem_bytes);
+int32_t trpl_predictive_chunks(int64_t rows, int64_t ncol, int32_t elem_bytes);
+int trpl_predictive_init_dev(void *state, int64_t ncol, void *stream);
+int trpl_predictive_accumulate_dev(const void *plI, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld,
+                                   const double *mag, const double *W, const int32_t *status, uint32_t flags,
+                                   void *state, void *workspace, int64_t workspace_bytes, void *stream);
+int trpl_predictive_finish_dev(const void *state, int64_t ncol, double *out /* [5][ncol]: mean, var, lo, hi, sw */,
+                               void *stream);
+int trpl_predictive(const void *plI, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld, const double *mag,
+                    const double *W, const int32_t *status, uint32_t flags, double *out, int32_t device, double *seconds);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the
  * measurement plan): S independent systems  ld[i] x[i-1] + d[i] x[i] + ud[i] x[i+1] = b[i],
  * i < L, the problem pcreduce solves (pvSimPCR.py:42-81), operands and result in HBM, arrays

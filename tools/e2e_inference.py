@@ -1,10 +1,14 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
+--predictive adds, after the posterior, the posterior-predictive PL band of every curve (predictive.posterior_predictive: the
+samples with a weight > 0 are re-solved and reduced on the device) as "predictive" -- mean, sqrt(var), lo, hi of log10 PL per
+time column, the number of samples used, and the rms distance of the mean to the synthetic observations in units of
+sqrt(var) -- and seconds["predictive"]; without it the output is unchanged.
 """
 import json
 import sys
@@ -12,7 +16,8 @@ import time
 
 sys.path.insert(0, ".")
 FIND_TF = "--find-tf" in sys.argv
-sys.argv = [a for a in sys.argv if a != "--find-tf"]
+PREDICTIVE = "--predictive" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive")]
 import numpy as np
 import torch
 import trpl_amd
@@ -91,4 +96,20 @@ if FIND_TF:
     out["seconds"]["find_tf"] = sync() - t6
     out["max_uncertainty"] = {n: {"tf": tf, "Q": q, "at_edge": bool(info["at_edge"][n])} for n, (tf, q) in unc.items()}
     out["find_tf_scans"] = {"rounds": info["scans"], "device_scans": info["device_scans"]}
+if PREDICTIVE:
+    from trpl_amd import predictive
+    t7 = sync()
+    bands = predictive.posterior_predictive(X.cpu().numpy(), W.cpu().numpy(), ini, [list(lens), T * dt, L, T, 1])
+    out["seconds"]["predictive"] = sync() - t7
+    obs_h = obs.cpu().numpy()
+    out["predictive"] = []
+    for c, b in enumerate(bands):
+        sd = np.sqrt(b["var"])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            z = (b["mean"] - obs_h[c]) / sd
+        z = z[np.isfinite(z)]                    # (a column on which every used sample agrees has no width)
+        out["predictive"].append({"n_used": b["n_used"], "n_flagged": b["n_flagged"],
+                                  "rms_distance_in_sigma": float(np.sqrt(np.mean(z * z))) if z.size else None,
+                                  "times": b["times"].tolist(), "mean": b["mean"].tolist(), "std": sd.tolist(),
+                                  "lo": b["lo"].tolist(), "hi": b["hi"].tolist()})
 print(json.dumps(out))

@@ -4,7 +4,7 @@
                                        moments_fast moments_strict moments_pair moments_predict_fast
                                        moments_predict_strict moments_predict_pair weighted_fast weighted_strict
                                        weighted_pair weighted_predict_fast weighted_predict_strict weighted_predict_pair
-                                       cut_fast cut_pair cut_predict_fast cut_predict_pair posterior posterior_scan]
+                                       cut_fast cut_pair cut_predict_fast cut_predict_pair posterior posterior_scan predictive]
 (cross-compiles, no GPU needed; a name is the translation unit csrc/stepper_<name>.hip, or csrc/<name>.hip where that exists)"""
 import os
 import re
