@@ -2,5 +2,5 @@
 #include "stepper_f32_impl.hpp"
 
 namespace trpl {
-hipError_t launch_stepper_f32(const StepArgs &a, hipStream_t stream) { return launch_stepper_f32_impl(a, stream); }
+template <> hipError_t launch_variant<Variant::plain, 0, Variant::f32>(const StepArgs &a, hipStream_t stream) { return launch_stepper_f32_impl(a, stream); }
 }  // namespace trpl

@@ -5,7 +5,8 @@
 
 namespace trpl {
 
-hipError_t launch_stepper_hist32(const StepArgs &a, hipStream_t stream)
+template <>
+hipError_t launch_variant<Variant::plain, 0, Variant::hist32>(const StepArgs &a, hipStream_t stream)
 {
     const int64_t nsys = a.S * a.C;
     if (nsys <= 0) return hipSuccess;

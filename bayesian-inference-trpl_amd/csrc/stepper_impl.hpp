@@ -23,22 +23,23 @@
 #pragma once
 #include "pcr.hpp"
 
-// TRPL_FLAG_PREDICT (include/trpl.h): a translation unit that defines TRPL_STEPPER_PREDICT=1 before including this header
-// (stepper_predict_*.hip) gets the steppers with the extrapolated start of every time step, as namespace trpl::predict
+// The variants of stepper_variants.hpp are this source compiled with switches (Makefile: -DTRPL_STEPPER_<WORD>=1 per object).
+// TRPL_FLAG_PREDICT (include/trpl.h): a translation unit compiled with TRPL_STEPPER_PREDICT=1
+// (the stepper_*predict_*.o objects) gets the steppers with the extrapolated start of every time step, as namespace trpl::predict
 // (its kernels are trpl::predict::stepper_kernel<...> and trpl::predict::pair::stepper_pair_kernel<...>); the helpers
 // stay in trpl.  Everywhere else the mode does not exist: PREDICT is false and its code is discarded at compile time,
 // so the default kernels are the same machine code as without it.
 #ifndef TRPL_STEPPER_PREDICT
 #define TRPL_STEPPER_PREDICT 0
 #endif
-// TRPL_FLAG_MOMENTS (include/trpl.h) is built the same way: a unit that defines TRPL_STEPPER_MOMENTS=1 (stepper_moments_*.hip)
+// TRPL_FLAG_MOMENTS (include/trpl.h) is built the same way: a unit with TRPL_STEPPER_MOMENTS=1 (stepper_moments_*.o)
 // gets the steppers whose likelihood sink also emits esum = sum e_i beside sse = sum e_i^2 (PlSinkT<true>), as namespace
 // trpl::moments -- outside predict, so the kernels are trpl::moments::[predict::][pair::]stepper...  Everywhere else the sink is
 // PlSinkT<false>, whose moments code is discarded at compile time.
 #ifndef TRPL_STEPPER_MOMENTS
 #define TRPL_STEPPER_MOMENTS 0
 #endif
-// TRPL_FLAG_WEIGHTED (include/trpl.h): a unit that defines TRPL_STEPPER_WEIGHTED=1 (stepper_weighted_*.hip) gets the moments
+// TRPL_FLAG_WEIGHTED (include/trpl.h): a unit with TRPL_STEPPER_WEIGHTED=1 (stepper_weighted_*.o) gets the moments
 // steppers whose sink multiplies every squared error and every error by the observation's weight (PlSinkT<true, PARK, true>:
 // sse = sum w e^2, esum = sum w e), as namespace trpl::weighted -- beside moments, not inside it: the kernels are
 // trpl::weighted::[predict::][pair::]stepper...  The weighted sink IS the moments sink plus one load and two multiplies per
@@ -50,7 +51,7 @@
 #undef TRPL_STEPPER_MOMENTS
 #define TRPL_STEPPER_MOMENTS 1
 #endif
-// TRPL_FLAG_CUT (include/trpl.h): a unit that defines TRPL_STEPPER_CUT=1 (stepper_cut_*.hip) gets the FAST likelihood steppers whose
+// TRPL_FLAG_CUT (include/trpl.h): a unit with TRPL_STEPPER_CUT=1 (stepper_cut_*.o) gets the FAST likelihood steppers whose
 // sink compares the running sse with StepArgs::sse_cut after every batch it adds and stops the system the first time it is above
 // (PlSinkT<false, PARK, false, true>), as namespace trpl::cut -- the kernels are trpl::cut::[predict::][pair::]stepper...  The cut
 // does not compose with the moments / weighted sinks.  Everywhere else CUT is false and its code is discarded at compile time.
@@ -60,31 +61,38 @@
 #if TRPL_STEPPER_CUT && TRPL_STEPPER_MOMENTS
 #error "TRPL_STEPPER_CUT does not combine with TRPL_STEPPER_MOMENTS / TRPL_STEPPER_WEIGHTED"
 #endif
-#if TRPL_STEPPER_CUT && TRPL_STEPPER_PREDICT
-#define TRPL_VARIANT_NS_BEGIN namespace cut { namespace predict {
-#define TRPL_VARIANT_NS_END } }
-#elif TRPL_STEPPER_CUT
-#define TRPL_VARIANT_NS_BEGIN namespace cut {
-#define TRPL_VARIANT_NS_END }
-#elif TRPL_STEPPER_WEIGHTED && TRPL_STEPPER_PREDICT
-#define TRPL_VARIANT_NS_BEGIN namespace weighted { namespace predict {
-#define TRPL_VARIANT_NS_END } }
+// The variant's namespace is composed from its sink and from PREDICT, each of which contributes a level or nothing:
+// TRPL_VARIANT_NS_BEGIN / _END open and close trpl::[<sink>::][predict::], TRPL_VARIANT_NS names it from trpl, and
+// TRPL_VARIANT_SINK is the sink's word in Variant::Sink (trpl_common.hpp).  WEIGHTED before MOMENTS: it sets both.
+#if TRPL_STEPPER_CUT
+#define TRPL_VARIANT_SINK cut
 #elif TRPL_STEPPER_WEIGHTED
-#define TRPL_VARIANT_NS_BEGIN namespace weighted {
-#define TRPL_VARIANT_NS_END }
-#elif TRPL_STEPPER_MOMENTS && TRPL_STEPPER_PREDICT
-#define TRPL_VARIANT_NS_BEGIN namespace moments { namespace predict {
-#define TRPL_VARIANT_NS_END } }
+#define TRPL_VARIANT_SINK weighted
 #elif TRPL_STEPPER_MOMENTS
-#define TRPL_VARIANT_NS_BEGIN namespace moments {
-#define TRPL_VARIANT_NS_END }
-#elif TRPL_STEPPER_PREDICT
-#define TRPL_VARIANT_NS_BEGIN namespace predict {
-#define TRPL_VARIANT_NS_END }
-#else
-#define TRPL_VARIANT_NS_BEGIN
-#define TRPL_VARIANT_NS_END
+#define TRPL_VARIANT_SINK moments
 #endif
+#ifdef TRPL_VARIANT_SINK
+#define TRPL_SINK_NS_BEGIN namespace TRPL_VARIANT_SINK {
+#define TRPL_SINK_NS_END }
+#define TRPL_SINK_NS TRPL_VARIANT_SINK::
+#else
+#define TRPL_VARIANT_SINK plain
+#define TRPL_SINK_NS_BEGIN
+#define TRPL_SINK_NS_END
+#define TRPL_SINK_NS
+#endif
+#if TRPL_STEPPER_PREDICT
+#define TRPL_PREDICT_NS_BEGIN namespace predict {
+#define TRPL_PREDICT_NS_END }
+#define TRPL_PREDICT_NS predict::
+#else
+#define TRPL_PREDICT_NS_BEGIN
+#define TRPL_PREDICT_NS_END
+#define TRPL_PREDICT_NS
+#endif
+#define TRPL_VARIANT_NS_BEGIN TRPL_SINK_NS_BEGIN TRPL_PREDICT_NS_BEGIN
+#define TRPL_VARIANT_NS_END TRPL_PREDICT_NS_END TRPL_SINK_NS_END
+#define TRPL_VARIANT_NS TRPL_SINK_NS TRPL_PREDICT_NS
 
 namespace trpl {
 
@@ -1130,35 +1138,22 @@ stepper_kernel(const StepArgs a)
     if (valid) sink.finish(status, itot);
 }
 
-#if TRPL_STEPPER_CUT
-// TRPL_FLAG_CUT: FAST, likelihood mode only -- one instantiation per L, no bundles, no snapshot / resume forms (check_launch)
-template <bool STRICT>
-hipError_t launch_stepper(const StepArgs &a, hipStream_t stream)
+#if TRPL_STEPPER_MOMENTS || TRPL_STEPPER_CUT
+// The argument guard of the likelihood-only sinks (TRPL_FLAG_MOMENTS, _WEIGHTED, _CUT), shared with the paired launcher
+static inline bool sink_args_ok(const StepArgs &a)
 {
-    static_assert(!STRICT, "the cut sink is batched: FAST only");
-    const int64_t nsys = a.S * a.C;
-    if (nsys <= 0) return hipSuccess;
-    if (a.bundle > 1 || a.n_snap > 0 || a.resN != nullptr || !a.sse || a.pl || a.esum || a.wts || !(a.sse_cut >= 0.0)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)nsys), block(64);
-    switch (a.L) {
-#define TRPL_CASE(LL) \
-    case LL: hipLaunchKernelGGL((stepper_kernel<LL, false, false>), grid, block, 0, stream, a); break;
-        TRPL_CASE(4) TRPL_CASE(8) TRPL_CASE(16) TRPL_CASE(32) TRPL_CASE(64) TRPL_CASE(128)
-        TRPL_CASE(256) TRPL_CASE(512)
-#undef TRPL_CASE
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    if (!a.sse) return false;
+    if constexpr (TRPL_STEPPER_CUT != 0) return !a.pl && !a.esum && !a.wts && a.sse_cut >= 0.0;
+    else return a.esum && (TRPL_STEPPER_WEIGHTED != 0) == (a.wts != nullptr);
 }
-#elif TRPL_STEPPER_MOMENTS
-// TRPL_FLAG_MOMENTS: likelihood mode only -- one instantiation per L, no bundles, no snapshot / resume forms (check_launch)
+// likelihood mode only -- one instantiation per L, no bundles, no snapshot / resume forms (check_launch); TRPL_FLAG_CUT: FAST only
 template <bool STRICT>
 hipError_t launch_stepper(const StepArgs &a, hipStream_t stream)
 {
+    static_assert(!(TRPL_STEPPER_CUT != 0 && STRICT), "the cut sink is batched: FAST only");
     const int64_t nsys = a.S * a.C;
     if (nsys <= 0) return hipSuccess;
-    if (a.bundle > 1 || a.n_snap > 0 || a.resN != nullptr || !a.sse || !a.esum) return hipErrorInvalidValue;
-    if ((TRPL_STEPPER_WEIGHTED != 0) != (a.wts != nullptr)) return hipErrorInvalidValue;
+    if (a.bundle > 1 || a.n_snap > 0 || a.resN != nullptr || !sink_args_ok(a)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)nsys), block(64);
     switch (a.L) {
 #define TRPL_CASE(LL) \

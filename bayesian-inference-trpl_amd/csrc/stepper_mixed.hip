@@ -25,5 +25,5 @@ static hipError_t launch_stepper_mixed_impl(const StepArgs &a, hipStream_t strea
     return hipGetLastError();
 }
 
-hipError_t launch_stepper_mixed(const StepArgs &a, hipStream_t stream) { return launch_stepper_mixed_impl(a, stream); }
+template <> hipError_t launch_variant<Variant::plain, 0, Variant::mixed>(const StepArgs &a, hipStream_t stream) { return launch_stepper_mixed_impl(a, stream); }
 }  // namespace trpl

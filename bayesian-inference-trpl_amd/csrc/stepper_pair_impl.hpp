@@ -508,12 +508,8 @@ hipError_t launch_stepper_pair_t(const StepArgs &a, hipStream_t stream)
     const bool always_seam = (a.flags & kFlagPairAlwaysSeam) != 0;
     const bool snap = a.n_snap > 0 || a.resN != nullptr;
     const dim3 grid((unsigned)nblk), block(64);
-#if TRPL_STEPPER_CUT                                // likelihood mode only: no snapshot forms (check_launch)
-    if (snap || !a.sse || a.pl || a.esum || a.wts || !(a.sse_cut >= 0.0)) return hipErrorInvalidValue;
-    if (always_seam) hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false, false>), grid, block, 0, stream, a);
-    else             hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false>), grid, block, 0, stream, a);
-#elif TRPL_STEPPER_MOMENTS                          // likelihood mode only: no snapshot forms (check_launch)
-    if (snap || !a.sse || !a.esum || (TRPL_STEPPER_WEIGHTED != 0) != (a.wts != nullptr)) return hipErrorInvalidValue;
+#if TRPL_STEPPER_MOMENTS || TRPL_STEPPER_CUT         // likelihood mode only: no snapshot forms (check_launch)
+    if (snap || !sink_args_ok(a)) return hipErrorInvalidValue;
     if (always_seam) hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false, false>), grid, block, 0, stream, a);
     else             hipLaunchKernelGGL((pair::stepper_pair_kernel<ISO, false>), grid, block, 0, stream, a);
 #else

@@ -7,7 +7,7 @@
 #include "pcr_batched_impl.hpp"
 
 namespace trpl {
-hipError_t launch_stepper_strict(const StepArgs &a, hipStream_t stream) { return launch_stepper<true>(a, stream); }
+template <> hipError_t launch_variant<Variant::plain, 0, Variant::strict>(const StepArgs &a, hipStream_t stream) { return launch_stepper<true>(a, stream); }
 hipError_t launch_pcr_batched_strict(const void *ld, const void *d, const void *ud, const void *b, void *x,
                                      int64_t S, int L, int elem_bytes, hipStream_t stream)
 {

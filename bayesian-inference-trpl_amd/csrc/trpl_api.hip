@@ -175,11 +175,22 @@ struct StepperChoice {
     enum Family { Single, Pair, F32 } family;        // trpl::stepper_kernel / pair::stepper_pair_kernel / f32::stepper_kernel
     int32_t L, bundle;                               // bundle: m of TRPL_FLAG_BUNDLE(m)
     bool strict, snap, mixed, hist32;                // template arguments of the one-system kernel, with bundle > 1
-    bool predict;                                    // the instantiation in namespace trpl::predict
-    bool moments;                                    // TRPL_FLAG_MOMENTS: the instantiation in namespace trpl::moments[::predict]
-    bool weighted;                                   // TRPL_FLAG_WEIGHTED: the instantiation in namespace trpl::weighted[::predict]
-    bool cut;                                        // TRPL_FLAG_CUT: the instantiation in namespace trpl::cut[::predict]
+    bool predict;                                    // TRPL_FLAG_PREDICT: the instantiation in namespace ...::predict
+    trpl::Variant::Sink sink;                        // TRPL_FLAG_MOMENTS / _WEIGHTED / _CUT: the instantiation in namespace trpl::<sink>
     bool optimistic;                                 // paired kernel: the optimistic seam (not TRPL_FLAG_PAIR_ALWAYS_SEAM)
+};
+
+// The likelihood sinks a flag selects, indexed by Variant::Sink: all of them exist for the plain fp64 steppers (FAST, paired
+// and, where `strict` says so, STRICT) in likelihood mode only.  A sink excludes the ones before it in this table.
+const struct SinkInfo {
+    uint32_t flag;
+    const char *name, *ns;                           // ns: its level of the kernels' namespace
+    bool strict;                                     // has STRICT units (the cut sink is batched: another granularity than STRICT's emit)
+} kSinks[trpl::Variant::kSinks] = {
+    {0, "", "", true},
+    {TRPL_FLAG_MOMENTS, "TRPL_FLAG_MOMENTS", "moments::", true},
+    {TRPL_FLAG_WEIGHTED, "TRPL_FLAG_WEIGHTED", "weighted::", true},      // emits both sums itself
+    {TRPL_FLAG_CUT, "TRPL_FLAG_CUT", "cut::", false},                    // tests the plain sse
 };
 
 // THE function that maps a call to a kernel: launch(), trpl_kernel_name, trpl_kernel_variant and pin_variant read its answer.
@@ -192,9 +203,9 @@ StepperChoice classify_stepper(uint32_t flags, int32_t L, int64_t nsys, int64_t 
     StepperChoice c = {StepperChoice::Single, L, flags_bundle(flags)};
     c.snap = snap;
     c.predict = (flags & TRPL_FLAG_PREDICT) != 0;
-    c.moments = (flags & TRPL_FLAG_MOMENTS) != 0;
-    c.weighted = (flags & TRPL_FLAG_WEIGHTED) != 0;
-    c.cut = (flags & TRPL_FLAG_CUT) != 0;
+    c.sink = trpl::Variant::plain;
+    for (int k = 1; k < trpl::Variant::kSinks; k++)
+        if (flags & kSinks[k].flag) c.sink = (trpl::Variant::Sink)k;        // check_launch accepts at most one
     c.optimistic = TRPL_PAIR_OPTIMISTIC != 0 && !(flags & TRPL_FLAG_PAIR_ALWAYS_SEAM);
     if (flags & TRPL_FLAG_FP32) c.family = StepperChoice::F32;
     else if (flags & TRPL_FLAG_STRICT) c.strict = true;
@@ -206,6 +217,31 @@ StepperChoice classify_stepper(uint32_t flags, int32_t L, int64_t nsys, int64_t 
             c.family = StepperChoice::Pair;
     }
     return c;
+}
+
+// The launcher of a choice, or nullptr where none is built: the table has exactly the lines of stepper_variants.hpp.
+typedef hipError_t StepperLauncher(const trpl::StepArgs &, hipStream_t);
+trpl::Variant::Unit unit_of(const StepperChoice &c)
+{
+    if (c.family == StepperChoice::F32) return trpl::Variant::f32;
+    if (c.mixed) return trpl::Variant::mixed;
+    if (c.hist32) return trpl::Variant::hist32;
+    if (c.family == StepperChoice::Pair) return trpl::Variant::pair;
+    return c.strict ? trpl::Variant::strict : trpl::Variant::fast;
+}
+StepperLauncher *find_launcher(const StepperChoice &c)
+{
+    static const struct Table {
+        StepperLauncher *fn[trpl::Variant::kSinks][2][trpl::Variant::kUnits] = {};
+        Table()
+        {
+#define TRPL_VARIANT(sink, predict, unit) \
+    fn[trpl::Variant::sink][predict][trpl::Variant::unit] = trpl::launch_variant<trpl::Variant::sink, predict, trpl::Variant::unit>;
+#include "stepper_variants.hpp"
+#undef TRPL_VARIANT
+        }
+    } table;
+    return table.fn[c.sink][c.predict][unit_of(c)];
 }
 
 int check_variant_flags(uint32_t flags, int32_t L)
@@ -223,20 +259,23 @@ uint32_t pin_variant(uint32_t flags, int64_t nsys, int32_t L, int64_t steps)
     return flags | (classify_stepper(flags, L, nsys, steps, false).family == StepperChoice::Pair ? TRPL_FLAG_KERNEL_PAIR : TRPL_FLAG_KERNEL_SINGLE);
 }
 
-// TRPL_FLAG_CUT: what the cut sink does not combine with.  Flags only, so that trpl_loglik_cut[_dev] can answer before they touch a device.
-int check_cut_flags(uint32_t flags)
+// What sink k refuses by the flags alone: the sinks before it (kSinks) and the steppers it is not built for.
+int check_sink_flags(int k, uint32_t flags)
 {
-    if (!(flags & TRPL_FLAG_CUT)) return TRPL_OK;
-    if (flags & (TRPL_FLAG_MOMENTS | TRPL_FLAG_WEIGHTED))
-        return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_CUT does not combine with %s (out of scope: the cut tests the plain sse)",
-                        (flags & TRPL_FLAG_MOMENTS) ? "TRPL_FLAG_MOMENTS" : "TRPL_FLAG_WEIGHTED");
-    if (flags & TRPL_FLAG_STRICT)
-        return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_CUT is not built for TRPL_FLAG_STRICT (its sink emits column by column: another granularity)");
+    const SinkInfo &s = kSinks[k];
+    if (!(flags & s.flag)) return TRPL_OK;
+    for (int j = 1; j < k; j++)
+        if (flags & kSinks[j].flag)
+            return api_fail(TRPL_ERR_ARG, "%s does not combine with %s (one sink per launch)", s.name, kSinks[j].name);
+    if (!s.strict && (flags & TRPL_FLAG_STRICT)) return api_fail(TRPL_ERR_UNSUPPORTED, "%s is not built for TRPL_FLAG_STRICT", s.name);
     if (flags & (TRPL_FLAG_FP32 | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
-        return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_CUT is not built for TRPL_FLAG_FP32, TRPL_FLAG_MIXED or TRPL_FLAG_HIST32");
-    if (flags_bundle(flags) > 1) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_CUT is not built for TRPL_FLAG_BUNDLE(m > 1)");
+        return api_fail(TRPL_ERR_UNSUPPORTED, "%s is not built for TRPL_FLAG_FP32, TRPL_FLAG_MIXED or TRPL_FLAG_HIST32", s.name);
+    if (flags_bundle(flags) > 1) return api_fail(TRPL_ERR_UNSUPPORTED, "%s is not built for TRPL_FLAG_BUNDLE(m > 1)", s.name);
     return TRPL_OK;
 }
+
+// TRPL_FLAG_CUT: what the cut sink does not combine with.  Flags only, so that trpl_loglik_cut[_dev] can answer before they touch a device.
+int check_cut_flags(uint32_t flags) { return check_sink_flags(trpl::Variant::cut, flags); }
 
 // Everything a stepper launch refuses because of its flags and shape: launch() and trpl_kernel_name run the same checks
 // before they classify, so a kernel name is only ever returned for an instantiation that exists and that the launch would run.
@@ -247,23 +286,11 @@ int check_launch(uint32_t flags, int32_t L, int64_t steps, bool snap, bool resum
     if (int rc = check_variant_flags(flags, L)) return rc;
     if (flags_bdf_order(flags) > 5u) return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_BDF_ORDER(%u): the order cap must be 1 .. 5 (0: the reference's ramp)", flags_bdf_order(flags));
     const int32_t bundle = flags_bundle(flags);
-    if (flags & TRPL_FLAG_MOMENTS) {                                        // the moments sink: plain fp64 steppers, likelihood mode
-        if (flags & (TRPL_FLAG_FP32 | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
-            return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_MOMENTS is not built for TRPL_FLAG_FP32, TRPL_FLAG_MIXED or TRPL_FLAG_HIST32");
-        if (bundle > 1) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_MOMENTS is not built for TRPL_FLAG_BUNDLE(m > 1)");
-        if (snap || resume) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_MOMENTS has no snapshot / resume instantiations (likelihood mode only)");
+    for (int k = 1; k < trpl::Variant::kSinks; k++) {                       // the sinks, in the table's order
+        if (int rc = check_sink_flags(k, flags)) return rc;
+        if ((flags & kSinks[k].flag) && (snap || resume))
+            return api_fail(TRPL_ERR_UNSUPPORTED, "%s has no snapshot / resume instantiations (likelihood mode only)", kSinks[k].name);
     }
-    if (flags & TRPL_FLAG_WEIGHTED) {                                       // the weighted sink: where the moments sink exists
-        if (flags & TRPL_FLAG_MOMENTS)
-            return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_WEIGHTED and TRPL_FLAG_MOMENTS exclude each other (the weighted sink already emits both sums)");
-        if (flags & (TRPL_FLAG_FP32 | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
-            return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_WEIGHTED is not built for TRPL_FLAG_FP32, TRPL_FLAG_MIXED or TRPL_FLAG_HIST32");
-        if (bundle > 1) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_WEIGHTED is not built for TRPL_FLAG_BUNDLE(m > 1)");
-        if (snap || resume) return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_WEIGHTED has no snapshot / resume instantiations (likelihood mode only)");
-    }
-    if (int rc = check_cut_flags(flags)) return rc;
-    if ((flags & TRPL_FLAG_CUT) && (snap || resume))
-        return api_fail(TRPL_ERR_UNSUPPORTED, "TRPL_FLAG_CUT has no snapshot / resume instantiations (likelihood mode only)");
     if (flags & TRPL_FLAG_PREDICT) {                                        // the extrapolated start: plain fp64 steppers only
         if (flags & (TRPL_FLAG_FP32 | TRPL_FLAG_MIXED | TRPL_FLAG_HIST32))
             return api_fail(TRPL_ERR_ARG, "TRPL_FLAG_PREDICT excludes TRPL_FLAG_FP32, TRPL_FLAG_MIXED and TRPL_FLAG_HIST32");
@@ -366,31 +393,11 @@ int launch(const trpl::StepArgs &a_in, uint32_t flags, hipStream_t st, int64_t s
     trpl::StepArgs a = a_in;
     a.bundle = c.bundle;
     if (c.family == StepperChoice::Pair) build_pair_table(a);
-    hipError_t (*fn)(const trpl::StepArgs &, hipStream_t) = c.predict ? trpl::launch_stepper_predict_fast : trpl::launch_stepper_fast;
-    const char *what = "";                          // the word the error message starts with
-    if (c.family == StepperChoice::F32) { fn = trpl::launch_stepper_f32; what = "fp32 "; }
-#ifdef TRPL_EXPERIMENTAL
-    else if (c.mixed) { fn = trpl::launch_stepper_mixed; what = "mixed "; }
-    else if (c.hist32) { fn = trpl::launch_stepper_hist32; what = "hist32 "; }
-#endif
-    else if (c.family == StepperChoice::Pair) { fn = c.predict ? trpl::launch_stepper_pair_predict : trpl::launch_stepper_pair; what = "pair "; }
-    else if (c.strict) fn = c.predict ? trpl::launch_stepper_predict_strict : trpl::launch_stepper_strict;
-    if (c.moments) {                                 // check_launch has left the plain fp64 steppers only
-        if (c.family == StepperChoice::Pair) fn = c.predict ? trpl::launch_stepper_moments_predict_pair : trpl::launch_stepper_moments_pair;
-        else if (c.strict) fn = c.predict ? trpl::launch_stepper_moments_predict_strict : trpl::launch_stepper_moments_strict;
-        else fn = c.predict ? trpl::launch_stepper_moments_predict_fast : trpl::launch_stepper_moments_fast;
-    }
-    if (c.weighted) {                                // likewise
-        if (c.family == StepperChoice::Pair) fn = c.predict ? trpl::launch_stepper_weighted_predict_pair : trpl::launch_stepper_weighted_pair;
-        else if (c.strict) fn = c.predict ? trpl::launch_stepper_weighted_predict_strict : trpl::launch_stepper_weighted_strict;
-        else fn = c.predict ? trpl::launch_stepper_weighted_predict_fast : trpl::launch_stepper_weighted_fast;
-    }
-    if (c.cut) {                                     // check_launch has left the two FAST steppers only
-        if (c.family == StepperChoice::Pair) fn = c.predict ? trpl::launch_stepper_cut_predict_pair : trpl::launch_stepper_cut_pair;
-        else fn = c.predict ? trpl::launch_stepper_cut_predict_fast : trpl::launch_stepper_cut_fast;
-    }
+    static const char *const kWord[trpl::Variant::kUnits] = {"", "", "pair ", "fp32 ", "mixed ", "hist32 "};   // what the error message starts with
+    StepperLauncher *const fn = find_launcher(c);
+    if (!fn) return api_fail(TRPL_ERR_UNSUPPORTED, "no stepper is built for this combination of flags (flags 0x%x, L = %d)", flags, a.L);
     const hipError_t e = fn(a, st);
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "%sstepper launch: %s", what, hipGetErrorString(e));
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "%sstepper launch: %s", kWord[unit_of(c)], hipGetErrorString(e));
     return TRPL_OK;
 }
 
@@ -427,8 +434,10 @@ int trpl_kernel_name(int64_t nsys, int32_t L, int64_t steps, uint32_t flags, int
     // (`snapshots` covers snapshots AND resume; the fp32 stepper has one instantiation and accepts a resume)
     if (int rc = check_launch(flags, L, steps, snapshots != 0 && !(flags & TRPL_FLAG_FP32), false)) return rc;
     const StepperChoice c = classify_stepper(flags, L, nsys, steps, snapshots != 0);
-    const char *tf[2] = {"false", "true"};           // stepper_predict_*.hip, stepper_moments_*.hip, stepper_weighted_*.hip, stepper_cut_*.hip
-    const char *ns = c.cut ? (c.predict ? "trpl::cut::predict::" : "trpl::cut::") : c.weighted ? (c.predict ? "trpl::weighted::predict::" : "trpl::weighted::") : c.moments ? (c.predict ? "trpl::moments::predict::" : "trpl::moments::") : (c.predict ? "trpl::predict::" : "trpl::");
+    if (!find_launcher(c)) return api_fail(TRPL_ERR_UNSUPPORTED, "no stepper is built for this combination of flags (flags 0x%x, L = %d)", flags, L);
+    const char *tf[2] = {"false", "true"};
+    char ns[64];                                     // trpl::[<sink>::][predict::] (stepper_impl.hpp: TRPL_VARIANT_NS_BEGIN)
+    snprintf(ns, sizeof ns, "trpl::%s%s", kSinks[c.sink].ns, c.predict ? "predict::" : "");
     int n;
     if (c.family == StepperChoice::F32)
         n = snprintf(buf, (size_t)buflen, "%sf32::stepper_kernel<%d>", ns, c.L);

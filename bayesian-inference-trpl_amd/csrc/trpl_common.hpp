@@ -96,37 +96,20 @@ __device__ __forceinline__ void bdf_row(int32_t row, T &a0, T &a1, T &a2, T &a3,
 // host-side row interpolation of the unfused call sequence (likelihood.hip; -ffp-contract=off)
 void interp_rows_any(const void *pl, int elem_bytes, int64_t rows, int64_t ld, const int32_t *hi, const double *dx,
                      const double *h, int64_t n_obs, double *out, int64_t out_ld);
-// The stepper launchers, one per translation unit because each unit has its own -ffp-contract flag (Makefile): what a
-// StepperChoice selects among (launch(), trpl_api.hip).  Inside a unit L, snapshots and bundles pick the instantiation.
-hipError_t launch_stepper_fast(const StepArgs &a, hipStream_t stream);            // one system per wavefront, fp64
-hipError_t launch_stepper_strict(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_pair(const StepArgs &a, hipStream_t stream);            // two systems per wavefront: FAST, L = 128
-hipError_t launch_stepper_f32(const StepArgs &a, hipStream_t stream);             // fp32 state, L >= 128
-// TRPL_FLAG_PREDICT (stepper_predict_{fast,strict,pair}.hip): the fp64 steppers with the extrapolated start of each step
-hipError_t launch_stepper_predict_fast(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_predict_strict(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_pair_predict(const StepArgs &a, hipStream_t stream);
-// TRPL_FLAG_MOMENTS (stepper_moments_*.hip): the fp64 steppers whose sink also emits esum, with and without PREDICT
-hipError_t launch_stepper_moments_fast(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_moments_strict(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_moments_pair(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_moments_predict_fast(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_moments_predict_strict(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_moments_predict_pair(const StepArgs &a, hipStream_t stream);
-// TRPL_FLAG_WEIGHTED (stepper_weighted_*.hip): the moments steppers whose sink weights every term
-hipError_t launch_stepper_weighted_fast(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_weighted_strict(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_weighted_pair(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_weighted_predict_fast(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_weighted_predict_strict(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_weighted_predict_pair(const StepArgs &a, hipStream_t stream);
-// TRPL_FLAG_CUT (stepper_cut_*.hip): the FAST likelihood steppers whose sink stops a system once its sse is above StepArgs::sse_cut
-hipError_t launch_stepper_cut_fast(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_cut_pair(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_cut_predict_fast(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_cut_predict_pair(const StepArgs &a, hipStream_t stream);
-hipError_t launch_stepper_mixed(const StepArgs &a, hipStream_t stream);           // L >= 128; `make EXPERIMENTAL=1` only: the default
-hipError_t launch_stepper_hist32(const StepArgs &a, hipStream_t stream);          // L = 256 / 512;   library must not reference them
+// The stepper launchers: what a StepperChoice selects among (launch(), trpl_api.hip), one per line of stepper_variants.hpp and
+// one per object, because each object has its own -ffp-contract flag and TRPL_STEPPER_* switches (Makefile).  Inside an object
+// L, snapshots and bundles pick the instantiation.  A launcher is the specialisation of launch_variant for its line.
+struct Variant {
+    enum Sink { plain, moments, weighted, cut, kSinks };              // what the likelihood sink emits (stepper_impl.hpp: PlSinkT)
+    // fast / strict: one system per wavefront, fp64; pair: two systems per wavefront, FAST, L = 128; f32: fp32 state, L >= 128;
+    // mixed (L >= 128) and hist32 (L = 256 / 512): `make EXPERIMENTAL=1` only
+    enum Unit { fast, strict, pair, f32, mixed, hist32, kUnits };
+};
+template <int SINK, int PREDICT, int UNIT> hipError_t launch_variant(const StepArgs &a, hipStream_t stream);
+#define TRPL_VARIANT(sink, predict, unit) \
+    template <> hipError_t launch_variant<Variant::sink, predict, Variant::unit>(const StepArgs &a, hipStream_t stream);
+#include "stepper_variants.hpp"
+#undef TRPL_VARIANT
 
 // likelihood.hip
 hipError_t launch_log10_clamp(void *x, int elem_bytes, int64_t rows, int64_t cols, int64_t ld, double mn,

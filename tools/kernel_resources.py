@@ -5,7 +5,9 @@
                                        moments_predict_strict moments_predict_pair weighted_fast weighted_strict
                                        weighted_pair weighted_predict_fast weighted_predict_strict weighted_predict_pair
                                        cut_fast cut_pair cut_predict_fast cut_predict_pair posterior posterior_scan predictive]
-(cross-compiles, no GPU needed; a name is the translation unit csrc/stepper_<name>.hip, or csrc/<name>.hip where that exists)"""
+(cross-compiles, no GPU needed; a name is an object of the library without its stepper_ prefix: csrc/<name>.hip or
+csrc/stepper_<name>.hip where that file exists, otherwise a variant of csrc/stepper_variants.hpp -- [sink_][predict_]unit --
+which is stepper_[pair_]variant.hip with the switch of each of its words, as the Makefile compiles it)"""
 import os
 import re
 import subprocess
@@ -13,19 +15,26 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bayesian-inference-trpl_amd", "csrc")
-CONTRACT = {"strict": "off", "predict_strict": "off", "moments_strict": "off", "moments_predict_strict": "off",
-            "weighted_strict": "off", "weighted_predict_strict": "off", "posterior": "off",
-            "posterior_scan": "off"}                                         # the Makefile's -ffp-contract of each unit; default on
+SWITCHES = ("moments", "weighted", "cut", "predict", "strict")              # -DTRPL_STEPPER_<WORD>=1 of a variant's words
+CONTRACT_OFF = ("posterior", "posterior_scan")                              # beside every stepper with the word "strict" (Makefile)
+
+
+def unit(n):
+    """(source, compiler flags) of the object `n`"""
+    words = n.split("_")
+    flags = ["-ffp-contract=" + ("off" if "strict" in words or n in CONTRACT_OFF else "on")]
+    for src in (os.path.join(CSRC, "%s.hip" % n), os.path.join(CSRC, "stepper_%s.hip" % n)):
+        if os.path.isfile(src):
+            return src, flags
+    src = os.path.join(CSRC, "stepper_pair_variant.hip" if words[-1] == "pair" else "stepper_variant.hip")
+    return src, flags + ["-DTRPL_STEPPER_%s=1" % w.upper() for w in words if w in SWITCHES]
 
 
 def main():
     for n in sys.argv[1:] or ["pair", "fast", "strict", "hist32"]:
-        src = os.path.join(CSRC, "%s.hip" % n)
-        if not os.path.isfile(src):
-            src = os.path.join(CSRC, "stepper_%s.hip" % n)
-        r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950",
-                            "-ffp-contract=" + CONTRACT.get(n, "on"), "-c", src,
-                            "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+        src, flags = unit(n)
+        r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950"] + flags +
+                           ["-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
         for b in re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]:
             name = b.split("\n")[0].split(" ")[0]
             g = lambda k: (re.search(k + r": (\d+)", b) or [None, "?"])[1]
