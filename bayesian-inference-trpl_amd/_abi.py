@@ -67,6 +67,9 @@ KERNEL_FAST, KERNEL_FAST_PAIR, KERNEL_STRICT, KERNEL_FP32, KERNEL_MIXED, KERNEL_
 ABI_VERSION = 5
 MAX_SNAPS = 16
 TF_SCAN_MAX = 64              # TRPL_TF_SCAN_MAX: temperatures of one trpl_posterior_tf_scan
+Q_MAX, Q_BLOCK = 8, 256       # TRPL_Q_MAX: requests of one trpl_weighted_quantiles; TRPL_Q_BLOCK: threads that sum one column
+Q_FIRST_ABOVE, Q_LAST_BELOW = 1, 2      # TRPL_Q_FIRST_ABOVE / TRPL_Q_LAST_BELOW: the two selection rules
+Q_FORCE_STREAM = 0x1          # TRPL_Q_FORCE_STREAM (tests): the streamed kernel at any column length
 
 
 class TrplError(RuntimeError):
@@ -171,6 +174,10 @@ SIGNATURES = {
     "trpl_predictive_accumulate_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _u32, _vp, _vp, _i64, _vp],
     "trpl_predictive_finish_dev": [_vp, _i64, _vp, _vp],
     "trpl_predictive": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _u32, _vp, _i32, _pd],
+    "trpl_quantiles_stage_rows": [],
+    "trpl_weighted_quantiles_dev": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _u32, _vp, _vp],
+    "trpl_weighted_quantiles": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _u32, _vp, _i32, _pd],
+    "trpl_predictive_gather_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _u32, _vp, _i64, _i64, _vp, _vp],
     "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
     "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
 }
@@ -299,7 +306,8 @@ def lib():
             fn.argtypes = argtypes
             fn.restype = C.c_char_p if name == "trpl_last_error" else (
                 C.c_int64 if name in ("trpl_posterior_workspace_bytes", "trpl_posterior_tf_scan_workspace", "trpl_shard_of",
-                                     "trpl_predictive_state_bytes", "trpl_predictive_workspace_bytes") else C.c_int)
+                                     "trpl_predictive_state_bytes", "trpl_predictive_workspace_bytes",
+                                     "trpl_quantiles_stage_rows") else C.c_int)
         _lib = dll
     return _lib
 

@@ -341,6 +341,55 @@ def predictive_finish_device(state, out):
                                                      _chk(out, torch.float64, "out"), _stream()))
 
 
+# ---- weighted quantiles of many columns under one weight vector (trpl_weighted_quantiles_dev, trpl_predictive_gather_dev) ----
+def quantile_requests(q, rule=None):
+    """(q, rule) as the host arrays trpl_weighted_quantiles* takes: q a number or a sequence of numbers in (0, 1); rule None
+    (Q_LAST_BELOW for q < 0.5, else Q_FIRST_ABOVE: the two ends of a credible interval and the median above), one rule, or
+    one per q."""
+    q = np.atleast_1d(np.ascontiguousarray(q, dtype=np.float64))
+    if q.ndim != 1:
+        raise ValueError("q must be a number or a one-dimensional sequence")
+    if rule is None:
+        rule = np.where(q < 0.5, _abi.Q_LAST_BELOW, _abi.Q_FIRST_ABOVE)
+    rule = np.ascontiguousarray(np.broadcast_to(np.asarray(rule, dtype=np.int32), q.shape))
+    return q, rule
+
+
+def weighted_quantiles_device(Y, Wq, q, out, rule=None, n=None, flags=0):
+    """trpl_weighted_quantiles_dev: out (K, ncols) f64 <- the K weighted quantiles of every column of the store Y (ncols, ldy)
+    f64 -- column c's n (default ldy) keys contiguous in row c of the tensor -- under the weights Wq (>= n,) f64 shared by
+    all columns (a row counts iff its weight is finite and > 0).  q, rule: quantile_requests."""
+    import torch
+    q, rule = quantile_requests(q, rule)
+    if Y.dim() != 2 or Wq.dim() != 1:
+        raise ValueError("Y must be (ncols, ldy) and Wq one-dimensional")
+    ncols, ldy = Y.shape
+    n = int(ldy if n is None else n)
+    if Wq.shape[0] < n or tuple(out.shape) != (q.size, ncols):
+        raise ValueError("Wq must hold n weights and out must be (K, ncols)")
+    _abi.check(_abi.lib().trpl_weighted_quantiles_dev(_chk(Y, torch.float64, "Y"), ncols, n, ldy, _chk(Wq, torch.float64, "Wq"),
+                                                      _abi.ptr(q), _abi.ptr(rule), q.size, int(flags),
+                                                      _chk(out, torch.float64, "out"), _stream()))
+
+
+def predictive_gather_device(pl, W, Y, Wq, row0=0, mag=None, status=None, ncol=None, flags=0):
+    """trpl_predictive_gather_dev: the y = log10 PL + mag of the block pl (rows, ld) f32/f64, as predictive_accumulate_device
+    forms them, transposed into the store: Y[i, row0 + j] = y[j, i] for Y (ncol, ldy) f64, and Wq[row0 + j] = W[j] for a
+    used row (weight finite and > 0, status zero or absent), else 0."""
+    import torch
+    if pl.dim() != 2 or pl.dtype not in (torch.float32, torch.float64):
+        raise ValueError("pl must be a 2-D float32/float64 tensor")
+    rows, ld = pl.shape
+    ncol = int(ld if ncol is None else ncol)
+    if Y.dim() != 2 or Y.shape[0] != ncol or Wq.dim() != 1 or Wq.shape[0] < int(row0) + rows or tuple(W.shape) != (rows,) \
+            or (mag is not None and tuple(mag.shape) != (rows,)) or (status is not None and tuple(status.shape) != (rows,)):
+        raise ValueError("shape mismatch")
+    _abi.check(_abi.lib().trpl_predictive_gather_dev(
+        _chk(pl, pl.dtype, "pl"), pl.element_size(), rows, ncol, ld, None if mag is None else _chk(mag, torch.float64, "mag"),
+        _chk(W, torch.float64, "W"), None if status is None else _chk(status, torch.int32, "status"), int(flags),
+        _chk(Y, torch.float64, "Y"), Y.shape[1], int(row0), _chk(Wq, torch.float64, "Wq"), _stream()))
+
+
 def posterior_hist_device(x, W, lo, hi, out, y=None, ylo=0.0, yhi=1.0):
     """out (bins,) or (bins, ybins) += weighted counts (W None: counts); the caller zeroes out."""
     import torch

@@ -185,6 +185,40 @@ def credible_interval(X, P):
     return xs[np.where(cs < 0.025)[0][-1]], xs[np.where(cs > 0.975)[0][0]]
 
 
+def quantiles(V, W, q, rule=None, device=0, info=None, flags=0):
+    """Weighted quantiles of the columns V (D, S) under the weights W (S,) in one device call (trpl_weighted_quantiles,
+    include/trpl.h): returns (K, D) for K requests q in (0, 1).  rule: one of _abi.Q_LAST_BELOW (the largest value whose
+    cumulative weight is < q sum W; NaN if there is none) / _abi.Q_FIRST_ABOVE (the smallest whose cumulative weight is
+    > q sum W) per request; None takes LAST_BELOW for q < 0.5 and FIRST_ABOVE otherwise.  A sample counts iff its weight is
+    finite and > 0; a NaN value among those makes that column's quantiles NaN."""
+    from .device import quantile_requests
+    V = _f64(V)
+    W = _f64(W)
+    if V.ndim == 1:
+        V = V[None, :]
+    if V.ndim != 2 or W.shape != (V.shape[1],):
+        raise ValueError("V must be (D, S) and W (S,)")
+    q, rule = quantile_requests(q, rule)
+    D, S = V.shape
+    out = np.empty((q.size, D))
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_weighted_quantiles(_abi.ptr(V), D, S, S, _abi.ptr(W), _abi.ptr(q), _abi.ptr(rule), q.size, int(flags),
+                                                  _abi.ptr(out), int(device), _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value)
+    return out
+
+
+def credible_intervals(columns, P, lo=0.025, hi=0.975, device=0):
+    """credible_interval (utils.py:185-196) of every column in ONE device call: `columns` maps a name to its (S,) values, P
+    are the weights.  Returns dict name -> (low, high): the last value whose cumulative weight is below lo * sum P and the
+    first whose cumulative weight is above hi * sum P (low is NaN where the reference raises IndexError)."""
+    names = list(columns)
+    V = np.stack([_f64(columns[k]) for k in names])
+    r = quantiles(V, P, [lo, hi], [_abi.Q_LAST_BELOW, _abi.Q_FIRST_ABOVE], device=device)
+    return {k: (float(r[0, i]), float(r[1, i])) for i, k in enumerate(names)}
+
+
 def summarize(columns, P, device=0):
     """stats_summarize + calc_covariance (utils.py:117-143) in one device pass: `columns` maps a name to its
     (S,) values.  Returns dict(names, mean, variance, sample_std, skew, kurtosis, covariance (D, D), w2)."""

@@ -857,6 +857,61 @@ int trpl_predictive(const void *plI, int32_t elem_bytes, int64_t rows, int64_t n
                     const double *W, const int32_t *status, uint32_t flags, double *out, int32_t device, double *seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_weighted_quantiles* -- weighted quantiles of many columns that share one weight vector: the credible interval of
+ * every parameter in one call (utils.py:185-196 is one column per call on the host), and, after trpl_predictive_gather_dev,
+ * the median and the 2.5 % / 97.5 % band of the posterior-predictive PL -- under weights that span 20 decades mean +- sd is
+ * no interval and the envelope is set by samples of weight 1e-300.  (csrc/quantiles.hip)
+ *
+ * Inputs.  Keys Y[ncols][ldy] fp64, the n keys of column c contiguous at Y + c * ldy (ldy >= n); weights Wq[n], shared by
+ * all columns; K <= TRPL_Q_MAX requests (q[k], rule[k]), HOST arrays in both forms.  Output out[K][ncols].
+ * Used rows.  Row j is used iff Wq[j] is finite and > 0.  An unused row's key is never looked at, NaN included.
+ * Cumulative sum.  S_c(v) = the sum of Wq[j] over the used rows of column c with key <= v, formed in ONE fixed order that
+ * is a pure function of n: thread t of a workgroup of TRPL_Q_BLOCK threads adds rows t, t + B, t + 2B, ... in that order;
+ * then a fixed tree over the 64 lanes of a wave (lane l += lane l + 32, + 16, ... + 1); then the waves in wave order.
+ * sw = S_c(+inf).  Floating-point addition is monotone in each operand, so this sum is non-decreasing in v and the selection
+ * below is well defined.  Keys equal as numbers form one point carrying their total weight; -0.0 and +0.0 are equal as
+ * numbers (either may be returned: == on a returned key is the test).
+ * Rules.  TRPL_Q_FIRST_ABOVE: the smallest key with S_c(v) > q * sw.  TRPL_Q_LAST_BELOW: the largest key with
+ * S_c(v) < q * sw; if there is none the result is NaN (the reference raises IndexError there).  On tie-free keys with
+ * weights that sum to 1 these are credible_interval's X_high and X_low, up to the rounding of the sum.  q * sw is one fp64
+ * product.  (FIRST_ABOVE is NaN as well in the one case where no key qualifies: a subnormal sw with q * sw rounding to sw.)
+ * NaN rule.  A NaN key in a used row makes every quantile of that column NaN, as trpl_predictive* does for mean and variance.
+ * +-inf keys order like numbers.  sw = 0 (no used row) gives NaN everywhere, and so does a sw that overflowed.
+ * Determinism.  No atomics; nothing depends on scheduling or on the device: the same call gives the same bits.  Columns of
+ * n <= trpl_quantiles_stage_rows() rows are held in LDS (two workgroups per compute unit fit), longer ones are streamed from
+ * memory in every pass; TRPL_Q_FORCE_STREAM (tests) takes the streamed form at any n.  Both give the same bits.
+ * Method.  Bisection on the order-preserving 64-bit image of the key, all K requests per pass, starting from the column's
+ * smallest and largest used key: at most 64 passes over the column, plus one for a LAST_BELOW request.
+ *
+ * trpl_predictive_gather_dev fills the store from a resident PL block, beside trpl_predictive_accumulate_dev and with its
+ * arguments: Y[i][row0 + j] = y[j][i] of trpl_predictive* (the same device function, TRPL_FLAG_NORMALIZE / TRPL_FLAG_PL_F32)
+ * for i < ncol, j < rows, and Wq[row0 + j] = W[j] if W[j] is finite and > 0 and (status == NULL or status[j] == 0), else 0.
+ * Every row is written (an unused row's y may be anything; its weight 0 keeps it out).  Any ld >= ncol, rows need only
+ * element alignment.  mag and status are nullable.
+ *
+ * Refused with TRPL_ERR_ARG before a device is touched, the message naming the argument: a NULL Y, Wq, q, rule, out, plI or
+ * W; ncols < 1, n < 1, ldy < n; K outside 1 .. TRPL_Q_MAX; a q outside (0, 1) or NaN; an unknown rule or flag; elem_bytes
+ * other than 4 or 8; rows < 1, ncol < 1, ld < ncol; row0 < 0 or row0 + rows > ldy.
+ * The _dev calls take device pointers (q and rule excepted), allocate nothing and never synchronise.
+ * trpl_weighted_quantiles is the host-buffer form; seconds (nullable) is the time of the selection on the device.
+ * Python: trpl_amd.posterior.quantiles / credible_intervals, trpl_amd.predictive.band_quantiles /
+ * posterior_predictive(quantiles=...), trpl_amd.device.weighted_quantiles_device / predictive_gather_device.
+ * ------------------------------------------------------------------------------------- */
+#define TRPL_Q_MAX 8
+#define TRPL_Q_BLOCK 256
+#define TRPL_Q_FIRST_ABOVE 1
+#define TRPL_Q_LAST_BELOW 2
+#define TRPL_Q_FORCE_STREAM 0x1
+int64_t trpl_quantiles_stage_rows(void);
+int trpl_weighted_quantiles_dev(const double *Y, int64_t ncols, int64_t n, int64_t ldy, const double *Wq, const double *q,
+                                const int32_t *rule, int32_t K, uint32_t flags, double *out /* [K][ncols] */, void *stream);
+int trpl_weighted_quantiles(const double *Y, int64_t ncols, int64_t n, int64_t ldy, const double *Wq, const double *q,
+                            const int32_t *rule, int32_t K, uint32_t flags, double *out, int32_t device, double *seconds);
+int trpl_predictive_gather_dev(const void *plI, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld, const double *mag,
+                               const double *W, const int32_t *status, uint32_t flags, double *Y, int64_t ldy, int64_t row0,
+                               double *Wq, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the
  * measurement plan): S independent systems  ld[i] x[i-1] + d[i] x[i] + ud[i] x[i+1] = b[i],
  * i < L, the problem pcreduce solves (pvSimPCR.py:42-81), operands and result in HBM, arrays

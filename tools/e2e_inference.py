@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -9,6 +9,8 @@ without it the output is unchanged.
 samples with a weight > 0 are re-solved and reduced on the device) as "predictive" -- mean, sqrt(var), lo, hi of log10 PL per
 time column, the number of samples used, and the rms distance of the mean to the synthetic observations in units of
 sqrt(var) -- and seconds["predictive"]; without it the output is unchanged.
+--quantiles (with --predictive) adds the 2.5 % / 50 % / 97.5 % weighted quantiles of log10 PL per time column ("q2.5", "median",
+"q97.5") and "inside_band", the share of the synthetic observations that lie inside [q2.5, q97.5].
 """
 import json
 import sys
@@ -17,7 +19,8 @@ import time
 sys.path.insert(0, ".")
 FIND_TF = "--find-tf" in sys.argv
 PREDICTIVE = "--predictive" in sys.argv
-sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive")]
+QUANTILES = "--quantiles" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles")]
 import numpy as np
 import torch
 import trpl_amd
@@ -99,7 +102,8 @@ if FIND_TF:
 if PREDICTIVE:
     from trpl_amd import predictive
     t7 = sync()
-    bands = predictive.posterior_predictive(X.cpu().numpy(), W.cpu().numpy(), ini, [list(lens), T * dt, L, T, 1])
+    bands = predictive.posterior_predictive(X.cpu().numpy(), W.cpu().numpy(), ini, [list(lens), T * dt, L, T, 1],
+                                            quantiles=(0.025, 0.5, 0.975) if QUANTILES else None)
     out["seconds"]["predictive"] = sync() - t7
     obs_h = obs.cpu().numpy()
     out["predictive"] = []
@@ -112,4 +116,10 @@ if PREDICTIVE:
                                   "rms_distance_in_sigma": float(np.sqrt(np.mean(z * z))) if z.size else None,
                                   "times": b["times"].tolist(), "mean": b["mean"].tolist(), "std": sd.tolist(),
                                   "lo": b["lo"].tolist(), "hi": b["hi"].tolist()})
+        if QUANTILES:
+            lo_q, med, hi_q = b["quantile"]
+            with np.errstate(invalid="ignore"):
+                inside = (obs_h[c] >= lo_q) & (obs_h[c] <= hi_q)
+            out["predictive"][-1].update({"q2.5": lo_q.tolist(), "median": med.tolist(), "q97.5": hi_q.tolist(),
+                                          "inside_band": float(np.mean(inside))})
 print(json.dumps(out))

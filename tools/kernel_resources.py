@@ -4,7 +4,8 @@
                                        moments_fast moments_strict moments_pair moments_predict_fast
                                        moments_predict_strict moments_predict_pair weighted_fast weighted_strict
                                        weighted_pair weighted_predict_fast weighted_predict_strict weighted_predict_pair
-                                       cut_fast cut_pair cut_predict_fast cut_predict_pair posterior posterior_scan predictive]
+                                       cut_fast cut_pair cut_predict_fast cut_predict_pair posterior posterior_scan predictive
+                                       quantiles]
 (cross-compiles, no GPU needed; a name is an object of the library without its stepper_ prefix: csrc/<name>.hip or
 csrc/stepper_<name>.hip where that file exists, otherwise a variant of csrc/stepper_variants.hpp -- [sink_][predict_]unit --
 which is stepper_[pair_]variant.hip with the switch of each of its words, as the Makefile compiles it)"""
