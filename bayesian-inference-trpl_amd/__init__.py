@@ -14,9 +14,10 @@ from .dataio import export, get_data, get_initpoints  # noqa: F401
 from .driver import almost_equal, bayes, bracket_times, interp_rows, is_grid_prefix, loglik, simulate  # noqa: F401
 from .likelihood import fastlog, prob  # noqa: F401
 from .model import checkpoint_steps, pvSim, solve_pl  # noqa: F401
+from .posterior import CORNER_COLUMNS, corner  # noqa: F401
 from .predictive import posterior_predictive  # noqa: F401
 from .sampler import (DEFAULT_DO_LOG, DEFAULT_MAXX, DEFAULT_MINX, PARAM_NAMES, UNIT_CONVERSIONS,  # noqa: F401
                       default_box, make_grid, random_grid)
 
 __all__ = ["pvSim", "solve_pl", "checkpoint_steps", "fastlog", "prob", "simulate", "bayes", "loglik", "random_grid", "make_grid",
-           "posterior_predictive", "TrplError"]
+           "posterior_predictive", "corner", "TrplError"]

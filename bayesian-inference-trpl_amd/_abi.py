@@ -70,6 +70,10 @@ TF_SCAN_MAX = 64              # TRPL_TF_SCAN_MAX: temperatures of one trpl_poste
 Q_MAX, Q_BLOCK = 8, 256       # TRPL_Q_MAX: requests of one trpl_weighted_quantiles; TRPL_Q_BLOCK: threads that sum one column
 Q_FIRST_ABOVE, Q_LAST_BELOW = 1, 2      # TRPL_Q_FIRST_ABOVE / TRPL_Q_LAST_BELOW: the two selection rules
 Q_FORCE_STREAM = 0x1          # TRPL_Q_FORCE_STREAM (tests): the streamed kernel at any column length
+# trpl_corner*: the primary columns of X, all column codes, the largest bin count; TRPL_COL_* in the order of the codes
+CORNER_PRIMARY, CORNER_MAX_COLS, CORNER_MAX_BINS = 13, 19, 128
+(COL_N0, COL_P0, COL_MU_N, COL_MU_P, COL_B, COL_SF, COL_SB, COL_CN, COL_CP, COL_TAU_N, COL_TAU_P, COL_LAMBDA, COL_MAG,
+ COL_TAU_EFF, COL_TAU_RAD, COL_S_SUM, COL_MU_EFF, COL_EPSILON, COL_TAU_SUM) = range(19)
 
 
 class TrplError(RuntimeError):
@@ -178,6 +182,11 @@ SIGNATURES = {
     "trpl_weighted_quantiles_dev": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _u32, _vp, _vp],
     "trpl_weighted_quantiles": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _u32, _vp, _i32, _pd],
     "trpl_predictive_gather_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _u32, _vp, _i64, _i64, _vp, _vp],
+    "trpl_corner_workspace_bytes": [_i64, _i32],
+    "trpl_corner_columns_dev": [_vp, _i64, _i64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "trpl_corner_hist_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "trpl_corner": [_vp, _i64, _i64, _vp, _f64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                    _i32, _pd],
     "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
     "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
 }
@@ -307,7 +316,7 @@ def lib():
             fn.restype = C.c_char_p if name == "trpl_last_error" else (
                 C.c_int64 if name in ("trpl_posterior_workspace_bytes", "trpl_posterior_tf_scan_workspace", "trpl_shard_of",
                                      "trpl_predictive_state_bytes", "trpl_predictive_workspace_bytes",
-                                     "trpl_quantiles_stage_rows") else C.c_int)
+                                     "trpl_quantiles_stage_rows", "trpl_corner_workspace_bytes") else C.c_int)
         _lib = dll
     return _lib
 

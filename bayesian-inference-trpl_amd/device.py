@@ -401,6 +401,62 @@ def posterior_hist_device(x, W, lo, hi, out, y=None, ylo=0.0, yhi=1.0):
         float(yhi), int(yb), _chk(out, torch.float64, "out"), _stream()))
 
 
+# ---- the corner, device-resident (trpl_corner_*_dev) ----
+def corner_workspace(S, D):
+    """A workspace tensor for corner_hist_device with S samples and D columns (one key byte per sample and column)."""
+    import torch
+    n = int(_abi.lib().trpl_corner_workspace_bytes(int(S), int(D)))
+    if n <= 0:
+        raise ValueError("S, D = %r are outside what trpl_corner_hist_dev accepts" % ((S, D),))
+    return torch.empty(n, dtype=torch.uint8, device="cuda")
+
+
+def corner_columns_device(X, cols, V, do_log=None, thickness=2000.0, excl_lo=None, excl_hi=None, LL=None, LLk=None, kept=None):
+    """V (D, S) <- the columns `cols` (TRPL_COL_* codes, host sequence) of the samples X (S, ld >= 13) f64, log10 where
+    do_log[d]; excl_lo / excl_hi (host, 13 each, NaN = not tested): LLk (S,) <- LL for a kept sample, NaN otherwise, and kept
+    (1,) int64 <- their number (trpl_corner_columns_dev)."""
+    import torch
+    cols = np.ascontiguousarray(cols, dtype=np.int32)
+    lg = np.zeros(cols.size, dtype=np.int32) if do_log is None else np.ascontiguousarray(do_log, dtype=np.int32)
+    if X.dim() != 2 or cols.ndim != 1 or lg.shape != cols.shape or tuple(V.shape) != (cols.size, X.shape[0]):
+        raise ValueError("X must be (S, ld), V (D, S) with D = len(cols) = len(do_log)")
+    S, ldx = X.shape
+    lo = None if excl_lo is None else np.ascontiguousarray(excl_lo, dtype=np.float64)
+    hi = None if excl_hi is None else np.ascontiguousarray(excl_hi, dtype=np.float64)
+    for a in (lo, hi):
+        if a is not None and a.shape != (_abi.CORNER_PRIMARY,):
+            raise ValueError("excl_lo and excl_hi must have %d entries" % _abi.CORNER_PRIMARY)
+    for t, name in ((LL, "LL"), (LLk, "LLk")):
+        if t is not None and tuple(t.shape) != (S,):
+            raise ValueError("%s must be (S,)" % name)
+    _abi.check(_abi.lib().trpl_corner_columns_dev(
+        _chk(X, torch.float64, "X"), S, ldx, _abi.ptr(cols), _abi.ptr(lg), cols.size, float(thickness), _abi.ptr(lo), _abi.ptr(hi),
+        None if LL is None else _chk(LL, torch.float64, "LL"), _chk(V, torch.float64, "V"),
+        None if LLk is None else _chk(LLk, torch.float64, "LLk"), None if kept is None else _chk(kept, torch.int64, "kept"),
+        _stream()))
+
+
+def corner_hist_device(V, W, lo, hi, h1, workspace, c1=None, h2=None):
+    """Every marginal of the columns V (D, S) under the weights W (S,): h1 (D, bins) weighted sums, c1 (D, bins) plain counts,
+    h2 (D (D - 1) / 2, bins, bins) in the reference's pair order; lo, hi host sequences of D limits.  Each bin is the sum of
+    its samples' weights in ascending sample index: the same bits in every run (trpl_corner_hist_dev)."""
+    import torch
+    D, S = V.shape
+    bins = h1.shape[1] if h1.dim() == 2 else -1
+    lo = np.ascontiguousarray(lo, dtype=np.float64)
+    hi = np.ascontiguousarray(hi, dtype=np.float64)
+    if tuple(W.shape) != (S,) or lo.shape != (D,) or hi.shape != (D,) or tuple(h1.shape) != (D, bins) \
+            or (c1 is not None and tuple(c1.shape) != (D, bins)) \
+            or (h2 is not None and tuple(h2.shape) != (D * (D - 1) // 2, bins, bins)):
+        raise ValueError("shape mismatch")
+    if workspace.numel() * workspace.element_size() < int(_abi.lib().trpl_corner_workspace_bytes(S, D)):
+        raise ValueError("workspace too small: see corner_workspace")
+    _abi.check(_abi.lib().trpl_corner_hist_dev(
+        _chk(V, torch.float64, "V"), S, S, D, _chk(W, torch.float64, "W"), _abi.ptr(lo), _abi.ptr(hi), int(bins),
+        _chk(h1, torch.float64, "h1"), None if c1 is None else _chk(c1, torch.float64, "c1"),
+        None if h2 is None or h2.numel() == 0 else _chk(h2, torch.float64, "h2"), _chk(workspace, workspace.dtype, "workspace"), _stream()))
+
+
 def credible_interval_device(x, W, lo=0.025, hi=0.975):
     """utils.py:185-196 on the device: sort by x, cumulate the weights, last point below `lo` and first
     above `hi` (torch.sort / cumsum: library plumbing, no custom kernel)."""

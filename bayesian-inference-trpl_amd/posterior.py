@@ -364,3 +364,140 @@ def calc_max_uncertainty(columns, LL, num_observations, device=0, span=1e4, rtol
         info.update(scans=inf["scans"], device_scans=inf["device_scans"], lo=dict(zip(names, inf["lo"].tolist())),
                     hi=dict(zip(names, inf["hi"].tolist())), at_edge=dict(zip(names, inf["at_edge"].tolist())))
     return {n: (float(tf[i]), float(q[i])) for i, n in enumerate(names)}
+
+
+# ---- the corner: every marginal of a finished run in one device call (trpl_corner, csrc/corner.hip) ----
+# the 13 columns of the exported X under the package's names (sampler.PARAM_NAMES; marginalization_visual.py:67-70 lists them
+# in this order) and the six secondary parameters of the same list, :69-70; the position is the TRPL_COL_* code
+CORNER_COLUMNS = ("n0", "p0", "mun", "mup", "B", "Sf", "Sb", "CN", "CP", "taun", "taup", "lambda", "mag_offset",
+                  "tau_eff", "tau_rad", "Sf+Sb", "mu'", "epsilon", "taun+taup")
+
+
+def _corner_codes(enabled, do_log):
+    enabled = list(enabled)
+    unknown = [n for n in list(enabled) + list(do_log) if n not in CORNER_COLUMNS]
+    if unknown:
+        raise ValueError("unknown column name(s) %r: CORNER_COLUMNS lists the names" % (unknown,))
+    if len(set(enabled)) != len(enabled):
+        raise ValueError("a column is enabled twice")
+    cols = np.array([CORNER_COLUMNS.index(n) for n in enabled], dtype=np.int32)
+    lg = np.array([1 if n in do_log else 0 for n in enabled], dtype=np.int32)
+    return enabled, cols, lg
+
+
+def _exclusion(exclude_limits):
+    """name -> (lo, hi) on the RAW values of primary columns -> the two host arrays of trpl_corner_columns_dev (NaN: not tested)."""
+    if exclude_limits is None:
+        return None, None
+    lo, hi = np.full(_abi.CORNER_PRIMARY, np.nan), np.full(_abi.CORNER_PRIMARY, np.nan)
+    for name, (a, b) in exclude_limits.items():
+        c = CORNER_COLUMNS.index(name) if name in CORNER_COLUMNS else _abi.CORNER_MAX_COLS
+        if c >= _abi.CORNER_PRIMARY:
+            raise ValueError("exclusion limits apply to the 13 primary columns, not to %r" % (name,))
+        if a != a or b != b:
+            raise ValueError("exclusion limits of %r must not be NaN" % (name,))
+        lo[c], hi[c] = a, b
+    return lo, hi
+
+
+def columns(X, enabled, thickness=2000.0, do_log=(), exclude_limits=None, LL=None, device=0):
+    """The plotted columns of a finished run, formed on the device: X (S, 13) in the user's units (*_BAYRAN_X.npy), `enabled` a
+    sequence of CORNER_COLUMNS names -- primary columns and the secondary parameters of secondary_parameters.py -- log10 taken of
+    those in do_log.  Returns V (D, S), the layout moments, quantiles, tf_scan, summarize, credible_intervals and
+    calc_max_uncertainty take.  With LL, returns (V, LLk, kept): LLk is LL with NaN at the samples outside exclude_limits
+    (name -> (lo, hi) on the raw values of primary columns, utils.py:145-155), kept the number of samples left by filter_nan and
+    the exclusion together; weights(LLk, tf) then normalises over the kept samples only.
+    Cost: this is the host-buffer call trpl_corner with one bin per axis, so besides the columns kernel it uploads X, runs the
+    weights on a flat likelihood (their NaNs are LLk's) and D one-bin histograms that each walk the S samples, and copies V back;
+    the upload and the copy dominate.  Tensors already on the device go through device.corner_columns_device, which runs
+    the columns kernel alone."""
+    X = _f64(X)
+    if X.ndim != 2 or X.shape[1] < _abi.CORNER_PRIMARY:
+        raise ValueError("X must be (S, 13)")
+    enabled, cols, lg = _corner_codes(enabled, do_log)
+    S, D = X.shape[0], cols.size
+    if LL is None:
+        if exclude_limits is not None:
+            raise ValueError("exclude_limits needs LL: the exclusion is returned as NaN in LLk")
+        LL_in = np.zeros(S)
+    else:
+        LL_in = _f64(LL)
+        if LL_in.shape != (S,):
+            raise ValueError("LL must have one entry per sample")
+    lo, hi = _exclusion(exclude_limits)
+    # the columns alone: trpl_corner with one bin per axis over [0, 1] (its histograms are ignored)
+    V, W = np.empty((D, S)), np.empty(S)
+    kept = np.zeros(1, dtype=np.int64)
+    h1, alo, ahi = np.zeros((D, 1)), np.zeros(D), np.ones(D)
+    flat = np.where(np.isnan(LL_in), np.nan, 0.0)                # equal likelihoods: every kept sample gets a finite weight
+    _abi.check(_abi.lib().trpl_corner(_abi.ptr(X), S, X.shape[1], _abi.ptr(flat), 1.0, _abi.ptr(cols), _abi.ptr(lg), D, float(thickness),
+                                      _abi.ptr(lo), _abi.ptr(hi), _abi.ptr(alo), _abi.ptr(ahi), 1, _abi.ptr(V), _abi.ptr(W),
+                                      _abi.ptr(kept), _abi.ptr(h1), None, None, int(device), None))
+    if LL is None:
+        return V
+    LLk = np.where(np.isnan(W), np.nan, LL_in)                   # W is NaN exactly where LLk is
+    return V, LLk, int(kept[0])
+
+
+def corner(X, LL, enabled, axis_limits, bin_count=96, tf=1.0, thickness=2000.0, do_log=(), exclude=False, secondary=None, device=0,
+           info=None):
+    """plot() of marginalization_visual.py:500-609 up to the drawing, in one device call (trpl_corner): exclusion by the axis
+    limits, secondary parameters, log10, tempered weights, and the 1-D marginal of every enabled column and the 2-D marginal of
+    every pair, each bin summed in ascending sample order (the same bits in every run).
+
+    X (S, 13) in the user's units, LL (S,) log-likelihoods (NaN: dropped, like filter_nan), enabled: CORNER_COLUMNS names in
+    plotting order, axis_limits: name -> (lo, hi) in PLOTTED units, i.e. after log10 for the names in do_log, as marginalize_1D /
+    marginalize_2D receive them from loglimits() (plotutils.py:56-59).  exclude=True drops the samples outside the limits of the
+    enabled PRIMARY columns, compared on the raw values as the reference does (utils.py:48-52): fromTK_get_axis_limits
+    (plotutils.py:19-23) holds the raw limits and loglimits() (plotutils.py:56-59) turns them into log10 afterwards, so a
+    log-scaled column's raw limits are 10 ** limit here.  secondary: name -> bool, which columns get the correction for
+    non-uniform sampling besides the names containing "mu" (default: the six secondary parameters, SECONDARY_PARAMS :72-75).
+    Returns {"h_1D": {name: (density, edges)}, "h_2D": {(px, py): (density, X_corr, Y_corr)}, "W", "kept", "V"} with the
+    densities formed on the host from the raw sums by the arithmetic of marginalize_1D / marginalize_2D above."""
+    X, LL = _f64(X), _f64(LL)
+    if X.ndim != 2 or X.shape[1] < _abi.CORNER_PRIMARY or LL.shape != (X.shape[0],):
+        raise ValueError("X must be (S, 13) and LL (S,)")
+    enabled, cols, lg = _corner_codes(enabled, do_log)
+    S, D, bins = X.shape[0], cols.size, int(bin_count)
+    if secondary is None:
+        secondary = {n: CORNER_COLUMNS.index(n) >= _abi.CORNER_PRIMARY for n in enabled}
+    lo = np.array([axis_limits[n][0] for n in enabled], dtype=np.float64)
+    hi = np.array([axis_limits[n][1] for n in enabled], dtype=np.float64)
+    excl = None
+    if exclude:
+        excl = {n: (10.0 ** lo[d], 10.0 ** hi[d]) if lg[d] else (lo[d], hi[d])
+                for d, n in enumerate(enabled) if cols[d] < _abi.CORNER_PRIMARY}
+    elo, ehi = _exclusion(excl)
+    if not 1 <= bins <= _abi.CORNER_MAX_BINS:
+        raise ValueError("bin_count must be in [1, %d]" % _abi.CORNER_MAX_BINS)
+    npair = D * (D - 1) // 2
+    V, W = np.empty((D, S)), np.empty(S)
+    kept = np.zeros(1, dtype=np.int64)
+    h1, c1, h2 = np.zeros((D, bins)), np.zeros((D, bins)), np.zeros((npair, bins, bins))
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_corner(_abi.ptr(X), S, X.shape[1], _abi.ptr(LL), float(tf), _abi.ptr(cols), _abi.ptr(lg), D,
+                                      float(thickness), _abi.ptr(elo), _abi.ptr(ehi), _abi.ptr(lo), _abi.ptr(hi), bins, _abi.ptr(V),
+                                      _abi.ptr(W), _abi.ptr(kept), _abi.ptr(h1), _abi.ptr(c1), _abi.ptr(h2) if npair else None,
+                                      int(device), _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value, h1=h1, c1=c1, h2=h2)
+    edges = [bin_edges(lo[d], hi[d], bins) for d in range(D)]
+    h_1D, h_2D = {}, {}
+    for d, n in enumerate(enabled):
+        e, raw = edges[d], h1[d]
+        marP = raw / (np.diff(e) * raw.sum())                              # numpy's density=True, as in marginalize_1D
+        if secondary.get(n, False) or "mu" in n:
+            corr = np.zeros_like(marP)
+            nz = c1[d] != 0
+            corr[nz] = marP[nz] / c1[d][nz]
+            marP = corr / np.sum(np.diff(e) * corr)
+        h_1D[n] = (marP, e)
+    p = 0
+    for i in range(1, D):                                                  # utils.py:103-106
+        for j in range(i):
+            raw = h2[p]
+            dens = raw / (np.outer(np.diff(edges[j]), np.diff(edges[i])) * raw.sum())
+            Y_corr, X_corr = np.meshgrid(edges[j], edges[i])               # :282, as the reference names them
+            h_2D[(enabled[j], enabled[i])] = (dens, X_corr, Y_corr)
+            p += 1
+    return {"h_1D": h_1D, "h_2D": h_2D, "W": W, "kept": int(kept[0]), "V": V}

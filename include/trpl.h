@@ -912,6 +912,99 @@ int trpl_predictive_gather_dev(const void *plI, int32_t elem_bytes, int64_t rows
                                double *Wq, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_corner* -- the corner: every posterior marginal of a finished run in one device call.  What plot() of
+ * Visualization/marginalization_visual.py:500-609 does after loading a run: drop the samples outside the axis limits
+ * (utils.py:48-52, :145-155), add the secondary parameters (utils.py:54-79, secondary_parameters.py), take log10 of the
+ * log-scaled columns, temper and normalise, fill one 1-D histogram per enabled parameter and one 2-D histogram per pair
+ * (utils.py:91-117, :239-285 -- the reference's only process pool).  (csrc/corner.hip)
+ *
+ * Column codes.  0 .. 12 are the 13 columns of the exported X (*_BAYRAN_X.npy, the user's units) in the reference's PARAM_ORDER
+ * (marginalization_visual.py:67-70); 13 .. 18 the six secondary parameters in that list's order.
+ *
+ * trpl_corner_columns_dev: one pass over the samples, each X row (S rows of ldx >= 13 doubles) read once.  V[d][s] (V is [D][S],
+ * the layout trpl_posterior_moments and trpl_weighted_quantiles take) is the value of cols[d], its log10 where dolog[d] != 0.
+ * cols and dolog are HOST arrays.  Secondary columns follow secondary_parameters.py:9-57, evaluated left to right in IEEE fp64
+ * with x**-1 = 1.0 / x and p0**2 = p0 * p0 (what NumPy does for those exponents):
+ *     tau_rad = 1 / (B p0) * 1e9;  t_aug = 1 / (Cp p0^2) * 1e9;  mu' = 2 / (1 / mu_n + 1 / mu_p);
+ *     Dif = mu' * 0.0257 / 1 * 1e14 / 1e9;  tau_surf = thickness / ((Sf + Sb) * 0.01) + thickness^2 / (pi^2 Dif);
+ *     tau_eff = 1 / (1 / tau_rad + 1 / t_aug + 1 / tau_surf + 1 / tau_n);  S_F+S_B, epsilon = 1 / lambda, tau_n + tau_p.
+ * The reference's own CALL of LI_tau_eff is broken: utils.py:61-62 passes seven arguments to a function of eight and leaves out
+ * CP.  This is the function as DEFINED (secondary_parameters.py:17-30), with CP = X[:, 8].
+ * Exclusion (excl_lo, excl_hi: HOST arrays of 13, both or neither).  Sample s is kept iff for every primary column c with a
+ * non-NaN excl_lo[c]:  excl_lo[c] <= X[s][c] <= excl_hi[c], on the RAW value -- a NaN value excludes the sample, as in
+ * utils.py:149-150; a NaN excl_lo[c] means column c is not tested.  LLk[s] (nullable; needs LL) = LL[s] for a kept sample, else
+ * NaN: filter_nan's marker, which trpl_posterior_weights_dev passes through, so trpl_posterior_weights_dev(LLk) normalises over
+ * the kept samples only (the reference excludes first, :520-523, and normalises afterwards, :589-591).  V is written for
+ * every sample.  kept (nullable, device int64) receives the number of samples that pass the exclusion and whose LL (when
+ * given) is not NaN: the reference's "Kept" after filter_nan and exclude.
+ *
+ * trpl_corner_hist_dev: V [D][ldv >= S], weights W[S], limits lo[D], hi[D] (HOST arrays), `bins` <= TRPL_CORNER_MAX_BINS equal
+ * bins per axis (128^2 fp64 bins are 128 KiB of the 160 KiB one workgroup may declare on gfx950; the GUI's default is 96).
+ * Outputs: h1[D][bins] weighted sums, c1[D][bins] (nullable) plain counts as doubles, h2[D (D - 1) / 2][bins][bins] (nullable)
+ * with pair p in the reference's order (utils.py:103-106): for i = 1 .. D-1, for j = 0 .. i-1: x = column j, y = column i,
+ * h2[p][x bin][y bin].  Every element is written (no zeroing by the caller).  Bins follow trpl_posterior_hist's rules: edges
+ * lo + (hi - lo) * k / bins exactly as the reference builds them, left-closed, the last closed on the right -- at the COMPUTED
+ * last edge, not hi --, outside and NaN dropped.  A sample enters the weighted sums iff its weight is finite and > 0
+ * (trpl_weighted_quantiles' rule) and the plain counts iff its weight is not NaN (it survived filter_nan and the exclusion):
+ * c1 is what marginalize_1D divides by for secondary parameters and mobilities (:248-257).
+ * ORDER, and therefore bits: every weighted bin is the fp64 sum of its samples' weights added ONE AT A TIME IN ASCENDING SAMPLE
+ * INDEX, starting from +0.0 -- numpy.add.at(out, key, w) on the host.  A pure function of the inputs: it does not depend on the
+ * grid, the device or the run.  No floating-point atomics.  (trpl_posterior_hist's sums are fp64 atomics in no fixed order.)
+ * workspace: trpl_corner_workspace_bytes(S, D) bytes of device memory (one key byte per sample and column; 0 for refused S, D).
+ *
+ * trpl_corner is the host-buffer form: stages X and LL, runs the columns, trpl_posterior_weights_dev on LLk at temperature tf,
+ * then the histograms.  Returns V [D][S] (nullable), W [S] (nullable), kept (nullable), h1, c1 (nullable), h2 (nullable);
+ * seconds (nullable) is the time of the three steps on the device.
+ * W is trpl_posterior_weights_dev of the MARKED full-length vector, bit for bit.  Against dropping the samples first and normalising
+ * the kept ones (the reference's order) it is the same number, not the same bits: the weight's exponent is lifted by ln S of the
+ * full length instead of ln kept, so exp sees another argument, and the normalising sum groups its terms by another grid; both
+ * lie within 16 ulp of an extended-precision evaluation at S <= 2048.
+ *
+ * Refused with TRPL_ERR_ARG before a device is touched, the message naming the argument: S < 0; D outside
+ * [1, TRPL_CORNER_MAX_COLS]; a column code outside [0, 18]; bins outside [1, TRPL_CORNER_MAX_BINS]; a lo or hi that is not finite,
+ * or hi <= lo; thickness_nm not finite and > 0 while tau_eff is requested; only one of excl_lo / excl_hi; a NaN excl_hi[c]
+ * beside a non-NaN excl_lo[c] (it would exclude every sample; excl_hi[c] of an untested column is ignored); ldx < 13; ldv < S; a
+ * NULL h1, cols, dolog, lo, hi, V, or (S > 0) X, W, workspace; LLk without LL; tf that is not > 0.  S == 0 succeeds and writes
+ * zeros.  The _dev calls take device pointers (the host arrays named above excepted), allocate nothing and never synchronise.
+ * Python: trpl_amd.posterior.columns / corner / CORNER_COLUMNS, trpl_amd.device.corner_columns_device / corner_hist_device /
+ * corner_workspace.
+ * ------------------------------------------------------------------------------------- */
+#define TRPL_CORNER_PRIMARY 13
+#define TRPL_CORNER_MAX_COLS 19
+#define TRPL_CORNER_MAX_BINS 128
+#define TRPL_COL_N0 0
+#define TRPL_COL_P0 1
+#define TRPL_COL_MU_N 2
+#define TRPL_COL_MU_P 3
+#define TRPL_COL_B 4
+#define TRPL_COL_SF 5
+#define TRPL_COL_SB 6
+#define TRPL_COL_CN 7
+#define TRPL_COL_CP 8
+#define TRPL_COL_TAU_N 9
+#define TRPL_COL_TAU_P 10
+#define TRPL_COL_LAMBDA 11
+#define TRPL_COL_MAG 12
+#define TRPL_COL_TAU_EFF 13
+#define TRPL_COL_TAU_RAD 14
+#define TRPL_COL_S_SUM 15
+#define TRPL_COL_MU_EFF 16
+#define TRPL_COL_EPSILON 17
+#define TRPL_COL_TAU_SUM 18
+int64_t trpl_corner_workspace_bytes(int64_t S, int32_t D);
+int trpl_corner_columns_dev(const double *X, int64_t S, int64_t ldx, const int32_t *cols /*host [D]*/, const int32_t *dolog /*host [D]*/,
+                            int32_t D, double thickness_nm, const double *excl_lo /*host [13], nullable*/,
+                            const double *excl_hi /*host [13], nullable*/, const double *LL /*nullable*/, double *V /* [D][S] */,
+                            double *LLk /*nullable*/, int64_t *kept /*nullable, device*/, void *stream);
+int trpl_corner_hist_dev(const double *V, int64_t S, int64_t ldv, int32_t D, const double *W, const double *lo /*host [D]*/,
+                         const double *hi /*host [D]*/, int32_t bins, double *h1 /* [D][bins] */, double *c1 /*nullable*/,
+                         double *h2 /*nullable: [D (D - 1) / 2][bins][bins]*/, void *workspace, void *stream);
+int trpl_corner(const double *X, int64_t S, int64_t ldx, const double *LL, double tf, const int32_t *cols, const int32_t *dolog,
+                int32_t D, double thickness_nm, const double *excl_lo, const double *excl_hi, const double *lo, const double *hi,
+                int32_t bins, double *V, double *W, int64_t *kept, double *h1, double *c1, double *h2, int32_t device,
+                double *seconds);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the
  * measurement plan): S independent systems  ld[i] x[i-1] + d[i] x[i] + ud[i] x[i+1] = b[i],
  * i < L, the problem pcreduce solves (pvSimPCR.py:42-81), operands and result in HBM, arrays

@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -11,6 +11,10 @@ time column, the number of samples used, and the rms distance of the mean to the
 sqrt(var) -- and seconds["predictive"]; without it the output is unchanged.
 --quantiles (with --predictive) adds the 2.5 % / 50 % / 97.5 % weighted quantiles of log10 PL per time column ("q2.5", "median",
 "q97.5") and "inside_band", the share of the synthetic observations that lie inside [q2.5, q97.5].
+--corner adds, at the end, the corner of the run (posterior.corner: the ten free parameters and five secondary ones -- tau_eff,
+tau_rad, Sf+Sb, mu', taun+taup; epsilon = 1 / lambda is one number in this box, which fixes lambda -- 96 bins,
+limits = the sampled box, every 1-D and 2-D marginal in one device call) as "corner": kept, the device seconds, and the mode of
+every 1-D marginal -- and seconds["corner"], the call with its copies; without it the output is unchanged.
 """
 import json
 import sys
@@ -20,7 +24,8 @@ sys.path.insert(0, ".")
 FIND_TF = "--find-tf" in sys.argv
 PREDICTIVE = "--predictive" in sys.argv
 QUANTILES = "--quantiles" in sys.argv
-sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles")]
+CORNER = "--corner" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner")]
 import numpy as np
 import torch
 import trpl_amd
@@ -122,4 +127,22 @@ if PREDICTIVE:
                 inside = (obs_h[c] >= lo_q) & (obs_h[c] <= hi_q)
             out["predictive"][-1].update({"q2.5": lo_q.tolist(), "median": med.tolist(), "q97.5": hi_q.tolist(),
                                           "inside_band": float(np.mean(inside))})
+if CORNER:
+    from trpl_amd import posterior
+    t8 = sync()
+    Xu, LLh = Xc.cpu().numpy(), P.cpu().numpy()
+    enabled = names + ["tau_eff", "tau_rad", "Sf+Sb", "mu'", "taun+taup"]
+    logged = [n for n, i in zip(names, cols) if lg[i]] + ["tau_eff", "tau_rad"]
+    Vh = posterior.columns(Xu, enabled, thickness=float(lens[0]), do_log=logged)
+    fin = np.where(np.isfinite(Vh), Vh, np.nan)
+    limits = {n: (float(np.nanmin(fin[d])), float(np.nanmax(fin[d]))) for d, n in enumerate(enabled)}   # plotutils.py:25-33
+    limits = {n: (a, b) if b > a else (a - 1.0, b + 1.0) for n, (a, b) in limits.items()}
+    cinfo = {}
+    cr = posterior.corner(Xu, LLh, enabled, limits, bin_count=96, tf=n_obs * c_val, thickness=float(lens[0]), do_log=logged, info=cinfo)
+    out["seconds"]["corner"] = sync() - t8
+    out["corner"] = {"kept": cr["kept"], "columns": len(enabled), "histograms": len(cr["h_1D"]) + len(cr["h_2D"]),
+                     "device_seconds": cinfo["seconds"],
+                     "mode": {n: float(0.5 * (e[int(np.argmax(d))] + e[int(np.argmax(d)) + 1])) for n, (d, e) in cr["h_1D"].items()}}
+    print("corner: kept %d of %d, %d histograms in %.3f ms on the device" % (cr["kept"], S, out["corner"]["histograms"],
+                                                                           1e3 * cinfo["seconds"]), file=sys.stderr)
 print(json.dumps(out))
