@@ -74,6 +74,7 @@ Q_FORCE_STREAM = 0x1          # TRPL_Q_FORCE_STREAM (tests): the streamed kernel
 CORNER_PRIMARY, CORNER_MAX_COLS, CORNER_MAX_BINS = 13, 19, 128
 (COL_N0, COL_P0, COL_MU_N, COL_MU_P, COL_B, COL_SF, COL_SB, COL_CN, COL_CP, COL_TAU_N, COL_TAU_P, COL_LAMBDA, COL_MAG,
  COL_TAU_EFF, COL_TAU_RAD, COL_S_SUM, COL_MU_EFF, COL_EPSILON, COL_TAU_SUM) = range(19)
+REFINE_MAX_DIMS, REFINE_MAX_PARENTS = 16, 1 << 20      # TRPL_REFINE_MAX_DIMS, TRPL_REFINE_MAX_PARENTS
 
 
 class TrplError(RuntimeError):
@@ -83,6 +84,7 @@ class TrplError(RuntimeError):
 
 
 _vp, _i32, _i64, _u32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_double
+_u64 = C.c_uint64
 _pd = C.POINTER(C.c_double)
 
 # name -> argtypes, exactly the prototypes of include/trpl.h
@@ -187,6 +189,17 @@ SIGNATURES = {
     "trpl_corner_hist_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "trpl_corner": [_vp, _i64, _i64, _vp, _f64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                     _i32, _pd],
+    "trpl_refine_chunk_rows": [],
+    "trpl_refine_tile_parents": [],
+    "trpl_refine_workspace_bytes": [_i64],
+    "trpl_refine_resample_dev": [_vp, _i64, _i64, _f64, _vp, _vp, _vp, _i64, _vp],
+    "trpl_refine_resample": [_vp, _i64, _i64, _f64, _vp, _vp, _i32, _pd],
+    "trpl_refine_draw_dev": [_vp, _vp, _i64, _i32, _i64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp],
+    "trpl_refine_draw": [_vp, _vp, _i64, _i32, _i64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _i32, _pd],
+    "trpl_refine_density_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
+    "trpl_refine_density": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _pd],
+    "trpl_refine_unit_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _u32, _i32, _vp, _vp],
+    "trpl_refine_unit": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _u32, _i32, _vp, _i32, _pd],
     "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
     "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
 }
@@ -316,7 +329,8 @@ def lib():
             fn.restype = C.c_char_p if name == "trpl_last_error" else (
                 C.c_int64 if name in ("trpl_posterior_workspace_bytes", "trpl_posterior_tf_scan_workspace", "trpl_shard_of",
                                      "trpl_predictive_state_bytes", "trpl_predictive_workspace_bytes",
-                                     "trpl_quantiles_stage_rows", "trpl_corner_workspace_bytes") else C.c_int)
+                                     "trpl_quantiles_stage_rows", "trpl_corner_workspace_bytes", "trpl_refine_chunk_rows",
+                                     "trpl_refine_tile_parents", "trpl_refine_workspace_bytes") else C.c_int)
         _lib = dll
     return _lib
 

@@ -457,6 +457,80 @@ def corner_hist_device(V, W, lo, hi, h1, workspace, c1=None, h2=None):
         None if h2 is None or h2.numel() == 0 else _chk(h2, torch.float64, "h2"), _chk(workspace, workspace.dtype, "workspace"), _stream()))
 
 
+# ---- refinement generations, device-resident (trpl_refine_*_dev) ----
+def _refine_box(minX, maxX, do_log):
+    lo = np.ascontiguousarray(minX, dtype=np.float64)
+    hi = np.ascontiguousarray(maxX, dtype=np.float64)
+    lg = np.ascontiguousarray(do_log, dtype=np.int32)
+    if not (lo.shape == hi.shape == lg.shape and lo.ndim == 1):
+        raise ValueError("minX, maxX and do_log must be one-dimensional and of equal length")
+    return lo, hi, lg
+
+
+def refine_workspace(S):
+    """A workspace tensor for refine_resample_device over S weights."""
+    import torch
+    n = int(_abi.lib().trpl_refine_workspace_bytes(int(S)))
+    if n <= 0:
+        raise ValueError("S = %r is outside what trpl_refine_resample_dev accepts" % (S,))
+    return torch.empty((n + 7) // 8, dtype=torch.float64, device="cuda")
+
+
+def refine_resample_device(W, idx, workspace, offset=0.5, stats=None):
+    """trpl_refine_resample_dev: idx (K,) int64 <- the K systematic draws of the weights W (S,) f64 (NaN or <= 0 counts as 0;
+    -1 everywhere when no weight is left), stats (3,) f64 optional <- sum w, sum w^2, (sum w)^2 / sum w^2."""
+    import torch
+    if W.dim() != 1 or idx.dim() != 1 or (stats is not None and tuple(stats.shape) != (3,)):
+        raise ValueError("W must be (S,), idx (K,) and stats (3,)")
+    _abi.check(_abi.lib().trpl_refine_resample_dev(
+        _chk(W, torch.float64, "W"), W.shape[0], idx.shape[0], float(offset), _chk(idx, torch.int64, "idx"),
+        None if stats is None else _chk(stats, torch.float64, "stats"), _chk(workspace, torch.float64, "workspace"),
+        workspace.numel() * 8, _stream()))
+
+
+def refine_draw_device(a, b, m, n_uniform, seed, generation, minX, maxX, do_log, U2, X2, flags=0):
+    """trpl_refine_draw_dev: the n_uniform + K m children of the boxes a, b (K, A) f64 -- U2 (S_g, A) unit coordinates, X2
+    (S_g, ncol) the samples in the box's units; minX, maxX, do_log host sequences, flags the TRPL_BOX_EQUAL_* bits."""
+    import torch
+    lo, hi, lg = _refine_box(minX, maxX, do_log)
+    if a.dim() != 2 or a.shape != b.shape:
+        raise ValueError("a and b must be (K, A)")
+    K, A = a.shape
+    total = int(n_uniform) + K * int(m)
+    if tuple(U2.shape) != (total, A) or tuple(X2.shape) != (total, lo.size):
+        raise ValueError("U2 must be (n_uniform + K m, A) and X2 (n_uniform + K m, ncol)")
+    _abi.check(_abi.lib().trpl_refine_draw_dev(
+        _chk(a, torch.float64, "a"), _chk(b, torch.float64, "b"), K, A, int(m), int(n_uniform), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        int(generation) & 0xFFFFFFFF, lo.size, _abi.ptr(lo), _abi.ptr(hi), _abi.ptr(lg), int(flags),
+        _chk(U2, torch.float64, "U2"), _chk(X2, torch.float64, "X2"), _stream()))
+
+
+def refine_density_device(U, a, b, inv_vol, B, A=None):
+    """trpl_refine_density_dev: B (S,) <- the sum of inv_vol (K,) over the closed boxes a, b (K, A) that hold each row of U
+    (S, ldu >= A), in ascending k: the sequential loop's bits."""
+    import torch
+    if U.dim() != 2 or a.dim() != 2 or a.shape != b.shape or tuple(inv_vol.shape) != (a.shape[0],) or tuple(B.shape) != (U.shape[0],):
+        raise ValueError("U must be (S, ldu), a and b (K, A), inv_vol (K,) and B (S,)")
+    K, Ab = a.shape
+    A = Ab if A is None else int(A)
+    if A != Ab:
+        raise ValueError("A must be the boxes' number of dimensions")
+    _abi.check(_abi.lib().trpl_refine_density_dev(
+        _chk(U, torch.float64, "U"), U.shape[0], U.shape[1], A, _chk(a, torch.float64, "a"), _chk(b, torch.float64, "b"),
+        _chk(inv_vol, torch.float64, "inv_vol"), K, _chk(B, torch.float64, "B"), _stream()))
+
+
+def refine_unit_device(X, minX, maxX, do_log, U, flags=0):
+    """trpl_refine_unit_dev: U (S, A) <- the unit coordinates of the active columns of X (S, ld >= ncol)."""
+    import torch
+    lo, hi, lg = _refine_box(minX, maxX, do_log)
+    if X.dim() != 2 or U.dim() != 2 or U.shape[0] != X.shape[0]:
+        raise ValueError("X must be (S, ld) and U (S, A)")
+    _abi.check(_abi.lib().trpl_refine_unit_dev(
+        _chk(X, torch.float64, "X"), X.shape[0], X.shape[1], lo.size, _abi.ptr(lo), _abi.ptr(hi), _abi.ptr(lg), int(flags),
+        U.shape[1], _chk(U, torch.float64, "U"), _stream()))
+
+
 def credible_interval_device(x, W, lo=0.025, hi=0.975):
     """utils.py:185-196 on the device: sort by x, cumulate the weights, last point below `lo` and first
     above `hi` (torch.sort / cumsum: library plumbing, no custom kernel)."""

@@ -1005,6 +1005,84 @@ int trpl_corner(const double *X, int64_t S, int64_t ldx, const double *LL, doubl
                 double *seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_refine_* -- refinement generations: a further generation of samples drawn around the posterior of the ones at hand, and
+ * the exact weights of the union.  (The reference's ancestor refined the cells above minP, Legacy/legacy.py:refineGrid; the
+ * random sampler that replaced it has no refinement.)  (csrc/refine.hip)
+ *
+ * Unit coordinates.  A column of the box (lo, hi, do_log, ncol, flags as trpl_sample_box takes them, HOST arrays) is ACTIVE when
+ * lo != hi and it is not the target of a TRPL_BOX_EQUAL_* override that is set (columns 2, 6, 8); the A <= TRPL_REFINE_MAX_DIMS
+ * active columns, in column order, are the dimensions.  u = (x - lo) / (hi - lo) for a linear column and
+ * (log10 x - log10 lo) / (log10 hi - log10 lo) for a log column; the prior is uniform on [0, 1]^A.  log10 of the bounds is the host's.
+ * A call whose A is not the box's number of active columns is refused.
+ *
+ * Proposal of a generation: K parents with boxes [a_kd, b_kd] (a, b are [K][A]), inv_vol[k] = 1 / prod_d (b_kd - a_kd); the
+ * generation has n_uniform + K * m children, the first n_uniform uniform in the cube, child n_uniform + j uniform in the box of
+ * parent j mod K: the counts are deterministic, so the mixture proportions are exact.  With generation 1 the uniform draw of S1
+ * samples, the deterministic-mixture density of ANY sample u of any generation is
+ *     r(u) = (S1 + sum_g [n_uniform_g + m_g * B_g(u)]) / S_total,    B_g(u) = sum_k inv_vol_k * 1[a_k <= u <= b_k]  (closed, every d),
+ * its weight at temperature tf is exp(LL / tf) / r(u), and LLc = LL - tf * ln r(u) handed to trpl_posterior_weights, _moments,
+ * trpl_weighted_quantiles, trpl_corner and the predictive band makes them work unchanged on the concatenated samples.  LLc is
+ * valid at the tf it was formed for: trpl_posterior_tf_scan over a refined set is NOT supported.
+ *
+ * trpl_refine_resample: systematic resampling.  W[S] weights (NaN or <= 0 counts as 0; +inf is refused by the host form and
+ * undefined in the _dev form), K draws, offset in [0, 1).  idx[k] (int64, non-decreasing) is the smallest i whose inclusive
+ * cumulative weight exceeds (k + offset) / K * sw, evaluated left to right in fp64 (a threshold that rounds up to sw is taken as the
+ * largest double below sw); stats[3] (nullable) = { sw, sum w^2, sw^2 / sum w^2 }; the squares are summed after scaling by
+ * the power of two of the largest weight, so the ratio (the effective sample size) is right where sum w^2 itself leaves fp64's
+ * range (weights near 1e-200: sum w^2 is then 0 or subnormal, the ratio is not).  The cumulative weight is formed in ONE order,
+ * a pure function of S: chunks of trpl_refine_chunk_rows() rows; in a chunk, thread t of 256 adds its 16 consecutive rows one
+ * after the other, the 256 thread totals are added one after the other, and so are the chunk totals; cum[i] = chunk prefix +
+ * (thread base + running sum).  Adding non-negative terms in a fixed order is monotone, so cum never decreases and every i is
+ * drawn floor(K p_i) or ceil(K p_i) times up to the rounding of cum.  sw == 0 (or S == 0): idx = -1 everywhere, stats = 0.
+ * workspace: trpl_refine_workspace_bytes(S) bytes of device memory.
+ *
+ * trpl_refine_draw: U2 [n_uniform + K m][A] and X2 [..][ncol].  Child n takes Philox4x32-10 (Salmon et al. 2011) with key
+ * (seed low word, seed high word) and counter (n low word, n high word, j, generation); call j gives the uniforms of dimensions 2j
+ * and 2j + 1: words (x0, x1) -> ((x0 >> 5) * 2^26 + (x1 >> 6)) / 2^53 and (x2, x3) the same way (genrand_res53, the sampler's
+ * form).  u = min(b, a + (b - a) * xi) with separate multiply and add (a = 0, b = 1 for the uniform children).  X2 follows
+ * trpl_sample_box's expressions: lo + (hi - lo) * u; pow(10, l + (lh - l) * u) with l, lh the log10 of the bounds; fixed columns
+ * copied; the overrides applied last.  U2 and the linear columns are pure functions of the arguments; log columns go through the
+ * device's pow.  a > b cannot be seen from the host in the _dev form: the children of such a box are all at b.
+ *
+ * trpl_refine_density: B[s] = B_g(u_s) for U [S][ldu >= A]; the sum over k is taken in ascending k, one fp64 add per member box
+ * starting from +0.0: the plain sequential loop, bit for bit, on any device.  A NaN coordinate lies in no box.  Parents are
+ * staged through LDS in tiles of trpl_refine_tile_parents().
+ *
+ * trpl_refine_unit: U [S][A] of existing samples X [S][ldx >= ncol].  It uses the device's log10, so it is not bit-pinned: the
+ * membership of a prior-generation sample at a box face may differ from a host computation by a last bit of u (an event of
+ * measure zero under the proposal).
+ *
+ * Refused with TRPL_ERR_ARG before a device is touched, the message naming the argument: a NULL W, idx, a, b, inv_vol, U, B, U2,
+ * X2, X, lo, hi, do_log (or workspace); S < 0; K < 1 or K > TRPL_REFINE_MAX_PARENTS; A outside [1, TRPL_REFINE_MAX_DIMS] or not the
+ * box's count; m < 0; n_uniform < 0; more than 2^31 - 2 children; offset outside [0, 1) or NaN; ldu < A; ldx < ncol; a +inf weight
+ * (host form).  The _dev calls take device pointers (the box arrays excepted), allocate nothing and never synchronise.
+ * Python: trpl_amd.refine, trpl_amd.device.refine_*_device.
+ * ------------------------------------------------------------------------------------- */
+#define TRPL_REFINE_MAX_DIMS 16
+#define TRPL_REFINE_MAX_PARENTS 1048576
+int64_t trpl_refine_chunk_rows(void);
+int64_t trpl_refine_tile_parents(void);
+int64_t trpl_refine_workspace_bytes(int64_t S);
+int trpl_refine_resample_dev(const double *W, int64_t S, int64_t K, double offset, int64_t *idx, double *stats /*nullable [3]*/,
+                             void *workspace, int64_t workspace_bytes, void *stream);
+int trpl_refine_resample(const double *W, int64_t S, int64_t K, double offset, int64_t *idx, double *stats /*nullable [3]*/,
+                         int32_t device, double *seconds);
+int trpl_refine_draw_dev(const double *a, const double *b, int64_t K, int32_t A, int64_t m, int64_t n_uniform, uint64_t seed,
+                         uint32_t generation, int32_t ncol, const double *lo /*host*/, const double *hi /*host*/,
+                         const int32_t *do_log /*host*/, uint32_t flags, double *U2, double *X2, void *stream);
+int trpl_refine_draw(const double *a, const double *b, int64_t K, int32_t A, int64_t m, int64_t n_uniform, uint64_t seed,
+                     uint32_t generation, int32_t ncol, const double *lo, const double *hi, const int32_t *do_log, uint32_t flags,
+                     double *U2, double *X2, int32_t device, double *seconds);
+int trpl_refine_density_dev(const double *U, int64_t S, int64_t ldu, int32_t A, const double *a, const double *b,
+                            const double *inv_vol, int64_t K, double *B, void *stream);
+int trpl_refine_density(const double *U, int64_t S, int64_t ldu, int32_t A, const double *a, const double *b, const double *inv_vol,
+                        int64_t K, double *B, int32_t device, double *seconds);
+int trpl_refine_unit_dev(const double *X, int64_t S, int64_t ldx, int32_t ncol, const double *lo /*host*/, const double *hi /*host*/,
+                         const int32_t *do_log /*host*/, uint32_t flags, int32_t A, double *U, void *stream);
+int trpl_refine_unit(const double *X, int64_t S, int64_t ldx, int32_t ncol, const double *lo, const double *hi, const int32_t *do_log,
+                     uint32_t flags, int32_t A, double *U, int32_t device, double *seconds);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the
  * measurement plan): S independent systems  ld[i] x[i-1] + d[i] x[i] + ud[i] x[i+1] = b[i],
  * i < L, the problem pcreduce solves (pvSimPCR.py:42-81), operands and result in HBM, arrays

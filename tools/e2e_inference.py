@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -15,6 +15,11 @@ sqrt(var) -- and seconds["predictive"]; without it the output is unchanged.
 tau_rad, Sf+Sb, mu', taun+taup; epsilon = 1 / lambda is one number in this box, which fixes lambda -- 96 bins,
 limits = the sampled box, every 1-D and 2-D marginal in one device call) as "corner": kept, the device seconds, and the mode of
 every 1-D marginal -- and seconds["corner"], the call with its copies; without it the output is unchanged.
+--refine [--rounds N] adds, at the end, N (default 1) refinement generations (trpl_amd.refine.run: parents resampled from the
+posterior, box-kernel children, the fused likelihood on them, deterministic-mixture weights of the union) as "refine": the
+effective sample size after every generation, the share of each generation's children with a weight > 0, the plain sum of the
+union's weights over the samples with a finite likelihood, and the numbers of NaN weights and of NaN in LLc among those
+samples -- and seconds["refine"]; without it the output is unchanged.
 """
 import json
 import sys
@@ -25,7 +30,13 @@ FIND_TF = "--find-tf" in sys.argv
 PREDICTIVE = "--predictive" in sys.argv
 QUANTILES = "--quantiles" in sys.argv
 CORNER = "--corner" in sys.argv
-sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner")]
+REFINE = "--refine" in sys.argv
+ROUNDS = 1
+if "--rounds" in sys.argv:
+    k = sys.argv.index("--rounds")
+    ROUNDS = int(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
+sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine")]
 import numpy as np
 import torch
 import trpl_amd
@@ -145,4 +156,30 @@ if CORNER:
                      "mode": {n: float(0.5 * (e[int(np.argmax(d))] + e[int(np.argmax(d)) + 1])) for n, (d, e) in cr["h_1D"].items()}}
     print("corner: kept %d of %d, %d histograms in %.3f ms on the device" % (cr["kept"], S, out["corner"]["histograms"],
                                                                            1e3 * cinfo["seconds"]), file=sys.stderr)
+if REFINE:
+    from trpl_amd import posterior, refine
+    t9 = sync()
+
+    def fused(X2):                                               # the fused likelihood of a generation's children
+        n = X2.shape[0]
+        Xd = torch.from_numpy(np.ascontiguousarray(X2)).to(dev)
+        P2 = torch.zeros(n, dtype=torch.float64, device=dev)
+        tdev.loglik_device(Xd, ini_d, lens, T * dt, L, T, obs, [T + 1] * C, P2, torch.empty((C, n), dtype=torch.float64, device=dev))
+        return P2.cpu().numpy()
+
+    tf = n_obs * c_val
+    K = max(1, min(1024, S // 32))
+    rinfo = {}
+    pop = refine.run(fused, X.cpu().numpy(), P.cpu().numpy(), lo, hi, lg, rounds=ROUNDS, K=K, m=28, n_uniform=max(1, S // 8), tf=tf,
+                     seed=42, info=rinfo)
+    X_all, LLc = pop.corrected(tf)
+    W_all = posterior.weights(LLc, tf)
+    LL_all = np.concatenate(pop.LL)
+    out["seconds"]["refine"] = sync() - t9
+    out["refine"] = {"rounds": ROUNDS, "parents": K, "children_per_parent": 28, "n_uniform": max(1, S // 8), "samples": int(X_all.shape[0]),
+                     "ess_per_generation": rinfo["ess"], "nonzero_share_of_children": rinfo["nonzero"],
+                     "weight_sum": float(np.sum(W_all[np.isfinite(LL_all)])), "nan_weights_from_finite_ll": int(np.sum(np.isnan(W_all) & np.isfinite(LL_all))),
+                     "nan_llc_from_finite_ll": int(np.sum(np.isnan(LLc) & np.isfinite(LL_all)))}
+    print("refine: effective sample size per generation %s, share of children with a weight > 0 %s"
+          % (["%.2f" % e for e in rinfo["ess"]], ["%.4f" % f for f in rinfo["nonzero"]]), file=sys.stderr)
 print(json.dumps(out))
