@@ -9,7 +9,8 @@ absent `numba`) first on sys.path, calls the reference functions, and stores *da
 
 Reference entry points exercised (file:line):
   pvSimPCR.pcreduce :42-81, pvSimPCR.norm2 :14-40          -> pcr_norm.npz
-  pvSimPCR.pvSim :309-401 (tEvol :227-306, iterate :93-225) -> pvsim_*.npz (pvsim_bundle: max_sims_per_block 2 and 3)
+  pvSimPCR.pvSim :309-401 (tEvol :227-306, iterate :93-225) -> pvsim_*.npz (pvsim_bundle: max_sims_per_block 2 and 3;
+                                                               pvsim_grids: L = 4, 16, 256)
   probs.fastlog :78-85, probs.prob :49-62                   -> probs.npz
   bayeslib.random_grid :18-32, bayeslib.bayes :207-252      -> bayes_e2e.npz, sampler.npz
   pvSim_fallback.pvSim_cpu_fallback :80-117 (as shipped)    -> fallback.npz
@@ -176,6 +177,19 @@ def case_pvsim_small():
                        init_mode="points")
     out["nc_plI"] = pl; out["nc_log"] = np.array(rec.log); out["nc_ini"] = ini_hi
     np.savez_compressed(os.path.join(OUT, "pvsim_small.npz"), X=X, **out)
+
+
+def case_pvsim_grids():
+    """The grid sizes pvsim_small leaves out (the product compiles L = 4 .. 512): the same film, window and tolerance as
+    case_pvsim_small at L = 4, 16, 256.  A size the reference cannot run (L = 512: its shared arrays) is left out."""
+    out = {}
+    X = np.vstack([draw(2), MARK * UNIT])
+    for L in (4, 16, 256):
+        x = (np.arange(L) + 0.5) * (500.0 / L)
+        ini = 1e17 * 1e-21 * np.exp(-6e-3 * x)
+        p, i = run_pvsim(X[:, :-1], 500, 30 * 0.05, L, 30, ini, np.float64, tol=6)
+        out[f"plI_L{L}"] = p; out[f"it_L{L}"] = i; out[f"ini_L{L}"] = ini
+    np.savez_compressed(os.path.join(OUT, "pvsim_grids.npz"), X=X, **out)
 
 
 def case_pvsim_bundle():
@@ -637,7 +651,7 @@ def case_posterior():
 
 
 CASES = {"posterior": case_posterior, "legacy_odeint": case_legacy_odeint, "tester_refine": case_tester_refine, "legacy_full": case_legacy_full, "csv_fixture": case_csv_fixture, "bayes_realdata": case_bayes_realdata, "pcr_norm": case_pcr_norm, "probs": case_probs, "sampler": case_sampler,
-         "pvsim_small": case_pvsim_small, "pvsim_power": case_pvsim_power, "pvsim_bundle": case_pvsim_bundle,
+         "pvsim_small": case_pvsim_small, "pvsim_grids": case_pvsim_grids, "pvsim_power": case_pvsim_power, "pvsim_bundle": case_pvsim_bundle,
          "pvsim_twothick": case_pvsim_twothick, "bayes_e2e": case_bayes_e2e,
          "fallback": case_fallback, "fallback64": case_fallback64}
 

@@ -44,26 +44,27 @@ def _observations(C, T, plT, offgrid):
     return times, [18.0 - 0.2 * t + 0.05 * rng.standard_normal(len(t)) for t in times]
 
 
-def _run(gpu, X, ini, lens, T, obs, times, kw, sse_cut=None, upto=None, P=None):
+def _run(gpu, X, ini, lens, T, obs, times, kw, sse_cut=None, upto=None, P=None, L=128):
     """One call; upto = k truncates every curve to its first min(k, n_obs) observations (the plain call a cut is compared with)."""
     if upto is not None:
         obs = [o[:upto] for o in obs]
         times = None if times is None else [t[:upto] for t in times]
     info = {}
-    P = gpu.loglik(X, ini, lens, T * DT, 128, T, obs, times=times, info=info, sse_cut=sse_cut,
+    P = gpu.loglik(X, ini, lens, T * DT, L, T, obs, times=times, info=info, sse_cut=sse_cut,
                    P=None if P is None else P.copy(), **kw)
     info["P"] = P
     return info
 
 
-def _check_against_plain(gpu, X, ini, lens, T, obs, times, kw, label):
+def _check_against_plain(gpu, X, ini, lens, T, obs, times, kw, label, L=128):
+    """L: the grid size (tests/test_gpu_stepper_grids.py runs this at every compiled one)."""
     n_obs = np.array([len(o) for o in obs])
     C, S = len(obs), len(X)
     P_in = np.linspace(-3.0, 5.0, S)
-    ref = _run(gpu, X, ini, lens, T, obs, times, kw, P=P_in)
+    ref = _run(gpu, X, ini, lens, T, obs, times, kw, P=P_in, L=L)
     conv = ref["status"] == 0
     level = float(np.median(ref["sse"][conv]))
-    out = _run(gpu, X, ini, lens, T, obs, times, kw, sse_cut=level, P=P_in)
+    out = _run(gpu, X, ini, lens, T, obs, times, kw, sse_cut=level, P=P_in, L=L)
     cc = out["cut_col"]
     cut, uncut = cc >= 0, cc == -1
     print("%s: level %.6g, cut %d / uncut %d / flagged %d of %d; iterations cut / plain = %.4f; cut counts %s"
@@ -82,7 +83,7 @@ def _check_against_plain(gpu, X, ini, lens, T, obs, times, kw, label):
     for k in sorted(set(cc[cut].tolist())):
         m = cc == k
         assert (n_obs[np.nonzero(m)[0]] >= k).all()
-        tr = _run(gpu, X, ini, lens, T, obs, times, kw, upto=k)
+        tr = _run(gpu, X, ini, lens, T, obs, times, kw, upto=k, L=L)
         assert np.array_equal(out["sse"][m], tr["sse"][m]), k
         assert np.array_equal(out["floor_col"][m], tr["floor_col"][m]), k
         assert not tr["status"][m].any()
@@ -90,7 +91,7 @@ def _check_against_plain(gpu, X, ini, lens, T, obs, times, kw, label):
             assert np.array_equal(out["iters_total"][m], tr["iters_total"][m]), k
             assert ((k % 64 == 0) | (n_obs[np.nonzero(m)[0]] == k)).all(), k
             if k > 64 and k % 64 == 0:                                   # minimality: one batch earlier the sum was not above
-                before = _run(gpu, X, ini, lens, T, obs, times, kw, upto=k - 64)
+                before = _run(gpu, X, ini, lens, T, obs, times, kw, upto=k - 64, L=L)
                 assert (before["sse"][m] <= level).all(), k
     # iterations
     assert out["iters_total"].sum() < ref["iters_total"].sum()

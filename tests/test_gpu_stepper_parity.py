@@ -202,6 +202,7 @@ def test_pvsim_float32_buffer_matches_reference(gpu, golden):
 
 
 def test_pvsim_small_grids_plT_and_nonconvergence(gpu, golden):
+    """Every compiled grid size, every sink and predict against the oracle: tests/test_gpu_stepper_grids.py."""
     g = golden("pvsim_small")
     X = g["X"]
     for L in (8, 32, 64):

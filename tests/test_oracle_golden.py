@@ -72,6 +72,18 @@ def test_pvsim_bundled_convergence_bit_exact(oracle, golden):
     assert (r["status"][:3] == r["status"][0]).all() and r["status"][6] == 0
 
 
+def test_pvsim_grids_the_sizes_the_small_golden_leaves_out(oracle, golden):
+    """L = 4, 16, 256 (oracle/gen_golden.py case_pvsim_grids: the reference's pvSim on pvsim_small's film, window and tolerance):
+    with pvsim_small (8, 32, 64) and the L = 128 goldens the oracle is pinned at every grid size the stepper is compiled for
+    but L = 512, which the reference cannot run (its shared arrays exceed the static limit); all three sizes asked for ran."""
+    g = golden("pvsim_grids")
+    X = g["X"]
+    for L in (4, 16, 256):
+        r = oracle.pvsim(X[:, :-1], 500, 30 * 0.05, L, 30, g[f"ini_L{L}"], tol=6, want_step_iters=True)
+        assert not r["status"].any() and r["plI"].shape == (3, 31)
+        assert np.array_equal(r["plI"], g[f"plI_L{L}"]) and np.array_equal(r["step_iters"], g[f"it_L{L}"])
+
+
 def test_pvsim_small_grids_plT_and_nonconvergence(oracle, golden):
     g = golden("pvsim_small")
     X = g["X"]
