@@ -18,47 +18,74 @@ def _chk(t, dtype, name):
     return t.data_ptr()
 
 
+def _opt(t, dtype, name):
+    """_chk for an optional tensor: None stays None (a NULL pointer)."""
+    return None if t is None else _chk(t, dtype, name)
+
+
+def _brackets(obs, obs_hi, obs_dx, obs_h):
+    """The bracketing arrays of driver.bracket_times as three pointers, each shaped like obs -- or three None on the grid
+    (obs_hi is None)."""
+    import torch
+    if obs_hi is None:
+        return [None, None, None]
+    if not (obs.shape == obs_hi.shape == obs_dx.shape == obs_h.shape):
+        raise ValueError("shape mismatch")
+    return [_chk(obs_hi, torch.int32, "obs_hi"), _chk(obs_dx, torch.float64, "obs_dx"), _chk(obs_h, torch.float64, "obs_h")]
+
+
+def _loglik_dev(entry, X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status, iters_total, tol, MAX, flags, floor_col,
+                plT=1, obs_hi=None, obs_dx=None, obs_h=None, wts=None, sse_cut=None, esum=None, cut_col=None):
+    """The one marshaller of the fused family trpl_loglik[_obs|_moments|_weighted|_cut]_dev: the arguments all five share,
+    with an entry point's own where include/trpl.h puts them -- wts after obs, the brackets after that (not in trpl_loglik_dev),
+    sse_cut before P, esum or cut_col after sse; trpl_loglik_obs_dev alone has no plT.  A new sink or argument goes HERE."""
+    import torch
+    f64 = torch.float64
+    S, Cn = X.shape[0], init_params.shape[0]
+    if X.shape[1] != 13 or init_params.shape[1] != L or obs.shape[0] != Cn or tuple(sse.shape) != (Cn, S) \
+            or tuple(P.shape) != (S,) or (wts is not None and wts.shape != obs.shape) \
+            or any(t is not None and tuple(t.shape) != (Cn, S) for t in (esum, cut_col)):
+        raise ValueError("shape mismatch")
+    brackets = _brackets(obs, obs_hi, obs_dx, obs_h)
+    lengths = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.float64), (Cn,)))
+    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
+    args = [_chk(X, f64, "X"), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T)]
+    if entry != "trpl_loglik_obs_dev":
+        args.append(int(plT))
+    args += [int(tol), int(MAX), _chk(init_params, f64, "init_params"), _chk(obs, f64, "obs")]
+    if entry == "trpl_loglik_weighted_dev":
+        args.append(_chk(wts, f64, "wts"))
+    if entry != "trpl_loglik_dev":
+        args += brackets
+    args += [obs.shape[1], _abi.ptr(n_obs)]
+    if entry == "trpl_loglik_cut_dev":
+        args.append(float(sse_cut))
+    args += [_chk(P, f64, "P"), _chk(sse, f64, "sse")]
+    if entry in ("trpl_loglik_moments_dev", "trpl_loglik_weighted_dev"):
+        args.append(_chk(esum, f64, "esum"))
+    if entry == "trpl_loglik_cut_dev":
+        args.append(_opt(cut_col, torch.int32, "cut_col"))
+    args += [_opt(status, torch.int32, "status"), _opt(iters_total, torch.int64, "iters_total"),
+             _opt(floor_col, torch.int32, "floor_col"), int(flags), _stream()]
+    _abi.check(getattr(_abi.lib(), entry)(*args))
+
+
 def loglik_device(X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status=None, iters_total=None,
                   tol=7, MAX=10000, plT=1, flags=0, floor_col=None):
     """trpl_loglik_dev on the current device and stream.  X (S,13) f64, init_params (C,L) f64,
     obs (C,obs_ld) f64, P (S,) f64 accumulated in place, sse (C,S) f64 out, optional status
     (C,S) int32, iters_total (C,S) int64 and floor_col (C,S) int32 (first compared PL column below the
     cancellation floor, -1 if none: include/trpl.h).  lengths / n_obs are host sequences."""
-    import torch
-    S, Cn = X.shape[0], init_params.shape[0]
-    if X.shape[1] != 13 or init_params.shape[1] != L or obs.shape[0] != Cn or tuple(sse.shape) != (Cn, S) \
-            or tuple(P.shape) != (S,):
-        raise ValueError("shape mismatch")
-    lengths = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.float64), (Cn,)))
-    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
-    _abi.check(_abi.lib().trpl_loglik_dev(
-        _chk(X, torch.float64, "X"), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol),
-        int(MAX), _chk(init_params, torch.float64, "init_params"), _chk(obs, torch.float64, "obs"),
-        obs.shape[1], _abi.ptr(n_obs), _chk(P, torch.float64, "P"), _chk(sse, torch.float64, "sse"),
-        None if status is None else _chk(status, torch.int32, "status"),
-        None if iters_total is None else _chk(iters_total, torch.int64, "iters_total"),
-        None if floor_col is None else _chk(floor_col, torch.int32, "floor_col"), int(flags), _stream()))
+    _loglik_dev("trpl_loglik_dev", X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status, iters_total, tol, MAX, flags,
+                floor_col, plT=plT)
 
 
 def loglik_obs_device(X, init_params, lengths, Time, L, T, obs, obs_hi, obs_dx, obs_h, n_obs, P, sse, status=None,
                       iters_total=None, tol=7, MAX=10000, flags=0, floor_col=None):
     """trpl_loglik_obs_dev: observation times off the simulation grid.  obs / obs_dx / obs_h (C,obs_ld)
     f64 and obs_hi (C,obs_ld) int32 are the bracketing arrays of driver.bracket_times, on the device."""
-    import torch
-    S, Cn = X.shape[0], init_params.shape[0]
-    if X.shape[1] != 13 or init_params.shape[1] != L or tuple(sse.shape) != (Cn, S) or tuple(P.shape) != (S,) \
-            or not (obs.shape == obs_hi.shape == obs_dx.shape == obs_h.shape) or obs.shape[0] != Cn:
-        raise ValueError("shape mismatch")
-    lengths = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.float64), (Cn,)))
-    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
-    _abi.check(_abi.lib().trpl_loglik_obs_dev(
-        _chk(X, torch.float64, "X"), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(tol), int(MAX),
-        _chk(init_params, torch.float64, "init_params"), _chk(obs, torch.float64, "obs"),
-        _chk(obs_hi, torch.int32, "obs_hi"), _chk(obs_dx, torch.float64, "obs_dx"), _chk(obs_h, torch.float64, "obs_h"),
-        obs.shape[1], _abi.ptr(n_obs), _chk(P, torch.float64, "P"), _chk(sse, torch.float64, "sse"),
-        None if status is None else _chk(status, torch.int32, "status"),
-        None if iters_total is None else _chk(iters_total, torch.int64, "iters_total"),
-        None if floor_col is None else _chk(floor_col, torch.int32, "floor_col"), int(flags), _stream()))
+    _loglik_dev("trpl_loglik_obs_dev", X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status, iters_total, tol, MAX,
+                flags, floor_col, obs_hi=obs_hi, obs_dx=obs_dx, obs_h=obs_h)
 
 
 def loglik_moments_device(X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, esum, status=None, iters_total=None,
@@ -66,24 +93,8 @@ def loglik_moments_device(X, init_params, lengths, Time, L, T, obs, n_obs, P, ss
     """trpl_loglik_moments_dev: loglik_device / loglik_obs_device (with the bracketing arrays obs_hi, obs_dx, obs_h) that
     also fills esum (C,S) f64, the sum of the log-errors whose squares make sse -- the input of mag_grid_device and
     mag_profile_device.  P, sse, status, iters_total and floor_col are loglik[_obs]_device's, bit for bit."""
-    import torch
-    S, Cn = X.shape[0], init_params.shape[0]
-    interp = obs_hi is not None
-    if X.shape[1] != 13 or init_params.shape[1] != L or obs.shape[0] != Cn or tuple(sse.shape) != (Cn, S) \
-            or tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (S,) \
-            or (interp and not (obs.shape == obs_hi.shape == obs_dx.shape == obs_h.shape)):
-        raise ValueError("shape mismatch")
-    lengths = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.float64), (Cn,)))
-    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
-    _abi.check(_abi.lib().trpl_loglik_moments_dev(
-        _chk(X, torch.float64, "X"), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol),
-        int(MAX), _chk(init_params, torch.float64, "init_params"), _chk(obs, torch.float64, "obs"),
-        _chk(obs_hi, torch.int32, "obs_hi") if interp else None, _chk(obs_dx, torch.float64, "obs_dx") if interp else None,
-        _chk(obs_h, torch.float64, "obs_h") if interp else None, obs.shape[1], _abi.ptr(n_obs),
-        _chk(P, torch.float64, "P"), _chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
-        None if status is None else _chk(status, torch.int32, "status"),
-        None if iters_total is None else _chk(iters_total, torch.int64, "iters_total"),
-        None if floor_col is None else _chk(floor_col, torch.int32, "floor_col"), int(flags), _stream()))
+    _loglik_dev("trpl_loglik_moments_dev", X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status, iters_total, tol, MAX,
+                flags, floor_col, plT=plT, obs_hi=obs_hi, obs_dx=obs_dx, obs_h=obs_h, esum=esum)
 
 
 def loglik_cut_device(X, init_params, lengths, Time, L, T, obs, n_obs, sse_cut, P, sse, cut_col=None, status=None,
@@ -93,52 +104,46 @@ def loglik_cut_device(X, init_params, lengths, Time, L, T, obs, n_obs, sse_cut, 
     early stop -- a system whose running sse is above sse_cut (a float >= 0 or +inf) after one of its 64-column batches
     takes no further time step.  cut_col (C,S) int32 optional: the leading observations in a cut system's sse, -1 for an
     uncut system (all its outputs are loglik_device's, bit for bit), -2 for a flagged one (include/trpl.h)."""
+    _loglik_dev("trpl_loglik_cut_dev", X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status, iters_total, tol, MAX,
+                flags, floor_col, plT=plT, obs_hi=obs_hi, obs_dx=obs_dx, obs_h=obs_h, sse_cut=sse_cut, cut_col=cut_col)
+
+
+def _mag_grid_dev(entry, sse, esum, per_curve, dtype, offsets, P):
+    """trpl_mag_grid_dev / trpl_mag_grid_w_dev: one call, the per-curve host vector n_obs (int64) or wsum (float64)."""
     import torch
-    S, Cn = X.shape[0], init_params.shape[0]
-    interp = obs_hi is not None
-    if X.shape[1] != 13 or init_params.shape[1] != L or obs.shape[0] != Cn or tuple(sse.shape) != (Cn, S) \
-            or tuple(P.shape) != (S,) or (cut_col is not None and tuple(cut_col.shape) != (Cn, S)) \
-            or (interp and not (obs.shape == obs_hi.shape == obs_dx.shape == obs_h.shape)):
+    Cn, S = sse.shape
+    off = np.ascontiguousarray(offsets, dtype=np.float64).ravel()
+    per_curve = np.ascontiguousarray(np.broadcast_to(np.asarray(per_curve, dtype=dtype), (Cn,)))
+    if tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (len(off), S):
         raise ValueError("shape mismatch")
-    lengths = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.float64), (Cn,)))
-    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
-    _abi.check(_abi.lib().trpl_loglik_cut_dev(
-        _chk(X, torch.float64, "X"), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol),
-        int(MAX), _chk(init_params, torch.float64, "init_params"), _chk(obs, torch.float64, "obs"),
-        _chk(obs_hi, torch.int32, "obs_hi") if interp else None, _chk(obs_dx, torch.float64, "obs_dx") if interp else None,
-        _chk(obs_h, torch.float64, "obs_h") if interp else None, obs.shape[1], _abi.ptr(n_obs), float(sse_cut),
-        _chk(P, torch.float64, "P"), _chk(sse, torch.float64, "sse"),
-        None if cut_col is None else _chk(cut_col, torch.int32, "cut_col"),
-        None if status is None else _chk(status, torch.int32, "status"),
-        None if iters_total is None else _chk(iters_total, torch.int64, "iters_total"),
-        None if floor_col is None else _chk(floor_col, torch.int32, "floor_col"), int(flags), _stream()))
+    _abi.check(getattr(_abi.lib(), entry)(_chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
+                                          _abi.ptr(per_curve), S, Cn, _abi.ptr(off), len(off),
+                                          _chk(P, torch.float64, "P"), _stream()))
+
+
+def _mag_profile_dev(entry, sse, esum, per_curve, dtype, best, P, best_per_curve):
+    """trpl_mag_profile_dev / trpl_mag_profile_w_dev: as _mag_grid_dev."""
+    import torch
+    Cn, S = sse.shape
+    per_curve = np.ascontiguousarray(np.broadcast_to(np.asarray(per_curve, dtype=dtype), (Cn,)))
+    if tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (S,) \
+            or tuple(best.shape) != ((Cn, S) if best_per_curve else (S,)):
+        raise ValueError("shape mismatch")
+    _abi.check(getattr(_abi.lib(), entry)(_chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
+                                          _abi.ptr(per_curve), S, Cn, _abi.MAG_PER_CURVE if best_per_curve else 0,
+                                          _chk(best, torch.float64, "best"), _chk(P, torch.float64, "P"), _stream()))
 
 
 def mag_grid_device(sse, esum, n_obs, offsets, P):
     """trpl_mag_grid_dev: P (M,S) f64 -= sum_c max(sse + 2 d_m esum + n_c d_m^2, 0) for the offsets d_m (host sequence,
     added to X[:, 12]); sse, esum (C,S) f64 from loglik_moments_device, n_obs a host sequence (C,)."""
-    import torch
-    Cn, S = sse.shape
-    off = np.ascontiguousarray(offsets, dtype=np.float64).ravel()
-    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
-    if tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (len(off), S):
-        raise ValueError("shape mismatch")
-    _abi.check(_abi.lib().trpl_mag_grid_dev(_chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
-                                            _abi.ptr(n_obs), S, Cn, _abi.ptr(off), len(off),
-                                            _chk(P, torch.float64, "P"), _stream()))
+    _mag_grid_dev("trpl_mag_grid_dev", sse, esum, n_obs, np.int64, offsets, P)
 
 
 def mag_profile_device(sse, esum, n_obs, best, P, per_curve=False):
     """trpl_mag_profile_dev: the likelihood-maximising offset best (S,) -- (C,S) with per_curve -- and P (S,) -= the
     squared error there (the profile likelihood over the magnitude offset)."""
-    import torch
-    Cn, S = sse.shape
-    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
-    if tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (S,) or tuple(best.shape) != ((Cn, S) if per_curve else (S,)):
-        raise ValueError("shape mismatch")
-    _abi.check(_abi.lib().trpl_mag_profile_dev(_chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
-                                               _abi.ptr(n_obs), S, Cn, _abi.MAG_PER_CURVE if per_curve else 0,
-                                               _chk(best, torch.float64, "best"), _chk(P, torch.float64, "P"), _stream()))
+    _mag_profile_dev("trpl_mag_profile_dev", sse, esum, n_obs, np.int64, best, P, per_curve)
 
 
 def loglik_weighted_device(X, init_params, lengths, Time, L, T, obs, wts, n_obs, P, sse, esum, status=None,
@@ -147,67 +152,57 @@ def loglik_weighted_device(X, init_params, lengths, Time, L, T, obs, wts, n_obs,
     """trpl_loglik_weighted_dev: loglik_moments_device with the observation weights wts, a device tensor shaped like obs:
     sse (C,S) = sum w e^2, esum (C,S) = sum w e, P (S,) -= sum_c sse.  The weights are NOT checked here (no
     synchronisation): finite and >= 0 is the caller's responsibility."""
-    import torch
-    S, Cn = X.shape[0], init_params.shape[0]
-    interp = obs_hi is not None
-    if X.shape[1] != 13 or init_params.shape[1] != L or obs.shape[0] != Cn or tuple(sse.shape) != (Cn, S) \
-            or tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (S,) or wts.shape != obs.shape \
-            or (interp and not (obs.shape == obs_hi.shape == obs_dx.shape == obs_h.shape)):
-        raise ValueError("shape mismatch")
-    lengths = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.float64), (Cn,)))
-    n_obs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_obs, dtype=np.int64), (Cn,)))
-    _abi.check(_abi.lib().trpl_loglik_weighted_dev(
-        _chk(X, torch.float64, "X"), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol),
-        int(MAX), _chk(init_params, torch.float64, "init_params"), _chk(obs, torch.float64, "obs"),
-        _chk(wts, torch.float64, "wts"),
-        _chk(obs_hi, torch.int32, "obs_hi") if interp else None, _chk(obs_dx, torch.float64, "obs_dx") if interp else None,
-        _chk(obs_h, torch.float64, "obs_h") if interp else None, obs.shape[1], _abi.ptr(n_obs),
-        _chk(P, torch.float64, "P"), _chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
-        None if status is None else _chk(status, torch.int32, "status"),
-        None if iters_total is None else _chk(iters_total, torch.int64, "iters_total"),
-        None if floor_col is None else _chk(floor_col, torch.int32, "floor_col"), int(flags), _stream()))
+    _loglik_dev("trpl_loglik_weighted_dev", X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status, iters_total, tol,
+                MAX, flags, floor_col, plT=plT, obs_hi=obs_hi, obs_dx=obs_dx, obs_h=obs_h, wts=wts, esum=esum)
 
 
 def mag_grid_w_device(sse, esum, wsum, offsets, P):
     """trpl_mag_grid_w_dev: mag_grid_device from the weighted moments; wsum a host sequence (C,), the sum of each
     curve's weights, in place of n_obs."""
-    import torch
-    Cn, S = sse.shape
-    off = np.ascontiguousarray(offsets, dtype=np.float64).ravel()
-    wsum = np.ascontiguousarray(np.broadcast_to(np.asarray(wsum, dtype=np.float64), (Cn,)))
-    if tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (len(off), S):
-        raise ValueError("shape mismatch")
-    _abi.check(_abi.lib().trpl_mag_grid_w_dev(_chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
-                                              _abi.ptr(wsum), S, Cn, _abi.ptr(off), len(off),
-                                              _chk(P, torch.float64, "P"), _stream()))
+    _mag_grid_dev("trpl_mag_grid_w_dev", sse, esum, wsum, np.float64, offsets, P)
 
 
 def mag_profile_w_device(sse, esum, wsum, best, P, per_curve=False):
     """trpl_mag_profile_w_dev: mag_profile_device from the weighted moments (wsum as in mag_grid_w_device)."""
+    _mag_profile_dev("trpl_mag_profile_w_dev", sse, esum, wsum, np.float64, best, P, per_curve)
+
+
+def _solve_pl_dev(entry, matPar, Length, Time, L, T, plI, status, iters_total, tol, MAX, plT, flags, dN=None, resume=None,
+                  snap=None):
+    """The one marshaller of trpl_solve_pl[_snap|_resume]_dev: head, where the solve starts -- dN, or resume = (t0, resN, resP,
+    resE) -- the PL block and, not in trpl_solve_pl_dev, the snapshot block snap = (snap_steps, plN, plP, plE)."""
     import torch
-    Cn, S = sse.shape
-    wsum = np.ascontiguousarray(np.broadcast_to(np.asarray(wsum, dtype=np.float64), (Cn,)))
-    if tuple(esum.shape) != (Cn, S) or tuple(P.shape) != (S,) or tuple(best.shape) != ((Cn, S) if per_curve else (S,)):
+    f64 = torch.float64
+    S = matPar.shape[0]
+    if matPar.shape[1] != 12 or (resume is None and tuple(dN.shape) != (L,)) or tuple(plI.shape) != (S, T // plT + 1):
         raise ValueError("shape mismatch")
-    _abi.check(_abi.lib().trpl_mag_profile_w_dev(_chk(sse, torch.float64, "sse"), _chk(esum, torch.float64, "esum"),
-                                                 _abi.ptr(wsum), S, Cn, _abi.MAG_PER_CURVE if per_curve else 0,
-                                                 _chk(best, torch.float64, "best"), _chk(P, torch.float64, "P"), _stream()))
+    if plI.dtype not in (torch.float32, torch.float64):
+        raise ValueError("plI must be float32 or float64")
+    if resume is None:
+        start = [_chk(dN, f64, "dN")]
+    else:
+        for t, w in zip(resume[1:], (L, L, L + 1)):
+            if tuple(t.shape) != (S, 5, w):
+                raise ValueError("resume tensors must be (S, 5, L) / (S, 5, L+1)")
+        start = [int(resume[0])] + [_chk(t, f64, name) for t, name in zip(resume[1:], ("resN", "resP", "resE"))]
+    tail = []
+    if snap is not None:
+        steps = np.ascontiguousarray(snap[0], dtype=np.int64)
+        n = len(steps)
+        for t, w in zip(snap[1:], (L, L, L + 1)):
+            if t is not None and tuple(t.shape) != (S, n, w):
+                raise ValueError("snapshot tensors must be (S, len(snap_steps), L) / (.., L+1)")
+        tail = [_abi.ptr(steps) if n else None, n] + [_opt(t, f64, name) for t, name in zip(snap[1:], ("plN", "plP", "plE"))]
+    _abi.check(getattr(_abi.lib(), entry)(
+        _chk(matPar, f64, "matPar"), S, float(Length), float(Time), int(L), int(T), int(plT), int(tol), int(MAX), *start,
+        _chk(plI, plI.dtype, "plI"), plI.element_size(), plI.shape[1], _opt(status, torch.int32, "status"),
+        _opt(iters_total, torch.int64, "iters_total"), *tail, int(flags), _stream()))
 
 
 def solve_pl_device(matPar, Length, Time, L, T, dN, plI, status=None, iters_total=None, tol=7, MAX=10000, plT=1,
                     flags=0):
     """trpl_solve_pl_dev: matPar (S,12) f64, dN (L,) f64, plI (S, T//plT+1) f32/f64 out."""
-    import torch
-    S = matPar.shape[0]
-    if matPar.shape[1] != 12 or tuple(dN.shape) != (L,) or tuple(plI.shape) != (S, T // plT + 1):
-        raise ValueError("shape mismatch")
-    if plI.dtype not in (torch.float32, torch.float64):
-        raise ValueError("plI must be float32 or float64")
-    _abi.check(_abi.lib().trpl_solve_pl_dev(
-        _chk(matPar, torch.float64, "matPar"), S, float(Length), float(Time), int(L), int(T), int(plT), int(tol),
-        int(MAX), _chk(dN, torch.float64, "dN"), _chk(plI, plI.dtype, "plI"), plI.element_size(), plI.shape[1],
-        None if status is None else _chk(status, torch.int32, "status"),
-        None if iters_total is None else _chk(iters_total, torch.int64, "iters_total"), int(flags), _stream()))
+    _solve_pl_dev("trpl_solve_pl_dev", matPar, Length, Time, L, T, plI, status, iters_total, tol, MAX, plT, flags, dN=dN)
 
 
 def pcr_solve_device(ld, d, ud, b, x, flags=0):
@@ -554,6 +549,26 @@ def sample_box_device(X, minX, maxX, do_log, seed=42, flags=0):
                                               _abi.ptr(lg), int(flags), _chk(X, torch.float64, "X"), _stream()))
 
 
+def _loglik_from_pl_dev(entry, pl, obs, mag, P, sse, obs_hi, obs_dx, obs_h, ncol, flags, status, wts=None, esum=None):
+    """The one marshaller of trpl_loglik[_moments|_weighted]_from_pl_dev: wts after obs (the weighted entry), esum after sse
+    (not in trpl_loglik_from_pl_dev)."""
+    import torch
+    f64 = torch.float64
+    if pl.dim() != 2 or pl.dtype not in (torch.float32, torch.float64):
+        raise ValueError("pl must be a 2-D float32/float64 tensor")
+    if wts is not None and wts.shape != obs.shape:
+        raise ValueError("shape mismatch")
+    rows, ld = pl.shape
+    args = [_chk(pl, pl.dtype, "pl"), pl.element_size(), rows, int(ld if ncol is None else ncol), ld, _chk(obs, f64, "obs")]
+    if entry == "trpl_loglik_weighted_from_pl_dev":
+        args.append(_chk(wts, f64, "wts"))
+    args += _brackets(obs, obs_hi, obs_dx, obs_h)
+    args += [obs.shape[0], _chk(mag, f64, "mag"), _opt(status, torch.int32, "status"), _opt(P, f64, "P"), _opt(sse, f64, "sse")]
+    if entry != "trpl_loglik_from_pl_dev":
+        args.append(_opt(esum, f64, "esum"))
+    _abi.check(getattr(_abi.lib(), entry)(*args, int(flags), _stream()))
+
+
 def loglik_from_pl_device(pl, obs, mag, P=None, sse=None, obs_hi=None, obs_dx=None, obs_h=None, ncol=None, flags=0,
                           status=None):
     """trpl_loglik_from_pl_dev: likelihood of PL rows resident in HBM (pl (rows, ld) f32/f64, as written by
@@ -561,57 +576,23 @@ def loglik_from_pl_device(pl, obs, mag, P=None, sse=None, obs_hi=None, obs_dx=No
     bracketing arrays obs_hi (int32), obs_dx, obs_h of driver.bracket_times.  mag (rows,) f64 log offsets;
     P (rows,) is decremented in place and/or sse (rows,) receives the squared-error sums; status (rows,)
     int32 from solve_pl_device makes flagged systems score +inf."""
-    import torch
-    if pl.dim() != 2 or pl.dtype not in (torch.float32, torch.float64):
-        raise ValueError("pl must be a 2-D float32/float64 tensor")
-    rows, ld = pl.shape
-    interp = obs_hi is not None
-    _abi.check(_abi.lib().trpl_loglik_from_pl_dev(
-        _chk(pl, pl.dtype, "pl"), pl.element_size(), rows, int(ld if ncol is None else ncol), ld,
-        _chk(obs, torch.float64, "obs"), _chk(obs_hi, torch.int32, "obs_hi") if interp else None,
-        _chk(obs_dx, torch.float64, "obs_dx") if interp else None, _chk(obs_h, torch.float64, "obs_h") if interp else None,
-        obs.shape[0], _chk(mag, torch.float64, "mag"), None if status is None else _chk(status, torch.int32, "status"),
-        None if P is None else _chk(P, torch.float64, "P"),
-        None if sse is None else _chk(sse, torch.float64, "sse"), int(flags), _stream()))
+    _loglik_from_pl_dev("trpl_loglik_from_pl_dev", pl, obs, mag, P, sse, obs_hi, obs_dx, obs_h, ncol, flags, status)
 
 
 def loglik_moments_from_pl_device(pl, obs, mag, P=None, sse=None, esum=None, obs_hi=None, obs_dx=None, obs_h=None,
                                   ncol=None, flags=0, status=None):
     """trpl_loglik_moments_from_pl_dev: loglik_from_pl_device that also fills esum (rows,) f64, the sum of the row's
     log-errors (NaN for a flagged row): the resident-PL source of mag_grid_device's moments."""
-    import torch
-    if pl.dim() != 2 or pl.dtype not in (torch.float32, torch.float64):
-        raise ValueError("pl must be a 2-D float32/float64 tensor")
-    rows, ld = pl.shape
-    interp = obs_hi is not None
-    _abi.check(_abi.lib().trpl_loglik_moments_from_pl_dev(
-        _chk(pl, pl.dtype, "pl"), pl.element_size(), rows, int(ld if ncol is None else ncol), ld,
-        _chk(obs, torch.float64, "obs"), _chk(obs_hi, torch.int32, "obs_hi") if interp else None,
-        _chk(obs_dx, torch.float64, "obs_dx") if interp else None, _chk(obs_h, torch.float64, "obs_h") if interp else None,
-        obs.shape[0], _chk(mag, torch.float64, "mag"), None if status is None else _chk(status, torch.int32, "status"),
-        None if P is None else _chk(P, torch.float64, "P"), None if sse is None else _chk(sse, torch.float64, "sse"),
-        None if esum is None else _chk(esum, torch.float64, "esum"), int(flags), _stream()))
+    _loglik_from_pl_dev("trpl_loglik_moments_from_pl_dev", pl, obs, mag, P, sse, obs_hi, obs_dx, obs_h, ncol, flags, status,
+                        esum=esum)
 
 
 def loglik_weighted_from_pl_device(pl, obs, wts, mag, P=None, sse=None, esum=None, obs_hi=None, obs_dx=None, obs_h=None,
                                    ncol=None, flags=0, status=None):
     """trpl_loglik_weighted_from_pl_dev: loglik_moments_from_pl_device with the weights wts (n_obs,) f64 of the
     observations: sse = sum w e^2, esum = sum w e per row."""
-    import torch
-    if pl.dim() != 2 or pl.dtype not in (torch.float32, torch.float64):
-        raise ValueError("pl must be a 2-D float32/float64 tensor")
-    if wts.shape != obs.shape:
-        raise ValueError("shape mismatch")
-    rows, ld = pl.shape
-    interp = obs_hi is not None
-    _abi.check(_abi.lib().trpl_loglik_weighted_from_pl_dev(
-        _chk(pl, pl.dtype, "pl"), pl.element_size(), rows, int(ld if ncol is None else ncol), ld,
-        _chk(obs, torch.float64, "obs"), _chk(wts, torch.float64, "wts"),
-        _chk(obs_hi, torch.int32, "obs_hi") if interp else None,
-        _chk(obs_dx, torch.float64, "obs_dx") if interp else None, _chk(obs_h, torch.float64, "obs_h") if interp else None,
-        obs.shape[0], _chk(mag, torch.float64, "mag"), None if status is None else _chk(status, torch.int32, "status"),
-        None if P is None else _chk(P, torch.float64, "P"), None if sse is None else _chk(sse, torch.float64, "sse"),
-        None if esum is None else _chk(esum, torch.float64, "esum"), int(flags), _stream()))
+    _loglik_from_pl_dev("trpl_loglik_weighted_from_pl_dev", pl, obs, mag, P, sse, obs_hi, obs_dx, obs_h, ncol, flags, status,
+                        wts=wts, esum=esum)
 
 
 def sse_accumulate_w_device(P, pl, values, wts, mag):
@@ -632,48 +613,16 @@ def solve_pl_snap_device(matPar, Length, Time, L, T, dN, plI, snap_steps, plN=No
                          iters_total=None, tol=7, MAX=10000, plT=1, flags=0):
     """trpl_solve_pl_snap_dev: solve_pl_device that also records the state at the time steps snap_steps
     (host sequence) into plN, plP (S, len(snap_steps), L) and plE (S, len(snap_steps), L+1), f64 tensors."""
-    import torch
-    S = matPar.shape[0]
-    steps = np.ascontiguousarray(snap_steps, dtype=np.int64)
-    n = len(steps)
-    if matPar.shape[1] != 12 or tuple(dN.shape) != (L,) or tuple(plI.shape) != (S, T // plT + 1):
-        raise ValueError("shape mismatch")
-    for t, w in ((plN, L), (plP, L), (plE, L + 1)):
-        if t is not None and tuple(t.shape) != (S, n, w):
-            raise ValueError("snapshot tensors must be (S, len(snap_steps), L) / (.., L+1)")
-    _abi.check(_abi.lib().trpl_solve_pl_snap_dev(
-        _chk(matPar, torch.float64, "matPar"), S, float(Length), float(Time), int(L), int(T), int(plT), int(tol),
-        int(MAX), _chk(dN, torch.float64, "dN"), _chk(plI, plI.dtype, "plI"), plI.element_size(), plI.shape[1],
-        None if status is None else _chk(status, torch.int32, "status"),
-        None if iters_total is None else _chk(iters_total, torch.int64, "iters_total"), _abi.ptr(steps), n,
-        None if plN is None else _chk(plN, torch.float64, "plN"), None if plP is None else _chk(plP, torch.float64, "plP"),
-        None if plE is None else _chk(plE, torch.float64, "plE"), int(flags), _stream()))
+    _solve_pl_dev("trpl_solve_pl_snap_dev", matPar, Length, Time, L, T, plI, status, iters_total, tol, MAX, plT, flags, dN=dN,
+                  snap=(snap_steps, plN, plP, plE))
 
 
 def solve_pl_resume_device(matPar, Length, Time, L, T, t0, resN, resP, resE, plI, snap_steps=(), plN=None, plP=None,
                            plE=None, status=None, iters_total=None, tol=7, MAX=10000, plT=1, flags=0):
     """trpl_solve_pl_resume_dev: continue at step t0 from the five raw time levels resN, resP (S, 5, L) and resE
     (S, 5, L+1), f64 tensors as recorded by solve_pl_snap_device(..., snap_steps=[t0-4 .. t0], flags=FLAG_SNAP_RAW)."""
-    import torch
-    S = matPar.shape[0]
-    steps = np.ascontiguousarray(snap_steps, dtype=np.int64)
-    n = len(steps)
-    if matPar.shape[1] != 12 or tuple(plI.shape) != (S, T // plT + 1):
-        raise ValueError("shape mismatch")
-    for t, w in ((resN, L), (resP, L), (resE, L + 1)):
-        if tuple(t.shape) != (S, 5, w):
-            raise ValueError("resume tensors must be (S, 5, L) / (S, 5, L+1)")
-    for t, w in ((plN, L), (plP, L), (plE, L + 1)):
-        if t is not None and tuple(t.shape) != (S, n, w):
-            raise ValueError("snapshot tensors must be (S, len(snap_steps), L) / (.., L+1)")
-    _abi.check(_abi.lib().trpl_solve_pl_resume_dev(
-        _chk(matPar, torch.float64, "matPar"), S, float(Length), float(Time), int(L), int(T), int(plT), int(tol),
-        int(MAX), int(t0), _chk(resN, torch.float64, "resN"), _chk(resP, torch.float64, "resP"),
-        _chk(resE, torch.float64, "resE"), _chk(plI, plI.dtype, "plI"), plI.element_size(), plI.shape[1],
-        None if status is None else _chk(status, torch.int32, "status"),
-        None if iters_total is None else _chk(iters_total, torch.int64, "iters_total"), _abi.ptr(steps) if n else None, n,
-        None if plN is None else _chk(plN, torch.float64, "plN"), None if plP is None else _chk(plP, torch.float64, "plP"),
-        None if plE is None else _chk(plE, torch.float64, "plE"), int(flags), _stream()))
+    _solve_pl_dev("trpl_solve_pl_resume_dev", matPar, Length, Time, L, T, plI, status, iters_total, tol, MAX, plT, flags,
+                  resume=(t0, resN, resP, resE), snap=(snap_steps, plN, plP, plE))
 
 
 class MultiDevice:

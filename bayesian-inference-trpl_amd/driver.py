@@ -7,6 +7,7 @@ Two paths compute the same P:
   * fused (`loglik`): one launch per experiment, PL never leaves the registers; usable when
     every observation time grid is a prefix of the simulation grid (the shipped example data).
 """
+import math
 import os
 import sys
 import time
@@ -243,101 +244,58 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
         | _abi.flag_bdf_order(bdf_order) | int(extra_flags) | (_abi.FLAG_PREDICT if predict else 0)
     sec = _abi.C.c_double(0.0)
     lib = _abi.lib()
-    if weights is not None:
-        import math
-        off = times is not None
+    weighted, cut, multi, off = weights is not None, sse_cut is not None, devices is not None, times is not None
+    entry = "trpl_loglik_weighted" if weighted else "trpl_loglik_moments" if moments else "trpl_loglik_cut" if cut \
+        else "trpl_loglik_multi" if multi else "trpl_loglik_obs" if off else "trpl_loglik"
+    own = {}                                       # the entry point's own outputs, as info receives them
+    if weighted or moments:
         esum = np.zeros((Cn, S))
-        wsum = np.array([math.fsum(w_mat[c, :n_obs[c]]) for c in range(Cn)])
-        _abi.check(lib.trpl_loglik_weighted(
-            _abi.ptr(X), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol), int(MAX), _abi.ptr(ini),
-            _abi.ptr(obs_mat), _abi.ptr(w_mat), _abi.ptr(hi_mat) if off else None, _abi.ptr(dx_mat) if off else None,
-            _abi.ptr(h_mat) if off else None, obs_ld, _abi.ptr(n_obs), _abi.ptr(P), _abi.ptr(sse), _abi.ptr(esum),
-            _abi.ptr(status), _abi.ptr(iters), _abi.ptr(floor_col), flags, int(device), _abi.C.byref(sec)))
-        if info is not None:
-            info.update(sse=sse, esum=esum, wsum=wsum, status=status, iters_total=iters, floor_col=floor_col,
-                        seconds=sec.value, P=P)
-        if mag_grid is not None:
-            offs = np.ascontiguousarray(mag_grid, dtype=np.float64).ravel()
-            Pm = np.zeros((len(offs), S)) if P_out is None else P_out
-            if not (Pm.dtype == np.float64 and Pm.flags.c_contiguous and Pm.shape == (len(offs), S)):
-                raise ValueError("P must be a contiguous float64 array of shape (len(mag_grid), S)")
-            _abi.check(lib.trpl_mag_grid_w(_abi.ptr(sse), _abi.ptr(esum), _abi.ptr(wsum), S, Cn, _abi.ptr(offs), len(offs), _abi.ptr(Pm)))
-            return Pm
-        if mag_profile:
-            per_curve = mag_profile == "per_curve"
-            Pp = np.zeros(S) if P_out is None else P_out
-            if not (Pp.dtype == np.float64 and Pp.flags.c_contiguous and Pp.shape == (S,)):
-                raise ValueError("P must be a contiguous float64 array of shape (S,)")
-            best = np.zeros((Cn, S) if per_curve else S)
-            _abi.check(lib.trpl_mag_profile_w(_abi.ptr(sse), _abi.ptr(esum), _abi.ptr(wsum), S, Cn,
-                                              _abi.MAG_PER_CURVE if per_curve else 0, _abi.ptr(best), _abi.ptr(Pp)))
-            return best, Pp
-        return P
-    if moments:
-        off = times is not None
-        esum = np.zeros((Cn, S))
-        _abi.check(lib.trpl_loglik_moments(
-            _abi.ptr(X), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol), int(MAX), _abi.ptr(ini),
-            _abi.ptr(obs_mat), _abi.ptr(hi_mat) if off else None, _abi.ptr(dx_mat) if off else None,
-            _abi.ptr(h_mat) if off else None, obs_ld, _abi.ptr(n_obs), _abi.ptr(P), _abi.ptr(sse), _abi.ptr(esum),
-            _abi.ptr(status), _abi.ptr(iters), _abi.ptr(floor_col), flags, int(device), _abi.C.byref(sec)))
-        if info is not None:
-            info.update(sse=sse, esum=esum, status=status, iters_total=iters, floor_col=floor_col, seconds=sec.value, P=P)
-        if mag_grid is not None:
-            offs = np.ascontiguousarray(mag_grid, dtype=np.float64).ravel()
-            Pm = np.zeros((len(offs), S)) if P_out is None else P_out
-            if not (Pm.dtype == np.float64 and Pm.flags.c_contiguous and Pm.shape == (len(offs), S)):
-                raise ValueError("P must be a contiguous float64 array of shape (len(mag_grid), S)")
-            _abi.check(lib.trpl_mag_grid(_abi.ptr(sse), _abi.ptr(esum), _abi.ptr(n_obs), S, Cn, _abi.ptr(offs), len(offs), _abi.ptr(Pm)))
-            return Pm
-        per_curve = mag_profile == "per_curve"
-        Pp = np.zeros(S) if P_out is None else P_out
-        if not (Pp.dtype == np.float64 and Pp.flags.c_contiguous and Pp.shape == (S,)):
-            raise ValueError("P must be a contiguous float64 array of shape (S,)")
-        best = np.zeros((Cn, S) if per_curve else S)
-        _abi.check(lib.trpl_mag_profile(_abi.ptr(sse), _abi.ptr(esum), _abi.ptr(n_obs), S, Cn,
-                                        _abi.MAG_PER_CURVE if per_curve else 0, _abi.ptr(best), _abi.ptr(Pp)))
-        return best, Pp
-    if sse_cut is not None:
-        off = times is not None
-        cut_col = np.full((Cn, S), -1, dtype=np.int32)
-        _abi.check(lib.trpl_loglik_cut(
-            _abi.ptr(X), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol), int(MAX), _abi.ptr(ini),
-            _abi.ptr(obs_mat), _abi.ptr(hi_mat) if off else None, _abi.ptr(dx_mat) if off else None,
-            _abi.ptr(h_mat) if off else None, obs_ld, _abi.ptr(n_obs), sse_cut, _abi.ptr(P), _abi.ptr(sse), _abi.ptr(cut_col),
-            _abi.ptr(status), _abi.ptr(iters), _abi.ptr(floor_col), flags, int(device), _abi.C.byref(sec)))
-        if info is not None:
-            info.update(sse=sse, status=status, iters_total=iters, floor_col=floor_col, seconds=sec.value, cut_col=cut_col,
-                        cut_fraction=float(np.mean(cut_col >= 0)) if cut_col.size else 0.0)
-        return P
-    if devices is not None:
+        own.update(esum=esum, P=P)                 # P: the one-offset likelihood trpl_loglik would return
+    if weighted:
+        own["wsum"] = wsum = np.array([math.fsum(w_mat[c, :n_obs[c]]) for c in range(Cn)])
+    if cut:
+        own["cut_col"] = cut_col = np.full((Cn, S), -1, dtype=np.int32)
+    if multi:
         dev = None if isinstance(devices, str) else np.ascontiguousarray(devices, dtype=np.int32)
         if isinstance(devices, str) and devices != "all":
             raise ValueError("devices must be None, 'all' or a list of device ordinals")
         if dev is not None and (dev.ndim != 1 or len(dev) < 1):
             raise ValueError("devices must name at least one device")
-        off = times is not None
-        rc = lib.trpl_loglik_multi(_abi.ptr(X), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT),
-                                   int(tol), int(MAX), _abi.ptr(ini), _abi.ptr(obs_mat),
-                                   _abi.ptr(hi_mat) if off else None, _abi.ptr(dx_mat) if off else None,
-                                   _abi.ptr(h_mat) if off else None, obs_ld, _abi.ptr(n_obs), _abi.ptr(P),
-                                   _abi.ptr(sse), _abi.ptr(status), _abi.ptr(iters), _abi.ptr(floor_col), flags,
-                                   None if dev is None else _abi.ptr(dev), 0 if dev is None else len(dev),
-                                   _abi.C.byref(sec))
-    elif times is None:
-        rc = lib.trpl_loglik(_abi.ptr(X), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(plT), int(tol),
-                             int(MAX), _abi.ptr(ini), _abi.ptr(obs_mat), obs_ld, _abi.ptr(n_obs), _abi.ptr(P),
-                             _abi.ptr(sse), _abi.ptr(status), _abi.ptr(iters), _abi.ptr(floor_col), flags, int(device),
-                             _abi.C.byref(sec))
-    else:
-        rc = lib.trpl_loglik_obs(_abi.ptr(X), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T), int(tol), int(MAX),
-                                 _abi.ptr(ini), _abi.ptr(obs_mat), _abi.ptr(hi_mat), _abi.ptr(dx_mat), _abi.ptr(h_mat),
-                                 obs_ld, _abi.ptr(n_obs), _abi.ptr(P), _abi.ptr(sse), _abi.ptr(status),
-                                 _abi.ptr(iters), _abi.ptr(floor_col), flags, int(device), _abi.C.byref(sec))
-    _abi.check(rc)
+    # The call, built once; an entry point's own arguments sit where include/trpl.h puts them: no plT in trpl_loglik_obs, wts
+    # after obs, no brackets in trpl_loglik, sse_cut before P, esum or cut_col after sse, the device list for the device.
+    head = [_abi.ptr(X), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T)] \
+        + ([] if entry == "trpl_loglik_obs" else [int(plT)]) + [int(tol), int(MAX), _abi.ptr(ini)]
+    brackets = [_abi.ptr(hi_mat), _abi.ptr(dx_mat), _abi.ptr(h_mat)] if off else [None, None, None]
+    observed = [_abi.ptr(obs_mat)] + ([_abi.ptr(w_mat)] if weighted else []) + ([] if entry == "trpl_loglik" else brackets) \
+        + [obs_ld, _abi.ptr(n_obs)]
+    outputs = ([sse_cut] if cut else []) + [_abi.ptr(P), _abi.ptr(sse)] + ([_abi.ptr(esum)] if "esum" in own else []) \
+        + ([_abi.ptr(cut_col)] if cut else []) + [_abi.ptr(status), _abi.ptr(iters), _abi.ptr(floor_col)]
+    tail = [flags] + ([_abi.ptr(dev), 0 if dev is None else len(dev)] if multi else [int(device)]) + [_abi.C.byref(sec)]
+    _abi.check(getattr(lib, entry)(*head, *observed, *outputs, *tail))
+    if cut:
+        own["cut_fraction"] = float(np.mean(cut_col >= 0)) if cut_col.size else 0.0
     if info is not None:
-        info.update(sse=sse, status=status, iters_total=iters, floor_col=floor_col, seconds=sec.value)
-    return P
+        info.update(sse=sse, status=status, iters_total=iters, floor_col=floor_col, seconds=sec.value, **own)
+    if not moments:
+        return P
+    # the likelihood over the magnitude offset, from the moments: n_obs, or the weighted entry points with wsum in its place
+    per_curve, w = (wsum, "_w") if weighted else (n_obs, "")
+    if mag_grid is not None:
+        offs = np.ascontiguousarray(mag_grid, dtype=np.float64).ravel()
+        Pm = np.zeros((len(offs), S)) if P_out is None else P_out
+        if not (Pm.dtype == np.float64 and Pm.flags.c_contiguous and Pm.shape == (len(offs), S)):
+            raise ValueError("P must be a contiguous float64 array of shape (len(mag_grid), S)")
+        _abi.check(getattr(lib, "trpl_mag_grid" + w)(_abi.ptr(sse), _abi.ptr(esum), _abi.ptr(per_curve), S, Cn, _abi.ptr(offs),
+                                                     len(offs), _abi.ptr(Pm)))
+        return Pm
+    best_per_curve = mag_profile == "per_curve"
+    Pp = np.zeros(S) if P_out is None else P_out
+    if not (Pp.dtype == np.float64 and Pp.flags.c_contiguous and Pp.shape == (S,)):
+        raise ValueError("P must be a contiguous float64 array of shape (S,)")
+    best = np.zeros((Cn, S) if best_per_curve else S)
+    _abi.check(getattr(lib, "trpl_mag_profile" + w)(_abi.ptr(sse), _abi.ptr(esum), _abi.ptr(per_curve), S, Cn,
+                                                    _abi.MAG_PER_CURVE if best_per_curve else 0, _abi.ptr(best), _abi.ptr(Pp)))
+    return best, Pp
 
 
 def next_cut(margin, best_total):
@@ -368,9 +326,6 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
     returns the first moment of the errors (trpl_loglik_moments_from_pl_dev), and after a block's last curve
     trpl_mag_grid_dev fills the M rows of every experiment.  weighted (gpu_info["weighted"]): every pass is
     trpl_loglik_weighted_from_pl_dev with the weights of the experiment's uncertainty column (and trpl_mag_grid_w_dev)."""
-    import math
-    import time
-
     import torch
 
     from . import device as tdev
@@ -380,7 +335,10 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
     flags = _abi.FLAG_NORMALIZE if normalize else 0
     with torch.cuda.device(dev):
         ini_d = torch.from_numpy(np.ascontiguousarray(init_params, dtype=np.float64)).to(dev)
-        # per (experiment, curve): observations and, off the grid, their brackets -- staged once
+        # per (experiment, curve), staged once: the keywords of its pass over a PL block -- observations, off the grid their
+        # brackets, weights -- and what trpl_mag_grid[_w]_dev takes for the curve, n_obs or the sum of the weights
+        def to_dev(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         staged = []
         for exp in e_data:
             per_curve = []
@@ -388,17 +346,18 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
                 t = np.asarray(exp[0][c], dtype=float)
                 o = np.asarray(exp[1][c], dtype=float)
                 w = weights_from_uncertainty(exp[2][c]) if weighted else None
-                if observations_on_grid(t, sim_t, literal):                   # bayeslib.py:182-183, and prefixes of the grid (below)
-                    per_curve.append((torch.from_numpy(np.ascontiguousarray(o)).to(dev), None))
-                else:
+                kw = {}
+                if not observations_on_grid(t, sim_t, literal):               # bayeslib.py:182-183, and prefixes of the grid (below)
                     order = np.argsort(t, kind="stable")
-                    hi, dx, h = bracket_times(sim_t, t[order])
-                    per_curve.append((torch.from_numpy(np.ascontiguousarray(o[order])).to(dev),
-                                      tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (hi, dx, h))))
-                    w = w[order] if weighted else None
-                if weighted:                                                  # (obs, brackets, weights, their sum)
-                    per_curve[-1] += (torch.from_numpy(np.ascontiguousarray(w)).to(dev), math.fsum(w))
+                    o, w = o[order], (w[order] if weighted else None)
+                    kw = dict(zip(("obs_hi", "obs_dx", "obs_h"), map(to_dev, bracket_times(sim_t, t[order]))))
+                kw["obs"] = to_dev(o)
+                if weighted:
+                    kw["wts"] = to_dev(w)
+                per_curve.append((kw, math.fsum(w) if weighted else len(o)))
             staged.append(per_curve)
+        pass_name = "loglik_weighted_from_pl_device" if weighted else \
+            "loglik_moments_from_pl_device" if mag_grid is not None else "loglik_from_pl_device"
         for blk in range(gpu_id * group, len(X), num_gpus * group):           # :131
             size = min(group, len(X) - blk)
             X_d = torch.from_numpy(np.ascontiguousarray(X[blk:blk + size], dtype=np.float64)).to(dev)
@@ -421,35 +380,15 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
                 torch.cuda.synchronize(dev)
                 t1 = time.perf_counter()
                 for e, per_curve in enumerate(staged):                        # :171
-                    o_d, br = per_curve[c][:2]
-                    if weighted:
-                        tdev.loglik_weighted_from_pl_device(pl_d, o_d, per_curve[c][2], mag_d,
-                                                            P=None if mag_grid is not None else P_d[e],
-                                                            sse=None if mag_grid is None else sse_d[e, c],
-                                                            esum=None if mag_grid is None else esum_d[e, c], flags=flags,
-                                                            status=st_d, obs_hi=None if br is None else br[0],
-                                                            obs_dx=None if br is None else br[1],
-                                                            obs_h=None if br is None else br[2])
-                        continue
-                    if mag_grid is not None:
-                        tdev.loglik_moments_from_pl_device(pl_d, o_d, mag_d, sse=sse_d[e, c], esum=esum_d[e, c], flags=flags,
-                                                           status=st_d, obs_hi=None if br is None else br[0],
-                                                           obs_dx=None if br is None else br[1],
-                                                           obs_h=None if br is None else br[2])
-                        continue
-                    tdev.loglik_from_pl_device(pl_d, o_d, mag_d, P=P_d[e], flags=flags, status=st_d,
-                                               obs_hi=None if br is None else br[0],
-                                               obs_dx=None if br is None else br[1],
-                                               obs_h=None if br is None else br[2])
+                    out = {"P": P_d[e]} if mag_grid is None else {"sse": sse_d[e, c], "esum": esum_d[e, c]}
+                    getattr(tdev, pass_name)(pl_d, mag=mag_d, flags=flags, status=st_d, **per_curve[c][0], **out)
                 torch.cuda.synchronize(dev)
                 solver_time[gpu_id] += t1 - t0
                 err_sq_time[gpu_id] += time.perf_counter() - t1
             if mag_grid is not None:
+                mag_grid_device = tdev.mag_grid_w_device if weighted else tdev.mag_grid_device
                 for e, per_curve in enumerate(staged):
-                    if weighted:
-                        tdev.mag_grid_w_device(sse_d[e], esum_d[e], [per_curve[c][3] for c in range(num_curves)], mag_grid, P_d[e])
-                        continue
-                    tdev.mag_grid_device(sse_d[e], esum_d[e], [len(per_curve[c][0]) for c in range(num_curves)], mag_grid, P_d[e])
+                    mag_grid_device(sse_d[e], esum_d[e], [n for _, n in per_curve], mag_grid, P_d[e])
                 P.reshape(len(e_data), M, S_all)[:, :, blk:blk + size] = P_d.cpu().numpy()
                 continue
             P[:, blk:blk + size] = P_d.cpu().numpy()
@@ -563,13 +502,15 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
             for e, exp in enumerate(e_data):
                 on_grid = fused_entry_point(exp[0], sim_t, num_curves, literal) == "trpl_loglik"
                 info = {}
+                args = (X[blk:blk + size], init_params, thicknesses, Time, L, T, [exp[1][c] for c in range(num_curves)])
+                common = dict(tol=sim_params[6], MAX=sim_params[7], pl_f32=(pl_dtype == np.float32), normalize=NORMALIZE,
+                              device=device, info=info, predict=predict,
+                              times=None if on_grid else [exp[0][c] for c in range(num_curves)])
+                if weighted:
+                    common["weights"] = [weights_from_uncertainty(exp[2][c]) for c in range(num_curves)]
                 if cut_margin is not None:         # one experiment, one device (checked above)
                     level = next_cut(cut_margin, best_total)
-                    loglik(X[blk:blk + size], init_params, thicknesses, Time, L, T,
-                           [exp[1][c] for c in range(num_curves)], tol=sim_params[6], MAX=sim_params[7],
-                           P=P[e, blk:blk + size], pl_f32=(pl_dtype == np.float32), normalize=NORMALIZE,
-                           device=device, info=info, times=None if on_grid else [exp[0][c] for c in range(num_curves)],
-                           predict=predict, sse_cut=level)
+                    loglik(*args, P=P[e, blk:blk + size], sse_cut=level, **common)
                     solver_time[gpu_id] += info["seconds"]
                     # a cut sample's reported total is above the level it was cut at, hence above the minimum so far:
                     # it never lowers it; NaN totals are skipped
@@ -581,23 +522,14 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
                         gpu_info["cut_log"].append({"block": blk, "sse_cut": level, "cut_fraction": info["cut_fraction"],
                                                     "iters_total": int(info["iters_total"].sum())})
                     continue
-                wkw = {"weights": [weights_from_uncertainty(exp[2][c]) for c in range(num_curves)]} if weighted else {}
                 if mag_grid is not None:
                     Pe = P[e].reshape(len(mag_grid), len(X))
                     Pm = np.ascontiguousarray(Pe[:, blk:blk + size])
-                    loglik(X[blk:blk + size], init_params, thicknesses, Time, L, T,
-                           [exp[1][c] for c in range(num_curves)], tol=sim_params[6], MAX=sim_params[7], P=Pm,
-                           pl_f32=(pl_dtype == np.float32), normalize=NORMALIZE, device=device, info=info,
-                           times=None if on_grid else [exp[0][c] for c in range(num_curves)], predict=predict,
-                           mag_grid=mag_grid, **wkw)
+                    loglik(*args, P=Pm, mag_grid=mag_grid, **common)
                     Pe[:, blk:blk + size] = Pm
                     solver_time[gpu_id] += info["seconds"]
                     continue
-                loglik(X[blk:blk + size], init_params, thicknesses, Time, L, T,
-                       [exp[1][c] for c in range(num_curves)], tol=sim_params[6], MAX=sim_params[7],
-                       P=P[e, blk:blk + size], pl_f32=(pl_dtype == np.float32), normalize=NORMALIZE,
-                       device=device, info=info, devices=gpu_info.get("devices"), bundle=_bundle_of(gpu_info, L),
-                       times=None if on_grid else [exp[0][c] for c in range(num_curves)], predict=predict, **wkw)
+                loglik(*args, P=P[e, blk:blk + size], devices=gpu_info.get("devices"), bundle=_bundle_of(gpu_info, L), **common)
                 solver_time[gpu_id] += info["seconds"]
         return
 
