@@ -173,6 +173,11 @@ SIGNATURES = {
     "trpl_posterior_tf_scan_workspace": [_i64, _i32, _i32],
     "trpl_posterior_tf_scan": [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _pd],
     "trpl_posterior_tf_scan_dev": [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "trpl_posterior_weights_lr": [_vp, _vp, _i64, _f64, _vp, _vp, _i32, _pd],
+    "trpl_posterior_weights_lr_dev": [_vp, _vp, _i64, _f64, _vp, _vp, _vp, _i64, _vp],
+    "trpl_posterior_tf_scan_lr_workspace": [_i64, _i32, _i32],
+    "trpl_posterior_tf_scan_lr": [_vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _pd],
+    "trpl_posterior_tf_scan_lr_dev": [_vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "trpl_predictive_state_bytes": [_i64],
     "trpl_predictive_workspace_bytes": [_i64, _i64, _i32],
     "trpl_predictive_chunks": [_i64, _i64, _i32],
@@ -327,7 +332,8 @@ def lib():
             fn = getattr(dll, name)
             fn.argtypes = argtypes
             fn.restype = C.c_char_p if name == "trpl_last_error" else (
-                C.c_int64 if name in ("trpl_posterior_workspace_bytes", "trpl_posterior_tf_scan_workspace", "trpl_shard_of",
+                C.c_int64 if name in ("trpl_posterior_workspace_bytes", "trpl_posterior_tf_scan_workspace",
+                                     "trpl_posterior_tf_scan_lr_workspace", "trpl_shard_of",
                                      "trpl_predictive_state_bytes", "trpl_predictive_workspace_bytes",
                                      "trpl_quantiles_stage_rows", "trpl_corner_workspace_bytes", "trpl_refine_chunk_rows",
                                      "trpl_refine_tile_parents", "trpl_refine_workspace_bytes") else C.c_int)

@@ -282,6 +282,49 @@ def posterior_tf_scan_device(LL, tfs, stats, workspace, V=None, mean=None, var=N
         workspace.numel() * 8, _stream()))
 
 
+def posterior_weights_lr_device(LL, log_ratio, tf, W, workspace, stats=None):
+    """W <- the normalised weights exp(LL / tf - log_ratio) of a refined set (trpl_posterior_weights_lr_dev): LL, log_ratio,
+    W (S,) f64; stats (2,) f64 optional {max of LL / tf - log_ratio, raw sum}; workspace as posterior_weights_device.  With
+    log_ratio = +0.0 everywhere the bits of posterior_weights_device."""
+    import torch
+    if LL.shape != W.shape or LL.shape != log_ratio.shape or LL.dim() != 1:
+        raise ValueError("LL, log_ratio and W must be (S,)")
+    _abi.check(_abi.lib().trpl_posterior_weights_lr_dev(
+        _chk(LL, torch.float64, "LL"), _chk(log_ratio, torch.float64, "log_ratio"), LL.shape[0], float(tf),
+        _chk(W, torch.float64, "W"), _opt(stats, torch.float64, "stats"), _chk(workspace, torch.float64, "workspace"),
+        workspace.numel() * 8, _stream()))
+
+
+def posterior_tf_scan_lr_workspace(S, D, K):
+    """A workspace tensor for posterior_tf_scan_lr_device with S samples, D columns and K temperatures."""
+    import torch
+    n = int(_abi.lib().trpl_posterior_tf_scan_lr_workspace(int(S), int(D), int(K)))
+    if n <= 0:
+        raise ValueError("S, D, K = %r are outside what trpl_posterior_tf_scan_lr accepts" % ((S, D, K),))
+    return torch.empty(n // 8, dtype=torch.float64, device="cuda")
+
+
+def posterior_tf_scan_lr_device(LL, log_ratio, tfs, stats, workspace, V=None, mean=None, var=None, Q=None):
+    """posterior_tf_scan_device with the proposal log-ratio log_ratio (S,) kept beside LL (trpl_posterior_tf_scan_lr_dev):
+    stats (K, 6) = [max, raw sum, sum W, sum W^2, count, ess]; with V (D, S) also mean, var, Q (K, D), row k being the bits
+    of posterior_weights_lr_device(LL, log_ratio, tfs[k]) + posterior_moments_device."""
+    import torch
+    S, K = LL.shape[0], tfs.shape[0]
+    D = 0 if V is None else V.shape[0]
+    if LL.dim() != 1 or tuple(log_ratio.shape) != (S,) or tfs.dim() != 1 or tuple(stats.shape) != (K, 6) \
+            or (D and tuple(V.shape) != (D, S)):
+        raise ValueError("shape mismatch")
+    outs = []
+    for t, name in ((mean, "mean"), (var, "var"), (Q, "Q")):
+        if D and (t is None or tuple(t.shape) != (K, D)):
+            raise ValueError("%s must be (K, D)" % name)
+        outs.append(_chk(t, torch.float64, name) if D else None)
+    _abi.check(_abi.lib().trpl_posterior_tf_scan_lr_dev(
+        _chk(LL, torch.float64, "LL"), _chk(log_ratio, torch.float64, "log_ratio"), S, _chk(V, torch.float64, "V") if D else None,
+        D, _chk(tfs, torch.float64, "tfs"), K, _chk(stats, torch.float64, "stats"), outs[0], outs[1], outs[2],
+        _chk(workspace, torch.float64, "workspace"), workspace.numel() * 8, _stream()))
+
+
 # ---- posterior-predictive band, device-resident (trpl_predictive_*_dev) ----
 def predictive_state(ncol):
     """The running state (5, ncol) f64 of a predictive band over ncol time columns: sw, mean, M2, lo, hi per column.

@@ -29,16 +29,30 @@ def filter_nan(X, LL):
     return np.asarray(X)[keep], LL[keep]
 
 
-def weights(LL, tf=1.0, device=0, info=None):
-    """normalize(LL / tf): posterior weights that sum to 1 (NaN stays NaN, -inf gives 0)."""
+def _log_ratio(log_ratio, S):
+    lnr = _f64(log_ratio)
+    if lnr.shape != (S,):
+        raise ValueError("log_ratio must have one entry per sample")
+    return lnr
+
+
+def weights(LL, tf=1.0, device=0, info=None, log_ratio=None):
+    """normalize(LL / tf): posterior weights that sum to 1 (NaN stays NaN, -inf gives 0).  log_ratio (S,): ln r(u) of a refined
+    set (refine.Population.log_ratio), kept beside LL -- the weights of exp(LL / tf) / r (trpl_posterior_weights_lr); a NaN in
+    either gives NaN, +inf in log_ratio gives 0; info["max"] is then the largest LL / tf - log_ratio."""
     LL = _f64(LL)
     if LL.ndim != 1:
         raise ValueError("LL must be one-dimensional")
     W = np.empty_like(LL)
     stats = np.zeros(2)
     sec = _abi.C.c_double(0.0)
-    _abi.check(_abi.lib().trpl_posterior_weights(_abi.ptr(LL), LL.size, float(tf), _abi.ptr(W), _abi.ptr(stats),
-                                                 int(device), _abi.C.byref(sec)))
+    if log_ratio is None:
+        _abi.check(_abi.lib().trpl_posterior_weights(_abi.ptr(LL), LL.size, float(tf), _abi.ptr(W), _abi.ptr(stats),
+                                                     int(device), _abi.C.byref(sec)))
+    else:
+        lnr = _log_ratio(log_ratio, LL.size)
+        _abi.check(_abi.lib().trpl_posterior_weights_lr(_abi.ptr(LL), _abi.ptr(lnr), LL.size, float(tf), _abi.ptr(W),
+                                                        _abi.ptr(stats), int(device), _abi.C.byref(sec)))
     if info is not None:
         info.update(max=stats[0], raw_sum=stats[1], seconds=sec.value)
     return W
@@ -238,12 +252,17 @@ def summarize(columns, P, device=0):
 TF_SCAN_POINTS = _abi.TF_SCAN_MAX          # temperatures per scan of the bracketed search
 
 
-def tf_scan(LL, tfs, V=None, device=0):
+def tf_scan(LL, tfs, V=None, device=0, log_ratio=None):
     """The posterior at every temperature of `tfs` (at most TF_SCAN_MAX) from one scan of the samples.
 
     Returns dict(stats (K, 4) = [nanmax(LL / tf), raw normalising sum, sum W^2, count of non-NaN LL], mean (K, D),
     var (K, D), Q (K, D) = sqrt(sum W^2 * var), the objective of tf_driver), row k being bit for bit what
-    weights(LL, tfs[k]) followed by moments(V, W) gives.  V is (D, S) or (S,); None: stats only (D = 0)."""
+    weights(LL, tfs[k]) followed by moments(V, W) gives.  V is (D, S) or (S,); None: stats only (D = 0).
+
+    log_ratio (S,): ln r(u) of a refined set, kept beside LL (trpl_posterior_tf_scan_lr).  Row k is then the bits of
+    weights(LL, tfs[k], log_ratio=log_ratio) followed by moments(V, W), stats is (K, 6) = [max of LL / tf - log_ratio, raw
+    normalising sum, sum W, sum W^2, count of samples with neither NaN, ess] and "ess" = stats[:, 5] = (sum W)^2 / sum W^2,
+    the effective sample size at each temperature (NaN where a weight is NaN)."""
     LL = _f64(LL)
     tfs = np.atleast_1d(_f64(tfs))
     if LL.ndim != 1 or tfs.ndim != 1:
@@ -257,10 +276,18 @@ def tf_scan(LL, tfs, V=None, device=0):
     if S != LL.size:
         raise ValueError("V must have one column entry per sample")
     K = tfs.size
-    out = {"stats": np.zeros((K, 4)), "mean": np.zeros((K, D)), "var": np.zeros((K, D)), "Q": np.zeros((K, D))}
-    _abi.check(_abi.lib().trpl_posterior_tf_scan(_abi.ptr(LL), S, _abi.ptr(V) if D else None, D, _abi.ptr(tfs), K,
-                                                 _abi.ptr(out["stats"]), _abi.ptr(out["mean"]), _abi.ptr(out["var"]),
-                                                 _abi.ptr(out["Q"]), int(device), None))
+    out = {"stats": np.zeros((K, 4 if log_ratio is None else 6)), "mean": np.zeros((K, D)), "var": np.zeros((K, D)),
+           "Q": np.zeros((K, D))}
+    if log_ratio is None:
+        _abi.check(_abi.lib().trpl_posterior_tf_scan(_abi.ptr(LL), S, _abi.ptr(V) if D else None, D, _abi.ptr(tfs), K,
+                                                     _abi.ptr(out["stats"]), _abi.ptr(out["mean"]), _abi.ptr(out["var"]),
+                                                     _abi.ptr(out["Q"]), int(device), None))
+        return out
+    lnr = _log_ratio(log_ratio, S)
+    _abi.check(_abi.lib().trpl_posterior_tf_scan_lr(_abi.ptr(LL), _abi.ptr(lnr), S, _abi.ptr(V) if D else None, D, _abi.ptr(tfs),
+                                                    K, _abi.ptr(out["stats"]), _abi.ptr(out["mean"]), _abi.ptr(out["var"]),
+                                                    _abi.ptr(out["Q"]), int(device), None))
+    out["ess"] = out["stats"][:, 5].copy()
     return out
 
 
@@ -311,7 +338,7 @@ def _bracket_search(objective, lo, hi, k, rtol):
     return tf, val, {"scans": scans, "rounds": rounds, "lo": lo, "hi": hi, "at_edge": at_edge}
 
 
-def _find_best_tf_columns(V, LL, u0, device, span, rtol):
+def _find_best_tf_columns(V, LL, u0, device, span, rtol, log_ratio=None):
     """find_best_tf of every row of V (D, S): (tf (D,), Q (D,), info of _bracket_search + device_scans)."""
     V, LL = _f64(V), _f64(LL)
     D = V.shape[0]
@@ -322,7 +349,7 @@ def _find_best_tf_columns(V, LL, u0, device, span, rtol):
         inv = inv.reshape(tfs.shape)
         Q = np.empty((uniq.size, D))
         for a in range(0, uniq.size, _abi.TF_SCAN_MAX):          # one device scan serves all D columns
-            Q[a:a + _abi.TF_SCAN_MAX] = tf_scan(LL, uniq[a:a + _abi.TF_SCAN_MAX], V, device=device)["Q"]
+            Q[a:a + _abi.TF_SCAN_MAX] = tf_scan(LL, uniq[a:a + _abi.TF_SCAN_MAX], V, device=device, log_ratio=log_ratio)["Q"]
             device_scans[0] += 1
         return Q[inv, np.arange(D)[None, :]]
 
@@ -334,36 +361,98 @@ def _find_best_tf_columns(V, LL, u0, device, span, rtol):
     return tf, q, info
 
 
-def find_best_tf(xi, P, u0, device=0, span=1e4, rtol=1e-6, info=None):
+def find_best_tf(xi, P, u0, device=0, span=1e4, rtol=1e-6, info=None, log_ratio=None):
     """utils.py:181-183, same positional arguments (xi the parameter's values, P the log-likelihoods, u0 the starting
     temperature) and return value (tf, Q) with Q = -tf_driver(ln tf, xi, P) = sqrt(sum W^2 * weighted variance),
     W = normalize(P / tf).  Instead of fmin from ln u0: the deterministic search of _bracket_search over
     [u0 / span, u0 * span] with TF_SCAN_POINTS temperatures per device scan (tf_scan), until the bracket's relative width
     is at most rtol.  info receives scans, lo, hi (the final bracket) and at_edge: True when the largest Q of the first
-    scan sat on an end of the outer bracket (the returned tf is then the best of that side, not a located maximum)."""
+    scan sat on an end of the outer bracket (the returned tf is then the best of that side, not a located maximum).
+    log_ratio (S,): over a refined set, ln r(u) beside the log-likelihoods P; W is then tf_scan's with that ratio."""
     xi = _f64(xi)
     if xi.ndim != 1:
         raise ValueError("xi must be one-dimensional")
-    tf, q, inf = _find_best_tf_columns(xi[None, :], P, u0, device, span, rtol)
+    tf, q, inf = _find_best_tf_columns(xi[None, :], P, u0, device, span, rtol, log_ratio)
     if info is not None:
         info.update(scans=inf["scans"], device_scans=inf["device_scans"], lo=float(inf["lo"][0]), hi=float(inf["hi"][0]),
                     at_edge=bool(inf["at_edge"][0]))
     return float(tf[0]), float(q[0])
 
 
-def calc_max_uncertainty(columns, LL, num_observations, device=0, span=1e4, rtol=1e-6, info=None):
+def calc_max_uncertainty(columns, LL, num_observations, device=0, span=1e4, rtol=1e-6, info=None, log_ratio=None):
     """LikelihoodData.calc_max_uncertainty (utils.py:128-133): dict param -> (tf, Q) = find_best_tf(columns[param], LL,
     num_observations / 2000), bit for bit.  The columns share the rounds and the device scans: the first round is one scan
     for all of them (the same outer bracket), a later round scans its distinct temperatures once for all D columns
     (each column keeps its own bracket, so that is up to one scan per distinct bracket).  info receives scans (rounds: those
-    of a single find_best_tf), device_scans, and per-parameter dicts lo, hi, at_edge."""
+    of a single find_best_tf), device_scans, and per-parameter dicts lo, hi, at_edge.  log_ratio: as in find_best_tf."""
     names = list(columns)
     V = np.stack([_f64(columns[k]) for k in names])
-    tf, q, inf = _find_best_tf_columns(V, LL, float(num_observations) / 2000.0, device, span, rtol)
+    tf, q, inf = _find_best_tf_columns(V, LL, float(num_observations) / 2000.0, device, span, rtol, log_ratio)
     if info is not None:
         info.update(scans=inf["scans"], device_scans=inf["device_scans"], lo=dict(zip(names, inf["lo"].tolist())),
                     hi=dict(zip(names, inf["hi"].tolist())), at_edge=dict(zip(names, inf["at_edge"].tolist())))
     return {n: (float(tf[i]), float(q[i])) for i, n in enumerate(names)}
+
+
+def _ess_search(objective, target, lo, hi, k, rtol):
+    """Deterministic search on a grid for the smallest temperature whose effective sample size reaches `target`.
+
+    objective(tfs) takes a (k,) array of temperatures and returns their (k,) effective sample sizes.  Every round lays k points,
+    equally spaced in ln tf and including both ends, over [lo, hi] and takes the SMALLEST grid temperature whose value is
+    >= target (a NaN never is).  The effective sample size need not be monotone in tf when the proposal ratio varies, so the
+    rule is stated on the grid and not as a root: of several crossings the lowest one the grid sees is followed.  The new
+    bracket is that point and its lower neighbour; rounds repeat until hi / lo - 1 <= rtol.  A round divides ln(hi / lo) by
+    k - 1, so rounds = max(1, ceil(ln(ln(hi / lo) / ln(1 + rtol)) / ln(k - 1))).  k >= 4.
+
+    Returns (tf, ess, info): tf is the upper end of the final bracket, a grid point whose value reached the target; info =
+    dict(scans, lo, hi, at_edge).  at_edge is "hi" when no point of the first grid reaches the target (hi and its value are
+    returned: the target was not met), "lo" when the lowest point already does (lo is returned), None otherwise."""
+    lo, hi, target = float(lo), float(hi), float(target)
+    if not (0 < lo < hi < np.inf):
+        raise ValueError("the bracket needs 0 < lo < hi < inf")
+    if k < 4 or not rtol > 0:
+        raise ValueError("k must be >= 4 and rtol > 0")
+    if not target > 0:
+        raise ValueError("target must be > 0")
+    frac = np.arange(k) / (k - 1)
+    scans = 0
+    while True:
+        llo, lhi = np.log(lo), np.log(hi)
+        tfs = np.exp(llo + (lhi - llo) * frac)
+        tfs[0], tfs[-1] = lo, hi                                     # the ends exactly: a grid never leaves its bracket
+        ess = np.asarray(objective(tfs), dtype=np.float64).reshape(k)
+        scans += 1
+        reached = ess >= target
+        i = int(np.argmax(reached)) if reached.any() else k - 1     # the first point that reaches the target
+        if scans == 1 and not reached.any():
+            return hi, float(ess[-1]), {"scans": scans, "lo": lo, "hi": hi, "at_edge": "hi"}
+        if scans == 1 and i == 0:
+            return lo, float(ess[0]), {"scans": scans, "lo": lo, "hi": hi, "at_edge": "lo"}
+        tf, val = float(tfs[i]), float(ess[i])
+        if i > 0:                                                    # (i == 0 after the first round: only a non-deterministic objective)
+            lo = float(tfs[i - 1])
+        hi = tf
+        if i == 0 or hi / lo - 1.0 <= rtol:
+            return tf, val, {"scans": scans, "lo": lo, "hi": hi, "at_edge": None}
+
+
+def tf_for_ess(LL, target, log_ratio=None, lo=1.0, hi=1e4, rtol=1e-6, device=0, info=None):
+    """(tf, ess): the smallest temperature of the grid search _ess_search over [lo, hi] at which the weights of
+    exp(LL / tf - log_ratio) have an effective sample size (sum W)^2 / sum W^2 of at least `target`, and that size;
+    TF_SCAN_POINTS temperatures per device scan (tf_scan(..., log_ratio=)["ess"]; log_ratio None: zeros, the unrefined set).
+    What building a proposal at a raised temperature needs (refine.run(target_ess=)).  A NaN in LL or log_ratio makes every
+    effective sample size NaN: drop such samples first (filter_nan) or give them LL = -inf.  info receives scans, lo, hi (the
+    final bracket) and at_edge: "hi" -- no temperature of the first grid reaches the target, hi and its ess are returned;
+    "lo" -- lo already does; None otherwise."""
+    LL = _f64(LL)
+    if LL.ndim != 1:
+        raise ValueError("LL must be one-dimensional")
+    lnr = np.zeros(LL.size) if log_ratio is None else _log_ratio(log_ratio, LL.size)
+    tf, ess, inf = _ess_search(lambda tfs: tf_scan(LL, tfs, device=device, log_ratio=lnr)["ess"], target, lo, hi,
+                               TF_SCAN_POINTS, rtol)
+    if info is not None:
+        info.update(inf)
+    return tf, ess
 
 
 # ---- the corner: every marginal of a finished run in one device call (trpl_corner, csrc/corner.hip) ----

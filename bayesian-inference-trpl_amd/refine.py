@@ -10,7 +10,11 @@ and every sample of every generation is weighted by the deterministic mixture of
     LLc = LL - tf ln r(u)
 
 so that posterior.weights / moments / quantiles / corner and posterior_predictive work unchanged on the concatenated (X, LLc).
-LLc is valid at the tf it was formed for: posterior.tf_scan / find_best_tf over a refined set are not supported.
+LLc is valid at the tf it was formed for only.  What depends on the temperature keeps ln r(u) beside LL instead:
+Population.log_ratio() returns (X, LL, ln r), and posterior.weights / tf_scan / find_best_tf / calc_max_uncertainty / tf_for_ess
+take it as log_ratio= (trpl_posterior_weights_lr, trpl_posterior_tf_scan_lr), so a temperature scan over a refined set is supported.
+run(target_ess=) uses it to build each generation's proposal at the lowest temperature whose effective sample size reaches a
+target, and comes down to the caller's tf as the union grows.
 
 All sampling happens in unit coordinates of the ACTIVE columns (minX != maxX and not the target of an equal-mu / equal-S /
 equal-Auger override); resampling, the draw, the mixture density and the unit map run on the device.  No CPU fallback.
@@ -197,8 +201,8 @@ class Population:
         if proposal is not None:
             self.proposals.append(proposal)
 
-    def corrected(self, tf=1.0):
-        """(X_all, LLc): the concatenated samples and LL - tf ln r(u), r recomputed over all generations' proposals."""
+    def _log_r(self):
+        """ln r(u) of every sample, r recomputed over all generations' proposals (the cached numerators brought up to date)."""
         if not self.X:
             raise ValueError("the population is empty")
         for g, U in enumerate(self.U):
@@ -209,7 +213,31 @@ class Population:
         total = float(self.sizes[0])
         for p in self.proposals:
             total += p.n_uniform + p.K * p.m
-        return np.concatenate(self.X), np.concatenate(self.LL) - float(tf) * np.log(np.concatenate(self._num) / total)
+        return np.log(np.concatenate(self._num) / total)
+
+    def corrected(self, tf=1.0):
+        """(X_all, LLc): the concatenated samples and LL - tf ln r(u), r recomputed over all generations' proposals."""
+        lnr = self._log_r()
+        return np.concatenate(self.X), np.concatenate(self.LL) - float(tf) * lnr
+
+    def log_ratio(self):
+        """(X_all, LL_all, lnr_all): the concatenated samples, their log-likelihoods and ln r(u) from corrected()'s numerators --
+        what posterior.weights / tf_scan / find_best_tf / calc_max_uncertainty / tf_for_ess take as (LL, log_ratio=), at any tf."""
+        lnr = self._log_r()
+        return np.concatenate(self.X), np.concatenate(self.LL), lnr
+
+    def tf_scan(self, tfs, V=None):
+        """posterior.tf_scan of the union at the temperatures tfs, with its log-ratio: stats (K, 6), ess (K,) and, with V (D, S),
+        mean, var, Q."""
+        _, LL, lnr = self.log_ratio()
+        return posterior.tf_scan(LL, tfs, V, device=self.device, log_ratio=lnr)
+
+    def tf_for_ess(self, target, lo=1.0, hi=1e4, rtol=1e-6, info=None):
+        """posterior.tf_for_ess of the union: (tf, ess), the smallest grid temperature in [lo, hi] whose effective sample size
+        reaches target.  A NaN likelihood counts as weight 0 here, as in resample and ess."""
+        _, LL, lnr = self.log_ratio()
+        return posterior.tf_for_ess(np.where(np.isnan(LL), -np.inf, LL), target, log_ratio=lnr, lo=lo, hi=hi, rtol=rtol,
+                                    device=self.device, info=info)
 
     def weights(self, tf=1.0):
         return posterior.weights(self.corrected(tf)[1], tf, device=self.device)
@@ -220,18 +248,33 @@ class Population:
 
 
 def run(loglik, X1, LL1, minX, maxX, do_log, sim_flags=None, rounds=1, K=1024, m=32, n_uniform=None, tf=1.0, h=None, offset=0.5, seed=1,
-        device=0, info=None):
+        device=0, info=None, target_ess=None, tf_hi=None):
     """Refine a first generation (X1, LL1) of the box by `rounds` further generations; loglik(X) -> LL is any callable (the fused
     likelihood, a toy).  n_uniform defaults to a ninth of the generation (K m / 8).  Returns the Population; info receives ess (one
     entry per generation: the union so far) and nonzero (the share of each further generation's children with a weight > 0 in the
-    final union)."""
+    final union).
+
+    target_ess: the temperature ladder.  Generation g's proposal is built from the union's weights at tf_g = max(tf,
+    tf_for_ess(union, target_ess, lo=tf, hi=tf_hi)), the lowest temperature at which the union so far has that effective sample
+    size (tf_hi defaults to 1e4 tf), through the log-ratio calls; tf stays the caller's final temperature, at which nonzero and
+    the last entry of ess are taken.  info then also receives tfs (one per further generation; the earlier entries of ess belong
+    to these) and ess_at_tf (the union's effective sample size at tf: the first generation's, then after each further one)."""
     pop = Population(device=device)
     U1, _ = unit_coords(X1, minX, maxX, do_log, sim_flags, device=device)
     pop.add(X1, U1, LL1)
     n_uniform = (int(K) * int(m)) // 8 if n_uniform is None else int(n_uniform)
-    esses = []
+    esses, tfs, at_tf = [], [], []
+    tf = float(tf)
     for g in range(2, 2 + int(rounds)):
-        W = pop.weights(tf)                                      # once per round; its effective sample size comes with the resampling
+        if target_ess is None:
+            W = pop.weights(tf)                                  # once per round; its effective sample size comes with the resampling
+        else:
+            _, LL, lnr = pop.log_ratio()
+            LL0 = np.where(np.isnan(LL), -np.inf, LL)            # a NaN likelihood counts as weight 0, as in resample
+            at_tf.append(float(posterior.tf_scan(LL0, [tf], device=device, log_ratio=lnr)["ess"][0]))
+            tfs.append(max(tf, posterior.tf_for_ess(LL0, target_ess, log_ratio=lnr, lo=tf, hi=1e4 * tf if tf_hi is None else float(tf_hi),
+                                                    device=device)[0]))
+            W = posterior.weights(LL, tfs[-1], device=device, log_ratio=lnr)
         sums = {}
         prop = make_proposal(np.concatenate(pop.U), W, K, m, n_uniform, h=h, offset=offset, seed=seed, generation=g, S1=pop.sizes[0],
                              device=device, info=sums)
@@ -243,4 +286,6 @@ def run(loglik, X1, LL1, minX, maxX, do_log, sim_flags=None, rounds=1, K=1024, m
         edges = np.cumsum([0] + pop.sizes)
         info.update(ess=esses + [float(resample(W, 1, device=device)[1]["ess"])],
                     nonzero=[float(np.mean(W[edges[g]:edges[g + 1]] > 0)) for g in range(1, len(pop.sizes))])
+        if target_ess is not None:
+            info.update(tfs=tfs, ess_at_tf=at_tf + [info["ess"][-1]])
     return pop

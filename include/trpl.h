@@ -805,6 +805,48 @@ int trpl_posterior_tf_scan_dev(const double *LL, int64_t S, const double *V, int
                                int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_posterior_weights_lr, trpl_posterior_tf_scan_lr -- the two calls above with a per-sample proposal log-ratio kept BESIDE
+ * the log-likelihood instead of folded into it: the temperature-dependent front end for a refined set (trpl_refine_*, below),
+ * whose sample s carries the weight exp(LL[s] / tf) / r(u_s).  With lnr[s] = ln r(u_s) (natural log, fp64):
+ *     e_k[s] = LL[s] / tf_k - lnr[s]
+ *     m_k    = nanmax_s e_k[s]
+ *     w_k[s] = exp(((e_k[s] - m_k) + 1000 ln 2) - ln S)            (the order of utils.py:164)
+ *     W_k    = w_k / nansum w_k
+ * The weight is trpl_posterior_weights' compensated form: the remainder of the division, the rounding of the subtraction of lnr
+ * and the roundings of the three sums are exact in fp64 and are put back.  m_k is NOT nanmax(LL) / tf_k: the sample that leads at
+ * one temperature need not lead at another, so the maximum is taken per temperature.
+ * NaN: a NaN in LL[s] or in lnr[s] gives a NaN weight; that sample is left out of m_k and of the normalising sum and is not
+ * counted, and the sums over the weights (sum W, sum W^2, the moments, ess) are then NaN, as in trpl_posterior_moments.  LL = -inf
+ * or lnr = +inf give a weight of exactly 0.  lnr = -inf is the caller's error (r >= S1 / S_total > 0 by construction) and is not
+ * looked for.
+ * trpl_posterior_weights_lr: one temperature; writes W[S] and stats (nullable) = { m, nansum of the unnormalised weights }.
+ * trpl_posterior_tf_scan_lr: K <= TRPL_TF_SCAN_MAX temperatures, D <= 16 columns V[D][S]; mean, var, Q [K][D] as
+ * trpl_posterior_tf_scan, and
+ *     stats[K][6] = { m_k, nansum of the unnormalised weights, sum W_k, sum W_k^2, count of samples with neither LL nor lnr
+ *                     NaN (the same for every k), ess_k = (sum W_k)^2 / sum W_k^2 }
+ * BIT FOR BIT: row k of the scan is trpl_posterior_weights_lr(LL, lnr, S, tfs[k]) followed by trpl_posterior_moments(V, S, D, W);
+ * trpl_posterior_weights_lr with lnr[s] = +0.0 for every s is trpl_posterior_weights; hence the scan with lnr = +0.0 is
+ * trpl_posterior_tf_scan in every output the two share.  No atomics; the result does not depend on scheduling.
+ * Refused with TRPL_ERR_ARG before a device is touched, the message naming the argument: what trpl_posterior_tf_scan refuses
+ * (S < 1; D outside [0, 16]; K < 1 or K > TRPL_TF_SCAN_MAX; a NULL LL, tfs, stats, or (D > 0) V, mean, var, Q; in the host form a
+ * tfs[k] that is not finite and > 0) and a NULL lnr; the weights call: S < 1, a NULL LL, lnr or W, a tf that is not finite and > 0.
+ * The _dev forms take device pointers for everything and a workspace -- trpl_posterior_workspace_bytes(1) bytes for the
+ * weights, trpl_posterior_tf_scan_lr_workspace(S, D, K) bytes (0 for arguments the scan refuses) for the scan; they allocate
+ * nothing, never synchronise and can be captured in a HIP graph.
+ * ------------------------------------------------------------------------------------- */
+int trpl_posterior_weights_lr(const double *LL, const double *lnr, int64_t S, double tf, double *W, double *stats /*nullable [2]*/,
+                              int32_t device, double *seconds);
+int trpl_posterior_weights_lr_dev(const double *LL, const double *lnr, int64_t S, double tf, double *W, double *stats,
+                                  void *workspace, int64_t workspace_bytes, void *stream);
+int64_t trpl_posterior_tf_scan_lr_workspace(int64_t S, int32_t D, int32_t K);
+int trpl_posterior_tf_scan_lr(const double *LL, const double *lnr, int64_t S, const double *V /*nullable: D == 0*/, int32_t D,
+                              const double *tfs, int32_t K, double *stats, double *mean, double *var, double *Q, int32_t device,
+                              double *seconds);
+int trpl_posterior_tf_scan_lr_dev(const double *LL, const double *lnr, int64_t S, const double *V, int32_t D, const double *tfs,
+                                  int32_t K, double *stats, double *mean, double *var, double *Q, void *workspace,
+                                  int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_predictive* -- the posterior-predictive PL band: the posterior taken back to the DATA.  Which PL(t) does the posterior
  * predict, and how wide is that prediction next to the measured curve (the check a user of the reference does by hand in NumPy
  * on a PL matrix copied to the host).  A streaming reduction over the samples, per time column, of a PL block resident in HBM
@@ -1022,7 +1064,8 @@ int trpl_corner(const double *X, int64_t S, int64_t ldx, const double *LL, doubl
  *     r(u) = (S1 + sum_g [n_uniform_g + m_g * B_g(u)]) / S_total,    B_g(u) = sum_k inv_vol_k * 1[a_k <= u <= b_k]  (closed, every d),
  * its weight at temperature tf is exp(LL / tf) / r(u), and LLc = LL - tf * ln r(u) handed to trpl_posterior_weights, _moments,
  * trpl_weighted_quantiles, trpl_corner and the predictive band makes them work unchanged on the concatenated samples.  LLc is
- * valid at the tf it was formed for: trpl_posterior_tf_scan over a refined set is NOT supported.
+ * valid at the tf it was formed for only; a temperature scan over a refined set keeps ln r(u) beside LL instead
+ * (trpl_posterior_weights_lr, trpl_posterior_tf_scan_lr above).
  *
  * trpl_refine_resample: systematic resampling.  W[S] weights (NaN or <= 0 counts as 0; +inf is refused by the host form and
  * undefined in the _dev form), K draws, offset in [0, 1).  idx[k] (int64, non-decreasing) is the smallest i whose inclusive

@@ -1,10 +1,12 @@
 """The temperature scan against the loop it replaces, in one process on one device.
 
-    python tools/bench_tf_scan.py [S] [D] [K]            (defaults 2^17, 13, 64)
+    python tools/bench_tf_scan.py [S] [D] [K] [--lr]     (defaults 2^17, 13, 64)
 
 scan: one trpl_posterior_tf_scan_dev over K temperatures.  loop: K x (trpl_posterior_weights_dev + trpl_posterior_moments_dev),
 the existing calls at the same temperatures (the yardstick of this same run).  Device events, the two passes interleaved,
-median of 3 passes of `reps` calls each.  Appends one JSON line to profiles/tf_scan_bench.jsonl; exit status 1 when the scan
+median of 3 passes of `reps` calls each.  --lr adds a third interleaved row, one trpl_posterior_tf_scan_lr_dev (the scan with a
+proposal log-ratio beside LL, uniform in [-3, 30]) at the same S, D, K: recorded as lr_ms and lr_over_scan, not gated (one more 8-byte
+read per sample and phase, K maxima in place of one).  Appends one JSON line to profiles/tf_scan_bench.jsonl; exit status 1 when the scan
 is slower than the loop."""
 import json
 import os
@@ -21,7 +23,9 @@ PEAK_TBS = 8.0
 
 
 def main():
-    S, D, K = (int(a) for a in (sys.argv[1:4] + ["131072", "13", "64"][len(sys.argv[1:4]):]))
+    with_lr = "--lr" in sys.argv
+    argv = [a for a in sys.argv[1:] if a != "--lr"]
+    S, D, K = (int(a) for a in (argv[:3] + ["131072", "13", "64"][len(argv[:3]):]))
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev)
     g.manual_seed(1)
@@ -39,6 +43,14 @@ def main():
 
     def scan():
         tdev.posterior_tf_scan_device(LL, tfs, out["stats"], ws, V=V, mean=out["mean"], var=out["var"], Q=out["Q"])
+
+    lnr = 33.0 * torch.rand(S, dtype=torch.float64, device=dev, generator=g) - 3.0
+    zero = torch.zeros_like(LL)
+    ws_lr = tdev.posterior_tf_scan_lr_workspace(S, D, K)
+    out_lr = {n: torch.zeros((K, 6 if n == "stats" else D), dtype=torch.float64, device=dev) for n in ("stats", "mean", "var", "Q")}
+
+    def scan_lr(ratio=lnr):
+        tdev.posterior_tf_scan_lr_device(LL, ratio, tfs, out_lr["stats"], ws_lr, V=V, mean=out_lr["mean"], var=out_lr["var"], Q=out_lr["Q"])
 
     def loop(keep=False):
         for k in range(K):
@@ -59,9 +71,16 @@ def main():
     scan(); loop(keep=True)
     torch.cuda.synchronize()
     assert torch.equal(out["var"], var_loop), "the scan and the loop disagree"
-    t_scan, t_loop = [], []
+    t_scan, t_loop, t_lr = [], [], []
+    if with_lr:
+        scan_lr(zero)
+        torch.cuda.synchronize()
+        assert torch.equal(out_lr["var"], out["var"]) and torch.equal(out_lr["Q"], out["Q"]), "a zero ratio does not give the scan's bits"
+        scan_lr()
     for _ in range(3):                                   # interleaved passes
         t_scan.append(timed(scan, 20))
+        if with_lr:
+            t_lr.append(timed(scan_lr, 20))
         t_loop.append(timed(loop, 2))
     ms_scan, ms_loop = float(np.median(t_scan)), float(np.median(t_loop))
     # bytes a streaming implementation has to move: LL in every phase that forms weights (3) + the max phase, V twice
@@ -75,6 +94,11 @@ def main():
             "scan_fraction_of_peak": scan_bytes / ms_scan / 1e9 / PEAK_TBS,
             "loop_algorithmic_bytes": loop_bytes, "loop_TBps": loop_bytes / ms_loop / 1e9,
             "loop_fraction_of_peak": loop_bytes / ms_loop / 1e9 / PEAK_TBS}
+    if with_lr:
+        ms_lr = float(np.median(t_lr))
+        lr_bytes = 8 * S * (8 + 2 * D)                   # LL and lnr in the four phases, V twice
+        line.update({"lr_ms": ms_lr, "lr_ms_passes": t_lr, "lr_over_scan": ms_lr / ms_scan, "lr_algorithmic_bytes": lr_bytes,
+                     "lr_TBps": lr_bytes / ms_lr / 1e9})
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     with open(os.path.join(ROOT, "profiles", "tf_scan_bench.jsonl"), "a") as f:
         f.write(json.dumps(line) + "\n")

@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -20,6 +20,12 @@ posterior, box-kernel children, the fused likelihood on them, deterministic-mixt
 effective sample size after every generation, the share of each generation's children with a weight > 0, the plain sum of the
 union's weights over the samples with a finite likelihood, and the numbers of NaN weights and of NaN in LLc among those
 samples -- and seconds["refine"]; without it the output is unchanged.
+--target-ess N (with --refine) builds every generation's proposal at the lowest temperature at which the union so far has an
+effective sample size of N (refine.run(target_ess=N): the temperature ladder, through the log-ratio scan) and adds "target_ess",
+"tf_per_generation" and "ess_at_tf" (the union's effective sample size at the final temperature after each generation) to "refine";
+tf per generation and the final effective sample size are printed.
+--find-tf with --refine also searches the temperature of largest uncertainty over the refined union, its proposal log-ratio kept
+beside the likelihoods (posterior.calc_max_uncertainty(log_ratio=)), as refine["max_uncertainty"].
 """
 import json
 import sys
@@ -35,6 +41,11 @@ ROUNDS = 1
 if "--rounds" in sys.argv:
     k = sys.argv.index("--rounds")
     ROUNDS = int(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
+TARGET_ESS = None
+if "--target-ess" in sys.argv:
+    k = sys.argv.index("--target-ess")
+    TARGET_ESS = float(sys.argv[k + 1])
     del sys.argv[k:k + 2]
 sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine")]
 import numpy as np
@@ -171,7 +182,7 @@ if REFINE:
     K = max(1, min(1024, S // 32))
     rinfo = {}
     pop = refine.run(fused, X.cpu().numpy(), P.cpu().numpy(), lo, hi, lg, rounds=ROUNDS, K=K, m=28, n_uniform=max(1, S // 8), tf=tf,
-                     seed=42, info=rinfo)
+                     seed=42, info=rinfo, target_ess=TARGET_ESS)
     X_all, LLc = pop.corrected(tf)
     W_all = posterior.weights(LLc, tf)
     LL_all = np.concatenate(pop.LL)
@@ -182,4 +193,19 @@ if REFINE:
                      "nan_llc_from_finite_ll": int(np.sum(np.isnan(LLc) & np.isfinite(LL_all)))}
     print("refine: effective sample size per generation %s, share of children with a weight > 0 %s"
           % (["%.2f" % e for e in rinfo["ess"]], ["%.4f" % f for f in rinfo["nonzero"]]), file=sys.stderr)
+    if TARGET_ESS is not None:
+        out["refine"].update(target_ess=TARGET_ESS, tf_per_generation=rinfo["tfs"], ess_at_tf=rinfo["ess_at_tf"])
+        print("refine: target %g, final tf %g; tf per generation %s; effective sample size at the final tf %s, final %.2f"
+              % (TARGET_ESS, tf, ["%.6g" % t for t in rinfo["tfs"]], ["%.2f" % e for e in rinfo["ess_at_tf"]], rinfo["ess"][-1]),
+              file=sys.stderr)
+    if FIND_TF:                                                  # the temperature scan over the refined union: ln r beside LL
+        t10 = sync()
+        _, LL_u, lnr_u = pop.log_ratio()
+        keep = ~np.isnan(LL_u)
+        Xg = X_all[keep] / sm.UNIT_CONVERSIONS
+        Vu = {n: (np.log10(Xg[:, i]) if lg[i] else Xg[:, i]) for n, i in zip(names, cols)}
+        uinfo = {}
+        unc = posterior.calc_max_uncertainty(Vu, LL_u[keep], n_obs, info=uinfo, log_ratio=lnr_u[keep])
+        out["seconds"]["refine_find_tf"] = sync() - t10
+        out["refine"]["max_uncertainty"] = {n: {"tf": t, "Q": q, "at_edge": bool(uinfo["at_edge"][n])} for n, (t, q) in unc.items()}
 print(json.dumps(out))
