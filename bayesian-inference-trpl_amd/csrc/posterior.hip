@@ -21,14 +21,16 @@ namespace post {
 
 constexpr int kLdsBins = 4096;
 
-// ---- weights: q = LL / tf; W = exp(q - nanmax(q) + c_up - c_size), roundings of the exponent put back; W /= nansum(W) ----
-__global__ void __launch_bounds__(kThreads) nanmax_partial(const double *LL, int64_t S, double tf, double *part)
+// ---- weights: e = LL / tf [- lnr]; W = exp(e - nanmax(e) + c_up - c_size), roundings of the exponent put back; W /= nansum(W).
+//      Src is Plain or Ratio (posterior_common.hpp): the same kernels serve the call with and without a log-ratio ----
+template <class Src>
+__global__ void __launch_bounds__(kThreads) nanmax_partial(Src src, int64_t S, double tf, double *part)
 {
     __shared__ double sm[kThreads / 64];
     double m = -INFINITY;
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < S; i += (int64_t)gridDim.x * kThreads) {
-        const double q = LL[i] / tf;
-        m = fmax(m, q);                      // fmax ignores NaN operands, like np.nanmax
+        double lost;                         // not needed for the maximum
+        m = fmax(m, Src::exponent(src.load(i), tf, lost));          // fmax ignores NaN operands, like np.nanmax
     }
     m = block_reduce<true>(m, sm);
     if (threadIdx.x == 0) part[blockIdx.x] = m;
@@ -44,25 +46,27 @@ __global__ void __launch_bounds__(kThreads) final_reduce(const double *part, int
     r = is_max ? block_reduce<true>(r, sm) : block_reduce<false>(r, sm);
     if (threadIdx.x == 0) out[(int64_t)blockIdx.y * ncol + c] = r;
 }
-__global__ void __launch_bounds__(kThreads) weights_partial(const double *LL, int64_t S, double tf, const double *mx,
-                                                            double c_up, double c_size, double *W, double *part)
+template <class Src>
+__global__ void __launch_bounds__(kThreads) weights_partial(Src src, int64_t S, double tf, const double *mx, double c_up,
+                                                            double c_size, double *W, double *part)
 {
     __shared__ double sm[kThreads / 64];
     const double m = mx[0];
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < S; i += (int64_t)gridDim.x * kThreads) {
-        const double w = tempered_weight(LL[i], tf, m, c_up, c_size);
+        const double w = tempered_weight<Src>(src.load(i), tf, m, c_up, c_size);
         W[i] = w;
         if (w == w) acc += w;                                 // np.nansum
     }
     acc = block_reduce<false>(acc, sm);
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
-__global__ void __launch_bounds__(kThreads) scale_kernel(double *W, int64_t S, const double *sum)
+// W /= sum (utils.py:165); thread 0 of block 0 leaves stats = {max, raw sum} where the caller asked for them
+__global__ void __launch_bounds__(kThreads) scale_kernel(double *W, int64_t S, const double *mx, const double *sum, double *stats)
 {
     const double s = sum[0];
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < S; i += (int64_t)gridDim.x * kThreads)
-        W[i] = W[i] / s;                                      // utils.py:165
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < S; i += (int64_t)gridDim.x * kThreads) W[i] = W[i] / s;
+    if (stats && blockIdx.x == 0 && threadIdx.x == 0) { stats[0] = mx[0]; stats[1] = s; }
 }
 
 // ---- moments pass 1: sum w, sum w^2, sum w v_d  (V is [D][S]: one contiguous column per parameter) ----
@@ -248,26 +252,30 @@ __global__ void __launch_bounds__(kThreads) hist_kernel(const double *x, const d
 
 size_t posterior_workspace_bytes(int D) { return sizeof(double) * ((size_t)post::kMaxBlocks * (size_t)(D > 0 ? D : 1) * (D + 2) + 64); }
 
-__global__ void copy2_kernel(const double *a, const double *b, double *out) { out[0] = a[0]; out[1] = b[0]; }
-
-// W[S] <- normalised posterior weights of LL[S] tempered by tf.  ws: >= posterior_workspace_bytes(1).
-// stats (nullable, device): {nanmax(LL/tf), nansum of the unnormalised weights} -- what a caller that
-// holds only a shard of the samples needs to renormalise across shards.
-hipError_t launch_posterior_weights(const double *LL, int64_t S, double tf, double *W, double *stats, double *ws,
-                                    hipStream_t st)
+template <class Src>
+static hipError_t launch_weights(Src src, int64_t S, double tf, double *W, double *stats, double *ws, hipStream_t st)
 {
     using namespace post;
-    if (S <= 0) return hipSuccess;
     const int nb = grid_for(S);
     double *part = ws, *mx = ws + kMaxBlocks, *sum = mx + 1;
     const double c_up = 1000.0 * log(2.0), c_size = log((double)S);                   // utils.py:164
-    hipLaunchKernelGGL(nanmax_partial, dim3(nb), dim3(kThreads), 0, st, LL, S, tf, part);
+    hipLaunchKernelGGL(nanmax_partial<Src>, dim3(nb), dim3(kThreads), 0, st, src, S, tf, part);
     hipLaunchKernelGGL(final_reduce, dim3(1, 1), dim3(kThreads), 0, st, part, nb, 1, true, mx);
-    hipLaunchKernelGGL(weights_partial, dim3(nb), dim3(kThreads), 0, st, LL, S, tf, mx, c_up, c_size, W, part);
+    hipLaunchKernelGGL(weights_partial<Src>, dim3(nb), dim3(kThreads), 0, st, src, S, tf, mx, c_up, c_size, W, part);
     hipLaunchKernelGGL(final_reduce, dim3(1, 1), dim3(kThreads), 0, st, part, nb, 1, false, sum);
-    hipLaunchKernelGGL(scale_kernel, dim3(nb), dim3(kThreads), 0, st, W, S, sum);
-    if (stats) hipLaunchKernelGGL(copy2_kernel, dim3(1), dim3(1), 0, st, mx, sum, stats);
+    hipLaunchKernelGGL(scale_kernel, dim3(nb), dim3(kThreads), 0, st, W, S, mx, sum, stats);
     return hipGetLastError();
+}
+
+// W[S] <- normalised posterior weights of LL[S] tempered by tf, exp(LL / tf - lnr) where lnr (nullable) is given.
+// ws: >= posterior_workspace_bytes(1).  stats (nullable, device): {nanmax of the exponent, nansum of the unnormalised
+// weights} -- what a caller that holds only a shard of the samples needs to renormalise across shards.
+hipError_t launch_posterior_weights(const double *LL, const double *lnr, int64_t S, double tf, double *W, double *stats, double *ws,
+                                    hipStream_t st)
+{
+    if (S <= 0) return hipSuccess;
+    return lnr ? launch_weights(post::Ratio{LL, lnr}, S, tf, W, stats, ws, st)
+               : launch_weights(post::Plain{LL}, S, tf, W, stats, ws, st);
 }
 
 // sums[2 + D]   = {sum w, sum w^2, sum w v_d}

@@ -1285,36 +1285,74 @@ int trpl_interp_rows(const void *pl, int32_t elem_bytes, int64_t rows, int64_t n
 /* ------------------------------------------------------------------ posterior core ------ */
 int64_t trpl_posterior_workspace_bytes(int32_t D) { return (int64_t)trpl::posterior_workspace_bytes(D); }
 
-int trpl_posterior_weights_dev(const double *LL, int64_t S, double tf, double *W, double *stats, void *workspace,
-                               int64_t workspace_bytes, void *stream)
+// The weights with and without a proposal log-ratio lnr are one call path below the argument checks, which differ: the plain
+// call accepts S == 0 (nothing to do) and has one message for its pointers, the log-ratio call refuses S < 1 and names the pointer.
+static int check_post_weights(const void *LL, int64_t S, double tf, const void *W, bool have_workspace)
 {
     if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
     if (S == 0) return TRPL_OK;
-    if (!LL || !W || !workspace) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
+    if (!LL || !W || !have_workspace) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
     if (!(tf > 0)) return api_fail(TRPL_ERR_ARG, "tf must be > 0");
-    if (workspace_bytes < (int64_t)trpl::posterior_workspace_bytes(1)) return api_fail(TRPL_ERR_ARG, "workspace too small");
-    hipError_t e = trpl::launch_posterior_weights(LL, S, tf, W, stats, (double *)workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "posterior weights launch: %s", hipGetErrorString(e));
     return TRPL_OK;
 }
 
-int trpl_posterior_weights(const double *LL, int64_t S, double tf, double *W, double *stats, int32_t device,
-                           double *seconds)
+static int check_post_weights_lr(const void *LL, const void *lnr, int64_t S, double tf, const void *W)
 {
-    if (seconds) *seconds = 0.0;
-    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
+    if (S < 1) return api_fail(TRPL_ERR_ARG, "S=%lld must be >= 1", (long long)S);
+    if (!LL) return api_fail(TRPL_ERR_ARG, "LL is NULL");
+    if (!lnr) return api_fail(TRPL_ERR_ARG, "lnr is NULL");
+    if (!W) return api_fail(TRPL_ERR_ARG, "W is NULL");
+    if (!(tf > 0) || !(tf < INFINITY)) return api_fail(TRPL_ERR_ARG, "tf=%g must be finite and > 0", tf);
+    return TRPL_OK;
+}
+
+static int weights_launch(const double *LL, const double *lnr, int64_t S, double tf, double *W, double *stats, void *workspace,
+                          void *stream)
+{
+    hipError_t e = trpl::launch_posterior_weights(LL, lnr, S, tf, W, stats, (double *)workspace, (hipStream_t)stream);
+    if (e != hipSuccess)
+        return api_fail(TRPL_ERR_HIP, "posterior weights%s launch: %s", lnr ? " (log-ratio)" : "", hipGetErrorString(e));
+    return TRPL_OK;
+}
+
+int trpl_posterior_weights_dev(const double *LL, int64_t S, double tf, double *W, double *stats, void *workspace,
+                               int64_t workspace_bytes, void *stream)
+{
+    if (int rc = check_post_weights(LL, S, tf, W, workspace != nullptr)) return rc;
     if (S == 0) return TRPL_OK;
-    if (!LL || !W) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
-    if (!(tf > 0)) return api_fail(TRPL_ERR_ARG, "tf must be > 0");
+    if (workspace_bytes < (int64_t)trpl::posterior_workspace_bytes(1)) return api_fail(TRPL_ERR_ARG, "workspace too small");
+    return weights_launch(LL, nullptr, S, tf, W, stats, workspace, stream);
+}
+
+int trpl_posterior_weights_lr_dev(const double *LL, const double *lnr, int64_t S, double tf, double *W, double *stats,
+                                  void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = check_post_weights_lr(LL, lnr, S, tf, W)) return rc;
+    if (!workspace) return api_fail(TRPL_ERR_ARG, "workspace is NULL");
+    if (workspace_bytes < (int64_t)trpl::posterior_workspace_bytes(1))
+        return api_fail(TRPL_ERR_ARG, "workspace of %lld bytes is smaller than trpl_posterior_workspace_bytes(1) = %lld",
+                        (long long)workspace_bytes, (long long)trpl::posterior_workspace_bytes(1));
+    return weights_launch(LL, lnr, S, tf, W, stats, workspace, stream);
+}
+
+// the host-buffer form of both, the arguments checked: stages LL (and lnr), runs the device form, copies W and stats back
+static int weights_staged(const double *LL, const double *lnr, int64_t S, double tf, double *W, double *stats, int32_t device,
+                          double *seconds)
+{
     if (int rc = select_device(device)) return rc;
     CallScope cs;
     HIP_TRY(cs.open());
-    DevBuf dL, dW, dSt, ws;
+    DevBuf dL, dR, dW, dSt, ws;
     const size_t wsb = trpl::posterior_workspace_bytes(1);
-    HIP_TRY(dL.alloc((size_t)S * 8, cs.st)); HIP_TRY(dW.alloc((size_t)S * 8, cs.st)); HIP_TRY(dSt.alloc(16, cs.st)); HIP_TRY(ws.alloc(wsb, cs.st));
+    HIP_TRY(dL.alloc((size_t)S * 8, cs.st));
+    if (lnr) HIP_TRY(dR.alloc((size_t)S * 8, cs.st));
+    HIP_TRY(dW.alloc((size_t)S * 8, cs.st)); HIP_TRY(dSt.alloc(16, cs.st)); HIP_TRY(ws.alloc(wsb, cs.st));
     HIP_TRY(hipMemcpyAsync(dL.p, LL, (size_t)S * 8, hipMemcpyHostToDevice, cs.st));
+    if (lnr) HIP_TRY(hipMemcpyAsync(dR.p, lnr, (size_t)S * 8, hipMemcpyHostToDevice, cs.st));
     const double t0 = now_s();
-    if (int rc = trpl_posterior_weights_dev(dL.as<double>(), S, tf, dW.as<double>(), dSt.as<double>(), ws.p, (int64_t)wsb, cs.st))
+    if (int rc = lnr ? trpl_posterior_weights_lr_dev(dL.as<double>(), dR.as<double>(), S, tf, dW.as<double>(), dSt.as<double>(), ws.p,
+                                                     (int64_t)wsb, cs.st)
+                     : trpl_posterior_weights_dev(dL.as<double>(), S, tf, dW.as<double>(), dSt.as<double>(), ws.p, (int64_t)wsb, cs.st))
         return rc;
     HIP_TRY(hipStreamSynchronize(cs.st));
     if (seconds) *seconds = now_s() - t0;
@@ -1322,6 +1360,23 @@ int trpl_posterior_weights(const double *LL, int64_t S, double tf, double *W, do
     if (stats) HIP_TRY(hipMemcpyAsync(stats, dSt.p, 16, hipMemcpyDeviceToHost, cs.st));
     HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
     return TRPL_OK;
+}
+
+int trpl_posterior_weights(const double *LL, int64_t S, double tf, double *W, double *stats, int32_t device,
+                           double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    if (int rc = check_post_weights(LL, S, tf, W, true)) return rc;
+    if (S == 0) return TRPL_OK;
+    return weights_staged(LL, nullptr, S, tf, W, stats, device, seconds);
+}
+
+int trpl_posterior_weights_lr(const double *LL, const double *lnr, int64_t S, double tf, double *W, double *stats, int32_t device,
+                              double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    if (int rc = check_post_weights_lr(LL, lnr, S, tf, W)) return rc;
+    return weights_staged(LL, lnr, S, tf, W, stats, device, seconds);
 }
 
 int trpl_posterior_moments_dev(const double *V, int64_t S, int32_t D, const double *W, const double *mean_in, double *sums,

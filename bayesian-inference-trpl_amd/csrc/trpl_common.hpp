@@ -147,8 +147,8 @@ hipError_t launch_mag_profile_w(const double *sse, const double *esum, const dou
 
 // posterior.hip: the consumer of P[S] (weights, weighted moments, weighted histograms)
 size_t posterior_workspace_bytes(int D);
-hipError_t launch_posterior_weights(const double *LL, int64_t S, double tf, double *W, double *stats, double *ws,
-                                    hipStream_t st);
+hipError_t launch_posterior_weights(const double *LL, const double *lnr /*nullable*/, int64_t S, double tf, double *W, double *stats,
+                                    double *ws, hipStream_t st);
 hipError_t launch_posterior_moments(const double *V, const double *W, int64_t S, int D, const double *mean_in, double *sums,
                                     double *central, double *ws, hipStream_t st);
 hipError_t launch_posterior_hist(const double *x, const double *y, const double *W, int64_t S, double xlo, double xhi,

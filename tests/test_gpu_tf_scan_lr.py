@@ -1,4 +1,4 @@
-"""trpl_posterior_weights_lr and trpl_posterior_tf_scan_lr on the device (include/trpl.h; csrc/posterior_lr.hip): the posterior
+"""trpl_posterior_weights_lr and trpl_posterior_tf_scan_lr on the device (include/trpl.h; csrc/posterior.hip, csrc/posterior_scan.hip): the posterior
 weights and the temperature scan with a proposal log-ratio kept beside LL.
 
 Bit contract (np.array_equal, NaN matching NaN, no tolerance): with lnr = +0.0 every shared output is that of posterior.weights /

@@ -88,28 +88,66 @@ def _shared_constants():
     return {k: int(v) for k, v in re.findall(r"constexpr int (k[A-Za-z]+) = (\d+);", src)}
 
 
+def _code(src):
+    return re.sub(r"//[^\n]*", "", src)
+
+
 def test_the_shared_pieces_are_defined_once():
-    """The launch geometry, the weight expression and the fixed-order reductions live in posterior_common.hpp; neither
-    translation unit restates them."""
+    """The launch geometry, the weight expression, the sample sources and the fixed-order reductions live in
+    posterior_common.hpp; neither translation unit restates them, and the weight expression is one function."""
     c = _shared_constants()
     assert c == {"kThreads": 256, "kMaxBlocks": 1024, "kMaxDim": 16}
     common = open(os.path.join(CSRC, "posterior_common.hpp")).read()
     assert "tempered_weight" in common and "block_reduce" in common and "grid_for" in common
+    assert "struct Plain" in common and "struct Ratio" in common
     for unit in ("posterior.hip", "posterior_scan.hip"):
         src = open(os.path.join(CSRC, unit)).read()
-        assert '#include "posterior_common.hpp"' in src and "tempered_weight(" in src, unit
+        assert '#include "posterior_common.hpp"' in src and "tempered_weight<Src>(" in src, unit
         assert not re.search(r"constexpr int (kThreads|kMaxBlocks|kMaxDim)\b", src), unit
-        assert "exp(" not in re.sub(r"//[^\n]*", "", src) and "__shfl_xor" not in src and "grid_for(int64_t" not in src, unit
+        assert "exp(" not in _code(src) and "__shfl_xor" not in src and "grid_for(int64_t" not in src, unit
+        assert "two_sum(double" not in src and "two_sum(" not in _code(src), unit
+    # the three two_sums and the exp of the weight: one function of the header, and nowhere else in it
+    funcs = re.findall(r"^__device__ __forceinline__ double (\w+)\([^)]*\)\n\{\n(.*?)^\}", _code(common), flags=re.S | re.M)
+    holders = [name for name, body in funcs if "exp(" in body or "two_sum(two_sum(" in body]
+    assert holders == ["weight"], holders
+    body = dict(funcs)["weight"]
+    assert body.count("two_sum(") == 3 and body.count("exp(") == 1 and "fma(w, corr, w)" in body
+    assert _code(common).count("exp(") == 1 and _code(common).count("two_sum(two_sum(two_sum(") == 1
     mk = open(os.path.join(ROOT, "bayesian-inference-trpl_amd", "Makefile")).read()
-    rule = re.search(r"\$\(OBJ\)/posterior_scan\.o:[^\n]*\n\t([^\n]*)", mk)
-    assert rule and "-ffp-contract=off" in rule.group(1) and "$(OBJ)/posterior_scan.o $(OBJ)/sampler.o" in mk
+    for unit in ("posterior", "posterior_scan"):
+        rule = re.search(r"\$\(OBJ\)/%s\.o:[^\n]*\n\t([^\n]*)" % unit, mk)
+        assert rule and "-ffp-contract=off" in rule.group(1), unit
+    assert "$(OBJ)/posterior_scan.o $(OBJ)/sampler.o" in mk
+
+
+def kernels_of(lib_path, namespace):
+    """{kernel name with its template arguments} of a namespace in the library: a kernel is what has a launch stub"""
+    nm = subprocess.run(["nm", "-D", "--defined-only", lib_path], capture_output=True, text=True).stdout
+    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
+    assert "trpl::post::lr::" not in filt
+    return set(re.findall(r"\b%s::__device_stub__(\w+(?:<[^()]*>)?)\(" % re.escape(namespace), filt)), nm
+
+
+SCAN_KERNELS = ({"max_count_partial", "tiled_max_count_partial"} |
+                {"%s<trpl::post::%s>" % (k, src) for src in ("Plain", "Ratio")
+                 for k in ("weights_partial", "moments1_partial", "moments2_partial", "finish_kernel")})
+# (scale_kernel reads no sample and is no template: one kernel serves both sources)
+WEIGHTS_KERNELS = {"scale_kernel"} | {"%s<trpl::post::%s>" % (k, src) for src in ("Plain", "Ratio")
+                                      for k in ("nanmax_partial", "weights_partial")}
 
 
 def test_the_scan_kernels_are_in_the_shared_object(trpl):
+    """The exact set of instantiations: the tiled three and the finish kernel once per source, the two max kernels (untiled
+    for Plain, tiled for Ratio), and the single-temperature weights kernels of posterior.hip."""
     A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
-    have = set(re.findall(r"trpl::post::scan::__device_stub__(\w+)\(", filt))       # a kernel is what has a launch stub
-    assert have == {"max_count_partial", "weights_partial", "moments1_partial", "moments2_partial", "finish_kernel"}, sorted(have)
+    have, nm = kernels_of(A.LIB_PATH, "trpl::post::scan")
+    assert have == SCAN_KERNELS, sorted(have)
+    have, _ = kernels_of(A.LIB_PATH, "trpl::post")
+    assert {k for k in have if re.match(r"(nanmax_partial|weights_partial|scale_kernel|copy2_kernel|one_)", k)} == WEIGHTS_KERNELS, sorted(have)
+    stubs = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
+    for line in stubs.splitlines():                       # the source is the kernels' first argument, by value
+        m = re.search(r"__device_stub__\w+<trpl::post::(Plain|Ratio)>\((.*)\)$", line)
+        if m and "finish_kernel" not in line:
+            assert m.group(2).startswith("trpl::post::" + m.group(1)), line
     for name in NEW:
         assert re.search(r"\bT %s\b" % name, nm), name

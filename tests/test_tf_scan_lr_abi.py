@@ -1,7 +1,7 @@
 """trpl_posterior_weights_lr[_dev], trpl_posterior_tf_scan_lr[_dev] and trpl_posterior_tf_scan_lr_workspace (include/trpl.h: the
 posterior weights and the temperature scan with a proposal log-ratio kept beside LL): header, binding and library agree; every
 refusal the header states is TRPL_ERR_ARG with its argument named, with no device present; the workspace is 0 for refused shapes;
-the Makefile compiles the unit without contraction; the exports are only added (ABI 5).  No GPU needed."""
+the Makefile compiles the shared unit without contraction; the exports are only added (ABI 5).  No GPU needed."""
 import os
 import re
 import subprocess
@@ -131,12 +131,14 @@ def test_workspace_bytes(trpl):
 
 
 def test_the_unit_is_compiled_without_contraction_and_shares_the_reductions():
+    """The calls with a ratio are instantiations of the kernels of posterior_scan.hip and posterior.hip: no unit of their own."""
     mk = open(os.path.join(PKG, "Makefile")).read()
-    rule = re.search(r"\$\(OBJ\)/posterior_lr\.o:([^\n]*)\n\t([^\n]*)", mk)
+    rule = re.search(r"\$\(OBJ\)/posterior_scan\.o:([^\n]*)\n\t([^\n]*)", mk)
     assert rule and "-ffp-contract=off" in rule.group(2) and "posterior_common.hpp" in rule.group(1)
     link = re.search(r"^\$\(LIB\):([^\n]*)", mk, flags=re.M).group(1)
-    assert "$(OBJ)/posterior_lr.o" in link
-    src = open(os.path.join(PKG, "csrc", "posterior_lr.hip")).read()
+    assert "$(OBJ)/posterior_scan.o" in link and "posterior_lr.o" not in link and "posterior_lr" not in mk
+    assert not os.path.exists(os.path.join(PKG, "csrc", "posterior_lr.hip"))
+    src = open(os.path.join(PKG, "csrc", "posterior_scan.hip")).read()
     assert '#include "posterior_common.hpp"' in src
     assert not re.search(r"constexpr int (kThreads|kMaxBlocks|kMaxDim)\b", src)
     assert "__shfl_xor" not in src and "grid_for(int64_t" not in src and "two_sum(double" not in src
@@ -144,11 +146,14 @@ def test_the_unit_is_compiled_without_contraction_and_shares_the_reductions():
 
 
 def test_the_kernels_are_in_the_shared_object(trpl):
+    from test_tf_scan_abi import SCAN_KERNELS, WEIGHTS_KERNELS, kernels_of
     A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
-    have = set(re.findall(r"trpl::post::lr::__device_stub__(\w+)\(", filt))           # a kernel is what has a launch stub
-    assert have == {"max_count_partial", "weights_partial", "moments1_partial", "moments2_partial", "finish_kernel",
-                    "one_max_partial", "one_weights_partial", "one_scale_kernel"}, sorted(have)
+    have, nm = kernels_of(A.LIB_PATH, "trpl::post::scan")           # also asserts that no trpl::post::lr:: symbol remains
+    assert have == SCAN_KERNELS, sorted(have)
+    assert {k for k in have if k.endswith("<trpl::post::Ratio>")} == {
+        "weights_partial<trpl::post::Ratio>", "moments1_partial<trpl::post::Ratio>", "moments2_partial<trpl::post::Ratio>",
+        "finish_kernel<trpl::post::Ratio>"}
+    have, _ = kernels_of(A.LIB_PATH, "trpl::post")
+    assert WEIGHTS_KERNELS <= have, sorted(have)
     for name in NEW:
         assert re.search(r"\bT %s\b" % name, nm), name
