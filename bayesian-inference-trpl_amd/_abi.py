@@ -205,6 +205,12 @@ SIGNATURES = {
     "trpl_refine_density": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _pd],
     "trpl_refine_unit_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _u32, _i32, _vp, _vp],
     "trpl_refine_unit": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _u32, _i32, _vp, _i32, _pd],
+    "trpl_refine_affine_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp],
+    "trpl_refine_affine": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _pd],
+    "trpl_refine_draw_oriented_dev": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp,
+                                      _vp, _vp],
+    "trpl_refine_draw_oriented": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp,
+                                  _i32, _pd],
     "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
     "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
 }

@@ -27,25 +27,15 @@
 #include <stdint.h>
 
 #include "api_util.hpp"
+#include "refine_common.hpp"
 
 namespace trpl {
 namespace refine {
 
-constexpr int kThreads = 256;
 constexpr int kRows = 16;                                        // consecutive rows one thread adds
 constexpr int kChunk = kThreads * kRows;                         // rows of one chunk: 32 KiB of cumulative weights in LDS
 constexpr int kTile = 128;                                       // parents per LDS tile: (2 * 16 + 1) * 8 * 128 = 33 KiB at A = 16
 constexpr int kPrefixTile = 1024;                                // chunk totals staged per round of the prefix kernel
-
-struct Box {
-    double lo[16], hi[16];     // bounds as sample_box receives them
-    double l[16], lh[16];      // log10 of both for the log columns (host libm)
-    int32_t do_log[16];
-    int32_t act[16];           // active index -> column
-    int32_t fixed[16];         // column -> 1: lo == hi, the value is lo
-    int32_t ncol, A;
-    uint32_t flags;            // TRPL_BOX_EQUAL_*
-};
 
 __device__ __forceinline__ double used(double w) { return w > 0.0 ? w : 0.0; }      // NaN and <= 0 count as 0
 
@@ -219,23 +209,7 @@ __global__ void __launch_bounds__(kThreads) resample_kernel(const double *W, int
     }
 }
 
-// ---- Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC 2011)
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ double res53(uint32_t x, uint32_t y)                  // genrand_res53, as csrc/sampler.hip forms it
-{
-    return ((double)(x >> 5) * 67108864.0 + (double)(y >> 6)) / 9007199254740992.0;
-}
-
+// Philox4x32-10, genrand_res53 and the expressions of a row of X: refine_common.hpp, shared with the oriented draw
 __global__ void __launch_bounds__(kThreads) draw_kernel(const double *a, const double *b, int64_t K, int64_t n_uniform, int64_t total,
                                                         uint32_t seed_lo, uint32_t seed_hi, uint32_t generation, const Box bx, double *U2,
                                                         double *X2)
@@ -246,8 +220,7 @@ __global__ void __launch_bounds__(kThreads) draw_kernel(const double *a, const d
     const int64_t par = uni ? 0 : (n - n_uniform) % K;
     const double *pa = a + par * bx.A, *pb = b + par * bx.A;
     double *row = X2 + n * bx.ncol;
-    for (int c = 0; c < bx.ncol; c++)
-        if (bx.fixed[c]) row[c] = bx.lo[c];
+    put_fixed(bx, row);
     for (int j = 0; 2 * j < bx.A; j++) {
         uint32_t r[4];
         philox4x32_10((uint32_t)n, (uint32_t)((uint64_t)n >> 32), (uint32_t)j, generation, seed_lo, seed_hi, r);
@@ -261,12 +234,10 @@ __global__ void __launch_bounds__(kThreads) draw_kernel(const double *a, const d
             u = u < hi ? u : hi;                                 // min(b, .)
             U2[n * bx.A + d] = u;
             const int c = bx.act[d];
-            row[c] = bx.do_log[c] ? pow(10.0, bx.l[c] + (bx.lh[c] - bx.l[c]) * u) : bx.lo[c] + (bx.hi[c] - bx.lo[c]) * u;
+            row[c] = column_value(bx, c, u);
         }
     }
-    if ((bx.flags & TRPL_BOX_EQUAL_MU) && bx.ncol > 3) row[2] = row[3];
-    if ((bx.flags & TRPL_BOX_EQUAL_S) && bx.ncol > 6) row[6] = row[5];
-    if ((bx.flags & TRPL_BOX_EQUAL_AUGER) && bx.ncol > 8) row[8] = row[7];
+    put_overrides(bx, row);
 }
 
 __global__ void __launch_bounds__(kThreads) unit_kernel(const double *X, int64_t S, int64_t ldx, const Box bx, double *U)
@@ -323,46 +294,7 @@ static void launch_density(unsigned grid, hipStream_t st, const double *U, int64
 
 using namespace trpl;
 
-static const int64_t kMaxBlocks = 0x7fffffff;                    // gridDim.x
-
-static int check_counts(int64_t K, int32_t A)
-{
-    if (K < 1 || K > TRPL_REFINE_MAX_PARENTS)
-        return api_fail(TRPL_ERR_ARG, "K=%lld must be in [1, TRPL_REFINE_MAX_PARENTS = %d]", (long long)K, TRPL_REFINE_MAX_PARENTS);
-    if (A < 1 || A > TRPL_REFINE_MAX_DIMS) return api_fail(TRPL_ERR_ARG, "A=%d must be in [1, %d]", A, TRPL_REFINE_MAX_DIMS);
-    return TRPL_OK;
-}
-
-// the box as sample_box takes it -> the kernels' view; refuses a box whose number of active columns is not A
-static int make_box(int32_t ncol, const double *lo, const double *hi, const int32_t *do_log, uint32_t flags, int32_t A, refine::Box &bx)
-{
-    if (ncol < 1 || ncol > 16) return api_fail(TRPL_ERR_ARG, "ncol=%d must be in [1, 16]", ncol);
-    if (!lo) return api_fail(TRPL_ERR_ARG, "lo is NULL");
-    if (!hi) return api_fail(TRPL_ERR_ARG, "hi is NULL");
-    if (!do_log) return api_fail(TRPL_ERR_ARG, "do_log is NULL");
-    if (flags & ~(uint32_t)(TRPL_BOX_EQUAL_MU | TRPL_BOX_EQUAL_S | TRPL_BOX_EQUAL_AUGER))
-        return api_fail(TRPL_ERR_ARG, "flags=0x%x: only the TRPL_BOX_EQUAL_* bits apply", flags);
-    bx = refine::Box();
-    bx.ncol = ncol; bx.flags = flags;
-    int n = 0;
-    for (int c = 0; c < ncol; c++) {
-        if (!(lo[c] <= hi[c])) return api_fail(TRPL_ERR_ARG, "column %d: lo must be <= hi", c);
-        if (do_log[c] && lo[c] != hi[c] && !(lo[c] > 0)) return api_fail(TRPL_ERR_ARG, "column %d: log-uniform needs lo > 0", c);
-        const bool target = (c == 2 && (flags & TRPL_BOX_EQUAL_MU) && ncol > 3) || (c == 6 && (flags & TRPL_BOX_EQUAL_S)) ||
-                            (c == 8 && (flags & TRPL_BOX_EQUAL_AUGER));
-        bx.lo[c] = lo[c]; bx.hi[c] = hi[c];
-        bx.fixed[c] = lo[c] == hi[c];
-        bx.do_log[c] = do_log[c] != 0 && !bx.fixed[c];
-        if (bx.do_log[c]) { bx.l[c] = log10(lo[c]); bx.lh[c] = log10(hi[c]); }
-        if (!bx.fixed[c] && !target) {
-            if (n < 16) bx.act[n] = c;
-            n++;
-        }
-    }
-    if (n != A) return api_fail(TRPL_ERR_ARG, "A=%d, but the box has %d active columns", A, n);
-    bx.A = A;
-    return TRPL_OK;
-}
+static const int64_t kMaxBlocks = kRefineMaxBlocks;
 
 static int check_resample(const void *W, int64_t S, int64_t K, double offset, const void *idx)
 {
@@ -377,12 +309,8 @@ static int check_resample(const void *W, int64_t S, int64_t K, double offset, co
 
 static int check_draw(const void *a, const void *b, int64_t K, int32_t A, int64_t m, int64_t n_uniform, const void *U2, const void *X2)
 {
-    if (int rc = check_counts(K, A)) return rc;
-    if (m < 0) return api_fail(TRPL_ERR_ARG, "m=%lld must be >= 0", (long long)m);
-    if (n_uniform < 0) return api_fail(TRPL_ERR_ARG, "n_uniform=%lld must be >= 0", (long long)n_uniform);
-    if (m > (kMaxBlocks - 1) / K || n_uniform > kMaxBlocks - 1 - K * m)
-        return api_fail(TRPL_ERR_ARG, "n_uniform=%lld + K * m = %lld * %lld is more than 2^31 - 2 children", (long long)n_uniform, (long long)K,
-                        (long long)m);
+    if (int rc = refine_check_counts(K, A)) return rc;
+    if (int rc = refine_check_children(K, m, n_uniform)) return rc;
     if (!a) return api_fail(TRPL_ERR_ARG, "a is NULL");
     if (!b) return api_fail(TRPL_ERR_ARG, "b is NULL");
     if (!U2) return api_fail(TRPL_ERR_ARG, "U2 is NULL");
@@ -394,7 +322,7 @@ static int check_density(const void *U, int64_t S, int64_t ldu, int32_t A, const
                          const void *B)
 {
     if (S < 0) return api_fail(TRPL_ERR_ARG, "S=%lld must be >= 0", (long long)S);
-    if (int rc = check_counts(K, A)) return rc;
+    if (int rc = refine_check_counts(K, A)) return rc;
     if (ldu < A) return api_fail(TRPL_ERR_ARG, "ldu=%lld must be >= A=%d", (long long)ldu, A);
     if ((S + refine::kThreads - 1) / refine::kThreads > kMaxBlocks)
         return api_fail(TRPL_ERR_ARG, "S=%lld is more than 2^31 - 1 blocks of %d samples", (long long)S, refine::kThreads);
@@ -482,7 +410,7 @@ int trpl_refine_draw_dev(const double *a, const double *b, int64_t K, int32_t A,
 {
     if (int rc = check_draw(a, b, K, A, m, n_uniform, U2, X2)) return rc;
     refine::Box bx;
-    if (int rc = make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
+    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
     const int64_t total = n_uniform + K * m;
     if (total == 0) return TRPL_OK;
     const int64_t nblk = (total + refine::kThreads - 1) / refine::kThreads;
@@ -500,7 +428,7 @@ int trpl_refine_draw(const double *a, const double *b, int64_t K, int32_t A, int
     if (seconds) *seconds = 0.0;
     if (int rc = check_draw(a, b, K, A, m, n_uniform, U2, X2)) return rc;
     refine::Box bx;
-    if (int rc = make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
+    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
     const int64_t total = n_uniform + K * m;
     if (total == 0) return TRPL_OK;
     if (int rc = select_device(device)) return rc;
@@ -575,7 +503,7 @@ int trpl_refine_unit_dev(const double *X, int64_t S, int64_t ldx, int32_t ncol, 
                          uint32_t flags, int32_t A, double *U, void *stream)
 {
     refine::Box bx;
-    if (int rc = make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
+    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
     if (int rc = check_unit(X, S, ldx, ncol, A, U)) return rc;
     if (S == 0) return TRPL_OK;
     const unsigned grid = (unsigned)((S + refine::kThreads - 1) / refine::kThreads);
@@ -590,7 +518,7 @@ int trpl_refine_unit(const double *X, int64_t S, int64_t ldx, int32_t ncol, cons
 {
     if (seconds) *seconds = 0.0;
     refine::Box bx;
-    if (int rc = make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
+    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
     if (int rc = check_unit(X, S, ldx, ncol, A, U)) return rc;
     if (S == 0) return TRPL_OK;
     if (int rc = select_device(device)) return rc;

@@ -569,6 +569,45 @@ def refine_unit_device(X, minX, maxX, do_log, U, flags=0):
         U.shape[1], _chk(U, torch.float64, "U"), _stream()))
 
 
+def refine_affine_device(U, M, c, Z, A=None):
+    """trpl_refine_affine_dev: Z (S, ldz >= A) <- M (U (S, ldu >= A) - c); M (A, A) lower triangular and c (A,) host arrays (only
+    j <= i of M is read), z_i = sum_{j <= i} M_ij (u_j - c_j) in ascending j."""
+    import torch
+    M = np.ascontiguousarray(M, dtype=np.float64)
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    if U.dim() != 2 or Z.dim() != 2 or Z.shape[0] != U.shape[0] or M.ndim != 2 or M.shape[0] != M.shape[1] or c.shape != (M.shape[0],):
+        raise ValueError("U must be (S, ldu), Z (S, ldz), M (A, A) and c (A,)")
+    if A is not None and int(A) != M.shape[0]:
+        raise ValueError("A must be M's number of dimensions")
+    _abi.check(_abi.lib().trpl_refine_affine_dev(
+        _chk(U, torch.float64, "U"), U.shape[0], U.shape[1], M.shape[0], _abi.ptr(M), _abi.ptr(c), _chk(Z, torch.float64, "Z"),
+        Z.shape[1], _stream()))
+
+
+def refine_draw_oriented_device(zc, h, L, c, m, n_uniform, seed, generation, minX, maxX, do_log, Z2, U2, X2, inside, flags=0):
+    """trpl_refine_draw_oriented_dev: the n_uniform + K m children of the boxes [zc - h, zc + h] in z, zc (K, A) f64 on the device;
+    h (A,), L (A, A) lower triangular and c (A,) host arrays.  Z2, U2 (S_g, A), X2 (S_g, ncol) f64 and inside (S_g,) int32 (0: the
+    child left the unit cube; it is not to be solved)."""
+    import torch
+    lo, hi, lg = _refine_box(minX, maxX, do_log)
+    h = np.ascontiguousarray(h, dtype=np.float64)
+    L = np.ascontiguousarray(L, dtype=np.float64)
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    if zc.dim() != 2:
+        raise ValueError("zc must be (K, A)")
+    K, A = zc.shape
+    if h.shape != (A,) or L.shape != (A, A) or c.shape != (A,):
+        raise ValueError("h must be (A,), L (A, A) and c (A,)")
+    total = int(n_uniform) + K * int(m)
+    if tuple(Z2.shape) != (total, A) or tuple(U2.shape) != (total, A) or tuple(X2.shape) != (total, lo.size) or tuple(inside.shape) != (total,):
+        raise ValueError("Z2 and U2 must be (n_uniform + K m, A), X2 (n_uniform + K m, ncol) and inside (n_uniform + K m,)")
+    _abi.check(_abi.lib().trpl_refine_draw_oriented_dev(
+        _chk(zc, torch.float64, "zc"), _abi.ptr(h), _abi.ptr(L), _abi.ptr(c), K, A, int(m), int(n_uniform),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(generation) & 0xFFFFFFFF, lo.size, _abi.ptr(lo), _abi.ptr(hi), _abi.ptr(lg), int(flags),
+        _chk(Z2, torch.float64, "Z2"), _chk(U2, torch.float64, "U2"), _chk(X2, torch.float64, "X2"), _chk(inside, torch.int32, "inside"),
+        _stream()))
+
+
 def credible_interval_device(x, W, lo=0.025, hi=0.975):
     """utils.py:185-196 on the device: sort by x, cumulate the weights, last point below `lo` and first
     above `hi` (torch.sort / cumsum: library plumbing, no custom kernel)."""

@@ -1126,6 +1126,58 @@ int trpl_refine_unit(const double *X, int64_t S, int64_t ldx, int32_t ncol, cons
                      uint32_t flags, int32_t A, double *U, int32_t device, double *seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_refine_affine, trpl_refine_draw_oriented -- oriented proposals: the boxes of a generation are axis-parallel in WHITENED
+ * coordinates z = M (u - c) instead of in u, so that they follow a posterior ridge that lies across the axes (B * p0 = const is a
+ * straight line at 45 degrees in the log10 unit coordinates).  (csrc/refine_oriented.hip)
+ *
+ * Orientation of a generation with A active columns (formed on the host from the device's weighted moments, A <= 16): c the
+ * weighted mean of U and Sigma its weighted covariance under the weights the proposal is built from; diagonal floor
+ * Sigma_dd >= (S1^(-1/A) / 2)^2 / 3 (the variance of the axis-parallel scheme's floor half-width); shrinkage Sigma_s = (1 - lam)
+ * Sigma + lam diag(Sigma), lam = clip((A + 1) / ESS, 0, 1) unless given; L = chol(Sigma_s) lower, M = L^-1 lower, logdet = sum ln
+ * L_dd.  Half-widths in z: h_d = sqrt(3) ESS^(-1 / (A + 4)) for every d (a whitened column has deviation 1).  Parent k is
+ * z_k = M (u_k - c) with the box [z_k - h, z_k + h], NOT clipped; inv_vol = 1 / (prod_d 2 h_d * exp(logdet)), the same for every
+ * parent, is the density in u.
+ *
+ * Arithmetic, bit-pinned: z_i = sum_{j <= i} M_ij * (u_j - c_j) and u_i = c_i + sum_{j <= i} L_ij * z_j, j ascending from +0.0:
+ * subtract, multiply, add, no contraction.  Only the lower triangles (j <= i) of the host matrices M and L ([A][A] row-major) are
+ * read.
+ *
+ * trpl_refine_affine: Z [S][ldz >= A] <- M (U [S][ldu >= A] - c), one thread per sample.
+ *
+ * trpl_refine_draw_oriented: zc [K][A] the parents in z (device memory in the _dev form), h [A], L, c HOST arrays.  The
+ * n_uniform + K m children are counted and keyed as in trpl_refine_draw (Philox4x32-10, counter (n low, n high, j, generation),
+ * call j -> dimensions 2j, 2j + 1, genrand_res53).  Child n_uniform + j of parent k = j mod K: z_d = zc_kd + h_d * (2 xi_d - 1),
+ * u = c + L z.  A uniform child: u_d = xi_d, and its row of Z2 is NaN (no z was drawn).  X2 by trpl_refine_draw's expressions from
+ * u.  inside[n] (int32) = 1 when every u_d lies in [0, 1], else 0: a child OUTSIDE the cube keeps its u and a finite X slightly
+ * beyond the prior box, is never solved, and enters the population with LL = -inf; it counts in S_total, which keeps the mixture
+ * proportions and therefore r(u) exact (rejection and redraw would not).  Uniform children are always inside.
+ *
+ * Density: B_g(u) = sum_k inv_vol * 1[z_k - h <= M_g (u - c_g) <= z_k + h] is trpl_refine_density on Z_g = trpl_refine_affine(U)
+ * with a = zc - h, b = zc + h, unchanged: k ascending, one fp64 add per member box from +0.0.  r(u) keeps its form; every
+ * generation carries its own (M_g, c_g), and a generation built without orientation contributes its term as before.
+ *
+ * Refused with TRPL_ERR_ARG before a device is touched: a NULL U, M, c, Z, zc, h, L, Z2, U2, X2, inside, lo, hi, do_log; A outside
+ * [1, 16] or not the box's count; ldu < A; ldz < A; S < 1; K < 1 or K > TRPL_REFINE_MAX_PARENTS; m < 0; n_uniform < 0; more than
+ * 2^31 - 2 children; a non-finite entry of M, L (lower triangle), c or h; a diagonal of M or L that is not > 0; h_d <= 0.  The _dev
+ * calls take device pointers for U, Z, zc, Z2, U2, X2, inside, allocate nothing and never synchronise.
+ * Python: trpl_amd.refine.orientation / affine / make_proposal(oriented=True), trpl_amd.device.refine_affine_device,
+ * refine_draw_oriented_device.
+ * ------------------------------------------------------------------------------------- */
+int trpl_refine_affine_dev(const double *U, int64_t S, int64_t ldu, int32_t A, const double *M /*host [A][A] row-major, lower*/,
+                           const double *c /*host [A]*/, double *Z, int64_t ldz, void *stream);
+int trpl_refine_affine(const double *U, int64_t S, int64_t ldu, int32_t A, const double *M, const double *c, double *Z, int64_t ldz,
+                       int32_t device, double *seconds);
+int trpl_refine_draw_oriented_dev(const double *zc, const double *h /*host [A]*/, const double *L /*host [A][A] row-major, lower*/,
+                                  const double *c /*host [A]*/, int64_t K, int32_t A, int64_t m, int64_t n_uniform, uint64_t seed,
+                                  uint32_t generation, int32_t ncol, const double *lo /*host*/, const double *hi /*host*/,
+                                  const int32_t *do_log /*host*/, uint32_t flags, double *Z2, double *U2, double *X2, int32_t *inside,
+                                  void *stream);
+int trpl_refine_draw_oriented(const double *zc, const double *h, const double *L, const double *c, int64_t K, int32_t A, int64_t m,
+                              int64_t n_uniform, uint64_t seed, uint32_t generation, int32_t ncol, const double *lo, const double *hi,
+                              const int32_t *do_log, uint32_t flags, double *Z2, double *U2, double *X2, int32_t *inside,
+                              int32_t device, double *seconds);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the
  * measurement plan): S independent systems  ld[i] x[i-1] + d[i] x[i] + ud[i] x[i+1] = b[i],
  * i < L, the problem pcreduce solves (pvSimPCR.py:42-81), operands and result in HBM, arrays

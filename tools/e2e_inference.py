@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -24,6 +24,10 @@ samples -- and seconds["refine"]; without it the output is unchanged.
 effective sample size of N (refine.run(target_ess=N): the temperature ladder, through the log-ratio scan) and adds "target_ess",
 "tf_per_generation" and "ess_at_tf" (the union's effective sample size at the final temperature after each generation) to "refine";
 tf per generation and the final effective sample size are printed.
+--oriented (with --refine) draws every generation in boxes that are axis-parallel in the whitened coordinates of the union so far
+(refine.run(oriented=True): DESIGN.md section 22) and adds "oriented", "outside_share_of_children" (the children that left the prior
+box: never solved, weight 0) and "shrinkage_per_generation" to "refine"; --shrink x fixes the covariance shrinkage instead of
+(A + 1) / ESS.
 --find-tf with --refine also searches the temperature of largest uncertainty over the refined union, its proposal log-ratio kept
 beside the likelihoods (posterior.calc_max_uncertainty(log_ratio=)), as refine["max_uncertainty"].
 """
@@ -47,7 +51,13 @@ if "--target-ess" in sys.argv:
     k = sys.argv.index("--target-ess")
     TARGET_ESS = float(sys.argv[k + 1])
     del sys.argv[k:k + 2]
-sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine")]
+ORIENTED = "--oriented" in sys.argv
+SHRINK = None
+if "--shrink" in sys.argv:
+    k = sys.argv.index("--shrink")
+    SHRINK = float(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
+sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented")]
 import numpy as np
 import torch
 import trpl_amd
@@ -182,7 +192,7 @@ if REFINE:
     K = max(1, min(1024, S // 32))
     rinfo = {}
     pop = refine.run(fused, X.cpu().numpy(), P.cpu().numpy(), lo, hi, lg, rounds=ROUNDS, K=K, m=28, n_uniform=max(1, S // 8), tf=tf,
-                     seed=42, info=rinfo, target_ess=TARGET_ESS)
+                     seed=42, info=rinfo, target_ess=TARGET_ESS, **({"oriented": True, "shrink": SHRINK} if ORIENTED else {}))
     X_all, LLc = pop.corrected(tf)
     W_all = posterior.weights(LLc, tf)
     LL_all = np.concatenate(pop.LL)
@@ -193,6 +203,10 @@ if REFINE:
                      "nan_llc_from_finite_ll": int(np.sum(np.isnan(LLc) & np.isfinite(LL_all)))}
     print("refine: effective sample size per generation %s, share of children with a weight > 0 %s"
           % (["%.2f" % e for e in rinfo["ess"]], ["%.4f" % f for f in rinfo["nonzero"]]), file=sys.stderr)
+    if ORIENTED:
+        out["refine"].update(oriented=True, outside_share_of_children=rinfo["outside"], shrinkage_per_generation=rinfo["lam"])
+        print("refine: oriented, share of children outside the prior box %s, shrinkage %s"
+              % (["%.4f" % f for f in rinfo["outside"]], ["%.3f" % f for f in rinfo["lam"]]), file=sys.stderr)
     if TARGET_ESS is not None:
         out["refine"].update(target_ess=TARGET_ESS, tf_per_generation=rinfo["tfs"], ess_at_tf=rinfo["ess_at_tf"])
         print("refine: target %g, final tf %g; tf per generation %s; effective sample size at the final tf %s, final %.2f"
