@@ -211,6 +211,12 @@ SIGNATURES = {
                                       _vp, _vp],
     "trpl_refine_draw_oriented": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp,
                                   _i32, _pd],
+    "trpl_mcmc_propose_dev": [_vp, _vp, _i64, _i64, _i32, _f64, _vp, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp],
+    "trpl_mcmc_propose": [_vp, _vp, _i64, _i64, _i32, _f64, _vp, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _i32, _pd],
+    "trpl_mcmc_accept_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f64, _i64, _u64, _u32, _vp, _vp],
+    "trpl_mcmc_accept": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f64, _i64, _u64, _u32, _vp, _i32, _pd],
+    "trpl_mcmc_chain_stats_dev": [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp],
+    "trpl_mcmc_chain_stats": [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _pd],
     "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
     "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
 }

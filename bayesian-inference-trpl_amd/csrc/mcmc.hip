@@ -1,0 +1,351 @@
+// Ensemble Metropolis sampling (trpl_mcmc_propose*, trpl_mcmc_accept*, trpl_mcmc_chain_stats*, include/trpl.h): the cheap half of a
+// Markov-chain sampler whose expensive half, the likelihood of every chain's proposal, is one launch of the fused likelihood.
+//
+//   propose_kernel<A>     one thread per chain.  The uniforms are the refinement draws' (Philox4x32-10, genrand_res53:
+//       refine_common.hpp) with the counter's third word moved to 0x100 + j: call j < 8 gives xi[2j], xi[2j + 1], call 8 the two
+//       partner uniforms.  With partners (differential evolution, ter Braak 2006): u'_d = (u_d + gamma (pa_d - pb_d)) + scale_d (2
+//       xi_d - 1); without (random walk): u'_d = u_d + scale_d (2 xi_d - 1).  inside = every u'_d in [0, 1]; X by the sampler's
+//       expressions from u', inside or not, as draw_oriented_kernel forms it.
+//   accept_kernel<A>      one thread per chain.  xi of counter word 0x109; the chain takes its proposal's U, X and LL when the
+//       proposal is inside, its LLp is neither NaN nor -inf, and the chain stands on a likelihood that is not above -inf, or
+//       d = (LLp - LL) / tf >= 0, or log(xi) < d.
+//   chain_stats_kernel    one thread per column q of a history H [n][ldh]: the mean and the centred sum of squares over the steps
+//       [t0, t1), both sums in ascending t from +0.0.  Adjacent threads read adjacent addresses.
+// Compiled with -ffp-contract=off like refine.hip: every result is its expression with one rounding per operation.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "api_util.hpp"
+#include "refine_common.hpp"
+
+namespace trpl {
+namespace mcmc {                                                 // the kernels of this unit; the box, Philox and X are trpl::refine's
+
+using namespace refine;
+
+constexpr uint32_t kStream = 0x100;                              // third counter word: 0x100 + j, apart from the draws' j < 8
+constexpr uint32_t kPartnerCall = 8, kAcceptCall = 9;
+
+struct Scale {
+    double s[16];
+};
+
+template <int A>
+__global__ void __launch_bounds__(kThreads) propose_kernel(const double *U, const double *partners, int64_t count, int64_t P,
+                                                           double gamma, const Scale sc, int64_t chain0, uint32_t seed_lo,
+                                                           uint32_t seed_hi, uint32_t step, const Box bx, double *Up, double *Xp,
+                                                           int32_t *inside)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t n = (uint64_t)(chain0 + i);
+    double xi[A];
+#pragma unroll
+    for (int j = 0; 2 * j < A; j++) {
+        uint32_t r[4];
+        philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), kStream + (uint32_t)j, step, seed_lo, seed_hi, r);
+        xi[2 * j] = res53(r[0], r[1]);
+        if (2 * j + 1 < A) xi[2 * j + 1] = res53(r[2], r[3]);
+    }
+    double u[A];
+#pragma unroll
+    for (int d = 0; d < A; d++) u[d] = U[i * A + d];
+    if (P >= 2) {
+        uint32_t r[4];
+        philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), kStream + kPartnerCall, step, seed_lo, seed_hi, r);
+        const double xa = res53(r[0], r[1]), xb = res53(r[2], r[3]);
+        int64_t a = (int64_t)(xa * (double)P), b = (int64_t)(xb * (double)(P - 1));
+        a = a < P - 1 ? a : P - 1;
+        b = b < P - 2 ? b : P - 2;
+        b += b >= a;
+        const double *pa = partners + a * A, *pb = partners + b * A;
+#pragma unroll
+        for (int d = 0; d < A; d++) u[d] = u[d] + gamma * (pa[d] - pb[d]);
+    }
+    bool in = true;
+    double *row = Xp + i * bx.ncol;
+    put_fixed(bx, row);
+#pragma unroll
+    for (int d = 0; d < A; d++) {
+        u[d] = u[d] + sc.s[d] * (2.0 * xi[d] - 1.0);
+        in = in && u[d] >= 0.0 && u[d] <= 1.0;                   // a NaN is outside
+        Up[i * A + d] = u[d];
+        const int c = bx.act[d];
+        row[c] = column_value(bx, c, u[d]);
+    }
+    put_overrides(bx, row);
+    inside[i] = in ? 1 : 0;
+}
+
+template <int A>
+__global__ void __launch_bounds__(kThreads) accept_kernel(double *U, double *X, double *LL, const double *Up, const double *Xp,
+                                                          const double *LLp, const int32_t *inside, int64_t count, int32_t ncol,
+                                                          double tf, int64_t chain0, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
+                                                          int32_t *accepted)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t n = (uint64_t)(chain0 + i);
+    uint32_t r[4];
+    philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), kStream + kAcceptCall, step, seed_lo, seed_hi, r);
+    const double xi = res53(r[0], r[1]);
+    const double ll = LL[i], llp = LLp[i];
+    const double d = (llp - ll) / tf;
+    const bool take = inside[i] != 0 && !(llp != llp) && llp > -INFINITY && (!(ll > -INFINITY) || d >= 0.0 || log(xi) < d);
+    accepted[i] = take ? 1 : 0;
+    if (!take) return;
+#pragma unroll
+    for (int k = 0; k < A; k++) U[i * A + k] = Up[i * A + k];
+    for (int c = 0; c < ncol; c++) X[i * ncol + c] = Xp[i * ncol + c];
+    LL[i] = llp;
+}
+
+__global__ void __launch_bounds__(kThreads) chain_stats_kernel(const double *H, int64_t ldh, int64_t Q, int64_t t0, int64_t t1,
+                                                               double *mean, double *m2)
+{
+    const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (q >= Q) return;
+    double s = 0.0;
+    for (int64_t t = t0; t < t1; t++) s = s + H[t * ldh + q];
+    const double mu = s / (double)(t1 - t0);
+    double v = 0.0;
+    for (int64_t t = t0; t < t1; t++) {
+        const double e = H[t * ldh + q] - mu;
+        v = v + e * e;
+    }
+    mean[q] = mu;
+    m2[q] = v;
+}
+
+template <int A>
+static void launch_propose(unsigned grid, hipStream_t st, const double *U, const double *partners, int64_t count, int64_t P, double gamma,
+                           const Scale &sc, int64_t chain0, uint64_t seed, uint32_t step, const Box &bx, double *Up, double *Xp,
+                           int32_t *inside)
+{
+    hipLaunchKernelGGL(propose_kernel<A>, dim3(grid), dim3(kThreads), 0, st, U, partners, count, P, gamma, sc, chain0, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), step, bx, Up, Xp, inside);
+}
+
+template <int A>
+static void launch_accept(unsigned grid, hipStream_t st, double *U, double *X, double *LL, const double *Up, const double *Xp,
+                          const double *LLp, const int32_t *inside, int64_t count, int32_t ncol, double tf, int64_t chain0, uint64_t seed,
+                          uint32_t step, int32_t *accepted)
+{
+    hipLaunchKernelGGL(accept_kernel<A>, dim3(grid), dim3(kThreads), 0, st, U, X, LL, Up, Xp, LLp, inside, count, ncol, tf, chain0,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), step, accepted);
+}
+
+}  // namespace mcmc
+}  // namespace trpl
+
+using namespace trpl;
+
+#define TRPL_MCMC_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+
+static int check_chains(int64_t count, int32_t A, int64_t chain0)
+{
+    if (count < 1) return api_fail(TRPL_ERR_ARG, "count=%lld must be >= 1", (long long)count);
+    if ((count + refine::kThreads - 1) / refine::kThreads > kRefineMaxBlocks)
+        return api_fail(TRPL_ERR_ARG, "count=%lld is more than 2^31 - 1 blocks of %d chains", (long long)count, refine::kThreads);
+    if (A < 1 || A > TRPL_REFINE_MAX_DIMS) return api_fail(TRPL_ERR_ARG, "A=%d must be in [1, %d]", A, TRPL_REFINE_MAX_DIMS);
+    if (chain0 < 0) return api_fail(TRPL_ERR_ARG, "chain0=%lld must be >= 0", (long long)chain0);
+    return TRPL_OK;
+}
+
+static int check_propose(const void *U, const void *partners, int64_t count, int64_t P, int32_t A, double gamma, const double *scale,
+                         int64_t chain0, const void *Up, const void *Xp, const void *inside, mcmc::Scale &sc)
+{
+    if (int rc = check_chains(count, A, chain0)) return rc;
+    if (P < 0 || P == 1) return api_fail(TRPL_ERR_ARG, "P=%lld must be 0 (random walk) or >= 2", (long long)P);
+    if (P > 0 && !partners) return api_fail(TRPL_ERR_ARG, "partners is NULL with P=%lld", (long long)P);
+    if (!U) return api_fail(TRPL_ERR_ARG, "U is NULL");
+    if (!scale) return api_fail(TRPL_ERR_ARG, "scale is NULL");
+    if (!Up) return api_fail(TRPL_ERR_ARG, "Up is NULL");
+    if (!Xp) return api_fail(TRPL_ERR_ARG, "Xp is NULL");
+    if (!inside) return api_fail(TRPL_ERR_ARG, "inside is NULL");
+    if (!isfinite(gamma)) return api_fail(TRPL_ERR_ARG, "gamma=%g must be finite", gamma);
+    sc = mcmc::Scale();
+    for (int d = 0; d < A; d++) {
+        if (!(isfinite(scale[d]) && scale[d] >= 0.0)) return api_fail(TRPL_ERR_ARG, "scale[%d]=%g must be finite and >= 0", d, scale[d]);
+        sc.s[d] = scale[d];
+    }
+    return TRPL_OK;
+}
+
+static int check_accept(const void *U, const void *X, const void *LL, const void *Up, const void *Xp, const void *LLp, const void *inside,
+                        int64_t count, int32_t A, int32_t ncol, double tf, int64_t chain0, const void *accepted)
+{
+    if (int rc = check_chains(count, A, chain0)) return rc;
+    if (ncol < 1 || ncol > 16) return api_fail(TRPL_ERR_ARG, "ncol=%d must be in [1, 16]", ncol);
+    if (!(isfinite(tf) && tf > 0.0)) return api_fail(TRPL_ERR_ARG, "tf=%g must be finite and > 0", tf);
+    if (!U) return api_fail(TRPL_ERR_ARG, "U is NULL");
+    if (!X) return api_fail(TRPL_ERR_ARG, "X is NULL");
+    if (!LL) return api_fail(TRPL_ERR_ARG, "LL is NULL");
+    if (!Up) return api_fail(TRPL_ERR_ARG, "Up is NULL");
+    if (!Xp) return api_fail(TRPL_ERR_ARG, "Xp is NULL");
+    if (!LLp) return api_fail(TRPL_ERR_ARG, "LLp is NULL");
+    if (!inside) return api_fail(TRPL_ERR_ARG, "inside is NULL");
+    if (!accepted) return api_fail(TRPL_ERR_ARG, "accepted is NULL");
+    return TRPL_OK;
+}
+
+static int check_chain_stats(const void *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, const void *mean, const void *m2)
+{
+    if (n < 1) return api_fail(TRPL_ERR_ARG, "n=%lld must be >= 1", (long long)n);
+    if (Q < 1) return api_fail(TRPL_ERR_ARG, "Q=%lld must be >= 1", (long long)Q);
+    if ((Q + refine::kThreads - 1) / refine::kThreads > kRefineMaxBlocks)
+        return api_fail(TRPL_ERR_ARG, "Q=%lld is more than 2^31 - 1 blocks of %d columns", (long long)Q, refine::kThreads);
+    if (ldh < Q) return api_fail(TRPL_ERR_ARG, "ldh=%lld must be >= Q=%lld", (long long)ldh, (long long)Q);
+    if (!(0 <= t0 && t0 < t1 && t1 <= n))
+        return api_fail(TRPL_ERR_ARG, "t0=%lld, t1=%lld: the range must satisfy 0 <= t0 < t1 <= n=%lld", (long long)t0, (long long)t1,
+                        (long long)n);
+    if (!H) return api_fail(TRPL_ERR_ARG, "H is NULL");
+    if (!mean) return api_fail(TRPL_ERR_ARG, "mean is NULL");
+    if (!m2) return api_fail(TRPL_ERR_ARG, "m2 is NULL");
+    return TRPL_OK;
+}
+
+extern "C" {
+
+int trpl_mcmc_propose_dev(const double *U, const double *partners, int64_t count, int64_t P, int32_t A, double gamma, const double *scale,
+                          int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol, const double *lo, const double *hi,
+                          const int32_t *do_log, uint32_t flags, double *Up, double *Xp, int32_t *inside, void *stream)
+{
+    mcmc::Scale sc;
+    if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, Up, Xp, inside, sc)) return rc;
+    refine::Box bx;
+    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
+    const unsigned grid = (unsigned)((count + refine::kThreads - 1) / refine::kThreads);
+    hipStream_t st = (hipStream_t)stream;
+    switch (A) {
+#define TRPL_CASE(n) case n: mcmc::launch_propose<n>(grid, st, U, partners, count, P, gamma, sc, chain0, seed, step, bx, Up, Xp, inside); break;
+        TRPL_MCMC_CASES(TRPL_CASE)
+#undef TRPL_CASE
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mcmc propose launch: %s", hipGetErrorString(e));
+    return TRPL_OK;
+}
+
+int trpl_mcmc_propose(const double *U, const double *partners, int64_t count, int64_t P, int32_t A, double gamma, const double *scale,
+                      int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol, const double *lo, const double *hi, const int32_t *do_log,
+                      uint32_t flags, double *Up, double *Xp, int32_t *inside, int32_t device, double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    mcmc::Scale sc;
+    if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, Up, Xp, inside, sc)) return rc;
+    refine::Box bx;
+    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
+    if (int rc = select_device(device)) return rc;
+    CallScope cs;
+    HIP_TRY(cs.open());
+    DevBuf dU, dP, dUp, dXp, dIn;
+    const size_t ub = (size_t)count * A * 8, pb = (size_t)P * A * 8, xb = (size_t)count * ncol * 8, ib = (size_t)count * 4;
+    HIP_TRY(dU.alloc(ub, cs.st)); HIP_TRY(dP.alloc(pb, cs.st)); HIP_TRY(dUp.alloc(ub, cs.st)); HIP_TRY(dXp.alloc(xb, cs.st));
+    HIP_TRY(dIn.alloc(ib, cs.st));
+    HIP_TRY(hipMemcpyAsync(dU.p, U, ub, hipMemcpyHostToDevice, cs.st));
+    if (P > 0) HIP_TRY(hipMemcpyAsync(dP.p, partners, pb, hipMemcpyHostToDevice, cs.st));
+    HIP_TRY(hipStreamSynchronize(cs.st));
+    const double t0 = now_s();
+    if (int rc = trpl_mcmc_propose_dev(dU.as<double>(), P > 0 ? dP.as<double>() : nullptr, count, P, A, gamma, scale, chain0, seed, step,
+                                       ncol, lo, hi, do_log, flags, dUp.as<double>(), dXp.as<double>(), dIn.as<int32_t>(), cs.st))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(cs.st));
+    if (seconds) *seconds = now_s() - t0;
+    HIP_TRY(hipMemcpyAsync(Up, dUp.p, ub, hipMemcpyDeviceToHost, cs.st));
+    HIP_TRY(hipMemcpyAsync(Xp, dXp.p, xb, hipMemcpyDeviceToHost, cs.st));
+    HIP_TRY(hipMemcpyAsync(inside, dIn.p, ib, hipMemcpyDeviceToHost, cs.st));
+    HIP_TRY(hipStreamSynchronize(cs.st));
+    return TRPL_OK;
+}
+
+int trpl_mcmc_accept_dev(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
+                         int64_t count, int32_t A, int32_t ncol, double tf, int64_t chain0, uint64_t seed, uint32_t step,
+                         int32_t *accepted, void *stream)
+{
+    if (int rc = check_accept(U, X, LL, Up, Xp, LLp, inside, count, A, ncol, tf, chain0, accepted)) return rc;
+    const unsigned grid = (unsigned)((count + refine::kThreads - 1) / refine::kThreads);
+    hipStream_t st = (hipStream_t)stream;
+    switch (A) {
+#define TRPL_CASE(n) case n: mcmc::launch_accept<n>(grid, st, U, X, LL, Up, Xp, LLp, inside, count, ncol, tf, chain0, seed, step, accepted); break;
+        TRPL_MCMC_CASES(TRPL_CASE)
+#undef TRPL_CASE
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mcmc accept launch: %s", hipGetErrorString(e));
+    return TRPL_OK;
+}
+
+int trpl_mcmc_accept(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
+                     int64_t count, int32_t A, int32_t ncol, double tf, int64_t chain0, uint64_t seed, uint32_t step, int32_t *accepted,
+                     int32_t device, double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    if (int rc = check_accept(U, X, LL, Up, Xp, LLp, inside, count, A, ncol, tf, chain0, accepted)) return rc;
+    if (int rc = select_device(device)) return rc;
+    CallScope cs;
+    HIP_TRY(cs.open());
+    DevBuf dU, dX, dLL, dUp, dXp, dLLp, dIn, dAcc;
+    const size_t ub = (size_t)count * A * 8, xb = (size_t)count * ncol * 8, lb = (size_t)count * 8, ib = (size_t)count * 4;
+    HIP_TRY(dU.alloc(ub, cs.st)); HIP_TRY(dX.alloc(xb, cs.st)); HIP_TRY(dLL.alloc(lb, cs.st)); HIP_TRY(dUp.alloc(ub, cs.st));
+    HIP_TRY(dXp.alloc(xb, cs.st)); HIP_TRY(dLLp.alloc(lb, cs.st)); HIP_TRY(dIn.alloc(ib, cs.st)); HIP_TRY(dAcc.alloc(ib, cs.st));
+    HIP_TRY(hipMemcpyAsync(dU.p, U, ub, hipMemcpyHostToDevice, cs.st));
+    HIP_TRY(hipMemcpyAsync(dX.p, X, xb, hipMemcpyHostToDevice, cs.st));
+    HIP_TRY(hipMemcpyAsync(dLL.p, LL, lb, hipMemcpyHostToDevice, cs.st));
+    HIP_TRY(hipMemcpyAsync(dUp.p, Up, ub, hipMemcpyHostToDevice, cs.st));
+    HIP_TRY(hipMemcpyAsync(dXp.p, Xp, xb, hipMemcpyHostToDevice, cs.st));
+    HIP_TRY(hipMemcpyAsync(dLLp.p, LLp, lb, hipMemcpyHostToDevice, cs.st));
+    HIP_TRY(hipMemcpyAsync(dIn.p, inside, ib, hipMemcpyHostToDevice, cs.st));
+    HIP_TRY(hipStreamSynchronize(cs.st));
+    const double t0 = now_s();
+    if (int rc = trpl_mcmc_accept_dev(dU.as<double>(), dX.as<double>(), dLL.as<double>(), dUp.as<double>(), dXp.as<double>(),
+                                      dLLp.as<double>(), dIn.as<int32_t>(), count, A, ncol, tf, chain0, seed, step, dAcc.as<int32_t>(),
+                                      cs.st))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(cs.st));
+    if (seconds) *seconds = now_s() - t0;
+    HIP_TRY(hipMemcpyAsync(U, dU.p, ub, hipMemcpyDeviceToHost, cs.st));
+    HIP_TRY(hipMemcpyAsync(X, dX.p, xb, hipMemcpyDeviceToHost, cs.st));
+    HIP_TRY(hipMemcpyAsync(LL, dLL.p, lb, hipMemcpyDeviceToHost, cs.st));
+    HIP_TRY(hipMemcpyAsync(accepted, dAcc.p, ib, hipMemcpyDeviceToHost, cs.st));
+    HIP_TRY(hipStreamSynchronize(cs.st));
+    return TRPL_OK;
+}
+
+int trpl_mcmc_chain_stats_dev(const double *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, double *mean, double *m2,
+                              void *stream)
+{
+    if (int rc = check_chain_stats(H, n, ldh, Q, t0, t1, mean, m2)) return rc;
+    const unsigned grid = (unsigned)((Q + refine::kThreads - 1) / refine::kThreads);
+    hipLaunchKernelGGL(mcmc::chain_stats_kernel, dim3(grid), dim3(refine::kThreads), 0, (hipStream_t)stream, H, ldh, Q, t0, t1, mean, m2);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mcmc chain stats launch: %s", hipGetErrorString(e));
+    return TRPL_OK;
+}
+
+int trpl_mcmc_chain_stats(const double *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, double *mean, double *m2,
+                          int32_t device, double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    if (int rc = check_chain_stats(H, n, ldh, Q, t0, t1, mean, m2)) return rc;
+    if (int rc = select_device(device)) return rc;
+    CallScope cs;
+    HIP_TRY(cs.open());
+    DevBuf dH, dM, dV;                                           // the steps of the range only, compact on the device
+    const int64_t steps = t1 - t0;
+    const size_t row = (size_t)Q * 8;
+    HIP_TRY(dH.alloc((size_t)steps * row, cs.st)); HIP_TRY(dM.alloc(row, cs.st)); HIP_TRY(dV.alloc(row, cs.st));
+    HIP_TRY(hipMemcpy2DAsync(dH.p, row, H + t0 * ldh, (size_t)ldh * 8, row, (size_t)steps, hipMemcpyHostToDevice, cs.st));
+    HIP_TRY(hipStreamSynchronize(cs.st));
+    const double s0 = now_s();
+    if (int rc = trpl_mcmc_chain_stats_dev(dH.as<double>(), steps, Q, Q, 0, steps, dM.as<double>(), dV.as<double>(), cs.st)) return rc;
+    HIP_TRY(hipStreamSynchronize(cs.st));
+    if (seconds) *seconds = now_s() - s0;
+    HIP_TRY(hipMemcpyAsync(mean, dM.p, row, hipMemcpyDeviceToHost, cs.st));
+    HIP_TRY(hipMemcpyAsync(m2, dV.p, row, hipMemcpyDeviceToHost, cs.st));
+    HIP_TRY(hipStreamSynchronize(cs.st));
+    return TRPL_OK;
+}
+
+}  // extern "C"

@@ -608,6 +608,58 @@ def refine_draw_oriented_device(zc, h, L, c, m, n_uniform, seed, generation, min
         _stream()))
 
 
+def mcmc_propose_device(U, partners, gamma, scale, chain0, seed, step, minX, maxX, do_log, Up, Xp, inside, flags=0):
+    """trpl_mcmc_propose_dev: Up (count, A), Xp (count, ncol) f64 and inside (count,) int32 <- one symmetric proposal per chain of U
+    (count, A) f64: u' = (u + gamma (pa - pb)) + scale (2 xi - 1) with two distinct rows of partners (P >= 2, A), or the random walk
+    u' = u + scale (2 xi - 1) with partners None.  scale (A,) is a host array (a scalar is broadcast); chain0 is the ensemble index of
+    the first row, which keys its Philox stream."""
+    import torch
+    lo, hi, lg = _refine_box(minX, maxX, do_log)
+    if U.dim() != 2:
+        raise ValueError("U must be (count, A)")
+    count, A = U.shape
+    scale = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (A,)))
+    if partners is not None and (partners.dim() != 2 or partners.shape[1] != A):
+        raise ValueError("partners must be (P, A)")
+    if tuple(Up.shape) != (count, A) or tuple(Xp.shape) != (count, lo.size) or tuple(inside.shape) != (count,):
+        raise ValueError("Up must be (count, A), Xp (count, ncol) and inside (count,)")
+    _abi.check(_abi.lib().trpl_mcmc_propose_dev(
+        _chk(U, torch.float64, "U"), _opt(partners, torch.float64, "partners"), count, 0 if partners is None else partners.shape[0], A,
+        float(gamma), _abi.ptr(scale), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, lo.size, _abi.ptr(lo),
+        _abi.ptr(hi), _abi.ptr(lg), int(flags), _chk(Up, torch.float64, "Up"), _chk(Xp, torch.float64, "Xp"),
+        _chk(inside, torch.int32, "inside"), _stream()))
+
+
+def mcmc_accept_device(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, accepted):
+    """trpl_mcmc_accept_dev: the Metropolis step of every chain at temperature tf.  U (count, A), X (count, ncol) and LL (count,) f64
+    take the rows of Up, Xp, LLp where the proposal is accepted and keep theirs elsewhere; accepted (count,) int32 says which."""
+    import torch
+    if U.dim() != 2 or X.dim() != 2 or X.shape[0] != U.shape[0] or Up.shape != U.shape or Xp.shape != X.shape:
+        raise ValueError("U and Up must be (count, A), X and Xp (count, ncol)")
+    count = U.shape[0]
+    if tuple(LL.shape) != (count,) or tuple(LLp.shape) != (count,) or tuple(inside.shape) != (count,) or tuple(accepted.shape) != (count,):
+        raise ValueError("LL, LLp, inside and accepted must be (count,)")
+    _abi.check(_abi.lib().trpl_mcmc_accept_dev(
+        _chk(U, torch.float64, "U"), _chk(X, torch.float64, "X"), _chk(LL, torch.float64, "LL"), _chk(Up, torch.float64, "Up"),
+        _chk(Xp, torch.float64, "Xp"), _chk(LLp, torch.float64, "LLp"), _chk(inside, torch.int32, "inside"), count, U.shape[1], X.shape[1],
+        float(tf), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, _chk(accepted, torch.int32, "accepted"), _stream()))
+
+
+def mcmc_chain_stats_device(H, t0, t1, mean, m2, Q=None):
+    """trpl_mcmc_chain_stats_dev: mean, m2 (Q,) f64 <- per column q < Q of the history H (n, ldh >= Q) f64, which stays where it is,
+    the mean and the centred sum of squares over the steps [t0, t1), both sums in ascending t: the plain loop's bits.  Q defaults
+    to ldh."""
+    import torch
+    if H.dim() != 2:
+        raise ValueError("H must be (n, ldh)")
+    Q = H.shape[1] if Q is None else int(Q)
+    if tuple(mean.shape) != (Q,) or tuple(m2.shape) != (Q,):
+        raise ValueError("mean and m2 must be (Q,)")
+    _abi.check(_abi.lib().trpl_mcmc_chain_stats_dev(
+        _chk(H, torch.float64, "H"), H.shape[0], H.shape[1], Q, int(t0), int(t1), _chk(mean, torch.float64, "mean"),
+        _chk(m2, torch.float64, "m2"), _stream()))
+
+
 def credible_interval_device(x, W, lo=0.025, hi=0.975):
     """utils.py:185-196 on the device: sort by x, cumulate the weights, last point below `lo` and first
     above `hi` (torch.sort / cumsum: library plumbing, no custom kernel)."""

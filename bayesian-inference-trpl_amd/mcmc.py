@@ -1,0 +1,212 @@
+"""Ensemble Metropolis sampling on the fused likelihood (trpl_mcmc_*, include/trpl.h; csrc/mcmc.hip).
+
+An importance-weighted population stops being useful when its effective sample size is a dozen.  Here C chains advance in
+lock-step instead: one sweep proposes a move for every chain, evaluates all proposals in one call of the likelihood, and accepts or
+rejects each by the Metropolis rule.  The proposal is differential evolution (ter Braak 2006): the difference of two other chains,
+scaled by gamma, plus a small uniform jitter -- it needs no tuning and follows a ridge of the posterior by construction.  The
+ensemble is cut into two halves that are updated in turn, each with partners from the OTHER half (ter Braak & Vrugt 2008;
+Foreman-Mackey et al. 2013): within a half-sweep the partners are fixed, so every chain's move is a symmetric Metropolis kernel
+that leaves the posterior invariant, and all chains of the half can move at once.  kind="rw" is the plain random walk.
+
+Chains live in the unit coordinates of `refine` (the active columns of the box, uniform prior on the cube); a proposal that leaves
+the cube is never solved and never accepted.  The proposal, the accept/reject step and the sums of split-R-hat run on the device;
+there is no CPU fallback.  This module takes and returns numpy arrays and goes through the host-buffer calls, like `refine`: the
+likelihood it drives is any callable on a host X.  A pipeline whose chains stay on the device composes the same steps from
+device.mcmc_propose_device / mcmc_accept_device / mcmc_chain_stats_device.
+
+Chains.samples() returns (X, W = 1): what posterior.moments / quantiles / columns / corner / credible_intervals and
+posterior_predictive take."""
+import numpy as np
+
+from . import _abi, posterior, refine
+from .refine import _box, _f64
+from .sampler import box_flags
+
+_M64, _M32 = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF
+
+
+def propose(U, partners, gamma, scale, chain0, seed, step, minX, maxX, do_log, sim_flags=None, device=0, info=None):
+    """(Up, Xp, inside): one symmetric proposal per chain of U (count, A) (trpl_mcmc_propose).  partners (P >= 2, A): u' = (u + gamma
+    (pa - pb)) + scale (2 xi - 1) with two distinct rows a, b of partners; partners None: the random walk u' = u + scale (2 xi - 1).
+    scale (A,) or a scalar.  chain0 is the ensemble index of U's first row and step the half-sweep: they key the Philox stream.
+    inside (count,) int32 is 0 where u' left the unit cube; Xp is formed either way."""
+    U = _f64(U)
+    lo, hi, lg = _box(minX, maxX, do_log)
+    if U.ndim != 2:
+        raise ValueError("U must be (count, A)")
+    count, A = U.shape
+    scale = np.ascontiguousarray(np.broadcast_to(_f64(scale), (A,)))
+    P = 0
+    if partners is not None:
+        partners = _f64(partners)
+        if partners.ndim != 2 or partners.shape[1] != A:
+            raise ValueError("partners must be (P, A)")
+        P = partners.shape[0]
+    Up, Xp, inside = np.empty((count, A)), np.empty((count, lo.size)), np.empty(count, dtype=np.int32)
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_mcmc_propose(_abi.ptr(U), None if partners is None else _abi.ptr(partners), count, P, A, float(gamma),
+                                            _abi.ptr(scale), int(chain0), int(seed) & _M64, int(step) & _M32, lo.size, _abi.ptr(lo),
+                                            _abi.ptr(hi), _abi.ptr(lg), box_flags(sim_flags), _abi.ptr(Up), _abi.ptr(Xp),
+                                            _abi.ptr(inside), int(device), _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value)
+    return Up, Xp, inside
+
+
+def accept(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device=0, info=None):
+    """accepted (count,) int32: the Metropolis step of every chain at temperature tf (trpl_mcmc_accept).  U (count, A), X (count,
+    ncol) and LL (count,) -- C-contiguous float64 arrays -- are updated IN PLACE: the rows of an accepted proposal are copied, the
+    others stay."""
+    for name, a in (("U", U), ("X", X), ("LL", LL)):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable):
+            raise ValueError("%s is updated in place: it must be a writeable C-contiguous float64 array" % name)
+    Up, Xp, LLp = _f64(Up), _f64(Xp), _f64(LLp)
+    inside = np.ascontiguousarray(inside, dtype=np.int32)
+    if U.ndim != 2 or X.ndim != 2 or X.shape[0] != U.shape[0] or Up.shape != U.shape or Xp.shape != X.shape:
+        raise ValueError("U and Up must be (count, A), X and Xp (count, ncol)")
+    count = U.shape[0]
+    if LL.shape != (count,) or LLp.shape != (count,) or inside.shape != (count,):
+        raise ValueError("LL, LLp and inside must be (count,)")
+    accepted = np.empty(count, dtype=np.int32)
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_mcmc_accept(_abi.ptr(U), _abi.ptr(X), _abi.ptr(LL), _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(LLp),
+                                           _abi.ptr(inside), count, U.shape[1], X.shape[1], float(tf), int(chain0), int(seed) & _M64,
+                                           int(step) & _M32, _abi.ptr(accepted), int(device), _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value)
+    return accepted
+
+
+def chain_stats(H, t0=0, t1=None, Q=None, device=0, info=None):
+    """(mean, m2), each (Q,): per column q < Q of the history H (n, ldh >= Q), the mean and the centred sum of squares over the steps
+    [t0, t1), both sums in ascending t from +0.0 (trpl_mcmc_chain_stats): the plain loop's bits.  Q defaults to ldh, t1 to n."""
+    H = _f64(H)
+    if H.ndim != 2:
+        raise ValueError("H must be (n, ldh)")
+    n, ldh = H.shape
+    Q = ldh if Q is None else int(Q)
+    t1 = n if t1 is None else int(t1)
+    mean, m2 = np.empty(max(Q, 0)), np.empty(max(Q, 0))
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_mcmc_chain_stats(_abi.ptr(H), n, ldh, Q, int(t0), t1, _abi.ptr(mean), _abi.ptr(m2), int(device),
+                                                _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value)
+    return mean, m2
+
+
+def start(X, LL, C, minX, maxX, do_log, sim_flags=None, tf=1.0, offset=0.5, log_ratio=None, device=0):
+    """(X0, U0, LL0): C starting states drawn from an importance-weighted set -- a first generation (X, LL), or a refined
+    Population's log_ratio() as (X, LL, log_ratio=) -- by refine.resample of posterior.weights at temperature tf, with their unit
+    coordinates (refine.unit_coords).  A set whose effective sample size is small starts many chains on the same point; the
+    differential-evolution jitter separates them."""
+    X, LL = _f64(X), _f64(LL)
+    W = posterior.weights(LL, tf, device=device, log_ratio=log_ratio)
+    idx, _ = refine.resample(W, int(C), offset, device=device)
+    X0 = np.ascontiguousarray(X[idx])
+    U0, _ = refine.unit_coords(X0, minX, maxX, do_log, sim_flags, device=device)
+    return X0, U0, np.ascontiguousarray(LL[idx])
+
+
+class Chains:
+    """The kept history of a run: U (n, C, A) unit coordinates, X (n, C, ncol) in the box's units, LL (n, C), accept (n, C) bool (the
+    chain moved in that sweep), one entry per kept sweep."""
+
+    def __init__(self, U, X, LL, accept, device=0):
+        self.U, self.X, self.LL, self.accept, self.device = U, X, LL, accept, device
+
+    def samples(self, burn=0, thin=1):
+        """(X (N, ncol), W = ones(N)): the states of the kept sweeps burn, burn + thin, ... of every chain, equally weighted."""
+        X = self.X[int(burn)::int(thin)]
+        X = np.ascontiguousarray(X.reshape(-1, X.shape[2]))
+        return X, np.ones(X.shape[0])
+
+    def rhat(self, burn=0):
+        """Split-R-hat of every active column (A,).  The kept sweeps from burn on are cut into two halves of n2 = n // 2: 2 C
+        sequences, whose means and centred sums of squares come from the device (chain_stats on the history where it lies).  W =
+        mean of m2 / (n2 - 1), B = n2 var(means, ddof 1), R-hat = sqrt(((n2 - 1) / n2 W + B / n2) / W)."""
+        n, C, A = self.U.shape
+        burn = int(burn)
+        n2 = (n - burn) // 2
+        if n2 < 2:
+            raise ValueError("split-R-hat needs two halves of at least 2 kept sweeps each; %d sweeps are left after burn" % max(n - burn, 0))
+        H = self.U.reshape(n, C * A)
+        parts = [chain_stats(H, burn + k * n2, burn + (k + 1) * n2, device=self.device) for k in (0, 1)]
+        mean = np.concatenate([p[0].reshape(C, A) for p in parts])          # (2 C, A)
+        m2 = np.concatenate([p[1].reshape(C, A) for p in parts])
+        W = np.mean(m2 / (n2 - 1), axis=0)
+        B = n2 * np.var(mean, axis=0, ddof=1)
+        return np.sqrt(((n2 - 1) / n2 * W + B / n2) / W)
+
+
+def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0, kind="de", gamma=None, scale=None, jump_every=0,
+        seed=1, keep_every=1, burn=0, max_history_bytes=4 << 30, device=0, info=None, U0=None):
+    """Advance the C chains that start at X0 (C, ncol), LL0 (C,) by `sweeps` sweeps; loglik(X) -> LL is any callable (the fused
+    likelihood, a toy).  Returns Chains: the states after the sweeps burn, burn + keep_every, ...
+
+    One sweep updates the chains [0, C / 2) with the chains [C / 2, C) as partners (step = 2 t, chain0 = 0), then the chains [C / 2,
+    C) with the already updated first half (step = 2 t + 1, chain0 = C / 2).  loglik is called on the proposals inside the cube only;
+    the others get LLp = -inf and are rejected.
+
+    kind="de": differential evolution, gamma defaulting to 2.38 / sqrt(2 A) and, with jump_every > 0, 1.0 on every jump_every-th
+    sweep (a jump between modes); scale (the uniform jitter's half-width, a scalar or (A,)) defaults to 1e-3.  kind="rw": the random
+    walk of half-width scale, which must be given; no partners.  U0 (C, A): the unit coordinates of X0 when they are at hand (start
+    returns them); default refine.unit_coords(X0).
+
+    The history of n kept sweeps takes n C (A + ncol + 1) 8 + n C bytes; a run whose history would exceed max_history_bytes raises
+    ValueError before anything is solved.  ValueError for an odd C or C < 4.  info receives accept (the share of chains that moved,
+    per sweep) and outside (the share of all proposals that left the cube)."""
+    X, LL = np.array(X0, dtype=np.float64, order="C"), np.array(LL0, dtype=np.float64, order="C")
+    lo, hi, lg = _box(minX, maxX, do_log)
+    if X.ndim != 2 or X.shape[1] != lo.size or LL.shape != (X.shape[0],):
+        raise ValueError("X0 must be (C, ncol) and LL0 (C,)")
+    C = X.shape[0]
+    if C < 4 or C % 2:
+        raise ValueError("C=%d: the two halves of the ensemble need an even number of chains, at least 4" % C)
+    if kind not in ("de", "rw"):
+        raise ValueError("kind must be 'de' or 'rw'")
+    if scale is None:
+        if kind == "rw":
+            raise ValueError("kind='rw' needs scale, the half-width of the random walk")
+        scale = 1e-3
+    sweeps, keep_every, burn, jump_every = int(sweeps), int(keep_every), int(burn), int(jump_every)
+    if sweeps < 1 or keep_every < 1 or burn < 0:
+        raise ValueError("sweeps and keep_every must be >= 1 and burn >= 0")
+    A = refine.active_columns(lo, hi, sim_flags).size
+    if not 1 <= A <= _abi.REFINE_MAX_DIMS:
+        raise ValueError("the box has %d active columns; a chain takes 1 .. %d" % (A, _abi.REFINE_MAX_DIMS))
+    kept = range(burn, sweeps, keep_every)
+    need = len(kept) * C * ((A + lo.size + 1) * 8 + 1)
+    if need > int(max_history_bytes):
+        raise ValueError("the history of %d sweeps x %d chains needs %d bytes, more than max_history_bytes = %d"
+                         % (len(kept), C, need, int(max_history_bytes)))
+    if U0 is None:
+        U, _ = refine.unit_coords(X, lo, hi, lg, sim_flags, device=device)
+    else:
+        U = np.array(U0, dtype=np.float64, order="C")
+        if U.shape != (C, A):
+            raise ValueError("U0 must be (C, A) with the box's A = %d active columns" % A)
+    gamma0 = 2.38 / np.sqrt(2.0 * A) if gamma is None else float(gamma)
+    half = C // 2
+    hU, hX = np.empty((len(kept), C, A)), np.empty((len(kept), C, lo.size))
+    hLL, hAcc = np.empty((len(kept), C)), np.empty((len(kept), C), dtype=bool)
+    shares, outside, row = [], 0, 0
+    moved = np.empty(C, dtype=bool)
+    for t in range(sweeps):
+        g = 1.0 if jump_every > 0 and (t + 1) % jump_every == 0 else gamma0
+        for k, (a, b) in enumerate(((0, half), (half, C))):
+            partners = None if kind == "rw" else (U[half:] if k == 0 else U[:half])
+            Up, Xp, inside = propose(U[a:b], partners, g, scale, a, seed, 2 * t + k, lo, hi, lg, sim_flags, device=device)
+            ok = inside != 0
+            LLp = np.full(b - a, -np.inf)
+            if ok.any():
+                LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok])))
+            outside += int((~ok).sum())
+            moved[a:b] = accept(U[a:b], X[a:b], LL[a:b], Up, Xp, LLp, inside, tf, a, seed, 2 * t + k, device=device) != 0
+        shares.append(float(moved.mean()))
+        if t >= burn and (t - burn) % keep_every == 0:
+            hU[row], hX[row], hLL[row], hAcc[row] = U, X, LL, moved
+            row += 1
+    if info is not None:
+        info.update(accept=shares, outside=outside / float(sweeps * C))
+    return Chains(hU, hX, hLL, hAcc, device=device)

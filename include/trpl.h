@@ -1178,6 +1178,69 @@ int trpl_refine_draw_oriented(const double *zc, const double *h, const double *L
                               int32_t device, double *seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_mcmc_propose, trpl_mcmc_accept, trpl_mcmc_chain_stats -- ensemble Metropolis sampling: `count` chains advance in lock-step,
+ * every chain's proposal is one row of one launch of the fused likelihood, and these calls are the rest of a sweep: a symmetric
+ * proposal drawn on the device, the accept/reject step, and the per-sequence sums of a convergence diagnostic.  Chains live in the
+ * unit coordinates of trpl_refine_* (the A active columns of the box, uniform prior on [0, 1]^A).  (csrc/mcmc.hip; DESIGN.md
+ * section 23)
+ *
+ * Randomness.  Chain i of a call is chain n = chain0 + i of the ensemble.  Philox4x32-10 with key (seed low word, seed high word)
+ * and counter (n low word, n high word, 0x100 + j, step); genrand_res53 as in trpl_refine_draw.  The 0x100 keeps the stream apart
+ * from the refinement draws (third word j < 8) under the same seed.  Call j = 0 .. 7: xi[2j] from words (x0, x1), xi[2j + 1] from
+ * (x2, x3).  Call j = 8: xi_a from (x0, x1), xi_b from (x2, x3), the partner choice.  Call j = 9: xi from (x0, x1), the acceptance.
+ *
+ * trpl_mcmc_propose: U [count][A] the chains, partners [P][A] (NULL with P = 0), gamma, scale [A] HOST array, the box as
+ * trpl_refine_draw takes it.  One thread per chain.  With P >= 2 (differential evolution: ter Braak 2006, with the partners taken
+ * from the complementary half of the ensemble as in ter Braak & Vrugt 2008 and Foreman-Mackey et al. 2013):
+ *     a = min((int64)(xi_a * P), P - 1),   b = min((int64)(xi_b * (P - 1)), P - 2),   b += (b >= a)      so that b != a,
+ *     u'_d = (u_d + gamma * (pa_d - pb_d)) + scale_d * (2 xi_d - 1)
+ * in exactly this order; with P = 0 (random walk) u'_d = u_d + scale_d * (2 xi_d - 1).  Both are symmetric in (u, u') as long as
+ * the partners do not depend on u.  The jitter is uniform, so every bit can be restated without a device log or cos.  Up
+ * [count][A] <- u'; inside[i] (int32) = 1 when every u'_d lies in [0, 1] (a NaN is outside), else 0; Xp [count][ncol] by
+ * trpl_refine_draw's expressions from u' whether inside or not (a proposal outside keeps a finite X slightly beyond the prior box
+ * and is not to be solved: its likelihood is -inf).  Up, inside and the linear columns of Xp are pure functions of the arguments.
+ *
+ * trpl_mcmc_accept: one thread per chain; U [count][A], X [count][ncol], LL [count] are updated in place from Up, Xp, LLp, inside,
+ * and accepted [count] (int32) is written.  With d = (LLp - LL) / tf, a chain takes its proposal exactly when
+ *     inside != 0,   LLp is not NaN,   LLp > -inf,   and one of   !(LL > -inf),   d >= 0,   log(xi) < d   (the device's log).
+ * !(LL > -inf) lets a chain that stands on a NaN or -inf likelihood always move to a finite one.  An accepted row of U, X, LL is
+ * the proposal's bits; a rejected row is not written.
+ *
+ * trpl_mcmc_chain_stats: H [n][ldh >= Q] a history that stays where it is, the steps [t0, t1).  One thread per column q < Q,
+ * adjacent threads reading adjacent addresses:
+ *     mean[q] = (sum of H[t][q], t ascending from +0.0) / (t1 - t0),    m2[q] = sum of (H[t][q] - mean[q])^2, t ascending from +0.0,
+ * subtract, multiply, add, no contraction: the plain loop, bit for bit.  A NaN propagates.  With the 2 C sequences of a split
+ * history as columns these are what split-R-hat is formed from (trpl_amd.mcmc.Chains.rhat).  The host-buffer form copies the steps
+ * of the range only.
+ *
+ * Refused with TRPL_ERR_ARG before a device is touched, the message naming the argument: a NULL U, scale, Up, Xp, inside, X, LL,
+ * LLp, accepted, H, mean, m2, lo, hi, do_log; count < 1 or more than 2^31 - 1 blocks of 256 chains; A outside [1, 16] or (propose)
+ * not the box's count; P == 1, P < 0, P > 0 with partners NULL; gamma not finite; a scale_d that is not finite or < 0; chain0 < 0;
+ * what trpl_refine_draw refuses of a box; (accept) ncol outside [1, 16], tf not finite or <= 0; (chain_stats) n < 1, Q < 1,
+ * ldh < Q, a range that does not satisfy 0 <= t0 < t1 <= n.  The _dev calls take device pointers (scale and the box arrays
+ * excepted), allocate nothing and never synchronise.
+ * Python: trpl_amd.mcmc, trpl_amd.device.mcmc_*_device.
+ * ------------------------------------------------------------------------------------- */
+int trpl_mcmc_propose_dev(const double *U, const double *partners /*nullable*/, int64_t count, int64_t P, int32_t A, double gamma,
+                          const double *scale /*host [A]*/, int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol,
+                          const double *lo /*host*/, const double *hi /*host*/, const int32_t *do_log /*host*/, uint32_t flags,
+                          double *Up, double *Xp, int32_t *inside, void *stream);
+int trpl_mcmc_propose(const double *U, const double *partners /*nullable*/, int64_t count, int64_t P, int32_t A, double gamma,
+                      const double *scale, int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol, const double *lo,
+                      const double *hi, const int32_t *do_log, uint32_t flags, double *Up, double *Xp, int32_t *inside, int32_t device,
+                      double *seconds);
+int trpl_mcmc_accept_dev(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
+                         int64_t count, int32_t A, int32_t ncol, double tf, int64_t chain0, uint64_t seed, uint32_t step,
+                         int32_t *accepted, void *stream);
+int trpl_mcmc_accept(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
+                     int64_t count, int32_t A, int32_t ncol, double tf, int64_t chain0, uint64_t seed, uint32_t step, int32_t *accepted,
+                     int32_t device, double *seconds);
+int trpl_mcmc_chain_stats_dev(const double *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, double *mean, double *m2,
+                              void *stream);
+int trpl_mcmc_chain_stats(const double *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, double *mean, double *m2,
+                          int32_t device, double *seconds);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the
  * measurement plan): S independent systems  ld[i] x[i-1] + d[i] x[i] + ud[i] x[i+1] = b[i],
  * i < L, the problem pcreduce solves (pvSimPCR.py:42-81), operands and result in HBM, arrays

@@ -1,0 +1,74 @@
+"""The three kernels of the ensemble Metropolis sampler on resident tensors, in one process on one device.
+
+    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--out profiles/mcmc_bench.jsonl]
+
+propose:     mcmc_propose_device of `chains` chains in the reference's box (A = 10 active columns), with `chains` partners
+             (differential evolution: two gathered partner rows per chain), and the random walk for comparison.
+accept:      mcmc_accept_device of the same chains, about a third of the proposals accepted.
+chain_stats: mcmc_chain_stats_device over a history of n steps of chains * A columns (one half of a split-R-hat: n / 2 steps).
+Device events around `reps` back-to-back calls after a warm-up, median of 3 interleaved passes (tools/bench_quantiles.measure).
+Appends one JSON line to --out."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import torch         # noqa: E402
+import trpl_amd      # noqa: E402,F401
+from trpl_amd import device as tdev, refine, sampler as sm   # noqa: E402
+from bench_quantiles import measure   # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--chains", type=int, default=1 << 16)
+    ap.add_argument("--A", type=int, default=10)
+    ap.add_argument("--n", type=int, default=256)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcmc_bench.jsonl"))
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    lo, hi, lg = sm.DEFAULT_MINX * sm.UNIT_CONVERSIONS, sm.DEFAULT_MAXX * sm.UNIT_CONVERSIONS, sm.DEFAULT_DO_LOG
+    A = len(refine.active_columns(lo, hi))
+    if A != a.A:
+        raise SystemExit("the reference's box has %d active columns" % A)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    C, ncol = a.chains, len(lo)
+    f64 = dict(dtype=torch.float64, device=dev)
+    U = torch.rand((C, A), generator=g, **f64) * 0.5 + 0.25
+    partners = torch.rand((C, A), generator=g, **f64) * 0.5 + 0.25
+    Up, Xp = torch.empty((C, A), **f64), torch.empty((C, ncol), **f64)
+    inside = torch.empty(C, dtype=torch.int32, device=dev)
+    gamma = 2.38 / (2.0 * A) ** 0.5
+    tdev.mcmc_propose_device(U, partners, gamma, 1e-3, 0, 42, 0, lo, hi, lg, Up, Xp, inside)
+    X = Xp.clone()
+    LL = -torch.rand(C, generator=g, **f64)
+    LLp = LL + 2.0 * torch.randn(C, generator=g, **f64) - 1.0
+    accepted = torch.empty(C, dtype=torch.int32, device=dev)
+    H = torch.rand((a.n, C * A), generator=g, **f64)
+    mean, m2 = torch.empty(C * A, **f64), torch.empty(C * A, **f64)
+    # accept overwrites its chains, so it runs on copies.  Every call decides alike: a chain that took its proposal stands on it at
+    # the next call (d = 0: taken again), one that refused refuses again (the same uniform) -- the same reads and writes each time
+    Ua, Xa, LLa = U.clone(), X.clone(), LL.clone()
+    ms, passes = measure({
+        "propose_de": lambda: tdev.mcmc_propose_device(U, partners, gamma, 1e-3, 0, 42, 0, lo, hi, lg, Up, Xp, inside),
+        "propose_rw": lambda: tdev.mcmc_propose_device(U, None, gamma, 0.05, 0, 42, 0, lo, hi, lg, Up, Xp, inside),
+        "accept": lambda: tdev.mcmc_accept_device(Ua, Xa, LLa, Up, Xp, LLp, inside, 1.0, 0, 42, 0, accepted),
+        "chain_stats": lambda: tdev.mcmc_chain_stats_device(H, 0, a.n // 2, mean, m2)}, a.reps)
+    torch.cuda.synchronize()
+    line = {"bench": "mcmc", "device": torch.cuda.get_device_name(0), "chains": C, "A": A, "ncol": ncol, "n": a.n, "reps": a.reps, "ms": ms,
+            "ms_passes": passes, "inside_share": float(inside.double().mean().item()), "accepted_share": float(accepted.double().mean().item()),
+            "chain_stats_bytes_per_second": 2.0 * 8.0 * (a.n // 2) * C * A / (ms["chain_stats"] * 1e-3)}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as f:
+        f.write(json.dumps(line) + "\n")
+    print(json.dumps(line))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -30,6 +30,12 @@ box: never solved, weight 0) and "shrinkage_per_generation" to "refine"; --shrin
 (A + 1) / ESS.
 --find-tf with --refine also searches the temperature of largest uncertainty over the refined union, its proposal log-ratio kept
 beside the likelihoods (posterior.calc_max_uncertainty(log_ratio=)), as refine["max_uncertainty"].
+--mcmc [--chains C] [--sweeps N] adds, at the end, an ensemble Metropolis run on the fused likelihood (trpl_amd.mcmc: DESIGN.md section
+23): C chains (default 1024) started from the importance run (mcmc.start) advance N sweeps (default 200) by differential-evolution
+proposals at the run's temperature; the second half of the sweeps is kept.  "mcmc" holds the acceptance share, the share of
+proposals that left the prior box, split-R-hat of every free parameter and its 2.5 / 50 / 97.5 % values from the chain beside
+those of the importance run, which are printed; seconds["mcmc"].  --rw x uses a random walk of half-width x (unit coordinates)
+instead.  Without --mcmc the output is unchanged.
 """
 import json
 import sys
@@ -57,7 +63,20 @@ if "--shrink" in sys.argv:
     k = sys.argv.index("--shrink")
     SHRINK = float(sys.argv[k + 1])
     del sys.argv[k:k + 2]
-sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented")]
+MCMC = "--mcmc" in sys.argv
+CHAINS, SWEEPS, RW = 1024, 200, None
+for flag, conv in (("--chains", int), ("--sweeps", int), ("--rw", float)):
+    if flag in sys.argv:
+        k = sys.argv.index(flag)
+        value = conv(sys.argv[k + 1])
+        del sys.argv[k:k + 2]
+        if flag == "--chains":
+            CHAINS = value
+        elif flag == "--sweeps":
+            SWEEPS = value
+        else:
+            RW = value
+sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented", "--mcmc")]
 import numpy as np
 import torch
 import trpl_amd
@@ -222,4 +241,44 @@ if REFINE:
         unc = posterior.calc_max_uncertainty(Vu, LL_u[keep], n_obs, info=uinfo, log_ratio=lnr_u[keep])
         out["seconds"]["refine_find_tf"] = sync() - t10
         out["refine"]["max_uncertainty"] = {n: {"tf": t, "Q": q, "at_edge": bool(uinfo["at_edge"][n])} for n, (t, q) in unc.items()}
+if MCMC:
+    from trpl_amd import mcmc, posterior
+    t11 = sync()
+
+    def fused_chain(X2):                                         # the fused likelihood of the proposals of one half-sweep
+        n = X2.shape[0]
+        Xd = torch.from_numpy(np.ascontiguousarray(X2)).to(dev)
+        P2 = torch.zeros(n, dtype=torch.float64, device=dev)
+        tdev.loglik_device(Xd, ini_d, lens, T * dt, L, T, obs, [T + 1] * C, P2, torch.empty((C, n), dtype=torch.float64, device=dev))
+        return P2.cpu().numpy()
+
+    tf = n_obs * c_val
+    X0, U0, LL0 = mcmc.start(X.cpu().numpy(), P.cpu().numpy(), CHAINS, lo, hi, lg, tf=tf)
+    minfo = {}
+    burn = SWEEPS // 2
+    ch = mcmc.run(fused_chain, X0, LL0, lo, hi, lg, sweeps=SWEEPS, tf=tf, seed=42, burn=burn, info=minfo, U0=U0,
+                  **({"kind": "rw", "scale": RW} if RW is not None else {}))
+    rhat = ch.rhat()
+    Xs, Ws = ch.samples()
+    Xg = Xs / sm.UNIT_CONVERSIONS
+    Vs = np.ascontiguousarray(np.stack([np.log10(Xg[:, i]) if lg[i] else Xg[:, i] for i in cols]))
+    qs = [0.025, 0.5, 0.975]
+    q_chain = posterior.quantiles(Vs, Ws, qs)
+    q_imp = posterior.quantiles(V.cpu().numpy(), W.cpu().numpy(), qs)
+    out["seconds"]["mcmc"] = sync() - t11
+    act = [int(i) for i in trpl_amd.refine.active_columns(lo, hi)]
+    out["mcmc"] = {"chains": CHAINS, "sweeps": SWEEPS, "kept_sweeps": int(ch.U.shape[0]), "proposal": "rw %g" % RW if RW is not None else "de",
+                   "distinct_starts": int(np.unique(LL0).size),
+                   "acceptance": float(np.mean(minfo["accept"])), "acceptance_kept": float(np.mean(minfo["accept"][burn:])),
+                   "outside_share_of_proposals": minfo["outside"], "worst_rhat": float(np.nanmax(rhat)),
+                   "rhat": {sm.PARAM_NAMES[c]: float(r) for c, r in zip(act, rhat)},
+                   "max_loglik": float(ch.LL.max()), "median_loglik": float(np.median(ch.LL[-1])),
+                   "quantiles": {n: {"truth": float(tr), "chain": [float(v) for v in q_chain[:, k]],
+                                     "importance": [float(v) for v in q_imp[:, k]]} for k, (n, tr) in enumerate(zip(names, truth))}}
+    print("mcmc (%s): %d chains from %d distinct starts, %d sweeps: acceptance %.3f (kept half %.3f), outside the prior box %.4f, worst R-hat %.3f"
+          % (out["mcmc"]["proposal"], CHAINS, out["mcmc"]["distinct_starts"], SWEEPS, out["mcmc"]["acceptance"],
+             out["mcmc"]["acceptance_kept"], minfo["outside"], out["mcmc"]["worst_rhat"]), file=sys.stderr)
+    for k, n in enumerate(names):
+        print("mcmc: %-8s truth %9.4f | chain %9.4f %9.4f %9.4f | importance %9.4f %9.4f %9.4f"
+              % ((n, truth[k]) + tuple(q_chain[:, k]) + tuple(q_imp[:, k])), file=sys.stderr)
 print(json.dumps(out))
