@@ -1,12 +1,15 @@
-// Host-side helpers shared by the translation units that implement include/trpl.h (trpl_api.hip,
-// trpl_multi.hip): the thread-local error message, RAII for the private streams and stream-ordered
-// allocations of the host-buffer calls, argument checks.  Nothing here throws.
+// Host-side helpers shared by every translation unit that implements include/trpl.h: the thread-local error message, RAII
+// for the private streams and stream-ordered allocations of the host-buffer calls (CallScope, DevBuf: the solver and likelihood
+// calls of trpl_api.hip and trpl_multi.hip use them directly), Staged, the staging of the analysis-side host-buffer calls
+// (the posterior / sampler / PCR tail of trpl_api.hip, posterior_scan.hip, predictive.hip, quantiles.hip, corner.hip,
+// refine.hip, refine_oriented.hip, mcmc.hip), argument checks.  Nothing here throws.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include <chrono>
+#include <type_traits>
 
 #include "../../include/trpl.h"
 #include "trpl_common.hpp"
@@ -59,6 +62,95 @@ struct DevBuf {                      // RAII device allocation for the host-buff
     ~DevBuf() { release(); }
     hipError_t alloc(size_t n, hipStream_t s) { st = s; return hipMallocAsync(&p, n ? n : 1, s); }
     template <typename T> T *as() { return (T *)p; }
+};
+
+int select_device(int32_t device);          // hipSetDevice with range check (trpl_api.hip)
+
+// The staging of a host-buffer call around its device-resident (_dev) form: the call declares its buffers, runs the _dev form on
+// stream() between begin() and finish(), and returns.  Counts are elements of T (bytes for void); every buffer is compact on the
+// device, a pitched one [rows][width] from or to a host leading dimension ld.  The first failed allocation or copy is recorded
+// (api_fail, TRPL_ERR_HIP) and turns every later declaration into a no-op that returns NULL; begin() returns it.
+// seconds is the device time of the _dev form: from the uploads having landed to its last kernel having finished.
+// Members are destroyed last to first: the buffers are released (hipFreeAsync), then the scope drains and destroys the stream.
+struct Staged {
+    static constexpr int kMaxBufs = 12;      // the largest user, trpl_corner, declares 11
+    CallScope cs;
+    DevBuf buf[kMaxBufs];
+    struct Back { void *host; const void *dev; size_t ld, width, rows; } back[kMaxBufs];      // in bytes
+    int nbuf = 0, nback = 0, rc = TRPL_OK;
+    double t0 = 0.0;
+
+    int open(int32_t device)
+    {
+        if (int r = select_device(device)) return r;
+        return ok(cs.open(), "hipStreamCreateWithFlags");
+    }
+    hipStream_t stream() const { return cs.st; }
+
+    int ok(hipError_t e, const char *what)
+    {
+        if (e != hipSuccess && !rc) rc = api_fail(TRPL_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+        return rc;
+    }
+    void *scratch(size_t bytes)
+    {
+        if (rc) return nullptr;
+        if (nbuf == kMaxBufs) { rc = api_fail(TRPL_ERR_HIP, "a host-buffer call stages at most %d buffers", kMaxBufs); return nullptr; }
+        return ok(buf[nbuf].alloc(bytes, cs.st), "hipMallocAsync") ? nullptr : buf[nbuf++].p;
+    }
+    // device copy of host[rows][ld], `width` of each row; no copy when host is NULL or there is nothing to copy
+    void *up(const void *host, size_t ld, size_t width, size_t rows)
+    {
+        void *d = scratch(width * rows);
+        if (!d || !host || !width || !rows) return d;
+        if (rows == 1) ok(hipMemcpyAsync(d, host, width, hipMemcpyHostToDevice, cs.st), "hipMemcpyAsync (upload)");
+        else ok(hipMemcpy2DAsync(d, width, host, ld, width, rows, hipMemcpyHostToDevice, cs.st), "hipMemcpy2DAsync (upload)");
+        return rc ? nullptr : d;
+    }
+    // finish() copies d back to host[rows][ld]; not when host is NULL or there is nothing to copy
+    void *down(void *d, void *host, size_t ld, size_t width, size_t rows)
+    {
+        if (d && host && width && rows) back[nback++] = {host, d, ld, width, rows};
+        return d;
+    }
+
+    template <typename T> const T *in(const T *host, size_t n) { return (const T *)up(host, 0, n * elem<T>(), 1); }
+    template <typename T> const T *in(const T *host, size_t ld, size_t width, size_t rows)
+    {
+        return (const T *)up(host, ld * elem<T>(), width * elem<T>(), rows);
+    }
+    template <typename T> T *out(T *host, size_t n) { return (T *)down(scratch(n * elem<T>()), host, 0, n * elem<T>(), 1); }
+    template <typename T> T *out(T *host, size_t ld, size_t width, size_t rows)
+    {
+        return (T *)down(scratch(width * elem<T>() * rows), host, ld * elem<T>(), width * elem<T>(), rows);
+    }
+    template <typename T> T *inout(T *host, size_t n) { return (T *)down(up(host, 0, n * elem<T>(), 1), host, 0, n * elem<T>(), 1); }
+
+    // the first recorded error, else: the uploads have landed, the clock starts
+    int begin()
+    {
+        if (ok(hipStreamSynchronize(cs.st), "hipStreamSynchronize (uploads)")) return rc;
+        t0 = now_s();
+        return TRPL_OK;
+    }
+    // the _dev form has finished (*seconds), the outputs are copied back and have landed
+    int finish(double *seconds)
+    {
+        if (ok(hipStreamSynchronize(cs.st), "hipStreamSynchronize")) return rc;
+        if (seconds) *seconds = now_s() - t0;
+        for (int i = 0; i < nback; i++) {
+            const Back &b = back[i];
+            if (b.rows == 1) ok(hipMemcpyAsync(b.host, b.dev, b.width, hipMemcpyDeviceToHost, cs.st), "hipMemcpyAsync (download)");
+            else ok(hipMemcpy2DAsync(b.host, b.ld, b.dev, b.width, b.width, b.rows, hipMemcpyDeviceToHost, cs.st), "hipMemcpy2DAsync (download)");
+        }
+        return ok(hipStreamSynchronize(cs.st), "hipStreamSynchronize (downloads)");
+    }
+
+private:
+    template <typename T> static constexpr size_t elem()
+    {
+        if constexpr (std::is_void_v<T>) return 1; else return sizeof(T);
+    }
 };
 
 // Thresholds (bytes) above which a host-buffer call pins (HostPin) / maps (HostMap) the caller's memory for its duration.
@@ -133,7 +225,6 @@ struct ProfRange {
 
 int no_weighted_flag(uint32_t flags);      // TRPL_ERR_ARG when TRPL_FLAG_WEIGHTED reaches an entry point that takes no weights
 int no_moments_flag(uint32_t flags);       // TRPL_ERR_ARG when TRPL_FLAG_MOMENTS reaches an entry point without an esum output
-int select_device(int32_t device);          // hipSetDevice with range check (trpl_api.hip)
 int check_grid(int32_t L, int64_t T, int32_t plT, int32_t max_iter, double time_ns);
 // the observation brackets of trpl_loglik_obs are host data in the host-buffer calls: sorted, in [1, T]
 int check_brackets(const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int32_t C, int64_t obs_ld,

@@ -324,41 +324,21 @@ int trpl_corner(const double *X, int64_t S, int64_t ldx, const double *LL, doubl
     if (int rc = check_hist((const void *)1, S, S, D, (const void *)1, lo, hi, bins, h1, h2)) return rc;
     if (S > 0 && !LL) return api_fail(TRPL_ERR_ARG, "LL is NULL");
     if (!(tf > 0.0)) return api_fail(TRPL_ERR_ARG, "tf=%g must be > 0", tf);
-    if (int rc = select_device(device)) return rc;
-    const int64_t npair = (int64_t)D * (D - 1) / 2;
-    const size_t h1b = (size_t)D * bins * 8, h2b = (size_t)npair * bins * bins * 8;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dX, dLL, dLLk, dV, dW, dKept, dH1, dC1, dH2, dWs, dKeys;
-    const size_t xb = S ? ((size_t)(S - 1) * (size_t)ldx + TRPL_CORNER_PRIMARY) * 8 : 0, sb = (size_t)S * 8;
-    const int64_t wsb = trpl_posterior_workspace_bytes(1);
-    HIP_TRY(dX.alloc(xb, cs.st)); HIP_TRY(dLL.alloc(sb, cs.st)); HIP_TRY(dLLk.alloc(sb, cs.st)); HIP_TRY(dV.alloc(sb * D, cs.st));
-    HIP_TRY(dW.alloc(sb, cs.st)); HIP_TRY(dKept.alloc(8, cs.st)); HIP_TRY(dH1.alloc(h1b, cs.st)); HIP_TRY(dC1.alloc(h1b, cs.st));
-    HIP_TRY(dH2.alloc(h2b, cs.st)); HIP_TRY(dWs.alloc((size_t)wsb, cs.st));
-    HIP_TRY(dKeys.alloc((size_t)trpl_corner_workspace_bytes(S, D), cs.st));
-    if (S > 0) {
-        HIP_TRY(hipMemcpyAsync(dX.p, X, xb, hipMemcpyHostToDevice, cs.st));
-        HIP_TRY(hipMemcpyAsync(dLL.p, LL, sb, hipMemcpyHostToDevice, cs.st));
-    }
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_corner_columns_dev(dX.as<double>(), S, ldx, cols, dolog, D, thickness_nm, excl_lo, excl_hi, dLL.as<double>(),
-                                         dV.as<double>(), dLLk.as<double>(), dKept.as<int64_t>(), cs.st))
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const int64_t npair = (int64_t)D * (D - 1) / 2, wsb = trpl_posterior_workspace_bytes(1);
+    const size_t h1n = (size_t)D * bins, s = (size_t)S;
+    const double *dX = sg.in(X, S ? (s - 1) * (size_t)ldx + TRPL_CORNER_PRIMARY : 0), *dLL = sg.in(LL, s);   // X ends with its last row
+    double *dLLk = (double *)sg.scratch(s * 8), *dV = sg.out(V, s * D), *dW = sg.out(W, s);
+    int64_t *dKept = sg.out(kept, 1);
+    double *dH1 = sg.out(h1, h1n), *dC1 = sg.out(c1, h1n), *dH2 = sg.out(h2, (size_t)npair * bins * bins);
+    void *dWs = sg.scratch((size_t)wsb), *dKeys = sg.scratch((size_t)trpl_corner_workspace_bytes(S, D));
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_corner_columns_dev(dX, S, ldx, cols, dolog, D, thickness_nm, excl_lo, excl_hi, dLL, dV, dLLk, dKept, sg.stream())) return rc;
+    if (int rc = trpl_posterior_weights_dev(dLLk, S, tf, dW, nullptr, dWs, wsb, sg.stream())) return rc;
+    if (int rc = trpl_corner_hist_dev(dV, S, S, D, dW, lo, hi, bins, dH1, c1 ? dC1 : nullptr, (h2 && npair) ? dH2 : nullptr, dKeys, sg.stream()))
         return rc;
-    if (int rc = trpl_posterior_weights_dev(dLLk.as<double>(), S, tf, dW.as<double>(), nullptr, dWs.p, wsb, cs.st)) return rc;
-    if (int rc = trpl_corner_hist_dev(dV.as<double>(), S, S, D, dW.as<double>(), lo, hi, bins, dH1.as<double>(), c1 ? dC1.as<double>() : nullptr,
-                                      (h2 && npair) ? dH2.as<double>() : nullptr, dKeys.p, cs.st))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    if (V && S > 0) HIP_TRY(hipMemcpyAsync(V, dV.p, sb * D, hipMemcpyDeviceToHost, cs.st));
-    if (W && S > 0) HIP_TRY(hipMemcpyAsync(W, dW.p, sb, hipMemcpyDeviceToHost, cs.st));
-    if (kept) HIP_TRY(hipMemcpyAsync(kept, dKept.p, 8, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipMemcpyAsync(h1, dH1.p, h1b, hipMemcpyDeviceToHost, cs.st));
-    if (c1) HIP_TRY(hipMemcpyAsync(c1, dC1.p, h1b, hipMemcpyDeviceToHost, cs.st));
-    if (h2 && npair) HIP_TRY(hipMemcpyAsync(h2, dH2.p, h2b, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    return TRPL_OK;
+    return sg.finish(seconds);
 }
 
 }  // extern "C"

@@ -118,36 +118,15 @@ __global__ void __launch_bounds__(kThreads) chain_stats_kernel(const double *H, 
     m2[q] = v;
 }
 
-template <int A>
-static void launch_propose(unsigned grid, hipStream_t st, const double *U, const double *partners, int64_t count, int64_t P, double gamma,
-                           const Scale &sc, int64_t chain0, uint64_t seed, uint32_t step, const Box &bx, double *Up, double *Xp,
-                           int32_t *inside)
-{
-    hipLaunchKernelGGL(propose_kernel<A>, dim3(grid), dim3(kThreads), 0, st, U, partners, count, P, gamma, sc, chain0, (uint32_t)seed,
-                       (uint32_t)(seed >> 32), step, bx, Up, Xp, inside);
-}
-
-template <int A>
-static void launch_accept(unsigned grid, hipStream_t st, double *U, double *X, double *LL, const double *Up, const double *Xp,
-                          const double *LLp, const int32_t *inside, int64_t count, int32_t ncol, double tf, int64_t chain0, uint64_t seed,
-                          uint32_t step, int32_t *accepted)
-{
-    hipLaunchKernelGGL(accept_kernel<A>, dim3(grid), dim3(kThreads), 0, st, U, X, LL, Up, Xp, LLp, inside, count, ncol, tf, chain0,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), step, accepted);
-}
-
 }  // namespace mcmc
 }  // namespace trpl
 
 using namespace trpl;
 
-#define TRPL_MCMC_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
-
 static int check_chains(int64_t count, int32_t A, int64_t chain0)
 {
     if (count < 1) return api_fail(TRPL_ERR_ARG, "count=%lld must be >= 1", (long long)count);
-    if ((count + refine::kThreads - 1) / refine::kThreads > kRefineMaxBlocks)
-        return api_fail(TRPL_ERR_ARG, "count=%lld is more than 2^31 - 1 blocks of %d chains", (long long)count, refine::kThreads);
+    if (int rc = refine_check_blocks("count", count, "chains")) return rc;
     if (A < 1 || A > TRPL_REFINE_MAX_DIMS) return api_fail(TRPL_ERR_ARG, "A=%d must be in [1, %d]", A, TRPL_REFINE_MAX_DIMS);
     if (chain0 < 0) return api_fail(TRPL_ERR_ARG, "chain0=%lld must be >= 0", (long long)chain0);
     return TRPL_OK;
@@ -194,8 +173,7 @@ static int check_chain_stats(const void *H, int64_t n, int64_t ldh, int64_t Q, i
 {
     if (n < 1) return api_fail(TRPL_ERR_ARG, "n=%lld must be >= 1", (long long)n);
     if (Q < 1) return api_fail(TRPL_ERR_ARG, "Q=%lld must be >= 1", (long long)Q);
-    if ((Q + refine::kThreads - 1) / refine::kThreads > kRefineMaxBlocks)
-        return api_fail(TRPL_ERR_ARG, "Q=%lld is more than 2^31 - 1 blocks of %d columns", (long long)Q, refine::kThreads);
+    if (int rc = refine_check_blocks("Q", Q, "columns")) return rc;
     if (ldh < Q) return api_fail(TRPL_ERR_ARG, "ldh=%lld must be >= Q=%lld", (long long)ldh, (long long)Q);
     if (!(0 <= t0 && t0 < t1 && t1 <= n))
         return api_fail(TRPL_ERR_ARG, "t0=%lld, t1=%lld: the range must satisfy 0 <= t0 < t1 <= n=%lld", (long long)t0, (long long)t1,
@@ -216,16 +194,17 @@ int trpl_mcmc_propose_dev(const double *U, const double *partners, int64_t count
     if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, Up, Xp, inside, sc)) return rc;
     refine::Box bx;
     if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
-    const unsigned grid = (unsigned)((count + refine::kThreads - 1) / refine::kThreads);
-    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(refine_blocks(count)), block(refine::kThreads);
     switch (A) {
-#define TRPL_CASE(n) case n: mcmc::launch_propose<n>(grid, st, U, partners, count, P, gamma, sc, chain0, seed, step, bx, Up, Xp, inside); break;
-        TRPL_MCMC_CASES(TRPL_CASE)
+#define TRPL_CASE(n)                                                                                                                   \
+    case n:                                                                                                                            \
+        hipLaunchKernelGGL(mcmc::propose_kernel<n>, grid, block, 0, (hipStream_t)stream, U, partners, count, P, gamma, sc, chain0,         \
+                           (uint32_t)seed, (uint32_t)(seed >> 32), step, bx, Up, Xp, inside);                                          \
+        break;
+        TRPL_REFINE_DIMS(TRPL_CASE)
 #undef TRPL_CASE
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mcmc propose launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    return refine_launched("mcmc propose");
 }
 
 int trpl_mcmc_propose(const double *U, const double *partners, int64_t count, int64_t P, int32_t A, double gamma, const double *scale,
@@ -237,27 +216,16 @@ int trpl_mcmc_propose(const double *U, const double *partners, int64_t count, in
     if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, Up, Xp, inside, sc)) return rc;
     refine::Box bx;
     if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dU, dP, dUp, dXp, dIn;
-    const size_t ub = (size_t)count * A * 8, pb = (size_t)P * A * 8, xb = (size_t)count * ncol * 8, ib = (size_t)count * 4;
-    HIP_TRY(dU.alloc(ub, cs.st)); HIP_TRY(dP.alloc(pb, cs.st)); HIP_TRY(dUp.alloc(ub, cs.st)); HIP_TRY(dXp.alloc(xb, cs.st));
-    HIP_TRY(dIn.alloc(ib, cs.st));
-    HIP_TRY(hipMemcpyAsync(dU.p, U, ub, hipMemcpyHostToDevice, cs.st));
-    if (P > 0) HIP_TRY(hipMemcpyAsync(dP.p, partners, pb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_mcmc_propose_dev(dU.as<double>(), P > 0 ? dP.as<double>() : nullptr, count, P, A, gamma, scale, chain0, seed, step,
-                                       ncol, lo, hi, do_log, flags, dUp.as<double>(), dXp.as<double>(), dIn.as<int32_t>(), cs.st))
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const double *dU = sg.in(U, (size_t)count * A), *dP = sg.in(partners, (size_t)P * A);
+    double *dUp = sg.out(Up, (size_t)count * A), *dXp = sg.out(Xp, (size_t)count * ncol);
+    int32_t *dIn = sg.out(inside, (size_t)count);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_mcmc_propose_dev(dU, P > 0 ? dP : nullptr, count, P, A, gamma, scale, chain0, seed, step, ncol, lo, hi, do_log, flags,
+                                       dUp, dXp, dIn, sg.stream()))
         return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(Up, dUp.p, ub, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipMemcpyAsync(Xp, dXp.p, xb, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipMemcpyAsync(inside, dIn.p, ib, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    return TRPL_OK;
+    return sg.finish(seconds);
 }
 
 int trpl_mcmc_accept_dev(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
@@ -265,16 +233,17 @@ int trpl_mcmc_accept_dev(double *U, double *X, double *LL, const double *Up, con
                          int32_t *accepted, void *stream)
 {
     if (int rc = check_accept(U, X, LL, Up, Xp, LLp, inside, count, A, ncol, tf, chain0, accepted)) return rc;
-    const unsigned grid = (unsigned)((count + refine::kThreads - 1) / refine::kThreads);
-    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(refine_blocks(count)), block(refine::kThreads);
     switch (A) {
-#define TRPL_CASE(n) case n: mcmc::launch_accept<n>(grid, st, U, X, LL, Up, Xp, LLp, inside, count, ncol, tf, chain0, seed, step, accepted); break;
-        TRPL_MCMC_CASES(TRPL_CASE)
+#define TRPL_CASE(n)                                                                                                                   \
+    case n:                                                                                                                            \
+        hipLaunchKernelGGL(mcmc::accept_kernel<n>, grid, block, 0, (hipStream_t)stream, U, X, LL, Up, Xp, LLp, inside, count, ncol, tf,   \
+                           chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step, accepted);                                           \
+        break;
+        TRPL_REFINE_DIMS(TRPL_CASE)
 #undef TRPL_CASE
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mcmc accept launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    return refine_launched("mcmc accept");
 }
 
 int trpl_mcmc_accept(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
@@ -283,45 +252,24 @@ int trpl_mcmc_accept(double *U, double *X, double *LL, const double *Up, const d
 {
     if (seconds) *seconds = 0.0;
     if (int rc = check_accept(U, X, LL, Up, Xp, LLp, inside, count, A, ncol, tf, chain0, accepted)) return rc;
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dU, dX, dLL, dUp, dXp, dLLp, dIn, dAcc;
-    const size_t ub = (size_t)count * A * 8, xb = (size_t)count * ncol * 8, lb = (size_t)count * 8, ib = (size_t)count * 4;
-    HIP_TRY(dU.alloc(ub, cs.st)); HIP_TRY(dX.alloc(xb, cs.st)); HIP_TRY(dLL.alloc(lb, cs.st)); HIP_TRY(dUp.alloc(ub, cs.st));
-    HIP_TRY(dXp.alloc(xb, cs.st)); HIP_TRY(dLLp.alloc(lb, cs.st)); HIP_TRY(dIn.alloc(ib, cs.st)); HIP_TRY(dAcc.alloc(ib, cs.st));
-    HIP_TRY(hipMemcpyAsync(dU.p, U, ub, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dX.p, X, xb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dLL.p, LL, lb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dUp.p, Up, ub, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dXp.p, Xp, xb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dLLp.p, LLp, lb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dIn.p, inside, ib, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_mcmc_accept_dev(dU.as<double>(), dX.as<double>(), dLL.as<double>(), dUp.as<double>(), dXp.as<double>(),
-                                      dLLp.as<double>(), dIn.as<int32_t>(), count, A, ncol, tf, chain0, seed, step, dAcc.as<int32_t>(),
-                                      cs.st))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(U, dU.p, ub, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipMemcpyAsync(X, dX.p, xb, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipMemcpyAsync(LL, dLL.p, lb, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipMemcpyAsync(accepted, dAcc.p, ib, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    return TRPL_OK;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    double *dU = sg.inout(U, (size_t)count * A), *dX = sg.inout(X, (size_t)count * ncol), *dLL = sg.inout(LL, (size_t)count);
+    const double *dUp = sg.in(Up, (size_t)count * A), *dXp = sg.in(Xp, (size_t)count * ncol), *dLLp = sg.in(LLp, (size_t)count);
+    const int32_t *dIn = sg.in(inside, (size_t)count);
+    int32_t *dAcc = sg.out(accepted, (size_t)count);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_mcmc_accept_dev(dU, dX, dLL, dUp, dXp, dLLp, dIn, count, A, ncol, tf, chain0, seed, step, dAcc, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 int trpl_mcmc_chain_stats_dev(const double *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, double *mean, double *m2,
                               void *stream)
 {
     if (int rc = check_chain_stats(H, n, ldh, Q, t0, t1, mean, m2)) return rc;
-    const unsigned grid = (unsigned)((Q + refine::kThreads - 1) / refine::kThreads);
-    hipLaunchKernelGGL(mcmc::chain_stats_kernel, dim3(grid), dim3(refine::kThreads), 0, (hipStream_t)stream, H, ldh, Q, t0, t1, mean, m2);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mcmc chain stats launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    hipLaunchKernelGGL(mcmc::chain_stats_kernel, dim3(refine_blocks(Q)), dim3(refine::kThreads), 0, (hipStream_t)stream, H, ldh, Q, t0, t1,
+                       mean, m2);
+    return refine_launched("mcmc chain stats");
 }
 
 int trpl_mcmc_chain_stats(const double *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, double *mean, double *m2,
@@ -329,23 +277,14 @@ int trpl_mcmc_chain_stats(const double *H, int64_t n, int64_t ldh, int64_t Q, in
 {
     if (seconds) *seconds = 0.0;
     if (int rc = check_chain_stats(H, n, ldh, Q, t0, t1, mean, m2)) return rc;
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dH, dM, dV;                                           // the steps of the range only, compact on the device
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
     const int64_t steps = t1 - t0;
-    const size_t row = (size_t)Q * 8;
-    HIP_TRY(dH.alloc((size_t)steps * row, cs.st)); HIP_TRY(dM.alloc(row, cs.st)); HIP_TRY(dV.alloc(row, cs.st));
-    HIP_TRY(hipMemcpy2DAsync(dH.p, row, H + t0 * ldh, (size_t)ldh * 8, row, (size_t)steps, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    const double s0 = now_s();
-    if (int rc = trpl_mcmc_chain_stats_dev(dH.as<double>(), steps, Q, Q, 0, steps, dM.as<double>(), dV.as<double>(), cs.st)) return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - s0;
-    HIP_TRY(hipMemcpyAsync(mean, dM.p, row, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipMemcpyAsync(m2, dV.p, row, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    return TRPL_OK;
+    const double *dH = sg.in(H + t0 * ldh, (size_t)ldh, (size_t)Q, (size_t)steps);      // the steps of the range only, compact on the device
+    double *dM = sg.out(mean, (size_t)Q), *dV = sg.out(m2, (size_t)Q);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_mcmc_chain_stats_dev(dH, steps, Q, Q, 0, steps, dM, dV, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 }  // extern "C"

@@ -356,33 +356,16 @@ static int scan_staged(const double *LL, const double *lnr, bool ratio, int64_t 
 {
     if (seconds) *seconds = 0.0;
     if (int rc = check_scan(LL, lnr, ratio, S, V, D, tfs, tfs, K, stats, mean, var, Q)) return rc;
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dL, dR, dV, dT, dSt, dM, dVar, dQ, ws;
-    const size_t wsb = (size_t)scan_workspace(S, D, K, ratio), kd = (size_t)K * D * 8, sb = (size_t)K * (ratio ? 48 : 32);
-    HIP_TRY(dL.alloc((size_t)S * 8, cs.st));
-    if (ratio) HIP_TRY(dR.alloc((size_t)S * 8, cs.st));
-    HIP_TRY(dV.alloc((size_t)S * D * 8, cs.st)); HIP_TRY(dT.alloc((size_t)K * 8, cs.st)); HIP_TRY(dSt.alloc(sb, cs.st));
-    HIP_TRY(dM.alloc(kd, cs.st)); HIP_TRY(dVar.alloc(kd, cs.st)); HIP_TRY(dQ.alloc(kd, cs.st)); HIP_TRY(ws.alloc(wsb, cs.st));
-    HIP_TRY(hipMemcpyAsync(dL.p, LL, (size_t)S * 8, hipMemcpyHostToDevice, cs.st));
-    if (ratio) HIP_TRY(hipMemcpyAsync(dR.p, lnr, (size_t)S * 8, hipMemcpyHostToDevice, cs.st));
-    if (D > 0) HIP_TRY(hipMemcpyAsync(dV.p, V, (size_t)S * D * 8, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dT.p, tfs, (size_t)K * 8, hipMemcpyHostToDevice, cs.st));
-    const double t0 = now_s();
-    if (int rc = scan_dev(dL.as<double>(), dR.as<double>(), ratio, S, D > 0 ? dV.as<double>() : nullptr, D, dT.as<double>(), K,
-                          dSt.as<double>(), dM.as<double>(), dVar.as<double>(), dQ.as<double>(), ws.p, (int64_t)wsb, cs.st))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(stats, dSt.p, sb, hipMemcpyDeviceToHost, cs.st));
-    if (D > 0) {
-        HIP_TRY(hipMemcpyAsync(mean, dM.p, kd, hipMemcpyDeviceToHost, cs.st));
-        HIP_TRY(hipMemcpyAsync(var, dVar.p, kd, hipMemcpyDeviceToHost, cs.st));
-        HIP_TRY(hipMemcpyAsync(Q, dQ.p, kd, hipMemcpyDeviceToHost, cs.st));
-    }
-    HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
-    return TRPL_OK;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const size_t wsb = (size_t)scan_workspace(S, D, K, ratio), kd = (size_t)K * D;
+    const double *dL = sg.in(LL, (size_t)S), *dR = ratio ? sg.in(lnr, (size_t)S) : nullptr, *dV = sg.in(V, (size_t)S * D);
+    const double *dT = sg.in(tfs, (size_t)K);
+    double *dSt = sg.out(stats, (size_t)K * (ratio ? 6 : 4)), *dM = sg.out(mean, kd), *dVar = sg.out(var, kd), *dQ = sg.out(Q, kd);
+    void *ws = sg.scratch(wsb);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = scan_dev(dL, dR, ratio, S, D > 0 ? dV : nullptr, D, dT, K, dSt, dM, dVar, dQ, ws, (int64_t)wsb, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 extern "C" {

@@ -284,36 +284,20 @@ int trpl_predictive(const void *plI, int32_t elem_bytes, int64_t rows, int64_t n
     if (seconds) *seconds = 0.0;
     if (int rc = check_accumulate(plI, elem_bytes, rows, ncol, ld, W, flags)) return rc;
     if (!out) return api_fail(TRPL_ERR_ARG, "out is NULL");
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dPl, dMag, dW, dSt, dState, dWs, dOut;
-    const size_t plb = (size_t)rows * (size_t)ld * (size_t)elem_bytes, sb = (size_t)trpl_predictive_state_bytes(ncol);
-    const size_t wsb = (size_t)trpl_predictive_workspace_bytes(rows, ncol, elem_bytes);
-    HIP_TRY(dPl.alloc(plb, cs.st)); HIP_TRY(dW.alloc((size_t)rows * 8, cs.st)); HIP_TRY(dState.alloc(sb, cs.st));
-    HIP_TRY(dWs.alloc(wsb, cs.st)); HIP_TRY(dOut.alloc(sb, cs.st));
-    HIP_TRY(hipMemcpyAsync(dPl.p, plI, plb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dW.p, W, (size_t)rows * 8, hipMemcpyHostToDevice, cs.st));
-    if (mag) {
-        HIP_TRY(dMag.alloc((size_t)rows * 8, cs.st));
-        HIP_TRY(hipMemcpyAsync(dMag.p, mag, (size_t)rows * 8, hipMemcpyHostToDevice, cs.st));
-    }
-    if (status) {
-        HIP_TRY(dSt.alloc((size_t)rows * 4, cs.st));
-        HIP_TRY(hipMemcpyAsync(dSt.p, status, (size_t)rows * 4, hipMemcpyHostToDevice, cs.st));
-    }
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_predictive_init_dev(dState.p, ncol, cs.st)) return rc;
-    if (int rc = trpl_predictive_accumulate_dev(dPl.p, elem_bytes, rows, ncol, ld, mag ? dMag.as<double>() : nullptr, dW.as<double>(),
-                                                status ? dSt.as<int32_t>() : nullptr, flags, dState.p, dWs.p, (int64_t)wsb, cs.st))
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const size_t sb = (size_t)trpl_predictive_state_bytes(ncol), wsb = (size_t)trpl_predictive_workspace_bytes(rows, ncol, elem_bytes);
+    const void *dPl = sg.in(plI, (size_t)rows * (size_t)ld * (size_t)elem_bytes);
+    const double *dW = sg.in(W, (size_t)rows), *dMag = mag ? sg.in(mag, (size_t)rows) : nullptr;
+    const int32_t *dSt = status ? sg.in(status, (size_t)rows) : nullptr;
+    void *dState = sg.scratch(sb), *dWs = sg.scratch(wsb);
+    double *dOut = (double *)sg.out((void *)out, sb);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_predictive_init_dev(dState, ncol, sg.stream())) return rc;
+    if (int rc = trpl_predictive_accumulate_dev(dPl, elem_bytes, rows, ncol, ld, dMag, dW, dSt, flags, dState, dWs, (int64_t)wsb, sg.stream()))
         return rc;
-    if (int rc = trpl_predictive_finish_dev(dState.p, ncol, dOut.as<double>(), cs.st)) return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(out, dOut.p, sb, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));        // the copy back has landed (and its errors surface here)
-    return TRPL_OK;
+    if (int rc = trpl_predictive_finish_dev(dState, ncol, dOut, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 }  // extern "C"

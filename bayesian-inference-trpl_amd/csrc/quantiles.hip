@@ -313,23 +313,13 @@ int trpl_weighted_quantiles(const double *Y, int64_t ncols, int64_t n, int64_t l
 {
     if (seconds) *seconds = 0.0;
     if (int rc = check_select(Y, ncols, n, ldy, Wq, q, rule, K, flags, out)) return rc;
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dY, dW, dOut;
-    const size_t yb = ((size_t)(ncols - 1) * (size_t)ldy + (size_t)n) * 8, ob = (size_t)K * (size_t)ncols * 8;
-    HIP_TRY(dY.alloc(yb, cs.st)); HIP_TRY(dW.alloc((size_t)n * 8, cs.st)); HIP_TRY(dOut.alloc(ob, cs.st));
-    HIP_TRY(hipMemcpyAsync(dY.p, Y, yb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dW.p, Wq, (size_t)n * 8, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_weighted_quantiles_dev(dY.as<double>(), ncols, n, ldy, dW.as<double>(), q, rule, K, flags, dOut.as<double>(), cs.st))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(out, dOut.p, ob, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    return TRPL_OK;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const double *dY = sg.in(Y, (size_t)(ncols - 1) * (size_t)ldy + (size_t)n), *dW = sg.in(Wq, (size_t)n);   // Y ends with its last column
+    double *dOut = sg.out(out, (size_t)K * (size_t)ncols);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_weighted_quantiles_dev(dY, ncols, n, ldy, dW, q, rule, K, flags, dOut, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 int trpl_predictive_gather_dev(const void *plI, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld, const double *mag,

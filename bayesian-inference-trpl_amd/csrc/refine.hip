@@ -282,19 +282,10 @@ __global__ void __launch_bounds__(kThreads) density_kernel(const double *U, int6
     if (s < S) B[s] = acc;
 }
 
-template <int A>
-static void launch_density(unsigned grid, hipStream_t st, const double *U, int64_t S, int64_t ldu, const double *a, const double *b,
-                           const double *inv_vol, int64_t K, double *B)
-{
-    hipLaunchKernelGGL(density_kernel<A>, dim3(grid), dim3(kThreads), 0, st, U, S, ldu, a, b, inv_vol, K, B);
-}
-
 }  // namespace refine
 }  // namespace trpl
 
 using namespace trpl;
-
-static const int64_t kMaxBlocks = kRefineMaxBlocks;
 
 static int check_resample(const void *W, int64_t S, int64_t K, double offset, const void *idx)
 {
@@ -324,8 +315,7 @@ static int check_density(const void *U, int64_t S, int64_t ldu, int32_t A, const
     if (S < 0) return api_fail(TRPL_ERR_ARG, "S=%lld must be >= 0", (long long)S);
     if (int rc = refine_check_counts(K, A)) return rc;
     if (ldu < A) return api_fail(TRPL_ERR_ARG, "ldu=%lld must be >= A=%d", (long long)ldu, A);
-    if ((S + refine::kThreads - 1) / refine::kThreads > kMaxBlocks)
-        return api_fail(TRPL_ERR_ARG, "S=%lld is more than 2^31 - 1 blocks of %d samples", (long long)S, refine::kThreads);
+    if (int rc = refine_check_blocks("S", S, "samples")) return rc;
     if (!a) return api_fail(TRPL_ERR_ARG, "a is NULL");
     if (!b) return api_fail(TRPL_ERR_ARG, "b is NULL");
     if (!inv_vol) return api_fail(TRPL_ERR_ARG, "inv_vol is NULL");
@@ -339,8 +329,7 @@ static int check_unit(const void *X, int64_t S, int64_t ldx, int32_t ncol, int32
     if (S < 0) return api_fail(TRPL_ERR_ARG, "S=%lld must be >= 0", (long long)S);
     if (A < 1 || A > TRPL_REFINE_MAX_DIMS) return api_fail(TRPL_ERR_ARG, "A=%d must be in [1, %d]", A, TRPL_REFINE_MAX_DIMS);
     if (ldx < ncol) return api_fail(TRPL_ERR_ARG, "ldx=%lld must be >= ncol=%d", (long long)ldx, ncol);
-    if ((S + refine::kThreads - 1) / refine::kThreads > kMaxBlocks)
-        return api_fail(TRPL_ERR_ARG, "S=%lld is more than 2^31 - 1 blocks of %d samples", (long long)S, refine::kThreads);
+    if (int rc = refine_check_blocks("S", S, "samples")) return rc;
     if (S > 0 && !X) return api_fail(TRPL_ERR_ARG, "X is NULL");
     if (S > 0 && !U) return api_fail(TRPL_ERR_ARG, "U is NULL");
     return TRPL_OK;
@@ -368,15 +357,13 @@ int trpl_refine_resample_dev(const double *W, int64_t S, int64_t K, double offse
         return api_fail(TRPL_ERR_ARG, "workspace_bytes=%lld is less than trpl_refine_workspace_bytes(S) = %lld", (long long)workspace_bytes,
                         (long long)trpl_refine_workspace_bytes(S));
     const int64_t nch = chunks_of(S);
-    if (nch > kMaxBlocks) return api_fail(TRPL_ERR_ARG, "S=%lld is more than 2^31 - 1 chunks", (long long)S);
+    if (nch > kRefineMaxBlocks) return api_fail(TRPL_ERR_ARG, "S=%lld is more than 2^31 - 1 chunks", (long long)S);
     hipStream_t st = (hipStream_t)stream;
     double *tot = (double *)workspace, *sq = tot + nch, *ex = sq + nch, *prefix = ex + nch;
     if (nch) hipLaunchKernelGGL(refine::chunk_sums_kernel, dim3((unsigned)nch), dim3(refine::kThreads), 0, st, W, S, tot, sq, ex);
     hipLaunchKernelGGL(refine::chunk_prefix_kernel, dim3(1), dim3(refine::kThreads), 0, st, tot, sq, ex, nch, prefix, stats);
     hipLaunchKernelGGL(refine::resample_kernel, dim3((unsigned)(nch ? nch : 1)), dim3(refine::kThreads), 0, st, W, S, K, offset, prefix, nch, idx);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "refine resample launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    return refine_launched("refine resample");
 }
 
 int trpl_refine_resample(const double *W, int64_t S, int64_t K, double offset, int64_t *idx, double *stats, int32_t device, double *seconds)
@@ -385,23 +372,16 @@ int trpl_refine_resample(const double *W, int64_t S, int64_t K, double offset, i
     if (int rc = check_resample(W, S, K, offset, idx)) return rc;
     for (int64_t i = 0; i < S; i++)
         if (W[i] == INFINITY) return api_fail(TRPL_ERR_ARG, "W[%lld] is +inf: a weight must be finite", (long long)i);
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dW, dIdx, dStats, dWs;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
     const int64_t wsb = trpl_refine_workspace_bytes(S);
-    HIP_TRY(dW.alloc((size_t)S * 8, cs.st)); HIP_TRY(dIdx.alloc((size_t)K * 8, cs.st)); HIP_TRY(dStats.alloc(24, cs.st));
-    HIP_TRY(dWs.alloc((size_t)wsb, cs.st));
-    if (S > 0) HIP_TRY(hipMemcpyAsync(dW.p, W, (size_t)S * 8, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_refine_resample_dev(dW.as<double>(), S, K, offset, dIdx.as<int64_t>(), dStats.as<double>(), dWs.p, wsb, cs.st)) return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(idx, dIdx.p, (size_t)K * 8, hipMemcpyDeviceToHost, cs.st));
-    if (stats) HIP_TRY(hipMemcpyAsync(stats, dStats.p, 24, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    return TRPL_OK;
+    const double *dW = sg.in(W, (size_t)S);
+    int64_t *dIdx = sg.out(idx, (size_t)K);
+    double *dStats = sg.out(stats, 3);
+    void *dWs = sg.scratch((size_t)wsb);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_refine_resample_dev(dW, S, K, offset, dIdx, dStats, dWs, wsb, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 int trpl_refine_draw_dev(const double *a, const double *b, int64_t K, int32_t A, int64_t m, int64_t n_uniform, uint64_t seed,
@@ -413,12 +393,9 @@ int trpl_refine_draw_dev(const double *a, const double *b, int64_t K, int32_t A,
     if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
     const int64_t total = n_uniform + K * m;
     if (total == 0) return TRPL_OK;
-    const int64_t nblk = (total + refine::kThreads - 1) / refine::kThreads;
-    hipLaunchKernelGGL(refine::draw_kernel, dim3((unsigned)nblk), dim3(refine::kThreads), 0, (hipStream_t)stream, a, b, K, n_uniform, total,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), generation, bx, U2, X2);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "refine draw launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    hipLaunchKernelGGL(refine::draw_kernel, dim3(refine_blocks(total)), dim3(refine::kThreads), 0, (hipStream_t)stream, a, b, K, n_uniform,
+                       total, (uint32_t)seed, (uint32_t)(seed >> 32), generation, bx, U2, X2);
+    return refine_launched("refine draw");
 }
 
 int trpl_refine_draw(const double *a, const double *b, int64_t K, int32_t A, int64_t m, int64_t n_uniform, uint64_t seed, uint32_t generation,
@@ -431,25 +408,13 @@ int trpl_refine_draw(const double *a, const double *b, int64_t K, int32_t A, int
     if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
     const int64_t total = n_uniform + K * m;
     if (total == 0) return TRPL_OK;
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dA, dB, dU, dX;
-    const size_t kb = (size_t)K * A * 8, ub = (size_t)total * A * 8, xb = (size_t)total * ncol * 8;
-    HIP_TRY(dA.alloc(kb, cs.st)); HIP_TRY(dB.alloc(kb, cs.st)); HIP_TRY(dU.alloc(ub, cs.st)); HIP_TRY(dX.alloc(xb, cs.st));
-    HIP_TRY(hipMemcpyAsync(dA.p, a, kb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dB.p, b, kb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_refine_draw_dev(dA.as<double>(), dB.as<double>(), K, A, m, n_uniform, seed, generation, ncol, lo, hi, do_log, flags,
-                                      dU.as<double>(), dX.as<double>(), cs.st))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(U2, dU.p, ub, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipMemcpyAsync(X2, dX.p, xb, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    return TRPL_OK;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const double *dA = sg.in(a, (size_t)K * A), *dB = sg.in(b, (size_t)K * A);
+    double *dU = sg.out(U2, (size_t)total * A), *dX = sg.out(X2, (size_t)total * ncol);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_refine_draw_dev(dA, dB, K, A, m, n_uniform, seed, generation, ncol, lo, hi, do_log, flags, dU, dX, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 int trpl_refine_density_dev(const double *U, int64_t S, int64_t ldu, int32_t A, const double *a, const double *b, const double *inv_vol,
@@ -457,18 +422,13 @@ int trpl_refine_density_dev(const double *U, int64_t S, int64_t ldu, int32_t A, 
 {
     if (int rc = check_density(U, S, ldu, A, a, b, inv_vol, K, B)) return rc;
     if (S == 0) return TRPL_OK;
-    const unsigned grid = (unsigned)((S + refine::kThreads - 1) / refine::kThreads);
-    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(refine_blocks(S)), block(refine::kThreads);
     switch (A) {
-#define TRPL_REFINE_CASE(n) case n: refine::launch_density<n>(grid, st, U, S, ldu, a, b, inv_vol, K, B); break;
-        TRPL_REFINE_CASE(1) TRPL_REFINE_CASE(2) TRPL_REFINE_CASE(3) TRPL_REFINE_CASE(4) TRPL_REFINE_CASE(5) TRPL_REFINE_CASE(6)
-        TRPL_REFINE_CASE(7) TRPL_REFINE_CASE(8) TRPL_REFINE_CASE(9) TRPL_REFINE_CASE(10) TRPL_REFINE_CASE(11) TRPL_REFINE_CASE(12)
-        TRPL_REFINE_CASE(13) TRPL_REFINE_CASE(14) TRPL_REFINE_CASE(15) TRPL_REFINE_CASE(16)
-#undef TRPL_REFINE_CASE
+#define TRPL_CASE(n) case n: hipLaunchKernelGGL(refine::density_kernel<n>, grid, block, 0, (hipStream_t)stream, U, S, ldu, a, b, inv_vol, K, B); break;
+        TRPL_REFINE_DIMS(TRPL_CASE)
+#undef TRPL_CASE
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "refine density launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    return refine_launched("refine density");
 }
 
 int trpl_refine_density(const double *U, int64_t S, int64_t ldu, int32_t A, const double *a, const double *b, const double *inv_vol, int64_t K,
@@ -477,26 +437,14 @@ int trpl_refine_density(const double *U, int64_t S, int64_t ldu, int32_t A, cons
     if (seconds) *seconds = 0.0;
     if (int rc = check_density(U, S, ldu, A, a, b, inv_vol, K, B)) return rc;
     if (S == 0) return TRPL_OK;
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dU, dA, dB, dV, dOut;
-    const size_t ub = ((size_t)(S - 1) * (size_t)ldu + A) * 8, kb = (size_t)K * A * 8;
-    HIP_TRY(dU.alloc(ub, cs.st)); HIP_TRY(dA.alloc(kb, cs.st)); HIP_TRY(dB.alloc(kb, cs.st)); HIP_TRY(dV.alloc((size_t)K * 8, cs.st));
-    HIP_TRY(dOut.alloc((size_t)S * 8, cs.st));
-    HIP_TRY(hipMemcpyAsync(dU.p, U, ub, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dA.p, a, kb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dB.p, b, kb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dV.p, inv_vol, (size_t)K * 8, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_refine_density_dev(dU.as<double>(), S, ldu, A, dA.as<double>(), dB.as<double>(), dV.as<double>(), K, dOut.as<double>(), cs.st))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(B, dOut.p, (size_t)S * 8, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    return TRPL_OK;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const double *dU = sg.in(U, (size_t)(S - 1) * (size_t)ldu + A);                      // the last row ends after its A entries
+    const double *dA = sg.in(a, (size_t)K * A), *dB = sg.in(b, (size_t)K * A), *dV = sg.in(inv_vol, (size_t)K);
+    double *dOut = sg.out(B, (size_t)S);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_refine_density_dev(dU, S, ldu, A, dA, dB, dV, K, dOut, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 int trpl_refine_unit_dev(const double *X, int64_t S, int64_t ldx, int32_t ncol, const double *lo, const double *hi, const int32_t *do_log,
@@ -506,11 +454,8 @@ int trpl_refine_unit_dev(const double *X, int64_t S, int64_t ldx, int32_t ncol, 
     if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
     if (int rc = check_unit(X, S, ldx, ncol, A, U)) return rc;
     if (S == 0) return TRPL_OK;
-    const unsigned grid = (unsigned)((S + refine::kThreads - 1) / refine::kThreads);
-    hipLaunchKernelGGL(refine::unit_kernel, dim3(grid), dim3(refine::kThreads), 0, (hipStream_t)stream, X, S, ldx, bx, U);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "refine unit launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    hipLaunchKernelGGL(refine::unit_kernel, dim3(refine_blocks(S)), dim3(refine::kThreads), 0, (hipStream_t)stream, X, S, ldx, bx, U);
+    return refine_launched("refine unit");
 }
 
 int trpl_refine_unit(const double *X, int64_t S, int64_t ldx, int32_t ncol, const double *lo, const double *hi, const int32_t *do_log,
@@ -521,21 +466,13 @@ int trpl_refine_unit(const double *X, int64_t S, int64_t ldx, int32_t ncol, cons
     if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
     if (int rc = check_unit(X, S, ldx, ncol, A, U)) return rc;
     if (S == 0) return TRPL_OK;
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dX, dU;
-    const size_t xb = ((size_t)(S - 1) * (size_t)ldx + ncol) * 8, ub = (size_t)S * A * 8;
-    HIP_TRY(dX.alloc(xb, cs.st)); HIP_TRY(dU.alloc(ub, cs.st));
-    HIP_TRY(hipMemcpyAsync(dX.p, X, xb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_refine_unit_dev(dX.as<double>(), S, ldx, ncol, lo, hi, do_log, flags, A, dU.as<double>(), cs.st)) return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(U, dU.p, ub, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    return TRPL_OK;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const double *dX = sg.in(X, (size_t)(S - 1) * (size_t)ldx + ncol);                   // the last row ends after its ncol entries
+    double *dU = sg.out(U, (size_t)S * A);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_refine_unit_dev(dX, S, ldx, ncol, lo, hi, do_log, flags, A, dU, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 }  // extern "C"

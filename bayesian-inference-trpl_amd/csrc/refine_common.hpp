@@ -63,6 +63,24 @@ __device__ __forceinline__ void put_overrides(const Box &bx, double *row)
 
 static const int64_t kRefineMaxBlocks = 0x7fffffff;              // gridDim.x
 
+// the number of active dimensions A a kernel is instantiated for: switch (A) { TRPL_REFINE_DIMS(CASE) }
+#define TRPL_REFINE_DIMS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+
+// the grid of one thread per item: blocks of kThreads over n, refused above gridDim.x ("S=.. is more than .. blocks of 256 samples")
+static inline unsigned refine_blocks(int64_t n) { return (unsigned)((n + refine::kThreads - 1) / refine::kThreads); }
+static inline int refine_check_blocks(const char *name, int64_t n, const char *items)
+{
+    if ((n + refine::kThreads - 1) / refine::kThreads > kRefineMaxBlocks)
+        return api_fail(TRPL_ERR_ARG, "%s=%lld is more than 2^31 - 1 blocks of %d %s", name, (long long)n, refine::kThreads, items);
+    return TRPL_OK;
+}
+// after the launches of a _dev form: TRPL_ERR_HIP "<what> launch: .." if one of them was refused
+static inline int refine_launched(const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRPL_OK : api_fail(TRPL_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
+}
+
 static inline int refine_check_counts(int64_t K, int32_t A)
 {
     if (K < 1 || K > TRPL_REFINE_MAX_PARENTS)

@@ -99,27 +99,10 @@ __global__ void __launch_bounds__(kThreads) draw_oriented_kernel(const double *z
     inside[n] = in ? 1 : 0;
 }
 
-template <int A>
-static void launch_affine(unsigned grid, hipStream_t st, const double *U, int64_t S, int64_t ldu, const Affine &mc, double *Z, int64_t ldz)
-{
-    hipLaunchKernelGGL(affine_kernel<A>, dim3(grid), dim3(kThreads), 0, st, U, S, ldu, mc, Z, ldz);
-}
-
-template <int A>
-static void launch_draw(unsigned grid, hipStream_t st, const double *zc, int64_t K, int64_t n_uniform, int64_t total, uint64_t seed,
-                        uint32_t generation, const Affine &lc, const HalfWidths &hw, const Box &bx, double *Z2, double *U2, double *X2,
-                        int32_t *inside)
-{
-    hipLaunchKernelGGL(draw_oriented_kernel<A>, dim3(grid), dim3(kThreads), 0, st, zc, K, n_uniform, total, (uint32_t)seed,
-                       (uint32_t)(seed >> 32), generation, lc, hw, bx, Z2, U2, X2, inside);
-}
-
 }  // namespace refine_oriented
 }  // namespace trpl
 
 using namespace trpl;
-
-#define TRPL_ORIENTED_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
 
 // a host lower-triangular [A][A] row-major matrix and a host vector -> the kernels' packed arguments; only j <= i is read.
 // Refuses a non-finite entry and a diagonal that is not positive.
@@ -145,8 +128,7 @@ static int check_affine(const void *U, int64_t S, int64_t ldu, int32_t A, const 
     if (A < 1 || A > TRPL_REFINE_MAX_DIMS) return api_fail(TRPL_ERR_ARG, "A=%d must be in [1, %d]", A, TRPL_REFINE_MAX_DIMS);
     if (ldu < A) return api_fail(TRPL_ERR_ARG, "ldu=%lld must be >= A=%d", (long long)ldu, A);
     if (ldz < A) return api_fail(TRPL_ERR_ARG, "ldz=%lld must be >= A=%d", (long long)ldz, A);
-    if ((S + refine::kThreads - 1) / refine::kThreads > kRefineMaxBlocks)
-        return api_fail(TRPL_ERR_ARG, "S=%lld is more than 2^31 - 1 blocks of %d samples", (long long)S, refine::kThreads);
+    if (int rc = refine_check_blocks("S", S, "samples")) return rc;
     if (!U) return api_fail(TRPL_ERR_ARG, "U is NULL");
     if (!M) return api_fail(TRPL_ERR_ARG, "M is NULL");
     if (!c) return api_fail(TRPL_ERR_ARG, "c is NULL");
@@ -184,16 +166,13 @@ int trpl_refine_affine_dev(const double *U, int64_t S, int64_t ldu, int32_t A, c
     if (int rc = check_affine(U, S, ldu, A, M, c, Z, ldz)) return rc;
     refine_oriented::Affine mc;
     if (int rc = pack_affine("M", M, c, A, mc)) return rc;
-    const unsigned grid = (unsigned)((S + refine::kThreads - 1) / refine::kThreads);
-    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(refine_blocks(S)), block(refine::kThreads);
     switch (A) {
-#define TRPL_CASE(n) case n: refine_oriented::launch_affine<n>(grid, st, U, S, ldu, mc, Z, ldz); break;
-        TRPL_ORIENTED_CASES(TRPL_CASE)
+#define TRPL_CASE(n) case n: hipLaunchKernelGGL(refine_oriented::affine_kernel<n>, grid, block, 0, (hipStream_t)stream, U, S, ldu, mc, Z, ldz); break;
+        TRPL_REFINE_DIMS(TRPL_CASE)
 #undef TRPL_CASE
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "refine affine launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    return refine_launched("refine affine");
 }
 
 int trpl_refine_affine(const double *U, int64_t S, int64_t ldu, int32_t A, const double *M, const double *c, double *Z, int64_t ldz,
@@ -203,21 +182,13 @@ int trpl_refine_affine(const double *U, int64_t S, int64_t ldu, int32_t A, const
     if (int rc = check_affine(U, S, ldu, A, M, c, Z, ldz)) return rc;
     refine_oriented::Affine mc;
     if (int rc = pack_affine("M", M, c, A, mc)) return rc;
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dU, dZ;                                               // both compact on the device: the rows' padding stays on the host
-    const size_t row = (size_t)A * 8;
-    HIP_TRY(dU.alloc((size_t)S * row, cs.st)); HIP_TRY(dZ.alloc((size_t)S * row, cs.st));
-    HIP_TRY(hipMemcpy2DAsync(dU.p, row, U, (size_t)ldu * 8, row, (size_t)S, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_refine_affine_dev(dU.as<double>(), S, A, A, M, c, dZ.as<double>(), A, cs.st)) return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpy2DAsync(Z, (size_t)ldz * 8, dZ.p, row, row, (size_t)S, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    return TRPL_OK;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const double *dU = sg.in(U, (size_t)ldu, (size_t)A, (size_t)S);                      // both compact on the device: the rows' padding
+    double *dZ = sg.out(Z, (size_t)ldz, (size_t)A, (size_t)S);                           // stays on the host
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_refine_affine_dev(dU, S, A, A, M, c, dZ, A, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 int trpl_refine_draw_oriented_dev(const double *zc, const double *h, const double *L, const double *c, int64_t K, int32_t A, int64_t m,
@@ -232,16 +203,17 @@ int trpl_refine_draw_oriented_dev(const double *zc, const double *h, const doubl
     if (int rc = pack_affine("L", L, c, A, lc)) return rc;
     const int64_t total = n_uniform + K * m;
     if (total == 0) return TRPL_OK;
-    const unsigned grid = (unsigned)((total + refine::kThreads - 1) / refine::kThreads);
-    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(refine_blocks(total)), block(refine::kThreads);
     switch (A) {
-#define TRPL_CASE(n) case n: refine_oriented::launch_draw<n>(grid, st, zc, K, n_uniform, total, seed, generation, lc, hw, bx, Z2, U2, X2, inside); break;
-        TRPL_ORIENTED_CASES(TRPL_CASE)
+#define TRPL_CASE(n)                                                                                                                   \
+    case n:                                                                                                                            \
+        hipLaunchKernelGGL(refine_oriented::draw_oriented_kernel<n>, grid, block, 0, (hipStream_t)stream, zc, K, n_uniform, total,         \
+                           (uint32_t)seed, (uint32_t)(seed >> 32), generation, lc, hw, bx, Z2, U2, X2, inside);                        \
+        break;
+        TRPL_REFINE_DIMS(TRPL_CASE)
 #undef TRPL_CASE
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "refine oriented draw launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    return refine_launched("refine oriented draw");
 }
 
 int trpl_refine_draw_oriented(const double *zc, const double *h, const double *L, const double *c, int64_t K, int32_t A, int64_t m,
@@ -258,27 +230,16 @@ int trpl_refine_draw_oriented(const double *zc, const double *h, const double *L
     if (int rc = pack_affine("L", L, c, A, lc)) return rc;
     const int64_t total = n_uniform + K * m;
     if (total == 0) return TRPL_OK;
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dC, dZ, dU, dX, dIn;
-    const size_t kb = (size_t)K * A * 8, ub = (size_t)total * A * 8, xb = (size_t)total * ncol * 8, ib = (size_t)total * 4;
-    HIP_TRY(dC.alloc(kb, cs.st)); HIP_TRY(dZ.alloc(ub, cs.st)); HIP_TRY(dU.alloc(ub, cs.st)); HIP_TRY(dX.alloc(xb, cs.st));
-    HIP_TRY(dIn.alloc(ib, cs.st));
-    HIP_TRY(hipMemcpyAsync(dC.p, zc, kb, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_refine_draw_oriented_dev(dC.as<double>(), h, L, c, K, A, m, n_uniform, seed, generation, ncol, lo, hi, do_log, flags,
-                                               dZ.as<double>(), dU.as<double>(), dX.as<double>(), dIn.as<int32_t>(), cs.st))
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const double *dC = sg.in(zc, (size_t)K * A);
+    double *dZ = sg.out(Z2, (size_t)total * A), *dU = sg.out(U2, (size_t)total * A), *dX = sg.out(X2, (size_t)total * ncol);
+    int32_t *dIn = sg.out(inside, (size_t)total);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_refine_draw_oriented_dev(dC, h, L, c, K, A, m, n_uniform, seed, generation, ncol, lo, hi, do_log, flags, dZ, dU, dX, dIn,
+                                               sg.stream()))
         return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(Z2, dZ.p, ub, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipMemcpyAsync(U2, dU.p, ub, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipMemcpyAsync(X2, dX.p, xb, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipMemcpyAsync(inside, dIn.p, ib, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    return TRPL_OK;
+    return sg.finish(seconds);
 }
 
 }  // extern "C"

@@ -1339,27 +1339,17 @@ int trpl_posterior_weights_lr_dev(const double *LL, const double *lnr, int64_t S
 static int weights_staged(const double *LL, const double *lnr, int64_t S, double tf, double *W, double *stats, int32_t device,
                           double *seconds)
 {
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dL, dR, dW, dSt, ws;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
     const size_t wsb = trpl::posterior_workspace_bytes(1);
-    HIP_TRY(dL.alloc((size_t)S * 8, cs.st));
-    if (lnr) HIP_TRY(dR.alloc((size_t)S * 8, cs.st));
-    HIP_TRY(dW.alloc((size_t)S * 8, cs.st)); HIP_TRY(dSt.alloc(16, cs.st)); HIP_TRY(ws.alloc(wsb, cs.st));
-    HIP_TRY(hipMemcpyAsync(dL.p, LL, (size_t)S * 8, hipMemcpyHostToDevice, cs.st));
-    if (lnr) HIP_TRY(hipMemcpyAsync(dR.p, lnr, (size_t)S * 8, hipMemcpyHostToDevice, cs.st));
-    const double t0 = now_s();
-    if (int rc = lnr ? trpl_posterior_weights_lr_dev(dL.as<double>(), dR.as<double>(), S, tf, dW.as<double>(), dSt.as<double>(), ws.p,
-                                                     (int64_t)wsb, cs.st)
-                     : trpl_posterior_weights_dev(dL.as<double>(), S, tf, dW.as<double>(), dSt.as<double>(), ws.p, (int64_t)wsb, cs.st))
+    const double *dL = sg.in(LL, (size_t)S), *dR = lnr ? sg.in(lnr, (size_t)S) : nullptr;
+    double *dW = sg.out(W, (size_t)S), *dSt = sg.out(stats, 2);
+    void *ws = sg.scratch(wsb);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = lnr ? trpl_posterior_weights_lr_dev(dL, dR, S, tf, dW, dSt, ws, (int64_t)wsb, sg.stream())
+                     : trpl_posterior_weights_dev(dL, S, tf, dW, dSt, ws, (int64_t)wsb, sg.stream()))
         return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(W, dW.p, (size_t)S * 8, hipMemcpyDeviceToHost, cs.st));
-    if (stats) HIP_TRY(hipMemcpyAsync(stats, dSt.p, 16, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
-    return TRPL_OK;
+    return sg.finish(seconds);
 }
 
 int trpl_posterior_weights(const double *LL, int64_t S, double tf, double *W, double *stats, int32_t device,
@@ -1403,27 +1393,15 @@ int trpl_posterior_moments(const double *V, int64_t S, int32_t D, const double *
     memset(central, 0, sizeof(double) * D * (D + 2));
     if (S == 0) return TRPL_OK;
     if (!V || !W) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dV, dW, dS, dC, dM, ws;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
     const size_t wsb = trpl::posterior_workspace_bytes(D);
-    if (mean_in) { HIP_TRY(dM.alloc((size_t)D * 8, cs.st)); HIP_TRY(hipMemcpyAsync(dM.p, mean_in, (size_t)D * 8, hipMemcpyHostToDevice, cs.st)); }
-    HIP_TRY(dV.alloc((size_t)S * D * 8, cs.st)); HIP_TRY(dW.alloc((size_t)S * 8, cs.st)); HIP_TRY(dS.alloc((2 + D) * 8, cs.st));
-    HIP_TRY(dC.alloc((size_t)D * (D + 2) * 8, cs.st)); HIP_TRY(ws.alloc(wsb, cs.st));
-    HIP_TRY(hipMemcpyAsync(dV.p, V, (size_t)S * D * 8, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dW.p, W, (size_t)S * 8, hipMemcpyHostToDevice, cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_posterior_moments_dev(dV.as<double>(), S, D, dW.as<double>(), mean_in ? dM.as<double>() : nullptr,
-                                            dS.as<double>(), dC.as<double>(), ws.p,
-                                            (int64_t)wsb, cs.st))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(sums, dS.p, (2 + D) * 8, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipMemcpyAsync(central, dC.p, (size_t)D * (D + 2) * 8, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
-    return TRPL_OK;
+    const double *dV = sg.in(V, (size_t)S * D), *dW = sg.in(W, (size_t)S), *dM = mean_in ? sg.in(mean_in, (size_t)D) : nullptr;
+    double *dS = sg.out(sums, (size_t)(2 + D)), *dC = sg.out(central, (size_t)D * (D + 2));
+    void *ws = sg.scratch(wsb);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_posterior_moments_dev(dV, S, D, dW, dM, dS, dC, ws, (int64_t)wsb, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 static int check_hist(int64_t S, double xlo, double xhi, int32_t xb, const double *y, double ylo, double yhi, int32_t yb)
@@ -1457,24 +1435,13 @@ int trpl_posterior_hist(const double *x, const double *y, const double *W, int64
     memset(out, 0, nb * 8);
     if (S == 0) return TRPL_OK;
     if (!x) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dx, dy, dW, dO;
-    HIP_TRY(dx.alloc((size_t)S * 8, cs.st)); HIP_TRY(dO.alloc(nb * 8, cs.st));
-    HIP_TRY(hipMemcpyAsync(dx.p, x, (size_t)S * 8, hipMemcpyHostToDevice, cs.st));
-    if (y) { HIP_TRY(dy.alloc((size_t)S * 8, cs.st)); HIP_TRY(hipMemcpyAsync(dy.p, y, (size_t)S * 8, hipMemcpyHostToDevice, cs.st)); }
-    if (W) { HIP_TRY(dW.alloc((size_t)S * 8, cs.st)); HIP_TRY(hipMemcpyAsync(dW.p, W, (size_t)S * 8, hipMemcpyHostToDevice, cs.st)); }
-    HIP_TRY(hipMemsetAsync(dO.p, 0, nb * 8, cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_posterior_hist_dev(dx.as<double>(), y ? dy.as<double>() : nullptr, W ? dW.as<double>() : nullptr, S, xlo,
-                                         xhi, xbins, ylo, yhi, ybins, dO.as<double>(), cs.st))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(out, dO.p, nb * 8, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
-    return TRPL_OK;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const double *dx = sg.in(x, (size_t)S), *dy = y ? sg.in(y, (size_t)S) : nullptr, *dW = W ? sg.in(W, (size_t)S) : nullptr;
+    double *dO = sg.inout(out, nb);                              // the kernel adds into it: up as zeros
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_posterior_hist_dev(dx, dy, dW, S, xlo, xhi, xbins, ylo, yhi, ybins, dO, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 /* ------------------------------------------------------------------ sampler -------------- */
@@ -1508,18 +1475,12 @@ int trpl_sample_box(uint32_t seed, int64_t S, int32_t ncol, const double *lo, co
     if (int rc = check_box(S, ncol, lo, hi, do_log)) return rc;
     if (S == 0) return TRPL_OK;
     if (!X) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    DevBuf dX;
-    HIP_TRY(dX.alloc((size_t)S * ncol * 8, cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_sample_box_dev(seed, S, ncol, lo, hi, do_log, flags, dX.as<double>(), cs.st)) return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(X, dX.p, (size_t)S * ncol * 8, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
-    return TRPL_OK;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    double *dX = sg.out(X, (size_t)S * ncol);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_sample_box_dev(seed, S, ncol, lo, hi, do_log, flags, dX, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 /* ------------------------------------------------------------------ batched PCR --------- */
@@ -1547,23 +1508,14 @@ int trpl_pcr_solve_batched(const void *ld, const void *d, const void *ud, const 
     if (seconds) *seconds = 0.0;
     if (S == 0) return TRPL_OK;
     if (!ld || !d || !ud || !b || !x) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
     const size_t n = (size_t)S * L * elem_bytes;
-    DevBuf bl, bd, bu, bb, bx;
-    HIP_TRY(bl.alloc(n, cs.st)); HIP_TRY(bd.alloc(n, cs.st)); HIP_TRY(bu.alloc(n, cs.st)); HIP_TRY(bb.alloc(n, cs.st)); HIP_TRY(bx.alloc(n, cs.st));
-    HIP_TRY(hipMemcpyAsync(bl.p, ld, n, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(bd.p, d, n, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(bu.p, ud, n, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(bb.p, b, n, hipMemcpyHostToDevice, cs.st));
-    const double t0 = now_s();
-    if (int rc = trpl_pcr_solve_batched_dev(bl.p, bd.p, bu.p, bb.p, bx.p, S, L, elem_bytes, flags, cs.st)) return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(x, bx.p, n, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
-    return TRPL_OK;
+    const void *bl = sg.in(ld, n), *bd = sg.in(d, n), *bu = sg.in(ud, n), *bb = sg.in(b, n);
+    void *bx = sg.out(x, n);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_pcr_solve_batched_dev(bl, bd, bu, bb, bx, S, L, elem_bytes, flags, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 }  // extern "C"

@@ -756,6 +756,9 @@ int trpl_sample_box_dev(uint32_t seed, int64_t S, int32_t ncol, const double *lo
  * centres the second call about the all-reduced means; histograms and sums add across shards.
  * The _dev forms take device pointers (out must be zeroed by the caller for hist) and a workspace of
  * trpl_posterior_workspace_bytes(D) bytes (D = 1 for the weights); nothing is allocated.
+ * seconds (nullable), here and in every other analysis-side host-buffer call of this header (trpl_sample_box, temperature scan,
+ * predictive band, quantiles, corner, refinement, MCMC, trpl_pcr_solve_batched): the device time of the _dev form, from the inputs having landed on the
+ * device to its last kernel having finished; the copies in and out are not in it.
  * ------------------------------------------------------------------------------------- */
 int64_t trpl_posterior_workspace_bytes(int32_t D);
 int trpl_posterior_weights(const double *LL, int64_t S, double tf, double *W, double *stats /*nullable [2]*/,

@@ -325,3 +325,28 @@ def test_corner_of_no_samples_is_zeros(gpu):
                                    info=info)
     assert out["kept"] == 0 and out["W"].size == 0
     assert not info["h1"].any() and not info["c1"].any() and not info["h2"].any()
+
+
+@pytest.mark.parametrize("S", (1, 257))
+def test_corner_host_form_without_its_optional_outputs(gpu, S):
+    """c1, h2, V, W and kept all NULL, one sample and one block boundary, ldx = 13 + 3 with X ending after its last row's entries:
+    h1 is bit for bit the full call's on the compact X."""
+    A_ = gpu._abi
+    X, LL = cr.draw(5, S)
+    names, bins = ["p0", "taun", "taup"], 8
+    limits = {n: (float(np.min(X[:, cr.NAMES.index(n)])) - 1.0, float(np.max(X[:, cr.NAMES.index(n)])) + 1.0) for n in names}
+    info = {}
+    with np.errstate(divide="ignore", invalid="ignore"):         # one sample: the densities of the empty bins are 0 / 0
+        gpu.posterior.corner(X, LL, names, limits, bin_count=bins, info=info)
+    _, cols, lg = gpu.posterior._corner_codes(names, ())
+    lo = np.array([limits[n][0] for n in names])
+    hi = np.array([limits[n][1] for n in names])
+    ld = X.shape[1] + 3
+    Xr = np.full((S - 1) * ld + A_.CORNER_PRIMARY, np.nan)
+    for s in range(S):
+        Xr[s * ld:s * ld + A_.CORNER_PRIMARY] = X[s, :A_.CORNER_PRIMARY]
+    h1 = np.full((len(names), bins), -7.0)
+    sec = A_.C.c_double(-1.0)
+    A_.check(A_.lib().trpl_corner(A_.ptr(Xr), S, ld, A_.ptr(LL), 1.0, A_.ptr(cols), A_.ptr(lg), len(names), 2000.0, None, None, A_.ptr(lo),
+                                  A_.ptr(hi), bins, None, None, None, A_.ptr(h1), None, None, 0, A_.C.byref(sec)))
+    assert _same_bits(h1, info["h1"]) and h1.sum() > 0.0 and sec.value > 0.0

@@ -118,6 +118,20 @@ def test_propose_against_the_restatement(gpu, torch_dev, A):
     assert 0 < outside < total                                   # both kinds occurred
 
 
+@pytest.mark.parametrize("count", (1, 257))
+def test_propose_host_form_without_partners(gpu, torch_dev, count):
+    """partners NULL with P = 0 through the host-buffer form, one chain and one block boundary: the _dev form's bits."""
+    A, flags = 3, 0
+    rng = np.random.default_rng(count)
+    lo, hi, lg = _box_for(A, flags, rng)
+    U, scale = _states(rng, count, A), rng.uniform(0.01, 0.05, A)
+    info = {}
+    Uh, Xh, ih = gpu.mcmc.propose(U, None, 0.6, scale, 7, 11, 5, lo, hi, lg, info=info)
+    Up, Xp, inside = _propose_dev(torch_dev, U, None, 0.6, scale, 7, 11, 5, lo, hi, lg, flags)
+    assert _same_bits(Uh, Up) and _same_bits(Xh, Xp) and np.array_equal(ih, inside)
+    assert _same_bits(Uh, mr.propose(U, None, 0.6, scale, 7, 11, 5, lo, hi, lg, flags)[0])
+
+
 # ------------------------------------------------------------------ accept
 @pytest.mark.parametrize("count", mr.ACCEPT_COUNTS)
 def test_accept_against_the_restatement(gpu, torch_dev, count):

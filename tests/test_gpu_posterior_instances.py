@@ -133,3 +133,35 @@ def test_hist_2d_on_every_edge_in_every_regime(gpu, xb, yb, S, lo, hi):
     x, y = hp.hist_points(rng, lo, hi, xb, S), hp.hist_points(rng, ylo, yhi, yb, S)
     check_hist(gpu.posterior, x, rng.random(S), lo, hi, xb, y, ylo, yhi, yb,
                label="2-D %d x %d S=%d (%g, %g) x (%g, %g)" % (xb, yb, S, lo, hi, ylo, yhi))
+
+
+# ------------------------------------------------------------------------------------------------ the host-buffer forms' optional pointers
+@pytest.mark.parametrize("S", [1, 257])
+def test_host_forms_without_their_optional_pointers(gpu, S):
+    """stats NULL (weights), mean_in NULL (moments), y and W NULL (hist), one sample and one block boundary: the bits of the calls
+    that pass them; the plain counts exactly numpy's."""
+    A_, po = gpu._abi, gpu.posterior
+    rng = np.random.default_rng(S)
+    LL = -50.0 * rng.random(S)
+    W = np.full(S, -7.0)
+    sec = A_.C.c_double(-1.0)
+    A_.check(A_.lib().trpl_posterior_weights(A_.ptr(LL), S, 10.0, A_.ptr(W), None, 0, A_.C.byref(sec)))
+    assert np.array_equal(W, po.weights(LL, 10.0)) and sec.value > 0.0
+    V = np.ascontiguousarray(rng.normal(size=(4, S)))
+    sums, central = np.full(6, -7.0), np.full((4, 6), -7.0)
+    A_.check(A_.lib().trpl_posterior_moments(A_.ptr(V), S, 4, A_.ptr(W), None, A_.ptr(sums), A_.ptr(central), 0, None))
+    got = po.moments(V, W)
+    assert np.array_equal(sums, got[0]) and np.array_equal(central, got[1])
+    x = np.ascontiguousarray(V[0])
+    out = np.full(8, -7.0)
+    A_.check(A_.lib().trpl_posterior_hist(A_.ptr(x), None, None, S, -1.0, 1.0, 8, 0.0, 1.0, 1, A_.ptr(out), 0, A_.C.byref(sec)))
+    assert np.array_equal(out, np.histogram(x, bins=8, range=(-1.0, 1.0))[0].astype(np.float64)) and sec.value > 0.0
+
+
+def test_weights_of_no_samples_return_at_once(gpu):
+    """S == 0: TRPL_OK, seconds 0, W and stats as they were."""
+    A_ = gpu._abi
+    W, stats = np.full(4, -7.0), np.full(2, -7.0)
+    sec = A_.C.c_double(-1.0)
+    A_.check(A_.lib().trpl_posterior_weights(None, 0, 10.0, A_.ptr(W), A_.ptr(stats), 0, A_.C.byref(sec)))
+    assert sec.value == 0.0 and np.all(W == -7.0) and np.all(stats == -7.0)

@@ -255,6 +255,59 @@ def test_resample_against_longdouble(gpu, torch_dev, name):
         assert np.array_equal(idx, _resample_dev(torch_dev, W, 64, rr.OFFSET)[0]) and info["ess"] > 0
 
 
+# ------------------------------------------------------------------ the host-buffer forms at the edges of their staging
+def _ragged(a, ld):
+    """The rows of `a` at leading dimension ld in a buffer that ENDS with the last row's entries; NaN in the padding."""
+    S, w = a.shape
+    flat = np.full((S - 1) * ld + w, np.nan)
+    for s in range(S):
+        flat[s * ld:s * ld + w] = a[s]
+    return flat
+
+
+@pytest.mark.parametrize("S", (1, 257))
+def test_host_forms_with_a_ragged_last_row_and_no_stats(gpu, torch_dev, S):
+    """One sample and one block boundary (257 = 256 + 1): ld = width + 3 with the buffer ending after the last row's entries, and
+    the optional stats absent.  Bit for bit the restatement (density), the compact call (unit) and the call with stats (resample)."""
+    A_, lib = gpu._abi, gpu._abi.lib()
+    rng = np.random.default_rng(S)
+    A = 3
+    a, b, iv = _parents(rng, 65, A)
+    U = _points(rng, S, A, a, b)
+    Ur, B = _ragged(U, A + 3), np.full(S, -7.0)
+    sec = A_.C.c_double(-1.0)
+    A_.check(lib.trpl_refine_density(A_.ptr(Ur), S, A + 3, A, A_.ptr(a), A_.ptr(b), A_.ptr(iv), 65, A_.ptr(B), 0, A_.C.byref(sec)))
+    assert _same_bits(B, rr.density(U, a, b, iv)) and sec.value > 0.0
+    assert _same_bits(B, _density_dev(torch_dev, U, a, b, iv))
+    lo, hi, lg = _box_for(A, 0, rng)
+    X = rr.from_unit(rng.random((S, A)), lo, hi, lg, 0)
+    want, _ = gpu.refine.unit_coords(X, lo, hi, lg)
+    Xr, got = _ragged(X, lo.size + 3), np.full((S, A), -7.0)
+    A_.check(lib.trpl_refine_unit(A_.ptr(Xr), S, lo.size + 3, lo.size, A_.ptr(lo), A_.ptr(hi), A_.ptr(lg), 0, A, A_.ptr(got), 0, None))
+    assert _same_bits(got, want)
+    W = rr.weight_pattern("decades", S)
+    idx = np.full(64, -7, dtype=np.int64)
+    A_.check(lib.trpl_refine_resample(A_.ptr(W), S, 64, rr.OFFSET, A_.ptr(idx), None, 0, None))
+    assert np.array_equal(idx, gpu.refine.resample(W, 64, rr.OFFSET)[0]) and np.array_equal(idx, _resample_dev(torch_dev, W, 64, rr.OFFSET)[0])
+
+
+def test_host_forms_with_nothing_to_do_return_at_once(gpu):
+    """S == 0 (density, unit) and n_uniform + K m == 0 (draw): TRPL_OK, seconds 0, the outputs as they were."""
+    A_, lib = gpu._abi, gpu._abi.lib()
+    rng = np.random.default_rng(0)
+    A = 3
+    a, b, iv = _parents(rng, 5, A)
+    lo, hi, lg = _box_for(A, 0, rng)
+    out = np.full(8, -7.0)
+    for call in (lambda sec: lib.trpl_refine_density(None, 0, A, A, A_.ptr(a), A_.ptr(b), A_.ptr(iv), 5, A_.ptr(out), 0, sec),
+                 lambda sec: lib.trpl_refine_unit(None, 0, lo.size, lo.size, A_.ptr(lo), A_.ptr(hi), A_.ptr(lg), 0, A, A_.ptr(out), 0, sec),
+                 lambda sec: lib.trpl_refine_draw(A_.ptr(a), A_.ptr(b), 5, A, 0, 0, 1, 2, lo.size, A_.ptr(lo), A_.ptr(hi), A_.ptr(lg), 0,
+                                                  A_.ptr(out), A_.ptr(out), 0, sec)):
+        sec = A_.C.c_double(-1.0)
+        A_.check(call(A_.C.byref(sec)))
+        assert sec.value == 0.0 and np.all(out == -7.0)
+
+
 # ------------------------------------------------------------------ end to end
 TOY_LO, TOY_HI, TOY_LG = np.array([2.0, 1e-3, -1.0]), np.array([5.0, 1e1, 1.0]), np.array([0, 1, 0])
 

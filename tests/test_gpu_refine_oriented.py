@@ -74,6 +74,36 @@ def test_affine_is_the_ascending_loop_bit_for_bit(gpu, torch_dev, A):
     assert _same_bits(Zh[:, :A], ro.affine(Up[:257, :A], M, c)) and np.all(Zh[:, A:] == -7.0)
 
 
+@pytest.mark.parametrize("S", (1, 257))
+def test_affine_host_form_with_padded_rows_on_both_sides(gpu, S):
+    """ldu = ldz = A + 3 through the host-buffer form, one sample and one block boundary: the rows bit for bit, the padding of Z stays."""
+    A = 3
+    rng = np.random.default_rng(S)
+    M, c = _lower(rng, A), rng.random(A)
+    Up = np.full((S, A + 3), np.nan)
+    Up[:, :A] = rng.random((S, A))
+    Zh = np.full((S, A + 3), -7.0)
+    A_ = gpu._abi
+    sec = A_.C.c_double(-1.0)
+    A_.check(A_.lib().trpl_refine_affine(A_.ptr(Up), S, A + 3, A, A_.ptr(M), A_.ptr(c), A_.ptr(Zh), A + 3, 0, A_.C.byref(sec)))
+    assert _same_bits(Zh[:, :A], ro.affine(Up[:, :A], M, c)) and np.all(Zh[:, A:] == -7.0) and sec.value > 0.0
+
+
+def test_oriented_draw_of_no_children_returns_at_once(gpu):
+    """n_uniform + K m == 0: TRPL_OK, seconds 0, the outputs as they were."""
+    A = 3
+    rng = np.random.default_rng(0)
+    lo, hi, lg = _box_for(A, 0, rng)
+    L, M, c, h = _tilted(rng, A)
+    zc = ro.affine(rng.uniform(0.2, 0.8, (5, A)), M, c)
+    out, ins = np.full(8, -7.0), np.full(8, -7, dtype=np.int32)
+    A_ = gpu._abi
+    sec = A_.C.c_double(-1.0)
+    A_.check(A_.lib().trpl_refine_draw_oriented(A_.ptr(zc), A_.ptr(h), A_.ptr(L), A_.ptr(c), 5, A, 0, 0, 1, 2, lo.size, A_.ptr(lo), A_.ptr(hi),
+                                                A_.ptr(lg), 0, A_.ptr(out), A_.ptr(out), A_.ptr(out), A_.ptr(ins), 0, A_.C.byref(sec)))
+    assert sec.value == 0.0 and np.all(out == -7.0) and np.all(ins == -7)
+
+
 # ------------------------------------------------------------------ draw
 def _tilted(rng, A):
     """An orientation tilted against the axes: L with off-diagonal entries of the size of its diagonal, c the cube's centre,
