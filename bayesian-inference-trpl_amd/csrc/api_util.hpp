@@ -1,8 +1,6 @@
-// Host-side helpers shared by every translation unit that implements include/trpl.h: the thread-local error message, RAII
-// for the private streams and stream-ordered allocations of the host-buffer calls (CallScope, DevBuf: the solver and likelihood
-// calls of trpl_api.hip and trpl_multi.hip use them directly), Staged, the staging of the analysis-side host-buffer calls
-// (the posterior / sampler / PCR tail of trpl_api.hip, posterior_scan.hip, predictive.hip, quantiles.hip, corner.hip,
-// refine.hip, refine_oriented.hip, mcmc.hip), argument checks.  Nothing here throws.
+// Host-side helpers shared by every translation unit that implements include/trpl.h: the thread-local error message, Staged, the
+// staging of every single-device host-buffer call, the RAII pieces it is made of (CallScope, DevBuf, HostPin, HostMap; only
+// trpl_multi.hip, which keeps per-device buffers across threads, also uses them directly), argument checks.  Nothing here throws.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -66,26 +64,87 @@ struct DevBuf {                      // RAII device allocation for the host-buff
 
 int select_device(int32_t device);          // hipSetDevice with range check (trpl_api.hip)
 
+// Thresholds (bytes) above which a host-buffer call pins (HostPin) / maps (HostMap) the caller's memory for its duration.
+// Measured with environment overrides in round 2 (profiles/r2_dropin_simulate.txt); constants since round 5: the
+// library reads no process-wide switch but TRPL_RCCL_LIBRARY.
+constexpr long long kHostPinMinBytes = (long long)8 << 20;
+constexpr long long kHostDirectMinBytes = (long long)8 << 20;
+
+// The caller's (pageable) host buffer pinned for the duration of a call, so that copies to and from it are
+// real asynchronous DMA at PCIe rate instead of being staged through the runtime's bounce buffers.  Pinning
+// costs time per page, so only large buffers are worth it; a refused registration (memory that cannot be
+// page-locked) is not an error -- the copy then takes the pageable path.  Memory that is already pinned
+// (hipHostMalloc, or registered by the caller) is left alone.
+// A HostPin / HostMap must outlive the stream's last operation: Staged holds its one before its CallScope.
+struct HostPin {
+    void *p = nullptr;
+    bool pinned = false;
+    static bool already_pinned(const void *ptr)
+    {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, ptr) == hipSuccess) return at.type == hipMemoryTypeHost;
+        (void)hipGetLastError();
+        return false;
+    }
+    void pin(const void *ptr, size_t bytes, unsigned flags = hipHostRegisterDefault)
+    {
+        constexpr long long min_bytes = kHostPinMinBytes;
+        if (!ptr || min_bytes < 0 || bytes < (size_t)min_bytes || already_pinned(ptr)) return;
+        if (hipHostRegister((void *)ptr, bytes, flags) == hipSuccess) { p = (void *)ptr; pinned = true; }
+        else (void)hipGetLastError();            // clear the sticky error of a refused registration
+    }
+    ~HostPin() { if (pinned) (void)hipHostUnregister(p); }
+};
+
+// The caller's host buffer mapped into the device's address space for the duration of a call: a kernel
+// writes its output straight into it across PCIe (no device copy of the matrix, no copy after the kernel).
+struct HostMap {
+    HostPin pin_;
+    // device-visible alias of [ptr, ptr + bytes), or nullptr (too small, refused, switched off)
+    void *map(void *ptr, size_t bytes)
+    {
+        constexpr long long min_bytes = kHostDirectMinBytes;
+        if (!ptr || min_bytes < 0 || bytes < (size_t)min_bytes) return nullptr;
+        if (!HostPin::already_pinned(ptr)) {
+            if (hipHostRegister(ptr, bytes, hipHostRegisterMapped) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+            pin_.p = ptr; pin_.pinned = true;
+        }
+        void *d = nullptr;
+        if (hipHostGetDevicePointer(&d, ptr, 0) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        return d;
+    }
+};
+
 // The staging of a host-buffer call around its device-resident (_dev) form: the call declares its buffers, runs the _dev form on
 // stream() between begin() and finish(), and returns.  Counts are elements of T (bytes for void); every buffer is compact on the
 // device, a pitched one [rows][width] from or to a host leading dimension ld.  The first failed allocation or copy is recorded
 // (api_fail, TRPL_ERR_HIP) and turns every later declaration into a no-op that returns NULL; begin() returns it.
-// seconds is the device time of the _dev form: from the uploads having landed to its last kernel having finished.
-// Members are destroyed last to first: the buffers are released (hipFreeAsync), then the scope drains and destroys the stream.
+// seconds is the device time of the _dev form: from the uploads having landed to its last kernel having finished; a call that
+// times its uploads too (open(device, true)) starts the clock once the stream exists.
+// Members are destroyed last to first: the buffers are released (hipFreeAsync), then the scope drains and destroys the stream,
+// then the caller's memory is unpinned.
 struct Staged {
-    static constexpr int kMaxBufs = 12;      // the largest user, trpl_corner, declares 11
+    static constexpr int kMaxBufs = 13;      // the largest user, trpl_loglik_weighted off the grid, declares 13
+    HostMap hm;                              // the one buffer of the caller's that pin() or map() holds for the call
     CallScope cs;
     DevBuf buf[kMaxBufs];
     struct Back { void *host; const void *dev; size_t ld, width, rows; } back[kMaxBufs];      // in bytes
     int nbuf = 0, nback = 0, rc = TRPL_OK;
     double t0 = 0.0;
+    bool timing = false;
 
-    int open(int32_t device)
+    int open(int32_t device, bool clock_from_here = false)
     {
         if (int r = select_device(device)) return r;
-        return ok(cs.open(), "hipStreamCreateWithFlags");
+        if (ok(cs.open(), "hipStreamCreateWithFlags")) return rc;
+        if (clock_from_here) { t0 = now_s(); timing = true; }
+        return TRPL_OK;
     }
     hipStream_t stream() const { return cs.st; }
+    // The caller's buffer pinned for the copies (HostPin's rules: large and not yet pinned), or mapped for a kernel to write through
+    // (HostMap: its device alias, or NULL).  Only on request: in / out / inout never pin.
+    void pin(const void *ptr, size_t bytes) { hm.pin_.pin(ptr, bytes); }
+    void *map(void *ptr, size_t bytes) { return hm.map(ptr, bytes); }
 
     int ok(hipError_t e, const char *what)
     {
@@ -125,12 +184,16 @@ struct Staged {
         return (T *)down(scratch(width * elem<T>() * rows), host, ld * elem<T>(), width * elem<T>(), rows);
     }
     template <typename T> T *inout(T *host, size_t n) { return (T *)down(up(host, 0, n * elem<T>(), 1), host, 0, n * elem<T>(), 1); }
+    template <typename T> T *inout(T *host, size_t ld, size_t width, size_t rows)
+    {
+        return (T *)down(up(host, ld * elem<T>(), width * elem<T>(), rows), host, ld * elem<T>(), width * elem<T>(), rows);
+    }
 
-    // the first recorded error, else: the uploads have landed, the clock starts
+    // the first recorded error, else: the uploads have landed, the clock starts unless open() started it
     int begin()
     {
         if (ok(hipStreamSynchronize(cs.st), "hipStreamSynchronize (uploads)")) return rc;
-        t0 = now_s();
+        if (!timing) t0 = now_s();
         return TRPL_OK;
     }
     // the _dev form has finished (*seconds), the outputs are copied back and have landed
@@ -150,57 +213,6 @@ private:
     template <typename T> static constexpr size_t elem()
     {
         if constexpr (std::is_void_v<T>) return 1; else return sizeof(T);
-    }
-};
-
-// Thresholds (bytes) above which a host-buffer call pins (HostPin) / maps (HostMap) the caller's memory for its duration.
-// Measured with environment overrides in round 2 (profiles/r2_dropin_simulate.txt); constants since round 5: the
-// library reads no process-wide switch but TRPL_RCCL_LIBRARY.
-constexpr long long kHostPinMinBytes = (long long)8 << 20;
-constexpr long long kHostDirectMinBytes = (long long)8 << 20;
-
-// The caller's (pageable) host buffer pinned for the duration of a call, so that copies to and from it are
-// real asynchronous DMA at PCIe rate instead of being staged through the runtime's bounce buffers.  Pinning
-// costs time per page, so only large buffers are worth it; a refused registration (memory that cannot be
-// page-locked) is not an error -- the copy then takes the pageable path.  Memory that is already pinned
-// (hipHostMalloc, or registered by the caller) is left alone.
-// Declare a HostPin / HostMap BEFORE the call's CallScope: it must outlive the stream's last operation.
-struct HostPin {
-    void *p = nullptr;
-    bool pinned = false;
-    static bool already_pinned(const void *ptr)
-    {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, ptr) == hipSuccess) return at.type == hipMemoryTypeHost;
-        (void)hipGetLastError();
-        return false;
-    }
-    void pin(const void *ptr, size_t bytes, unsigned flags = hipHostRegisterDefault)
-    {
-        constexpr long long min_bytes = kHostPinMinBytes;
-        if (!ptr || min_bytes < 0 || bytes < (size_t)min_bytes || already_pinned(ptr)) return;
-        if (hipHostRegister((void *)ptr, bytes, flags) == hipSuccess) { p = (void *)ptr; pinned = true; }
-        else (void)hipGetLastError();            // clear the sticky error of a refused registration
-    }
-    ~HostPin() { if (pinned) (void)hipHostUnregister(p); }
-};
-
-// The caller's host buffer mapped into the device's address space for the duration of a call: a kernel
-// writes its output straight into it across PCIe (no device copy of the matrix, no copy after the kernel).
-struct HostMap {
-    HostPin pin_;
-    // device-visible alias of [ptr, ptr + bytes), or nullptr (too small, refused, switched off)
-    void *map(void *ptr, size_t bytes)
-    {
-        constexpr long long min_bytes = kHostDirectMinBytes;
-        if (!ptr || min_bytes < 0 || bytes < (size_t)min_bytes) return nullptr;
-        if (!HostPin::already_pinned(ptr)) {
-            if (hipHostRegister(ptr, bytes, hipHostRegisterMapped) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            pin_.p = ptr; pin_.pinned = true;
-        }
-        void *d = nullptr;
-        if (hipHostGetDevicePointer(&d, ptr, 0) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        return d;
     }
 };
 

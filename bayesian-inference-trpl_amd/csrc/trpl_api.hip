@@ -477,6 +477,14 @@ int trpl_device_count(void)
 }
 
 /* ------------------------------------------------------------------ solve_pl ------------ */
+// what both forms check alike; the rest of the head runs in each form's own order, as it always has
+static int check_solve_counts(int64_t S, int32_t n_snap)
+{
+    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
+    if (n_snap < 0 || n_snap > trpl::kMaxSnaps) return api_fail(TRPL_ERR_ARG, "n_snap=%d must be in [0, %d]", n_snap, trpl::kMaxSnaps);
+    return TRPL_OK;
+}
+
 static int solve_pl_dev_impl(const double *matpar, int64_t S, double length_nm, double time_ns, int32_t L, int64_t T,
                              int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN, int64_t t0,
                              const double *resN, const double *resP, const double *resE, void *plI,
@@ -487,8 +495,7 @@ static int solve_pl_dev_impl(const double *matpar, int64_t S, double length_nm, 
     const bool resume = resN || resP || resE;
     if (int rc = no_moments_flag(flags)) return rc;
     if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
-    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
-    if (n_snap < 0 || n_snap > trpl::kMaxSnaps) return api_fail(TRPL_ERR_ARG, "n_snap=%d must be in [0, %d]", n_snap, trpl::kMaxSnaps);
+    if (int rc = check_solve_counts(S, n_snap)) return rc;
     if (n_snap > 0 && !snap_steps) return api_fail(TRPL_ERR_ARG, "snap_steps must not be NULL when n_snap > 0");
     if (resume && !(resN && resP && resE)) return api_fail(TRPL_ERR_ARG, "resN, resP and resE go together");
     if (resume && (t0 < 4 || t0 > T)) return api_fail(TRPL_ERR_ARG, "t0=%lld must be in [4, T]: a resume needs five BDF levels", (long long)t0);
@@ -570,65 +577,39 @@ static int solve_pl_host_impl(const double *matpar, int64_t S, double length_nm,
     if (resume && !(resN && resP && resE)) return api_fail(TRPL_ERR_ARG, "resN, resP and resE go together");
     if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
     if (pl_elem_bytes != 4 && pl_elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "pl_elem_bytes must be 4 or 8");
-    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
-    if (n_snap < 0 || n_snap > trpl::kMaxSnaps) return api_fail(TRPL_ERR_ARG, "n_snap=%d must be in [0, %d]", n_snap, trpl::kMaxSnaps);
+    if (int rc = check_solve_counts(S, n_snap)) return rc;
     if (seconds) *seconds = 0.0;
     if (S == 0) return TRPL_OK;
     if (!matpar || (!dN && !resume) || !plI) return api_fail(TRPL_ERR_ARG, "matpar, dN and plI must not be NULL");
     const int64_t ncol = T / plT + 1;
     if (pl_ld < ncol) return api_fail(TRPL_ERR_ARG, "pl_ld=%lld < T/plT+1", (long long)pl_ld);
-    if (int rc = select_device(device)) return rc;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
     // A large PL matrix is written by the kernel STRAIGHT INTO the caller's buffer (pinned and mapped for
     // the duration of the call): the stores cross PCIe while the time-stepping goes on (a 1024 x 80 001 fp32
     // block is 328 MB over a ~0.3 s kernel, ~1 GB/s), so there is no device copy of the matrix and no
-    // device-to-host copy after the kernel.  Small or unmappable buffers are staged through device memory.
-    HostMap map;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    const size_t span = ((size_t)(S - 1) * pl_ld + ncol) * pl_elem_bytes;
-    void *pl_direct = map.map(plI, span);
-    DevBuf dm, dn, dp, ds, di, sN, sP, sE, rN, rP, rE;
-    HIP_TRY(dm.alloc((size_t)S * 12 * 8, cs.st));
-    HIP_TRY(dn.alloc((size_t)L * 8, cs.st));
-    if (resume) {                                    // the five BDF levels of every system, solver units
-        const size_t bNP = (size_t)S * 5 * L * 8, bE = (size_t)S * 5 * (L + 1) * 8;
-        HIP_TRY(rN.alloc(bNP, cs.st)); HIP_TRY(rP.alloc(bNP, cs.st)); HIP_TRY(rE.alloc(bE, cs.st));
-        HIP_TRY(hipMemcpyAsync(rN.p, resN, bNP, hipMemcpyHostToDevice, cs.st));
-        HIP_TRY(hipMemcpyAsync(rP.p, resP, bNP, hipMemcpyHostToDevice, cs.st));
-        HIP_TRY(hipMemcpyAsync(rE.p, resE, bE, hipMemcpyHostToDevice, cs.st));
-    }
-    if (!pl_direct) HIP_TRY(dp.alloc((size_t)S * ncol * pl_elem_bytes, cs.st));
-    HIP_TRY(ds.alloc((size_t)S * 4, cs.st));
-    HIP_TRY(di.alloc((size_t)S * 8, cs.st));
-    HIP_TRY(hipMemcpyAsync(dm.p, matpar, (size_t)S * 12 * 8, hipMemcpyHostToDevice, cs.st));
-    if (dN) HIP_TRY(hipMemcpyAsync(dn.p, dN, (size_t)L * 8, hipMemcpyHostToDevice, cs.st));
-    if (resume && !pl_direct)                        // the staged PL matrix starts as the caller's: columns before t0 are kept
-        HIP_TRY(hipMemcpy2DAsync(dp.p, (size_t)ncol * pl_elem_bytes, plI, (size_t)pl_ld * pl_elem_bytes,
-                                 (size_t)ncol * pl_elem_bytes, (size_t)S, hipMemcpyHostToDevice, cs.st));
+    // device-to-host copy after the kernel.  Small or unmappable buffers are staged through device memory:
+    // on a resume as a copy of the caller's matrix, because columns before t0 are kept.
+    const size_t eb = (size_t)pl_elem_bytes;
+    void *dpl = sg.map(plI, ((size_t)(S - 1) * pl_ld + ncol) * eb);
+    const int64_t dpl_ld = dpl ? pl_ld : ncol;
+    if (!dpl) dpl = resume ? sg.inout(plI, pl_ld * eb, ncol * eb, (size_t)S) : sg.out(plI, pl_ld * eb, ncol * eb, (size_t)S);
+    const double *dm = sg.in(matpar, (size_t)S * 12), *dn = sg.in(dN, (size_t)L);
+    // the five BDF levels of every system, solver units
+    const size_t rNP = (size_t)S * 5 * L, rE = (size_t)S * 5 * (L + 1);
+    const double *rN = resume ? sg.in(resN, rNP) : nullptr, *rP = resume ? sg.in(resP, rNP) : nullptr;
+    const double *rEd = resume ? sg.in(resE, rE) : nullptr;
+    int32_t *ds = sg.out(status, (size_t)S);
+    int64_t *di = sg.out(iters_total, (size_t)S);
     // snapshot buffers start as copies of the caller's (pvSimPCR.py:366-368): unfilled slots keep their contents
-    const size_t nNP = (size_t)S * n_snap * L * 8, nE = (size_t)S * n_snap * (L + 1) * 8;
-    if (n_snap > 0 && plN) { HIP_TRY(sN.alloc(nNP, cs.st)); HIP_TRY(hipMemcpyAsync(sN.p, plN, nNP, hipMemcpyHostToDevice, cs.st)); }
-    if (n_snap > 0 && plP) { HIP_TRY(sP.alloc(nNP, cs.st)); HIP_TRY(hipMemcpyAsync(sP.p, plP, nNP, hipMemcpyHostToDevice, cs.st)); }
-    if (n_snap > 0 && plE) { HIP_TRY(sE.alloc(nE, cs.st)); HIP_TRY(hipMemcpyAsync(sE.p, plE, nE, hipMemcpyHostToDevice, cs.st)); }
-    const double tic = now_s();
-    if (int rc = solve_pl_dev_impl(dm.as<double>(), S, length_nm, time_ns, L, T, plT, tol_exp, max_iter,
-                                   dn.as<double>(), t0, rN.as<double>(), rP.as<double>(), rE.as<double>(),
-                                   pl_direct ? pl_direct : dp.p, pl_elem_bytes, pl_direct ? pl_ld : ncol,
-                                   ds.as<int32_t>(), di.as<int64_t>(), snap_steps, n_snap, sN.as<double>(), sP.as<double>(),
-                                   sE.as<double>(), flags, cs.st))
+    const size_t nNP = (size_t)S * n_snap * L, nE = (size_t)S * n_snap * (L + 1);
+    double *sN = n_snap > 0 && plN ? sg.inout(plN, nNP) : nullptr, *sP = n_snap > 0 && plP ? sg.inout(plP, nNP) : nullptr;
+    double *sE = n_snap > 0 && plE ? sg.inout(plE, nE) : nullptr;
+    if (int rc = sg.begin()) return rc;
+    if (int rc = solve_pl_dev_impl(dm, S, length_nm, time_ns, L, T, plT, tol_exp, max_iter, dn, t0, rN, rP, rEd, dpl, pl_elem_bytes,
+                                   dpl_ld, ds, di, snap_steps, n_snap, sN, sP, sE, flags, sg.stream()))
         return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - tic;                      /* pvSimPCR.py:378-381 */
-    if (!pl_direct)
-        HIP_TRY(hipMemcpy2DAsync(plI, (size_t)pl_ld * pl_elem_bytes, dp.p, (size_t)ncol * pl_elem_bytes,
-                                 (size_t)ncol * pl_elem_bytes, (size_t)S, hipMemcpyDeviceToHost, cs.st));
-    if (status) HIP_TRY(hipMemcpyAsync(status, ds.p, (size_t)S * 4, hipMemcpyDeviceToHost, cs.st));
-    if (iters_total) HIP_TRY(hipMemcpyAsync(iters_total, di.p, (size_t)S * 8, hipMemcpyDeviceToHost, cs.st));
-    if (sN.p) HIP_TRY(hipMemcpyAsync(plN, sN.p, nNP, hipMemcpyDeviceToHost, cs.st));
-    if (sP.p) HIP_TRY(hipMemcpyAsync(plP, sP.p, nNP, hipMemcpyDeviceToHost, cs.st));
-    if (sE.p) HIP_TRY(hipMemcpyAsync(plE, sE.p, nE, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
-    return TRPL_OK;
+    return sg.finish(seconds);                                  /* pvSimPCR.py:378-381 */
 }
 
 int trpl_solve_pl_snap(const double *matpar, int64_t S, double length_nm, double time_ns, int32_t L, int64_t T,
@@ -667,14 +648,24 @@ int trpl_solve_pl(const double *matpar, int64_t S, double length_nm, double time
 }
 
 /* ------------------------------------------------------------------ log10 clamp --------- */
+// both forms: the host form's message names no numbers; its seconds are zeroed once the shape is accepted
+static int check_log10_clamp(const void *x, int32_t elem_bytes, int64_t rows, int64_t cols, int64_t ld, bool numbers, double *seconds)
+{
+    if (elem_bytes != 4 && elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "elem_bytes must be 4 or 8");
+    if (rows < 0 || cols < 0 || ld < cols)
+        return numbers ? api_fail(TRPL_ERR_ARG, "bad shape rows=%lld cols=%lld ld=%lld", (long long)rows, (long long)cols, (long long)ld)
+                       : api_fail(TRPL_ERR_ARG, "bad shape");
+    if (seconds) *seconds = 0.0;
+    if (rows == 0 || cols == 0) return TRPL_OK;
+    if (!x) return api_fail(TRPL_ERR_ARG, "x must not be NULL");
+    return TRPL_OK;
+}
+
 int trpl_log10_clamp_dev(void *x, int32_t elem_bytes, int64_t rows, int64_t cols, int64_t ld, double min,
                          void *stream)
 {
-    if (elem_bytes != 4 && elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "elem_bytes must be 4 or 8");
-    if (rows < 0 || cols < 0 || ld < cols) return api_fail(TRPL_ERR_ARG, "bad shape rows=%lld cols=%lld ld=%lld",
-                                                       (long long)rows, (long long)cols, (long long)ld);
+    if (int rc = check_log10_clamp(x, elem_bytes, rows, cols, ld, true, nullptr)) return rc;
     if (rows == 0 || cols == 0) return TRPL_OK;
-    if (!x) return api_fail(TRPL_ERR_ARG, "x must not be NULL");
     hipError_t e = trpl::launch_log10_clamp(x, elem_bytes, rows, cols, ld, min, (hipStream_t)stream);
     if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "log10_clamp launch: %s", hipGetErrorString(e));
     return TRPL_OK;
@@ -684,90 +675,77 @@ int trpl_log10_clamp(void *x, int32_t elem_bytes, int64_t rows, int64_t cols, in
                      int32_t device, double *seconds)
 {
     ProfRange range("trpl_log10_clamp (fastlog)");
-    if (elem_bytes != 4 && elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "elem_bytes must be 4 or 8");
-    if (rows < 0 || cols < 0 || ld < cols) return api_fail(TRPL_ERR_ARG, "bad shape");
-    if (seconds) *seconds = 0.0;
+    if (int rc = check_log10_clamp(x, elem_bytes, rows, cols, ld, false, seconds)) return rc;
     if (rows == 0 || cols == 0) return TRPL_OK;
-    if (!x) return api_fail(TRPL_ERR_ARG, "x must not be NULL");
-    if (int rc = select_device(device)) return rc;
-    HostPin pin;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    const double t0 = now_s();                                   /* probs.py:79: includes the copies */
-    DevBuf dx;
-    const size_t rowb = (size_t)cols * elem_bytes;
-    pin.pin(x, ((size_t)(rows - 1) * ld + cols) * elem_bytes);
-    HIP_TRY(dx.alloc(rowb * rows, cs.st));
-    HIP_TRY(hipMemcpy2DAsync(dx.p, rowb, x, (size_t)ld * elem_bytes, rowb, (size_t)rows, hipMemcpyHostToDevice, cs.st));
-    if (int rc = trpl_log10_clamp_dev(dx.p, elem_bytes, rows, cols, cols, min, cs.st)) return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    HIP_TRY(hipMemcpy2DAsync(x, (size_t)ld * elem_bytes, dx.p, rowb, rowb, (size_t)rows, hipMemcpyDeviceToHost, cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
-    return TRPL_OK;
+    Staged sg;
+    if (int rc = sg.open(device, true)) return rc;               /* probs.py:79: the clock includes the copy in */
+    const size_t eb = (size_t)elem_bytes;
+    sg.pin(x, ((size_t)(rows - 1) * ld + cols) * eb);
+    void *dx = sg.inout(x, ld * eb, cols * eb, (size_t)rows);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_log10_clamp_dev(dx, elem_bytes, rows, cols, cols, min, sg.stream())) return rc;
+    return sg.finish(seconds);
 }
 
 /* ------------------------------------------------------------------ sse accumulate ------ */
-int trpl_sse_accumulate_dev(double *P, const void *plI, int32_t elem_bytes, int64_t rows, int64_t n_obs,
-                            int64_t ld, const double *values, const double *mag, void *stream)
+// all four forms (weighted: trpl_sse_accumulate_w[_dev], probs.py:40); the host forms' seconds are zeroed once the shape is accepted
+static int check_sse_accumulate(const double *P, const void *plI, int32_t elem_bytes, int64_t rows, int64_t n_obs, int64_t ld,
+                                const double *values, const double *wts, bool weighted, const double *mag, double *seconds)
 {
     if (elem_bytes != 4 && elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "elem_bytes must be 4 or 8");
     if (rows < 0 || n_obs < 0 || ld < n_obs) return api_fail(TRPL_ERR_ARG, "bad shape");
+    if (seconds) *seconds = 0.0;
     if (rows == 0) return TRPL_OK;
-    if (!P || !mag || (n_obs && (!plI || !values))) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
+    if (!P || !mag || (n_obs && (!plI || !values || (weighted && !wts)))) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
+    return TRPL_OK;
+}
+
+int trpl_sse_accumulate_dev(double *P, const void *plI, int32_t elem_bytes, int64_t rows, int64_t n_obs,
+                            int64_t ld, const double *values, const double *mag, void *stream)
+{
+    if (int rc = check_sse_accumulate(P, plI, elem_bytes, rows, n_obs, ld, values, nullptr, false, mag, nullptr)) return rc;
+    if (rows == 0) return TRPL_OK;
     hipError_t e = trpl::launch_sse_accumulate(P, plI, elem_bytes, rows, n_obs, ld, values, mag, (hipStream_t)stream);
     if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "sse_accumulate launch: %s", hipGetErrorString(e));
     return TRPL_OK;
+}
+
+int trpl_sse_accumulate_w_dev(double *P, const void *plI, int32_t elem_bytes, int64_t rows, int64_t n_obs, int64_t ld,
+                              const double *values, const double *wts, const double *mag, void *stream)
+{
+    if (int rc = check_sse_accumulate(P, plI, elem_bytes, rows, n_obs, ld, values, wts, true, mag, nullptr)) return rc;
+    if (rows == 0) return TRPL_OK;
+    hipError_t e = trpl::launch_sse_accumulate_w(P, plI, elem_bytes, rows, n_obs, ld, values, wts, mag, (hipStream_t)stream);
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "sse_accumulate_w launch: %s", hipGetErrorString(e));
+    return TRPL_OK;
+}
+
+// the host-buffer form of both, the arguments checked, rows > 0
+static int sse_accumulate_staged(double *P, const void *plI, int32_t elem_bytes, int64_t rows, int64_t n_obs, int64_t ld,
+                                 const double *values, const double *wts, bool weighted, const double *mag, int32_t device,
+                                 double *seconds)
+{
+    Staged sg;
+    if (int rc = sg.open(device, true)) return rc;               /* probs.py:51: the clock includes the copies in */
+    const size_t eb = (size_t)elem_bytes;
+    if (n_obs) sg.pin(plI, ((size_t)(rows - 1) * ld + n_obs) * eb);
+    double *dP = sg.inout(P, (size_t)rows);
+    const void *dpl = sg.in(plI, ld * eb, n_obs * eb, (size_t)rows);
+    const double *dv = sg.in(values, (size_t)n_obs), *dw = weighted ? sg.in(wts, (size_t)n_obs) : nullptr, *dm = sg.in(mag, (size_t)rows);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = weighted ? trpl_sse_accumulate_w_dev(dP, dpl, elem_bytes, rows, n_obs, n_obs, dv, dw, dm, sg.stream())
+                          : trpl_sse_accumulate_dev(dP, dpl, elem_bytes, rows, n_obs, n_obs, dv, dm, sg.stream()))
+        return rc;
+    return sg.finish(seconds);
 }
 
 int trpl_sse_accumulate(double *P, const void *plI, int32_t elem_bytes, int64_t rows, int64_t n_obs, int64_t ld,
                         const double *values, const double *mag, int32_t device, double *seconds)
 {
     ProfRange range("trpl_sse_accumulate (prob)");
-    if (elem_bytes != 4 && elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "elem_bytes must be 4 or 8");
-    if (rows < 0 || n_obs < 0 || ld < n_obs) return api_fail(TRPL_ERR_ARG, "bad shape");
-    if (seconds) *seconds = 0.0;
+    if (int rc = check_sse_accumulate(P, plI, elem_bytes, rows, n_obs, ld, values, nullptr, false, mag, seconds)) return rc;
     if (rows == 0) return TRPL_OK;
-    if (!P || !mag || (n_obs && (!plI || !values))) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
-    if (int rc = select_device(device)) return rc;
-    HostPin pin;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    const double t0 = now_s();                                   /* probs.py:51 */
-    DevBuf dP, dpl, dv, dm;
-    const size_t rowb = (size_t)n_obs * elem_bytes;
-    if (n_obs) pin.pin(plI, ((size_t)(rows - 1) * ld + n_obs) * elem_bytes);
-    HIP_TRY(dP.alloc((size_t)rows * 8, cs.st));
-    HIP_TRY(dpl.alloc(rowb * rows, cs.st));
-    HIP_TRY(dv.alloc((size_t)n_obs * 8, cs.st));
-    HIP_TRY(dm.alloc((size_t)rows * 8, cs.st));
-    HIP_TRY(hipMemcpyAsync(dP.p, P, (size_t)rows * 8, hipMemcpyHostToDevice, cs.st));
-    if (n_obs) {
-        HIP_TRY(hipMemcpy2DAsync(dpl.p, rowb, plI, (size_t)ld * elem_bytes, rowb, (size_t)rows, hipMemcpyHostToDevice, cs.st));
-        HIP_TRY(hipMemcpyAsync(dv.p, values, (size_t)n_obs * 8, hipMemcpyHostToDevice, cs.st));
-    }
-    HIP_TRY(hipMemcpyAsync(dm.p, mag, (size_t)rows * 8, hipMemcpyHostToDevice, cs.st));
-    if (int rc = trpl_sse_accumulate_dev(dP.as<double>(), dpl.p, elem_bytes, rows, n_obs, n_obs, dv.as<double>(),
-                                         dm.as<double>(), cs.st))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    HIP_TRY(hipMemcpyAsync(P, dP.p, (size_t)rows * 8, hipMemcpyDeviceToHost, cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
-    return TRPL_OK;
-}
-
-/* ------------------------------------------------------------------ weighted sse accumulate (probs.py:40) */
-int trpl_sse_accumulate_w_dev(double *P, const void *plI, int32_t elem_bytes, int64_t rows, int64_t n_obs, int64_t ld,
-                              const double *values, const double *wts, const double *mag, void *stream)
-{
-    if (elem_bytes != 4 && elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "elem_bytes must be 4 or 8");
-    if (rows < 0 || n_obs < 0 || ld < n_obs) return api_fail(TRPL_ERR_ARG, "bad shape");
-    if (rows == 0) return TRPL_OK;
-    if (!P || !mag || (n_obs && (!plI || !values || !wts))) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
-    hipError_t e = trpl::launch_sse_accumulate_w(P, plI, elem_bytes, rows, n_obs, ld, values, wts, mag, (hipStream_t)stream);
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "sse_accumulate_w launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    return sse_accumulate_staged(P, plI, elem_bytes, rows, n_obs, ld, values, nullptr, false, mag, device, seconds);
 }
 
 // the weights of one curve, host data: finite and >= 0
@@ -783,40 +761,10 @@ int trpl_sse_accumulate_w(double *P, const void *plI, int32_t elem_bytes, int64_
                           const double *values, const double *wts, const double *mag, int32_t device, double *seconds)
 {
     ProfRange range("trpl_sse_accumulate_w (prob, uncertainty-weighted)");
-    if (elem_bytes != 4 && elem_bytes != 8) return api_fail(TRPL_ERR_ARG, "elem_bytes must be 4 or 8");
-    if (rows < 0 || n_obs < 0 || ld < n_obs) return api_fail(TRPL_ERR_ARG, "bad shape");
-    if (seconds) *seconds = 0.0;
+    if (int rc = check_sse_accumulate(P, plI, elem_bytes, rows, n_obs, ld, values, wts, true, mag, seconds)) return rc;
     if (rows == 0) return TRPL_OK;
-    if (!P || !mag || (n_obs && (!plI || !values || !wts))) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
     if (int rc = check_weights(wts, n_obs, 0)) return rc;
-    if (int rc = select_device(device)) return rc;
-    HostPin pin;
-    CallScope cs;
-    HIP_TRY(cs.open());
-    const double t0 = now_s();
-    DevBuf dP, dpl, dv, dw, dm;
-    const size_t rowb = (size_t)n_obs * elem_bytes;
-    if (n_obs) pin.pin(plI, ((size_t)(rows - 1) * ld + n_obs) * elem_bytes);
-    HIP_TRY(dP.alloc((size_t)rows * 8, cs.st));
-    HIP_TRY(dpl.alloc(rowb * rows, cs.st));
-    HIP_TRY(dv.alloc((size_t)n_obs * 8, cs.st));
-    HIP_TRY(dw.alloc((size_t)n_obs * 8, cs.st));
-    HIP_TRY(dm.alloc((size_t)rows * 8, cs.st));
-    HIP_TRY(hipMemcpyAsync(dP.p, P, (size_t)rows * 8, hipMemcpyHostToDevice, cs.st));
-    if (n_obs) {
-        HIP_TRY(hipMemcpy2DAsync(dpl.p, rowb, plI, (size_t)ld * elem_bytes, rowb, (size_t)rows, hipMemcpyHostToDevice, cs.st));
-        HIP_TRY(hipMemcpyAsync(dv.p, values, (size_t)n_obs * 8, hipMemcpyHostToDevice, cs.st));
-        HIP_TRY(hipMemcpyAsync(dw.p, wts, (size_t)n_obs * 8, hipMemcpyHostToDevice, cs.st));
-    }
-    HIP_TRY(hipMemcpyAsync(dm.p, mag, (size_t)rows * 8, hipMemcpyHostToDevice, cs.st));
-    if (int rc = trpl_sse_accumulate_w_dev(dP.as<double>(), dpl.p, elem_bytes, rows, n_obs, n_obs, dv.as<double>(),
-                                           dw.as<double>(), dm.as<double>(), cs.st))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    HIP_TRY(hipMemcpyAsync(P, dP.p, (size_t)rows * 8, hipMemcpyDeviceToHost, cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
-    return TRPL_OK;
+    return sse_accumulate_staged(P, plI, elem_bytes, rows, n_obs, ld, values, wts, true, mag, device, seconds);
 }
 
 /* ------------------------------------------------------------------ loglik from stored PL */
@@ -869,6 +817,15 @@ int trpl_loglik_weighted_from_pl_dev(const void *plI, int32_t elem_bytes, int64_
 }
 
 /* ------------------------------------------------------------------ fused loglik -------- */
+// the three bracket arrays of an off-grid call: all or none, and on every time step
+static int check_interp(const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int32_t plT)
+{
+    const bool interp = obs_hi || obs_dx || obs_h;
+    if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
+    if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
+    return TRPL_OK;
+}
+
 // Which of the two flags the entry points set themselves a call may carry: wts -- the weighted entry points (they set
 // TRPL_FLAG_WEIGHTED; with TRPL_FLAG_MOMENTS: refused, the weighted sink already emits both sums); esum alone -- the moments entry
 // points (they set TRPL_FLAG_MOMENTS); every other caller must carry neither.
@@ -908,9 +865,8 @@ static int loglik_dev_impl(const double *X, int64_t S, int32_t C, const double *
     if (C < 1 || C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAX_CURVES);
     if (S == 0) return TRPL_OK;
     if (!X || !lengths_nm || !dN || !obs || !n_obs || !P || !sse) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
-    const bool interp = obs_hi || obs_dx || obs_h;
-    if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
-    if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
+    if (int rc = check_interp(obs_hi, obs_dx, obs_h, plT)) return rc;
+    const bool interp = obs_hi != nullptr;
     const int64_t ncol = T / plT + 1;
     for (int c = 0; c < C; c++) {
         if (!(lengths_nm[c] > 0)) return api_fail(TRPL_ERR_ARG, "lengths_nm[%d] must be > 0", c);
@@ -991,55 +947,27 @@ static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double 
     if (S == 0) return TRPL_OK;
     if (!X || !lengths_nm || !dN || !obs || !n_obs || !P) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
     if (obs_ld < 1) return api_fail(TRPL_ERR_ARG, "obs_ld must be >= 1");
-    if (int rc = select_device(device)) return rc;
-    CallScope cs;
-    HIP_TRY(cs.open());
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
     const bool interp = obs_hi != nullptr;
     if (interp) {                                    // the brackets are host data here: validate them
         if (int rc = check_brackets(obs_hi, obs_dx, obs_h, C, obs_ld, n_obs, T)) return rc;
     }
-    DevBuf dX, ddN, dobs, dhi, ddx, dh, dP, dsse, dst, dit, dfl, des, dwt, dcc;
+    // sse, status and iters_total are the _dev form's whether the caller takes them or not; floor_col, esum and cut_col only on request
     const size_t nsys = (size_t)S * C, nobs = (size_t)C * obs_ld;
-    HIP_TRY(dX.alloc((size_t)S * 13 * 8, cs.st));
-    HIP_TRY(ddN.alloc((size_t)C * L * 8, cs.st));
-    HIP_TRY(dobs.alloc(nobs * 8, cs.st));
-    HIP_TRY(dP.alloc((size_t)S * 8, cs.st));
-    HIP_TRY(dsse.alloc(nsys * 8, cs.st));
-    HIP_TRY(dst.alloc(nsys * 4, cs.st));
-    HIP_TRY(dit.alloc(nsys * 8, cs.st));
-    if (floor_col) HIP_TRY(dfl.alloc(nsys * 4, cs.st));
-    if (esum) HIP_TRY(des.alloc(nsys * 8, cs.st));
-    if (cut_col) HIP_TRY(dcc.alloc(nsys * 4, cs.st));
-    if (wts) { HIP_TRY(dwt.alloc(nobs * 8, cs.st)); HIP_TRY(hipMemcpyAsync(dwt.p, wts, nobs * 8, hipMemcpyHostToDevice, cs.st)); }
-    HIP_TRY(hipMemcpyAsync(dX.p, X, (size_t)S * 13 * 8, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(ddN.p, dN, (size_t)C * L * 8, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dobs.p, obs, nobs * 8, hipMemcpyHostToDevice, cs.st));
-    HIP_TRY(hipMemcpyAsync(dP.p, P, (size_t)S * 8, hipMemcpyHostToDevice, cs.st));
-    if (interp) {
-        HIP_TRY(dhi.alloc(nobs * 4, cs.st)); HIP_TRY(ddx.alloc(nobs * 8, cs.st)); HIP_TRY(dh.alloc(nobs * 8, cs.st));
-        HIP_TRY(hipMemcpyAsync(dhi.p, obs_hi, nobs * 4, hipMemcpyHostToDevice, cs.st));
-        HIP_TRY(hipMemcpyAsync(ddx.p, obs_dx, nobs * 8, hipMemcpyHostToDevice, cs.st));
-        HIP_TRY(hipMemcpyAsync(dh.p, obs_h, nobs * 8, hipMemcpyHostToDevice, cs.st));
-    }
-    const double t0 = now_s();
-    if (int rc = loglik_dev_impl(dX.as<double>(), S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter,
-                                 ddN.as<double>(), dobs.as<double>(), interp ? dhi.as<int32_t>() : nullptr,
-                                 interp ? ddx.as<double>() : nullptr, interp ? dh.as<double>() : nullptr, obs_ld, n_obs,
-                                 dP.as<double>(), dsse.as<double>(), dst.as<int32_t>(), dit.as<int64_t>(),
-                                 dfl.as<int32_t>(), flags, cs.st, esum ? des.as<double>() : nullptr,
-                                 wts ? dwt.as<double>() : nullptr, sse_cut, cut_col ? dcc.as<int32_t>() : nullptr))
+    const double *dX = sg.in(X, (size_t)S * 13), *ddN = sg.in(dN, (size_t)C * L), *dobs = sg.in(obs, nobs);
+    const double *dwt = wts ? sg.in(wts, nobs) : nullptr;
+    const int32_t *dhi = interp ? sg.in(obs_hi, nobs) : nullptr;
+    const double *ddx = interp ? sg.in(obs_dx, nobs) : nullptr, *dh = interp ? sg.in(obs_h, nobs) : nullptr;
+    double *dP = sg.inout(P, (size_t)S), *dsse = sg.out(sse, nsys), *des = esum ? sg.out(esum, nsys) : nullptr;
+    int32_t *dst = sg.out(status, nsys), *dfl = floor_col ? sg.out(floor_col, nsys) : nullptr;
+    int32_t *dcc = cut_col ? sg.out(cut_col, nsys) : nullptr;
+    int64_t *dit = sg.out(iters_total, nsys);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = loglik_dev_impl(dX, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, ddN, dobs, dhi, ddx, dh, obs_ld, n_obs,
+                                 dP, dsse, dst, dit, dfl, flags, sg.stream(), des, dwt, sse_cut, dcc))
         return rc;
-    HIP_TRY(hipStreamSynchronize(cs.st));
-    if (seconds) *seconds = now_s() - t0;
-    HIP_TRY(hipMemcpyAsync(P, dP.p, (size_t)S * 8, hipMemcpyDeviceToHost, cs.st));
-    if (sse) HIP_TRY(hipMemcpyAsync(sse, dsse.p, nsys * 8, hipMemcpyDeviceToHost, cs.st));
-    if (esum) HIP_TRY(hipMemcpyAsync(esum, des.p, nsys * 8, hipMemcpyDeviceToHost, cs.st));
-    if (cut_col) HIP_TRY(hipMemcpyAsync(cut_col, dcc.p, nsys * 4, hipMemcpyDeviceToHost, cs.st));
-    if (status) HIP_TRY(hipMemcpyAsync(status, dst.p, nsys * 4, hipMemcpyDeviceToHost, cs.st));
-    if (iters_total) HIP_TRY(hipMemcpyAsync(iters_total, dit.p, nsys * 8, hipMemcpyDeviceToHost, cs.st));
-    if (floor_col) HIP_TRY(hipMemcpyAsync(floor_col, dfl.p, nsys * 4, hipMemcpyDeviceToHost, cs.st));
-    HIP_TRY(hipStreamSynchronize(cs.st));        // the copies back have landed (and their errors surface here)
-    return TRPL_OK;
+    return sg.finish(seconds);
 }
 
 int trpl_loglik(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
@@ -1085,9 +1013,7 @@ int trpl_loglik_moments(const double *X, int64_t S, int32_t C, const double *len
 {
     ProfRange range("trpl_loglik_moments (pvSim + fastlog + lnP's mag_grid moments, fused)");
     if (S > 0 && !esum) return api_fail(TRPL_ERR_ARG, "esum must not be NULL");
-    const bool interp = obs_hi || obs_dx || obs_h;
-    if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
-    if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
+    if (int rc = check_interp(obs_hi, obs_dx, obs_h, plT)) return rc;
     if (S == 0) flags &= ~(uint32_t)TRPL_FLAG_MOMENTS;
     return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
                             obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds, esum);
@@ -1112,9 +1038,7 @@ int trpl_loglik_cut(const double *X, int64_t S, int32_t C, const double *lengths
                     int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device, double *seconds)
 {
     ProfRange range("trpl_loglik_cut (pvSim + fastlog + prob with early stop, fused)");
-    const bool interp = obs_hi || obs_dx || obs_h;
-    if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
-    if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
+    if (int rc = check_interp(obs_hi, obs_dx, obs_h, plT)) return rc;
     return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
                             obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds, nullptr, nullptr,
                             &sse_cut, cut_col);
@@ -1141,9 +1065,7 @@ int trpl_loglik_weighted(const double *X, int64_t S, int32_t C, const double *le
 {
     ProfRange range("trpl_loglik_weighted (pvSim + fastlog + uncertainty-weighted prob, fused)");
     if (S > 0 && (!esum || !wts)) return api_fail(TRPL_ERR_ARG, "esum and wts must not be NULL");
-    const bool interp = obs_hi || obs_dx || obs_h;
-    if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
-    if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
+    if (int rc = check_interp(obs_hi, obs_dx, obs_h, plT)) return rc;
     if (S == 0) flags &= ~(uint32_t)TRPL_FLAG_WEIGHTED;
     if (S > 0 && n_obs && C >= 1 && C <= TRPL_MAX_CURVES && obs_ld >= 1)      // the weights are host data here: validate them
         for (int c = 0; c < C; c++)

@@ -248,7 +248,8 @@ int trpl_device_count(void);
  *                  that system stops there and its remaining PL entries are NaN (the
  *                  reference leaves them uninitialised and stops the whole launch).
  *   iters_total[s] (nullable) inner iterations summed over the steps taken.
- *   seconds        (nullable) kernel time, like pvSim's return value (pvSimPCR.py:378-381).
+ *   seconds        (nullable) device time of the solve, like pvSim's return value (pvSimPCR.py:378-381); defined once for
+ *                  all host-buffer calls at trpl_posterior_weights below.
  * L must be a power of two, 4 <= L <= 512.
  * ------------------------------------------------------------------------------------- */
 int trpl_solve_pl(const double *matpar, int64_t S, double length_nm, double time_ns, int32_t L,
@@ -756,9 +757,11 @@ int trpl_sample_box_dev(uint32_t seed, int64_t S, int32_t ncol, const double *lo
  * centres the second call about the all-reduced means; histograms and sums add across shards.
  * The _dev forms take device pointers (out must be zeroed by the caller for hist) and a workspace of
  * trpl_posterior_workspace_bytes(D) bytes (D = 1 for the weights); nothing is allocated.
- * seconds (nullable), here and in every other analysis-side host-buffer call of this header (trpl_sample_box, temperature scan,
- * predictive band, quantiles, corner, refinement, MCMC, trpl_pcr_solve_batched): the device time of the _dev form, from the inputs having landed on the
- * device to its last kernel having finished; the copies in and out are not in it.
+ * seconds (nullable), here, in trpl_solve_pl[_snap|_resume], trpl_loglik[_obs|_moments|_weighted|_cut] and in every other
+ * analysis-side host-buffer call of this header (trpl_sample_box, temperature scan, predictive band, quantiles, corner, refinement,
+ * MCMC, trpl_pcr_solve_batched): the device time of the _dev form, from the inputs having landed on the device to its last kernel
+ * having finished; the copies in and out are not in it.  Three calls keep the reference's clock instead, which starts before the
+ * copies in (probs.py:79, :51): trpl_log10_clamp and trpl_sse_accumulate[_w] time the uploads plus the kernel, not the copy back.
  * ------------------------------------------------------------------------------------- */
 int64_t trpl_posterior_workspace_bytes(int32_t D);
 int trpl_posterior_weights(const double *LL, int64_t S, double tf, double *W, double *stats /*nullable [2]*/,

@@ -146,3 +146,72 @@ def test_the_three_passes_over_a_resident_pl_block_agree(gpu, problem, pl_block,
     assert np.array_equal(out["moments"]["sse"], out["plain"]["sse"]) and np.array_equal(out["moments"]["P"], out["plain"]["P"])
     for k in ("P", "sse", "esum"):
         assert np.array_equal(out["ones"][k], out["moments"][k]), k
+
+
+ENTRY = {("plain", False): "trpl_loglik", ("plain", True): "trpl_loglik_obs", "moments": "trpl_loglik_moments",
+         "weighted": "trpl_loglik_weighted", "cut": "trpl_loglik_cut"}
+
+
+def _raw(gpu, entry, at, d, lens, level, P, sse, esum, cut_col, status, iters, floor_col, tail, S_=S):
+    """One call of a fused entry point, host-buffer or _dev, argument by argument as include/trpl.h lists them; `at` turns a
+    buffer (or None) into its address, `tail` is (device, seconds) or (stream,)."""
+    a = gpu._abi
+    base = entry[:-4] if entry.endswith("_dev") else entry
+    n_obs = np.array(N_OBS, dtype=np.int64)
+    args = [at(d["X"]), S_, C, a.ptr(lens), TIME, L, T]
+    if base != "trpl_loglik_obs":
+        args.append(1)
+    args += [7, 10000, at(d["ini"]), at(d["obs"])]
+    if base == "trpl_loglik_weighted":
+        args.append(at(d["wts"]))
+    if base != "trpl_loglik":
+        args += [at(d["br"].get(k)) for k in ("obs_hi", "obs_dx", "obs_h")]
+    args += [OBS_LD, a.ptr(n_obs)]
+    if base == "trpl_loglik_cut":
+        args.append(float(level))
+    args += [at(P), at(sse)]
+    if base in ("trpl_loglik_moments", "trpl_loglik_weighted"):
+        args.append(at(esum))
+    if base == "trpl_loglik_cut":
+        args.append(at(cut_col))
+    args += [at(status), at(iters), at(floor_col), a.kernel_flag("single"), *tail]
+    a.check(getattr(a.lib(), entry)(*args))
+
+
+@pytest.mark.parametrize("sink,off", CASES, ids=["%s-%s" % (s, "times" if o else "grid") for s, o in CASES])
+def test_host_buffer_forms_equal_their_device_forms_with_and_without_the_optional_outputs(gpu, problem, sink, off):
+    """The five host-buffer entry points called directly, once with every optional output given and once with all of them NULL
+    (sse, status, iters_total, floor_col, cut_col; esum is not optional where there is one): P, and esum, are the same either way,
+    and every output given is the _dev form's bit for bit.  seconds is a clock: finite and > 0; 0 when there are no samples."""
+    import ctypes
+    import torch
+    p = problem
+    d = _staged(gpu, p, off)
+    h = {k: (v.cpu().numpy() if k != "br" else {n: t.cpu().numpy() for n, t in v.items()}) for k, v in d.items()}
+    entry = ENTRY.get((sink, off)) or ENTRY[sink]
+    level = float(np.median(p["plain"][off]["sse"].sum(axis=0)))
+    moments = sink in ("moments", "weighted")
+    new = lambda dtype, fill, shape=(C, S): np.full(shape, fill, dtype=dtype)
+    out = dict(P=new(np.float64, 0.0, (S,)), sse=new(np.float64, 0.0), esum=new(np.float64, 0.0) if moments else None,
+               cut_col=new(np.int32, 7) if sink == "cut" else None, status=new(np.int32, 7), iters=new(np.int64, 0),
+               floor_col=new(np.int32, 7))
+    dev = {k: None if v is None else torch.from_numpy(v.copy()).cuda() for k, v in out.items()}
+    sec = ctypes.c_double(-1.0)
+    _raw(gpu, entry, gpu._abi.ptr, h, p["lens"], level, tail=(0, ctypes.byref(sec)), **out)
+    _raw(gpu, entry + "_dev", lambda t: None if t is None else t.data_ptr(), d, p["lens"], level,
+         tail=(torch.cuda.current_stream().cuda_stream,), **dev)
+    torch.cuda.synchronize()
+    assert np.isfinite(sec.value) and sec.value > 0
+    assert np.isfinite(out["P"]).all() and (out["sse"] > 0).all() and (out["iters"] > 0).all() and (out["status"] != 7).all()
+    for k, v in out.items():
+        if v is not None:
+            assert np.array_equal(v, dev[k].cpu().numpy()), (sink, off, k)
+    bare = dict.fromkeys(out, None)
+    bare.update(P=new(np.float64, 0.0, (S,)), esum=new(np.float64, 0.0) if moments else None)
+    sec = ctypes.c_double(-1.0)
+    _raw(gpu, entry, gpu._abi.ptr, h, p["lens"], level, tail=(0, ctypes.byref(sec)), **bare)
+    assert np.isfinite(sec.value) and sec.value > 0
+    assert np.array_equal(bare["P"], out["P"]) and (not moments or np.array_equal(bare["esum"], out["esum"]))
+    sec = ctypes.c_double(-1.0)
+    _raw(gpu, entry, gpu._abi.ptr, h, p["lens"], level, tail=(0, ctypes.byref(sec)), S_=0, **bare)
+    assert sec.value == 0.0

@@ -73,3 +73,105 @@ def test_host_buffer_solve_writes_pl_straight_into_the_callers_memory(gpu):
     with ThreadPoolExecutor(2) as ex:
         list(ex.map(lambda b: gpu.solve_pl(X, lens[1], Time, 128, T, ini[1], out=b), bufs))
     assert np.array_equal(bufs[0], bufs[1])
+
+
+# ----------------------------------------------------------------------------- the staged solve against its _dev form
+S5, L5, T5, DT5 = 5, 32, 96, 2.0 ** -5          # DT5 a power of two: a segment of t0 steps has the window's time step exactly
+
+
+@pytest.fixture(scope="module")
+def small(gpu):
+    w = gpu.workloads
+    ini, lens = w.twothick(L5)
+    return dict(X=np.ascontiguousarray(w.samples(S5, seed=13)[:, :12]), ini=np.ascontiguousarray(ini[0]), length=float(lens[0]))
+
+
+def _stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _solve_snap(gpu, p, dev, plT, pl, ld, status, iters, steps, n_snap, plN, plP, plE):
+    """trpl_solve_pl_snap (numpy buffers; returns seconds) or trpl_solve_pl_snap_dev (CUDA tensors), the arguments as given."""
+    import ctypes
+    import torch
+    a = gpu._abi
+    at = (lambda t: None if t is None else t.data_ptr()) if dev else a.ptr
+    give = (lambda v: torch.from_numpy(v).cuda()) if dev else (lambda v: v)
+    X, ini = give(p["X"]), give(p["ini"])
+    sec = ctypes.c_double(-1.0)
+    args = [at(X), S5, p["length"], T5 * DT5, L5, T5, plT, 7, 10000, at(ini), at(pl), pl.element_size() if dev else pl.itemsize, ld,
+            at(status), at(iters), a.ptr(steps), n_snap, at(plN), at(plP), at(plE), 0]
+    if dev:
+        a.check(a.lib().trpl_solve_pl_snap_dev(*args, _stream()))
+        torch.cuda.synchronize()
+        return None
+    a.check(a.lib().trpl_solve_pl_snap(*args, 0, ctypes.byref(sec)))
+    return sec.value
+
+
+@pytest.mark.parametrize("outputs", [False, True], ids=["status-null", "status-given"])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("plT", [1, 4])
+def test_staged_solve_equals_the_device_form_bit_for_bit(gpu, small, plT, dtype, outputs):
+    """A PL matrix below the mapping threshold goes through device memory and a pitched copy back: rows of ncol columns in a
+    leading dimension of ncol + 3, the padding keeps the caller's sentinel; status and iters_total both NULL or both given."""
+    import torch
+    ncol = T5 // plT + 1
+    ld = ncol + 3
+    host = np.full((S5, ld), -7.0, dtype=dtype)
+    dev = torch.from_numpy(host.copy()).cuda()
+    st, it = (np.full(S5, 9, np.int32), np.full(S5, -1, np.int64)) if outputs else (None, None)
+    dst, dit = (torch.from_numpy(st.copy()).cuda(), torch.from_numpy(it.copy()).cuda()) if outputs else (None, None)
+    sec = _solve_snap(gpu, small, False, plT, host, ld, st, it, None, 0, None, None, None)
+    _solve_snap(gpu, small, True, plT, dev, ld, dst, dit, None, 0, None, None, None)
+    assert np.isfinite(sec) and sec > 0
+    assert np.isfinite(host[:, :ncol]).all() and (host[:, :ncol] > 0).all() and (host[:, ncol:] == -7.0).all()
+    assert np.array_equal(host, dev.cpu().numpy())
+    if outputs:
+        assert not st.any() and (it > 0).all()
+        assert np.array_equal(st, dst.cpu().numpy()) and np.array_equal(it, dit.cpu().numpy())
+
+
+def test_staged_snapshots_keep_the_unfilled_slot_and_take_pln_alone(gpu, small):
+    """n_snap = 3 with one step outside [0, T]: that slot keeps the caller's sentinel, in the host-buffer form (the snapshot
+    arrays go up and come back) as in the _dev form; plP and plE are NULL."""
+    import torch
+    steps = np.array([10, T5 + 5, 40], dtype=np.int64)
+    plN = np.full((S5, 3, L5), -3.0)
+    dN = torch.from_numpy(plN.copy()).cuda()
+    pl, dpl = np.empty((S5, T5 + 1)), torch.empty((S5, T5 + 1), dtype=torch.float64, device="cuda")
+    sec = _solve_snap(gpu, small, False, 1, pl, T5 + 1, None, None, steps, 3, plN, None, None)
+    _solve_snap(gpu, small, True, 1, dpl, T5 + 1, None, None, steps, 3, dN, None, None)
+    assert np.isfinite(sec) and sec > 0
+    assert (plN[:, 1] == -3.0).all() and np.isfinite(plN).all() and (plN[:, [0, 2]] != -3.0).all() and not np.array_equal(plN[:, 0], plN[:, 2])
+    assert np.array_equal(plN, dN.cpu().numpy()) and np.array_equal(pl, dpl.cpu().numpy())
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+def test_staged_resume_keeps_the_columns_before_t0_in_a_padded_matrix(gpu, small, dtype):
+    """The small twin of test_continue_into_a_large_host_buffer_written_in_place: below the mapping threshold a resume stages the
+    caller's matrix up and back (pitched, rows of ncol columns in ncol + 3), so columns before ceil(t0 / plT) and the padding
+    keep the caller's sentinel and the rest is the uninterrupted run."""
+    p, t0, plT = small, 41, 4
+    Time, ncol, first = T5 * DT5, T5 // plT + 1, -(-41 // 4)
+    full, st, _, _ = gpu.solve_pl(p["X"], p["length"], Time, L5, T5, p["ini"], plT=plT, dtype=dtype)
+    ck = {}
+    gpu.solve_pl(p["X"], p["length"], Time * t0 / T5, L5, t0, p["ini"], plT=plT, snap_steps=gpu.checkpoint_steps(t0), snapshots=ck,
+                 snap_raw=True, dtype=dtype)
+    big = np.full((S5, ncol + 3), -3.0, dtype=dtype)
+    _, st_b, _, sec = gpu.solve_pl(p["X"], p["length"], Time, L5, T5, None, plT=plT, out=big[:, :ncol],
+                                   resume=(t0, ck["plN"], ck["plP"], ck["plE"]))
+    assert not st.any() and not st_b.any() and np.isfinite(sec) and sec > 0
+    assert (big[:, :first] == -3.0).all() and (big[:, ncol:] == -3.0).all()
+    assert np.array_equal(big[:, first:ncol], full[:, first:])
+
+
+def test_solve_seconds_are_zero_at_the_early_return(gpu, small):
+    import ctypes
+    a, p = gpu._abi, small
+    sec = ctypes.c_double(-1.0)
+    pl = np.empty((1, T5 + 1))
+    a.check(a.lib().trpl_solve_pl(a.ptr(p["X"]), 0, p["length"], T5 * DT5, L5, T5, 1, 7, 10000, a.ptr(p["ini"]), a.ptr(pl), 8, T5 + 1,
+                                  None, None, 0, 0, ctypes.byref(sec)))
+    assert sec.value == 0.0

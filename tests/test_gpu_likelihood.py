@@ -583,3 +583,69 @@ def test_literal_interpolation_switch_reaches_the_multi_experiment_branch(gpu, o
         res[name] = P
     assert np.isfinite(res["prefix"]).all() and (res["prefix"] < 0).all()
     assert np.max(np.abs(res["literal"] / res["prefix"] - 1)) < 1e-13
+
+
+# ----------------------------------------------------------------------------- the staged probs calls against their _dev forms
+def _dev_stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+def test_staged_fastlog_and_prob_equal_their_device_forms_bit_for_bit(gpu, dtype):
+    """trpl_log10_clamp and trpl_sse_accumulate[_w] on rows of 7 in a leading dimension of 10: what the host-buffer forms bring back
+    is what the _dev forms leave on the device, the padding keeps the caller's sentinel; then no observations (P unchanged) and no
+    rows (nothing to do: seconds stay 0)."""
+    import ctypes
+    import torch
+    a, lib = gpu._abi, gpu._abi.lib()
+    rng = np.random.default_rng(5)
+    rows, cols, ld, eb = 3, 7, 10, np.dtype(dtype).itemsize
+    x = rng.lognormal(-5, 2, (rows, ld)).astype(dtype)
+    x[0, 2] = 0.0                                                   # clamped to MIN
+    x[:, cols:] = -7.0
+    up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).cuda()
+    sec = ctypes.c_double(-1.0)
+    host, dev = x.copy(), up(x)
+    a.check(lib.trpl_log10_clamp(a.ptr(host), eb, rows, cols, ld, 1e-30, 0, ctypes.byref(sec)))
+    a.check(lib.trpl_log10_clamp_dev(dev.data_ptr(), eb, rows, cols, ld, 1e-30, _dev_stream()))
+    torch.cuda.synchronize()
+    assert np.isfinite(sec.value) and sec.value > 0
+    assert np.isfinite(host[:, :cols]).all() and abs(host[0, 2] + 30.0) < 1e-4 and (host[:, cols:] == -7.0).all()
+    assert np.array_equal(host, dev.cpu().numpy())
+    values, wts, mag, P0 = rng.uniform(-9, -1, cols), rng.uniform(0.1, 3.0, cols), rng.uniform(-1, 1, rows), rng.normal(size=rows)
+    dval, dwt, dmag = up(values), up(wts), up(mag)
+    for weighted in (False, True):
+        name = "trpl_sse_accumulate_w" if weighted else "trpl_sse_accumulate"
+        w_h, w_d = ([a.ptr(wts)], [dwt.data_ptr()]) if weighted else ([], [])
+        for n_obs in (cols, 0):
+            P, dP = P0.copy(), up(P0)
+            sec = ctypes.c_double(-1.0)
+            a.check(getattr(lib, name)(a.ptr(P), a.ptr(host), eb, rows, n_obs, ld, a.ptr(values), *w_h, a.ptr(mag), 0, ctypes.byref(sec)))
+            a.check(getattr(lib, name + "_dev")(dP.data_ptr(), dev.data_ptr(), eb, rows, n_obs, ld, dval.data_ptr(), *w_d,
+                                                dmag.data_ptr(), _dev_stream()))
+            torch.cuda.synchronize()
+            assert np.isfinite(sec.value) and sec.value > 0
+            assert np.array_equal(P, dP.cpu().numpy()) and np.array_equal(P, P0) == (n_obs == 0), (name, n_obs)
+        P, sec = P0.copy(), ctypes.c_double(-1.0)
+        a.check(getattr(lib, name)(a.ptr(P), a.ptr(host), eb, 0, cols, ld, a.ptr(values), *w_h, a.ptr(mag), 0, ctypes.byref(sec)))
+        assert sec.value == 0.0 and np.array_equal(P, P0)
+    sec = ctypes.c_double(-1.0)
+    a.check(lib.trpl_log10_clamp(a.ptr(host), eb, 0, cols, ld, 1e-30, 0, ctypes.byref(sec)))
+    assert sec.value == 0.0
+
+
+def test_fastlog_of_a_buffer_above_the_pinning_threshold_equals_the_blockwise_call(gpu):
+    """Just over 8 MiB with a ragged leading dimension: the call pins the caller's memory for its copies.  Its rows are the rows
+    of the same data pushed through in four blocks below the threshold; the padding is untouched."""
+    rng = np.random.default_rng(6)
+    rows, cols, ld = 1024, 2039, 2053
+    big = rng.lognormal(-5, 2, (rows, ld)).astype(np.float32)
+    big[:, cols:] = -7.0
+    assert ((rows - 1) * ld + cols) * 4 > (8 << 20) > (rows // 4) * ld * 4
+    blocks = big.copy()
+    assert gpu.fastlog(big[:, :cols], 1e-30) > 0
+    for r in range(0, rows, rows // 4):
+        gpu.fastlog(blocks[r:r + rows // 4, :cols], 1e-30)
+    assert np.isfinite(big[:, :cols]).all() and (big[:, cols:] == -7.0).all()
+    assert np.array_equal(big, blocks)
