@@ -1,6 +1,7 @@
 // Host-side helpers shared by every translation unit that implements include/trpl.h: the thread-local error message, Staged, the
-// staging of every single-device host-buffer call, the RAII pieces it is made of (CallScope, DevBuf, HostPin, HostMap; only
-// trpl_multi.hip, which keeps per-device buffers across threads, also uses them directly), argument checks.  Nothing here throws.
+// staging of every host-buffer call (trpl_loglik_multi holds one per shard), the RAII pieces it is made of (CallScope, DevBuf,
+// HostPin, HostMap; outside Staged only trpl_loglik_multi_dev uses one, a DevBuf for an sse the caller does not take), LoglikCall,
+// the argument record of the fused likelihood, argument checks.  Nothing here throws.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -235,9 +236,38 @@ struct ProfRange {
     ProfRange &operator=(const ProfRange &) = delete;
 };
 
+// The arguments of one fused-likelihood call, device pointers: what the trpl_loglik*_dev entry points take, by name.  esum, wts,
+// sse_cut and cut_col select the sink (trpl_loglik_moments / _weighted / _cut) and are NULL elsewhere; the brackets are NULL on the grid.
+struct LoglikCall {
+    const double *X = nullptr;
+    int64_t S = 0;
+    int32_t C = 0;
+    const double *lengths_nm = nullptr;              // host, like n_obs
+    double time_ns = 0.0;
+    int32_t L = 0;
+    int64_t T = 0;
+    int32_t plT = 1, tol_exp = 0, max_iter = 0;
+    const double *dN = nullptr, *obs = nullptr, *wts = nullptr;
+    const int32_t *obs_hi = nullptr;
+    const double *obs_dx = nullptr, *obs_h = nullptr;
+    int64_t obs_ld = 0;
+    const int64_t *n_obs = nullptr;
+    const double *sse_cut = nullptr;                 // host: the threshold of the cut entry points
+    double *P = nullptr, *sse = nullptr, *esum = nullptr;
+    int32_t *cut_col = nullptr, *status = nullptr;
+    int64_t *iters_total = nullptr;
+    int32_t *floor_col = nullptr;
+    uint32_t flags = 0;
+};
+// every check of a trpl_loglik*_dev call, then its launches and the reduction over the curves on `stream` (trpl_api.hip)
+int loglik_dev(const LoglikCall &k, hipStream_t stream);
+
 int no_weighted_flag(uint32_t flags);      // TRPL_ERR_ARG when TRPL_FLAG_WEIGHTED reaches an entry point that takes no weights
 int no_moments_flag(uint32_t flags);       // TRPL_ERR_ARG when TRPL_FLAG_MOMENTS reaches an entry point without an esum output
 int check_grid(int32_t L, int64_t T, int32_t plT, int32_t max_iter, double time_ns);
+int check_batch(const LoglikCall &k);       // check_grid, then S >= 0 and C in [1, TRPL_MAX_CURVES]: what every fused-likelihood head shares
+// the three bracket arrays of an off-grid call: all or none, and on every time step
+int check_interp(const void *obs_hi, const void *obs_dx, const void *obs_h, int32_t plT);
 // the observation brackets of trpl_loglik_obs are host data in the host-buffer calls: sorted, in [1, T]
 int check_brackets(const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int32_t C, int64_t obs_ld,
                    const int64_t *n_obs, int64_t T);

@@ -357,22 +357,6 @@ void mag_profile_host_w(const double *sse, const double *esum, const double *wsu
     for (int64_t s = 0; s < S; s++) mag_profile_one(sse, esum, wsum, S, C, s, per_curve, best, P + s);
 }
 
-void mag_grid_host(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, const double *offsets,
-                   int64_t M, double *P)
-{
-    double n[kMagMaxCurves];
-    for (int c = 0; c < C; c++) n[c] = (double)n_obs[c];
-    mag_grid_host_w(sse, esum, n, S, C, offsets, M, P);
-}
-
-void mag_profile_host(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, bool per_curve,
-                      double *best, double *P)
-{
-    double n[kMagMaxCurves];
-    for (int c = 0; c < C; c++) n[c] = (double)n_obs[c];
-    mag_profile_host_w(sse, esum, n, S, C, per_curve, best, P);
-}
-
 struct MagArgs {
     double n[kMagMaxCurves];
     double d[kMagChunk];
@@ -424,14 +408,6 @@ hipError_t launch_mag_grid_w(const double *sse, const double *esum, const double
     return hipGetLastError();
 }
 
-hipError_t launch_mag_grid(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C,
-                           const double *offsets, int64_t M, double *P, hipStream_t stream)
-{
-    double n[kMagMaxCurves];
-    for (int c = 0; c < C; c++) n[c] = (double)n_obs[c];
-    return launch_mag_grid_w(sse, esum, n, S, C, offsets, M, P, stream);
-}
-
 hipError_t launch_mag_profile_w(const double *sse, const double *esum, const double *wsum, int64_t S, int C, bool per_curve,
                                 double *best, double *P, hipStream_t stream)
 {
@@ -443,14 +419,6 @@ hipError_t launch_mag_profile_w(const double *sse, const double *esum, const dou
     hipLaunchKernelGGL(mag_profile_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, sse, esum, S, C, per_curve ? 1 : 0,
                        best, P, g);
     return hipGetLastError();
-}
-
-hipError_t launch_mag_profile(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, bool per_curve,
-                              double *best, double *P, hipStream_t stream)
-{
-    double n[kMagMaxCurves];
-    for (int c = 0; c < C; c++) n[c] = (double)n_obs[c];
-    return launch_mag_profile_w(sse, esum, n, S, C, per_curve, best, P, stream);
 }
 
 // ---- host-side time interpolation of the unfused call sequence (bayeslib.py:184-191) ----

@@ -63,6 +63,22 @@ int check_grid(int32_t L, int64_t T, int32_t plT, int32_t max_iter, double time_
     return TRPL_OK;
 }
 
+int check_batch(const LoglikCall &k)
+{
+    if (int rc = check_grid(k.L, k.T, k.plT, k.max_iter, k.time_ns)) return rc;
+    if (k.S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
+    if (k.C < 1 || k.C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", k.C, TRPL_MAX_CURVES);
+    return TRPL_OK;
+}
+
+int check_interp(const void *obs_hi, const void *obs_dx, const void *obs_h, int32_t plT)
+{
+    const bool interp = obs_hi || obs_dx || obs_h;
+    if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
+    if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
+    return TRPL_OK;
+}
+
 // plT as the kernels see it: a stride beyond the window stores column 0 only, whatever its size
 static inline int32_t kernel_plT(int32_t plT, int64_t T) { return (int64_t)plT > T + 1 ? (int32_t)(T + 1) : plT; }
 
@@ -817,15 +833,6 @@ int trpl_loglik_weighted_from_pl_dev(const void *plI, int32_t elem_bytes, int64_
 }
 
 /* ------------------------------------------------------------------ fused loglik -------- */
-// the three bracket arrays of an off-grid call: all or none, and on every time step
-static int check_interp(const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int32_t plT)
-{
-    const bool interp = obs_hi || obs_dx || obs_h;
-    if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
-    if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
-    return TRPL_OK;
-}
-
 // Which of the two flags the entry points set themselves a call may carry: wts -- the weighted entry points (they set
 // TRPL_FLAG_WEIGHTED; with TRPL_FLAG_MOMENTS: refused, the weighted sink already emits both sums); esum alone -- the moments entry
 // points (they set TRPL_FLAG_MOMENTS); every other caller must carry neither.
@@ -850,73 +857,169 @@ static int entry_flags(uint32_t &flags, bool esum, bool wts, bool cut = false)
     return no_moments_flag(flags);
 }
 
-static int loglik_dev_impl(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
-                           int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
-                           const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
-                           int64_t obs_ld, const int64_t *n_obs, double *P, double *sse, int32_t *status,
-                           int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream, double *esum = nullptr,
-                           const double *wts = nullptr, const double *sse_cut = nullptr, int32_t *cut_col = nullptr)
+// the sink flag of the record's optional pointers and the sse_cut range: the first checks of both forms
+static int check_sink(const LoglikCall &k, uint32_t &flags)
 {
     // sse_cut: the cut entry points (NULL everywhere else)
-    if (int rc = entry_flags(flags, esum != nullptr, wts != nullptr, sse_cut != nullptr)) return rc;
-    if (sse_cut && !(*sse_cut >= 0.0)) return api_fail(TRPL_ERR_ARG, "sse_cut=%g must be >= 0 or +inf", *sse_cut);
-    if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
-    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
-    if (C < 1 || C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAX_CURVES);
+    if (int rc = entry_flags(flags, k.esum != nullptr, k.wts != nullptr, k.sse_cut != nullptr)) return rc;
+    if (k.sse_cut && !(*k.sse_cut >= 0.0)) return api_fail(TRPL_ERR_ARG, "sse_cut=%g must be >= 0 or +inf", *k.sse_cut);
+    return TRPL_OK;
+}
+
+}  // extern "C": trpl::loglik_dev is called from trpl_multi.hip too
+
+int trpl::loglik_dev(const LoglikCall &k, hipStream_t stream)
+{
+    uint32_t flags = k.flags;
+    if (int rc = check_sink(k, flags)) return rc;
+    if (int rc = check_batch(k)) return rc;
+    const int64_t S = k.S, T = k.T, obs_ld = k.obs_ld;
+    const int32_t C = k.C, L = k.L;
     if (S == 0) return TRPL_OK;
-    if (!X || !lengths_nm || !dN || !obs || !n_obs || !P || !sse) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
-    if (int rc = check_interp(obs_hi, obs_dx, obs_h, plT)) return rc;
-    const bool interp = obs_hi != nullptr;
-    const int64_t ncol = T / plT + 1;
+    if (!k.X || !k.lengths_nm || !k.dN || !k.obs || !k.n_obs || !k.P || !k.sse) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
+    if (int rc = check_interp(k.obs_hi, k.obs_dx, k.obs_h, k.plT)) return rc;
+    const bool interp = k.obs_hi != nullptr;
+    const int64_t ncol = T / k.plT + 1;
     for (int c = 0; c < C; c++) {
-        if (!(lengths_nm[c] > 0)) return api_fail(TRPL_ERR_ARG, "lengths_nm[%d] must be > 0", c);
-        if (n_obs[c] < 1 || n_obs[c] > obs_ld || (!interp && n_obs[c] > ncol))
+        if (!(k.lengths_nm[c] > 0)) return api_fail(TRPL_ERR_ARG, "lengths_nm[%d] must be > 0", c);
+        if (k.n_obs[c] < 1 || k.n_obs[c] > obs_ld || (!interp && k.n_obs[c] > ncol))
             return api_fail(TRPL_ERR_ARG, "n_obs[%d]=%lld out of range (obs_ld %lld, grid columns %lld)", c,
-                        (long long)n_obs[c], (long long)obs_ld, (long long)ncol);
+                        (long long)k.n_obs[c], (long long)obs_ld, (long long)ncol);
     }
     // A launch carries the constants of at most kMaxCurves curves in its argument block; bayeslib.simulate loops over any
     // number of curves (bayeslib.py:117), so more are run as consecutive launches of up to kMaxCurves on the same stream,
     // each writing its own rows of the [C][S] outputs, before ONE reduction over all C in curve order (probs.py:44).  The
     // stepper variant is chosen once from the whole batch, so a system's bits do not depend on the grouping.
-    const int64_t steps = loglik_steps(interp, C, n_obs, plT, T);
+    const int64_t steps = loglik_steps(interp, C, k.n_obs, k.plT, T);
     if (C > trpl::kMaxCurves) flags = pin_variant(flags, S * (int64_t)C, L, steps);
     for (int c0 = 0; c0 < C; c0 += trpl::kMaxCurves) {
         const int Cg = C - c0 < trpl::kMaxCurves ? C - c0 : trpl::kMaxCurves;
         if (S * (int64_t)Cg > 0x7fffffffLL) return api_fail(TRPL_ERR_ARG, "S*C too large for one launch");
         trpl::StepArgs a;
         memset(&a, 0, sizeof a);
-        a.X = X; a.xld = 13; a.dN = dN + (int64_t)c0 * L; a.obs = obs + (int64_t)c0 * obs_ld;
-        a.obs_hi = obs_hi ? obs_hi + (int64_t)c0 * obs_ld : nullptr;
-        a.obs_dx = obs_dx ? obs_dx + (int64_t)c0 * obs_ld : nullptr;
-        a.obs_h = obs_h ? obs_h + (int64_t)c0 * obs_ld : nullptr;
-        a.obs_ld = obs_ld; a.sse = sse + (int64_t)c0 * S;
-        a.esum = esum ? esum + (int64_t)c0 * S : nullptr;
-        a.wts = wts ? wts + (int64_t)c0 * obs_ld : nullptr;
-        a.sse_cut = sse_cut ? *sse_cut : 0.0;
-        a.cut_col = cut_col ? cut_col + (int64_t)c0 * S : nullptr;
-        a.status = status ? status + (int64_t)c0 * S : nullptr;
-        a.iters_total = iters_total ? iters_total + (int64_t)c0 * S : nullptr;
-        a.floor_col = floor_col ? floor_col + (int64_t)c0 * S : nullptr;
-        a.S = S; a.C = Cg; a.L = L; a.T = T; a.plT = kernel_plT(plT, T); a.MAX = max_iter; a.flags = flags;
-        a.TOL = pow(10.0, -(double)tol_exp);
+        a.X = k.X; a.xld = 13; a.dN = k.dN + (int64_t)c0 * L; a.obs = k.obs + (int64_t)c0 * obs_ld;
+        a.obs_hi = k.obs_hi ? k.obs_hi + (int64_t)c0 * obs_ld : nullptr;
+        a.obs_dx = k.obs_dx ? k.obs_dx + (int64_t)c0 * obs_ld : nullptr;
+        a.obs_h = k.obs_h ? k.obs_h + (int64_t)c0 * obs_ld : nullptr;
+        a.obs_ld = obs_ld; a.sse = k.sse + (int64_t)c0 * S;
+        a.esum = k.esum ? k.esum + (int64_t)c0 * S : nullptr;
+        a.wts = k.wts ? k.wts + (int64_t)c0 * obs_ld : nullptr;
+        a.sse_cut = k.sse_cut ? *k.sse_cut : 0.0;
+        a.cut_col = k.cut_col ? k.cut_col + (int64_t)c0 * S : nullptr;
+        a.status = k.status ? k.status + (int64_t)c0 * S : nullptr;
+        a.iters_total = k.iters_total ? k.iters_total + (int64_t)c0 * S : nullptr;
+        a.floor_col = k.floor_col ? k.floor_col + (int64_t)c0 * S : nullptr;
+        a.S = S; a.C = Cg; a.L = L; a.T = T; a.plT = kernel_plT(k.plT, T); a.MAX = k.max_iter; a.flags = flags;
+        a.TOL = pow(10.0, -(double)k.tol_exp);
         for (int c = 0; c < Cg; c++) {
-            curve_const(lengths_nm[c0 + c], time_ns, L, T, a.curve[c]);
-            a.curve[c].n_obs = n_obs[c0 + c];
+            curve_const(k.lengths_nm[c0 + c], k.time_ns, L, T, a.curve[c]);
+            a.curve[c].n_obs = k.n_obs[c0 + c];
         }
-        if (int rc = launch(a, flags, (hipStream_t)stream, steps)) return rc;
+        if (int rc = launch(a, flags, stream, steps)) return rc;
     }
-    hipError_t e = trpl::launch_reduce_curves(P, sse, S, C, (hipStream_t)stream);
+    hipError_t e = trpl::launch_reduce_curves(k.P, k.sse, S, C, stream);
     if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "reduce_curves launch: %s", hipGetErrorString(e));
     return TRPL_OK;
 }
+
+// the host-buffer form of loglik_dev: the record's pointers are the caller's host arrays
+static int loglik_host(const LoglikCall &k, int32_t device, double *seconds)
+{
+    { uint32_t f = k.flags; if (int rc = check_sink(k, f)) return rc; }
+    if (int rc = check_batch(k)) return rc;
+    if (seconds) *seconds = 0.0;
+    if (k.S == 0) return TRPL_OK;
+    if (!k.X || !k.lengths_nm || !k.dN || !k.obs || !k.n_obs || !k.P) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
+    if (k.obs_ld < 1) return api_fail(TRPL_ERR_ARG, "obs_ld must be >= 1");
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const bool interp = k.obs_hi != nullptr;
+    if (interp) {                                    // the brackets are host data here: validate them
+        if (int rc = check_brackets(k.obs_hi, k.obs_dx, k.obs_h, k.C, k.obs_ld, k.n_obs, k.T)) return rc;
+    }
+    // sse, status and iters_total are the _dev form's whether the caller takes them or not; floor_col, esum and cut_col only on request
+    const size_t nsys = (size_t)k.S * k.C, nobs = (size_t)k.C * k.obs_ld;
+    LoglikCall d = k;
+    d.X = sg.in(k.X, (size_t)k.S * 13); d.dN = sg.in(k.dN, (size_t)k.C * k.L); d.obs = sg.in(k.obs, nobs);
+    d.wts = k.wts ? sg.in(k.wts, nobs) : nullptr;
+    d.obs_hi = interp ? sg.in(k.obs_hi, nobs) : nullptr;
+    d.obs_dx = interp ? sg.in(k.obs_dx, nobs) : nullptr; d.obs_h = interp ? sg.in(k.obs_h, nobs) : nullptr;
+    d.P = sg.inout(k.P, (size_t)k.S); d.sse = sg.out(k.sse, nsys); d.esum = k.esum ? sg.out(k.esum, nsys) : nullptr;
+    d.status = sg.out(k.status, nsys); d.floor_col = k.floor_col ? sg.out(k.floor_col, nsys) : nullptr;
+    d.cut_col = k.cut_col ? sg.out(k.cut_col, nsys) : nullptr;
+    d.iters_total = sg.out(k.iters_total, nsys);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = loglik_dev(d, sg.stream())) return rc;
+    return sg.finish(seconds);
+}
+
+/* ------------------------------------------------------------------ magnitude grid and profile from the moments */
+// trpl_mag_grid[_w][_dev] and trpl_mag_profile[_w][_dev]: one body per operation.  The per-curve coefficient is a count (N = int64_t:
+// n_obs, >= 1, converted exactly) or a sum of weights (N = double: wsum, finite and >= 0); either way likelihood.hip gets doubles.
+// on_device: the kernels on `stream`; else the host loop.
+template <typename N>
+static int check_mag(const double *sse, const double *esum, const N *v, int64_t S, int32_t C, const double *P, bool need_P, double *n)
+{
+    constexpr bool counts = std::is_same_v<N, int64_t>;
+    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
+    if (C < 1 || C > TRPL_MAG_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAG_MAX_CURVES);
+    if (!v) return api_fail(TRPL_ERR_ARG, "%s must not be NULL", counts ? "n_obs" : "wsum");
+    for (int c = 0; c < C; c++) {
+        if constexpr (counts) {
+            if (v[c] < 1) return api_fail(TRPL_ERR_ARG, "n_obs[%d]=%lld must be >= 1", c, (long long)v[c]);
+        } else {
+            if (!(v[c] >= 0.0) || !(v[c] < INFINITY)) return api_fail(TRPL_ERR_ARG, "wsum[%d]=%g must be finite and >= 0", c, v[c]);
+        }
+        n[c] = (double)v[c];
+    }
+    if (S > 0 && (!sse || !esum || (need_P && !P))) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
+    return TRPL_OK;
+}
+
+template <typename N>
+static int mag_grid(const double *sse, const double *esum, const N *v, int64_t S, int32_t C, const double *offsets, int64_t M,
+                    double *P, bool on_device, void *stream)
+{
+    double n[trpl::kMagMaxCurves];
+    if (M < 0) return api_fail(TRPL_ERR_ARG, "M must be >= 0");
+    if (int rc = check_mag(sse, esum, v, S, C, P, M > 0, n)) return rc;
+    if (S == 0 || M == 0) return TRPL_OK;
+    if (!offsets) return api_fail(TRPL_ERR_ARG, "offsets must not be NULL");
+    if (!on_device) { trpl::mag_grid_host_w(sse, esum, n, S, C, offsets, M, P); return TRPL_OK; }
+    hipError_t e = trpl::launch_mag_grid_w(sse, esum, n, S, C, offsets, M, P, (hipStream_t)stream);
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mag_grid%s launch: %s", std::is_same_v<N, double> ? "_w" : "", hipGetErrorString(e));
+    return TRPL_OK;
+}
+
+template <typename N>
+static int mag_profile(const double *sse, const double *esum, const N *v, int64_t S, int32_t C, uint32_t flags, double *best,
+                       double *P, bool on_device, void *stream)
+{
+    const char *w = std::is_same_v<N, double> ? "_w" : "";
+    double n[trpl::kMagMaxCurves];
+    if (flags & ~(uint32_t)TRPL_MAG_PER_CURVE) return api_fail(TRPL_ERR_ARG, "trpl_mag_profile%s: unknown flag bits 0x%x", w, flags);
+    if (int rc = check_mag(sse, esum, v, S, C, P, true, n)) return rc;
+    if (S == 0) return TRPL_OK;
+    if (!best) return api_fail(TRPL_ERR_ARG, "best must not be NULL");
+    const bool per_curve = (flags & TRPL_MAG_PER_CURVE) != 0;
+    if (!on_device) { trpl::mag_profile_host_w(sse, esum, n, S, C, per_curve, best, P); return TRPL_OK; }
+    hipError_t e = trpl::launch_mag_profile_w(sse, esum, n, S, C, per_curve, best, P, (hipStream_t)stream);
+    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mag_profile%s launch: %s", w, hipGetErrorString(e));
+    return TRPL_OK;
+}
+
+extern "C" {
 
 int trpl_loglik_dev(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
                     int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
                     const double *obs, int64_t obs_ld, const int64_t *n_obs, double *P, double *sse,
                     int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream)
 {
-    return loglik_dev_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, nullptr, nullptr,
-                           nullptr, obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, stream);
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = plT; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    return loglik_dev(k, (hipStream_t)stream);
 }
 
 int trpl_loglik_obs_dev(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
@@ -926,48 +1029,12 @@ int trpl_loglik_obs_dev(const double *X, int64_t S, int32_t C, const double *len
                         int32_t *floor_col, uint32_t flags, void *stream)
 {
     if (!obs_hi || !obs_dx || !obs_h) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h must not be NULL");
-    return loglik_dev_impl(X, S, C, lengths_nm, time_ns, L, T, 1, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
-                           obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, stream);
-}
-
-static int loglik_host_impl(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
-                            int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
-                            const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
-                            int64_t obs_ld, const int64_t *n_obs, double *P, double *sse, int32_t *status,
-                            int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device, double *seconds,
-                            double *esum = nullptr, const double *wts = nullptr, const double *sse_cut = nullptr,
-                            int32_t *cut_col = nullptr)
-{
-    { uint32_t f = flags; if (int rc = entry_flags(f, esum != nullptr, wts != nullptr, sse_cut != nullptr)) return rc; }
-    if (sse_cut && !(*sse_cut >= 0.0)) return api_fail(TRPL_ERR_ARG, "sse_cut=%g must be >= 0 or +inf", *sse_cut);
-    if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
-    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
-    if (C < 1 || C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAX_CURVES);
-    if (seconds) *seconds = 0.0;
-    if (S == 0) return TRPL_OK;
-    if (!X || !lengths_nm || !dN || !obs || !n_obs || !P) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
-    if (obs_ld < 1) return api_fail(TRPL_ERR_ARG, "obs_ld must be >= 1");
-    Staged sg;
-    if (int rc = sg.open(device)) return rc;
-    const bool interp = obs_hi != nullptr;
-    if (interp) {                                    // the brackets are host data here: validate them
-        if (int rc = check_brackets(obs_hi, obs_dx, obs_h, C, obs_ld, n_obs, T)) return rc;
-    }
-    // sse, status and iters_total are the _dev form's whether the caller takes them or not; floor_col, esum and cut_col only on request
-    const size_t nsys = (size_t)S * C, nobs = (size_t)C * obs_ld;
-    const double *dX = sg.in(X, (size_t)S * 13), *ddN = sg.in(dN, (size_t)C * L), *dobs = sg.in(obs, nobs);
-    const double *dwt = wts ? sg.in(wts, nobs) : nullptr;
-    const int32_t *dhi = interp ? sg.in(obs_hi, nobs) : nullptr;
-    const double *ddx = interp ? sg.in(obs_dx, nobs) : nullptr, *dh = interp ? sg.in(obs_h, nobs) : nullptr;
-    double *dP = sg.inout(P, (size_t)S), *dsse = sg.out(sse, nsys), *des = esum ? sg.out(esum, nsys) : nullptr;
-    int32_t *dst = sg.out(status, nsys), *dfl = floor_col ? sg.out(floor_col, nsys) : nullptr;
-    int32_t *dcc = cut_col ? sg.out(cut_col, nsys) : nullptr;
-    int64_t *dit = sg.out(iters_total, nsys);
-    if (int rc = sg.begin()) return rc;
-    if (int rc = loglik_dev_impl(dX, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, ddN, dobs, dhi, ddx, dh, obs_ld, n_obs,
-                                 dP, dsse, dst, dit, dfl, flags, sg.stream(), des, dwt, sse_cut, dcc))
-        return rc;
-    return sg.finish(seconds);
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = 1; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h;
+    return loglik_dev(k, (hipStream_t)stream);
 }
 
 int trpl_loglik(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
@@ -976,8 +1043,11 @@ int trpl_loglik(const double *X, int64_t S, int32_t C, const double *lengths_nm,
                 int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device, double *seconds)
 {
     ProfRange range("trpl_loglik (pvSim + fastlog + prob, fused)");
-    return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, nullptr, nullptr,
-                            nullptr, obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds);
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = plT; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    return loglik_host(k, device, seconds);
 }
 
 int trpl_loglik_obs(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
@@ -988,8 +1058,12 @@ int trpl_loglik_obs(const double *X, int64_t S, int32_t C, const double *lengths
 {
     ProfRange range("trpl_loglik_obs (pvSim + fastlog + griddata + prob, fused)");
     if (!obs_hi || !obs_dx || !obs_h) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h must not be NULL");
-    return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, 1, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
-                            obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds);
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = 1; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h;
+    return loglik_host(k, device, seconds);
 }
 
 /* ------------------------------------------------------------------ moments + magnitude grid (probs.py:5-18) */
@@ -1001,8 +1075,12 @@ int trpl_loglik_moments_dev(const double *X, int64_t S, int32_t C, const double 
 {
     if (S > 0 && !esum) return api_fail(TRPL_ERR_ARG, "esum must not be NULL");
     if (S == 0) flags &= ~(uint32_t)TRPL_FLAG_MOMENTS;            // nothing is launched; the common checks still run
-    return loglik_dev_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
-                           obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, stream, esum);
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = plT; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h; k.esum = esum;
+    return loglik_dev(k, (hipStream_t)stream);
 }
 
 int trpl_loglik_moments(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
@@ -1015,8 +1093,12 @@ int trpl_loglik_moments(const double *X, int64_t S, int32_t C, const double *len
     if (S > 0 && !esum) return api_fail(TRPL_ERR_ARG, "esum must not be NULL");
     if (int rc = check_interp(obs_hi, obs_dx, obs_h, plT)) return rc;
     if (S == 0) flags &= ~(uint32_t)TRPL_FLAG_MOMENTS;
-    return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
-                            obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds, esum);
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = plT; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h; k.esum = esum;
+    return loglik_host(k, device, seconds);
 }
 
 /* ------------------------------------------------------------------ fused loglik with early stop (probs.py:5-18 bval_cutoff) */
@@ -1026,9 +1108,12 @@ int trpl_loglik_cut_dev(const double *X, int64_t S, int32_t C, const double *len
                         const int64_t *n_obs, double sse_cut, double *P, double *sse, int32_t *cut_col, int32_t *status,
                         int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream)
 {
-    return loglik_dev_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
-                           obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, stream, nullptr, nullptr, &sse_cut,
-                           cut_col);
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = plT; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h; k.sse_cut = &sse_cut; k.cut_col = cut_col;
+    return loglik_dev(k, (hipStream_t)stream);
 }
 
 int trpl_loglik_cut(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
@@ -1039,9 +1124,12 @@ int trpl_loglik_cut(const double *X, int64_t S, int32_t C, const double *lengths
 {
     ProfRange range("trpl_loglik_cut (pvSim + fastlog + prob with early stop, fused)");
     if (int rc = check_interp(obs_hi, obs_dx, obs_h, plT)) return rc;
-    return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
-                            obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds, nullptr, nullptr,
-                            &sse_cut, cut_col);
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = plT; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h; k.sse_cut = &sse_cut; k.cut_col = cut_col;
+    return loglik_host(k, device, seconds);
 }
 
 /* ------------------------------------------------------------------ uncertainty-weighted fused loglik (probs.py:40) */
@@ -1053,8 +1141,12 @@ int trpl_loglik_weighted_dev(const double *X, int64_t S, int32_t C, const double
 {
     if (S > 0 && (!esum || !wts)) return api_fail(TRPL_ERR_ARG, "esum and wts must not be NULL");
     if (S == 0) flags &= ~(uint32_t)TRPL_FLAG_WEIGHTED;           // nothing is launched; the common checks still run
-    return loglik_dev_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
-                           obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, stream, esum, S > 0 ? wts : nullptr);
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = plT; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h; k.esum = esum; k.wts = S > 0 ? wts : nullptr;
+    return loglik_dev(k, (hipStream_t)stream);
 }
 
 int trpl_loglik_weighted(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
@@ -1071,123 +1163,60 @@ int trpl_loglik_weighted(const double *X, int64_t S, int32_t C, const double *le
         for (int c = 0; c < C; c++)
             if (n_obs[c] >= 1 && n_obs[c] <= obs_ld)
                 if (int rc = check_weights(wts + (int64_t)c * obs_ld, n_obs[c], c)) return rc;
-    return loglik_host_impl(X, S, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
-                            obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, device, seconds, esum,
-                            S > 0 ? wts : nullptr);
-}
-
-static int check_mag_w(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C, const double *P, bool need_P)
-{
-    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
-    if (C < 1 || C > TRPL_MAG_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAG_MAX_CURVES);
-    if (!wsum) return api_fail(TRPL_ERR_ARG, "wsum must not be NULL");
-    for (int c = 0; c < C; c++)
-        if (!(wsum[c] >= 0.0) || !(wsum[c] < INFINITY)) return api_fail(TRPL_ERR_ARG, "wsum[%d]=%g must be finite and >= 0", c, wsum[c]);
-    if (S > 0 && (!sse || !esum || (need_P && !P))) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
-    return TRPL_OK;
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = plT; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h; k.esum = esum; k.wts = S > 0 ? wts : nullptr;
+    return loglik_host(k, device, seconds);
 }
 
 int trpl_mag_grid_w(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C, const double *offsets,
                     int64_t M, double *P)
 {
-    if (M < 0) return api_fail(TRPL_ERR_ARG, "M must be >= 0");
-    if (int rc = check_mag_w(sse, esum, wsum, S, C, P, M > 0)) return rc;
-    if (S == 0 || M == 0) return TRPL_OK;
-    if (!offsets) return api_fail(TRPL_ERR_ARG, "offsets must not be NULL");
-    trpl::mag_grid_host_w(sse, esum, wsum, S, C, offsets, M, P);
-    return TRPL_OK;
+    return mag_grid(sse, esum, wsum, S, C, offsets, M, P, false, nullptr);
 }
 
 int trpl_mag_grid_w_dev(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C, const double *offsets,
                         int64_t M, double *P, void *stream)
 {
-    if (M < 0) return api_fail(TRPL_ERR_ARG, "M must be >= 0");
-    if (int rc = check_mag_w(sse, esum, wsum, S, C, P, M > 0)) return rc;
-    if (S == 0 || M == 0) return TRPL_OK;
-    if (!offsets) return api_fail(TRPL_ERR_ARG, "offsets must not be NULL");
-    hipError_t e = trpl::launch_mag_grid_w(sse, esum, wsum, S, C, offsets, M, P, (hipStream_t)stream);
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mag_grid_w launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    return mag_grid(sse, esum, wsum, S, C, offsets, M, P, true, stream);
 }
 
 int trpl_mag_profile_w(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C, uint32_t flags,
                        double *best, double *P)
 {
-    if (flags & ~(uint32_t)TRPL_MAG_PER_CURVE) return api_fail(TRPL_ERR_ARG, "trpl_mag_profile_w: unknown flag bits 0x%x", flags);
-    if (int rc = check_mag_w(sse, esum, wsum, S, C, P, true)) return rc;
-    if (S == 0) return TRPL_OK;
-    if (!best) return api_fail(TRPL_ERR_ARG, "best must not be NULL");
-    trpl::mag_profile_host_w(sse, esum, wsum, S, C, (flags & TRPL_MAG_PER_CURVE) != 0, best, P);
-    return TRPL_OK;
+    return mag_profile(sse, esum, wsum, S, C, flags, best, P, false, nullptr);
 }
 
 int trpl_mag_profile_w_dev(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C, uint32_t flags,
                            double *best, double *P, void *stream)
 {
-    if (flags & ~(uint32_t)TRPL_MAG_PER_CURVE) return api_fail(TRPL_ERR_ARG, "trpl_mag_profile_w: unknown flag bits 0x%x", flags);
-    if (int rc = check_mag_w(sse, esum, wsum, S, C, P, true)) return rc;
-    if (S == 0) return TRPL_OK;
-    if (!best) return api_fail(TRPL_ERR_ARG, "best must not be NULL");
-    hipError_t e = trpl::launch_mag_profile_w(sse, esum, wsum, S, C, (flags & TRPL_MAG_PER_CURVE) != 0, best, P, (hipStream_t)stream);
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mag_profile_w launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
-}
-
-static int check_mag(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C, const double *P, bool need_P)
-{
-    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
-    if (C < 1 || C > TRPL_MAG_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAG_MAX_CURVES);
-    if (!n_obs) return api_fail(TRPL_ERR_ARG, "n_obs must not be NULL");
-    for (int c = 0; c < C; c++)
-        if (n_obs[c] < 1) return api_fail(TRPL_ERR_ARG, "n_obs[%d]=%lld must be >= 1", c, (long long)n_obs[c]);
-    if (S > 0 && (!sse || !esum || (need_P && !P))) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
-    return TRPL_OK;
+    return mag_profile(sse, esum, wsum, S, C, flags, best, P, true, stream);
 }
 
 int trpl_mag_grid(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C, const double *offsets,
                   int64_t M, double *P)
 {
-    if (M < 0) return api_fail(TRPL_ERR_ARG, "M must be >= 0");
-    if (int rc = check_mag(sse, esum, n_obs, S, C, P, M > 0)) return rc;
-    if (S == 0 || M == 0) return TRPL_OK;
-    if (!offsets) return api_fail(TRPL_ERR_ARG, "offsets must not be NULL");
-    trpl::mag_grid_host(sse, esum, n_obs, S, C, offsets, M, P);
-    return TRPL_OK;
+    return mag_grid(sse, esum, n_obs, S, C, offsets, M, P, false, nullptr);
 }
 
 int trpl_mag_grid_dev(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C, const double *offsets,
                       int64_t M, double *P, void *stream)
 {
-    if (M < 0) return api_fail(TRPL_ERR_ARG, "M must be >= 0");
-    if (int rc = check_mag(sse, esum, n_obs, S, C, P, M > 0)) return rc;
-    if (S == 0 || M == 0) return TRPL_OK;
-    if (!offsets) return api_fail(TRPL_ERR_ARG, "offsets must not be NULL");
-    hipError_t e = trpl::launch_mag_grid(sse, esum, n_obs, S, C, offsets, M, P, (hipStream_t)stream);
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mag_grid launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    return mag_grid(sse, esum, n_obs, S, C, offsets, M, P, true, stream);
 }
 
 int trpl_mag_profile(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C, uint32_t flags,
                      double *best, double *P)
 {
-    if (flags & ~(uint32_t)TRPL_MAG_PER_CURVE) return api_fail(TRPL_ERR_ARG, "trpl_mag_profile: unknown flag bits 0x%x", flags);
-    if (int rc = check_mag(sse, esum, n_obs, S, C, P, true)) return rc;
-    if (S == 0) return TRPL_OK;
-    if (!best) return api_fail(TRPL_ERR_ARG, "best must not be NULL");
-    trpl::mag_profile_host(sse, esum, n_obs, S, C, (flags & TRPL_MAG_PER_CURVE) != 0, best, P);
-    return TRPL_OK;
+    return mag_profile(sse, esum, n_obs, S, C, flags, best, P, false, nullptr);
 }
 
 int trpl_mag_profile_dev(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int32_t C, uint32_t flags,
                          double *best, double *P, void *stream)
 {
-    if (flags & ~(uint32_t)TRPL_MAG_PER_CURVE) return api_fail(TRPL_ERR_ARG, "trpl_mag_profile: unknown flag bits 0x%x", flags);
-    if (int rc = check_mag(sse, esum, n_obs, S, C, P, true)) return rc;
-    if (S == 0) return TRPL_OK;
-    if (!best) return api_fail(TRPL_ERR_ARG, "best must not be NULL");
-    hipError_t e = trpl::launch_mag_profile(sse, esum, n_obs, S, C, (flags & TRPL_MAG_PER_CURVE) != 0, best, P, (hipStream_t)stream);
-    if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "mag_profile launch: %s", hipGetErrorString(e));
-    return TRPL_OK;
+    return mag_profile(sse, esum, n_obs, S, C, flags, best, P, true, stream);
 }
 
 /* ------------------------------------------------------------------ host interpolation --- */

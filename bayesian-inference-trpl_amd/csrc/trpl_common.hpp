@@ -127,15 +127,7 @@ hipError_t launch_sse_accumulate_w(double *P, const void *pl, int elem_bytes, in
 // the magnitude-offset grid / profile from the moments (trpl_mag_grid, trpl_mag_profile): host forms and their kernels
 constexpr int kMagMaxCurves = 64;          // TRPL_MAG_MAX_CURVES
 constexpr int kMagChunk = 256;             // offsets per launch (kernel arguments)
-void mag_grid_host(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, const double *offsets,
-                   int64_t M, double *P);
-void mag_profile_host(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, bool per_curve,
-                      double *best, double *P);
-hipError_t launch_mag_grid(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C,
-                           const double *offsets, int64_t M, double *P, hipStream_t stream);
-hipError_t launch_mag_profile(const double *sse, const double *esum, const int64_t *n_obs, int64_t S, int C, bool per_curve,
-                              double *best, double *P, hipStream_t stream);
-// the weighted forms (trpl_mag_grid_w, trpl_mag_profile_w): wsum[c] = sum_i w_ci in place of n_obs[c]
+// wsum[c]: the quadratic coefficient of curve c, (double)n_obs[c] for trpl_mag_grid / trpl_mag_profile, sum_i w_ci for the _w forms
 void mag_grid_host_w(const double *sse, const double *esum, const double *wsum, int64_t S, int C, const double *offsets,
                      int64_t M, double *P);
 void mag_profile_host_w(const double *sse, const double *esum, const double *wsum, int64_t S, int C, bool per_curve,

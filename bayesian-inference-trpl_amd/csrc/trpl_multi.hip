@@ -16,24 +16,6 @@
 
 using namespace trpl;
 
-namespace {
-
-// one shard's fused solve on the current device: trpl_loglik_dev / trpl_loglik_obs_dev
-int shard_loglik(const double *X, int64_t n, int32_t C, const double *lengths_nm, double time_ns, int32_t L, int64_t T,
-                 int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN, const double *obs,
-                 const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t obs_ld, const int64_t *n_obs,
-                 double *P, double *sse, int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags,
-                 hipStream_t st)
-{
-    if (obs_hi)
-        return trpl_loglik_obs_dev(X, n, C, lengths_nm, time_ns, L, T, tol_exp, max_iter, dN, obs, obs_hi, obs_dx, obs_h,
-                                   obs_ld, n_obs, P, sse, status, iters_total, floor_col, flags, st);
-    return trpl_loglik_dev(X, n, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN, obs, obs_ld, n_obs, P, sse,
-                           status, iters_total, floor_col, flags, st);
-}
-
-}  // namespace
-
 extern "C" {
 
 int trpl_shard_bounds(int64_t S, int32_t n_shards, int32_t shard, int64_t *lo, int64_t *hi)
@@ -55,20 +37,10 @@ int64_t trpl_shard_of(int64_t S, int32_t n_shards, int64_t s)
 }  // extern "C" (reopened below)
 
 namespace {
-struct Shard {                       // one device's share of the samples; released on its own device
+struct Shard : Staged {              // one device's share of the samples, staged; released on its own device
     int dev = 0;
     int64_t lo = 0, hi = 0;
-    hipStream_t st = nullptr;
-    DevBuf X, dN, obs, ohi, odx, oh, P, sse, status, iters, floorc;
-    ~Shard()
-    {
-        (void)hipSetDevice(dev);
-        for (DevBuf *b : {&X, &dN, &obs, &ohi, &odx, &oh, &P, &sse, &status, &iters, &floorc}) b->release();   // stream-ordered frees
-        if (st) {
-            (void)hipStreamSynchronize(st);
-            (void)hipStreamDestroy(st);
-        }
-    }
+    ~Shard() { (void)hipSetDevice(dev); }            // runs before Staged's members go: the frees, the drain, the stream
 };
 }  // namespace
 
@@ -82,10 +54,11 @@ int trpl_loglik_multi(const double *X, int64_t S, int32_t C, const double *lengt
                       int32_t *floor_col, uint32_t flags, const int32_t *devices, int32_t n_devices, double *seconds)
 {
     ProfRange range("trpl_loglik_multi (sample shards over the visible devices)");
+    LoglikCall call;                                 // what every shard shares; X, S and the outputs are the shard's
+    call.C = C; call.lengths_nm = lengths_nm; call.time_ns = time_ns; call.L = L; call.T = T; call.plT = plT; call.tol_exp = tol_exp;
+    call.max_iter = max_iter; call.obs_ld = obs_ld; call.n_obs = n_obs; call.S = S;
     if (int rc = no_moments_flag(flags)) return rc;
-    if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
-    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
-    if (C < 1 || C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAX_CURVES);
+    if (int rc = check_batch(call)) return rc;
     if (seconds) *seconds = 0.0;
     if (!X || !lengths_nm || !dN || !obs || !n_obs || !P) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
     if (obs_ld < 1) return api_fail(TRPL_ERR_ARG, "obs_ld must be >= 1");
@@ -107,6 +80,7 @@ int trpl_loglik_multi(const double *X, int64_t S, int32_t C, const double *lengt
         if (int rc = check_brackets(obs_hi, obs_dx, obs_h, C, obs_ld, n_obs, T)) return rc;
     }
     if (S == 0) return TRPL_OK;
+    call.flags = flags;
     int prev = 0;
     (void)hipGetDevice(&prev);
 
@@ -119,64 +93,35 @@ int trpl_loglik_multi(const double *X, int64_t S, int32_t C, const double *lengt
         Shard &q = sh[r];
         q.dev = devices ? devices[r] : r;
         (void)trpl_shard_bounds(S, n_devices, r, &q.lo, &q.hi);
-        const int64_t n = q.hi - q.lo;
+        const size_t n = (size_t)(q.hi - q.lo);
         if (n == 0) continue;
-        const size_t nsys = (size_t)n * C;
-        rc = [&]() -> int {
-            HIP_TRY(hipSetDevice(q.dev));
-            HIP_TRY(hipStreamCreateWithFlags(&q.st, hipStreamNonBlocking));
-            HIP_TRY(q.X.alloc((size_t)n * 13 * 8, q.st)); HIP_TRY(q.dN.alloc((size_t)C * L * 8, q.st)); HIP_TRY(q.obs.alloc(nobs * 8, q.st));
-            HIP_TRY(q.P.alloc((size_t)n * 8, q.st)); HIP_TRY(q.sse.alloc(nsys * 8, q.st)); HIP_TRY(q.status.alloc(nsys * 4, q.st));
-            HIP_TRY(q.iters.alloc(nsys * 8, q.st));
-            if (floor_col) HIP_TRY(q.floorc.alloc(nsys * 4, q.st));
-            HIP_TRY(hipMemcpyAsync(q.X.p, X + q.lo * 13, (size_t)n * 13 * 8, hipMemcpyHostToDevice, q.st));
-            HIP_TRY(hipMemcpyAsync(q.dN.p, dN, (size_t)C * L * 8, hipMemcpyHostToDevice, q.st));
-            HIP_TRY(hipMemcpyAsync(q.obs.p, obs, nobs * 8, hipMemcpyHostToDevice, q.st));
-            HIP_TRY(hipMemcpyAsync(q.P.p, P + q.lo, (size_t)n * 8, hipMemcpyHostToDevice, q.st));
-            if (interp) {
-                HIP_TRY(q.ohi.alloc(nobs * 4, q.st)); HIP_TRY(q.odx.alloc(nobs * 8, q.st)); HIP_TRY(q.oh.alloc(nobs * 8, q.st));
-                HIP_TRY(hipMemcpyAsync(q.ohi.p, obs_hi, nobs * 4, hipMemcpyHostToDevice, q.st));
-                HIP_TRY(hipMemcpyAsync(q.odx.p, obs_dx, nobs * 8, hipMemcpyHostToDevice, q.st));
-                HIP_TRY(hipMemcpyAsync(q.oh.p, obs_h, nobs * 8, hipMemcpyHostToDevice, q.st));
-            }
-            return shard_loglik(q.X.as<double>(), n, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, q.dN.as<double>(),
-                                q.obs.as<double>(), interp ? q.ohi.as<int32_t>() : nullptr,
-                                interp ? q.odx.as<double>() : nullptr, interp ? q.oh.as<double>() : nullptr, obs_ld,
-                                n_obs, q.P.as<double>(), q.sse.as<double>(), q.status.as<int32_t>(),
-                                q.iters.as<int64_t>(), q.floorc.as<int32_t>(), flags, q.st);
-        }();
+        if ((rc = q.open(q.dev)) != TRPL_OK) break;
+        // per-curve outputs are [C][S] on the host and [C][n] on the device: one strided copy each.  sse, status and iters_total are
+        // the _dev form's whether the caller takes them or not, floor_col only on request
+        auto mine = [&](auto *host) { return host ? host + q.lo : nullptr; };
+        LoglikCall k = call;
+        k.S = (int64_t)n;
+        k.X = q.in(X + q.lo * 13, n * 13); k.dN = q.in(dN, (size_t)C * L); k.obs = q.in(obs, nobs);
+        if (interp) { k.obs_hi = q.in(obs_hi, nobs); k.obs_dx = q.in(obs_dx, nobs); k.obs_h = q.in(obs_h, nobs); }
+        k.P = q.inout(P + q.lo, n);
+        k.sse = q.out(mine(sse), (size_t)S, n, (size_t)C);
+        k.status = q.out(mine(status), (size_t)S, n, (size_t)C);
+        k.iters_total = q.out(mine(iters_total), (size_t)S, n, (size_t)C);
+        if (floor_col) k.floor_col = q.out(floor_col + q.lo, (size_t)S, n, (size_t)C);
+        rc = q.rc ? q.rc : loglik_dev(k, q.stream());            // the sticky error, not begin(): nothing waits for the uploads
     }
     // only now the copies back: a device-to-host copy into pageable memory blocks the calling thread until
     // the shard's kernel has finished, so issuing it inside the loop above would run the devices one
     // after the other
     for (int r = 0; r < n_devices && rc == TRPL_OK; r++) {
-        Shard &q = sh[r];
-        const int64_t n = q.hi - q.lo;
-        if (n == 0 || !q.st) continue;
-        rc = [&]() -> int {
-            HIP_TRY(hipSetDevice(q.dev));
-            HIP_TRY(hipMemcpyAsync(P + q.lo, q.P.p, (size_t)n * 8, hipMemcpyDeviceToHost, q.st));
-            // per-curve outputs are [C][S] on the host and [C][n] on the device: one strided copy each
-            if (sse)
-                HIP_TRY(hipMemcpy2DAsync(sse + q.lo, (size_t)S * 8, q.sse.p, (size_t)n * 8, (size_t)n * 8, C,
-                                         hipMemcpyDeviceToHost, q.st));
-            if (status)
-                HIP_TRY(hipMemcpy2DAsync(status + q.lo, (size_t)S * 4, q.status.p, (size_t)n * 4, (size_t)n * 4, C,
-                                         hipMemcpyDeviceToHost, q.st));
-            if (iters_total)
-                HIP_TRY(hipMemcpy2DAsync(iters_total + q.lo, (size_t)S * 8, q.iters.p, (size_t)n * 8, (size_t)n * 8, C,
-                                         hipMemcpyDeviceToHost, q.st));
-            if (floor_col)
-                HIP_TRY(hipMemcpy2DAsync(floor_col + q.lo, (size_t)S * 4, q.floorc.p, (size_t)n * 4, (size_t)n * 4, C,
-                                         hipMemcpyDeviceToHost, q.st));
-            return TRPL_OK;
-        }();
+        if (!sh[r].stream()) continue;
+        if ((rc = sh[r].ok(hipSetDevice(sh[r].dev), "hipSetDevice")) == TRPL_OK) rc = sh[r].finish(nullptr);
     }
     // drain every stream that was started, also after a failure (the host buffers are borrowed)
     for (int r = 0; r < n_devices; r++) {
-        if (!sh[r].st) continue;
+        if (!sh[r].stream()) continue;
         hipError_t e = hipSetDevice(sh[r].dev);
-        if (e == hipSuccess) e = hipStreamSynchronize(sh[r].st);
+        if (e == hipSuccess) e = hipStreamSynchronize(sh[r].stream());
         if (e != hipSuccess && rc == TRPL_OK)
             rc = api_fail(TRPL_ERR_HIP, "device %d (shard %d): %s", sh[r].dev, r, hipGetErrorString(e));
     }
@@ -400,16 +345,17 @@ int trpl_loglik_multi_dev(trpl_multi_t *h, const double *const *X, int64_t S, in
                           int32_t *const *floor_col, uint32_t flags)
 {
     if (!h) return api_fail(TRPL_ERR_ARG, "handle must not be NULL");
-    if (int rc = check_grid(L, T, plT, max_iter, time_ns)) return rc;
-    if (S < 0) return api_fail(TRPL_ERR_ARG, "S must be >= 0");
-    if (C < 1 || C > TRPL_MAX_CURVES) return api_fail(TRPL_ERR_ARG, "C=%d must be in [1, %d]", C, TRPL_MAX_CURVES);
+    LoglikCall call;                                 // what every rank shares; X, S, the tables and the outputs are the rank's
+    call.C = C; call.lengths_nm = lengths_nm; call.time_ns = time_ns; call.L = L; call.T = T; call.plT = plT; call.tol_exp = tol_exp;
+    call.max_iter = max_iter; call.obs_ld = obs_ld; call.n_obs = n_obs; call.S = S;
+    if (int rc = check_batch(call)) return rc;
     if (!X || !lengths_nm || !dN || !obs || !n_obs || !P_full) return api_fail(TRPL_ERR_ARG, "NULL pointer argument");
     const bool interp = obs_hi || obs_dx || obs_h;
-    if (interp && !(obs_hi && obs_dx && obs_h)) return api_fail(TRPL_ERR_ARG, "obs_hi, obs_dx and obs_h go together");
-    if (interp && plT != 1) return api_fail(TRPL_ERR_ARG, "off-grid observations need plT = 1");
+    if (int rc = check_interp(obs_hi, obs_dx, obs_h, plT)) return rc;
     if (int rc = no_moments_flag(flags)) return rc;
     if (int rc = pin_sharded_batch(flags, S, C, L, T, plT, interp, n_obs, obs_ld)) return rc;
     if (S == 0) return TRPL_OK;
+    call.flags = flags;
     const int n = h->n;
     for (int r = 0; r < n; r++)                          // every rank receives the gathered vector, also one whose shard is empty
         if (!P_full[r]) return api_fail(TRPL_ERR_ARG, "P_full[%d] must not be NULL", r);
@@ -443,12 +389,13 @@ int trpl_loglik_multi_dev(trpl_multi_t *h, const double *const *X, int64_t S, in
             double *sse_r = sse ? sse[r] : nullptr;
             DevBuf tmp;                              // the fused call needs somewhere to put the per-curve sums
             if (!sse_r) { HIP_TRY(tmp.alloc((size_t)nr * C * 8, h->st[r])); sse_r = tmp.as<double>(); }
-            if (int e = shard_loglik(X[r], nr, C, lengths_nm, time_ns, L, T, plT, tol_exp, max_iter, dN[r], obs[r],
-                                     interp ? obs_hi[r] : nullptr, interp ? obs_dx[r] : nullptr,
-                                     interp ? obs_h[r] : nullptr, obs_ld, n_obs, h->send[r], sse_r,
-                                     status ? status[r] : nullptr, iters_total ? iters_total[r] : nullptr,
-                                     floor_col ? floor_col[r] : nullptr, flags, h->st[r]))
-                return e;
+            LoglikCall k = call;
+            k.S = nr; k.X = X[r]; k.dN = dN[r]; k.obs = obs[r]; k.P = h->send[r]; k.sse = sse_r;
+            if (interp) { k.obs_hi = obs_hi[r]; k.obs_dx = obs_dx[r]; k.obs_h = obs_h[r]; }
+            k.status = status ? status[r] : nullptr;
+            k.iters_total = iters_total ? iters_total[r] : nullptr;
+            k.floor_col = floor_col ? floor_col[r] : nullptr;
+            if (int e = loglik_dev(k, h->st[r])) return e;
         }
         // ONE collective: all-gather of `widest` fp64 per rank (RCCL over xGMI), straight into P_full when the
         // shards are equal, through the padded scratch + an unpadding pass otherwise

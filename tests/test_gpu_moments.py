@@ -378,3 +378,48 @@ def test_bayes_with_a_mag_grid_equals_plain_runs_at_the_shifted_offsets(gpu, gol
         with pytest.raises(ValueError) as ei:
             run(g["minX"], g["maxX"], mag_grid=offsets, **bad)
         assert word in str(ei.value)
+
+
+# ------------------------------------------------------------------------------------------------------- the eight mag exports
+@pytest.mark.parametrize("C", [1, 2, 64])
+@pytest.mark.parametrize("S", [1, 257])
+def test_mag_exports_route_counts_and_weight_sums_to_the_same_arithmetic(gpu, S, C):
+    """trpl_mag_grid / trpl_mag_profile: the host form, the _dev form, and the _w forms given wsum = n_obs.astype(float64) return
+    the same bits -- the grid at M = 1, 256 and 257 (the second launch starts at offset 256), the profile with and without
+    TRPL_MAG_PER_CURVE.  The kernels themselves are pinned by test_gpu_likelihood_instances.py; this pins that each of the eight
+    exports reaches the arithmetic of its name with the per-curve vector converted exactly."""
+    import torch
+
+    import likelihood_ref as R
+    a, lib = gpu._abi, gpu._abi.lib()
+    m = R.mag_moments(S, C, False)
+    vec = {"": m["n"], "_w": m["n"].astype(np.float64)}
+    assert m["n"].dtype == np.int64
+    dsse, desum = torch.from_numpy(m["sse"]).cuda(), torch.from_numpy(m["esum"]).cuda()
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def run(name, sfx, on_device, mid, outs):
+        """outs: host arrays holding the start values; returns what the export leaves in them."""
+        got = [o.copy() for o in outs]
+        if on_device:
+            dev = [torch.from_numpy(o).cuda() for o in got]
+            a.check(getattr(lib, "%s%s_dev" % (name, sfx))(dsse.data_ptr(), desum.data_ptr(), a.ptr(vec[sfx]), S, C, *mid,
+                                                           *[d.data_ptr() for d in dev], stream))
+            torch.cuda.synchronize()
+            return [d.cpu().numpy() for d in dev]
+        a.check(getattr(lib, name + sfx)(a.ptr(m["sse"]), a.ptr(m["esum"]), a.ptr(vec[sfx]), S, C, *mid, *[a.ptr(o) for o in got]))
+        return got
+
+    forms = [(sfx, dev) for sfx in ("", "_w") for dev in (False, True)]
+    for M in (1, 256, 257):
+        offsets = R.mag_offsets(M)
+        res = [run("trpl_mag_grid", sfx, dev, (a.ptr(offsets), M), [np.tile(m["P0"], (M, 1))]) for sfx, dev in forms]
+        assert S == 1 or not np.array_equal(res[0][0], np.tile(m["P0"], (M, 1)))
+        for r, form in zip(res[1:], forms[1:]):
+            assert np.array_equal(r[0], res[0][0]), (M, form)
+    for per_curve in (False, True):
+        start = [np.full((C, S) if per_curve else S, 5.0), m["P0"]]
+        res = [run("trpl_mag_profile", sfx, dev, (a.MAG_PER_CURVE if per_curve else 0,), start) for sfx, dev in forms]
+        assert S == 1 or not np.array_equal(res[0][1], m["P0"])
+        for r, form in zip(res[1:], forms[1:]):
+            assert np.array_equal(r[0], res[0][0], equal_nan=True) and np.array_equal(r[1], res[0][1]), (per_curve, form)

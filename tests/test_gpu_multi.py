@@ -2,6 +2,7 @@
 trpl_loglik_multi_dev (device-resident, RCCL) on a one-rank communicator and on 2-4 "ranks" of one GPU against tests/mock_rccl,
 sharded = single launch bit for bit across the pair threshold, bench.py's N = 2 control flow as child processes (gloo), the
 rank driver over a one-rank nccl group, stream ordering against torch."""
+import ctypes
 import json
 import os
 import subprocess
@@ -472,3 +473,118 @@ def test_multi_device_call_is_ordered_against_the_callers_torch_stream(gpu):
         torch.cuda.synchronize()
         md.synchronize()
     assert torch.equal(out, want["b"])
+
+
+# ------------------------------------------------------------------ trpl_loglik_multi's staged shards, through the C ABI
+GUARD = 8                                       # sentinel elements on either side of every host output
+TOL_EXP, MAX_ITER = 7, 1000
+
+
+class _Guarded:
+    """A host array pre-filled with `fill`, between two runs of sentinels the call must leave alone."""
+    def __init__(self, shape, dtype, fill):
+        self.sentinel = np.array(-77, dtype=dtype)
+        self.buf = np.full(int(np.prod(shape)) + 2 * GUARD, self.sentinel, dtype=dtype)
+        self.a = self.buf[GUARD:-GUARD].reshape(shape)
+        self.a[...] = fill
+
+    def intact(self):
+        return (self.buf[:GUARD] == self.sentinel).all() and (self.buf[-GUARD:] == self.sentinel).all()
+
+
+def _shard_case(gpu, S, C, offgrid):
+    w = gpu.workloads
+    ini3, lens3 = w.power_scan(128)
+    reps = -(-C // 3)
+    ini = np.ascontiguousarray(np.tile(ini3, (reps, 1))[:C])
+    lens = np.ascontiguousarray(np.tile(lens3, reps)[:C] * (1.0 + 0.01 * np.arange(C)))
+    T = 40
+    if offgrid:
+        n = 5
+        obs = np.full((C, n), 19.0) + 0.1 * np.arange(C)[:, None]
+        hi = np.tile(np.array([2, 3, 5, 7, 9], dtype=np.int32), (C, 1))
+        brackets = (hi, np.full((C, n), 0.01), np.full((C, n), 0.025))
+    else:
+        n = T + 1
+        obs = np.tile(20.0 - 0.01 * np.arange(n), (C, 1)) + 0.1 * np.arange(C)[:, None]
+        brackets = None
+    return dict(X=w.samples(S, seed=17), S=S, C=C, ini=ini, lens=lens, T=T, Time=T * DT, obs=np.ascontiguousarray(obs), n=n,
+                n_obs=np.full(C, n, dtype=np.int64), brackets=brackets, P0=np.linspace(-3.0, 2.0, S))
+
+
+def _outputs(S, C, every):
+    out = dict(P=_Guarded(S, np.float64, 0.0))
+    if every:
+        out.update(sse=_Guarded((C, S), np.float64, -5.0), status=_Guarded((C, S), np.int32, -5),
+                   iters_total=_Guarded((C, S), np.int64, -5), floor_col=_Guarded((C, S), np.int32, -5))
+    return out
+
+
+def _call_loglik(gpu, c, out, devices=None):
+    """trpl_loglik / trpl_loglik_obs on device 0, or trpl_loglik_multi over `devices`; returns (rc, seconds)."""
+    a, lib = gpu._abi, gpu._abi.lib()
+    out["P"].a[...] = c["P0"]
+    o = [a.ptr(out[k].a) if k in out else None for k in ("P", "sse", "status", "iters_total", "floor_col")]
+    seconds = ctypes.c_double(5.0)
+    head = (a.ptr(c["X"]), c["S"], c["C"], a.ptr(c["lens"]), c["Time"], 128, c["T"])
+    br = [a.ptr(b) for b in c["brackets"]] if c["brackets"] else [None, None, None]
+    if devices is not None:
+        dev = np.array(devices, dtype=np.int32)
+        rc = lib.trpl_loglik_multi(*head, 1, TOL_EXP, MAX_ITER, a.ptr(c["ini"]), a.ptr(c["obs"]), *br, c["n"], a.ptr(c["n_obs"]),
+                                   *o, 0, a.ptr(dev), len(dev), ctypes.byref(seconds))
+    elif c["brackets"]:
+        rc = lib.trpl_loglik_obs(*head, TOL_EXP, MAX_ITER, a.ptr(c["ini"]), a.ptr(c["obs"]), *br, c["n"], a.ptr(c["n_obs"]), *o, 0,
+                                 0, ctypes.byref(seconds))
+    else:
+        rc = lib.trpl_loglik(*head, 1, TOL_EXP, MAX_ITER, a.ptr(c["ini"]), a.ptr(c["obs"]), c["n"], a.ptr(c["n_obs"]), *o, 0, 0,
+                             ctypes.byref(seconds))
+    return rc, seconds.value
+
+
+_single = {}
+
+
+def _reference(gpu, S, C, offgrid):
+    """The single-device call's outputs, computed once per case and left unchanged."""
+    key = (S, C, offgrid)
+    if key not in _single:
+        c, out = _shard_case(gpu, S, C, offgrid), _outputs(S, C, True)
+        rc, _ = _call_loglik(gpu, c, out)
+        assert rc == gpu._abi.OK, gpu._abi.lib().trpl_last_error()
+        assert (out["iters_total"].a > 0).all() and (out["sse"].a != -5.0).all() and (out["floor_col"].a != -5).all()
+        for v in out.values():
+            v.a.setflags(write=False)
+        _single[key] = c, out
+    return _single[key]
+
+
+@pytest.mark.parametrize("offgrid", [False, True], ids=["ongrid", "offgrid"])
+@pytest.mark.parametrize("S,C,devices", [(7, 3, [0, 0, 0]), (2, 3, [0, 0, 0, 0]), (5, 17, [0, 0])],
+                         ids=["shards-3-2-2", "empty-shards", "two-curve-groups"])
+def test_multi_staged_shards_equal_the_single_device_call_bit_for_bit(gpu, S, C, devices, offgrid):
+    """trpl_loglik_multi, one staged shard per entry of `devices`, against trpl_loglik / trpl_loglik_obs on the same arrays: S = 7
+    over three shards (3 / 2 / 2: every pitched copy back lands at its own non-zero column offset of the [C][S] rows), S = 2 over
+    four (two empty shards), and C = 17 = kMaxCurves + 1 over two, where each shard's direct call launches two curve groups.  With
+    every output requested, and with every optional one NULL.  The host arrays are pre-filled and stand between sentinels."""
+    A = gpu._abi
+    c, want = _reference(gpu, S, C, offgrid)
+    for every in (True, False):
+        out = _outputs(S, C, every)
+        rc, seconds = _call_loglik(gpu, c, out, devices)
+        assert rc == A.OK, A.lib().trpl_last_error()
+        assert seconds > 0.0
+        for k, v in out.items():
+            assert v.intact(), k
+            assert np.array_equal(v.a, want[k].a), (k, every)
+
+
+def test_multi_seconds_is_zero_for_a_refused_call_and_for_an_empty_batch(gpu):
+    A = gpu._abi
+    c, _ = _reference(gpu, 7, 3, False)
+    out = _outputs(7, 3, True)
+    rc, seconds = _call_loglik(gpu, c, out, [0, 99])
+    assert rc == A.ERR_ARG and b"out of range" in A.lib().trpl_last_error() and seconds == 0.0
+    assert np.array_equal(out["P"].a, c["P0"]) and (out["sse"].a == -5.0).all()
+    rc, seconds = _call_loglik(gpu, dict(c, S=0), out, [0, 0])
+    assert rc == A.OK and seconds == 0.0
+    assert np.array_equal(out["P"].a, c["P0"]) and (out["sse"].a == -5.0).all() and all(v.intact() for v in out.values())
