@@ -75,6 +75,7 @@ CORNER_PRIMARY, CORNER_MAX_COLS, CORNER_MAX_BINS = 13, 19, 128
 (COL_N0, COL_P0, COL_MU_N, COL_MU_P, COL_B, COL_SF, COL_SB, COL_CN, COL_CP, COL_TAU_N, COL_TAU_P, COL_LAMBDA, COL_MAG,
  COL_TAU_EFF, COL_TAU_RAD, COL_S_SUM, COL_MU_EFF, COL_EPSILON, COL_TAU_SUM) = range(19)
 REFINE_MAX_DIMS, REFINE_MAX_PARENTS = 16, 1 << 20      # TRPL_REFINE_MAX_DIMS, TRPL_REFINE_MAX_PARENTS
+MCMC_FOLD = 0x10              # TRPL_MCMC_FOLD: trpl_mcmc_propose reflects a proposal back at the faces of the unit cube
 
 
 class TrplError(RuntimeError):

@@ -5,7 +5,10 @@
 //       refine_common.hpp) with the counter's third word moved to 0x100 + j: call j < 8 gives xi[2j], xi[2j + 1], call 8 the two
 //       partner uniforms.  With partners (differential evolution, ter Braak 2006): u'_d = (u_d + gamma (pa_d - pb_d)) + scale_d (2
 //       xi_d - 1); without (random walk): u'_d = u_d + scale_d (2 xi_d - 1).  inside = every u'_d in [0, 1]; X by the sampler's
-//       expressions from u', inside or not, as draw_oriented_kernel forms it.
+//       expressions from u', inside or not, as draw_oriented_kernel forms it.  The body is propose_body<A, FOLD>; propose_kernel
+//       is FOLD = false.
+//   propose_fold_kernel<A>  the same body with FOLD = true (TRPL_MCMC_FOLD, include/trpl.h): each u'_d that fails the range test
+//       is reflected back into [0, 1] before it is stored and turned into X; inside = 0 (a NaN is left), 2 (folded) or 1 (untouched).
 //   accept_kernel<A>      one thread per chain.  xi of counter word 0x109; the chain takes its proposal's U, X and LL when the
 //       proposal is inside, its LLp is neither NaN nor -inf, and the chain stands on a likelihood that is not above -inf, or
 //       d = (LLp - LL) / tf >= 0, or log(xi) < d.
@@ -31,11 +34,20 @@ struct Scale {
     double s[16];
 };
 
-template <int A>
-__global__ void __launch_bounds__(kThreads) propose_kernel(const double *U, const double *partners, int64_t count, int64_t P,
-                                                           double gamma, const Scale sc, int64_t chain0, uint32_t seed_lo,
-                                                           uint32_t seed_hi, uint32_t step, const Box bx, double *Up, double *Xp,
-                                                           int32_t *inside)
+// fold (include/trpl.h, TRPL_MCMC_FOLD): v reflected at the faces of [0, 1] as often as needed.  Called only for a v that failed the
+// range test, so the fmod is off the common path; fmod is exact, the add and the subtract round once each.  NaN and +-inf give NaN.
+__device__ __forceinline__ double fold_outside(double v)
+{
+    double r = fmod(v, 2.0);
+    if (r < 0.0) r = r + 2.0;
+    if (r > 1.0) r = 2.0 - r;
+    return r;
+}
+
+template <int A, bool FOLD>
+__device__ __forceinline__ void propose_body(const double *U, const double *partners, int64_t count, int64_t P, double gamma, const Scale &sc,
+                                             int64_t chain0, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, const Box &bx, double *Up,
+                                             double *Xp, int32_t *inside)
 {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= count) return;
@@ -63,20 +75,48 @@ __global__ void __launch_bounds__(kThreads) propose_kernel(const double *U, cons
 #pragma unroll
         for (int d = 0; d < A; d++) u[d] = u[d] + gamma * (pa[d] - pb[d]);
     }
-    bool in = true;
+    bool in = true, folded = false;
     double *row = Xp + i * bx.ncol;
     put_fixed(bx, row);
 #pragma unroll
     for (int d = 0; d < A; d++) {
         u[d] = u[d] + sc.s[d] * (2.0 * xi[d] - 1.0);
-        in = in && u[d] >= 0.0 && u[d] <= 1.0;                   // a NaN is outside
+        if (FOLD) {
+            if (!(u[d] >= 0.0 && u[d] <= 1.0)) {
+                u[d] = fold_outside(u[d]);
+                folded = true;
+            }
+            in = in && u[d] == u[d];                             // after the fold only a NaN is left outside
+        } else {
+            in = in && u[d] >= 0.0 && u[d] <= 1.0;               // a NaN is outside
+        }
         Up[i * A + d] = u[d];
         const int c = bx.act[d];
         row[c] = column_value(bx, c, u[d]);
     }
     put_overrides(bx, row);
-    inside[i] = in ? 1 : 0;
+    inside[i] = !in ? 0 : folded ? 2 : 1;
 }
+
+#define TRPL_PROPOSE_PARAMS                                                                                                            \
+    const double *U, const double *partners, int64_t count, int64_t P, double gamma, const Scale sc, int64_t chain0, uint32_t seed_lo,  \
+        uint32_t seed_hi, uint32_t step, const Box bx, double *Up, double *Xp, int32_t *inside
+#define TRPL_PROPOSE_ARGS U, partners, count, P, gamma, sc, chain0, seed_lo, seed_hi, step, bx, Up, Xp, inside
+
+template <int A>
+__global__ void __launch_bounds__(kThreads) propose_kernel(TRPL_PROPOSE_PARAMS)
+{
+    propose_body<A, false>(TRPL_PROPOSE_ARGS);
+}
+
+template <int A>
+__global__ void __launch_bounds__(kThreads) propose_fold_kernel(TRPL_PROPOSE_PARAMS)
+{
+    propose_body<A, true>(TRPL_PROPOSE_ARGS);
+}
+
+#undef TRPL_PROPOSE_PARAMS
+#undef TRPL_PROPOSE_ARGS
 
 template <int A>
 __global__ void __launch_bounds__(kThreads) accept_kernel(double *U, double *X, double *LL, const double *Up, const double *Xp,
@@ -133,7 +173,7 @@ static int check_chains(int64_t count, int32_t A, int64_t chain0)
 }
 
 static int check_propose(const void *U, const void *partners, int64_t count, int64_t P, int32_t A, double gamma, const double *scale,
-                         int64_t chain0, const void *Up, const void *Xp, const void *inside, mcmc::Scale &sc)
+                         int64_t chain0, uint32_t flags, const void *Up, const void *Xp, const void *inside, mcmc::Scale &sc)
 {
     if (int rc = check_chains(count, A, chain0)) return rc;
     if (P < 0 || P == 1) return api_fail(TRPL_ERR_ARG, "P=%lld must be 0 (random walk) or >= 2", (long long)P);
@@ -144,6 +184,8 @@ static int check_propose(const void *U, const void *partners, int64_t count, int
     if (!Xp) return api_fail(TRPL_ERR_ARG, "Xp is NULL");
     if (!inside) return api_fail(TRPL_ERR_ARG, "inside is NULL");
     if (!isfinite(gamma)) return api_fail(TRPL_ERR_ARG, "gamma=%g must be finite", gamma);
+    if (flags & ~(uint32_t)(TRPL_BOX_EQUAL_MU | TRPL_BOX_EQUAL_S | TRPL_BOX_EQUAL_AUGER | TRPL_MCMC_FOLD))
+        return api_fail(TRPL_ERR_ARG, "flags=0x%x: only the TRPL_BOX_EQUAL_* bits and TRPL_MCMC_FOLD apply", flags);
     sc = mcmc::Scale();
     for (int d = 0; d < A; d++) {
         if (!(isfinite(scale[d]) && scale[d] >= 0.0)) return api_fail(TRPL_ERR_ARG, "scale[%d]=%g must be finite and >= 0", d, scale[d]);
@@ -191,15 +233,16 @@ int trpl_mcmc_propose_dev(const double *U, const double *partners, int64_t count
                           const int32_t *do_log, uint32_t flags, double *Up, double *Xp, int32_t *inside, void *stream)
 {
     mcmc::Scale sc;
-    if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, Up, Xp, inside, sc)) return rc;
+    if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, flags, Up, Xp, inside, sc)) return rc;
     refine::Box bx;
-    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
+    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags & ~(uint32_t)TRPL_MCMC_FOLD, A, bx)) return rc;
     const dim3 grid(refine_blocks(count)), block(refine::kThreads);
+    const bool fold = (flags & TRPL_MCMC_FOLD) != 0;
     switch (A) {
 #define TRPL_CASE(n)                                                                                                                   \
     case n:                                                                                                                            \
-        hipLaunchKernelGGL(mcmc::propose_kernel<n>, grid, block, 0, (hipStream_t)stream, U, partners, count, P, gamma, sc, chain0,         \
-                           (uint32_t)seed, (uint32_t)(seed >> 32), step, bx, Up, Xp, inside);                                          \
+        hipLaunchKernelGGL(fold ? mcmc::propose_fold_kernel<n> : mcmc::propose_kernel<n>, grid, block, 0, (hipStream_t)stream, U,         \
+                           partners, count, P, gamma, sc, chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step, bx, Up, Xp, inside);    \
         break;
         TRPL_REFINE_DIMS(TRPL_CASE)
 #undef TRPL_CASE
@@ -213,9 +256,9 @@ int trpl_mcmc_propose(const double *U, const double *partners, int64_t count, in
 {
     if (seconds) *seconds = 0.0;
     mcmc::Scale sc;
-    if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, Up, Xp, inside, sc)) return rc;
+    if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, flags, Up, Xp, inside, sc)) return rc;
     refine::Box bx;
-    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags, A, bx)) return rc;
+    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags & ~(uint32_t)TRPL_MCMC_FOLD, A, bx)) return rc;
     Staged sg;
     if (int rc = sg.open(device)) return rc;
     const double *dU = sg.in(U, (size_t)count * A), *dP = sg.in(partners, (size_t)P * A);

@@ -612,7 +612,9 @@ def mcmc_propose_device(U, partners, gamma, scale, chain0, seed, step, minX, max
     """trpl_mcmc_propose_dev: Up (count, A), Xp (count, ncol) f64 and inside (count,) int32 <- one symmetric proposal per chain of U
     (count, A) f64: u' = (u + gamma (pa - pb)) + scale (2 xi - 1) with two distinct rows of partners (P >= 2, A), or the random walk
     u' = u + scale (2 xi - 1) with partners None.  scale (A,) is a host array (a scalar is broadcast); chain0 is the ensemble index of
-    the first row, which keys its Philox stream."""
+    the first row, which keys its Philox stream.  flags: the TRPL_BOX_EQUAL_* bits and _abi.MCMC_FOLD (TRPL_MCMC_FOLD,
+    include/trpl.h): with it a u' that leaves the unit cube is reflected back at the faces, and inside is a code -- 0 some coordinate
+    is not finite, 1 nothing needed folding, 2 at least one coordinate was folded; without it inside is 0 (outside) or 1."""
     import torch
     lo, hi, lg = _refine_box(minX, maxX, do_log)
     if U.dim() != 2:

@@ -1,4 +1,4 @@
-"""Ensemble Metropolis sampling on the fused likelihood (trpl_mcmc_*, include/trpl.h; csrc/mcmc.hip).
+"""Ensemble Metropolis sampling on the fused likelihood (trpl_mcmc_*, include/trpl.h; csrc/mcmc.hip; DESIGN.md sections 23 and 25).
 
 An importance-weighted population stops being useful when its effective sample size is a dozen.  Here C chains advance in
 lock-step instead: one sweep proposes a move for every chain, evaluates all proposals in one call of the likelihood, and accepts or
@@ -8,8 +8,10 @@ ensemble is cut into two halves that are updated in turn, each with partners fro
 Foreman-Mackey et al. 2013): within a half-sweep the partners are fixed, so every chain's move is a symmetric Metropolis kernel
 that leaves the posterior invariant, and all chains of the half can move at once.  kind="rw" is the plain random walk.
 
-Chains live in the unit coordinates of `refine` (the active columns of the box, uniform prior on the cube); a proposal that leaves
-the cube is never solved and never accepted.  The proposal, the accept/reject step and the sums of split-R-hat run on the device;
+Chains live in the unit coordinates of `refine` (the active columns of the box, uniform prior on the cube).  With bounds="reject",
+the default, a proposal that leaves the cube is never solved and never accepted; with bounds="fold" it is reflected back at the
+faces (TRPL_MCMC_FOLD, include/trpl.h), which keeps the proposal symmetric, so every proposal is solved and can be accepted -- what
+a posterior that lies against a face of the box needs.  The proposal, the accept/reject step and the sums of split-R-hat run on the device;
 there is no CPU fallback.  This module takes and returns numpy arrays and goes through the host-buffer calls, like `refine`: the
 likelihood it drives is any callable on a host X.  A pipeline whose chains stay on the device composes the same steps from
 device.mcmc_propose_device / mcmc_accept_device / mcmc_chain_stats_device.
@@ -25,11 +27,13 @@ from .sampler import box_flags
 _M64, _M32 = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF
 
 
-def propose(U, partners, gamma, scale, chain0, seed, step, minX, maxX, do_log, sim_flags=None, device=0, info=None):
+def propose(U, partners, gamma, scale, chain0, seed, step, minX, maxX, do_log, sim_flags=None, device=0, info=None, fold=False):
     """(Up, Xp, inside): one symmetric proposal per chain of U (count, A) (trpl_mcmc_propose).  partners (P >= 2, A): u' = (u + gamma
     (pa - pb)) + scale (2 xi - 1) with two distinct rows a, b of partners; partners None: the random walk u' = u + scale (2 xi - 1).
     scale (A,) or a scalar.  chain0 is the ensemble index of U's first row and step the half-sweep: they key the Philox stream.
-    inside (count,) int32 is 0 where u' left the unit cube; Xp is formed either way."""
+    inside (count,) int32 is 0 where u' left the unit cube; Xp is formed either way.  fold=True (TRPL_MCMC_FOLD): u' is reflected
+    back at the faces of the cube, and inside is 0 where a coordinate is not finite, 1 where nothing was folded, 2 where something
+    was."""
     U = _f64(U)
     lo, hi, lg = _box(minX, maxX, do_log)
     if U.ndim != 2:
@@ -46,8 +50,8 @@ def propose(U, partners, gamma, scale, chain0, seed, step, minX, maxX, do_log, s
     sec = _abi.C.c_double(0.0)
     _abi.check(_abi.lib().trpl_mcmc_propose(_abi.ptr(U), None if partners is None else _abi.ptr(partners), count, P, A, float(gamma),
                                             _abi.ptr(scale), int(chain0), int(seed) & _M64, int(step) & _M32, lo.size, _abi.ptr(lo),
-                                            _abi.ptr(hi), _abi.ptr(lg), box_flags(sim_flags), _abi.ptr(Up), _abi.ptr(Xp),
-                                            _abi.ptr(inside), int(device), _abi.C.byref(sec)))
+                                            _abi.ptr(hi), _abi.ptr(lg), box_flags(sim_flags) | (_abi.MCMC_FOLD if fold else 0),
+                                            _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(inside), int(device), _abi.C.byref(sec)))
     if info is not None:
         info.update(seconds=sec.value)
     return Up, Xp, inside
@@ -140,13 +144,14 @@ class Chains:
 
 
 def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0, kind="de", gamma=None, scale=None, jump_every=0,
-        seed=1, keep_every=1, burn=0, max_history_bytes=4 << 30, device=0, info=None, U0=None):
+        seed=1, keep_every=1, burn=0, max_history_bytes=4 << 30, device=0, info=None, U0=None, bounds="reject"):
     """Advance the C chains that start at X0 (C, ncol), LL0 (C,) by `sweeps` sweeps; loglik(X) -> LL is any callable (the fused
     likelihood, a toy).  Returns Chains: the states after the sweeps burn, burn + keep_every, ...
 
     One sweep updates the chains [0, C / 2) with the chains [C / 2, C) as partners (step = 2 t, chain0 = 0), then the chains [C / 2,
-    C) with the already updated first half (step = 2 t + 1, chain0 = C / 2).  loglik is called on the proposals inside the cube only;
-    the others get LLp = -inf and are rejected.
+    C) with the already updated first half (step = 2 t + 1, chain0 = C / 2).  bounds="reject": loglik is called on the proposals
+    inside the cube only; the others get LLp = -inf and are rejected.  bounds="fold": a proposal that leaves the cube is reflected
+    back at its faces (propose(fold=True)) and solved like any other; only one with a coordinate that is not finite is left out.
 
     kind="de": differential evolution, gamma defaulting to 2.38 / sqrt(2 A) and, with jump_every > 0, 1.0 on every jump_every-th
     sweep (a jump between modes); scale (the uniform jitter's half-width, a scalar or (A,)) defaults to 1e-3.  kind="rw": the random
@@ -154,8 +159,10 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
     returns them); default refine.unit_coords(X0).
 
     The history of n kept sweeps takes n C (A + ncol + 1) 8 + n C bytes; a run whose history would exceed max_history_bytes raises
-    ValueError before anything is solved.  ValueError for an odd C or C < 4.  info receives accept (the share of chains that moved,
-    per sweep) and outside (the share of all proposals that left the cube)."""
+    ValueError before anything is solved.  ValueError for an odd C or C < 4, or a bounds that is neither string.  info receives
+    accept (the share of chains that moved, per sweep), outside (the share of all proposals that were not solved: those that left
+    the cube, or under bounds="fold" the non-finite ones, normally 0.0) and folded (the share of all proposals that were reflected
+    back: 0.0 under bounds="reject")."""
     X, LL = np.array(X0, dtype=np.float64, order="C"), np.array(LL0, dtype=np.float64, order="C")
     lo, hi, lg = _box(minX, maxX, do_log)
     if X.ndim != 2 or X.shape[1] != lo.size or LL.shape != (X.shape[0],):
@@ -165,6 +172,8 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
         raise ValueError("C=%d: the two halves of the ensemble need an even number of chains, at least 4" % C)
     if kind not in ("de", "rw"):
         raise ValueError("kind must be 'de' or 'rw'")
+    if bounds not in ("reject", "fold"):
+        raise ValueError("bounds must be 'reject' or 'fold'")
     if scale is None:
         if kind == "rw":
             raise ValueError("kind='rw' needs scale, the half-width of the random walk")
@@ -190,23 +199,25 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
     half = C // 2
     hU, hX = np.empty((len(kept), C, A)), np.empty((len(kept), C, lo.size))
     hLL, hAcc = np.empty((len(kept), C)), np.empty((len(kept), C), dtype=bool)
-    shares, outside, row = [], 0, 0
+    shares, outside, folded, row = [], 0, 0, 0
     moved = np.empty(C, dtype=bool)
     for t in range(sweeps):
         g = 1.0 if jump_every > 0 and (t + 1) % jump_every == 0 else gamma0
         for k, (a, b) in enumerate(((0, half), (half, C))):
             partners = None if kind == "rw" else (U[half:] if k == 0 else U[:half])
-            Up, Xp, inside = propose(U[a:b], partners, g, scale, a, seed, 2 * t + k, lo, hi, lg, sim_flags, device=device)
+            Up, Xp, inside = propose(U[a:b], partners, g, scale, a, seed, 2 * t + k, lo, hi, lg, sim_flags, device=device,
+                                         fold=bounds == "fold")
             ok = inside != 0
             LLp = np.full(b - a, -np.inf)
             if ok.any():
                 LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok])))
             outside += int((~ok).sum())
+            folded += int((inside == 2).sum())
             moved[a:b] = accept(U[a:b], X[a:b], LL[a:b], Up, Xp, LLp, inside, tf, a, seed, 2 * t + k, device=device) != 0
         shares.append(float(moved.mean()))
         if t >= burn and (t - burn) % keep_every == 0:
             hU[row], hX[row], hLL[row], hAcc[row] = U, X, LL, moved
             row += 1
     if info is not None:
-        info.update(accept=shares, outside=outside / float(sweeps * C))
+        info.update(accept=shares, outside=outside / float(sweeps * C), folded=folded / float(sweeps * C))
     return Chains(hU, hX, hLL, hAcc, device=device)

@@ -1225,8 +1225,26 @@ int trpl_refine_draw_oriented(const double *zc, const double *h, const double *L
  * what trpl_refine_draw refuses of a box; (accept) ncol outside [1, 16], tf not finite or <= 0; (chain_stats) n < 1, Q < 1,
  * ldh < Q, a range that does not satisfy 0 <= t0 < t1 <= n.  The _dev calls take device pointers (scale and the box arrays
  * excepted), allocate nothing and never synchronise.
+ *
+ * TRPL_MCMC_FOLD, a bit of the `flags` of trpl_mcmc_propose / trpl_mcmc_propose_dev only: a proposal that leaves the unit cube is
+ * reflected back at its faces, as often as needed, and no longer thrown away.  Each active coordinate goes through fold after the
+ * last addition of the expression above, u'_d = ... + scale_d * (2 xi_d - 1); in fp64, one rounding per operation, in this order:
+ *     v in [0, 1] (v >= 0.0 && v <= 1.0): unchanged, the same bits (-0.0 included)
+ *     otherwise: r = fmod(v, 2.0); if (r < 0.0) r = r + 2.0; if (r > 1.0) r = 2.0 - r; v = r
+ * fmod is exact, so any correct implementation gives numpy.fmod's bits; a NaN or +-inf gives NaN.  fold is applied per dimension.
+ * Up holds the folded coordinate and Xp is formed from it by the same expressions; a fixed column and the TRPL_BOX_EQUAL_*
+ * overrides are unaffected.  inside[i] becomes a code: 0 some coordinate is not finite, 1 no coordinate needed folding, 2 at
+ * least one was folded; trpl_mcmc_accept tests inside != 0 and is unchanged.  Without the bit inside stays 0 / 1 and every output
+ * bit is as before.  Why no Hastings term is needed: for fixed partners the unfolded increment gamma (pa - pb) + scale (2 xi - 1)
+ * has a density p symmetric about 0 (the ordered pair (a, b) is uniform, so (b, a) is as likely), and the reflections at the faces
+ * are isometries.  So q(y | x) = sum over the reflection group g of p(g(y) - x) is symmetric in (x, y), and the Metropolis rule of
+ * trpl_mcmc_accept leaves the posterior invariant as it stands.
+ * Refused (TRPL_ERR_ARG, "flags=0x.."): in trpl_mcmc_propose* any bit other than TRPL_BOX_EQUAL_* and TRPL_MCMC_FOLD;
+ * TRPL_MCMC_FOLD in trpl_refine_draw*, trpl_refine_unit* and trpl_refine_draw_oriented*, where folding would change the proposal
+ * density r(u).
  * Python: trpl_amd.mcmc, trpl_amd.device.mcmc_*_device.
  * ------------------------------------------------------------------------------------- */
+#define TRPL_MCMC_FOLD 0x10
 int trpl_mcmc_propose_dev(const double *U, const double *partners /*nullable*/, int64_t count, int64_t P, int32_t A, double gamma,
                           const double *scale /*host [A]*/, int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol,
                           const double *lo /*host*/, const double *hi /*host*/, const int32_t *do_log /*host*/, uint32_t flags,

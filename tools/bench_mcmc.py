@@ -1,9 +1,12 @@
 """The three kernels of the ensemble Metropolis sampler on resident tensors, in one process on one device.
 
-    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--out profiles/mcmc_bench.jsonl]
+    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--fold] [--out profiles/mcmc_bench.jsonl]
 
 propose:     mcmc_propose_device of `chains` chains in the reference's box (A = 10 active columns), with `chains` partners
              (differential evolution: two gathered partner rows per chain), and the random walk for comparison.
+             --fold adds the differential-evolution propose with TRPL_MCMC_FOLD at the same shape, on chains of which half lie
+             within 1e-3 of a face of the cube, so that the fmod path of the fold runs; the unfolded call of the same process is
+             propose_de.
 accept:      mcmc_accept_device of the same chains, about a third of the proposals accepted.
 chain_stats: mcmc_chain_stats_device over a history of n steps of chains * A columns (one half of a split-R-hat: n / 2 steps).
 Device events around `reps` back-to-back calls after a warm-up, median of 3 interleaved passes (tools/bench_quantiles.measure).
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--A", type=int, default=10)
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--fold", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcmc_bench.jsonl"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -54,15 +58,28 @@ def main():
     # accept overwrites its chains, so it runs on copies.  Every call decides alike: a chain that took its proposal stands on it at
     # the next call (d = 0: taken again), one that refused refuses again (the same uniform) -- the same reads and writes each time
     Ua, Xa, LLa = U.clone(), X.clone(), LL.clone()
-    ms, passes = measure({
+    calls = {
         "propose_de": lambda: tdev.mcmc_propose_device(U, partners, gamma, 1e-3, 0, 42, 0, lo, hi, lg, Up, Xp, inside),
         "propose_rw": lambda: tdev.mcmc_propose_device(U, None, gamma, 0.05, 0, 42, 0, lo, hi, lg, Up, Xp, inside),
         "accept": lambda: tdev.mcmc_accept_device(Ua, Xa, LLa, Up, Xp, LLp, inside, 1.0, 0, 42, 0, accepted),
-        "chain_stats": lambda: tdev.mcmc_chain_stats_device(H, 0, a.n // 2, mean, m2)}, a.reps)
+        "chain_stats": lambda: tdev.mcmc_chain_stats_device(H, 0, a.n // 2, mean, m2)}
+    if a.fold:
+        # every second chain within 1e-3 of a face in every coordinate: its proposal leaves the cube and is folded.  Outputs of its
+        # own, so that accept reads what propose_de wrote, as without --fold
+        Uf = U.clone()
+        near = torch.rand((C // 2, A), generator=g, **f64) * 1e-3
+        Uf[::2] = torch.where(torch.rand((C // 2, A), generator=g, **f64) < 0.5, near, 1.0 - near)
+        Upf, Xpf, codes = torch.empty_like(Up), torch.empty_like(Xp), torch.empty_like(inside)
+        flags = trpl_amd._abi.MCMC_FOLD
+        calls["propose_de_fold"] = lambda: tdev.mcmc_propose_device(Uf, partners, gamma, 1e-3, 0, 42, 0, lo, hi, lg, Upf, Xpf, codes,
+                                                                     flags=flags)
+    ms, passes = measure(calls, a.reps)
     torch.cuda.synchronize()
     line = {"bench": "mcmc", "device": torch.cuda.get_device_name(0), "chains": C, "A": A, "ncol": ncol, "n": a.n, "reps": a.reps, "ms": ms,
             "ms_passes": passes, "inside_share": float(inside.double().mean().item()), "accepted_share": float(accepted.double().mean().item()),
             "chain_stats_bytes_per_second": 2.0 * 8.0 * (a.n // 2) * C * A / (ms["chain_stats"] * 1e-3)}
+    if a.fold:
+        line["folded_share"] = float((codes == 2).double().mean().item())
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as f:
         f.write(json.dumps(line) + "\n")

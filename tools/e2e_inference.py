@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--fold]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -35,7 +35,9 @@ beside the likelihoods (posterior.calc_max_uncertainty(log_ratio=)), as refine["
 proposals at the run's temperature; the second half of the sweeps is kept.  "mcmc" holds the acceptance share, the share of
 proposals that left the prior box, split-R-hat of every free parameter and its 2.5 / 50 / 97.5 % values from the chain beside
 those of the importance run, which are printed; seconds["mcmc"].  --rw x uses a random walk of half-width x (unit coordinates)
-instead.  Without --mcmc the output is unchanged.
+instead.  --fold reflects a proposal that leaves the prior box back at its faces (mcmc.run(bounds="fold"): DESIGN.md section 25),
+so that every proposal is solved; "mcmc" then gains "bounds" and "folded", the share of proposals that were reflected.  Without
+--mcmc the output is unchanged, and so is "mcmc" without --fold.
 """
 import json
 import sys
@@ -64,6 +66,7 @@ if "--shrink" in sys.argv:
     SHRINK = float(sys.argv[k + 1])
     del sys.argv[k:k + 2]
 MCMC = "--mcmc" in sys.argv
+FOLD = "--fold" in sys.argv
 CHAINS, SWEEPS, RW = 1024, 200, None
 for flag, conv in (("--chains", int), ("--sweeps", int), ("--rw", float)):
     if flag in sys.argv:
@@ -76,7 +79,7 @@ for flag, conv in (("--chains", int), ("--sweeps", int), ("--rw", float)):
             SWEEPS = value
         else:
             RW = value
-sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented", "--mcmc")]
+sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented", "--mcmc", "--fold")]
 import numpy as np
 import torch
 import trpl_amd
@@ -257,7 +260,7 @@ if MCMC:
     minfo = {}
     burn = SWEEPS // 2
     ch = mcmc.run(fused_chain, X0, LL0, lo, hi, lg, sweeps=SWEEPS, tf=tf, seed=42, burn=burn, info=minfo, U0=U0,
-                  **({"kind": "rw", "scale": RW} if RW is not None else {}))
+                  **({"kind": "rw", "scale": RW} if RW is not None else {}), **({"bounds": "fold"} if FOLD else {}))
     rhat = ch.rhat()
     Xs, Ws = ch.samples()
     Xg = Xs / sm.UNIT_CONVERSIONS
@@ -275,6 +278,9 @@ if MCMC:
                    "max_loglik": float(ch.LL.max()), "median_loglik": float(np.median(ch.LL[-1])),
                    "quantiles": {n: {"truth": float(tr), "chain": [float(v) for v in q_chain[:, k]],
                                      "importance": [float(v) for v in q_imp[:, k]]} for k, (n, tr) in enumerate(zip(names, truth))}}
+    if FOLD:
+        out["mcmc"].update(bounds="fold", folded=minfo["folded"])
+        print("mcmc: bounds=fold, %.4f of the proposals reflected at a face" % minfo["folded"], file=sys.stderr)
     print("mcmc (%s): %d chains from %d distinct starts, %d sweeps: acceptance %.3f (kept half %.3f), outside the prior box %.4f, worst R-hat %.3f"
           % (out["mcmc"]["proposal"], CHAINS, out["mcmc"]["distinct_starts"], SWEEPS, out["mcmc"]["acceptance"],
              out["mcmc"]["acceptance_kept"], minfo["outside"], out["mcmc"]["worst_rhat"]), file=sys.stderr)
