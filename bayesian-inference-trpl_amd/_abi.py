@@ -22,7 +22,7 @@ FLAG_PAIR_ALWAYS_SEAM, FLAG_PAIR_ADJACENT, FLAG_MULTI_FORCE_PAD = 0x20000, 0x400
 FLAG_PREDICT = 0x100000    # opt-in: extrapolated start of every time step's iteration (include/trpl.h)
 FLAG_MOMENTS = 0x200000    # set by trpl_loglik_moments[_dev] themselves (esum beside sse); trpl_kernel_name accepts it
 FLAG_WEIGHTED = 0x400000   # set by trpl_loglik_weighted[_dev] themselves (sse, esum weighted per observation)
-FLAG_CUT = 0x800000        # set by trpl_loglik_cut[_dev] themselves (a system stops once its running sse is above sse_cut)
+FLAG_CUT = 0x800000        # set by trpl_loglik_cut[_levels][_dev] themselves (a system stops once its running sse is above sse_cut / its cut_level)
 MAG_PER_CURVE = 0x1        # trpl_mag_profile: one best offset per curve instead of one per sample
 MAG_MAX_CURVES = 64        # TRPL_MAG_MAX_CURVES
 MULTI_ALLOW_DUPLICATE_DEVICES = 0x1     # trpl_multi_create_ex
@@ -147,6 +147,10 @@ SIGNATURES = {
                         _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _pd],
     "trpl_loglik_cut_dev": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f64,
                             _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
+    "trpl_loglik_cut_levels": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _pd],
+    "trpl_loglik_cut_levels_dev": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "trpl_loglik_multi": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64,
                           _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _i32, _pd],
     "trpl_multi_create": [_vp, _i32, _vp],
@@ -218,6 +222,8 @@ SIGNATURES = {
     "trpl_mcmc_accept": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f64, _i64, _u64, _u32, _vp, _i32, _pd],
     "trpl_mcmc_chain_stats_dev": [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp],
     "trpl_mcmc_chain_stats": [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _pd],
+    "trpl_mcmc_levels_dev": [_vp, _i64, _f64, _i64, _u64, _u32, _vp, _vp],
+    "trpl_mcmc_levels": [_vp, _i64, _f64, _i64, _u64, _u32, _vp, _i32, _pd],
     "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
     "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
 }

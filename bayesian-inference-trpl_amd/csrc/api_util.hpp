@@ -125,7 +125,7 @@ struct HostMap {
 // Members are destroyed last to first: the buffers are released (hipFreeAsync), then the scope drains and destroys the stream,
 // then the caller's memory is unpinned.
 struct Staged {
-    static constexpr int kMaxBufs = 13;      // the largest user, trpl_loglik_weighted off the grid, declares 13
+    static constexpr int kMaxBufs = 13;      // the largest users, trpl_loglik_weighted and trpl_loglik_cut_levels off the grid, declare 13
     HostMap hm;                              // the one buffer of the caller's that pin() or map() holds for the call
     CallScope cs;
     DevBuf buf[kMaxBufs];
@@ -237,7 +237,7 @@ struct ProfRange {
 };
 
 // The arguments of one fused-likelihood call, device pointers: what the trpl_loglik*_dev entry points take, by name.  esum, wts,
-// sse_cut and cut_col select the sink (trpl_loglik_moments / _weighted / _cut) and are NULL elsewhere; the brackets are NULL on the grid.
+// sse_cut (or cut_level) and cut_col select the sink (trpl_loglik_moments / _weighted / _cut / _cut_levels) and are NULL elsewhere; the brackets are NULL on the grid.
 struct LoglikCall {
     const double *X = nullptr;
     int64_t S = 0;
@@ -253,6 +253,7 @@ struct LoglikCall {
     int64_t obs_ld = 0;
     const int64_t *n_obs = nullptr;
     const double *sse_cut = nullptr;                 // host: the threshold of the cut entry points
+    const double *cut_level = nullptr;               // [C][S]: a level per system (trpl_loglik_cut_levels[_dev]) in the place of sse_cut
     double *P = nullptr, *sse = nullptr, *esum = nullptr;
     int32_t *cut_col = nullptr, *status = nullptr;
     int64_t *iters_total = nullptr;

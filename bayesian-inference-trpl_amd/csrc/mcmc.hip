@@ -12,6 +12,9 @@
 //   accept_kernel<A>      one thread per chain.  xi of counter word 0x109; the chain takes its proposal's U, X and LL when the
 //       proposal is inside, its LLp is neither NaN nor -inf, and the chain stands on a likelihood that is not above -inf, or
 //       d = (LLp - LL) / tf >= 0, or log(xi) < d.
+//   levels_kernel         one thread per chain.  The accept step's xi (the same counter word, res53 and log), turned into the level of
+//       trpl_loglik_cut_levels above which a proposal's running sse makes its rejection by accept_kernel certain: -(LL + tf log(xi)),
+//       or that plus a few ulps, whichever the accept step's own expression confirms; +inf (never cut) when neither does.
 //   chain_stats_kernel    one thread per column q of a history H [n][ldh]: the mean and the centred sum of squares over the steps
 //       [t0, t1), both sums in ascending t from +0.0.  Adjacent threads read adjacent addresses.
 // Compiled with -ffp-contract=off like refine.hip: every result is its expression with one rounding per operation.
@@ -141,6 +144,34 @@ __global__ void __launch_bounds__(kThreads) accept_kernel(double *U, double *X, 
     LL[i] = llp;
 }
 
+// Early rejection (include/trpl.h, trpl_mcmc_levels): a candidate level l is taken only if the accept step's own d, formed for a proposal
+// with LLp = -l, is negative and not above log(xi) -- then every LLp <= -l has a d no larger (subtraction and division by tf > 0 are
+// monotone) and accept_kernel rejects it with the same (seed, chain, step).
+__global__ void __launch_bounds__(kThreads) levels_kernel(const double *LL, int64_t count, double tf, int64_t chain0, uint32_t seed_lo,
+                                                          uint32_t seed_hi, uint32_t step, double *level)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t n = (uint64_t)(chain0 + i);
+    uint32_t r[4];
+    philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), kStream + kAcceptCall, step, seed_lo, seed_hi, r);
+    const double xi = res53(r[0], r[1]);
+    const double ll = LL[i];
+    double lv = INFINITY;
+    if (!(ll != ll) && ll > -INFINITY && xi != 0.0) {
+        const double lx = log(xi);
+        const double l0 = -(ll + tf * lx);
+        double cand = l0;
+        for (int k = 0; k < 2; k++) {
+            const double q = -cand;
+            const double dq = (q - ll) / tf;
+            if (dq < 0.0 && !(lx < dq)) { lv = cand; break; }
+            cand = l0 + (fabs(ll) + l0) * 0x1p-40;
+        }
+    }
+    level[i] = lv;
+}
+
 __global__ void __launch_bounds__(kThreads) chain_stats_kernel(const double *H, int64_t ldh, int64_t Q, int64_t t0, int64_t t1,
                                                                double *mean, double *m2)
 {
@@ -208,6 +239,17 @@ static int check_accept(const void *U, const void *X, const void *LL, const void
     if (!LLp) return api_fail(TRPL_ERR_ARG, "LLp is NULL");
     if (!inside) return api_fail(TRPL_ERR_ARG, "inside is NULL");
     if (!accepted) return api_fail(TRPL_ERR_ARG, "accepted is NULL");
+    return TRPL_OK;
+}
+
+static int check_levels(const void *LL, int64_t count, double tf, int64_t chain0, const void *level)
+{
+    if (count < 1) return api_fail(TRPL_ERR_ARG, "count=%lld must be >= 1", (long long)count);
+    if (int rc = refine_check_blocks("count", count, "chains")) return rc;
+    if (!(isfinite(tf) && tf > 0.0)) return api_fail(TRPL_ERR_ARG, "tf=%g must be finite and > 0", tf);
+    if (chain0 < 0) return api_fail(TRPL_ERR_ARG, "chain0=%lld must be >= 0", (long long)chain0);
+    if (!LL) return api_fail(TRPL_ERR_ARG, "LL is NULL");
+    if (!level) return api_fail(TRPL_ERR_ARG, "level is NULL");
     return TRPL_OK;
 }
 
@@ -303,6 +345,29 @@ int trpl_mcmc_accept(double *U, double *X, double *LL, const double *Up, const d
     int32_t *dAcc = sg.out(accepted, (size_t)count);
     if (int rc = sg.begin()) return rc;
     if (int rc = trpl_mcmc_accept_dev(dU, dX, dLL, dUp, dXp, dLLp, dIn, count, A, ncol, tf, chain0, seed, step, dAcc, sg.stream())) return rc;
+    return sg.finish(seconds);
+}
+
+int trpl_mcmc_levels_dev(const double *LL, int64_t count, double tf, int64_t chain0, uint64_t seed, uint32_t step, double *level,
+                         void *stream)
+{
+    if (int rc = check_levels(LL, count, tf, chain0, level)) return rc;
+    hipLaunchKernelGGL(mcmc::levels_kernel, dim3(refine_blocks(count)), dim3(refine::kThreads), 0, (hipStream_t)stream, LL, count, tf,
+                       chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step, level);
+    return refine_launched("mcmc levels");
+}
+
+int trpl_mcmc_levels(const double *LL, int64_t count, double tf, int64_t chain0, uint64_t seed, uint32_t step, double *level,
+                     int32_t device, double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    if (int rc = check_levels(LL, count, tf, chain0, level)) return rc;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const double *dLL = sg.in(LL, (size_t)count);
+    double *dLv = sg.out(level, (size_t)count);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_mcmc_levels_dev(dLL, count, tf, chain0, seed, step, dLv, sg.stream())) return rc;
     return sg.finish(seconds);
 }
 

@@ -264,7 +264,7 @@ __device__ __forceinline__ bool correct_mixed(const double (&lo)[NR], const doub
 // err * w -- the square first, then the weight, so that w = 1 leaves the moments sink's bits and a power of two scales them
 // exactly.  The weight is one more coalesced load beside obs's; its row pointer is not kept (the paired kernel has no
 // register for it) but formed from obs's when a batch is flushed: wts and obs share their indexing.
-// CUT (TRPL_FLAG_CUT): after every batch the sink adds, the running sse is compared with a.sse_cut (wave-uniform; a NaN sum never
+// CUT (TRPL_FLAG_CUT): after every batch the sink adds, the running sse is compared with the system's level (a.cut_level[orow], else a.sse_cut: wave-uniform; a NaN sum never
 // compares true); the first time it is above, the number of leading observations in the sum is recorded and the sink accepts
 // nothing more: the kernel leaves its time loop (one system) or parks the system like a flagged one (paired).  sse is a sum of
 // non-negative terms and never decreases, so the system's final sse would have been above the level too.  The paired kernel's
@@ -306,6 +306,16 @@ struct PlSinkT {
         else return cut_at;
     }
     __device__ __forceinline__ bool is_cut() const { return cut_count() >= 0; }
+    // CUT only: this system's level -- a.cut_level[orow] (trpl_loglik_cut_levels) or the call's one a.sse_cut.  Read when a batch is
+    // tested, through the kernel arguments and the wave-uniform orow (below 2^31: a launch has at most that many systems), as a
+    // scalar load from memory the kernel never writes: no vector register is touched and no register holds the pointer or the level
+    // across the time loop (the paired kernel has none to spare).  The two sinks of a paired wavefront each read their own.
+    __device__ __forceinline__ double level() const
+    {
+        if (!a.cut_level) return a.sse_cut;
+        typedef const __attribute__((address_space(4))) double const_double;
+        return ((const_double *)(uintptr_t)a.cut_level)[__builtin_amdgcn_readfirstlane((int32_t)orow)];
+    }
     // CUT only: one batch's sum of err^2 (wave-uniform) joins the running sse, which is then tested; count: the observations in
     // the sum after it.  Returns whether the system is cut now.
     __device__ __forceinline__ bool add_and_test(double q2, int32_t count)
@@ -313,7 +323,7 @@ struct PlSinkT {
         double s2;
         if constexpr (PARK) s2 = park[0] + q2;                       // one wavefront: its LDS accesses are in program order
         else s2 = sse + q2;
-        const bool over = uniform_d(s2) > a.sse_cut;
+        const bool over = uniform_d(s2) > level();
         if constexpr (PARK) { if (lane_ == 0) { park[0] = s2; if (over) park[1] = (double)count; } }
         else { sse = s2; if (over) cut_at = count; }
         return over;
@@ -1143,7 +1153,7 @@ stepper_kernel(const StepArgs a)
 static inline bool sink_args_ok(const StepArgs &a)
 {
     if (!a.sse) return false;
-    if constexpr (TRPL_STEPPER_CUT != 0) return !a.pl && !a.esum && !a.wts && a.sse_cut >= 0.0;
+    if constexpr (TRPL_STEPPER_CUT != 0) return !a.pl && !a.esum && !a.wts && (a.cut_level || a.sse_cut >= 0.0);
     else return a.esum && (TRPL_STEPPER_WEIGHTED != 0) == (a.wts != nullptr);
 }
 // likelihood mode only -- one instantiation per L, no bundles, no snapshot / resume forms (check_launch); TRPL_FLAG_CUT: FAST only

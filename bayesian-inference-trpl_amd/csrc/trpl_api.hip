@@ -362,7 +362,7 @@ int pin_sharded_batch(uint32_t &flags, int64_t S, int32_t C, int32_t L, int64_t 
 
 // TRPL_FLAG_MOMENTS belongs to trpl_loglik_moments[_dev], which set it themselves: the other entry points have no esum output
 // ... and TRPL_FLAG_WEIGHTED to trpl_loglik_weighted[_dev]: the other entry points take no weights
-// ... and TRPL_FLAG_CUT to trpl_loglik_cut[_dev]: the other entry points have no sse_cut
+// ... and TRPL_FLAG_CUT to trpl_loglik_cut[_levels][_dev]: the other entry points have no sse_cut and no cut_level
 static int no_cut_flag(uint32_t flags)
 {
     if (flags & TRPL_FLAG_CUT)
@@ -860,8 +860,8 @@ static int entry_flags(uint32_t &flags, bool esum, bool wts, bool cut = false)
 // the sink flag of the record's optional pointers and the sse_cut range: the first checks of both forms
 static int check_sink(const LoglikCall &k, uint32_t &flags)
 {
-    // sse_cut: the cut entry points (NULL everywhere else)
-    if (int rc = entry_flags(flags, k.esum != nullptr, k.wts != nullptr, k.sse_cut != nullptr)) return rc;
+    // sse_cut, or cut_level in its place: the cut entry points (both NULL everywhere else)
+    if (int rc = entry_flags(flags, k.esum != nullptr, k.wts != nullptr, k.sse_cut != nullptr || k.cut_level != nullptr)) return rc;
     if (k.sse_cut && !(*k.sse_cut >= 0.0)) return api_fail(TRPL_ERR_ARG, "sse_cut=%g must be >= 0 or +inf", *k.sse_cut);
     return TRPL_OK;
 }
@@ -906,6 +906,7 @@ int trpl::loglik_dev(const LoglikCall &k, hipStream_t stream)
         a.wts = k.wts ? k.wts + (int64_t)c0 * obs_ld : nullptr;
         a.sse_cut = k.sse_cut ? *k.sse_cut : 0.0;
         a.cut_col = k.cut_col ? k.cut_col + (int64_t)c0 * S : nullptr;
+        a.cut_level = k.cut_level ? k.cut_level + (int64_t)c0 * S : nullptr;
         a.status = k.status ? k.status + (int64_t)c0 * S : nullptr;
         a.iters_total = k.iters_total ? k.iters_total + (int64_t)c0 * S : nullptr;
         a.floor_col = k.floor_col ? k.floor_col + (int64_t)c0 * S : nullptr;
@@ -947,6 +948,7 @@ static int loglik_host(const LoglikCall &k, int32_t device, double *seconds)
     d.P = sg.inout(k.P, (size_t)k.S); d.sse = sg.out(k.sse, nsys); d.esum = k.esum ? sg.out(k.esum, nsys) : nullptr;
     d.status = sg.out(k.status, nsys); d.floor_col = k.floor_col ? sg.out(k.floor_col, nsys) : nullptr;
     d.cut_col = k.cut_col ? sg.out(k.cut_col, nsys) : nullptr;
+    d.cut_level = k.cut_level ? sg.in(k.cut_level, nsys) : nullptr;
     d.iters_total = sg.out(k.iters_total, nsys);
     if (int rc = sg.begin()) return rc;
     if (int rc = loglik_dev(d, sg.stream())) return rc;
@@ -1129,6 +1131,57 @@ int trpl_loglik_cut(const double *X, int64_t S, int32_t C, const double *lengths
     k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
     k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
     k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h; k.sse_cut = &sse_cut; k.cut_col = cut_col;
+    return loglik_host(k, device, seconds);
+}
+
+/* ------------------------------------------------------------------ the early stop with a level per system (MCMC early rejection) */
+// the host form sees its levels: each >= 0 or +inf, checked before a device is touched
+static int check_levels(const double *cut_level, int64_t S, int32_t C)
+{
+    for (int32_t c = 0; c < C; c++)
+        for (int64_t s = 0; s < S; s++)
+            if (!(cut_level[(int64_t)c * S + s] >= 0.0))
+                return api_fail(TRPL_ERR_ARG, "cut_level[c=%d][s=%lld]=%g must be >= 0 or +inf", c, (long long)s, cut_level[(int64_t)c * S + s]);
+    return TRPL_OK;
+}
+
+int trpl_loglik_cut_levels_dev(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
+                               int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN, const double *obs,
+                               const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t obs_ld,
+                               const int64_t *n_obs, const double *cut_level, double *P, double *sse, int32_t *cut_col,
+                               int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags, void *stream)
+{
+    if (S > 0 && !cut_level) return api_fail(TRPL_ERR_ARG, "cut_level must not be NULL");
+    const double none = INFINITY;                                 // S == 0: nothing is launched; the common checks still run
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = plT; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h; k.cut_col = cut_col;
+    if (S > 0) k.cut_level = cut_level; else k.sse_cut = &none;
+    return loglik_dev(k, (hipStream_t)stream);
+}
+
+int trpl_loglik_cut_levels(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
+                           int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN, const double *obs,
+                           const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t obs_ld,
+                           const int64_t *n_obs, const double *cut_level, double *P, double *sse, int32_t *cut_col,
+                           int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device,
+                           double *seconds)
+{
+    ProfRange range("trpl_loglik_cut_levels (pvSim + fastlog + prob with a stop level per system, fused)");
+    if (S > 0 && !cut_level) return api_fail(TRPL_ERR_ARG, "cut_level must not be NULL");
+    if (int rc = check_interp(obs_hi, obs_dx, obs_h, plT)) return rc;
+    const double none = INFINITY;
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = plT; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h; k.cut_col = cut_col;
+    if (S > 0) k.cut_level = cut_level; else k.sse_cut = &none;
+    { uint32_t f = flags; if (int rc = check_sink(k, f)) return rc; }       // the flag refusals before the levels are read
+    if (int rc = check_batch(k)) return rc;                                  // S >= 0 and C in range: the extent of cut_level
+    if (S > 0) { if (int rc = check_levels(cut_level, S, C)) return rc; }
     return loglik_host(k, device, seconds);
 }
 

@@ -73,6 +73,7 @@ struct StepArgs {
     const double *wts;      // [C][obs_ld] observation weights, indexed like obs (TRPL_FLAG_WEIGHTED kernels only), or nullptr
     double sse_cut;         // TRPL_FLAG_CUT kernels only: a system stops once its running sse is above this (>= 0 or +inf)
     int32_t *cut_col;       // [C][S] out (TRPL_FLAG_CUT kernels only) or nullptr: leading observations in a cut system's sse; -1 uncut; -2 flagged
+    const double *cut_level; // [C][S], indexed like cut_col (TRPL_FLAG_CUT kernels only), or nullptr: system (c, s) stops above cut_level[c][s] instead of sse_cut
 };
 
 // BDF coefficient table of tEvol (pvSimPCR.py:241-250): time step t takes the row min(t, 4) -- order 1 (Euler) at t = 0,

@@ -35,16 +35,16 @@ def _brackets(obs, obs_hi, obs_dx, obs_h):
 
 
 def _loglik_dev(entry, X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status, iters_total, tol, MAX, flags, floor_col,
-                plT=1, obs_hi=None, obs_dx=None, obs_h=None, wts=None, sse_cut=None, esum=None, cut_col=None):
-    """The one marshaller of the fused family trpl_loglik[_obs|_moments|_weighted|_cut]_dev: the arguments all five share,
+                plT=1, obs_hi=None, obs_dx=None, obs_h=None, wts=None, sse_cut=None, esum=None, cut_col=None, cut_level=None):
+    """The one marshaller of the fused family trpl_loglik[_obs|_moments|_weighted|_cut|_cut_levels]_dev: the arguments all six share,
     with an entry point's own where include/trpl.h puts them -- wts after obs, the brackets after that (not in trpl_loglik_dev),
-    sse_cut before P, esum or cut_col after sse; trpl_loglik_obs_dev alone has no plT.  A new sink or argument goes HERE."""
+    sse_cut (or cut_level (C,S) f64 in its place) before P, esum or cut_col after sse; trpl_loglik_obs_dev alone has no plT.  A new sink or argument goes HERE."""
     import torch
     f64 = torch.float64
     S, Cn = X.shape[0], init_params.shape[0]
     if X.shape[1] != 13 or init_params.shape[1] != L or obs.shape[0] != Cn or tuple(sse.shape) != (Cn, S) \
             or tuple(P.shape) != (S,) or (wts is not None and wts.shape != obs.shape) \
-            or any(t is not None and tuple(t.shape) != (Cn, S) for t in (esum, cut_col)):
+            or any(t is not None and tuple(t.shape) != (Cn, S) for t in (esum, cut_col, cut_level)):
         raise ValueError("shape mismatch")
     brackets = _brackets(obs, obs_hi, obs_dx, obs_h)
     lengths = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.float64), (Cn,)))
@@ -60,10 +60,12 @@ def _loglik_dev(entry, X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, 
     args += [obs.shape[1], _abi.ptr(n_obs)]
     if entry == "trpl_loglik_cut_dev":
         args.append(float(sse_cut))
+    if entry == "trpl_loglik_cut_levels_dev":
+        args.append(_chk(cut_level, f64, "cut_level"))
     args += [_chk(P, f64, "P"), _chk(sse, f64, "sse")]
     if entry in ("trpl_loglik_moments_dev", "trpl_loglik_weighted_dev"):
         args.append(_chk(esum, f64, "esum"))
-    if entry == "trpl_loglik_cut_dev":
+    if entry in ("trpl_loglik_cut_dev", "trpl_loglik_cut_levels_dev"):
         args.append(_opt(cut_col, torch.int32, "cut_col"))
     args += [_opt(status, torch.int32, "status"), _opt(iters_total, torch.int64, "iters_total"),
              _opt(floor_col, torch.int32, "floor_col"), int(flags), _stream()]
@@ -106,6 +108,19 @@ def loglik_cut_device(X, init_params, lengths, Time, L, T, obs, n_obs, sse_cut, 
     uncut system (all its outputs are loglik_device's, bit for bit), -2 for a flagged one (include/trpl.h)."""
     _loglik_dev("trpl_loglik_cut_dev", X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status, iters_total, tol, MAX,
                 flags, floor_col, plT=plT, obs_hi=obs_hi, obs_dx=obs_dx, obs_h=obs_h, sse_cut=sse_cut, cut_col=cut_col)
+
+
+def loglik_cut_levels_device(X, init_params, lengths, Time, L, T, obs, n_obs, cut_level, P, sse, cut_col=None, status=None,
+                             iters_total=None, tol=7, MAX=10000, plT=1, flags=0, floor_col=None, obs_hi=None, obs_dx=None,
+                             obs_h=None):
+    """trpl_loglik_cut_levels_dev: loglik_cut_device with a level per system -- cut_level (C,S) f64 on the device in the place of
+    sse_cut.  System (c, s) reports what loglik_cut_device reports for it at sse_cut = cut_level[c, s], bit for bit, whatever the
+    other systems' levels.  Nobody looks at the values here: a NaN level never cuts, a negative one cuts after the first batch
+    (include/trpl.h).  The levels of a Metropolis step come from mcmc_levels_device."""
+    if cut_level is None:
+        raise ValueError("cut_level must be a (C,S) float64 tensor")
+    _loglik_dev("trpl_loglik_cut_levels_dev", X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status, iters_total, tol, MAX,
+                flags, floor_col, plT=plT, obs_hi=obs_hi, obs_dx=obs_dx, obs_h=obs_h, cut_col=cut_col, cut_level=cut_level)
 
 
 def _mag_grid_dev(entry, sse, esum, per_curve, dtype, offsets, P):
@@ -645,6 +660,18 @@ def mcmc_accept_device(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, ac
         _chk(U, torch.float64, "U"), _chk(X, torch.float64, "X"), _chk(LL, torch.float64, "LL"), _chk(Up, torch.float64, "Up"),
         _chk(Xp, torch.float64, "Xp"), _chk(LLp, torch.float64, "LLp"), _chk(inside, torch.int32, "inside"), count, U.shape[1], X.shape[1],
         float(tf), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, _chk(accepted, torch.int32, "accepted"), _stream()))
+
+
+def mcmc_levels_device(LL, tf, chain0, seed, step, level):
+    """trpl_mcmc_levels_dev: level (count,) f64 <- for every chain the sse level above which mcmc_accept_device, called with the same
+    (tf, chain0, seed, step), is certain to reject the proposal: the cut_level of loglik_cut_levels_device, +inf where nothing may
+    be cut (include/trpl.h).  LL (count,) f64 is the chains' current log-likelihood, minus the summed sse of a P started from zero."""
+    import torch
+    if LL.dim() != 1 or tuple(level.shape) != tuple(LL.shape):
+        raise ValueError("LL and level must be (count,)")
+    _abi.check(_abi.lib().trpl_mcmc_levels_dev(
+        _chk(LL, torch.float64, "LL"), LL.shape[0], float(tf), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF,
+        _chk(level, torch.float64, "level"), _stream()))
 
 
 def mcmc_chain_stats_device(H, t0, t1, mean, m2, Q=None):

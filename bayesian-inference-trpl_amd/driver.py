@@ -139,7 +139,7 @@ def overlap_window(full, done, budget, num_curves):
 def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=None, pl_f32=False,
            normalize=False, strict=False, device=0, info=None, times=None, fp32=False, devices=None, kernel=None,
            mixed=False, bundle=1, hist32=False, bdf_order=None, extra_flags=0, predict=False, mag_grid=None,
-           mag_profile=False, weights=None, sse_cut=None):
+           mag_profile=False, weights=None, sse_cut=None, cut_levels=None):
     """Fused likelihood of one experiment (trpl_loglik / trpl_loglik_obs / trpl_loglik_multi).
 
     X (S,13) solver units; init_params (C,L) nm^-3; lengths scalar or (C,); obs = list of C
@@ -170,12 +170,22 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
     outputs are the plain call's bit for bit.  info also receives cut_col (C, S) (leading observations in a cut system's sum,
     -1 uncut, -2 flagged) and cut_fraction, the share of systems with cut_col >= 0.  Single-device calls on the plain FAST
     steppers only: not with mag_grid, mag_profile, weights, devices or bundle > 1.
+    cut_levels: sse_cut with a level per system (trpl_loglik_cut_levels) -- (S,), one level per sample given to each of its
+    curves, or (C, S); every level >= 0 or +inf.  System (c, s) reports what sse_cut = cut_levels[c, s] would make it report, bit
+    for bit, whatever the other levels; info receives cut_col and cut_fraction as with sse_cut.  Excludes sse_cut and is refused
+    with what sse_cut is refused with.  The levels of a Metropolis step: mcmc.reject_levels.
     """
-    if sse_cut is not None:
+    if cut_levels is not None:
+        if sse_cut is not None:
+            raise ValueError("cut_levels and sse_cut exclude each other")
+        cut_levels = np.asarray(cut_levels, dtype=np.float64)
+    if sse_cut is not None or cut_levels is not None:
+        word = "sse_cut" if sse_cut is not None else "cut_levels"
         for name, on in (("mag_grid", mag_grid is not None), ("mag_profile", bool(mag_profile)), ("weights", weights is not None),
                          ("devices", devices is not None), ("bundle", int(bundle) != 1)):
             if on:
-                raise ValueError("sse_cut: not available with %s (trpl_loglik_cut runs the plain FAST steppers on one device)" % name)
+                raise ValueError("%s: not available with %s (trpl_loglik_cut runs the plain FAST steppers on one device)" % (word, name))
+    if sse_cut is not None:
         sse_cut = float(sse_cut)
         if not sse_cut >= 0.0:
             raise ValueError("sse_cut must be >= 0 or +inf, got %r" % (sse_cut,))
@@ -230,6 +240,12 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
             if w.shape != o.shape:
                 raise ValueError("curve %d: %d weights for %d observations" % (c, len(w), len(o)))
             w_mat[c, :len(o)] = w[order] if times is not None else w
+    if cut_levels is not None:
+        if cut_levels.shape not in ((S,), (Cn, S)):
+            raise ValueError("cut_levels must have shape (S,) or (C, S) = (%d, %d), got %r" % (Cn, S, cut_levels.shape))
+        if not np.all(cut_levels >= 0.0):
+            raise ValueError("cut_levels must be >= 0 or +inf everywhere")
+        cut_levels = np.ascontiguousarray(np.broadcast_to(cut_levels, (Cn, S)))
     if P is None:
         P = np.zeros(S)
     if not (P.dtype == np.float64 and P.flags.c_contiguous and P.shape == (S,)):
@@ -244,8 +260,10 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
         | _abi.flag_bdf_order(bdf_order) | int(extra_flags) | (_abi.FLAG_PREDICT if predict else 0)
     sec = _abi.C.c_double(0.0)
     lib = _abi.lib()
-    weighted, cut, multi, off = weights is not None, sse_cut is not None, devices is not None, times is not None
-    entry = "trpl_loglik_weighted" if weighted else "trpl_loglik_moments" if moments else "trpl_loglik_cut" if cut \
+    levels = cut_levels is not None
+    weighted, cut, multi, off = weights is not None, sse_cut is not None or levels, devices is not None, times is not None
+    entry = "trpl_loglik_weighted" if weighted else "trpl_loglik_moments" if moments else "trpl_loglik_cut_levels" if levels \
+        else "trpl_loglik_cut" if cut \
         else "trpl_loglik_multi" if multi else "trpl_loglik_obs" if off else "trpl_loglik"
     own = {}                                       # the entry point's own outputs, as info receives them
     if weighted or moments:
@@ -262,13 +280,13 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
         if dev is not None and (dev.ndim != 1 or len(dev) < 1):
             raise ValueError("devices must name at least one device")
     # The call, built once; an entry point's own arguments sit where include/trpl.h puts them: no plT in trpl_loglik_obs, wts
-    # after obs, no brackets in trpl_loglik, sse_cut before P, esum or cut_col after sse, the device list for the device.
+    # after obs, no brackets in trpl_loglik, sse_cut (or cut_level) before P, esum or cut_col after sse, the device list for the device.
     head = [_abi.ptr(X), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T)] \
         + ([] if entry == "trpl_loglik_obs" else [int(plT)]) + [int(tol), int(MAX), _abi.ptr(ini)]
     brackets = [_abi.ptr(hi_mat), _abi.ptr(dx_mat), _abi.ptr(h_mat)] if off else [None, None, None]
     observed = [_abi.ptr(obs_mat)] + ([_abi.ptr(w_mat)] if weighted else []) + ([] if entry == "trpl_loglik" else brackets) \
         + [obs_ld, _abi.ptr(n_obs)]
-    outputs = ([sse_cut] if cut else []) + [_abi.ptr(P), _abi.ptr(sse)] + ([_abi.ptr(esum)] if "esum" in own else []) \
+    outputs = ([_abi.ptr(cut_levels) if levels else sse_cut] if cut else []) + [_abi.ptr(P), _abi.ptr(sse)] + ([_abi.ptr(esum)] if "esum" in own else []) \
         + ([_abi.ptr(cut_col)] if cut else []) + [_abi.ptr(status), _abi.ptr(iters), _abi.ptr(floor_col)]
     tail = [flags] + ([_abi.ptr(dev), 0 if dev is None else len(dev)] if multi else [int(device)]) + [_abi.C.byref(sec)]
     _abi.check(getattr(lib, entry)(*head, *observed, *outputs, *tail))

@@ -14,7 +14,7 @@ faces (TRPL_MCMC_FOLD, include/trpl.h), which keeps the proposal symmetric, so e
 a posterior that lies against a face of the box needs.  The proposal, the accept/reject step and the sums of split-R-hat run on the device;
 there is no CPU fallback.  This module takes and returns numpy arrays and goes through the host-buffer calls, like `refine`: the
 likelihood it drives is any callable on a host X.  A pipeline whose chains stay on the device composes the same steps from
-device.mcmc_propose_device / mcmc_accept_device / mcmc_chain_stats_device.
+device.mcmc_propose_device / mcmc_levels_device / mcmc_accept_device / mcmc_chain_stats_device.
 
 Chains.samples() returns (X, W = 1): what posterior.moments / quantiles / columns / corner / credible_intervals and
 posterior_predictive take."""
@@ -81,6 +81,24 @@ def accept(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device=0, info
     return accepted
 
 
+def reject_levels(LL, tf, chain0, seed, step, device=0, info=None):
+    """level (count,): for every chain the sse level above which accept(), called with the same (tf, chain0, seed, step), is certain
+    to reject the proposal (trpl_mcmc_levels) -- the cut_levels of driver.loglik, one per proposal.  The accept step's uniform
+    depends on (seed; chain, step) only, so the level is known before the proposal is solved.  +inf where nothing may be cut: a
+    chain whose LL is NaN or -inf accepts anything.  LL must be minus the summed sse, i.e. come from a likelihood whose P starts
+    from zero (include/trpl.h has the argument)."""
+    LL = _f64(LL)
+    if LL.ndim != 1:
+        raise ValueError("LL must be (count,)")
+    level = np.empty(LL.shape[0])
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_mcmc_levels(_abi.ptr(LL), LL.shape[0], float(tf), int(chain0), int(seed) & _M64, int(step) & _M32,
+                                           _abi.ptr(level), int(device), _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value)
+    return level
+
+
 def chain_stats(H, t0=0, t1=None, Q=None, device=0, info=None):
     """(mean, m2), each (Q,): per column q < Q of the history H (n, ldh >= Q), the mean and the centred sum of squares over the steps
     [t0, t1), both sums in ascending t from +0.0 (trpl_mcmc_chain_stats): the plain loop's bits.  Q defaults to ldh, t1 to n."""
@@ -144,7 +162,7 @@ class Chains:
 
 
 def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0, kind="de", gamma=None, scale=None, jump_every=0,
-        seed=1, keep_every=1, burn=0, max_history_bytes=4 << 30, device=0, info=None, U0=None, bounds="reject"):
+        seed=1, keep_every=1, burn=0, max_history_bytes=4 << 30, device=0, info=None, U0=None, bounds="reject", early_reject=False):
     """Advance the C chains that start at X0 (C, ncol), LL0 (C,) by `sweeps` sweeps; loglik(X) -> LL is any callable (the fused
     likelihood, a toy).  Returns Chains: the states after the sweeps burn, burn + keep_every, ...
 
@@ -157,6 +175,13 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
     sweep (a jump between modes); scale (the uniform jitter's half-width, a scalar or (A,)) defaults to 1e-3.  kind="rw": the random
     walk of half-width scale, which must be given; no partners.  U0 (C, A): the unit coordinates of X0 when they are at hand (start
     returns them); default refine.unit_coords(X0).
+
+    early_reject=True (Solonen et al. 2012): each half-sweep computes reject_levels of its chains from their current LL and calls
+    loglik(Xp[ok], cut_levels=levels[ok]), so a proposal whose running squared error makes its rejection certain stops being
+    solved (trpl_loglik_cut_levels).  The callable must accept that keyword, one level per row, and its LL must be minus the summed
+    sse of a P started from zero (driver.loglik with P=None); LL0 must come from such a call too.  accept is called unchanged, and
+    the returned Chains are bit for bit those of the run without it: a cut proposal is one that run rejects.  info then also
+    receives early_reject, the share of solved proposals that were given a finite level.
 
     The history of n kept sweeps takes n C (A + ncol + 1) 8 + n C bytes; a run whose history would exceed max_history_bytes raises
     ValueError before anything is solved.  ValueError for an odd C or C < 4, or a bounds that is neither string.  info receives
@@ -200,6 +225,7 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
     hU, hX = np.empty((len(kept), C, A)), np.empty((len(kept), C, lo.size))
     hLL, hAcc = np.empty((len(kept), C)), np.empty((len(kept), C), dtype=bool)
     shares, outside, folded, row = [], 0, 0, 0
+    levelled, solved = 0, 0
     moved = np.empty(C, dtype=bool)
     for t in range(sweeps):
         g = 1.0 if jump_every > 0 and (t + 1) % jump_every == 0 else gamma0
@@ -209,7 +235,12 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
                                          fold=bounds == "fold")
             ok = inside != 0
             LLp = np.full(b - a, -np.inf)
-            if ok.any():
+            if ok.any() and early_reject:
+                levels = reject_levels(LL[a:b], tf, a, seed, 2 * t + k, device=device)[ok]
+                LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok]), cut_levels=levels))
+                levelled += int(np.isfinite(levels).sum())
+                solved += int(ok.sum())
+            elif ok.any():
                 LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok])))
             outside += int((~ok).sum())
             folded += int((inside == 2).sum())
@@ -220,4 +251,6 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
             row += 1
     if info is not None:
         info.update(accept=shares, outside=outside / float(sweeps * C), folded=folded / float(sweeps * C))
+        if early_reject:
+            info.update(early_reject=levelled / float(max(solved, 1)))
     return Chains(hU, hX, hLL, hAcc, device=device)

@@ -182,7 +182,7 @@ extern "C" {
                                      gpu_info["weighted"] */
 #define TRPL_FLAG_CUT 0x800000      /* the FAST likelihood-mode steppers whose sink stops a system as soon as its running sse is above
                                      the caller's sse_cut (their own instantiations, trpl::cut::[predict::][pair::]stepper...; the
-                                     existing kernels are the same machine code as without them).  SET BY trpl_loglik_cut[_dev]
+                                     existing kernels are the same machine code as without them).  SET BY trpl_loglik_cut[_levels][_dev]
                                      THEMSELVES: every other entry point has no sse_cut and answers TRPL_ERR_ARG before it touches
                                      a device.  trpl_kernel_name / trpl_kernel_variant accept it and name the instantiation after
                                      the usual launch checks.  FAST only, every L, both FAST kernels, with and without
@@ -634,6 +634,38 @@ int trpl_loglik_cut_dev(const double *X, int64_t S, int32_t C, const double *len
                         int64_t obs_ld, const int64_t *n_obs /*host*/, double sse_cut, double *P, double *sse,
                         int32_t *cut_col, int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags,
                         void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * trpl_loglik_cut_levels -- trpl_loglik_cut with A LEVEL PER SYSTEM: the arguments of trpl_loglik_cut[_dev] with
+ *   cut_level   [C][S] f64, indexed like cut_col,
+ * in the place of sse_cut.  TRPL_FLAG_CUT is set by the call; the kernels (the same 20 trpl::cut:: instantiations), flags,
+ * combinations and refusals are trpl_loglik_cut's.  Its consumer is a Metropolis sampler, whose rejection threshold differs from
+ * chain to chain and is known before the solve (trpl_mcmc_levels below).
+ * System (c, s) tests `running sse > cut_level[c][s]` after every batch its sink adds.  Every output of a system is what
+ * trpl_loglik_cut returns for it at sse_cut = cut_level[c][s], bit for bit: a cut system reports the truncated plain call, an
+ * uncut system the full plain call, and the paragraphs above on status, floor_col, iters_total and non-converged systems hold
+ * with the system's own level.  The proof is trpl_loglik_cut's, system by system: the sum never decreases.
+ * A system's outputs do not depend on the levels of other systems, on its wavefront partner, on the pairing rule, on the seam
+ * form or on sharding: the level is read by the system's own sink through its own output row (the two sinks of a paired
+ * wavefront each read theirs), once per batch, as a wave-uniform scalar load.
+ * P[s] -= sum_c sse[c][s] over the reported values, as in trpl_loglik_cut.
+ * The host form checks every level (>= 0 or +inf) before it touches a device: a NaN or negative level is TRPL_ERR_ARG and the
+ * message names the curve and the sample ("cut_level[c=..][s=..]").  The _dev form cannot look at the levels: there a NaN level
+ * never cuts, and a negative level cuts after the first batch.  A NULL cut_level is TRPL_ERR_ARG.  The host form stages
+ * cut_level like cut_col.  There is no trpl_loglik_multi* form.
+ * ------------------------------------------------------------------------------------- */
+int trpl_loglik_cut_levels(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns,
+                           int32_t L, int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
+                           const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                           int64_t obs_ld, const int64_t *n_obs, const double *cut_level /* [C][S] */, double *P, double *sse,
+                           int32_t *cut_col, int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags,
+                           int32_t device, double *seconds);
+int trpl_loglik_cut_levels_dev(const double *X, int64_t S, int32_t C, const double *lengths_nm /*host*/, double time_ns,
+                               int32_t L, int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
+                               const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                               int64_t obs_ld, const int64_t *n_obs /*host*/, const double *cut_level /* [C][S] */, double *P,
+                               double *sse, int32_t *cut_col, int32_t *status, int64_t *iters_total, int32_t *floor_col,
+                               uint32_t flags, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * trpl_loglik_multi -- trpl_loglik / trpl_loglik_obs over several devices from ONE host thread:
@@ -1263,6 +1295,31 @@ int trpl_mcmc_chain_stats_dev(const double *H, int64_t n, int64_t ldh, int64_t Q
                               void *stream);
 int trpl_mcmc_chain_stats(const double *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, double *mean, double *m2,
                           int32_t device, double *seconds);
+
+/* ---------------------------------------------------------------------------------------
+ * trpl_mcmc_levels -- EARLY REJECTION (Solonen et al. 2012): for each of `count` chains the level of trpl_loglik_cut_levels above
+ * which a proposal's running sse makes its rejection by trpl_mcmc_accept certain.  The accept step's uniform depends on (seed;
+ * chain, step) only, so the level is known before the proposal is solved; cutting at it changes no decision of the chain, it only
+ * stops paying for proposals whose rejection is already decided.
+ * One thread per chain; LL [count] in, level [count] out.  xi is drawn exactly as trpl_mcmc_accept draws it for the same (seed,
+ * chain0 + i, step): Philox counter word 0x100 + 9, the same 53-bit uniform, the same log.  level = +inf (never cut) when LL is NaN
+ * or not above -inf, when xi == 0, or when neither candidate verifies.  The candidates, in order: l0 = -(LL + tf log(xi)), then
+ * l0 + (fabs(LL) + l0) 2^-40.  A candidate l is taken only if, with q = -l, the accept step's own expression dq = (q - LL) / tf
+ * satisfies dq < 0 && !(log(xi) < dq).
+ * WHY THAT IS SAFE.  Subtraction and division by tf > 0 are monotone under round-to-nearest, so every LLp <= q has d = (LLp - LL) /
+ * tf <= dq: d < 0 and log(xi) < d is false, and trpl_mcmc_accept with the same (seed, chain, step) rejects it.  A system cut at
+ * `level` reports sse_c > level, and the sample's P = fl(... fl(0 - sse_0) ... - sse_c ...) <= -sse_c < q because every term is
+ * non-negative and rounding is monotone.  Hence a cut proposal is always one the uncut run would have rejected, and its reported
+ * LLp is never stored: the chain's U, X, LL and accept flags are those of the run without levels, bit for bit.
+ * PRECONDITION: the likelihood starts P from +0.0, so that LL = -sum sse; the level of a chain is given to each of its C curves (a
+ * curve alone above the level is enough, since the others only lower P further).
+ * Refused (TRPL_ERR_ARG): count < 1 or more chains than the grid holds; tf not finite or not > 0; chain0 < 0; "LL is NULL", "level is
+ * NULL".  Python: trpl_amd.mcmc.reject_levels, trpl_amd.mcmc.run(early_reject=True), trpl_amd.device.mcmc_levels_device.
+ * ------------------------------------------------------------------------------------- */
+int trpl_mcmc_levels_dev(const double *LL, int64_t count, double tf, int64_t chain0, uint64_t seed, uint32_t step, double *level,
+                         void *stream);
+int trpl_mcmc_levels(const double *LL, int64_t count, double tf, int64_t chain0, uint64_t seed, uint32_t step, double *level,
+                     int32_t device, double *seconds);
 
 /* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the

@@ -9,8 +9,11 @@ of --reps.  Shape: Power_scan x 65 536 samples x 3 curves, L = 128, T = 8000 (th
      sse_cut = exact_cut_margin(tf) + best_total for tf = 1 and the larger --tf values; recorded per tf: cut_fraction, the
      sum of iters_total cut / plain, the time ratio cut / plain, and how far the time ratio falls short of the iteration
      ratio (cut waves leave at batch boundaries, and a pair waits for its slower half).  No target: a measurement.
+  3. LEVELS (--levels): trpl_loglik_cut_levels_dev with one value in every entry of cut_level against trpl_loglik_cut_dev at that
+     sse_cut -- the same outputs bit for bit (asserted), so the ratio is the cost of reading the level per system: at +inf (nothing
+     is cut) and at the median of the plain sse (half the systems are).  No target: a measurement.  --no-gain leaves out part 2.
 One JSON line; the yardstick of every ratio is the plain call of the same run.
-    python tools/bench_cut.py [--samples 65536] [--steps 8000] [--reps 3] [--tf 10,100] [--out FILE]"""
+    python tools/bench_cut.py [--samples 65536] [--steps 8000] [--reps 3] [--tf 10,100] [--levels] [--no-gain] [--out FILE]"""
 import argparse
 import gzip
 import json
@@ -34,6 +37,8 @@ def main():
     ap.add_argument("--steps", type=int, default=8000)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--tf", default="10,100", help="tempering factors measured beside tf = 1")
+    ap.add_argument("--levels", action="store_true", help="also time trpl_loglik_cut_levels_dev at a uniform level array")
+    ap.add_argument("--no-gain", action="store_true", help="leave out part 2")
     ap.add_argument("--out", default=None, help="also append the line to this file")
     args = ap.parse_args()
     import torch
@@ -88,7 +93,42 @@ def main():
                                   "kernel": trpl_amd._abi.kernel_name(S * C, L, T, fl | trpl_amd._abi.FLAG_CUT)}
         ok = ok and a / b >= REQUIRED
 
+    # ---- 3. the level call beside the scalar call at the same level ----
+    if args.levels:
+        lv = torch.empty((C, S), dtype=torch.float64, device=dev)
+
+        def levels(fl, o, n):
+            P.zero_()
+            tdev.loglik_cut_levels_device(X, ini_d, lens, T * DT, L, T, o, n, lv, P, sse, cut_col=cc, status=st, iters_total=it, flags=fl)
+
+        line["levels"] = {}
+        for mode, fl in modes:
+            plain(fl, obs, n_syn); torch.cuda.synchronize()
+            rec = {}
+            for what, level in (("inf", float("inf")), ("median", float(sse[st == 0].median()))):
+                lv.fill_(level)
+                cut(fl, obs, n_syn, level); torch.cuda.synchronize()
+                want = (P.clone(), sse.clone(), cc.clone(), it.clone())
+                levels(fl, obs, n_syn); torch.cuda.synchronize()
+                assert all(torch.equal(a, b) for a, b in zip(want, (P, sse, cc, it))), "the level call is the scalar call, bit for bit"
+                ts, tl = [], []
+                for _ in range(args.reps):                                                        # interleaved
+                    ts.append(timed(cut, fl, obs, n_syn, level))
+                    tl.append(timed(levels, fl, obs, n_syn))
+                a, b = float(np.median(ts)), float(np.median(tl))
+                rec[what] = {"level": level, "cut_fraction": float((cc >= 0).double().mean()), "levels_over_scalar_time": b / a,
+                             "scalar_s": ts, "levels_s": tl}
+            line["levels"][mode] = rec
+
     # ---- 2. gain against the shipped observations ----
+    if args.no_gain:
+        line["overhead_ok"] = ok
+        s = json.dumps(line)
+        print(s, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(s + "\n")
+        return 0 if ok else 1
     work_dir = tempfile.mkdtemp(prefix="trpl_cut_")
     obs_csv = os.path.join(work_dir, "Balancedhighsurf_Power_scan_Observations.csv")
     with gzip.open(os.path.join(GOLDEN, "obs_balanced_full.csv.gz"), "rb") as fh, open(obs_csv, "wb") as out:

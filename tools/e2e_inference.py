@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--fold]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--fold] [--early-reject]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -38,6 +38,10 @@ those of the importance run, which are printed; seconds["mcmc"].  --rw x uses a 
 instead.  --fold reflects a proposal that leaves the prior box back at its faces (mcmc.run(bounds="fold"): DESIGN.md section 25),
 so that every proposal is solved; "mcmc" then gains "bounds" and "folded", the share of proposals that were reflected.  Without
 --mcmc the output is unchanged, and so is "mcmc" without --fold.
+--early-reject (with --mcmc) stops solving a proposal once its rejection is certain (mcmc.run(early_reject=True): DESIGN.md section
+26; the chain is the same, bit for bit) and adds "early_reject" to "mcmc": the share of solved proposals that were cut and the
+system-timesteps solved.  With or without it "mcmc" holds "system_timesteps", the solver iterations summed over every proposal, and
+the same numbers are printed.
 """
 import json
 import sys
@@ -67,6 +71,7 @@ if "--shrink" in sys.argv:
     del sys.argv[k:k + 2]
 MCMC = "--mcmc" in sys.argv
 FOLD = "--fold" in sys.argv
+EARLY = "--early-reject" in sys.argv
 CHAINS, SWEEPS, RW = 1024, 200, None
 for flag, conv in (("--chains", int), ("--sweeps", int), ("--rw", float)):
     if flag in sys.argv:
@@ -79,7 +84,7 @@ for flag, conv in (("--chains", int), ("--sweeps", int), ("--rw", float)):
             SWEEPS = value
         else:
             RW = value
-sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented", "--mcmc", "--fold")]
+sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented", "--mcmc", "--fold", "--early-reject")]
 import numpy as np
 import torch
 import trpl_amd
@@ -248,11 +253,23 @@ if MCMC:
     from trpl_amd import mcmc, posterior
     t11 = sync()
 
-    def fused_chain(X2):                                         # the fused likelihood of the proposals of one half-sweep
+    work = {"iters": 0, "cut": 0, "solved": 0}
+
+    def fused_chain(X2, cut_levels=None):                        # the fused likelihood of the proposals of one half-sweep
         n = X2.shape[0]
         Xd = torch.from_numpy(np.ascontiguousarray(X2)).to(dev)
-        P2 = torch.zeros(n, dtype=torch.float64, device=dev)
-        tdev.loglik_device(Xd, ini_d, lens, T * dt, L, T, obs, [T + 1] * C, P2, torch.empty((C, n), dtype=torch.float64, device=dev))
+        P2 = torch.zeros(n, dtype=torch.float64, device=dev)         # from zero: what early rejection's levels assume
+        sse2 = torch.empty((C, n), dtype=torch.float64, device=dev)
+        it2 = torch.empty((C, n), dtype=torch.int64, device=dev)
+        if cut_levels is None:
+            tdev.loglik_device(Xd, ini_d, lens, T * dt, L, T, obs, [T + 1] * C, P2, sse2, iters_total=it2)
+        else:                                                    # one level per proposal, given to each of its curves
+            lv = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(cut_levels, (C, n)))).to(dev)
+            cc = torch.empty((C, n), dtype=torch.int32, device=dev)
+            tdev.loglik_cut_levels_device(Xd, ini_d, lens, T * dt, L, T, obs, [T + 1] * C, lv, P2, sse2, cut_col=cc, iters_total=it2)
+            work["cut"] += int((cc >= 0).any(dim=0).sum())
+        work["iters"] += int(it2.sum())
+        work["solved"] += n
         return P2.cpu().numpy()
 
     tf = n_obs * c_val
@@ -260,7 +277,7 @@ if MCMC:
     minfo = {}
     burn = SWEEPS // 2
     ch = mcmc.run(fused_chain, X0, LL0, lo, hi, lg, sweeps=SWEEPS, tf=tf, seed=42, burn=burn, info=minfo, U0=U0,
-                  **({"kind": "rw", "scale": RW} if RW is not None else {}), **({"bounds": "fold"} if FOLD else {}))
+                  **({"kind": "rw", "scale": RW} if RW is not None else {}), **({"bounds": "fold"} if FOLD else {}), **({"early_reject": True} if EARLY else {}))
     rhat = ch.rhat()
     Xs, Ws = ch.samples()
     Xg = Xs / sm.UNIT_CONVERSIONS
@@ -278,6 +295,12 @@ if MCMC:
                    "max_loglik": float(ch.LL.max()), "median_loglik": float(np.median(ch.LL[-1])),
                    "quantiles": {n: {"truth": float(tr), "chain": [float(v) for v in q_chain[:, k]],
                                      "importance": [float(v) for v in q_imp[:, k]]} for k, (n, tr) in enumerate(zip(names, truth))}}
+    out["mcmc"]["system_timesteps"] = work["iters"]
+    if EARLY:
+        out["mcmc"]["early_reject"] = {"cut_share_of_solved_proposals": work["cut"] / float(max(work["solved"], 1)),
+                                       "levelled_share": minfo["early_reject"]}
+    print("mcmc: early_reject=%s: %d proposals solved, %.4f of them cut, %d system-timesteps (solver iterations)"
+          % (EARLY, work["solved"], work["cut"] / float(max(work["solved"], 1)), work["iters"]), file=sys.stderr)
     if FOLD:
         out["mcmc"].update(bounds="fold", folded=minfo["folded"])
         print("mcmc: bounds=fold, %.4f of the proposals reflected at a face" % minfo["folded"], file=sys.stderr)
