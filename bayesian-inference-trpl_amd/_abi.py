@@ -76,6 +76,7 @@ CORNER_PRIMARY, CORNER_MAX_COLS, CORNER_MAX_BINS = 13, 19, 128
  COL_TAU_EFF, COL_TAU_RAD, COL_S_SUM, COL_MU_EFF, COL_EPSILON, COL_TAU_SUM) = range(19)
 REFINE_MAX_DIMS, REFINE_MAX_PARENTS = 16, 1 << 20      # TRPL_REFINE_MAX_DIMS, TRPL_REFINE_MAX_PARENTS
 MCMC_FOLD = 0x10              # TRPL_MCMC_FOLD: trpl_mcmc_propose reflects a proposal back at the faces of the unit cube
+MCMC_MAX_RUNGS = 64           # TRPL_MCMC_MAX_RUNGS: temperatures of one trpl_mcmc_*_rungs / trpl_mcmc_swap call
 
 
 class TrplError(RuntimeError):
@@ -224,6 +225,16 @@ SIGNATURES = {
     "trpl_mcmc_chain_stats": [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _pd],
     "trpl_mcmc_levels_dev": [_vp, _i64, _f64, _i64, _u64, _u32, _vp, _vp],
     "trpl_mcmc_levels": [_vp, _i64, _f64, _i64, _u64, _u32, _vp, _i32, _pd],
+    "trpl_mcmc_propose_rungs_dev": [_vp, _vp, _i64, _i64, _i64, _i32, _f64, _vp, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp,
+                                    _vp],
+    "trpl_mcmc_propose_rungs": [_vp, _vp, _i64, _i64, _i64, _i32, _f64, _vp, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _i32,
+                                _pd],
+    "trpl_mcmc_accept_rungs_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _vp],
+    "trpl_mcmc_accept_rungs": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _i32, _pd],
+    "trpl_mcmc_levels_rungs_dev": [_vp, _i64, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _vp],
+    "trpl_mcmc_levels_rungs": [_vp, _i64, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _i32, _pd],
+    "trpl_mcmc_swap_dev": [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _i64, _u64, _u32, _vp, _vp],
+    "trpl_mcmc_swap": [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _i64, _u64, _u32, _vp, _i32, _pd],
     "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
     "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
 }

@@ -5,7 +5,7 @@
 //       refine_common.hpp) with the counter's third word moved to 0x100 + j: call j < 8 gives xi[2j], xi[2j + 1], call 8 the two
 //       partner uniforms.  With partners (differential evolution, ter Braak 2006): u'_d = (u_d + gamma (pa_d - pb_d)) + scale_d (2
 //       xi_d - 1); without (random walk): u'_d = u_d + scale_d (2 xi_d - 1).  inside = every u'_d in [0, 1]; X by the sampler's
-//       expressions from u', inside or not, as draw_oriented_kernel forms it.  The body is propose_body<A, FOLD>; propose_kernel
+//       expressions from u', inside or not, as draw_oriented_kernel forms it.  The body is propose_body<A, FOLD, RUNGS>; propose_kernel
 //       is FOLD = false.
 //   propose_fold_kernel<A>  the same body with FOLD = true (TRPL_MCMC_FOLD, include/trpl.h): each u'_d that fails the range test
 //       is reflected back into [0, 1] before it is stored and turned into X; inside = 0 (a NaN is left), 2 (folded) or 1 (untouched).
@@ -17,6 +17,15 @@
 //       or that plus a few ulps, whichever the accept step's own expression confirms; +inf (never cut) when neither does.
 //   chain_stats_kernel    one thread per column q of a history H [n][ldh]: the mean and the centred sum of squares over the steps
 //       [t0, t1), both sums in ascending t from +0.0.  Adjacent threads read adjacent addresses.
+// Parallel tempering (trpl_mcmc_*_rungs*, trpl_mcmc_swap*, include/trpl.h): K rungs of `group` chains each in one
+// contiguous block, row k group + c chain c of rung k, advanced by one launch each.
+//   propose_rungs_kernel<A>, propose_rungs_fold_kernel<A>   propose_body with the partners of chain i narrowed to the rows
+//       [(i / group) group, + group) of `partners` and P = group in the index expressions: a rung's slice is propose_kernel's bits.
+//   accept_rungs_kernel<A>, levels_rungs_kernel   accept_body and levels_body with tf = ladder[i / group]; the ladder travels by value.
+//   swap_kernel<A>        one thread per row of the block; the thread of the lower row a of a pair (k, k + 1), k = parity, parity + 2, ..,
+//       decides it: xi of counter word 0x10a keyed by row a, d = (LL[b] - LL[a]) * (1 / tf[k] - 1 / tf[k + 1]), the rows of U, X and LL
+//       exchanged when neither LL is NaN and d >= 0 or log(xi) < d.  The thread of an upper row writes nothing; an unpaired row's
+//       writes swapped = 0 only.
 // Compiled with -ffp-contract=off like refine.hip: every result is its expression with one rounding per operation.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -31,10 +40,14 @@ namespace mcmc {                                                 // the kernels 
 using namespace refine;
 
 constexpr uint32_t kStream = 0x100;                              // third counter word: 0x100 + j, apart from the draws' j < 8
-constexpr uint32_t kPartnerCall = 8, kAcceptCall = 9;
+constexpr uint32_t kPartnerCall = 8, kAcceptCall = 9, kSwapCall = 10;
 
 struct Scale {
     double s[16];
+};
+
+struct Ladder {                                                  // the temperatures of the rungs, by value like Scale
+    double tf[TRPL_MCMC_MAX_RUNGS];
 };
 
 // fold (include/trpl.h, TRPL_MCMC_FOLD): v reflected at the faces of [0, 1] as often as needed.  Called only for a v that failed the
@@ -47,13 +60,18 @@ __device__ __forceinline__ double fold_outside(double v)
     return r;
 }
 
-template <int A, bool FOLD>
-__device__ __forceinline__ void propose_body(const double *U, const double *partners, int64_t count, int64_t P, double gamma, const Scale &sc,
-                                             int64_t chain0, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, const Box &bx, double *Up,
-                                             double *Xp, int32_t *inside)
+// RUNGS: the partners of chain i are the `group` rows of its rung, [(i / group) group, + group) of `partners`
+template <int A, bool FOLD, bool RUNGS>
+__device__ __forceinline__ void propose_body(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, double gamma,
+                                             const Scale &sc, int64_t chain0, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, const Box &bx,
+                                             double *Up, double *Xp, int32_t *inside)
 {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= count) return;
+    if (RUNGS) {
+        partners += (i / group) * group * A;
+        P = group;
+    }
     const uint64_t n = (uint64_t)(chain0 + i);
     double xi[A];
 #pragma unroll
@@ -104,31 +122,40 @@ __device__ __forceinline__ void propose_body(const double *U, const double *part
 #define TRPL_PROPOSE_PARAMS                                                                                                            \
     const double *U, const double *partners, int64_t count, int64_t P, double gamma, const Scale sc, int64_t chain0, uint32_t seed_lo,  \
         uint32_t seed_hi, uint32_t step, const Box bx, double *Up, double *Xp, int32_t *inside
-#define TRPL_PROPOSE_ARGS U, partners, count, P, gamma, sc, chain0, seed_lo, seed_hi, step, bx, Up, Xp, inside
+#define TRPL_PROPOSE_ARGS(group) U, partners, count, P, group, gamma, sc, chain0, seed_lo, seed_hi, step, bx, Up, Xp, inside
 
 template <int A>
 __global__ void __launch_bounds__(kThreads) propose_kernel(TRPL_PROPOSE_PARAMS)
 {
-    propose_body<A, false>(TRPL_PROPOSE_ARGS);
+    propose_body<A, false, false>(TRPL_PROPOSE_ARGS(0));
 }
 
 template <int A>
 __global__ void __launch_bounds__(kThreads) propose_fold_kernel(TRPL_PROPOSE_PARAMS)
 {
-    propose_body<A, true>(TRPL_PROPOSE_ARGS);
+    propose_body<A, true, false>(TRPL_PROPOSE_ARGS(0));
+}
+
+template <int A>
+__global__ void __launch_bounds__(kThreads) propose_rungs_kernel(TRPL_PROPOSE_PARAMS, int64_t group)
+{
+    propose_body<A, false, true>(TRPL_PROPOSE_ARGS(group));
+}
+
+template <int A>
+__global__ void __launch_bounds__(kThreads) propose_rungs_fold_kernel(TRPL_PROPOSE_PARAMS, int64_t group)
+{
+    propose_body<A, true, true>(TRPL_PROPOSE_ARGS(group));
 }
 
 #undef TRPL_PROPOSE_PARAMS
 #undef TRPL_PROPOSE_ARGS
 
 template <int A>
-__global__ void __launch_bounds__(kThreads) accept_kernel(double *U, double *X, double *LL, const double *Up, const double *Xp,
-                                                          const double *LLp, const int32_t *inside, int64_t count, int32_t ncol,
-                                                          double tf, int64_t chain0, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
-                                                          int32_t *accepted)
+__device__ __forceinline__ void accept_body(int64_t i, double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp,
+                                            const int32_t *inside, int32_t ncol, double tf, int64_t chain0, uint32_t seed_lo,
+                                            uint32_t seed_hi, uint32_t step, int32_t *accepted)
 {
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= count) return;
     const uint64_t n = (uint64_t)(chain0 + i);
     uint32_t r[4];
     philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), kStream + kAcceptCall, step, seed_lo, seed_hi, r);
@@ -144,14 +171,36 @@ __global__ void __launch_bounds__(kThreads) accept_kernel(double *U, double *X, 
     LL[i] = llp;
 }
 
-// Early rejection (include/trpl.h, trpl_mcmc_levels): a candidate level l is taken only if the accept step's own d, formed for a proposal
-// with LLp = -l, is negative and not above log(xi) -- then every LLp <= -l has a d no larger (subtraction and division by tf > 0 are
-// monotone) and accept_kernel rejects it with the same (seed, chain, step).
-__global__ void __launch_bounds__(kThreads) levels_kernel(const double *LL, int64_t count, double tf, int64_t chain0, uint32_t seed_lo,
-                                                          uint32_t seed_hi, uint32_t step, double *level)
+#define TRPL_ACCEPT_PARAMS(tf_type)                                                                                                    \
+    double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside, int64_t count,        \
+        int32_t ncol, tf_type tf, int64_t chain0, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, int32_t *accepted
+#define TRPL_ACCEPT_ARGS(tf) i, U, X, LL, Up, Xp, LLp, inside, ncol, tf, chain0, seed_lo, seed_hi, step, accepted
+
+template <int A>
+__global__ void __launch_bounds__(kThreads) accept_kernel(TRPL_ACCEPT_PARAMS(double))
 {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= count) return;
+    accept_body<A>(TRPL_ACCEPT_ARGS(tf));
+}
+
+template <int A>
+__global__ void __launch_bounds__(kThreads) accept_rungs_kernel(TRPL_ACCEPT_PARAMS(const Ladder), int64_t group)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= count) return;
+    accept_body<A>(TRPL_ACCEPT_ARGS(tf.tf[i / group]));
+}
+
+#undef TRPL_ACCEPT_PARAMS
+#undef TRPL_ACCEPT_ARGS
+
+// Early rejection (include/trpl.h, trpl_mcmc_levels): a candidate level l is taken only if the accept step's own d, formed for a proposal
+// with LLp = -l, is negative and not above log(xi) -- then every LLp <= -l has a d no larger (subtraction and division by tf > 0 are
+// monotone) and accept_kernel rejects it with the same (seed, chain, step).
+__device__ __forceinline__ void levels_body(int64_t i, const double *LL, double tf, int64_t chain0, uint32_t seed_lo, uint32_t seed_hi,
+                                            uint32_t step, double *level)
+{
     const uint64_t n = (uint64_t)(chain0 + i);
     uint32_t r[4];
     philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), kStream + kAcceptCall, step, seed_lo, seed_hi, r);
@@ -170,6 +219,65 @@ __global__ void __launch_bounds__(kThreads) levels_kernel(const double *LL, int6
         }
     }
     level[i] = lv;
+}
+
+__global__ void __launch_bounds__(kThreads) levels_kernel(const double *LL, int64_t count, double tf, int64_t chain0, uint32_t seed_lo,
+                                                          uint32_t seed_hi, uint32_t step, double *level)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= count) return;
+    levels_body(i, LL, tf, chain0, seed_lo, seed_hi, step, level);
+}
+
+// The safety argument above is per chain -- it never compares two chains -- so it holds with a temperature per rung.
+__global__ void __launch_bounds__(kThreads) levels_rungs_kernel(const double *LL, int64_t count, const Ladder tf, int64_t group,
+                                                                int64_t chain0, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
+                                                                double *level)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= count) return;
+    levels_body(i, LL, tf.tf[i / group], chain0, seed_lo, seed_hi, step, level);
+}
+
+// Replica exchange (include/trpl.h, trpl_mcmc_swap): count = K group rows.  Row i belongs to rung k = i / group; it is the lower row of a
+// pair when k - parity is even and not negative and k + 1 < K, the upper row when k - parity is odd and positive, else unpaired.
+template <int A>
+__global__ void __launch_bounds__(kThreads) swap_kernel(double *U, double *X, double *LL, int64_t count, int32_t K, int64_t group,
+                                                        int32_t ncol, const Ladder tf, int32_t parity, int64_t chain0, uint32_t seed_lo,
+                                                        uint32_t seed_hi, uint32_t step, int32_t *swapped)
+{
+    const int64_t a = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (a >= count) return;
+    const int32_t k = (int32_t)(a / group);
+    const int32_t rel = k - parity;
+    if (rel > 0 && (rel & 1)) return;                            // the upper row of a pair: its lower row's thread writes it
+    if (rel < 0 || k + 1 >= K) {                                 // unpaired
+        swapped[a] = 0;
+        return;
+    }
+    const int64_t b = a + group;
+    const uint64_t n = (uint64_t)(chain0 + a);
+    uint32_t r[4];
+    philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), kStream + kSwapCall, step, seed_lo, seed_hi, r);
+    const double xi = res53(r[0], r[1]);
+    const double la = LL[a], lb = LL[b];
+    const double d = (lb - la) * (1.0 / tf.tf[k] - 1.0 / tf.tf[k + 1]);
+    const bool take = !(la != la) && !(lb != lb) && (d >= 0.0 || log(xi) < d);
+    swapped[a] = swapped[b] = take ? 1 : 0;
+    if (!take) return;
+#pragma unroll
+    for (int j = 0; j < A; j++) {
+        const double ua = U[a * A + j], ub = U[b * A + j];
+        U[a * A + j] = ub;
+        U[b * A + j] = ua;
+    }
+    for (int c = 0; c < ncol; c++) {
+        const double xa = X[a * ncol + c], xb = X[b * ncol + c];
+        X[a * ncol + c] = xb;
+        X[b * ncol + c] = xa;
+    }
+    LL[a] = lb;
+    LL[b] = la;
 }
 
 __global__ void __launch_bounds__(kThreads) chain_stats_kernel(const double *H, int64_t ldh, int64_t Q, int64_t t0, int64_t t1,
@@ -250,6 +358,50 @@ static int check_levels(const void *LL, int64_t count, double tf, int64_t chain0
     if (chain0 < 0) return api_fail(TRPL_ERR_ARG, "chain0=%lld must be >= 0", (long long)chain0);
     if (!LL) return api_fail(TRPL_ERR_ARG, "LL is NULL");
     if (!level) return api_fail(TRPL_ERR_ARG, "level is NULL");
+    return TRPL_OK;
+}
+
+// the ladder of the *_rungs calls and of the swap: K, group and the K temperatures, copied into the kernel argument
+static int check_ladder(int32_t K, int64_t group, const double *tf, mcmc::Ladder &lad)
+{
+    if (K < 1 || K > TRPL_MCMC_MAX_RUNGS) return api_fail(TRPL_ERR_ARG, "K=%d must be in [1, %d]", K, TRPL_MCMC_MAX_RUNGS);
+    if (group < 1) return api_fail(TRPL_ERR_ARG, "group=%lld must be >= 1", (long long)group);
+    if (int rc = refine_check_blocks("group", group, "chains")) return rc;
+    if (!tf) return api_fail(TRPL_ERR_ARG, "tf is NULL");
+    lad = mcmc::Ladder();
+    for (int k = 0; k < K; k++) {
+        if (!(isfinite(tf[k]) && tf[k] > 0.0)) return api_fail(TRPL_ERR_ARG, "tf[%d]=%g must be finite and > 0", k, tf[k]);
+        lad.tf[k] = tf[k];
+    }
+    return TRPL_OK;
+}
+
+static int check_rung_count(int64_t count, int32_t K, int64_t group)
+{
+    if (count != (int64_t)K * group)
+        return api_fail(TRPL_ERR_ARG, "count=%lld must be K * group = %d * %lld", (long long)count, K, (long long)group);
+    return TRPL_OK;
+}
+
+static int check_propose_rungs(int64_t count, int64_t P, int64_t group)
+{
+    if (group < 2) return api_fail(TRPL_ERR_ARG, "group=%lld must be >= 2", (long long)group);
+    if (P < group || P % group) return api_fail(TRPL_ERR_ARG, "P=%lld must be a positive multiple of group=%lld", (long long)P, (long long)group);
+    if (count > P) return api_fail(TRPL_ERR_ARG, "count=%lld must be <= P=%lld", (long long)count, (long long)P);
+    return TRPL_OK;
+}
+
+static int check_swap(const void *U, const void *X, const void *LL, int32_t K, int64_t group, int32_t A, int32_t ncol, const double *tf,
+                      int32_t parity, int64_t chain0, const void *swapped, mcmc::Ladder &lad)
+{
+    if (int rc = check_ladder(K, group, tf, lad)) return rc;
+    if (int rc = check_chains((int64_t)K * group, A, chain0)) return rc;
+    if (ncol < 1 || ncol > 16) return api_fail(TRPL_ERR_ARG, "ncol=%d must be in [1, 16]", ncol);
+    if (parity != 0 && parity != 1) return api_fail(TRPL_ERR_ARG, "parity=%d must be 0 or 1", parity);
+    if (!U) return api_fail(TRPL_ERR_ARG, "U is NULL");
+    if (!X) return api_fail(TRPL_ERR_ARG, "X is NULL");
+    if (!LL) return api_fail(TRPL_ERR_ARG, "LL is NULL");
+    if (!swapped) return api_fail(TRPL_ERR_ARG, "swapped is NULL");
     return TRPL_OK;
 }
 
@@ -368,6 +520,160 @@ int trpl_mcmc_levels(const double *LL, int64_t count, double tf, int64_t chain0,
     double *dLv = sg.out(level, (size_t)count);
     if (int rc = sg.begin()) return rc;
     if (int rc = trpl_mcmc_levels_dev(dLL, count, tf, chain0, seed, step, dLv, sg.stream())) return rc;
+    return sg.finish(seconds);
+}
+
+int trpl_mcmc_propose_rungs_dev(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, int32_t A, double gamma,
+                                const double *scale, int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol, const double *lo,
+                                const double *hi, const int32_t *do_log, uint32_t flags, double *Up, double *Xp, int32_t *inside, void *stream)
+{
+    mcmc::Scale sc;
+    if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, flags, Up, Xp, inside, sc)) return rc;
+    if (int rc = check_propose_rungs(count, P, group)) return rc;
+    refine::Box bx;
+    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags & ~(uint32_t)TRPL_MCMC_FOLD, A, bx)) return rc;
+    const dim3 grid(refine_blocks(count)), block(refine::kThreads);
+    const bool fold = (flags & TRPL_MCMC_FOLD) != 0;
+    switch (A) {
+#define TRPL_CASE(n)                                                                                                                   \
+    case n:                                                                                                                            \
+        hipLaunchKernelGGL(fold ? mcmc::propose_rungs_fold_kernel<n> : mcmc::propose_rungs_kernel<n>, grid, block, 0,                    \
+                           (hipStream_t)stream, U, partners, count, P, gamma, sc, chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step,  \
+                           bx, Up, Xp, inside, group);                                                                                 \
+        break;
+        TRPL_REFINE_DIMS(TRPL_CASE)
+#undef TRPL_CASE
+    }
+    return refine_launched("mcmc propose rungs");
+}
+
+int trpl_mcmc_propose_rungs(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, int32_t A, double gamma,
+                            const double *scale, int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol, const double *lo,
+                            const double *hi, const int32_t *do_log, uint32_t flags, double *Up, double *Xp, int32_t *inside,
+                            int32_t device, double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    mcmc::Scale sc;
+    if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, flags, Up, Xp, inside, sc)) return rc;
+    if (int rc = check_propose_rungs(count, P, group)) return rc;
+    refine::Box bx;
+    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags & ~(uint32_t)TRPL_MCMC_FOLD, A, bx)) return rc;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const double *dU = sg.in(U, (size_t)count * A), *dP = sg.in(partners, (size_t)P * A);
+    double *dUp = sg.out(Up, (size_t)count * A), *dXp = sg.out(Xp, (size_t)count * ncol);
+    int32_t *dIn = sg.out(inside, (size_t)count);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_mcmc_propose_rungs_dev(dU, dP, count, P, group, A, gamma, scale, chain0, seed, step, ncol, lo, hi, do_log, flags, dUp,
+                                             dXp, dIn, sg.stream()))
+        return rc;
+    return sg.finish(seconds);
+}
+
+int trpl_mcmc_accept_rungs_dev(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp,
+                               const int32_t *inside, int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group, const double *tf,
+                               int64_t chain0, uint64_t seed, uint32_t step, int32_t *accepted, void *stream)
+{
+    mcmc::Ladder lad;
+    if (int rc = check_ladder(K, group, tf, lad)) return rc;
+    if (int rc = check_accept(U, X, LL, Up, Xp, LLp, inside, count, A, ncol, lad.tf[0], chain0, accepted)) return rc;
+    if (int rc = check_rung_count(count, K, group)) return rc;
+    const dim3 grid(refine_blocks(count)), block(refine::kThreads);
+    switch (A) {
+#define TRPL_CASE(n)                                                                                                                   \
+    case n:                                                                                                                            \
+        hipLaunchKernelGGL(mcmc::accept_rungs_kernel<n>, grid, block, 0, (hipStream_t)stream, U, X, LL, Up, Xp, LLp, inside, count, ncol, \
+                           lad, chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step, accepted, group);                                \
+        break;
+        TRPL_REFINE_DIMS(TRPL_CASE)
+#undef TRPL_CASE
+    }
+    return refine_launched("mcmc accept rungs");
+}
+
+int trpl_mcmc_accept_rungs(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
+                           int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group, const double *tf, int64_t chain0,
+                           uint64_t seed, uint32_t step, int32_t *accepted, int32_t device, double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    mcmc::Ladder lad;
+    if (int rc = check_ladder(K, group, tf, lad)) return rc;
+    if (int rc = check_accept(U, X, LL, Up, Xp, LLp, inside, count, A, ncol, lad.tf[0], chain0, accepted)) return rc;
+    if (int rc = check_rung_count(count, K, group)) return rc;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    double *dU = sg.inout(U, (size_t)count * A), *dX = sg.inout(X, (size_t)count * ncol), *dLL = sg.inout(LL, (size_t)count);
+    const double *dUp = sg.in(Up, (size_t)count * A), *dXp = sg.in(Xp, (size_t)count * ncol), *dLLp = sg.in(LLp, (size_t)count);
+    const int32_t *dIn = sg.in(inside, (size_t)count);
+    int32_t *dAcc = sg.out(accepted, (size_t)count);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_mcmc_accept_rungs_dev(dU, dX, dLL, dUp, dXp, dLLp, dIn, count, A, ncol, K, group, tf, chain0, seed, step, dAcc,
+                                            sg.stream()))
+        return rc;
+    return sg.finish(seconds);
+}
+
+int trpl_mcmc_levels_rungs_dev(const double *LL, int64_t count, int32_t K, int64_t group, const double *tf, int64_t chain0, uint64_t seed,
+                               uint32_t step, double *level, void *stream)
+{
+    mcmc::Ladder lad;
+    if (int rc = check_ladder(K, group, tf, lad)) return rc;
+    if (int rc = check_levels(LL, count, lad.tf[0], chain0, level)) return rc;
+    if (int rc = check_rung_count(count, K, group)) return rc;
+    hipLaunchKernelGGL(mcmc::levels_rungs_kernel, dim3(refine_blocks(count)), dim3(refine::kThreads), 0, (hipStream_t)stream, LL, count,
+                       lad, group, chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step, level);
+    return refine_launched("mcmc levels rungs");
+}
+
+int trpl_mcmc_levels_rungs(const double *LL, int64_t count, int32_t K, int64_t group, const double *tf, int64_t chain0, uint64_t seed,
+                           uint32_t step, double *level, int32_t device, double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    mcmc::Ladder lad;
+    if (int rc = check_ladder(K, group, tf, lad)) return rc;
+    if (int rc = check_levels(LL, count, lad.tf[0], chain0, level)) return rc;
+    if (int rc = check_rung_count(count, K, group)) return rc;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const double *dLL = sg.in(LL, (size_t)count);
+    double *dLv = sg.out(level, (size_t)count);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_mcmc_levels_rungs_dev(dLL, count, K, group, tf, chain0, seed, step, dLv, sg.stream())) return rc;
+    return sg.finish(seconds);
+}
+
+int trpl_mcmc_swap_dev(double *U, double *X, double *LL, int32_t K, int64_t group, int32_t A, int32_t ncol, const double *tf,
+                       int32_t parity, int64_t chain0, uint64_t seed, uint32_t step, int32_t *swapped, void *stream)
+{
+    mcmc::Ladder lad;
+    if (int rc = check_swap(U, X, LL, K, group, A, ncol, tf, parity, chain0, swapped, lad)) return rc;
+    const int64_t count = (int64_t)K * group;
+    const dim3 grid(refine_blocks(count)), block(refine::kThreads);
+    switch (A) {
+#define TRPL_CASE(n)                                                                                                                   \
+    case n:                                                                                                                            \
+        hipLaunchKernelGGL(mcmc::swap_kernel<n>, grid, block, 0, (hipStream_t)stream, U, X, LL, count, K, group, ncol, lad, parity,      \
+                           chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step, swapped);                                             \
+        break;
+        TRPL_REFINE_DIMS(TRPL_CASE)
+#undef TRPL_CASE
+    }
+    return refine_launched("mcmc swap");
+}
+
+int trpl_mcmc_swap(double *U, double *X, double *LL, int32_t K, int64_t group, int32_t A, int32_t ncol, const double *tf, int32_t parity,
+                   int64_t chain0, uint64_t seed, uint32_t step, int32_t *swapped, int32_t device, double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    mcmc::Ladder lad;
+    if (int rc = check_swap(U, X, LL, K, group, A, ncol, tf, parity, chain0, swapped, lad)) return rc;
+    const int64_t count = (int64_t)K * group;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    double *dU = sg.inout(U, (size_t)count * A), *dX = sg.inout(X, (size_t)count * ncol), *dLL = sg.inout(LL, (size_t)count);
+    int32_t *dSw = sg.out(swapped, (size_t)count);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_mcmc_swap_dev(dU, dX, dLL, K, group, A, ncol, tf, parity, chain0, seed, step, dSw, sg.stream())) return rc;
     return sg.finish(seconds);
 }
 

@@ -674,6 +674,86 @@ def mcmc_levels_device(LL, tf, chain0, seed, step, level):
         _chk(level, torch.float64, "level"), _stream()))
 
 
+def _ladder(tf):
+    tf = np.ascontiguousarray(tf, dtype=np.float64)
+    if tf.ndim != 1 or tf.size < 1:
+        raise ValueError("tf must be (K,), the temperatures of the rungs")
+    return tf
+
+
+def mcmc_propose_rungs_device(U, partners, group, gamma, scale, chain0, seed, step, minX, maxX, do_log, Up, Xp, inside, flags=0):
+    """trpl_mcmc_propose_rungs_dev: mcmc_propose_device for a block of rungs of `group` chains each (parallel tempering, include/trpl.h):
+    chain i of U (count, A) takes its two partners from the rows [(i // group) group, + group) of partners (P, A), P a multiple of
+    group and count <= P.  Rung k's rows are mcmc_propose_device's on that slice with that partner block and chain0 + k group."""
+    import torch
+    lo, hi, lg = _refine_box(minX, maxX, do_log)
+    if U.dim() != 2:
+        raise ValueError("U must be (count, A)")
+    count, A = U.shape
+    scale = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (A,)))
+    if partners is None or partners.dim() != 2 or partners.shape[1] != A:
+        raise ValueError("partners must be (P, A)")
+    if tuple(Up.shape) != (count, A) or tuple(Xp.shape) != (count, lo.size) or tuple(inside.shape) != (count,):
+        raise ValueError("Up must be (count, A), Xp (count, ncol) and inside (count,)")
+    _abi.check(_abi.lib().trpl_mcmc_propose_rungs_dev(
+        _chk(U, torch.float64, "U"), _chk(partners, torch.float64, "partners"), count, partners.shape[0], int(group), A, float(gamma),
+        _abi.ptr(scale), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, lo.size, _abi.ptr(lo), _abi.ptr(hi),
+        _abi.ptr(lg), int(flags), _chk(Up, torch.float64, "Up"), _chk(Xp, torch.float64, "Xp"), _chk(inside, torch.int32, "inside"),
+        _stream()))
+
+
+def mcmc_accept_rungs_device(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, accepted):
+    """trpl_mcmc_accept_rungs_dev: mcmc_accept_device with a temperature per rung.  tf (K,) is a host array; the count rows are K rungs
+    of count / K chains, and chain i decides at tf[i // (count / K)]."""
+    import torch
+    tf = _ladder(tf)
+    if U.dim() != 2 or X.dim() != 2 or X.shape[0] != U.shape[0] or Up.shape != U.shape or Xp.shape != X.shape:
+        raise ValueError("U and Up must be (count, A), X and Xp (count, ncol)")
+    count = U.shape[0]
+    if tuple(LL.shape) != (count,) or tuple(LLp.shape) != (count,) or tuple(inside.shape) != (count,) or tuple(accepted.shape) != (count,):
+        raise ValueError("LL, LLp, inside and accepted must be (count,)")
+    if count % tf.size:
+        raise ValueError("count = %d is no multiple of the %d rungs" % (count, tf.size))
+    _abi.check(_abi.lib().trpl_mcmc_accept_rungs_dev(
+        _chk(U, torch.float64, "U"), _chk(X, torch.float64, "X"), _chk(LL, torch.float64, "LL"), _chk(Up, torch.float64, "Up"),
+        _chk(Xp, torch.float64, "Xp"), _chk(LLp, torch.float64, "LLp"), _chk(inside, torch.int32, "inside"), count, U.shape[1], X.shape[1],
+        tf.size, count // tf.size, _abi.ptr(tf), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF,
+        _chk(accepted, torch.int32, "accepted"), _stream()))
+
+
+def mcmc_levels_rungs_device(LL, tf, chain0, seed, step, level):
+    """trpl_mcmc_levels_rungs_dev: mcmc_levels_device with a temperature per rung, tf (K,) a host array: the levels that
+    mcmc_accept_rungs_device, called with the same (tf, chain0, seed, step), is certain to reject above."""
+    import torch
+    tf = _ladder(tf)
+    if LL.dim() != 1 or tuple(level.shape) != tuple(LL.shape):
+        raise ValueError("LL and level must be (count,)")
+    if LL.shape[0] % tf.size:
+        raise ValueError("count = %d is no multiple of the %d rungs" % (LL.shape[0], tf.size))
+    _abi.check(_abi.lib().trpl_mcmc_levels_rungs_dev(
+        _chk(LL, torch.float64, "LL"), LL.shape[0], tf.size, LL.shape[0] // tf.size, _abi.ptr(tf), int(chain0),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, _chk(level, torch.float64, "level"), _stream()))
+
+
+def mcmc_swap_device(U, X, LL, tf, parity, chain0, seed, step, swapped):
+    """trpl_mcmc_swap_dev: the replica exchange between adjacent rungs of one block.  U (K group, A), X (K group, ncol) and LL (K
+    group,) f64 are exchanged IN PLACE between the rows k group + c and (k + 1) group + c for k = parity, parity + 2, ..; tf (K,) is
+    a host array; swapped (K group,) int32 is 1 on both rows of an exchanged pair, 0 elsewhere (include/trpl.h has the rule)."""
+    import torch
+    tf = _ladder(tf)
+    if U.dim() != 2 or X.dim() != 2 or X.shape[0] != U.shape[0]:
+        raise ValueError("U must be (K group, A) and X (K group, ncol)")
+    count = U.shape[0]
+    if tuple(LL.shape) != (count,) or tuple(swapped.shape) != (count,):
+        raise ValueError("LL and swapped must be (K group,)")
+    if count % tf.size:
+        raise ValueError("the %d rows are no multiple of the %d rungs" % (count, tf.size))
+    _abi.check(_abi.lib().trpl_mcmc_swap_dev(
+        _chk(U, torch.float64, "U"), _chk(X, torch.float64, "X"), _chk(LL, torch.float64, "LL"), tf.size, count // tf.size, U.shape[1],
+        X.shape[1], _abi.ptr(tf), int(parity), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF,
+        _chk(swapped, torch.int32, "swapped"), _stream()))
+
+
 def mcmc_chain_stats_device(H, t0, t1, mean, m2, Q=None):
     """trpl_mcmc_chain_stats_dev: mean, m2 (Q,) f64 <- per column q < Q of the history H (n, ldh >= Q) f64, which stays where it is,
     the mean and the centred sum of squares over the steps [t0, t1), both sums in ascending t: the plain loop's bits.  Q defaults

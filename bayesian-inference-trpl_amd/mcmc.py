@@ -16,6 +16,11 @@ there is no CPU fallback.  This module takes and returns numpy arrays and goes t
 likelihood it drives is any callable on a host X.  A pipeline whose chains stay on the device composes the same steps from
 device.mcmc_propose_device / mcmc_levels_device / mcmc_accept_device / mcmc_chain_stats_device.
 
+run_tempered is parallel tempering (replica exchange): K copies of the ensemble at a ladder of temperatures,
+all advanced by one call each of propose_rungs / reject_levels_rungs / accept_rungs and ONE call of the likelihood per half-sweep,
+with states of adjacent rungs exchanged by swap.  The hot rungs cross between separated modes that a single temperature leaves
+only slowly; Tempered.rung(0) is the ensemble at the temperature the caller asked for.
+
 Chains.samples() returns (X, W = 1): what posterior.moments / quantiles / columns / corner / credible_intervals and
 posterior_predictive take."""
 import numpy as np
@@ -97,6 +102,121 @@ def reject_levels(LL, tf, chain0, seed, step, device=0, info=None):
     if info is not None:
         info.update(seconds=sec.value)
     return level
+
+
+def _ladder(tf):
+    tf = _f64(tf)
+    if tf.ndim != 1 or not 1 <= tf.size <= _abi.MCMC_MAX_RUNGS:
+        raise ValueError("the ladder must be (K,), 1 <= K <= %d temperatures" % _abi.MCMC_MAX_RUNGS)
+    return tf
+
+
+def propose_rungs(U, partners, group, gamma, scale, chain0, seed, step, minX, maxX, do_log, sim_flags=None, device=0, info=None,
+                  fold=False):
+    """(Up, Xp, inside): propose() for a block of rungs of `group` chains each (trpl_mcmc_propose_rungs): chain i of U (count, A) takes
+    its two partners from the rows [(i // group) group, + group) of partners (P, A); P is a multiple of group, count <= P.  The rows
+    of rung k are propose() on that slice of U with that block of partners and chain0 + k group, bit for bit."""
+    U, partners = _f64(U), _f64(partners)
+    lo, hi, lg = _box(minX, maxX, do_log)
+    if U.ndim != 2:
+        raise ValueError("U must be (count, A)")
+    count, A = U.shape
+    scale = np.ascontiguousarray(np.broadcast_to(_f64(scale), (A,)))
+    if partners.ndim != 2 or partners.shape[1] != A:
+        raise ValueError("partners must be (P, A)")
+    Up, Xp, inside = np.empty((count, A)), np.empty((count, lo.size)), np.empty(count, dtype=np.int32)
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_mcmc_propose_rungs(_abi.ptr(U), _abi.ptr(partners), count, partners.shape[0], int(group), A, float(gamma),
+                                                  _abi.ptr(scale), int(chain0), int(seed) & _M64, int(step) & _M32, lo.size,
+                                                  _abi.ptr(lo), _abi.ptr(hi), _abi.ptr(lg),
+                                                  box_flags(sim_flags) | (_abi.MCMC_FOLD if fold else 0), _abi.ptr(Up), _abi.ptr(Xp),
+                                                  _abi.ptr(inside), int(device), _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value)
+    return Up, Xp, inside
+
+
+def accept_rungs(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device=0, info=None):
+    """accepted (count,) int32: accept() with a temperature per rung (trpl_mcmc_accept_rungs).  tf (K,): the count rows are K rungs of
+    count / K chains each.  U, X and LL are updated IN PLACE.  The rows of rung k are accept() on them with tf[k] and chain0 + k
+    count / K, bit for bit."""
+    for name, a in (("U", U), ("X", X), ("LL", LL)):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable):
+            raise ValueError("%s is updated in place: it must be a writeable C-contiguous float64 array" % name)
+    tf = _ladder(tf)
+    Up, Xp, LLp = _f64(Up), _f64(Xp), _f64(LLp)
+    inside = np.ascontiguousarray(inside, dtype=np.int32)
+    if U.ndim != 2 or X.ndim != 2 or X.shape[0] != U.shape[0] or Up.shape != U.shape or Xp.shape != X.shape:
+        raise ValueError("U and Up must be (count, A), X and Xp (count, ncol)")
+    count = U.shape[0]
+    if LL.shape != (count,) or LLp.shape != (count,) or inside.shape != (count,):
+        raise ValueError("LL, LLp and inside must be (count,)")
+    if count % tf.size:
+        raise ValueError("count = %d is no multiple of the %d rungs" % (count, tf.size))
+    accepted = np.empty(count, dtype=np.int32)
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_mcmc_accept_rungs(_abi.ptr(U), _abi.ptr(X), _abi.ptr(LL), _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(LLp),
+                                                 _abi.ptr(inside), count, U.shape[1], X.shape[1], tf.size, count // tf.size, _abi.ptr(tf),
+                                                 int(chain0), int(seed) & _M64, int(step) & _M32, _abi.ptr(accepted), int(device),
+                                                 _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value)
+    return accepted
+
+
+def reject_levels_rungs(LL, tf, chain0, seed, step, device=0, info=None):
+    """level (count,): reject_levels() with a temperature per rung (trpl_mcmc_levels_rungs), tf (K,): the levels above which
+    accept_rungs(), called with the same (tf, chain0, seed, step), is certain to reject."""
+    LL, tf = _f64(LL), _ladder(tf)
+    if LL.ndim != 1:
+        raise ValueError("LL must be (count,)")
+    if LL.shape[0] % tf.size:
+        raise ValueError("count = %d is no multiple of the %d rungs" % (LL.shape[0], tf.size))
+    level = np.empty(LL.shape[0])
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_mcmc_levels_rungs(_abi.ptr(LL), LL.shape[0], tf.size, LL.shape[0] // tf.size, _abi.ptr(tf), int(chain0),
+                                                 int(seed) & _M64, int(step) & _M32, _abi.ptr(level), int(device), _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value)
+    return level
+
+
+def swap(U, X, LL, tf, parity, chain0, seed, step, device=0, info=None):
+    """swapped (K group,) int32: the replica exchange between adjacent rungs of one block (trpl_mcmc_swap).  U (K group, A), X (K group,
+    ncol) and LL (K group,) -- writeable C-contiguous float64 arrays -- are exchanged IN PLACE between the rows a = k group + c and
+    b = a + group for k = parity, parity + 2, .. with k + 1 < K: with d = (LL[b] - LL[a]) (1 / tf[k] - 1 / tf[k + 1]), when neither
+    LL is NaN and d >= 0 or log(xi) < d.  swapped is 1 on both rows of an exchanged pair, 0 on every other row."""
+    for name, a in (("U", U), ("X", X), ("LL", LL)):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable):
+            raise ValueError("%s is exchanged in place: it must be a writeable C-contiguous float64 array" % name)
+    tf = _ladder(tf)
+    if U.ndim != 2 or X.ndim != 2 or X.shape[0] != U.shape[0] or LL.shape != (U.shape[0],):
+        raise ValueError("U must be (K group, A), X (K group, ncol) and LL (K group,)")
+    count = U.shape[0]
+    if count % tf.size:
+        raise ValueError("the %d rows are no multiple of the %d rungs" % (count, tf.size))
+    swapped = np.empty(count, dtype=np.int32)
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_mcmc_swap(_abi.ptr(U), _abi.ptr(X), _abi.ptr(LL), tf.size, count // tf.size, U.shape[1], X.shape[1],
+                                         _abi.ptr(tf), int(parity), int(chain0), int(seed) & _M64, int(step) & _M32, _abi.ptr(swapped),
+                                         int(device), _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value)
+    return swapped
+
+
+def geometric_ladder(tf, tf_hot, K):
+    """(K,) temperatures from tf to tf_hot in equal ratios: tf (tf_hot / tf)^(k / (K - 1)); K = 1 gives [tf]."""
+    tf, tf_hot, K = float(tf), float(tf_hot), int(K)
+    if not (np.isfinite(tf) and np.isfinite(tf_hot) and tf > 0.0 and tf_hot > 0.0):
+        raise ValueError("tf and tf_hot must be finite and > 0")
+    if not 1 <= K <= _abi.MCMC_MAX_RUNGS:
+        raise ValueError("K=%d must be in [1, %d]" % (K, _abi.MCMC_MAX_RUNGS))
+    if K == 1:
+        return np.array([tf])
+    out = tf * (tf_hot / tf) ** (np.arange(K) / float(K - 1))
+    out[0], out[-1] = tf, tf_hot
+    return out
 
 
 def chain_stats(H, t0=0, t1=None, Q=None, device=0, info=None):
@@ -254,3 +374,142 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
         if early_reject:
             info.update(early_reject=levelled / float(max(solved, 1)))
     return Chains(hU, hX, hLL, hAcc, device=device)
+
+
+class Tempered:
+    """The kept history of run_tempered: ladder (K,) the temperatures, rung(k) the Chains of rung k in run's (n, C, A) layout,
+    swap_rate (K - 1,) the share of the proposed exchanges between rungs k and k + 1 that took place (NaN where none was proposed)."""
+
+    def __init__(self, ladder, chains, swap_rate):
+        self.ladder, self._chains, self.swap_rate = ladder, chains, swap_rate
+
+    def rung(self, k):
+        return self._chains[k]
+
+    def samples(self, burn=0, thin=1):
+        """rung(0).samples(burn, thin): ladder[0] is the temperature the caller asked for."""
+        return self._chains[0].samples(burn, thin)
+
+
+def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sweeps=1000, swap_every=1, kind="de", gamma=None,
+                 scale=None, jump_every=0, seed=1, keep_every=1, burn=0, max_history_bytes=4 << 30, device=0, info=None, U0=None,
+                 bounds="reject", early_reject=False):
+    """Parallel tempering (replica exchange: Swendsen & Wang 1986, Geyer 1991): K = len(ladder) copies of run's
+    ensemble of C chains, rung k at temperature ladder[k], advanced together, and states of adjacent rungs exchanged by the
+    Metropolis rule of swap().  The hot rungs cross between separated modes; the exchange carries that down to rung 0, whose
+    temperature ladder[0] is the one the caller wants.  Returns Tempered.
+
+    X0 (C, ncol) and LL0 (C,) start every rung from the same states; X0 (K, C, ncol) and LL0 (K, C) give each rung its own (U0
+    likewise (C, A) or (K, C, A)).  The state is held half-major: with g = C / 2, row h K g + k g + c is chain c of half h of rung
+    k, so the first halves of all rungs are one contiguous block and the second halves the other, and the row index keys Philox.
+    One half-sweep is one propose_rungs over a block with the other block as partners (kind="rw": propose over the block),
+    optionally one reject_levels_rungs, ONE call of loglik on the proposals of all rungs that are to be solved, and one
+    accept_rungs; step and chain0 are run's (2 t + h, the block's first row).  After every swap_every-th sweep t (t + 1 a multiple
+    of swap_every) each block gets one swap with parity = (t // swap_every) % 2, step = t and chain0 the block's first row.  With
+    ladder = [tf] no swap is called and rung(0) is run(..., tf=tf)'s Chains bit for bit.
+
+    The other keywords are run's.  Chains.accept of a rung is the Metropolis step's flag of the rung's slots; an exchange does not
+    count as a move.  The history takes n K C (A + ncol + 1) 8 + n K C bytes and is refused above max_history_bytes before anything
+    is solved.  info receives run's keys per rung -- accept (sweeps, K), outside (K,), folded (K,), early_reject (K,) -- and
+    swap_rate (K - 1,)."""
+    ladder = np.array(ladder, dtype=np.float64, order="C")
+    if ladder.ndim != 1 or not 1 <= ladder.size <= _abi.MCMC_MAX_RUNGS:
+        raise ValueError("ladder must be (K,), 1 <= K <= %d temperatures" % _abi.MCMC_MAX_RUNGS)
+    if not np.all(np.isfinite(ladder) & (ladder > 0.0)):
+        raise ValueError("every temperature of the ladder must be finite and > 0")
+    K = ladder.size
+    X, LL = np.array(X0, dtype=np.float64, order="C"), np.array(LL0, dtype=np.float64, order="C")
+    lo, hi, lg = _box(minX, maxX, do_log)
+    if X.ndim == 2 and LL.ndim == 1:
+        X, LL = np.broadcast_to(X, (K,) + X.shape), np.broadcast_to(LL, (K,) + LL.shape)
+    if X.ndim != 3 or X.shape[0] != K or X.shape[2] != lo.size or LL.shape != X.shape[:2]:
+        raise ValueError("X0 must be (C, ncol) and LL0 (C,), or (K, C, ncol) and (K, C) with the ladder's K = %d" % K)
+    C = X.shape[1]
+    if C < 4 or C % 2:
+        raise ValueError("C=%d: the two halves of the ensemble need an even number of chains, at least 4" % C)
+    if kind not in ("de", "rw"):
+        raise ValueError("kind must be 'de' or 'rw'")
+    if bounds not in ("reject", "fold"):
+        raise ValueError("bounds must be 'reject' or 'fold'")
+    if scale is None:
+        if kind == "rw":
+            raise ValueError("kind='rw' needs scale, the half-width of the random walk")
+        scale = 1e-3
+    sweeps, keep_every, burn, jump_every, swap_every = int(sweeps), int(keep_every), int(burn), int(jump_every), int(swap_every)
+    if sweeps < 1 or keep_every < 1 or burn < 0 or swap_every < 1:
+        raise ValueError("sweeps, keep_every and swap_every must be >= 1 and burn >= 0")
+    A = refine.active_columns(lo, hi, sim_flags).size
+    if not 1 <= A <= _abi.REFINE_MAX_DIMS:
+        raise ValueError("the box has %d active columns; a chain takes 1 .. %d" % (A, _abi.REFINE_MAX_DIMS))
+    kept = range(burn, sweeps, keep_every)
+    need = len(kept) * K * C * ((A + lo.size + 1) * 8 + 1)
+    if need > int(max_history_bytes):
+        raise ValueError("the history of %d sweeps x %d rungs x %d chains needs %d bytes, more than max_history_bytes = %d"
+                         % (len(kept), K, C, need, int(max_history_bytes)))
+    g = C // 2
+    half = K * g
+
+    def half_major(a):                                           # (K, C, ...) -> (2 K g, ...), a writeable copy
+        return np.array(a.reshape((K, 2, g) + a.shape[2:]).swapaxes(0, 1).reshape((2 * half,) + a.shape[2:]), order="C")
+
+    def rung_major(a):                                           # (2 K g, ...) -> (K, C, ...)
+        return a.reshape((2, K, g) + a.shape[1:]).swapaxes(0, 1).reshape((K, C) + a.shape[1:])
+
+    X, LL = half_major(X), half_major(LL)
+    if U0 is None:
+        U, _ = refine.unit_coords(X, lo, hi, lg, sim_flags, device=device)
+    else:
+        U = np.array(U0, dtype=np.float64, order="C")
+        if U.shape == (C, A):
+            U = np.broadcast_to(U, (K, C, A))
+        if U.shape != (K, C, A):
+            raise ValueError("U0 must be (C, A) or (K, C, A) with the box's A = %d active columns" % A)
+        U = half_major(U)
+    gamma0 = 2.38 / np.sqrt(2.0 * A) if gamma is None else float(gamma)
+    hU, hX = np.empty((K, len(kept), C, A)), np.empty((K, len(kept), C, lo.size))
+    hLL, hAcc = np.empty((K, len(kept), C)), np.empty((K, len(kept), C), dtype=bool)
+    rung_of = np.repeat(np.arange(K), g)                         # the rung of every row of a block
+    shares, row = np.empty((sweeps, K)), 0
+    outside, folded = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
+    levelled, solved = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
+    tried, done = np.zeros(max(K - 1, 0), dtype=np.int64), np.zeros(max(K - 1, 0), dtype=np.int64)
+    moved = np.empty(2 * half, dtype=bool)
+    for t in range(sweeps):
+        gm = 1.0 if jump_every > 0 and (t + 1) % jump_every == 0 else gamma0
+        for h, (a, b) in enumerate(((0, half), (half, 2 * half))):
+            if kind == "rw":
+                Up, Xp, inside = propose(U[a:b], None, gm, scale, a, seed, 2 * t + h, lo, hi, lg, sim_flags, device=device,
+                                         fold=bounds == "fold")
+            else:
+                Up, Xp, inside = propose_rungs(U[a:b], U[half:] if h == 0 else U[:half], g, gm, scale, a, seed, 2 * t + h, lo, hi, lg,
+                                               sim_flags, device=device, fold=bounds == "fold")
+            ok = inside != 0
+            LLp = np.full(half, -np.inf)
+            if ok.any() and early_reject:
+                levels = reject_levels_rungs(LL[a:b], ladder, a, seed, 2 * t + h, device=device)[ok]
+                LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok]), cut_levels=levels))
+                levelled += np.bincount(rung_of[ok][np.isfinite(levels)], minlength=K)
+                solved += np.bincount(rung_of[ok], minlength=K)
+            elif ok.any():
+                LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok])))
+            outside += np.bincount(rung_of[~ok], minlength=K)
+            folded += np.bincount(rung_of[inside == 2], minlength=K)
+            moved[a:b] = accept_rungs(U[a:b], X[a:b], LL[a:b], Up, Xp, LLp, inside, ladder, a, seed, 2 * t + h, device=device) != 0
+        shares[t] = rung_major(moved).mean(axis=1)
+        if K > 1 and (t + 1) % swap_every == 0:
+            parity = (t // swap_every) % 2
+            for a, b in ((0, half), (half, 2 * half)):
+                sw = swap(U[a:b], X[a:b], LL[a:b], ladder, parity, a, seed, t, device=device)
+                lower = np.arange(parity, K - 1, 2)
+                tried[lower] += g
+                done[lower] += sw.reshape(K, g)[lower].sum(axis=1)
+        if t >= burn and (t - burn) % keep_every == 0:
+            hU[:, row], hX[:, row], hLL[:, row], hAcc[:, row] = rung_major(U), rung_major(X), rung_major(LL), rung_major(moved)
+            row += 1
+    with np.errstate(invalid="ignore"):
+        swap_rate = done / tried.astype(np.float64)
+    if info is not None:
+        info.update(accept=shares, outside=outside / float(sweeps * C), folded=folded / float(sweeps * C), swap_rate=swap_rate)
+        if early_reject:
+            info.update(early_reject=levelled / np.maximum(solved, 1).astype(np.float64))
+    return Tempered(ladder, [Chains(hU[k], hX[k], hLL[k], hAcc[k], device=device) for k in range(K)], swap_rate)

@@ -1322,6 +1322,73 @@ int trpl_mcmc_levels(const double *LL, int64_t count, double tf, int64_t chain0,
                      int32_t device, double *seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_mcmc_propose_rungs, trpl_mcmc_accept_rungs, trpl_mcmc_levels_rungs, trpl_mcmc_swap -- PARALLEL TEMPERING (replica exchange:
+ * Swendsen & Wang 1986, Geyer 1991): K copies ("rungs") of the ensemble run at temperatures tf[0 .. K), every rung by the rules of
+ * trpl_mcmc_propose / _levels / _accept at its own temperature, and states of adjacent rungs are exchanged by a Metropolis rule.  The
+ * hot rungs cross between separated regions of the posterior; the exchange carries that down to the rung the caller wants.  All K
+ * rungs advance in ONE call each, so a half-sweep stays one launch of the likelihood.  (csrc/mcmc.hip)
+ *
+ * Layout.  A block is K rungs of `group` chains: row k * group + c is chain c of rung k, count == K * group.  tf is a HOST array of K
+ * values, copied into the kernel argument like scale; it need not be sorted.  Chain i of a call is chain chain0 + i of the ensemble,
+ * as above: the row index keys Philox, so with K = 1 every stream is that of the calls above.
+ *
+ * trpl_mcmc_propose_rungs: trpl_mcmc_propose with `group`: chain i draws its two distinct partners from the rows [(i / group) *
+ * group, + group) of partners [P][A], by the index expressions of trpl_mcmc_propose with P replaced by group.  group >= 2, P a
+ * multiple of group, count <= P.  TRPL_MCMC_FOLD applies unchanged.  The rows [k group, (k + 1) group) of Up, Xp and inside are, bit
+ * for bit, trpl_mcmc_propose on those rows of U with those rows of partners and chain0 + k group.
+ * trpl_mcmc_accept_rungs, trpl_mcmc_levels_rungs: trpl_mcmc_accept and trpl_mcmc_levels with (K, group, tf[K]) where the scalar tf
+ * is: chain i uses tf[i / group].  Rung k's rows are bit for bit the scalar call on them with tf[k] and chain0 + k group.  The safety
+ * argument of trpl_mcmc_levels never compares two chains, so it holds per chain as it stands.
+ *
+ * trpl_mcmc_swap: U [K group][A], X [K group][ncol], LL [K group] in place, swapped [K group] (int32) out.  The pairs are the rungs
+ * (k, k + 1) for k = parity, parity + 2, .. with k + 1 < K, and every c < group: rows a = k group + c and b = a + group.  One thread
+ * decides a pair.  xi is the 53-bit uniform of Philox counter (n low, n high, 0x100 + 10, step), n = chain0 + a, from (x0, x1);
+ *     d = (LL[b] - LL[a]) * (1.0 / tf[k] - 1.0 / tf[k + 1])        (fp64, one rounding per operation)
+ * and the pair is exchanged exactly when neither LL[a] nor LL[b] is NaN and (d >= 0 || log(xi) < d) (the device's log).  A NaN d
+ * (both -inf, or 0 * inf at equal temperatures) exchanges nothing.  An exchange swaps the rows a and b of U, X and LL; swapped is 1
+ * on both rows of an exchanged pair and 0 on every other row of the block.  A row of no pair (rung k < parity, or the last rung when
+ * it has no upper neighbour of this parity) is not touched apart from swapped = 0.  K = 1 has no pair and writes zeros.
+ * WHY THE PRODUCT OF THE TEMPERED POSTERIORS STAYS INVARIANT.  The joint state is (x_0 .. x_{K-1}) with density prod_k p(x_k)
+ * L(x_k)^(1 / tf[k]) on the cube.  Exchanging x_k and x_{k+1} is its own inverse, so as a proposal it is symmetric (it is proposed
+ * with probability 1 from either side, whatever the states are), and its Metropolis ratio is
+ *     L(x_{k+1})^(1/tf[k]) L(x_k)^(1/tf[k+1]) / (L(x_k)^(1/tf[k]) L(x_{k+1})^(1/tf[k+1])) = exp(d)
+ * -- the uniform prior cancels.  Accepting with min(1, exp(d)) is therefore the exact Metropolis rule on the joint state.  Pairs of
+ * one parity are disjoint, so deciding them at once is a product of such kernels; alternating parities is a deterministic cycle
+ * of invariant kernels.  The marginal of rung k stays p L^(1 / tf[k]); that of tf[0] is the posterior the caller asked for.
+ *
+ * Refused (TRPL_ERR_ARG, before a device is touched, the message naming the argument): what trpl_mcmc_propose / _accept / _levels
+ * refuse of the arguments they share; K outside [1, TRPL_MCMC_MAX_RUNGS]; group < 1 (propose: < 2); "tf is NULL"; a tf[k] that is
+ * not finite and > 0 ("tf[k]="); count != K * group; (propose) P not a positive multiple of group, count > P; (swap) parity other
+ * than 0 or 1, "swapped is NULL".
+ * Python: trpl_amd.mcmc.propose_rungs / accept_rungs / reject_levels_rungs / swap / run_tempered, trpl_amd.device.mcmc_*_rungs_device,
+ * trpl_amd.device.mcmc_swap_device.
+ * ------------------------------------------------------------------------------------- */
+#define TRPL_MCMC_MAX_RUNGS 64
+int trpl_mcmc_propose_rungs_dev(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, int32_t A, double gamma,
+                                const double *scale /*host [A]*/, int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol,
+                                const double *lo /*host*/, const double *hi /*host*/, const int32_t *do_log /*host*/, uint32_t flags,
+                                double *Up, double *Xp, int32_t *inside, void *stream);
+int trpl_mcmc_propose_rungs(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, int32_t A, double gamma,
+                            const double *scale, int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol, const double *lo,
+                            const double *hi, const int32_t *do_log, uint32_t flags, double *Up, double *Xp, int32_t *inside,
+                            int32_t device, double *seconds);
+int trpl_mcmc_accept_rungs_dev(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp,
+                               const int32_t *inside, int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group,
+                               const double *tf /*host [K]*/, int64_t chain0, uint64_t seed, uint32_t step, int32_t *accepted,
+                               void *stream);
+int trpl_mcmc_accept_rungs(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
+                           int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group, const double *tf, int64_t chain0,
+                           uint64_t seed, uint32_t step, int32_t *accepted, int32_t device, double *seconds);
+int trpl_mcmc_levels_rungs_dev(const double *LL, int64_t count, int32_t K, int64_t group, const double *tf /*host [K]*/, int64_t chain0,
+                               uint64_t seed, uint32_t step, double *level, void *stream);
+int trpl_mcmc_levels_rungs(const double *LL, int64_t count, int32_t K, int64_t group, const double *tf, int64_t chain0, uint64_t seed,
+                           uint32_t step, double *level, int32_t device, double *seconds);
+int trpl_mcmc_swap_dev(double *U, double *X, double *LL, int32_t K, int64_t group, int32_t A, int32_t ncol, const double *tf /*host [K]*/,
+                       int32_t parity, int64_t chain0, uint64_t seed, uint32_t step, int32_t *swapped /*[K group]*/, void *stream);
+int trpl_mcmc_swap(double *U, double *X, double *LL, int32_t K, int64_t group, int32_t A, int32_t ncol, const double *tf, int32_t parity,
+                   int64_t chain0, uint64_t seed, uint32_t step, int32_t *swapped, int32_t device, double *seconds);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the
  * measurement plan): S independent systems  ld[i] x[i-1] + d[i] x[i] + ud[i] x[i+1] = b[i],
  * i < L, the problem pcreduce solves (pvSimPCR.py:42-81), operands and result in HBM, arrays

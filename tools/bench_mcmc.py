@@ -1,6 +1,6 @@
 """The three kernels of the ensemble Metropolis sampler on resident tensors, in one process on one device.
 
-    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--fold] [--out profiles/mcmc_bench.jsonl]
+    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--fold] [--tempered [--rungs 16]] [--out profiles/mcmc_bench.jsonl]
 
 propose:     mcmc_propose_device of `chains` chains in the reference's box (A = 10 active columns), with `chains` partners
              (differential evolution: two gathered partner rows per chain), and the random walk for comparison.
@@ -8,6 +8,9 @@ propose:     mcmc_propose_device of `chains` chains in the reference's box (A = 
              within 1e-3 of a face of the cube, so that the fmod path of the fold runs; the unfolded call of the same process is
              propose_de.
 accept:      mcmc_accept_device of the same chains, about a third of the proposals accepted.
+--tempered:  the four kernels of parallel tempering at the same rows, cut into --rungs rungs on geometric_ladder(1, 64, rungs):
+             propose_rungs (partners from the chain's own rung), accept_rungs and levels_rungs (a temperature per rung, beside
+             levels, the scalar call) and swap (parity 0).
 chain_stats: mcmc_chain_stats_device over a history of n steps of chains * A columns (one half of a split-R-hat: n / 2 steps).
 Device events around `reps` back-to-back calls after a warm-up, median of 3 interleaved passes (tools/bench_quantiles.measure).
 Appends one JSON line to --out."""
@@ -32,6 +35,8 @@ def main():
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--fold", action="store_true")
+    ap.add_argument("--tempered", action="store_true")
+    ap.add_argument("--rungs", type=int, default=16)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcmc_bench.jsonl"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -73,6 +78,23 @@ def main():
         flags = trpl_amd._abi.MCMC_FOLD
         calls["propose_de_fold"] = lambda: tdev.mcmc_propose_device(Uf, partners, gamma, 1e-3, 0, 42, 0, lo, hi, lg, Upf, Xpf, codes,
                                                                      flags=flags)
+    if a.tempered:
+        # the same rows as --rungs rungs of chains / rungs each: the partners of a chain come from its rung's block, the temperature
+        # from the ladder.  accept and swap overwrite their chains, so they run on copies; the share of pairs a swap call
+        # exchanges differs from call to call (an exchanged pair stands the other way round at the next), swapped_share is the last's
+        K = a.rungs
+        if C % K or C // K < 2:
+            raise SystemExit("--chains must be a multiple of --rungs, two chains per rung at least")
+        ladder = trpl_amd.mcmc.geometric_ladder(1.0, 64.0, K)
+        Upr, Xpr, insr = torch.empty_like(Up), torch.empty_like(Xp), torch.empty_like(inside)
+        Ur, Xr, LLr, accr = U.clone(), X.clone(), LL.clone(), torch.empty_like(accepted)
+        Us, Xs, LLs, swapped = U.clone(), X.clone(), LL.clone(), torch.empty_like(accepted)
+        level = torch.empty(C, **f64)
+        calls["propose_rungs"] = lambda: tdev.mcmc_propose_rungs_device(U, partners, C // K, gamma, 1e-3, 0, 42, 0, lo, hi, lg, Upr, Xpr, insr)
+        calls["accept_rungs"] = lambda: tdev.mcmc_accept_rungs_device(Ur, Xr, LLr, Up, Xp, LLp, inside, ladder, 0, 42, 0, accr)
+        calls["levels"] = lambda: tdev.mcmc_levels_device(LL, 1.0, 0, 42, 0, level)
+        calls["levels_rungs"] = lambda: tdev.mcmc_levels_rungs_device(LL, ladder, 0, 42, 0, level)
+        calls["swap"] = lambda: tdev.mcmc_swap_device(Us, Xs, LLs, ladder, 0, 0, 42, 0, swapped)
     ms, passes = measure(calls, a.reps)
     torch.cuda.synchronize()
     line = {"bench": "mcmc", "device": torch.cuda.get_device_name(0), "chains": C, "A": A, "ncol": ncol, "n": a.n, "reps": a.reps, "ms": ms,
@@ -80,6 +102,8 @@ def main():
             "chain_stats_bytes_per_second": 2.0 * 8.0 * (a.n // 2) * C * A / (ms["chain_stats"] * 1e-3)}
     if a.fold:
         line["folded_share"] = float((codes == 2).double().mean().item())
+    if a.tempered:
+        line.update(rungs=a.rungs, swapped_share=float(swapped.double().mean().item()))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as f:
         f.write(json.dumps(line) + "\n")

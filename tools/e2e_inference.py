@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--fold] [--early-reject]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--fold] [--early-reject] [--tempered K [--tf-hot x]]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -42,6 +42,11 @@ so that every proposal is solved; "mcmc" then gains "bounds" and "folded", the s
 26; the chain is the same, bit for bit) and adds "early_reject" to "mcmc": the share of solved proposals that were cut and the
 system-timesteps solved.  With or without it "mcmc" holds "system_timesteps", the solver iterations summed over every proposal, and
 the same numbers are printed.
+--tempered K (with --mcmc; composes with --fold and --early-reject) runs parallel tempering instead (mcmc.run_tempered: DESIGN.md section
+27): K rungs of C chains each on mcmc.geometric_ladder(tf, tf_hot, K), every half-sweep still one call of the fused likelihood.
+--tf-hot x sets the hottest temperature; the default is the temperature at which the importance run reaches an effective sample
+size of 64 (posterior.tf_for_ess).  "mcmc" is the cold rung's, as without the flag; "tempered" beside it holds the ladder and, per
+rung, acceptance and worst R-hat, the swap rates and the seconds, which are printed.
 """
 import json
 import sys
@@ -72,8 +77,8 @@ if "--shrink" in sys.argv:
 MCMC = "--mcmc" in sys.argv
 FOLD = "--fold" in sys.argv
 EARLY = "--early-reject" in sys.argv
-CHAINS, SWEEPS, RW = 1024, 200, None
-for flag, conv in (("--chains", int), ("--sweeps", int), ("--rw", float)):
+CHAINS, SWEEPS, RW, TEMPERED, TF_HOT = 1024, 200, None, 0, None
+for flag, conv in (("--chains", int), ("--sweeps", int), ("--rw", float), ("--tempered", int), ("--tf-hot", float)):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = conv(sys.argv[k + 1])
@@ -82,6 +87,10 @@ for flag, conv in (("--chains", int), ("--sweeps", int), ("--rw", float)):
             CHAINS = value
         elif flag == "--sweeps":
             SWEEPS = value
+        elif flag == "--tempered":
+            TEMPERED = value
+        elif flag == "--tf-hot":
+            TF_HOT = value
         else:
             RW = value
 sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented", "--mcmc", "--fold", "--early-reject")]
@@ -276,8 +285,28 @@ if MCMC:
     X0, U0, LL0 = mcmc.start(X.cpu().numpy(), P.cpu().numpy(), CHAINS, lo, hi, lg, tf=tf)
     minfo = {}
     burn = SWEEPS // 2
-    ch = mcmc.run(fused_chain, X0, LL0, lo, hi, lg, sweeps=SWEEPS, tf=tf, seed=42, burn=burn, info=minfo, U0=U0,
-                  **({"kind": "rw", "scale": RW} if RW is not None else {}), **({"bounds": "fold"} if FOLD else {}), **({"early_reject": True} if EARLY else {}))
+    opts = dict(sweeps=SWEEPS, seed=42, burn=burn, info=minfo, U0=U0, **({"kind": "rw", "scale": RW} if RW is not None else {}),
+                **({"bounds": "fold"} if FOLD else {}), **({"early_reject": True} if EARLY else {}))
+    if TEMPERED:
+        hot_ess = None
+        if TF_HOT is None:                                       # hot enough for the importance run to hold 64 effective samples
+            Pn = P.cpu().numpy()
+            TF_HOT, hot_ess = posterior.tf_for_ess(np.where(np.isnan(Pn), -np.inf, Pn), 64.0, lo=tf, hi=1e4 * tf)
+        ladder = mcmc.geometric_ladder(tf, TF_HOT, TEMPERED)
+        t_run = time.time()
+        tempered = mcmc.run_tempered(fused_chain, X0, LL0, lo, hi, lg, ladder, **opts)
+        t_run = time.time() - t_run
+        rungs = [tempered.rung(k) for k in range(TEMPERED)]
+        ch = rungs[0]
+        rung_info = dict(minfo)
+        minfo = {"accept": list(rung_info["accept"][:, 0]), "outside": float(rung_info["outside"][0]), "folded": float(rung_info["folded"][0])}
+        if EARLY:
+            minfo["early_reject"] = float(rung_info["early_reject"][0])
+    else:
+        t_run = time.time()
+        ch = mcmc.run(fused_chain, X0, LL0, lo, hi, lg, tf=tf, **opts)
+        t_run = time.time() - t_run
+        print("mcmc: %.2f s, %.4f s per sweep" % (t_run, t_run / SWEEPS), file=sys.stderr)
     rhat = ch.rhat()
     Xs, Ws = ch.samples()
     Xg = Xs / sm.UNIT_CONVERSIONS
@@ -307,6 +336,17 @@ if MCMC:
     print("mcmc (%s): %d chains from %d distinct starts, %d sweeps: acceptance %.3f (kept half %.3f), outside the prior box %.4f, worst R-hat %.3f"
           % (out["mcmc"]["proposal"], CHAINS, out["mcmc"]["distinct_starts"], SWEEPS, out["mcmc"]["acceptance"],
              out["mcmc"]["acceptance_kept"], minfo["outside"], out["mcmc"]["worst_rhat"]), file=sys.stderr)
+    if TEMPERED:
+        worst = [float(np.nanmax(r.rhat())) for r in rungs]
+        out["mcmc"]["tempered"] = {"rungs": TEMPERED, "ladder": [float(v) for v in ladder], "tf_hot_ess": hot_ess,
+                                   "acceptance": [float(v) for v in rung_info["accept"].mean(axis=0)], "worst_rhat": worst,
+                                   "swap_rate": [float(v) for v in tempered.swap_rate], "seconds_run": t_run,
+                                   "seconds_per_sweep": t_run / SWEEPS}
+        for k in range(TEMPERED):
+            print("mcmc: rung %2d  tf %10.4g  acceptance %.3f  worst R-hat %.3f  swap rate to the next %s"
+                  % (k, ladder[k], out["mcmc"]["tempered"]["acceptance"][k], worst[k],
+                     "%.3f" % tempered.swap_rate[k] if k + 1 < TEMPERED else "-"), file=sys.stderr)
+        print("mcmc: tempered, %d rungs: %.2f s, %.4f s per sweep" % (TEMPERED, t_run, t_run / SWEEPS), file=sys.stderr)
     for k, n in enumerate(names):
         print("mcmc: %-8s truth %9.4f | chain %9.4f %9.4f %9.4f | importance %9.4f %9.4f %9.4f"
               % ((n, truth[k]) + tuple(q_chain[:, k]) + tuple(q_imp[:, k])), file=sys.stderr)
