@@ -235,6 +235,12 @@ SIGNATURES = {
     "trpl_mcmc_levels_rungs": [_vp, _i64, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _i32, _pd],
     "trpl_mcmc_swap_dev": [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _i64, _u64, _u32, _vp, _vp],
     "trpl_mcmc_swap": [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _i64, _u64, _u32, _vp, _i32, _pd],
+    "trpl_mcmc_autocov_tile": [],
+    "trpl_mcmc_autocov_dev": [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp],
+    "trpl_mcmc_autocov": [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _pd],
+    "trpl_mcmc_autocov_pool_dev": [_vp, _i64, _i64, _i64, _i32, _vp, _vp],
+    "trpl_mcmc_autocov_pool": [_vp, _i64, _i64, _i64, _i32, _vp, _i32, _pd],
+    "trpl_mcmc_autocov_chains": [_vp, _i64, _i64, _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _pd],
     "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
     "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
 }

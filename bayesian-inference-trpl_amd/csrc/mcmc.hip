@@ -17,6 +17,13 @@
 //       or that plus a few ulps, whichever the accept step's own expression confirms; +inf (never cut) when neither does.
 //   chain_stats_kernel    one thread per column q of a history H [n][ldh]: the mean and the centred sum of squares over the steps
 //       [t0, t1), both sums in ascending t from +0.0.  Adjacent threads read adjacent addresses.
+// Autocovariance sums (trpl_mcmc_autocov*, include/trpl.h): what the effective sample size is formed from.
+//   autocov_mean_kernel   chain_stats_kernel's first pass alone: mean[q], the bits of chain_stats.
+//   autocov_kernel<TL>    one thread per column q and tile of TL consecutive lags [l0, l0 + TL): s[l][q] = sum over t of e[t] e[t + l],
+//       e = H - mean, t ascending from +0.0.  The thread walks u = t + l upward and pairs e[u] with the TL centred values before it,
+//       kept in a register window that rotates with static indices (the time loop is unrolled by TL): per step two loads, two
+//       subtracts, TL multiplies and TL adds.  u upward is t upward for every lag, and the product commutes: the definition's bits.
+//   autocov_pool_kernel   one thread per (l, a): pooled[l][a] = sum over c < M of s[l][c A + a], c ascending from +0.0; 16 loads ahead.
 // Parallel tempering (trpl_mcmc_*_rungs*, trpl_mcmc_swap*, include/trpl.h): K rungs of `group` chains each in one
 // contiguous block, row k group + c chain c of rung k, advanced by one launch each.
 //   propose_rungs_kernel<A>, propose_rungs_fold_kernel<A>   propose_body with the partners of chain i narrowed to the rows
@@ -297,6 +304,96 @@ __global__ void __launch_bounds__(kThreads) chain_stats_kernel(const double *H, 
     m2[q] = v;
 }
 
+// ---- autocovariance sums.  kAutocovTile is trpl_mcmc_autocov_tile(): with 8 lags per thread the kernel takes 72 VGPRs, 7 waves per
+// SIMD and no scratch; 16 lags take 166 and leave 3 waves.
+constexpr int kAutocovTile = 8;
+
+__global__ void __launch_bounds__(kThreads) autocov_mean_kernel(const double *H, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, double *mean)
+{
+    const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (q >= Q) return;
+    double s = 0.0;
+    for (int64_t t = t0; t < t1; t++) s = s + H[t * ldh + q];
+    mean[q] = s / (double)(t1 - t0);
+}
+
+// TL steps r = base .. base + TL - 1 of a thread's walk: e[r] (row hw) enters slot r % TL = j of the window, e[l0 + r] (row hu) multiplies
+// the window's e[r - k] into the sum of lag l0 + k.  FIRST (base = 0): e[r - k] exists from r = k on.  PARTIAL: only `left` < TL steps
+// remain.  Every index of w and acc is a constant after unrolling.
+template <int TL, bool FIRST, bool PARTIAL>
+__device__ __forceinline__ void autocov_chunk(const double *hw, const double *hu, int64_t ldh, double mu, int64_t left, double (&w)[TL],
+                                              double (&acc)[TL])
+{
+    double hv[TL], uv[TL];                                       // the chunk's 2 TL loads are issued before its arithmetic
+#pragma unroll
+    for (int j = 0; j < TL; j++) {
+        if (PARTIAL && j >= left) break;
+        hv[j] = hw[j * ldh];
+        uv[j] = hu[j * ldh];
+    }
+#pragma unroll
+    for (int j = 0; j < TL; j++) {
+        if (PARTIAL && j >= left) break;
+        w[j] = hv[j] - mu;
+        const double eu = uv[j] - mu;
+#pragma unroll
+        for (int k = 0; k < TL; k++) {
+            if (FIRST && k > j) continue;
+            acc[k] = acc[k] + eu * w[(j - k + TL) % TL];
+        }
+    }
+}
+
+// Block b serves the lag tile b / qblocks and the columns (b % qblocks) kThreads + thread: the tiles go out in ascending l0, the
+// longest walks first.  (Measured, DESIGN.md section 28: the other order, the tiles of one block of columns adjacent so that they share
+// their rows of H in a cache, is 1.6 x faster where H is far larger than the caches and 1.4 x slower where it fits, the usual case.)  A
+// block's R = m - l0 steps are the same for all its threads, so no branch diverges.  Reads stay inside the rows [t0, t1): hw reads
+// t0 + r and hu reads t0 + l0 + r for r < R = (t1 - t0) - l0, whatever k; a lag l0 + k >= L of the edge tile is summed and not stored.
+template <int TL>
+__global__ void __launch_bounds__(kThreads) autocov_kernel(const double *H, int64_t ldh, int64_t Q, int64_t qblocks, int64_t t0, int64_t t1,
+                                                           int64_t L, const double *mean, double *s, int64_t lds)
+{
+    const int64_t tile = (int64_t)blockIdx.x / qblocks;
+    const int64_t q = ((int64_t)blockIdx.x % qblocks) * kThreads + threadIdx.x;
+    if (q >= Q) return;
+    const int64_t l0 = tile * TL, R = (t1 - t0) - l0;
+    const double mu = mean[q];
+    const double *hw = H + t0 * ldh + q, *hu = hw + l0 * ldh;
+    double w[TL], acc[TL];
+#pragma unroll
+    for (int k = 0; k < TL; k++) w[k] = acc[k] = 0.0;
+    if (R >= TL) autocov_chunk<TL, true, false>(hw, hu, ldh, mu, TL, w, acc);
+    else autocov_chunk<TL, true, true>(hw, hu, ldh, mu, R, w, acc);
+    int64_t base = TL;
+    for (; base + TL <= R; base += TL) autocov_chunk<TL, false, false>(hw + base * ldh, hu + base * ldh, ldh, mu, TL, w, acc);
+    if (base < R) autocov_chunk<TL, false, true>(hw + base * ldh, hu + base * ldh, ldh, mu, R - base, w, acc);
+#pragma unroll
+    for (int k = 0; k < TL; k++)
+        if (l0 + k < L) s[(l0 + k) * lds + q] = acc[k];
+}
+
+// One sum is sequential in c by definition, so a thread is as fast as its loads: kPoolAhead of them are issued before they are added,
+// in order, and the L A threads go out in blocks of one wavefront, over as many compute units as there are.
+constexpr int kPoolThreads = 64, kPoolAhead = 16;
+
+__global__ void __launch_bounds__(kPoolThreads) autocov_pool_kernel(const double *s, int64_t L, int64_t lds, int64_t M, int32_t A, double *pooled)
+{
+    const int64_t i = (int64_t)blockIdx.x * kPoolThreads + threadIdx.x;
+    if (i >= L * A) return;
+    const double *row = s + (i / A) * lds + i % A;
+    double p = 0.0;
+    int64_t c = 0;
+    for (; c + kPoolAhead <= M; c += kPoolAhead) {
+        double v[kPoolAhead];
+#pragma unroll
+        for (int k = 0; k < kPoolAhead; k++) v[k] = row[(c + k) * A];
+#pragma unroll
+        for (int k = 0; k < kPoolAhead; k++) p = p + v[k];
+    }
+    for (; c < M; c++) p = p + row[c * A];
+    pooled[i] = p;
+}
+
 }  // namespace mcmc
 }  // namespace trpl
 
@@ -417,6 +514,56 @@ static int check_chain_stats(const void *H, int64_t n, int64_t ldh, int64_t Q, i
     if (!H) return api_fail(TRPL_ERR_ARG, "H is NULL");
     if (!mean) return api_fail(TRPL_ERR_ARG, "mean is NULL");
     if (!m2) return api_fail(TRPL_ERR_ARG, "m2 is NULL");
+    return TRPL_OK;
+}
+
+// the shape of an autocovariance call: check_chain_stats' refusals in its order and words, then the lags and the grid
+static int check_autocov_shape(int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, int64_t L)
+{
+    if (n < 1) return api_fail(TRPL_ERR_ARG, "n=%lld must be >= 1", (long long)n);
+    if (Q < 1) return api_fail(TRPL_ERR_ARG, "Q=%lld must be >= 1", (long long)Q);
+    if (int rc = refine_check_blocks("Q", Q, "columns")) return rc;
+    if (ldh < Q) return api_fail(TRPL_ERR_ARG, "ldh=%lld must be >= Q=%lld", (long long)ldh, (long long)Q);
+    if (!(0 <= t0 && t0 < t1 && t1 <= n))
+        return api_fail(TRPL_ERR_ARG, "t0=%lld, t1=%lld: the range must satisfy 0 <= t0 < t1 <= n=%lld", (long long)t0, (long long)t1,
+                        (long long)n);
+    if (L < 1 || L > t1 - t0) return api_fail(TRPL_ERR_ARG, "L=%lld must be in [1, t1 - t0 = %lld]", (long long)L, (long long)(t1 - t0));
+    const int64_t tiles = (L + mcmc::kAutocovTile - 1) / mcmc::kAutocovTile;
+    if (tiles > kRefineMaxBlocks / (int64_t)refine_blocks(Q))
+        return api_fail(TRPL_ERR_ARG, "L=%lld: %lld tiles of %d lags for Q=%lld are more than 2^31 - 1 blocks of %d columns", (long long)L,
+                        (long long)tiles, mcmc::kAutocovTile, (long long)Q, refine::kThreads);
+    return TRPL_OK;
+}
+
+static int check_autocov(const void *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, int64_t L, const void *mean, const void *s,
+                         int64_t lds)
+{
+    if (int rc = check_autocov_shape(n, ldh, Q, t0, t1, L)) return rc;
+    if (lds < Q) return api_fail(TRPL_ERR_ARG, "lds=%lld must be >= Q=%lld", (long long)lds, (long long)Q);
+    if (!H) return api_fail(TRPL_ERR_ARG, "H is NULL");
+    if (!mean) return api_fail(TRPL_ERR_ARG, "mean is NULL");
+    if (!s) return api_fail(TRPL_ERR_ARG, "s is NULL");
+    return TRPL_OK;
+}
+
+// M sequences of A columns each: M A fits an int64 once M has passed the grid's limit
+static int check_autocov_groups(int64_t M, int32_t A)
+{
+    if (M < 1) return api_fail(TRPL_ERR_ARG, "M=%lld must be >= 1", (long long)M);
+    if (int rc = refine_check_blocks("M", M, "sequences")) return rc;
+    if (A < 1 || A > TRPL_REFINE_MAX_DIMS) return api_fail(TRPL_ERR_ARG, "A=%d must be in [1, %d]", A, TRPL_REFINE_MAX_DIMS);
+    return TRPL_OK;
+}
+
+static int check_autocov_pool(const void *s, int64_t L, int64_t lds, int64_t M, int32_t A, const void *pooled)
+{
+    if (L < 1) return api_fail(TRPL_ERR_ARG, "L=%lld must be >= 1", (long long)L);
+    if (int rc = check_autocov_groups(M, A)) return rc;
+    if (L > kRefineMaxBlocks * (int64_t)mcmc::kPoolThreads / A)
+        return api_fail(TRPL_ERR_ARG, "L=%lld lags of A=%d columns are more than 2^31 - 1 blocks of %d sums", (long long)L, A, mcmc::kPoolThreads);
+    if (lds < M * A) return api_fail(TRPL_ERR_ARG, "lds=%lld must be >= M * A = %lld", (long long)lds, (long long)(M * A));
+    if (!s) return api_fail(TRPL_ERR_ARG, "s is NULL");
+    if (!pooled) return api_fail(TRPL_ERR_ARG, "pooled is NULL");
     return TRPL_OK;
 }
 
@@ -698,6 +845,81 @@ int trpl_mcmc_chain_stats(const double *H, int64_t n, int64_t ldh, int64_t Q, in
     double *dM = sg.out(mean, (size_t)Q), *dV = sg.out(m2, (size_t)Q);
     if (int rc = sg.begin()) return rc;
     if (int rc = trpl_mcmc_chain_stats_dev(dH, steps, Q, Q, 0, steps, dM, dV, sg.stream())) return rc;
+    return sg.finish(seconds);
+}
+
+int trpl_mcmc_autocov_tile(void) { return mcmc::kAutocovTile; }
+
+int trpl_mcmc_autocov_dev(const double *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, int64_t L, double *mean, double *s,
+                          int64_t lds, void *stream)
+{
+    if (int rc = check_autocov(H, n, ldh, Q, t0, t1, L, mean, s, lds)) return rc;
+    const int64_t qblocks = refine_blocks(Q), tiles = (L + mcmc::kAutocovTile - 1) / mcmc::kAutocovTile;
+    hipLaunchKernelGGL(mcmc::autocov_mean_kernel, dim3((unsigned)qblocks), dim3(refine::kThreads), 0, (hipStream_t)stream, H, ldh, Q, t0, t1,
+                       mean);
+    hipLaunchKernelGGL(mcmc::autocov_kernel<mcmc::kAutocovTile>, dim3((unsigned)(qblocks * tiles)), dim3(refine::kThreads), 0,
+                       (hipStream_t)stream, H, ldh, Q, qblocks, t0, t1, L, mean, s, lds);
+    return refine_launched("mcmc autocov");
+}
+
+int trpl_mcmc_autocov(const double *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, int64_t L, double *mean, double *s,
+                      int32_t device, double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    if (int rc = check_autocov(H, n, ldh, Q, t0, t1, L, mean, s, Q)) return rc;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const int64_t steps = t1 - t0;
+    const double *dH = sg.in(H + t0 * ldh, (size_t)ldh, (size_t)Q, (size_t)steps);      // the steps of the range only, compact on the device
+    double *dM = sg.out(mean, (size_t)Q), *dS = sg.out(s, (size_t)L * Q);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_mcmc_autocov_dev(dH, steps, Q, Q, 0, steps, L, dM, dS, Q, sg.stream())) return rc;
+    return sg.finish(seconds);
+}
+
+int trpl_mcmc_autocov_pool_dev(const double *s, int64_t L, int64_t lds, int64_t M, int32_t A, double *pooled, void *stream)
+{
+    if (int rc = check_autocov_pool(s, L, lds, M, A, pooled)) return rc;
+    hipLaunchKernelGGL(mcmc::autocov_pool_kernel, dim3((unsigned)((L * A + mcmc::kPoolThreads - 1) / mcmc::kPoolThreads)),
+                       dim3(mcmc::kPoolThreads), 0, (hipStream_t)stream, s, L, lds, M, A, pooled);
+    return refine_launched("mcmc autocov pool");
+}
+
+int trpl_mcmc_autocov_pool(const double *s, int64_t L, int64_t lds, int64_t M, int32_t A, double *pooled, int32_t device, double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    if (int rc = check_autocov_pool(s, L, lds, M, A, pooled)) return rc;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const int64_t Q = M * A;
+    const double *dS = sg.in(s, (size_t)lds, (size_t)Q, (size_t)L);
+    double *dP = sg.out(pooled, (size_t)L * A);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_mcmc_autocov_pool_dev(dS, L, Q, M, A, dP, sg.stream())) return rc;
+    return sg.finish(seconds);
+}
+
+int trpl_mcmc_autocov_chains(const double *H, int64_t n, int64_t ldh, int64_t M, int32_t A, int64_t t0, int64_t t1, int64_t L, double *mean,
+                             double *m2, double *pooled, int32_t device, double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    if (int rc = check_autocov_groups(M, A)) return rc;
+    const int64_t Q = M * A;
+    if (int rc = check_autocov_shape(n, ldh, Q, t0, t1, L)) return rc;
+    if (!H) return api_fail(TRPL_ERR_ARG, "H is NULL");
+    if (!mean) return api_fail(TRPL_ERR_ARG, "mean is NULL");
+    if (!m2) return api_fail(TRPL_ERR_ARG, "m2 is NULL");
+    if (!pooled) return api_fail(TRPL_ERR_ARG, "pooled is NULL");
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    const int64_t steps = t1 - t0;
+    const double *dH = sg.in(H + t0 * ldh, (size_t)ldh, (size_t)Q, (size_t)steps);
+    double *dM = sg.out(mean, (size_t)Q), *dP = sg.out(pooled, (size_t)L * A);
+    double *dS = (double *)sg.scratch((size_t)L * Q * sizeof(double));                  // s stays on the device: only its row 0 goes back
+    sg.down(dS, m2, 0, (size_t)Q * sizeof(double), 1);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = trpl_mcmc_autocov_dev(dH, steps, Q, Q, 0, steps, L, dM, dS, Q, sg.stream())) return rc;
+    if (int rc = trpl_mcmc_autocov_pool_dev(dS, L, Q, M, A, dP, sg.stream())) return rc;
     return sg.finish(seconds);
 }
 

@@ -769,6 +769,31 @@ def mcmc_chain_stats_device(H, t0, t1, mean, m2, Q=None):
         _chk(m2, torch.float64, "m2"), _stream()))
 
 
+def mcmc_autocov_device(H, t0, t1, mean, s, Q=None):
+    """trpl_mcmc_autocov_dev: mean (Q,) and s (L, lds >= Q) f64 <- per column q < Q of the history H (n, ldh >= Q) f64, which stays
+    where it is, the mean over the steps [t0, t1) and the sums s[l][q] of e[t] e[t + l], e = H - mean, over ascending t, for the
+    L = s.shape[0] <= t1 - t0 lags 0 .. L - 1: the plain loop's bits, s[0] those of mcmc_chain_stats_device's m2.  Q defaults to ldh."""
+    import torch
+    if H.dim() != 2 or s.dim() != 2:
+        raise ValueError("H must be (n, ldh) and s (L, lds)")
+    Q = H.shape[1] if Q is None else int(Q)
+    if tuple(mean.shape) != (Q,):
+        raise ValueError("mean must be (Q,)")
+    _abi.check(_abi.lib().trpl_mcmc_autocov_dev(
+        _chk(H, torch.float64, "H"), H.shape[0], H.shape[1], Q, int(t0), int(t1), s.shape[0], _chk(mean, torch.float64, "mean"),
+        _chk(s, torch.float64, "s"), s.shape[1], _stream()))
+
+
+def mcmc_autocov_pool_device(s, M, A, pooled):
+    """trpl_mcmc_autocov_pool_dev: pooled (L, A) f64 <- the sums over the M sequences of s (L, lds >= M A) f64, whose columns are M
+    groups of A: pooled[l][a] = sum over c of s[l][c A + a], c ascending."""
+    import torch
+    if s.dim() != 2 or tuple(pooled.shape) != (s.shape[0], int(A)):
+        raise ValueError("s must be (L, lds) and pooled (L, A)")
+    _abi.check(_abi.lib().trpl_mcmc_autocov_pool_dev(
+        _chk(s, torch.float64, "s"), s.shape[0], s.shape[1], int(M), int(A), _chk(pooled, torch.float64, "pooled"), _stream()))
+
+
 def credible_interval_device(x, W, lo=0.025, hi=0.975):
     """utils.py:185-196 on the device: sort by x, cumulate the weights, last point below `lo` and first
     above `hi` (torch.sort / cumsum: library plumbing, no custom kernel)."""

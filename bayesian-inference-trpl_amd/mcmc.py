@@ -22,7 +22,9 @@ with states of adjacent rungs exchanged by swap.  The hot rungs cross between se
 only slowly; Tempered.rung(0) is the ensemble at the temperature the caller asked for.
 
 Chains.samples() returns (X, W = 1): what posterior.moments / quantiles / columns / corner / credible_intervals and
-posterior_predictive take."""
+posterior_predictive take.  Those states are not independent draws: Chains.ess() says how many independent draws they amount to per column, Chains.mcse()
+the Monte-Carlo error of a mean, Chains.autocorr() the pooled autocorrelation; the sums over the steps and the
+chains run on the device (autocov, autocov_pool), the estimator on top is ess_from_sums."""
 import numpy as np
 
 from . import _abi, posterior, refine
@@ -237,6 +239,82 @@ def chain_stats(H, t0=0, t1=None, Q=None, device=0, info=None):
     return mean, m2
 
 
+def autocov(H, max_lag, t0=0, t1=None, Q=None, device=0, info=None):
+    """(mean (Q,), s (max_lag, Q)): per column q < Q of the history H (n, ldh >= Q) over the steps [t0, t1), the mean and the sums
+    s[l][q] of e[t] e[t + l], e = H - mean, t = t0 .. t1 - 1 - l ascending from +0.0, for the lags l < max_lag <= t1 - t0
+    (trpl_mcmc_autocov): the plain loop's bits; s[0] is chain_stats' m2.  Q defaults to ldh, t1 to n."""
+    H = _f64(H)
+    if H.ndim != 2:
+        raise ValueError("H must be (n, ldh)")
+    n, ldh = H.shape
+    Q = ldh if Q is None else int(Q)
+    t1 = n if t1 is None else int(t1)
+    L = int(max_lag)
+    mean, s = np.empty(max(Q, 0)), np.empty((max(L, 0), max(Q, 0)))
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_mcmc_autocov(_abi.ptr(H), n, ldh, Q, int(t0), t1, L, _abi.ptr(mean), _abi.ptr(s), int(device),
+                                            _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value)
+    return mean, s
+
+
+def autocov_pool(s, M, A, device=0, info=None):
+    """pooled (L, A): the sums of autocov over the M sequences of s (L, lds >= M A), whose columns are M groups of A:
+    pooled[l][a] = sum over c of s[l][c A + a], c ascending from +0.0 (trpl_mcmc_autocov_pool)."""
+    s = _f64(s)
+    if s.ndim != 2:
+        raise ValueError("s must be (L, lds)")
+    L, lds = s.shape
+    pooled = np.empty((L, max(int(A), 0)))
+    sec = _abi.C.c_double(0.0)
+    _abi.check(_abi.lib().trpl_mcmc_autocov_pool(_abi.ptr(s), L, lds, int(M), int(A), _abi.ptr(pooled), int(device), _abi.C.byref(sec)))
+    if info is not None:
+        info.update(seconds=sec.value)
+    return pooled
+
+
+def ess_from_sums(mean, m2, pooled, m):
+    """(ess (A,), info): the effective sample size of M sequences of m steps each from their sums -- mean and m2 (M, A) (or (M A,),
+    sequence-major) of chain_stats, pooled (L, A) of autocov_pool.  Pure numpy; the rule is Geyer's initial monotone sequence on
+    the pooled autocorrelation (Geyer 1992; Vehtari et al. 2021).  Per column:
+        W = mean over the sequences of m2 / (m - 1),   B / m = var(mean, ddof 1) (0 for M = 1),   var+ = (m - 1) / m W + B / m,
+        acov[l] = pooled[l] / (M m),   rho[l] = 1 - (W - acov[l]) / var+,   rho[0] = 1,
+        P_k = rho[2k] + rho[2k + 1];   K = the first k where P_k > 0 fails, or L // 2 if it never fails -- then truncated is True:
+        the lags ran out before the correlation did, and the ESS is an upper bound;   P made non-increasing by a running minimum,
+        tau = max(-1 + 2 sum_{k < K} P_k, 1 / log10(M m)),   ess = M m / tau.
+    info: tau, var_plus (A,), rho (L, A), K (A,) int, truncated (A,) bool."""
+    pooled = np.asarray(pooled, dtype=np.float64)
+    if pooled.ndim != 2:
+        raise ValueError("pooled must be (L, A)")
+    L, A = pooled.shape
+    mean, m2 = np.asarray(mean, dtype=np.float64).reshape(-1, A), np.asarray(m2, dtype=np.float64).reshape(-1, A)
+    M, m = mean.shape[0], int(m)
+    if m2.shape != mean.shape or M < 1 or L < 1:
+        raise ValueError("mean and m2 must be (M, A) and pooled (L, A)")
+    if m < 2:
+        raise ValueError("m=%d: a sequence needs at least 2 steps" % m)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        W = np.mean(m2 / (m - 1), axis=0)
+        Bm = np.var(mean, axis=0, ddof=1) if M > 1 else np.zeros(A)
+        var_plus = (m - 1) / m * W + Bm
+        rho = 1.0 - (W - pooled / float(M * m)) / var_plus
+    rho[0] = 1.0
+    pairs = L // 2
+    P = rho[0:2 * pairs:2] + rho[1:2 * pairs:2]                  # (pairs, A)
+    K, truncated, tau = np.empty(A, dtype=np.int64), np.empty(A, dtype=bool), np.empty(A)
+    floor = 1.0 / np.log10(M * m)
+    for a in range(A):
+        stop = np.flatnonzero(~(P[:, a] > 0.0))
+        truncated[a] = stop.size == 0
+        K[a] = pairs if truncated[a] else stop[0]
+        mono = np.minimum.accumulate(P[:K[a], a])
+        total = float(np.cumsum(mono)[-1]) if K[a] else 0.0      # the pairs added one by one, in order
+        tau[a] = max(-1.0 + 2.0 * total, floor)
+    ess = M * m / tau
+    return ess, dict(tau=tau, var_plus=var_plus, rho=rho, K=K, truncated=truncated)
+
+
 def start(X, LL, C, minX, maxX, do_log, sim_flags=None, tf=1.0, offset=0.5, log_ratio=None, device=0):
     """(X0, U0, LL0): C starting states drawn from an importance-weighted set -- a first generation (X, LL), or a refined
     Population's log_ratio() as (X, LL, log_ratio=) -- by refine.resample of posterior.weights at temperature tf, with their unit
@@ -279,6 +357,46 @@ class Chains:
         W = np.mean(m2 / (n2 - 1), axis=0)
         B = n2 * np.var(mean, axis=0, ddof=1)
         return np.sqrt(((n2 - 1) / n2 * W + B / n2) / W)
+
+    def ess(self, burn=0, max_lag=None, values=None, max_workspace_bytes=1 << 30):
+        """(ess (D,), info): the effective sample size of the kept sweeps from burn on, per column -- how many independent draws the
+        n2 x 2 C states amount to (ess_from_sums has the rule and info's keys).  The history is cut into the two halves of rhat,
+        2 C sequences of n2 = (n - burn) // 2; each half is one trpl_mcmc_autocov_chains call (the sums over the steps and over
+        the chains on the device, s in device scratch), and the pooled sums are added, half 0 + half 1.  max_lag defaults to n2.
+        values (n, C, D), 1 <= D <= 16, asks about other columns than U: LL[..., None], X, a derived column of posterior.columns.
+        The scratch of a call, 8 max_lag C D bytes, is refused above max_workspace_bytes before anything runs."""
+        n, C = self.U.shape[:2]
+        V = self.U if values is None else _f64(values)
+        if V.ndim != 3 or V.shape[:2] != (n, C) or not 1 <= V.shape[2] <= _abi.REFINE_MAX_DIMS:
+            raise ValueError("values must be (n, C, D) = (%d, %d, 1 .. %d)" % (n, C, _abi.REFINE_MAX_DIMS))
+        D = V.shape[2]
+        burn = int(burn)
+        n2 = (n - burn) // 2
+        if n2 < 2:
+            raise ValueError("split-R-hat needs two halves of at least 2 kept sweeps each; %d sweeps are left after burn" % max(n - burn, 0))
+        L = n2 if max_lag is None else int(max_lag)
+        if not 1 <= L <= n2:
+            raise ValueError("max_lag=%d must be in [1, n2 = %d]" % (L, n2))
+        need = 8 * L * C * D
+        if need > int(max_workspace_bytes):
+            raise ValueError("the sums of %d lags x %d chains x %d columns need %d bytes of device scratch, more than "
+                             "max_workspace_bytes = %d" % (L, C, D, need, int(max_workspace_bytes)))
+        H = _f64(V).reshape(n, C * D)
+        mean, m2, pooled = np.empty((2, C * D)), np.empty((2, C * D)), np.empty((2, L, D))
+        for k in (0, 1):
+            _abi.check(_abi.lib().trpl_mcmc_autocov_chains(_abi.ptr(H), n, C * D, C, D, burn + k * n2, burn + (k + 1) * n2, L,
+                                                           _abi.ptr(mean[k]), _abi.ptr(m2[k]), _abi.ptr(pooled[k]), int(self.device),
+                                                           None))
+        return ess_from_sums(mean.reshape(2 * C, D), m2.reshape(2 * C, D), pooled[0] + pooled[1], n2)
+
+    def autocorr(self, burn=0, max_lag=None, values=None):
+        """rho (max_lag, D): the pooled autocorrelation of ess(), lag by lag."""
+        return self.ess(burn, max_lag, values)[1]["rho"]
+
+    def mcse(self, burn=0, max_lag=None, values=None):
+        """(D,): the Monte-Carlo standard error of the mean of each column over the kept sweeps from burn on, sqrt(var+ / ess)."""
+        ess, info = self.ess(burn, max_lag, values)
+        return np.sqrt(info["var_plus"] / ess)
 
 
 def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0, kind="de", gamma=None, scale=None, jump_every=0,

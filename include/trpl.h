@@ -1389,6 +1389,57 @@ int trpl_mcmc_swap(double *U, double *X, double *LL, int32_t K, int64_t group, i
                    int64_t chain0, uint64_t seed, uint32_t step, int32_t *swapped, int32_t device, double *seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_mcmc_autocov, trpl_mcmc_autocov_pool, trpl_mcmc_autocov_chains -- the sums of the chains' AUTOCOVARIANCE, from which the
+ * effective sample size of a run and the Monte-Carlo error of its posterior means are formed (Geyer 1992; Vehtari, Gelman, Simpson,
+ * Carpenter & Buerkner 2021).  The kept states of a chain are not independent draws; these calls say how many independent draws they
+ * amount to.  (csrc/mcmc.hip)
+ *
+ * trpl_mcmc_autocov: H [n][ldh >= Q] a history that stays where it is, the steps [t0, t1), m = t1 - t0, and L lags, 1 <= L <= m.
+ * mean [Q] and s [L][lds >= Q] out:
+ *     mean[q] = (sum of H[t][q], t ascending from +0.0) / m                       trpl_mcmc_chain_stats' expression and bits
+ *     e[t]    = H[t][q] - mean[q]
+ *     s[l][q] = sum over t = t0 .. t1 - 1 - l, ascending, from +0.0, of e[t] * e[t + l]
+ * subtract, multiply, add, no contraction: the plain loop, bit for bit.  Every (l, q) sum is sequential in t, so the bits do not
+ * depend on how (l, q) is spread over threads; s[0][q] is trpl_mcmc_chain_stats' m2[q] bit for bit.  A NaN propagates through its
+ * column only.  A thread owns one column and a tile of trpl_mcmc_autocov_tile() consecutive lags, adjacent threads adjacent
+ * columns; no element of H outside the rows [t0, t1) and the columns [0, Q) is read, no element of s outside [0, L) x [0, Q) is
+ * written.  The host-buffer form copies the steps of the range only and returns s compact, [L][Q].
+ *
+ * trpl_mcmc_autocov_pool: s [L][lds >= M A] in, pooled [L][A] out, the columns read as M sequences of A columns each:
+ *     pooled[l][a] = sum over c = 0 .. M - 1, ascending, from +0.0, of s[l][c * A + a]
+ * one thread per (l, a), fixed order, no atomics.
+ *
+ * trpl_mcmc_autocov_chains: the host-buffer fused form: H [n][ldh >= M A] is staged (the steps of the range only), both kernels
+ * run with s in device scratch (8 L M A bytes), and only mean [M A], m2 [M A] = s[0] and pooled [L][A] come back: the bits of the
+ * two calls above.
+ *
+ * THE ESTIMATOR (trpl_amd.mcmc.ess_from_sums; numpy, one rule).  Per column a, over M sequences of m steps:
+ *     W = mean over c of m2 / (m - 1),   B / m = var(mean_c, ddof 1),   var+ = (m - 1) / m W + B / m,
+ *     acov[l] = pooled[l] / (M m),   rho[l] = 1 - (W - acov[l]) / var+,   rho[0] = 1,
+ *     P_k = rho[2k] + rho[2k + 1] (Geyer's pairs),   K = the first k where P_k > 0 fails, or L / 2 if it never fails (the sum is then
+ *     truncated by L and the ESS an upper bound),   P made non-increasing by a running minimum,
+ *     tau = max(-1 + 2 sum_{k < K} P_k, 1 / log10(M m)),   ess = M m / tau.
+ * trpl_amd.mcmc.Chains.ess applies it to the 2 C sequences of a history split in halves, as split-R-hat splits it: one
+ * trpl_mcmc_autocov_chains call per half, the pooled sums added, half 0 + half 1.
+ *
+ * Refused with TRPL_ERR_ARG before a device is touched, the message naming the argument: a NULL H, mean, s, m2, pooled; n < 1,
+ * Q < 1, ldh < Q, lds < Q (pool: lds < M * A); a range that does not satisfy 0 <= t0 < t1 <= n; L < 1 or L > t1 - t0; M < 1; A
+ * outside [1, TRPL_REFINE_MAX_DIMS]; more than 2^31 - 1 blocks: of 256 columns, of 256 sequences, of 256 columns times the lag tiles,
+ * or of 64 sums of the pool.  The _dev calls take device pointers, allocate nothing and never synchronise.
+ * Python: trpl_amd.mcmc.autocov / autocov_pool / ess_from_sums, Chains.ess / autocorr / mcse, trpl_amd.device.mcmc_autocov_device /
+ * mcmc_autocov_pool_device.
+ * ------------------------------------------------------------------------------------- */
+int trpl_mcmc_autocov_tile(void);
+int trpl_mcmc_autocov_dev(const double *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, int64_t L, double *mean, double *s,
+                          int64_t lds, void *stream);
+int trpl_mcmc_autocov(const double *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, int64_t L, double *mean, double *s,
+                      int32_t device, double *seconds);
+int trpl_mcmc_autocov_pool_dev(const double *s, int64_t L, int64_t lds, int64_t M, int32_t A, double *pooled, void *stream);
+int trpl_mcmc_autocov_pool(const double *s, int64_t L, int64_t lds, int64_t M, int32_t A, double *pooled, int32_t device, double *seconds);
+int trpl_mcmc_autocov_chains(const double *H, int64_t n, int64_t ldh, int64_t M, int32_t A, int64_t t0, int64_t t1, int64_t L, double *mean,
+                             double *m2, double *pooled, int32_t device, double *seconds);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the
  * measurement plan): S independent systems  ld[i] x[i-1] + d[i] x[i] + ud[i] x[i+1] = b[i],
  * i < L, the problem pcreduce solves (pvSimPCR.py:42-81), operands and result in HBM, arrays

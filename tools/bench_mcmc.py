@@ -1,6 +1,7 @@
 """The three kernels of the ensemble Metropolis sampler on resident tensors, in one process on one device.
 
-    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--fold] [--tempered [--rungs 16]] [--out profiles/mcmc_bench.jsonl]
+    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--fold] [--tempered [--rungs 16]] [--autocov]
+                               [--out profiles/mcmc_bench.jsonl]
 
 propose:     mcmc_propose_device of `chains` chains in the reference's box (A = 10 active columns), with `chains` partners
              (differential evolution: two gathered partner rows per chain), and the random walk for comparison.
@@ -12,6 +13,11 @@ accept:      mcmc_accept_device of the same chains, about a third of the proposa
              propose_rungs (partners from the chain's own rung), accept_rungs and levels_rungs (a temperature per rung, beside
              levels, the scalar call) and swap (parity 0).
 chain_stats: mcmc_chain_stats_device over a history of n steps of chains * A columns (one half of a split-R-hat: n / 2 steps).
+--autocov:   the two kernels of the effective sample size over the same chains * A columns, at L = 64 and L = 512 lags:
+             mcmc_autocov_device over one half of a history (max(n / 2, L) steps, so L = 64 runs on chain_stats' own range) and
+             mcmc_autocov_pool_device over its s.  The line records beside each time the two floors it is to be read against
+             (DESIGN.md section 28): H read once per lag tile and s written once at 6.1 TB/s, and two fp64 instructions per term
+             at 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz.
 Device events around `reps` back-to-back calls after a warm-up, median of 3 interleaved passes (tools/bench_quantiles.measure).
 Appends one JSON line to --out."""
 import argparse
@@ -37,6 +43,7 @@ def main():
     ap.add_argument("--fold", action="store_true")
     ap.add_argument("--tempered", action="store_true")
     ap.add_argument("--rungs", type=int, default=16)
+    ap.add_argument("--autocov", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcmc_bench.jsonl"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -95,6 +102,20 @@ def main():
         calls["levels"] = lambda: tdev.mcmc_levels_device(LL, 1.0, 0, 42, 0, level)
         calls["levels_rungs"] = lambda: tdev.mcmc_levels_rungs_device(LL, ladder, 0, 42, 0, level)
         calls["swap"] = lambda: tdev.mcmc_swap_device(Us, Xs, LLs, ladder, 0, 0, 42, 0, swapped)
+    floors = {}
+    if a.autocov:
+        tile, Q = trpl_amd._abi.lib().trpl_mcmc_autocov_tile(), C * A
+        for L in (64, 512):
+            m = max(a.n // 2, L)
+            Hl = H if m <= a.n else torch.rand((m, Q), generator=g, **f64)
+            mean_l, s_l, pooled_l = torch.empty(Q, **f64), torch.empty((L, Q), **f64), torch.empty((L, A), **f64)
+            calls["autocov_L%d" % L] = lambda Hl=Hl, m=m, mean_l=mean_l, s_l=s_l: tdev.mcmc_autocov_device(Hl, 0, m, mean_l, s_l)
+            calls["autocov_pool_L%d" % L] = lambda s_l=s_l, pooled_l=pooled_l: tdev.mcmc_autocov_pool_device(s_l, C, A, pooled_l)
+            terms = Q * sum(m - l for l in range(L))
+            tiles = (L + tile - 1) // tile
+            floors["autocov_L%d" % L] = {"steps": m, "terms": terms, "fp64_floor_ms": 2.0 * terms / (256 * 4 * 16 * 2.4e9) * 1e3,
+                                         "hbm_floor_ms": 8.0 * Q * (tiles * m + m + L) / 6.1e12 * 1e3}
+            floors["autocov_pool_L%d" % L] = {"hbm_floor_ms": 8.0 * L * (Q + A) / 6.1e12 * 1e3}
     ms, passes = measure(calls, a.reps)
     torch.cuda.synchronize()
     line = {"bench": "mcmc", "device": torch.cuda.get_device_name(0), "chains": C, "A": A, "ncol": ncol, "n": a.n, "reps": a.reps, "ms": ms,
@@ -104,6 +125,8 @@ def main():
         line["folded_share"] = float((codes == 2).double().mean().item())
     if a.tempered:
         line.update(rungs=a.rungs, swapped_share=float(swapped.double().mean().item()))
+    if a.autocov:
+        line.update(autocov_tile=tile, autocov_floors=floors)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as f:
         f.write(json.dumps(line) + "\n")

@@ -37,7 +37,9 @@ proposals that left the prior box, split-R-hat of every free parameter and its 2
 those of the importance run, which are printed; seconds["mcmc"].  --rw x uses a random walk of half-width x (unit coordinates)
 instead.  --fold reflects a proposal that leaves the prior box back at its faces (mcmc.run(bounds="fold"): DESIGN.md section 25),
 so that every proposal is solved; "mcmc" then gains "bounds" and "folded", the share of proposals that were reflected.  Without
---mcmc the output is unchanged, and so is "mcmc" without --fold.
+--mcmc the output is unchanged, and so is "mcmc" without --fold.  "mcmc" also holds "ess": per free parameter the effective sample
+size of the kept sweeps (Chains.ess: DESIGN.md section 28), the autocorrelation time tau in sweeps, whether the lags truncated the
+sum (the ESS is then an upper bound) and the Monte-Carlo error of the mean in unit coordinates, printed beside R-hat.
 --early-reject (with --mcmc) stops solving a proposal once its rejection is certain (mcmc.run(early_reject=True): DESIGN.md section
 26; the chain is the same, bit for bit) and adds "early_reject" to "mcmc": the share of solved proposals that were cut and the
 system-timesteps solved.  With or without it "mcmc" holds "system_timesteps", the solver iterations summed over every proposal, and
@@ -336,6 +338,15 @@ if MCMC:
     print("mcmc (%s): %d chains from %d distinct starts, %d sweeps: acceptance %.3f (kept half %.3f), outside the prior box %.4f, worst R-hat %.3f"
           % (out["mcmc"]["proposal"], CHAINS, out["mcmc"]["distinct_starts"], SWEEPS, out["mcmc"]["acceptance"],
              out["mcmc"]["acceptance_kept"], minfo["outside"], out["mcmc"]["worst_rhat"]), file=sys.stderr)
+    ess, einfo = ch.ess()                                        # the kept sweeps as 2 C split sequences, every lag
+    mcse = np.sqrt(einfo["var_plus"] / ess)
+    out["mcmc"]["ess"] = {sm.PARAM_NAMES[c]: {"ess": float(e), "tau": float(t), "truncated": bool(tr), "mcse_unit": float(s)}
+                          for c, e, t, tr, s in zip(act, ess, einfo["tau"], einfo["truncated"], mcse)}
+    out["mcmc"]["kept_states"] = int(2 * (ch.U.shape[0] // 2) * CHAINS)
+    for c, r, e, t, tr in zip(act, rhat, ess, einfo["tau"], einfo["truncated"]):
+        print("mcmc: %-8s R-hat %.3f  ESS %9.1f of %d kept states  tau %8.2f sweeps%s"
+              % (sm.PARAM_NAMES[c], r, e, out["mcmc"]["kept_states"], t, "  (truncated by the lags: ESS is an upper bound)" if tr else ""),
+              file=sys.stderr)
     if TEMPERED:
         worst = [float(np.nanmax(r.rhat())) for r in rungs]
         out["mcmc"]["tempered"] = {"rungs": TEMPERED, "ladder": [float(v) for v in ladder], "tf_hot_ess": hot_ess,
