@@ -77,6 +77,7 @@ CORNER_PRIMARY, CORNER_MAX_COLS, CORNER_MAX_BINS = 13, 19, 128
 REFINE_MAX_DIMS, REFINE_MAX_PARENTS = 16, 1 << 20      # TRPL_REFINE_MAX_DIMS, TRPL_REFINE_MAX_PARENTS
 MCMC_FOLD = 0x10              # TRPL_MCMC_FOLD: trpl_mcmc_propose reflects a proposal back at the faces of the unit cube
 MCMC_MAX_RUNGS = 64           # TRPL_MCMC_MAX_RUNGS: temperatures of one trpl_mcmc_*_rungs / trpl_mcmc_swap call
+SEED_MASK, STEP_MASK = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF      # a uint64_t seed and a uint32_t step of the trpl_mcmc_* calls, from any int
 
 
 class TrplError(RuntimeError):

@@ -33,10 +33,21 @@
 //       decides it: xi of counter word 0x10a keyed by row a, d = (LL[b] - LL[a]) * (1 / tf[k] - 1 / tf[k + 1]), the rows of U, X and LL
 //       exchanged when neither LL is NaN and d >= 0 or log(xi) < d.  The thread of an upper row writes nothing; an unpaired row's
 //       writes swapped = 0 only.
+// The host half, after the kernels.  Propose, accept, levels and swap have one argument record each (ProposeCall, AcceptCall,
+// LevelsCall, SwapCall: the entry point's arguments in its order; `rungs` marks a *_rungs call, whose group, K and ladder are read
+// only then) and three functions on it: check (every refusal of the operation, in the order the entry points have always had; it
+// makes the kernel arguments Scale, Box, Ladder), launch (the kernel of the record, on a stream) and stage (the record's buffers
+// through a Staged).  on_stream is every _dev form: check, launch.  staged is every host-buffer form: check before a device is
+// opened, stage, launch -- the record is checked once.  An extern "C" entry point fills a record and returns one of the two.  A new
+// argument goes into the record, its refusal into check, its buffer into stage; a new operation is a record with these three.
+// chain_stats and the autocovariance calls are a kernel or two each and stay written out; their refusals share check_history.
 // Compiled with -ffp-contract=off like refine.hip: every result is its expression with one rounding per operation.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <initializer_list>
+#include <type_traits>
 
 #include "api_util.hpp"
 #include "refine_common.hpp"
@@ -399,73 +410,37 @@ __global__ void __launch_bounds__(kPoolThreads) autocov_pool_kernel(const double
 
 using namespace trpl;
 
-static int check_chains(int64_t count, int32_t A, int64_t chain0)
+namespace {                                                      // the host half: the file comment has its structure
+
+// "<name> is NULL" for the first pointer of the list that is
+int check_not_null(std::initializer_list<std::pair<const char *, const void *>> ptrs)
+{
+    for (const auto &q : ptrs)
+        if (!q.second) return api_fail(TRPL_ERR_ARG, "%s is NULL", q.first);
+    return TRPL_OK;
+}
+
+int check_count(int64_t count)
 {
     if (count < 1) return api_fail(TRPL_ERR_ARG, "count=%lld must be >= 1", (long long)count);
-    if (int rc = refine_check_blocks("count", count, "chains")) return rc;
+    return refine_check_blocks("count", count, "chains");
+}
+
+int check_chains(int64_t count, int32_t A, int64_t chain0)
+{
+    if (int rc = check_count(count)) return rc;
     if (A < 1 || A > TRPL_REFINE_MAX_DIMS) return api_fail(TRPL_ERR_ARG, "A=%d must be in [1, %d]", A, TRPL_REFINE_MAX_DIMS);
     if (chain0 < 0) return api_fail(TRPL_ERR_ARG, "chain0=%lld must be >= 0", (long long)chain0);
     return TRPL_OK;
 }
 
-static int check_propose(const void *U, const void *partners, int64_t count, int64_t P, int32_t A, double gamma, const double *scale,
-                         int64_t chain0, uint32_t flags, const void *Up, const void *Xp, const void *inside, mcmc::Scale &sc)
-{
-    if (int rc = check_chains(count, A, chain0)) return rc;
-    if (P < 0 || P == 1) return api_fail(TRPL_ERR_ARG, "P=%lld must be 0 (random walk) or >= 2", (long long)P);
-    if (P > 0 && !partners) return api_fail(TRPL_ERR_ARG, "partners is NULL with P=%lld", (long long)P);
-    if (!U) return api_fail(TRPL_ERR_ARG, "U is NULL");
-    if (!scale) return api_fail(TRPL_ERR_ARG, "scale is NULL");
-    if (!Up) return api_fail(TRPL_ERR_ARG, "Up is NULL");
-    if (!Xp) return api_fail(TRPL_ERR_ARG, "Xp is NULL");
-    if (!inside) return api_fail(TRPL_ERR_ARG, "inside is NULL");
-    if (!isfinite(gamma)) return api_fail(TRPL_ERR_ARG, "gamma=%g must be finite", gamma);
-    if (flags & ~(uint32_t)(TRPL_BOX_EQUAL_MU | TRPL_BOX_EQUAL_S | TRPL_BOX_EQUAL_AUGER | TRPL_MCMC_FOLD))
-        return api_fail(TRPL_ERR_ARG, "flags=0x%x: only the TRPL_BOX_EQUAL_* bits and TRPL_MCMC_FOLD apply", flags);
-    sc = mcmc::Scale();
-    for (int d = 0; d < A; d++) {
-        if (!(isfinite(scale[d]) && scale[d] >= 0.0)) return api_fail(TRPL_ERR_ARG, "scale[%d]=%g must be finite and >= 0", d, scale[d]);
-        sc.s[d] = scale[d];
-    }
-    return TRPL_OK;
-}
-
-static int check_accept(const void *U, const void *X, const void *LL, const void *Up, const void *Xp, const void *LLp, const void *inside,
-                        int64_t count, int32_t A, int32_t ncol, double tf, int64_t chain0, const void *accepted)
-{
-    if (int rc = check_chains(count, A, chain0)) return rc;
-    if (ncol < 1 || ncol > 16) return api_fail(TRPL_ERR_ARG, "ncol=%d must be in [1, 16]", ncol);
-    if (!(isfinite(tf) && tf > 0.0)) return api_fail(TRPL_ERR_ARG, "tf=%g must be finite and > 0", tf);
-    if (!U) return api_fail(TRPL_ERR_ARG, "U is NULL");
-    if (!X) return api_fail(TRPL_ERR_ARG, "X is NULL");
-    if (!LL) return api_fail(TRPL_ERR_ARG, "LL is NULL");
-    if (!Up) return api_fail(TRPL_ERR_ARG, "Up is NULL");
-    if (!Xp) return api_fail(TRPL_ERR_ARG, "Xp is NULL");
-    if (!LLp) return api_fail(TRPL_ERR_ARG, "LLp is NULL");
-    if (!inside) return api_fail(TRPL_ERR_ARG, "inside is NULL");
-    if (!accepted) return api_fail(TRPL_ERR_ARG, "accepted is NULL");
-    return TRPL_OK;
-}
-
-static int check_levels(const void *LL, int64_t count, double tf, int64_t chain0, const void *level)
-{
-    if (count < 1) return api_fail(TRPL_ERR_ARG, "count=%lld must be >= 1", (long long)count);
-    if (int rc = refine_check_blocks("count", count, "chains")) return rc;
-    if (!(isfinite(tf) && tf > 0.0)) return api_fail(TRPL_ERR_ARG, "tf=%g must be finite and > 0", tf);
-    if (chain0 < 0) return api_fail(TRPL_ERR_ARG, "chain0=%lld must be >= 0", (long long)chain0);
-    if (!LL) return api_fail(TRPL_ERR_ARG, "LL is NULL");
-    if (!level) return api_fail(TRPL_ERR_ARG, "level is NULL");
-    return TRPL_OK;
-}
-
 // the ladder of the *_rungs calls and of the swap: K, group and the K temperatures, copied into the kernel argument
-static int check_ladder(int32_t K, int64_t group, const double *tf, mcmc::Ladder &lad)
+int check_ladder(int32_t K, int64_t group, const double *tf, mcmc::Ladder &lad)
 {
     if (K < 1 || K > TRPL_MCMC_MAX_RUNGS) return api_fail(TRPL_ERR_ARG, "K=%d must be in [1, %d]", K, TRPL_MCMC_MAX_RUNGS);
     if (group < 1) return api_fail(TRPL_ERR_ARG, "group=%lld must be >= 1", (long long)group);
     if (int rc = refine_check_blocks("group", group, "chains")) return rc;
     if (!tf) return api_fail(TRPL_ERR_ARG, "tf is NULL");
-    lad = mcmc::Ladder();
     for (int k = 0; k < K; k++) {
         if (!(isfinite(tf[k]) && tf[k] > 0.0)) return api_fail(TRPL_ERR_ARG, "tf[%d]=%g must be finite and > 0", k, tf[k]);
         lad.tf[k] = tf[k];
@@ -473,36 +448,210 @@ static int check_ladder(int32_t K, int64_t group, const double *tf, mcmc::Ladder
     return TRPL_OK;
 }
 
-static int check_rung_count(int64_t count, int32_t K, int64_t group)
+// ---- the records: an entry point's arguments in its order, then what check() makes of them for the kernel.  rungs marks a *_rungs
+// call: group, K and ladder are read only then, and tf only without.
+struct ProposeCall {
+    const double *U, *partners; int64_t count, P; bool rungs; int64_t group; int32_t A; double gamma; const double *scale;
+    int64_t chain0; uint64_t seed; uint32_t step; int32_t ncol; const double *lo, *hi; const int32_t *do_log; uint32_t flags;
+    double *Up, *Xp; int32_t *inside;
+    mcmc::Scale sc = {}; refine::Box bx = {};
+};
+struct AcceptCall {
+    double *U, *X, *LL; const double *Up, *Xp, *LLp; const int32_t *inside; int64_t count; int32_t A, ncol; double tf; bool rungs;
+    int32_t K; int64_t group; const double *ladder; int64_t chain0; uint64_t seed; uint32_t step; int32_t *accepted;
+    mcmc::Ladder lad = {};
+};
+struct LevelsCall {
+    const double *LL; int64_t count; double tf; bool rungs; int32_t K; int64_t group; const double *ladder; int64_t chain0; uint64_t seed;
+    uint32_t step; double *level;
+    mcmc::Ladder lad = {};
+};
+struct SwapCall {                                                // count: K group, the rows of one block; check() sets it
+    double *U, *X, *LL; int64_t count; int32_t K; int64_t group; int32_t A, ncol; const double *tf; int32_t parity; int64_t chain0;
+    uint64_t seed; uint32_t step; int32_t *swapped;
+    mcmc::Ladder lad = {};
+};
+
+// ---- check: every refusal of an operation, in the order its entry points have always had
+int check(ProposeCall &k)
 {
-    if (count != (int64_t)K * group)
-        return api_fail(TRPL_ERR_ARG, "count=%lld must be K * group = %d * %lld", (long long)count, K, (long long)group);
+    if (int rc = check_chains(k.count, k.A, k.chain0)) return rc;
+    if (k.P < 0 || k.P == 1) return api_fail(TRPL_ERR_ARG, "P=%lld must be 0 (random walk) or >= 2", (long long)k.P);
+    if (k.P > 0 && !k.partners) return api_fail(TRPL_ERR_ARG, "partners is NULL with P=%lld", (long long)k.P);
+    if (int rc = check_not_null({{"U", k.U}, {"scale", k.scale}, {"Up", k.Up}, {"Xp", k.Xp}, {"inside", k.inside}})) return rc;
+    if (!isfinite(k.gamma)) return api_fail(TRPL_ERR_ARG, "gamma=%g must be finite", k.gamma);
+    if (k.flags & ~(uint32_t)(TRPL_BOX_EQUAL_MU | TRPL_BOX_EQUAL_S | TRPL_BOX_EQUAL_AUGER | TRPL_MCMC_FOLD))
+        return api_fail(TRPL_ERR_ARG, "flags=0x%x: only the TRPL_BOX_EQUAL_* bits and TRPL_MCMC_FOLD apply", k.flags);
+    for (int d = 0; d < k.A; d++) {
+        if (!(isfinite(k.scale[d]) && k.scale[d] >= 0.0)) return api_fail(TRPL_ERR_ARG, "scale[%d]=%g must be finite and >= 0", d, k.scale[d]);
+        k.sc.s[d] = k.scale[d];
+    }
+    if (k.rungs && k.group < 2) return api_fail(TRPL_ERR_ARG, "group=%lld must be >= 2", (long long)k.group);
+    if (k.rungs && (k.P < k.group || k.P % k.group))
+        return api_fail(TRPL_ERR_ARG, "P=%lld must be a positive multiple of group=%lld", (long long)k.P, (long long)k.group);
+    if (k.rungs && k.count > k.P) return api_fail(TRPL_ERR_ARG, "count=%lld must be <= P=%lld", (long long)k.count, (long long)k.P);
+    return refine_make_box(k.ncol, k.lo, k.hi, k.do_log, k.flags & ~(uint32_t)TRPL_MCMC_FOLD, k.A, k.bx);
+}
+
+int check(AcceptCall &k)
+{
+    if (k.rungs) {                                               // a rung call refuses its ladder first and its count last
+        if (int rc = check_ladder(k.K, k.group, k.ladder, k.lad)) return rc;
+        k.tf = k.lad.tf[0];
+    }
+    if (int rc = check_chains(k.count, k.A, k.chain0)) return rc;
+    if (k.ncol < 1 || k.ncol > 16) return api_fail(TRPL_ERR_ARG, "ncol=%d must be in [1, 16]", k.ncol);
+    if (!(isfinite(k.tf) && k.tf > 0.0)) return api_fail(TRPL_ERR_ARG, "tf=%g must be finite and > 0", k.tf);
+    if (int rc = check_not_null({{"U", k.U}, {"X", k.X}, {"LL", k.LL}, {"Up", k.Up}, {"Xp", k.Xp}, {"LLp", k.LLp}, {"inside", k.inside},
+                                 {"accepted", k.accepted}}))
+        return rc;
+    if (k.rungs && k.count != (int64_t)k.K * k.group)
+        return api_fail(TRPL_ERR_ARG, "count=%lld must be K * group = %d * %lld", (long long)k.count, k.K, (long long)k.group);
     return TRPL_OK;
 }
 
-static int check_propose_rungs(int64_t count, int64_t P, int64_t group)
+int check(LevelsCall &k)
 {
-    if (group < 2) return api_fail(TRPL_ERR_ARG, "group=%lld must be >= 2", (long long)group);
-    if (P < group || P % group) return api_fail(TRPL_ERR_ARG, "P=%lld must be a positive multiple of group=%lld", (long long)P, (long long)group);
-    if (count > P) return api_fail(TRPL_ERR_ARG, "count=%lld must be <= P=%lld", (long long)count, (long long)P);
+    if (k.rungs) {                                               // a rung call refuses its ladder first and its count last
+        if (int rc = check_ladder(k.K, k.group, k.ladder, k.lad)) return rc;
+        k.tf = k.lad.tf[0];
+    }
+    if (int rc = check_count(k.count)) return rc;
+    if (!(isfinite(k.tf) && k.tf > 0.0)) return api_fail(TRPL_ERR_ARG, "tf=%g must be finite and > 0", k.tf);
+    if (k.chain0 < 0) return api_fail(TRPL_ERR_ARG, "chain0=%lld must be >= 0", (long long)k.chain0);
+    if (int rc = check_not_null({{"LL", k.LL}, {"level", k.level}})) return rc;
+    if (k.rungs && k.count != (int64_t)k.K * k.group)
+        return api_fail(TRPL_ERR_ARG, "count=%lld must be K * group = %d * %lld", (long long)k.count, k.K, (long long)k.group);
     return TRPL_OK;
 }
 
-static int check_swap(const void *U, const void *X, const void *LL, int32_t K, int64_t group, int32_t A, int32_t ncol, const double *tf,
-                      int32_t parity, int64_t chain0, const void *swapped, mcmc::Ladder &lad)
+int check(SwapCall &k)
 {
-    if (int rc = check_ladder(K, group, tf, lad)) return rc;
-    if (int rc = check_chains((int64_t)K * group, A, chain0)) return rc;
-    if (ncol < 1 || ncol > 16) return api_fail(TRPL_ERR_ARG, "ncol=%d must be in [1, 16]", ncol);
-    if (parity != 0 && parity != 1) return api_fail(TRPL_ERR_ARG, "parity=%d must be 0 or 1", parity);
-    if (!U) return api_fail(TRPL_ERR_ARG, "U is NULL");
-    if (!X) return api_fail(TRPL_ERR_ARG, "X is NULL");
-    if (!LL) return api_fail(TRPL_ERR_ARG, "LL is NULL");
-    if (!swapped) return api_fail(TRPL_ERR_ARG, "swapped is NULL");
-    return TRPL_OK;
+    if (int rc = check_ladder(k.K, k.group, k.tf, k.lad)) return rc;
+    k.count = (int64_t)k.K * k.group;
+    if (int rc = check_chains(k.count, k.A, k.chain0)) return rc;
+    if (k.ncol < 1 || k.ncol > 16) return api_fail(TRPL_ERR_ARG, "ncol=%d must be in [1, 16]", k.ncol);
+    if (k.parity != 0 && k.parity != 1) return api_fail(TRPL_ERR_ARG, "parity=%d must be 0 or 1", k.parity);
+    return check_not_null({{"U", k.U}, {"X", k.X}, {"LL", k.LL}, {"swapped", k.swapped}});
 }
 
-static int check_chain_stats(const void *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, const void *mean, const void *m2)
+// ---- launch: the kernel of a checked record on a stream.  TRPL_MCMC_LAUNCH is the switch (A) over kernel<1> .. kernel<16>: its
+// kernel argument names the instantiation by `n`.  A kernel<A> is emitted where its launch stands; the functions keep the order the
+// code object has had, the single-temperature kernels before the rung kernels.
+#define TRPL_MCMC_CASE(v, ...)                                                                                                         \
+    case v: {                                                                                                                          \
+        constexpr int n = v;                                                                                                           \
+        hipLaunchKernelGGL(__VA_ARGS__);                                                                                               \
+    } break;
+#define TRPL_MCMC_CASES(...)                                                                                                           \
+    TRPL_MCMC_CASE(1, __VA_ARGS__) TRPL_MCMC_CASE(2, __VA_ARGS__) TRPL_MCMC_CASE(3, __VA_ARGS__) TRPL_MCMC_CASE(4, __VA_ARGS__)        \
+    TRPL_MCMC_CASE(5, __VA_ARGS__) TRPL_MCMC_CASE(6, __VA_ARGS__) TRPL_MCMC_CASE(7, __VA_ARGS__) TRPL_MCMC_CASE(8, __VA_ARGS__)        \
+    TRPL_MCMC_CASE(9, __VA_ARGS__) TRPL_MCMC_CASE(10, __VA_ARGS__) TRPL_MCMC_CASE(11, __VA_ARGS__) TRPL_MCMC_CASE(12, __VA_ARGS__)     \
+    TRPL_MCMC_CASE(13, __VA_ARGS__) TRPL_MCMC_CASE(14, __VA_ARGS__) TRPL_MCMC_CASE(15, __VA_ARGS__) TRPL_MCMC_CASE(16, __VA_ARGS__)
+#define TRPL_MCMC_LAUNCH(A, kernel, count, ...)                                                                                        \
+    switch (A) { TRPL_MCMC_CASES(kernel, dim3(refine_blocks(count)), dim3(refine::kThreads), 0, __VA_ARGS__) }
+
+int launch_propose(const ProposeCall &k, hipStream_t stream)
+{
+    const bool fold = (k.flags & TRPL_MCMC_FOLD) != 0;
+    TRPL_MCMC_LAUNCH(k.A, fold ? mcmc::propose_fold_kernel<n> : mcmc::propose_kernel<n>, k.count, stream, k.U, k.partners, k.count, k.P,
+                     k.gamma, k.sc, k.chain0, (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.step, k.bx, k.Up, k.Xp, k.inside)
+    return refine_launched("mcmc propose");
+}
+
+int launch_accept(const AcceptCall &k, hipStream_t stream)
+{
+    TRPL_MCMC_LAUNCH(k.A, mcmc::accept_kernel<n>, k.count, stream, k.U, k.X, k.LL, k.Up, k.Xp, k.LLp, k.inside, k.count, k.ncol, k.tf,
+                     k.chain0, (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.step, k.accepted)
+    return refine_launched("mcmc accept");
+}
+
+int launch(const LevelsCall &k, hipStream_t stream)
+{
+    const dim3 grid(refine_blocks(k.count)), block(refine::kThreads);
+    if (k.rungs)
+        hipLaunchKernelGGL(mcmc::levels_rungs_kernel, grid, block, 0, stream, k.LL, k.count, k.lad, k.group, k.chain0, (uint32_t)k.seed,
+                           (uint32_t)(k.seed >> 32), k.step, k.level);
+    else
+        hipLaunchKernelGGL(mcmc::levels_kernel, grid, block, 0, stream, k.LL, k.count, k.tf, k.chain0, (uint32_t)k.seed,
+                           (uint32_t)(k.seed >> 32), k.step, k.level);
+    return refine_launched(k.rungs ? "mcmc levels rungs" : "mcmc levels");
+}
+
+int launch(const ProposeCall &k, hipStream_t stream)
+{
+    if (!k.rungs) return launch_propose(k, stream);
+    const bool fold = (k.flags & TRPL_MCMC_FOLD) != 0;
+    TRPL_MCMC_LAUNCH(k.A, fold ? mcmc::propose_rungs_fold_kernel<n> : mcmc::propose_rungs_kernel<n>, k.count, stream, k.U, k.partners,
+                     k.count, k.P, k.gamma, k.sc, k.chain0, (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.step, k.bx, k.Up, k.Xp, k.inside,
+                     k.group)
+    return refine_launched("mcmc propose rungs");
+}
+
+int launch(const AcceptCall &k, hipStream_t stream)
+{
+    if (!k.rungs) return launch_accept(k, stream);
+    TRPL_MCMC_LAUNCH(k.A, mcmc::accept_rungs_kernel<n>, k.count, stream, k.U, k.X, k.LL, k.Up, k.Xp, k.LLp, k.inside, k.count, k.ncol, k.lad,
+                     k.chain0, (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.step, k.accepted, k.group)
+    return refine_launched("mcmc accept rungs");
+}
+
+int launch(const SwapCall &k, hipStream_t stream)
+{
+    TRPL_MCMC_LAUNCH(k.A, mcmc::swap_kernel<n>, k.count, stream, k.U, k.X, k.LL, k.count, k.K, k.group, k.ncol, k.lad, k.parity, k.chain0,
+                     (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.step, k.swapped)
+    return refine_launched("mcmc swap");
+}
+
+// ---- stage: the record's buffers through a Staged, host pointers replaced by their device copies
+void stage(ProposeCall &k, Staged &sg)
+{
+    const size_t n = (size_t)k.count;
+    const double *partners = sg.in(k.partners, (size_t)k.P * k.A);
+    k.U = sg.in(k.U, n * k.A); k.partners = k.P > 0 ? partners : nullptr;
+    k.Up = sg.out(k.Up, n * k.A); k.Xp = sg.out(k.Xp, n * k.ncol); k.inside = sg.out(k.inside, n);
+}
+
+void stage(AcceptCall &k, Staged &sg)
+{
+    const size_t n = (size_t)k.count;
+    k.U = sg.inout(k.U, n * k.A); k.X = sg.inout(k.X, n * k.ncol); k.LL = sg.inout(k.LL, n);
+    k.Up = sg.in(k.Up, n * k.A); k.Xp = sg.in(k.Xp, n * k.ncol); k.LLp = sg.in(k.LLp, n);
+    k.inside = sg.in(k.inside, n); k.accepted = sg.out(k.accepted, n);
+}
+
+void stage(LevelsCall &k, Staged &sg) { k.LL = sg.in(k.LL, (size_t)k.count); k.level = sg.out(k.level, (size_t)k.count); }
+
+void stage(SwapCall &k, Staged &sg)
+{
+    const size_t n = (size_t)k.count;
+    k.U = sg.inout(k.U, n * k.A); k.X = sg.inout(k.X, n * k.ncol); k.LL = sg.inout(k.LL, n); k.swapped = sg.out(k.swapped, n);
+}
+
+// ---- the two forms of an entry point.  on_stream is a _dev form: every check, then the launch on the caller's stream.  staged is
+// a host-buffer form: every check before a device is opened, then the launch of the same record on its staged buffers.
+template <class Call>
+int on_stream(Call k, void *stream)
+{
+    if (int rc = check(k)) return rc;
+    return launch(k, (hipStream_t)stream);
+}
+
+template <class Call>
+int staged(Call k, int32_t device, double *seconds)
+{
+    if (seconds) *seconds = 0.0;
+    if (int rc = check(k)) return rc;
+    Staged sg;
+    if (int rc = sg.open(device)) return rc;
+    stage(k, sg);
+    if (int rc = sg.begin()) return rc;
+    if (int rc = launch(k, sg.stream())) return rc;
+    return sg.finish(seconds);
+}
+
+// ---- the histories of chain_stats and the autocovariance sums
+int check_history(int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1)
 {
     if (n < 1) return api_fail(TRPL_ERR_ARG, "n=%lld must be >= 1", (long long)n);
     if (Q < 1) return api_fail(TRPL_ERR_ARG, "Q=%lld must be >= 1", (long long)Q);
@@ -511,22 +660,19 @@ static int check_chain_stats(const void *H, int64_t n, int64_t ldh, int64_t Q, i
     if (!(0 <= t0 && t0 < t1 && t1 <= n))
         return api_fail(TRPL_ERR_ARG, "t0=%lld, t1=%lld: the range must satisfy 0 <= t0 < t1 <= n=%lld", (long long)t0, (long long)t1,
                         (long long)n);
-    if (!H) return api_fail(TRPL_ERR_ARG, "H is NULL");
-    if (!mean) return api_fail(TRPL_ERR_ARG, "mean is NULL");
-    if (!m2) return api_fail(TRPL_ERR_ARG, "m2 is NULL");
     return TRPL_OK;
 }
 
-// the shape of an autocovariance call: check_chain_stats' refusals in its order and words, then the lags and the grid
-static int check_autocov_shape(int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, int64_t L)
+int check_chain_stats(const void *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, const void *mean, const void *m2)
 {
-    if (n < 1) return api_fail(TRPL_ERR_ARG, "n=%lld must be >= 1", (long long)n);
-    if (Q < 1) return api_fail(TRPL_ERR_ARG, "Q=%lld must be >= 1", (long long)Q);
-    if (int rc = refine_check_blocks("Q", Q, "columns")) return rc;
-    if (ldh < Q) return api_fail(TRPL_ERR_ARG, "ldh=%lld must be >= Q=%lld", (long long)ldh, (long long)Q);
-    if (!(0 <= t0 && t0 < t1 && t1 <= n))
-        return api_fail(TRPL_ERR_ARG, "t0=%lld, t1=%lld: the range must satisfy 0 <= t0 < t1 <= n=%lld", (long long)t0, (long long)t1,
-                        (long long)n);
+    if (int rc = check_history(n, ldh, Q, t0, t1)) return rc;
+    return check_not_null({{"H", H}, {"mean", mean}, {"m2", m2}});
+}
+
+// the shape of an autocovariance call: the history, then the lags and the grid
+int check_autocov_shape(int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, int64_t L)
+{
+    if (int rc = check_history(n, ldh, Q, t0, t1)) return rc;
     if (L < 1 || L > t1 - t0) return api_fail(TRPL_ERR_ARG, "L=%lld must be in [1, t1 - t0 = %lld]", (long long)L, (long long)(t1 - t0));
     const int64_t tiles = (L + mcmc::kAutocovTile - 1) / mcmc::kAutocovTile;
     if (tiles > kRefineMaxBlocks / (int64_t)refine_blocks(Q))
@@ -535,19 +681,16 @@ static int check_autocov_shape(int64_t n, int64_t ldh, int64_t Q, int64_t t0, in
     return TRPL_OK;
 }
 
-static int check_autocov(const void *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, int64_t L, const void *mean, const void *s,
-                         int64_t lds)
+int check_autocov(const void *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, int64_t L, const void *mean, const void *s,
+                  int64_t lds)
 {
     if (int rc = check_autocov_shape(n, ldh, Q, t0, t1, L)) return rc;
     if (lds < Q) return api_fail(TRPL_ERR_ARG, "lds=%lld must be >= Q=%lld", (long long)lds, (long long)Q);
-    if (!H) return api_fail(TRPL_ERR_ARG, "H is NULL");
-    if (!mean) return api_fail(TRPL_ERR_ARG, "mean is NULL");
-    if (!s) return api_fail(TRPL_ERR_ARG, "s is NULL");
-    return TRPL_OK;
+    return check_not_null({{"H", H}, {"mean", mean}, {"s", s}});
 }
 
 // M sequences of A columns each: M A fits an int64 once M has passed the grid's limit
-static int check_autocov_groups(int64_t M, int32_t A)
+int check_autocov_groups(int64_t M, int32_t A)
 {
     if (M < 1) return api_fail(TRPL_ERR_ARG, "M=%lld must be >= 1", (long long)M);
     if (int rc = refine_check_blocks("M", M, "sequences")) return rc;
@@ -555,17 +698,17 @@ static int check_autocov_groups(int64_t M, int32_t A)
     return TRPL_OK;
 }
 
-static int check_autocov_pool(const void *s, int64_t L, int64_t lds, int64_t M, int32_t A, const void *pooled)
+int check_autocov_pool(const void *s, int64_t L, int64_t lds, int64_t M, int32_t A, const void *pooled)
 {
     if (L < 1) return api_fail(TRPL_ERR_ARG, "L=%lld must be >= 1", (long long)L);
     if (int rc = check_autocov_groups(M, A)) return rc;
     if (L > kRefineMaxBlocks * (int64_t)mcmc::kPoolThreads / A)
         return api_fail(TRPL_ERR_ARG, "L=%lld lags of A=%d columns are more than 2^31 - 1 blocks of %d sums", (long long)L, A, mcmc::kPoolThreads);
     if (lds < M * A) return api_fail(TRPL_ERR_ARG, "lds=%lld must be >= M * A = %lld", (long long)lds, (long long)(M * A));
-    if (!s) return api_fail(TRPL_ERR_ARG, "s is NULL");
-    if (!pooled) return api_fail(TRPL_ERR_ARG, "pooled is NULL");
-    return TRPL_OK;
+    return check_not_null({{"s", s}, {"pooled", pooled}});
 }
+
+}  // namespace
 
 extern "C" {
 
@@ -573,125 +716,51 @@ int trpl_mcmc_propose_dev(const double *U, const double *partners, int64_t count
                           int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol, const double *lo, const double *hi,
                           const int32_t *do_log, uint32_t flags, double *Up, double *Xp, int32_t *inside, void *stream)
 {
-    mcmc::Scale sc;
-    if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, flags, Up, Xp, inside, sc)) return rc;
-    refine::Box bx;
-    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags & ~(uint32_t)TRPL_MCMC_FOLD, A, bx)) return rc;
-    const dim3 grid(refine_blocks(count)), block(refine::kThreads);
-    const bool fold = (flags & TRPL_MCMC_FOLD) != 0;
-    switch (A) {
-#define TRPL_CASE(n)                                                                                                                   \
-    case n:                                                                                                                            \
-        hipLaunchKernelGGL(fold ? mcmc::propose_fold_kernel<n> : mcmc::propose_kernel<n>, grid, block, 0, (hipStream_t)stream, U,         \
-                           partners, count, P, gamma, sc, chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step, bx, Up, Xp, inside);    \
-        break;
-        TRPL_REFINE_DIMS(TRPL_CASE)
-#undef TRPL_CASE
-    }
-    return refine_launched("mcmc propose");
+    return on_stream(ProposeCall{U, partners, count, P, false, 0, A, gamma, scale, chain0, seed, step, ncol, lo, hi, do_log, flags, Up, Xp,
+                                 inside}, stream);
 }
 
 int trpl_mcmc_propose(const double *U, const double *partners, int64_t count, int64_t P, int32_t A, double gamma, const double *scale,
                       int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol, const double *lo, const double *hi, const int32_t *do_log,
                       uint32_t flags, double *Up, double *Xp, int32_t *inside, int32_t device, double *seconds)
 {
-    if (seconds) *seconds = 0.0;
-    mcmc::Scale sc;
-    if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, flags, Up, Xp, inside, sc)) return rc;
-    refine::Box bx;
-    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags & ~(uint32_t)TRPL_MCMC_FOLD, A, bx)) return rc;
-    Staged sg;
-    if (int rc = sg.open(device)) return rc;
-    const double *dU = sg.in(U, (size_t)count * A), *dP = sg.in(partners, (size_t)P * A);
-    double *dUp = sg.out(Up, (size_t)count * A), *dXp = sg.out(Xp, (size_t)count * ncol);
-    int32_t *dIn = sg.out(inside, (size_t)count);
-    if (int rc = sg.begin()) return rc;
-    if (int rc = trpl_mcmc_propose_dev(dU, P > 0 ? dP : nullptr, count, P, A, gamma, scale, chain0, seed, step, ncol, lo, hi, do_log, flags,
-                                       dUp, dXp, dIn, sg.stream()))
-        return rc;
-    return sg.finish(seconds);
+    return staged(ProposeCall{U, partners, count, P, false, 0, A, gamma, scale, chain0, seed, step, ncol, lo, hi, do_log, flags, Up, Xp,
+                              inside}, device, seconds);
 }
 
 int trpl_mcmc_accept_dev(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
                          int64_t count, int32_t A, int32_t ncol, double tf, int64_t chain0, uint64_t seed, uint32_t step,
                          int32_t *accepted, void *stream)
 {
-    if (int rc = check_accept(U, X, LL, Up, Xp, LLp, inside, count, A, ncol, tf, chain0, accepted)) return rc;
-    const dim3 grid(refine_blocks(count)), block(refine::kThreads);
-    switch (A) {
-#define TRPL_CASE(n)                                                                                                                   \
-    case n:                                                                                                                            \
-        hipLaunchKernelGGL(mcmc::accept_kernel<n>, grid, block, 0, (hipStream_t)stream, U, X, LL, Up, Xp, LLp, inside, count, ncol, tf,   \
-                           chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step, accepted);                                           \
-        break;
-        TRPL_REFINE_DIMS(TRPL_CASE)
-#undef TRPL_CASE
-    }
-    return refine_launched("mcmc accept");
+    return on_stream(AcceptCall{U, X, LL, Up, Xp, LLp, inside, count, A, ncol, tf, false, 0, 0, nullptr, chain0, seed, step, accepted}, stream);
 }
 
 int trpl_mcmc_accept(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
                      int64_t count, int32_t A, int32_t ncol, double tf, int64_t chain0, uint64_t seed, uint32_t step, int32_t *accepted,
                      int32_t device, double *seconds)
 {
-    if (seconds) *seconds = 0.0;
-    if (int rc = check_accept(U, X, LL, Up, Xp, LLp, inside, count, A, ncol, tf, chain0, accepted)) return rc;
-    Staged sg;
-    if (int rc = sg.open(device)) return rc;
-    double *dU = sg.inout(U, (size_t)count * A), *dX = sg.inout(X, (size_t)count * ncol), *dLL = sg.inout(LL, (size_t)count);
-    const double *dUp = sg.in(Up, (size_t)count * A), *dXp = sg.in(Xp, (size_t)count * ncol), *dLLp = sg.in(LLp, (size_t)count);
-    const int32_t *dIn = sg.in(inside, (size_t)count);
-    int32_t *dAcc = sg.out(accepted, (size_t)count);
-    if (int rc = sg.begin()) return rc;
-    if (int rc = trpl_mcmc_accept_dev(dU, dX, dLL, dUp, dXp, dLLp, dIn, count, A, ncol, tf, chain0, seed, step, dAcc, sg.stream())) return rc;
-    return sg.finish(seconds);
+    return staged(AcceptCall{U, X, LL, Up, Xp, LLp, inside, count, A, ncol, tf, false, 0, 0, nullptr, chain0, seed, step, accepted}, device,
+                  seconds);
 }
 
 int trpl_mcmc_levels_dev(const double *LL, int64_t count, double tf, int64_t chain0, uint64_t seed, uint32_t step, double *level,
                          void *stream)
 {
-    if (int rc = check_levels(LL, count, tf, chain0, level)) return rc;
-    hipLaunchKernelGGL(mcmc::levels_kernel, dim3(refine_blocks(count)), dim3(refine::kThreads), 0, (hipStream_t)stream, LL, count, tf,
-                       chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step, level);
-    return refine_launched("mcmc levels");
+    return on_stream(LevelsCall{LL, count, tf, false, 0, 0, nullptr, chain0, seed, step, level}, stream);
 }
 
 int trpl_mcmc_levels(const double *LL, int64_t count, double tf, int64_t chain0, uint64_t seed, uint32_t step, double *level,
                      int32_t device, double *seconds)
 {
-    if (seconds) *seconds = 0.0;
-    if (int rc = check_levels(LL, count, tf, chain0, level)) return rc;
-    Staged sg;
-    if (int rc = sg.open(device)) return rc;
-    const double *dLL = sg.in(LL, (size_t)count);
-    double *dLv = sg.out(level, (size_t)count);
-    if (int rc = sg.begin()) return rc;
-    if (int rc = trpl_mcmc_levels_dev(dLL, count, tf, chain0, seed, step, dLv, sg.stream())) return rc;
-    return sg.finish(seconds);
+    return staged(LevelsCall{LL, count, tf, false, 0, 0, nullptr, chain0, seed, step, level}, device, seconds);
 }
 
 int trpl_mcmc_propose_rungs_dev(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, int32_t A, double gamma,
                                 const double *scale, int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol, const double *lo,
                                 const double *hi, const int32_t *do_log, uint32_t flags, double *Up, double *Xp, int32_t *inside, void *stream)
 {
-    mcmc::Scale sc;
-    if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, flags, Up, Xp, inside, sc)) return rc;
-    if (int rc = check_propose_rungs(count, P, group)) return rc;
-    refine::Box bx;
-    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags & ~(uint32_t)TRPL_MCMC_FOLD, A, bx)) return rc;
-    const dim3 grid(refine_blocks(count)), block(refine::kThreads);
-    const bool fold = (flags & TRPL_MCMC_FOLD) != 0;
-    switch (A) {
-#define TRPL_CASE(n)                                                                                                                   \
-    case n:                                                                                                                            \
-        hipLaunchKernelGGL(fold ? mcmc::propose_rungs_fold_kernel<n> : mcmc::propose_rungs_kernel<n>, grid, block, 0,                    \
-                           (hipStream_t)stream, U, partners, count, P, gamma, sc, chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step,  \
-                           bx, Up, Xp, inside, group);                                                                                 \
-        break;
-        TRPL_REFINE_DIMS(TRPL_CASE)
-#undef TRPL_CASE
-    }
-    return refine_launched("mcmc propose rungs");
+    return on_stream(ProposeCall{U, partners, count, P, true, group, A, gamma, scale, chain0, seed, step, ncol, lo, hi, do_log, flags, Up,
+                                 Xp, inside}, stream);
 }
 
 int trpl_mcmc_propose_rungs(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, int32_t A, double gamma,
@@ -699,129 +768,47 @@ int trpl_mcmc_propose_rungs(const double *U, const double *partners, int64_t cou
                             const double *hi, const int32_t *do_log, uint32_t flags, double *Up, double *Xp, int32_t *inside,
                             int32_t device, double *seconds)
 {
-    if (seconds) *seconds = 0.0;
-    mcmc::Scale sc;
-    if (int rc = check_propose(U, partners, count, P, A, gamma, scale, chain0, flags, Up, Xp, inside, sc)) return rc;
-    if (int rc = check_propose_rungs(count, P, group)) return rc;
-    refine::Box bx;
-    if (int rc = refine_make_box(ncol, lo, hi, do_log, flags & ~(uint32_t)TRPL_MCMC_FOLD, A, bx)) return rc;
-    Staged sg;
-    if (int rc = sg.open(device)) return rc;
-    const double *dU = sg.in(U, (size_t)count * A), *dP = sg.in(partners, (size_t)P * A);
-    double *dUp = sg.out(Up, (size_t)count * A), *dXp = sg.out(Xp, (size_t)count * ncol);
-    int32_t *dIn = sg.out(inside, (size_t)count);
-    if (int rc = sg.begin()) return rc;
-    if (int rc = trpl_mcmc_propose_rungs_dev(dU, dP, count, P, group, A, gamma, scale, chain0, seed, step, ncol, lo, hi, do_log, flags, dUp,
-                                             dXp, dIn, sg.stream()))
-        return rc;
-    return sg.finish(seconds);
+    return staged(ProposeCall{U, partners, count, P, true, group, A, gamma, scale, chain0, seed, step, ncol, lo, hi, do_log, flags, Up, Xp,
+                              inside}, device, seconds);
 }
 
 int trpl_mcmc_accept_rungs_dev(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp,
                                const int32_t *inside, int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group, const double *tf,
                                int64_t chain0, uint64_t seed, uint32_t step, int32_t *accepted, void *stream)
 {
-    mcmc::Ladder lad;
-    if (int rc = check_ladder(K, group, tf, lad)) return rc;
-    if (int rc = check_accept(U, X, LL, Up, Xp, LLp, inside, count, A, ncol, lad.tf[0], chain0, accepted)) return rc;
-    if (int rc = check_rung_count(count, K, group)) return rc;
-    const dim3 grid(refine_blocks(count)), block(refine::kThreads);
-    switch (A) {
-#define TRPL_CASE(n)                                                                                                                   \
-    case n:                                                                                                                            \
-        hipLaunchKernelGGL(mcmc::accept_rungs_kernel<n>, grid, block, 0, (hipStream_t)stream, U, X, LL, Up, Xp, LLp, inside, count, ncol, \
-                           lad, chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step, accepted, group);                                \
-        break;
-        TRPL_REFINE_DIMS(TRPL_CASE)
-#undef TRPL_CASE
-    }
-    return refine_launched("mcmc accept rungs");
+    return on_stream(AcceptCall{U, X, LL, Up, Xp, LLp, inside, count, A, ncol, 0.0, true, K, group, tf, chain0, seed, step, accepted}, stream);
 }
 
 int trpl_mcmc_accept_rungs(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
                            int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group, const double *tf, int64_t chain0,
                            uint64_t seed, uint32_t step, int32_t *accepted, int32_t device, double *seconds)
 {
-    if (seconds) *seconds = 0.0;
-    mcmc::Ladder lad;
-    if (int rc = check_ladder(K, group, tf, lad)) return rc;
-    if (int rc = check_accept(U, X, LL, Up, Xp, LLp, inside, count, A, ncol, lad.tf[0], chain0, accepted)) return rc;
-    if (int rc = check_rung_count(count, K, group)) return rc;
-    Staged sg;
-    if (int rc = sg.open(device)) return rc;
-    double *dU = sg.inout(U, (size_t)count * A), *dX = sg.inout(X, (size_t)count * ncol), *dLL = sg.inout(LL, (size_t)count);
-    const double *dUp = sg.in(Up, (size_t)count * A), *dXp = sg.in(Xp, (size_t)count * ncol), *dLLp = sg.in(LLp, (size_t)count);
-    const int32_t *dIn = sg.in(inside, (size_t)count);
-    int32_t *dAcc = sg.out(accepted, (size_t)count);
-    if (int rc = sg.begin()) return rc;
-    if (int rc = trpl_mcmc_accept_rungs_dev(dU, dX, dLL, dUp, dXp, dLLp, dIn, count, A, ncol, K, group, tf, chain0, seed, step, dAcc,
-                                            sg.stream()))
-        return rc;
-    return sg.finish(seconds);
+    return staged(AcceptCall{U, X, LL, Up, Xp, LLp, inside, count, A, ncol, 0.0, true, K, group, tf, chain0, seed, step, accepted}, device,
+                  seconds);
 }
 
 int trpl_mcmc_levels_rungs_dev(const double *LL, int64_t count, int32_t K, int64_t group, const double *tf, int64_t chain0, uint64_t seed,
                                uint32_t step, double *level, void *stream)
 {
-    mcmc::Ladder lad;
-    if (int rc = check_ladder(K, group, tf, lad)) return rc;
-    if (int rc = check_levels(LL, count, lad.tf[0], chain0, level)) return rc;
-    if (int rc = check_rung_count(count, K, group)) return rc;
-    hipLaunchKernelGGL(mcmc::levels_rungs_kernel, dim3(refine_blocks(count)), dim3(refine::kThreads), 0, (hipStream_t)stream, LL, count,
-                       lad, group, chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step, level);
-    return refine_launched("mcmc levels rungs");
+    return on_stream(LevelsCall{LL, count, 0.0, true, K, group, tf, chain0, seed, step, level}, stream);
 }
 
 int trpl_mcmc_levels_rungs(const double *LL, int64_t count, int32_t K, int64_t group, const double *tf, int64_t chain0, uint64_t seed,
                            uint32_t step, double *level, int32_t device, double *seconds)
 {
-    if (seconds) *seconds = 0.0;
-    mcmc::Ladder lad;
-    if (int rc = check_ladder(K, group, tf, lad)) return rc;
-    if (int rc = check_levels(LL, count, lad.tf[0], chain0, level)) return rc;
-    if (int rc = check_rung_count(count, K, group)) return rc;
-    Staged sg;
-    if (int rc = sg.open(device)) return rc;
-    const double *dLL = sg.in(LL, (size_t)count);
-    double *dLv = sg.out(level, (size_t)count);
-    if (int rc = sg.begin()) return rc;
-    if (int rc = trpl_mcmc_levels_rungs_dev(dLL, count, K, group, tf, chain0, seed, step, dLv, sg.stream())) return rc;
-    return sg.finish(seconds);
+    return staged(LevelsCall{LL, count, 0.0, true, K, group, tf, chain0, seed, step, level}, device, seconds);
 }
 
 int trpl_mcmc_swap_dev(double *U, double *X, double *LL, int32_t K, int64_t group, int32_t A, int32_t ncol, const double *tf,
                        int32_t parity, int64_t chain0, uint64_t seed, uint32_t step, int32_t *swapped, void *stream)
 {
-    mcmc::Ladder lad;
-    if (int rc = check_swap(U, X, LL, K, group, A, ncol, tf, parity, chain0, swapped, lad)) return rc;
-    const int64_t count = (int64_t)K * group;
-    const dim3 grid(refine_blocks(count)), block(refine::kThreads);
-    switch (A) {
-#define TRPL_CASE(n)                                                                                                                   \
-    case n:                                                                                                                            \
-        hipLaunchKernelGGL(mcmc::swap_kernel<n>, grid, block, 0, (hipStream_t)stream, U, X, LL, count, K, group, ncol, lad, parity,      \
-                           chain0, (uint32_t)seed, (uint32_t)(seed >> 32), step, swapped);                                             \
-        break;
-        TRPL_REFINE_DIMS(TRPL_CASE)
-#undef TRPL_CASE
-    }
-    return refine_launched("mcmc swap");
+    return on_stream(SwapCall{U, X, LL, 0, K, group, A, ncol, tf, parity, chain0, seed, step, swapped}, stream);
 }
 
 int trpl_mcmc_swap(double *U, double *X, double *LL, int32_t K, int64_t group, int32_t A, int32_t ncol, const double *tf, int32_t parity,
                    int64_t chain0, uint64_t seed, uint32_t step, int32_t *swapped, int32_t device, double *seconds)
 {
-    if (seconds) *seconds = 0.0;
-    mcmc::Ladder lad;
-    if (int rc = check_swap(U, X, LL, K, group, A, ncol, tf, parity, chain0, swapped, lad)) return rc;
-    const int64_t count = (int64_t)K * group;
-    Staged sg;
-    if (int rc = sg.open(device)) return rc;
-    double *dU = sg.inout(U, (size_t)count * A), *dX = sg.inout(X, (size_t)count * ncol), *dLL = sg.inout(LL, (size_t)count);
-    int32_t *dSw = sg.out(swapped, (size_t)count);
-    if (int rc = sg.begin()) return rc;
-    if (int rc = trpl_mcmc_swap_dev(dU, dX, dLL, K, group, A, ncol, tf, parity, chain0, seed, step, dSw, sg.stream())) return rc;
-    return sg.finish(seconds);
+    return staged(SwapCall{U, X, LL, 0, K, group, A, ncol, tf, parity, chain0, seed, step, swapped}, device, seconds);
 }
 
 int trpl_mcmc_chain_stats_dev(const double *H, int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1, double *mean, double *m2,
@@ -906,10 +893,7 @@ int trpl_mcmc_autocov_chains(const double *H, int64_t n, int64_t ldh, int64_t M,
     if (int rc = check_autocov_groups(M, A)) return rc;
     const int64_t Q = M * A;
     if (int rc = check_autocov_shape(n, ldh, Q, t0, t1, L)) return rc;
-    if (!H) return api_fail(TRPL_ERR_ARG, "H is NULL");
-    if (!mean) return api_fail(TRPL_ERR_ARG, "mean is NULL");
-    if (!m2) return api_fail(TRPL_ERR_ARG, "m2 is NULL");
-    if (!pooled) return api_fail(TRPL_ERR_ARG, "pooled is NULL");
+    if (int rc = check_not_null({{"H", H}, {"mean", mean}, {"m2", m2}, {"pooled", pooled}})) return rc;
     Staged sg;
     if (int rc = sg.open(device)) return rc;
     const int64_t steps = t1 - t0;

@@ -623,6 +623,12 @@ def refine_draw_oriented_device(zc, h, L, c, m, n_uniform, seed, generation, min
         _stream()))
 
 
+# ---- ensemble Metropolis sampling, device-resident (trpl_mcmc_*_dev).  These calls are bound by their launch, 10 to 20 us each, so
+# every wrapper marshals its own call: a marshaller shared by a pair, as mcmc.py has for the host-buffer calls, costs a Python frame
+# per call, which shows at this size.
+_M64, _M32 = _abi.SEED_MASK, _abi.STEP_MASK
+
+
 def mcmc_propose_device(U, partners, gamma, scale, chain0, seed, step, minX, maxX, do_log, Up, Xp, inside, flags=0):
     """trpl_mcmc_propose_dev: Up (count, A), Xp (count, ncol) f64 and inside (count,) int32 <- one symmetric proposal per chain of U
     (count, A) f64: u' = (u + gamma (pa - pb)) + scale (2 xi - 1) with two distinct rows of partners (P >= 2, A), or the random walk
@@ -642,7 +648,7 @@ def mcmc_propose_device(U, partners, gamma, scale, chain0, seed, step, minX, max
         raise ValueError("Up must be (count, A), Xp (count, ncol) and inside (count,)")
     _abi.check(_abi.lib().trpl_mcmc_propose_dev(
         _chk(U, torch.float64, "U"), _opt(partners, torch.float64, "partners"), count, 0 if partners is None else partners.shape[0], A,
-        float(gamma), _abi.ptr(scale), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, lo.size, _abi.ptr(lo),
+        float(gamma), _abi.ptr(scale), int(chain0), int(seed) & _M64, int(step) & _M32, lo.size, _abi.ptr(lo),
         _abi.ptr(hi), _abi.ptr(lg), int(flags), _chk(Up, torch.float64, "Up"), _chk(Xp, torch.float64, "Xp"),
         _chk(inside, torch.int32, "inside"), _stream()))
 
@@ -659,7 +665,7 @@ def mcmc_accept_device(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, ac
     _abi.check(_abi.lib().trpl_mcmc_accept_dev(
         _chk(U, torch.float64, "U"), _chk(X, torch.float64, "X"), _chk(LL, torch.float64, "LL"), _chk(Up, torch.float64, "Up"),
         _chk(Xp, torch.float64, "Xp"), _chk(LLp, torch.float64, "LLp"), _chk(inside, torch.int32, "inside"), count, U.shape[1], X.shape[1],
-        float(tf), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, _chk(accepted, torch.int32, "accepted"), _stream()))
+        float(tf), int(chain0), int(seed) & _M64, int(step) & _M32, _chk(accepted, torch.int32, "accepted"), _stream()))
 
 
 def mcmc_levels_device(LL, tf, chain0, seed, step, level):
@@ -670,7 +676,7 @@ def mcmc_levels_device(LL, tf, chain0, seed, step, level):
     if LL.dim() != 1 or tuple(level.shape) != tuple(LL.shape):
         raise ValueError("LL and level must be (count,)")
     _abi.check(_abi.lib().trpl_mcmc_levels_dev(
-        _chk(LL, torch.float64, "LL"), LL.shape[0], float(tf), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF,
+        _chk(LL, torch.float64, "LL"), LL.shape[0], float(tf), int(chain0), int(seed) & _M64, int(step) & _M32,
         _chk(level, torch.float64, "level"), _stream()))
 
 
@@ -697,7 +703,7 @@ def mcmc_propose_rungs_device(U, partners, group, gamma, scale, chain0, seed, st
         raise ValueError("Up must be (count, A), Xp (count, ncol) and inside (count,)")
     _abi.check(_abi.lib().trpl_mcmc_propose_rungs_dev(
         _chk(U, torch.float64, "U"), _chk(partners, torch.float64, "partners"), count, partners.shape[0], int(group), A, float(gamma),
-        _abi.ptr(scale), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, lo.size, _abi.ptr(lo), _abi.ptr(hi),
+        _abi.ptr(scale), int(chain0), int(seed) & _M64, int(step) & _M32, lo.size, _abi.ptr(lo), _abi.ptr(hi),
         _abi.ptr(lg), int(flags), _chk(Up, torch.float64, "Up"), _chk(Xp, torch.float64, "Xp"), _chk(inside, torch.int32, "inside"),
         _stream()))
 
@@ -717,7 +723,7 @@ def mcmc_accept_rungs_device(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, st
     _abi.check(_abi.lib().trpl_mcmc_accept_rungs_dev(
         _chk(U, torch.float64, "U"), _chk(X, torch.float64, "X"), _chk(LL, torch.float64, "LL"), _chk(Up, torch.float64, "Up"),
         _chk(Xp, torch.float64, "Xp"), _chk(LLp, torch.float64, "LLp"), _chk(inside, torch.int32, "inside"), count, U.shape[1], X.shape[1],
-        tf.size, count // tf.size, _abi.ptr(tf), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF,
+        tf.size, count // tf.size, _abi.ptr(tf), int(chain0), int(seed) & _M64, int(step) & _M32,
         _chk(accepted, torch.int32, "accepted"), _stream()))
 
 
@@ -732,7 +738,7 @@ def mcmc_levels_rungs_device(LL, tf, chain0, seed, step, level):
         raise ValueError("count = %d is no multiple of the %d rungs" % (LL.shape[0], tf.size))
     _abi.check(_abi.lib().trpl_mcmc_levels_rungs_dev(
         _chk(LL, torch.float64, "LL"), LL.shape[0], tf.size, LL.shape[0] // tf.size, _abi.ptr(tf), int(chain0),
-        int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, _chk(level, torch.float64, "level"), _stream()))
+        int(seed) & _M64, int(step) & _M32, _chk(level, torch.float64, "level"), _stream()))
 
 
 def mcmc_swap_device(U, X, LL, tf, parity, chain0, seed, step, swapped):
@@ -750,7 +756,7 @@ def mcmc_swap_device(U, X, LL, tf, parity, chain0, seed, step, swapped):
         raise ValueError("the %d rows are no multiple of the %d rungs" % (count, tf.size))
     _abi.check(_abi.lib().trpl_mcmc_swap_dev(
         _chk(U, torch.float64, "U"), _chk(X, torch.float64, "X"), _chk(LL, torch.float64, "LL"), tf.size, count // tf.size, U.shape[1],
-        X.shape[1], _abi.ptr(tf), int(parity), int(chain0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF,
+        X.shape[1], _abi.ptr(tf), int(parity), int(chain0), int(seed) & _M64, int(step) & _M32,
         _chk(swapped, torch.int32, "swapped"), _stream()))
 
 

@@ -31,79 +31,22 @@ from . import _abi, posterior, refine
 from .refine import _box, _f64
 from .sampler import box_flags
 
-_M64, _M32 = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF
+_M64, _M32 = _abi.SEED_MASK, _abi.STEP_MASK
 
 
-def propose(U, partners, gamma, scale, chain0, seed, step, minX, maxX, do_log, sim_flags=None, device=0, info=None, fold=False):
-    """(Up, Xp, inside): one symmetric proposal per chain of U (count, A) (trpl_mcmc_propose).  partners (P >= 2, A): u' = (u + gamma
-    (pa - pb)) + scale (2 xi - 1) with two distinct rows a, b of partners; partners None: the random walk u' = u + scale (2 xi - 1).
-    scale (A,) or a scalar.  chain0 is the ensemble index of U's first row and step the half-sweep: they key the Philox stream.
-    inside (count,) int32 is 0 where u' left the unit cube; Xp is formed either way.  fold=True (TRPL_MCMC_FOLD): u' is reflected
-    back at the faces of the cube, and inside is 0 where a coordinate is not finite, 1 where nothing was folded, 2 where something
-    was."""
-    U = _f64(U)
-    lo, hi, lg = _box(minX, maxX, do_log)
-    if U.ndim != 2:
-        raise ValueError("U must be (count, A)")
-    count, A = U.shape
-    scale = np.ascontiguousarray(np.broadcast_to(_f64(scale), (A,)))
-    P = 0
-    if partners is not None:
-        partners = _f64(partners)
-        if partners.ndim != 2 or partners.shape[1] != A:
-            raise ValueError("partners must be (P, A)")
-        P = partners.shape[0]
-    Up, Xp, inside = np.empty((count, A)), np.empty((count, lo.size)), np.empty(count, dtype=np.int32)
+def _timed(entry, info, *args):
+    """The host-buffer call `entry` of the library on args, a device at their end, with its `seconds` behind them: info, a dict or
+    None, receives seconds.  Every timed front end of this module goes through here."""
     sec = _abi.C.c_double(0.0)
-    _abi.check(_abi.lib().trpl_mcmc_propose(_abi.ptr(U), None if partners is None else _abi.ptr(partners), count, P, A, float(gamma),
-                                            _abi.ptr(scale), int(chain0), int(seed) & _M64, int(step) & _M32, lo.size, _abi.ptr(lo),
-                                            _abi.ptr(hi), _abi.ptr(lg), box_flags(sim_flags) | (_abi.MCMC_FOLD if fold else 0),
-                                            _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(inside), int(device), _abi.C.byref(sec)))
+    _abi.check(getattr(_abi.lib(), entry)(*args, _abi.C.byref(sec)))
     if info is not None:
         info.update(seconds=sec.value)
-    return Up, Xp, inside
 
 
-def accept(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device=0, info=None):
-    """accepted (count,) int32: the Metropolis step of every chain at temperature tf (trpl_mcmc_accept).  U (count, A), X (count,
-    ncol) and LL (count,) -- C-contiguous float64 arrays -- are updated IN PLACE: the rows of an accepted proposal are copied, the
-    others stay."""
+def _in_place(how, U, X, LL):
     for name, a in (("U", U), ("X", X), ("LL", LL)):
         if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable):
-            raise ValueError("%s is updated in place: it must be a writeable C-contiguous float64 array" % name)
-    Up, Xp, LLp = _f64(Up), _f64(Xp), _f64(LLp)
-    inside = np.ascontiguousarray(inside, dtype=np.int32)
-    if U.ndim != 2 or X.ndim != 2 or X.shape[0] != U.shape[0] or Up.shape != U.shape or Xp.shape != X.shape:
-        raise ValueError("U and Up must be (count, A), X and Xp (count, ncol)")
-    count = U.shape[0]
-    if LL.shape != (count,) or LLp.shape != (count,) or inside.shape != (count,):
-        raise ValueError("LL, LLp and inside must be (count,)")
-    accepted = np.empty(count, dtype=np.int32)
-    sec = _abi.C.c_double(0.0)
-    _abi.check(_abi.lib().trpl_mcmc_accept(_abi.ptr(U), _abi.ptr(X), _abi.ptr(LL), _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(LLp),
-                                           _abi.ptr(inside), count, U.shape[1], X.shape[1], float(tf), int(chain0), int(seed) & _M64,
-                                           int(step) & _M32, _abi.ptr(accepted), int(device), _abi.C.byref(sec)))
-    if info is not None:
-        info.update(seconds=sec.value)
-    return accepted
-
-
-def reject_levels(LL, tf, chain0, seed, step, device=0, info=None):
-    """level (count,): for every chain the sse level above which accept(), called with the same (tf, chain0, seed, step), is certain
-    to reject the proposal (trpl_mcmc_levels) -- the cut_levels of driver.loglik, one per proposal.  The accept step's uniform
-    depends on (seed; chain, step) only, so the level is known before the proposal is solved.  +inf where nothing may be cut: a
-    chain whose LL is NaN or -inf accepts anything.  LL must be minus the summed sse, i.e. come from a likelihood whose P starts
-    from zero (include/trpl.h has the argument)."""
-    LL = _f64(LL)
-    if LL.ndim != 1:
-        raise ValueError("LL must be (count,)")
-    level = np.empty(LL.shape[0])
-    sec = _abi.C.c_double(0.0)
-    _abi.check(_abi.lib().trpl_mcmc_levels(_abi.ptr(LL), LL.shape[0], float(tf), int(chain0), int(seed) & _M64, int(step) & _M32,
-                                           _abi.ptr(level), int(device), _abi.C.byref(sec)))
-    if info is not None:
-        info.update(seconds=sec.value)
-    return level
+            raise ValueError("%s is %s in place: it must be a writeable C-contiguous float64 array" % (name, how))
 
 
 def _ladder(tf):
@@ -113,39 +56,42 @@ def _ladder(tf):
     return tf
 
 
-def propose_rungs(U, partners, group, gamma, scale, chain0, seed, step, minX, maxX, do_log, sim_flags=None, device=0, info=None,
-                  fold=False):
-    """(Up, Xp, inside): propose() for a block of rungs of `group` chains each (trpl_mcmc_propose_rungs): chain i of U (count, A) takes
-    its two partners from the rows [(i // group) group, + group) of partners (P, A); P is a multiple of group, count <= P.  The rows
-    of rung k are propose() on that slice of U with that block of partners and chain0 + k group, bit for bit."""
-    U, partners = _f64(U), _f64(partners)
+def _rung_args(tf, count, refusal="count = %d is no multiple of the %d rungs"):
+    """[K, group, tf]: the temperature arguments of a *_rungs call or a swap on count rows, tf a ladder that _ladder has passed."""
+    if count % tf.size:
+        raise ValueError(refusal % (count, tf.size))
+    return [tf.size, count // tf.size, _abi.ptr(tf)]
+
+
+def _propose(U, partners, group, gamma, scale, chain0, seed, step, minX, maxX, do_log, sim_flags, device, info, fold):
+    """trpl_mcmc_propose, or with a group trpl_mcmc_propose_rungs, which takes it behind P: the marshaller of propose and
+    propose_rungs.  A new argument of either goes HERE."""
+    U = _f64(U)
     lo, hi, lg = _box(minX, maxX, do_log)
     if U.ndim != 2:
         raise ValueError("U must be (count, A)")
     count, A = U.shape
     scale = np.ascontiguousarray(np.broadcast_to(_f64(scale), (A,)))
-    if partners.ndim != 2 or partners.shape[1] != A:
-        raise ValueError("partners must be (P, A)")
+    P = 0
+    if partners is not None or group is not None:
+        partners = _f64(partners)
+        if partners.ndim != 2 or partners.shape[1] != A:
+            raise ValueError("partners must be (P, A)")
+        P = partners.shape[0]
     Up, Xp, inside = np.empty((count, A)), np.empty((count, lo.size)), np.empty(count, dtype=np.int32)
-    sec = _abi.C.c_double(0.0)
-    _abi.check(_abi.lib().trpl_mcmc_propose_rungs(_abi.ptr(U), _abi.ptr(partners), count, partners.shape[0], int(group), A, float(gamma),
-                                                  _abi.ptr(scale), int(chain0), int(seed) & _M64, int(step) & _M32, lo.size,
-                                                  _abi.ptr(lo), _abi.ptr(hi), _abi.ptr(lg),
-                                                  box_flags(sim_flags) | (_abi.MCMC_FOLD if fold else 0), _abi.ptr(Up), _abi.ptr(Xp),
-                                                  _abi.ptr(inside), int(device), _abi.C.byref(sec)))
-    if info is not None:
-        info.update(seconds=sec.value)
+    _timed("trpl_mcmc_propose" if group is None else "trpl_mcmc_propose_rungs", info,
+           _abi.ptr(U), None if partners is None else _abi.ptr(partners), count, P, *([] if group is None else [group]), A,
+           float(gamma), _abi.ptr(scale), int(chain0), int(seed) & _M64, int(step) & _M32, lo.size, _abi.ptr(lo), _abi.ptr(hi),
+           _abi.ptr(lg), box_flags(sim_flags) | (_abi.MCMC_FOLD if fold else 0), _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(inside), int(device))
     return Up, Xp, inside
 
 
-def accept_rungs(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device=0, info=None):
-    """accepted (count,) int32: accept() with a temperature per rung (trpl_mcmc_accept_rungs).  tf (K,): the count rows are K rungs of
-    count / K chains each.  U, X and LL are updated IN PLACE.  The rows of rung k are accept() on them with tf[k] and chain0 + k
-    count / K, bit for bit."""
-    for name, a in (("U", U), ("X", X), ("LL", LL)):
-        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable):
-            raise ValueError("%s is updated in place: it must be a writeable C-contiguous float64 array" % name)
-    tf = _ladder(tf)
+def _accept(rungs, U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device, info):
+    """trpl_mcmc_accept, or with rungs trpl_mcmc_accept_rungs, which takes (K, group, tf (K,)) where the other takes tf: the marshaller
+    of accept and accept_rungs."""
+    _in_place("updated", U, X, LL)
+    if rungs:
+        tf = _ladder(tf)
     Up, Xp, LLp = _f64(Up), _f64(Xp), _f64(LLp)
     inside = np.ascontiguousarray(inside, dtype=np.int32)
     if U.ndim != 2 or X.ndim != 2 or X.shape[0] != U.shape[0] or Up.shape != U.shape or Xp.shape != X.shape:
@@ -153,34 +99,73 @@ def accept_rungs(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device=0
     count = U.shape[0]
     if LL.shape != (count,) or LLp.shape != (count,) or inside.shape != (count,):
         raise ValueError("LL, LLp and inside must be (count,)")
-    if count % tf.size:
-        raise ValueError("count = %d is no multiple of the %d rungs" % (count, tf.size))
+    temper = _rung_args(tf, count) if rungs else [float(tf)]
     accepted = np.empty(count, dtype=np.int32)
-    sec = _abi.C.c_double(0.0)
-    _abi.check(_abi.lib().trpl_mcmc_accept_rungs(_abi.ptr(U), _abi.ptr(X), _abi.ptr(LL), _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(LLp),
-                                                 _abi.ptr(inside), count, U.shape[1], X.shape[1], tf.size, count // tf.size, _abi.ptr(tf),
-                                                 int(chain0), int(seed) & _M64, int(step) & _M32, _abi.ptr(accepted), int(device),
-                                                 _abi.C.byref(sec)))
-    if info is not None:
-        info.update(seconds=sec.value)
+    _timed("trpl_mcmc_accept_rungs" if rungs else "trpl_mcmc_accept", info,
+           _abi.ptr(U), _abi.ptr(X), _abi.ptr(LL), _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(LLp), _abi.ptr(inside), count, U.shape[1], X.shape[1],
+           *temper, int(chain0), int(seed) & _M64, int(step) & _M32, _abi.ptr(accepted), int(device))
     return accepted
+
+
+def _levels(rungs, LL, tf, chain0, seed, step, device, info):
+    """trpl_mcmc_levels, or with rungs trpl_mcmc_levels_rungs: the marshaller of reject_levels and reject_levels_rungs."""
+    LL = _f64(LL)
+    if rungs:
+        tf = _ladder(tf)
+    if LL.ndim != 1:
+        raise ValueError("LL must be (count,)")
+    temper = _rung_args(tf, LL.shape[0]) if rungs else [float(tf)]
+    level = np.empty(LL.shape[0])
+    _timed("trpl_mcmc_levels_rungs" if rungs else "trpl_mcmc_levels", info,
+           _abi.ptr(LL), LL.shape[0], *temper, int(chain0), int(seed) & _M64, int(step) & _M32, _abi.ptr(level), int(device))
+    return level
+
+
+def propose(U, partners, gamma, scale, chain0, seed, step, minX, maxX, do_log, sim_flags=None, device=0, info=None, fold=False):
+    """(Up, Xp, inside): one symmetric proposal per chain of U (count, A) (trpl_mcmc_propose).  partners (P >= 2, A): u' = (u + gamma
+    (pa - pb)) + scale (2 xi - 1) with two distinct rows a, b of partners; partners None: the random walk u' = u + scale (2 xi - 1).
+    scale (A,) or a scalar.  chain0 is the ensemble index of U's first row and step the half-sweep: they key the Philox stream.
+    inside (count,) int32 is 0 where u' left the unit cube; Xp is formed either way.  fold=True (TRPL_MCMC_FOLD): u' is reflected
+    back at the faces of the cube, and inside is 0 where a coordinate is not finite, 1 where nothing was folded, 2 where something
+    was."""
+    return _propose(U, partners, None, gamma, scale, chain0, seed, step, minX, maxX, do_log, sim_flags, device, info, fold)
+
+
+def accept(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device=0, info=None):
+    """accepted (count,) int32: the Metropolis step of every chain at temperature tf (trpl_mcmc_accept).  U (count, A), X (count,
+    ncol) and LL (count,) -- C-contiguous float64 arrays -- are updated IN PLACE: the rows of an accepted proposal are copied, the
+    others stay."""
+    return _accept(False, U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device, info)
+
+
+def reject_levels(LL, tf, chain0, seed, step, device=0, info=None):
+    """level (count,): for every chain the sse level above which accept(), called with the same (tf, chain0, seed, step), is certain
+    to reject the proposal (trpl_mcmc_levels) -- the cut_levels of driver.loglik, one per proposal.  The accept step's uniform
+    depends on (seed; chain, step) only, so the level is known before the proposal is solved.  +inf where nothing may be cut: a
+    chain whose LL is NaN or -inf accepts anything.  LL must be minus the summed sse, i.e. come from a likelihood whose P starts
+    from zero (include/trpl.h has the argument)."""
+    return _levels(False, LL, tf, chain0, seed, step, device, info)
+
+
+def propose_rungs(U, partners, group, gamma, scale, chain0, seed, step, minX, maxX, do_log, sim_flags=None, device=0, info=None,
+                  fold=False):
+    """(Up, Xp, inside): propose() for a block of rungs of `group` chains each (trpl_mcmc_propose_rungs): chain i of U (count, A) takes
+    its two partners from the rows [(i // group) group, + group) of partners (P, A); P is a multiple of group, count <= P.  The rows
+    of rung k are propose() on that slice of U with that block of partners and chain0 + k group, bit for bit."""
+    return _propose(U, partners, int(group), gamma, scale, chain0, seed, step, minX, maxX, do_log, sim_flags, device, info, fold)
+
+
+def accept_rungs(U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device=0, info=None):
+    """accepted (count,) int32: accept() with a temperature per rung (trpl_mcmc_accept_rungs).  tf (K,): the count rows are K rungs of
+    count / K chains each.  U, X and LL are updated IN PLACE.  The rows of rung k are accept() on them with tf[k] and chain0 + k
+    count / K, bit for bit."""
+    return _accept(True, U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device, info)
 
 
 def reject_levels_rungs(LL, tf, chain0, seed, step, device=0, info=None):
     """level (count,): reject_levels() with a temperature per rung (trpl_mcmc_levels_rungs), tf (K,): the levels above which
     accept_rungs(), called with the same (tf, chain0, seed, step), is certain to reject."""
-    LL, tf = _f64(LL), _ladder(tf)
-    if LL.ndim != 1:
-        raise ValueError("LL must be (count,)")
-    if LL.shape[0] % tf.size:
-        raise ValueError("count = %d is no multiple of the %d rungs" % (LL.shape[0], tf.size))
-    level = np.empty(LL.shape[0])
-    sec = _abi.C.c_double(0.0)
-    _abi.check(_abi.lib().trpl_mcmc_levels_rungs(_abi.ptr(LL), LL.shape[0], tf.size, LL.shape[0] // tf.size, _abi.ptr(tf), int(chain0),
-                                                 int(seed) & _M64, int(step) & _M32, _abi.ptr(level), int(device), _abi.C.byref(sec)))
-    if info is not None:
-        info.update(seconds=sec.value)
-    return level
+    return _levels(True, LL, tf, chain0, seed, step, device, info)
 
 
 def swap(U, X, LL, tf, parity, chain0, seed, step, device=0, info=None):
@@ -188,22 +173,14 @@ def swap(U, X, LL, tf, parity, chain0, seed, step, device=0, info=None):
     ncol) and LL (K group,) -- writeable C-contiguous float64 arrays -- are exchanged IN PLACE between the rows a = k group + c and
     b = a + group for k = parity, parity + 2, .. with k + 1 < K: with d = (LL[b] - LL[a]) (1 / tf[k] - 1 / tf[k + 1]), when neither
     LL is NaN and d >= 0 or log(xi) < d.  swapped is 1 on both rows of an exchanged pair, 0 on every other row."""
-    for name, a in (("U", U), ("X", X), ("LL", LL)):
-        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable):
-            raise ValueError("%s is exchanged in place: it must be a writeable C-contiguous float64 array" % name)
+    _in_place("exchanged", U, X, LL)
     tf = _ladder(tf)
     if U.ndim != 2 or X.ndim != 2 or X.shape[0] != U.shape[0] or LL.shape != (U.shape[0],):
         raise ValueError("U must be (K group, A), X (K group, ncol) and LL (K group,)")
-    count = U.shape[0]
-    if count % tf.size:
-        raise ValueError("the %d rows are no multiple of the %d rungs" % (count, tf.size))
-    swapped = np.empty(count, dtype=np.int32)
-    sec = _abi.C.c_double(0.0)
-    _abi.check(_abi.lib().trpl_mcmc_swap(_abi.ptr(U), _abi.ptr(X), _abi.ptr(LL), tf.size, count // tf.size, U.shape[1], X.shape[1],
-                                         _abi.ptr(tf), int(parity), int(chain0), int(seed) & _M64, int(step) & _M32, _abi.ptr(swapped),
-                                         int(device), _abi.C.byref(sec)))
-    if info is not None:
-        info.update(seconds=sec.value)
+    K, group, ladder = _rung_args(tf, U.shape[0], "the %d rows are no multiple of the %d rungs")
+    swapped = np.empty(U.shape[0], dtype=np.int32)
+    _timed("trpl_mcmc_swap", info, _abi.ptr(U), _abi.ptr(X), _abi.ptr(LL), K, group, U.shape[1], X.shape[1], ladder, int(parity), int(chain0),
+           int(seed) & _M64, int(step) & _M32, _abi.ptr(swapped), int(device))
     return swapped
 
 
@@ -231,11 +208,7 @@ def chain_stats(H, t0=0, t1=None, Q=None, device=0, info=None):
     Q = ldh if Q is None else int(Q)
     t1 = n if t1 is None else int(t1)
     mean, m2 = np.empty(max(Q, 0)), np.empty(max(Q, 0))
-    sec = _abi.C.c_double(0.0)
-    _abi.check(_abi.lib().trpl_mcmc_chain_stats(_abi.ptr(H), n, ldh, Q, int(t0), t1, _abi.ptr(mean), _abi.ptr(m2), int(device),
-                                                _abi.C.byref(sec)))
-    if info is not None:
-        info.update(seconds=sec.value)
+    _timed("trpl_mcmc_chain_stats", info, _abi.ptr(H), n, ldh, Q, int(t0), t1, _abi.ptr(mean), _abi.ptr(m2), int(device))
     return mean, m2
 
 
@@ -251,11 +224,7 @@ def autocov(H, max_lag, t0=0, t1=None, Q=None, device=0, info=None):
     t1 = n if t1 is None else int(t1)
     L = int(max_lag)
     mean, s = np.empty(max(Q, 0)), np.empty((max(L, 0), max(Q, 0)))
-    sec = _abi.C.c_double(0.0)
-    _abi.check(_abi.lib().trpl_mcmc_autocov(_abi.ptr(H), n, ldh, Q, int(t0), t1, L, _abi.ptr(mean), _abi.ptr(s), int(device),
-                                            _abi.C.byref(sec)))
-    if info is not None:
-        info.update(seconds=sec.value)
+    _timed("trpl_mcmc_autocov", info, _abi.ptr(H), n, ldh, Q, int(t0), t1, L, _abi.ptr(mean), _abi.ptr(s), int(device))
     return mean, s
 
 
@@ -267,10 +236,7 @@ def autocov_pool(s, M, A, device=0, info=None):
         raise ValueError("s must be (L, lds)")
     L, lds = s.shape
     pooled = np.empty((L, max(int(A), 0)))
-    sec = _abi.C.c_double(0.0)
-    _abi.check(_abi.lib().trpl_mcmc_autocov_pool(_abi.ptr(s), L, lds, int(M), int(A), _abi.ptr(pooled), int(device), _abi.C.byref(sec)))
-    if info is not None:
-        info.update(seconds=sec.value)
+    _timed("trpl_mcmc_autocov_pool", info, _abi.ptr(s), L, lds, int(M), int(A), _abi.ptr(pooled), int(device))
     return pooled
 
 
@@ -399,6 +365,92 @@ class Chains:
         return np.sqrt(info["var_plus"] / ess)
 
 
+def _proposal_args(C, kind, bounds, scale):
+    """What run and run_tempered refuse alike about the ensemble and its proposal; returns scale with kind="de"'s default."""
+    if C < 4 or C % 2:
+        raise ValueError("C=%d: the two halves of the ensemble need an even number of chains, at least 4" % C)
+    if kind not in ("de", "rw"):
+        raise ValueError("kind must be 'de' or 'rw'")
+    if bounds not in ("reject", "fold"):
+        raise ValueError("bounds must be 'reject' or 'fold'")
+    if scale is None:
+        if kind == "rw":
+            raise ValueError("kind='rw' needs scale, the half-width of the random walk")
+        scale = 1e-3
+    return scale
+
+
+def _active(lo, hi, sim_flags):
+    A = refine.active_columns(lo, hi, sim_flags).size
+    if not 1 <= A <= _abi.REFINE_MAX_DIMS:
+        raise ValueError("the box has %d active columns; a chain takes 1 .. %d" % (A, _abi.REFINE_MAX_DIMS))
+    return A
+
+
+def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jump_every, seed, kept, device, fold, early_reject, tf=None,
+            ladder=None, swap_every=1):
+    """The sweeps of run (tf: the C rows of U, X, LL as run holds them, the single-temperature front ends) and of run_tempered
+    (ladder (K,): the 2 K g rows half-major, the *_rungs front ends and the swap).  The state is advanced in place.  Returns the
+    history -- U, X, LL, accept, each (K, n, C, ..), K = 1 for run -- and the counters: accept (sweeps, K) the share of chains that
+    moved, outside, folded, levelled, solved (K,) proposals, tried, done (K - 1,) exchanges."""
+    lo, hi, lg = box
+    K = 1 if ladder is None else ladder.size
+    half, A = U.shape[0] // 2, U.shape[1]
+    g, C = half // K, 2 * half // K
+    levels_of, accept_of, temper = (reject_levels, accept, tf) if ladder is None else (reject_levels_rungs, accept_rungs, ladder)
+    if K == 1:                                                   # one rung: the rows are the rung
+        rung_major, per_rung = (lambda a: a[None]), np.count_nonzero
+    else:
+        def rung_major(a):                                       # (2 K g, ...) -> (K, C, ...)
+            return a.reshape((2, K, g) + a.shape[1:]).swapaxes(0, 1).reshape((K, C) + a.shape[1:])
+
+        def per_rung(flags):                                     # (K g,) flags of a block's rows -> how many are set in each rung
+            return flags.reshape(K, g).sum(axis=1)
+
+    gamma0 = 2.38 / np.sqrt(2.0 * A) if gamma is None else float(gamma)
+    hU, hX = np.empty((K, len(kept), C, A)), np.empty((K, len(kept), C, lo.size))
+    hLL, hAcc = np.empty((K, len(kept), C)), np.empty((K, len(kept), C), dtype=bool)
+    shares, tried, done = np.empty((sweeps, K)), np.zeros(K - 1, dtype=np.int64), np.zeros(K - 1, dtype=np.int64)
+    outside, folded, levelled, solved = (np.zeros(K, dtype=np.int64) for _ in range(4))
+    moved, row = np.empty(2 * half, dtype=bool), 0
+    for t in range(sweeps):
+        gm = 1.0 if jump_every > 0 and (t + 1) % jump_every == 0 else gamma0
+        for h, (a, b) in enumerate(((0, half), (half, 2 * half))):
+            step = 2 * t + h                                     # with chain0 = a, the key of the half-sweep's calls
+            if kind == "rw":
+                Up, Xp, inside = propose(U[a:b], None, gm, scale, a, seed, step, lo, hi, lg, sim_flags, device=device, fold=fold)
+            elif ladder is None:
+                Up, Xp, inside = propose(U[a:b], U[half:] if h == 0 else U[:half], gm, scale, a, seed, step, lo, hi, lg, sim_flags,
+                                         device=device, fold=fold)
+            else:
+                Up, Xp, inside = propose_rungs(U[a:b], U[half:] if h == 0 else U[:half], g, gm, scale, a, seed, step, lo, hi, lg,
+                                               sim_flags, device=device, fold=fold)
+            ok = inside != 0
+            LLp = np.full(half, -np.inf)
+            if ok.any() and early_reject:
+                levels = levels_of(LL[a:b], temper, a, seed, step, device=device)
+                LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok]), cut_levels=levels[ok]))
+                levelled += per_rung(ok & np.isfinite(levels))
+                solved += per_rung(ok)
+            elif ok.any():
+                LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok])))
+            outside += per_rung(~ok)
+            folded += per_rung(inside == 2)
+            moved[a:b] = accept_of(U[a:b], X[a:b], LL[a:b], Up, Xp, LLp, inside, temper, a, seed, step, device=device) != 0
+        shares[t] = rung_major(moved).mean(axis=1)
+        if K > 1 and (t + 1) % swap_every == 0:
+            parity = (t // swap_every) % 2
+            for a, b in ((0, half), (half, 2 * half)):
+                sw = swap(U[a:b], X[a:b], LL[a:b], ladder, parity, a, seed, t, device=device)
+                lower = np.arange(parity, K - 1, 2)
+                tried[lower] += g
+                done[lower] += sw.reshape(K, g)[lower].sum(axis=1)
+        if t >= kept.start and (t - kept.start) % kept.step == 0:
+            hU[:, row], hX[:, row], hLL[:, row], hAcc[:, row] = rung_major(U), rung_major(X), rung_major(LL), rung_major(moved)
+            row += 1
+    return (hU, hX, hLL, hAcc), dict(accept=shares, outside=outside, folded=folded, levelled=levelled, solved=solved, tried=tried, done=done)
+
+
 def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0, kind="de", gamma=None, scale=None, jump_every=0,
         seed=1, keep_every=1, burn=0, max_history_bytes=4 << 30, device=0, info=None, U0=None, bounds="reject", early_reject=False):
     """Advance the C chains that start at X0 (C, ncol), LL0 (C,) by `sweeps` sweeps; loglik(X) -> LL is any callable (the fused
@@ -431,22 +483,11 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
     if X.ndim != 2 or X.shape[1] != lo.size or LL.shape != (X.shape[0],):
         raise ValueError("X0 must be (C, ncol) and LL0 (C,)")
     C = X.shape[0]
-    if C < 4 or C % 2:
-        raise ValueError("C=%d: the two halves of the ensemble need an even number of chains, at least 4" % C)
-    if kind not in ("de", "rw"):
-        raise ValueError("kind must be 'de' or 'rw'")
-    if bounds not in ("reject", "fold"):
-        raise ValueError("bounds must be 'reject' or 'fold'")
-    if scale is None:
-        if kind == "rw":
-            raise ValueError("kind='rw' needs scale, the half-width of the random walk")
-        scale = 1e-3
-    sweeps, keep_every, burn, jump_every = int(sweeps), int(keep_every), int(burn), int(jump_every)
+    scale = _proposal_args(C, kind, bounds, scale)
+    sweeps, keep_every, burn = int(sweeps), int(keep_every), int(burn)
     if sweeps < 1 or keep_every < 1 or burn < 0:
         raise ValueError("sweeps and keep_every must be >= 1 and burn >= 0")
-    A = refine.active_columns(lo, hi, sim_flags).size
-    if not 1 <= A <= _abi.REFINE_MAX_DIMS:
-        raise ValueError("the box has %d active columns; a chain takes 1 .. %d" % (A, _abi.REFINE_MAX_DIMS))
+    A = _active(lo, hi, sim_flags)
     kept = range(burn, sweeps, keep_every)
     need = len(kept) * C * ((A + lo.size + 1) * 8 + 1)
     if need > int(max_history_bytes):
@@ -458,40 +499,14 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
         U = np.array(U0, dtype=np.float64, order="C")
         if U.shape != (C, A):
             raise ValueError("U0 must be (C, A) with the box's A = %d active columns" % A)
-    gamma0 = 2.38 / np.sqrt(2.0 * A) if gamma is None else float(gamma)
-    half = C // 2
-    hU, hX = np.empty((len(kept), C, A)), np.empty((len(kept), C, lo.size))
-    hLL, hAcc = np.empty((len(kept), C)), np.empty((len(kept), C), dtype=bool)
-    shares, outside, folded, row = [], 0, 0, 0
-    levelled, solved = 0, 0
-    moved = np.empty(C, dtype=bool)
-    for t in range(sweeps):
-        g = 1.0 if jump_every > 0 and (t + 1) % jump_every == 0 else gamma0
-        for k, (a, b) in enumerate(((0, half), (half, C))):
-            partners = None if kind == "rw" else (U[half:] if k == 0 else U[:half])
-            Up, Xp, inside = propose(U[a:b], partners, g, scale, a, seed, 2 * t + k, lo, hi, lg, sim_flags, device=device,
-                                         fold=bounds == "fold")
-            ok = inside != 0
-            LLp = np.full(b - a, -np.inf)
-            if ok.any() and early_reject:
-                levels = reject_levels(LL[a:b], tf, a, seed, 2 * t + k, device=device)[ok]
-                LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok]), cut_levels=levels))
-                levelled += int(np.isfinite(levels).sum())
-                solved += int(ok.sum())
-            elif ok.any():
-                LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok])))
-            outside += int((~ok).sum())
-            folded += int((inside == 2).sum())
-            moved[a:b] = accept(U[a:b], X[a:b], LL[a:b], Up, Xp, LLp, inside, tf, a, seed, 2 * t + k, device=device) != 0
-        shares.append(float(moved.mean()))
-        if t >= burn and (t - burn) % keep_every == 0:
-            hU[row], hX[row], hLL[row], hAcc[row] = U, X, LL, moved
-            row += 1
+    hist, n = _sweeps(loglik, U, X, LL, tf=tf, box=(lo, hi, lg), sim_flags=sim_flags, sweeps=sweeps, kind=kind, gamma=gamma, scale=scale,
+                      jump_every=int(jump_every), seed=seed, kept=kept, device=device, fold=bounds == "fold", early_reject=early_reject)
     if info is not None:
-        info.update(accept=shares, outside=outside / float(sweeps * C), folded=folded / float(sweeps * C))
+        info.update(accept=n["accept"][:, 0].tolist(), outside=int(n["outside"][0]) / float(sweeps * C),
+                    folded=int(n["folded"][0]) / float(sweeps * C))
         if early_reject:
-            info.update(early_reject=levelled / float(max(solved, 1)))
-    return Chains(hU, hX, hLL, hAcc, device=device)
+            info.update(early_reject=int(n["levelled"][0]) / float(max(int(n["solved"][0]), 1)))
+    return Chains(*(h[0] for h in hist), device=device)
 
 
 class Tempered:
@@ -543,35 +558,19 @@ def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sw
     if X.ndim != 3 or X.shape[0] != K or X.shape[2] != lo.size or LL.shape != X.shape[:2]:
         raise ValueError("X0 must be (C, ncol) and LL0 (C,), or (K, C, ncol) and (K, C) with the ladder's K = %d" % K)
     C = X.shape[1]
-    if C < 4 or C % 2:
-        raise ValueError("C=%d: the two halves of the ensemble need an even number of chains, at least 4" % C)
-    if kind not in ("de", "rw"):
-        raise ValueError("kind must be 'de' or 'rw'")
-    if bounds not in ("reject", "fold"):
-        raise ValueError("bounds must be 'reject' or 'fold'")
-    if scale is None:
-        if kind == "rw":
-            raise ValueError("kind='rw' needs scale, the half-width of the random walk")
-        scale = 1e-3
-    sweeps, keep_every, burn, jump_every, swap_every = int(sweeps), int(keep_every), int(burn), int(jump_every), int(swap_every)
+    scale = _proposal_args(C, kind, bounds, scale)
+    sweeps, keep_every, burn, swap_every = int(sweeps), int(keep_every), int(burn), int(swap_every)
     if sweeps < 1 or keep_every < 1 or burn < 0 or swap_every < 1:
         raise ValueError("sweeps, keep_every and swap_every must be >= 1 and burn >= 0")
-    A = refine.active_columns(lo, hi, sim_flags).size
-    if not 1 <= A <= _abi.REFINE_MAX_DIMS:
-        raise ValueError("the box has %d active columns; a chain takes 1 .. %d" % (A, _abi.REFINE_MAX_DIMS))
+    A = _active(lo, hi, sim_flags)
     kept = range(burn, sweeps, keep_every)
     need = len(kept) * K * C * ((A + lo.size + 1) * 8 + 1)
     if need > int(max_history_bytes):
         raise ValueError("the history of %d sweeps x %d rungs x %d chains needs %d bytes, more than max_history_bytes = %d"
                          % (len(kept), K, C, need, int(max_history_bytes)))
-    g = C // 2
-    half = K * g
 
     def half_major(a):                                           # (K, C, ...) -> (2 K g, ...), a writeable copy
-        return np.array(a.reshape((K, 2, g) + a.shape[2:]).swapaxes(0, 1).reshape((2 * half,) + a.shape[2:]), order="C")
-
-    def rung_major(a):                                           # (2 K g, ...) -> (K, C, ...)
-        return a.reshape((2, K, g) + a.shape[1:]).swapaxes(0, 1).reshape((K, C) + a.shape[1:])
+        return np.array(a.reshape((K, 2, C // 2) + a.shape[2:]).swapaxes(0, 1).reshape((K * C,) + a.shape[2:]), order="C")
 
     X, LL = half_major(X), half_major(LL)
     if U0 is None:
@@ -583,51 +582,13 @@ def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sw
         if U.shape != (K, C, A):
             raise ValueError("U0 must be (C, A) or (K, C, A) with the box's A = %d active columns" % A)
         U = half_major(U)
-    gamma0 = 2.38 / np.sqrt(2.0 * A) if gamma is None else float(gamma)
-    hU, hX = np.empty((K, len(kept), C, A)), np.empty((K, len(kept), C, lo.size))
-    hLL, hAcc = np.empty((K, len(kept), C)), np.empty((K, len(kept), C), dtype=bool)
-    rung_of = np.repeat(np.arange(K), g)                         # the rung of every row of a block
-    shares, row = np.empty((sweeps, K)), 0
-    outside, folded = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
-    levelled, solved = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
-    tried, done = np.zeros(max(K - 1, 0), dtype=np.int64), np.zeros(max(K - 1, 0), dtype=np.int64)
-    moved = np.empty(2 * half, dtype=bool)
-    for t in range(sweeps):
-        gm = 1.0 if jump_every > 0 and (t + 1) % jump_every == 0 else gamma0
-        for h, (a, b) in enumerate(((0, half), (half, 2 * half))):
-            if kind == "rw":
-                Up, Xp, inside = propose(U[a:b], None, gm, scale, a, seed, 2 * t + h, lo, hi, lg, sim_flags, device=device,
-                                         fold=bounds == "fold")
-            else:
-                Up, Xp, inside = propose_rungs(U[a:b], U[half:] if h == 0 else U[:half], g, gm, scale, a, seed, 2 * t + h, lo, hi, lg,
-                                               sim_flags, device=device, fold=bounds == "fold")
-            ok = inside != 0
-            LLp = np.full(half, -np.inf)
-            if ok.any() and early_reject:
-                levels = reject_levels_rungs(LL[a:b], ladder, a, seed, 2 * t + h, device=device)[ok]
-                LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok]), cut_levels=levels))
-                levelled += np.bincount(rung_of[ok][np.isfinite(levels)], minlength=K)
-                solved += np.bincount(rung_of[ok], minlength=K)
-            elif ok.any():
-                LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok])))
-            outside += np.bincount(rung_of[~ok], minlength=K)
-            folded += np.bincount(rung_of[inside == 2], minlength=K)
-            moved[a:b] = accept_rungs(U[a:b], X[a:b], LL[a:b], Up, Xp, LLp, inside, ladder, a, seed, 2 * t + h, device=device) != 0
-        shares[t] = rung_major(moved).mean(axis=1)
-        if K > 1 and (t + 1) % swap_every == 0:
-            parity = (t // swap_every) % 2
-            for a, b in ((0, half), (half, 2 * half)):
-                sw = swap(U[a:b], X[a:b], LL[a:b], ladder, parity, a, seed, t, device=device)
-                lower = np.arange(parity, K - 1, 2)
-                tried[lower] += g
-                done[lower] += sw.reshape(K, g)[lower].sum(axis=1)
-        if t >= burn and (t - burn) % keep_every == 0:
-            hU[:, row], hX[:, row], hLL[:, row], hAcc[:, row] = rung_major(U), rung_major(X), rung_major(LL), rung_major(moved)
-            row += 1
+    hist, n = _sweeps(loglik, U, X, LL, ladder=ladder, swap_every=swap_every, box=(lo, hi, lg), sim_flags=sim_flags, sweeps=sweeps, kind=kind,
+                      gamma=gamma, scale=scale, jump_every=int(jump_every), seed=seed, kept=kept, device=device, fold=bounds == "fold",
+                      early_reject=early_reject)
     with np.errstate(invalid="ignore"):
-        swap_rate = done / tried.astype(np.float64)
+        swap_rate = n["done"] / n["tried"].astype(np.float64)
     if info is not None:
-        info.update(accept=shares, outside=outside / float(sweeps * C), folded=folded / float(sweeps * C), swap_rate=swap_rate)
+        info.update(accept=n["accept"], outside=n["outside"] / float(sweeps * C), folded=n["folded"] / float(sweeps * C), swap_rate=swap_rate)
         if early_reject:
-            info.update(early_reject=levelled / np.maximum(solved, 1).astype(np.float64))
-    return Tempered(ladder, [Chains(hU[k], hX[k], hLL[k], hAcc[k], device=device) for k in range(K)], swap_rate)
+            info.update(early_reject=n["levelled"] / np.maximum(n["solved"], 1).astype(np.float64))
+    return Tempered(ladder, [Chains(*(h[k] for h in hist), device=device) for k in range(K)], swap_rate)

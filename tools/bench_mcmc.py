@@ -1,7 +1,8 @@
 """The three kernels of the ensemble Metropolis sampler on resident tensors, in one process on one device.
 
     python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--fold] [--tempered [--rungs 16]] [--autocov]
-                               [--out profiles/mcmc_bench.jsonl]
+                               [--out profiles/mcmc_bench.jsonl] [--label parent]
+    python tools/bench_mcmc.py --host-loop [--out ...] [--label ...]
 
 propose:     mcmc_propose_device of `chains` chains in the reference's box (A = 10 active columns), with `chains` partners
              (differential evolution: two gathered partner rows per chain), and the random walk for comparison.
@@ -18,6 +19,11 @@ chain_stats: mcmc_chain_stats_device over a history of n steps of chains * A col
              mcmc_autocov_pool_device over its s.  The line records beside each time the two floors it is to be read against
              (DESIGN.md section 28): H read once per lag tile and s written once at 6.1 TB/s, and two fp64 instructions per term
              at 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz.
+--host-loop: nothing of the above.  Wall-clock seconds per sweep of mcmc.run and of mcmc.run_tempered (4 rungs on geometric_ladder(1, 64, 4))
+             through the host-buffer calls, with a numpy toy likelihood: 256 chains, a unit box of A = 3 columns, 200 sweeps -- what
+             the sampler's own Python and staging cost per sweep, the likelihood being next to nothing.  One warm-up of 10 sweeps,
+             then the median of 3 interleaved passes.
+--label:     a word that goes into the line as "label", to tell two builds' lines apart.
 Device events around `reps` back-to-back calls after a warm-up, median of 3 interleaved passes (tools/bench_quantiles.measure).
 Appends one JSON line to --out."""
 import argparse
@@ -34,8 +40,47 @@ from trpl_amd import device as tdev, refine, sampler as sm   # noqa: E402
 from bench_quantiles import measure   # noqa: E402
 
 
+def host_loop():
+    import time
+    import numpy as np
+    from trpl_amd import mcmc
+    C, A, sweeps, K = 256, 3, 200, 4
+    lo, hi, lg = np.zeros(A), np.ones(A), np.zeros(A, dtype=np.int32)
+
+    def loglik(X, cut_levels=None):
+        return -np.sum((X - 0.5) ** 2, axis=1) / 0.02
+
+    U0 = np.random.default_rng(1).uniform(0.3, 0.7, (C, A))
+    X0, ladder = U0.copy(), mcmc.geometric_ladder(1.0, 64.0, K)
+    LL0 = loglik(X0)
+    runs = {"run": lambda n: mcmc.run(loglik, X0, LL0, lo, hi, lg, sweeps=n, seed=1, U0=U0),
+            "run_tempered": lambda n: mcmc.run_tempered(loglik, X0, LL0, lo, hi, lg, ladder, sweeps=n, seed=1, U0=U0)}
+    passes = {name: [] for name in runs}
+    for name, f in runs.items():
+        f(10)
+    for _ in range(3):
+        for name, f in runs.items():
+            t0 = time.perf_counter()
+            f(sweeps)
+            passes[name].append((time.perf_counter() - t0) / sweeps)
+    return {"bench": "mcmc_host_loop", "chains": C, "A": A, "sweeps": sweeps, "rungs": K,
+            "s_per_sweep": {name: sorted(p)[1] for name, p in passes.items()}, "s_per_sweep_passes": passes}
+
+
+def write(a, line):
+    if a.label:
+        line["label"] = a.label
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as f:
+        f.write(json.dumps(line) + "\n")
+    print(json.dumps(line))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--host-loop", action="store_true")
+    ap.add_argument("--label", default=None)
     ap.add_argument("--chains", type=int, default=1 << 16)
     ap.add_argument("--A", type=int, default=10)
     ap.add_argument("--n", type=int, default=256)
@@ -46,6 +91,8 @@ def main():
     ap.add_argument("--autocov", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcmc_bench.jsonl"))
     a = ap.parse_args()
+    if a.host_loop:
+        return write(a, host_loop())
     dev = torch.device("cuda", 0)
     lo, hi, lg = sm.DEFAULT_MINX * sm.UNIT_CONVERSIONS, sm.DEFAULT_MAXX * sm.UNIT_CONVERSIONS, sm.DEFAULT_DO_LOG
     A = len(refine.active_columns(lo, hi))
@@ -127,11 +174,7 @@ def main():
         line.update(rungs=a.rungs, swapped_share=float(swapped.double().mean().item()))
     if a.autocov:
         line.update(autocov_tile=tile, autocov_floors=floors)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "a") as f:
-        f.write(json.dumps(line) + "\n")
-    print(json.dumps(line))
-    return 0
+    return write(a, line)
 
 
 if __name__ == "__main__":
