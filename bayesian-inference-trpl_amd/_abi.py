@@ -242,6 +242,16 @@ SIGNATURES = {
     "trpl_mcmc_autocov_pool_dev": [_vp, _i64, _i64, _i64, _i32, _vp, _vp],
     "trpl_mcmc_autocov_pool": [_vp, _i64, _i64, _i64, _i32, _vp, _i32, _pd],
     "trpl_mcmc_autocov_chains": [_vp, _i64, _i64, _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _pd],
+    "trpl_mcmc_propose_stretch_dev": [_vp, _vp, _i64, _i64, _i64, _i32, _f64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp,
+                                      _vp, _vp],
+    "trpl_mcmc_propose_stretch": [_vp, _vp, _i64, _i64, _i64, _i32, _f64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp,
+                                  _i32, _pd],
+    "trpl_mcmc_accept_h_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _vp],
+    "trpl_mcmc_accept_h": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _i32, _pd],
+    "trpl_mcmc_levels_h_dev": [_vp, _vp, _i64, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _vp],
+    "trpl_mcmc_levels_h": [_vp, _vp, _i64, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _i32, _pd],
+    "trpl_mcmc_prior_term_dev": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "trpl_mcmc_prior_term": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _pd],
     "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
     "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
 }

@@ -40,6 +40,7 @@
 // through a Staged).  on_stream is every _dev form: check, launch.  staged is every host-buffer form: check before a device is
 // opened, stage, launch -- the record is checked once.  An extern "C" entry point fills a record and returns one of the two.  A new
 // argument goes into the record, its refusal into check, its buffer into stage; a new operation is a record with these three.
+// on_stream and staged, the shared checks and the Philox call indices are mcmc_common.hpp's, shared with mcmc_hastings.hip.
 // chain_stats and the autocovariance calls are a kernel or two each and stay written out; their refusals share check_history.
 // Compiled with -ffp-contract=off like refine.hip: every result is its expression with one rounding per operation.
 #include <hip/hip_runtime.h>
@@ -50,6 +51,7 @@
 #include <type_traits>
 
 #include "api_util.hpp"
+#include "mcmc_common.hpp"
 #include "refine_common.hpp"
 
 namespace trpl {
@@ -57,15 +59,8 @@ namespace mcmc {                                                 // the kernels 
 
 using namespace refine;
 
-constexpr uint32_t kStream = 0x100;                              // third counter word: 0x100 + j, apart from the draws' j < 8
-constexpr uint32_t kPartnerCall = 8, kAcceptCall = 9, kSwapCall = 10;
-
 struct Scale {
     double s[16];
-};
-
-struct Ladder {                                                  // the temperatures of the rungs, by value like Scale
-    double tf[TRPL_MCMC_MAX_RUNGS];
 };
 
 // fold (include/trpl.h, TRPL_MCMC_FOLD): v reflected at the faces of [0, 1] as often as needed.  Called only for a v that failed the
@@ -412,42 +407,6 @@ using namespace trpl;
 
 namespace {                                                      // the host half: the file comment has its structure
 
-// "<name> is NULL" for the first pointer of the list that is
-int check_not_null(std::initializer_list<std::pair<const char *, const void *>> ptrs)
-{
-    for (const auto &q : ptrs)
-        if (!q.second) return api_fail(TRPL_ERR_ARG, "%s is NULL", q.first);
-    return TRPL_OK;
-}
-
-int check_count(int64_t count)
-{
-    if (count < 1) return api_fail(TRPL_ERR_ARG, "count=%lld must be >= 1", (long long)count);
-    return refine_check_blocks("count", count, "chains");
-}
-
-int check_chains(int64_t count, int32_t A, int64_t chain0)
-{
-    if (int rc = check_count(count)) return rc;
-    if (A < 1 || A > TRPL_REFINE_MAX_DIMS) return api_fail(TRPL_ERR_ARG, "A=%d must be in [1, %d]", A, TRPL_REFINE_MAX_DIMS);
-    if (chain0 < 0) return api_fail(TRPL_ERR_ARG, "chain0=%lld must be >= 0", (long long)chain0);
-    return TRPL_OK;
-}
-
-// the ladder of the *_rungs calls and of the swap: K, group and the K temperatures, copied into the kernel argument
-int check_ladder(int32_t K, int64_t group, const double *tf, mcmc::Ladder &lad)
-{
-    if (K < 1 || K > TRPL_MCMC_MAX_RUNGS) return api_fail(TRPL_ERR_ARG, "K=%d must be in [1, %d]", K, TRPL_MCMC_MAX_RUNGS);
-    if (group < 1) return api_fail(TRPL_ERR_ARG, "group=%lld must be >= 1", (long long)group);
-    if (int rc = refine_check_blocks("group", group, "chains")) return rc;
-    if (!tf) return api_fail(TRPL_ERR_ARG, "tf is NULL");
-    for (int k = 0; k < K; k++) {
-        if (!(isfinite(tf[k]) && tf[k] > 0.0)) return api_fail(TRPL_ERR_ARG, "tf[%d]=%g must be finite and > 0", k, tf[k]);
-        lad.tf[k] = tf[k];
-    }
-    return TRPL_OK;
-}
-
 // ---- the records: an entry point's arguments in its order, then what check() makes of them for the kernel.  rungs marks a *_rungs
 // call: group, K and ladder are read only then, and tf only without.
 struct ProposeCall {
@@ -535,22 +494,8 @@ int check(SwapCall &k)
     return check_not_null({{"U", k.U}, {"X", k.X}, {"LL", k.LL}, {"swapped", k.swapped}});
 }
 
-// ---- launch: the kernel of a checked record on a stream.  TRPL_MCMC_LAUNCH is the switch (A) over kernel<1> .. kernel<16>: its
-// kernel argument names the instantiation by `n`.  A kernel<A> is emitted where its launch stands; the functions keep the order the
+// ---- launch: the kernel of a checked record on a stream, through TRPL_MCMC_LAUNCH (mcmc_common.hpp).  The functions keep the order the
 // code object has had, the single-temperature kernels before the rung kernels.
-#define TRPL_MCMC_CASE(v, ...)                                                                                                         \
-    case v: {                                                                                                                          \
-        constexpr int n = v;                                                                                                           \
-        hipLaunchKernelGGL(__VA_ARGS__);                                                                                               \
-    } break;
-#define TRPL_MCMC_CASES(...)                                                                                                           \
-    TRPL_MCMC_CASE(1, __VA_ARGS__) TRPL_MCMC_CASE(2, __VA_ARGS__) TRPL_MCMC_CASE(3, __VA_ARGS__) TRPL_MCMC_CASE(4, __VA_ARGS__)        \
-    TRPL_MCMC_CASE(5, __VA_ARGS__) TRPL_MCMC_CASE(6, __VA_ARGS__) TRPL_MCMC_CASE(7, __VA_ARGS__) TRPL_MCMC_CASE(8, __VA_ARGS__)        \
-    TRPL_MCMC_CASE(9, __VA_ARGS__) TRPL_MCMC_CASE(10, __VA_ARGS__) TRPL_MCMC_CASE(11, __VA_ARGS__) TRPL_MCMC_CASE(12, __VA_ARGS__)     \
-    TRPL_MCMC_CASE(13, __VA_ARGS__) TRPL_MCMC_CASE(14, __VA_ARGS__) TRPL_MCMC_CASE(15, __VA_ARGS__) TRPL_MCMC_CASE(16, __VA_ARGS__)
-#define TRPL_MCMC_LAUNCH(A, kernel, count, ...)                                                                                        \
-    switch (A) { TRPL_MCMC_CASES(kernel, dim3(refine_blocks(count)), dim3(refine::kThreads), 0, __VA_ARGS__) }
-
 int launch_propose(const ProposeCall &k, hipStream_t stream)
 {
     const bool fold = (k.flags & TRPL_MCMC_FOLD) != 0;
@@ -628,27 +573,7 @@ void stage(SwapCall &k, Staged &sg)
     k.U = sg.inout(k.U, n * k.A); k.X = sg.inout(k.X, n * k.ncol); k.LL = sg.inout(k.LL, n); k.swapped = sg.out(k.swapped, n);
 }
 
-// ---- the two forms of an entry point.  on_stream is a _dev form: every check, then the launch on the caller's stream.  staged is
-// a host-buffer form: every check before a device is opened, then the launch of the same record on its staged buffers.
-template <class Call>
-int on_stream(Call k, void *stream)
-{
-    if (int rc = check(k)) return rc;
-    return launch(k, (hipStream_t)stream);
-}
-
-template <class Call>
-int staged(Call k, int32_t device, double *seconds)
-{
-    if (seconds) *seconds = 0.0;
-    if (int rc = check(k)) return rc;
-    Staged sg;
-    if (int rc = sg.open(device)) return rc;
-    stage(k, sg);
-    if (int rc = sg.begin()) return rc;
-    if (int rc = launch(k, sg.stream())) return rc;
-    return sg.finish(seconds);
-}
+// the two forms of an entry point, on_stream and staged, are mcmc_common.hpp's
 
 // ---- the histories of chain_stats and the autocovariance sums
 int check_history(int64_t n, int64_t ldh, int64_t Q, int64_t t0, int64_t t1)

@@ -760,6 +760,76 @@ def mcmc_swap_device(U, X, LL, tf, parity, chain0, seed, step, swapped):
         _chk(swapped, torch.int32, "swapped"), _stream()))
 
 
+def mcmc_propose_stretch_device(U, partners, group, a, chain0, seed, step, minX, maxX, do_log, Up, Xp, inside, z, lnq, flags=0):
+    """trpl_mcmc_propose_stretch_dev: Up (count, A), Xp (count, ncol), z (count,), lnq (count,) f64 and inside (count,) int32 <- one
+    stretch proposal per chain of U (count, A) f64 (Goodman & Weare 2010): u' = p + z (u - p), p a row of the chain's rung [(i //
+    group) group, + group) of partners (P, A), z = ((a - 1) xi + 1)^2 / a, lnq = (A - 1) log(z) the h of mcmc_accept_h_device.  group
+    None: one rung of P.  flags: the TRPL_BOX_EQUAL_* bits; _abi.MCMC_FOLD is refused."""
+    import torch
+    lo, hi, lg = _refine_box(minX, maxX, do_log)
+    if U.dim() != 2:
+        raise ValueError("U must be (count, A)")
+    count, A = U.shape
+    if partners is None or partners.dim() != 2 or partners.shape[1] != A:
+        raise ValueError("partners must be (P, A)")
+    if tuple(Up.shape) != (count, A) or tuple(Xp.shape) != (count, lo.size) or not (
+            tuple(inside.shape) == tuple(z.shape) == tuple(lnq.shape) == (count,)):
+        raise ValueError("Up must be (count, A), Xp (count, ncol) and inside, z and lnq (count,)")
+    _abi.check(_abi.lib().trpl_mcmc_propose_stretch_dev(
+        _chk(U, torch.float64, "U"), _chk(partners, torch.float64, "partners"), count, partners.shape[0],
+        partners.shape[0] if group is None else int(group), A, float(a), int(chain0), int(seed) & _M64, int(step) & _M32, lo.size,
+        _abi.ptr(lo), _abi.ptr(hi), _abi.ptr(lg), int(flags), _chk(Up, torch.float64, "Up"), _chk(Xp, torch.float64, "Xp"),
+        _chk(inside, torch.int32, "inside"), _chk(z, torch.float64, "z"), _chk(lnq, torch.float64, "lnq"), _stream()))
+
+
+def mcmc_accept_h_device(U, X, LL, Up, Xp, LLp, inside, h, tf, chain0, seed, step, accepted):
+    """trpl_mcmc_accept_h_dev: mcmc_accept_rungs_device with an untempered log term h (count,) f64 per chain: d = (LLp - LL) / tf + h.
+    tf (K,) is a host array, or a scalar for one temperature."""
+    import torch
+    tf = _ladder(np.atleast_1d(np.asarray(tf, dtype=np.float64)))
+    if U.dim() != 2 or X.dim() != 2 or X.shape[0] != U.shape[0] or Up.shape != U.shape or Xp.shape != X.shape:
+        raise ValueError("U and Up must be (count, A), X and Xp (count, ncol)")
+    count = U.shape[0]
+    if not (tuple(LL.shape) == tuple(LLp.shape) == tuple(inside.shape) == tuple(h.shape) == tuple(accepted.shape) == (count,)):
+        raise ValueError("LL, LLp, inside, h and accepted must be (count,)")
+    if count % tf.size:
+        raise ValueError("count = %d is no multiple of the %d rungs" % (count, tf.size))
+    _abi.check(_abi.lib().trpl_mcmc_accept_h_dev(
+        _chk(U, torch.float64, "U"), _chk(X, torch.float64, "X"), _chk(LL, torch.float64, "LL"), _chk(Up, torch.float64, "Up"),
+        _chk(Xp, torch.float64, "Xp"), _chk(LLp, torch.float64, "LLp"), _chk(inside, torch.int32, "inside"), _chk(h, torch.float64, "h"),
+        count, U.shape[1], X.shape[1], tf.size, count // tf.size, _abi.ptr(tf), int(chain0), int(seed) & _M64, int(step) & _M32,
+        _chk(accepted, torch.int32, "accepted"), _stream()))
+
+
+def mcmc_levels_h_device(LL, h, tf, chain0, seed, step, level):
+    """trpl_mcmc_levels_h_dev: level (count,) f64 <- the levels that mcmc_accept_h_device, called with the same (h, tf, chain0, seed,
+    step), is certain to reject above; +inf also where h is NaN or infinite.  A level can be negative: pass max(level, 0) on."""
+    import torch
+    tf = _ladder(np.atleast_1d(np.asarray(tf, dtype=np.float64)))
+    if LL.dim() != 1 or tuple(level.shape) != tuple(LL.shape) or tuple(h.shape) != tuple(LL.shape):
+        raise ValueError("LL, h and level must be (count,)")
+    if LL.shape[0] % tf.size:
+        raise ValueError("count = %d is no multiple of the %d rungs" % (LL.shape[0], tf.size))
+    _abi.check(_abi.lib().trpl_mcmc_levels_h_dev(
+        _chk(LL, torch.float64, "LL"), _chk(h, torch.float64, "h"), LL.shape[0], tf.size, LL.shape[0] // tf.size, _abi.ptr(tf),
+        int(chain0), int(seed) & _M64, int(step) & _M32, _chk(level, torch.float64, "level"), _stream()))
+
+
+def mcmc_prior_term_device(U, Up, mean, sd, h_out, h_in=None):
+    """trpl_mcmc_prior_term_dev: h_out (count,) f64 <- h_in + (lnp(Up) - lnp(U)) for the independent Gaussian prior (mean, sd), host
+    arrays (A,), in the unit coordinates U and Up (count, A) f64; h_in None is zero, and may be h_out."""
+    import torch
+    if U.dim() != 2 or Up.shape != U.shape or tuple(h_out.shape) != (U.shape[0],) or (h_in is not None and h_in.shape != h_out.shape):
+        raise ValueError("U and Up must be (count, A), h_out and h_in (count,)")
+    count, A = U.shape
+    mean, sd = np.ascontiguousarray(mean, dtype=np.float64), np.ascontiguousarray(sd, dtype=np.float64)
+    if mean.shape != (A,) or sd.shape != (A,):
+        raise ValueError("mean and sd must be (A,)")
+    _abi.check(_abi.lib().trpl_mcmc_prior_term_dev(
+        _chk(U, torch.float64, "U"), _chk(Up, torch.float64, "Up"), count, A, _abi.ptr(mean), _abi.ptr(sd),
+        _opt(h_in, torch.float64, "h_in"), _chk(h_out, torch.float64, "h_out"), _stream()))
+
+
 def mcmc_chain_stats_device(H, t0, t1, mean, m2, Q=None):
     """trpl_mcmc_chain_stats_dev: mean, m2 (Q,) f64 <- per column q < Q of the history H (n, ldh >= Q) f64, which stays where it is,
     the mean and the centred sum of squares over the steps [t0, t1), both sums in ascending t: the plain loop's bits.  Q defaults

@@ -7,6 +7,9 @@ scaled by gamma, plus a small uniform jitter -- it needs no tuning and follows a
 ensemble is cut into two halves that are updated in turn, each with partners from the OTHER half (ter Braak & Vrugt 2008;
 Foreman-Mackey et al. 2013): within a half-sweep the partners are fixed, so every chain's move is a symmetric Metropolis kernel
 that leaves the posterior invariant, and all chains of the half can move at once.  kind="rw" is the plain random walk.
+kind="stretch" is the affine-invariant stretch move (Goodman & Weare 2010), an asymmetric proposal, and prior= an informative
+Gaussian prior: both enter the accept step and the early-rejection level as an untempered log term per chain (accept_h,
+reject_levels_h).
 
 Chains live in the unit coordinates of `refine` (the active columns of the box, uniform prior on the cube).  With bounds="reject",
 the default, a proposal that leaves the cube is never solved and never accepted; with bounds="fold" it is reflected back at the
@@ -86,9 +89,10 @@ def _propose(U, partners, group, gamma, scale, chain0, seed, step, minX, maxX, d
     return Up, Xp, inside
 
 
-def _accept(rungs, U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device, info):
-    """trpl_mcmc_accept, or with rungs trpl_mcmc_accept_rungs, which takes (K, group, tf (K,)) where the other takes tf: the marshaller
-    of accept and accept_rungs."""
+def _accept(rungs, U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device, info, h=None):
+    """trpl_mcmc_accept, or with rungs trpl_mcmc_accept_rungs, which takes (K, group, tf (K,)) where the other takes tf, or with h
+    trpl_mcmc_accept_h, which takes h behind inside and the ladder like accept_rungs: the marshaller of accept, accept_rungs and
+    accept_h."""
     _in_place("updated", U, X, LL)
     if rungs:
         tf = _ladder(tf)
@@ -99,25 +103,38 @@ def _accept(rungs, U, X, LL, Up, Xp, LLp, inside, tf, chain0, seed, step, device
     count = U.shape[0]
     if LL.shape != (count,) or LLp.shape != (count,) or inside.shape != (count,):
         raise ValueError("LL, LLp and inside must be (count,)")
+    term = []
+    if h is not None:
+        h = _f64(h)
+        if h.shape != (count,):
+            raise ValueError("h must be (count,)")
+        term = [_abi.ptr(h)]
     temper = _rung_args(tf, count) if rungs else [float(tf)]
     accepted = np.empty(count, dtype=np.int32)
-    _timed("trpl_mcmc_accept_rungs" if rungs else "trpl_mcmc_accept", info,
-           _abi.ptr(U), _abi.ptr(X), _abi.ptr(LL), _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(LLp), _abi.ptr(inside), count, U.shape[1], X.shape[1],
-           *temper, int(chain0), int(seed) & _M64, int(step) & _M32, _abi.ptr(accepted), int(device))
+    _timed("trpl_mcmc_accept_h" if h is not None else "trpl_mcmc_accept_rungs" if rungs else "trpl_mcmc_accept", info,
+           _abi.ptr(U), _abi.ptr(X), _abi.ptr(LL), _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(LLp), _abi.ptr(inside), *term, count, U.shape[1],
+           X.shape[1], *temper, int(chain0), int(seed) & _M64, int(step) & _M32, _abi.ptr(accepted), int(device))
     return accepted
 
 
-def _levels(rungs, LL, tf, chain0, seed, step, device, info):
-    """trpl_mcmc_levels, or with rungs trpl_mcmc_levels_rungs: the marshaller of reject_levels and reject_levels_rungs."""
+def _levels(rungs, LL, tf, chain0, seed, step, device, info, h=None):
+    """trpl_mcmc_levels, or with rungs trpl_mcmc_levels_rungs, or with h trpl_mcmc_levels_h (h behind LL, the ladder like levels_rungs):
+    the marshaller of reject_levels, reject_levels_rungs and reject_levels_h."""
     LL = _f64(LL)
     if rungs:
         tf = _ladder(tf)
     if LL.ndim != 1:
         raise ValueError("LL must be (count,)")
+    term = []
+    if h is not None:
+        h = _f64(h)
+        if h.shape != LL.shape:
+            raise ValueError("h must be (count,)")
+        term = [_abi.ptr(h)]
     temper = _rung_args(tf, LL.shape[0]) if rungs else [float(tf)]
     level = np.empty(LL.shape[0])
-    _timed("trpl_mcmc_levels_rungs" if rungs else "trpl_mcmc_levels", info,
-           _abi.ptr(LL), LL.shape[0], *temper, int(chain0), int(seed) & _M64, int(step) & _M32, _abi.ptr(level), int(device))
+    _timed("trpl_mcmc_levels_h" if h is not None else "trpl_mcmc_levels_rungs" if rungs else "trpl_mcmc_levels", info,
+           _abi.ptr(LL), *term, LL.shape[0], *temper, int(chain0), int(seed) & _M64, int(step) & _M32, _abi.ptr(level), int(device))
     return level
 
 
@@ -182,6 +199,88 @@ def swap(U, X, LL, tf, parity, chain0, seed, step, device=0, info=None):
     _timed("trpl_mcmc_swap", info, _abi.ptr(U), _abi.ptr(X), _abi.ptr(LL), K, group, U.shape[1], X.shape[1], ladder, int(parity), int(chain0),
            int(seed) & _M64, int(step) & _M32, _abi.ptr(swapped), int(device))
     return swapped
+
+
+def propose_stretch(U, partners, group, a, chain0, seed, step, minX, maxX, do_log, sim_flags=None, device=0, info=None):
+    """(Up, Xp, inside, z, lnq): one stretch proposal per chain of U (count, A) (trpl_mcmc_propose_stretch; Goodman & Weare 2010):
+    u' = p + z (u - p) with p one row of the chain's rung [(i // group) group, + group) of partners (P, A) and z = ((a - 1) xi + 1)^2
+    / a.  group None: one rung, group = P.  z (count,) is the stretch and lnq (count,) = (A - 1) log(z) the Hastings term that
+    accept_h takes as h.  inside is 0 where u' left the unit cube; Xp is formed either way.  There is no fold: a reflected stretch is
+    not reversible."""
+    U, partners = _f64(U), _f64(partners)
+    lo, hi, lg = _box(minX, maxX, do_log)
+    if U.ndim != 2:
+        raise ValueError("U must be (count, A)")
+    count, A = U.shape
+    if partners.ndim != 2 or partners.shape[1] != A:
+        raise ValueError("partners must be (P, A)")
+    P = partners.shape[0]
+    Up, Xp, inside = np.empty((count, A)), np.empty((count, lo.size)), np.empty(count, dtype=np.int32)
+    z, lnq = np.empty(count), np.empty(count)
+    _timed("trpl_mcmc_propose_stretch", info, _abi.ptr(U), _abi.ptr(partners), count, P, P if group is None else int(group), A, float(a),
+           int(chain0), int(seed) & _M64, int(step) & _M32, lo.size, _abi.ptr(lo), _abi.ptr(hi), _abi.ptr(lg), box_flags(sim_flags),
+           _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(inside), _abi.ptr(z), _abi.ptr(lnq), int(device))
+    return Up, Xp, inside, z, lnq
+
+
+def accept_h(U, X, LL, Up, Xp, LLp, inside, h, tf, chain0, seed, step, device=0, info=None):
+    """accepted (count,) int32: accept_rungs() with an untempered log term h (count,) per chain (trpl_mcmc_accept_h): d = (LLp - LL) /
+    tf + h.  tf (K,), or a scalar for one temperature.  h is the log of the proposal's ratio q(u' -> u) / q(u -> u') (propose_stretch's
+    lnq), of the prior's ratio (prior_term), or their sum; a chain whose h is NaN or -inf stays.  With h = 0 the bits of accept_rungs."""
+    return _accept(True, U, X, LL, Up, Xp, LLp, inside, np.atleast_1d(_f64(tf)), chain0, seed, step, device, info, h=h)
+
+
+def reject_levels_h(LL, h, tf, chain0, seed, step, device=0, info=None):
+    """level (count,): reject_levels_rungs() for accept_h() called with the same (h, tf, chain0, seed, step) (trpl_mcmc_levels_h).  +inf
+    also where h is NaN or infinite.  A level can be negative (h far below zero: every LLp <= 0 is rejected); driver.loglik takes
+    max(level, 0)."""
+    return _levels(True, LL, np.atleast_1d(_f64(tf)), chain0, seed, step, device, info, h=h)
+
+
+def prior_term(U, Up, mean, sd, h=None, device=0, info=None):
+    """h_out (count,) = h + (lnp(Up) - lnp(U)), lnp(u) = sum_d -t^2 / 2 with t = (u_d - mean_d) / sd_d: the log ratio of an independent
+    Gaussian prior in unit coordinates between the proposals Up and the chains U, both (count, A), added to h (None: zeros)
+    (trpl_mcmc_prior_term).  mean and sd are (A,); sd_d = inf is a flat column and adds exactly 0."""
+    U, Up = _f64(U), _f64(Up)
+    if U.ndim != 2 or Up.shape != U.shape:
+        raise ValueError("U and Up must be (count, A)")
+    count, A = U.shape
+    mean, sd = _f64(mean), _f64(sd)
+    if mean.shape != (A,) or sd.shape != (A,):
+        raise ValueError("mean and sd must be (A,)")
+    if h is not None:
+        h = _f64(h)
+        if h.shape != (count,):
+            raise ValueError("h must be (count,)")
+    out = np.empty(count)
+    _timed("trpl_mcmc_prior_term", info, _abi.ptr(U), _abi.ptr(Up), count, A, _abi.ptr(mean), _abi.ptr(sd),
+           None if h is None else _abi.ptr(h), _abi.ptr(out), int(device))
+    return out
+
+
+def gaussian_prior(center_X, width, minX, maxX, do_log, sim_flags=None):
+    """(mean_u, sd_u), each (A,): the prior= of run and run_tempered from a centre row center_X (ncol,) in the box's units and a width
+    (ncol,) per column -- one standard deviation, in the column's units on a linear column and in decades on a log column; inf (or
+    a fixed column) means flat.  The unit coordinate of a column is (x - lo) / (hi - lo), in log10 on a log column, so the Gaussian
+    is one in x on a linear column and a log-normal on a log column."""
+    lo, hi, lg = _box(minX, maxX, do_log)
+    c, w = np.broadcast_to(_f64(center_X), lo.shape), np.broadcast_to(_f64(width), lo.shape)
+    act = refine.active_columns(lo, hi, sim_flags)
+    mean, sd = np.full(act.size, 0.5), np.full(act.size, np.inf)
+    for k, col in enumerate(act):
+        if np.isinf(w[col]) and w[col] > 0:
+            continue
+        if not (w[col] > 0 and np.isfinite(c[col])):
+            raise ValueError("column %d: the width must be > 0 (inf: flat) and the centre finite" % col)
+        if lg[col]:
+            if not c[col] > 0:
+                raise ValueError("column %d: the centre of a log column must be > 0" % col)
+            span = np.log10(hi[col]) - np.log10(lo[col])
+            mean[k], sd[k] = (np.log10(c[col]) - np.log10(lo[col])) / span, w[col] / span
+        else:
+            span = hi[col] - lo[col]
+            mean[k], sd[k] = (c[col] - lo[col]) / span, w[col] / span
+    return mean, sd
 
 
 def geometric_ladder(tf, tf_hot, K):
@@ -365,19 +464,39 @@ class Chains:
         return np.sqrt(info["var_plus"] / ess)
 
 
-def _proposal_args(C, kind, bounds, scale):
+def _proposal_args(C, kind, bounds, scale, gamma=None, jump_every=0, stretch_a=2.0):
     """What run and run_tempered refuse alike about the ensemble and its proposal; returns scale with kind="de"'s default."""
     if C < 4 or C % 2:
         raise ValueError("C=%d: the two halves of the ensemble need an even number of chains, at least 4" % C)
-    if kind not in ("de", "rw"):
-        raise ValueError("kind must be 'de' or 'rw'")
+    if kind not in ("de", "rw", "stretch"):
+        raise ValueError("kind must be 'de', 'rw' or 'stretch'")
     if bounds not in ("reject", "fold"):
         raise ValueError("bounds must be 'reject' or 'fold'")
+    if kind == "stretch":
+        if gamma is not None or scale is not None or int(jump_every) != 0:
+            raise ValueError("kind='stretch' has no gamma, scale or jump_every: the move's only parameter is stretch_a")
+        if bounds != "reject":
+            raise ValueError("kind='stretch' needs bounds='reject': a reflected stretch is not reversible")
+        if not (np.isfinite(stretch_a) and stretch_a > 1.0):
+            raise ValueError("stretch_a=%r must be finite and > 1" % (stretch_a,))
+        return 0.0
     if scale is None:
         if kind == "rw":
             raise ValueError("kind='rw' needs scale, the half-width of the random walk")
         scale = 1e-3
     return scale
+
+
+def _prior_args(prior, A):
+    """prior=(mean_u, sd_u) of run and run_tempered as two (A,) arrays, or None."""
+    if prior is None:
+        return None
+    mean, sd = (_f64(v) for v in prior)
+    if mean.shape != (A,) or sd.shape != (A,):
+        raise ValueError("prior must be (mean_u, sd_u), each (A,) with the box's A = %d active columns" % A)
+    if not (np.all(np.isfinite(mean)) and np.all(sd > 0.0)):
+        raise ValueError("prior: every mean must be finite and every sd > 0 (inf: a flat column)")
+    return mean, sd
 
 
 def _active(lo, hi, sim_flags):
@@ -388,16 +507,22 @@ def _active(lo, hi, sim_flags):
 
 
 def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jump_every, seed, kept, device, fold, early_reject, tf=None,
-            ladder=None, swap_every=1):
+            ladder=None, swap_every=1, stretch_a=2.0, prior=None):
     """The sweeps of run (tf: the C rows of U, X, LL as run holds them, the single-temperature front ends) and of run_tempered
     (ladder (K,): the 2 K g rows half-major, the *_rungs front ends and the swap).  The state is advanced in place.  Returns the
     history -- U, X, LL, accept, each (K, n, C, ..), K = 1 for run -- and the counters: accept (sweeps, K) the share of chains that
-    moved, outside, folded, levelled, solved (K,) proposals, tried, done (K - 1,) exchanges."""
+    moved, outside, folded, levelled, solved (K,) proposals, tried, done (K - 1,) exchanges.
+
+    kind="stretch" or a prior makes every half-sweep a Metropolis-Hastings step: it forms h (count,) -- propose_stretch's lnq, plus
+    prior_term -- and goes through accept_h and reject_levels_h, which take a ladder of one for run.  A proposal whose h is NaN or
+    -inf is not solved and counts as outside.  With neither, the calls are exactly the ones above."""
     lo, hi, lg = box
+    hastings = kind == "stretch" or prior is not None
     K = 1 if ladder is None else ladder.size
     half, A = U.shape[0] // 2, U.shape[1]
     g, C = half // K, 2 * half // K
     levels_of, accept_of, temper = (reject_levels, accept, tf) if ladder is None else (reject_levels_rungs, accept_rungs, ladder)
+    ladder_h = np.array([float(tf)]) if ladder is None else ladder
     if K == 1:                                                   # one rung: the rows are the rung
         rung_major, per_rung = (lambda a: a[None]), np.count_nonzero
     else:
@@ -417,7 +542,11 @@ def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jum
         gm = 1.0 if jump_every > 0 and (t + 1) % jump_every == 0 else gamma0
         for h, (a, b) in enumerate(((0, half), (half, 2 * half))):
             step = 2 * t + h                                     # with chain0 = a, the key of the half-sweep's calls
-            if kind == "rw":
+            hh = None
+            if kind == "stretch":
+                Up, Xp, inside, _, hh = propose_stretch(U[a:b], U[half:] if h == 0 else U[:half], g, stretch_a, a, seed, step, lo, hi, lg,
+                                                        sim_flags, device=device)
+            elif kind == "rw":
                 Up, Xp, inside = propose(U[a:b], None, gm, scale, a, seed, step, lo, hi, lg, sim_flags, device=device, fold=fold)
             elif ladder is None:
                 Up, Xp, inside = propose(U[a:b], U[half:] if h == 0 else U[:half], gm, scale, a, seed, step, lo, hi, lg, sim_flags,
@@ -426,9 +555,16 @@ def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jum
                 Up, Xp, inside = propose_rungs(U[a:b], U[half:] if h == 0 else U[:half], g, gm, scale, a, seed, step, lo, hi, lg,
                                                sim_flags, device=device, fold=fold)
             ok = inside != 0
+            if prior is not None:
+                hh = prior_term(U[a:b], Up, prior[0], prior[1], hh, device=device)
+            if hastings:
+                ok &= ~np.isnan(hh) & (hh > -np.inf)
             LLp = np.full(half, -np.inf)
             if ok.any() and early_reject:
-                levels = levels_of(LL[a:b], temper, a, seed, step, device=device)
+                if hastings:                                     # a level below 0 cuts what sse >= 0 has decided already
+                    levels = np.maximum(reject_levels_h(LL[a:b], hh, ladder_h, a, seed, step, device=device), 0.0)
+                else:
+                    levels = levels_of(LL[a:b], temper, a, seed, step, device=device)
                 LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok]), cut_levels=levels[ok]))
                 levelled += per_rung(ok & np.isfinite(levels))
                 solved += per_rung(ok)
@@ -436,7 +572,10 @@ def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jum
                 LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok])))
             outside += per_rung(~ok)
             folded += per_rung(inside == 2)
-            moved[a:b] = accept_of(U[a:b], X[a:b], LL[a:b], Up, Xp, LLp, inside, temper, a, seed, step, device=device) != 0
+            if hastings:
+                moved[a:b] = accept_h(U[a:b], X[a:b], LL[a:b], Up, Xp, LLp, inside, hh, ladder_h, a, seed, step, device=device) != 0
+            else:
+                moved[a:b] = accept_of(U[a:b], X[a:b], LL[a:b], Up, Xp, LLp, inside, temper, a, seed, step, device=device) != 0
         shares[t] = rung_major(moved).mean(axis=1)
         if K > 1 and (t + 1) % swap_every == 0:
             parity = (t // swap_every) % 2
@@ -452,7 +591,8 @@ def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jum
 
 
 def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0, kind="de", gamma=None, scale=None, jump_every=0,
-        seed=1, keep_every=1, burn=0, max_history_bytes=4 << 30, device=0, info=None, U0=None, bounds="reject", early_reject=False):
+        seed=1, keep_every=1, burn=0, max_history_bytes=4 << 30, device=0, info=None, U0=None, bounds="reject", stretch_a=2.0, prior=None,
+        early_reject=False):
     """Advance the C chains that start at X0 (C, ncol), LL0 (C,) by `sweeps` sweeps; loglik(X) -> LL is any callable (the fused
     likelihood, a toy).  Returns Chains: the states after the sweeps burn, burn + keep_every, ...
 
@@ -465,6 +605,17 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
     sweep (a jump between modes); scale (the uniform jitter's half-width, a scalar or (A,)) defaults to 1e-3.  kind="rw": the random
     walk of half-width scale, which must be given; no partners.  U0 (C, A): the unit coordinates of X0 when they are at hand (start
     returns them); default refine.unit_coords(X0).
+
+    kind="stretch": the affine-invariant stretch move (Goodman & Weare 2010; propose_stretch) with stretch_a > 1, default 2: each
+    chain moves along the line through one chain of the other half, u' = p + z (u - p), and the factor z^(A - 1) enters the accept
+    step as its Hastings term (accept_h).  It has no other parameter: gamma, scale and jump_every must be left at their defaults, and
+    bounds must be "reject" (a reflected stretch is not reversible); ValueError otherwise.  info receives stretch_a.
+
+    prior=(mean_u, sd_u), each (A,): an independent Gaussian prior in the unit coordinates of the active columns on top of the
+    uniform one on the cube (gaussian_prior makes the pair from a centre and widths in the box's units; sd inf is a flat column).
+    Valid with every kind and both bounds.  Its log ratio enters the accept step untempered (prior_term, accept_h): Chains.LL stays
+    the likelihood alone, so early_reject and tf keep their meaning.  A prior whose widths are all inf gives the Chains of the run
+    without it, bit for bit.
 
     early_reject=True (Solonen et al. 2012): each half-sweep computes reject_levels of its chains from their current LL and calls
     loglik(Xp[ok], cut_levels=levels[ok]), so a proposal whose running squared error makes its rejection certain stops being
@@ -483,11 +634,12 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
     if X.ndim != 2 or X.shape[1] != lo.size or LL.shape != (X.shape[0],):
         raise ValueError("X0 must be (C, ncol) and LL0 (C,)")
     C = X.shape[0]
-    scale = _proposal_args(C, kind, bounds, scale)
+    scale = _proposal_args(C, kind, bounds, scale, gamma, jump_every, stretch_a)
     sweeps, keep_every, burn = int(sweeps), int(keep_every), int(burn)
     if sweeps < 1 or keep_every < 1 or burn < 0:
         raise ValueError("sweeps and keep_every must be >= 1 and burn >= 0")
     A = _active(lo, hi, sim_flags)
+    prior = _prior_args(prior, A)
     kept = range(burn, sweeps, keep_every)
     need = len(kept) * C * ((A + lo.size + 1) * 8 + 1)
     if need > int(max_history_bytes):
@@ -500,8 +652,11 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
         if U.shape != (C, A):
             raise ValueError("U0 must be (C, A) with the box's A = %d active columns" % A)
     hist, n = _sweeps(loglik, U, X, LL, tf=tf, box=(lo, hi, lg), sim_flags=sim_flags, sweeps=sweeps, kind=kind, gamma=gamma, scale=scale,
-                      jump_every=int(jump_every), seed=seed, kept=kept, device=device, fold=bounds == "fold", early_reject=early_reject)
+                      jump_every=int(jump_every), seed=seed, kept=kept, device=device, fold=bounds == "fold", early_reject=early_reject,
+                      stretch_a=float(stretch_a), prior=prior)
     if info is not None:
+        if kind == "stretch":
+            info.update(stretch_a=float(stretch_a))
         info.update(accept=n["accept"][:, 0].tolist(), outside=int(n["outside"][0]) / float(sweeps * C),
                     folded=int(n["folded"][0]) / float(sweeps * C))
         if early_reject:
@@ -526,7 +681,7 @@ class Tempered:
 
 def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sweeps=1000, swap_every=1, kind="de", gamma=None,
                  scale=None, jump_every=0, seed=1, keep_every=1, burn=0, max_history_bytes=4 << 30, device=0, info=None, U0=None,
-                 bounds="reject", early_reject=False):
+                 bounds="reject", stretch_a=2.0, prior=None, early_reject=False):
     """Parallel tempering (replica exchange: Swendsen & Wang 1986, Geyer 1991): K = len(ladder) copies of run's
     ensemble of C chains, rung k at temperature ladder[k], advanced together, and states of adjacent rungs exchanged by the
     Metropolis rule of swap().  The hot rungs cross between separated modes; the exchange carries that down to rung 0, whose
@@ -539,7 +694,8 @@ def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sw
     optionally one reject_levels_rungs, ONE call of loglik on the proposals of all rungs that are to be solved, and one
     accept_rungs; step and chain0 are run's (2 t + h, the block's first row).  After every swap_every-th sweep t (t + 1 a multiple
     of swap_every) each block gets one swap with parity = (t // swap_every) % 2, step = t and chain0 the block's first row.  With
-    ladder = [tf] no swap is called and rung(0) is run(..., tf=tf)'s Chains bit for bit.
+    ladder = [tf] no swap is called and rung(0) is run(..., tf=tf)'s Chains bit for bit.  kind="stretch" takes each chain's partner
+    from its own rung; a prior is common to the rungs and is not tempered, so it cancels in the swap, which is unchanged.
 
     The other keywords are run's.  Chains.accept of a rung is the Metropolis step's flag of the rung's slots; an exchange does not
     count as a move.  The history takes n K C (A + ncol + 1) 8 + n K C bytes and is refused above max_history_bytes before anything
@@ -558,11 +714,12 @@ def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sw
     if X.ndim != 3 or X.shape[0] != K or X.shape[2] != lo.size or LL.shape != X.shape[:2]:
         raise ValueError("X0 must be (C, ncol) and LL0 (C,), or (K, C, ncol) and (K, C) with the ladder's K = %d" % K)
     C = X.shape[1]
-    scale = _proposal_args(C, kind, bounds, scale)
+    scale = _proposal_args(C, kind, bounds, scale, gamma, jump_every, stretch_a)
     sweeps, keep_every, burn, swap_every = int(sweeps), int(keep_every), int(burn), int(swap_every)
     if sweeps < 1 or keep_every < 1 or burn < 0 or swap_every < 1:
         raise ValueError("sweeps, keep_every and swap_every must be >= 1 and burn >= 0")
     A = _active(lo, hi, sim_flags)
+    prior = _prior_args(prior, A)
     kept = range(burn, sweeps, keep_every)
     need = len(kept) * K * C * ((A + lo.size + 1) * 8 + 1)
     if need > int(max_history_bytes):
@@ -584,10 +741,12 @@ def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sw
         U = half_major(U)
     hist, n = _sweeps(loglik, U, X, LL, ladder=ladder, swap_every=swap_every, box=(lo, hi, lg), sim_flags=sim_flags, sweeps=sweeps, kind=kind,
                       gamma=gamma, scale=scale, jump_every=int(jump_every), seed=seed, kept=kept, device=device, fold=bounds == "fold",
-                      early_reject=early_reject)
+                      early_reject=early_reject, stretch_a=float(stretch_a), prior=prior)
     with np.errstate(invalid="ignore"):
         swap_rate = n["done"] / n["tried"].astype(np.float64)
     if info is not None:
+        if kind == "stretch":
+            info.update(stretch_a=float(stretch_a))
         info.update(accept=n["accept"], outside=n["outside"] / float(sweeps * C), folded=n["folded"] / float(sweeps * C), swap_rate=swap_rate)
         if early_reject:
             info.update(early_reject=n["levelled"] / np.maximum(n["solved"], 1).astype(np.float64))

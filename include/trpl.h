@@ -1440,6 +1440,80 @@ int trpl_mcmc_autocov_chains(const double *H, int64_t n, int64_t ldh, int64_t M,
                              double *m2, double *pooled, int32_t device, double *seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_mcmc_accept_h, trpl_mcmc_levels_h, trpl_mcmc_propose_stretch, trpl_mcmc_prior_term -- METROPOLIS-HASTINGS: an untempered
+ * additive log term h [count] per chain in the accept rule and in the early-rejection level, and the two users of it: an asymmetric
+ * proposal (the affine-invariant stretch move of Goodman & Weare 2010, h = ln z^(A - 1)) and an informative prior (independent
+ * Gaussians in unit coordinates, h = ln p(u') - ln p(u)).  The term is NOT divided by the temperature: tempering tempers the
+ * likelihood, not the prior and not the proposal's ratio.  LL stays the likelihood alone, so LL = -sse and early rejection keep
+ * working.  All four calls take a block of K rungs of `group` chains (trpl_mcmc_*_rungs above); K = 1 is the single temperature.
+ * (csrc/mcmc_hastings.hip)
+ *
+ * trpl_mcmc_accept_h: trpl_mcmc_accept_rungs with h [count] behind inside.  The same xi (Philox counter word 0x100 + 9, key (seed;
+ * chain0 + i, step)), the same copy of the rows, the same `accepted`;
+ *     d = (LLp - LL) / tf[i / group] + h[i]                       (fp64, one rounding per operation)
+ * and the proposal is taken exactly when inside != 0, LLp is neither NaN nor -inf, h is neither NaN nor -inf, and LL is not above
+ * -inf, or d >= 0, or log(xi) < d.  h = +inf accepts whatever the likelihoods are (d = +inf), unless they make d a NaN.  With
+ * h[i] = +0.0 (or -0.0) everywhere every output is trpl_mcmc_accept_rungs', bit for bit: x + 0.0 is x but for x = -0.0, which no
+ * comparison tells from +0.0.
+ * WHY THE POSTERIOR STAYS INVARIANT.  With the proposal density q(u -> u') and the prior p, accepting with min(1, exp(d)),
+ * d = (ln L(u') - ln L(u)) / tf + ln(p(u') q(u' -> u) / (p(u) q(u -> u'))), is the Metropolis-Hastings rule for the density p L^(1/tf).
+ *
+ * trpl_mcmc_levels_h: trpl_mcmc_levels_rungs with h [count] behind LL.  level = +inf where trpl_mcmc_levels gives +inf, and where
+ * h[i] is NaN or infinite.  Otherwise the candidates, in order: l0 = -(LL + tf (log(xi) - h)), then l0 + (fabs(LL) + l0) 2^-40; a
+ * candidate l is taken only if the accept step's own dq = (-l - LL) / tf + h satisfies dq < 0 && !(log(xi) < dq); +inf if neither
+ * does.  WHY THAT IS SAFE: as for trpl_mcmc_levels, every LLp <= -l has (LLp - LL) / tf <= (-l - LL) / tf, and adding the same h to
+ * both is monotone under round-to-nearest, so d <= dq, d < 0 and log(xi) < d is false: trpl_mcmc_accept_h with the same (seed,
+ * chain, step, h) rejects.  A level may be negative (h far below zero): then every LLp = -sse <= 0 is rejected; the caller passes
+ * max(level, 0) to trpl_loglik_cut_levels, which is no less safe.  With h = +0.0 the bits are trpl_mcmc_levels_rungs'.
+ *
+ * trpl_mcmc_propose_stretch: one stretch proposal per chain of U [count][A] with a partner from the chain's rung of partners [P][A]:
+ * row (i / group) group + a, a = min((int64)(xa group), group - 1), xa the first uniform of the partner call (counter word 0x100 +
+ * 8); xi the first uniform of counter word 0x100 + 11;
+ *     s = (a - 1) xi + 1,   z = s s / a,   u'_d = p_d + z (u_d - p_d)      (one rounding per operation, in this order)
+ * so that z has the density proportional to 1 / sqrt(z) on [1 / a, a], for which g(1 / z) = z g(z).  Out: Up [count][A], Xp
+ * [count][ncol] by the sampler's expressions, formed either way, inside [count] (0 where a coordinate is outside [0, 1] or NaN,
+ * else 1), z [count] and lnq [count] = (double)(A - 1) log(z), the h of the move: with partners taken from the OTHER half of the
+ * ensemble the move u -> p + z (u - p) has the ratio z^(A - 1) p(u') / p(u) (Goodman & Weare 2010, eq. 7).  There is no jitter and
+ * no fold.  TRPL_MCMC_FOLD is refused: a stretch reflected at a face of the cube is not reversible through the same partner -- the
+ * line from p through the folded point does not pass through u -- so z^(A - 1) would not be its ratio.
+ *
+ * trpl_mcmc_prior_term: h_out[i] = h_in[i] + (lnp(Up_i) - lnp(U_i)), lnp(u) = the sum over d ascending, from +0.0, of (-0.5 t) t
+ * with t = (u_d - mean_d) / sd_d.  A column with sd_d = +inf contributes exactly +0.0.  h_in NULL means +0.0; h_in may be h_out.
+ * mean [A] and sd [A] are HOST arrays, copied into the kernel argument like scale.  The prior is common to the rungs, so it cancels
+ * in trpl_mcmc_swap, which stays as it is.
+ *
+ * Refused (TRPL_ERR_ARG, before a device is touched, the message naming the argument): every refusal of the *_rungs counterpart
+ * of the arguments they share; "h is NULL", "z is NULL", "lnq is NULL", "h_out is NULL", "mean is NULL", "sd is NULL"; (stretch) a
+ * not finite or <= 1, P < 1, group < 1, P no multiple of group, count > P, "partners is NULL", TRPL_MCMC_FOLD in flags; (prior)
+ * sd[d] NaN or <= 0, mean[d] not finite.  The _dev calls take device pointers, allocate nothing and never synchronise.
+ * Python: trpl_amd.mcmc.propose_stretch / accept_h / reject_levels_h / prior_term / gaussian_prior, run and run_tempered with
+ * kind="stretch" or prior=, trpl_amd.device.mcmc_propose_stretch_device / mcmc_accept_h_device / mcmc_levels_h_device /
+ * mcmc_prior_term_device.
+ * ------------------------------------------------------------------------------------- */
+int trpl_mcmc_propose_stretch_dev(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, int32_t A, double a,
+                                  int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol, const double *lo /*host*/,
+                                  const double *hi /*host*/, const int32_t *do_log /*host*/, uint32_t flags, double *Up, double *Xp,
+                                  int32_t *inside, double *z, double *lnq, void *stream);
+int trpl_mcmc_propose_stretch(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, int32_t A, double a,
+                              int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol, const double *lo, const double *hi,
+                              const int32_t *do_log, uint32_t flags, double *Up, double *Xp, int32_t *inside, double *z, double *lnq,
+                              int32_t device, double *seconds);
+int trpl_mcmc_accept_h_dev(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
+                           const double *h, int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group,
+                           const double *tf /*host [K]*/, int64_t chain0, uint64_t seed, uint32_t step, int32_t *accepted, void *stream);
+int trpl_mcmc_accept_h(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
+                       const double *h, int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group, const double *tf, int64_t chain0,
+                       uint64_t seed, uint32_t step, int32_t *accepted, int32_t device, double *seconds);
+int trpl_mcmc_levels_h_dev(const double *LL, const double *h, int64_t count, int32_t K, int64_t group, const double *tf /*host [K]*/,
+                           int64_t chain0, uint64_t seed, uint32_t step, double *level, void *stream);
+int trpl_mcmc_levels_h(const double *LL, const double *h, int64_t count, int32_t K, int64_t group, const double *tf, int64_t chain0,
+                       uint64_t seed, uint32_t step, double *level, int32_t device, double *seconds);
+int trpl_mcmc_prior_term_dev(const double *U, const double *Up, int64_t count, int32_t A, const double *mean /*host [A]*/,
+                             const double *sd /*host [A]*/, const double *h_in /*nullable*/, double *h_out, void *stream);
+int trpl_mcmc_prior_term(const double *U, const double *Up, int64_t count, int32_t A, const double *mean, const double *sd,
+                         const double *h_in /*nullable*/, double *h_out, int32_t device, double *seconds);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the
  * measurement plan): S independent systems  ld[i] x[i-1] + d[i] x[i] + ud[i] x[i+1] = b[i],
  * i < L, the problem pcreduce solves (pvSimPCR.py:42-81), operands and result in HBM, arrays

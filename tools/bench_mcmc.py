@@ -1,6 +1,6 @@
 """The three kernels of the ensemble Metropolis sampler on resident tensors, in one process on one device.
 
-    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--fold] [--tempered [--rungs 16]] [--autocov]
+    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--fold] [--tempered [--rungs 16]] [--hastings] [--autocov]
                                [--out profiles/mcmc_bench.jsonl] [--label parent]
     python tools/bench_mcmc.py --host-loop [--out ...] [--label ...]
 
@@ -13,6 +13,9 @@ accept:      mcmc_accept_device of the same chains, about a third of the proposa
 --tempered:  the four kernels of parallel tempering at the same rows, cut into --rungs rungs on geometric_ladder(1, 64, rungs):
              propose_rungs (partners from the chain's own rung), accept_rungs and levels_rungs (a temperature per rung, beside
              levels, the scalar call) and swap (parity 0).
+--hastings:  the four Metropolis-Hastings kernels at the same rows and the same --rungs rungs, beside the three
+             rung kernels they extend, in the same process: propose_stretch beside propose_rungs, accept_h beside accept_rungs,
+             levels_h beside levels_rungs, and prior_term (two Gaussian columns, the rest flat).
 chain_stats: mcmc_chain_stats_device over a history of n steps of chains * A columns (one half of a split-R-hat: n / 2 steps).
 --autocov:   the two kernels of the effective sample size over the same chains * A columns, at L = 64 and L = 512 lags:
              mcmc_autocov_device over one half of a history (max(n / 2, L) steps, so L = 64 runs on chain_stats' own range) and
@@ -88,6 +91,7 @@ def main():
     ap.add_argument("--fold", action="store_true")
     ap.add_argument("--tempered", action="store_true")
     ap.add_argument("--rungs", type=int, default=16)
+    ap.add_argument("--hastings", action="store_true")
     ap.add_argument("--autocov", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcmc_bench.jsonl"))
     a = ap.parse_args()
@@ -149,6 +153,25 @@ def main():
         calls["levels"] = lambda: tdev.mcmc_levels_device(LL, 1.0, 0, 42, 0, level)
         calls["levels_rungs"] = lambda: tdev.mcmc_levels_rungs_device(LL, ladder, 0, 42, 0, level)
         calls["swap"] = lambda: tdev.mcmc_swap_device(Us, Xs, LLs, ladder, 0, 0, 42, 0, swapped)
+    if a.hastings:
+        K = a.rungs
+        if C % K or C // K < 2:
+            raise SystemExit("--chains must be a multiple of --rungs, two chains per rung at least")
+        ladder_h = trpl_amd.mcmc.geometric_ladder(1.0, 64.0, K)
+        Uph, Xph, insh, zh, lnq = torch.empty_like(Up), torch.empty_like(Xp), torch.empty_like(inside), torch.empty(C, **f64), torch.empty(C, **f64)
+        Uh, Xh, LLh, acch = U.clone(), X.clone(), LL.clone(), torch.empty_like(accepted)
+        Ug, Xg, LLg, accg = U.clone(), X.clone(), LL.clone(), torch.empty_like(accepted)
+        hterm, level_h, level_g = torch.randn(C, generator=g, **f64), torch.empty(C, **f64), torch.empty(C, **f64)
+        pm, psd = [0.5] * A, [0.1, 0.2] + [float("inf")] * (A - 2)
+        if not a.tempered:                                       # the kernels they extend, unless --tempered has them already
+            Upg, Xpg, insg = torch.empty_like(Up), torch.empty_like(Xp), torch.empty_like(inside)
+            calls["propose_rungs"] = lambda: tdev.mcmc_propose_rungs_device(U, partners, C // K, gamma, 1e-3, 0, 42, 0, lo, hi, lg, Upg, Xpg, insg)
+            calls["accept_rungs"] = lambda: tdev.mcmc_accept_rungs_device(Ug, Xg, LLg, Up, Xp, LLp, inside, ladder_h, 0, 42, 0, accg)
+            calls["levels_rungs"] = lambda: tdev.mcmc_levels_rungs_device(LL, ladder_h, 0, 42, 0, level_g)
+        calls["propose_stretch"] = lambda: tdev.mcmc_propose_stretch_device(U, partners, C // K, 2.0, 0, 42, 0, lo, hi, lg, Uph, Xph, insh, zh, lnq)
+        calls["accept_h"] = lambda: tdev.mcmc_accept_h_device(Uh, Xh, LLh, Up, Xp, LLp, inside, hterm, ladder_h, 0, 42, 0, acch)
+        calls["levels_h"] = lambda: tdev.mcmc_levels_h_device(LL, hterm, ladder_h, 0, 42, 0, level_h)
+        calls["prior_term"] = lambda: tdev.mcmc_prior_term_device(U, Up, pm, psd, lnq, lnq)
     floors = {}
     if a.autocov:
         tile, Q = trpl_amd._abi.lib().trpl_mcmc_autocov_tile(), C * A
@@ -172,6 +195,9 @@ def main():
         line["folded_share"] = float((codes == 2).double().mean().item())
     if a.tempered:
         line.update(rungs=a.rungs, swapped_share=float(swapped.double().mean().item()))
+    if a.hastings:
+        line.update(rungs=a.rungs, hastings=True, stretch_inside_share=float(insh.double().mean().item()),
+                    accepted_h_share=float(acch.double().mean().item()))
     if a.autocov:
         line.update(autocov_tile=tile, autocov_floors=floors)
     return write(a, line)

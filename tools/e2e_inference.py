@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--fold] [--early-reject] [--tempered K [--tf-hot x]]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject] [--tempered K [--tf-hot x]]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -49,6 +49,11 @@ the same numbers are printed.
 --tf-hot x sets the hottest temperature; the default is the temperature at which the importance run reaches an effective sample
 size of 64 (posterior.tf_for_ess).  "mcmc" is the cold rung's, as without the flag; "tempered" beside it holds the ladder and, per
 rung, acceptance and worst R-hat, the swap rates and the seconds, which are printed.
+--stretch [a] (with --mcmc; not with --rw or --fold) proposes by the affine-invariant stretch move instead (mcmc.run(kind="stretch",
+stretch_a=a), a defaulting to 2: DESIGN.md section 30).  --prior NAME=CENTER:WIDTH (with --mcmc; repeatable) puts a Gaussian prior on
+the free parameter NAME (a name of sampler.PARAM_NAMES): CENTER in the units of the search box, WIDTH one standard deviation in the
+same units on a linear parameter and in decades on a logarithmic one (mcmc.gaussian_prior).  "mcmc" then gains "stretch_a" and
+"prior"; both compose with --early-reject and --tempered.
 """
 import json
 import sys
@@ -95,6 +100,21 @@ for flag, conv in (("--chains", int), ("--sweeps", int), ("--rw", float), ("--te
             TF_HOT = value
         else:
             RW = value
+STRETCH = None
+if "--stretch" in sys.argv:
+    k = sys.argv.index("--stretch")
+    try:
+        STRETCH = float(sys.argv[k + 1])
+        del sys.argv[k:k + 2]
+    except (IndexError, ValueError):
+        STRETCH = 2.0
+        del sys.argv[k]
+PRIORS = {}
+while "--prior" in sys.argv:
+    k = sys.argv.index("--prior")
+    name, spec = sys.argv[k + 1].split("=")
+    PRIORS[name] = tuple(float(v) for v in spec.split(":"))
+    del sys.argv[k:k + 2]
 sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented", "--mcmc", "--fold", "--early-reject")]
 import numpy as np
 import torch
@@ -287,7 +307,16 @@ if MCMC:
     X0, U0, LL0 = mcmc.start(X.cpu().numpy(), P.cpu().numpy(), CHAINS, lo, hi, lg, tf=tf)
     minfo = {}
     burn = SWEEPS // 2
-    opts = dict(sweeps=SWEEPS, seed=42, burn=burn, info=minfo, U0=U0, **({"kind": "rw", "scale": RW} if RW is not None else {}),
+    hastings = {}
+    if STRETCH is not None:
+        hastings.update(kind="stretch", stretch_a=STRETCH)
+    if PRIORS:                                                   # centres and linear widths in the box's units, like lo and hi
+        centre, width = np.array(lo, dtype=np.float64), np.full(len(lo), np.inf)
+        for name, (c0, w0) in PRIORS.items():
+            i = sm.PARAM_NAMES.index(name)
+            centre[i], width[i] = c0 * sm.UNIT_CONVERSIONS[i], w0 if lg[i] else w0 * sm.UNIT_CONVERSIONS[i]
+        hastings.update(prior=mcmc.gaussian_prior(centre, width, lo, hi, lg))
+    opts = dict(sweeps=SWEEPS, seed=42, burn=burn, info=minfo, U0=U0, **({"kind": "rw", "scale": RW} if RW is not None else {}), **hastings,
                 **({"bounds": "fold"} if FOLD else {}), **({"early_reject": True} if EARLY else {}))
     if TEMPERED:
         hot_ess = None
@@ -318,7 +347,7 @@ if MCMC:
     q_imp = posterior.quantiles(V.cpu().numpy(), W.cpu().numpy(), qs)
     out["seconds"]["mcmc"] = sync() - t11
     act = [int(i) for i in trpl_amd.refine.active_columns(lo, hi)]
-    out["mcmc"] = {"chains": CHAINS, "sweeps": SWEEPS, "kept_sweeps": int(ch.U.shape[0]), "proposal": "rw %g" % RW if RW is not None else "de",
+    out["mcmc"] = {"chains": CHAINS, "sweeps": SWEEPS, "kept_sweeps": int(ch.U.shape[0]), "proposal": "rw %g" % RW if RW is not None else "stretch %g" % STRETCH if STRETCH is not None else "de",
                    "distinct_starts": int(np.unique(LL0).size),
                    "acceptance": float(np.mean(minfo["accept"])), "acceptance_kept": float(np.mean(minfo["accept"][burn:])),
                    "outside_share_of_proposals": minfo["outside"], "worst_rhat": float(np.nanmax(rhat)),
@@ -327,6 +356,10 @@ if MCMC:
                    "quantiles": {n: {"truth": float(tr), "chain": [float(v) for v in q_chain[:, k]],
                                      "importance": [float(v) for v in q_imp[:, k]]} for k, (n, tr) in enumerate(zip(names, truth))}}
     out["mcmc"]["system_timesteps"] = work["iters"]
+    if STRETCH is not None:
+        out["mcmc"]["stretch_a"] = STRETCH
+    if PRIORS:
+        out["mcmc"]["prior"] = {name: {"center": c0, "width": w0} for name, (c0, w0) in PRIORS.items()}
     if EARLY:
         out["mcmc"]["early_reject"] = {"cut_share_of_solved_proposals": work["cut"] / float(max(work["solved"], 1)),
                                        "levelled_share": minfo["early_reject"]}
