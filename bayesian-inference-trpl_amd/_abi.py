@@ -153,6 +153,11 @@ SIGNATURES = {
                                _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _pd],
     "trpl_loglik_cut_levels_dev": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
+    # budget [S] where cut_level is, curves_per_launch after it, cut_level [C][S] out before P
+    "trpl_loglik_cut_budget": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                               _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _pd],
+    "trpl_loglik_cut_budget_dev": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                   _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "trpl_loglik_multi": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64,
                           _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _i32, _pd],
     "trpl_multi_create": [_vp, _i32, _vp],

@@ -125,7 +125,7 @@ struct HostMap {
 // Members are destroyed last to first: the buffers are released (hipFreeAsync), then the scope drains and destroys the stream,
 // then the caller's memory is unpinned.
 struct Staged {
-    static constexpr int kMaxBufs = 13;      // the largest users, trpl_loglik_weighted and trpl_loglik_cut_levels off the grid, declare 13
+    static constexpr int kMaxBufs = 14;      // the largest user, trpl_loglik_cut_budget off the grid, declares 14 (trpl_loglik_weighted and _cut_levels: 13)
     HostMap hm;                              // the one buffer of the caller's that pin() or map() holds for the call
     CallScope cs;
     DevBuf buf[kMaxBufs];
@@ -254,6 +254,10 @@ struct LoglikCall {
     const int64_t *n_obs = nullptr;
     const double *sse_cut = nullptr;                 // host: the threshold of the cut entry points
     const double *cut_level = nullptr;               // [C][S]: a level per system (trpl_loglik_cut_levels[_dev]) in the place of sse_cut
+    // trpl_loglik_cut_budget[_dev]: budget [S], a level per sample for its total, spent over launches of curves_per_launch curves;
+    // cut_level is then the call's OUTPUT (the entry points take it as double *): loglik_dev fills its rows before each launch
+    const double *budget = nullptr;
+    int32_t curves_per_launch = 0;
     double *P = nullptr, *sse = nullptr, *esum = nullptr;
     int32_t *cut_col = nullptr, *status = nullptr;
     int64_t *iters_total = nullptr;

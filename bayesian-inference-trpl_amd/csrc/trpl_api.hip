@@ -890,11 +890,21 @@ int trpl::loglik_dev(const LoglikCall &k, hipStream_t stream)
     // number of curves (bayeslib.py:117), so more are run as consecutive launches of up to kMaxCurves on the same stream,
     // each writing its own rows of the [C][S] outputs, before ONE reduction over all C in curve order (probs.py:44).  The
     // stepper variant is chosen once from the whole batch, so a system's bits do not depend on the grouping.
+    // trpl_loglik_cut_budget[_dev] (k.budget): groups of curves_per_launch curves instead, and before each group the kernel of
+    // cut_budget.hip writes the group's rows of cut_level from the budget and the sse rows the earlier groups have reported
+    // (stream order: a group's sinks read levels that are complete, and its sse is complete before the next group's levels).
     const int64_t steps = loglik_steps(interp, C, k.n_obs, k.plT, T);
-    if (C > trpl::kMaxCurves) flags = pin_variant(flags, S * (int64_t)C, L, steps);
-    for (int c0 = 0; c0 < C; c0 += trpl::kMaxCurves) {
-        const int Cg = C - c0 < trpl::kMaxCurves ? C - c0 : trpl::kMaxCurves;
+    const int group = k.budget ? k.curves_per_launch : trpl::kMaxCurves;
+    if (k.budget && (group < 1 || group > trpl::kMaxCurves || !k.cut_level))
+        return api_fail(TRPL_ERR_ARG, "curves_per_launch=%d must be in [1, %d], with a cut_level to fill", group, trpl::kMaxCurves);
+    if (C > group) flags = pin_variant(flags, S * (int64_t)C, L, steps);
+    for (int c0 = 0; c0 < C; c0 += group) {
+        const int Cg = C - c0 < group ? C - c0 : group;
         if (S * (int64_t)Cg > 0x7fffffffLL) return api_fail(TRPL_ERR_ARG, "S*C too large for one launch");
+        if (k.budget) {
+            hipError_t e = trpl::launch_budget_level(k.budget, k.sse, const_cast<double *>(k.cut_level), S, c0, Cg, stream);
+            if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "budget level launch: %s", hipGetErrorString(e));
+        }
         trpl::StepArgs a;
         memset(&a, 0, sizeof a);
         a.X = k.X; a.xld = 13; a.dN = k.dN + (int64_t)c0 * L; a.obs = k.obs + (int64_t)c0 * obs_ld;
@@ -948,7 +958,12 @@ static int loglik_host(const LoglikCall &k, int32_t device, double *seconds)
     d.P = sg.inout(k.P, (size_t)k.S); d.sse = sg.out(k.sse, nsys); d.esum = k.esum ? sg.out(k.esum, nsys) : nullptr;
     d.status = sg.out(k.status, nsys); d.floor_col = k.floor_col ? sg.out(k.floor_col, nsys) : nullptr;
     d.cut_col = k.cut_col ? sg.out(k.cut_col, nsys) : nullptr;
-    d.cut_level = k.cut_level ? sg.in(k.cut_level, nsys) : nullptr;
+    if (k.budget) {                                  // the budget in, the levels every system ran at out
+        d.budget = sg.in(k.budget, (size_t)k.S);
+        d.cut_level = sg.out(const_cast<double *>(k.cut_level), nsys);
+    } else {
+        d.cut_level = k.cut_level ? sg.in(k.cut_level, nsys) : nullptr;
+    }
     d.iters_total = sg.out(k.iters_total, nsys);
     if (int rc = sg.begin()) return rc;
     if (int rc = loglik_dev(d, sg.stream())) return rc;
@@ -1182,6 +1197,59 @@ int trpl_loglik_cut_levels(const double *X, int64_t S, int32_t C, const double *
     { uint32_t f = flags; if (int rc = check_sink(k, f)) return rc; }       // the flag refusals before the levels are read
     if (int rc = check_batch(k)) return rc;                                  // S >= 0 and C in range: the extent of cut_level
     if (S > 0) { if (int rc = check_levels(cut_level, S, C)) return rc; }
+    return loglik_host(k, device, seconds);
+}
+
+/* ------------------------------------------------------------------ the early stop on a sample's total: a budget carried across the curves */
+// what both forms refuse before anything else: the two arrays and the group size
+static int check_budget_args(int64_t S, const double *budget, int32_t curves_per_launch, const double *cut_level)
+{
+    if (S > 0 && !budget) return api_fail(TRPL_ERR_ARG, "budget must not be NULL");
+    if (S > 0 && !cut_level) return api_fail(TRPL_ERR_ARG, "cut_level must not be NULL");
+    if (curves_per_launch < 1 || curves_per_launch > trpl::kMaxCurves)
+        return api_fail(TRPL_ERR_ARG, "curves_per_launch=%d must be in [1, %d]", curves_per_launch, trpl::kMaxCurves);
+    return TRPL_OK;
+}
+
+int trpl_loglik_cut_budget_dev(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
+                               int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN, const double *obs,
+                               const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t obs_ld,
+                               const int64_t *n_obs, const double *budget, int32_t curves_per_launch, double *cut_level, double *P,
+                               double *sse, int32_t *cut_col, int32_t *status, int64_t *iters_total, int32_t *floor_col,
+                               uint32_t flags, void *stream)
+{
+    if (int rc = check_budget_args(S, budget, curves_per_launch, cut_level)) return rc;
+    const double none = INFINITY;                                 // S == 0: nothing is launched; the common checks still run
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = plT; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h; k.cut_col = cut_col;
+    if (S > 0) { k.budget = budget; k.curves_per_launch = curves_per_launch; k.cut_level = cut_level; } else k.sse_cut = &none;
+    return loglik_dev(k, (hipStream_t)stream);
+}
+
+int trpl_loglik_cut_budget(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns, int32_t L,
+                           int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN, const double *obs,
+                           const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t obs_ld,
+                           const int64_t *n_obs, const double *budget, int32_t curves_per_launch, double *cut_level, double *P,
+                           double *sse, int32_t *cut_col, int32_t *status, int64_t *iters_total, int32_t *floor_col,
+                           uint32_t flags, int32_t device, double *seconds)
+{
+    ProfRange range("trpl_loglik_cut_budget (pvSim + fastlog + prob with a stop budget per sample, fused)");
+    if (int rc = check_budget_args(S, budget, curves_per_launch, cut_level)) return rc;
+    if (int rc = check_interp(obs_hi, obs_dx, obs_h, plT)) return rc;
+    const double none = INFINITY;
+    LoglikCall k;
+    k.X = X; k.S = S; k.C = C; k.lengths_nm = lengths_nm; k.time_ns = time_ns; k.L = L; k.T = T; k.plT = plT; k.tol_exp = tol_exp;
+    k.max_iter = max_iter; k.dN = dN; k.obs = obs; k.obs_ld = obs_ld; k.n_obs = n_obs; k.P = P; k.sse = sse; k.status = status;
+    k.iters_total = iters_total; k.floor_col = floor_col; k.flags = flags;
+    k.obs_hi = obs_hi; k.obs_dx = obs_dx; k.obs_h = obs_h; k.cut_col = cut_col;
+    if (S > 0) { k.budget = budget; k.curves_per_launch = curves_per_launch; k.cut_level = cut_level; } else k.sse_cut = &none;
+    { uint32_t f = flags; if (int rc = check_sink(k, f)) return rc; }       // the flag refusals before the budgets are read
+    if (int rc = check_batch(k)) return rc;
+    for (int64_t s = 0; s < S; s++)                                          // the host form sees its budgets: each >= 0 or +inf
+        if (!(budget[s] >= 0.0)) return api_fail(TRPL_ERR_ARG, "budget[s=%lld]=%g must be >= 0 or +inf", (long long)s, budget[s]);
     return loglik_host(k, device, seconds);
 }
 

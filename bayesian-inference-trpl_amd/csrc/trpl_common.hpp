@@ -118,6 +118,8 @@ hipError_t launch_log10_clamp(void *x, int elem_bytes, int64_t rows, int64_t col
 hipError_t launch_sse_accumulate(double *P, const void *pl, int elem_bytes, int64_t rows, int64_t n_obs,
                                  int64_t ld, const double *values, const double *mag, hipStream_t stream);
 hipError_t launch_reduce_curves(double *P, const double *sse, int64_t S, int C, hipStream_t stream);
+// cut_budget.hip: the level of the curves c0 .. c0 + g - 1 from budget [S] and the reported sse rows 0 .. c0 - 1 (trpl_loglik_cut_budget)
+hipError_t launch_budget_level(const double *budget, const double *sse, double *cut_level, int64_t S, int c0, int g, hipStream_t stream);
 hipError_t launch_pl_loglik(const void *pl, int elem_bytes, int64_t rows, int64_t ld, const double *obs,
                             const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t n_obs,
                             const double *mag, const int32_t *status, double *P, double *sse_out, uint32_t flags,

@@ -35,16 +35,19 @@ def _brackets(obs, obs_hi, obs_dx, obs_h):
 
 
 def _loglik_dev(entry, X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status, iters_total, tol, MAX, flags, floor_col,
-                plT=1, obs_hi=None, obs_dx=None, obs_h=None, wts=None, sse_cut=None, esum=None, cut_col=None, cut_level=None):
-    """The one marshaller of the fused family trpl_loglik[_obs|_moments|_weighted|_cut|_cut_levels]_dev: the arguments all six share,
-    with an entry point's own where include/trpl.h puts them -- wts after obs, the brackets after that (not in trpl_loglik_dev),
-    sse_cut (or cut_level (C,S) f64 in its place) before P, esum or cut_col after sse; trpl_loglik_obs_dev alone has no plT.  A new sink or argument goes HERE."""
+                plT=1, obs_hi=None, obs_dx=None, obs_h=None, wts=None, sse_cut=None, esum=None, cut_col=None, cut_level=None, budget=None,
+                curves_per_launch=1):
+    """The one marshaller of the fused family trpl_loglik[_obs|_moments|_weighted|_cut|_cut_levels|_cut_budget]_dev: the arguments all seven
+    share, with an entry point's own where include/trpl.h puts them -- wts after obs, the brackets after that (not in trpl_loglik_dev),
+    sse_cut (or cut_level (C,S) f64 in its place; or budget (S,) f64, curves_per_launch and the cut_level to fill) before P, esum or
+    cut_col after sse; trpl_loglik_obs_dev alone has no plT.  A new sink or argument goes HERE."""
     import torch
     f64 = torch.float64
     S, Cn = X.shape[0], init_params.shape[0]
     if X.shape[1] != 13 or init_params.shape[1] != L or obs.shape[0] != Cn or tuple(sse.shape) != (Cn, S) \
             or tuple(P.shape) != (S,) or (wts is not None and wts.shape != obs.shape) \
-            or any(t is not None and tuple(t.shape) != (Cn, S) for t in (esum, cut_col, cut_level)):
+            or any(t is not None and tuple(t.shape) != (Cn, S) for t in (esum, cut_col, cut_level)) \
+            or (budget is not None and tuple(budget.shape) != (S,)):
         raise ValueError("shape mismatch")
     brackets = _brackets(obs, obs_hi, obs_dx, obs_h)
     lengths = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.float64), (Cn,)))
@@ -62,10 +65,12 @@ def _loglik_dev(entry, X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, 
         args.append(float(sse_cut))
     if entry == "trpl_loglik_cut_levels_dev":
         args.append(_chk(cut_level, f64, "cut_level"))
+    if entry == "trpl_loglik_cut_budget_dev":
+        args += [_chk(budget, f64, "budget"), int(curves_per_launch), _chk(cut_level, f64, "cut_level")]
     args += [_chk(P, f64, "P"), _chk(sse, f64, "sse")]
     if entry in ("trpl_loglik_moments_dev", "trpl_loglik_weighted_dev"):
         args.append(_chk(esum, f64, "esum"))
-    if entry in ("trpl_loglik_cut_dev", "trpl_loglik_cut_levels_dev"):
+    if entry in ("trpl_loglik_cut_dev", "trpl_loglik_cut_levels_dev", "trpl_loglik_cut_budget_dev"):
         args.append(_opt(cut_col, torch.int32, "cut_col"))
     args += [_opt(status, torch.int32, "status"), _opt(iters_total, torch.int64, "iters_total"),
              _opt(floor_col, torch.int32, "floor_col"), int(flags), _stream()]
@@ -121,6 +126,22 @@ def loglik_cut_levels_device(X, init_params, lengths, Time, L, T, obs, n_obs, cu
         raise ValueError("cut_level must be a (C,S) float64 tensor")
     _loglik_dev("trpl_loglik_cut_levels_dev", X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status, iters_total, tol, MAX,
                 flags, floor_col, plT=plT, obs_hi=obs_hi, obs_dx=obs_dx, obs_h=obs_h, cut_col=cut_col, cut_level=cut_level)
+
+
+def loglik_cut_budget_device(X, init_params, lengths, Time, L, T, obs, n_obs, budget, cut_level, P, sse, curves_per_launch=1,
+                             cut_col=None, status=None, iters_total=None, tol=7, MAX=10000, plT=1, flags=0, floor_col=None,
+                             obs_hi=None, obs_dx=None, obs_h=None):
+    """trpl_loglik_cut_budget_dev: the early stop on a sample's TOTAL -- budget (S,) f64 on the device is the level for sum_c sse[c, s],
+    spent over consecutive launches of curves_per_launch (1 .. 16) curves: before each launch a kernel gives its curves the level the
+    budget leaves after what the earlier curves reported.  cut_level (C,S) f64 is an OUTPUT, the level every system ran at; every
+    system reports what loglik_cut_levels_device reports for it at that level, bit for bit.  A sample with any cut_col >= 0 has a plain
+    total >= its budget.  Nobody looks at the values here: a NaN budget never cuts, a negative one cuts every system of the sample after
+    its first batch (include/trpl.h)."""
+    if budget is None or cut_level is None:
+        raise ValueError("budget must be a (S,) and cut_level a (C,S) float64 tensor")
+    _loglik_dev("trpl_loglik_cut_budget_dev", X, init_params, lengths, Time, L, T, obs, n_obs, P, sse, status, iters_total, tol, MAX,
+                flags, floor_col, plT=plT, obs_hi=obs_hi, obs_dx=obs_dx, obs_h=obs_h, cut_col=cut_col, cut_level=cut_level, budget=budget,
+                curves_per_launch=curves_per_launch)
 
 
 def _mag_grid_dev(entry, sse, esum, per_curve, dtype, offsets, P):

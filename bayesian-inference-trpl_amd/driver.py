@@ -139,7 +139,7 @@ def overlap_window(full, done, budget, num_curves):
 def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=None, pl_f32=False,
            normalize=False, strict=False, device=0, info=None, times=None, fp32=False, devices=None, kernel=None,
            mixed=False, bundle=1, hist32=False, bdf_order=None, extra_flags=0, predict=False, mag_grid=None,
-           mag_profile=False, weights=None, sse_cut=None, cut_levels=None):
+           mag_profile=False, weights=None, sse_cut=None, cut_levels=None, cut_budget=None, curves_per_launch=1):
     """Fused likelihood of one experiment (trpl_loglik / trpl_loglik_obs / trpl_loglik_multi).
 
     X (S,13) solver units; init_params (C,L) nm^-3; lengths scalar or (C,); obs = list of C
@@ -174,13 +174,29 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
     curves, or (C, S); every level >= 0 or +inf.  System (c, s) reports what sse_cut = cut_levels[c, s] would make it report, bit
     for bit, whatever the other levels; info receives cut_col and cut_fraction as with sse_cut.  Excludes sse_cut and is refused
     with what sse_cut is refused with.  The levels of a Metropolis step: mcmc.reject_levels.
+    cut_budget: (S,), every entry >= 0 or +inf -- a level for each sample's TOTAL sum_c sse[c, s], spent across its curves
+    (trpl_loglik_cut_budget): the curves run as consecutive launches of curves_per_launch (1 .. 16) curves, and each launch's curves
+    run at the level the budget leaves after what the earlier curves reported (include/trpl.h has the rule and its proof).  A sample
+    with a cut system has a plain total >= its budget.  info receives cut_col and cut_fraction as with sse_cut, cut_level (C, S), the
+    level every system ran at (-1: the sample was past its budget already), and cut_samples, the share of samples with any cut_col >=
+    0.  curves_per_launch=1 is the tightest and serialises the curves; >= C is cut_levels with the budget as every curve's level.
+    Excludes sse_cut and cut_levels and is refused with what those are refused with.
     """
+    if cut_budget is not None:
+        if sse_cut is not None or cut_levels is not None:
+            raise ValueError("cut_budget, cut_levels and sse_cut exclude each other")
+        cut_budget = np.ascontiguousarray(cut_budget, dtype=np.float64)
+        curves_per_launch = int(curves_per_launch)
+        if not 1 <= curves_per_launch <= 16:
+            raise ValueError("curves_per_launch must be in [1, 16], got %d" % curves_per_launch)
+    elif curves_per_launch != 1:
+        raise ValueError("curves_per_launch goes with cut_budget")
     if cut_levels is not None:
         if sse_cut is not None:
             raise ValueError("cut_levels and sse_cut exclude each other")
         cut_levels = np.asarray(cut_levels, dtype=np.float64)
-    if sse_cut is not None or cut_levels is not None:
-        word = "sse_cut" if sse_cut is not None else "cut_levels"
+    if sse_cut is not None or cut_levels is not None or cut_budget is not None:
+        word = "sse_cut" if sse_cut is not None else "cut_levels" if cut_levels is not None else "cut_budget"
         for name, on in (("mag_grid", mag_grid is not None), ("mag_profile", bool(mag_profile)), ("weights", weights is not None),
                          ("devices", devices is not None), ("bundle", int(bundle) != 1)):
             if on:
@@ -246,6 +262,11 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
         if not np.all(cut_levels >= 0.0):
             raise ValueError("cut_levels must be >= 0 or +inf everywhere")
         cut_levels = np.ascontiguousarray(np.broadcast_to(cut_levels, (Cn, S)))
+    if cut_budget is not None:
+        if cut_budget.shape != (S,):
+            raise ValueError("cut_budget must have shape (S,) = (%d,), got %r" % (S, cut_budget.shape))
+        if not np.all(cut_budget >= 0.0):
+            raise ValueError("cut_budget must be >= 0 or +inf everywhere")
     if P is None:
         P = np.zeros(S)
     if not (P.dtype == np.float64 and P.flags.c_contiguous and P.shape == (S,)):
@@ -260,10 +281,10 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
         | _abi.flag_bdf_order(bdf_order) | int(extra_flags) | (_abi.FLAG_PREDICT if predict else 0)
     sec = _abi.C.c_double(0.0)
     lib = _abi.lib()
-    levels = cut_levels is not None
-    weighted, cut, multi, off = weights is not None, sse_cut is not None or levels, devices is not None, times is not None
+    levels, budget = cut_levels is not None, cut_budget is not None
+    weighted, cut, multi, off = weights is not None, sse_cut is not None or levels or budget, devices is not None, times is not None
     entry = "trpl_loglik_weighted" if weighted else "trpl_loglik_moments" if moments else "trpl_loglik_cut_levels" if levels \
-        else "trpl_loglik_cut" if cut \
+        else "trpl_loglik_cut_budget" if budget else "trpl_loglik_cut" if cut \
         else "trpl_loglik_multi" if multi else "trpl_loglik_obs" if off else "trpl_loglik"
     own = {}                                       # the entry point's own outputs, as info receives them
     if weighted or moments:
@@ -273,6 +294,8 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
         own["wsum"] = wsum = np.array([math.fsum(w_mat[c, :n_obs[c]]) for c in range(Cn)])
     if cut:
         own["cut_col"] = cut_col = np.full((Cn, S), -1, dtype=np.int32)
+    if budget:
+        own["cut_level"] = level_out = np.full((Cn, S), np.inf)
     if multi:
         dev = None if isinstance(devices, str) else np.ascontiguousarray(devices, dtype=np.int32)
         if isinstance(devices, str) and devices != "all":
@@ -280,18 +303,23 @@ def loglik(X, init_params, lengths, Time, L, T, obs, tol=7, MAX=10000, plT=1, P=
         if dev is not None and (dev.ndim != 1 or len(dev) < 1):
             raise ValueError("devices must name at least one device")
     # The call, built once; an entry point's own arguments sit where include/trpl.h puts them: no plT in trpl_loglik_obs, wts
-    # after obs, no brackets in trpl_loglik, sse_cut (or cut_level) before P, esum or cut_col after sse, the device list for the device.
+    # after obs, no brackets in trpl_loglik, sse_cut (or cut_level; or budget, curves_per_launch and the cut_level to fill) before P,
+    # esum or cut_col after sse, the device list for the device.
     head = [_abi.ptr(X), S, Cn, _abi.ptr(lengths), float(Time), int(L), int(T)] \
         + ([] if entry == "trpl_loglik_obs" else [int(plT)]) + [int(tol), int(MAX), _abi.ptr(ini)]
     brackets = [_abi.ptr(hi_mat), _abi.ptr(dx_mat), _abi.ptr(h_mat)] if off else [None, None, None]
     observed = [_abi.ptr(obs_mat)] + ([_abi.ptr(w_mat)] if weighted else []) + ([] if entry == "trpl_loglik" else brackets) \
         + [obs_ld, _abi.ptr(n_obs)]
-    outputs = ([_abi.ptr(cut_levels) if levels else sse_cut] if cut else []) + [_abi.ptr(P), _abi.ptr(sse)] + ([_abi.ptr(esum)] if "esum" in own else []) \
+    level_args = [_abi.ptr(cut_budget), curves_per_launch, _abi.ptr(level_out)] if budget else [_abi.ptr(cut_levels)] if levels \
+        else [sse_cut] if cut else []
+    outputs = level_args + [_abi.ptr(P), _abi.ptr(sse)] + ([_abi.ptr(esum)] if "esum" in own else []) \
         + ([_abi.ptr(cut_col)] if cut else []) + [_abi.ptr(status), _abi.ptr(iters), _abi.ptr(floor_col)]
     tail = [flags] + ([_abi.ptr(dev), 0 if dev is None else len(dev)] if multi else [int(device)]) + [_abi.C.byref(sec)]
     _abi.check(getattr(lib, entry)(*head, *observed, *outputs, *tail))
     if cut:
         own["cut_fraction"] = float(np.mean(cut_col >= 0)) if cut_col.size else 0.0
+    if budget:
+        own["cut_samples"] = float(np.mean((cut_col >= 0).any(axis=0))) if cut_col.size else 0.0
     if info is not None:
         info.update(sse=sse, status=status, iters_total=iters, floor_col=floor_col, seconds=sec.value, **own)
     if not moments:
@@ -436,8 +464,14 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
     sse_cut = next_cut(margin, smallest sum_c sse over all finished samples).  A cut sample's P is an upper bound of its
     likelihood, at least `margin` below the best finished sample's; with margin = posterior.exact_cut_margin(tf) (and P
     starting from equal values, as bayes() does) the posterior weights at that tf equal the uncut run's.
-    gpu_info['cut_log'], if a list, receives one dict per block (sse_cut, cut_fraction, iters_total summed).  Anything but
+    gpu_info['cut_log'], if a list, receives one dict per block (sse_cut, cut_fraction, cut_samples -- the share of the block's samples
+    with any cut system -- and iters_total summed).  Anything but
     the fused one-experiment level on one device is a ValueError naming the option.
+    gpu_info['cut_budget'] = True beside 'cut_margin' (default False): the same level is a level for a sample's TOTAL, so each later
+    block runs trpl_loglik_cut_budget with it as every sample's budget, spent across the curves in launches of
+    gpu_info['curves_per_launch'] (default 1) curves -- a sample stops once its curves together are past the level, not only when
+    one curve alone is.  A cut sample's total is at or above the level, which is all the paragraph above needs: the posterior
+    weights stay the uncut run's.  Without 'cut_margin' it is a ValueError.
     """
     group = int(gpu_info["sims_per_gpu"])
     num_gpus = int(gpu_info["num_gpus"])
@@ -484,6 +518,11 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
         if not fused:
             raise ValueError("gpu_info['cut_margin'] needs the fused level: gpu_info['fused'] = True, log_pl, PL stride 1 and "
                              "observation times inside the simulated window")
+    cut_budget = bool(gpu_info.get("cut_budget", False))
+    if cut_budget and cut_margin is None:
+        raise ValueError("gpu_info['cut_budget'] needs gpu_info['cut_margin']: the budget of a sample is margin + the best total so far")
+    if gpu_info.get("curves_per_launch") is not None and not cut_budget:
+        raise ValueError("gpu_info['curves_per_launch'] goes with gpu_info['cut_budget']")
     mag_grid = gpu_info.get("mag_grid")
     if mag_grid is not None:
         mag_grid = np.ascontiguousarray(mag_grid, dtype=np.float64).ravel()
@@ -528,9 +567,13 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
                     common["weights"] = [weights_from_uncertainty(exp[2][c]) for c in range(num_curves)]
                 if cut_margin is not None:         # one experiment, one device (checked above)
                     level = next_cut(cut_margin, best_total)
-                    loglik(*args, P=P[e, blk:blk + size], sse_cut=level, **common)
+                    if cut_budget:
+                        loglik(*args, P=P[e, blk:blk + size], cut_budget=np.full(size, level),
+                               curves_per_launch=int(gpu_info.get("curves_per_launch") or 1), **common)
+                    else:
+                        loglik(*args, P=P[e, blk:blk + size], sse_cut=level, **common)
                     solver_time[gpu_id] += info["seconds"]
-                    # a cut sample's reported total is above the level it was cut at, hence above the minimum so far:
+                    # a cut sample's reported total is at or above the level it was cut at, hence above the minimum so far:
                     # it never lowers it; NaN totals are skipped
                     total = info["sse"].sum(axis=0)
                     if np.any(total == total):
@@ -538,6 +581,7 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
                         best_total = low if best_total is None else min(best_total, low)
                     if isinstance(gpu_info.get("cut_log"), list):
                         gpu_info["cut_log"].append({"block": blk, "sse_cut": level, "cut_fraction": info["cut_fraction"],
+                                                    "cut_samples": float(np.mean((info["cut_col"] >= 0).any(axis=0))),
                                                     "iters_total": int(info["iters_total"].sum())})
                     continue
                 if mag_grid is not None:

@@ -499,6 +499,13 @@ def _prior_args(prior, A):
     return mean, sd
 
 
+def _early_reject_arg(early_reject):
+    """run's early_reject: False, True (a level per system, cut_levels) or "sample" (the level as the sample's budget, cut_budget)."""
+    if not (early_reject is False or early_reject is True or (isinstance(early_reject, str) and early_reject == "sample")):
+        raise ValueError("early_reject must be False, True or \"sample\", got %r" % (early_reject,))
+    return early_reject
+
+
 def _active(lo, hi, sim_flags):
     A = refine.active_columns(lo, hi, sim_flags).size
     if not 1 <= A <= _abi.REFINE_MAX_DIMS:
@@ -518,6 +525,7 @@ def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jum
     -inf is not solved and counts as outside.  With neither, the calls are exactly the ones above."""
     lo, hi, lg = box
     hastings = kind == "stretch" or prior is not None
+    level_kw = "cut_budget" if early_reject == "sample" else "cut_levels"       # the level is per system, or the sample's budget
     K = 1 if ladder is None else ladder.size
     half, A = U.shape[0] // 2, U.shape[1]
     g, C = half // K, 2 * half // K
@@ -565,7 +573,7 @@ def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jum
                     levels = np.maximum(reject_levels_h(LL[a:b], hh, ladder_h, a, seed, step, device=device), 0.0)
                 else:
                     levels = levels_of(LL[a:b], temper, a, seed, step, device=device)
-                LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok]), cut_levels=levels[ok]))
+                LLp[ok] = _f64(loglik(np.ascontiguousarray(Xp[ok]), **{level_kw: levels[ok]}))
                 levelled += per_rung(ok & np.isfinite(levels))
                 solved += per_rung(ok)
             elif ok.any():
@@ -624,11 +632,18 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
     the returned Chains are bit for bit those of the run without it: a cut proposal is one that run rejects.  info then also
     receives early_reject, the share of solved proposals that were given a finite level.
 
+    early_reject="sample": the same levels, passed as loglik(Xp[ok], cut_budget=levels[ok]) -- the level is one for the proposal's
+    summed sse, so it is spent across the curves (trpl_loglik_cut_budget; the callable chooses curves_per_launch) instead of being
+    given to each curve whole: a proposal stops once its curves together decide its rejection.  A cut proposal's total is at or
+    above its level, which accept rejects, so the Chains are again those of the run without it, bit for bit.  Any other value than
+    False, True or "sample" is a ValueError.
+
     The history of n kept sweeps takes n C (A + ncol + 1) 8 + n C bytes; a run whose history would exceed max_history_bytes raises
     ValueError before anything is solved.  ValueError for an odd C or C < 4, or a bounds that is neither string.  info receives
     accept (the share of chains that moved, per sweep), outside (the share of all proposals that were not solved: those that left
     the cube, or under bounds="fold" the non-finite ones, normally 0.0) and folded (the share of all proposals that were reflected
     back: 0.0 under bounds="reject")."""
+    early_reject = _early_reject_arg(early_reject)
     X, LL = np.array(X0, dtype=np.float64, order="C"), np.array(LL0, dtype=np.float64, order="C")
     lo, hi, lg = _box(minX, maxX, do_log)
     if X.ndim != 2 or X.shape[1] != lo.size or LL.shape != (X.shape[0],):
@@ -701,6 +716,7 @@ def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sw
     count as a move.  The history takes n K C (A + ncol + 1) 8 + n K C bytes and is refused above max_history_bytes before anything
     is solved.  info receives run's keys per rung -- accept (sweeps, K), outside (K,), folded (K,), early_reject (K,) -- and
     swap_rate (K - 1,)."""
+    early_reject = _early_reject_arg(early_reject)
     ladder = np.array(ladder, dtype=np.float64, order="C")
     if ladder.ndim != 1 or not 1 <= ladder.size <= _abi.MCMC_MAX_RUNGS:
         raise ValueError("ladder must be (K,), 1 <= K <= %d temperatures" % _abi.MCMC_MAX_RUNGS)

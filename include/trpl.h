@@ -668,7 +668,70 @@ int trpl_loglik_cut_levels_dev(const double *X, int64_t S, int32_t C, const doub
                                uint32_t flags, void *stream);
 
 /* ---------------------------------------------------------------------------------------
- * trpl_loglik_multi -- trpl_loglik / trpl_loglik_obs over several devices from ONE host thread:
+ * trpl_loglik_cut_budget -- the early stop on a SAMPLE'S TOTAL: a budget carried across the curves.  trpl_loglik_cut[_levels] test
+ * each (curve, sample) system on its own, although the levels their callers have (a Metropolis step's, margin + best total) are
+ * levels for the sample's SUMMED squared error: a sample whose error is spread evenly over C curves runs to about C times the level
+ * before one system stops.  This call spends one level per sample across its curves.  The arguments of trpl_loglik_cut_levels[_dev]
+ * with
+ *   budget             [S] f64, the level for sum_c sse[c][s], where cut_level is;
+ *   curves_per_launch  g, 1 <= g <= TRPL_MAX_CURVES, directly after it;
+ *   cut_level          [C][S] f64 OUT, directly before P: the level every system ran at.
+ * TRPL_FLAG_CUT is set by the call; the steppers (the same 20 trpl::cut:: instantiations), flags, combinations and refusals are
+ * trpl_loglik_cut's.  No stepper and no sink is changed: the only new kernel is trpl::budget::level_kernel (csrc/cut_budget.hip).
+ * THE RULE.  The C curves run as consecutive launches of g curves each (the last one possibly ragged), on the same stream, in curve
+ * order; the stepper variant is pinned once from the whole batch (as for C > TRPL_MAX_CURVES), so a system's bits do not depend on
+ * g.  Before launch j, whose first curve is c0 = j g, one thread per sample forms the level that all curves of that launch run at,
+ * from B = budget[s] and the REPORTED sse of the curves 0 .. c0 - 1, and writes it into the rows c0 .. c0 + g - 1 of cut_level:
+ *   R = the sum of sse[c][s], c = 0 .. c0 - 1 in ascending order from +0.0, one rounding per addition (the unit is built with
+ *       -ffp-contract=off): minus what the reduction over the curves makes of a P that starts at zero;
+ *   launch 0:    level = B itself (nothing is carried yet; B = 0 cuts every system with a non-zero error after its first batch);
+ *   B or R NaN:  level = +inf, in launch 0 too (the sample is never cut; the host form refuses a NaN budget, the _dev form cannot look);
+ *   B = +inf:    level = +inf, whatever R;
+ *   R >= B:      level = -1.0 -- the sample is already past its budget, and the sink cuts its later systems after their first
+ *                64-column batch, as trpl_loglik_cut_levels_dev says a negative level does;
+ *   otherwise the candidates are l0 = max(fl(B - R), 0), nextafter(l0, +inf) and nextafter of that: the first l with
+ *                fl(R + l) >= B is the level; if none verifies, +inf.
+ * For B > 0 launch 0's level is also what the rule gives at R = +0.0; with g >= C the call is trpl_loglik_cut_levels with budget[s] as the level
+ * of every curve of sample s, and budget = +inf everywhere gives the plain call with cut_col = -1.
+ * WHAT IS REPORTED.  Every output of system (c, s) is, bit for bit, what trpl_loglik_cut_levels_dev reports for it at the returned
+ * cut_level[c][s]; P[s] -= sum_c sse[c][s] over the reported values, as in trpl_loglik_cut.  The results do not depend on
+ * sharding, pairing rule or seam form (a sample's levels are formed from its own rows only).
+ * WHY THAT IS SAFE.  Floating-point addition of non-negative terms is monotone: a <= a' and b <= b' give fl(a + b) <= fl(a' + b').
+ * A system cut at a level l >= 0 reports sse_c > l, and its plain sse_c (the sum never decreases) is above l too.  R is the
+ * reported total of the curves before it, at or below their plain total.  So for a sample with a cut system both the reported total
+ * and the plain call's total are  fl(.. fl(R + sse_c) ..) >= fl(R + l) >= B,  the last step being the test the rule made before it
+ * took l.  A level of -1.0 is only given when R >= B already, and every later term keeps the total there.  Hence: a sample with any
+ * cut_col >= 0 has a plain total >= budget[s], and its reported P is at or below P_in - budget[s] when P_in is +0.0.
+ * With budget = a level of trpl_mcmc_levels*, LLp = -total <= -level = q is rejected by trpl_mcmc_accept's own expression (the
+ * property stated there holds for every LLp <= q).  With budget = margin + best total, the posterior weight of a sample whose total
+ * is at or above it is exactly 0.0 (posterior.exact_cut_margin's argument uses <=).
+ * HOW TIGHT.  l is l0 or one of its two successors, so a sample stops once a later curve's running sse is above about B - R: with
+ * g = 1 the whole of what the earlier curves reported is spent.  WHAT IT COSTS.  g < C serialises the curves: C / g launches, each
+ * as long as its slowest uncut system, and each filling the device only from S g systems.  It pays where S is large or most
+ * samples die in their first curves, and loses on small batches (DESIGN.md has the measurements).
+ * Refused with TRPL_ERR_ARG: budget or cut_level NULL with S > 0 ("budget must not be NULL", "cut_level must not be NULL");
+ * curves_per_launch outside [1, TRPL_MAX_CURVES]; host form only, before a device is touched: a NaN or negative budget[s], the
+ * message names the sample ("budget[s=..]").  The _dev form allocates nothing and never synchronises; a negative budget there cuts
+ * every system of the sample after its first batch.  The host form stages budget in and cut_level out.  There is no
+ * trpl_loglik_multi* form.  Python: trpl_amd.driver.loglik(cut_budget=, curves_per_launch=), trpl_amd.mcmc.run(early_reject="sample"),
+ * gpu_info["cut_budget"], trpl_amd.device.loglik_cut_budget_device.
+ * ------------------------------------------------------------------------------------- */
+int trpl_loglik_cut_budget(const double *X, int64_t S, int32_t C, const double *lengths_nm, double time_ns,
+                           int32_t L, int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
+                           const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                           int64_t obs_ld, const int64_t *n_obs, const double *budget /* [S] */, int32_t curves_per_launch,
+                           double *cut_level /* [C][S] out */, double *P, double *sse, int32_t *cut_col, int32_t *status,
+                           int64_t *iters_total, int32_t *floor_col, uint32_t flags, int32_t device, double *seconds);
+int trpl_loglik_cut_budget_dev(const double *X, int64_t S, int32_t C, const double *lengths_nm /*host*/, double time_ns,
+                               int32_t L, int64_t T, int32_t plT, int32_t tol_exp, int32_t max_iter, const double *dN,
+                               const double *obs, const int32_t *obs_hi, const double *obs_dx, const double *obs_h,
+                               int64_t obs_ld, const int64_t *n_obs /*host*/, const double *budget /* [S] */,
+                               int32_t curves_per_launch, double *cut_level /* [C][S] out */, double *P, double *sse,
+                               int32_t *cut_col, int32_t *status, int64_t *iters_total, int32_t *floor_col, uint32_t flags,
+                               void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * trpl_loglik_multi --trpl_loglik / trpl_loglik_obs over several devices from ONE host thread:
  * replaces the reference's distribution of 1024-sample blocks over GPUs (bayeslib.py:131 and the
  * commented-out threaded driver :235-246; one SLURM array task per GPU, :231).  The samples are cut
  * into n_devices contiguous shards (trpl_shard_bounds); every shard is staged, solved and copied back

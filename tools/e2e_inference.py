@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject] [--tempered K [--tf-hot x]]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject [sample]] [--tempered K [--tf-hot x]]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -43,7 +43,8 @@ sum (the ESS is then an upper bound) and the Monte-Carlo error of the mean in un
 --early-reject (with --mcmc) stops solving a proposal once its rejection is certain (mcmc.run(early_reject=True): DESIGN.md section
 26; the chain is the same, bit for bit) and adds "early_reject" to "mcmc": the share of solved proposals that were cut and the
 system-timesteps solved.  With or without it "mcmc" holds "system_timesteps", the solver iterations summed over every proposal, and
-the same numbers are printed.
+the same numbers are printed.  --early-reject sample spends each proposal's level as a budget across its curves instead
+(mcmc.run(early_reject="sample"), trpl_loglik_cut_budget with one curve per launch; --curves-per-launch g for another grouping).
 --tempered K (with --mcmc; composes with --fold and --early-reject) runs parallel tempering instead (mcmc.run_tempered: DESIGN.md section
 27): K rungs of C chains each on mcmc.geometric_ladder(tf, tf_hot, K), every half-sweep still one call of the fused likelihood.
 --tf-hot x sets the hottest temperature; the default is the temperature at which the importance run reaches an effective sample
@@ -84,6 +85,14 @@ if "--shrink" in sys.argv:
 MCMC = "--mcmc" in sys.argv
 FOLD = "--fold" in sys.argv
 EARLY = "--early-reject" in sys.argv
+if EARLY and sys.argv.index("--early-reject") + 1 < len(sys.argv) and sys.argv[sys.argv.index("--early-reject") + 1] == "sample":
+    del sys.argv[sys.argv.index("--early-reject") + 1]
+    EARLY = "sample"
+CURVES_PER_LAUNCH = 1
+if "--curves-per-launch" in sys.argv:
+    k = sys.argv.index("--curves-per-launch")
+    CURVES_PER_LAUNCH = int(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
 CHAINS, SWEEPS, RW, TEMPERED, TF_HOT = 1024, 200, None, 0, None
 for flag, conv in (("--chains", int), ("--sweeps", int), ("--rw", float), ("--tempered", int), ("--tf-hot", float)):
     if flag in sys.argv:
@@ -286,13 +295,20 @@ if MCMC:
 
     work = {"iters": 0, "cut": 0, "solved": 0}
 
-    def fused_chain(X2, cut_levels=None):                        # the fused likelihood of the proposals of one half-sweep
+    def fused_chain(X2, cut_levels=None, cut_budget=None):                        # the fused likelihood of the proposals of one half-sweep
         n = X2.shape[0]
         Xd = torch.from_numpy(np.ascontiguousarray(X2)).to(dev)
         P2 = torch.zeros(n, dtype=torch.float64, device=dev)         # from zero: what early rejection's levels assume
         sse2 = torch.empty((C, n), dtype=torch.float64, device=dev)
         it2 = torch.empty((C, n), dtype=torch.int64, device=dev)
-        if cut_levels is None:
+        if cut_budget is not None:                               # one level per proposal, spent across its curves
+            bd = torch.from_numpy(np.ascontiguousarray(cut_budget)).to(dev)
+            lv = torch.empty((C, n), dtype=torch.float64, device=dev)
+            cc = torch.empty((C, n), dtype=torch.int32, device=dev)
+            tdev.loglik_cut_budget_device(Xd, ini_d, lens, T * dt, L, T, obs, [T + 1] * C, bd, lv, P2, sse2, curves_per_launch=CURVES_PER_LAUNCH,
+                                          cut_col=cc, iters_total=it2)
+            work["cut"] += int((cc >= 0).any(dim=0).sum())
+        elif cut_levels is None:
             tdev.loglik_device(Xd, ini_d, lens, T * dt, L, T, obs, [T + 1] * C, P2, sse2, iters_total=it2)
         else:                                                    # one level per proposal, given to each of its curves
             lv = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(cut_levels, (C, n)))).to(dev)
@@ -317,7 +333,7 @@ if MCMC:
             centre[i], width[i] = c0 * sm.UNIT_CONVERSIONS[i], w0 if lg[i] else w0 * sm.UNIT_CONVERSIONS[i]
         hastings.update(prior=mcmc.gaussian_prior(centre, width, lo, hi, lg))
     opts = dict(sweeps=SWEEPS, seed=42, burn=burn, info=minfo, U0=U0, **({"kind": "rw", "scale": RW} if RW is not None else {}), **hastings,
-                **({"bounds": "fold"} if FOLD else {}), **({"early_reject": True} if EARLY else {}))
+                **({"bounds": "fold"} if FOLD else {}), **({"early_reject": EARLY} if EARLY else {}))
     if TEMPERED:
         hot_ess = None
         if TF_HOT is None:                                       # hot enough for the importance run to hold 64 effective samples
