@@ -29,18 +29,23 @@
 //   propose_rungs_kernel<A>, propose_rungs_fold_kernel<A>   propose_body with the partners of chain i narrowed to the rows
 //       [(i / group) group, + group) of `partners` and P = group in the index expressions: a rung's slice is propose_kernel's bits.
 //   accept_rungs_kernel<A>, levels_rungs_kernel   accept_body and levels_body with tf = ladder[i / group]; the ladder travels by value.
+//   hastings_accept_kernel<A>, hastings_levels_kernel   (trpl_mcmc_accept_h*, trpl_mcmc_levels_h*) the same
+//       two bodies with H = true, an untempered log term h[i] per chain: d = (LLp - LL) / tf[i / group] + h[i], and the level that goes
+//       with that d.  At h = +-0.0 they give the rung kernels' bits: the quotient is the same source line, and the sum changes no value
+//       but -0.0, which no comparison sees.  What produces h, the stretch move and the prior term, is mcmc_hastings.hip.
 //   swap_kernel<A>        one thread per row of the block; the thread of the lower row a of a pair (k, k + 1), k = parity, parity + 2, ..,
 //       decides it: xi of counter word 0x10a keyed by row a, d = (LL[b] - LL[a]) * (1 / tf[k] - 1 / tf[k + 1]), the rows of U, X and LL
 //       exchanged when neither LL is NaN and d >= 0 or log(xi) < d.  The thread of an upper row writes nothing; an unpaired row's
 //       writes swapped = 0 only.
 // The host half, after the kernels.  Propose, accept, levels and swap have one argument record each (ProposeCall, AcceptCall,
 // LevelsCall, SwapCall: the entry point's arguments in its order; `rungs` marks a *_rungs call, whose group, K and ladder are read
-// only then) and three functions on it: check (every refusal of the operation, in the order the entry points have always had; it
-// makes the kernel arguments Scale, Box, Ladder), launch (the kernel of the record, on a stream) and stage (the record's buffers
-// through a Staged).  on_stream is every _dev form: check, launch.  staged is every host-buffer form: check before a device is
-// opened, stage, launch -- the record is checked once.  An extern "C" entry point fills a record and returns one of the two.  A new
-// argument goes into the record, its refusal into check, its buffer into stage; a new operation is a record with these three.
-// on_stream and staged, the shared checks and the Philox call indices are mcmc_common.hpp's, shared with mcmc_hastings.hip.
+// only then, `with_h` a *_h call, a rung call whose h is read only then) and three functions on it: check (every refusal of the
+// operation, for each of its forms in the order the entry points have always had; it makes the kernel arguments Scale, Box, Ladder),
+// launch (the kernel of the record, on a stream) and stage (the record's buffers through a Staged).  on_stream is every _dev form:
+// check, launch.  staged is every host-buffer form: check before a device is opened, stage, launch -- the record is checked once.  An
+// extern "C" entry point fills a record and returns one of the two.  A new argument goes into the record, its refusal into check, its
+// buffer into stage; a new operation is a record with these three.  on_stream and staged, the shared checks and the Philox call
+// indices are mcmc_common.hpp's, shared with mcmc_hastings.hip, which has the stretch move and the prior term in the same structure.
 // chain_stats and the autocovariance calls are a kernel or two each and stay written out; their refusals share check_history.
 // Compiled with -ffp-contract=off like refine.hip: every result is its expression with one rounding per operation.
 #include <hip/hip_runtime.h>
@@ -164,9 +169,12 @@ __global__ void __launch_bounds__(kThreads) propose_rungs_fold_kernel(TRPL_PROPO
 #undef TRPL_PROPOSE_PARAMS
 #undef TRPL_PROPOSE_ARGS
 
-template <int A>
+// The accept step of all three forms.  H: the call has a Hastings term (include/trpl.h, trpl_mcmc_accept_h), an untempered h[i] added
+// to d; a proposal whose term is NaN or -inf is not taken.  Without it h is not read and d is the quotient alone.  tf() gives the
+// chain's temperature where d is formed.
+template <int A, bool H, class TF>
 __device__ __forceinline__ void accept_body(int64_t i, double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp,
-                                            const int32_t *inside, int32_t ncol, double tf, int64_t chain0, uint32_t seed_lo,
+                                            const int32_t *inside, const double *h, int32_t ncol, TF tf, int64_t chain0, uint32_t seed_lo,
                                             uint32_t seed_hi, uint32_t step, int32_t *accepted)
 {
     const uint64_t n = (uint64_t)(chain0 + i);
@@ -174,8 +182,12 @@ __device__ __forceinline__ void accept_body(int64_t i, double *U, double *X, dou
     philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), kStream + kAcceptCall, step, seed_lo, seed_hi, r);
     const double xi = res53(r[0], r[1]);
     const double ll = LL[i], llp = LLp[i];
-    const double d = (llp - ll) / tf;
-    const bool take = inside[i] != 0 && !(llp != llp) && llp > -INFINITY && (!(ll > -INFINITY) || d >= 0.0 || log(xi) < d);
+    double hv = 0.0;
+    if constexpr (H) hv = h[i];
+    const double d0 = (llp - ll) / tf();
+    const double d = H ? d0 + hv : d0;
+    const bool take = inside[i] != 0 && !(llp != llp) && llp > -INFINITY && (!H || (!(hv != hv) && hv > -INFINITY)) &&
+                      (!(ll > -INFINITY) || d >= 0.0 || log(xi) < d);
     accepted[i] = take ? 1 : 0;
     if (!take) return;
 #pragma unroll
@@ -187,14 +199,14 @@ __device__ __forceinline__ void accept_body(int64_t i, double *U, double *X, dou
 #define TRPL_ACCEPT_PARAMS(tf_type)                                                                                                    \
     double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside, int64_t count,        \
         int32_t ncol, tf_type tf, int64_t chain0, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, int32_t *accepted
-#define TRPL_ACCEPT_ARGS(tf) i, U, X, LL, Up, Xp, LLp, inside, ncol, tf, chain0, seed_lo, seed_hi, step, accepted
+#define TRPL_ACCEPT_ARGS(h, tf) i, U, X, LL, Up, Xp, LLp, inside, h, ncol, tf, chain0, seed_lo, seed_hi, step, accepted
 
 template <int A>
 __global__ void __launch_bounds__(kThreads) accept_kernel(TRPL_ACCEPT_PARAMS(double))
 {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= count) return;
-    accept_body<A>(TRPL_ACCEPT_ARGS(tf));
+    accept_body<A, false>(TRPL_ACCEPT_ARGS(nullptr, [tf] { return tf; }));
 }
 
 template <int A>
@@ -202,7 +214,19 @@ __global__ void __launch_bounds__(kThreads) accept_rungs_kernel(TRPL_ACCEPT_PARA
 {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= count) return;
-    accept_body<A>(TRPL_ACCEPT_ARGS(tf.tf[i / group]));
+    const double t = tf.tf[i / group];
+    accept_body<A, false>(TRPL_ACCEPT_ARGS(nullptr, [t] { return t; }));
+}
+
+template <int A>
+__global__ void __launch_bounds__(kThreads) hastings_accept_kernel(double *U, double *X, double *LL, const double *Up, const double *Xp,
+                                                                   const double *LLp, const int32_t *inside, const double *h, int64_t count,
+                                                                   int32_t ncol, const Ladder tf, int64_t group, int64_t chain0,
+                                                                   uint32_t seed_lo, uint32_t seed_hi, uint32_t step, int32_t *accepted)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= count) return;
+    accept_body<A, true>(TRPL_ACCEPT_ARGS(h, [&] { return tf.tf[i / group]; }));
 }
 
 #undef TRPL_ACCEPT_PARAMS
@@ -210,23 +234,32 @@ __global__ void __launch_bounds__(kThreads) accept_rungs_kernel(TRPL_ACCEPT_PARA
 
 // Early rejection (include/trpl.h, trpl_mcmc_levels): a candidate level l is taken only if the accept step's own d, formed for a proposal
 // with LLp = -l, is negative and not above log(xi) -- then every LLp <= -l has a d no larger (subtraction and division by tf > 0 are
-// monotone) and accept_kernel rejects it with the same (seed, chain, step).
-__device__ __forceinline__ void levels_body(int64_t i, const double *LL, double tf, int64_t chain0, uint32_t seed_lo, uint32_t seed_hi,
-                                            uint32_t step, double *level)
+// monotone) and the accept kernel rejects it with the same (seed, chain, step).  The argument is per chain -- it never compares two
+// chains -- so it holds with a temperature per rung.  With a Hastings term (H; trpl_mcmc_levels_h) it survives the added constant:
+// every LLp <= -l has (LLp - LL) / tf <= (-l - LL) / tf as before, and adding the same h to both sides is monotone under
+// round-to-nearest, so d <= dq < 0 and log(xi) < d is false: hastings_accept_kernel rejects with the same (seed, chain, step, h).  The
+// level is +inf (never cut) where neither candidate is confirmed, and where h is NaN or infinite.
+template <bool H, class TF>
+__device__ __forceinline__ void levels_body(int64_t i, const double *LL, const double *h, TF tf, int64_t chain0, uint32_t seed_lo,
+                                            uint32_t seed_hi, uint32_t step, double *level)
 {
     const uint64_t n = (uint64_t)(chain0 + i);
     uint32_t r[4];
     philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), kStream + kAcceptCall, step, seed_lo, seed_hi, r);
     const double xi = res53(r[0], r[1]);
     const double ll = LL[i];
+    double hv = 0.0;
+    if constexpr (H) hv = h[i];
+    const double t = tf();
     double lv = INFINITY;
-    if (!(ll != ll) && ll > -INFINITY && xi != 0.0) {
+    if (!(ll != ll) && ll > -INFINITY && xi != 0.0 && (!H || (!(hv != hv) && fabs(hv) < INFINITY))) {
         const double lx = log(xi);
-        const double l0 = -(ll + tf * lx);
+        const double l0 = H ? -(ll + t * (lx - hv)) : -(ll + t * lx);
         double cand = l0;
         for (int k = 0; k < 2; k++) {
             const double q = -cand;
-            const double dq = (q - ll) / tf;
+            const double dq0 = (q - ll) / t;
+            const double dq = H ? dq0 + hv : dq0;
             if (dq < 0.0 && !(lx < dq)) { lv = cand; break; }
             cand = l0 + (fabs(ll) + l0) * 0x1p-40;
         }
@@ -239,17 +272,26 @@ __global__ void __launch_bounds__(kThreads) levels_kernel(const double *LL, int6
 {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= count) return;
-    levels_body(i, LL, tf, chain0, seed_lo, seed_hi, step, level);
+    levels_body<false>(i, LL, nullptr, [tf] { return tf; }, chain0, seed_lo, seed_hi, step, level);
 }
 
-// The safety argument above is per chain -- it never compares two chains -- so it holds with a temperature per rung.
 __global__ void __launch_bounds__(kThreads) levels_rungs_kernel(const double *LL, int64_t count, const Ladder tf, int64_t group,
                                                                 int64_t chain0, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
                                                                 double *level)
 {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= count) return;
-    levels_body(i, LL, tf.tf[i / group], chain0, seed_lo, seed_hi, step, level);
+    const double t = tf.tf[i / group];
+    levels_body<false>(i, LL, nullptr, [t] { return t; }, chain0, seed_lo, seed_hi, step, level);
+}
+
+__global__ void __launch_bounds__(kThreads) hastings_levels_kernel(const double *LL, const double *h, int64_t count, const Ladder tf,
+                                                                   int64_t group, int64_t chain0, uint32_t seed_lo, uint32_t seed_hi,
+                                                                   uint32_t step, double *level)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= count) return;
+    levels_body<true>(i, LL, h, [&] { return tf.tf[i / group]; }, chain0, seed_lo, seed_hi, step, level);
 }
 
 // Replica exchange (include/trpl.h, trpl_mcmc_swap): count = K group rows.  Row i belongs to rung k = i / group; it is the lower row of a
@@ -408,7 +450,8 @@ using namespace trpl;
 namespace {                                                      // the host half: the file comment has its structure
 
 // ---- the records: an entry point's arguments in its order, then what check() makes of them for the kernel.  rungs marks a *_rungs
-// call: group, K and ladder are read only then, and tf only without.
+// call: group, K and ladder are read only then, and tf only without.  with_h marks a *_h call, which is a rung call (K = 1: one
+// temperature): h is read only then.
 struct ProposeCall {
     const double *U, *partners; int64_t count, P; bool rungs; int64_t group; int32_t A; double gamma; const double *scale;
     int64_t chain0; uint64_t seed; uint32_t step; int32_t ncol; const double *lo, *hi; const int32_t *do_log; uint32_t flags;
@@ -416,13 +459,13 @@ struct ProposeCall {
     mcmc::Scale sc = {}; refine::Box bx = {};
 };
 struct AcceptCall {
-    double *U, *X, *LL; const double *Up, *Xp, *LLp; const int32_t *inside; int64_t count; int32_t A, ncol; double tf; bool rungs;
-    int32_t K; int64_t group; const double *ladder; int64_t chain0; uint64_t seed; uint32_t step; int32_t *accepted;
+    double *U, *X, *LL; const double *Up, *Xp, *LLp; const int32_t *inside; const double *h; int64_t count; int32_t A, ncol; double tf;
+    bool rungs, with_h; int32_t K; int64_t group; const double *ladder; int64_t chain0; uint64_t seed; uint32_t step; int32_t *accepted;
     mcmc::Ladder lad = {};
 };
 struct LevelsCall {
-    const double *LL; int64_t count; double tf; bool rungs; int32_t K; int64_t group; const double *ladder; int64_t chain0; uint64_t seed;
-    uint32_t step; double *level;
+    const double *LL, *h; int64_t count; double tf; bool rungs, with_h; int32_t K; int64_t group; const double *ladder; int64_t chain0;
+    uint64_t seed; uint32_t step; double *level;
     mcmc::Ladder lad = {};
 };
 struct SwapCall {                                                // count: K group, the rows of one block; check() sets it
@@ -461,9 +504,10 @@ int check(AcceptCall &k)
     if (int rc = check_chains(k.count, k.A, k.chain0)) return rc;
     if (k.ncol < 1 || k.ncol > 16) return api_fail(TRPL_ERR_ARG, "ncol=%d must be in [1, 16]", k.ncol);
     if (!(isfinite(k.tf) && k.tf > 0.0)) return api_fail(TRPL_ERR_ARG, "tf=%g must be finite and > 0", k.tf);
-    if (int rc = check_not_null({{"U", k.U}, {"X", k.X}, {"LL", k.LL}, {"Up", k.Up}, {"Xp", k.Xp}, {"LLp", k.LLp}, {"inside", k.inside},
-                                 {"accepted", k.accepted}}))
+    if (int rc = check_not_null({{"U", k.U}, {"X", k.X}, {"LL", k.LL}, {"Up", k.Up}, {"Xp", k.Xp}, {"LLp", k.LLp}, {"inside", k.inside}}))
         return rc;
+    if (k.with_h && !k.h) return api_fail(TRPL_ERR_ARG, "h is NULL");
+    if (int rc = check_not_null({{"accepted", k.accepted}})) return rc;
     if (k.rungs && k.count != (int64_t)k.K * k.group)
         return api_fail(TRPL_ERR_ARG, "count=%lld must be K * group = %d * %lld", (long long)k.count, k.K, (long long)k.group);
     return TRPL_OK;
@@ -478,7 +522,9 @@ int check(LevelsCall &k)
     if (int rc = check_count(k.count)) return rc;
     if (!(isfinite(k.tf) && k.tf > 0.0)) return api_fail(TRPL_ERR_ARG, "tf=%g must be finite and > 0", k.tf);
     if (k.chain0 < 0) return api_fail(TRPL_ERR_ARG, "chain0=%lld must be >= 0", (long long)k.chain0);
-    if (int rc = check_not_null({{"LL", k.LL}, {"level", k.level}})) return rc;
+    if (int rc = check_not_null({{"LL", k.LL}})) return rc;
+    if (k.with_h && !k.h) return api_fail(TRPL_ERR_ARG, "h is NULL");
+    if (int rc = check_not_null({{"level", k.level}})) return rc;
     if (k.rungs && k.count != (int64_t)k.K * k.group)
         return api_fail(TRPL_ERR_ARG, "count=%lld must be K * group = %d * %lld", (long long)k.count, k.K, (long long)k.group);
     return TRPL_OK;
@@ -494,51 +540,51 @@ int check(SwapCall &k)
     return check_not_null({{"U", k.U}, {"X", k.X}, {"LL", k.LL}, {"swapped", k.swapped}});
 }
 
-// ---- launch: the kernel of a checked record on a stream, through TRPL_MCMC_LAUNCH (mcmc_common.hpp).  The functions keep the order the
-// code object has had, the single-temperature kernels before the rung kernels.
-int launch_propose(const ProposeCall &k, hipStream_t stream)
+// ---- launch: the kernel of a checked record on a stream, through TRPL_MCMC_LAUNCH (mcmc_common.hpp)
+int launch(const ProposeCall &k, hipStream_t stream)
 {
     const bool fold = (k.flags & TRPL_MCMC_FOLD) != 0;
+    if (k.rungs) {
+        TRPL_MCMC_LAUNCH(k.A, fold ? mcmc::propose_rungs_fold_kernel<n> : mcmc::propose_rungs_kernel<n>, k.count, stream, k.U, k.partners,
+                         k.count, k.P, k.gamma, k.sc, k.chain0, (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.step, k.bx, k.Up, k.Xp,
+                         k.inside, k.group)
+        return refine_launched("mcmc propose rungs");
+    }
     TRPL_MCMC_LAUNCH(k.A, fold ? mcmc::propose_fold_kernel<n> : mcmc::propose_kernel<n>, k.count, stream, k.U, k.partners, k.count, k.P,
                      k.gamma, k.sc, k.chain0, (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.step, k.bx, k.Up, k.Xp, k.inside)
     return refine_launched("mcmc propose");
 }
 
-int launch_accept(const AcceptCall &k, hipStream_t stream)
+int launch(const AcceptCall &k, hipStream_t stream)
 {
+    const uint32_t lo = (uint32_t)k.seed, hi = (uint32_t)(k.seed >> 32);
+    if (k.with_h) {
+        TRPL_MCMC_LAUNCH(k.A, mcmc::hastings_accept_kernel<n>, k.count, stream, k.U, k.X, k.LL, k.Up, k.Xp, k.LLp, k.inside, k.h, k.count,
+                         k.ncol, k.lad, k.group, k.chain0, lo, hi, k.step, k.accepted)
+        return refine_launched("mcmc accept h");
+    }
+    if (k.rungs) {
+        TRPL_MCMC_LAUNCH(k.A, mcmc::accept_rungs_kernel<n>, k.count, stream, k.U, k.X, k.LL, k.Up, k.Xp, k.LLp, k.inside, k.count, k.ncol,
+                         k.lad, k.chain0, lo, hi, k.step, k.accepted, k.group)
+        return refine_launched("mcmc accept rungs");
+    }
     TRPL_MCMC_LAUNCH(k.A, mcmc::accept_kernel<n>, k.count, stream, k.U, k.X, k.LL, k.Up, k.Xp, k.LLp, k.inside, k.count, k.ncol, k.tf,
-                     k.chain0, (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.step, k.accepted)
+                     k.chain0, lo, hi, k.step, k.accepted)
     return refine_launched("mcmc accept");
 }
 
 int launch(const LevelsCall &k, hipStream_t stream)
 {
     const dim3 grid(refine_blocks(k.count)), block(refine::kThreads);
-    if (k.rungs)
-        hipLaunchKernelGGL(mcmc::levels_rungs_kernel, grid, block, 0, stream, k.LL, k.count, k.lad, k.group, k.chain0, (uint32_t)k.seed,
-                           (uint32_t)(k.seed >> 32), k.step, k.level);
+    const uint32_t lo = (uint32_t)k.seed, hi = (uint32_t)(k.seed >> 32);
+    if (k.with_h)
+        hipLaunchKernelGGL(mcmc::hastings_levels_kernel, grid, block, 0, stream, k.LL, k.h, k.count, k.lad, k.group, k.chain0, lo, hi, k.step,
+                           k.level);
+    else if (k.rungs)
+        hipLaunchKernelGGL(mcmc::levels_rungs_kernel, grid, block, 0, stream, k.LL, k.count, k.lad, k.group, k.chain0, lo, hi, k.step, k.level);
     else
-        hipLaunchKernelGGL(mcmc::levels_kernel, grid, block, 0, stream, k.LL, k.count, k.tf, k.chain0, (uint32_t)k.seed,
-                           (uint32_t)(k.seed >> 32), k.step, k.level);
-    return refine_launched(k.rungs ? "mcmc levels rungs" : "mcmc levels");
-}
-
-int launch(const ProposeCall &k, hipStream_t stream)
-{
-    if (!k.rungs) return launch_propose(k, stream);
-    const bool fold = (k.flags & TRPL_MCMC_FOLD) != 0;
-    TRPL_MCMC_LAUNCH(k.A, fold ? mcmc::propose_rungs_fold_kernel<n> : mcmc::propose_rungs_kernel<n>, k.count, stream, k.U, k.partners,
-                     k.count, k.P, k.gamma, k.sc, k.chain0, (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.step, k.bx, k.Up, k.Xp, k.inside,
-                     k.group)
-    return refine_launched("mcmc propose rungs");
-}
-
-int launch(const AcceptCall &k, hipStream_t stream)
-{
-    if (!k.rungs) return launch_accept(k, stream);
-    TRPL_MCMC_LAUNCH(k.A, mcmc::accept_rungs_kernel<n>, k.count, stream, k.U, k.X, k.LL, k.Up, k.Xp, k.LLp, k.inside, k.count, k.ncol, k.lad,
-                     k.chain0, (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.step, k.accepted, k.group)
-    return refine_launched("mcmc accept rungs");
+        hipLaunchKernelGGL(mcmc::levels_kernel, grid, block, 0, stream, k.LL, k.count, k.tf, k.chain0, lo, hi, k.step, k.level);
+    return refine_launched(k.with_h ? "mcmc levels h" : k.rungs ? "mcmc levels rungs" : "mcmc levels");
 }
 
 int launch(const SwapCall &k, hipStream_t stream)
@@ -562,10 +608,18 @@ void stage(AcceptCall &k, Staged &sg)
     const size_t n = (size_t)k.count;
     k.U = sg.inout(k.U, n * k.A); k.X = sg.inout(k.X, n * k.ncol); k.LL = sg.inout(k.LL, n);
     k.Up = sg.in(k.Up, n * k.A); k.Xp = sg.in(k.Xp, n * k.ncol); k.LLp = sg.in(k.LLp, n);
-    k.inside = sg.in(k.inside, n); k.accepted = sg.out(k.accepted, n);
+    k.inside = sg.in(k.inside, n);
+    if (k.with_h) k.h = sg.in(k.h, n);
+    k.accepted = sg.out(k.accepted, n);
 }
 
-void stage(LevelsCall &k, Staged &sg) { k.LL = sg.in(k.LL, (size_t)k.count); k.level = sg.out(k.level, (size_t)k.count); }
+void stage(LevelsCall &k, Staged &sg)
+{
+    const size_t n = (size_t)k.count;
+    k.LL = sg.in(k.LL, n);
+    if (k.with_h) k.h = sg.in(k.h, n);
+    k.level = sg.out(k.level, n);
+}
 
 void stage(SwapCall &k, Staged &sg)
 {
@@ -657,27 +711,28 @@ int trpl_mcmc_accept_dev(double *U, double *X, double *LL, const double *Up, con
                          int64_t count, int32_t A, int32_t ncol, double tf, int64_t chain0, uint64_t seed, uint32_t step,
                          int32_t *accepted, void *stream)
 {
-    return on_stream(AcceptCall{U, X, LL, Up, Xp, LLp, inside, count, A, ncol, tf, false, 0, 0, nullptr, chain0, seed, step, accepted}, stream);
+    return on_stream(AcceptCall{U, X, LL, Up, Xp, LLp, inside, nullptr, count, A, ncol, tf, false, false, 0, 0, nullptr, chain0, seed, step,
+                                accepted}, stream);
 }
 
 int trpl_mcmc_accept(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
                      int64_t count, int32_t A, int32_t ncol, double tf, int64_t chain0, uint64_t seed, uint32_t step, int32_t *accepted,
                      int32_t device, double *seconds)
 {
-    return staged(AcceptCall{U, X, LL, Up, Xp, LLp, inside, count, A, ncol, tf, false, 0, 0, nullptr, chain0, seed, step, accepted}, device,
-                  seconds);
+    return staged(AcceptCall{U, X, LL, Up, Xp, LLp, inside, nullptr, count, A, ncol, tf, false, false, 0, 0, nullptr, chain0, seed, step,
+                             accepted}, device, seconds);
 }
 
 int trpl_mcmc_levels_dev(const double *LL, int64_t count, double tf, int64_t chain0, uint64_t seed, uint32_t step, double *level,
                          void *stream)
 {
-    return on_stream(LevelsCall{LL, count, tf, false, 0, 0, nullptr, chain0, seed, step, level}, stream);
+    return on_stream(LevelsCall{LL, nullptr, count, tf, false, false, 0, 0, nullptr, chain0, seed, step, level}, stream);
 }
 
 int trpl_mcmc_levels(const double *LL, int64_t count, double tf, int64_t chain0, uint64_t seed, uint32_t step, double *level,
                      int32_t device, double *seconds)
 {
-    return staged(LevelsCall{LL, count, tf, false, 0, 0, nullptr, chain0, seed, step, level}, device, seconds);
+    return staged(LevelsCall{LL, nullptr, count, tf, false, false, 0, 0, nullptr, chain0, seed, step, level}, device, seconds);
 }
 
 int trpl_mcmc_propose_rungs_dev(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, int32_t A, double gamma,
@@ -701,27 +756,56 @@ int trpl_mcmc_accept_rungs_dev(double *U, double *X, double *LL, const double *U
                                const int32_t *inside, int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group, const double *tf,
                                int64_t chain0, uint64_t seed, uint32_t step, int32_t *accepted, void *stream)
 {
-    return on_stream(AcceptCall{U, X, LL, Up, Xp, LLp, inside, count, A, ncol, 0.0, true, K, group, tf, chain0, seed, step, accepted}, stream);
+    return on_stream(AcceptCall{U, X, LL, Up, Xp, LLp, inside, nullptr, count, A, ncol, 0.0, true, false, K, group, tf, chain0, seed, step,
+                                accepted}, stream);
 }
 
 int trpl_mcmc_accept_rungs(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
                            int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group, const double *tf, int64_t chain0,
                            uint64_t seed, uint32_t step, int32_t *accepted, int32_t device, double *seconds)
 {
-    return staged(AcceptCall{U, X, LL, Up, Xp, LLp, inside, count, A, ncol, 0.0, true, K, group, tf, chain0, seed, step, accepted}, device,
-                  seconds);
+    return staged(AcceptCall{U, X, LL, Up, Xp, LLp, inside, nullptr, count, A, ncol, 0.0, true, false, K, group, tf, chain0, seed, step,
+                             accepted}, device, seconds);
 }
 
 int trpl_mcmc_levels_rungs_dev(const double *LL, int64_t count, int32_t K, int64_t group, const double *tf, int64_t chain0, uint64_t seed,
                                uint32_t step, double *level, void *stream)
 {
-    return on_stream(LevelsCall{LL, count, 0.0, true, K, group, tf, chain0, seed, step, level}, stream);
+    return on_stream(LevelsCall{LL, nullptr, count, 0.0, true, false, K, group, tf, chain0, seed, step, level}, stream);
 }
 
 int trpl_mcmc_levels_rungs(const double *LL, int64_t count, int32_t K, int64_t group, const double *tf, int64_t chain0, uint64_t seed,
                            uint32_t step, double *level, int32_t device, double *seconds)
 {
-    return staged(LevelsCall{LL, count, 0.0, true, K, group, tf, chain0, seed, step, level}, device, seconds);
+    return staged(LevelsCall{LL, nullptr, count, 0.0, true, false, K, group, tf, chain0, seed, step, level}, device, seconds);
+}
+
+int trpl_mcmc_accept_h_dev(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
+                           const double *h, int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group, const double *tf,
+                           int64_t chain0, uint64_t seed, uint32_t step, int32_t *accepted, void *stream)
+{
+    return on_stream(AcceptCall{U, X, LL, Up, Xp, LLp, inside, h, count, A, ncol, 0.0, true, true, K, group, tf, chain0, seed, step, accepted},
+                     stream);
+}
+
+int trpl_mcmc_accept_h(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
+                       const double *h, int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group, const double *tf, int64_t chain0,
+                       uint64_t seed, uint32_t step, int32_t *accepted, int32_t device, double *seconds)
+{
+    return staged(AcceptCall{U, X, LL, Up, Xp, LLp, inside, h, count, A, ncol, 0.0, true, true, K, group, tf, chain0, seed, step, accepted},
+                  device, seconds);
+}
+
+int trpl_mcmc_levels_h_dev(const double *LL, const double *h, int64_t count, int32_t K, int64_t group, const double *tf, int64_t chain0,
+                           uint64_t seed, uint32_t step, double *level, void *stream)
+{
+    return on_stream(LevelsCall{LL, h, count, 0.0, true, true, K, group, tf, chain0, seed, step, level}, stream);
+}
+
+int trpl_mcmc_levels_h(const double *LL, const double *h, int64_t count, int32_t K, int64_t group, const double *tf, int64_t chain0,
+                       uint64_t seed, uint32_t step, double *level, int32_t device, double *seconds)
+{
+    return staged(LevelsCall{LL, h, count, 0.0, true, true, K, group, tf, chain0, seed, step, level}, device, seconds);
 }
 
 int trpl_mcmc_swap_dev(double *U, double *X, double *LL, int32_t K, int64_t group, int32_t A, int32_t ncol, const double *tf,

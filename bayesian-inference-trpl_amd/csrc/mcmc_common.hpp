@@ -1,8 +1,8 @@
-// What the two units of the ensemble sampler share (mcmc.hip: the symmetric proposals, the Metropolis step, tempering, the chain
-// sums; mcmc_hastings.hip: the same step with a Hastings term, the stretch move, the prior term): the Philox stream and its call
-// indices, the ladder as a kernel argument, the host checks of the chains and the ladder, the switch over the instantiations and
-// the two forms of an entry point.  One definition of each, so a call index is taken once.  Both units are compiled with
-// -ffp-contract=off.
+// What the two units of the ensemble sampler share (mcmc.hip: the symmetric proposals, the Metropolis step with and without a
+// Hastings term, tempering, the chain sums; mcmc_hastings.hip: what produces the term, the stretch move and the prior term): the
+// Philox stream and its call indices, the ladder as a kernel argument, the host checks of the chains and the ladder, the switch over
+// the instantiations and the two forms of an entry point.  One definition of each, so a call index is taken once.  Both units are
+// compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -1,20 +1,9 @@
-// The Metropolis-Hastings half of the ensemble sampler (trpl_mcmc_propose_stretch*, trpl_mcmc_accept_h*, trpl_mcmc_levels_h*,
-// trpl_mcmc_prior_term*, include/trpl.h): an untempered additive log term h per chain in the accept rule and in
-// the early-rejection level, and the two users of it -- the affine-invariant stretch move, whose h is ln z^(A - 1), and an independent
-// Gaussian prior in unit coordinates, whose h is ln p(u') - ln p(u).  Everything is for a ladder of temperatures; K = 1 is the single
-// temperature.
+// The two producers of a Hastings term (trpl_mcmc_propose_stretch*, trpl_mcmc_prior_term*, include/trpl.h): the
+// untempered additive log term h per chain that trpl_mcmc_accept_h and trpl_mcmc_levels_h (mcmc.hip: hastings_accept_kernel,
+// hastings_levels_kernel) take into the accept rule and the early-rejection level.  The affine-invariant stretch move's h is ln z^(A - 1); an
+// independent Gaussian prior's, in unit coordinates, is ln p(u') - ln p(u).  Both are for a ladder of temperatures; K = 1 is the
+// single temperature.
 //
-//   hastings_accept_kernel<A>   accept_body of mcmc.hip with h: the same Philox call (0x100 + 9, key (seed; chain0 + i, step)), the
-//       same copy of the rows, the same `accepted`.  d = (LLp - LL) / tf[i / group] + h[i]; the proposal is taken when it is inside,
-//       LLp and h are neither NaN nor -inf, and the chain stands on a likelihood that is not above -inf, or d >= 0, or log(xi) < d.
-//       With h = +0.0 the sum changes no value but -0.0, which no comparison sees: accept_rungs_kernel's outputs bit for bit.
-//   hastings_levels_kernel      levels_body of mcmc.hip with h: l0 = -(LL + tf (log(xi) - h)), then l0 + (fabs(LL) + l0) 2^-40; a
-//       candidate l is taken only if the accept kernel's own dq = (-l - LL) / tf + h satisfies dq < 0 && !(log(xi) < dq).  +inf where
-//       levels_body gives +inf, and where h is NaN or infinite.  The monotonicity argument of mcmc.hip survives the added constant:
-//       every LLp <= -l has (LLp - LL) / tf <= (-l - LL) / tf as before, and adding the same h to both sides is monotone under
-//       round-to-nearest, so d <= dq: d < 0 and log(xi) < d is false, and hastings_accept_kernel rejects with the same (seed, chain,
-//       step, h).  The argument never compares two chains, so it holds with a temperature per rung.  With h = +0.0, lx - 0.0 is lx and
-//       dq + 0.0 compares as dq: levels_rungs_kernel's bits.
 //   stretch_kernel<A>           one stretch proposal per chain (Goodman & Weare 2010, in the split-ensemble form of Foreman-Mackey
 //       et al. 2013): the partner row p = partners[(i / group) group + a], a = min((int64)(xa group), group - 1), xa the first uniform
 //       of the partner call 0x100 + 8; xi the first uniform of call 0x100 + 11; s = (a_par - 1) xi + 1, z = s s / a_par (the density
@@ -81,56 +70,6 @@ __global__ void __launch_bounds__(kThreads) stretch_kernel(const double *U, cons
 }
 
 template <int A>
-__global__ void __launch_bounds__(kThreads) hastings_accept_kernel(double *U, double *X, double *LL, const double *Up, const double *Xp,
-                                                                   const double *LLp, const int32_t *inside, const double *h, int64_t count,
-                                                                   int32_t ncol, const Ladder tf, int64_t group, int64_t chain0,
-                                                                   uint32_t seed_lo, uint32_t seed_hi, uint32_t step, int32_t *accepted)
-{
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= count) return;
-    const uint64_t n = (uint64_t)(chain0 + i);
-    uint32_t r[4];
-    philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), kStream + kAcceptCall, step, seed_lo, seed_hi, r);
-    const double xi = res53(r[0], r[1]);
-    const double ll = LL[i], llp = LLp[i], hv = h[i];
-    const double d = (llp - ll) / tf.tf[i / group] + hv;
-    const bool take = inside[i] != 0 && !(llp != llp) && llp > -INFINITY && !(hv != hv) && hv > -INFINITY &&
-                      (!(ll > -INFINITY) || d >= 0.0 || log(xi) < d);
-    accepted[i] = take ? 1 : 0;
-    if (!take) return;
-#pragma unroll
-    for (int k = 0; k < A; k++) U[i * A + k] = Up[i * A + k];
-    for (int c = 0; c < ncol; c++) X[i * ncol + c] = Xp[i * ncol + c];
-    LL[i] = llp;
-}
-
-__global__ void __launch_bounds__(kThreads) hastings_levels_kernel(const double *LL, const double *h, int64_t count, const Ladder tf,
-                                                                   int64_t group, int64_t chain0, uint32_t seed_lo, uint32_t seed_hi,
-                                                                   uint32_t step, double *level)
-{
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= count) return;
-    const uint64_t n = (uint64_t)(chain0 + i);
-    uint32_t r[4];
-    philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), kStream + kAcceptCall, step, seed_lo, seed_hi, r);
-    const double xi = res53(r[0], r[1]);
-    const double ll = LL[i], hv = h[i], t = tf.tf[i / group];
-    double lv = INFINITY;
-    if (!(ll != ll) && ll > -INFINITY && xi != 0.0 && !(hv != hv) && fabs(hv) < INFINITY) {
-        const double lx = log(xi);
-        const double l0 = -(ll + t * (lx - hv));
-        double cand = l0;
-        for (int k = 0; k < 2; k++) {
-            const double q = -cand;
-            const double dq = (q - ll) / t + hv;
-            if (dq < 0.0 && !(lx < dq)) { lv = cand; break; }
-            cand = l0 + (fabs(ll) + l0) * 0x1p-40;
-        }
-    }
-    level[i] = lv;
-}
-
-template <int A>
 __device__ __forceinline__ double log_prior(const double *u, const Prior &pr)
 {
     double s = 0.0;
@@ -164,22 +103,12 @@ struct StretchCall {
     const double *lo, *hi; const int32_t *do_log; uint32_t flags; double *Up, *Xp; int32_t *inside; double *z, *lnq;
     refine::Box bx = {};
 };
-struct AcceptHCall {
-    double *U, *X, *LL; const double *Up, *Xp, *LLp; const int32_t *inside; const double *h; int64_t count; int32_t A, ncol, K;
-    int64_t group; const double *ladder; int64_t chain0; uint64_t seed; uint32_t step; int32_t *accepted;
-    mcmc::Ladder lad = {};
-};
-struct LevelsHCall {
-    const double *LL, *h; int64_t count; int32_t K; int64_t group; const double *ladder; int64_t chain0; uint64_t seed; uint32_t step;
-    double *level;
-    mcmc::Ladder lad = {};
-};
 struct PriorCall {
     const double *U, *Up; int64_t count; int32_t A; const double *mean, *sd, *h_in; double *h_out;
     mcmc::Prior pr = {};
 };
 
-// ---- check: the refusals of the *_rungs counterpart in its order, then the call's own
+// ---- check: the stretch refuses what trpl_mcmc_propose_rungs refuses, in its order, then its own
 int check(StretchCall &k)
 {
     if (int rc = check_chains(k.count, k.A, k.chain0)) return rc;
@@ -197,30 +126,6 @@ int check(StretchCall &k)
     if (k.P % k.group) return api_fail(TRPL_ERR_ARG, "P=%lld must be a positive multiple of group=%lld", (long long)k.P, (long long)k.group);
     if (k.count > k.P) return api_fail(TRPL_ERR_ARG, "count=%lld must be <= P=%lld", (long long)k.count, (long long)k.P);
     return refine_make_box(k.ncol, k.lo, k.hi, k.do_log, k.flags, k.A, k.bx);
-}
-
-int check(AcceptHCall &k)
-{
-    if (int rc = check_ladder(k.K, k.group, k.ladder, k.lad)) return rc;
-    if (int rc = check_chains(k.count, k.A, k.chain0)) return rc;
-    if (k.ncol < 1 || k.ncol > 16) return api_fail(TRPL_ERR_ARG, "ncol=%d must be in [1, 16]", k.ncol);
-    if (int rc = check_not_null({{"U", k.U}, {"X", k.X}, {"LL", k.LL}, {"Up", k.Up}, {"Xp", k.Xp}, {"LLp", k.LLp}, {"inside", k.inside},
-                                 {"h", k.h}, {"accepted", k.accepted}}))
-        return rc;
-    if (k.count != (int64_t)k.K * k.group)
-        return api_fail(TRPL_ERR_ARG, "count=%lld must be K * group = %d * %lld", (long long)k.count, k.K, (long long)k.group);
-    return TRPL_OK;
-}
-
-int check(LevelsHCall &k)
-{
-    if (int rc = check_ladder(k.K, k.group, k.ladder, k.lad)) return rc;
-    if (int rc = check_count(k.count)) return rc;
-    if (k.chain0 < 0) return api_fail(TRPL_ERR_ARG, "chain0=%lld must be >= 0", (long long)k.chain0);
-    if (int rc = check_not_null({{"LL", k.LL}, {"h", k.h}, {"level", k.level}})) return rc;
-    if (k.count != (int64_t)k.K * k.group)
-        return api_fail(TRPL_ERR_ARG, "count=%lld must be K * group = %d * %lld", (long long)k.count, k.K, (long long)k.group);
-    return TRPL_OK;
 }
 
 int check(PriorCall &k)
@@ -245,20 +150,6 @@ int launch(const StretchCall &k, hipStream_t stream)
     return refine_launched("mcmc propose stretch");
 }
 
-int launch(const AcceptHCall &k, hipStream_t stream)
-{
-    TRPL_MCMC_LAUNCH(k.A, mcmc::hastings_accept_kernel<n>, k.count, stream, k.U, k.X, k.LL, k.Up, k.Xp, k.LLp, k.inside, k.h, k.count, k.ncol,
-                     k.lad, k.group, k.chain0, (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.step, k.accepted)
-    return refine_launched("mcmc accept h");
-}
-
-int launch(const LevelsHCall &k, hipStream_t stream)
-{
-    hipLaunchKernelGGL(mcmc::hastings_levels_kernel, dim3(refine_blocks(k.count)), dim3(refine::kThreads), 0, stream, k.LL, k.h, k.count, k.lad,
-                       k.group, k.chain0, (uint32_t)k.seed, (uint32_t)(k.seed >> 32), k.step, k.level);
-    return refine_launched("mcmc levels h");
-}
-
 int launch(const PriorCall &k, hipStream_t stream)
 {
     TRPL_MCMC_LAUNCH(k.A, mcmc::prior_term_kernel<n>, k.count, stream, k.U, k.Up, k.count, k.pr, k.h_in, k.h_out)
@@ -272,20 +163,6 @@ void stage(StretchCall &k, Staged &sg)
     k.partners = sg.in(k.partners, (size_t)k.P * k.A); k.U = sg.in(k.U, n * k.A);
     k.Up = sg.out(k.Up, n * k.A); k.Xp = sg.out(k.Xp, n * k.ncol); k.inside = sg.out(k.inside, n);
     k.z = sg.out(k.z, n); k.lnq = sg.out(k.lnq, n);
-}
-
-void stage(AcceptHCall &k, Staged &sg)
-{
-    const size_t n = (size_t)k.count;
-    k.U = sg.inout(k.U, n * k.A); k.X = sg.inout(k.X, n * k.ncol); k.LL = sg.inout(k.LL, n);
-    k.Up = sg.in(k.Up, n * k.A); k.Xp = sg.in(k.Xp, n * k.ncol); k.LLp = sg.in(k.LLp, n);
-    k.inside = sg.in(k.inside, n); k.h = sg.in(k.h, n); k.accepted = sg.out(k.accepted, n);
-}
-
-void stage(LevelsHCall &k, Staged &sg)
-{
-    const size_t n = (size_t)k.count;
-    k.LL = sg.in(k.LL, n); k.h = sg.in(k.h, n); k.level = sg.out(k.level, n);
 }
 
 void stage(PriorCall &k, Staged &sg)
@@ -316,32 +193,6 @@ int trpl_mcmc_propose_stretch(const double *U, const double *partners, int64_t c
 {
     return staged(StretchCall{U, partners, count, P, group, A, a, chain0, seed, step, ncol, lo, hi, do_log, flags, Up, Xp, inside, z, lnq},
                   device, seconds);
-}
-
-int trpl_mcmc_accept_h_dev(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
-                           const double *h, int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group, const double *tf,
-                           int64_t chain0, uint64_t seed, uint32_t step, int32_t *accepted, void *stream)
-{
-    return on_stream(AcceptHCall{U, X, LL, Up, Xp, LLp, inside, h, count, A, ncol, K, group, tf, chain0, seed, step, accepted}, stream);
-}
-
-int trpl_mcmc_accept_h(double *U, double *X, double *LL, const double *Up, const double *Xp, const double *LLp, const int32_t *inside,
-                       const double *h, int64_t count, int32_t A, int32_t ncol, int32_t K, int64_t group, const double *tf, int64_t chain0,
-                       uint64_t seed, uint32_t step, int32_t *accepted, int32_t device, double *seconds)
-{
-    return staged(AcceptHCall{U, X, LL, Up, Xp, LLp, inside, h, count, A, ncol, K, group, tf, chain0, seed, step, accepted}, device, seconds);
-}
-
-int trpl_mcmc_levels_h_dev(const double *LL, const double *h, int64_t count, int32_t K, int64_t group, const double *tf, int64_t chain0,
-                           uint64_t seed, uint32_t step, double *level, void *stream)
-{
-    return on_stream(LevelsHCall{LL, h, count, K, group, tf, chain0, seed, step, level}, stream);
-}
-
-int trpl_mcmc_levels_h(const double *LL, const double *h, int64_t count, int32_t K, int64_t group, const double *tf, int64_t chain0,
-                       uint64_t seed, uint32_t step, double *level, int32_t device, double *seconds)
-{
-    return staged(LevelsHCall{LL, h, count, K, group, tf, chain0, seed, step, level}, device, seconds);
 }
 
 int trpl_mcmc_prior_term_dev(const double *U, const double *Up, int64_t count, int32_t A, const double *mean, const double *sd,

@@ -1509,7 +1509,8 @@ int trpl_mcmc_autocov_chains(const double *H, int64_t n, int64_t ldh, int64_t M,
  * Gaussians in unit coordinates, h = ln p(u') - ln p(u)).  The term is NOT divided by the temperature: tempering tempers the
  * likelihood, not the prior and not the proposal's ratio.  LL stays the likelihood alone, so LL = -sse and early rejection keep
  * working.  All four calls take a block of K rungs of `group` chains (trpl_mcmc_*_rungs above); K = 1 is the single temperature.
- * (csrc/mcmc_hastings.hip)
+ * (accept and levels: csrc/mcmc.hip, beside the calls above, whose argument record they share; the stretch and the prior term:
+ * csrc/mcmc_hastings.hip; DESIGN.md sections 30 and 32)
  *
  * trpl_mcmc_accept_h: trpl_mcmc_accept_rungs with h [count] behind inside.  The same xi (Philox counter word 0x100 + 9, key (seed;
  * chain0 + i, step)), the same copy of the rows, the same `accepted`;

@@ -53,6 +53,8 @@ def test_the_library_holds_the_kernels_and_their_unit_is_uncontracted(trpl):
     rule = re.search(r"\$\(OBJ\)/mcmc_hastings\.o:([^\n]*)\n\t([^\n]*)", mk)
     assert rule and "-ffp-contract=off" in rule.group(2) and "refine_common.hpp" in rule.group(1)
     assert "$(OBJ)/mcmc_hastings.o" in mk.split("$(LIB):")[1]
+    rule = re.search(r"\$\(OBJ\)/mcmc\.o:([^\n]*)\n\t([^\n]*)", mk)              # hastings_accept_kernel and hastings_levels_kernel are its
+    assert rule and "-ffp-contract=off" in rule.group(2) and "mcmc.hip" in rule.group(1)
 
 
 def _args():

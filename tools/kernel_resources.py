@@ -8,7 +8,9 @@
                                        quantiles corner refine refine_oriented mcmc mcmc_hastings cut_budget]
 (cross-compiles, no GPU needed; a name is an object of the library without its stepper_ prefix: csrc/<name>.hip or
 csrc/stepper_<name>.hip where that file exists, otherwise a variant of csrc/stepper_variants.hpp -- [sink_][predict_]unit --
-which is stepper_[pair_]variant.hip with the switch of each of its words, as the Makefile compiles it)"""
+which is stepper_[pair_]variant.hip with the switch of each of its words, as the Makefile compiles it; mcmc has the sampler's
+accept and levels kernels in all three forms, hastings_accept_kernel and hastings_levels_kernel among them, mcmc_hastings the
+stretch move and the prior term)"""
 import os
 import re
 import subprocess
