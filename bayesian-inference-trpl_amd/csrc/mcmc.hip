@@ -68,16 +68,7 @@ struct Scale {
     double s[16];
 };
 
-// fold (include/trpl.h, TRPL_MCMC_FOLD): v reflected at the faces of [0, 1] as often as needed.  Called only for a v that failed the
-// range test, so the fmod is off the common path; fmod is exact, the add and the subtract round once each.  NaN and +-inf give NaN.
-__device__ __forceinline__ double fold_outside(double v)
-{
-    double r = fmod(v, 2.0);
-    if (r < 0.0) r = r + 2.0;
-    if (r > 1.0) r = 2.0 - r;
-    return r;
-}
-
+// fold_outside, the reflection of TRPL_MCMC_FOLD, is mcmc_common.hpp's, shared with mcmc_subspace.hip.
 // RUNGS: the partners of chain i are the `group` rows of its rung, [(i / group) group, + group) of `partners`
 template <int A, bool FOLD, bool RUNGS>
 __device__ __forceinline__ void propose_body(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, double gamma,

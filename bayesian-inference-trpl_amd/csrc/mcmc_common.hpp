@@ -1,7 +1,8 @@
-// What the two units of the ensemble sampler share (mcmc.hip: the symmetric proposals, the Metropolis step with and without a
-// Hastings term, tempering, the chain sums; mcmc_hastings.hip: what produces the term, the stretch move and the prior term): the
-// Philox stream and its call indices, the ladder as a kernel argument, the host checks of the chains and the ladder, the switch over
-// the instantiations and the two forms of an entry point.  One definition of each, so a call index is taken once.  Both units are
+// What the units of the ensemble sampler share (mcmc.hip: the symmetric proposals, the Metropolis step with and without a
+// Hastings term, tempering, the chain sums; mcmc_hastings.hip: what produces the term, the stretch move and the prior term;
+// mcmc_subspace.hip: the subspace differential-evolution proposal): the Philox stream and its call indices, the fold of
+// TRPL_MCMC_FOLD, the ladder as a kernel argument, the host checks of the chains and the ladder, the switch over
+// the instantiations and the two forms of an entry point.  One definition of each, so a call index is taken once.  All units are
 // compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +20,20 @@ namespace mcmc {
 
 constexpr uint32_t kStream = 0x100;                              // third counter word: 0x100 + j, apart from the draws' j < 8
 constexpr uint32_t kPartnerCall = 8, kAcceptCall = 9, kSwapCall = 10, kStretchCall = 11;
+// the subspace move (mcmc_subspace.hip): the crossover uniforms c_d are calls 12 + j, the jump-jitter uniforms v_d calls 20 + j (j < 8:
+// coordinates 2j and 2j + 1, as the draws' calls), call 28 the class and the number of pairs with the fallback coordinate, call
+// 28 + p the partners of pair p = 1 .. TRPL_MCMC_MAX_PAIRS - 1 (pair 0 is kPartnerCall)
+constexpr uint32_t kCrossCall = 12, kJumpCall = 20, kSelectCall = 28, kPairCall = 28;
+
+// fold (include/trpl.h, TRPL_MCMC_FOLD): v reflected at the faces of [0, 1] as often as needed.  Called only for a v that failed the
+// range test, so the fmod is off the common path; fmod is exact, the add and the subtract round once each.  NaN and +-inf give NaN.
+__device__ __forceinline__ double fold_outside(double v)
+{
+    double r = fmod(v, 2.0);
+    if (r < 0.0) r = r + 2.0;
+    if (r > 1.0) r = 2.0 - r;
+    return r;
+}
 
 struct Ladder {                                                  // the temperatures of the rungs, by value like Scale
     double tf[TRPL_MCMC_MAX_RUNGS];

@@ -803,6 +803,40 @@ def mcmc_propose_stretch_device(U, partners, group, a, chain0, seed, step, minX,
         _chk(inside, torch.int32, "inside"), _chk(z, torch.float64, "z"), _chk(lnq, torch.float64, "lnq"), _stream()))
 
 
+def mcmc_propose_subspace_device(U, partners, group, gamma_tab, scale, chain0, seed, step, minX, maxX, do_log, Up, Xp, inside, mask, sel,
+                                 ncr=3, pcr=None, e_width=0.05, flags=0):
+    """trpl_mcmc_propose_subspace_dev: Up (count, A), Xp (count, ncol) f64 and inside, mask, sel (count,) int32 <- one subspace
+    differential-evolution proposal per chain of U (count, A) f64 (DREAM; include/trpl.h has the rule): a random subset of the
+    coordinates moves along the sum of delta difference pairs of the chain's rung [(i // group) group, + group) of partners (P, A).
+    gamma_tab (pairs, A) is a host array, the gamma by (delta - 1, selected - 1); pcr (ncr,) the host shares of the crossover classes,
+    None for equal ones; scale (A,) as in mcmc_propose_device.  group None: one rung of P.  mask has bit d set where coordinate d
+    moved, sel is delta | class << 8.  flags: the TRPL_BOX_EQUAL_* bits and _abi.MCMC_FOLD."""
+    import torch
+    lo, hi, lg = _refine_box(minX, maxX, do_log)
+    if U.dim() != 2:
+        raise ValueError("U must be (count, A)")
+    count, A = U.shape
+    scale = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (A,)))
+    tab = np.ascontiguousarray(gamma_tab, dtype=np.float64)
+    if tab.ndim != 2 or tab.shape[1] != A:
+        raise ValueError("gamma_tab must be (pairs, A)")
+    if pcr is not None:
+        pcr = np.ascontiguousarray(pcr, dtype=np.float64)
+        if pcr.shape != (int(ncr),):
+            raise ValueError("pcr must be (ncr,)")
+    if partners is None or partners.dim() != 2 or partners.shape[1] != A:
+        raise ValueError("partners must be (P, A)")
+    if tuple(Up.shape) != (count, A) or tuple(Xp.shape) != (count, lo.size) or not (
+            tuple(inside.shape) == tuple(mask.shape) == tuple(sel.shape) == (count,)):
+        raise ValueError("Up must be (count, A), Xp (count, ncol) and inside, mask and sel (count,)")
+    _abi.check(_abi.lib().trpl_mcmc_propose_subspace_dev(
+        _chk(U, torch.float64, "U"), _chk(partners, torch.float64, "partners"), count, partners.shape[0],
+        partners.shape[0] if group is None else int(group), A, 1.0, _abi.ptr(scale), int(chain0), int(seed) & _M64, int(step) & _M32,
+        lo.size, _abi.ptr(lo), _abi.ptr(hi), _abi.ptr(lg), int(flags), _chk(Up, torch.float64, "Up"), _chk(Xp, torch.float64, "Xp"),
+        _chk(inside, torch.int32, "inside"), tab.shape[0], int(ncr), None if pcr is None else _abi.ptr(pcr), _abi.ptr(tab), float(e_width),
+        _chk(mask, torch.int32, "mask"), _chk(sel, torch.int32, "sel"), _stream()))
+
+
 def mcmc_accept_h_device(U, X, LL, Up, Xp, LLp, inside, h, tf, chain0, seed, step, accepted):
     """trpl_mcmc_accept_h_dev: mcmc_accept_rungs_device with an untempered log term h (count,) f64 per chain: d = (LLp - LL) / tf + h.
     tf (K,) is a host array, or a scalar for one temperature."""

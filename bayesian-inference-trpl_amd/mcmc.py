@@ -9,7 +9,9 @@ Foreman-Mackey et al. 2013): within a half-sweep the partners are fixed, so ever
 that leaves the posterior invariant, and all chains of the half can move at once.  kind="rw" is the plain random walk.
 kind="stretch" is the affine-invariant stretch move (Goodman & Weare 2010), an asymmetric proposal, and prior= an informative
 Gaussian prior: both enter the accept step and the early-rejection level as an untempered log term per chain (accept_h,
-reject_levels_h).
+reject_levels_h).  kind="subspace" is DREAM's move (Vrugt et al. 2009; propose_subspace):
+differential evolution on a random subset of the coordinates, along the sum of several difference pairs -- symmetric like "de", so
+it goes through the same accept step.
 
 Chains live in the unit coordinates of `refine` (the active columns of the box, uniform prior on the cube).  With bounds="reject",
 the default, a proposal that leaves the cube is never solved and never accepted; with bounds="fold" it is reflected back at the
@@ -221,6 +223,58 @@ def propose_stretch(U, partners, group, a, chain0, seed, step, minX, maxX, do_lo
            int(chain0), int(seed) & _M64, int(step) & _M32, lo.size, _abi.ptr(lo), _abi.ptr(hi), _abi.ptr(lg), box_flags(sim_flags),
            _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(inside), _abi.ptr(z), _abi.ptr(lnq), int(device))
     return Up, Xp, inside, z, lnq
+
+
+def subspace_gamma_table(pairs, A, factor=1.0):
+    """(pairs, A): the gamma of the subspace move by (delta - 1, dsel - 1), factor * 2.38 / sqrt(2 delta dsel) -- ter Braak's optimal
+    jump for delta difference pairs in a subspace of dsel coordinates."""
+    delta, dsel = np.arange(1, int(pairs) + 1, dtype=np.float64)[:, None], np.arange(1, int(A) + 1, dtype=np.float64)[None, :]
+    return np.ascontiguousarray(float(factor) * (2.38 / np.sqrt(2.0 * delta * dsel)))
+
+
+def _pcr_arg(pcr, ncr):
+    """pcr of propose_subspace, run and run_tempered as an (ncr,) array of shares, or None (equal shares)."""
+    if pcr is None:
+        return None
+    pcr = _f64(pcr)
+    if pcr.shape != (ncr,):
+        raise ValueError("pcr must be (ncr,) = (%d,) shares of the crossover classes" % ncr)
+    if not (np.all(np.isfinite(pcr)) and np.all(pcr >= 0.0) and pcr.sum() > 0.0):
+        raise ValueError("pcr: every share must be finite and >= 0 and their sum > 0")
+    return pcr
+
+
+def propose_subspace(U, partners, group, gamma_tab, scale, chain0, seed, step, minX, maxX, do_log, ncr=3, pcr=None, e_width=0.05,
+                     sim_flags=None, device=0, info=None, fold=False):
+    """(Up, Xp, inside, mask, sel): one subspace differential-evolution proposal per chain of U (count, A)
+    (trpl_mcmc_propose_subspace; DREAM, Vrugt et al. 2009).  Per chain: a crossover class m is drawn with the shares pcr (ncr,) (None:
+    equal), CR = (m + 1) / ncr; each coordinate is selected with probability CR (one at random if none is); delta, uniform in 1 ..
+    pairs = gamma_tab.shape[0], pairs of distinct rows (a, b) are drawn from the chain's rung [(i // group) group, + group) of partners
+    (P, A); on the selected coordinates u' = (u + g e sum_p (pa_p - pb_p)) + scale (2 xi - 1) with g = gamma_tab[delta - 1][selected
+    - 1] and e = 1 + e_width (2 v - 1); the others keep their bits.  group None: one rung, group = P.  mask (count,) int32 has bit d
+    set where coordinate d moved; sel (count,) int32 is delta | m << 8.  inside and fold as in propose.  With ncr = 1, one pair,
+    e_width = 0 and a table filled with gamma the first three are propose_rungs' bit for bit."""
+    U, partners = _f64(U), _f64(partners)
+    lo, hi, lg = _box(minX, maxX, do_log)
+    if U.ndim != 2:
+        raise ValueError("U must be (count, A)")
+    count, A = U.shape
+    if partners.ndim != 2 or partners.shape[1] != A:
+        raise ValueError("partners must be (P, A)")
+    tab = _f64(gamma_tab)
+    if tab.ndim != 2 or tab.shape[1] != A:
+        raise ValueError("gamma_tab must be (pairs, A)")
+    ncr = int(ncr)
+    pcr = _pcr_arg(pcr, ncr)
+    scale = np.ascontiguousarray(np.broadcast_to(_f64(scale), (A,)))
+    P = partners.shape[0]
+    Up, Xp = np.empty((count, A)), np.empty((count, lo.size))
+    inside, mask, sel = (np.empty(count, dtype=np.int32) for _ in range(3))
+    _timed("trpl_mcmc_propose_subspace", info, _abi.ptr(U), _abi.ptr(partners), count, P, P if group is None else int(group), A, 1.0,
+           _abi.ptr(scale), int(chain0), int(seed) & _M64, int(step) & _M32, lo.size, _abi.ptr(lo), _abi.ptr(hi), _abi.ptr(lg),
+           box_flags(sim_flags) | (_abi.MCMC_FOLD if fold else 0), _abi.ptr(Up), _abi.ptr(Xp), _abi.ptr(inside), tab.shape[0], ncr,
+           None if pcr is None else _abi.ptr(pcr), _abi.ptr(tab), float(e_width), _abi.ptr(mask), _abi.ptr(sel), int(device))
+    return Up, Xp, inside, mask, sel
 
 
 def accept_h(U, X, LL, Up, Xp, LLp, inside, h, tf, chain0, seed, step, device=0, info=None):
@@ -464,14 +518,25 @@ class Chains:
         return np.sqrt(info["var_plus"] / ess)
 
 
-def _proposal_args(C, kind, bounds, scale, gamma=None, jump_every=0, stretch_a=2.0):
-    """What run and run_tempered refuse alike about the ensemble and its proposal; returns scale with kind="de"'s default."""
+_SUBSPACE_DEFAULTS = dict(pairs=3, ncr=3, e_width=0.05, pcr=None, adapt_cr=False)
+
+
+def _proposal_args(C, kind, bounds, scale, gamma=None, jump_every=0, stretch_a=2.0, burn=0, **subspace):
+    """What run and run_tempered refuse alike about the ensemble and its proposal; returns (scale with kind="de"'s default, the
+    subspace move's settings or None).  subspace: pairs, ncr, e_width, pcr, adapt_cr as run takes them -- kind="subspace"'s alone."""
     if C < 4 or C % 2:
         raise ValueError("C=%d: the two halves of the ensemble need an even number of chains, at least 4" % C)
-    if kind not in ("de", "rw", "stretch"):
-        raise ValueError("kind must be 'de', 'rw' or 'stretch'")
+    if kind not in ("de", "rw", "stretch", "subspace"):
+        raise ValueError("kind must be 'de', 'rw', 'stretch' or 'subspace'")
     if bounds not in ("reject", "fold"):
         raise ValueError("bounds must be 'reject' or 'fold'")
+    sub = dict(_SUBSPACE_DEFAULTS, **subspace)
+    if kind != "subspace":
+        for name, default in _SUBSPACE_DEFAULTS.items():
+            given = sub[name]
+            if not (given is default or (isinstance(default, (int, float)) and not isinstance(given, bool) and np.isscalar(given)
+                                         and given == default)):
+                raise ValueError("%s belongs to kind='subspace'; kind=%r has none" % (name, kind))
     if kind == "stretch":
         if gamma is not None or scale is not None or int(jump_every) != 0:
             raise ValueError("kind='stretch' has no gamma, scale or jump_every: the move's only parameter is stretch_a")
@@ -479,12 +544,43 @@ def _proposal_args(C, kind, bounds, scale, gamma=None, jump_every=0, stretch_a=2
             raise ValueError("kind='stretch' needs bounds='reject': a reflected stretch is not reversible")
         if not (np.isfinite(stretch_a) and stretch_a > 1.0):
             raise ValueError("stretch_a=%r must be finite and > 1" % (stretch_a,))
-        return 0.0
+        return 0.0, None
     if scale is None:
         if kind == "rw":
             raise ValueError("kind='rw' needs scale, the half-width of the random walk")
         scale = 1e-3
-    return scale
+    if kind != "subspace":
+        return scale, None
+    pairs, ncr, e_width = sub["pairs"], sub["ncr"], sub["e_width"]
+    if isinstance(pairs, bool) or not (isinstance(pairs, (int, np.integer)) and 1 <= pairs <= _abi.MCMC_MAX_PAIRS):
+        raise ValueError("pairs=%r must be an integer in [1, %d]" % (pairs, _abi.MCMC_MAX_PAIRS))
+    if isinstance(ncr, bool) or not (isinstance(ncr, (int, np.integer)) and 1 <= ncr <= _abi.MCMC_MAX_CR):
+        raise ValueError("ncr=%r must be an integer in [1, %d]" % (ncr, _abi.MCMC_MAX_CR))
+    if not (isinstance(e_width, (int, float, np.floating)) and 0.0 <= e_width < 1.0):
+        raise ValueError("e_width=%r must be in [0, 1)" % (e_width,))
+    if gamma is not None and not np.isfinite(gamma):
+        raise ValueError("gamma=%r, the factor on the subspace move's table, must be finite" % (gamma,))
+    if not (sub["adapt_cr"] is False or sub["adapt_cr"] is True):
+        raise ValueError("adapt_cr must be False or True")
+    if sub["adapt_cr"] and int(burn) < 1:
+        raise ValueError("adapt_cr=True adapts the crossover shares during the burn sweeps only: burn must be >= 1")
+    pcr = _pcr_arg(sub["pcr"], int(ncr))
+    return scale, dict(pairs=int(pairs), ncr=int(ncr), e_width=float(e_width), adapt=sub["adapt_cr"], burn=int(burn),
+                       pcr=np.full(int(ncr), 1.0 / int(ncr)) if pcr is None else pcr / pcr.sum())
+
+
+def adapted_pcr(jump, tried, ncr):
+    """(ncr,): the crossover shares of adapt_cr from the squared jump summed per class and the proposals tried per class: proportional
+    to the mean squared jump per proposal (a class not tried yet takes the mean of the others; a total of zero gives equal shares),
+    floored at 1 / (10 ncr) and then renormalised -- so no share ends below (1 / (10 ncr)) / 1.1."""
+    jump, tried = np.asarray(jump, dtype=np.float64), np.asarray(tried)
+    mean = np.full(ncr, np.nan)
+    mean[tried > 0] = jump[tried > 0] / tried[tried > 0]
+    mean[tried <= 0] = mean[tried > 0].mean() if np.any(tried > 0) else 1.0
+    total = mean.sum()
+    q = mean / total if total > 0.0 and np.isfinite(total) else np.full(ncr, 1.0 / ncr)
+    q = np.maximum(q, 1.0 / (10.0 * ncr))
+    return q / q.sum()
 
 
 def _prior_args(prior, A):
@@ -506,6 +602,14 @@ def _early_reject_arg(early_reject):
     return early_reject
 
 
+def _subspace_info(info, subspace, n):
+    """What info receives about kind="subspace" from _sweeps' counters."""
+    if subspace is not None:
+        info.update(pairs=subspace["pairs"], ncr=subspace["ncr"], pcr=n["pcr"].tolist(), mean_dsel=n["dsel"])
+        if subspace["adapt"]:
+            info.update(pcr_trace=n["pcr_trace"])
+
+
 def _active(lo, hi, sim_flags):
     A = refine.active_columns(lo, hi, sim_flags).size
     if not 1 <= A <= _abi.REFINE_MAX_DIMS:
@@ -514,7 +618,7 @@ def _active(lo, hi, sim_flags):
 
 
 def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jump_every, seed, kept, device, fold, early_reject, tf=None,
-            ladder=None, swap_every=1, stretch_a=2.0, prior=None):
+            ladder=None, swap_every=1, stretch_a=2.0, prior=None, subspace=None):
     """The sweeps of run (tf: the C rows of U, X, LL as run holds them, the single-temperature front ends) and of run_tempered
     (ladder (K,): the 2 K g rows half-major, the *_rungs front ends and the swap).  The state is advanced in place.  Returns the
     history -- U, X, LL, accept, each (K, n, C, ..), K = 1 for run -- and the counters: accept (sweeps, K) the share of chains that
@@ -522,7 +626,13 @@ def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jum
 
     kind="stretch" or a prior makes every half-sweep a Metropolis-Hastings step: it forms h (count,) -- propose_stretch's lnq, plus
     prior_term -- and goes through accept_h and reject_levels_h, which take a ladder of one for run.  A proposal whose h is NaN or
-    -inf is not solved and counts as outside.  With neither, the calls are exactly the ones above."""
+    -inf is not solved and counts as outside.  With neither, the calls are exactly the ones above.
+
+    kind="subspace" (subspace: _proposal_args' settings) proposes with propose_subspace, its table subspace_gamma_table times gamma; a
+    jump sweep is propose / propose_rungs with gamma = 1, all coordinates.  The counters then also hold dsel, the mean number of
+    coordinates a subspace proposal moved, pcr (ncr,) the shares the kept sweeps ran with and pcr_trace (sweeps, ncr) the shares of
+    every sweep.  With adapt the sweeps t < burn sum, per class, the squared jump of the accepted proposals in units of the rung's
+    current deviation per column, and the proposals tried; adapted_pcr of the two replaces the shares after each such sweep."""
     lo, hi, lg = box
     hastings = kind == "stretch" or prior is not None
     level_kw = "cut_budget" if early_reject == "sample" else "cut_levels"       # the level is per system, or the sample's budget
@@ -541,22 +651,39 @@ def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jum
             return flags.reshape(K, g).sum(axis=1)
 
     gamma0 = 2.38 / np.sqrt(2.0 * A) if gamma is None else float(gamma)
+    if subspace is not None:
+        tab = subspace_gamma_table(subspace["pairs"], A, 1.0 if gamma is None else float(gamma))
+        ncr, pcr = subspace["ncr"], subspace["pcr"]
+        pcr_trace, dsel_sum, dsel_n = np.empty((sweeps, ncr)), 0, 0
+        jump, tried_cr = np.zeros(ncr), np.zeros(ncr, dtype=np.int64)
     hU, hX = np.empty((K, len(kept), C, A)), np.empty((K, len(kept), C, lo.size))
     hLL, hAcc = np.empty((K, len(kept), C)), np.empty((K, len(kept), C), dtype=bool)
     shares, tried, done = np.empty((sweeps, K)), np.zeros(K - 1, dtype=np.int64), np.zeros(K - 1, dtype=np.int64)
     outside, folded, levelled, solved = (np.zeros(K, dtype=np.int64) for _ in range(4))
     moved, row = np.empty(2 * half, dtype=bool), 0
     for t in range(sweeps):
-        gm = 1.0 if jump_every > 0 and (t + 1) % jump_every == 0 else gamma0
+        jumping = jump_every > 0 and (t + 1) % jump_every == 0
+        gm = 1.0 if jumping else gamma0
+        adapting = subspace is not None and subspace["adapt"] and t < subspace["burn"] and not jumping
+        if subspace is not None:
+            pcr_trace[t] = pcr
         for h, (a, b) in enumerate(((0, half), (half, 2 * half))):
             step = 2 * t + h                                     # with chain0 = a, the key of the half-sweep's calls
             hh = None
-            if kind == "stretch":
+            if subspace is not None and not jumping:
+                Up, Xp, inside, mask, sel = propose_subspace(U[a:b], U[half:] if h == 0 else U[:half], g, tab, scale, a, seed, step, lo, hi,
+                                                             lg, ncr, pcr, subspace["e_width"], sim_flags, device=device, fold=fold)
+                dsel_sum += int(np.unpackbits(np.ascontiguousarray(mask).view(np.uint8)).sum())
+                dsel_n += half
+                if adapting:                                     # the deviation of each rung's ensemble as it stands, both halves
+                    sd = rung_major(U).std(axis=1)
+                    before = U[a:b].copy()
+            elif kind == "stretch":
                 Up, Xp, inside, _, hh = propose_stretch(U[a:b], U[half:] if h == 0 else U[:half], g, stretch_a, a, seed, step, lo, hi, lg,
                                                         sim_flags, device=device)
             elif kind == "rw":
                 Up, Xp, inside = propose(U[a:b], None, gm, scale, a, seed, step, lo, hi, lg, sim_flags, device=device, fold=fold)
-            elif ladder is None:
+            elif ladder is None:                                 # "de", and the jump sweep of "subspace"
                 Up, Xp, inside = propose(U[a:b], U[half:] if h == 0 else U[:half], gm, scale, a, seed, step, lo, hi, lg, sim_flags,
                                          device=device, fold=fold)
             else:
@@ -584,6 +711,14 @@ def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jum
                 moved[a:b] = accept_h(U[a:b], X[a:b], LL[a:b], Up, Xp, LLp, inside, hh, ladder_h, a, seed, step, device=device) != 0
             else:
                 moved[a:b] = accept_of(U[a:b], X[a:b], LL[a:b], Up, Xp, LLp, inside, temper, a, seed, step, device=device) != 0
+            if adapting:
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    z2 = (((U[a:b] - before) / np.repeat(sd, g, axis=0)) ** 2).sum(axis=1)      # a rejected chain has not moved: zero
+                cls = sel >> 8
+                jump += np.bincount(cls, weights=np.where(np.isfinite(z2), z2, 0.0), minlength=ncr)[:ncr]
+                tried_cr += np.bincount(cls, minlength=ncr)[:ncr]
+        if adapting:
+            pcr = adapted_pcr(jump, tried_cr, ncr)
         shares[t] = rung_major(moved).mean(axis=1)
         if K > 1 and (t + 1) % swap_every == 0:
             parity = (t // swap_every) % 2
@@ -595,12 +730,15 @@ def _sweeps(loglik, U, X, LL, *, box, sim_flags, sweeps, kind, gamma, scale, jum
         if t >= kept.start and (t - kept.start) % kept.step == 0:
             hU[:, row], hX[:, row], hLL[:, row], hAcc[:, row] = rung_major(U), rung_major(X), rung_major(LL), rung_major(moved)
             row += 1
-    return (hU, hX, hLL, hAcc), dict(accept=shares, outside=outside, folded=folded, levelled=levelled, solved=solved, tried=tried, done=done)
+    n = dict(accept=shares, outside=outside, folded=folded, levelled=levelled, solved=solved, tried=tried, done=done)
+    if subspace is not None:
+        n.update(dsel=dsel_sum / float(max(dsel_n, 1)), pcr=pcr, pcr_trace=pcr_trace)
+    return (hU, hX, hLL, hAcc), n
 
 
 def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0, kind="de", gamma=None, scale=None, jump_every=0,
         seed=1, keep_every=1, burn=0, max_history_bytes=4 << 30, device=0, info=None, U0=None, bounds="reject", stretch_a=2.0, prior=None,
-        early_reject=False):
+        pairs=3, ncr=3, e_width=0.05, pcr=None, adapt_cr=False, early_reject=False):
     """Advance the C chains that start at X0 (C, ncol), LL0 (C,) by `sweeps` sweeps; loglik(X) -> LL is any callable (the fused
     likelihood, a toy).  Returns Chains: the states after the sweeps burn, burn + keep_every, ...
 
@@ -618,6 +756,22 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
     chain moves along the line through one chain of the other half, u' = p + z (u - p), and the factor z^(A - 1) enters the accept
     step as its Hastings term (accept_h).  It has no other parameter: gamma, scale and jump_every must be left at their defaults, and
     bounds must be "reject" (a reflected stretch is not reversible); ValueError otherwise.  info receives stretch_a.
+
+    kind="subspace": DREAM's move (Vrugt et al. 2009; propose_subspace): each proposal moves a random subset of the coordinates --
+    a crossover class m of ncr is drawn with the shares pcr (default equal), each coordinate is selected with probability (m + 1) /
+    ncr -- along the sum of delta difference pairs of the other half, delta uniform in 1 .. pairs, with gamma * 2.38 / sqrt(2 delta
+    dsel) for the dsel selected coordinates (gamma: a factor, default 1) times 1 + e_width (2 v - 1), plus the jitter of half-width
+    scale (default as for "de").  The move is symmetric: both bounds, prior, every early_reject and jump_every apply as for "de"; a
+    jump sweep is "de"'s with gamma = 1 and moves all coordinates.  pairs, ncr, e_width, pcr and adapt_cr belong to this kind alone
+    (ValueError with another).  info receives pairs, ncr, pcr (the shares of the kept sweeps) and mean_dsel, the mean number of
+    coordinates a proposal moved.
+    adapt_cr=True adapts the shares as DREAM does, during the burn sweeps ONLY: each of them adds, per class, the squared jump of the
+    accepted proposals -- sum_d ((u_new_d - u_old_d) / sd_d)^2 with sd_d the current ensemble's deviation of column d; a rejected
+    chain counts zero -- and the proposals tried, and sets pcr_m proportional to the mean squared jump per proposal of class m,
+    floored at 1 / (10 ncr) before renormalising (adapted_pcr).  The shares are frozen after the last burn sweep, so the kept sweeps
+    are a Markov chain with a fixed kernel that leaves the posterior invariant; the burn sweeps, whose kernel depends on the history,
+    are not, and are discarded for that reason.  burn = 0 with adapt_cr=True is a ValueError.  info also receives pcr_trace (sweeps,
+    ncr), the shares every sweep ran with.
 
     prior=(mean_u, sd_u), each (A,): an independent Gaussian prior in the unit coordinates of the active columns on top of the
     uniform one on the cube (gaussian_prior makes the pair from a centre and widths in the box's units; sd inf is a flat column).
@@ -649,7 +803,8 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
     if X.ndim != 2 or X.shape[1] != lo.size or LL.shape != (X.shape[0],):
         raise ValueError("X0 must be (C, ncol) and LL0 (C,)")
     C = X.shape[0]
-    scale = _proposal_args(C, kind, bounds, scale, gamma, jump_every, stretch_a)
+    scale, subspace = _proposal_args(C, kind, bounds, scale, gamma, jump_every, stretch_a, burn=burn, pairs=pairs, ncr=ncr, e_width=e_width,
+                                     pcr=pcr, adapt_cr=adapt_cr)
     sweeps, keep_every, burn = int(sweeps), int(keep_every), int(burn)
     if sweeps < 1 or keep_every < 1 or burn < 0:
         raise ValueError("sweeps and keep_every must be >= 1 and burn >= 0")
@@ -668,10 +823,11 @@ def run(loglik, X0, LL0, minX, maxX, do_log, sim_flags=None, sweeps=1000, tf=1.0
             raise ValueError("U0 must be (C, A) with the box's A = %d active columns" % A)
     hist, n = _sweeps(loglik, U, X, LL, tf=tf, box=(lo, hi, lg), sim_flags=sim_flags, sweeps=sweeps, kind=kind, gamma=gamma, scale=scale,
                       jump_every=int(jump_every), seed=seed, kept=kept, device=device, fold=bounds == "fold", early_reject=early_reject,
-                      stretch_a=float(stretch_a), prior=prior)
+                      stretch_a=float(stretch_a), prior=prior, subspace=subspace)
     if info is not None:
         if kind == "stretch":
             info.update(stretch_a=float(stretch_a))
+        _subspace_info(info, subspace, n)
         info.update(accept=n["accept"][:, 0].tolist(), outside=int(n["outside"][0]) / float(sweeps * C),
                     folded=int(n["folded"][0]) / float(sweeps * C))
         if early_reject:
@@ -696,7 +852,7 @@ class Tempered:
 
 def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sweeps=1000, swap_every=1, kind="de", gamma=None,
                  scale=None, jump_every=0, seed=1, keep_every=1, burn=0, max_history_bytes=4 << 30, device=0, info=None, U0=None,
-                 bounds="reject", stretch_a=2.0, prior=None, early_reject=False):
+                 bounds="reject", stretch_a=2.0, prior=None, pairs=3, ncr=3, e_width=0.05, pcr=None, adapt_cr=False, early_reject=False):
     """Parallel tempering (replica exchange: Swendsen & Wang 1986, Geyer 1991): K = len(ladder) copies of run's
     ensemble of C chains, rung k at temperature ladder[k], advanced together, and states of adjacent rungs exchanged by the
     Metropolis rule of swap().  The hot rungs cross between separated modes; the exchange carries that down to rung 0, whose
@@ -710,7 +866,7 @@ def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sw
     accept_rungs; step and chain0 are run's (2 t + h, the block's first row).  After every swap_every-th sweep t (t + 1 a multiple
     of swap_every) each block gets one swap with parity = (t // swap_every) % 2, step = t and chain0 the block's first row.  With
     ladder = [tf] no swap is called and rung(0) is run(..., tf=tf)'s Chains bit for bit.  kind="stretch" takes each chain's partner
-    from its own rung; a prior is common to the rungs and is not tempered, so it cancels in the swap, which is unchanged.
+    from its own rung, kind="subspace" all its pairs (its shares pcr are common to the rungs, adapted on all of them together); a prior is common to the rungs and is not tempered, so it cancels in the swap, which is unchanged.
 
     The other keywords are run's.  Chains.accept of a rung is the Metropolis step's flag of the rung's slots; an exchange does not
     count as a move.  The history takes n K C (A + ncol + 1) 8 + n K C bytes and is refused above max_history_bytes before anything
@@ -730,7 +886,8 @@ def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sw
     if X.ndim != 3 or X.shape[0] != K or X.shape[2] != lo.size or LL.shape != X.shape[:2]:
         raise ValueError("X0 must be (C, ncol) and LL0 (C,), or (K, C, ncol) and (K, C) with the ladder's K = %d" % K)
     C = X.shape[1]
-    scale = _proposal_args(C, kind, bounds, scale, gamma, jump_every, stretch_a)
+    scale, subspace = _proposal_args(C, kind, bounds, scale, gamma, jump_every, stretch_a, burn=burn, pairs=pairs, ncr=ncr, e_width=e_width,
+                                     pcr=pcr, adapt_cr=adapt_cr)
     sweeps, keep_every, burn, swap_every = int(sweeps), int(keep_every), int(burn), int(swap_every)
     if sweeps < 1 or keep_every < 1 or burn < 0 or swap_every < 1:
         raise ValueError("sweeps, keep_every and swap_every must be >= 1 and burn >= 0")
@@ -757,12 +914,13 @@ def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sw
         U = half_major(U)
     hist, n = _sweeps(loglik, U, X, LL, ladder=ladder, swap_every=swap_every, box=(lo, hi, lg), sim_flags=sim_flags, sweeps=sweeps, kind=kind,
                       gamma=gamma, scale=scale, jump_every=int(jump_every), seed=seed, kept=kept, device=device, fold=bounds == "fold",
-                      early_reject=early_reject, stretch_a=float(stretch_a), prior=prior)
+                      early_reject=early_reject, stretch_a=float(stretch_a), prior=prior, subspace=subspace)
     with np.errstate(invalid="ignore"):
         swap_rate = n["done"] / n["tried"].astype(np.float64)
     if info is not None:
         if kind == "stretch":
             info.update(stretch_a=float(stretch_a))
+        _subspace_info(info, subspace, n)
         info.update(accept=n["accept"], outside=n["outside"] / float(sweeps * C), folded=n["folded"] / float(sweeps * C), swap_rate=swap_rate)
         if early_reject:
             info.update(early_reject=n["levelled"] / np.maximum(n["solved"], 1).astype(np.float64))

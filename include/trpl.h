@@ -1578,6 +1578,84 @@ int trpl_mcmc_prior_term(const double *U, const double *Up, int64_t count, int32
                          const double *h_in /*nullable*/, double *h_out, int32_t device, double *seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_mcmc_propose_subspace -- SUBSPACE DIFFERENTIAL EVOLUTION (DREAM: Vrugt, ter Braak, Diks, Robinson, Hyman & Higdon 2009): the
+ * proposal of trpl_mcmc_propose_rungs on a random subset of the coordinates, along the sum of several difference vectors, with a gamma
+ * chosen for the subset's size and the number of pairs and a small multiplicative jitter on the jump.  A full-dimensional DE move
+ * pushes all A coordinates along one difference vector with one gamma = 2.38 / sqrt(2 A), the known weak point of DE-MC from about ten
+ * dimensions on (ter Braak 2006).  The move is symmetric, so trpl_mcmc_accept*, trpl_mcmc_levels*, trpl_mcmc_prior_term and
+ * trpl_mcmc_swap take it as they stand.  For a block of rungs of `group` chains each; K = 1 (group = the half ensemble) is the single
+ * temperature.  (csrc/mcmc_subspace.hip)
+ *
+ * Arguments: those of trpl_mcmc_propose_rungs in its order, then pairs in [1, TRPL_MCMC_MAX_PAIRS], ncr in [1, TRPL_MCMC_MAX_CR], pcr
+ * [ncr] (HOST, nullable: equal shares), gamma_tab [pairs][A] (HOST), e_width in [0, 1), mask [count] and sel [count] (int32, out).
+ * `gamma` is checked as trpl_mcmc_propose_rungs checks it and is otherwise not read: the move's gamma is the table's.  The host turns
+ * pcr into cumulative shares, cdf[m] = (pcr[0] + .. + pcr[m], ascending from +0.0) / (their sum in the same order), or (m + 1) / ncr
+ * without pcr; the shares and the table travel in the kernel argument, so the device takes no square root.
+ *
+ * Randomness.  The stream of the calls above, key (seed) and counter (n low, n high, 0x100 + j, step), n = chain0 + i; every uniform
+ * is genrand_res53 of (x0, x1) or (x2, x3).  The calls of this move:
+ *     j = 0 .. 7      xi[2j], xi[2j + 1]   the additive jitter, the calls of trpl_mcmc_propose
+ *     j = 8           xi_a, xi_b           the partners of pair 0, the call of trpl_mcmc_propose
+ *     j = 12 .. 19    c[2(j - 12)], c[2(j - 12) + 1]    the crossover uniforms
+ *     j = 20 .. 27    v[2(j - 20)], v[2(j - 20) + 1]    the jump-jitter uniforms
+ *     j = 28          xi_m from (x0, x1), the crossover class; xi_s from (x2, x3), the number of pairs and the fallback coordinate
+ *     j = 28 + p      xi_a, xi_b           the partners of pair p = 1 .. TRPL_MCMC_MAX_PAIRS - 1 (j = 29, 30, 31)
+ * (9, 10 and 11 are the acceptance, the swap and the stretch.)
+ *
+ * The rule, one thread per chain, fp64 with one rounding per operation, in this order:
+ *     m     = the first index with xi_m < cdf[m], or ncr - 1 if there is none;      CR = (double)(m + 1) / (double)ncr
+ *     t     = xi_s * (double)pairs;   delta = min((int)t, pairs - 1) + 1;   xi_f = t - (double)(delta - 1)
+ *             (delta is uniform in 1 .. pairs; the fraction of t is independent of its integer part, so xi_f is uniform too)
+ *     coordinate d is selected when c_d < CR; if none is, coordinate min((int)(xi_f * A), A - 1) alone;   dsel = the number selected
+ *     pair p < delta: a_p = min((int64)(xi_a * group), group - 1), b_p = min((int64)(xi_b * (group - 1)), group - 2), b_p += (b_p >=
+ *             a_p), rows of the chain's rung [(i / group) * group, + group) of partners, as trpl_mcmc_propose_rungs draws its pair
+ *     D_d   = (pa_0[d] - pb_0[d]), then + (pa_p[d] - pb_p[d]) for p = 1 .. delta - 1 in turn
+ *     g     = gamma_tab[delta - 1][dsel - 1]
+ *     selected d:    u'_d = (u_d + (g * (1.0 + e_width * (2.0 * v_d - 1.0))) * D_d) + scale_d * (2.0 * xi_d - 1.0)
+ *     unselected d:  u'_d = u_d, the same bits; no jitter
+ * then, for the selected coordinates only, the range test of trpl_mcmc_propose or with TRPL_MCMC_FOLD its fold: inside is 0 / 1, or
+ * with the fold the code 0 / 1 / 2.  An unselected coordinate takes no part in `inside`.  Xp is formed from u' for every column by
+ * the expressions of trpl_mcmc_propose.  mask[i] has bit d set where coordinate d was selected (never 0); sel[i] = delta | m << 8.
+ * a_p != b_p inside a pair; the pairs are drawn independently of each other, so two pairs may share a chain or be the same pair --
+ * DREAM draws them without replacement, which needs a rejection loop or a partial shuffle per thread and changes nothing below.
+ *
+ * WHY THE MOVE IS SYMMETRIC.  The mask, delta, the class and the factor e_d = 1 + e_width (2 v_d - 1) are drawn from the counter
+ * alone: they do not depend on the chain's state.  The partners are the other half of the ensemble, which is fixed while this half
+ * is updated.  Given (mask, delta, e), the increment of the selected coordinates is g e_d sum_p (pa_p - pb_p)_d + scale_d (2 xi_d - 1).
+ * Exchanging a_p and b_p in every pair is as likely as the draw itself (the ordered pair (a, b) is uniform over a != b, so (b, a) has
+ * the same probability) and negates the sum; 2 xi_d - 1 is symmetric about 0.  So the increment's density is symmetric about 0 on the
+ * selected subspace and the unselected coordinates stay: q(u -> u') = q(u' -> u), conditionally on (mask, delta, e) and therefore
+ * after averaging over them, whatever their distribution -- pcr may be anything that does not look at the state.  With
+ * TRPL_MCMC_FOLD the reflections at the faces are isometries of the selected subspace, and the argument of trpl_mcmc_propose's fold
+ * carries over word for word.  No Hastings term arises.
+ *
+ * THE ANCHOR.  With ncr = 1, pairs = 1, e_width = 0 and gamma_tab filled with gamma, every output (Up, Xp, inside) is
+ * trpl_mcmc_propose_rungs' with that gamma, bit for bit, folded or not: CR = 1 selects every coordinate (c_d < 1 always), pair 0 and
+ * the additive jitter use the calls of trpl_mcmc_propose, 1.0 + (+-0.0) = 1.0 and g * 1.0 = g.  mask is then 2^A - 1 and sel is 1.
+ *
+ * Refused (TRPL_ERR_ARG, before a device is touched, the message naming the argument): what trpl_mcmc_propose_rungs refuses, in its
+ * order (group < 2 among them), then pairs outside [1, TRPL_MCMC_MAX_PAIRS]; ncr outside [1, TRPL_MCMC_MAX_CR]; a pcr[m] that is
+ * negative or not finite; a pcr whose sum is not positive; a gamma_tab entry that is not finite; e_width outside [0, 1); "gamma_tab is
+ * NULL", "mask is NULL", "sel is NULL"; then what trpl_refine_draw refuses of a box.  TRPL_MCMC_FOLD is honoured; any bit other than
+ * it and TRPL_BOX_EQUAL_* is refused.  The _dev call takes device pointers (scale, pcr, gamma_tab and the box arrays excepted),
+ * allocates nothing and never synchronises.
+ * Python: trpl_amd.mcmc.propose_subspace / subspace_gamma_table, run and run_tempered with kind="subspace",
+ * trpl_amd.device.mcmc_propose_subspace_device.
+ * ------------------------------------------------------------------------------------- */
+#define TRPL_MCMC_MAX_PAIRS 4
+#define TRPL_MCMC_MAX_CR 8
+int trpl_mcmc_propose_subspace_dev(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, int32_t A, double gamma,
+                                   const double *scale /*host [A]*/, int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol,
+                                   const double *lo /*host*/, const double *hi /*host*/, const int32_t *do_log /*host*/, uint32_t flags,
+                                   double *Up, double *Xp, int32_t *inside, int32_t pairs, int32_t ncr, const double *pcr /*host [ncr], nullable*/,
+                                   const double *gamma_tab /*host [pairs][A]*/, double e_width, int32_t *mask, int32_t *sel, void *stream);
+int trpl_mcmc_propose_subspace(const double *U, const double *partners, int64_t count, int64_t P, int64_t group, int32_t A, double gamma,
+                               const double *scale, int64_t chain0, uint64_t seed, uint32_t step, int32_t ncol, const double *lo,
+                               const double *hi, const int32_t *do_log, uint32_t flags, double *Up, double *Xp, int32_t *inside,
+                               int32_t pairs, int32_t ncr, const double *pcr /*nullable*/, const double *gamma_tab, double e_width,
+                               int32_t *mask, int32_t *sel, int32_t device, double *seconds);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the
  * measurement plan): S independent systems  ld[i] x[i-1] + d[i] x[i] + ud[i] x[i+1] = b[i],
  * i < L, the problem pcreduce solves (pvSimPCR.py:42-81), operands and result in HBM, arrays

@@ -1,6 +1,6 @@
 """The three kernels of the ensemble Metropolis sampler on resident tensors, in one process on one device.
 
-    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--fold] [--tempered [--rungs 16]] [--hastings] [--autocov]
+    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--fold] [--tempered [--rungs 16]] [--hastings] [--subspace] [--autocov]
                                [--out profiles/mcmc_bench.jsonl] [--label parent]
     python tools/bench_mcmc.py --host-loop [--out ...] [--label ...]
 
@@ -16,6 +16,10 @@ accept:      mcmc_accept_device of the same chains, about a third of the proposa
 --hastings:  the four Metropolis-Hastings kernels at the same rows and the same --rungs rungs, beside the three
              rung kernels they extend, in the same process: propose_stretch beside propose_rungs, accept_h beside accept_rungs,
              levels_h beside levels_rungs, and prior_term (two Gaussian columns, the rest flat).
+--subspace:  the subspace differential-evolution proposal at the same rows and the same --rungs rungs, beside
+             propose_rungs in the same process: propose_subspace with the defaults of mcmc.run (3 pairs, 3 classes, e_width 0.05), and
+             propose_subspace_anchor at the setting where it is propose_rungs bit for bit (one pair, one class, e_width 0).  The line
+             records the mean number of pairs and of moved coordinates, from which the extra partner rows follow.
 chain_stats: mcmc_chain_stats_device over a history of n steps of chains * A columns (one half of a split-R-hat: n / 2 steps).
 --autocov:   the two kernels of the effective sample size over the same chains * A columns, at L = 64 and L = 512 lags:
              mcmc_autocov_device over one half of a history (max(n / 2, L) steps, so L = 64 runs on chain_stats' own range) and
@@ -92,6 +96,7 @@ def main():
     ap.add_argument("--tempered", action="store_true")
     ap.add_argument("--rungs", type=int, default=16)
     ap.add_argument("--hastings", action="store_true")
+    ap.add_argument("--subspace", action="store_true")
     ap.add_argument("--autocov", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcmc_bench.jsonl"))
     a = ap.parse_args()
@@ -172,6 +177,19 @@ def main():
         calls["accept_h"] = lambda: tdev.mcmc_accept_h_device(Uh, Xh, LLh, Up, Xp, LLp, inside, hterm, ladder_h, 0, 42, 0, acch)
         calls["levels_h"] = lambda: tdev.mcmc_levels_h_device(LL, hterm, ladder_h, 0, 42, 0, level_h)
         calls["prior_term"] = lambda: tdev.mcmc_prior_term_device(U, Up, pm, psd, lnq, lnq)
+    if a.subspace:
+        K = a.rungs
+        if C % K or C // K < 2:
+            raise SystemExit("--chains must be a multiple of --rungs, two chains per rung at least")
+        Ups, Xps, inss, mask, sel = torch.empty_like(Up), torch.empty_like(Xp), torch.empty_like(inside), torch.empty_like(inside), torch.empty_like(inside)
+        tab, one = trpl_amd.mcmc.subspace_gamma_table(3, A), [[gamma] * A]
+        if not (a.tempered or a.hastings):                       # the kernel it extends, unless another switch has it already
+            Upq, Xpq, insq = torch.empty_like(Up), torch.empty_like(Xp), torch.empty_like(inside)
+            calls["propose_rungs"] = lambda: tdev.mcmc_propose_rungs_device(U, partners, C // K, gamma, 1e-3, 0, 42, 0, lo, hi, lg, Upq, Xpq, insq)
+        calls["propose_subspace_anchor"] = lambda: tdev.mcmc_propose_subspace_device(U, partners, C // K, one, 1e-3, 0, 42, 0, lo, hi, lg, Ups, Xps,
+                                                                                     inss, mask, sel, ncr=1, e_width=0.0)
+        calls["propose_subspace"] = lambda: tdev.mcmc_propose_subspace_device(U, partners, C // K, tab, 1e-3, 0, 42, 0, lo, hi, lg, Ups, Xps, inss,
+                                                                              mask, sel)
     floors = {}
     if a.autocov:
         tile, Q = trpl_amd._abi.lib().trpl_mcmc_autocov_tile(), C * A
@@ -198,6 +216,11 @@ def main():
     if a.hastings:
         line.update(rungs=a.rungs, hastings=True, stretch_inside_share=float(insh.double().mean().item()),
                     accepted_h_share=float(acch.double().mean().item()))
+    if a.subspace:                                               # the last call of the measurement is propose_subspace: its mask and sel
+        dsel = sum(((mask >> d) & 1).double().mean().item() for d in range(A))
+        line.update(rungs=a.rungs, subspace=True, subspace_mean_pairs=float((sel & 0xFF).double().mean().item()), subspace_mean_dsel=float(dsel),
+                    subspace_over_rungs=ms["propose_subspace"] / ms["propose_rungs"],
+                    subspace_anchor_over_rungs=ms["propose_subspace_anchor"] / ms["propose_rungs"])
     if a.autocov:
         line.update(autocov_tile=tile, autocov_floors=floors)
     return write(a, line)

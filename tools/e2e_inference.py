@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject [sample]] [--tempered K [--tf-hot x]]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--subspace [--pairs n] [--ncr n] [--adapt-cr]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject [sample]] [--tempered K [--tf-hot x]]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -55,6 +55,10 @@ stretch_a=a), a defaulting to 2: DESIGN.md section 30).  --prior NAME=CENTER:WID
 the free parameter NAME (a name of sampler.PARAM_NAMES): CENTER in the units of the search box, WIDTH one standard deviation in the
 same units on a linear parameter and in decades on a logarithmic one (mcmc.gaussian_prior).  "mcmc" then gains "stretch_a" and
 "prior"; both compose with --early-reject and --tempered.
+--subspace [--pairs n] [--ncr n] [--adapt-cr] (with --mcmc; not with --rw or --stretch) proposes by DREAM's subspace move instead
+(mcmc.run(kind="subspace", pairs=n, ncr=n, adapt_cr=...): DESIGN.md section 33); it composes with --fold, --early-reject and --tempered.
+"mcmc" then gains "subspace": pairs, ncr, the crossover shares pcr of the kept sweeps and mean_dsel, the mean number of coordinates
+a proposal moved.
 """
 import json
 import sys
@@ -118,13 +122,21 @@ if "--stretch" in sys.argv:
     except (IndexError, ValueError):
         STRETCH = 2.0
         del sys.argv[k]
+SUBSPACE = "--subspace" in sys.argv
+ADAPT_CR = "--adapt-cr" in sys.argv
+PAIRS, NCR = 3, 3
+for flag in ("--pairs", "--ncr"):
+    if flag in sys.argv:
+        k = sys.argv.index(flag)
+        PAIRS, NCR = (int(sys.argv[k + 1]), NCR) if flag == "--pairs" else (PAIRS, int(sys.argv[k + 1]))
+        del sys.argv[k:k + 2]
 PRIORS = {}
 while "--prior" in sys.argv:
     k = sys.argv.index("--prior")
     name, spec = sys.argv[k + 1].split("=")
     PRIORS[name] = tuple(float(v) for v in spec.split(":"))
     del sys.argv[k:k + 2]
-sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented", "--mcmc", "--fold", "--early-reject")]
+sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented", "--mcmc", "--fold", "--early-reject", "--subspace", "--adapt-cr")]
 import numpy as np
 import torch
 import trpl_amd
@@ -326,6 +338,8 @@ if MCMC:
     hastings = {}
     if STRETCH is not None:
         hastings.update(kind="stretch", stretch_a=STRETCH)
+    if SUBSPACE:
+        hastings.update(kind="subspace", pairs=PAIRS, ncr=NCR, adapt_cr=ADAPT_CR)
     if PRIORS:                                                   # centres and linear widths in the box's units, like lo and hi
         centre, width = np.array(lo, dtype=np.float64), np.full(len(lo), np.inf)
         for name, (c0, w0) in PRIORS.items():
@@ -349,6 +363,7 @@ if MCMC:
         minfo = {"accept": list(rung_info["accept"][:, 0]), "outside": float(rung_info["outside"][0]), "folded": float(rung_info["folded"][0])}
         if EARLY:
             minfo["early_reject"] = float(rung_info["early_reject"][0])
+        minfo.update({k: rung_info[k] for k in ("pairs", "ncr", "pcr", "mean_dsel") if k in rung_info})
     else:
         t_run = time.time()
         ch = mcmc.run(fused_chain, X0, LL0, lo, hi, lg, tf=tf, **opts)
@@ -363,7 +378,7 @@ if MCMC:
     q_imp = posterior.quantiles(V.cpu().numpy(), W.cpu().numpy(), qs)
     out["seconds"]["mcmc"] = sync() - t11
     act = [int(i) for i in trpl_amd.refine.active_columns(lo, hi)]
-    out["mcmc"] = {"chains": CHAINS, "sweeps": SWEEPS, "kept_sweeps": int(ch.U.shape[0]), "proposal": "rw %g" % RW if RW is not None else "stretch %g" % STRETCH if STRETCH is not None else "de",
+    out["mcmc"] = {"chains": CHAINS, "sweeps": SWEEPS, "kept_sweeps": int(ch.U.shape[0]), "proposal": "rw %g" % RW if RW is not None else "stretch %g" % STRETCH if STRETCH is not None else "subspace" if SUBSPACE else "de",
                    "distinct_starts": int(np.unique(LL0).size),
                    "acceptance": float(np.mean(minfo["accept"])), "acceptance_kept": float(np.mean(minfo["accept"][burn:])),
                    "outside_share_of_proposals": minfo["outside"], "worst_rhat": float(np.nanmax(rhat)),
@@ -374,6 +389,12 @@ if MCMC:
     out["mcmc"]["system_timesteps"] = work["iters"]
     if STRETCH is not None:
         out["mcmc"]["stretch_a"] = STRETCH
+    if SUBSPACE:
+        out["mcmc"]["subspace"] = {"pairs": minfo["pairs"], "ncr": minfo["ncr"], "pcr": [float(v) for v in minfo["pcr"]],
+                                   "mean_dsel": float(minfo["mean_dsel"]), "adapt_cr": ADAPT_CR}
+        print("mcmc: subspace, %d pairs, %d classes with shares %s%s: %.2f coordinates moved per proposal"
+              % (PAIRS, NCR, ["%.3f" % v for v in minfo["pcr"]], " (adapted during the burn sweeps)" if ADAPT_CR else "", minfo["mean_dsel"]),
+              file=sys.stderr)
     if PRIORS:
         out["mcmc"]["prior"] = {name: {"center": c0, "width": w0} for name, (c0, w0) in PRIORS.items()}
     if EARLY:
