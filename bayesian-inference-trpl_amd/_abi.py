@@ -77,6 +77,7 @@ CORNER_PRIMARY, CORNER_MAX_COLS, CORNER_MAX_BINS = 13, 19, 128
 REFINE_MAX_DIMS, REFINE_MAX_PARENTS = 16, 1 << 20      # TRPL_REFINE_MAX_DIMS, TRPL_REFINE_MAX_PARENTS
 MCMC_FOLD = 0x10              # TRPL_MCMC_FOLD: trpl_mcmc_propose reflects a proposal back at the faces of the unit cube
 MCMC_MAX_RUNGS = 64           # TRPL_MCMC_MAX_RUNGS: temperatures of one trpl_mcmc_*_rungs / trpl_mcmc_swap call
+MCMC_EVIDENCE_SUMS = 6        # TRPL_MCMC_EVIDENCE_SUMS: the columns of a row of trpl_mcmc_evidence_sums' sums
 MCMC_MAX_PAIRS, MCMC_MAX_CR = 4, 8      # TRPL_MCMC_MAX_PAIRS, TRPL_MCMC_MAX_CR: difference pairs and crossover classes of trpl_mcmc_propose_subspace
 SEED_MASK, STEP_MASK = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF      # a uint64_t seed and a uint32_t step of the trpl_mcmc_* calls, from any int
 
@@ -262,6 +263,8 @@ SIGNATURES = {
                                        _i32, _i32, _vp, _vp, _f64, _vp, _vp, _vp],
     "trpl_mcmc_propose_subspace": [_vp, _vp, _i64, _i64, _i64, _i32, _f64, _vp, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp,
                                    _i32, _i32, _vp, _vp, _f64, _vp, _vp, _i32, _pd],
+    "trpl_mcmc_evidence_sums_dev": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
+    "trpl_mcmc_evidence_sums": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _pd],
     "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
     "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
 }

@@ -925,6 +925,23 @@ def mcmc_autocov_pool_device(s, M, A, pooled):
         _chk(s, torch.float64, "s"), s.shape[0], s.shape[1], int(M), int(A), _chk(pooled, torch.float64, "pooled"), _stream()))
 
 
+def mcmc_evidence_sums_device(LL, tf, t0, t1, ext, sums):
+    """trpl_mcmc_evidence_sums_dev: ext (K, 2) and sums (K, B, 6) f64 <- the kept LL (K, n, C) f64 of the K rungs of the host ladder tf
+    (K,), which stays where it is, over the steps [t0, t1) in B = sums.shape[1] blocks of (t1 - t0) / B steps: the extrema of each
+    rung and per block [sum LL, up, up2, down, down2, count above -inf], the stepping-stone sums of mcmc.log_evidence_ratios in one
+    fixed association (include/trpl.h has the rule)."""
+    import torch
+    tf = _ladder(tf)
+    if LL.dim() != 3 or LL.shape[0] != tf.size:
+        raise ValueError("LL must be (K, n, C) with the ladder's K = %d" % tf.size)
+    K = tf.size
+    if tuple(ext.shape) != (K, 2) or sums.dim() != 3 or sums.shape[0] != K or sums.shape[2] != _abi.MCMC_EVIDENCE_SUMS:
+        raise ValueError("ext must be (K, 2) and sums (K, B, %d)" % _abi.MCMC_EVIDENCE_SUMS)
+    _abi.check(_abi.lib().trpl_mcmc_evidence_sums_dev(
+        _chk(LL, torch.float64, "LL"), K, LL.shape[1], LL.shape[2], int(t0), int(t1), sums.shape[1], _abi.ptr(tf),
+        _chk(ext, torch.float64, "ext"), _chk(sums, torch.float64, "sums"), _stream()))
+
+
 def credible_interval_device(x, W, lo=0.025, hi=0.975):
     """utils.py:185-196 on the device: sort by x, cumulate the weights, last point below `lo` and first
     above `hi` (torch.sort / cumsum: library plumbing, no custom kernel)."""

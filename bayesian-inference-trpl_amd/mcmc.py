@@ -434,6 +434,78 @@ def ess_from_sums(mean, m2, pooled, m):
     return ess, dict(tau=tau, var_plus=var_plus, rho=rho, K=K, truncated=truncated)
 
 
+def evidence_sums(LL, tf, t0=0, t1=None, blocks=1, device=0, info=None):
+    """(ext (K, 2), sums (K, blocks, 6)): from the kept LL (K, n, C) of the K rungs of the ladder tf (K,), over the steps [t0, t1) cut
+    into `blocks` blocks of (t1 - t0) / blocks consecutive steps, the [maximum, minimum] of each rung and per block [sum LL, up, up2,
+    down, down2, count above -inf] (trpl_mcmc_evidence_sums; include/trpl.h has the terms, the rule of -inf and the one association
+    of every sum).  What log_evidence_ratios takes.  t1 defaults to n."""
+    LL, tf = _f64(LL), _ladder(tf)
+    if LL.ndim != 3 or LL.shape[0] != tf.size:
+        raise ValueError("LL must be (K, n, C) with the ladder's K = %d" % tf.size)
+    K, n, C = LL.shape
+    t1 = n if t1 is None else int(t1)
+    B = int(blocks)
+    ext, sums = np.empty((K, 2)), np.empty((K, max(B, 0), _abi.MCMC_EVIDENCE_SUMS))
+    _timed("trpl_mcmc_evidence_sums", info, _abi.ptr(LL), K, n, C, int(t0), t1, B, _abi.ptr(tf), _abi.ptr(ext), _abi.ptr(sums), int(device))
+    return ext, sums
+
+
+def log_evidence_ratios(ext, sums, ladder):
+    """The log-evidence differences between the adjacent rungs of a ladder (K,) from evidence_sums' ext (K, 2) and sums (K, B, 6).
+    Pure numpy, one rule (restated in include/trpl.h).  With Z(tf) the integral of exp(LL / tf) p(u) over the cube, delta_k =
+    1 / tf_k - 1 / tf_(k+1), N_k the count of a rung's values above -inf (a state at -inf has no mass at any temperature), every
+    sum over the blocks in ascending b, for each pair k, k + 1 three estimates of ln Z(tf_k) - ln Z(tf_(k+1)):
+        forward = delta_k a  + ln(up_(k+1) / N_(k+1))      stepping-stone sampling from the hotter rung (Xie et al. 2011); a, a' are the
+        reverse = delta_k a' - ln(down_k / N_k)            the same from the colder rung                         kernel's centres
+        ti      = delta_k (mean LL_k + mean LL_(k+1)) / 2  the trapezoid of thermodynamic integration (Lartillot & Philippe 2006)
+    forward is the stable direction (its terms are bounded by the hot rung's best state); reverse is carried by the colder rung's worst
+    states and is biased upward when they are rare: where the two disagree by more than their errors, the rungs are too far apart
+    or the run has not equilibrated (DESIGN.md section 34 has a case).
+    ti has the trapezoid's discretisation bias, which no error bar shows.  Each estimate has a leave-one-block-out jackknife
+    standard error over the B blocks (NaN for B = 1).  term_ess (K - 1, 2) = (sum e)^2 / (N sum e^2) of the forward and the reverse
+    sum: the share of the states that carry it, the warning sign of a stepping stone that rests on a handful.  A Gaussian prior= of
+    the run is common to the rungs and cancels in every difference.
+    Returns dict(delta, N (K,), forward, reverse, ti and <name>_se (K - 1,), term_ess, <name>_total and <name>_total_se: the pairs
+    added in ascending k from 0.0 -- ln Z(tf_0) - ln Z(tf_(K-1)) -- and their errors in quadrature; K = 1: empty and 0.0)."""
+    tf = _ladder(ladder)
+    K = tf.size
+    ext, sums = np.asarray(ext, dtype=np.float64), np.asarray(sums, dtype=np.float64)
+    if ext.shape != (K, 2) or sums.ndim != 3 or sums.shape[0] != K or sums.shape[1] < 1 or sums.shape[2] != _abi.MCMC_EVIDENCE_SUMS:
+        raise ValueError("ext must be (K, 2) and sums (K, B >= 1, %d) with the ladder's K = %d" % (_abi.MCMC_EVIDENCE_SUMS, K))
+    B = sums.shape[1]
+    delta = 1.0 / tf[:-1] - 1.0 / tf[1:]
+    a_up = np.where(delta >= 0.0, ext[1:, 0], ext[1:, 1])       # the centre of up of rung k + 1, of down of rung k
+    a_down = np.where(delta >= 0.0, ext[:-1, 1], ext[:-1, 0])
+
+    def estimates(S):                                            # S (K, 6): a rung's sums over some of the blocks
+        N = S[:, 5]
+        mean = S[:, 0] / N
+        forward = np.where(delta == 0.0, 0.0, delta * a_up) + np.log(S[1:, 1] / N[1:])
+        reverse = np.where(delta == 0.0, 0.0, delta * a_down) - np.log(S[:-1, 3] / N[:-1])
+        return np.stack([forward, reverse, delta * (mean[:-1] + mean[1:]) / 2.0])
+
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        head, tail = np.zeros((B + 1, K, sums.shape[2])), np.zeros((B + 1, K, sums.shape[2]))
+        for b in range(B):                                       # head[b]: the blocks before b; tail[b]: the blocks from b on
+            head[b + 1] = head[b] + sums[:, b]
+            tail[B - 1 - b] = sums[:, B - 1 - b] + tail[B - b]
+        S = head[B]
+        est = estimates(S)
+        if B > 1:
+            left_out = np.stack([estimates(head[b] + tail[b + 1]) for b in range(B)])        # (B, 3, K - 1)
+            se = np.sqrt((B - 1.0) / B * np.sum((left_out - np.mean(left_out, axis=0)) ** 2, axis=0))
+        else:
+            se = np.full(est.shape, np.nan)
+        term_ess = np.stack([S[1:, 1] ** 2 / (S[1:, 5] * S[1:, 2]), S[:-1, 3] ** 2 / (S[:-1, 5] * S[:-1, 4])], axis=1)
+    out = dict(delta=delta, N=S[:, 5].copy(), term_ess=term_ess, blocks=B)
+    for i, name in enumerate(("forward", "reverse", "ti")):
+        total, var = 0.0, 0.0
+        for k in range(K - 1):
+            total, var = total + float(est[i, k]), var + float(se[i, k]) ** 2
+        out.update({name: est[i], name + "_se": se[i], name + "_total": total, name + "_total_se": float(np.sqrt(var))})
+    return out
+
+
 def start(X, LL, C, minX, maxX, do_log, sim_flags=None, tf=1.0, offset=0.5, log_ratio=None, device=0):
     """(X0, U0, LL0): C starting states drawn from an importance-weighted set -- a first generation (X, LL), or a refined
     Population's log_ratio() as (X, LL, log_ratio=) -- by refine.resample of posterior.weights at temperature tf, with their unit
@@ -848,6 +920,45 @@ class Tempered:
     def samples(self, burn=0, thin=1):
         """rung(0).samples(burn, thin): ladder[0] is the temperature the caller asked for."""
         return self._chains[0].samples(burn, thin)
+
+    def log_evidence(self, burn=0, blocks=16, base=None):
+        """The log-evidence estimates of the run (log_evidence_ratios has the rule and the keys): the kept LL of the K rungs from the
+        kept sweep `burn` on, in `blocks` blocks of consecutive sweeps for the jackknife errors, through one evidence_sums call --
+        the hot rungs' histories give every ratio Z(ladder[k]) / Z(ladder[k + 1]) without another solve.  The oldest kept sweeps
+        after burn are dropped until `blocks` divides the range: dropped says how many, t0 and t1 are the range.  K = 1: no call,
+        empty ratios and totals of 0.0.
+
+        base = (LL, tf_hot_check) or (LL, tf_hot_check, log_ratio) of an importance run -- the uniform first generation, or a
+        refined Population's log_ratio() -- anchors the ladder: base_ln_z = posterior.log_evidence(LL, ladder[-1], log_ratio) is ln Z
+        at the hottest rung (base_se, base_ess beside it), and ln_z = dict(forward, reverse, ti) the absolute ln Z(ladder[0]) =
+        base_ln_z + <name>_total, ln_z_se the two errors in quadrature.  tf_hot_check must be ladder[-1] (ValueError): the base is
+        only trustworthy at the temperature its effective sample size was checked at (posterior.tf_for_ess).  A Gaussian prior= of
+        the run is common to the rungs and cancels in every ratio; only the base needs it: pass log_ratio = -ln p(u) of the
+        base's draws (plus the Population's log_ratio, if refined)."""
+        K, burn, blocks = len(self._chains), int(burn), int(blocks)
+        if base is not None:
+            if len(base) not in (2, 3):
+                raise ValueError("base must be (LL, tf_hot_check) or (LL, tf_hot_check, log_ratio)")
+            if float(base[1]) != float(self.ladder[-1]):
+                raise ValueError("tf_hot_check = %r is not the hottest rung's temperature ladder[-1] = %r" % (float(base[1]), float(self.ladder[-1])))
+        n = self._chains[0].LL.shape[0]
+        if burn < 0 or blocks < 1 or n - burn < blocks:
+            raise ValueError("blocks=%d must be >= 1 and at most the %d kept sweeps left after burn=%d" % (blocks, max(n - burn, 0), burn))
+        dropped = (n - burn) % blocks
+        t0 = burn + dropped
+        if K == 1:
+            ext, sums = np.full((1, 2), np.nan), np.zeros((1, blocks, _abi.MCMC_EVIDENCE_SUMS))
+        else:
+            ext, sums = evidence_sums(np.stack([c.LL for c in self._chains]), self.ladder, t0, n, blocks, device=self._chains[0].device)
+        out = log_evidence_ratios(ext, sums, self.ladder)
+        out.update(dropped=dropped, t0=t0, t1=n)
+        if base is not None:
+            ln_z, binfo = posterior.log_evidence(base[0], float(self.ladder[-1]), base[2] if len(base) == 3 else None,
+                                                 device=self._chains[0].device)
+            out.update(base_ln_z=ln_z, base_se=binfo["se"], base_ess=binfo["ess"],
+                       ln_z={name: ln_z + out[name + "_total"] for name in ("forward", "reverse", "ti")},
+                       ln_z_se={name: float(np.sqrt(out[name + "_total_se"] ** 2 + binfo["se"] ** 2)) for name in ("forward", "reverse", "ti")})
+        return out
 
 
 def run_tempered(loglik, X0, LL0, minX, maxX, do_log, ladder, sim_flags=None, sweeps=1000, swap_every=1, kind="de", gamma=None,

@@ -455,6 +455,39 @@ def tf_for_ess(LL, target, log_ratio=None, lo=1.0, hi=1e4, rtol=1e-6, device=0, 
     return tf, ess
 
 
+def log_evidence(LL, tf, log_ratio=None, device=0):
+    """(ln_z, info): the log of the marginal likelihood Z(tf) = integral of exp(LL(u) / tf) p(u) du from an importance run: the log of
+    the mean over the samples with no NaN of exp(LL / tf - log_ratio).  LL (S,) of draws from the prior box (log_ratio None), or of a
+    refined set with its Population.log_ratio(); with an informative prior p on uniform draws, log_ratio = -ln p(u).  tf a scalar, or
+    an array of at most TF_SCAN_MAX temperatures, which gives arrays back.
+
+    Formed from ONE tf_scan call: its raw normalising sum is the sum of exp(((e - max e) + 1000 ln 2) - ln S), e = LL / tf - log_ratio,
+    so ln_z = max e - 1000 ln 2 + ln S + ln(raw sum) - ln N with N the count of samples with no NaN.  info: ess, the effective sample
+    size (sum W)^2 / sum W^2 of the weights; se = sqrt(1 / ess - 1 / N), the standard error of ln_z (the relative error of the mean);
+    count = N.  A NaN sample is left out of ln_z and of N but makes ess and se NaN, as it does in tf_scan: drop such samples first
+    (filter_nan) where the error is wanted.  The estimate is trustworthy where ess is large -- at the temperature tf_for_ess puts the hottest rung of a ladder,
+    from which mcmc.Tempered.log_evidence bridges down to the temperature wanted."""
+    import math
+    LL = _f64(LL)
+    scalar = np.ndim(tf) == 0
+    tfs = np.atleast_1d(_f64(tf))
+    if LL.ndim != 1 or LL.size < 1:
+        raise ValueError("LL must be one-dimensional and not empty")
+    if tfs.ndim != 1 or not 1 <= tfs.size <= TF_SCAN_POINTS:
+        raise ValueError("tf must be a scalar or (K,), 1 <= K <= %d temperatures" % TF_SCAN_POINTS)
+    st = tf_scan(LL, tfs, device=device, log_ratio=log_ratio)["stats"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if log_ratio is None:
+            top, raw, count, ess = st[:, 0], st[:, 1], st[:, 3], 1.0 / st[:, 2]
+        else:
+            top, raw, count, ess = st[:, 0], st[:, 1], st[:, 4], st[:, 5]
+        ln_z = top - 1000.0 * math.log(2.0) + math.log(LL.size) + np.log(raw) - np.log(count)
+        se = np.sqrt(np.maximum(1.0 / ess - 1.0 / count, 0.0))
+    if scalar:
+        return float(ln_z[0]), dict(ess=float(ess[0]), se=float(se[0]), count=float(count[0]))
+    return ln_z, dict(ess=ess.copy(), se=se, count=count.copy())
+
+
 # ---- the corner: every marginal of a finished run in one device call (trpl_corner, csrc/corner.hip) ----
 # the 13 columns of the exported X under the package's names (sampler.PARAM_NAMES; marginalization_visual.py:67-70 lists them
 # in this order) and the six secondary parameters of the same list, :69-70; the position is the TRPL_COL_* code

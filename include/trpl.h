@@ -1656,6 +1656,61 @@ int trpl_mcmc_propose_subspace(const double *U, const double *partners, int64_t 
                                int32_t *mask, int32_t *sel, int32_t device, double *seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_mcmc_evidence_sums -- the sums of the LOG-EVIDENCE estimates of a tempered run: what stepping-stone sampling (Xie, Lewis, Fan,
+ * Kuo & Chen 2011) and thermodynamic integration (Lartillot & Philippe 2006) need of the kept likelihoods of the K rungs, so that the
+ * hot rungs of trpl_mcmc_swap's ladder also give every ratio Z(tf_k) / Z(tf_k+1) of the marginal likelihood
+ *     Z(tf) = integral over the cube of exp(LL(u) / tf) p(u) du
+ * without another solve.  (csrc/mcmc_evidence.hip)
+ *
+ * LL [K][n][C] in, contiguous and rung-major (the kept history of trpl_amd.mcmc.run_tempered), the steps [t0, t1) cut into B blocks
+ * of w = (t1 - t0) / B consecutive steps; tf [K] on the host, copied into the kernel argument like trpl_mcmc_swap's.  With
+ *     delta_k = 1.0 / tf[k] - 1.0 / tf[k + 1]                                      trpl_mcmc_swap's expression
+ * ext [K][2] out: the maximum and the minimum of the rung's LL over the range, a zero as +0.0; both NaN when a value of the rung in
+ * the range is NaN.  sums [K][B][TRPL_MCMC_EVIDENCE_SUMS] out, for block b of rung k over its w C values x:
+ *     0  sum of x
+ *     1  up    = sum of e,   e = exp(delta_(k-1) * (x - a)),  a the rung's maximum if delta_(k-1) >= 0, else its minimum; +0.0 for k = 0
+ *     2  up2   = sum of e * e
+ *     3  down  = sum of e',  e' = exp((-delta_k) * (x - a')), a' the rung's minimum if delta_k >= 0, else its maximum; +0.0 for k = K - 1
+ *     4  down2 = sum of e' * e'
+ *     5  the number of x above -inf, as a double
+ * up is the rung's stepping-stone sum towards rung k - 1, down the reverse estimate towards rung k + 1; the centring keeps every
+ * exponent <= 0.  The exponent is a subtraction and a product in fp64, one rounding each, no contraction.  THE RULE OF -inf AND
+ * ZERO: an x = -inf is not put through the expression; it gives +0.0 to a sum whose coefficient (delta_(k-1) for up, -delta_k for
+ * down) is >= 0 and +inf to one whose coefficient is < 0, and -inf to the sum of x.  A coefficient of +-0.0 (two equal
+ * temperatures) gives 1.0 for every x above -inf, so up = down = slot 5 exactly.  A NaN makes the extrema and every sum of every
+ * block of its own rung NaN and touches no other rung.
+ * Every sum has one association, a function of (w, C) alone: one workgroup of 256 threads per (k, b); thread j adds the elements j,
+ * j + 256, .. of the block in (t, c) row-major order, ascending from +0.0; the 256 partials are added by the halving tree
+ * p[j] = p[j] + p[j + s], s = 128 .. 1.  No atomics: the same call gives the same bits on every run and every device.  Two
+ * passes: the extrema (per block into the block's own row of sums, then per rung into ext), then the sums, which overwrite those
+ * rows; nothing but ext and sums is written, nothing outside the rows [t0, t1) is read.  The host-buffer form copies the steps of
+ * the range only.
+ *
+ * THE ESTIMATOR (trpl_amd.mcmc.log_evidence_ratios; numpy, one rule).  N_k = slot 5 summed over the blocks, the sums below over the
+ * blocks in ascending b, mean_k = (sum of slot 0) / N_k.  For every adjacent pair k, k + 1 three estimates of
+ * ln Z(tf_k) - ln Z(tf_k+1):
+ *     forward = delta_k * a  + ln(up_(k+1) / N_(k+1))      from the hotter rung, a its centre
+ *     reverse = delta_k * a' - ln(down_k / N_k)            from the colder rung, a' its centre
+ *     ti      = delta_k * (mean_k + mean_(k+1)) / 2        the trapezoid of thermodynamic integration
+ * (delta_k = 0: the product with the centre is taken as 0).  Each has a leave-one-block-out jackknife standard error over the B
+ * blocks, sqrt((B - 1) / B * sum over b of (theta_(-b) - mean of theta_(-b))^2), NaN for B = 1, and each exponential sum its
+ * term_ess = (sum e)^2 / (N sum e^2), the share of the states that carry it.  The totals over the ladder add the pairs in
+ * ascending k from 0.0 and their errors in quadrature.  A prior common to the rungs cancels in every ratio.
+ *
+ * Refused with TRPL_ERR_ARG before a device is touched, the message naming the argument: a NULL LL, tf, ext or sums; K outside
+ * [1, TRPL_MCMC_MAX_RUNGS]; n < 1; C < 1 (or K n C above 2^60 - 1); a range that does not satisfy 0 <= t0 < t1 <= n; B < 1 or B not
+ * dividing t1 - t0; a tf[k] that is not finite and > 0; K B above 2^31 - 1 workgroups.  The _dev call takes device pointers (tf
+ * excepted), allocates nothing and never synchronises.
+ * Python: trpl_amd.mcmc.evidence_sums / log_evidence_ratios, Tempered.log_evidence, trpl_amd.posterior.log_evidence (the base of an
+ * absolute ln Z), trpl_amd.device.mcmc_evidence_sums_device.
+ * ------------------------------------------------------------------------------------- */
+#define TRPL_MCMC_EVIDENCE_SUMS 6
+int trpl_mcmc_evidence_sums_dev(const double *LL, int32_t K, int64_t n, int64_t C, int64_t t0, int64_t t1, int64_t B,
+                                const double *tf /*host [K]*/, double *ext, double *sums, void *stream);
+int trpl_mcmc_evidence_sums(const double *LL, int32_t K, int64_t n, int64_t C, int64_t t0, int64_t t1, int64_t B, const double *tf,
+                            double *ext, double *sums, int32_t device, double *seconds);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_pcr_solve_batched_dev -- the stand-alone batched tridiagonal solve (unit U1 of the
  * measurement plan): S independent systems  ld[i] x[i-1] + d[i] x[i] + ud[i] x[i+1] = b[i],
  * i < L, the problem pcreduce solves (pvSimPCR.py:42-81), operands and result in HBM, arrays

@@ -1,6 +1,6 @@
 """The three kernels of the ensemble Metropolis sampler on resident tensors, in one process on one device.
 
-    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--fold] [--tempered [--rungs 16]] [--hastings] [--subspace] [--autocov]
+    python tools/bench_mcmc.py [--chains 65536] [--A 10] [--n 256] [--reps 5] [--fold] [--tempered [--rungs 16]] [--hastings] [--subspace] [--autocov] [--evidence]
                                [--out profiles/mcmc_bench.jsonl] [--label parent]
     python tools/bench_mcmc.py --host-loop [--out ...] [--label ...]
 
@@ -26,6 +26,9 @@ chain_stats: mcmc_chain_stats_device over a history of n steps of chains * A col
              mcmc_autocov_pool_device over its s.  The line records beside each time the two floors it is to be read against
              (DESIGN.md section 28): H read once per lag tile and s written once at 6.1 TB/s, and two fp64 instructions per term
              at 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz.
+--evidence:  the sums of the log-evidence estimates (mcmc_evidence_sums_device) over the kept LL of 16 rungs on
+             geometric_ladder(1, 64, 16) in 16 blocks, at 1024 chains x 100 steps (the oldest 4 trimmed, as Tempered.log_evidence
+             trims them) and at 65536 chains x 128 steps, each beside its floor: the range of LL read twice at 6.1 TB/s.
 --host-loop: nothing of the above.  Wall-clock seconds per sweep of mcmc.run and of mcmc.run_tempered (4 rungs on geometric_ladder(1, 64, 4))
              through the host-buffer calls, with a numpy toy likelihood: 256 chains, a unit box of A = 3 columns, 200 sweeps -- what
              the sampler's own Python and staging cost per sweep, the likelihood being next to nothing.  One warm-up of 10 sweeps,
@@ -98,6 +101,7 @@ def main():
     ap.add_argument("--hastings", action="store_true")
     ap.add_argument("--subspace", action="store_true")
     ap.add_argument("--autocov", action="store_true")
+    ap.add_argument("--evidence", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcmc_bench.jsonl"))
     a = ap.parse_args()
     if a.host_loop:
@@ -204,6 +208,17 @@ def main():
             floors["autocov_L%d" % L] = {"steps": m, "terms": terms, "fp64_floor_ms": 2.0 * terms / (256 * 4 * 16 * 2.4e9) * 1e3,
                                          "hbm_floor_ms": 8.0 * Q * (tiles * m + m + L) / 6.1e12 * 1e3}
             floors["autocov_pool_L%d" % L] = {"hbm_floor_ms": 8.0 * L * (Q + A) / 6.1e12 * 1e3}
+    if a.evidence:
+        Ke, Be = 16, 16
+        ladder_e = trpl_amd.mcmc.geometric_ladder(1.0, 64.0, Ke)
+        for Ce, ne in ((1024, 100), (1 << 16, 128)):
+            t0e = ne % Be
+            LLe = -10.0 * torch.rand((Ke, ne, Ce), generator=g, **f64)
+            ext_e, sums_e = torch.empty((Ke, 2), **f64), torch.empty((Ke, Be, trpl_amd._abi.MCMC_EVIDENCE_SUMS), **f64)
+            name = "evidence_C%d_n%d" % (Ce, ne)
+            calls[name] = lambda LLe=LLe, t0e=t0e, ne=ne, ext_e=ext_e, sums_e=sums_e: tdev.mcmc_evidence_sums_device(LLe, ladder_e, t0e, ne, ext_e,
+                                                                                                                   sums_e)
+            floors[name] = {"rungs": Ke, "blocks": Be, "steps": ne - t0e, "hbm_floor_ms": 2.0 * 8.0 * Ke * (ne - t0e) * Ce / 6.1e12 * 1e3}
     ms, passes = measure(calls, a.reps)
     torch.cuda.synchronize()
     line = {"bench": "mcmc", "device": torch.cuda.get_device_name(0), "chains": C, "A": A, "ncol": ncol, "n": a.n, "reps": a.reps, "ms": ms,
@@ -222,7 +237,9 @@ def main():
                     subspace_over_rungs=ms["propose_subspace"] / ms["propose_rungs"],
                     subspace_anchor_over_rungs=ms["propose_subspace_anchor"] / ms["propose_rungs"])
     if a.autocov:
-        line.update(autocov_tile=tile, autocov_floors=floors)
+        line.update(autocov_tile=tile, autocov_floors={k: v for k, v in floors.items() if k.startswith("autocov")})
+    if a.evidence:
+        line.update(evidence_floors={k: v for k, v in floors.items() if k.startswith("evidence")})
     return write(a, line)
 
 

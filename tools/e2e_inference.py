@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--subspace [--pairs n] [--ncr n] [--adapt-cr]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject [sample]] [--tempered K [--tf-hot x]]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--subspace [--pairs n] [--ncr n] [--adapt-cr]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject [sample]] [--tempered K [--tf-hot x] [--evidence]]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -50,6 +50,11 @@ the same numbers are printed.  --early-reject sample spends each proposal's leve
 --tf-hot x sets the hottest temperature; the default is the temperature at which the importance run reaches an effective sample
 size of 64 (posterior.tf_for_ess).  "mcmc" is the cold rung's, as without the flag; "tempered" beside it holds the ladder and, per
 rung, acceptance and worst R-hat, the swap rates and the seconds, which are printed.
+--evidence (with --tempered) adds the log-evidence estimates of the run (Tempered.log_evidence: DESIGN.md section 34): the
+differences ln Z(tf) - ln Z(tf_hot) by stepping-stone sampling from the hotter and from the colder rung of each pair and by
+thermodynamic integration, with their block-jackknife errors and the smallest term_ess, the base ln Z(tf_hot) of the importance run
+(posterior.log_evidence at the hottest rung; with --prior its log-ratio is minus the sampler's unnormalised log prior) and the
+absolute ln Z(tf) of each estimator, under "tempered" as "evidence" and printed side by side.
 --stretch [a] (with --mcmc; not with --rw or --fold) proposes by the affine-invariant stretch move instead (mcmc.run(kind="stretch",
 stretch_a=a), a defaulting to 2: DESIGN.md section 30).  --prior NAME=CENTER:WIDTH (with --mcmc; repeatable) puts a Gaussian prior on
 the free parameter NAME (a name of sampler.PARAM_NAMES): CENTER in the units of the search box, WIDTH one standard deviation in the
@@ -88,6 +93,7 @@ if "--shrink" in sys.argv:
     del sys.argv[k:k + 2]
 MCMC = "--mcmc" in sys.argv
 FOLD = "--fold" in sys.argv
+EVIDENCE = "--evidence" in sys.argv
 EARLY = "--early-reject" in sys.argv
 if EARLY and sys.argv.index("--early-reject") + 1 < len(sys.argv) and sys.argv[sys.argv.index("--early-reject") + 1] == "sample":
     del sys.argv[sys.argv.index("--early-reject") + 1]
@@ -136,7 +142,7 @@ while "--prior" in sys.argv:
     name, spec = sys.argv[k + 1].split("=")
     PRIORS[name] = tuple(float(v) for v in spec.split(":"))
     del sys.argv[k:k + 2]
-sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented", "--mcmc", "--fold", "--early-reject", "--subspace", "--adapt-cr")]
+sys.argv = [a for a in sys.argv if a not in ("--find-tf", "--predictive", "--quantiles", "--corner", "--refine", "--oriented", "--mcmc", "--fold", "--early-reject", "--subspace", "--adapt-cr", "--evidence")]
 import numpy as np
 import torch
 import trpl_amd
@@ -428,6 +434,31 @@ if MCMC:
                   % (k, ladder[k], out["mcmc"]["tempered"]["acceptance"][k], worst[k],
                      "%.3f" % tempered.swap_rate[k] if k + 1 < TEMPERED else "-"), file=sys.stderr)
         print("mcmc: tempered, %d rungs: %.2f s, %.4f s per sweep" % (TEMPERED, t_run, t_run / SWEEPS), file=sys.stderr)
+        if EVIDENCE:
+            Pn = P.cpu().numpy()
+            base_lnr = None
+            if PRIORS:                                           # the sampler's prior term, unnormalised: -ln p(u) of the base's draws
+                Ub, _ = trpl_amd.refine.unit_coords(X.cpu().numpy(), lo, hi, lg)
+                p_mean, p_sd = hastings["prior"]
+                base_lnr = 0.5 * np.sum(((Ub - p_mean) / p_sd) ** 2, axis=1)
+            ev = tempered.log_evidence(blocks=16, base=(np.where(np.isnan(Pn), -np.inf, Pn), TF_HOT, base_lnr))
+            names3 = ("forward", "reverse", "ti")
+            out["mcmc"]["tempered"]["evidence"] = {
+                "blocks": ev["blocks"], "dropped_sweeps": ev["dropped"], "min_term_ess": float(ev["term_ess"].min()),
+                "base_ln_z": ev["base_ln_z"], "base_se": ev["base_se"], "base_ess": ev["base_ess"],
+                **{n: {"total": ev[n + "_total"], "total_se": ev[n + "_total_se"], "pairs": [float(v) for v in ev[n]],
+                       "pairs_se": [float(v) for v in ev[n + "_se"]], "ln_z": ev["ln_z"][n], "ln_z_se": ev["ln_z_se"][n]} for n in names3}}
+            print("evidence: base ln Z(tf_hot = %.4g) = %.4f +- %.4f (importance run, ess %.1f)" % (TF_HOT, ev["base_ln_z"], ev["base_se"], ev["base_ess"]),
+                  file=sys.stderr)
+            print("evidence: %d blocks of %d kept sweeps (%d dropped), smallest term_ess %.4f"
+                  % (ev["blocks"], (ev["t1"] - ev["t0"]) // ev["blocks"], ev["dropped"], ev["term_ess"].min()), file=sys.stderr)
+            for n in names3:
+                print("evidence: %-7s ln Z(tf) - ln Z(tf_hot) = %12.4f +- %.4f   ln Z(tf = %.4g) = %12.4f +- %.4f"
+                      % (n, ev[n + "_total"], ev[n + "_total_se"], tf, ev["ln_z"][n], ev["ln_z_se"][n]), file=sys.stderr)
+            for k in range(TEMPERED - 1):
+                print("evidence: pair %2d-%-2d  forward %11.4f +- %.4f  reverse %11.4f +- %.4f  ti %11.4f +- %.4f  term_ess %.4f %.4f"
+                      % (k, k + 1, ev["forward"][k], ev["forward_se"][k], ev["reverse"][k], ev["reverse_se"][k], ev["ti"][k], ev["ti_se"][k],
+                         ev["term_ess"][k, 0], ev["term_ess"][k, 1]), file=sys.stderr)
     for k, n in enumerate(names):
         print("mcmc: %-8s truth %9.4f | chain %9.4f %9.4f %9.4f | importance %9.4f %9.4f %9.4f"
               % ((n, truth[k]) + tuple(q_chain[:, k]) + tuple(q_imp[:, k])), file=sys.stderr)
