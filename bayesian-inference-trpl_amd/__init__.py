@@ -9,7 +9,7 @@ from . import _abi  # noqa: F401
 _abi.ensure_built()            # a fresh checkout builds here, before this process can have touched the GPU
 from ._abi import (FLAG_FP32, FLAG_FP32_LONG, FLAG_KERNEL_PAIR, FLAG_KERNEL_SINGLE, FLAG_MIXED, FLAG_NORMALIZE, FLAG_PL_F32, FLAG_SNAP_RAW,  # noqa: F401
                    FLAG_PREDICT, FLAG_STRICT, TrplError)
-from . import dataio, device, dist, mcmc, posterior, predictive, refine, workloads  # noqa: F401
+from . import dataio, device, dist, irf, mcmc, posterior, predictive, refine, workloads  # noqa: F401
 from .dataio import export, get_data, get_initpoints  # noqa: F401
 from .driver import almost_equal, bayes, bracket_times, interp_rows, is_grid_prefix, loglik, simulate  # noqa: F401
 from .likelihood import fastlog, prob  # noqa: F401

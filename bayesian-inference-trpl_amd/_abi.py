@@ -79,6 +79,8 @@ MCMC_FOLD = 0x10              # TRPL_MCMC_FOLD: trpl_mcmc_propose reflects a pro
 MCMC_MAX_RUNGS = 64           # TRPL_MCMC_MAX_RUNGS: temperatures of one trpl_mcmc_*_rungs / trpl_mcmc_swap call
 MCMC_EVIDENCE_SUMS = 6        # TRPL_MCMC_EVIDENCE_SUMS: the columns of a row of trpl_mcmc_evidence_sums' sums
 MCMC_MAX_PAIRS, MCMC_MAX_CR = 4, 8      # TRPL_MCMC_MAX_PAIRS, TRPL_MCMC_MAX_CR: difference pairs and crossover classes of trpl_mcmc_propose_subspace
+IRF_MAX_TAPS = 1024           # TRPL_IRF_MAX_TAPS: taps of one trpl_convolve_irf (trpl_irf_max_taps())
+IRF_TILE_COLS, IRF_TILE_ROWS, IRF_GRID_CAP = 512, 4, 65536      # TRPL_IRF_TILE_COLS / _ROWS: a workgroup's tile; TRPL_IRF_GRID_CAP: workgroups of a launch
 SEED_MASK, STEP_MASK = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF      # a uint64_t seed and a uint32_t step of the trpl_mcmc_* calls, from any int
 
 
@@ -203,6 +205,9 @@ SIGNATURES = {
     "trpl_weighted_quantiles_dev": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _u32, _vp, _vp],
     "trpl_weighted_quantiles": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _u32, _vp, _i32, _pd],
     "trpl_predictive_gather_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _u32, _vp, _i64, _i64, _vp, _vp],
+    "trpl_irf_max_taps": [],
+    "trpl_convolve_irf_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _i64, _vp],
+    "trpl_convolve_irf": [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _i64, _i32, _pd],
     "trpl_corner_workspace_bytes": [_i64, _i32],
     "trpl_corner_columns_dev": [_vp, _i64, _i64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "trpl_corner_hist_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],

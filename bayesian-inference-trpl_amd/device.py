@@ -464,6 +464,24 @@ def predictive_gather_device(pl, W, Y, Wq, row0=0, mag=None, status=None, ncol=N
         _chk(Y, torch.float64, "Y"), Y.shape[1], int(row0), _chk(Wq, torch.float64, "Wq"), _stream()))
 
 
+def convolve_irf_device(pl, h, k0, out, ncol=None):
+    """trpl_convolve_irf_dev: out (rows, out_ld) <- the block pl (rows, ld) f32/f64, as solve_pl_device wrote it, convolved
+    with the instrument response h (K,) f64 whose tap k0 sits at time zero: out[r, j] = sum_k h[k] pl[r, j + k0 - k] for
+    j < ncol - k0, in fp64 and in ascending k (include/trpl.h).  out has pl's dtype and at least ncol - k0 columns; the columns
+    beyond are not written.  ncol (default ld): the valid columns of pl."""
+    import torch
+    if pl.dim() != 2 or pl.dtype not in (torch.float32, torch.float64):
+        raise ValueError("pl must be a 2-D float32/float64 tensor")
+    rows, ld = pl.shape
+    ncol = int(ld if ncol is None else ncol)
+    if h.dim() != 1 or out.dim() != 2 or out.dtype != pl.dtype or out.shape[0] != rows:
+        raise ValueError("h must be (K,) and out (rows, >= ncol - k0) of pl's dtype")
+    if out.shape[1] < ncol - int(k0):
+        raise ValueError("out must have at least ncol - k0 = %d columns, got %d" % (ncol - int(k0), out.shape[1]))
+    _abi.check(_abi.lib().trpl_convolve_irf_dev(_chk(pl, pl.dtype, "pl"), pl.element_size(), rows, ncol, ld, _chk(h, torch.float64, "h"),
+                                                h.shape[0], int(k0), _chk(out, out.dtype, "out"), out.shape[1], _stream()))
+
+
 def posterior_hist_device(x, W, lo, hi, out, y=None, ylo=0.0, yhi=1.0):
     """out (bins,) or (bins, ybins) += weighted counts (W None: counts); the caller zeroes out."""
     import torch

@@ -363,7 +363,7 @@ def _bundle_of(gpu_info, L):
 
 def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_params, normalize, pl_dtype, group,
                        num_gpus, gpu_id, device, solver_time, err_sq_time, sim_t, bundle=1, literal=False, predict=False,
-                       mag_grid=None, weighted=False):
+                       mag_grid=None, weighted=False, irf=None):
     """Several experiments, fused option on: the reference's own loop order -- curves -> sample blocks ->
     experiments (bayeslib.py:117-171) -- with the block's PL matrix kept in HBM: one solve per (curve, block)
     (trpl_solve_pl_dev), then one pass over it per experiment (trpl_loglik_from_pl_dev: normalise, clamp,
@@ -371,7 +371,9 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
     (gpu_info["interpolate_prefix"]).  mag_grid (gpu_info["mag_grid"]): P is (n_exp, M * S); each pass over the PL block also
     returns the first moment of the errors (trpl_loglik_moments_from_pl_dev), and after a block's last curve
     trpl_mag_grid_dev fills the M rows of every experiment.  weighted (gpu_info["weighted"]): every pass is
-    trpl_loglik_weighted_from_pl_dev with the weights of the experiment's uncertainty column (and trpl_mag_grid_w_dev)."""
+    trpl_loglik_weighted_from_pl_dev with the weights of the experiment's uncertainty column (and trpl_mag_grid_w_dev).
+    irf (gpu_info["irf"]) = (h, k0): every solved block is convolved with the instrument response (trpl_convolve_irf_dev) and the
+    passes run over the convolved block, whose ncol is T + 1 - k0."""
     import torch
 
     from . import device as tdev
@@ -381,6 +383,8 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
     flags = _abi.FLAG_NORMALIZE if normalize else 0
     with torch.cuda.device(dev):
         ini_d = torch.from_numpy(np.ascontiguousarray(init_params, dtype=np.float64)).to(dev)
+        if irf is not None:
+            h_d = torch.from_numpy(irf[0]).to(dev)
         # per (experiment, curve), staged once: the keywords of its pass over a PL block -- observations, off the grid their
         # brackets, weights -- and what trpl_mag_grid[_w]_dev takes for the curve, n_obs or the sum of the weights
         def to_dev(a):
@@ -411,6 +415,7 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
             P_d = torch.from_numpy(np.ascontiguousarray(P[:, blk:blk + size])).to(dev)
             pl_d = torch.empty((size, T // sim_params[4] + 1), dtype=tdt, device=dev)     # :137
             st_d = torch.empty(size, dtype=torch.int32, device=dev)
+            seen_d = pl_d if irf is None else torch.empty((size, pl_d.shape[1] - irf[1]), dtype=tdt, device=dev)   # what the passes read
             if mag_grid is not None:
                 S_all, M = len(X), len(mag_grid)
                 P_d = torch.from_numpy(np.ascontiguousarray(
@@ -425,9 +430,11 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
                                      flags=_abi.flag_bundle(bundle, L) | (_abi.FLAG_PREDICT if predict else 0))
                 torch.cuda.synchronize(dev)
                 t1 = time.perf_counter()
+                if irf is not None:
+                    tdev.convolve_irf_device(pl_d, h_d, irf[1], seen_d)
                 for e, per_curve in enumerate(staged):                        # :171
                     out = {"P": P_d[e]} if mag_grid is None else {"sse": sse_d[e, c], "esum": esum_d[e, c]}
-                    getattr(tdev, pass_name)(pl_d, mag=mag_d, flags=flags, status=st_d, **per_curve[c][0], **out)
+                    getattr(tdev, pass_name)(seen_d, mag=mag_d, flags=flags, status=st_d, **per_curve[c][0], **out)
                 torch.cuda.synchronize(dev)
                 solver_time[gpu_id] += t1 - t0
                 err_sq_time[gpu_id] += time.perf_counter() - t1
@@ -472,6 +479,12 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
     gpu_info['curves_per_launch'] (default 1) curves -- a sample stops once its curves together are past the level, not only when
     one curve alone is.  A cut sample's total is at or above the level, which is all the paragraph above needs: the posterior
     weights stay the uncut run's.  Without 'cut_margin' it is a ValueError.
+    gpu_info['irf'] = (h, k0) (default None: nothing changes): the instrument response in the model (irf.gaussian,
+    irf.from_samples; taps at the spacing of the simulation grid, tap k0 at time zero).  Every solved PL block is convolved on the
+    device (trpl_convolve_irf_dev) before it is compared, on the resident-PL level whatever the number of experiments; the convolved
+    curve ends at Time * (T - k0) / T, and a later observation is a ValueError.  Combines with 'predict', 'weighted' and 'mag_grid'
+    (passes over the same block).  The unfused sequence, 'devices', 'cut_margin' and self_normalize are a ValueError naming the
+    option: the fused steppers compare the bare curve, and a convolved curve's first column is not PL(0).
     """
     group = int(gpu_info["sims_per_gpu"])
     num_gpus = int(gpu_info["num_gpus"])
@@ -523,6 +536,23 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
         raise ValueError("gpu_info['cut_budget'] needs gpu_info['cut_margin']: the budget of a sample is margin + the best total so far")
     if gpu_info.get("curves_per_launch") is not None and not cut_budget:
         raise ValueError("gpu_info['curves_per_launch'] goes with gpu_info['cut_budget']")
+    irf = gpu_info.get("irf")
+    if irf is not None:
+        from .irf import _check_irf, last_time
+        irf = _check_irf(irf)
+        for name, bad in (("devices", gpu_info.get("devices") is not None), ("cut_margin", cut_margin is not None),
+                          ("self_normalize", bool(NORMALIZE))):
+            if bad:
+                raise ValueError("gpu_info['irf'] does not combine with %s: the convolution runs on the resident-PL level of one "
+                                 "device, on curves that are not self-normalised" % name)
+        if not fused:
+            raise ValueError("gpu_info['irf'] needs the fused level, not the unfused sequence: gpu_info['fused'] = True, log_pl, PL "
+                             "stride 1 and observation times inside the simulated window")
+        if T + 1 - irf[1] < 2:
+            raise ValueError("gpu_info['irf']: k0 = %d leaves fewer than two columns of a window of T = %d steps" % (irf[1], T))
+        if any(np.max(np.asarray(exp[0][c], dtype=float)) > sim_t[T - irf[1]] for exp in e_data for c in range(num_curves)):
+            raise ValueError("gpu_info['irf']: an observation lies after Time * (T - k0) / T = %g, the last convolved column"
+                             % last_time(Time, T, irf[1]))
     mag_grid = gpu_info.get("mag_grid")
     if mag_grid is not None:
         mag_grid = np.ascontiguousarray(mag_grid, dtype=np.float64).ravel()
@@ -538,11 +568,11 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
         if P.shape != (len(e_data), len(mag_grid) * len(X)) or not P.flags.c_contiguous:
             raise ValueError("gpu_info['mag_grid']: P must be a contiguous (n_exp, M * S) = (%d, %d) array"
                              % (len(e_data), len(mag_grid) * len(X)))
-    if fused and len(e_data) > 1 and gpu_info.get("devices") is None:
+    if fused and (len(e_data) > 1 or irf is not None) and gpu_info.get("devices") is None:
         _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_params, NORMALIZE, pl_dtype,
                            group, num_gpus, gpu_id, device, solver_time, err_sq_time, sim_t,
                            bundle=_bundle_of(gpu_info, L), literal=bool(gpu_info.get("interpolate_prefix", False)),
-                           predict=predict, mag_grid=mag_grid, weighted=weighted)
+                           predict=predict, mag_grid=mag_grid, weighted=weighted, irf=irf)
         return
     if fused:
         # An experiment sampled exactly on the full simulation grid is compared point by point (the reference's bypass,

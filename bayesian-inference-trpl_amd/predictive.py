@@ -108,7 +108,7 @@ def merge(a, b):
 
 
 def posterior_predictive(X, W, init_params, sim_params, lengths=None, block=4096, predict=False, normalize=False, tol=7,
-                         MAX=10000, device=0, quantiles=None, max_store_bytes=8 << 30):
+                         MAX=10000, device=0, quantiles=None, max_store_bytes=8 << 30, irf=None):
     """The posterior-predictive band of every curve.
 
     X (S, 13) samples in the solver's units (columns 0..11 matPar, 12 the magnitude offset), W (S,) their posterior weights
@@ -123,7 +123,10 @@ def posterior_predictive(X, W, init_params, sim_params, lengths=None, block=4096
     (K, ncol), the weighted quantiles of y per time column (band_quantiles' default rules).  The y of every block is kept in
     a store (ncol, n_used) fp64 on the device (predictive_gather_device beside the accumulation) and one selection follows
     the last block; a store above max_store_bytes raises ValueError, before anything is solved.  One device only: quantiles
-    do not merge (see merge)."""
+    do not merge (see merge).
+    irf = (h, k0) (irf.gaussian, irf.from_samples; taps at the spacing of the PL columns): every solved block is convolved with
+    the instrument response on the device (convolve_irf_device) before it is accumulated and gathered.  The band is then of the
+    quantity the detector saw and has ncol - k0 columns, at the first ncol - k0 times; not with normalize."""
     import torch
 
     from . import device as tdev
@@ -140,8 +143,17 @@ def posterior_predictive(X, W, init_params, sim_params, lengths=None, block=4096
         raise ValueError("init_params must be (C, L) and block >= 1")
     with np.errstate(invalid="ignore"):
         sel = np.flatnonzero(np.isfinite(W) & (W > 0))
-    ncol = T // plT + 1
+    ncol = ncol_pl = T // plT + 1
     times = np.linspace(0, Time, T + 1)[::plT]
+    if irf is not None:
+        from .irf import _check_irf
+        irf = _check_irf(irf)
+        if normalize:
+            raise ValueError("irf does not combine with normalize: a convolved curve's first column is not PL(0)")
+        if ncol_pl - irf[1] < 1:
+            raise ValueError("irf: k0 = %d leaves no column of %d" % (irf[1], ncol_pl))
+        ncol = ncol_pl - irf[1]
+        times = times[:ncol]
     if quantiles is not None:
         quantiles = tuple(float(v) for v in np.atleast_1d(quantiles))
         if not 1 <= len(quantiles) <= _abi.Q_MAX or not all(0.0 < v < 1.0 for v in quantiles):
@@ -166,7 +178,10 @@ def posterior_predictive(X, W, init_params, sim_params, lengths=None, block=4096
         ini_d = torch.from_numpy(init_params).to(dev)
         Xs = torch.from_numpy(np.ascontiguousarray(X[sel])).to(dev)
         Ws = torch.from_numpy(np.ascontiguousarray(W[sel])).to(dev)
-        pl_d = torch.empty((block, ncol), dtype=torch.float64, device=dev)
+        pl_d = torch.empty((block, ncol_pl), dtype=torch.float64, device=dev)
+        if irf is not None:
+            h_d = torch.from_numpy(irf[0]).to(dev)
+            seen_d = torch.empty((block, ncol), dtype=torch.float64, device=dev)          # what the band is taken of
         st_d = torch.empty(block, dtype=torch.int32, device=dev)
         state, out = tdev.predictive_state(ncol), torch.empty((5, ncol), dtype=torch.float64, device=dev)
         sizes = {block, sel.size % block or block}               # the row counts that occur: full blocks and the last one
@@ -183,10 +198,13 @@ def posterior_predictive(X, W, init_params, sim_params, lengths=None, block=4096
                 mat_d, mag_d = Xs[a:a + n, :12].contiguous(), Xs[a:a + n, 12].contiguous()
                 tdev.solve_pl_device(mat_d, lens[c], Time, L, T, ini_d[c].contiguous(), pl_d[:n], status=st_d[:n], tol=tol,
                                      MAX=MAX, plT=plT, flags=flags)
-                tdev.predictive_accumulate_device(pl_d[:n], Ws[a:a + n], state, ws, mag=mag_d, status=st_d[:n],
+                if irf is not None:
+                    tdev.convolve_irf_device(pl_d[:n], h_d, irf[1], seen_d[:n])
+                blk_d = pl_d[:n] if irf is None else seen_d[:n]
+                tdev.predictive_accumulate_device(blk_d, Ws[a:a + n], state, ws, mag=mag_d, status=st_d[:n],
                                                   flags=_abi.FLAG_NORMALIZE if normalize else 0)
                 if quantiles is not None:
-                    tdev.predictive_gather_device(pl_d[:n], Ws[a:a + n], Y, Wq, row0=a, mag=mag_d, status=st_d[:n],
+                    tdev.predictive_gather_device(blk_d, Ws[a:a + n], Y, Wq, row0=a, mag=mag_d, status=st_d[:n],
                                                   flags=_abi.FLAG_NORMALIZE if normalize else 0)
                 n_flagged += int((st_d[:n] != 0).sum().item())
                 n_solved += n

@@ -1055,6 +1055,50 @@ int trpl_predictive_gather_dev(const void *plI, int32_t elem_bytes, int64_t rows
                                double *Wq, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_convolve_irf* -- the instrument response in the model: a measured TRPL decay is PL(t) convolved with the response
+ * function (IRF) of the detection chain.  The reference compares the bare PL(t) and sidesteps the IRF by cutting the data after
+ * its peak; this call maps a PL block resident in HBM (the output of trpl_solve_pl_dev) to the block the detector saw, which
+ * every consumer of a resident PL block -- trpl_loglik[_moments|_weighted]_from_pl_dev, trpl_predictive_*,
+ * trpl_predictive_gather_dev -- then takes unchanged.  (csrc/irf.hip)
+ *
+ * Definition.  pl [rows][ld] fp32 / fp64 (elem_bytes) as trpl_solve_pl_dev wrote it, ncol valid columns on a uniform time grid;
+ * h[0 .. K-1] the IRF samples at that grid's spacing; k0 the index of the tap that sits at time zero, normally the peak.  The
+ * output has ncol_out = ncol - k0 valid columns, in the input's element type:
+ *     out[r][j] = sum over k = 0 .. K-1, ascending, of  h[k] * (double)pl[r][j + k0 - k]          0 <= j < ncol_out
+ *   - a term whose column j + k0 - k is negative is skipped, not added as zero: there is no PL before the excitation;
+ *   - no column index exceeds ncol - 1: the last k0 columns are not produced, their sums would need PL past the solved window;
+ *   - the accumulator is fp64 and starts at +0.0; each term is one rounded product followed by one rounded addition, never a
+ *     fused multiply-add; a 4-byte output is the fp64 sum rounded once.
+ * The result is therefore, bit for bit, the NumPy loop  for k: acc[:, lo:hi] += h[k] * pl64[:, lo + k0 - k : hi + k0 - k]
+ * (lo = max(0, k - k0), hi = ncol_out), the same on every run and every device: no atomics, every output is one thread's own sum.
+ * NaN and inf follow IEEE through that expression: a NaN element poisons exactly the output columns whose window covers it,
+ * and 0 * NaN is NaN.  Bytes of out beyond ncol_out in a row are not written.  Any ld >= ncol and out_ld >= ncol_out: rows need
+ * only element alignment.
+ * Work.  A workgroup convolves a tile of TRPL_IRF_TILE_ROWS rows x TRPL_IRF_TILE_COLS output columns from one staged copy of
+ * the TRPL_IRF_TILE_COLS + K - 1 input columns it reads; the grid holds at most TRPL_IRF_GRID_CAP workgroups, which walk the
+ * tiles.  None of this enters the result.
+ *
+ * Refused with TRPL_ERR_ARG before a device is touched, the message naming the argument: elem_bytes other than 4 or 8;
+ * rows < 0; ncol < 1; ld < ncol; K < 1 or K > TRPL_IRF_MAX_TAPS (at the reference's 0.25 ns steps a 256 ns response); k0 outside
+ * [0, K - 1]; ncol - k0 < 1; out_ld < ncol - k0; with rows > 0 a NULL pl, h or out, and out == pl; in the host-buffer form
+ * also a tap that is not finite (its index is named).  rows == 0 is TRPL_OK without a launch.
+ * The _dev call takes device pointers only, allocates nothing and never synchronises.  trpl_convolve_irf is the host-buffer
+ * form (pl, h and out on the host); seconds (nullable) is the time of the kernel on the device.  The count of the cap:
+ * trpl_irf_max_taps.
+ * Python: trpl_amd.irf.gaussian / from_samples / convolve / loglik, trpl_amd.device.convolve_irf_device,
+ * gpu_info["irf"] of simulate / bayes, posterior_predictive(irf=...).
+ * ------------------------------------------------------------------------------------- */
+#define TRPL_IRF_MAX_TAPS 1024
+#define TRPL_IRF_TILE_COLS 512
+#define TRPL_IRF_TILE_ROWS 4
+#define TRPL_IRF_GRID_CAP 65536
+int trpl_irf_max_taps(void);
+int trpl_convolve_irf_dev(const void *pl, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld,
+                          const double *h /*device [K]*/, int32_t K, int32_t k0, void *out, int64_t out_ld, void *stream);
+int trpl_convolve_irf(const void *pl, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld, const double *h, int32_t K,
+                      int32_t k0, void *out, int64_t out_ld, int32_t device, double *seconds);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_corner* -- the corner: every posterior marginal of a finished run in one device call.  What plot() of
  * Visualization/marginalization_visual.py:500-609 does after loading a run: drop the samples outside the axis limits
  * (utils.py:48-52, :145-155), add the secondary parameters (utils.py:54-79, secondary_parameters.py), take log10 of the

@@ -1,0 +1,140 @@
+"""The instrument-response convolution (trpl_convolve_irf_dev) against its two floors, in one process on one device.
+
+    python tools/bench_irf.py [--rows 65536] [--ncol 8001] [--taps 5,33,257,1024] [--route] [--out profiles/irf_bench.jsonl]
+
+kernel:  one trpl_convolve_irf_dev over a [rows][ncol] PL matrix (ld = ncol: odd, rows only element-aligned) in fp64 and in fp32,
+         per tap count K with k0 = K // 2: 3 warm-ups, then the median of 10 calls timed one by one with device events.  Beside
+         the milliseconds: the HBM floor -- one read of the block and one write of the convolved block at the 8 TB/s peak -- and
+         the fp64 floor -- two fp64 instructions per term (a product and an addition, no fused multiply-add by contract) at one
+         64-wide fp64 instruction per 4 cycles and SIMD, 1024 SIMDs at 2.4 GHz -- and which of the two binds at that K.
+--route: the resident route solve -> convolve -> likelihood at the default bench shape (Power_scan, 3 curves, L = 128, T = 8000,
+         one block of 8192 samples) with a 33-tap Gaussian response, each of the three calls timed with device events per curve:
+         the convolution's share of the route's seconds, and the route without it.
+Appends one JSON line per measurement to --out."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np   # noqa: E402
+import torch         # noqa: E402
+import trpl_amd      # noqa: E402
+from trpl_amd import device as tdev   # noqa: E402
+
+PEAK_BPS = 8.0e12
+FP64_LANE_INSTR_PS = 256 * 4 * (64 / 4) * 2.4e9      # CUs x SIMDs x lanes per cycle x clock
+
+
+def events():
+    return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+
+def bench_kernel(a, out):
+    dev = torch.device("cuda", 0)
+    rows, ncol = a.rows, a.ncol
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    for dt in (torch.float64, torch.float32):
+        elem = 8 if dt == torch.float64 else 4
+        pl = torch.empty((rows, ncol), dtype=dt, device=dev)
+        pl.uniform_(-12.0, 0.0, generator=g)
+        pl.mul_(float(np.log(10.0))).exp_()                      # PL = 10^U(-12, 0): a decaying curve's range
+        for K in a.taps:
+            k0 = K // 2
+            ncol_out = ncol - k0
+            h = torch.from_numpy(np.random.default_rng(K).uniform(0.1, 1.0, K)).to(dev)
+            cv = torch.empty((rows, ncol_out), dtype=dt, device=dev)
+            for _ in range(3):
+                tdev.convolve_irf_device(pl, h, k0, cv)
+            torch.cuda.synchronize()
+            ms = []
+            for _ in range(10):
+                e0, e1 = events()
+                e0.record()
+                tdev.convolve_irf_device(pl, h, k0, cv)
+                e1.record()
+                torch.cuda.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            med = float(np.median(ms))
+            nbytes = rows * (ncol + ncol_out) * elem
+            terms = rows * ncol_out * K
+            hbm_ms, fp64_ms = nbytes / PEAK_BPS * 1e3, 2 * terms / FP64_LANE_INSTR_PS * 1e3
+            line = {"bench": "irf_kernel", "device": torch.cuda.get_device_name(0), "rows": rows, "ncol": ncol, "elem_bytes": elem, "K": K,
+                    "k0": k0, "ms": med, "ms_min": float(min(ms)), "ms_max": float(max(ms)), "hbm_floor_ms": hbm_ms,
+                    "fp64_floor_ms": fp64_ms, "binding_floor": "hbm" if hbm_ms >= fp64_ms else "fp64",
+                    "ms_over_binding_floor": med / max(hbm_ms, fp64_ms), "TBps": nbytes / med / 1e9}
+            out(line)
+        del pl, cv
+
+
+def bench_route(a, out):
+    dev = torch.device("cuda", 0)
+    w = trpl_amd.workloads
+    L, T, S = 128, 8000, a.samples
+    Time = T * 0.025
+    ini, lens = w.power_scan(L)
+    X = w.samples(S)
+    h, k0 = trpl_amd.irf.gaussian(0.188, Time / T, rel_cut=1e-6)
+    X_d = torch.from_numpy(X).to(dev)
+    mat, mag = X_d[:, :12].contiguous(), X_d[:, 12].contiguous()
+    ini_d, h_d = torch.from_numpy(ini).to(dev), torch.from_numpy(h).to(dev)
+    pl = torch.empty((S, T + 1), dtype=torch.float64, device=dev)
+    cv = torch.empty((S, T + 1 - k0), dtype=torch.float64, device=dev)
+    st = torch.zeros(S, dtype=torch.int32, device=dev)
+    P = torch.zeros(S, dtype=torch.float64, device=dev)
+    obs = torch.zeros(T + 1 - k0, dtype=torch.float64, device=dev)
+    runs = []
+    for rep in range(1 + a.route_reps):                              # the first pass warms up
+        t = {"solve": 0.0, "convolve": 0.0, "loglik": 0.0, "loglik_bare": 0.0}
+        for c in range(3):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+            ev[0].record()
+            tdev.solve_pl_device(mat, lens[c], Time, L, T, ini_d[c].contiguous(), pl, status=st)
+            ev[1].record()
+            tdev.convolve_irf_device(pl, h_d, k0, cv)
+            ev[2].record()
+            tdev.loglik_from_pl_device(cv, obs, mag, P=P, status=st)
+            ev[3].record()
+            tdev.loglik_from_pl_device(pl, obs, mag, P=P, status=st)         # the route without the response reads the bare block
+            ev[4].record()
+            torch.cuda.synchronize()
+            for k, (i, j) in zip(t, ((0, 1), (1, 2), (2, 3), (3, 4))):
+                t[k] += ev[i].elapsed_time(ev[j]) / 1e3
+        if rep:
+            runs.append(t)
+    med = {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
+    with_irf, without = med["solve"] + med["convolve"] + med["loglik"], med["solve"] + med["loglik_bare"]
+    out({"bench": "irf_route", "device": torch.cuda.get_device_name(0), "workload": "Power_scan", "curves": 3, "L": L, "T": T, "samples": S,
+         "K": int(len(h)), "k0": int(k0), "seconds": med, "route_with_irf_s": with_irf, "route_without_irf_s": without,
+         "irf_share_of_route": med["convolve"] / with_irf, "reps": a.route_reps})
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=65536)
+    ap.add_argument("--ncol", type=int, default=8001)
+    ap.add_argument("--taps", type=lambda s: [int(v) for v in s.split(",")], default=[5, 33, 257, 1024])
+    ap.add_argument("--route", action="store_true")
+    ap.add_argument("--samples", type=int, default=8192)
+    ap.add_argument("--route-reps", type=int, default=3)
+    ap.add_argument("--no-kernel", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "irf_bench.jsonl"))
+    a = ap.parse_args()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+
+    def out(line):
+        with open(a.out, "a") as f:
+            f.write(json.dumps(line) + "\n")
+        print(json.dumps(line), flush=True)
+
+    if not a.no_kernel:
+        bench_kernel(a, out)
+    if a.route:
+        bench_route(a, out)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

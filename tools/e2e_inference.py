@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--subspace [--pairs n] [--ncr n] [--adapt-cr]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject [sample]] [--tempered K [--tf-hot x] [--evidence]]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--subspace [--pairs n] [--ncr n] [--adapt-cr]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject [sample]] [--tempered K [--tf-hot x] [--evidence]]] [--irf FWHM_NS]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -64,6 +64,11 @@ same units on a linear parameter and in decades on a logarithmic one (mcmc.gauss
 (mcmc.run(kind="subspace", pairs=n, ncr=n, adapt_cr=...): DESIGN.md section 33); it composes with --fold, --early-reject and --tempered.
 "mcmc" then gains "subspace": pairs, ncr, the crossover shares pcr of the kept sweeps and mean_dsel, the mean number of coordinates
 a proposal moved.
+--irf FWHM_NS adds, at the end, the same importance run with the instrument response in the model (trpl_amd.irf: DESIGN.md section
+35): a Gaussian response of that full width at half maximum on the run's time step (irf.gaussian), the observations the marked
+point's curves convolved with it (what the detector would have recorded), every sample scored by irf.loglik (solve, convolve,
+likelihood on the resident PL block).  "irf" holds the taps, the effective sample size and the 2.5 / 50 / 97.5 % values of every
+free parameter beside those of the run without the response, which are printed -- recorded, not gated -- and seconds["irf"].
 """
 import json
 import sys
@@ -136,6 +141,11 @@ for flag in ("--pairs", "--ncr"):
         k = sys.argv.index(flag)
         PAIRS, NCR = (int(sys.argv[k + 1]), NCR) if flag == "--pairs" else (PAIRS, int(sys.argv[k + 1]))
         del sys.argv[k:k + 2]
+IRF_FWHM = None
+if "--irf" in sys.argv:
+    k = sys.argv.index("--irf")
+    IRF_FWHM = float(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
 PRIORS = {}
 while "--prior" in sys.argv:
     k = sys.argv.index("--prior")
@@ -462,4 +472,28 @@ if MCMC:
     for k, n in enumerate(names):
         print("mcmc: %-8s truth %9.4f | chain %9.4f %9.4f %9.4f | importance %9.4f %9.4f %9.4f"
               % ((n, truth[k]) + tuple(q_chain[:, k]) + tuple(q_imp[:, k])), file=sys.stderr)
+if IRF_FWHM is not None:
+    from trpl_amd import irf as tirf, posterior
+    t12 = sync()
+    resp = tirf.gaussian(IRF_FWHM, dt)
+    n_conv = T + 1 - resp[1]
+    seen = tirf.convolve(10.0 ** obs.cpu().numpy(), *resp)       # the marked point's curves as the detector records them
+    LL_irf = tirf.loglik(X.cpu().numpy(), ini, lens, T * dt, L, T, [np.log10(seen[c]) for c in range(C)], resp)
+    tf_irf = C * n_conv * c_val
+    W_irf = posterior.weights(LL_irf, tf_irf)
+    qs = [0.025, 0.5, 0.975]
+    q_irf = posterior.quantiles(V.cpu().numpy(), W_irf, qs)
+    q_bare = posterior.quantiles(V.cpu().numpy(), W.cpu().numpy(), qs)
+    out["seconds"]["irf"] = sync() - t12
+    ess_irf = float(1.0 / np.nansum(W_irf * W_irf))
+    out["irf"] = {"fwhm_ns": IRF_FWHM, "taps": int(len(resp[0])), "k0": int(resp[1]), "columns": n_conv, "tf": tf_irf,
+                  "effective_sample_size": ess_irf, "effective_sample_size_without": out["effective_sample_size"],
+                  "max_loglik": float(np.nanmax(LL_irf)),
+                  "quantiles": {n: {"truth": float(tr), "with_irf": [float(v) for v in q_irf[:, k]], "without": [float(v) for v in q_bare[:, k]]}
+                                for k, (n, tr) in enumerate(zip(names, truth))}}
+    print("irf: Gaussian of %g ns, %d taps: effective sample size %.2f (without the response %.2f), %.2f s"
+          % (IRF_FWHM, len(resp[0]), ess_irf, out["effective_sample_size"], out["seconds"]["irf"]), file=sys.stderr)
+    for k, n in enumerate(names):
+        print("irf: %-8s truth %9.4f | with the response %9.4f %9.4f %9.4f | without %9.4f %9.4f %9.4f"
+              % ((n, truth[k]) + tuple(q_irf[:, k]) + tuple(q_bare[:, k])), file=sys.stderr)
 print(json.dumps(out))
