@@ -81,6 +81,7 @@ MCMC_EVIDENCE_SUMS = 6        # TRPL_MCMC_EVIDENCE_SUMS: the columns of a row of
 MCMC_MAX_PAIRS, MCMC_MAX_CR = 4, 8      # TRPL_MCMC_MAX_PAIRS, TRPL_MCMC_MAX_CR: difference pairs and crossover classes of trpl_mcmc_propose_subspace
 IRF_MAX_TAPS = 1024           # TRPL_IRF_MAX_TAPS: taps of one trpl_convolve_irf (trpl_irf_max_taps())
 IRF_TILE_COLS, IRF_TILE_ROWS, IRF_GRID_CAP = 512, 4, 65536      # TRPL_IRF_TILE_COLS / _ROWS: a workgroup's tile; TRPL_IRF_GRID_CAP: workgroups of a launch
+IRF_BANK_MAX_RESPONSES, IRF_BANK_BLOCK = 256, 8      # TRPL_IRF_BANK_MAX_RESPONSES: responses of one trpl_loglik_irf_bank; TRPL_IRF_BANK_BLOCK: those of one pass over the taps
 SEED_MASK, STEP_MASK = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF      # a uint64_t seed and a uint32_t step of the trpl_mcmc_* calls, from any int
 
 
@@ -208,6 +209,15 @@ SIGNATURES = {
     "trpl_irf_max_taps": [],
     "trpl_convolve_irf_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _i64, _vp],
     "trpl_convolve_irf": [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _i64, _i32, _pd],
+    "trpl_irf_bank_max_responses": [],
+    "trpl_irf_bank_block": [],
+    # H, J, K, k0 after ld; obs, the three brackets, n_obs, wts; mag, status; sse, esum [J][rows]
+    "trpl_loglik_irf_bank_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                 _u32, _vp],
+    "trpl_loglik_irf_bank": [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _u32,
+                             _i32, _pd],
+    "trpl_irf_bank_profile_dev": [_vp, _i32, _i64, _vp, _vp, _vp],
+    "trpl_irf_bank_profile": [_vp, _i32, _i64, _vp, _vp],
     "trpl_corner_workspace_bytes": [_i64, _i32],
     "trpl_corner_columns_dev": [_vp, _i64, _i64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "trpl_corner_hist_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],

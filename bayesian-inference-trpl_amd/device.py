@@ -482,6 +482,40 @@ def convolve_irf_device(pl, h, k0, out, ncol=None):
                                                 h.shape[0], int(k0), _chk(out, out.dtype, "out"), out.shape[1], _stream()))
 
 
+def loglik_irf_bank_device(pl, H, k0, obs, mag, sse, esum=None, wts=None, obs_hi=None, obs_dx=None, obs_h=None, ncol=None, flags=0,
+                           status=None):
+    """trpl_loglik_irf_bank_dev: the block pl (rows, ld) f32/f64, as solve_pl_device wrote it, scored against the bank H (J, K) f64
+    of instrument responses whose tap k0 sits at time zero: sse (J, rows) f64 and esum (J, rows) f64 (optional) receive, per
+    response, the bits of convolve_irf_device followed by loglik_moments_from_pl_device (with wts (n_obs,) f64:
+    loglik_weighted_from_pl_device) on the same obs (n_obs,), brackets, mag (rows,) and status (rows,) int32 -- without the
+    convolved block ever being written.  ncol (default ld): the valid columns of pl."""
+    import torch
+    f64 = torch.float64
+    if pl.dim() != 2 or pl.dtype not in (torch.float32, torch.float64):
+        raise ValueError("pl must be a 2-D float32/float64 tensor")
+    rows, ld = pl.shape
+    if H.dim() != 2 or obs.dim() != 1 or tuple(mag.shape) != (rows,) or tuple(sse.shape) != (H.shape[0], rows):
+        raise ValueError("H must be (J, K), obs (n_obs,), mag (rows,) and sse (J, rows)")
+    if (esum is not None and esum.shape != sse.shape) or (wts is not None and wts.shape != obs.shape) \
+            or (status is not None and tuple(status.shape) != (rows,)):
+        raise ValueError("shape mismatch")
+    _abi.check(_abi.lib().trpl_loglik_irf_bank_dev(
+        _chk(pl, pl.dtype, "pl"), pl.element_size(), rows, int(ld if ncol is None else ncol), ld, _chk(H, f64, "H"), H.shape[0],
+        H.shape[1], int(k0), _chk(obs, f64, "obs"), *_brackets(obs, obs_hi, obs_dx, obs_h), obs.shape[0], _opt(wts, f64, "wts"),
+        _chk(mag, f64, "mag"), _opt(status, torch.int32, "status"), _chk(sse, f64, "sse"), _opt(esum, f64, "esum"), int(flags),
+        _stream()))
+
+
+def irf_bank_profile_device(Pbank, best, P):
+    """trpl_irf_bank_profile_dev: P (S,) f64 <- the greatest Pbank[j, s] of Pbank (J, S) f64, best (S,) int32 <- the first j that
+    attains it; where every value is -inf or NaN, best = -1 and P = -inf."""
+    import torch
+    if Pbank.dim() != 2 or tuple(best.shape) != (Pbank.shape[1],) or tuple(P.shape) != (Pbank.shape[1],):
+        raise ValueError("Pbank must be (J, S), best and P (S,)")
+    _abi.check(_abi.lib().trpl_irf_bank_profile_dev(_chk(Pbank, torch.float64, "Pbank"), Pbank.shape[0], Pbank.shape[1],
+                                                    _chk(best, torch.int32, "best"), _chk(P, torch.float64, "P"), _stream()))
+
+
 def posterior_hist_device(x, W, lo, hi, out, y=None, ylo=0.0, yhi=1.0):
     """out (bins,) or (bins, ybins) += weighted counts (W None: counts); the caller zeroes out."""
     import torch

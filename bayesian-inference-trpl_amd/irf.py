@@ -9,9 +9,15 @@ include/trpl.h; csrc/irf.hip): every consumer of such a block takes the convolve
     from_samples(t_ns, counts, dt_ns)       a measured response resampled onto the simulation grid -> (h, k0)
     convolve(pl, h, k0)                     one PL matrix on the host -> the (rows, ncol - k0) convolved matrix
     loglik(X, ..., obs, irf)                the resident route solve -> convolve -> likelihood; X -> LL for refine / mcmc
+    gaussian_bank(fwhms_ns, shifts_ns, dt_ns)   a bank of Gaussian responses, widths x time shifts -> (H, k0, table)
+    shift_bank((h, k0), shifts_ns, dt_ns)   a measured response at several time shifts -> (H, k0, table)
+    loglik_bank(X, ..., obs, bank)          solve -> the likelihood per response of the bank, from one solve -> P (J, S)
+    loglik_profile(X, ..., obs, bank)       the profile of loglik_bank over the bank; X -> LL for refine / mcmc
 
 An IRF is the pair (h, k0): the taps at the grid's spacing and the index of the tap that sits at time zero (the peak).  The
 convolved curve has k0 columns less than the solved one: its last k0 columns would need PL past the solved window.
+A bank is J responses of one length and one k0, H (J, K): a time shift lives in the taps of a row, zero-padded to the common
+length (trpl_loglik_irf_bank*, include/trpl.h; csrc/irf_bank.hip).
 """
 import math
 
@@ -136,30 +142,13 @@ def last_time(Time, T, k0):
     return float(Time) * (int(T) - int(k0)) / int(T)
 
 
-def loglik(X, init_params, lengths, Time, L, T, obs, irf, times=None, weights=None, tol=7, MAX=10000, pl_f32=False,
-           predict=False, block=8192, device=0, P=None, info=None, normalize=False):
-    """The likelihood of one experiment with the instrument response in the model, on the resident route: per block of `block`
-    samples and per curve, solve_pl_device writes the PL block into HBM, convolve_irf_device maps it to the block the detector
-    saw, and loglik_from_pl_device (with weights=: loglik_weighted_from_pl_device) scores that block -- only X goes in and P
-    comes out.
+_NO_NORMALIZE = "normalize: self-normalisation does not combine with an IRF (the convolved curve's first column is not PL(0))"
 
-    X, init_params, lengths, Time, L, T, obs, times, weights, tol, MAX, predict, device, P as driver.loglik takes them; irf =
-    (h, k0), the taps at the spacing Time / T of the simulation grid and the index of the tap at time zero (gaussian,
-    from_samples).  The convolved curve has ncol_out = T + 1 - k0 columns, at the first ncol_out times of the grid.  With
-    times=None observation i of a curve sits on column i, so len(obs[c]) <= ncol_out; otherwise the times are bracketed exactly
-    as driver.loglik brackets them, on the convolved columns: an observation later than Time * (T - k0) / T is a ValueError.
-    pl_f32: the PL block (solved and convolved) is float32, as the reference's buffer is.  Accumulates into P (S,) if given,
-    else starts from zeros; returns P.  info receives sse (C, S), status (C, S) and ncol_out.
-    normalize: self-normalisation is a ValueError -- normalising a convolved curve to its own first column is not what the
-    reference's flag means (its first column is a fraction of the response's area, not PL(0)).
-    A sample's bits are those of its block's launches: cut the samples with `block` as the run that is compared with cuts them.
 
-    functools.partial(loglik, init_params=..., ..., irf=...) is a valid `loglik` for refine.run, mcmc.run and
-    mcmc.run_tempered WITHOUT early_reject: the early stop lives in the fused steppers (trpl_loglik_cut*), which compare the
-    bare curve and never see a convolved one."""
-    if normalize:
-        raise ValueError("normalize: self-normalisation does not combine with an IRF (the convolved curve's first column is not PL(0))")
-    h, k0 = _check_irf(irf)
+def _stage(X, init_params, lengths, Time, L, T, obs, k0, times, weights, block):
+    """What loglik and loglik_bank check and stage before a device is touched: X, the curves' constants, and per curve the
+    keyword arrays of the scoring call -- obs, with times the three brackets on the convolved columns (sorted by time), with
+    weights wts.  Returns (X, ini, lengths, staged, ncol_out)."""
     X = np.ascontiguousarray(X, dtype=np.float64)
     if X.ndim != 2 or X.shape[1] != 13:
         raise ValueError("X must have shape (S, 13)")
@@ -209,6 +198,35 @@ def loglik(X, init_params, lengths, Time, L, T, obs, irf, times=None, weights=No
         if w is not None:
             kw["wts"] = w
         staged.append(kw)
+    return X, ini, lengths, staged, ncol_out
+
+
+def loglik(X, init_params, lengths, Time, L, T, obs, irf, times=None, weights=None, tol=7, MAX=10000, pl_f32=False,
+           predict=False, block=8192, device=0, P=None, info=None, normalize=False):
+    """The likelihood of one experiment with the instrument response in the model, on the resident route: per block of `block`
+    samples and per curve, solve_pl_device writes the PL block into HBM, convolve_irf_device maps it to the block the detector
+    saw, and loglik_from_pl_device (with weights=: loglik_weighted_from_pl_device) scores that block -- only X goes in and P
+    comes out.
+
+    X, init_params, lengths, Time, L, T, obs, times, weights, tol, MAX, predict, device, P as driver.loglik takes them; irf =
+    (h, k0), the taps at the spacing Time / T of the simulation grid and the index of the tap at time zero (gaussian,
+    from_samples).  The convolved curve has ncol_out = T + 1 - k0 columns, at the first ncol_out times of the grid.  With
+    times=None observation i of a curve sits on column i, so len(obs[c]) <= ncol_out; otherwise the times are bracketed exactly
+    as driver.loglik brackets them, on the convolved columns: an observation later than Time * (T - k0) / T is a ValueError.
+    pl_f32: the PL block (solved and convolved) is float32, as the reference's buffer is.  Accumulates into P (S,) if given,
+    else starts from zeros; returns P.  info receives sse (C, S), status (C, S) and ncol_out.
+    normalize: self-normalisation is a ValueError -- normalising a convolved curve to its own first column is not what the
+    reference's flag means (its first column is a fraction of the response's area, not PL(0)).
+    A sample's bits are those of its block's launches: cut the samples with `block` as the run that is compared with cuts them.
+
+    functools.partial(loglik, init_params=..., ..., irf=...) is a valid `loglik` for refine.run, mcmc.run and
+    mcmc.run_tempered WITHOUT early_reject: the early stop lives in the fused steppers (trpl_loglik_cut*), which compare the
+    bare curve and never see a convolved one."""
+    if normalize:
+        raise ValueError(_NO_NORMALIZE)
+    h, k0 = _check_irf(irf)
+    X, ini, lengths, staged, ncol_out = _stage(X, init_params, lengths, Time, L, T, obs, k0, times, weights, block)
+    S, Cn, L, T, block = X.shape[0], ini.shape[0], int(L), int(T), int(block)
     if P is None:
         P = np.zeros(S)
     if not (P.dtype == np.float64 and P.flags.c_contiguous and P.shape == (S,)):
@@ -250,3 +268,194 @@ def loglik(X, init_params, lengths, Time, L, T, obs, irf, times=None, weights=No
             sse[:, blk:blk + n] = sse_d.cpu().numpy()
             status[:, blk:blk + n] = st_d.cpu().numpy()
     return P
+
+
+# ------------------------------------------------------------------------------------------------ a bank of responses
+def bank_cap():
+    """trpl_irf_bank_max_responses(): the most responses one bank holds."""
+    return int(_abi.lib().trpl_irf_bank_max_responses())
+
+
+def _check_bank(bank):
+    """(H float64 (J, K) contiguous, k0 int) of a bank (H, k0) or (H, k0, table), refused as the library refuses it."""
+    try:
+        H, k0 = bank[0], bank[1]
+    except (TypeError, IndexError, KeyError):
+        raise ValueError("bank must be (H, k0) or (H, k0, table)")
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    k0 = int(k0)
+    if H.ndim != 2 or not 1 <= H.shape[0] <= _abi.IRF_BANK_MAX_RESPONSES or not 1 <= H.shape[1] <= _abi.IRF_MAX_TAPS:
+        raise ValueError("bank: H must be (J, K) with 1 .. %d responses of 1 .. %d taps" % (_abi.IRF_BANK_MAX_RESPONSES, _abi.IRF_MAX_TAPS))
+    if not 0 <= k0 < H.shape[1]:
+        raise ValueError("bank: k0 = %d must be in [0, K - 1 = %d]" % (k0, H.shape[1] - 1))
+    if not np.all(np.isfinite(H)):
+        raise ValueError("bank: every tap must be finite")
+    return H, k0
+
+
+def _check_counts(J, K):
+    if J > bank_cap():
+        raise ValueError("a bank of %d responses is more than trpl_irf_bank_max_responses() = %d" % (J, bank_cap()))
+    if K > max_taps():
+        raise ValueError("the bank needs %d taps, more than trpl_irf_max_taps() = %d" % (K, max_taps()))
+
+
+def gaussian_bank(fwhms_ns, shifts_ns, dt_ns, rel_cut=1e-12):
+    """A bank of Gaussian responses on a grid of spacing dt_ns: every width of fwhms_ns at every time shift of shifts_ns,
+    width-major -- J = len(fwhms_ns) * len(shifts_ns), row j = w * len(shifts_ns) + s, table[j] = (fwhm, shift).  The taps of a row
+    are exp(-4 ln2 (((k - k0) - shift / dt) dt / fwhm)^2), 0.0 where that is below rel_cut, divided by the row's own math.fsum.
+    K = 2 k0 + 1 and k0 are common to the rows: the fewest taps that hold the widest response at the largest |shift|.  A positive
+    shift moves the convolved curve later.  With shift 0 a row is gaussian(fwhm, dt_ns, rel_cut) zero-padded, bit for bit.
+    Returns (H (J, K), k0, table (J, 2)).  ValueError above max_taps() taps or bank_cap() responses."""
+    fw = np.atleast_1d(np.asarray(fwhms_ns, dtype=np.float64))
+    sh = np.atleast_1d(np.asarray(shifts_ns, dtype=np.float64))
+    dt_ns, rel_cut = float(dt_ns), float(rel_cut)
+    if fw.ndim != 1 or sh.ndim != 1 or fw.size < 1 or sh.size < 1:
+        raise ValueError("fwhms_ns and shifts_ns must be one-dimensional and not empty")
+    if not (np.all(np.isfinite(fw)) and np.all(fw > 0.0) and np.all(np.isfinite(sh)) and dt_ns > 0.0 and math.isfinite(dt_ns)):
+        raise ValueError("fwhms_ns and dt_ns must be finite and > 0, shifts_ns finite")
+    if not 0.0 < rel_cut < 1.0:
+        raise ValueError("rel_cut must lie in (0, 1)")
+    J = fw.size * sh.size
+    reach = float(fw.max()) / dt_ns * math.sqrt(math.log(1.0 / rel_cut) / (4.0 * math.log(2.0))) + float(np.abs(sh).max()) / dt_ns
+    _check_counts(J, 2 * int(reach) - 1)                       # before anything of that size is built; exactly, below
+    m0 = int(reach) + 2
+    c = 4.0 * math.log(2.0)
+    rows, table = [], []
+    for f in fw.tolist():
+        for t in sh.tolist():
+            sig = t / dt_ns
+            v = [math.exp(-c * ((n - sig) * dt_ns / f) ** 2) for n in range(-m0, m0 + 1)]
+            rows.append([x if x >= rel_cut else 0.0 for x in v])
+            table.append((f, t))
+    m = max((abs(n - m0) for r in rows for n, x in enumerate(r) if x != 0.0), default=0)
+    _check_counts(J, 2 * m + 1)
+    H = np.empty((J, 2 * m + 1), dtype=np.float64)
+    for j, r in enumerate(rows):
+        r = r[m0 - m:m0 + m + 1]
+        total = math.fsum(r)
+        if not total > 0.0:
+            raise ValueError("fwhm %g ns at shift %g ns on a %g ns grid leaves no tap above rel_cut" % (table[j] + (dt_ns,)))
+        H[j] = [x / total for x in r]
+    return H, m, np.array(table, dtype=np.float64)
+
+
+def shift_bank(irf, shifts_ns, dt_ns):
+    """A measured response (h, k0) (from_samples) at the time shifts shifts_ns, on the grid of spacing dt_ns: row j holds the taps
+    moved by shifts_ns[j] / dt_ns steps -- the response resampled linearly between its taps, zero outside them: with shift / dt =
+    i + f, 0 <= f < 1, tap n of the row is (1 - f) h[n - i] + f h[n - i - 1].  A shift of a whole number of steps moves the taps
+    exactly; the rows are not normalised again (the resampling keeps the sum up to rounding).  K and k0 are common to the rows:
+    the taps of (h, k0) padded with zeros on either side as far as the shifts reach.  A positive shift moves the convolved curve
+    later.  Returns (H (J, K), k0, table (J,) = the shifts).  ValueError above max_taps() taps or bank_cap() responses."""
+    h, k0 = _check_irf(irf)
+    sh = np.atleast_1d(np.asarray(shifts_ns, dtype=np.float64))
+    dt_ns = float(dt_ns)
+    if sh.ndim != 1 or sh.size < 1 or not np.all(np.isfinite(sh)) or not (dt_ns > 0.0 and math.isfinite(dt_ns)):
+        raise ValueError("shifts_ns must be one-dimensional, not empty and finite, dt_ns finite and > 0")
+    sig = sh / dt_ns
+    if float(np.abs(sig).max()) > 4 * _abi.IRF_MAX_TAPS:
+        raise ValueError("a shift of %g steps is far more than trpl_irf_max_taps() = %d" % (float(np.abs(sig).max()), _abi.IRF_MAX_TAPS))
+    whole = np.floor(sig)
+    frac = sig - whole
+    left = max(0, -int(whole.min()))
+    right = max(0, int(np.max(whole + (frac > 0.0))))
+    K = h.size + left + right
+    _check_counts(sh.size, K)
+    H = np.zeros((sh.size, K), dtype=np.float64)
+    for j in range(sh.size):
+        i, f = int(whole[j]), float(frac[j])
+        a = left + i                                            # the row's index of tap 0 moved by the whole steps
+        if f == 0.0:
+            H[j, a:a + h.size] = h
+        else:
+            H[j, a:a + h.size] = (1.0 - f) * h
+            H[j, a + 1:a + 1 + h.size] += f * h
+    return H, k0 + left, sh.copy()
+
+
+def loglik_bank(X, init_params, lengths, Time, L, T, obs, bank, times=None, weights=None, tol=7, MAX=10000, pl_f32=False,
+                predict=False, block=8192, device=0, info=None, normalize=False):
+    """loglik for every response of a bank at once, from ONE solve per block and curve: solve_pl_device writes the PL block and
+    loglik_irf_bank_device scores it against the J responses of bank = (H (J, K), k0[, table]) (gaussian_bank, shift_bank) -- the
+    convolved blocks are never written.  Returns P (J, S): row j is, bit for bit, loglik(X, ..., irf=(H[j], k0)) with the same
+    arguments (P started from zeros, the curves subtracted in order).  Every other argument, the blocking and the refusals are
+    loglik's.  info receives sse (J, C, S), esum (J, C, S) -- the sums of the errors, so that a magnitude profile can follow --
+    status (C, S) and ncol_out."""
+    if normalize:
+        raise ValueError(_NO_NORMALIZE)
+    H, k0 = _check_bank(bank)
+    X, ini, lengths, staged, ncol_out = _stage(X, init_params, lengths, Time, L, T, obs, k0, times, weights, block)
+    S, Cn, L, T, block, J = X.shape[0], ini.shape[0], int(L), int(T), int(block), H.shape[0]
+    for c, kw in enumerate(staged):
+        if len(kw["obs"]) < 1:
+            raise ValueError("curve %d: a bank needs at least one observation per curve" % c)
+    P = np.zeros((J, S))
+    sse = np.zeros((J, Cn, S))
+    esum = np.zeros((J, Cn, S))
+    status = np.zeros((Cn, S), dtype=np.int32)
+    if info is not None:
+        info.update(sse=sse, esum=esum, status=status, ncol_out=ncol_out)
+    if S == 0:
+        return P
+
+    import torch
+
+    from . import device as tdev
+    dev = torch.device("cuda", device)
+    tdt = torch.float32 if pl_f32 else torch.float64
+    with torch.cuda.device(dev):
+        def to_dev(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        ini_d, H_d = to_dev(ini), to_dev(H)
+        staged = [{k: to_dev(v) for k, v in kw.items()} for kw in staged]
+        pl_d = torch.empty((min(block, S), T + 1), dtype=tdt, device=dev)
+        for blk in range(0, S, block):
+            n = min(block, S - blk)
+            X_d = to_dev(X[blk:blk + n])
+            mat_d, mag_d = X_d[:, :12].contiguous(), X_d[:, 12].contiguous()
+            P_d = torch.zeros((J, n), dtype=torch.float64, device=dev)
+            sse_d = torch.zeros((Cn, J, n), dtype=torch.float64, device=dev)
+            es_d = torch.zeros((Cn, J, n), dtype=torch.float64, device=dev)
+            st_d = torch.zeros((Cn, n), dtype=torch.int32, device=dev)
+            for c in range(Cn):
+                tdev.solve_pl_device(mat_d, lengths[c], Time, L, T, ini_d[c].contiguous(), pl_d[:n], status=st_d[c], tol=tol,
+                                     MAX=MAX, flags=_abi.FLAG_PREDICT if predict else 0)
+                tdev.loglik_irf_bank_device(pl_d[:n], H_d, k0, mag=mag_d, sse=sse_d[c], esum=es_d[c], status=st_d[c], **staged[c])
+                P_d -= sse_d[c]                                   # loglik's P[s] -= sse, curves in order
+            P[:, blk:blk + n] = P_d.cpu().numpy()
+            sse[:, :, blk:blk + n] = sse_d.cpu().numpy().transpose(1, 0, 2)
+            esum[:, :, blk:blk + n] = es_d.cpu().numpy().transpose(1, 0, 2)
+            status[:, blk:blk + n] = st_d.cpu().numpy()
+    return P
+
+
+def loglik_profile(X, init_params, lengths, Time, L, T, obs, bank, times=None, weights=None, tol=7, MAX=10000, pl_f32=False,
+                   predict=False, block=8192, device=0, info=None, normalize=False):
+    """The profile likelihood over a bank of instrument responses: LL[s] = max_j loglik_bank(...)[j, s].  The curves are summed
+    first -- one response serves all curves of an experiment -- then irf_bank_profile_device takes the greatest row per sample.
+    Returns LL (S,); info receives loglik_bank's entries, P (J, S) and best (S,) int32, the first response that attains the
+    maximum (-1, with LL = -inf, where every response scores -inf or NaN).  The time shift and the width of the response are
+    nuisance parameters that do not enter the solve: the profile costs one solve per sample, like mag_profile.
+
+    functools.partial(loglik_profile, init_params=..., ..., bank=...) is a valid `loglik` for refine.run, mcmc.run and
+    mcmc.run_tempered WITHOUT early_reject: the early stop lives in the fused steppers (trpl_loglik_cut*), which compare the
+    bare curve and never see a convolved one."""
+    own = {}
+    Pb = loglik_bank(X, init_params, lengths, Time, L, T, obs, bank, times=times, weights=weights, tol=tol, MAX=MAX, pl_f32=pl_f32,
+                     predict=predict, block=block, device=device, info=own, normalize=normalize)
+    J, S = Pb.shape
+    LL = np.full(S, -np.inf)
+    best = np.full(S, -1, dtype=np.int32)
+    if S:
+        import torch
+
+        from . import device as tdev
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            LL_d = torch.empty(S, dtype=torch.float64, device=dev)
+            best_d = torch.empty(S, dtype=torch.int32, device=dev)
+            tdev.irf_bank_profile_device(torch.from_numpy(Pb).to(dev), best_d, LL_d)
+            LL, best = LL_d.cpu().numpy(), best_d.cpu().numpy()
+    if info is not None:
+        info.update(own, P=Pb, best=best)
+    return LL

@@ -1099,6 +1099,66 @@ int trpl_convolve_irf(const void *pl, int32_t elem_bytes, int64_t rows, int64_t 
                       int32_t k0, void *out, int64_t out_ld, int32_t device, double *seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * trpl_loglik_irf_bank* -- the likelihood of a resident PL block against a BANK of J candidate instrument responses, from one
+ * solve and one call.  The arrival time of the excitation is not known to a fraction of a grid step and the width of the
+ * response only to some tens of per cent: both are nuisance parameters that do not enter the solve, like the magnitude offset
+ * of trpl_mag_grid.  A bank is H [J][K] fp64: J responses of ONE length K and ONE index k0 of the tap at time zero -- a shift
+ * lives in the taps of a row, zero-padded to the common length, so that all J responses read the same window of PL.
+ * (csrc/irf_bank.hip)
+ *
+ * Definition.  For every j < J and every row, sse[j][row] and esum[j][row] (both [J][rows]; esum nullable) are, bit for bit,
+ * what these two calls produce for that row:
+ *     trpl_convolve_irf_dev(pl, elem_bytes, rows, ncol, ld, H + j K, K, k0, cv, ncol - k0, stream)
+ *     trpl_loglik_moments_from_pl_dev(cv, elem_bytes, rows, ncol - k0, ncol - k0, obs, obs_hi, obs_dx, obs_h, n_obs, mag, status,
+ *                                     NULL, sse + j rows, esum + j rows, flags, stream)
+ * (trpl_loglik_weighted_from_pl_dev with wts [n_obs] when wts is given).  That fixes the convolved value (fp64 accumulator from
+ * +0.0, ascending k, one rounded product and one rounded addition per term, a term left of column 0 skipped, a 4-byte block
+ * rounds the sum to float before the logarithm), the error (y + mag - obs with y = log10 max(cv, DBL_MIN), through fp32 under
+ * TRPL_FLAG_PL_F32 or a 4-byte block; off the grid ((y_hi - y_lo) / obs_h) * obs_dx + y_lo on the convolved columns obs_hi - 1
+ * and obs_hi), the association of the sums (a 256-thread workgroup per row: thread t adds observations t, t + 256, ... in
+ * ascending order, an xor butterfly inside each 64-lane wave, then ((p0 + p1) + p2) + p3) and the flagged-row rule (status != 0
+ * or a NaN sum: sse = +inf, esum = NaN).  obs_hi [n_obs] in [1, ncol - k0 - 1], in ANY order.  The convolved block is never
+ * written: the kernel convolves at the observed columns only, TRPL_IRF_BANK_BLOCK responses per pass over the taps.  None of
+ * the blocking enters the result.
+ *
+ * Refused with TRPL_ERR_ARG before a device is touched, the message naming the argument, in this order: elem_bytes other than
+ * 4 or 8; rows < 0 or > 2^31 - 1; ncol < 1 or > 2^31 - 1; ld < ncol; K < 1 or K > TRPL_IRF_MAX_TAPS; k0 outside [0, K - 1];
+ * ncol - k0 < 1; J < 1 or J > TRPL_IRF_BANK_MAX_RESPONSES; n_obs < 1; obs_hi, obs_dx and obs_h not all NULL or all non-NULL;
+ * on the grid n_obs > ncol - k0; off the grid ncol - k0 < 2; TRPL_FLAG_NORMALIZE (the convolved curve's first column is a
+ * fraction of the response's area, not PL(0)); any other flag than TRPL_FLAG_PL_F32; with rows > 0 a NULL pl, H, obs, mag or
+ * sse.  rows == 0 is TRPL_OK without a launch.  The host-buffer form (every array on the host; seconds, nullable, the kernel's
+ * time) then also refuses a tap that is not finite, a weight that is not finite and >= 0, and an obs_hi outside
+ * [1, ncol - k0 - 1], each with its index.  The _dev call takes device pointers only, allocates nothing and never synchronises;
+ * there the caller owns those three.
+ *
+ * trpl_irf_bank_profile* -- the profile over the bank: Pbank [J][S] -> P[s] = the greatest Pbank[j][s], best[s] (int32) = the
+ * first j that attains it; a NaN is never the greatest, and where every value is -inf or NaN best = -1 and P = -inf.  The host
+ * form is PLAIN HOST CODE (no device, like trpl_mag_profile); the _dev kernel (one thread per sample) equals it bit for bit.
+ * Refused: J outside [1, TRPL_IRF_BANK_MAX_RESPONSES]; S < 0; with S > 0 a NULL Pbank, best or P.  S == 0 is TRPL_OK.
+ *
+ * Out of scope: a marginal (log-sum-exp) over the bank; composition with trpl_mag_grid / trpl_mag_profile (esum is returned so
+ * that it can follow); gpu_info["irf_bank"] inside simulate / bayes; multi-device forms; a bank inside the fused steppers.
+ * Python: trpl_amd.irf.gaussian_bank / shift_bank / loglik_bank / loglik_profile, trpl_amd.device.loglik_irf_bank_device /
+ * irf_bank_profile_device.
+ * ------------------------------------------------------------------------------------- */
+#define TRPL_IRF_BANK_MAX_RESPONSES 256
+#define TRPL_IRF_BANK_BLOCK 8
+int trpl_irf_bank_max_responses(void);
+int trpl_irf_bank_block(void);
+int trpl_loglik_irf_bank_dev(const void *pl, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld,
+                             const double *H /*device [J][K]*/, int32_t J, int32_t K, int32_t k0, const double *obs,
+                             const int32_t *obs_hi, const double *obs_dx, const double *obs_h, int64_t n_obs,
+                             const double *wts /*nullable*/, const double *mag, const int32_t *status /*nullable*/,
+                             double *sse /*[J][rows]*/, double *esum /*[J][rows], nullable*/, uint32_t flags, void *stream);
+int trpl_loglik_irf_bank(const void *pl, int32_t elem_bytes, int64_t rows, int64_t ncol, int64_t ld, const double *H, int32_t J,
+                         int32_t K, int32_t k0, const double *obs, const int32_t *obs_hi, const double *obs_dx,
+                         const double *obs_h, int64_t n_obs, const double *wts, const double *mag, const int32_t *status,
+                         double *sse, double *esum, uint32_t flags, int32_t device, double *seconds);
+int trpl_irf_bank_profile_dev(const double *Pbank /*[J][S]*/, int32_t J, int64_t S, int32_t *best /*[S]*/, double *P /*[S]*/,
+                              void *stream);
+int trpl_irf_bank_profile(const double *Pbank, int32_t J, int64_t S, int32_t *best, double *P);
+
+/* ---------------------------------------------------------------------------------------
  * trpl_corner* -- the corner: every posterior marginal of a finished run in one device call.  What plot() of
  * Visualization/marginalization_visual.py:500-609 does after loading a run: drop the samples outside the axis limits
  * (utils.py:48-52, :145-155), add the secondary parameters (utils.py:54-79, secondary_parameters.py), take log10 of the

@@ -10,6 +10,11 @@ kernel:  one trpl_convolve_irf_dev over a [rows][ncol] PL matrix (ld = ncol: odd
 --route: the resident route solve -> convolve -> likelihood at the default bench shape (Power_scan, 3 curves, L = 128, T = 8000,
          one block of 8192 samples) with a 33-tap Gaussian response, each of the three calls timed with device events per curve:
          the convolution's share of the route's seconds, and the route without it.
+--bank:  trpl_loglik_irf_bank_dev beside the loop it replaces -- J x (trpl_convolve_irf_dev + trpl_loglik_moments_from_pl_dev) -- on
+         the same [rows][ncol] matrix with dense on-grid observations (n_obs = ncol - k0), per K of --taps and J of --responses, both
+         timed in this process as above.  Floors: the fp64 floor of the convolution at the observed columns, two instructions per
+         term, times J; the HBM floor of ONE read of the block.  With --route also the resident route solve -> bank -> profile at
+         the default bench shape with 33 taps and J = 16.  Lines go to profiles/irf_bank_bench.jsonl unless --out is given.
 Appends one JSON line per measurement to --out."""
 import argparse
 import json
@@ -111,6 +116,108 @@ def bench_route(a, out):
          "irf_share_of_route": med["convolve"] / with_irf, "reps": a.route_reps})
 
 
+def timed(fn, warm=3, reps=10):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = events()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return float(np.median(ms)), float(min(ms)), float(max(ms))
+
+
+def bench_bank(a, out):
+    dev = torch.device("cuda", 0)
+    rows, ncol = a.rows, a.ncol
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    for dt in (torch.float64, torch.float32):
+        elem = 8 if dt == torch.float64 else 4
+        pl = torch.empty((rows, ncol), dtype=dt, device=dev)
+        pl.uniform_(-12.0, 0.0, generator=g)
+        pl.mul_(float(np.log(10.0))).exp_()
+        mag = torch.zeros(rows, dtype=torch.float64, device=dev)
+        for K in a.taps:
+            k0 = K // 2
+            n_obs = ncol - k0
+            obs = torch.zeros(n_obs, dtype=torch.float64, device=dev)
+            cv = torch.empty((rows, n_obs), dtype=dt, device=dev)
+            for J in a.responses:
+                H = torch.from_numpy(np.random.default_rng(K + J).uniform(0.1, 1.0, (J, K))).to(dev)
+                sse = torch.empty((J, rows), dtype=torch.float64, device=dev)
+                esum = torch.empty((J, rows), dtype=torch.float64, device=dev)
+
+                def loop():
+                    for j in range(J):
+                        tdev.convolve_irf_device(pl, H[j], k0, cv)
+                        tdev.loglik_moments_from_pl_device(cv, obs, mag, sse=sse[j], esum=esum[j])
+
+                def bank():
+                    tdev.loglik_irf_bank_device(pl, H, k0, obs, mag, sse, esum=esum)
+
+                loop_ms, bank_ms = timed(loop), timed(bank)
+                terms = rows * n_obs * K * J
+                out({"bench": "irf_bank", "device": torch.cuda.get_device_name(0), "rows": rows, "ncol": ncol, "elem_bytes": elem, "K": K,
+                     "k0": k0, "J": J, "n_obs": n_obs, "bank_ms": bank_ms[0], "bank_ms_min": bank_ms[1], "bank_ms_max": bank_ms[2],
+                     "loop_ms": loop_ms[0], "loop_ms_min": loop_ms[1], "loop_ms_max": loop_ms[2], "loop_over_bank": loop_ms[0] / bank_ms[0],
+                     "fp64_floor_ms": 2 * terms / FP64_LANE_INSTR_PS * 1e3, "hbm_floor_ms": rows * ncol * elem / PEAK_BPS * 1e3})
+        del pl, cv
+
+
+def bench_bank_route(a, out):
+    dev = torch.device("cuda", 0)
+    w = trpl_amd.workloads
+    L, T, S, J = 128, 8000, a.samples, 16
+    Time = T * 0.025
+    dt = Time / T
+    ini, lens = w.power_scan(L)
+    X = w.samples(S)
+    H, k0, _ = trpl_amd.irf.gaussian_bank([0.15, 0.188], np.linspace(-2 * dt, 2 * dt, 8), dt, rel_cut=1e-6)
+    X_d = torch.from_numpy(X).to(dev)
+    mat, mag = X_d[:, :12].contiguous(), X_d[:, 12].contiguous()
+    ini_d, H_d = torch.from_numpy(ini).to(dev), torch.from_numpy(H).to(dev)
+    pl = torch.empty((S, T + 1), dtype=torch.float64, device=dev)
+    st = torch.zeros(S, dtype=torch.int32, device=dev)
+    obs = torch.zeros(T + 1 - k0, dtype=torch.float64, device=dev)
+    sse = torch.empty((3, J, S), dtype=torch.float64, device=dev)
+    P = torch.zeros((J, S), dtype=torch.float64, device=dev)
+    LL = torch.empty(S, dtype=torch.float64, device=dev)
+    best = torch.empty(S, dtype=torch.int32, device=dev)
+    runs = []
+    for rep in range(1 + a.route_reps):
+        t = {"solve": 0.0, "bank": 0.0, "profile": 0.0}
+        P.zero_()
+        for c in range(3):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record()
+            tdev.solve_pl_device(mat, lens[c], Time, L, T, ini_d[c].contiguous(), pl, status=st)
+            ev[1].record()
+            tdev.loglik_irf_bank_device(pl, H_d, k0, obs, mag, sse[c], status=st)
+            ev[2].record()
+            torch.cuda.synchronize()
+            P -= sse[c]
+            t["solve"] += ev[0].elapsed_time(ev[1]) / 1e3
+            t["bank"] += ev[1].elapsed_time(ev[2]) / 1e3
+        e0, e1 = events()
+        e0.record()
+        tdev.irf_bank_profile_device(P, best, LL)
+        e1.record()
+        torch.cuda.synchronize()
+        t["profile"] = e0.elapsed_time(e1) / 1e3
+        if rep:
+            runs.append(t)
+    med = {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
+    total = sum(med.values())
+    out({"bench": "irf_bank_route", "device": torch.cuda.get_device_name(0), "workload": "Power_scan", "curves": 3, "L": L, "T": T,
+         "samples": S, "K": int(H.shape[1]), "k0": int(k0), "J": int(H.shape[0]), "seconds": med, "route_s": total,
+         "bank_share_of_route": med["bank"] / total, "reps": a.route_reps})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=65536)
@@ -120,8 +227,14 @@ def main():
     ap.add_argument("--samples", type=int, default=8192)
     ap.add_argument("--route-reps", type=int, default=3)
     ap.add_argument("--no-kernel", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "irf_bench.jsonl"))
+    ap.add_argument("--bank", action="store_true")
+    ap.add_argument("--responses", type=lambda s: [int(v) for v in s.split(",")], default=[1, 8, 32])
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "irf_bank_bench.jsonl" if a.bank else "irf_bench.jsonl")
+    if a.bank and a.taps == [5, 33, 257, 1024]:
+        a.taps = [5, 33, 257]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
 
     def out(line):
@@ -129,6 +242,12 @@ def main():
             f.write(json.dumps(line) + "\n")
         print(json.dumps(line), flush=True)
 
+    if a.bank:
+        if not a.no_kernel:
+            bench_bank(a, out)
+        if a.route:
+            bench_bank_route(a, out)
+        return 0
     if not a.no_kernel:
         bench_kernel(a, out)
     if a.route:

@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--subspace [--pairs n] [--ncr n] [--adapt-cr]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject [sample]] [--tempered K [--tf-hot x] [--evidence]]] [--irf FWHM_NS]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--subspace [--pairs n] [--ncr n] [--adapt-cr]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject [sample]] [--tempered K [--tf-hot x] [--evidence]]] [--irf FWHM_NS [--irf-shifts LO:HI:N] [--irf-widths LO:HI:N]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -69,6 +69,11 @@ a proposal moved.
 point's curves convolved with it (what the detector would have recorded), every sample scored by irf.loglik (solve, convolve,
 likelihood on the resident PL block).  "irf" holds the taps, the effective sample size and the 2.5 / 50 / 97.5 % values of every
 free parameter beside those of the run without the response, which are printed -- recorded, not gated -- and seconds["irf"].
+--irf-shifts LO:HI:N (ns) and --irf-widths LO:HI:N (ns; default: the one width of --irf) add the profile over a bank of responses
+(irf.gaussian_bank, irf.loglik_profile: DESIGN.md section 36): the observations are the marked point's curves convolved with a
+response of the bank that is NOT its centre (three quarters along each axis), every sample is scored by the profile and, beside it,
+by irf.loglik with the response fixed at the bank's centre.  "irf_bank" holds the posterior-weighted distribution of the best
+response, the effective sample sizes and the intervals of both runs, which are printed -- recorded, not gated.
 """
 import json
 import sys
@@ -146,6 +151,16 @@ if "--irf" in sys.argv:
     k = sys.argv.index("--irf")
     IRF_FWHM = float(sys.argv[k + 1])
     del sys.argv[k:k + 2]
+IRF_SHIFTS = IRF_WIDTHS = None
+for flag in ("--irf-shifts", "--irf-widths"):
+    if flag in sys.argv:
+        k = sys.argv.index(flag)
+        lo_, hi_, n_ = sys.argv[k + 1].split(":")
+        grid_ = [float(lo_) + (float(hi_) - float(lo_)) * i / max(int(n_) - 1, 1) for i in range(int(n_))]
+        IRF_SHIFTS, IRF_WIDTHS = (grid_, IRF_WIDTHS) if flag == "--irf-shifts" else (IRF_SHIFTS, grid_)
+        del sys.argv[k:k + 2]
+if (IRF_SHIFTS is not None or IRF_WIDTHS is not None) and IRF_FWHM is None:
+    sys.exit("--irf-shifts / --irf-widths need --irf FWHM_NS")
 PRIORS = {}
 while "--prior" in sys.argv:
     k = sys.argv.index("--prior")
@@ -496,4 +511,46 @@ if IRF_FWHM is not None:
     for k, n in enumerate(names):
         print("irf: %-8s truth %9.4f | with the response %9.4f %9.4f %9.4f | without %9.4f %9.4f %9.4f"
               % ((n, truth[k]) + tuple(q_irf[:, k]) + tuple(q_bare[:, k])), file=sys.stderr)
+if IRF_FWHM is not None and (IRF_SHIFTS is not None or IRF_WIDTHS is not None):
+    # the profile over a bank of responses: the detector's response is NOT the bank's centre
+    t13 = sync()
+    shifts = [0.0] if IRF_SHIFTS is None else IRF_SHIFTS
+    widths = [IRF_FWHM] if IRF_WIDTHS is None else IRF_WIDTHS
+    bank = tirf.gaussian_bank(widths, shifts, dt)
+    Hb, kb, table = bank
+    J = len(Hb)
+    centre = (len(widths) // 2) * len(shifts) + len(shifts) // 2
+    true_w, true_s = int(round(0.75 * (len(widths) - 1))), int(round(0.75 * (len(shifts) - 1)))
+    j_true = true_w * len(shifts) + true_s
+    if j_true == centre and J > 1:
+        j_true = J - 1
+    seen_b = tirf.convolve(10.0 ** obs.cpu().numpy(), Hb[j_true], kb)
+    obs_b = [np.log10(seen_b[c]) for c in range(C)]
+    binfo = {}
+    Xh = X.cpu().numpy()
+    LL_prof = tirf.loglik_profile(Xh, ini, lens, T * dt, L, T, obs_b, bank, info=binfo)
+    LL_fix = tirf.loglik(Xh, ini, lens, T * dt, L, T, obs_b, (Hb[centre], kb))
+    tf_b = C * (T + 1 - kb) * c_val
+    W_prof, W_fix = posterior.weights(LL_prof, tf_b), posterior.weights(LL_fix, tf_b)
+    ok = binfo["best"] >= 0
+    share = np.bincount(binfo["best"][ok], weights=np.nan_to_num(W_prof[ok]), minlength=J)
+    ess_prof, ess_fix = float(1.0 / np.nansum(W_prof * W_prof)), float(1.0 / np.nansum(W_fix * W_fix))
+    q_prof = posterior.quantiles(V.cpu().numpy(), W_prof, [0.025, 0.5, 0.975])
+    q_fix = posterior.quantiles(V.cpu().numpy(), W_fix, [0.025, 0.5, 0.975])
+    out["seconds"]["irf_bank"] = sync() - t13
+    out["irf_bank"] = {"responses": J, "taps": int(Hb.shape[1]), "k0": int(kb), "table": table.tolist(), "true_response": j_true,
+                       "fixed_response": centre, "best_share": share.tolist(), "recovered_response": int(np.argmax(share)),
+                       "effective_sample_size_profile": ess_prof, "effective_sample_size_fixed": ess_fix,
+                       "quantiles": {n: {"truth": float(tr), "profile": [float(v) for v in q_prof[:, k]], "fixed": [float(v) for v in q_fix[:, k]]}
+                                     for k, (n, tr) in enumerate(zip(names, truth))}}
+    print("irf bank: %d responses of %d taps; the detector's is %d (fwhm %g ns, shift %g ns), the fixed run uses %d (fwhm %g ns, shift %g ns)"
+          % ((J, Hb.shape[1], j_true) + tuple(table[j_true]) + (centre,) + tuple(table[centre])), file=sys.stderr)
+    print("irf bank: effective sample size %.2f with the profile, %.2f with the fixed response, %.2f s"
+          % (ess_prof, ess_fix, out["seconds"]["irf_bank"]), file=sys.stderr)
+    for j in np.argsort(-share)[:min(J, 8)]:
+        print("irf bank: response %3d  fwhm %8.4f ns  shift %+9.5f ns  posterior share of best %.4f%s"
+              % (j, table[j][0], table[j][1], share[j], "   <- the detector's" if j == j_true else ""), file=sys.stderr)
+    for k, n in enumerate(names):
+        print("irf bank: %-8s truth %9.4f | profile %9.4f %9.4f %9.4f | fixed response %9.4f %9.4f %9.4f"
+              % ((n, truth[k]) + tuple(q_prof[:, k]) + tuple(q_fix[:, k])), file=sys.stderr)
 print(json.dumps(out))
