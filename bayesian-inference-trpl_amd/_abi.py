@@ -82,6 +82,8 @@ MCMC_MAX_PAIRS, MCMC_MAX_CR = 4, 8      # TRPL_MCMC_MAX_PAIRS, TRPL_MCMC_MAX_CR:
 IRF_MAX_TAPS = 1024           # TRPL_IRF_MAX_TAPS: taps of one trpl_convolve_irf (trpl_irf_max_taps())
 IRF_TILE_COLS, IRF_TILE_ROWS, IRF_GRID_CAP = 512, 4, 65536      # TRPL_IRF_TILE_COLS / _ROWS: a workgroup's tile; TRPL_IRF_GRID_CAP: workgroups of a launch
 IRF_BANK_MAX_RESPONSES, IRF_BANK_BLOCK = 256, 8      # TRPL_IRF_BANK_MAX_RESPONSES: responses of one trpl_loglik_irf_bank; TRPL_IRF_BANK_BLOCK: those of one pass over the taps
+NUISANCE_MAX_OFFSETS = 64     # TRPL_NUISANCE_MAX_OFFSETS: magnitude offsets of one trpl_nuisance_reduce
+NUISANCE_MAG_FIXED, NUISANCE_MAG_GRID, NUISANCE_MAG_PROFILE, NUISANCE_MARGINAL = 0x0, 0x1, 0x2, 0x10      # TRPL_NUISANCE_*: a mag mode | the marginal
 SEED_MASK, STEP_MASK = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF      # a uint64_t seed and a uint32_t step of the trpl_mcmc_* calls, from any int
 
 
@@ -218,6 +220,11 @@ SIGNATURES = {
                              _i32, _pd],
     "trpl_irf_bank_profile_dev": [_vp, _i32, _i64, _vp, _vp, _vp],
     "trpl_irf_bank_profile": [_vp, _i32, _i64, _vp, _vp],
+    "trpl_nuisance_max_offsets": [],
+    "trpl_nuisance_bound": [_f64, _f64, _i32, _f64],
+    # sse, esum [C][J][S], wsum (host); S, C, J; offsets (host), M; logw, tf, flags; P, best, best_mag
+    "trpl_nuisance_reduce_dev": [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _f64, _u32, _vp, _vp, _vp, _vp],
+    "trpl_nuisance_reduce": [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _f64, _u32, _vp, _vp, _vp],
     "trpl_corner_workspace_bytes": [_i64, _i32],
     "trpl_corner_columns_dev": [_vp, _i64, _i64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "trpl_corner_hist_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
@@ -411,7 +418,8 @@ def lib():
                                      "trpl_posterior_tf_scan_lr_workspace", "trpl_shard_of",
                                      "trpl_predictive_state_bytes", "trpl_predictive_workspace_bytes",
                                      "trpl_quantiles_stage_rows", "trpl_corner_workspace_bytes", "trpl_refine_chunk_rows",
-                                     "trpl_refine_tile_parents", "trpl_refine_workspace_bytes") else C.c_int)
+                                     "trpl_refine_tile_parents", "trpl_refine_workspace_bytes") else
+                C.c_double if name == "trpl_nuisance_bound" else C.c_int)
         _lib = dll
     return _lib
 

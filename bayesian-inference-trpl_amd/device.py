@@ -516,6 +516,51 @@ def irf_bank_profile_device(Pbank, best, P):
                                                     _chk(best, torch.int32, "best"), _chk(P, torch.float64, "P"), _stream()))
 
 
+def nuisance_flags(mag, marginal):
+    """(flags, offsets) of a trpl_nuisance_reduce call: mag "fixed", "profile" or a sequence of offsets (grid mode); offsets is a
+    host float64 array or None."""
+    if isinstance(mag, str):
+        if mag not in ("fixed", "profile"):
+            raise ValueError('mag must be "fixed", "profile" or a sequence of offsets, got %r' % (mag,))
+        flags, off = (_abi.NUISANCE_MAG_FIXED if mag == "fixed" else _abi.NUISANCE_MAG_PROFILE), None
+    else:
+        off = np.ascontiguousarray(mag, dtype=np.float64).ravel()
+        flags = _abi.NUISANCE_MAG_GRID
+    return flags | (_abi.NUISANCE_MARGINAL if marginal else 0), off
+
+
+def nuisance_reduce_device(sse, esum, wsum, P, best=None, best_mag=None, mag="fixed", marginal=False, tf=1.0, log_prior=None):
+    """trpl_nuisance_reduce_dev: P (S,) f64 <- the reduction over the nuisance grid, J responses x M magnitude offsets, of the
+    moments sse, esum (C, J, S) f64 as loglik_irf_bank_device wrote them curve by curve (esum may be None with mag="fixed");
+    wsum a host sequence (C,), n_obs or the sum of each curve's weights.  mag: "fixed" (M = 1, the offset 0), "profile" (M = 1,
+    the likelihood-maximising offset per response) or a host sequence of M offsets (the grid).  marginal=False: the greatest
+    cell; True: tf * log sum_i exp(v_i / tf + log_prior_i) (include/trpl.h).  log_prior (J * M,) or (J, M): a float64 CUDA tensor,
+    used as it is (NaN and +inf are the caller's to exclude), or a host array, checked and uploaded; marginal only.  best (S,)
+    int32 and best_mag (S,) f64, optional: the first cell j * M + m that attains the maximum and its offset."""
+    import torch
+    f64 = torch.float64
+    if sse.dim() != 3:
+        raise ValueError("sse must be (C, J, S)")
+    Cn, J, S = sse.shape
+    flags, off = nuisance_flags(mag, marginal)
+    M = 1 if off is None else len(off)
+    wsum = np.ascontiguousarray(np.broadcast_to(np.asarray(wsum, dtype=np.float64), (Cn,)))
+    if (esum is not None and esum.shape != sse.shape) or tuple(P.shape) != (S,) \
+            or any(t is not None and tuple(t.shape) != (S,) for t in (best, best_mag)):
+        raise ValueError("shape mismatch")
+    if log_prior is not None and not isinstance(log_prior, torch.Tensor):
+        lp = np.ascontiguousarray(log_prior, dtype=np.float64)
+        if marginal and (np.isnan(lp).any() or (lp == np.inf).any()):
+            raise ValueError("log_prior must not hold NaN or +inf")
+        log_prior = torch.from_numpy(lp).to(sse.device)
+    if log_prior is not None and log_prior.numel() != J * M:
+        raise ValueError("log_prior must hold J * M = %d entries, got %d" % (J * M, log_prior.numel()))
+    _abi.check(_abi.lib().trpl_nuisance_reduce_dev(
+        _chk(sse, f64, "sse"), _opt(esum, f64, "esum"), _abi.ptr(wsum), S, Cn, J, None if off is None else _abi.ptr(off), M,
+        _opt(log_prior, f64, "log_prior"), float(tf), flags, _chk(P, f64, "P"), _opt(best, torch.int32, "best"),
+        _opt(best_mag, f64, "best_mag"), _stream()))
+
+
 def posterior_hist_device(x, W, lo, hi, out, y=None, ylo=0.0, yhi=1.0):
     """out (bins,) or (bins, ybins) += weighted counts (W None: counts); the caller zeroes out."""
     import torch

@@ -363,7 +363,7 @@ def _bundle_of(gpu_info, L):
 
 def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_params, normalize, pl_dtype, group,
                        num_gpus, gpu_id, device, solver_time, err_sq_time, sim_t, bundle=1, literal=False, predict=False,
-                       mag_grid=None, weighted=False, irf=None):
+                       mag_grid=None, weighted=False, irf=None, irf_bank=None):
     """Several experiments, fused option on: the reference's own loop order -- curves -> sample blocks ->
     experiments (bayeslib.py:117-171) -- with the block's PL matrix kept in HBM: one solve per (curve, block)
     (trpl_solve_pl_dev), then one pass over it per experiment (trpl_loglik_from_pl_dev: normalise, clamp,
@@ -373,7 +373,10 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
     trpl_mag_grid_dev fills the M rows of every experiment.  weighted (gpu_info["weighted"]): every pass is
     trpl_loglik_weighted_from_pl_dev with the weights of the experiment's uncertainty column (and trpl_mag_grid_w_dev).
     irf (gpu_info["irf"]) = (h, k0): every solved block is convolved with the instrument response (trpl_convolve_irf_dev) and the
-    passes run over the convolved block, whose ncol is T + 1 - k0."""
+    passes run over the convolved block, whose ncol is T + 1 - k0.
+    irf_bank (gpu_info["irf_bank"]) = dict(H, k0, mag, marginal, tf, log_prior): per experiment and curve the pass is
+    trpl_loglik_irf_bank_dev, the moments of the J responses stay in HBM, and after a block's last curve ONE
+    trpl_nuisance_reduce_dev per experiment adds the maximum or the marginal over responses x magnitude offsets to P."""
     import torch
 
     from . import device as tdev
@@ -385,6 +388,9 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
         ini_d = torch.from_numpy(np.ascontiguousarray(init_params, dtype=np.float64)).to(dev)
         if irf is not None:
             h_d = torch.from_numpy(irf[0]).to(dev)
+        if irf_bank is not None:
+            H_d = torch.from_numpy(irf_bank["H"]).to(dev)
+            lp_d = None if irf_bank["log_prior"] is None else torch.from_numpy(irf_bank["log_prior"]).to(dev)
         # per (experiment, curve), staged once: the keywords of its pass over a PL block -- observations, off the grid their
         # brackets, weights -- and what trpl_mag_grid[_w]_dev takes for the curve, n_obs or the sum of the weights
         def to_dev(a):
@@ -422,6 +428,10 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
                     P.reshape(len(e_data), M, S_all)[:, :, blk:blk + size])).to(dev)            # (n_exp, M, size)
                 sse_d = torch.zeros((len(e_data), num_curves, size), dtype=torch.float64, device=dev)
                 esum_d = torch.zeros_like(sse_d)
+            if irf_bank is not None:
+                sse_d = torch.zeros((len(e_data), num_curves, len(irf_bank["H"]), size), dtype=torch.float64, device=dev)
+                esum_d = torch.zeros_like(sse_d)
+                LL_d = torch.empty(size, dtype=torch.float64, device=dev)
             for c in range(num_curves):                                       # :117
                 torch.cuda.synchronize(dev)
                 t0 = time.perf_counter()
@@ -433,11 +443,20 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
                 if irf is not None:
                     tdev.convolve_irf_device(pl_d, h_d, irf[1], seen_d)
                 for e, per_curve in enumerate(staged):                        # :171
+                    if irf_bank is not None:
+                        tdev.loglik_irf_bank_device(pl_d, H_d, irf_bank["k0"], mag=mag_d, sse=sse_d[e, c], esum=esum_d[e, c], status=st_d,
+                                                    **per_curve[c][0])
+                        continue
                     out = {"P": P_d[e]} if mag_grid is None else {"sse": sse_d[e, c], "esum": esum_d[e, c]}
                     getattr(tdev, pass_name)(seen_d, mag=mag_d, flags=flags, status=st_d, **per_curve[c][0], **out)
                 torch.cuda.synchronize(dev)
                 solver_time[gpu_id] += t1 - t0
                 err_sq_time[gpu_id] += time.perf_counter() - t1
+            if irf_bank is not None:
+                for e, per_curve in enumerate(staged):
+                    tdev.nuisance_reduce_device(sse_d[e], esum_d[e], [float(n) for _, n in per_curve], LL_d, mag=irf_bank["mag"],
+                                                marginal=irf_bank["marginal"], tf=irf_bank["tf"], log_prior=lp_d)
+                    P_d[e] += LL_d
             if mag_grid is not None:
                 mag_grid_device = tdev.mag_grid_w_device if weighted else tdev.mag_grid_device
                 for e, per_curve in enumerate(staged):
@@ -445,6 +464,30 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
                 P.reshape(len(e_data), M, S_all)[:, :, blk:blk + size] = P_d.cpu().numpy()
                 continue
             P[:, blk:blk + size] = P_d.cpu().numpy()
+
+
+def _check_irf_bank(opt):
+    """gpu_info['irf_bank'] checked as irf.loglik_nuisance checks its arguments -> dict(H, k0, mag, marginal, tf, log_prior)."""
+    from . import device as tdev
+    from .irf import _check_bank, _check_prior
+    if not isinstance(opt, dict) or "bank" not in opt:
+        raise ValueError("gpu_info['irf_bank'] must be a dict with the entry bank=(H, k0[, table])")
+    unknown = set(opt) - {"bank", "mag", "reduce", "tf", "log_prior"}
+    if unknown:
+        raise ValueError("gpu_info['irf_bank']: unknown entries %s" % sorted(unknown))
+    H, k0 = _check_bank(opt["bank"])
+    mag, reduce, tf = opt.get("mag", "fixed"), opt.get("reduce", "max"), float(opt.get("tf", 1.0))
+    if reduce not in ("max", "marginal"):
+        raise ValueError('gpu_info[\'irf_bank\']: reduce must be "max" or "marginal", got %r' % (reduce,))
+    marginal = reduce == "marginal"
+    _, off = tdev.nuisance_flags(mag, marginal)
+    M = 1 if off is None else len(off)
+    if not 1 <= M <= _abi.NUISANCE_MAX_OFFSETS or (off is not None and not np.all(np.isfinite(off))):
+        raise ValueError("gpu_info['irf_bank']: mag as a grid holds 1 .. %d finite offsets" % _abi.NUISANCE_MAX_OFFSETS)
+    if marginal and not (tf > 0.0 and math.isfinite(tf)):
+        raise ValueError("gpu_info['irf_bank']: tf must be finite and > 0")
+    return dict(H=H, k0=k0, mag=mag if off is None else off, marginal=marginal, tf=tf,
+                log_prior=_check_prior(opt.get("log_prior"), H.shape[0], M, marginal))
 
 
 def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_params, sim_flags, gpu_info, gpu_id,
@@ -485,6 +528,14 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
     curve ends at Time * (T - k0) / T, and a later observation is a ValueError.  Combines with 'predict', 'weighted' and 'mag_grid'
     (passes over the same block).  The unfused sequence, 'devices', 'cut_margin' and self_normalize are a ValueError naming the
     option: the fused steppers compare the bare curve, and a convolved curve's first column is not PL(0).
+    gpu_info['irf_bank'] = dict(bank=(H, k0[, table]), mag="fixed" | "profile" | offsets, reduce="max" | "marginal", tf=1.0,
+    log_prior=None) (default absent: nothing changes): the instrument response and the magnitude offset as nuisance parameters,
+    reduced on the device (irf.loglik_nuisance has the meaning of every entry; only bank is required).  On the resident-PL level
+    of one device, whatever the number of experiments: per experiment, block and curve one trpl_loglik_irf_bank_dev, then one
+    trpl_nuisance_reduce_dev per experiment and block, whose result is added to P (n_exp, S); the moments never leave the device.
+    Combines with 'predict' and 'weighted'.  'irf', 'mag_grid', 'devices', 'num_gpus' > 1, 'cut_margin', 'max_sims_per_block' > 1,
+    self_normalize and the unfused sequence are a ValueError naming the option; so is an observation after the last convolved
+    column, Time * (T - k0) / T.
     """
     group = int(gpu_info["sims_per_gpu"])
     num_gpus = int(gpu_info["num_gpus"])
@@ -553,6 +604,26 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
         if any(np.max(np.asarray(exp[0][c], dtype=float)) > sim_t[T - irf[1]] for exp in e_data for c in range(num_curves)):
             raise ValueError("gpu_info['irf']: an observation lies after Time * (T - k0) / T = %g, the last convolved column"
                              % last_time(Time, T, irf[1]))
+    irf_bank = gpu_info.get("irf_bank")
+    if irf_bank is not None:
+        irf_bank = _check_irf_bank(irf_bank)
+        for name, bad in (("irf", irf is not None), ("mag_grid", gpu_info.get("mag_grid") is not None),
+                          ("devices", gpu_info.get("devices") is not None), ("num_gpus", num_gpus != 1),
+                          ("cut_margin", cut_margin is not None), ("max_sims_per_block", int(gpu_info.get("max_sims_per_block", 1)) > 1),
+                          ("self_normalize", bool(NORMALIZE))):
+            if bad:
+                raise ValueError("gpu_info['irf_bank'] does not combine with %s: the bank is scored on the resident-PL level of one "
+                                 "device, on curves that are not self-normalised, and brings its own reduction over the magnitude "
+                                 "offset" % name)
+        if not fused:
+            raise ValueError("gpu_info['irf_bank'] needs the fused level, not the unfused sequence: gpu_info['fused'] = True, log_pl, PL "
+                             "stride 1 and observation times inside the simulated window")
+        k0 = irf_bank["k0"]
+        if T + 1 - k0 < 2:
+            raise ValueError("gpu_info['irf_bank']: k0 = %d leaves fewer than two columns of a window of T = %d steps" % (k0, T))
+        if any(np.max(np.asarray(exp[0][c], dtype=float)) > sim_t[T - k0] for exp in e_data for c in range(num_curves)):
+            raise ValueError("gpu_info['irf_bank']: an observation lies after Time * (T - k0) / T = %g, the last convolved column"
+                             % (float(Time) * (T - k0) / T))
     mag_grid = gpu_info.get("mag_grid")
     if mag_grid is not None:
         mag_grid = np.ascontiguousarray(mag_grid, dtype=np.float64).ravel()
@@ -568,11 +639,11 @@ def simulate(model, e_data, P, X, plI, plI_int, num_curves, sim_params, init_par
         if P.shape != (len(e_data), len(mag_grid) * len(X)) or not P.flags.c_contiguous:
             raise ValueError("gpu_info['mag_grid']: P must be a contiguous (n_exp, M * S) = (%d, %d) array"
                              % (len(e_data), len(mag_grid) * len(X)))
-    if fused and (len(e_data) > 1 or irf is not None) and gpu_info.get("devices") is None:
+    if fused and (len(e_data) > 1 or irf is not None or irf_bank is not None) and gpu_info.get("devices") is None:
         _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_params, NORMALIZE, pl_dtype,
                            group, num_gpus, gpu_id, device, solver_time, err_sq_time, sim_t,
                            bundle=_bundle_of(gpu_info, L), literal=bool(gpu_info.get("interpolate_prefix", False)),
-                           predict=predict, mag_grid=mag_grid, weighted=weighted, irf=irf)
+                           predict=predict, mag_grid=mag_grid, weighted=weighted, irf=irf, irf_bank=irf_bank)
         return
     if fused:
         # An experiment sampled exactly on the full simulation grid is compared point by point (the reference's bypass,

@@ -13,6 +13,8 @@ include/trpl.h; csrc/irf.hip): every consumer of such a block takes the convolve
     shift_bank((h, k0), shifts_ns, dt_ns)   a measured response at several time shifts -> (H, k0, table)
     loglik_bank(X, ..., obs, bank)          solve -> the likelihood per response of the bank, from one solve -> P (J, S)
     loglik_profile(X, ..., obs, bank)       the profile of loglik_bank over the bank; X -> LL for refine / mcmc
+    loglik_nuisance(X, ..., obs, bank, mag=, reduce=)   the maximum or the marginal over responses x magnitude offsets, reduced
+                                            on the device; X -> LL for refine / mcmc
 
 An IRF is the pair (h, k0): the taps at the grid's spacing and the index of the tap that sits at time zero (the peak).  The
 convolved curve has k0 columns less than the solved one: its last k0 columns would need PL past the solved window.
@@ -458,4 +460,114 @@ def loglik_profile(X, init_params, lengths, Time, L, T, obs, bank, times=None, w
             LL, best = LL_d.cpu().numpy(), best_d.cpu().numpy()
     if info is not None:
         info.update(own, P=Pb, best=best)
+    return LL
+
+
+def _check_prior(log_prior, J, M, marginal):
+    """The log prior weights of the J x M cells as a (J * M,) float64 array, or None: (J, M), (J * M,) or, with M == 1, (J,)."""
+    if log_prior is None:
+        return np.full(J * M, -math.log(J * M)) if marginal else None
+    if not marginal:
+        raise ValueError('log_prior: only reduce="marginal" takes prior weights')
+    lp = np.ascontiguousarray(log_prior, dtype=np.float64)
+    if lp.size != J * M or lp.shape not in ((J, M), (J * M,)):
+        raise ValueError("log_prior must have shape (J, M) = (%d, %d) or (J * M,), got %r" % (J, M, lp.shape))
+    if np.isnan(lp).any() or (lp == np.inf).any():
+        raise ValueError("log_prior must not hold NaN or +inf (-inf excludes a cell)")
+    return lp.ravel()
+
+
+def loglik_nuisance(X, init_params, lengths, Time, L, T, obs, bank, mag="fixed", reduce="max", tf=1.0, log_prior=None, times=None,
+                    weights=None, tol=7, MAX=10000, pl_f32=False, predict=False, block=8192, device=0, keep_moments=False,
+                    info=None, normalize=False):
+    """The likelihood of one experiment with its nuisance parameters reduced on the device: the J responses of bank = (H (J, K),
+    k0[, table]) x the magnitude offset.  loglik_bank's staging and block loop -- one solve per block and curve,
+    loglik_irf_bank_device for the J responses -- and, while the block's moments are resident, ONE nuisance_reduce_device over
+    its cells: only LL, best, best_mag and status come down.
+
+    mag: "fixed" (the offset of X[:, 12] as it is), "profile" (per response the likelihood-maximising common offset of the
+    curves, mag_profile's) or a sequence of M <= 64 offsets (the grid of mag_grid); cell j * M + m is response j at offset m.
+    reduce: "max", the profile -- LL[s] = the greatest cell -- or "marginal", LL[s] = tf * log sum_i exp(v_i / tf + log_prior_i),
+    the log of the marginal of the tempered joint posterior over the cells.  log_prior (J, M) or (J * M,): the log prior weight
+    of each cell, -inf excludes one; None is the uniform prior -ln(J M) per cell; marginal only.  weights: the curves' wsum is
+    the math.fsum of each curve's weights, else the number of its observations.  Every other argument, the blocking and the
+    refusals are loglik_bank's.  mag="fixed", reduce="max" is loglik_profile, bit for bit.
+
+    Returns LL (S,).  info receives best (S,) int32, the first cell that attains the maximum (-1, with LL = -inf, where every
+    cell is -inf or NaN), best_mag (S,), the offset at that cell, status (C, S), ncol_out, cells = (J, M) and, with
+    keep_moments=True only, sse and esum (J, C, S).
+
+    functools.partial(loglik_nuisance, init_params=..., ..., bank=...) is a valid `loglik` for refine.run and mcmc.run WITHOUT
+    early_reject: the early stop lives in the fused steppers (trpl_loglik_cut*), which compare the bare curve and never see a
+    convolved one.  A marginal is formed at ONE tf: it is a valid `loglik` for refine.run and mcmc.run at that tf, and NOT for
+    mcmc.run_tempered, whose rungs differ in tf (the maximum is valid there)."""
+    if normalize:
+        raise ValueError(_NO_NORMALIZE)
+    if reduce not in ("max", "marginal"):
+        raise ValueError('reduce must be "max" or "marginal", got %r' % (reduce,))
+    marginal = reduce == "marginal"
+    from . import device as tdev
+    _, off = tdev.nuisance_flags(mag, marginal)
+    M = 1 if off is None else len(off)
+    if not 1 <= M <= _abi.NUISANCE_MAX_OFFSETS:
+        raise ValueError("mag: a grid holds 1 .. %d offsets, got %d" % (_abi.NUISANCE_MAX_OFFSETS, M))
+    if off is not None and not np.all(np.isfinite(off)):
+        raise ValueError("mag: every offset must be finite")
+    tf = float(tf)
+    if marginal and not (tf > 0.0 and math.isfinite(tf)):
+        raise ValueError("tf must be finite and > 0")
+    H, k0 = _check_bank(bank)
+    X, ini, lengths, staged, ncol_out = _stage(X, init_params, lengths, Time, L, T, obs, k0, times, weights, block)
+    S, Cn, L, T, block, J = X.shape[0], ini.shape[0], int(L), int(T), int(block), H.shape[0]
+    for c, kw in enumerate(staged):
+        if len(kw["obs"]) < 1:
+            raise ValueError("curve %d: a bank needs at least one observation per curve" % c)
+    lp = _check_prior(log_prior, J, M, marginal)
+    wsum = np.array([float(len(kw["obs"])) if weights is None else math.fsum(kw["wts"]) for kw in staged])
+    LL = np.full(S, -np.inf)
+    best = np.full(S, -1, dtype=np.int32)
+    best_mag = np.full(S, np.nan)
+    status = np.zeros((Cn, S), dtype=np.int32)
+    if info is not None:
+        info.update(best=best, best_mag=best_mag, status=status, ncol_out=ncol_out, cells=(J, M))
+        if keep_moments:
+            info.update(sse=np.zeros((J, Cn, S)), esum=np.zeros((J, Cn, S)))
+    if S == 0:
+        return LL
+
+    import torch
+
+    dev = torch.device("cuda", device)
+    tdt = torch.float32 if pl_f32 else torch.float64
+    with torch.cuda.device(dev):
+        def to_dev(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        ini_d, H_d = to_dev(ini), to_dev(H)
+        lp_d = None if lp is None else to_dev(lp)
+        staged = [{k: to_dev(v) for k, v in kw.items()} for kw in staged]
+        size = min(block, S)
+        pl_d = torch.empty((size, T + 1), dtype=tdt, device=dev)
+        LL_d = torch.empty(size, dtype=torch.float64, device=dev)
+        best_d = torch.empty(size, dtype=torch.int32, device=dev)
+        bm_d = torch.empty(size, dtype=torch.float64, device=dev)
+        for blk in range(0, S, block):
+            n = min(block, S - blk)
+            X_d = to_dev(X[blk:blk + n])
+            mat_d, mag_d = X_d[:, :12].contiguous(), X_d[:, 12].contiguous()
+            sse_d = torch.zeros((Cn, J, n), dtype=torch.float64, device=dev)
+            es_d = torch.zeros((Cn, J, n), dtype=torch.float64, device=dev)
+            st_d = torch.zeros((Cn, n), dtype=torch.int32, device=dev)
+            for c in range(Cn):
+                tdev.solve_pl_device(mat_d, lengths[c], Time, L, T, ini_d[c].contiguous(), pl_d[:n], status=st_d[c], tol=tol,
+                                     MAX=MAX, flags=_abi.FLAG_PREDICT if predict else 0)
+                tdev.loglik_irf_bank_device(pl_d[:n], H_d, k0, mag=mag_d, sse=sse_d[c], esum=es_d[c], status=st_d[c], **staged[c])
+            tdev.nuisance_reduce_device(sse_d, es_d, wsum, LL_d[:n], best=best_d[:n], best_mag=bm_d[:n], mag=mag, marginal=marginal,
+                                        tf=tf, log_prior=lp_d)
+            LL[blk:blk + n] = LL_d[:n].cpu().numpy()
+            best[blk:blk + n] = best_d[:n].cpu().numpy()
+            best_mag[blk:blk + n] = bm_d[:n].cpu().numpy()
+            status[:, blk:blk + n] = st_d.cpu().numpy()
+            if keep_moments and info is not None:
+                info["sse"][:, :, blk:blk + n] = sse_d.cpu().numpy().transpose(1, 0, 2)
+                info["esum"][:, :, blk:blk + n] = es_d.cpu().numpy().transpose(1, 0, 2)
     return LL

@@ -1136,8 +1136,9 @@ int trpl_convolve_irf(const void *pl, int32_t elem_bytes, int64_t rows, int64_t 
  * form is PLAIN HOST CODE (no device, like trpl_mag_profile); the _dev kernel (one thread per sample) equals it bit for bit.
  * Refused: J outside [1, TRPL_IRF_BANK_MAX_RESPONSES]; S < 0; with S > 0 a NULL Pbank, best or P.  S == 0 is TRPL_OK.
  *
- * Out of scope: a marginal (log-sum-exp) over the bank; composition with trpl_mag_grid / trpl_mag_profile (esum is returned so
- * that it can follow); gpu_info["irf_bank"] inside simulate / bayes; multi-device forms; a bank inside the fused steppers.
+ * What follows the moments -- the marginal (log-sum-exp) over the bank, the composition with the magnitude offset, and
+ * gpu_info["irf_bank"] inside simulate / bayes -- is trpl_nuisance_reduce*, below.
+ * Out of scope: multi-device forms; a bank inside the fused steppers; a response chosen per curve.
  * Python: trpl_amd.irf.gaussian_bank / shift_bank / loglik_bank / loglik_profile, trpl_amd.device.loglik_irf_bank_device /
  * irf_bank_profile_device.
  * ------------------------------------------------------------------------------------- */
@@ -1157,6 +1158,88 @@ int trpl_loglik_irf_bank(const void *pl, int32_t elem_bytes, int64_t rows, int64
 int trpl_irf_bank_profile_dev(const double *Pbank /*[J][S]*/, int32_t J, int64_t S, int32_t *best /*[S]*/, double *P /*[S]*/,
                               void *stream);
 int trpl_irf_bank_profile(const double *Pbank, int32_t J, int64_t S, int32_t *best, double *P);
+
+/* ---------------------------------------------------------------------------------------
+ * trpl_nuisance_reduce* -- one reduction over the nuisance grid of an experiment: the J responses of a bank x M magnitude
+ * offsets, from the moments trpl_loglik_irf_bank* left in HBM.  sse, esum [C][J][S] fp64 (curve-major: curve c holds the [J][S]
+ * block one trpl_loglik_irf_bank_dev wrote for it); wsum [C] HOST fp64, the quadratic coefficient of curve c: (double)n_obs[c], or
+ * the sum of the curve's weights, as trpl_mag_*_w take it; offsets [M] HOST fp64; P [S] fp64, WRITTEN, not accumulated; best [S]
+ * int32 (nullable), the first cell i = j M + m that attains the maximum; best_mag [S] fp64 (nullable), the offset at that cell.
+ * (csrc/nuisance.hip)
+ *
+ * The value of a cell, v[j][m].  Curves in ascending c, every operation rounded once, no fused multiply-add.  flags holds one
+ * mag mode:
+ *   TRPL_NUISANCE_MAG_FIXED    M = 1, no offsets, esum nullable:  v[j] = +0.0 - (((+0.0 + sse_0) + sse_1) + ...).  That is
+ *       -(sum) in every bit but the sign of a zero total, which is +0.0: row j of the P (J, S) that P -= sse_c from zeros gives
+ *       (irf.loglik_bank), bit for bit.  FIXED with the maximum is trpl_irf_bank_profile on that P, in P and best; best_mag = +0.0.
+ *   TRPL_NUISANCE_MAG_GRID     1 <= M <= TRPL_NUISANCE_MAX_OFFSETS:  v[j][m] = +0.0 - sum_c t_c from +0.0, with d = offsets[m] and
+ *       t_c = (sse_c + (2.0 d) esum_c) + wsum_c (d d), clamped from below at 0.0; t_c = +inf where sse_c is +inf or NaN, esum_c is
+ *       not finite, or the expression is NaN (trpl_mag_grid_w's term and rule: such a cell is -inf).  With J = 1, v[0][m] is row
+ *       m of trpl_mag_grid_w on a P started from +0.0, bit for bit.
+ *   TRPL_NUISANCE_MAG_PROFILE  M = 1, no offsets:  per response j, E = sum_c esum_c and N = sum_c wsum_c from +0.0, d_j =
+ *       (0.0 - E) / N, v[j] = +0.0 - sum_c t_c(d_j) as above; the offset reported is d_j where every sse_c < +inf and E is
+ *       finite, else NaN.  Where N == 0 and every sse_c < +inf there is nothing to fit: v[j] = +0.0, d_j = NaN.  That is best and
+ *       P of trpl_mag_profile_w (flags 0, P started from +0.0) on the slice sse[:][j][:], esum[:][j][:], bit for bit.
+ *       best_mag = d_j of the winning response.
+ *
+ * The reduction, over the cells in ascending i = j M + m:
+ *   the maximum (default)    P[s] = the greatest v, best = the first cell that attains it.  A NaN is never the greatest; where every
+ *       cell is -inf or NaN: P = -inf, best = -1, best_mag = NaN (trpl_irf_bank_profile's rules).
+ *   TRPL_NUISANCE_MARGINAL   a_i = v_i / tf + logw_i (one division, one addition; logw NULL: + 0.0).  Pass 1: mx = the greatest a
+ *       and best, a NaN a counting as -inf.  Pass 2: sum = sum_i exp(a_i - mx) from +0.0 in ascending i, a NaN term skipped.
+ *       P = tf * (mx + log(sum)).  Everything -inf or NaN: as above.  exp(P / tf) = sum_i w_i exp(v_i / tf), w_i = exp(logw_i): the
+ *       log of the marginal of the tempered joint posterior over the cells, at ONE tf.  logw [J M] fp64: -inf excludes a cell.
+ *
+ * Host and device.  trpl_nuisance_reduce is PLAIN HOST CODE (no device, like trpl_mag_profile), every pointer a host pointer.
+ * trpl_nuisance_reduce_dev takes device pointers for sse, esum, P, best, best_mag and logw, host pointers for wsum and offsets
+ * (they travel as kernel arguments), allocates nothing and never synchronises; one thread per sample, no atomics, LDS or
+ * scratch.  logw is a device array there because J M doubles (up to 128 KiB) do not fit kernel arguments; its values are the
+ * caller's to vouch for, as the taps of trpl_loglik_irf_bank_dev are.  With the maximum the kernel equals the host form bit for bit
+ * in P, best and best_mag.  With the marginal best is equal (a_i is IEEE division and addition on both sides) and P obeys a bound,
+ * because exp and log are the device library's there and libm's here.
+ *
+ * The bound of the marginal.  Let A_i = v_i / tf + logw_i and R = tf (MX + ln sum_i exp(A_i - MX)) in exact arithmetic from the fp64
+ * cell values, n = J M, u = 2^-53, B = the greatest |v_i| / tf + |logw_i| over the cells with a finite a_i.
+ *   a_i carries two roundings: |a_i - A_i| <= u |v_i| / tf + u |a_i| <= (2 + u) u B.  ln-sum-exp moves by at most the greatest
+ *       change of an argument, so this costs at most 3 u B in R / tf.
+ *   t_i = a_i - mx carries one rounding, u |t_i|, and a term contributes only for |t_i| <= 745; relative to the sum, which is at
+ *       least its greatest term 1, the terms exp(t_i) |t_i| <= 1 / e each: at most (n - 1) u / e.
+ *   exp and log are 1 ulp each in the ROCm device library's table of double-precision functions: a relative 2 u per term of the
+ *       sum, and 2 u ln(sum) <= 2 u ln(n) < 20 u for n <= 16384.
+ *   the n - 1 additions of terms in (0, 1]: a relative (n - 1) u of the sum; terms below exp(-745) that vanish: below u in all.
+ *   one addition and one product: 2 u |R|.
+ * In sum |P - R| <= TRPL_NUISANCE_BOUND: u (tf (3 B + 2 n + 24) + 3 |R|), the constants 1 + 1 / e, 22 and 2 rounded up to cover the
+ * second-order terms.  The host form obeys the same bound (libm's exp and log are below 1 ulp).
+ *
+ * Refused with TRPL_ERR_ARG before a device is touched, the message naming the argument, in this order: S < 0; C outside
+ * [1, TRPL_MAG_MAX_CURVES]; J outside [1, TRPL_IRF_BANK_MAX_RESPONSES]; an unknown mag mode or flag bit; M outside
+ * [1, TRPL_NUISANCE_MAX_OFFSETS] in grid mode, M != 1 otherwise; offsets NULL in grid mode, non-NULL otherwise; esum NULL unless
+ * FIXED; a wsum that is not finite and >= 0; an offset that is not finite; with the marginal, tf not finite or not > 0, and (host
+ * form) a logw entry that is NaN or +inf; without the marginal, logw non-NULL; with S > 0 a NULL sse, wsum or P.  S == 0 is
+ * TRPL_OK without a launch.
+ *
+ * Out of scope: multi-device forms; an analytic marginal over the offset; per-cell posterior shares as an output; a marginal
+ * across the rungs of a tempered run (the rungs differ in tf).
+ * Python: trpl_amd.device.nuisance_reduce_device, trpl_amd.irf.loglik_nuisance, gpu_info["irf_bank"] of driver.simulate / bayes.
+ * ------------------------------------------------------------------------------------- */
+#define TRPL_NUISANCE_MAX_OFFSETS 64
+#define TRPL_NUISANCE_MAG_FIXED 0x0u
+#define TRPL_NUISANCE_MAG_GRID 0x1u
+#define TRPL_NUISANCE_MAG_PROFILE 0x2u
+#define TRPL_NUISANCE_MAG_MASK 0x3u
+#define TRPL_NUISANCE_MARGINAL 0x10u
+/* the bound above: tf, B = max_i (|v_i| / tf + |logw_i|), n = J M, R the exact value */
+#define TRPL_NUISANCE_BOUND(tf, B, n, R) \
+    (1.1102230246251565e-16 * ((tf) * (3.0 * (B) + 2.0 * (double)(n) + 24.0) + 3.0 * ((R) < 0 ? -(R) : (R))))
+int trpl_nuisance_max_offsets(void);
+double trpl_nuisance_bound(double tf, double B, int32_t n, double R);   /* TRPL_NUISANCE_BOUND, for callers that cannot read a macro */
+int trpl_nuisance_reduce_dev(const double *sse /*[C][J][S]*/, const double *esum /*[C][J][S]*/, const double *wsum /*HOST [C]*/,
+                             int64_t S, int32_t C, int32_t J, const double *offsets /*HOST [M]*/, int32_t M,
+                             const double *logw /*device [J M], nullable*/, double tf, uint32_t flags, double *P /*[S]*/,
+                             int32_t *best /*[S], nullable*/, double *best_mag /*[S], nullable*/, void *stream);
+int trpl_nuisance_reduce(const double *sse, const double *esum, const double *wsum, int64_t S, int32_t C, int32_t J,
+                         const double *offsets, int32_t M, const double *logw /*HOST [J M], nullable*/, double tf, uint32_t flags,
+                         double *P, int32_t *best, double *best_mag);
 
 /* ---------------------------------------------------------------------------------------
  * trpl_corner* -- the corner: every posterior marginal of a finished run in one device call.  What plot() of

@@ -1,6 +1,6 @@
 """The instrument-response convolution (trpl_convolve_irf_dev) against its two floors, in one process on one device.
 
-    python tools/bench_irf.py [--rows 65536] [--ncol 8001] [--taps 5,33,257,1024] [--route] [--out profiles/irf_bench.jsonl]
+    python tools/bench_irf.py [--rows 65536] [--ncol 8001] [--taps 5,33,257,1024] [--route] [--bank] [--nuisance] [--out profiles/irf_bench.jsonl]
 
 kernel:  one trpl_convolve_irf_dev over a [rows][ncol] PL matrix (ld = ncol: odd, rows only element-aligned) in fp64 and in fp32,
          per tap count K with k0 = K // 2: 3 warm-ups, then the median of 10 calls timed one by one with device events.  Beside
@@ -15,6 +15,12 @@ kernel:  one trpl_convolve_irf_dev over a [rows][ncol] PL matrix (ld = ncol: odd
          timed in this process as above.  Floors: the fp64 floor of the convolution at the observed columns, two instructions per
          term, times J; the HBM floor of ONE read of the block.  With --route also the resident route solve -> bank -> profile at
          the default bench shape with 33 taps and J = 16.  Lines go to profiles/irf_bank_bench.jsonl unless --out is given.
+--nuisance: trpl_nuisance_reduce_dev over moments [3][J][rows] per J of --responses (default 8,32,256): FIXED + max, PROFILE + max and
+         GRID (M = 16) + marginal, timed as above.  Floor: ONE read of the moments the shape needs (sse alone under FIXED) at the
+         8 TB/s peak.  Beside FIXED + max the tail of irf.loglik_profile that it replaces, in wall-clock seconds in this process:
+         the download of P (J, rows), its upload and trpl_irf_bank_profile_dev.  With --route also the resident route solve -> bank ->
+         reduce at the default bench shape with J = 16: the reduction's share beside the solve.  Lines go to
+         profiles/nuisance_bench.jsonl unless --out is given.
 Appends one JSON line per measurement to --out."""
 import argparse
 import json
@@ -218,6 +224,101 @@ def bench_bank_route(a, out):
          "bank_share_of_route": med["bank"] / total, "reps": a.route_reps})
 
 
+def bench_nuisance(a, out):
+    import time
+    dev = torch.device("cuda", 0)
+    S, C, M = a.rows, 3, 16
+    wsum = [float(a.ncol)] * C
+    offsets = np.linspace(-0.3, 0.3, M)
+    g = torch.Generator(device=dev)
+    g.manual_seed(2)
+    P = torch.empty(S, dtype=torch.float64, device=dev)
+    best = torch.empty(S, dtype=torch.int32, device=dev)
+    bmag = torch.empty(S, dtype=torch.float64, device=dev)
+    for J in a.responses:
+        mean = torch.empty((C, J, S), dtype=torch.float64, device=dev).normal_(0.0, 0.1, generator=g)
+        esum = mean * a.ncol
+        sse = (mean * mean + 0.01) * a.ncol                           # moments of n_obs errors of about 0.1
+        del mean
+        lp = torch.full((J * M,), -float(np.log(J * M)), dtype=torch.float64, device=dev)
+        shapes = (("fixed_max", dict(mag="fixed"), 1), ("profile_max", dict(mag="profile"), 2),
+                  ("grid16_marginal", dict(mag=offsets, marginal=True, tf=10.0, log_prior=lp), 2))
+        for name, kw, arrays in shapes:
+            ms = timed(lambda: tdev.nuisance_reduce_device(sse, esum, wsum, P, best=best, best_mag=bmag, **kw))
+            floor = arrays * C * J * S * 8 / PEAK_BPS * 1e3
+            out({"bench": "nuisance_reduce", "device": torch.cuda.get_device_name(0), "shape": name, "S": S, "C": C, "J": J,
+                 "M": M if name.startswith("grid") else 1, "ms": ms[0], "ms_min": ms[1], "ms_max": ms[2], "hbm_floor_ms": floor,
+                 "ms_over_floor": ms[0] / floor})
+        # the tail of irf.loglik_profile: P (J, S) comes down, is handed to the profile as a host array, goes up and is reduced
+        Pb = torch.zeros((J, S), dtype=torch.float64, device=dev)
+        for c in range(C):
+            Pb -= sse[c]
+        secs = []
+        for _ in range(13):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            host = Pb.cpu().numpy()
+            t1 = time.perf_counter()
+            up = torch.from_numpy(host).to(dev)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            tdev.irf_bank_profile_device(up, best, P)
+            torch.cuda.synchronize()
+            secs.append((t1 - t0, t2 - t1, time.perf_counter() - t2))
+        med = [float(np.median([r[k] for r in secs[3:]])) for k in range(3)]
+        out({"bench": "irf_profile_tail", "device": torch.cuda.get_device_name(0), "S": S, "J": J, "download_ms": med[0] * 1e3,
+             "upload_ms": med[1] * 1e3, "profile_ms": med[2] * 1e3, "tail_ms": sum(med) * 1e3})
+        del sse, esum, Pb
+
+
+def bench_nuisance_route(a, out):
+    dev = torch.device("cuda", 0)
+    w = trpl_amd.workloads
+    L, T, S = 128, 8000, a.samples
+    Time = T * 0.025
+    dt = Time / T
+    ini, lens = w.power_scan(L)
+    X = w.samples(S)
+    H, k0, _ = trpl_amd.irf.gaussian_bank([0.15, 0.188], np.linspace(-2 * dt, 2 * dt, 8), dt, rel_cut=1e-6)
+    J = H.shape[0]
+    X_d = torch.from_numpy(X).to(dev)
+    mat, mag = X_d[:, :12].contiguous(), X_d[:, 12].contiguous()
+    ini_d, H_d = torch.from_numpy(ini).to(dev), torch.from_numpy(H).to(dev)
+    pl = torch.empty((S, T + 1), dtype=torch.float64, device=dev)
+    st = torch.zeros(S, dtype=torch.int32, device=dev)
+    obs = torch.zeros(T + 1 - k0, dtype=torch.float64, device=dev)
+    sse = torch.empty((3, J, S), dtype=torch.float64, device=dev)
+    esum = torch.empty((3, J, S), dtype=torch.float64, device=dev)
+    LL = torch.empty(S, dtype=torch.float64, device=dev)
+    runs = []
+    for rep in range(1 + a.route_reps):
+        t = {"solve": 0.0, "bank": 0.0}
+        for c in range(3):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record()
+            tdev.solve_pl_device(mat, lens[c], Time, L, T, ini_d[c].contiguous(), pl, status=st)
+            ev[1].record()
+            tdev.loglik_irf_bank_device(pl, H_d, k0, obs, mag, sse[c], esum=esum[c], status=st)
+            ev[2].record()
+            torch.cuda.synchronize()
+            t["solve"] += ev[0].elapsed_time(ev[1]) / 1e3
+            t["bank"] += ev[1].elapsed_time(ev[2]) / 1e3
+        for name, kw in (("reduce_fixed_max", dict()), ("reduce_profile_max", dict(mag="profile")),
+                         ("reduce_grid16_marginal", dict(mag=np.linspace(-0.3, 0.3, 16), marginal=True, tf=10.0))):
+            e0, e1 = events()
+            e0.record()
+            tdev.nuisance_reduce_device(sse, esum, [float(T + 1 - k0)] * 3, LL, **kw)
+            e1.record()
+            torch.cuda.synchronize()
+            t[name] = e0.elapsed_time(e1) / 1e3
+        if rep:
+            runs.append(t)
+    med = {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
+    out({"bench": "nuisance_route", "device": torch.cuda.get_device_name(0), "workload": "Power_scan", "curves": 3, "L": L, "T": T,
+         "samples": S, "K": int(H.shape[1]), "k0": int(k0), "J": int(J), "seconds": med,
+         "reduce_over_solve": {k: med[k] / med["solve"] for k in med if k.startswith("reduce")}, "reps": a.route_reps})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=65536)
@@ -228,11 +329,14 @@ def main():
     ap.add_argument("--route-reps", type=int, default=3)
     ap.add_argument("--no-kernel", action="store_true")
     ap.add_argument("--bank", action="store_true")
-    ap.add_argument("--responses", type=lambda s: [int(v) for v in s.split(",")], default=[1, 8, 32])
+    ap.add_argument("--nuisance", action="store_true")
+    ap.add_argument("--responses", type=lambda s: [int(v) for v in s.split(",")], default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.responses is None:
+        a.responses = [8, 32, 256] if a.nuisance else [1, 8, 32]
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "irf_bank_bench.jsonl" if a.bank else "irf_bench.jsonl")
+        a.out = os.path.join(ROOT, "profiles", "nuisance_bench.jsonl" if a.nuisance else "irf_bank_bench.jsonl" if a.bank else "irf_bench.jsonl")
     if a.bank and a.taps == [5, 33, 257, 1024]:
         a.taps = [5, 33, 257]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -242,6 +346,12 @@ def main():
             f.write(json.dumps(line) + "\n")
         print(json.dumps(line), flush=True)
 
+    if a.nuisance:
+        if not a.no_kernel:
+            bench_nuisance(a, out)
+        if a.route:
+            bench_nuisance_route(a, out)
+        return 0
     if a.bank:
         if not a.no_kernel:
             bench_bank(a, out)

@@ -1,7 +1,7 @@
 """End-to-end on one GPU, everything device-resident: draw the parameter box (trpl_sample_box_dev), solve
 and score every sample against observations synthesised at the reference's marked point
 (Visualization/config.txt:57-68) with the fused kernel (trpl_loglik_dev), then the posterior core
-(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--subspace [--pairs n] [--ncr n] [--adapt-cr]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject [sample]] [--tempered K [--tf-hot x] [--evidence]]] [--irf FWHM_NS [--irf-shifts LO:HI:N] [--irf-widths LO:HI:N]]
+(weights, moments, marginals).  Prints one JSON line.  Usage: python tools/e2e_inference.py [S] [T] [c] [--find-tf] [--predictive [--quantiles]] [--corner] [--refine [--rounds N] [--target-ess N] [--oriented [--shrink x]]] [--mcmc [--chains C] [--sweeps N] [--rw x] [--stretch [a]] [--subspace [--pairs n] [--ncr n] [--adapt-cr]] [--prior NAME=CENTER:WIDTH ...] [--fold] [--early-reject [sample]] [--tempered K [--tf-hot x] [--evidence]]] [--irf FWHM_NS [--irf-shifts LO:HI:N] [--irf-widths LO:HI:N] [--irf-reduce max|marginal] [--irf-mag fixed|profile]]
 --find-tf adds, between likelihood and posterior, the temperature of largest uncertainty of every free parameter
 (posterior.calc_max_uncertainty, utils.py:128-133, on the device temperature scan) as "max_uncertainty" in the output;
 without it the output is unchanged.
@@ -74,6 +74,10 @@ free parameter beside those of the run without the response, which are printed -
 response of the bank that is NOT its centre (three quarters along each axis), every sample is scored by the profile and, beside it,
 by irf.loglik with the response fixed at the bank's centre.  "irf_bank" holds the posterior-weighted distribution of the best
 response, the effective sample sizes and the intervals of both runs, which are printed -- recorded, not gated.
+--irf-reduce max|marginal and --irf-mag fixed|profile (beside --irf-shifts / --irf-widths; defaults max and fixed, the run above
+unchanged) score every sample by irf.loglik_nuisance instead: the maximum or, at the run's tf and under the
+uniform prior, the marginal over the bank, with the magnitude offset as it is or profiled per response.  The same lines are printed
+for the chosen reduction; "irf_bank" also holds "reduce", "mag" and the posterior-weighted mean of the best offset.
 """
 import json
 import sys
@@ -159,6 +163,16 @@ for flag in ("--irf-shifts", "--irf-widths"):
         grid_ = [float(lo_) + (float(hi_) - float(lo_)) * i / max(int(n_) - 1, 1) for i in range(int(n_))]
         IRF_SHIFTS, IRF_WIDTHS = (grid_, IRF_WIDTHS) if flag == "--irf-shifts" else (IRF_SHIFTS, grid_)
         del sys.argv[k:k + 2]
+IRF_REDUCE, IRF_MAG = "max", "fixed"
+for flag, allowed in (("--irf-reduce", ("max", "marginal")), ("--irf-mag", ("fixed", "profile"))):
+    if flag in sys.argv:
+        k = sys.argv.index(flag)
+        if sys.argv[k + 1] not in allowed:
+            sys.exit("%s takes %s" % (flag, " or ".join(allowed)))
+        IRF_REDUCE, IRF_MAG = (sys.argv[k + 1], IRF_MAG) if flag == "--irf-reduce" else (IRF_REDUCE, sys.argv[k + 1])
+        del sys.argv[k:k + 2]
+if (IRF_REDUCE, IRF_MAG) != ("max", "fixed") and IRF_SHIFTS is None and IRF_WIDTHS is None:
+    sys.exit("--irf-reduce / --irf-mag need --irf-shifts or --irf-widths")
 if (IRF_SHIFTS is not None or IRF_WIDTHS is not None) and IRF_FWHM is None:
     sys.exit("--irf-shifts / --irf-widths need --irf FWHM_NS")
 PRIORS = {}
@@ -528,9 +542,12 @@ if IRF_FWHM is not None and (IRF_SHIFTS is not None or IRF_WIDTHS is not None):
     obs_b = [np.log10(seen_b[c]) for c in range(C)]
     binfo = {}
     Xh = X.cpu().numpy()
-    LL_prof = tirf.loglik_profile(Xh, ini, lens, T * dt, L, T, obs_b, bank, info=binfo)
-    LL_fix = tirf.loglik(Xh, ini, lens, T * dt, L, T, obs_b, (Hb[centre], kb))
     tf_b = C * (T + 1 - kb) * c_val
+    if (IRF_REDUCE, IRF_MAG) == ("max", "fixed"):
+        LL_prof = tirf.loglik_profile(Xh, ini, lens, T * dt, L, T, obs_b, bank, info=binfo)
+    else:
+        LL_prof = tirf.loglik_nuisance(Xh, ini, lens, T * dt, L, T, obs_b, bank, mag=IRF_MAG, reduce=IRF_REDUCE, tf=tf_b, info=binfo)
+    LL_fix = tirf.loglik(Xh, ini, lens, T * dt, L, T, obs_b, (Hb[centre], kb))
     W_prof, W_fix = posterior.weights(LL_prof, tf_b), posterior.weights(LL_fix, tf_b)
     ok = binfo["best"] >= 0
     share = np.bincount(binfo["best"][ok], weights=np.nan_to_num(W_prof[ok]), minlength=J)
@@ -543,6 +560,11 @@ if IRF_FWHM is not None and (IRF_SHIFTS is not None or IRF_WIDTHS is not None):
                        "effective_sample_size_profile": ess_prof, "effective_sample_size_fixed": ess_fix,
                        "quantiles": {n: {"truth": float(tr), "profile": [float(v) for v in q_prof[:, k]], "fixed": [float(v) for v in q_fix[:, k]]}
                                      for k, (n, tr) in enumerate(zip(names, truth))}}
+    out["irf_bank"].update(reduce=IRF_REDUCE, mag=IRF_MAG)
+    if "best_mag" in binfo:
+        out["irf_bank"]["best_mag_mean"] = float(np.nansum(np.nan_to_num(W_prof[ok]) * np.nan_to_num(binfo["best_mag"][ok])))
+        print("irf bank: reduce %s, mag %s at tf %g: posterior-weighted mean of the best offset %+.5f"
+              % (IRF_REDUCE, IRF_MAG, tf_b, out["irf_bank"]["best_mag_mean"]), file=sys.stderr)
     print("irf bank: %d responses of %d taps; the detector's is %d (fwhm %g ns, shift %g ns), the fixed run uses %d (fwhm %g ns, shift %g ns)"
           % ((J, Hb.shape[1], j_true) + tuple(table[j_true]) + (centre,) + tuple(table[centre])), file=sys.stderr)
     print("irf bank: effective sample size %.2f with the profile, %.2f with the fixed response, %.2f s"

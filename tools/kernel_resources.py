@@ -6,14 +6,15 @@
                                        weighted_pair weighted_predict_fast weighted_predict_strict weighted_predict_pair
                                        cut_fast cut_pair cut_predict_fast cut_predict_pair posterior posterior_scan predictive
                                        quantiles corner refine refine_oriented mcmc mcmc_hastings mcmc_subspace
-                                       mcmc_evidence cut_budget irf irf_bank]
+                                       mcmc_evidence cut_budget irf irf_bank nuisance]
 (cross-compiles, no GPU needed; a name is an object of the library without its stepper_ prefix: csrc/<name>.hip or
 csrc/stepper_<name>.hip where that file exists, otherwise a variant of csrc/stepper_variants.hpp -- [sink_][predict_]unit --
 which is stepper_[pair_]variant.hip with the switch of each of its words, as the Makefile compiles it; mcmc has the sampler's
 accept and levels kernels in all three forms, hastings_accept_kernel and hastings_levels_kernel among them, mcmc_hastings the
 stretch move and the prior term, mcmc_subspace the subspace proposal, mcmc_evidence the extrema and the sums of the log-evidence
 estimates, irf the instrument-response convolution, whose LDS is dynamic and not in the table: 32 (n + n / 8 + 1) bytes with n = 518 + K,
-irf_bank the likelihood against a bank of responses and the profile over it, all LDS static)"""
+irf_bank the likelihood against a bank of responses and the profile over it, all LDS static, nuisance the reduction over
+responses x magnitude offsets: three mag modes, each with the maximum and with the marginal)"""
 import os
 import re
 import subprocess
@@ -22,7 +23,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bayesian-inference-trpl_amd", "csrc")
 SWITCHES = ("moments", "weighted", "cut", "predict", "strict")              # -DTRPL_STEPPER_<WORD>=1 of a variant's words
-CONTRACT_OFF = ("posterior", "posterior_scan", "corner", "refine", "refine_oriented", "mcmc", "mcmc_hastings", "mcmc_subspace", "mcmc_evidence", "cut_budget", "irf", "irf_bank")                            # beside every stepper with the word "strict" (Makefile)
+CONTRACT_OFF = ("posterior", "posterior_scan", "corner", "refine", "refine_oriented", "mcmc", "mcmc_hastings", "mcmc_subspace", "mcmc_evidence", "cut_budget", "irf", "irf_bank", "nuisance")                            # beside every stepper with the word "strict" (Makefile)
 
 
 def unit(n):
