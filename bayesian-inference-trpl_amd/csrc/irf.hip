@@ -8,7 +8,8 @@
 // Tile structure.  A workgroup of kRows waves takes a tile of kRows rows x kTileCols output columns; wave w owns row w.
 //   stage    the wave copies the kTileCols + K - 1 input columns its tile reads, j0 + k0 - (K - 1) .. j0 + k0 + kTileCols - 1,
 //            into LDS as fp64, 64 consecutive columns per load (rows are only element-aligned: ld = T/plT + 1 is usually odd,
-//            so every lane loads one element).  A column outside [0, ncol - 1] is staged as 0.0 and never enters a stored sum:
+//            so every lane loads one element).  A column outside [0, ncol - 1] is staged as 0.0 (irf_common.hpp's clamp_col and
+//            staged_value, which irf_bank.hip stages with too: here the kRun loads go first, then their LDS writes) and never enters a stored sum:
 //            left of 0 the term is skipped by a test (tiles that touch column 0 run the EDGE instantiation of the tap loop),
 //            right of ncol - 1 only outputs j >= ncol - k0 would read it, and those are not stored.  Each PL element is
 //            fetched once per tile; the K - 1 columns two neighbouring tiles share come from L2 the second time.
@@ -26,6 +27,7 @@
 #include <stdint.h>
 
 #include "api_util.hpp"
+#include "irf_common.hpp"
 
 namespace trpl {
 namespace irf {
@@ -91,12 +93,12 @@ __global__ void __launch_bounds__(kThreads) convolve(const T *__restrict__ pl, i
 #pragma unroll
                 for (int u = 0; u < kRun; u++) {                          // every load is of a column of the row: no branch
                     const int64_t c = c_first + i0 + 64 * u;
-                    x[u] = prow[c < 0 ? 0 : c < ncol ? c : ncol - 1];
+                    x[u] = prow[clamp_col(c, ncol)];
                 }
 #pragma unroll
                 for (int u = 0; u < kRun; u++) {
                     const int64_t c = c_first + i0 + 64 * u;
-                    if (i0 + 64 * u < n_in) xs[phys(i0 + 64 * u + kRun)] = (c >= 0 && c < ncol) ? (double)x[u] : 0.0;
+                    if (i0 + 64 * u < n_in) xs[phys(i0 + 64 * u + kRun)] = staged_value<T>(x[u], c, ncol);
                 }
             }
             if (lane == 0) xs[phys(kRun - 1)] = 0.0;

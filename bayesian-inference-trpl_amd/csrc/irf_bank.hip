@@ -4,7 +4,8 @@
 //     cv[c] = sum over k = 0 .. K-1, ascending, of  H[j][k] * (double)pl[r][c + k0 - k]          (csrc/irf.hip's sum, same bits)
 // rounds it to the block's element type, takes log_pl of it (log_pl.hpp) and adds the squared error to sse[j][r] and the error to
 // esum[j][r] with pl_loglik_kernel's mapping (likelihood.hip): one 256-thread workgroup per row, thread t adds observations
-// t, t + 256, ... in ascending order, the xor butterfly inside each wave, then ((p0 + p1) + p2) + p3.  The results are the bits of
+// t, t + 256, ... in ascending order, the xor butterfly inside each wave, then the four wave sums in order.  The kernel shares
+// those expressions with pl_loglik_kernel (pl_score.hpp) and the staged column with irf.hip (irf_common.hpp).  The results are the bits of
 // trpl_convolve_irf_dev followed by trpl_loglik_moments_from_pl_dev (trpl_loglik_weighted_from_pl_dev with wts), per response;
 // the convolved block never exists.  Compiled with -ffp-contract=off like both of those units: one rounded product and one
 // rounded addition per term.
@@ -26,7 +27,9 @@
 #include <stdint.h>
 
 #include "api_util.hpp"
+#include "irf_common.hpp"
 #include "log_pl.hpp"
+#include "pl_score.hpp"
 
 namespace trpl {
 namespace irf_bank {
@@ -46,11 +49,7 @@ template <typename T>
 struct MemX {                                          // a column outside the row is never used: any element of the row does
     const T *row;
     int64_t c, ncol;
-    __device__ __forceinline__ double operator()(int d) const
-    {
-        const int64_t q = c - d;
-        return (double)row[q < 0 ? 0 : q < ncol ? q : ncol - 1];
-    }
+    __device__ __forceinline__ double operator()(int d) const { return (double)row[clamp_col(c - d, ncol)]; }
 };
 
 // NC convolved columns, c - k0 (v = 0) and with NC = 2 the one before it (v = 1), for W responses whose taps start at Hb, K apart:
@@ -86,11 +85,7 @@ __device__ __forceinline__ void conv(const X &x, const double *__restrict__ Hb, 
 template <typename T>
 __device__ __forceinline__ void stage(double *xs, const T *__restrict__ prow, int64_t cb, int n_in, int64_t ncol)
 {
-    for (int s = threadIdx.x; s < n_in; s += kThreads) {
-        const int64_t c = cb + s;
-        const T v = prow[c < 0 ? 0 : c < ncol ? c : ncol - 1];
-        xs[s] = (c >= 0 && c < ncol) ? (double)v : 0.0;
-    }
+    for (int s = threadIdx.x; s < n_in; s += kThreads) xs[s] = staged_col<T>(prow, cb + s, ncol);
 }
 
 // the arguments of the kernel but pl, H, sse and esum, which travel as __restrict__ parameters of their own: the taps are
@@ -173,35 +168,25 @@ __device__ __forceinline__ void pass(const Args &a, const T *__restrict__ prow, 
 #pragma unroll
                 for (int j = 0; j < W; j++) {
                     const T v = (T)acc[0][j];                            // what trpl_convolve_irf_dev stores
-                    double y;
-                    if constexpr (OFFGRID) {                             // pl_loglik_kernel's expressions from here on
+                    double y = log_pl<T>(v, v, false, f32);
+                    if constexpr (OFFGRID) {
                         const T vl = (T)acc[1][j];
-                        const double lg_hi = log_pl<T>(v, v, false, f32), lg_lo = log_pl<T>(vl, vl, false, f32);
-                        const double dy = f32 ? (double)((float)lg_hi - (float)lg_lo) : lg_hi - lg_lo;
-                        y = (dy / oh) * odx + lg_lo;
-                    } else {
-                        y = log_pl<T>(v, v, false, f32);
+                        y = interp_log_pl(y, log_pl<T>(vl, vl, false, f32), oh, odx, f32);
                     }
-                    double err = y + m;
-                    err -= ob;
-                    if constexpr (WT) { s2[j] += (err * err) * w; s1[j] += err * w; }
-                    else { s2[j] += err * err; s1[j] += err; }
+                    score_add<WT>(y, m, ob, w, s2[j], s1[j]);
                 }
             }
         }
 #pragma unroll
     for (int j = 0; j < W; j++) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s2[j] += __shfl_xor(s2[j], off, 64);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s1[j] += __shfl_xor(s1[j], off, 64);
+        wave_add(s2[j]);
+        wave_add(s1[j]);
         if (lane == 0) { part[0][j][wave] = s2[j]; part[1][j][wave] = s1[j]; }
     }
     __syncthreads();
     if (tid < W) {
-        const double *p = part[0][tid], *q = part[1][tid];
-        double r2 = ((p[0] + p[1]) + p[2]) + p[3], r1 = ((q[0] + q[1]) + q[2]) + q[3];
-        if (flagged || !(r2 == r2)) { r2 = INFINITY; r1 = NAN; }
+        double r2 = row_sum(part[0][tid]), r1 = row_sum(part[1][tid]);
+        row_flag(flagged, r2, r1);
         sse[(int64_t)tid * a.rows + row] = r2;
         if (esum) esum[(int64_t)tid * a.rows + row] = r1;
     }
@@ -386,9 +371,7 @@ int trpl_irf_bank_profile_dev(const double *Pbank, int32_t J, int64_t S, int32_t
 {
     if (int rc = check_profile(Pbank, J, S, best, P)) return rc;
     if (S == 0) return TRPL_OK;
-    int64_t blocks = (S + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(irf_bank::profile, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, Pbank, (int)J, S, best, P);
+    hipLaunchKernelGGL(irf_bank::profile, dim3(per_sample_blocks(S)), dim3(256), 0, (hipStream_t)stream, Pbank, (int)J, S, best, P);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return api_fail(TRPL_ERR_HIP, "irf_bank_profile launch: %s", hipGetErrorString(e));
     return TRPL_OK;

@@ -5,6 +5,8 @@
 #include <math.h>
 
 #include "log_pl.hpp"
+#include "mag_moments.hpp"
+#include "pl_score.hpp"
 #include "trpl_common.hpp"
 
 namespace trpl {
@@ -208,7 +210,8 @@ hipError_t launch_reduce_curves(double *P, const double *sse, int64_t S, int C, 
 // otherwise leave most of the chip idle behind the fp64 log10), threads stride over the observations,
 // fixed-order block reduction at the end: the sum is associated differently from probs.prob's serial loop (~1e-16);
 // trpl_log10_clamp + trpl_sse_accumulate remain the bit-exact pair.  HBM-bound: n_obs (or 2 n_obs,
-// off-grid) PL elements per row.  log_pl (log_pl.hpp) forms the model value; the predictive band shares it.
+// off-grid) PL elements per row.  log_pl (log_pl.hpp) forms the model value; the predictive band shares it.  What follows it --
+// the interpolation, the error and its sums, the finish of a row -- is pl_score.hpp, which the bank kernel (irf_bank.hip) shares.
 // ---------------------------------------------------------------------------------------------
 
 // MOM (trpl_loglik_moments_from_pl_dev): the sum of the errors beside the sum of their squares, in its own instantiation --
@@ -234,33 +237,22 @@ __global__ void __launch_bounds__(256) pl_loglik_kernel(const T *pl, int64_t row
         double y;
         if (obs_hi) {
             const int64_t hi = obs_hi[i];
-            const double lg_hi = log_pl<T>(r[hi], v0, normalize, f32), lg_lo = log_pl<T>(r[hi - 1], v0, normalize, f32);
-            const double dy = f32 ? (double)((float)lg_hi - (float)lg_lo) : lg_hi - lg_lo;
-            y = (dy / obs_h[i]) * obs_dx[i] + lg_lo;            // scipy interp1d: slope * (x - x_lo) + y_lo
+            y = interp_log_pl(log_pl<T>(r[hi], v0, normalize, f32), log_pl<T>(r[hi - 1], v0, normalize, f32), obs_h[i], obs_dx[i], f32);
         } else {
             y = log_pl<T>(r[i], v0, normalize, f32);
         }
-        double err = y + m;
-        err -= obs[i];
-        if constexpr (WT) { const double w = wts[i]; acc += (err * err) * w; acc1 += err * w; }
-        else {
-            acc += err * err;
-            if constexpr (MOM) acc1 += err;
-        }
+        double w = 1.0;
+        if constexpr (WT) w = wts[i];
+        score_add<WT, MOM>(y, m, obs[i], w, acc, acc1);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if constexpr (MOM) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) acc1 += __shfl_xor(acc1, off, 64);
-    }
+    wave_add(acc);
+    if constexpr (MOM) wave_add(acc1);
     if (lane == 0) { part[threadIdx.x >> 6] = acc; if constexpr (MOM) part1[threadIdx.x >> 6] = acc1; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        acc = ((part[0] + part[1]) + part[2]) + part[3];
-        if constexpr (MOM) acc1 = ((part1[0] + part1[1]) + part1[2]) + part1[3];
-        // a system flagged non-converged (its PL is NaN from that step on) scores +inf, like the fused path
-        if ((status && status[row] != 0) || !(acc == acc)) { acc = INFINITY; acc1 = NAN; }
+        acc = row_sum(part);
+        if constexpr (MOM) acc1 = row_sum(part1);
+        row_flag(status && status[row] != 0, acc, acc1);
         if constexpr (MOM) { if (esum_out) esum_out[row] = acc1; }
         if (sse_out) sse_out[row] = acc;
         if (P) P[row] -= acc;                                   // probs.py:44,:60
@@ -294,33 +286,24 @@ hipError_t launch_pl_loglik(const void *pl, int elem_bytes, int64_t rows, int64_
 
 // ---------------------------------------------------------------------------------------------
 // The mag_grid loop of the reference's older likelihood (probs.lnP, probs.py:5-18) from the two moments the
-// TRPL_FLAG_MOMENTS steppers emit: sum_i (e_i + d)^2 = sse + 2 d esum + n d^2.  ONE expression, compiled for the host and
-// for the device in this translation unit (-ffp-contract=off: no fused multiply-add on either side, IEEE divide), so
-// that the plain host forms and the kernels agree bit for bit.
+// TRPL_FLAG_MOMENTS steppers emit: sum_i (e_i + d)^2 = sse + 2 d esum + n d^2.  mag_term, the ordered curve sum and the
+// shared-offset profile are mag_moments.hpp, ONE expression each, compiled for the host and for the device in this translation
+// unit (-ffp-contract=off: no fused multiply-add on either side, IEEE divide), so that the plain host forms and the kernels agree
+// bit for bit; trpl_nuisance_reduce* (nuisance.hip) shares them.
 // ---------------------------------------------------------------------------------------------
-__host__ __device__ inline double mag_term(double sse, double esum, double n, double d)
-{
-    const double t1 = (2.0 * d) * esum;
-    const double t2 = n * (d * d);
-    const double v = (sse + t1) + t2;
-    if (!(sse < INFINITY) || !(esum - esum == 0.0) || !(v == v)) return INFINITY;       // a flagged system, or NaN / inf moments
-    return v < 0.0 ? 0.0 : v;
-}
 
 // P[m][s] -= sum_c mag_term(.., offsets[m]), curves in order
 __host__ __device__ inline void mag_grid_one(const double *sse, const double *esum, const double *n, int64_t S, int C, int64_t s,
                                              double d, double *P)
 {
-    double acc = 0.0;
-    for (int c = 0; c < C; c++) acc += mag_term(sse[(int64_t)c * S + s], esum[(int64_t)c * S + s], n[c], d);
-    *P = *P - acc;
+    *P = *P - mag_curve_sum(sse + s, esum + s, n, S, C, d);
 }
 
 __host__ __device__ inline void mag_profile_one(const double *sse, const double *esum, const double *n, int64_t S, int C, int64_t s,
                                                 bool per_curve, double *best, double *P)
 {
     double acc = 0.0;
-    if (per_curve) {
+    if (per_curve) {                             // an offset of its own per curve: no sum at one d to share
         for (int c = 0; c < C; c++) {
             const double e = esum[(int64_t)c * S + s];
             // a curve whose weights are all zero (trpl_mag_profile_w; n_obs >= 1 never gets here) has no observation:
@@ -331,13 +314,10 @@ __host__ __device__ inline void mag_profile_one(const double *sse, const double 
             acc += mag_term(sse[(int64_t)c * S + s], e, n[c], d);
         }
     } else {
-        double E = 0.0, N = 0.0;
-        bool ok = true;
-        for (int c = 0; c < C; c++) { E += esum[(int64_t)c * S + s]; N += n[c]; ok = ok && sse[(int64_t)c * S + s] < INFINITY; }
-        if (N == 0.0 && ok) { best[s] = NAN; return; }                // every weight zero: nothing to fit, P stays
-        const double d = (0.0 - E) / N;
-        best[s] = (ok && E - E == 0.0) ? d : NAN;
-        for (int c = 0; c < C; c++) acc += mag_term(sse[(int64_t)c * S + s], esum[(int64_t)c * S + s], n[c], d);
+        const MagShared p = mag_shared_offset(sse + s, esum + s, n, S, C);
+        if (p.empty) { best[s] = NAN; return; }                       // every weight zero: nothing to fit, P stays
+        best[s] = p.best;
+        acc = mag_curve_sum(sse + s, esum + s, n, S, C, p.d);
     }
     *P = *P - acc;
 }
@@ -398,12 +378,10 @@ hipError_t launch_mag_grid_w(const double *sse, const double *esum, const double
     if (S <= 0 || M <= 0) return hipSuccess;
     MagArgs g = {};
     for (int c = 0; c < C; c++) g.n[c] = wsum[c];
-    int64_t blocks = (S + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
     for (int64_t m0 = 0; m0 < M; m0 += kMagChunk) {          // offsets travel as kernel arguments, kMagChunk per launch
         const int mc = (int)(M - m0 < kMagChunk ? M - m0 : kMagChunk);
         for (int m = 0; m < mc; m++) g.d[m] = offsets[m0 + m];
-        hipLaunchKernelGGL(mag_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, sse, esum, S, C, mc, P + m0 * S, g);
+        hipLaunchKernelGGL(mag_grid_kernel, dim3(per_sample_blocks(S)), dim3(256), 0, stream, sse, esum, S, C, mc, P + m0 * S, g);
     }
     return hipGetLastError();
 }
@@ -414,9 +392,7 @@ hipError_t launch_mag_profile_w(const double *sse, const double *esum, const dou
     if (S <= 0) return hipSuccess;
     MagArgs g = {};
     for (int c = 0; c < C; c++) g.n[c] = wsum[c];
-    int64_t blocks = (S + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(mag_profile_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, sse, esum, S, C, per_curve ? 1 : 0,
+    hipLaunchKernelGGL(mag_profile_kernel, dim3(per_sample_blocks(S)), dim3(256), 0, stream, sse, esum, S, C, per_curve ? 1 : 0,
                        best, P, g);
     return hipGetLastError();
 }

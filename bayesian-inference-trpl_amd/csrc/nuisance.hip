@@ -1,9 +1,9 @@
 // One reduction over the nuisance grid of an experiment (trpl_nuisance_reduce*, include/trpl.h): the J responses of a bank x M
-// magnitude offsets, from the moments sse, esum [C][J][S] that trpl_loglik_irf_bank* left in HBM.  The value of a cell restates
-// likelihood.hip's mag_term, mag_grid_one and mag_profile_one (the shared-offset form) and irf.loglik_bank's P -= sse; the maximum
-// restates irf_bank.hip's profile_one.  ONE body, compiled for the host and for the device in this translation unit
-// (-ffp-contract=off: no fused multiply-add on either side, IEEE divide), so that the plain host form and the kernel agree bit for
-// bit wherever no exp or log is taken.
+// magnitude offsets, from the moments sse, esum [C][J][S] that trpl_loglik_irf_bank* left in HBM.  The value of a cell shares
+// mag_term, the ordered curve sum and the shared-offset profile with likelihood.hip's trpl_mag_grid* and trpl_mag_profile*
+// (mag_moments.hpp) and restates irf.loglik_bank's P -= sse; the maximum restates irf_bank.hip's profile_one.  ONE body, compiled
+// for the host and for the device in this translation unit (-ffp-contract=off: no fused multiply-add on either side, IEEE divide),
+// so that the plain host form and the kernel agree bit for bit wherever no exp or log is taken.
 //
 // Loop order.  One thread per sample, a wavefront's loads contiguous along s.  Per thread the responses j are the outer loop; under
 // GRID the offsets go kTile at a time with their sums in registers and the curves inside, so that a sample's 2 C moments of response j
@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "api_util.hpp"
+#include "mag_moments.hpp"
 
 namespace trpl {
 namespace nuisance {
@@ -29,16 +30,6 @@ struct Args {
     double d[TRPL_NUISANCE_MAX_OFFSETS];       // offsets
 };
 
-// likelihood.hip's mag_term: the squared error of a curve at offset d from its two moments, +inf for a flagged system or NaN / inf moments
-__host__ __device__ inline double mag_term(double sse, double esum, double n, double d)
-{
-    const double t1 = (2.0 * d) * esum;
-    const double t2 = n * (d * d);
-    const double v = (sse + t1) + t2;
-    if (!(sse < INFINITY) || !(esum - esum == 0.0) || !(v == v)) return INFINITY;
-    return v < 0.0 ? 0.0 : v;
-}
-
 // f(i, v, d) for every cell of sample s in ascending i = j M + m: its value and the offset it stands for
 template <int MODE, typename F>
 __host__ __device__ inline void visit(const double *__restrict__ sse, const double *__restrict__ esum, const Args &g, int64_t S, int C,
@@ -52,14 +43,9 @@ __host__ __device__ inline void visit(const double *__restrict__ sse, const doub
             for (int c = 0; c < C; c++) acc += sse[o + c * JS];
             f(j, 0.0 - acc, 0.0);
         } else if constexpr (MODE == kProfile) {                         // mag_profile_one, one offset for all curves
-            double E = 0.0, N = 0.0;
-            bool ok = true;
-            for (int c = 0; c < C; c++) { E += esum[o + c * JS]; N += g.n[c]; ok = ok && sse[o + c * JS] < INFINITY; }
-            if (N == 0.0 && ok) { f(j, 0.0, (double)NAN); continue; }    // every weight zero: nothing to fit
-            const double d = (0.0 - E) / N;
-            double acc = 0.0;
-            for (int c = 0; c < C; c++) acc += mag_term(sse[o + c * JS], esum[o + c * JS], g.n[c], d);
-            f(j, 0.0 - acc, (ok && E - E == 0.0) ? d : (double)NAN);
+            const MagShared p = mag_shared_offset(sse + o, esum + o, g.n, JS, C);
+            if (p.empty) { f(j, 0.0, (double)NAN); continue; }           // every weight zero: nothing to fit
+            f(j, 0.0 - mag_curve_sum(sse + o, esum + o, g.n, JS, C, p.d), p.best);
         } else {
             for (int m0 = 0; m0 < M; m0 += kTile) {
                 double acc[kTile];
@@ -223,11 +209,9 @@ int trpl_nuisance_reduce_dev(const double *sse, const double *esum, const double
     if (int rc = check_nuisance(sse, esum, wsum, S, C, J, offsets, M, logw, false, tf, flags, P)) return rc;
     if (S == 0) return TRPL_OK;
     const nuisance::Args g = pack(wsum, C, offsets, M);
-    int64_t blocks = (S + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
 #define TRPL_NUISANCE_LAUNCH(MM, GG)                                                                                               \
-    hipLaunchKernelGGL((nuisance::reduce<MM, GG>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sse, esum, S, (int)C, (int)J, \
-                       (int)M, logw, tf, P, best, best_mag, g)
+    hipLaunchKernelGGL((nuisance::reduce<MM, GG>), dim3(per_sample_blocks(S)), dim3(256), 0, (hipStream_t)stream, sse, esum, S, (int)C, \
+                       (int)J, (int)M, logw, tf, P, best, best_mag, g)
     TRPL_NUISANCE_DISPATCH(TRPL_NUISANCE_LAUNCH);
 #undef TRPL_NUISANCE_LAUNCH
     hipError_t e = hipGetLastError();

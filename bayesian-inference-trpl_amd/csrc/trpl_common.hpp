@@ -127,6 +127,12 @@ hipError_t launch_pl_loglik(const void *pl, int elem_bytes, int64_t rows, int64_
 // trpl_sse_accumulate_w: launch_sse_accumulate with every squared residual times wts[i] (probs.py:40)
 hipError_t launch_sse_accumulate_w(double *P, const void *pl, int elem_bytes, int64_t rows, int64_t n_obs, int64_t ld,
                                    const double *values, const double *wts, const double *mag, hipStream_t stream);
+// the grid of the kernels that take one sample per thread in a grid-stride loop: 256-thread workgroups, at most 4096 of them
+inline unsigned per_sample_blocks(int64_t S)
+{
+    const int64_t blocks = (S + 255) / 256;
+    return (unsigned)(blocks > 4096 ? 4096 : blocks);
+}
 // the magnitude-offset grid / profile from the moments (trpl_mag_grid, trpl_mag_profile): host forms and their kernels
 constexpr int kMagMaxCurves = 64;          // TRPL_MAG_MAX_CURVES
 constexpr int kMagChunk = 256;             // offsets per launch (kernel arguments)

@@ -468,24 +468,15 @@ def _simulate_resident(e_data, P, X, num_curves, thicknesses, sim_params, init_p
 
 def _check_irf_bank(opt):
     """gpu_info['irf_bank'] checked as irf.loglik_nuisance checks its arguments -> dict(H, k0, mag, marginal, tf, log_prior)."""
-    from . import device as tdev
-    from .irf import _check_bank, _check_prior
+    from .irf import _check_bank, _check_prior, _check_reduction
     if not isinstance(opt, dict) or "bank" not in opt:
         raise ValueError("gpu_info['irf_bank'] must be a dict with the entry bank=(H, k0[, table])")
     unknown = set(opt) - {"bank", "mag", "reduce", "tf", "log_prior"}
     if unknown:
         raise ValueError("gpu_info['irf_bank']: unknown entries %s" % sorted(unknown))
     H, k0 = _check_bank(opt["bank"])
-    mag, reduce, tf = opt.get("mag", "fixed"), opt.get("reduce", "max"), float(opt.get("tf", 1.0))
-    if reduce not in ("max", "marginal"):
-        raise ValueError('gpu_info[\'irf_bank\']: reduce must be "max" or "marginal", got %r' % (reduce,))
-    marginal = reduce == "marginal"
-    _, off = tdev.nuisance_flags(mag, marginal)
-    M = 1 if off is None else len(off)
-    if not 1 <= M <= _abi.NUISANCE_MAX_OFFSETS or (off is not None and not np.all(np.isfinite(off))):
-        raise ValueError("gpu_info['irf_bank']: mag as a grid holds 1 .. %d finite offsets" % _abi.NUISANCE_MAX_OFFSETS)
-    if marginal and not (tf > 0.0 and math.isfinite(tf)):
-        raise ValueError("gpu_info['irf_bank']: tf must be finite and > 0")
+    mag = opt.get("mag", "fixed")
+    marginal, off, M, tf = _check_reduction(mag, opt.get("reduce", "max"), float(opt.get("tf", 1.0)), where="gpu_info['irf_bank']: ")
     return dict(H=H, k0=k0, mag=mag if off is None else off, marginal=marginal, tf=tf,
                 log_prior=_check_prior(opt.get("log_prior"), H.shape[0], M, marginal))
 

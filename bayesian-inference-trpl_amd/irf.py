@@ -203,6 +203,102 @@ def _stage(X, init_params, lengths, Time, L, T, obs, k0, times, weights, block):
     return X, ini, lengths, staged, ncol_out
 
 
+def _check_reduction(mag, reduce, tf, where=""):
+    """The reduction over responses x magnitude offsets as loglik_nuisance and gpu_info['irf_bank'] (where names it) take it ->
+    (marginal, off, M, tf): off the host array of grid offsets or None, M the offsets per response."""
+    from . import device as tdev
+    if reduce not in ("max", "marginal"):
+        raise ValueError(where + 'reduce must be "max" or "marginal", got %r' % (reduce,))
+    marginal = reduce == "marginal"
+    _, off = tdev.nuisance_flags(mag, marginal)
+    M = 1 if off is None else len(off)
+    count_ok, finite = 1 <= M <= _abi.NUISANCE_MAX_OFFSETS, off is None or bool(np.all(np.isfinite(off)))
+    if where and not (count_ok and finite):
+        raise ValueError(where + "mag as a grid holds 1 .. %d finite offsets" % _abi.NUISANCE_MAX_OFFSETS)
+    if not count_ok:
+        raise ValueError("mag: a grid holds 1 .. %d offsets, got %d" % (_abi.NUISANCE_MAX_OFFSETS, M))
+    if not finite:
+        raise ValueError("mag: every offset must be finite")
+    tf = float(tf)
+    if marginal and not (tf > 0.0 and math.isfinite(tf)):
+        raise ValueError(where + "tf must be finite and > 0")
+    return marginal, off, M, tf
+
+
+class _Resident:
+    """What the resident routes -- loglik, loglik_bank, loglik_nuisance -- have in common: the refusals and the staging before a
+    device is touched, in one order, and the loop over blocks of samples and curves around the one solve.  irf = (h, k0) or bank
+    = (H, k0[, table]); reduction = (mag, reduce, tf) is checked between the normalize refusal and the bank (_check_reduction ->
+    marginal, off, M, tf).  A route adds its host results, then per block its device buffers, per curve its scoring calls and at
+    the end of a block its downloads."""
+
+    def __init__(self, X, init_params, lengths, Time, L, T, obs, times, weights, block, normalize, irf=None, bank=None, reduction=None):
+        if normalize:
+            raise ValueError(_NO_NORMALIZE)
+        if reduction is not None:
+            self.marginal, self.off, self.M, self.tf = _check_reduction(*reduction)
+        self.taps, self.k0 = _check_irf(irf) if bank is None else _check_bank(bank)
+        self.X, self.ini, self.lengths, self.staged, self.ncol_out = _stage(X, init_params, lengths, Time, L, T, obs, self.k0, times,
+                                                                            weights, block)
+        if bank is not None:
+            for c, kw in enumerate(self.staged):
+                if len(kw["obs"]) < 1:
+                    raise ValueError("curve %d: a bank needs at least one observation per curve" % c)
+        self.S, self.Cn, self.Time, self.L, self.T, self.block = self.X.shape[0], self.ini.shape[0], Time, int(L), int(T), int(block)
+        self.status = np.zeros((self.Cn, self.S), dtype=np.int32)
+
+    def blocks(self, tol, MAX, pl_f32, predict, device):
+        """The blocks of `block` samples, one after the other, each as a namespace b: n samples, sl their slice of the host arrays,
+        first (the route's buffers that outlive a block are made then: size rows serve every block), mag (n,), pl (n, T + 1) the PL
+        block, taps and kw the uploaded responses and per-curve keywords, torch, tdev, dev, to_dev(host array), zeros(*shape) f64.
+        b.curves() yields c = 0 .. C - 1 with curve c solved into b.pl and its flags in b.status[c].  After the route's part of a
+        block status comes down.  Without a sample nothing is yielded and no device is touched."""
+        if self.S == 0:
+            return
+        import types
+
+        import torch
+
+        from . import device as tdev
+        dev = torch.device("cuda", device)
+        Cn, T = self.Cn, self.T
+        with torch.cuda.device(dev):
+            def to_dev(a):
+                return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+            def zeros(*shape):
+                return torch.zeros(shape, dtype=torch.float64, device=dev)
+            ini_d, taps_d = to_dev(self.ini), to_dev(self.taps)
+            staged = [{k: to_dev(v) for k, v in kw.items()} for kw in self.staged]
+            size = min(self.block, self.S)
+            pl_d = torch.empty((size, T + 1), dtype=torch.float32 if pl_f32 else torch.float64, device=dev)
+            for blk in range(0, self.S, self.block):
+                n = min(self.block, self.S - blk)
+                X_d = to_dev(self.X[blk:blk + n])
+                mat_d = X_d[:, :12].contiguous()
+                b = types.SimpleNamespace(n=n, sl=slice(blk, blk + n), first=blk == 0, size=size, mag=X_d[:, 12].contiguous(), pl=pl_d[:n],
+                                          taps=taps_d, kw=staged, torch=torch, tdev=tdev, dev=dev, to_dev=to_dev, zeros=zeros)
+
+                def curves():
+                    b.status = torch.zeros((Cn, n), dtype=torch.int32, device=dev)
+                    for c in range(Cn):
+                        tdev.solve_pl_device(mat_d, self.lengths[c], self.Time, self.L, T, ini_d[c].contiguous(), b.pl, status=b.status[c],
+                                             tol=tol, MAX=MAX, flags=_abi.FLAG_PREDICT if predict else 0)
+                        yield c
+                b.curves = curves
+                yield b
+                self.status[:, b.sl] = b.status.cpu().numpy()
+
+    def bank_moments(self, b, c, sse_d, es_d):
+        """curve c of block b against the J responses: its moments into sse_d[c], es_d[c] (J, n)"""
+        b.tdev.loglik_irf_bank_device(b.pl, b.taps, self.k0, mag=b.mag, sse=sse_d[c], esum=es_d[c], status=b.status[c], **b.kw[c])
+
+
+def _moments_down(host, dev_t, sl):
+    """the moments of a block, (C, J, n) on the device, into the columns sl of the host's (J, C, S)"""
+    host[:, :, sl] = dev_t.cpu().numpy().transpose(1, 0, 2)
+
+
 def loglik(X, init_params, lengths, Time, L, T, obs, irf, times=None, weights=None, tol=7, MAX=10000, pl_f32=False,
            predict=False, block=8192, device=0, P=None, info=None, normalize=False):
     """The likelihood of one experiment with the instrument response in the model, on the resident route: per block of `block`
@@ -224,51 +320,24 @@ def loglik(X, init_params, lengths, Time, L, T, obs, irf, times=None, weights=No
     functools.partial(loglik, init_params=..., ..., irf=...) is a valid `loglik` for refine.run, mcmc.run and
     mcmc.run_tempered WITHOUT early_reject: the early stop lives in the fused steppers (trpl_loglik_cut*), which compare the
     bare curve and never see a convolved one."""
-    if normalize:
-        raise ValueError(_NO_NORMALIZE)
-    h, k0 = _check_irf(irf)
-    X, ini, lengths, staged, ncol_out = _stage(X, init_params, lengths, Time, L, T, obs, k0, times, weights, block)
-    S, Cn, L, T, block = X.shape[0], ini.shape[0], int(L), int(T), int(block)
+    r = _Resident(X, init_params, lengths, Time, L, T, obs, times, weights, block, normalize, irf=irf)
     if P is None:
-        P = np.zeros(S)
-    if not (P.dtype == np.float64 and P.flags.c_contiguous and P.shape == (S,)):
+        P = np.zeros(r.S)
+    if not (P.dtype == np.float64 and P.flags.c_contiguous and P.shape == (r.S,)):
         raise ValueError("P must be a contiguous float64 array of shape (S,)")
-    sse = np.zeros((Cn, S))
-    status = np.zeros((Cn, S), dtype=np.int32)
+    sse = np.zeros((r.Cn, r.S))
     if info is not None:
-        info.update(sse=sse, status=status, ncol_out=ncol_out)
-    if S == 0:
-        return P
-
-    import torch
-
-    from . import device as tdev
-    dev = torch.device("cuda", device)
-    tdt = torch.float32 if pl_f32 else torch.float64
-    score = tdev.loglik_from_pl_device if weights is None else tdev.loglik_weighted_from_pl_device
-    with torch.cuda.device(dev):
-        def to_dev(a):
-            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        ini_d, h_d = to_dev(ini), to_dev(h)
-        staged = [{k: to_dev(v) for k, v in kw.items()} for kw in staged]
-        size = min(block, S)
-        pl_d = torch.empty((size, T + 1), dtype=tdt, device=dev)
-        cv_d = torch.empty((size, ncol_out), dtype=tdt, device=dev)
-        for blk in range(0, S, block):
-            n = min(block, S - blk)
-            X_d = to_dev(X[blk:blk + n])
-            mat_d, mag_d = X_d[:, :12].contiguous(), X_d[:, 12].contiguous()
-            P_d = to_dev(P[blk:blk + n])
-            sse_d = torch.zeros((Cn, n), dtype=torch.float64, device=dev)
-            st_d = torch.zeros((Cn, n), dtype=torch.int32, device=dev)
-            for c in range(Cn):
-                tdev.solve_pl_device(mat_d, lengths[c], Time, L, T, ini_d[c].contiguous(), pl_d[:n], status=st_d[c], tol=tol,
-                                     MAX=MAX, flags=_abi.FLAG_PREDICT if predict else 0)
-                tdev.convolve_irf_device(pl_d[:n], h_d, k0, cv_d[:n])
-                score(cv_d[:n], mag=mag_d, P=P_d, sse=sse_d[c], status=st_d[c], **staged[c])
-            P[blk:blk + n] = P_d.cpu().numpy()
-            sse[:, blk:blk + n] = sse_d.cpu().numpy()
-            status[:, blk:blk + n] = st_d.cpu().numpy()
+        info.update(sse=sse, status=r.status, ncol_out=r.ncol_out)
+    for b in r.blocks(tol, MAX, pl_f32, predict, device):
+        if b.first:
+            cv_d = b.pl.new_empty((b.size, r.ncol_out))
+            score = b.tdev.loglik_from_pl_device if weights is None else b.tdev.loglik_weighted_from_pl_device
+        P_d, sse_d = b.to_dev(P[b.sl]), b.zeros(r.Cn, b.n)
+        for c in b.curves():
+            b.tdev.convolve_irf_device(b.pl, b.taps, r.k0, cv_d[:b.n])
+            score(cv_d[:b.n], mag=b.mag, P=P_d, sse=sse_d[c], status=b.status[c], **b.kw[c])
+        P[b.sl] = P_d.cpu().numpy()
+        sse[:, b.sl] = sse_d.cpu().numpy()
     return P
 
 
@@ -383,51 +452,21 @@ def loglik_bank(X, init_params, lengths, Time, L, T, obs, bank, times=None, weig
     arguments (P started from zeros, the curves subtracted in order).  Every other argument, the blocking and the refusals are
     loglik's.  info receives sse (J, C, S), esum (J, C, S) -- the sums of the errors, so that a magnitude profile can follow --
     status (C, S) and ncol_out."""
-    if normalize:
-        raise ValueError(_NO_NORMALIZE)
-    H, k0 = _check_bank(bank)
-    X, ini, lengths, staged, ncol_out = _stage(X, init_params, lengths, Time, L, T, obs, k0, times, weights, block)
-    S, Cn, L, T, block, J = X.shape[0], ini.shape[0], int(L), int(T), int(block), H.shape[0]
-    for c, kw in enumerate(staged):
-        if len(kw["obs"]) < 1:
-            raise ValueError("curve %d: a bank needs at least one observation per curve" % c)
-    P = np.zeros((J, S))
-    sse = np.zeros((J, Cn, S))
-    esum = np.zeros((J, Cn, S))
-    status = np.zeros((Cn, S), dtype=np.int32)
+    r = _Resident(X, init_params, lengths, Time, L, T, obs, times, weights, block, normalize, bank=bank)
+    J = r.taps.shape[0]
+    P = np.zeros((J, r.S))
+    sse = np.zeros((J, r.Cn, r.S))
+    esum = np.zeros((J, r.Cn, r.S))
     if info is not None:
-        info.update(sse=sse, esum=esum, status=status, ncol_out=ncol_out)
-    if S == 0:
-        return P
-
-    import torch
-
-    from . import device as tdev
-    dev = torch.device("cuda", device)
-    tdt = torch.float32 if pl_f32 else torch.float64
-    with torch.cuda.device(dev):
-        def to_dev(a):
-            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        ini_d, H_d = to_dev(ini), to_dev(H)
-        staged = [{k: to_dev(v) for k, v in kw.items()} for kw in staged]
-        pl_d = torch.empty((min(block, S), T + 1), dtype=tdt, device=dev)
-        for blk in range(0, S, block):
-            n = min(block, S - blk)
-            X_d = to_dev(X[blk:blk + n])
-            mat_d, mag_d = X_d[:, :12].contiguous(), X_d[:, 12].contiguous()
-            P_d = torch.zeros((J, n), dtype=torch.float64, device=dev)
-            sse_d = torch.zeros((Cn, J, n), dtype=torch.float64, device=dev)
-            es_d = torch.zeros((Cn, J, n), dtype=torch.float64, device=dev)
-            st_d = torch.zeros((Cn, n), dtype=torch.int32, device=dev)
-            for c in range(Cn):
-                tdev.solve_pl_device(mat_d, lengths[c], Time, L, T, ini_d[c].contiguous(), pl_d[:n], status=st_d[c], tol=tol,
-                                     MAX=MAX, flags=_abi.FLAG_PREDICT if predict else 0)
-                tdev.loglik_irf_bank_device(pl_d[:n], H_d, k0, mag=mag_d, sse=sse_d[c], esum=es_d[c], status=st_d[c], **staged[c])
-                P_d -= sse_d[c]                                   # loglik's P[s] -= sse, curves in order
-            P[:, blk:blk + n] = P_d.cpu().numpy()
-            sse[:, :, blk:blk + n] = sse_d.cpu().numpy().transpose(1, 0, 2)
-            esum[:, :, blk:blk + n] = es_d.cpu().numpy().transpose(1, 0, 2)
-            status[:, blk:blk + n] = st_d.cpu().numpy()
+        info.update(sse=sse, esum=esum, status=r.status, ncol_out=r.ncol_out)
+    for b in r.blocks(tol, MAX, pl_f32, predict, device):
+        P_d, sse_d, es_d = b.zeros(J, b.n), b.zeros(r.Cn, J, b.n), b.zeros(r.Cn, J, b.n)
+        for c in b.curves():
+            r.bank_moments(b, c, sse_d, es_d)
+            P_d -= sse_d[c]                                       # loglik's P[s] -= sse, curves in order
+        P[:, b.sl] = P_d.cpu().numpy()
+        _moments_down(sse, sse_d, b.sl)
+        _moments_down(esum, es_d, b.sl)
     return P
 
 
@@ -501,73 +540,31 @@ def loglik_nuisance(X, init_params, lengths, Time, L, T, obs, bank, mag="fixed",
     early_reject: the early stop lives in the fused steppers (trpl_loglik_cut*), which compare the bare curve and never see a
     convolved one.  A marginal is formed at ONE tf: it is a valid `loglik` for refine.run and mcmc.run at that tf, and NOT for
     mcmc.run_tempered, whose rungs differ in tf (the maximum is valid there)."""
-    if normalize:
-        raise ValueError(_NO_NORMALIZE)
-    if reduce not in ("max", "marginal"):
-        raise ValueError('reduce must be "max" or "marginal", got %r' % (reduce,))
-    marginal = reduce == "marginal"
-    from . import device as tdev
-    _, off = tdev.nuisance_flags(mag, marginal)
-    M = 1 if off is None else len(off)
-    if not 1 <= M <= _abi.NUISANCE_MAX_OFFSETS:
-        raise ValueError("mag: a grid holds 1 .. %d offsets, got %d" % (_abi.NUISANCE_MAX_OFFSETS, M))
-    if off is not None and not np.all(np.isfinite(off)):
-        raise ValueError("mag: every offset must be finite")
-    tf = float(tf)
-    if marginal and not (tf > 0.0 and math.isfinite(tf)):
-        raise ValueError("tf must be finite and > 0")
-    H, k0 = _check_bank(bank)
-    X, ini, lengths, staged, ncol_out = _stage(X, init_params, lengths, Time, L, T, obs, k0, times, weights, block)
-    S, Cn, L, T, block, J = X.shape[0], ini.shape[0], int(L), int(T), int(block), H.shape[0]
-    for c, kw in enumerate(staged):
-        if len(kw["obs"]) < 1:
-            raise ValueError("curve %d: a bank needs at least one observation per curve" % c)
-    lp = _check_prior(log_prior, J, M, marginal)
-    wsum = np.array([float(len(kw["obs"])) if weights is None else math.fsum(kw["wts"]) for kw in staged])
+    r = _Resident(X, init_params, lengths, Time, L, T, obs, times, weights, block, normalize, bank=bank, reduction=(mag, reduce, tf))
+    S, Cn, J = r.S, r.Cn, r.taps.shape[0]
+    lp = _check_prior(log_prior, J, r.M, r.marginal)
+    wsum = np.array([float(len(kw["obs"])) if weights is None else math.fsum(kw["wts"]) for kw in r.staged])
     LL = np.full(S, -np.inf)
     best = np.full(S, -1, dtype=np.int32)
     best_mag = np.full(S, np.nan)
-    status = np.zeros((Cn, S), dtype=np.int32)
     if info is not None:
-        info.update(best=best, best_mag=best_mag, status=status, ncol_out=ncol_out, cells=(J, M))
+        info.update(best=best, best_mag=best_mag, status=r.status, ncol_out=r.ncol_out, cells=(J, r.M))
         if keep_moments:
             info.update(sse=np.zeros((J, Cn, S)), esum=np.zeros((J, Cn, S)))
-    if S == 0:
-        return LL
-
-    import torch
-
-    dev = torch.device("cuda", device)
-    tdt = torch.float32 if pl_f32 else torch.float64
-    with torch.cuda.device(dev):
-        def to_dev(a):
-            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        ini_d, H_d = to_dev(ini), to_dev(H)
-        lp_d = None if lp is None else to_dev(lp)
-        staged = [{k: to_dev(v) for k, v in kw.items()} for kw in staged]
-        size = min(block, S)
-        pl_d = torch.empty((size, T + 1), dtype=tdt, device=dev)
-        LL_d = torch.empty(size, dtype=torch.float64, device=dev)
-        best_d = torch.empty(size, dtype=torch.int32, device=dev)
-        bm_d = torch.empty(size, dtype=torch.float64, device=dev)
-        for blk in range(0, S, block):
-            n = min(block, S - blk)
-            X_d = to_dev(X[blk:blk + n])
-            mat_d, mag_d = X_d[:, :12].contiguous(), X_d[:, 12].contiguous()
-            sse_d = torch.zeros((Cn, J, n), dtype=torch.float64, device=dev)
-            es_d = torch.zeros((Cn, J, n), dtype=torch.float64, device=dev)
-            st_d = torch.zeros((Cn, n), dtype=torch.int32, device=dev)
-            for c in range(Cn):
-                tdev.solve_pl_device(mat_d, lengths[c], Time, L, T, ini_d[c].contiguous(), pl_d[:n], status=st_d[c], tol=tol,
-                                     MAX=MAX, flags=_abi.FLAG_PREDICT if predict else 0)
-                tdev.loglik_irf_bank_device(pl_d[:n], H_d, k0, mag=mag_d, sse=sse_d[c], esum=es_d[c], status=st_d[c], **staged[c])
-            tdev.nuisance_reduce_device(sse_d, es_d, wsum, LL_d[:n], best=best_d[:n], best_mag=bm_d[:n], mag=mag, marginal=marginal,
-                                        tf=tf, log_prior=lp_d)
-            LL[blk:blk + n] = LL_d[:n].cpu().numpy()
-            best[blk:blk + n] = best_d[:n].cpu().numpy()
-            best_mag[blk:blk + n] = bm_d[:n].cpu().numpy()
-            status[:, blk:blk + n] = st_d.cpu().numpy()
-            if keep_moments and info is not None:
-                info["sse"][:, :, blk:blk + n] = sse_d.cpu().numpy().transpose(1, 0, 2)
-                info["esum"][:, :, blk:blk + n] = es_d.cpu().numpy().transpose(1, 0, 2)
+    for b in r.blocks(tol, MAX, pl_f32, predict, device):
+        if b.first:
+            lp_d = None if lp is None else b.to_dev(lp)
+            LL_d, bm_d = b.mag.new_empty(b.size), b.mag.new_empty(b.size)
+            best_d = b.torch.empty(b.size, dtype=b.torch.int32, device=b.dev)
+        sse_d, es_d = b.zeros(Cn, J, b.n), b.zeros(Cn, J, b.n)
+        for c in b.curves():
+            r.bank_moments(b, c, sse_d, es_d)
+        b.tdev.nuisance_reduce_device(sse_d, es_d, wsum, LL_d[:b.n], best=best_d[:b.n], best_mag=bm_d[:b.n], mag=mag, marginal=r.marginal,
+                                      tf=r.tf, log_prior=lp_d)
+        LL[b.sl] = LL_d[:b.n].cpu().numpy()
+        best[b.sl] = best_d[:b.n].cpu().numpy()
+        best_mag[b.sl] = bm_d[:b.n].cpu().numpy()
+        if keep_moments and info is not None:
+            _moments_down(info["sse"], sse_d, b.sl)
+            _moments_down(info["esum"], es_d, b.sl)
     return LL
