@@ -1,5 +1,9 @@
 """ctypes binding of libtrpl_hip.so (the C ABI declared in include/trpl.h).
 
+The argument and return types of every entry point are read from the prototypes of include/trpl.h when this module is
+imported (_parse_header): a new entry point is declared there and nowhere else.  The constants below restate the header's
+#defines as literals; tests/test_abi.py holds them to it.
+
 The library is built in-tree by `make -C bayesian-inference-trpl_amd` (or
 `__graft_entry__.build()`).  There is NO fallback: if the shared object is missing or a call
 fails, an exception is raised -- the product path never routes through the CPU oracle.
@@ -93,203 +97,46 @@ class TrplError(RuntimeError):
         self.code = code
 
 
-_vp, _i32, _i64, _u32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_double
-_u64 = C.c_uint64
+_HEADER = os.path.join(os.path.dirname(_HERE), "include", "trpl.h")
 _pd = C.POINTER(C.c_double)
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "double": C.c_double}
+_RETURNS = dict(_SCALARS, **{"int": C.c_int, "const char *": C.c_char_p})
 
-# name -> argtypes, exactly the prototypes of include/trpl.h
-SIGNATURES = {
-    "trpl_abi_version": [],
-    "trpl_last_error": [],
-    "trpl_has_experimental": [],
-    "trpl_device_count": [],
-    "trpl_pair_table": [_vp, _vp, _i32, _i32, _i64, _f64, _vp, _vp, _vp, _vp],
-    "trpl_solve_pl": [_vp, _i64, _f64, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i64, _vp, _vp, _u32,
-                      _i32, _pd],
-    "trpl_solve_pl_dev": [_vp, _i64, _f64, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i64, _vp, _vp,
-                          _u32, _vp],
-    "trpl_solve_pl_snap": [_vp, _i64, _f64, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i64, _vp, _vp, _vp,
-                           _i32, _vp, _vp, _vp, _u32, _i32, _pd],
-    "trpl_solve_pl_snap_dev": [_vp, _i64, _f64, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i64, _vp, _vp,
-                               _vp, _i32, _vp, _vp, _vp, _u32, _vp],
-    "trpl_solve_pl_resume": [_vp, _i64, _f64, _f64, _i32, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _i64,
-                             _vp, _vp, _vp, _i32, _vp, _vp, _vp, _u32, _i32, _pd],
-    "trpl_solve_pl_resume_dev": [_vp, _i64, _f64, _f64, _i32, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i32,
-                                 _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _u32, _vp],
-    "trpl_log10_clamp": [_vp, _i32, _i64, _i64, _i64, _f64, _i32, _pd],
-    "trpl_log10_clamp_dev": [_vp, _i32, _i64, _i64, _i64, _f64, _vp],
-    "trpl_sse_accumulate": [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _i32, _pd],
-    "trpl_sse_accumulate_dev": [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp],
-    "trpl_loglik": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
-                    _vp, _vp, _u32, _i32, _pd],
-    "trpl_loglik_dev": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp,
-                        _vp, _vp, _vp, _u32, _vp],
-    "trpl_loglik_obs": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
-                        _vp, _vp, _vp, _vp, _u32, _i32, _pd],
-    "trpl_loglik_obs_dev": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
-                            _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    "trpl_interp_rows": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64],
-    "trpl_loglik_from_pl_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _u32, _vp],
-    "trpl_loglik_moments": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
-                            _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _pd],
-    "trpl_loglik_moments_dev": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64,
-                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    "trpl_loglik_moments_from_pl_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
-                                        _u32, _vp],
-    "trpl_mag_grid": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp],
-    "trpl_mag_grid_dev": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp],
-    "trpl_mag_profile": [_vp, _vp, _vp, _i64, _i32, _u32, _vp, _vp],
-    "trpl_mag_profile_dev": [_vp, _vp, _vp, _i64, _i32, _u32, _vp, _vp, _vp],
-    "trpl_loglik_weighted": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
-                             _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _pd],
-    "trpl_loglik_weighted_dev": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    "trpl_loglik_weighted_from_pl_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
-                                         _u32, _vp],
-    "trpl_sse_accumulate_w": [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _pd],
-    "trpl_sse_accumulate_w_dev": [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
-    "trpl_mag_grid_w": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp],
-    "trpl_mag_grid_w_dev": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp],
-    "trpl_mag_profile_w": [_vp, _vp, _vp, _i64, _i32, _u32, _vp, _vp],
-    "trpl_mag_profile_w_dev": [_vp, _vp, _vp, _i64, _i32, _u32, _vp, _vp, _vp],
-    "trpl_loglik_cut": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f64,
-                        _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _pd],
-    "trpl_loglik_cut_dev": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f64,
-                            _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    "trpl_loglik_cut_levels": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
-                               _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _pd],
-    "trpl_loglik_cut_levels_dev": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
-                                   _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    # budget [S] where cut_level is, curves_per_launch after it, cut_level [C][S] out before P
-    "trpl_loglik_cut_budget": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
-                               _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _pd],
-    "trpl_loglik_cut_budget_dev": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
-                                   _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    "trpl_loglik_multi": [_vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64,
-                          _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _i32, _pd],
-    "trpl_multi_create": [_vp, _i32, _vp],
-    "trpl_multi_create_ex": [_vp, _i32, _u32, _vp],
-    "trpl_multi_destroy": [_vp],
-    "trpl_multi_device_count": [_vp],
-    "trpl_multi_synchronize": [_vp],
-    "trpl_loglik_multi_dev": [_vp, _vp, _i64, _i32, _vp, _f64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
-                              _i64, _vp, _vp, _vp, _vp, _vp, _vp, _u32],
-    "trpl_multi_wait_stream": [_vp, _i32, _vp],
-    "trpl_multi_release_stream": [_vp, _i32, _vp],
-    "trpl_shard_bounds": [_i64, _i32, _i32, _vp, _vp],
-    "trpl_shard_of": [_i64, _i32, _i64],
-    "trpl_kernel_variant": [_i64, _i32, _i64, _u32],
-    "trpl_kernel_name": [_i64, _i32, _i64, _u32, _i32, _vp, _i64],
-    "trpl_sample_box": [_u32, _i64, _i32, _vp, _vp, _vp, _u32, _vp, _i32, _pd],
-    "trpl_sample_box_dev": [_u32, _i64, _i32, _vp, _vp, _vp, _u32, _vp, _vp],
-    "trpl_posterior_workspace_bytes": [_i32],
-    "trpl_posterior_weights": [_vp, _i64, _f64, _vp, _vp, _i32, _pd],
-    "trpl_posterior_weights_dev": [_vp, _i64, _f64, _vp, _vp, _vp, _i64, _vp],
-    "trpl_posterior_moments": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _pd],
-    "trpl_posterior_moments_dev": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
-    "trpl_posterior_hist": [_vp, _vp, _vp, _i64, _f64, _f64, _i32, _f64, _f64, _i32, _vp, _i32, _pd],
-    "trpl_posterior_hist_dev": [_vp, _vp, _vp, _i64, _f64, _f64, _i32, _f64, _f64, _i32, _vp, _vp],
-    "trpl_posterior_tf_scan_workspace": [_i64, _i32, _i32],
-    "trpl_posterior_tf_scan": [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _pd],
-    "trpl_posterior_tf_scan_dev": [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
-    "trpl_posterior_weights_lr": [_vp, _vp, _i64, _f64, _vp, _vp, _i32, _pd],
-    "trpl_posterior_weights_lr_dev": [_vp, _vp, _i64, _f64, _vp, _vp, _vp, _i64, _vp],
-    "trpl_posterior_tf_scan_lr_workspace": [_i64, _i32, _i32],
-    "trpl_posterior_tf_scan_lr": [_vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _pd],
-    "trpl_posterior_tf_scan_lr_dev": [_vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
-    "trpl_predictive_state_bytes": [_i64],
-    "trpl_predictive_workspace_bytes": [_i64, _i64, _i32],
-    "trpl_predictive_chunks": [_i64, _i64, _i32],
-    "trpl_predictive_init_dev": [_vp, _i64, _vp],
-    "trpl_predictive_accumulate_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _u32, _vp, _vp, _i64, _vp],
-    "trpl_predictive_finish_dev": [_vp, _i64, _vp, _vp],
-    "trpl_predictive": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _u32, _vp, _i32, _pd],
-    "trpl_quantiles_stage_rows": [],
-    "trpl_weighted_quantiles_dev": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _u32, _vp, _vp],
-    "trpl_weighted_quantiles": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _u32, _vp, _i32, _pd],
-    "trpl_predictive_gather_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _u32, _vp, _i64, _i64, _vp, _vp],
-    "trpl_irf_max_taps": [],
-    "trpl_convolve_irf_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _i64, _vp],
-    "trpl_convolve_irf": [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _i64, _i32, _pd],
-    "trpl_irf_bank_max_responses": [],
-    "trpl_irf_bank_block": [],
-    # H, J, K, k0 after ld; obs, the three brackets, n_obs, wts; mag, status; sse, esum [J][rows]
-    "trpl_loglik_irf_bank_dev": [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
-                                 _u32, _vp],
-    "trpl_loglik_irf_bank": [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _u32,
-                             _i32, _pd],
-    "trpl_irf_bank_profile_dev": [_vp, _i32, _i64, _vp, _vp, _vp],
-    "trpl_irf_bank_profile": [_vp, _i32, _i64, _vp, _vp],
-    "trpl_nuisance_max_offsets": [],
-    "trpl_nuisance_bound": [_f64, _f64, _i32, _f64],
-    # sse, esum [C][J][S], wsum (host); S, C, J; offsets (host), M; logw, tf, flags; P, best, best_mag
-    "trpl_nuisance_reduce_dev": [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _f64, _u32, _vp, _vp, _vp, _vp],
-    "trpl_nuisance_reduce": [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _f64, _u32, _vp, _vp, _vp],
-    "trpl_corner_workspace_bytes": [_i64, _i32],
-    "trpl_corner_columns_dev": [_vp, _i64, _i64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "trpl_corner_hist_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
-    "trpl_corner": [_vp, _i64, _i64, _vp, _f64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
-                    _i32, _pd],
-    "trpl_refine_chunk_rows": [],
-    "trpl_refine_tile_parents": [],
-    "trpl_refine_workspace_bytes": [_i64],
-    "trpl_refine_resample_dev": [_vp, _i64, _i64, _f64, _vp, _vp, _vp, _i64, _vp],
-    "trpl_refine_resample": [_vp, _i64, _i64, _f64, _vp, _vp, _i32, _pd],
-    "trpl_refine_draw_dev": [_vp, _vp, _i64, _i32, _i64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp],
-    "trpl_refine_draw": [_vp, _vp, _i64, _i32, _i64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _i32, _pd],
-    "trpl_refine_density_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
-    "trpl_refine_density": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _pd],
-    "trpl_refine_unit_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _u32, _i32, _vp, _vp],
-    "trpl_refine_unit": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _u32, _i32, _vp, _i32, _pd],
-    "trpl_refine_affine_dev": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp],
-    "trpl_refine_affine": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _pd],
-    "trpl_refine_draw_oriented_dev": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp,
-                                      _vp, _vp],
-    "trpl_refine_draw_oriented": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp,
-                                  _i32, _pd],
-    "trpl_mcmc_propose_dev": [_vp, _vp, _i64, _i64, _i32, _f64, _vp, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp],
-    "trpl_mcmc_propose": [_vp, _vp, _i64, _i64, _i32, _f64, _vp, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _i32, _pd],
-    "trpl_mcmc_accept_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f64, _i64, _u64, _u32, _vp, _vp],
-    "trpl_mcmc_accept": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f64, _i64, _u64, _u32, _vp, _i32, _pd],
-    "trpl_mcmc_chain_stats_dev": [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp],
-    "trpl_mcmc_chain_stats": [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _pd],
-    "trpl_mcmc_levels_dev": [_vp, _i64, _f64, _i64, _u64, _u32, _vp, _vp],
-    "trpl_mcmc_levels": [_vp, _i64, _f64, _i64, _u64, _u32, _vp, _i32, _pd],
-    "trpl_mcmc_propose_rungs_dev": [_vp, _vp, _i64, _i64, _i64, _i32, _f64, _vp, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp,
-                                    _vp],
-    "trpl_mcmc_propose_rungs": [_vp, _vp, _i64, _i64, _i64, _i32, _f64, _vp, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _i32,
-                                _pd],
-    "trpl_mcmc_accept_rungs_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _vp],
-    "trpl_mcmc_accept_rungs": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _i32, _pd],
-    "trpl_mcmc_levels_rungs_dev": [_vp, _i64, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _vp],
-    "trpl_mcmc_levels_rungs": [_vp, _i64, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _i32, _pd],
-    "trpl_mcmc_swap_dev": [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _i64, _u64, _u32, _vp, _vp],
-    "trpl_mcmc_swap": [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _i64, _u64, _u32, _vp, _i32, _pd],
-    "trpl_mcmc_autocov_tile": [],
-    "trpl_mcmc_autocov_dev": [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp],
-    "trpl_mcmc_autocov": [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _pd],
-    "trpl_mcmc_autocov_pool_dev": [_vp, _i64, _i64, _i64, _i32, _vp, _vp],
-    "trpl_mcmc_autocov_pool": [_vp, _i64, _i64, _i64, _i32, _vp, _i32, _pd],
-    "trpl_mcmc_autocov_chains": [_vp, _i64, _i64, _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _pd],
-    "trpl_mcmc_propose_stretch_dev": [_vp, _vp, _i64, _i64, _i64, _i32, _f64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp,
-                                      _vp, _vp],
-    "trpl_mcmc_propose_stretch": [_vp, _vp, _i64, _i64, _i64, _i32, _f64, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp,
-                                  _i32, _pd],
-    "trpl_mcmc_accept_h_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _vp],
-    "trpl_mcmc_accept_h": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _i32, _pd],
-    "trpl_mcmc_levels_h_dev": [_vp, _vp, _i64, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _vp],
-    "trpl_mcmc_levels_h": [_vp, _vp, _i64, _i32, _i64, _vp, _i64, _u64, _u32, _vp, _i32, _pd],
-    "trpl_mcmc_prior_term_dev": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
-    "trpl_mcmc_prior_term": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _pd],
-    "trpl_mcmc_propose_subspace_dev": [_vp, _vp, _i64, _i64, _i64, _i32, _f64, _vp, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp,
-                                       _i32, _i32, _vp, _vp, _f64, _vp, _vp, _vp],
-    "trpl_mcmc_propose_subspace": [_vp, _vp, _i64, _i64, _i64, _i32, _f64, _vp, _i64, _u64, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp,
-                                   _i32, _i32, _vp, _vp, _f64, _vp, _vp, _i32, _pd],
-    "trpl_mcmc_evidence_sums_dev": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
-    "trpl_mcmc_evidence_sums": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _pd],
-    "trpl_pcr_solve_batched": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _i32, _pd],
-    "trpl_pcr_solve_batched_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _u32, _vp],
-}
+
+def _parse_header(text):
+    """name -> (restype, argtypes) of every trpl_* prototype in `text`, the contents of include/trpl.h.  A parameter with a
+    `*` is a c_void_p, except `double *seconds`, a POINTER(c_double) (callers pass byref); any other is one of _SCALARS, a
+    return type one of _RETURNS.  A spelling outside these raises ValueError: nothing is guessed."""
+    import re
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    text = "\n".join(ln for ln in text.split("\n") if not ln.lstrip().startswith("#"))
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w\s*]*?)\b(trpl_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        ret, args = " ".join(ret.split()), " ".join(args.split())
+        argtypes = []
+        for a in ([] if args == "void" else args.split(", ")):
+            kind = a.replace("const ", "").split(" ")[0]
+            if "*" in a:
+                argtypes.append(_pd if a == "double *seconds" else C.c_void_p)
+            elif kind in _SCALARS:
+                argtypes.append(_SCALARS[kind])
+            else:
+                raise ValueError("include/trpl.h: parameter %r of %s is of no type the binding knows" % (a, name))
+        if ret not in _RETURNS:
+            raise ValueError("include/trpl.h: return type %r of %s is none the binding knows" % (ret, name))
+        out[name] = (_RETURNS[ret], argtypes)
+    return out
+
+
+# name -> argtypes and name -> restype, read from include/trpl.h at import: the header is the binding, there is no table to
+# keep in step with it.  Without the header both are empty, and lib() refuses to load anything.
+try:
+    with open(_HEADER) as _fh:
+        _protos = _parse_header(_fh.read())
+except OSError:
+    _protos = {}
+SIGNATURES = {name: argtypes for name, (_, argtypes) in _protos.items()}
+RESTYPES = {name: restype for name, (restype, _) in _protos.items()}
 
 _lib = None
 
@@ -301,7 +148,7 @@ def source_hash():
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp")))
-    files += [os.path.join(os.path.dirname(_HERE), "include", "trpl.h"), os.path.join(_HERE, "Makefile")]
+    files += [_HEADER, os.path.join(_HERE, "Makefile")]
     h = hashlib.sha256()
     for f in files:
         with open(f, "rb") as fh:
@@ -385,9 +232,14 @@ def _share_torch_hip_runtime():
 
 
 def lib():
-    """Load libtrpl_hip.so once; raise loudly if it is absent and cannot be built."""
+    """Load libtrpl_hip.so once; raise loudly if it is absent and cannot be built.  The argument and return types of every
+    entry point come from include/trpl.h, so a tree without that header raises ImportError here (it used to make only
+    library_is_current() false)."""
     global _lib
     if _lib is None:
+        if not SIGNATURES:
+            raise ImportError("%s could not be read: the package needs include/trpl.h beside it (the ctypes binding is "
+                              "derived from that header)" % _HEADER)
         if not os.path.isfile(LIB_PATH):
             _build_if_stale()
         if not os.path.isfile(LIB_PATH):
@@ -413,13 +265,7 @@ def lib():
                 continue
             fn = getattr(dll, name)
             fn.argtypes = argtypes
-            fn.restype = C.c_char_p if name == "trpl_last_error" else (
-                C.c_int64 if name in ("trpl_posterior_workspace_bytes", "trpl_posterior_tf_scan_workspace",
-                                     "trpl_posterior_tf_scan_lr_workspace", "trpl_shard_of",
-                                     "trpl_predictive_state_bytes", "trpl_predictive_workspace_bytes",
-                                     "trpl_quantiles_stage_rows", "trpl_corner_workspace_bytes", "trpl_refine_chunk_rows",
-                                     "trpl_refine_tile_parents", "trpl_refine_workspace_bytes") else
-                C.c_double if name == "trpl_nuisance_bound" else C.c_int)
+            fn.restype = RESTYPES[name]
         _lib = dll
     return _lib
 

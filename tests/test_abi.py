@@ -9,23 +9,71 @@ import sys
 import numpy as np
 import pytest
 
+import abi_header as H
 from conftest import ROOT
 
 
-def header_symbols():
-    text = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(trpl_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_library_exports_every_declared_symbol(trpl):
-    names = header_symbols()
+    names = sorted(set(re.findall(r"\b(trpl_[a-z0-9_]+)\s*\(", H.code())))
     assert len(names) >= 13
     dll = trpl._abi.lib()
     for n in names:
         assert hasattr(dll, n), n
     assert set(trpl._abi.SIGNATURES) == set(names)       # the binding covers the whole header
     assert dll.trpl_abi_version() == 5 == trpl._abi.ABI_VERSION
+
+
+def test_binding_types_are_the_headers_for_every_prototype(trpl):
+    """The ctypes class of every parameter and return value, stated here from the declaration's text as tests/abi_header.py
+    reads it, is the one trpl_amd._abi derived with its own reader -- an int64_t bound as a double would pass every count."""
+    A = trpl._abi
+    scalar = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64,
+              "double": ctypes.c_double}
+    returned = dict(scalar, **{"int": ctypes.c_int, "const char *": ctypes.c_char_p})
+
+    def expected(decl):
+        if "*" in decl:
+            return ctypes.POINTER(ctypes.c_double) if decl == "double *seconds" else ctypes.c_void_p
+        kind, _name = decl.replace("const ", "").split()
+        return scalar[kind]
+
+    assert len(H.names()) >= 152 and set(H.names()) == set(A.SIGNATURES) == set(A.RESTYPES)
+    for name in H.names():
+        want = [expected(p) for p in H.params(name)]
+        assert len(want) == len(A.SIGNATURES[name]) and all(a is b for a, b in zip(want, A.SIGNATURES[name])), name
+        fn = getattr(A.lib(), name)
+        assert list(fn.argtypes or []) == want and fn.restype is returned[H.returns(name)] is A.RESTYPES[name], name
+
+
+def test_binding_types_spot_checks(trpl):
+    """Written out by hand, from include/trpl.h as a person reads it: no reader of the header is involved."""
+    from ctypes import POINTER, c_char_p, c_double, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+    A = trpl._abi
+    lib = A.lib()
+    draw = A.SIGNATURES["trpl_refine_draw"]
+    assert (draw[6], draw[7]) == (c_uint64, c_uint32) and c_uint64 not in draw[:6] + draw[8:]      # seed, step
+    assert A.SIGNATURES["trpl_nuisance_bound"] == [c_double, c_double, c_int32, c_double]
+    assert lib.trpl_nuisance_bound.restype is c_double
+    assert lib.trpl_shard_of.restype is c_int64 and lib.trpl_last_error.restype is c_char_p
+    assert A.SIGNATURES["trpl_solve_pl"][-1] is POINTER(c_double) is lib.trpl_solve_pl.argtypes[-1]
+    assert A.SIGNATURES["trpl_loglik_multi_dev"][:2] == [c_void_p, c_void_p]
+
+
+@pytest.mark.parametrize("proto, word", [("int trpl_x(const double *a,\n           long n,\n           double *seconds);\n", "long n"),
+                                         ("unsigned trpl_x(const double *a,\n                int64_t n,\n                void *stream);\n", "unsigned")])
+def test_the_header_reader_refuses_a_type_it_does_not_know(trpl, proto, word):
+    with pytest.raises(ValueError, match="trpl_x") as e:
+        trpl._abi._parse_header(proto)
+    assert word in str(e.value)
+    restype, argtypes = trpl._abi._parse_header(proto.replace("long n", "int64_t n").replace("unsigned", "int"))["trpl_x"]      # the rest is fine
+    assert restype is ctypes.c_int and argtypes[:2] == [ctypes.c_void_p, ctypes.c_int64] and len(argtypes) == 3
+
+
+def test_lib_refuses_to_load_without_the_header(trpl, monkeypatch):
+    monkeypatch.setattr(trpl._abi, "_lib", None)
+    monkeypatch.setattr(trpl._abi, "SIGNATURES", {})         # what a tree without include/trpl.h has at import
+    with pytest.raises(ImportError, match="needs include/trpl.h beside it"):
+        trpl._abi.lib()
 
 
 def test_cites_reference_interfaces():
@@ -240,8 +288,7 @@ def test_bundle_flag_encoding_matches_the_header():
     import re
     import trpl_amd
     A = trpl_amd._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    assert re.search(r"#define TRPL_FLAG_BUNDLE\(m\) \(\(uint32_t\)\(\(\(m\) - 1\) & 0xF\) << 8\)", hdr)
+    assert re.search(r"#define TRPL_FLAG_BUNDLE\(m\) \(\(uint32_t\)\(\(\(m\) - 1\) & 0xF\) << 8\)", H.code())
     assert [A.flag_bundle(m) for m in (1, 2, 3, 4, 16)] == [0, 0x100, 0x200, 0x300, 0xF00]
     for bad in (0, 17):
         with pytest.raises(ValueError):
@@ -297,9 +344,8 @@ def test_python_constants_equal_the_headers_defines():
     """Every flag, kernel id and documented constant of include/trpl.h that the Python binding restates has the same
     value there (the header is the contract; the envelope constants are what the -m gpu parity tests assert)."""
     from trpl_amd import _abi as A
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +([0-9][0-9a-fA-Fx.e+-]*)\b", hdr, flags=re.M))
-    num = lambda v: int(v, 0) if re.fullmatch(r"0[xX][0-9a-fA-F]+|\d+", v) else float(v)
+    hdr = H.code()
+    defs = H.defines()
     pairs = {"TRPL_FLAG_STRICT": A.FLAG_STRICT, "TRPL_FLAG_PL_F32": A.FLAG_PL_F32, "TRPL_FLAG_NORMALIZE": A.FLAG_NORMALIZE,
              "TRPL_FLAG_FP32": A.FLAG_FP32, "TRPL_FLAG_KERNEL_PAIR": A.FLAG_KERNEL_PAIR, "TRPL_FLAG_KERNEL_SINGLE": A.FLAG_KERNEL_SINGLE,
              "TRPL_FLAG_MIXED": A.FLAG_MIXED, "TRPL_FLAG_SNAP_RAW": A.FLAG_SNAP_RAW, "TRPL_FLAG_FP32_LONG": A.FLAG_FP32_LONG,
@@ -313,7 +359,12 @@ def test_python_constants_equal_the_headers_defines():
              "TRPL_MULTI_ALLOW_DUPLICATE_DEVICES": A.MULTI_ALLOW_DUPLICATE_DEVICES}
     for name, val in pairs.items():
         assert name in defs, name
-        assert num(defs[name]) == val, (name, defs[name], val)
+        assert defs[name] == val, (name, defs[name], val)
+    # ... and so has every numeric #define TRPL_X for which the binding has an attribute X: 83 of the header's 88
+    covered = [name for name in defs if hasattr(A, name[len("TRPL_"):])]
+    for name in covered:
+        assert getattr(A, name[len("TRPL_"):]) == defs[name], (name, defs[name])
+    assert len(covered) >= 83 and set(pairs) <= set(covered), len(covered)
     flags = [v for k, v in pairs.items() if k.startswith("TRPL_FLAG_")]
     assert len(set(flags)) == len(flags) and all(f & (f - 1) == 0 for f in flags)          # distinct single bits
     assert not any(f & 0xF00 for f in flags)                                                # TRPL_FLAG_BUNDLE's field
@@ -366,11 +417,8 @@ def test_kernel_name_refuses_what_a_launch_refuses(trpl):
     name without a kernel would silently attach nothing.  On every accepted combination the name and trpl_kernel_variant's
     code describe the same kernel (both are read off one classification, csrc/trpl_api.hip classify_stepper)."""
     import itertools
-    import subprocess
     A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
-    have = set(re.findall(r"(trpl::(?:predict::)?(?:pair::|f32::)?stepper(?:_pair)?_kernel<[^>]*>)", filt))
+    have = set(re.findall(r"(trpl::(?:predict::)?(?:pair::|f32::)?stepper(?:_pair)?_kernel<[^>]*>)", H.demangled()))
     assert len(have) >= 40, len(have)
     exp = A.has_experimental()
     named = refused = 0

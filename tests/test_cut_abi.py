@@ -12,28 +12,29 @@ import sys
 import numpy as np
 import pytest
 
+import abi_header as H
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("trpl_loglik_cut", "trpl_loglik_cut_dev")
 
 
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()          # with its comments: the sentences below
     for name in NEW:
-        assert re.search(r"\bint %s\s*\(" % name, code), name
+        assert H.returns(name) == "int", name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        n_args = len(re.search(r"\bint %s\s*\(([^;]*)\);" % name, code).group(1).split(","))
+        n_args = len(H.params(name))
         assert n_args == len(A.SIGNATURES[name]), (name, n_args)
     # the arguments of the moments calls without esum, plus sse_cut and cut_col
     assert len(A.SIGNATURES["trpl_loglik_cut"]) == len(A.SIGNATURES["trpl_loglik_moments"]) + 1
     assert len(A.SIGNATURES["trpl_loglik_cut_dev"]) == len(A.SIGNATURES["trpl_loglik_moments_dev"]) + 1
-    proto = re.search(r"\bint trpl_loglik_cut\s*\(([^;]*)\);", code).group(1)
+    proto = ", ".join(H.params("trpl_loglik_cut"))
     assert "double sse_cut" in proto and "int32_t *cut_col" in proto and "esum" not in proto
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_FLAG_CUT"], 0) == A.FLAG_CUT == 0x800000
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.lib().trpl_abi_version()          # additive: the version stays
-    others = [int(v, 0) for k, v in defs.items() if k.startswith("TRPL_FLAG_") and k != "TRPL_FLAG_CUT"]
+    defs = H.defines()
+    assert defs["TRPL_FLAG_CUT"] == A.FLAG_CUT == 0x800000
+    assert defs["TRPL_ABI_VERSION"] == 5 == A.lib().trpl_abi_version()          # additive: the version stays
+    others = [v for k, v in defs.items() if k.startswith("TRPL_FLAG_") and k != "TRPL_FLAG_CUT"]
     assert A.FLAG_CUT & (A.FLAG_CUT - 1) == 0
     assert not any(A.FLAG_CUT & o for o in others) and not A.FLAG_CUT & (0xF00 | (7 << 14))
     # the sentences the header owes its readers
@@ -46,8 +47,7 @@ def test_header_binding_and_library_agree(trpl):
 
 def test_every_cut_kernel_name_exists_in_the_library(trpl):
     A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
+    filt = H.demangled()
     have = set(re.findall(r"(trpl::cut::(?:predict::)?(?:pair::)?stepper(?:_pair)?_kernel<[^>]*>)", filt))
     # the one-system FAST kernel at the 8 grids, the paired kernel in both seam forms; each with and without PREDICT
     assert len(have) == 20, sorted(have)

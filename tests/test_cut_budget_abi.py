@@ -4,10 +4,11 @@ carry the codes the header states, with no device present; the ABI version stays
 trpl::cut:: steppers.  No GPU needed."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
+
+import abi_header as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("trpl_loglik_cut_budget", "trpl_loglik_cut_budget_dev")
@@ -15,25 +16,23 @@ NEW = ("trpl_loglik_cut_budget", "trpl_loglik_cut_budget_dev")
 
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()          # with its comments: the sentences below
     for name in NEW:
-        assert re.search(r"\bint %s\s*\(" % name, code), name
+        assert H.returns(name) == "int", name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        n_args = len(re.search(r"\bint %s\s*\(([^;]*)\);" % name, code).group(1).split(","))
+        n_args = len(H.params(name))
         assert n_args == len(A.SIGNATURES[name]), (name, n_args)
     # the arguments of trpl_loglik_cut_levels: budget where cut_level is, curves_per_launch after it, cut_level before P
     for dev in ("", "_dev"):
         bd, lv = A.SIGNATURES["trpl_loglik_cut_budget" + dev], A.SIGNATURES["trpl_loglik_cut_levels" + dev]
         assert len(bd) == len(lv) + 2
         assert bd[:18] == lv[:18] and bd[18] is A.C.c_int32 and bd[19] is A.C.c_void_p and bd[20:] == lv[18:]
-        proto = " ".join(re.search(r"\bint trpl_loglik_cut_budget%s\s*\(([^;]*)\);" % dev, code).group(1).split())
+        proto = ", ".join(H.params("trpl_loglik_cut_budget" + dev))
         names = [a.split()[-1].lstrip("*") for a in proto.split(",")]
         assert names[16:22] == ["n_obs", "budget", "curves_per_launch", "cut_level", "P", "sse"] and names[22] == "cut_col", names
         assert "const double *budget" in proto and "int32_t curves_per_launch" in proto and ", double *cut_level" in proto
         assert "sse_cut" not in proto
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.lib().trpl_abi_version()          # additive: the version stays
+    assert H.defines()["TRPL_ABI_VERSION"] == 5 == A.lib().trpl_abi_version()          # additive: the version stays
     assert not any("trpl_loglik_multi" in n and "budget" in n for n in A.SIGNATURES)  # there is no multi form
     # the sentences the header owes its readers: the rule, the proof, the refusals
     flat = " ".join(hdr.split()).replace(" * ", " ")
@@ -45,9 +44,7 @@ def test_header_binding_and_library_agree(trpl):
 
 
 def test_the_kernel_is_in_the_library_and_its_unit_is_built_uncontracted(trpl):
-    A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
+    filt = H.demangled()
     assert "trpl::budget::level_kernel" in filt
     have = set(re.findall(r"(trpl::cut::(?:predict::)?(?:pair::)?stepper(?:_pair)?_kernel<[^>]*>)", filt))
     assert len(have) == 20, sorted(have)                                              # no stepper was added

@@ -3,10 +3,11 @@ of a Metropolis step): header, binding and library agree on the four symbols; th
 no device present; the ABI version stays 5 and the shared object still holds exactly the 20 trpl::cut:: steppers.  No GPU needed."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
+
+import abi_header as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("trpl_loglik_cut_levels", "trpl_loglik_cut_levels_dev", "trpl_mcmc_levels", "trpl_mcmc_levels_dev")
@@ -14,12 +15,11 @@ NEW = ("trpl_loglik_cut_levels", "trpl_loglik_cut_levels_dev", "trpl_mcmc_levels
 
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()          # with its comments: the sentences below
     for name in NEW:
-        assert re.search(r"\bint %s\s*\(" % name, code), name
+        assert H.returns(name) == "int", name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        n_args = len(re.search(r"\bint %s\s*\(([^;]*)\);" % name, code).group(1).split(","))
+        n_args = len(H.params(name))
         assert n_args == len(A.SIGNATURES[name]), (name, n_args)
     # the cut calls' arguments, a pointer where sse_cut is
     for dev in ("", "_dev"):
@@ -27,12 +27,11 @@ def test_header_binding_and_library_agree(trpl):
         assert len(lv) == len(cut)
         diff = [k for k in range(len(cut)) if lv[k] is not cut[k]]
         assert diff == [17] and cut[17] is A.C.c_double and lv[17] is A.C.c_void_p
-        proto = re.search(r"\bint trpl_loglik_cut_levels%s\s*\(([^;]*)\);" % dev, code).group(1)
+        proto = ", ".join(H.params("trpl_loglik_cut_levels" + dev))
         assert "const double *cut_level" in proto and "sse_cut" not in proto and "int32_t *cut_col" in proto
         assert proto.index("n_obs") < proto.index("cut_level") < proto.index("double *P")
     assert len(A.SIGNATURES["trpl_mcmc_levels"]) == 9 and len(A.SIGNATURES["trpl_mcmc_levels_dev"]) == 8
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.lib().trpl_abi_version()          # additive: the version stays
+    assert H.defines()["TRPL_ABI_VERSION"] == 5 == A.lib().trpl_abi_version()          # additive: the version stays
     assert not any("trpl_loglik_multi" in n and "level" in n for n in A.SIGNATURES)  # there is no multi form
     # the sentences the header owes its readers
     flat = " ".join(hdr.split()).replace(" * ", " ")
@@ -46,9 +45,7 @@ def test_header_binding_and_library_agree(trpl):
 
 
 def test_the_library_still_holds_exactly_the_twenty_cut_steppers(trpl):
-    A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
+    filt = H.demangled()
     have = set(re.findall(r"(trpl::cut::(?:predict::)?(?:pair::)?stepper(?:_pair)?_kernel<[^>]*>)", filt))
     assert len(have) == 20, sorted(have)
     assert "trpl::mcmc::levels_kernel" in filt

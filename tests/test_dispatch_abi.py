@@ -6,7 +6,8 @@ import ctypes as C
 import itertools
 import os
 import re
-import subprocess
+
+import abi_header as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -14,9 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_every_accepted_combination_names_a_built_kernel_and_every_refusal_keeps_its_code(trpl):
     A = trpl._abi
     lib = A.lib()
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
-    have = set(re.findall(r"(trpl::(?:\w+::)*stepper(?:_pair)?_kernel<[^>]*>)", filt))
+    have = set(re.findall(r"(trpl::(?:\w+::)*stepper(?:_pair)?_kernel<[^>]*>)", H.demangled()))
     want = {}
     for line in open(os.path.join(ROOT, "tests", "golden", "dispatch_codes.txt")):
         if not line.startswith("#"):

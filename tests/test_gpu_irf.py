@@ -4,20 +4,16 @@ more than two tiles; one tap up to the cap; the tap of time zero first, second a
 that are only element-aligned, with a canary behind every row -- and the routes that carry it: irf.loglik against the three
 device calls issued by hand, gpu_info["irf"] of simulate, posterior_predictive(irf=...).  Tile and cap are read from
 include/trpl.h (tests/test_irf_host.py checks that the binding agrees)."""
-import os
-import re
-
 import numpy as np
 import pytest
 
+import abi_header as H
 import irf_ref as R
 import likelihood_ref as LR
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_HDR = open(os.path.join(ROOT, "include", "trpl.h")).read()
-_define = lambda name: int(re.search(r"#define %s (\d+)" % name, _HDR).group(1))
+_define = H.defines().__getitem__
 TC, TR, CAP, MAXK = _define("TRPL_IRF_TILE_COLS"), _define("TRPL_IRF_TILE_ROWS"), _define("TRPL_IRF_GRID_CAP"), _define("TRPL_IRF_MAX_TAPS")
 NCOLS = [1, 2, 63, 64, 65, TC - 1, TC, TC + 1, 2 * TC + 3]
 KS = [1, 2, 3, 64, 65, MAXK]

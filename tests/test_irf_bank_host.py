@@ -4,14 +4,12 @@ trpl_irf_bank_profile[_dev] through the C ABI with the message naming the argume
 irf.loglik_profile, and the ABI.  No compute call touches a device here."""
 import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_header as H
 import irf_ref as R
-from conftest import ROOT
 
 DT = 0.03125                                                 # 2^-5: shift / dt is exact for shifts that are multiples of it
 
@@ -126,16 +124,12 @@ NEW = ("trpl_irf_bank_max_responses", "trpl_irf_bank_block", "trpl_loglik_irf_ba
 
 
 def test_header_binding_and_library_agree(trpl):
-    text = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    define = lambda name: int(re.search(r"#define %s (\d+)" % name, text).group(1))
+    define = H.defines().__getitem__
     A = trpl._abi
     lib = A.lib()
     for name in NEW:
         assert name in A.SIGNATURES and hasattr(lib, name), name
-        proto = re.search(r"\b%s\(([^;]*)\);" % name, text)
-        assert proto, name
-        args = proto.group(1).strip()
-        count = 0 if args == "void" else len(re.sub(r"/\*.*?\*/", "", args, flags=re.S).split(","))
+        count = len(H.params(name))
         assert count == len(A.SIGNATURES[name]), (name, count)
     assert (define("TRPL_IRF_BANK_MAX_RESPONSES"), define("TRPL_IRF_BANK_BLOCK")) == (A.IRF_BANK_MAX_RESPONSES, A.IRF_BANK_BLOCK)
     assert lib.trpl_irf_bank_max_responses() == A.IRF_BANK_MAX_RESPONSES >= 256

@@ -4,14 +4,12 @@ trpl_amd.irf.gaussian / from_samples, every refusal of trpl_convolve_irf[_dev] t
 argument, and the ValueErrors of irf.loglik and of gpu_info["irf"].  No compute call is made here."""
 import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_header as H
 import irf_ref as R
-from conftest import ROOT
 
 
 # ------------------------------------------------------------------------------------------------ the restatement
@@ -131,8 +129,7 @@ def test_from_samples(trpl):
 
 # ------------------------------------------------------------------------------------------------ the C ABI
 def test_header_binding_and_kernel_agree_on_the_constants(trpl):
-    text = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    define = lambda name: int(re.search(r"#define %s (\d+)" % name, text).group(1))
+    define = H.defines().__getitem__
     A = trpl._abi
     assert (define("TRPL_IRF_MAX_TAPS"), define("TRPL_IRF_TILE_COLS"), define("TRPL_IRF_TILE_ROWS"), define("TRPL_IRF_GRID_CAP")) \
         == (A.IRF_MAX_TAPS, A.IRF_TILE_COLS, A.IRF_TILE_ROWS, A.IRF_GRID_CAP)

@@ -3,10 +3,11 @@ are in the library and their unit is compiled without contraction; every refusal
 naming the argument, decided with no device present; the Python layer's own refusals.  No GPU needed."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
+
+import abi_header as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("trpl_mcmc_propose", "trpl_mcmc_propose_dev", "trpl_mcmc_accept", "trpl_mcmc_accept_dev", "trpl_mcmc_chain_stats",
@@ -15,15 +16,11 @@ NEW = ("trpl_mcmc_propose", "trpl_mcmc_propose_dev", "trpl_mcmc_accept", "trpl_m
 
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name in NEW:
-        proto = re.search(r"\bint %s\s*\(([^;]*)\);" % name, code)
-        assert proto, name
+        assert H.returns(name) == "int", name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        assert len(proto.group(1).split(",")) == len(A.SIGNATURES[name]), name
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.lib().trpl_abi_version() == A.ABI_VERSION          # additive: the version stays
+        assert len(H.params(name)) == len(A.SIGNATURES[name]), name
+    assert H.defines()["TRPL_ABI_VERSION"] == 5 == A.lib().trpl_abi_version() == A.ABI_VERSION          # additive: the version stays
     for fn in ("propose", "accept", "chain_stats", "start", "run", "Chains"):
         assert callable(getattr(trpl.mcmc, fn)), fn
     for fn in ("mcmc_propose_device", "mcmc_accept_device", "mcmc_chain_stats_device"):
@@ -31,11 +28,9 @@ def test_header_binding_and_library_agree(trpl):
 
 
 def test_the_library_exports_the_symbols_and_holds_the_kernels(trpl):
-    A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
     for name in NEW:
-        assert re.search(r"\bT %s\b" % name, nm), name
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
+        assert re.search(r"\bT %s\b" % name, H.exports()), name
+    filt = H.demangled()
     for kernel in ("propose_kernel", "accept_kernel"):
         have = {int(n) for n in re.findall(r"trpl::mcmc::__device_stub__%s<(\d+)>" % kernel, filt)}
         assert have == set(range(1, 17)), (kernel, sorted(have))

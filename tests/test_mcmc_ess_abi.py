@@ -2,14 +2,13 @@
 header, binding and library agree; the kernels are in the library beside the ones the sampler had; every refusal the header states
 is TRPL_ERR_ARG with a message naming the argument, decided with no device present; the Python refusals of Chains.ess.  No GPU
 needed."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_header as H
+
 NEW = {"trpl_mcmc_autocov_dev": 11, "trpl_mcmc_autocov": 11, "trpl_mcmc_autocov_pool_dev": 7, "trpl_mcmc_autocov_pool": 8,
        "trpl_mcmc_autocov_chains": 13}
 TILE = 8                                                         # trpl_mcmc_autocov_tile(): the lags one thread sums
@@ -17,17 +16,13 @@ TILE = 8                                                         # trpl_mcmc_aut
 
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name, n_args in NEW.items():
-        proto = re.search(r"\bint %s\s*\(([^;]*)\);" % name, code)
-        assert proto, name
+        assert H.returns(name) == "int", name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        assert len(proto.group(1).split(",")) == len(A.SIGNATURES[name]) == n_args, name
-    assert re.search(r"\bint trpl_mcmc_autocov_tile\s*\(void\);", code) and A.SIGNATURES["trpl_mcmc_autocov_tile"] == []
+        assert len(H.params(name)) == len(A.SIGNATURES[name]) == n_args, name
+    assert re.search(r"\bint trpl_mcmc_autocov_tile\s*\(void\);", H.code()) and A.SIGNATURES["trpl_mcmc_autocov_tile"] == []
     assert A.lib().trpl_mcmc_autocov_tile() == TILE
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.lib().trpl_abi_version() == A.ABI_VERSION          # additive: the version stays
+    assert H.defines()["TRPL_ABI_VERSION"] == 5 == A.lib().trpl_abi_version() == A.ABI_VERSION          # additive: the version stays
     for fn in ("autocov", "autocov_pool", "ess_from_sums"):
         assert callable(getattr(trpl.mcmc, fn)), fn
     for fn in ("ess", "autocorr", "mcse"):
@@ -37,11 +32,9 @@ def test_header_binding_and_library_agree(trpl):
 
 
 def test_the_library_exports_the_symbols_and_holds_the_kernels(trpl):
-    A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
     for name in list(NEW) + ["trpl_mcmc_autocov_tile"]:
-        assert re.search(r"\bT %s\b" % name, nm), name
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
+        assert re.search(r"\bT %s\b" % name, H.exports()), name
+    filt = H.demangled()
     tiles = {int(n) for n in re.findall(r"trpl::mcmc::__device_stub__autocov_kernel<(\d+)>", filt)}
     assert tiles == {TILE}, sorted(tiles)
     for kernel in ("autocov_mean_kernel", "autocov_pool_kernel", "chain_stats_kernel", "levels_kernel", "levels_rungs_kernel"):

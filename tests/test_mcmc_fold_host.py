@@ -8,20 +8,18 @@ Measured with this stream on the face toy (256 chains, 400 sweeps, 200 dropped, 
     largest distance from the analytic value in standard errors: fold 2.13, reject 2.61 (the gate is 5)
 Chi-square of the uniform toy (20 bins, 5120 pooled coordinates, gate 63.68): fold at most 25.5, the clamp at least 7.0e3."""
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_header as H
 import mcmc_fold_ref as fr
 import mcmc_ref as mr
 import test_mcmc_abi as abi_mcmc
 import test_refine_abi as abi_refine
 import test_refine_oriented_abi as abi_oriented
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FOLD = 0x10
 
 
@@ -192,11 +190,10 @@ def test_the_seed_of_the_device_end_to_end_case_excuses_no_decision():
 
 # ------------------------------------------------------------------ the ABI, no device
 def test_the_header_and_the_binding_agree(trpl):
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_MCMC_FOLD"], 0) == trpl._abi.MCMC_FOLD == FOLD
-    assert int(defs["TRPL_ABI_VERSION"]) == 5
-    taken = int(defs["TRPL_BOX_EQUAL_MU"], 0) | int(defs["TRPL_BOX_EQUAL_S"], 0) | int(defs["TRPL_BOX_EQUAL_AUGER"], 0)
+    defs = H.defines()
+    assert defs["TRPL_MCMC_FOLD"] == trpl._abi.MCMC_FOLD == FOLD
+    assert defs["TRPL_ABI_VERSION"] == 5
+    taken = defs["TRPL_BOX_EQUAL_MU"] | defs["TRPL_BOX_EQUAL_S"] | defs["TRPL_BOX_EQUAL_AUGER"]
     assert taken == 7 and not FOLD & (taken | 0x8)              # apart from the box bits and from the pinned refusal of 0x8
 
 
@@ -235,9 +232,7 @@ def test_the_refinement_draws_refuse_the_flag(trpl):
 
 
 def test_the_library_holds_the_fold_kernels(trpl):
-    nm = subprocess.run(["nm", "-D", "--defined-only", trpl._abi.LIB_PATH], capture_output=True, text=True).stdout
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
-    have = [int(n) for n in re.findall(r"trpl::mcmc::__device_stub__propose_fold_kernel<(\d+)>", filt)]
+    have = [int(n) for n in re.findall(r"trpl::mcmc::__device_stub__propose_fold_kernel<(\d+)>", H.demangled())]
     assert sorted(have) == list(range(1, 17)), sorted(have)
 
 

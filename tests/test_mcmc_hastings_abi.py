@@ -5,10 +5,11 @@ run and run_tempered with kind="stretch" and prior=.  No GPU needed."""
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
+
+import abi_header as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("trpl_mcmc_propose_stretch", "trpl_mcmc_propose_stretch_dev", "trpl_mcmc_accept_h", "trpl_mcmc_accept_h_dev",
@@ -17,19 +18,15 @@ NEW = ("trpl_mcmc_propose_stretch", "trpl_mcmc_propose_stretch_dev", "trpl_mcmc_
 
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name in NEW:
-        proto = re.search(r"\bint %s\s*\(([^;]*)\);" % name, code)
-        assert proto, name
+        assert H.returns(name) == "int", name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        assert len(proto.group(1).split(",")) == len(A.SIGNATURES[name]), name
+        assert len(H.params(name)) == len(A.SIGNATURES[name]), name
     for form in ("", "_dev"):                                    # h beside the arguments of the *_rungs calls
         assert len(A.SIGNATURES["trpl_mcmc_accept_h" + form]) == len(A.SIGNATURES["trpl_mcmc_accept_rungs" + form]) + 1
         assert len(A.SIGNATURES["trpl_mcmc_levels_h" + form]) == len(A.SIGNATURES["trpl_mcmc_levels_rungs" + form]) + 1
     assert len(A.SIGNATURES["trpl_mcmc_propose_stretch"]) == 22 and len(A.SIGNATURES["trpl_mcmc_prior_term"]) == 10
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.lib().trpl_abi_version() == A.ABI_VERSION          # additive: the version stays
+    assert H.defines()["TRPL_ABI_VERSION"] == 5 == A.lib().trpl_abi_version() == A.ABI_VERSION          # additive: the version stays
     for fn in ("propose_stretch", "accept_h", "reject_levels_h", "prior_term", "gaussian_prior"):
         assert callable(getattr(trpl.mcmc, fn)), fn
     for fn in ("mcmc_propose_stretch_device", "mcmc_accept_h_device", "mcmc_levels_h_device", "mcmc_prior_term_device"):
@@ -40,11 +37,9 @@ def test_header_binding_and_library_agree(trpl):
 
 
 def test_the_library_holds_the_kernels_and_their_unit_is_uncontracted(trpl):
-    A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
     for name in NEW:
-        assert re.search(r"\bT %s\b" % name, nm), name
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
+        assert re.search(r"\bT %s\b" % name, H.exports()), name
+    filt = H.demangled()
     for kernel in ("stretch_kernel", "hastings_accept_kernel", "prior_term_kernel"):
         have = {int(n) for n in re.findall(r"trpl::mcmc::__device_stub__%s<(\d+)>" % kernel, filt)}
         assert have == set(range(1, 17)), (kernel, sorted(have))

@@ -6,9 +6,10 @@ import inspect
 import itertools
 import os
 import re
-import subprocess
 
 import numpy as np
+
+import abi_header as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("trpl_mcmc_propose_subspace", "trpl_mcmc_propose_subspace_dev")
@@ -19,22 +20,20 @@ ARGS = ("U", "partners", "count", "P", "group", "A", "gamma", "scale", "chain0",
 
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()          # with its comments: the Philox indices below
     for name in NEW:
-        proto = re.search(r"\bint %s\s*\(([^;]*)\);" % name, code)
-        assert proto, name
+        assert H.returns(name) == "int", name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        names = [re.search(r"(\w+)\s*$", a).group(1) for a in proto.group(1).split(",")]
+        names = [re.search(r"(\w+)\s*$", a).group(1) for a in H.params(name)]
         tail = ["stream"] if name.endswith("_dev") else ["device", "seconds"]
         assert names == list(ARGS) + tail, name                   # propose_rungs' arguments in its order, then the move's
         assert len(names) == len(A.SIGNATURES[name]), name
         rungs = A.SIGNATURES[name.replace("subspace", "rungs")]
         assert A.SIGNATURES[name][:19] == rungs[:19] and A.SIGNATURES[name][26:] == rungs[19:], name
         assert [t.__name__ for t in A.SIGNATURES[name][19:26]] == ["c_int", "c_int", "c_void_p", "c_void_p", "c_double", "c_void_p", "c_void_p"]
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_MCMC_MAX_PAIRS"]) == 4 == A.MCMC_MAX_PAIRS and int(defs["TRPL_MCMC_MAX_CR"]) == 8 == A.MCMC_MAX_CR
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.lib().trpl_abi_version() == A.ABI_VERSION          # additive: the version stays
+    defs = H.defines()
+    assert defs["TRPL_MCMC_MAX_PAIRS"] == 4 == A.MCMC_MAX_PAIRS and defs["TRPL_MCMC_MAX_CR"] == 8 == A.MCMC_MAX_CR
+    assert defs["TRPL_ABI_VERSION"] == 5 == A.lib().trpl_abi_version() == A.ABI_VERSION          # additive: the version stays
     for j in ("12 .. 19", "20 .. 27", "j = 28 ", "j = 28 + p"):  # every Philox index of the move is written into the header
         assert j in hdr, j
     common = open(os.path.join(ROOT, "bayesian-inference-trpl_amd", "csrc", "mcmc_common.hpp")).read()
@@ -47,12 +46,9 @@ def test_header_binding_and_library_agree(trpl):
 
 
 def test_the_library_holds_the_kernel_and_its_unit_is_uncontracted(trpl):
-    A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
     for name in NEW:
-        assert re.search(r"\bT %s\b" % name, nm), name
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
-    have = set(re.findall(r"trpl::mcmc::__device_stub__subspace_kernel<(\d+), (true|false)>", filt))
+        assert re.search(r"\bT %s\b" % name, H.exports()), name
+    have = set(re.findall(r"trpl::mcmc::__device_stub__subspace_kernel<(\d+), (true|false)>", H.demangled()))
     assert have == {(str(n), f) for n in range(1, 17) for f in ("true", "false")}, sorted(have)
     mk = open(os.path.join(ROOT, "bayesian-inference-trpl_amd", "Makefile")).read()
     rule = re.search(r"\$\(OBJ\)/mcmc_subspace\.o:([^\n]*)\n\t([^\n]*)", mk)

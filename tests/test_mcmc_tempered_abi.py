@@ -1,36 +1,32 @@
 """trpl_mcmc_propose_rungs*, trpl_mcmc_accept_rungs*, trpl_mcmc_levels_rungs*, trpl_mcmc_swap* (include/trpl.h, parallel tempering):
 header, binding and library agree; the kernels are in the library for every A; every refusal the header states is TRPL_ERR_ARG with
 a message naming the argument, decided with no device present; the Python refusals of run_tempered.  No GPU needed."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_header as H
+
 NEW = ("trpl_mcmc_propose_rungs", "trpl_mcmc_propose_rungs_dev", "trpl_mcmc_accept_rungs", "trpl_mcmc_accept_rungs_dev",
        "trpl_mcmc_levels_rungs", "trpl_mcmc_levels_rungs_dev", "trpl_mcmc_swap", "trpl_mcmc_swap_dev")
 
 
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name in NEW:
-        proto = re.search(r"\bint %s\s*\(([^;]*)\);" % name, code)
-        assert proto, name
+        assert H.returns(name) == "int", name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        assert len(proto.group(1).split(",")) == len(A.SIGNATURES[name]), name
+        assert len(H.params(name)) == len(A.SIGNATURES[name]), name
     # group beside trpl_mcmc_propose's arguments; K, group and the ladder where the scalar tf was
     for form in ("", "_dev"):
         assert len(A.SIGNATURES["trpl_mcmc_propose_rungs" + form]) == len(A.SIGNATURES["trpl_mcmc_propose" + form]) + 1
         assert len(A.SIGNATURES["trpl_mcmc_accept_rungs" + form]) == len(A.SIGNATURES["trpl_mcmc_accept" + form]) + 2
         assert len(A.SIGNATURES["trpl_mcmc_levels_rungs" + form]) == len(A.SIGNATURES["trpl_mcmc_levels" + form]) + 2
     assert len(A.SIGNATURES["trpl_mcmc_swap"]) == 15 and len(A.SIGNATURES["trpl_mcmc_swap_dev"]) == 14
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_MCMC_MAX_RUNGS"]) == A.MCMC_MAX_RUNGS == 64
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.lib().trpl_abi_version() == A.ABI_VERSION          # additive: the version stays
+    defs = H.defines()
+    assert defs["TRPL_MCMC_MAX_RUNGS"] == A.MCMC_MAX_RUNGS == 64
+    assert defs["TRPL_ABI_VERSION"] == 5 == A.lib().trpl_abi_version() == A.ABI_VERSION          # additive: the version stays
     for fn in ("propose_rungs", "accept_rungs", "reject_levels_rungs", "swap", "geometric_ladder", "run_tempered", "Tempered"):
         assert callable(getattr(trpl.mcmc, fn)), fn
     for fn in ("mcmc_propose_rungs_device", "mcmc_accept_rungs_device", "mcmc_levels_rungs_device", "mcmc_swap_device"):
@@ -38,11 +34,9 @@ def test_header_binding_and_library_agree(trpl):
 
 
 def test_the_library_exports_the_symbols_and_holds_the_kernels(trpl):
-    A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
     for name in NEW:
-        assert re.search(r"\bT %s\b" % name, nm), name
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
+        assert re.search(r"\bT %s\b" % name, H.exports()), name
+    filt = H.demangled()
     for kernel in ("propose_rungs_kernel", "propose_rungs_fold_kernel", "accept_rungs_kernel", "swap_kernel"):
         have = {int(n) for n in re.findall(r"trpl::mcmc::__device_stub__%s<(\d+)>" % kernel, filt)}
         assert have == set(range(1, 17)), (kernel, sorted(have))

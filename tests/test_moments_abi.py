@@ -6,10 +6,11 @@ TRPL_ERR_ARG before a device is touched.  No GPU needed."""
 import itertools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
+
+import abi_header as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("trpl_loglik_moments", "trpl_loglik_moments_dev", "trpl_loglik_moments_from_pl_dev", "trpl_mag_grid",
@@ -19,19 +20,18 @@ NEW = ("trpl_loglik_moments", "trpl_loglik_moments_dev", "trpl_loglik_moments_fr
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
     hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name in NEW:
-        assert re.search(r"\bint %s\s*\(" % name, code), name
+        assert H.returns(name) == "int", name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        n_args = len(re.search(r"\bint %s\s*\(([^;]*)\);" % name, code).group(1).split(","))
+        n_args = len(H.params(name))
         assert n_args == len(A.SIGNATURES[name]), (name, n_args)
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_FLAG_MOMENTS"], 0) == A.FLAG_MOMENTS == 0x200000
-    assert int(defs["TRPL_MAG_PER_CURVE"], 0) == A.MAG_PER_CURVE
-    assert int(defs["TRPL_MAG_MAX_CURVES"], 0) == A.MAG_MAX_CURVES
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.lib().trpl_abi_version()          # additive: the version stays
+    defs = H.defines()
+    assert defs["TRPL_FLAG_MOMENTS"] == A.FLAG_MOMENTS == 0x200000
+    assert defs["TRPL_MAG_PER_CURVE"] == A.MAG_PER_CURVE
+    assert defs["TRPL_MAG_MAX_CURVES"] == A.MAG_MAX_CURVES
+    assert defs["TRPL_ABI_VERSION"] == 5 == A.lib().trpl_abi_version()          # additive: the version stays
     # one free bit: no other flag of the solver entry points, nor the bundle / BDF-order fields, holds it
-    others = [int(v, 0) for k, v in defs.items() if k.startswith("TRPL_FLAG_") and k != "TRPL_FLAG_MOMENTS"]
+    others = [v for k, v in defs.items() if k.startswith("TRPL_FLAG_") and k != "TRPL_FLAG_MOMENTS"]
     assert A.FLAG_MOMENTS & (A.FLAG_MOMENTS - 1) == 0
     assert not any(A.FLAG_MOMENTS & o for o in others) and not A.FLAG_MOMENTS & (0xF00 | (7 << 14))
     assert "probs.py:5-18" in hdr and "trpl_loglik_multi* has no moments form" in hdr
@@ -39,9 +39,7 @@ def test_header_binding_and_library_agree(trpl):
 
 def test_every_moments_kernel_name_exists_in_the_library(trpl):
     A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
-    have = set(re.findall(r"(trpl::moments::(?:predict::)?(?:pair::)?stepper(?:_pair)?_kernel<[^>]*>)", filt))
+    have = set(re.findall(r"(trpl::moments::(?:predict::)?(?:pair::)?stepper(?:_pair)?_kernel<[^>]*>)", H.demangled()))
     # one-system FAST and STRICT at the 8 grids, the paired kernel in both seam forms; each with and without PREDICT
     assert len(have) == 2 * (8 * 2 + 2), sorted(have)
     named = set()

@@ -10,6 +10,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_header as H
 import nuisance_ref as N
 from conftest import ROOT
 from irf_ref import same_bits
@@ -213,15 +214,13 @@ NEW = ("trpl_nuisance_max_offsets", "trpl_nuisance_bound", "trpl_nuisance_reduce
 
 
 def test_header_binding_and_library_agree(trpl):
-    text = open(os.path.join(ROOT, "include", "trpl.h")).read()
+    text = open(os.path.join(ROOT, "include", "trpl.h")).read()          # with its comments: the sentences below
     A = trpl._abi
     lib = A.lib()
     for name in NEW:
         assert name in A.SIGNATURES and hasattr(lib, name), name
-        proto = re.search(r"\b%s\(([^;]*)\);" % name, text)
-        args = re.sub(r"/\*.*?\*/", "", proto.group(1), flags=re.S).strip()
-        assert (0 if args == "void" else len(args.split(","))) == len(A.SIGNATURES[name]), name
-    define = lambda name: int(re.search(r"#define %s (\w+)" % name, text).group(1).rstrip("u"), 0)
+        assert len(H.params(name)) == len(A.SIGNATURES[name]), name
+    define = H.defines().__getitem__
     assert define("TRPL_NUISANCE_MAX_OFFSETS") == A.NUISANCE_MAX_OFFSETS == lib.trpl_nuisance_max_offsets() == 64
     assert [define("TRPL_NUISANCE_" + n) for n in ("MAG_FIXED", "MAG_GRID", "MAG_PROFILE", "MARGINAL")] \
         == [A.NUISANCE_MAG_FIXED, A.NUISANCE_MAG_GRID, A.NUISANCE_MAG_PROFILE, A.NUISANCE_MARGINAL]

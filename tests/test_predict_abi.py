@@ -1,30 +1,21 @@
 """TRPL_FLAG_PREDICT (include/trpl.h) without a device: the flag's value and bit, the kernel names a predict launch runs
 and that the library contains them, the default names untouched, the refusals, and the Python layer's own refusal."""
 import itertools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
-
-def header_flags():
-    text = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    return {m.group(1): int(m.group(2), 16) for m in re.finditer(r"#define (TRPL_FLAG_[A-Z0-9_]+) (0x[0-9A-Fa-f]+)", text)}
+import abi_header as H
 
 
 def library_kernels(A):
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
-    return set(re.findall(r"(trpl::(?:predict::)?(?:pair::|f32::)?stepper(?:_pair)?_kernel<[^>]*>)", filt))
+    return set(re.findall(r"(trpl::(?:predict::)?(?:pair::|f32::)?stepper(?:_pair)?_kernel<[^>]*>)", H.demangled()))
 
 
 def test_flag_value_is_one_free_bit(trpl):
     A = trpl._abi
-    flags = header_flags()
+    flags = {k: v for k, v in H.defines().items() if k.startswith("TRPL_FLAG_")}
     assert flags["TRPL_FLAG_PREDICT"] == A.FLAG_PREDICT == 0x100000
     p = A.FLAG_PREDICT
     assert p & (p - 1) == 0                                                  # a single bit

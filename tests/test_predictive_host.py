@@ -1,14 +1,11 @@
 """The posterior-predictive band without a device: the reference and its allowances (tests/predictive_ref.py) are ones fp64
 itself can meet on every input family the -m gpu tests use; predictive.merge (plain NumPy) combines finished bands; header,
 binding and library agree on the seven entry points; the argument checks need no device."""
-import os
-import re
-
 import numpy as np
 import pytest
 
+import abi_header as H
 import predictive_ref as pr
-from conftest import ROOT
 
 SYMBOLS = ("trpl_predictive_state_bytes", "trpl_predictive_workspace_bytes", "trpl_predictive_chunks", "trpl_predictive_init_dev",
            "trpl_predictive_accumulate_dev", "trpl_predictive_finish_dev", "trpl_predictive")
@@ -92,15 +89,13 @@ def test_merge_with_an_empty_side_is_the_identity(trpl):
 
 
 def test_header_binding_and_library_agree_on_the_seven_symbols(trpl):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "trpl.h")).read(), flags=re.S)
     lib = trpl._abi.lib()
     for name in SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert H.returns(name), name
         assert name in trpl._abi.SIGNATURES and hasattr(lib, name), name
     # the argument counts of the binding are the header's
     for name in SYMBOLS:
-        args = re.search(r"\b%s\s*\(([^;]*)\)\s*;" % name, text).group(1)
-        assert len(args.split(",")) == len(trpl._abi.SIGNATURES[name]), name
+        assert len(H.params(name)) == len(trpl._abi.SIGNATURES[name]), name
     assert trpl.posterior_predictive is trpl.predictive.posterior_predictive
 
 

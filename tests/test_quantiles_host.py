@@ -1,14 +1,11 @@
 """The weighted quantiles without a device: the extended-precision reference (tests/quantiles_ref.py) is the reference's
 credible_interval on tie-free inputs, every input family of the -m gpu tests stays within the ambiguity cap, header, binding
 and library agree, and every refusal comes before a device is touched."""
-import os
-import re
-
 import numpy as np
 import pytest
 
+import abi_header as H
 import quantiles_ref as qr
-from conftest import ROOT
 
 SYMBOLS = ("trpl_quantiles_stage_rows", "trpl_weighted_quantiles_dev", "trpl_weighted_quantiles", "trpl_predictive_gather_dev")
 
@@ -90,19 +87,15 @@ def test_every_input_family_of_the_gpu_tests_meets_the_ambiguity_cap(trpl):
 
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    defs = dict(re.findall(r"^#define (TRPL_Q_[A-Z_]+) +(\S+)", hdr, flags=re.M))
     want = {"TRPL_Q_MAX": A.Q_MAX, "TRPL_Q_BLOCK": A.Q_BLOCK, "TRPL_Q_FIRST_ABOVE": A.Q_FIRST_ABOVE, "TRPL_Q_LAST_BELOW": A.Q_LAST_BELOW,
             "TRPL_Q_FORCE_STREAM": A.Q_FORCE_STREAM}
-    assert {k: int(v, 0) for k, v in defs.items()} == want
+    assert {k: v for k, v in H.defines().items() if k.startswith("TRPL_Q_")} == want
     assert (qr.FIRST_ABOVE, qr.LAST_BELOW) == (A.Q_FIRST_ABOVE, A.Q_LAST_BELOW) and max(qr.REQUESTS) == A.Q_MAX
     assert A.Q_BLOCK % 64 == 0 and A.Q_FIRST_ABOVE != A.Q_LAST_BELOW and 0 not in (A.Q_FIRST_ABOVE, A.Q_LAST_BELOW)
-    text = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     lib = A.lib()
     for name in SYMBOLS:
-        args = re.search(r"\b%s\s*\(([^;]*)\)\s*;" % name, text).group(1).strip()
         assert name in A.SIGNATURES and hasattr(lib, name), name
-        assert (0 if args == "void" else len(args.split(","))) == len(A.SIGNATURES[name]), name
+        assert len(H.params(name)) == len(A.SIGNATURES[name]), name
     assert A.ABI_VERSION == 5 == lib.trpl_abi_version()                    # new symbols only
     # two workgroups of staged rows (a 64-bit key image and a weight each) fit the 160 KiB of LDS of a compute unit
     stage = lib.trpl_quantiles_stage_rows()

@@ -2,9 +2,10 @@
 message naming the argument, decided with no device present.  No GPU needed."""
 import os
 import re
-import subprocess
 
 import numpy as np
+
+import abi_header as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("trpl_refine_chunk_rows", "trpl_refine_tile_parents", "trpl_refine_workspace_bytes", "trpl_refine_resample",
@@ -14,18 +15,15 @@ NEW = ("trpl_refine_chunk_rows", "trpl_refine_tile_parents", "trpl_refine_worksp
 
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name in NEW:
-        proto = re.search(r"\b(?:int|int64_t) %s\s*\(([^;]*)\);" % name, code)
-        assert proto, name
+        assert H.returns(name) in ("int", "int64_t"), name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        args = [a for a in proto.group(1).split(",") if a.strip() != "void"]
+        args = [a for a in H.params(name) if a.strip() != "void"]
         assert len(args) == len(A.SIGNATURES[name]), name
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_REFINE_MAX_DIMS"]) == A.REFINE_MAX_DIMS == 16
-    assert int(defs["TRPL_REFINE_MAX_PARENTS"]) == A.REFINE_MAX_PARENTS
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.lib().trpl_abi_version()          # additive: the version stays
+    defs = H.defines()
+    assert defs["TRPL_REFINE_MAX_DIMS"] == A.REFINE_MAX_DIMS == 16
+    assert defs["TRPL_REFINE_MAX_PARENTS"] == A.REFINE_MAX_PARENTS
+    assert defs["TRPL_ABI_VERSION"] == 5 == A.lib().trpl_abi_version()          # additive: the version stays
     for name in NEW[:3]:
         assert getattr(A.lib(), name).restype.__name__ == "c_long", name
     for fn in ("resample", "unit_coords", "bandwidth", "make_proposal", "draw", "density", "log_ratio", "run", "Population", "Proposal"):
@@ -35,12 +33,9 @@ def test_header_binding_and_library_agree(trpl):
 
 
 def test_the_library_exports_the_symbols_and_holds_the_kernels(trpl):
-    A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
     for name in NEW:
-        assert re.search(r"\bT %s\b" % name, nm), name
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
-    have = set(re.findall(r"trpl::refine::__device_stub__(\w+)[<(]", filt))
+        assert re.search(r"\bT %s\b" % name, H.exports()), name
+    have = set(re.findall(r"trpl::refine::__device_stub__(\w+)[<(]", H.demangled()))
     assert have == {"chunk_sums_kernel", "chunk_prefix_kernel", "resample_kernel", "draw_kernel", "unit_kernel", "density_kernel"}, sorted(have)
     mk = open(os.path.join(ROOT, "bayesian-inference-trpl_amd", "Makefile")).read()
     rule = re.search(r"\$\(OBJ\)/refine\.o:[^\n]*\n\t([^\n]*)", mk)

@@ -4,9 +4,10 @@ named, with no device present; the shared object holds the scan's kernels; the c
 are defined once.  No GPU needed."""
 import os
 import re
-import subprocess
 
 import numpy as np
+
+import abi_header as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bayesian-inference-trpl_amd", "csrc")
@@ -15,16 +16,13 @@ NEW = ("trpl_posterior_tf_scan", "trpl_posterior_tf_scan_dev", "trpl_posterior_t
 
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name in NEW:
-        proto = re.search(r"\b(?:int|int64_t) %s\s*\(([^;]*)\);" % name, code)
-        assert proto, name
+        assert H.returns(name) in ("int", "int64_t"), name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        assert len(proto.group(1).split(",")) == len(A.SIGNATURES[name]), name
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_TF_SCAN_MAX"]) == A.TF_SCAN_MAX == 64 == trpl.posterior.TF_SCAN_POINTS
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.lib().trpl_abi_version()          # additive: the version stays
+        assert len(H.params(name)) == len(A.SIGNATURES[name]), name
+    defs = H.defines()
+    assert defs["TRPL_TF_SCAN_MAX"] == A.TF_SCAN_MAX == 64 == trpl.posterior.TF_SCAN_POINTS
+    assert defs["TRPL_ABI_VERSION"] == 5 == A.lib().trpl_abi_version()          # additive: the version stays
     assert A.lib().trpl_posterior_tf_scan_workspace.restype.__name__ == "c_long"      # bytes, not an int
     for fn in ("tf_scan", "find_best_tf", "calc_max_uncertainty", "_bracket_search"):
         assert callable(getattr(trpl.posterior, fn)), fn
@@ -120,12 +118,11 @@ def test_the_shared_pieces_are_defined_once():
     assert "$(OBJ)/posterior_scan.o $(OBJ)/sampler.o" in mk
 
 
-def kernels_of(lib_path, namespace):
+def kernels_of(namespace):
     """{kernel name with its template arguments} of a namespace in the library: a kernel is what has a launch stub"""
-    nm = subprocess.run(["nm", "-D", "--defined-only", lib_path], capture_output=True, text=True).stdout
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
+    filt = H.demangled()
     assert "trpl::post::lr::" not in filt
-    return set(re.findall(r"\b%s::__device_stub__(\w+(?:<[^()]*>)?)\(" % re.escape(namespace), filt)), nm
+    return set(re.findall(r"\b%s::__device_stub__(\w+(?:<[^()]*>)?)\(" % re.escape(namespace), filt)), H.exports()
 
 
 SCAN_KERNELS = ({"max_count_partial", "tiled_max_count_partial"} |
@@ -139,13 +136,11 @@ WEIGHTS_KERNELS = {"scale_kernel"} | {"%s<trpl::post::%s>" % (k, src) for src in
 def test_the_scan_kernels_are_in_the_shared_object(trpl):
     """The exact set of instantiations: the tiled three and the finish kernel once per source, the two max kernels (untiled
     for Plain, tiled for Ratio), and the single-temperature weights kernels of posterior.hip."""
-    A = trpl._abi
-    have, nm = kernels_of(A.LIB_PATH, "trpl::post::scan")
+    have, nm = kernels_of("trpl::post::scan")
     assert have == SCAN_KERNELS, sorted(have)
-    have, _ = kernels_of(A.LIB_PATH, "trpl::post")
+    have, _ = kernels_of("trpl::post")
     assert {k for k in have if re.match(r"(nanmax_partial|weights_partial|scale_kernel|copy2_kernel|one_)", k)} == WEIGHTS_KERNELS, sorted(have)
-    stubs = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
-    for line in stubs.splitlines():                       # the source is the kernels' first argument, by value
+    for line in H.demangled().splitlines():                       # the source is the kernels' first argument, by value
         m = re.search(r"__device_stub__\w+<trpl::post::(Plain|Ratio)>\((.*)\)$", line)
         if m and "finish_kernel" not in line:
             assert m.group(2).startswith("trpl::post::" + m.group(1)), line

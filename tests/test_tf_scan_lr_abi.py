@@ -4,9 +4,10 @@ refusal the header states is TRPL_ERR_ARG with its argument named, with no devic
 the Makefile compiles the shared unit without contraction; the exports are only added (ABI 5).  No GPU needed."""
 import os
 import re
-import subprocess
 
 import numpy as np
+
+import abi_header as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "bayesian-inference-trpl_amd")
@@ -16,17 +17,14 @@ NEW = ("trpl_posterior_weights_lr", "trpl_posterior_weights_lr_dev", "trpl_poste
 
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
-    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()          # with its comments: the sentences below
     for name in NEW:
-        proto = re.search(r"\b(?:int|int64_t) %s\s*\(([^;]*)\);" % name, code)
-        assert proto, name
+        assert H.returns(name) in ("int", "int64_t"), name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        assert len(proto.group(1).split(",")) == len(A.SIGNATURES[name]), name
+        assert len(H.params(name)) == len(A.SIGNATURES[name]), name
         # the ratio follows LL in every call that takes samples
-        assert name.endswith("workspace") or [a.split()[-1].lstrip("*") for a in proto.group(1).split(",")][:2] == ["LL", "lnr"], name
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.ABI_VERSION == A.lib().trpl_abi_version()      # additive: the version stays
+        assert name.endswith("workspace") or [a.split()[-1].lstrip("*") for a in H.params(name)][:2] == ["LL", "lnr"], name
+    assert H.defines()["TRPL_ABI_VERSION"] == 5 == A.ABI_VERSION == A.lib().trpl_abi_version()      # additive: the version stays
     assert A.lib().trpl_posterior_tf_scan_lr_workspace.restype.__name__ == "c_long"               # bytes, not an int
     for name in NEW:
         if not name.endswith("workspace"):
@@ -147,13 +145,12 @@ def test_the_unit_is_compiled_without_contraction_and_shares_the_reductions():
 
 def test_the_kernels_are_in_the_shared_object(trpl):
     from test_tf_scan_abi import SCAN_KERNELS, WEIGHTS_KERNELS, kernels_of
-    A = trpl._abi
-    have, nm = kernels_of(A.LIB_PATH, "trpl::post::scan")           # also asserts that no trpl::post::lr:: symbol remains
+    have, nm = kernels_of("trpl::post::scan")           # also asserts that no trpl::post::lr:: symbol remains
     assert have == SCAN_KERNELS, sorted(have)
     assert {k for k in have if k.endswith("<trpl::post::Ratio>")} == {
         "weights_partial<trpl::post::Ratio>", "moments1_partial<trpl::post::Ratio>", "moments2_partial<trpl::post::Ratio>",
         "finish_kernel<trpl::post::Ratio>"}
-    have, _ = kernels_of(A.LIB_PATH, "trpl::post")
+    have, _ = kernels_of("trpl::post")
     assert WEIGHTS_KERNELS <= have, sorted(have)
     for name in NEW:
         assert re.search(r"\bT %s\b" % name, nm), name

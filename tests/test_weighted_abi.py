@@ -12,6 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_header as H
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("trpl_loglik_weighted", "trpl_loglik_weighted_dev", "trpl_loglik_weighted_from_pl_dev", "trpl_sse_accumulate_w",
        "trpl_sse_accumulate_w_dev", "trpl_mag_grid_w", "trpl_mag_grid_w_dev", "trpl_mag_profile_w", "trpl_mag_profile_w_dev")
@@ -20,12 +22,11 @@ NEW = ("trpl_loglik_weighted", "trpl_loglik_weighted_dev", "trpl_loglik_weighted
 def test_header_binding_and_library_agree(trpl):
     A = trpl._abi
     hdr = open(os.path.join(ROOT, "include", "trpl.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     assert len(NEW) == 9
     for name in NEW:
-        assert re.search(r"\bint %s\s*\(" % name, code), name
+        assert H.returns(name) == "int", name
         assert name in A.SIGNATURES and hasattr(A.lib(), name), name
-        n_args = len(re.search(r"\bint %s\s*\(([^;]*)\);" % name, code).group(1).split(","))
+        n_args = len(H.params(name))
         assert n_args == len(A.SIGNATURES[name]), (name, n_args)
     # the arguments of the moments calls plus the weights
     for name, base in (("trpl_loglik_weighted", "trpl_loglik_moments"), ("trpl_loglik_weighted_dev", "trpl_loglik_moments_dev"),
@@ -35,11 +36,11 @@ def test_header_binding_and_library_agree(trpl):
     for name in ("trpl_mag_grid", "trpl_mag_grid_dev", "trpl_mag_profile", "trpl_mag_profile_dev"):
         assert len(A.SIGNATURES[name.replace("trpl_mag_grid", "trpl_mag_grid_w").replace("trpl_mag_profile", "trpl_mag_profile_w")]) \
             == len(A.SIGNATURES[name])
-    defs = dict(re.findall(r"^#define (TRPL_[A-Z0-9_]+) +(0x[0-9a-fA-F]+|\d+)\b", hdr, flags=re.M))
-    assert int(defs["TRPL_FLAG_WEIGHTED"], 0) == A.FLAG_WEIGHTED == 0x400000
-    assert int(defs["TRPL_ABI_VERSION"]) == 5 == A.lib().trpl_abi_version()          # additive: the version stays
+    defs = H.defines()
+    assert defs["TRPL_FLAG_WEIGHTED"] == A.FLAG_WEIGHTED == 0x400000
+    assert defs["TRPL_ABI_VERSION"] == 5 == A.lib().trpl_abi_version()          # additive: the version stays
     # one free bit: no other flag of the solver entry points, nor the bundle / BDF-order fields, holds it
-    others = [int(v, 0) for k, v in defs.items() if k.startswith("TRPL_FLAG_") and k != "TRPL_FLAG_WEIGHTED"]
+    others = [v for k, v in defs.items() if k.startswith("TRPL_FLAG_") and k != "TRPL_FLAG_WEIGHTED"]
     assert A.FLAG_WEIGHTED & (A.FLAG_WEIGHTED - 1) == 0
     assert not any(A.FLAG_WEIGHTED & o for o in others) and not A.FLAG_WEIGHTED & (0xF00 | (7 << 14))
     assert "probs.py:20-62" in hdr and "probs.py:40" in hdr and "bayes_io.py:75-76" in hdr
@@ -48,8 +49,7 @@ def test_header_binding_and_library_agree(trpl):
 
 def test_every_weighted_kernel_name_exists_in_the_library(trpl):
     A = trpl._abi
-    nm = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True, text=True).stdout
-    filt = subprocess.run(["c++filt"], input=nm, capture_output=True, text=True).stdout
+    filt = H.demangled()
     have = set(re.findall(r"(trpl::weighted::(?:predict::)?(?:pair::)?stepper(?:_pair)?_kernel<[^>]*>)", filt))
     # one-system FAST and STRICT at the 8 grids, the paired kernel in both seam forms; each with and without PREDICT
     assert len(have) == 36, sorted(have)
