@@ -395,11 +395,19 @@ int select_device(int32_t device)
     return TRPL_OK;
 }
 
+std::atomic<int64_t> g_pair_launch_info[3];
+
 }  // namespace trpl
 
 using namespace trpl;
 
 namespace {
+
+#if TRPL_SLOT_TIMELINE
+// measurement build only: where the paired kernel's waves record their blocks, and whether its launch stays one block per wave
+uint64_t *g_slot_timeline = nullptr;
+int32_t g_slot_timeline_classic = 0;
+#endif
 
 // steps: how many time steps the launch will take (T, or up to the last observation in likelihood mode)
 int launch(const trpl::StepArgs &a_in, uint32_t flags, hipStream_t st, int64_t steps)
@@ -409,6 +417,9 @@ int launch(const trpl::StepArgs &a_in, uint32_t flags, hipStream_t st, int64_t s
     trpl::StepArgs a = a_in;
     a.bundle = c.bundle;
     if (c.family == StepperChoice::Pair) build_pair_table(a);
+#if TRPL_SLOT_TIMELINE
+    a.timeline = g_slot_timeline; a.timeline_classic = g_slot_timeline_classic;
+#endif
     static const char *const kWord[trpl::Variant::kUnits] = {"", "", "pair ", "fp32 ", "mixed ", "hist32 "};   // what the error message starts with
     StepperLauncher *const fn = find_launcher(c);
     if (!fn) return api_fail(TRPL_ERR_UNSUPPORTED, "no stepper is built for this combination of flags (flags 0x%x, L = %d)", flags, a.L);
@@ -431,6 +442,19 @@ int trpl_has_experimental(void)
 #endif
 }
 const char *trpl_last_error(void) { return g_err; }
+
+// Tests and tools (not in include/trpl.h): out[0] paired-stepper launches of this process with persistent waves on a ticket, out[1]
+// those of one block per wave, out[2] the resident waves R the last persistent-capable launch compared its blocks with
+void trpl_pair_launch_info(int64_t *out)
+{
+    for (int i = 0; i < 3; i++) out[i] = trpl::g_pair_launch_info[i].load(std::memory_order_relaxed);
+}
+
+#if TRPL_SLOT_TIMELINE
+// measurement build only (tools/slot_timeline.py; not in include/trpl.h): every later paired-stepper launch records into
+// buf, a device buffer of 4 x 8 bytes per block of the launch (NULL: none); classic != 0 keeps one block per wave
+void trpl_debug_slot_timeline(void *buf, int32_t classic) { g_slot_timeline = (uint64_t *)buf; g_slot_timeline_classic = classic; }
+#endif
 
 int trpl_kernel_variant(int64_t nsys, int32_t L, int64_t steps, uint32_t flags)
 {

@@ -3,6 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
+#ifndef TRPL_SLOT_TIMELINE
+#define TRPL_SLOT_TIMELINE 0      // measurement build only (tools/slot_timeline.py): lane 0 of every paired-kernel wave records, per block
+                                  // it processes, the block, the 100 MHz clock at its start and end and the hardware id words
+#endif
+
 namespace trpl {
 
 constexpr int kMaxCurves = 16;
@@ -74,7 +81,21 @@ struct StepArgs {
     double sse_cut;         // TRPL_FLAG_CUT kernels only: a system stops once its running sse is above this (>= 0 or +inf)
     int32_t *cut_col;       // [C][S] out (TRPL_FLAG_CUT kernels only) or nullptr: leading observations in a cut system's sse; -1 uncut; -2 flagged
     const double *cut_level; // [C][S], indexed like cut_col (TRPL_FLAG_CUT kernels only), or nullptr: system (c, s) stops above cut_level[c][s] instead of sse_cut
+    // stepper_pair only, set by its launcher: the slot of the launch's block ticket (persistent waves: grid < blocks), or
+    // -1: one block per wave, grid = blocks (stepper_pair_impl.hpp)
+    int32_t ticket_slot;
+#if TRPL_SLOT_TIMELINE
+    // measurement build only (tools/slot_timeline.py): [blocks][4] records {block, start, end, hardware id} of the paired
+    // kernel, or nullptr; timeline_classic != 0 keeps the launch at one block per wave
+    uint64_t *timeline;
+    int32_t timeline_classic;
+#endif
 };
+
+// What the paired stepper's launches of this process took (stepper_pair_impl.hpp; trpl_pair_launch_info, trpl_api.hip):
+// [0] launches with persistent waves on a ticket, [1] launches of one block per wave, [2] the resident waves the last
+// persistent-capable launch was measured against (compute units x occupancy).  Relaxed counters, for tests and tools.
+extern std::atomic<int64_t> g_pair_launch_info[3];
 
 // BDF coefficient table of tEvol (pvSimPCR.py:241-250): time step t takes the row min(t, 4) -- order 1 (Euler) at t = 0,
 // ramping to order 5 from t = 4 on.  TRPL_FLAG_BDF_ORDER(k) (bits 14-16 of the flags, k = 1 .. 5; 0 = the reference's ramp)
